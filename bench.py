@@ -1,6 +1,6 @@
 """Headline benchmark: sampled fields/sec of the DYffusion h-step rollout (BASELINE.json metric).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--nb NB] [--ensemble-total M]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--nb NB] [--ensemble-total M] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 One "step" = one `DYffusion.sample` call = one full h=16 rollout (16 forecaster + 44 interpolator forwards,
@@ -8,11 +8,17 @@ cold sampling, refine pass, MC dropout ON in the interpolator) over NB ensemble 
 libdyffusion_hip.so as a captured hipGraph.  Workload = BASELINE.json configs[1]: Navier-Stokes 221x42, C=3 (+2
 static channels), unet_simple dim 64 @256^2, bf16 MFMA / fp32 accumulate.
 
-Beside the headline line (N = 1) the JSON carries: `batch_curve` + `strong_scaling_projection` (what sharding a FIXED ensemble over 8
-GPUs would give, from this GPU's own small-batch rates), `config1_ns_c2` (the 2-channel NS variant), `config3_ns_ar64` (BASELINE
-configs[3]), `config2_oisst` (+ its batch curve), `config4_synth512`, `train_step` (both backbones) and `cpu_baseline`.
-For N > 1: the NS line (weak by default) + a `strong` object (50- and 80-row ensembles split over the ranks) + `config2_oisst` /
-`config4_synth512` on 300 / 8 rows sharded N ways, every one through the engine-owned all-gather, with `nranks_seen` = ncclCommCount.
+A plain run does only what the headline figure needs: set up, W warm-up steps, K timed steps, the outputs of the last timed step
+(`--dump-outputs DIR`: DIR/t<i>_preds.npy, float32, a seeded sample of at most DUMP_BYTES of the rows), the JSON line.  The inputs,
+weights and dropout seed are fixed, so two builds run with the same arguments can be compared output for output.
+
+Everything else is measured only with `--full`.  Beside the headline line (N = 1) the JSON then carries: `roofline` /
+`roofline_dec5_sparse` / `hbm_kernels` (per-kernel timings of eager rollouts), `batch_curve` + `strong_scaling_projection` (what
+sharding a FIXED ensemble over 8 GPUs would give, from this GPU's own small-batch rates), `config1_ns_c2` (the 2-channel NS variant),
+`config3_ns_ar64` (BASELINE configs[3]), `config2_oisst` (+ its batch curve), `config4_synth512`, `train_step` (both backbones) and
+`cpu_baseline`.  For N > 1: the NS line (weak by default) + the exchange's own cost, `rank0_alone`, a `strong` object (50- and 80-row
+ensembles split over the ranks) + `config2_oisst` / `config4_synth512` on 300 / 8 rows sharded N ways, every one through the
+engine-owned all-gather, with `nranks_seen` = ncclCommCount.
 
 N > 1 (one process per GPU, RCCL): rows are independent ensemble members, so the rollout itself has no exchange step;
 every rank keeps the SAME seed and samples its block of global rows (the dropout streams are keyed by the global row, so
@@ -175,6 +181,27 @@ def _time_rollouts(model, x0, reps, static=None):
     dt = (time.perf_counter() - t0) / reps
     assert all(bool(torch.isfinite(v).all()) for v in out.values()), "non-finite forecast"
     return dt
+
+
+DUMP_BYTES = 64_000_000  # --dump-outputs: the most the written arrays may hold in all
+
+
+def dump_outputs(preds, out_dir):
+    """--dump-outputs: the forecast dict of the last timed step ({"t<i>_preds": (rows, C, H, W)}, what `DYffusion.sample` returns) as
+    out_dir/t<i>_preds.npy in float32.  When all rows would not fit into DUMP_BYTES, a fixed sample of rows (seed 0, sorted, the same
+    rows in every file) is written instead: the same arguments give the same rows."""
+    import numpy as np
+
+    rows = next(iter(preds.values())).shape[0]
+    row_bytes = sum(4 * v[0].numel() for v in preds.values())
+    keep = min(rows, (DUMP_BYTES - 128 * len(preds)) // row_bytes)  # (128: the header of one .npy file)
+    sel = np.arange(rows) if keep == rows else np.sort(np.random.default_rng(0).choice(rows, keep, replace=False))
+    idx = torch.from_numpy(sel).to(next(iter(preds.values())).device)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in preds.items():
+        np.save(os.path.join(out_dir, name + ".npy"), v.index_select(0, idx).float().cpu().numpy())
+    log(f"outputs of the last timed step: {len(preds)} arrays of {keep} of {rows} rows -> {out_dir}"
+        + ("" if keep == rows else f" (rows {sel.tolist()})"))
 
 
 def projection(curve, total, parts=8):
@@ -547,11 +574,12 @@ def cpu_baseline(F, I):
 
 
 def self_launch(n):
-    """Replace this process by `python -m torch.distributed.run --nnodes=1 --nproc-per-node n --master-addr 127.0.0.1 --master-port P
-    bench.py <the same arguments>` (P: a free port picked here).  When the host shows fewer GPUs than ranks (the one-GPU rehearsal of
-    the N > 1 branch: ranks wrap onto the devices there are) RCCL cannot build the communicator ("Duplicate GPU detected"), so
-    torch.distributed is pointed at gloo unless the caller chose a backend."""
+    """Run `python -m torch.distributed.run --nnodes=1 --nproc-per-node n --master-addr 127.0.0.1 --master-port P bench.py <the same
+    arguments>` (P: a free port picked here) as a child process on this process's stdout / stderr and exit with its status.  When the
+    host shows fewer GPUs than ranks (the one-GPU rehearsal of the N > 1 branch: ranks wrap onto the devices there are) RCCL cannot build
+    the communicator ("Duplicate GPU detected"), so torch.distributed is pointed at gloo unless the caller chose a backend."""
     import socket
+    import subprocess
 
     with socket.socket() as sock:
         sock.bind(("127.0.0.1", 0))
@@ -567,7 +595,7 @@ def self_launch(n):
     log("self-launch: " + " ".join(cmd))
     sys.stdout.flush()
     sys.stderr.flush()
-    os.execve(sys.executable, cmd, env)
+    raise SystemExit(subprocess.run(cmd, env=env).returncode)
 
 
 def claim_stdout():
@@ -590,9 +618,14 @@ def main():
                          "(experiment/navier_stokes.yaml:12-16)")
     ap.add_argument("--ensemble-total", type=int, default=int(os.environ.get("DYF_BENCH_ENSEMBLE", "0")),
                     help="strong scaling: a fixed ensemble of this many rows split over the ranks (0 = weak scaling, --nb rows per rank)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline line: rooflines and per-kernel figures, batch curves, the other configurations, "
+                         "training steps, the CPU baseline (N = 1); the exchange's cost, rank 0 alone, strong scaling (N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the forecast fields of the last timed step as DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline")
     ap.add_argument("--no-extra-configs", action="store_true",
-                    help="only the headline NS line (+ rooflines): no batch curve, no other configs, no training steps")
+                    help="with --full: only the headline NS line (+ rooflines): no batch curve, no other configs, no training steps")
     ap.add_argument("--no-graph", action="store_true")
     args = ap.parse_args()
 
@@ -602,7 +635,7 @@ def main():
     if world != args.gpus:
         if "WORLD_SIZE" in os.environ or args.gpus < 1:
             raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}: the launcher's rank count and --gpus disagree")
-        # plain `python bench.py --gpus N` (no launcher): re-execute this file under torch.distributed.run, one rank per GPU --
+        # plain `python bench.py --gpus N` (no launcher): run this file again under torch.distributed.run, one rank per GPU --
         # the same command line the driver uses for N > 1; rank 0 of the child prints the ONE JSON line on the inherited stdout
         return self_launch(args.gpus)
     json_out = claim_stdout()
@@ -641,7 +674,8 @@ def main():
     def sharded_run(mdl, x_full, s_full, hw, horizon, steps, warmup, gather=gather):
         """K timed steps of `mdl` on the rows of x_full sharded over the ranks: every rank samples its block of global rows (same seed,
         global-row dropout streams) and, N > 1, the forecast stack is all-gathered inside EVERY step (one collective, issued by the
-        engine on the rollout's stream when it owns a communicator).  Returns (seconds MAX over ranks, exchange used, ncclCommCount)."""
+        engine on the rollout's stream when it owns a communicator).  Returns (seconds MAX over ranks, exchange used, ncclCommCount,
+        the forecast dict of the last timed step)."""
         rows = x_full.shape[0]
         lo, hi = shard_rows(rows, world, rank)
         exch, seen = "none", 0
@@ -677,7 +711,7 @@ def main():
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             dt = float(t.item())
         assert all(bool(torch.isfinite(v).all()) for v in preds.values()), "non-finite forecast"
-        return dt, exch, seen
+        return dt, exch, seen, preds
 
     def rank0_alone(make, x_full, s_full, steps, warmup=1):
         """The N = 1 equivalent measured INSIDE the N > 1 job, same node, same process: rank 0 samples all rows of x_full by itself
@@ -709,13 +743,13 @@ def main():
         """One fixed ensemble sharded over the ranks: fields/s with the exchange, the same steps WITHOUT the exchange (its own cost =
         the difference), and rank 0 alone on the whole ensemble -> a same-node speed-up."""
         rows = x_full.shape[0]
-        d, ex, seen = sharded_run(mdl, x_full, s_full, hw, horizon, steps, 1)
+        d, ex, seen, _ = sharded_run(mdl, x_full, s_full, hw, horizon, steps, 1)
         ent = {"total_rows": rows, "rows_per_gpu": rows_per_rank(rows, world), "scaling": "strong",
                "rows_by_rank": [b - a for a, b in (shard_rows(rows, world, r) for r in range(world))],
                "fields_per_s": round(rows * horizon * steps / d, 1), "ms_per_step": round(1e3 * d / steps, 3), "exchange": ex, "nranks_seen": seen,
                "row_groups": mdl._engine.row_groups}
         if gather:
-            d0, _, _ = sharded_run(mdl, x_full, s_full, hw, horizon, steps, 1, gather=False)
+            d0, *_ = sharded_run(mdl, x_full, s_full, hw, horizon, steps, 1, gather=False)
             ent["ms_per_step_without_exchange"] = round(1e3 * d0 / steps, 3)
             ent["exchange_ms_per_step"] = round(1e3 * (d - d0) / steps, 3)
         if alone is not None:
@@ -733,8 +767,11 @@ def main():
     model.seed(2)
     model._ensure_engine((H, W), max(nb, args.nb if world > 1 else nb))
     log("engine created, weights uploaded")
-    dt, exchange, nranks_seen = sharded_run(model, x0, static, (H, W), HORIZON, args.steps, args.warmup)
+    dt, exchange, nranks_seen, preds = sharded_run(model, x0, static, (H, W), HORIZON, args.steps, args.warmup)
     log(f"timed region done: {dt:.3f} s for {args.steps} steps")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(preds, args.dump_outputs)
+    del preds
 
     fields = total_rows * HORIZON * args.steps
     eng = model._engine
@@ -762,8 +799,9 @@ def main():
         result["nranks_seen"] = nranks_seen  # ncclCommCount of the engine's communicator (0: the torch.distributed route ran)
         result["rows_by_rank"] = [b - a for a, b in (shard_rows(total_rows, world, r) for r in range(world))]
         result["devices_visible"] = ndev
+    if world > 1 and args.full:
         if gather:  # the all-gather's own cost: the same K steps without it
-            d0, _, _ = sharded_run(model, x0, static, (H, W), HORIZON, args.steps, 1, gather=False)
+            d0, *_ = sharded_run(model, x0, static, (H, W), HORIZON, args.steps, 1, gather=False)
             result["ms_per_step_without_exchange"] = round(1e3 * d0 / args.steps, 3)
             result["exchange_ms_per_step"] = round(1e3 * (dt - d0) / args.steps, 3)
         # N = 1 equivalent inside this run: rank 0 alone on ONE rank's rows (weak scaling: the per-GPU work is what stays fixed) or on
@@ -775,7 +813,7 @@ def main():
                                  "speedup_of_this_line": round((fields / dt) / (xa.shape[0] * HORIZON * args.steps / d1), 3),
                                  "ideal": world if not strong else round(total_rows / nb, 3)}
 
-    extras = not args.no_extra_configs
+    extras = args.full and not args.no_extra_configs
     if world > 1 and extras:
         # ---- N > 1: the other multi-GPU workloads of BASELINE.json, each sharded over the ranks through the same exchange.
         # STRONG scaling of the headline workload: a fixed ensemble (the reference's 50 members; its 80-row evaluation batch) split over
@@ -817,7 +855,7 @@ def main():
                 result[key] = {"error": f"{type(ex).__name__}: {ex}"}
             torch.cuda.empty_cache()
 
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and args.full:
         # roofline of the dominant kernel: conv_halo_rows_kernel<0> (dense form; dec3 + dec4 = 27 % of a forward's time), largest launch
         # dec4.  achieved = algorithmic FLOPs of one launch / average duration of that launch INSIDE the rollout: HIP events around every
         # dec4 conv (60 launches: 16 forecaster + 44 interpolator forwards, MC dropout on) of one eagerly launched rollout on the launch

@@ -81,7 +81,7 @@ def _check_multirank_line(res, world, rows_per_gpu, strong_rows=(("ensemble_50",
 
 def test_bench_two_ranks_on_one_gpu_torch_exchange_and_consistency_with_one_rank():
     # (50 members; 200 rows = the reference's NS test ensemble, 4 x 50: 100 rows per rank here)
-    two, _ = _run_bench(2, ["--steps", "2", "--warmup", "1", "--nb", "8"], {"DYF_BENCH_STRONG_ROWS": "50,200"})
+    two, _ = _run_bench(2, ["--full", "--steps", "2", "--warmup", "1", "--nb", "8"], {"DYF_BENCH_STRONG_ROWS": "50,200"})
     _check_multirank_line(two, 2, 8, strong_rows=(("ensemble_50", 50), ("ensemble_200", 200)))
     assert two["strong"]["ensemble_200"]["rows_by_rank"] == [100, 100]
     assert "all-gather" in two["config"]["parallelism"] and "torch-owned" in two["config"]["parallelism"]
@@ -97,10 +97,12 @@ def test_bench_two_ranks_on_one_gpu_torch_exchange_and_consistency_with_one_rank
 
 def test_bench_self_launches_its_ranks_when_no_launcher_started_it():
     """`python bench.py --gpus 2 --steps 2 --warmup 1` -- the driver's N = 1 command with another N, nothing in the environment:
-    bench.py re-executes itself under torch.distributed.run (it used to SystemExit), notices that one visible GPU
-    cannot carry two RCCL ranks and points torch.distributed at gloo, and rank 0 prints the one line.  (Headline section only:
-    --no-extra-configs; the `strong` / OISST / 512^2 sections of the N > 1 line are covered by the torchrun-launched tests.)"""
-    res, err = _run_bench(2, ["--steps", "2", "--warmup", "1", "--nb", "8", "--no-extra-configs"], {}, self_launch=True, timeout=900)
+    bench.py runs itself again under torch.distributed.run in a child process (it used to SystemExit), notices
+    that one visible GPU cannot carry two RCCL ranks and points torch.distributed at gloo, and rank 0 prints the one line.  (Headline
+    section + the exchange's cost and rank 0 alone: --full --no-extra-configs; the `strong` / OISST / 512^2 sections of the N > 1
+    line are covered by the torchrun-launched tests.)"""
+    res, err = _run_bench(2, ["--full", "--steps", "2", "--warmup", "1", "--nb", "8", "--no-extra-configs"], {}, self_launch=True,
+                          timeout=900)
     assert "self-launch:" in err and "torch.distributed.run" in err
     assert res["n_gpus"] == 2 and res["scaling"] == "weak" and res["config"]["total_rows"] == 16 and res["value"] > 0
     assert res["nranks_seen"] == 0 and res["devices_visible"] >= 1 and res["rows_by_rank"] == [8, 8]
@@ -110,7 +112,7 @@ def test_bench_self_launches_its_ranks_when_no_launcher_started_it():
 
 
 def test_bench_two_ranks_engine_exchange_requested_falls_back_on_every_rank_or_runs():
-    res, err = _run_bench(2, ["--steps", "1", "--warmup", "1", "--nb", "4"], {"DYF_BENCH_EXCHANGE": "engine"})
+    res, err = _run_bench(2, ["--full", "--steps", "1", "--warmup", "1", "--nb", "4"], {"DYF_BENCH_EXCHANGE": "engine"})
     _check_multirank_line(res, 2, 4)
     exch = {res["strong"][k]["exchange"] for k in res["strong"]} | {res["config2_oisst"]["exchange"], res["config4_synth512"]["exchange"]}
     print("exchange with DYF_BENCH_EXCHANGE=engine and two ranks on one device:", exch, "nranks_seen", res["nranks_seen"])

@@ -7,7 +7,7 @@ R=$PWD
 O=$R/gpurun_out
 mkdir -p $O
 export TMPDIR=/tmp
-python bench.py --steps 20 --warmup 5 > $O/${TAG}_bench_1gpu.json 2> $O/${TAG}_bench_1gpu.err
+python bench.py --full --steps 20 --warmup 5 > $O/${TAG}_bench_1gpu.json 2> $O/${TAG}_bench_1gpu.err
 echo "bench rc $?"
 prof() {  # name, command...
   name=$1; shift
@@ -18,7 +18,7 @@ prof() {  # name, command...
   echo "profile $name: $(wc -l < $O/${TAG}_${name}_kernel_stats.txt) lines"
 }
 cd $R
-prof bench_nb80 python $R/bench.py --nb 80 --steps 10 --warmup 2 --no-extra-configs --no-cpu-baseline
+prof bench_nb80 python $R/bench.py --full --nb 80 --steps 10 --warmup 2 --no-extra-configs --no-cpu-baseline
 prof oisst_nb300_groups3 python $R/tools/bench_oisst.py 300
 prof oisst_nb38 python $R/tools/bench_oisst.py 38
 prof synth512_nb4_fp16 python $R/tools/bench_synth512.py 4 fp16 rollout
