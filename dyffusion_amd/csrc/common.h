@@ -1,6 +1,7 @@
 // Shared device/host helpers for the gfx950 DYffusion engine.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <cstdlib>
 #include <cstring>
 #include <stdint.h>
 
@@ -14,18 +15,6 @@
 #endif
 typedef uint16_t el16_t;
 
-// Timing-experiment switches that produce WRONG RESULTS (one part of a kernel's work removed to see what it costs; their findings
-// are recorded in DESIGN.md) exist only in experiment builds: tools/build_variant.sh compiles ONE translation unit with
-// -DDYF_EXPERIMENT_BUILD plus the switch into tools/variants/libvar_<name>.so.  A product build (__graft_entry__.build) that sees
-// any of them stops here, and the run-time ones (DYF_GN_FUSE_NOWAIT, DYF_EXP_DEC5_1316) are not compiled in.
-#if !defined(DYF_EXPERIMENT_BUILD) &&                                                                                               \
-    (defined(HALO_EXP_NO_DMA_WAIT) || defined(HALO_EXP_NO_STORE) || defined(HALO_EXP_W_ALIAS) || defined(HALO_EXP_W_SHARE) ||        \
-     defined(HALO_EXP_NO_HALO) || defined(HALO_EXP_NO_EPI) || defined(HALO_EXP_TIMELINE) || defined(HALO_EXP_LDS_SKIP) || defined(FA_EXP_NO_EXP) ||                \
-     defined(FA_EXP_NOSYNC) || defined(FA_EXP_NO_VT) || defined(FA4_X_NOEXP) || defined(FA4_X_MFMAONLY) || defined(FA4_X_NOQK) ||    \
-     defined(FA4_X_NOPV) || defined(FA4_X_NOSTAGE))
-#error "a wrong-results timing switch (HALO_EXP_* / FA_EXP_* / FA4_X_*) is defined in a product build: use tools/build_variant.sh"
-#endif
-
 // Kernel-form log (test seam, include/dyffusion_hip_testing.h dyf_debug_form_log*): every launcher that chooses between kernel
 // forms notes the form it took and the batch rows of the launch; off unless a test enables it (one predictable branch).
 extern bool g_dyf_form_log_on;
@@ -34,14 +23,19 @@ static inline void dyf_form_note(const char* form, long long rows) {
     if (g_dyf_form_log_on) dyf_form_note_slow(form, rows);
 }
 
-// Kernel-form switches (the A/B + parity harness): which of several equivalent kernel forms a launcher takes, thresholds of the
-// form policy, a few wrong-results timing probes.  Their values come ONLY from dyf_debug_set_form (include/dyffusion_hip_testing.h,
-// called by tests/ and tools/): the library reads NONE of them from the environment (round 5 did: a stray DYF_* variable changed
-// kernel forms, and for the training operands the numerics, under a caller who never asked).  dyf_form(key) = the value set for
-// `key`, or nullptr -- one relaxed load when nothing is set, which is every production process.  Keys keep their historic names.
+// Kernel-form switches (the A/B + parity harness): which of several equivalent kernel forms a launcher takes, and thresholds of
+// the form policy.  Their values come ONLY from dyf_debug_set_form (include/dyffusion_hip_testing.h, called by tests/ and tools/):
+// the library reads NONE of them from the environment (round 5 did: a stray DYF_* variable changed kernel forms, and for the
+// training operands the numerics, under a caller who never asked).  dyf_form(key) = the value set for `key`, or nullptr -- one
+// relaxed load when nothing is set, which is every production process.  Keys keep their historic names.
 extern int g_dyf_form_count;
 const char* dyf_form_slow(const char* key);
 static inline const char* dyf_form(const char* key) { return g_dyf_form_count ? dyf_form_slow(key) : nullptr; }
+// dyf_form_int(key, dflt) = the value set for `key` as an integer (strtoll), or dflt when nothing is set; reads the table once.
+static inline long long dyf_form_int(const char* key, long long dflt) {
+    const char* v = dyf_form(key);
+    return v ? strtoll(v, nullptr, 10) : dflt;
+}
 
 // In-rollout timing of ONE named kernel (bench.py `hbm_kernels`; include/dyffusion_hip_testing.h dyf_time_named_kernel_in_rollout):
 // the launchers of the HBM-bound kernels (norm / activation / resample / readout) open a KernelProf scope around their launch with

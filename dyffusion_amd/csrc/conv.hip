@@ -714,11 +714,11 @@ static hipError_t launch_igemm(ConvArgs a, hipStream_t stream) {
         // output pixels pays more for writing / re-reading the partials than it gains (enc1 at NB = 7: 224 tiles, 58 MB of
         // partials).  Tiny problems (<= 32 tiles) always get the layer's full factor, so small batches, their row splits and
         // the paired launches sum in the same order and stay bit-identical.
-        const bool enabled = !(dyf_form("DYF_SPLITK") && atoi(dyf_form("DYF_SPLITK")) == 0);
+        const bool enabled = dyf_form_int("DYF_SPLITK", 1) != 0;
         const int nk = a.kh * a.kw * ((a.c0 + a.c1) >> 6);
         const long long tiles = (((long long)(a.n_sel > 0 ? a.n_sel : a.n) * a.ho * a.wo + BM - 1) / BM) * tiles_n;
-        const long long max_tiles = dyf_form("DYF_SPLITK_MAX_TILES") ? atoll(dyf_form("DYF_SPLITK_MAX_TILES")) : 128;
-        const long long fill = dyf_form("DYF_SPLITK_FILL") ? atoll(dyf_form("DYF_SPLITK_FILL")) : 512;
+        const long long max_tiles = dyf_form_int("DYF_SPLITK_MAX_TILES", 128);
+        const long long fill = dyf_form_int("DYF_SPLITK_FILL", 512);
         int s = std::min(16, nk / 8);
         while (s > 1 && s * tiles > fill) s >>= 1;
         const long long need = (long long)s * M * a.cout;
@@ -753,12 +753,11 @@ hipError_t conv_init() {
 // plain 3x3 / s1 convs with 64 or 128 (a multiple of 64 that is not one of 256) output channels on planes of any size: SP = 5 of the
 // halo kernel, when the 16 x 32 tiles cover the plane reasonably (>= 60 %) and the launch has enough of them
 static bool halo5_policy(const ConvArgs& a) {
-    const bool h5_all = dyf_form("DYF_HALO5_ALL") && atoi(dyf_form("DYF_HALO5_ALL")) != 0;
-    if (!(!a.up2x && a.kh == 3 && a.kw == 3 && a.stride == 1 && a.cout % 64 == 0 && (a.cout % 256 != 0 || h5_all) && a.out_f32 == nullptr &&
+    if (!(!a.up2x && a.kh == 3 && a.kw == 3 && a.stride == 1 && a.cout % 64 == 0 && a.cout % 256 != 0 && a.out_f32 == nullptr &&
           a.residual == nullptr))
         return false;
-    if (dyf_form("DYF_HALO5") && atoi(dyf_form("DYF_HALO5")) == 0) return false;
-    const long long h5_min = dyf_form("DYF_HALO5_MIN_TILES") ? atoll(dyf_form("DYF_HALO5_MIN_TILES")) : 64;
+    if (dyf_form_int("DYF_HALO5", 1) == 0) return false;
+    const long long h5_min = dyf_form_int("DYF_HALO5_MIN_TILES", 64);
     const long long nsel = a.n_sel > 0 ? a.n_sel : a.n;
     ConvArgs b = a;
     b.wpk_up_frag = conv_lookup_halo3_frag(b.wpk);
@@ -790,11 +789,11 @@ hipError_t launch_conv_stats(const ConvArgs& a_in, int path, hipStream_t stream,
     // a fused nearest upsample exists in ONE form: refuse rather than read a low-resolution tensor as the full-size one
     if (a.up_nearest && !(path == 1 && conv_mfma_supported(a) && halo5_policy(a) && a.h % 2 == 0 && a.w % 2 == 0 && a.c1 == 0)) return hipErrorInvalidValue;
     if (path == 1 && conv_mfma_supported(a)) {
-        const bool use_halo = !(dyf_form("DYF_UP_HALO") && atoi(dyf_form("DYF_UP_HALO")) == 0);
+        const bool use_halo = dyf_form_int("DYF_UP_HALO", 1) != 0;
         // halo form from 32 x 32 low-res planes on; below that (dec2: 16 x 16, 2 tiles per image) the materialised upsample +
         // plain 3x3 halo conv is still slightly ahead (7 715 vs 7 690 fields/s with DYF_HALO_MIN_PLANE=16: 640 workgroups of
         // the fused form fill 1.25 rounds of the 512 resident ones)
-        const int halo_min = dyf_form("DYF_HALO_MIN_PLANE") ? atoi(dyf_form("DYF_HALO_MIN_PLANE")) : 32;
+        const int halo_min = dyf_form_int("DYF_HALO_MIN_PLANE", 32);
         if (a.up2x && a.up_cols)  // sparse-column form: only the halo kernel writes the compact output tensor
             return conv_up_halo_supported(a) ? launch_conv_up_halo(a, stream) : hipErrorInvalidValue;
         if (a.up2x && use_halo && a.h >= halo_min && a.w >= halo_min && conv_up_halo_supported(a)) return launch_conv_up_halo(a, stream);
@@ -802,16 +801,14 @@ hipError_t launch_conv_stats(const ConvArgs& a_in, int path, hipStream_t stream,
         // instead of one gather per tap); DYF_HALO3=0 disables, DYF_HALO3_MIN_TILES sets the smallest launch (measured at NB = 80,
         // enc3 with 320 tiles 115 -> 94 us; round 4, with the rows forms: from 80 tiles on -- NS at 7 / 10 / 25 rows +3.4 / +5.7 /
         // +2.5 % against the 256 of rounds 1-3, nothing lost at 4 or 80 rows; 64 costs 2.4 % at 4 rows)
-        const bool h5_all = dyf_form("DYF_HALO5_ALL") && atoi(dyf_form("DYF_HALO5_ALL")) != 0;
-        if (!a.up2x && a.kh == 3 && a.kw == 3 && a.cout % 256 == 0 && !h5_all && a.out_f32 == nullptr && a.residual == nullptr) {
-            const char* h3 = dyf_form("DYF_HALO3");
-            if (!(h3 && atoi(h3) == 0)) {
+        if (!a.up2x && a.kh == 3 && a.kw == 3 && a.cout % 256 == 0 && a.out_f32 == nullptr && a.residual == nullptr) {
+            if (dyf_form_int("DYF_HALO3", 1) != 0) {
                 ConvArgs b = a;
                 b.wpk_up_frag = conv_lookup_halo3_frag(b.wpk);
-                const char* mt3 = dyf_form("DYF_HALO3_MIN_TILES");
+                const long long min_tiles3 = dyf_form_int("DYF_HALO3_MIN_TILES", 80);
                 const long long tiles3 = (nsel * a.h * a.w / 128) * (a.cout / 256);
-                const bool rows = !(dyf_form("DYF_HALO_ROWS") && atoi(dyf_form("DYF_HALO_ROWS")) == 0);
-                if (b.wpk_up_frag && tiles3 >= (mt3 ? atoll(mt3) : 80) && conv_halo3_supported(b))
+                const bool rows = dyf_form_int("DYF_HALO_ROWS", 1) != 0;
+                if (b.wpk_up_frag && tiles3 >= min_tiles3 && conv_halo3_supported(b))
                     return rows && conv_halo_rows3_supported(b) ? launch_conv_halo_rows3(b, stream) : launch_conv_halo3(b, stream);
             }
         }
@@ -840,39 +837,37 @@ hipError_t launch_conv_stats(const ConvArgs& a_in, int path, hipStream_t stream,
         }
         if (!a.up2x && a.kh == 4 && a.kw == 4 && a.stride == 2 && a.cout % 128 == 0 && a.c1 == 0 && a.out_f32 == nullptr &&
             a.residual == nullptr && a.pix_pitch0 == 0) {  // 4x4 / s2 convs: the same kernel on the space-to-depth view
-            const char* h3 = dyf_form("DYF_HALO3");
-            if (!(h3 && atoi(h3) == 0)) {
+            if (dyf_form_int("DYF_HALO3", 1) != 0) {
                 ConvArgs b = a;
                 b.wpk_up_frag = conv_lookup_halo3_frag(b.wpk);
-                const char* mt3 = dyf_form("DYF_HALO_S2_MIN_TILES");  // (its own switch since round 5; DYF_HALO3_MIN_TILES still applies when unset)
-                if (!mt3) mt3 = dyf_form("DYF_HALO3_MIN_TILES");
+                // (its own switch since round 5; DYF_HALO3_MIN_TILES still applies when unset)
+                const long long min_tiles3 = dyf_form_int("DYF_HALO_S2_MIN_TILES", dyf_form_int("DYF_HALO3_MIN_TILES", 80));
                 // cout % 256 == 0: 8 x 16 tiles x 256 channels; else 16 x 16 tiles x 128 channels
                 const long long tiles3 = a.cout % 256 == 0 ? (nsel * a.ho * a.wo / 128) * (a.cout / 256)
                                                            : (nsel * a.ho * a.wo / 256) * (a.cout / 128);
-                if (b.wpk_up_frag && tiles3 >= (mt3 ? atoll(mt3) : 80) && conv_halo_s2_supported(b)) return launch_conv_halo_s2(b, stream);
+                if (b.wpk_up_frag && tiles3 >= min_tiles3 && conv_halo_s2_supported(b)) return launch_conv_halo_s2(b, stream);
             }
         }
-        const bool use_igemm2 = !(dyf_form("DYF_IGEMM2") && atoi(dyf_form("DYF_IGEMM2")) == 0);
+        const bool use_igemm2 = dyf_form_int("DYF_IGEMM2", 1) != 0;
         if (!a.up2x && use_igemm2 && a.cout % 64 == 0) {  // cout % 128 == 0: 256 x 128 tiles, else 256 x 64
             ConvArgs b = a;
             if (!b.wpk_frag) b.wpk_frag = conv_lookup_frag(b.wpk);
             // 256 x 128 tiles pay off once they fill the chip (2 workgroups x 256 CUs); below that the 128 x 128 form's
             // finer tiles win (measured at NB = 50: dec2/enc2 with 400 tiles +9 %/+4 %, enc3 with 200 tiles -20 %)
             const long long tiles2 = ((nsel * a.ho * a.wo + 255) / 256) * (a.cout % 128 == 0 ? a.cout / 128 : a.cout / 64);
-            const char* mt = dyf_form("DYF_IGEMM2_MIN_TILES");  // tests force the form on small problems
-            const long long min_tiles = mt ? atoll(mt) : 384;
+            const long long min_tiles = dyf_form_int("DYF_IGEMM2_MIN_TILES", 384);  // tests force the form on small problems
             if (tiles2 >= min_tiles && conv_igemm2_supported(b)) return launch_conv_igemm2(b, stream);
         }
         // few rows: 1x1 / 2x2-s2 convs whose 128 x 128 tiles would not even fill a quarter of the chip (the split-K regime of
         // launch_igemm) run on conv_skinny_kernel -- K split over the four waves of a 32 x 32 tile, one launch (DYF_SKINNY=0 disables)
         if (!a.up2x && a.cout % 128 == 0) {
-            const bool skinny = !(dyf_form("DYF_SKINNY") && atoi(dyf_form("DYF_SKINNY")) == 0);
+            const bool skinny = dyf_form_int("DYF_SKINNY", 1) != 0;
             const long long tiles128 = ((nsel * a.ho * a.wo + 127) / 128) * (a.cout / 128);
             ConvArgs b = a;
             if (!b.wpk_frag) b.wpk_frag = conv_lookup_frag(b.wpk);
             // (64 tiles of 128 x 128: NS at 1 / 4 / 7 / 10 rows +10.6 / +4 / +2 / +1 %, nothing lost at 25 / 38; at 128 the 25- and
             // 38-row rollouts lose 2.5 %)
-            const long long sk_max = dyf_form("DYF_SKINNY_MAX_TILES") ? atoll(dyf_form("DYF_SKINNY_MAX_TILES")) : 64;
+            const long long sk_max = dyf_form_int("DYF_SKINNY_MAX_TILES", 64);
             if (skinny && tiles128 <= sk_max && conv_skinny_supported(b)) return launch_conv_skinny(b, stream);
         }
         if (a.cout % 128 == 0)
@@ -921,14 +916,14 @@ hipError_t launch_conv_gn_fused(const ConvArgs& a_in, int path, hipStream_t stre
         // 256-channel level on SMALL planes (15 x 15 at OISST: one 16 x 16 tile per sample): conv_gn16_kernel with four 64-channel column
         // blocks per sample instead of conv_igemm2_kernel<2, true>'s 256-pixel x 128-channel tiles -- half the K chain per workgroup,
         // more than twice the workgroups (400 against 176 at 100 rows).  DYF_GN16_C256=0: off
-        const bool on = !(dyf_form("DYF_GN16") && atoi(dyf_form("DYF_GN16")) == 0) && !(dyf_form("DYF_GN16_C256") && atoi(dyf_form("DYF_GN16_C256")) == 0);
+        const bool on = dyf_form_int("DYF_GN16", 1) != 0 && dyf_form_int("DYF_GN16_C256", 1) != 0;
         ConvArgs b = a;
         b.wpk_up_frag = conv_lookup_frag64(b.wpk);
         const int slots16 = conv_gn16_slots(a.h, a.w);
         const long long tiles16 = nsel * slots16 * (a.cout / 64);
-        const bool covers16 = 10ll * a.h * a.w >= 6ll * slots16 * 256 || (dyf_form("DYF_GN16_ANY_PLANE") && atoi(dyf_form("DYF_GN16_ANY_PLANE")) != 0);
-        const long long max_plane = dyf_form("DYF_GN16_C256_MAX_PLANE") ? atoll(dyf_form("DYF_GN16_C256_MAX_PLANE")) : 1024;
-        const long long c256_min = dyf_form("DYF_GN16_MIN_TILES") ? atoll(dyf_form("DYF_GN16_MIN_TILES")) : 64;
+        const bool covers16 = 10ll * a.h * a.w >= 6ll * slots16 * 256 || dyf_form_int("DYF_GN16_ANY_PLANE", 0) != 0;
+        const long long max_plane = dyf_form_int("DYF_GN16_C256_MAX_PLANE", 1024);
+        const long long c256_min = dyf_form_int("DYF_GN16_MIN_TILES", 64);
         if (on && b.wpk_up_frag && covers16 && (long long)a.h * a.w <= max_plane && tiles16 >= c256_min && slots16 <= GN_FUSE_MAX_SLOTS &&
             slots16 <= G.max_slots && conv_gn16_supported(b)) {
             b.gnf.slots = slots16;
@@ -937,17 +932,17 @@ hipError_t launch_conv_gn_fused(const ConvArgs& a_in, int path, hipStream_t stre
         }
     }
     if (a.kh == 3 && a.kw == 3 && a.stride == 1 && a.pad == 1 && a.cout % 64 == 0 && a.cout % 256 != 0) {
-        const bool h5 = !(dyf_form("DYF_HALO5") && atoi(dyf_form("DYF_HALO5")) == 0);
-        const long long h5_min = dyf_form("DYF_HALO5_MIN_TILES") ? atoll(dyf_form("DYF_HALO5_MIN_TILES")) : 64;
+        const bool h5 = dyf_form_int("DYF_HALO5", 1) != 0;
+        const long long h5_min = dyf_form_int("DYF_HALO5_MIN_TILES", 64);
         ConvArgs b = a;
         b.wpk_up_frag = conv_lookup_halo3_frag(b.wpk);
         {   // 16 x 16 tiles, three workgroups per CU (conv_gn16.hip; DYF_GN16=0: the 16 x 32 form below)
-            const bool g16 = !(dyf_form("DYF_GN16") && atoi(dyf_form("DYF_GN16")) == 0);
-            const long long g16_min = dyf_form("DYF_GN16_MIN_TILES") ? atoll(dyf_form("DYF_GN16_MIN_TILES")) : 64;
+            const bool g16 = dyf_form_int("DYF_GN16", 1) != 0;
+            const long long g16_min = dyf_form_int("DYF_GN16_MIN_TILES", 64);
             const int slots16 = conv_gn16_slots(a.h, a.w);
             const long long tiles16 = nsel * slots16 * (a.cout / 64);
             // (planes that fill less than 60 % of their tiles are left to the other forms; DYF_GN16_ANY_PLANE=1: the tests' tiny planes)
-            const bool covers16 = 10ll * a.h * a.w >= 6ll * slots16 * 256 || (dyf_form("DYF_GN16_ANY_PLANE") && atoi(dyf_form("DYF_GN16_ANY_PLANE")) != 0);
+            const bool covers16 = 10ll * a.h * a.w >= 6ll * slots16 * 256 || dyf_form_int("DYF_GN16_ANY_PLANE", 0) != 0;
             if (g16 && b.wpk_up_frag && covers16 && tiles16 >= g16_min && slots16 <= GN_FUSE_MAX_SLOTS && slots16 <= G.max_slots &&
                 conv_gn16_supported(b)) {
                 b.gnf.slots = slots16;
@@ -965,7 +960,7 @@ hipError_t launch_conv_gn_fused(const ConvArgs& a_in, int path, hipStream_t stre
             return launch_conv_halo5(b, stream);
         }
     }
-    const bool use_igemm2 = !(dyf_form("DYF_IGEMM2") && atoi(dyf_form("DYF_IGEMM2")) == 0);
+    const bool use_igemm2 = dyf_form_int("DYF_IGEMM2", 1) != 0;
     if (use_igemm2 && a.cout % 128 == 0) {
         ConvArgs b = a;
         if (!b.wpk_frag) b.wpk_frag = conv_lookup_frag(b.wpk);
@@ -975,9 +970,7 @@ hipError_t launch_conv_gn_fused(const ConvArgs& a_in, int path, hipStream_t stre
         // from 32 tiles on.  Measured at the end of round 4, OISST shapes, fields/s with the threshold at 256 (the first choice) /
         // 64 / 16: 300 rows 4 154 / 4 165 / 4 181, 150 rows 3 568 / 3 626 / 3 631, 75 rows 2 360 / 2 494 / 2 479, 38 rows 1 548 /
         // 1 619 / 1 654, 16 rows 811 / 811 / 791 (32: 818) -- DYF_GN_FUSE_MIN_TILES overrides, DYF_IGEMM2_MIN_TILES (tests) wins
-        const char* mt = dyf_form("DYF_IGEMM2_MIN_TILES");
-        const char* mf = dyf_form("DYF_GN_FUSE_MIN_TILES");
-        const long long min_tiles = mt ? atoll(mt) : mf ? atoll(mf) : 32;
+        const long long min_tiles = dyf_form_int("DYF_IGEMM2_MIN_TILES", dyf_form_int("DYF_GN_FUSE_MIN_TILES", 32));
         const int slots = conv_igemm2_gn_slots(a.ho, a.wo);
         // flattened-M tiles cut a sample into 128-row slabs at (n * plane) % 128: unless plane % 128 == 0 (or the tiles are 2-D) the
         // fp32 partial sums of a sample are grouped by its POSITION in the launch, and (mean, 1/std) differ in the last bits between
@@ -987,8 +980,7 @@ hipError_t launch_conv_gn_fused(const ConvArgs& a_in, int path, hipStream_t stre
         // few tiles: the 128-pixel tile form (half the K chain per wave, twice the workgroups) while the 256-pixel tiles would leave
         // CUs idle -- DYF_IGEMM2_BM128_BELOW tiles (0 = never); not for batch_invariant engines whose planes are not slab-aligned
         // (the same position argument as above, with 64-row slabs)
-        const char* b128 = dyf_form("DYF_IGEMM2_BM128_BELOW");  // read per launch (parity test)
-        const long long bm128_below = b128 ? atoll(b128) : 224;
+        const long long bm128_below = dyf_form_int("DYF_IGEMM2_BM128_BELOW", 224);  // read per launch (parity test)
         const int slots128 = conv_igemm2_gn_slots_bm128(a.ho, a.wo);
         const bool free128 = (a.wo % 16 == 0 && a.ho % 8 == 0) || (a.ho * a.wo) % 64 == 0;
         if (tiles2 >= min_tiles && tiles2 < bm128_below && slots128 > 0 && slots128 <= GN_FUSE_MAX_SLOTS && slots128 <= G.max_slots &&

@@ -129,12 +129,7 @@ __global__ __launch_bounds__(512) void conv_enc0_stem_kernel(ConvArgs a, const e
             const int off = k * 1024 + lane * 16;                 // byte offset inside the tile
             const int px = off / (NT * 64), within = off - px * (NT * 64);
             const uint4 ov = *(const uint4*)(ostage + px * OROW + within);
-#ifdef DYF_NT_STORES  // experiment: non-temporal stores
-            typedef __attribute__((ext_vector_type(4))) unsigned nt_u32x4;
-            __builtin_nontemporal_store(__builtin_bit_cast(nt_u32x4, ov), (nt_u32x4*)((unsigned char*)tbase + off));
-#else
             *(uint4*)((unsigned char*)tbase + off) = ov;
-#endif
         }
     };
 
@@ -179,7 +174,7 @@ void pack_enc0_stem_frag(const el16_t* wpk, int cout, el16_t* out) {
 
 // the fused-stem view of enc0 (engine.hip fused_enc0_args): 16-channel pixels declared as 64-channel ones, kh = 4, kw = 1
 bool conv_enc0_stem_supported(const ConvArgs& a) {
-    const bool on = !(dyf_form("DYF_ENC0_STEM") && atoi(dyf_form("DYF_ENC0_STEM")) == 0);
+    const bool on = dyf_form_int("DYF_ENC0_STEM", 1) != 0;
     if (!on || a.pix_pitch0 != 16 || a.c0 != 64 || a.c1 != 0 || a.kh != 4 || a.kw != 1 || a.stride != 2 || a.pad != 0) return false;
     if (a.up2x || a.residual || a.out_f32 || !a.out_el16 || (a.cout != 64 && a.cout != 128)) return false;
     if (a.wo % 32 != 0 || (a.ho * (a.wo / 32)) % 16 != 0 || a.h != 2 * a.ho + 2 || a.w != 2 * a.wo + 2) return false;

@@ -5,7 +5,7 @@
 // cat([x, skip]) of unequal channel counts (conv.hip launch_conv_gn_fused holds the policy).
 //
 // Why a second form beside conv_up_halo_kernel<5, 2> (16 x 32 tiles, 128 accumulator registers per wave, 80 KB of LDS, two workgroups
-// per CU): a phase timeline of that kernel (tools/timeline_oisst.py, profiles/r06_halo5_timeline.txt) shows a tile's life as a SERIAL
+// per CU): a phase timeline of that kernel (a since-retired experiment build, profiles/r06_halo5_timeline.txt) shows a tile's life as a SERIAL
 // chain -- 10-15 k cycles until its 78 KB halo has landed, 11-14 k of K loop (9.2 k of matrix work), 4-5 k statistics, 4-10 k waiting
 // for the sample's other tiles, 9-20 k epilogue -- i.e. the matrix pipe works for 15-18 % of a wave's life and NOTHING on the CU
 // overlaps it except the one other workgroup (which started at the same time and is in the same phase; delaying it changed nothing:
@@ -45,15 +45,6 @@ constexpr int LDS16_TOTAL = COEF16_OFF + 512; // 42 752 B: three workgroups per 
 constexpr unsigned WSTEP16 = 8192u;           // weight bytes of one (tap, chunk) step of a 64-channel block: [ks][nt][lane] x 16 B
 }  // namespace
 
-#ifdef HALO_EXP_TIMELINE  // experiment builds only (tools/build_variant.sh, tools/timeline_oisst.py): per-wave shader-clock stamps at the phase boundaries
-__device__ unsigned long long g_gn16_tl[1 << 18];
-#define TL16(K) if (blockIdx.x < 8192 && lane == 0) g_gn16_tl[(blockIdx.x * 4 + wave) * 8 + (K)] = __builtin_amdgcn_s_memtime();
-#include <cstdio>
-#include <string>
-#include <vector>
-#else
-#define TL16(K)
-#endif
 __global__ __launch_bounds__(256, 3) void conv_gn16_kernel(ConvArgs a, int tiles_x, int tiles_per_img, int tiles_m, int tiles_n) {
 #if defined(__HIP_DEVICE_COMPILE__)
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -61,7 +52,6 @@ __global__ __launch_bounds__(256, 3) void conv_gn16_kernel(ConvArgs a, int tiles
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l31 = lane & 31, hi = lane >> 5;
-    TL16(0)
 
     // XCD-aware tile id (block b runs on XCD b % 8): every XCD walks a contiguous range of tiles, the column blocks of one tile are
     // consecutive (they share the halo in L2)
@@ -140,10 +130,7 @@ __global__ __launch_bounds__(256, 3) void conv_gn16_kernel(ConvArgs a, int tiles
         issue_halo(chunk);
         const unsigned wbase = (unsigned)((tn * cpt + chunk) * 16) * WSTEP16;
         // weight fragments: ring of WAHEAD + 1 sets, requested WAHEAD sub-steps ahead (an L2 round trip is longer than one sub-step's 4 MFMAs)
-#ifndef G16_WAHEAD
-#define G16_WAHEAD 5
-#endif
-        constexpr int WAHEAD = G16_WAHEAD, WR = WAHEAD + 1;
+        constexpr int WAHEAD = 5, WR = WAHEAD + 1;
         u32x4 wq[WR][2];
 #pragma unroll
         for (int p = 0; p < WAHEAD; ++p)
@@ -151,12 +138,9 @@ __global__ __launch_bounds__(256, 3) void conv_gn16_kernel(ConvArgs a, int tiles
             for (int nt = 0; nt < 2; ++nt)
                 wq[p][nt] = __builtin_amdgcn_raw_buffer_load_b128(rsrc_w, w_voff + nt * 1024, wbase + (unsigned)(p >> 2) * WSTEP16 + (unsigned)(p & 3) * 2048u, 0);
         // this wave's part of the halo has landed (the 2 x WAHEAD weight loads behind it may still fly) ...
-        if constexpr (WAHEAD == 3) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-        else if constexpr (WAHEAD == 5) asm volatile("s_waitcnt vmcnt(10)" ::: "memory");
-        else if constexpr (WAHEAD == 7) asm volatile("s_waitcnt vmcnt(14)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        static_assert(2 * WAHEAD == 10, "vmcnt below counts the weight loads in flight");
+        asm volatile("s_waitcnt vmcnt(10)" ::: "memory");
         __syncthreads();                                   // ... and so has everybody else's
-        if (chunk == 0) { TL16(1) }
         el16x8_t pq[2][2];
         unsigned ab[2], ax[2];
         auto tap_addr = [&](int tap) {
@@ -199,7 +183,6 @@ __global__ __launch_bounds__(256, 3) void conv_gn16_kernel(ConvArgs a, int tiles
 
     // ---- epilogue straight from the accumulators: lane (l31, hi) of tile (nt, mt) holds pixel l31 of pixel tile mt and channels
     // nt * 32 + 8 g + 4 hi + {0..3} (g = register group r >> 2)
-    TL16(2)
     const GnFuse& G = a.gnf;
     const RngKey key = drop_row_key(a.drop, n_img);
     const uint32_t row0 = (uint32_t)n_img * (uint32_t)(a.ho * a.wo * a.cout);  // dropout streams are per batch row
@@ -269,7 +252,6 @@ __global__ __launch_bounds__(256, 3) void conv_gn16_kernel(ConvArgs a, int tiles
             }
         }
     }
-    TL16(3)
     __syncthreads();  // the four waves' statistics are in LDS (and every wave has left the K loop)
     // Phase B: wave 0 adds the waves' values in wave order, publishes the workgroup's slot (16 granules), sweeps the sample's slots and
     // parks (A, C) of the block's 64 channels in LDS
@@ -314,10 +296,8 @@ __global__ __launch_bounds__(256, 3) void conv_gn16_kernel(ConvArgs a, int tiles
         const float2 ac = gn_fuse_coef(G, ch_blk + lane, a.coef_div > 1 ? n_img / a.coef_div : n_img, mr);
         cfA[lane] = ac.x;
         cfC[lane] = ac.y;
-        TL16(6)
     }
     __syncthreads();
-    TL16(4)
     // Phase C: y * A + C -> SiLU -> dropout -> (+ residual) -> 16-bit; groups 2 g2 and 2 g2 + 1 are packed and exchanged between lanes
     // l and l + 32 (v_permlane32_swap), after which every lane owns 8 consecutive channels = one 16-byte store
     auto fused = [&](auto mode_c) {
@@ -366,7 +346,6 @@ __global__ __launch_bounds__(256, 3) void conv_gn16_kernel(ConvArgs a, int tiles
     };
     if (a.drop.mode == 1) fused(std::integral_constant<int, 1>{});
     else fused(std::integral_constant<int, 0>{});
-    TL16(5)
 #undef HKEY16
 #endif
 }
@@ -390,22 +369,5 @@ hipError_t launch_conv_gn16(const ConvArgs& a, hipStream_t stream) {
     const int tiles_m = a.n * tiles_per_img, tiles_n = a.cout / 64;
     dyf_form_note("conv_gn16_kernel+gn_fused", a.n);
     hipLaunchKernelGGL(conv_gn16_kernel, dim3(tiles_m * tiles_n), dim3(256), LDS16_TOTAL, stream, a, tiles_x, tiles_per_img, tiles_m, tiles_n);
-#ifdef HALO_EXP_TIMELINE
-    if (const char* tl = dyf_form("DYF_TIMELINE_DUMP")) {  // "path:N": the stamps of the N-th launch of the process (eager launches only)
-        static int count = 0;
-        const char* colon = strrchr(tl, ':');
-        if (colon && ++count == atoi(colon + 1)) {
-            (void)hipStreamSynchronize(stream);
-            std::vector<unsigned long long> h((size_t)1 << 18);
-            (void)hipMemcpyFromSymbol(h.data(), HIP_SYMBOL(g_gn16_tl), h.size() * 8);
-            if (FILE* f = fopen(std::string(tl, colon - tl).c_str(), "wb")) {
-                const int hdr[4] = {tiles_m * tiles_n, a.n, a.residual != nullptr, a.drop.mode};
-                fwrite(hdr, sizeof(int), 4, f);
-                fwrite(h.data(), 8, (size_t)std::min(tiles_m * tiles_n, 8192) * 32, f);
-                fclose(f);
-            }
-        }
-    }
-#endif
     return hipGetLastError();
 }

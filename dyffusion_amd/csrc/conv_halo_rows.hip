@@ -59,19 +59,11 @@ struct RowsCfg {
     static constexpr int PER_WAVE = (INSTR + R_NWAVES - 1) / R_NWAVES;
     static constexpr int HOFF_OFF = NBUF * BYTES;     // per-thread halo source offsets [PER_WAVE][256]
     static constexpr int TAB_END = HOFF_OFF + PER_WAVE * 1024;    // 60 416 / 69 632 B
-    // output staging (dense forms, -DHALO_NO_STAGE disables): per wave one tile row of [32 pixels][64 channels] 16-bit + 16 B pad
+    // output staging (dense forms): per wave one tile row of [32 pixels][64 channels] 16-bit + 16 B pad
     // per pixel; the sparse form has no room for it next to its 55 KB halo (two workgroups per CU)
-#ifndef HALO_NO_STAGE
     static constexpr bool STAGE = SP != 1;
-#else
-    static constexpr bool STAGE = false;
-#endif
     // sparse form: room for HALF a tile row per wave (16 pixels, two passes per row) + the row's compact column indices
-#ifndef HALO_NO_STAGE
     static constexpr bool STAGE_HALF = SP == 1 && SH == 0;
-#else
-    static constexpr bool STAGE_HALF = false;
-#endif
     static constexpr int OROW = 144;
     static constexpr int LDS_TOTAL = TAB_END + (STAGE ? R_NWAVES * 32 * OROW : 0) +
                                      (STAGE_HALF ? R_NWAVES * (16 * OROW + 128) : 0);  // 78 848 / 79 360 B: two workgroups per CU
@@ -221,14 +213,9 @@ __device__ __forceinline__ void conv_halo_rows_body(const ConvArgs& a, int tiles
     el16x8_t pq[2][6];  // pixel fragments: halo rows 0..5 of the current / next super-slot
     unsigned ab = 0, ax = 0, pa = 0;
 
-#ifdef HALO_EXP_W_ALIAS
-#define W_ALIAS(x) ((x) & 0x3FFFu)
-#else
-#define W_ALIAS(x) (x)
-#endif
 #define ISSUE_B(SET, SOFF)                                                                                   \
     _Pragma("unroll") for (int nt = 0; nt < 2; ++nt)                                                         \
-        bq[SET][nt] = __builtin_amdgcn_raw_buffer_load_b128(rsrc_w, w_voff + nt * 1024, W_ALIAS(SOFF), 0);
+        bq[SET][nt] = __builtin_amdgcn_raw_buffer_load_b128(rsrc_w, w_voff + nt * 1024, SOFF, 0);
 #define DSRO(dst, addr, OFF) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(OFF));
 #define LGKM_WAIT0                                                        \
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                    \
@@ -276,13 +263,7 @@ __device__ __forceinline__ void conv_halo_rows_body(const ConvArgs& a, int tiles
     }
 
     issue_halo(cbeg);
-    // timing experiments (wrong results): -DHALO_EXP_W_SHARE makes the four waves stream the SAME fragments (do simultaneous
-    // requests meet in L1?), -DHALO_EXP_W_ALIAS serves the stream from 16 KB
-#ifdef HALO_EXP_W_SHARE
-    const unsigned soff_w = 0u;
-#else
     const unsigned soff_w = (unsigned)(wpy * (R_STEP_BYTES / 2) + wpx * 2048);
-#endif
     unsigned soff_c = (unsigned)((tn * cpt + cbeg) * 16) * (unsigned)R_STEP_BYTES + soff_w, soff_n = soff_c;
     // (pinned in program order: the compiler's own vmcnt at the loop head is merged over the entry and the back edge)
     PIN
@@ -300,11 +281,7 @@ __device__ __forceinline__ void conv_halo_rows_body(const ConvArgs& a, int tiles
             __builtin_amdgcn_sched_barrier(0);
             if (chunk + 1 < cend) issue_halo(chunk + 1);
         } else {
-#ifdef HALO_EXP_NO_DMA_WAIT  // timing experiment (wrong results): the single-buffered halo is not waited for
-            asm volatile("s_waitcnt vmcnt(24)" ::: "memory");
-#else
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
             __builtin_amdgcn_s_barrier();
             __builtin_amdgcn_sched_barrier(0);
         }
@@ -413,15 +390,9 @@ __device__ __forceinline__ void conv_halo_rows_body(const ConvArgs& a, int tiles
                 for (int k = 0; k < 4; ++k) {
                     const int px = 8 * k + rpx;
                     const uint4 o = *(const uint4*)(ost + px * H::OROW + rch * 16);
-#ifdef HALO_EXP_NO_STORE  // timing experiment (wrong results): the staged epilogue without its global stores
-                    if (o.x == 0x12345678u && o.y == 0x9abcdef0u)
-#endif
-#ifndef HALO_NO_NT_STORE  // non-temporal stores (the output is not read again by this kernel, and the weights / halos keep their
-                         // place in L2): dec4 558 -> 545 us; -DHALO_NO_NT_STORE restores plain stores
+                    // non-temporal stores (the output is not read again by this kernel, and the weights / halos keep their place in
+                    // L2): dec4 558 -> 545 us
                     __builtin_nontemporal_store(__builtin_bit_cast(u32x4, o), (u32x4*)(a.out_el16 + (size_t)(row_base + t * st_stride + (uint32_t)px * pstride + rch * 8)));
-#else
-                    *(uint4*)(a.out_el16 + (size_t)(row_base + t * st_stride + (uint32_t)px * pstride + rch * 8)) = o;
-#endif
                 }
             }
             return;
@@ -493,7 +464,6 @@ __device__ __forceinline__ void conv_halo_rows_body(const ConvArgs& a, int tiles
             // all 32 list slots, laid OVER the halo buffer -- the K loop is over, a barrier makes sure every wave is done reading it
             // (their halo leaves no LDS for a staging area of its own; stored as 32-byte pieces straight from the registers these
             // tiles wrote 1.24x the output and the stores cost 9 % of the launch: 537 vs 489 us with the stores removed).
-#ifndef HALO_NO_STAGE_SHAPES
             __syncthreads();
             unsigned char* ost = (unsigned char*)smem + wave * (32 * H::OROW + 128);
             int* cst = (int*)(ost + 32 * H::OROW);
@@ -540,17 +510,12 @@ __device__ __forceinline__ void conv_halo_rows_body(const ConvArgs& a, int tiles
                     const int orow = 2 * (ty0 + R_TH * (px / H::COLS) + t) + wpy;  // output row of the slot's row set
                     const uint4 val = *(const uint4*)(ost + px * H::OROW + rch * 16);
                     if (c >= 0) {
-#ifndef HALO_NO_NT_STORE
                         __builtin_nontemporal_store(__builtin_bit_cast(u32x4, val),
                                                     (u32x4*)(a.out_el16 + ((size_t)((n_img * a.ho + orow) * a.up_wo_store + c) * a.cout + tn * 64 + rch * 8)));
-#else
-                        *(uint4*)(a.out_el16 + ((size_t)((n_img * a.ho + orow) * a.up_wo_store + c) * a.cout + tn * 64 + rch * 8)) = val;
-#endif
                     }
                 }
             }
             return;
-#endif
         }
         // 32-channel half outermost, tile rows, then the two 16-channel groups of the half: the two 32-byte pieces of a pixel's
         // 64-byte half block are stored back to back and leave the L2 as whole 64-byte writes (with the channel groups
@@ -587,11 +552,7 @@ __device__ __forceinline__ void conv_halo_rows_body(const ConvArgs& a, int tiles
                     uint4 o;
                     o.x = s0[0]; o.y = s1[0]; o.z = s0[1]; o.w = s1[1];
                     const uint32_t sbase = store0 + t * st_stride + cg0;
-#ifdef HALO_EXP_NO_STORE  // timing experiment (wrong results): the register-store epilogue without its stores
-                    if (o.x == 0x12345678u && o.y == 0x9abcdef0u) *(uint4*)(a.out_el16 + (size_t)(sbase + 8 * hi)) = o;
-#else
                     if (SP != 1 || lane_valid) *(uint4*)(a.out_el16 + (size_t)(sbase + 8 * hi)) = o;
-#endif
                 }
             }
         }
@@ -634,10 +595,8 @@ __global__ __launch_bounds__(256, 2) void conv_halo_rows_tr_kernel(ConvArgs a, i
 // ragged round (256 < tiles <= 384: 2.5 half-tiles per CU instead of 2 whole ones on a quarter of the chip).  DYF_ROWS_TR = 4 / 2 /
 // 1 forces a shape (read per launch); measured in DESIGN.md 5 (round 5).
 static int rows_tile_rows(long long tiles4, int h) {
-    if (const char* f = dyf_form("DYF_ROWS_TR")) {
-        const int t = atoi(f);
-        if ((t == 1 || t == 2 || t == 4) && h % t == 0) return t;
-    }
+    const long long t = dyf_form_int("DYF_ROWS_TR", 0);
+    if ((t == 1 || t == 2 || t == 4) && h % t == 0) return (int)t;
     // measured (NS decoder, us per launch with 4- / 2- / 1-row tiles; dec3 = 16 tiles per row, dec4 = 64, dec2 = 8): dec3 at 4 rows
     // 43.3 / 36.8 / 36.8, at 7 rows 51.2 / 39.7 / 55.7, at 10 rows 52.8 / 60.3 / 76.9, at 20 rows 101.7 / 93.8 / 128.5; dec4 at 1 row
     // 30.5 / 22.0 / 21.8, at 2 rows 31.4 / 24.7 / 32.5, at 4 rows 36.6 / 40.1 / 54.4; dec2 at 10 rows 53.3 (split-K) / 48.5 / 82.9, at 14
@@ -663,12 +622,10 @@ __global__ __launch_bounds__(256, 2) void conv_halo_rows_splitk_kernel(ConvArgs 
 // DYF_HALO_SPLITK_FORCE=s forces a factor (tests); both read per launch.
 static int rows_splitk_factor(const ConvArgs& a, long long tiles_sel, long long tiles, int cpt, long long m_cout) {
     if (a.splitk_ws == nullptr || a.out_f32 != nullptr || a.out_el16 == nullptr || (a.cout & 3) != 0) return 1;
-    const char* on = dyf_form("DYF_HALO_SPLITK");
-    if (on && atoi(on) == 0) return 1;
+    if (dyf_form_int("DYF_HALO_SPLITK", 1) == 0) return 1;
     int best = 1;
-    if (const char* f = dyf_form("DYF_HALO_SPLITK_FORCE")) {
-        best = atoi(f);
-        if (best < 1 || best > 8 || (best & (best - 1)) != 0 || cpt % best != 0) best = 1;
+    if (const long long force = dyf_form_int("DYF_HALO_SPLITK_FORCE", 0)) {
+        best = force >= 1 && force <= 8 && (force & (force - 1)) == 0 && cpt % force == 0 ? (int)force : 1;
     } else {
         // the model is evaluated for the rows the form is pinned to (n_sel) so that a batch_invariant engine keeps one factor
         const double bytes = (double)m_cout * ((double)tiles_sel / (double)std::max<long long>(tiles, 1)) * 4.0;
@@ -682,26 +639,6 @@ static int rows_splitk_factor(const ConvArgs& a, long long tiles_sel, long long 
     }
     while (best > 1 && (long long)best * m_cout > a.splitk_cap) best >>= 1;
     return best;
-}
-
-// EXPERIMENT (DYF_ROWS_PERSISTENT=512; off by default: measured SLOWER, dec4 541 -> 555 us, dec3 283 -> 287 us -- the hardware already
-// starts a new one-tile workgroup the moment one retires, so nothing is gained, and the tile boundary adds a barrier).
-// Persistent form: 512 resident workgroups walk the tiles (stride = grid, a multiple of 8: a workgroup stays on its XCD).  A wave
-// that ends waits for its stores to be acknowledged (s_endpgm implies s_waitcnt 0) and holds its registers and LDS meanwhile: in
-// the one-tile form that store phase is 12-17 % of dec3 / dec4 (565 vs 470 us with the stores removed).  Here the next tile's halo
-// DMA and weight stream are issued right behind the stores; the boundary between tiles is a bare s_barrier behind an LDS wait (not
-// __syncthreads, whose fence would wait for the stores).
-template <int SP, int SH = 0>
-__global__ __launch_bounds__(256, 2) void conv_halo_rows_persistent_kernel(ConvArgs a, int tiles_x, int tiles_per_img, int tiles_m, int tiles_n) {
-    const int total = tiles_m * tiles_n;
-    for (int bid = (int)blockIdx.x; bid < total; bid += (int)gridDim.x) {
-        conv_halo_rows_body<SP, SH>(a, tiles_x, tiles_per_img, tiles_m, tiles_n, bid);
-#if defined(__HIP_DEVICE_COMPILE__)
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-#endif
-    }
 }
 
 // The 16-entry and the 4-entry list tiles of the mixed sparse tiling in ONE grid (blocks [0, n2): 4-entry tiles, the rest: 16-entry
@@ -760,9 +697,6 @@ hipError_t conv_halo_rows_init() {
         e = hipFuncSetAttribute((const void*)conv_halo_rows_kernel<1, 2>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (RowsCfg<1, 2>::LDS_TOTAL));
     if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void*)conv_halo_rows_persistent_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                RowsCfg<0>::LDS_TOTAL);
-    if (e == hipSuccess)
         e = hipFuncSetAttribute((const void*)(conv_halo_rows_tr_kernel<0, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, (RowsCfg<0, 0, 2>::LDS_TOTAL));
     if (e == hipSuccess)
         e = hipFuncSetAttribute((const void*)(conv_halo_rows_tr_kernel<0, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, (RowsCfg<0, 0, 1>::LDS_TOTAL));
@@ -792,7 +726,7 @@ hipError_t launch_conv_halo_rows_up(const ConvArgs& a, hipStream_t stream) {
         constexpr int LDS_S0 = RowsCfg<1, 0>::LDS_TOTAL, LDS_S1 = RowsCfg<1, 1>::LDS_TOTAL, LDS_S2 = RowsCfg<1, 2>::LDS_TOTAL;
         const int cnt[3] = {a.up_mix[0], a.up_mix[1], a.up_mix[2]};
         const int off[3] = {0, 32 * cnt[0], 32 * cnt[0] + 16 * cnt[1]}, cb[3] = {0, cnt[0], cnt[0] + cnt[1]};
-        const bool one_grid = !(dyf_form("DYF_SPARSE_MIXED_ONE_GRID") && atoi(dyf_form("DYF_SPARSE_MIXED_ONE_GRID")) == 0);
+        const bool one_grid = dyf_form_int("DYF_SPARSE_MIXED_ONE_GRID", 1) != 0;
         if (one_grid && cnt[1] > 0 && cnt[2] > 0) {  // the 16- and 4-entry tiles in one grid; 32-entry tiles (if any) on their own below
             RowsMixGeom g1{off[1], cb[1], cnt[1], cnt[1] * (a.h / (2 * R_TH)), a.n * cnt[1] * (a.h / (2 * R_TH))};
             RowsMixGeom g2{off[2], cb[2], cnt[2], cnt[2] * (a.h / (8 * R_TH)), a.n * cnt[2] * (a.h / (8 * R_TH))};
@@ -820,11 +754,6 @@ hipError_t launch_conv_halo_rows_up(const ConvArgs& a, hipStream_t stream) {
     }
     const int tiles_x = sparse ? a.up_ntiles : a.w / R_TW, tiles_per_img = tiles_x * (a.h / R_TH);
     int tiles_m = a.n * tiles_per_img;
-#ifdef DYF_EXPERIMENT_BUILD
-    // timing experiment (WRONG results): 13 of 16 sparse tiles -- what packing the 52-column lists without padded slots would save
-    const bool exp1316 = dyf_form("DYF_EXP_DEC5_1316") && atoi(dyf_form("DYF_EXP_DEC5_1316")) != 0;
-    if (sparse && exp1316) tiles_m = tiles_m * 13 / 16;
-#endif
     if (!sparse) {
         const long long sel4 = (long long)(a.n_sel > 0 ? a.n_sel : a.n) * tiles_per_img * tiles_n;
         const int tr = rows_tile_rows(sel4, a.h);
@@ -850,12 +779,8 @@ hipError_t launch_conv_halo_rows_up(const ConvArgs& a, hipStream_t stream) {
         }
     }
     dyf_form_note(sparse ? "conv_halo_rows_kernel<1>" : "conv_halo_rows_kernel<0>", a.n);
-    const int persist = dyf_form("DYF_ROWS_PERSISTENT") ? atoi(dyf_form("DYF_ROWS_PERSISTENT")) : 0;
     if (sparse)
         hipLaunchKernelGGL((conv_halo_rows_kernel<1, 0>), dim3(tiles_m * tiles_n), dim3(256), RowsCfg<1>::LDS_TOTAL, stream, a, tiles_x,
-                           tiles_per_img, tiles_m, tiles_n);
-    else if (persist > 0 && tiles_m * tiles_n > persist)
-        hipLaunchKernelGGL(conv_halo_rows_persistent_kernel<0>, dim3(persist), dim3(256), RowsCfg<0>::LDS_TOTAL, stream, a, tiles_x,
                            tiles_per_img, tiles_m, tiles_n);
     else
         hipLaunchKernelGGL(conv_halo_rows_kernel<0>, dim3(tiles_m * tiles_n), dim3(256), RowsCfg<0>::LDS_TOTAL, stream, a, tiles_x,
@@ -873,8 +798,7 @@ hipError_t launch_conv_halo_rows3(const ConvArgs& a, hipStream_t stream) {
         // long per MFMA with half tiles, comes from the Infinity Cache there, not from a warm L2) -- whole rollouts, same box, two runs each,
         // ms at 1 / 4 / 7 / 10 rows: short tiles for the upsample form only 8.90 / 14.69 / 20.20 / 26.37, for both forms 8.90 / 14.79 / 20.39 /
         // 26.68, four-row tiles only 9.09 / 14.85 / 20.28 / 26.46.  DYF_ROWS_TR_PLAIN=1 (or DYF_ROWS_TR) applies the rule here too.
-        const char* tpe = dyf_form("DYF_ROWS_TR_PLAIN");
-        const int tr = ((tpe && atoi(tpe) != 0) || dyf_form("DYF_ROWS_TR")) ? rows_tile_rows(sel, a.h) : 4;
+        const int tr = (dyf_form_int("DYF_ROWS_TR_PLAIN", 0) != 0 || dyf_form("DYF_ROWS_TR")) ? rows_tile_rows(sel, a.h) : 4;
         if (tr != 4) {
             const int tpi = tiles_x * (a.h / tr), tm = a.n * tpi;
             dyf_form_note(tr == 2 ? "conv_halo_rows_kernel<2>+tr2" : "conv_halo_rows_kernel<2>+tr1", a.n);

@@ -442,7 +442,6 @@ __global__ __launch_bounds__(256, 2) void conv_igemm2_kernel(ConvArgs a, int M, 
             dst[lane] = ac.x;
             dst[64 + lane] = ac.y;
         };
-        if (G.slots < 0) nslotsA = nslotsB = 0;  // timing experiment
         if (liveA) coefs(nA, nslotsA, gcf);
         if (cross) coefs(nA + 1, nslotsB, gcf + 128);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this wave's own table writes, read back below by its other lanes
@@ -664,16 +663,10 @@ hipError_t launch_conv_igemm2(const ConvArgs& a, hipStream_t stream) {
     // 256 x 128 tiles whenever cout allows.  Tried (round 3): 256 x 64 tiles when the large ones quantise badly on the 512 resident
     // workgroups -- the 15 x 15 level of the ResNet-UNet at 300 rows is 528 tiles = two rounds for 1.03 rounds of work, 1 056 small
     // tiles are three rounds of half the size -- but a small tile takes ~0.75 of a large one's time (every pixel fragment feeds half
-    // as many MFMAs): OISST rollout 675 -> 698 ms.  DYF_IGEMM2_BALANCE=1 re-enables the experiment.
-    const bool balance = dyf_form("DYF_IGEMM2_BALANCE") && atoi(dyf_form("DYF_IGEMM2_BALANCE")) != 0;
-    bool small = a.cout % 128 != 0;
-    if (!small && balance) {
-        const long long sel = a.n_sel > 0 ? ((long long)a.n_sel * a.ho * a.wo + BM - 1) / BM : tiles_m;
-        const long long tb = sel * (a.cout / 128), ts = sel * (a.cout / 64);
-        small = 0.56 * (double)((ts + 511) / 512) < 0.92 * (double)((tb + 511) / 512);
-    }
+    // as many MFMAs): OISST rollout 675 -> 698 ms.
+    const bool small = a.cout % 128 != 0;
     // SH3 (one gather per window row): 3x3 / stride 1 / pad 1 on row-major tiles (the kernel tiles 2-D when wo % 16 == 0 && ho % 16 == 0)
-    const bool sh3_on = !(dyf_form("DYF_IGEMM2_SH3") && atoi(dyf_form("DYF_IGEMM2_SH3")) == 0);  // (read per launch: tests compare the two forms)
+    const bool sh3_on = dyf_form_int("DYF_IGEMM2_SH3", 1) != 0;  // (read per launch: tests compare the two forms)
     const bool sh3 = sh3_on && a.kh == 3 && a.kw == 3 && a.stride == 1 && a.pad == 1 && a.ho == a.h && a.wo == a.w && a.wo >= 2 &&
                      !(a.wo % 16 == 0 && a.ho % TH == 0);
     if (a.gnf.gran != nullptr && a.gnf.bm == 128) {  // the 128-pixel tile form (launch_conv_gn_fused chose it and counted its slots)
@@ -694,14 +687,10 @@ hipError_t launch_conv_igemm2(const ConvArgs& a, hipStream_t stream) {
         dyf_form_note("conv_igemm2_kernel<2>+gn_fused", a.n);
         if (sh3) dyf_form_note("conv_igemm2_kernel+sh3", a.n);  // (a note of its own: the form log's kernel names stay those of the tile shape)
         const int tiles_n = a.cout / 128;
-        ConvArgs b = a;
-#ifdef DYF_EXPERIMENT_BUILD
-        if (dyf_form("DYF_GN_FUSE_NOWAIT")) b.gnf.slots = -1;  // timing experiment (WRONG results): no granule sweep
-#endif
         if (sh3)
-            hipLaunchKernelGGL((conv_igemm2_kernel<2, true, true>), dim3(tiles_m * tiles_n), dim3(256), LDS_TOTAL_SH3 + 4096, stream, b, (int)M, tiles_m, tiles_n);
+            hipLaunchKernelGGL((conv_igemm2_kernel<2, true, true>), dim3(tiles_m * tiles_n), dim3(256), LDS_TOTAL_SH3 + 4096, stream, a, (int)M, tiles_m, tiles_n);
         else
-            hipLaunchKernelGGL((conv_igemm2_kernel<2, true>), dim3(tiles_m * tiles_n), dim3(256), LDS_TOTAL + 4096, stream, b, (int)M, tiles_m, tiles_n);
+            hipLaunchKernelGGL((conv_igemm2_kernel<2, true>), dim3(tiles_m * tiles_n), dim3(256), LDS_TOTAL + 4096, stream, a, (int)M, tiles_m, tiles_n);
         return hipGetLastError();
     }
     dyf_form_note(small ? "conv_igemm2_kernel<1>" : "conv_igemm2_kernel<2>", a.n);

@@ -33,10 +33,6 @@
 #include <algorithm>
 #include <type_traits>
 #include <vector>
-#ifdef HALO_EXP_TIMELINE
-#include <cstdio>
-#include <string>
-#endif
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
 
@@ -89,14 +85,10 @@ struct HaloCfg {
     static constexpr int PER_WAVE = (INSTR + NWAVES - 1) / NWAVES;
     static constexpr bool HAS_TAB = SP != 5;            // per-thread halo source offsets parked in LDS
     static constexpr int TAB_END = HOFF_OFF + (HAS_TAB ? PER_WAVE * 1024 : 0);    // 53 760 / 65 024 / (SP 5) 79 360 B
-    // output staging of the stride-2 forms (-DHALO_NO_STAGE disables): per wave one pixel tile of [32 pixels][64 channels] 16-bit +
+    // output staging of the stride-2 forms: per wave one pixel tile of [32 pixels][64 channels] 16-bit +
     // 16 B pad per pixel -> whole 128-byte lines per store instruction (see conv_halo_rows.hip); the other forms run on the rows
     // kernels (SP 0-2) or have no LDS left (SP 5)
-#ifndef HALO_NO_STAGE
     static constexpr bool STAGE = SP == 3 || SP == 4;
-#else
-    static constexpr bool STAGE = false;
-#endif
     static constexpr int OROW = 144;
     static constexpr int LDS_TOTAL = TAB_END + (STAGE ? NWAVES * 32 * OROW : 0);  // SP 3 / 4: 72 192 B, two workgroups per CU
 };
@@ -109,13 +101,6 @@ struct HaloCfg {
 // OISST rollout 121.3 -> 114.7 us (300 rows), 51.7 -> 48.7 us (100 rows).
 // EPI = 2 (SP = 5 only): GroupNorm fused into this conv -- in-launch statistics exchange between the workgroups of a sample, then
 // normalise + FiLM + SiLU + dropout (+ residual) in the epilogue (gn_fused.h; ConvArgs::gnf).
-#ifdef HALO_EXP_TIMELINE  // experiment builds only (tools/build_variant.sh): per-wave shader-clock stamps at the phase boundaries of the EPI = 2 form
-__device__ unsigned long long g_halo_tl[1 << 18];
-#define TL_STAMP(K)                                                                                              \
-    if (EPI == 2 && blockIdx.x < 8192 && lane == 0) g_halo_tl[(blockIdx.x * 4 + wave) * 8 + (K)] = __builtin_amdgcn_s_memtime();
-#else
-#define TL_STAMP(K)
-#endif
 template <int SP, int EPI = 0>
 __global__ __launch_bounds__(256, 2) void conv_up_halo_kernel(ConvArgs a, int tiles_x, int tiles_per_img, int tiles_m,
                                                               int tiles_n, int xmode) {
@@ -132,7 +117,6 @@ __global__ __launch_bounds__(256, 2) void conv_up_halo_kernel(ConvArgs a, int ti
     const int l31 = lane & 31, hi = lane >> 5;
     const int wpy = wave >> 1, wpx = wave & 1;  // output phase of this wave
 
-    TL_STAMP(0)
     // XCD-aware tile id; the column blocks of one tile are consecutive (they share the halo in L2)
     const int total = tiles_m * tiles_n;
     const int bid = blockIdx.x;
@@ -227,9 +211,6 @@ __global__ __launch_bounds__(256, 2) void conv_up_halo_kernel(ConvArgs a, int ti
     }
 
     auto issue_halo = [&](int chunk) {
-#ifdef HALO_EXP_NO_HALO
-        if (a.n > 0) return;  // timing experiment (wrong results): no halo DMA
-#endif
         const int cb = H::S2 ? (chunk >> 2) << 6 : chunk << 6;
         const bool second = !H::S2 && cb >= a.c0;
         unsigned coff = (unsigned)((second ? cb - a.c0 : cb) * 2);
@@ -311,21 +292,9 @@ __global__ __launch_bounds__(256, 2) void conv_up_halo_kernel(ConvArgs a, int ti
 
     // weights of one (tap, chunk) step: WSTEP bytes, inside [ks][column tile][lane] x 16 B with KSS bytes per k16 sub-step
     constexpr unsigned WSTEP = SP == 5 ? 8192u : (unsigned)STEP_BYTES, KSS = SP == 5 ? 2048u : 4096u;
-// timing experiments (wrong results): -DHALO_EXP_W_ALIAS serves the weight stream from 16 KB (L1 hits), -DHALO_EXP_LDS_SKIP
-// drops the pixel-fragment reads of odd k16 sub-steps (half the LDS read traffic)
-#ifdef HALO_EXP_W_ALIAS
-#define W_ALIAS(x) ((x) & 0x3FFFu)
-#else
-#define W_ALIAS(x) (x)
-#endif
-#ifdef HALO_EXP_LDS_SKIP
-#define LDS_KEEP(KS) (((KS) & 1) == 0)
-#else
-#define LDS_KEEP(KS) true
-#endif
 #define ISSUE_B(SET, SOFF, KS)                                                                               \
     _Pragma("unroll") for (int nt = 0; nt < 2; ++nt)                                                         \
-        bq[SET][nt] = __builtin_amdgcn_raw_buffer_load_b128(rsrc_w, w_voff + nt * 1024, W_ALIAS((SOFF) + (KS) * KSS), 0);
+        bq[SET][nt] = __builtin_amdgcn_raw_buffer_load_b128(rsrc_w, w_voff + nt * 1024, (SOFF) + (KS) * KSS, 0);
 #define DSR(dst, addr) asm volatile("ds_read_b128 %0, %1" : "=v"(dst) : "v"(addr));
 #define LGKM_WAIT(N)                                                      \
     asm volatile("s_waitcnt lgkmcnt(" #N ")" ::: "memory");               \
@@ -346,7 +315,7 @@ __global__ __launch_bounds__(256, 2) void conv_up_halo_kernel(ConvArgs a, int ti
 #define RDA1(SET, KS, MT)                                                                                    \
     {                                                                                                        \
         const unsigned pm = (ax[MT] ^ (unsigned)((KS) << 5)) + ab[MT];                                       \
-        if (LDS_KEEP(KS)) DSR(aq[SET][MT], pm)                                                               \
+        DSR(aq[SET][MT], pm)                                                                                 \
     }
 #define MF(NT, MT, ASET, BSET)                                                                               \
     acc[NT][MT] = DYF_MFMA_32x32x16(__builtin_bit_cast(el16x8_t, bq[BSET][NT]), aq[ASET][MT], \
@@ -386,22 +355,17 @@ __global__ __launch_bounds__(256, 2) void conv_up_halo_kernel(ConvArgs a, int ti
     // (pinned in program order: the compiler otherwise issues the oldest set LAST, and its own s_waitcnt at the loop head --
     // merged over the entry edge and the back edge -- becomes vmcnt(2) in the first sub-step of EVERY chunk: a full drain of
     // the weight ring and of the halo DMA just requested for the next chunk, i.e. no double buffering at all)
-#ifndef HALO_NO_PREPIN
-#define PPIN PIN
-#else
-#define PPIN
-#endif
-    PPIN
+    PIN
     if (H::S2) {
-        ISSUE_B(0, soff_cur, 0) PPIN
-        ISSUE_B(1, soff_cur, 1) PPIN
-        ISSUE_B(2, soff_cur, 2) PPIN
+        ISSUE_B(0, soff_cur, 0) PIN
+        ISSUE_B(1, soff_cur, 1) PIN
+        ISSUE_B(2, soff_cur, 2) PIN
     } else {
-        ISSUE_B(0, soff_c, 0) PPIN
-        ISSUE_B(1, soff_c, 1) PPIN
-        ISSUE_B(2, soff_c, 2) PPIN
-        ISSUE_B(3, soff_c, 3) PPIN
-        ISSUE_B(4, soff_c + WSTEP, 0) PPIN
+        ISSUE_B(0, soff_c, 0) PIN
+        ISSUE_B(1, soff_c, 1) PIN
+        ISSUE_B(2, soff_c, 2) PIN
+        ISSUE_B(3, soff_c, 3) PIN
+        ISSUE_B(4, soff_c + WSTEP, 0) PIN
     }
     for (int chunk = 0; chunk < cpt; ++chunk) {
         if (H::NBUF == 2) {
@@ -418,7 +382,6 @@ __global__ __launch_bounds__(256, 2) void conv_up_halo_kernel(ConvArgs a, int ti
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();
             __builtin_amdgcn_sched_barrier(0);
-            if (chunk == 0) { TL_STAMP(1) }
         }
         const unsigned Hs = lds_base + (H::NBUF == 2 ? (chunk & 1) * HALO_BYTES : 0);
         asm volatile("" : "+v"(hp0));  // keep the per-tap LDS addresses from being hoisted out of the chunk loop
@@ -495,19 +458,6 @@ __global__ __launch_bounds__(256, 2) void conv_up_halo_kernel(ConvArgs a, int ti
 #undef DSR
 #undef ISSUE_B
 
-#ifdef HALO_EXP_NO_EPI
-    if (a.n > 0) {  // timing experiment (wrong results): no epilogue; the accumulators stay live through an impossible store
-        float sacc = 0.0f;
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-            for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) sacc += acc[nt][mt][r];
-        if (sacc == 12345.678f) a.out_el16[0] = 1;
-        return;
-    }
-#endif
     // ---- epilogue straight from the accumulators.  Lane (l31, hi) of tile (nt, mt) holds pixel l31 of pixel tile mt and
     // channels half*32 + 8*g + 4*hi + {0..3} (g = register group r >> 2).  Groups 2*g2 and 2*g2+1 are packed to bf16 and
     // exchanged between lanes l and l+32 (v_permlane32_swap), after which every lane owns 8 consecutive channels = 16 B.
@@ -530,7 +480,6 @@ __global__ __launch_bounds__(256, 2) void conv_up_halo_kernel(ConvArgs a, int ti
                            : o0;
     const uint32_t smt_stride = SP == 1 ? (uint32_t)(4 * a.up_wo_store * a.cout) : mt_stride;
     if constexpr (EPI == 2) {
-        TL_STAMP(2)
         // ---- GroupNorm fused (gn_fused.h).  Phase A: (sum, sum of squares) of y = acc + bias per 8-channel octet over this wave's
         // 128 pixels (pixels beyond a ragged plane masked by a 0 / 1 factor), reduce-scatter butterfly, 16 granules per wave.
         const GnFuse& G = a.gnf;
@@ -590,7 +539,6 @@ __global__ __launch_bounds__(256, 2) void conv_up_halo_kernel(ConvArgs a, int ti
             }
         };
         if (has_res) load_res(0, 0, rq[0]);
-        TL_STAMP(3)
         // Phase B: wave 0 sweeps the sample's granules and parks (A, C) of the block's 64 channels in LDS (its own 512 bytes behind
         // the halo: the other waves may still be in their K loop)
         float* cfA = (float*)(smem + H::LDS_TOTAL);
@@ -603,10 +551,8 @@ __global__ __launch_bounds__(256, 2) void conv_up_halo_kernel(ConvArgs a, int ti
             const float2 ac = gn_fuse_coef(G, ch_blk + lane, a.coef_div > 1 ? n_img / a.coef_div : n_img, mr);
             cfA[lane] = ac.x;
             cfC[lane] = ac.y;
-            TL_STAMP(6)
         }
         __syncthreads();
-        TL_STAMP(4)
         // Phase C: y * A + C -> SiLU -> dropout -> (+ residual) -> 16-bit, stored as the plain epilogue stores
         auto fused = [&](auto mode_c) {
             constexpr int MODE = decltype(mode_c)::value;
@@ -656,7 +602,6 @@ __global__ __launch_bounds__(256, 2) void conv_up_halo_kernel(ConvArgs a, int ti
         };
         if (a.drop.mode == 1) fused(std::integral_constant<int, 1>{});
         else fused(std::integral_constant<int, 0>{});
-        TL_STAMP(5)
         return;
     }
     // (activation, dropout mode) are wave-uniform: the whole epilogue is instantiated per pair and dispatched once
@@ -708,11 +653,7 @@ __global__ __launch_bounds__(256, 2) void conv_up_halo_kernel(ConvArgs a, int ti
                 for (int k = 0; k < 4; ++k) {
                     const int px = 8 * k + rpx;
                     const uint4 o = *(const uint4*)(ost + px * H::OROW + rch * 16);
-#ifdef DYF_NT_STORES  // experiment: non-temporal stores
-                    __builtin_nontemporal_store(__builtin_bit_cast(u32x4, o), (u32x4*)(a.out_el16 + (size_t)(tile_base + mt * mt_stride + (uint32_t)((px >> 4) * a.wo + (px & 15)) * (uint32_t)a.cout + rch * 8)));
-#else
                     *(uint4*)(a.out_el16 + (size_t)(tile_base + mt * mt_stride + (uint32_t)((px >> 4) * a.wo + (px & 15)) * (uint32_t)a.cout + rch * 8)) = o;
-#endif
                 }
             }
             return;
@@ -735,96 +676,6 @@ __global__ __launch_bounds__(256, 2) void conv_up_halo_kernel(ConvArgs a, int ti
                 k4c[o] = *(const float4*)(a.coef_c + ci_base + (o >> 2) * 32 + 8 * (o & 3));
             }
         }
-#ifdef H5_LEAN  // EXPERIMENT, measured slower and off (see the end of this comment)
-        // SP = 5 without activation / dropout (every conv of the ResNet-UNet that feeds a GroupNorm, and its plain 3x3 convs):
-        // y = acc * A + C is formed ONCE, in place, with packed fp32 math (a lane's channel pairs are register pairs), octet by octet
-        // with the octet's coefficients loaded there (all 16 loads up front spilled); pixels outside a ragged plane are zeroed (they
-        // are not stored and then add nothing to the sums); the sums of the octet follow at once, the store loop reads y.
-        // PMC had counted 2 461 vector instructions per wave against 384 MFMAs, ~1 100 of them in this epilogue (y formed twice --
-        // once per pass, behind an opaque copy that kept the two passes apart --, masked scalar sums, register copies).
-        // Measured (level-0 64 -> 64 convs of the OISST rollout, 300 rows): 116.5 us without it, 152 us with it (228 us in its first
-        // form with the 16 coefficient loads up front): the kernel already sits at 256 registers with 5 spill slots; in the full
-        // kernel (all activation x dropout epilogues instantiated) this path comes out with 52-199 spill slots -- ~230 MB of scratch
-        // traffic per launch -- although it allocates 250 registers and no spill when it is the only epilogue (PLAIN_EPI; there: 119.8 us against 114.7 us).  The
-        // instruction count does drop (epilogue ~930 -> ~620 VALU per wave); what it needs is register headroom first.
-        if constexpr (STATS) {
-            typedef float f32x2 __attribute__((ext_vector_type(2)));
-            f32x2 m2[4];
-#pragma unroll
-            for (int mt = 0; mt < 4; ++mt) {
-                const float m = (lane_valid && orow0 + 2 * mt < a.ho) ? 1.0f : 0.0f;
-                m2[mt] = f32x2{m, m};
-            }
-            const bool stats = a.gn_part != nullptr;
-            float w[16];
-#pragma unroll
-            for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const float4 ka = *(const float4*)(a.coef_a + ci_base + nt * 32 + 8 * g), kc = *(const float4*)(a.coef_c + ci_base + nt * 32 + 8 * g);
-                    const f32x2 k01 = {ka.x, ka.y}, k23 = {ka.z, ka.w}, c01 = {kc.x, kc.y}, c23 = {kc.z, kc.w};
-                    f32x2 s1a = {0.0f, 0.0f}, s1b = {0.0f, 0.0f}, s2a = {0.0f, 0.0f}, s2b = {0.0f, 0.0f};  // two chains each: packed ops have latency
-#pragma unroll
-                    for (int mt = 0; mt < 4; ++mt) {
-                        f32x2 y01 = {acc[nt][mt][4 * g + 0], acc[nt][mt][4 * g + 1]}, y23 = {acc[nt][mt][4 * g + 2], acc[nt][mt][4 * g + 3]};
-                        y01 = (y01 * k01 + c01) * m2[mt];
-                        y23 = (y23 * k23 + c23) * m2[mt];
-                        acc[nt][mt][4 * g + 0] = y01.x; acc[nt][mt][4 * g + 1] = y01.y;
-                        acc[nt][mt][4 * g + 2] = y23.x; acc[nt][mt][4 * g + 3] = y23.y;
-                        s1a += y01;
-                        s1b += y23;
-                        s2a = y01 * y01 + s2a;
-                        s2b = y23 * y23 + s2b;
-                    }
-                    s1a += s1b;
-                    s2a += s2b;
-                    w[2 * (4 * nt + g)] = s1a.x + s1a.y;
-                    w[2 * (4 * nt + g) + 1] = s2a.x + s2a.y;
-                    __builtin_amdgcn_sched_barrier(0);  // octet by octet: hoisted together the 64 packed products got fresh registers and spilled
-                }
-            if (stats) {
-                // wave reduction: the reduce-scatter butterfly of the general path below
-#pragma unroll
-                for (int half = 8, d = 1; half >= 1; half >>= 1, d <<= 1) {
-                    const bool up = (lane & d) != 0;
-#pragma unroll
-                    for (int j = 0; j < half; ++j) {
-                        const float send = up ? w[j] : w[j + half];
-                        const float keep = up ? w[j + half] : w[j];
-                        w[j] = keep + __shfl_xor(send, d, 64);
-                    }
-                }
-                float tot = w[0];
-                tot += __shfl_xor(tot, 16, 64);
-                tot += __shfl_xor(tot, 32, 64);
-                if (lane < 16) {
-                    const int idx = 8 * (lane & 1) + 4 * ((lane >> 1) & 1) + 2 * ((lane >> 2) & 1) + ((lane >> 3) & 1);
-                    const int slot = t_in * NWAVES + wave;
-                    a.gn_part[((size_t)(n_img * a.gn_slots + slot) * (a.cout >> 3) + tn * 8) * 2 + idx] = tot;
-                }
-            }
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-                for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-                    for (int g2 = 0; g2 < 2; ++g2) {
-                        const uint32_t p0 = pack_el16x2(acc[nt][mt][8 * g2 + 0], acc[nt][mt][8 * g2 + 1]), p1 = pack_el16x2(acc[nt][mt][8 * g2 + 2], acc[nt][mt][8 * g2 + 3]);
-                        const uint32_t q0 = pack_el16x2(acc[nt][mt][8 * g2 + 4], acc[nt][mt][8 * g2 + 5]), q1 = pack_el16x2(acc[nt][mt][8 * g2 + 6], acc[nt][mt][8 * g2 + 7]);
-                        const auto s0 = __builtin_amdgcn_permlane32_swap(p0, q0, false, false);
-                        const auto s1 = __builtin_amdgcn_permlane32_swap(p1, q1, false, false);
-                        uint4 o;
-                        o.x = s0[0]; o.y = s1[0]; o.z = s0[1]; o.w = s1[1];
-                        const uint32_t sbase = store0 + mt * smt_stride + nt * 32 + 16 * g2;
-#ifdef HALO_EXP_NO_STORE
-                        if (a.n < 0)
-#endif
-                        if (lane_valid && orow0 + 2 * mt < a.ho) *(uint4*)(a.out_el16 + (size_t)(sbase + 8 * hi)) = o;
-                    }
-            return;
-        }
-#endif
         if constexpr (STATS) if (a.gn_part != nullptr) {
             float mval[4];
 #pragma unroll
@@ -915,9 +766,6 @@ __global__ __launch_bounds__(256, 2) void conv_up_halo_kernel(ConvArgs a, int ti
                     uint4 o;
                     o.x = s0[0]; o.y = s1[0]; o.z = s0[1]; o.w = s1[1];
                     const uint32_t sbase = store0 + mt * smt_stride + cg0;
-#ifdef HALO_EXP_NO_STORE
-                    if (a.n < 0)  // timing experiment (wrong results): the epilogue computes, nothing is stored
-#endif
                     if ((SP != 1 && SP != 5) || (lane_valid && (SP != 5 || orow0 + 2 * mt < a.ho)))
                         *(uint4*)(a.out_el16 + (size_t)(sbase + 8 * hi)) = o;
                 }
@@ -1077,31 +925,10 @@ hipError_t launch_conv_halo5(const ConvArgs& a, hipStream_t stream) {
     const int tiles_m = a.n * tiles_per_img, tiles_n = a.cout / 64;
     dyf_form_note(a.gnf.gran ? "conv_up_halo_kernel<5>+gn_fused" : "conv_up_halo_kernel<5>", a.n);
     if (a.up_nearest) dyf_form_note("conv_up_halo_kernel<5>+nearest_up", a.n);
-    const bool plain_epi = !(dyf_form("DYF_HALO5_PLAIN_EPI") && atoi(dyf_form("DYF_HALO5_PLAIN_EPI")) == 0);
+    const bool plain_epi = dyf_form_int("DYF_HALO5_PLAIN_EPI", 1) != 0;
     if (a.gnf.gran != nullptr) {  // GroupNorm fused: + 1 KB of LDS for the per-channel (A, C) table
-        ConvArgs b = a;
-#ifdef DYF_EXPERIMENT_BUILD
-        if (dyf_form("DYF_GN_FUSE_NOWAIT")) b.gnf.slots = 0;  // timing experiment (WRONG results): no granule sweep
-#endif
-        hipLaunchKernelGGL((conv_up_halo_kernel<5, 2>), dim3(tiles_m * tiles_n), dim3(256), H5::LDS_TOTAL + 1024, stream, b, tiles_x,
+        hipLaunchKernelGGL((conv_up_halo_kernel<5, 2>), dim3(tiles_m * tiles_n), dim3(256), H5::LDS_TOTAL + 1024, stream, a, tiles_x,
                            tiles_per_img, tiles_m, tiles_n, 0);
-#ifdef HALO_EXP_TIMELINE
-        if (const char* tl = dyf_form("DYF_TIMELINE_DUMP")) {  // "path:N": the stamps of the N-th fused launch of the process (eager launches only)
-            static int count = 0;
-            const char* colon = strrchr(tl, ':');
-            if (colon && ++count == atoi(colon + 1)) {
-                (void)hipStreamSynchronize(stream);
-                std::vector<unsigned long long> h((size_t)1 << 18);
-                (void)hipMemcpyFromSymbol(h.data(), HIP_SYMBOL(g_halo_tl), h.size() * 8);
-                if (FILE* f = fopen(std::string(tl, colon - tl).c_str(), "wb")) {
-                    const int hdr[4] = {tiles_m * tiles_n, a.n, a.residual != nullptr, a.drop.mode};
-                    fwrite(hdr, sizeof(int), 4, f);
-                    fwrite(h.data(), 8, (size_t)std::min(tiles_m * tiles_n, 8192) * 32, f);
-                    fclose(f);
-                }
-            }
-        }
-#endif
     }
     else if (plain_epi && a.act == ACT_NONE && a.drop.mode == 0)
         hipLaunchKernelGGL((conv_up_halo_kernel<5, 1>), dim3(tiles_m * tiles_n), dim3(256), H5::LDS_TOTAL, stream, a, tiles_x,
@@ -1574,14 +1401,12 @@ hipError_t launch_conv_up_halo(const ConvArgs& a, hipStream_t stream) {
         // few rows: the K-split form (one sample per workgroup instead of eight: 8 x as many, 8 waves each -- past ~40 rows the form
         // above, whose workgroups already fill the chip, does the same sums with less LDS traffic).  DYF_UP_BORDER_SPLIT_ROWS
         // moves the switch (0 = never); the form is chosen for ConvArgs::n_sel rows when the engine pins the forms (batch_invariant)
-        const char* sre = dyf_form("DYF_UP_BORDER_SPLIT_ROWS");  // read per launch (parity tests)
-        const int split_rows = sre ? atoi(sre) : 40;
+        const long long split_rows = dyf_form_int("DYF_UP_BORDER_SPLIT_ROWS", 40);  // read per launch (parity tests)
         // EXPERIMENT, off by default (DYF_UP_BORDER_RING4=1 enables; read per launch): the four-slot ring without the K split for many
         // rows.  Measured SLOWER than the two-slot kernel where it would apply: NS at 80 rows 8 784-8 804 against 8 843-8 851 fields/s
         // (three runs each, same box), dec3 / dec4 / dec5 at 80 rows 306.6 / 568.7 / 527.9 against 293.8 / 560.9 / 523.7 us -- with
         // 480-1 440 workgroups the chip is full either way and the ring's 64 KB of LDS per workgroup halves the resident ones.
-        const char* r4e = dyf_form("DYF_UP_BORDER_RING4");
-        const bool ring4 = r4e && atoi(r4e) != 0;
+        const bool ring4 = dyf_form_int("DYF_UP_BORDER_RING4", 0) != 0;
         if ((a.n_sel > 0 ? a.n_sel : a.n) <= split_rows) {
             dyf_form_note("up_border_split_kernel", a.n);
             hipLaunchKernelGGL((up_border_split_kernel<UB_SPLIT_NW, true>), dim3(4 * tr + 4 * tc + 4, a.n, a.cout / 64), dim3(UB_SPLIT_NW * 64),
@@ -1596,7 +1421,7 @@ hipError_t launch_conv_up_halo(const ConvArgs& a, hipStream_t stream) {
     const bool sparse = a.up_cols != nullptr;
     // rows form (conv_halo_rows.hip: one-row pixel tiles, half the LDS fragment reads) where the plane tiles by 4 x 32;
     // DYF_HALO_ROWS=0 keeps this file's kernels.  The sparse lists are planned for one form or the other (32 / 16 slots).
-    const bool rows = !(dyf_form("DYF_HALO_ROWS") && atoi(dyf_form("DYF_HALO_ROWS")) == 0);
+    const bool rows = dyf_form_int("DYF_HALO_ROWS", 1) != 0;
     if (sparse ? ((a.up_mix[0] | a.up_mix[1] | a.up_mix[2]) != 0 || a.up_npad != a.up_ntiles * 16) : (rows && conv_halo_rows_up_supported(a)))
         return launch_conv_halo_rows_up(a, stream);
     const int tiles_x = sparse ? a.up_ntiles : a.w / TILE_W, tiles_per_img = tiles_x * (a.h / TILE_H);
@@ -1609,7 +1434,7 @@ hipError_t launch_conv_up_halo(const ConvArgs& a, hipStream_t stream) {
         // DYF_HALO_TN_XCD=1: one column block per XCD (measured on dec4 at NB=80: HBM-side reads 722 -> 513 MB because the
         // weights stay in L2, but the two column blocks of a tile read their halo on different XCDs; time 649 -> 663 us,
         // whole rollout unchanged -- the extra reads of the default mapping are served by the Infinity Cache).  Off by default.
-        const int xenv = dyf_form("DYF_HALO_TN_XCD") ? atoi(dyf_form("DYF_HALO_TN_XCD")) : 0;
+        const long long xenv = dyf_form_int("DYF_HALO_TN_XCD", 0);
         const bool xmode = (xenv & 1) != 0 && (tiles_n == 2 || tiles_n == 4 || tiles_n == 8);
         const int groups = xmode ? 8 / tiles_n : 1, chunk = (tiles_m + groups - 1) / groups;
         const unsigned grid = xmode ? (unsigned)(8 * chunk) : (unsigned)(tiles_m * tiles_n);

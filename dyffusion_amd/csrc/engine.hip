@@ -177,7 +177,7 @@ dyf_status net_forward(dyf_engine* e, int which, const Source* srcs, int nsrc, i
     // a forward that draws masks starts by filling the row-key table and advancing the forward counter: a one-block kernel of its
     // own, or -- fused stem, no dropout inside the stem -- block 0 of the stem launch (kernels.hip stem_rng_begin)
     const bool draws = o.dropout_mode == 1 && (n.cfg.dropout > 0.0f || n.cfg.input_dropout > 0.0f);
-    const bool fold_rng = !(dyf_form("DYF_FOLD_RNG_BEGIN") && atoi(dyf_form("DYF_FOLD_RNG_BEGIN")) == 0);
+    const bool fold_rng = dyf_form_int("DYF_FOLD_RNG_BEGIN", 1) != 0;
     const bool rng_in_stem = draws && fold_rng && n.stem_fused && e->cfg.enable_mfma && e->fuse_stem && n.cfg.input_dropout == 0.0f;
     if (draws && !rng_in_stem)
         HIP_TRY(e, launch_rng_begin_forward(e->rng_state, e->row_keys, nb, o.src_rows > 0 ? o.src_rows : nb, st));
@@ -272,7 +272,7 @@ dyf_status net_forward(dyf_engine* e, int which, const Source* srcs, int nsrc, i
         // 1 x 1 decoder blocks (dec0, dec1): the pointwise conv commutes with the per-channel bilinear upsample, so it runs on the
         // LOW-res cat[x, skip] (a quarter of the pixels, nothing materialised) into fp32 and one pass upsamples + applies the block's
         // epilogue (kernels.h Up2xEpiArgs); DYF_DEC_COMMUTE=0 keeps upsample -> conv
-        const bool commute = !(dyf_form("DYF_DEC_COMMUTE") && atoi(dyf_form("DYF_DEC_COMMUTE")) == 0);
+        const bool commute = dyf_form_int("DYF_DEC_COMMUTE", 1) != 0;
         const bool commuted = commute && b.k == 1 && b.stride == 1 && b.pad == 0 && e->cfg.enable_mfma && (b.cout & 3) == 0 &&
                               (size_t)nb * lh * lw * b.cout * sizeof(float) <= (size_t)nb * b.in_h * b.in_w * b.cin * sizeof(el16_t);
         if (use_fused_up(e, b, f)) {
@@ -412,11 +412,11 @@ dyf_status dyf_engine_create(const dyf_engine_config* cfg, dyf_engine** out_engi
 
     dyf_engine* e = new dyf_engine();
     e->cfg = *cfg;
-    if (const char* fu = dyf_form("DYF_FUSE_UP2X")) e->fuse_up2x = atoi(fu) != 0;
-    if (const char* fm = dyf_form("DYF_FUSE_MIN_PLANE")) e->fuse_min_plane = atoi(fm);
-    if (const char* fs = dyf_form("DYF_FUSE_STEM")) e->fuse_stem = atoi(fs) != 0;
-    if (const char* pi = dyf_form("DYF_PAIR_INTERP")) e->pair_interp = atoi(pi) != 0;
-    if (const char* pz = dyf_form("DYF_POISON_DEC5")) e->poison_dec5 = atoi(pz) != 0;
+    e->fuse_up2x = dyf_form_int("DYF_FUSE_UP2X", e->fuse_up2x) != 0;
+    e->fuse_min_plane = (int)dyf_form_int("DYF_FUSE_MIN_PLANE", e->fuse_min_plane);
+    e->fuse_stem = dyf_form_int("DYF_FUSE_STEM", e->fuse_stem) != 0;
+    e->pair_interp = dyf_form_int("DYF_PAIR_INTERP", e->pair_interp) != 0;
+    e->poison_dec5 = dyf_form_int("DYF_POISON_DEC5", e->poison_dec5) != 0;
     if (conv_init() != hipSuccess || linattn_fused_init() != hipSuccess || hipStreamCreateWithFlags(&e->cap_stream, hipStreamNonBlocking) != hipSuccess) {
         delete e;
         return fail(nullptr, DYF_ERR_HIP, "engine initialisation failed (conv_init / stream create)");
@@ -523,20 +523,18 @@ dyf_status dyf_engine_create(const dyf_engine_config* cfg, dyf_engine** out_engi
         if (hipHostGetDevicePointer((void**)&e->gn_err_dev, e->gn_err_host, 0) != hipSuccess) e->gn_err_dev = nullptr;
     }
     if (!e->gn_err_dev) e->gn_fuse_disabled = true;  // no way to report a timed-out sweep: keep to the three-kernel path
-    if (const char* gf = dyf_form("DYF_GN_FUSED")) if (atoi(gf) == 0) e->gn_fuse_disabled = true;
+    if (dyf_form_int("DYF_GN_FUSED", 1) == 0) e->gn_fuse_disabled = true;
     {
         dyf_status rs = rn_alloc_workspace(e);
         if (rs != DYF_OK) return bail(rs, e->err);
         rs = sc_alloc_workspace(e);
         if (rs != DYF_OK) return bail(rs, e->err);
     }
-    if (const char* gm = dyf_form("DYF_GROUP_MIN_ROWS")) e->group_min_rows = std::max(1, atoi(gm));
+    e->group_min_rows = (int)std::max(1LL, dyf_form_int("DYF_GROUP_MIN_ROWS", e->group_min_rows));
     *out_engine = e;
     if (!g_creating_group_child) {
         // default: DYF_ROW_GROUPS, else by architecture (measured on the ResNet-UNet shapes)
-        int g = 1;
-        if (const char* rg = dyf_form("DYF_ROW_GROUPS")) g = atoi(rg);
-        else g = default_row_groups(e);
+        const int g = (int)dyf_form_int("DYF_ROW_GROUPS", default_row_groups(e));
         if (g > 1) {
             dyf_status gs = dyf_set_row_groups(e, g);
             if (gs != DYF_OK) {
@@ -578,8 +576,7 @@ dyf_status dyf_set_row_groups(dyf_engine* e, int32_t n_groups) {
         c->is_group_child = true;
         // kernel forms of a group's launches are chosen by the tile count of all n_groups concurrent launches (OISST 300 rows:
         // 3 680 -> 3 750 fields/s; the 100-row shares otherwise fall below the tile thresholds of the large-batch forms)
-        c->form_rows_scale = n_groups;
-        if (const char* fs = dyf_form("DYF_GROUP_FORM_SCALE")) c->form_rows_scale = atoi(fs) != 0 ? n_groups : 1;
+        c->form_rows_scale = dyf_form_int("DYF_GROUP_FORM_SCALE", 1) != 0 ? n_groups : 1;
         e->groups.push_back(c);
         if (hipStreamCreateWithFlags(&c->group_stream, hipStreamNonBlocking) != hipSuccess ||
             hipEventCreateWithFlags(&c->group_done, hipEventDisableTiming) != hipSuccess) {
@@ -761,7 +758,7 @@ static dyf_status load_weights_one(dyf_engine* e, int32_t which, int32_t n_tenso
             // The readout (sparse transposed conv + final resample, readout kernels in kernels.hip) reads only the columns
             // of the last decoder block that the final bilinear interpolation touches: for the NS grid (42 native columns
             // from a 512-wide transposed-conv output) 104 of 256.  Plan the column lists of the sparse halo form.
-            const bool sparse_ok = !(dyf_form("DYF_SPARSE_DEC5") && atoi(dyf_form("DYF_SPARSE_DEC5")) == 0);  // read per upload
+            const bool sparse_ok = dyf_form_int("DYF_SPARSE_DEC5", 1) != 0;  // read per upload
             if (i == 11 && b.wpk_up_frag && sparse_ok) {
                 const int iw = b.out_w, tw = 2 * iw, ow = e->cfg.width;
                 std::vector<uint8_t> needed(iw, 0);
@@ -784,12 +781,12 @@ static dyf_status load_weights_one(dyf_engine* e, int32_t which, int32_t n_tenso
                 int nt = 0, nv0 = 0, nv1 = 0;
                 // the compact tensor is read by the MFMA form of the readout only (dim 64, <= 4 output channels)
                 // list tiles of 32 slots for the rows form of the halo kernel (conv_halo_rows.hip), 16 for conv_up_halo_kernel<1>
-                const bool rows_env = !(dyf_form("DYF_HALO_ROWS") && atoi(dyf_form("DYF_HALO_ROWS")) == 0);
+                const bool rows_env = dyf_form_int("DYF_HALO_ROWS", 1) != 0;
                 int slots = rows_env && (b.out_h / 2) % 4 == 0 ? conv_halo_rows_slots() : 16;
                 bool planned = false;
                 int mix[3] = {0, 0, 0};
                 // mixed list tiling (no padded MFMA lanes: 52 entries = 3 x 16 + 4) first; DYF_SPARSE_MIXED=0: uniform tiles only
-                const bool mixed_env = !(dyf_form("DYF_SPARSE_MIXED") && atoi(dyf_form("DYF_SPARSE_MIXED")) == 0);
+                const bool mixed_env = dyf_form_int("DYF_SPARSE_MIXED", 1) != 0;
                 if (n.dim == 64 && n.cfg.out_channels <= 4 && mixed_env && slots == conv_halo_rows_slots() &&
                     plan_up_sparse_columns_mixed(needed, iw / 2, b.out_h / 2, cols, cbase, cidx, cmap, mix, nv0, nv1)) {
                     planned = true;
@@ -1357,7 +1354,7 @@ dyf_status run_plan(dyf_engine* e, int nb, const uint8_t* const* masks, const fl
     // straight into the contiguous [k][nb][C][H][W] block of the forecast stack.  k is bounded by the workspace (2 max_batch rows):
     // an engine created for 80 rows refines a 10-row call in one 150-row launch instead of eight 20-row ones (the small-batch /
     // ensemble-sharded regime); at nb = max_batch it is the pair it always was.  DYF_REFINE_BATCH caps k.
-    const int refine_cap = dyf_form("DYF_REFINE_BATCH") ? std::max(1, atoi(dyf_form("DYF_REFINE_BATCH"))) : 1 << 20;  // read per capture
+    const int refine_cap = (int)std::max(1LL, dyf_form_int("DYF_REFINE_BATCH", 1 << 20));  // read per capture
     const int kmax = can_pair ? std::max(1, std::min(refine_cap, 2 * e->cfg.max_batch / nb)) : 1;
     for (size_t r = 0; r < ph.refine_times.size();) {
         size_t k = 1;

@@ -70,9 +70,7 @@ __device__ __forceinline__ double gn_shfl_xor_f64(double v, int d) {
 // Bounded by TIME (s_memrealtime: a constant 100 MHz counter), not by passes: under time-slicing (two processes on one GPU) a sweep
 // can legitimately take milliseconds; 2 s without a match is a dead launch.  The clock and the error word (another sweep of this
 // engine already gave up: do not queue 2 s behind every later conv of the rollout) are looked at every 1 024 passes.
-#ifndef GN_FUSE_TIMEOUT_TICKS
-#define GN_FUSE_TIMEOUT_TICKS 200000000ull
-#endif
+constexpr unsigned long long GN_FUSE_TIMEOUT_TICKS = 200000000ull;
 template <int MAXJ>
 __device__ __forceinline__ float2 gn_fuse_sweep(const unsigned long long* base, int slot_stride, int nslots, uint32_t tag, int cpg,
                                                double inv_count, uint32_t* err, int lane, uint32_t timeout_ticks = 0) {

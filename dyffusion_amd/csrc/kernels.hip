@@ -413,8 +413,8 @@ __global__ __launch_bounds__(512) void stem16_rows_kernel(StemArgs a, int nblk) 
 hipError_t launch_stem16(const StemArgs& a, hipStream_t s) {
     const int cp = (a.cin + 3) / 4 * 4;  // cin <= 15 (the fused stem's bias channel is slot cin)
     const size_t lds = (size_t)(ST_ROWS + 2) * a.w * cp * sizeof(float) + (size_t)(a.uw + 2 + ST_ROWS) * 16 + 8 * 2048;  // rows + stencil tables + per-wave output tiles
-    const char* env = dyf_form("DYF_STEM16_ROWS");  // read per launch: the parity test flips it
-    if (!(env && atoi(env) == 0) && lds <= 48 * 1024 && cp <= 16 && a.h <= a.uh && 2 * (a.uw + 2) >= 512) {
+    const bool rows = dyf_form_int("DYF_STEM16_ROWS", 1) != 0;  // read per launch: the parity test flips it
+    if (rows && lds <= 48 * 1024 && cp <= 16 && a.h <= a.uh && 2 * (a.uw + 2) >= 512) {
         const int nblk = (a.uh + 2 + ST_ROWS - 1) / ST_ROWS;
         const dim3 grid((unsigned)(a.n * nblk)), block(512);
         dyf_form_note("stem16_rows_kernel", a.n);
@@ -568,8 +568,8 @@ hipError_t launch_up2x(const Up2xArgs& a, hipStream_t s) {
     const bool vec = (a.c0 % 8 == 0) && (a.c1 % 8 == 0);
     const long long total = (long long)a.n * 4 * a.h * a.w * (vec ? c / 8 : c);
     const unsigned blocks = (unsigned)((total + 255) / 256);
-    const char* env = dyf_form("DYF_UP2X_QUAD");  // read per launch (parity test)
-    if (vec && !(env && atoi(env) == 0) && a.h >= 2 && a.w >= 2) {
+    const bool quad = dyf_form_int("DYF_UP2X_QUAD", 1) != 0;  // read per launch (parity test)
+    if (vec && quad && a.h >= 2 && a.w >= 2) {
         const long long quads = total / 4;
         dyf_form_note("up2x_quad_kernel", a.n);
         KernelProf kp("up2x_quad_kernel", s, (double)a.n * a.h * a.w * c * 2.0 * 5.0);  // read once, write 4x
@@ -728,8 +728,8 @@ __global__ __launch_bounds__(256) void groupnorm_wave_kernel(GroupNormArgs a) {
 
 hipError_t launch_groupnorm(const GroupNormArgs& a, hipStream_t s) {
     const int cpg = a.groups > 0 ? a.c / a.groups : 0;
-    const char* we = dyf_form("DYF_GN_WAVE");  // read per launch (parity test)
-    if (!(we && atoi(we) == 0) && cpg > 0 && cpg * a.groups == a.c && (cpg & 3) == 0 && a.act != ACT_GELU &&
+    const bool wave = dyf_form_int("DYF_GN_WAVE", 1) != 0;  // read per launch (parity test)
+    if (wave && cpg > 0 && cpg * a.groups == a.c && (cpg & 3) == 0 && a.act != ACT_GELU &&
         (size_t)a.n * a.hw * a.c < 0xFFFFFFF0ull) {
         const int pieces = a.hw * (cpg >> 2);
         const unsigned blocks = (unsigned)((a.n * a.groups + 3) / 4);
@@ -1269,8 +1269,8 @@ __global__ __launch_bounds__(256, 4) void readout_dma_kernel(ReadoutArgs a, int 
 
 hipError_t launch_readout(const ReadoutArgs& a, hipStream_t s) {
     const long long total = (long long)a.n * a.oh * a.ow;
-    const bool regw = !(dyf_form("DYF_READOUT_REGW") && atoi(dyf_form("DYF_READOUT_REGW")) == 0);
-    const bool use_mfma = !(dyf_form("DYF_READOUT_MFMA") && atoi(dyf_form("DYF_READOUT_MFMA")) == 0);
+    const bool regw = dyf_form_int("DYF_READOUT_REGW", 1) != 0;
+    const bool use_mfma = dyf_form_int("DYF_READOUT_MFMA", 1) != 0;
     if (a.col_map && !(a.wfrag && a.cin == 64 && a.cout >= 1 && a.cout <= 4)) return hipErrorInvalidValue;
     if ((use_mfma || a.col_map) && a.wfrag && a.cin == 64 && a.cout >= 1 && a.cout <= 4 && total < (1ll << 30)) {
         const long long groups = (total + 15) / 16;
@@ -1279,7 +1279,7 @@ hipError_t launch_readout(const ReadoutArgs& a, hipStream_t s) {
         if (per < 1) per = 1;
         waves = (groups + per - 1) / per;
         // DMA-staged gather (DYF_READOUT_DMA=0: the register-shuffle form); the DMA's buffer descriptor addresses < 4 GB
-        const bool use_dma = !(dyf_form("DYF_READOUT_DMA") && atoi(dyf_form("DYF_READOUT_DMA")) == 0);
+        const bool use_dma = dyf_form_int("DYF_READOUT_DMA", 1) != 0;
         const bool dma = use_dma && a.row_tab && a.col_tab && (size_t)a.n * a.ih * a.iw_store * 128 < 0x7F000000ull;
         dyf_form_note(dma ? "readout_dma_kernel" : "readout_mfma_kernel", a.n);
         KernelProf kp(dma ? "readout_dma_kernel" : "readout_mfma_kernel", s,

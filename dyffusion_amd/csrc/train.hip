@@ -1209,7 +1209,7 @@ dyf_status talloc(dyf_engine* e, std::vector<void*>& owner, T** out, size_t coun
     else {
         // test hook (DYF_TRAIN_POISON=1): blocks handed out without zero-fill start as NaN patterns, so a kernel that consumes a
         // buffer it did not fully write shows up in the gradients instead of hiding behind whatever the block held before
-        const bool poison = dyf_form("DYF_TRAIN_POISON") && atoi(dyf_form("DYF_TRAIN_POISON")) != 0;
+        const bool poison = dyf_form_int("DYF_TRAIN_POISON", 0) != 0;
         if (poison) TK(hipMemsetAsync(p, 0xFF, bytes, ts ? ts->stream : nullptr));
     }
     owner.push_back(p);
@@ -1262,7 +1262,7 @@ float* splitk_ws(dyf_engine* e) {
 
 // DYF_TRAIN_MFMA=0 keeps the plain VALU kernels (A/B and a second implementation for the tests)
 bool train_mfma() {
-    const bool on = !(dyf_form("DYF_TRAIN_MFMA") && atoi(dyf_form("DYF_TRAIN_MFMA")) == 0);
+    const bool on = dyf_form_int("DYF_TRAIN_MFMA", 1) != 0;
     return on;
 }
 
@@ -1271,10 +1271,10 @@ dyf_status conv_fwd(dyf_engine* e, const TConv& g, const float* x, const float* 
         TK(hipGetLastError());
         return DYF_OK;
     }
-    const bool small = !(dyf_form("DYF_TRAIN_SMALLC") && atoi(dyf_form("DYF_TRAIN_SMALLC")) == 0);  // =0: the round-3 VALU forms (A/B)
+    const bool small = dyf_form_int("DYF_TRAIN_SMALLC", 1) != 0;  // =0: the round-3 VALU forms (A/B)
     const long long Mf = (long long)g.n * g.ho * g.wo;
     if (small && g.cout % 64 == 0 && g.wo % 32 == 0 && g.cin <= 8 && g.k * g.k * g.cin <= 126 && g.k < 256 && Mf >= 4096 &&
-        !(dyf_form("DYF_TRAIN_SMALLC_MFMA") && atoi(dyf_form("DYF_TRAIN_SMALLC_MFMA")) == 0)) {
+        dyf_form_int("DYF_TRAIN_SMALLC_MFMA", 1) != 0) {
         const long long tiles = Mf / 32;
         const int tpw = (int)std::max<long long>(1, (tiles + 4095) / 4096);  // ~4 096 waves per 64-channel block
         hipLaunchKernelGGL(t_conv_fwd_smallc_mfma, dim3((unsigned)((tiles + 4ll * tpw - 1) / (4ll * tpw)), (unsigned)(g.cout / 64)), dim3(256), 0, st, g, x,
@@ -1291,9 +1291,9 @@ dyf_status conv_dgrad(dyf_engine* e, const TConv& g, const float* dz, const floa
         TK(hipGetLastError());
         return DYF_OK;
     }
-    const bool small = !(dyf_form("DYF_TRAIN_SMALLC") && atoi(dyf_form("DYF_TRAIN_SMALLC")) == 0);
+    const bool small = dyf_form_int("DYF_TRAIN_SMALLC", 1) != 0;
     if (small && g.s == 2 && g.k == 4 && g.p == 1 && g.cin <= 4 && g.cout == 64 && g.h % 2 == 0 && g.w % 2 == 0 && g.ho == g.h / 2 && g.wo == g.w / 2 &&
-        !(dyf_form("DYF_TRAIN_CT_ROWS") && atoi(dyf_form("DYF_TRAIN_CT_ROWS")) == 0)) {
+        dyf_form_int("DYF_TRAIN_CT_ROWS", 1) != 0) {
         const int wc = (g.w / 2 + 63) / 64;
         constexpr size_t lds = (size_t)(16 * 64 * 4 + 3 * CT_COLS * CT_PITCH) * sizeof(float);
         if (!train_raise_dynamic_lds(t_conv_dgrad_smalln_s2_rows, (int)lds))
@@ -1337,9 +1337,9 @@ dyf_status conv_wgrad(dyf_engine* e, const TConv& g, const float* dz, const floa
         TK(hipGetLastError());
         return DYF_OK;
     }
-    const bool small = !(dyf_form("DYF_TRAIN_SMALLC") && atoi(dyf_form("DYF_TRAIN_SMALLC")) == 0);
+    const bool small = dyf_form_int("DYF_TRAIN_SMALLC", 1) != 0;
     if (small && g.cout % 64 == 0 && M >= 4096 && g.wo % 2 == 0 && g.k * g.k * g.cin + 1 <= 128 && g.cin <= 8 &&
-        !(dyf_form("DYF_TRAIN_SMALLC_MFMA") && atoi(dyf_form("DYF_TRAIN_SMALLC_MFMA")) == 0)) {  // read per call: tests run both forms
+        dyf_form_int("DYF_TRAIN_SMALLC_MFMA", 1) != 0) {  // read per call: tests run both forms
         const long long pairs = M / 2;
         const int ppw = (int)std::max<long long>(64, (pairs + 2047) / 2048);  // ~2 048 waves per 64-channel block
         const dim3 grid((unsigned)((pairs + 4ll * ppw - 1) / (4ll * ppw)), (unsigned)(g.cout / 64));
@@ -2064,8 +2064,8 @@ dyf_status dyf_train_conv_check(dyf_engine* e, int32_t kind, int32_t n, int32_t 
     // test seam DYF_TRAIN_CHECK_DZ_EXP2 = k: the output gradient is scaled by 2^-k first -- the magnitudes a mean-reduced loss gives at
     // real batch sizes (1e-6 .. 1e-7) -- to show that the 16-bit gradient operand keeps its accuracy there (bf16 in both builds: an
     // fp16 operand would be subnormal or zero; a power of two commutes with the rounding, so the check's tolerance is unchanged)
-    if (const char* k2 = dyf_form("DYF_TRAIN_CHECK_DZ_EXP2"))
-        hipLaunchKernelGGL(t_scale_exp2, dim3(nblk(nz)), dim3(256), 0, st, z, nz, -atoi(k2));
+    if (const long long k2 = dyf_form_int("DYF_TRAIN_CHECK_DZ_EXP2", 0))
+        hipLaunchKernelGGL(t_scale_exp2, dim3(nblk(nz)), dim3(256), 0, st, z, nz, -(int)k2);
     const TrainPrecisionScope precision(e->train_precision);
     if (train_operands16()) {
         hipLaunchKernelGGL(t_round16, dim3(nblk(nx)), dim3(256), 0, st, x, nx);
@@ -2110,7 +2110,7 @@ dyf_status dyf_train_conv_check(dyf_engine* e, int32_t kind, int32_t n, int32_t 
             memcpy(&d, &hm[0], 4); memcpy(&m, &hm[1], 4); memcpy(&ga, &hm[2], 4);
             res[pass] = m > 0.0f ? d / m : 1.0f;  // an all-zero reference is a failed check, not a perfect one
             if (!(ga > 0.0f)) res[pass] = 1.0f;
-            if (dyf_form("DYF_TRAIN_CHECK_VERBOSE")) fprintf(stderr, "conv_check kind %d pass %d: max|diff| %g max|ref| %g max|got| %g\n", kind, pass, d, m, ga);
+            if (dyf_form_int("DYF_TRAIN_CHECK_VERBOSE", 0) != 0) fprintf(stderr, "conv_check kind %d pass %d: max|diff| %g max|ref| %g max|got| %g\n", kind, pass, d, m, ga);
         }
         if (kind >= 2) { res[1] = res[0]; break; }
     }

@@ -450,7 +450,7 @@ bool train_operands16() {
 static void plan_splitk(long long tiles, int stages, int& splits, int& len) {
     splits = 1;
     len = 0;
-    const bool enabled = !(dyf_form("DYF_TRAIN_SPLITK") && atoi(dyf_form("DYF_TRAIN_SPLITK")) == 0);
+    const bool enabled = dyf_form_int("DYF_TRAIN_SPLITK", 1) != 0;
     if (!enabled || tiles >= 128 || stages < 16) return;
     long long want = std::min<long long>((512 + tiles - 1) / tiles, stages / 4);  // >= 4 stages per split
     if (want < 2) return;
@@ -484,7 +484,7 @@ bool tgemm_conv_dgrad(const TConv& g, const float* dz, const float* w, const flo
     const bool h16 = train_operands16() && g.cout % GK16 == 0;
     if (h16 && thalo_conv3x3(g, 1, dz, w, bias, dx, ws, ws_floats, st)) return true;
     {   // 4 x 4 / stride 2 / pad 1: one launch slice per parity class of the input pixels (see the kernel); small planes keep split-K
-        const bool pclass = !(dyf_form("DYF_TRAIN_DGRAD_PARITY") && atoi(dyf_form("DYF_TRAIN_DGRAD_PARITY")) == 0);  // per call: tests flip it
+        const bool pclass = dyf_form_int("DYF_TRAIN_DGRAD_PARITY", 1) != 0;  // per call: tests flip it
         const long long mq = ((long long)g.n * g.h * g.w / 4 + GM - 1) / GM;
         if (h16 && pclass && g.k == 4 && g.s == 2 && g.p == 1 && g.h % 2 == 0 && g.w % 2 == 0 && g.ho == g.h / 2 && g.wo == g.w / 2 &&
             mq * (g.cin / GN) >= 64 && mq <= 0x7fffffffll) {

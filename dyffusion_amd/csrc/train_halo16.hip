@@ -315,8 +315,7 @@ __global__ __launch_bounds__(256, 2) void t_wgrad3x3_16(int h, int w, int cin, i
 }
 
 bool halo16_enabled() {
-    const char* v = dyf_form("DYF_TRAIN_HALO16");  // =0: the tap-by-tap implicit GEMM of train_gemm.hip for these layers too (A/B)
-    return !(v && atoi(v) == 0);
+    return dyf_form_int("DYF_TRAIN_HALO16", 1) != 0;  // =0: the tap-by-tap implicit GEMM of train_gemm.hip for these layers too (A/B)
 }
 
 }  // namespace

@@ -619,7 +619,7 @@ struct RCtx {
 
     // DYF_TRAIN_DEBUG=1: synchronise after every recorded op and report the first failing one (debugging aid)
     dyf::RT* dbg(dyf::RT* y, const char* what) {
-        const bool on = dyf_form("DYF_TRAIN_DEBUG") != nullptr;
+        const bool on = dyf_form_int("DYF_TRAIN_DEBUG", 0) != 0;
         if (on) {
             const hipError_t se = hipDeviceSynchronize();
             fprintf(stderr, "train op %-10s -> %zu floats: %s\n", what, y ? y->n : (size_t)0, hipGetErrorString(se));

@@ -237,7 +237,7 @@ hipError_t launch_stem_conv(const StemConvArgs& a, hipStream_t s) {
     const long long total = (long long)a.n * a.h * a.w;
     if (a.wfrag && a.dim == 64 && a.ksteps >= 1 && a.ksteps == stem_frag_steps(a.k, a.cin) && a.nsrc <= 4 &&
         (long long)a.h * a.w * 4 < (1ll << 31)) {
-        const bool use_mfma = !(dyf_form("DYF_STEM_MFMA") && atoi(dyf_form("DYF_STEM_MFMA")) == 0);
+        const bool use_mfma = dyf_form_int("DYF_STEM_MFMA", 1) != 0;
         if (use_mfma) {
             const int ts = (a.k * a.k + 15) / 16;
             const size_t lds = (size_t)a.ksteps * 4 * 64 * 16;
@@ -455,10 +455,7 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(GnActArgs a, const float2
 // Walk form of gn_apply_kernel (channel chunks per pixel a power of two <= 256): a thread keeps ONE 16-byte channel chunk and
 // applies it to GP pixels of its sample: the per-chunk coefficient setup (GroupNorm affine x FiLM: 6 vector loads, ~50 VALU) is
 // paid once instead of per pixel, and the GP tensor loads (and residual loads) are in flight together.
-#ifndef GN_GP
-#define GN_GP 4
-#endif
-constexpr int GP = GN_GP;
+constexpr int GP = 4;
 __global__ __launch_bounds__(256) void gn_apply_walk_kernel(GnActArgs a, const float2* mr) {
     const int chunks = a.c >> 3, cpg = a.c / a.groups;
     const int n = blockIdx.y;
@@ -614,165 +611,6 @@ __global__ __launch_bounds__(256) void gn_apply_part_kernel(GnActArgs a) {
     }
 }
 
-// Small planes (a sample's tensor fits the registers of one 512- or 1024-lane workgroup: hw * c / 8 <= THREADS * MAXI chunks -- the 30x30x128
-// and 15x15x256 levels of the OISST ResNet-UNet, whose convs do not produce statistics): ONE kernel, one read of the tensor from HBM.
-// A lane keeps one 16-byte channel chunk column and, KEEP, MAXI pixels of it in registers (512 lanes x 16 chunks = 128 KB: the
-// 15x15x256 level); larger samples (30x30x128 = 225 KB: 1024 lanes would have to hold it in 64 of their 128 registers, which
-// spills) are walked twice, the second time out of L2.  The statistics are reduced like gn_stats_kernel's
-// (lane sums in fp32, butterfly over the lanes of a group, one LDS slot per (wave, group), the waves added in order in fp64:
-// deterministic), then normalise + FiLM + activation + dropout (+ residual) run from the registers.  Would replace gn_stats_kernel +
-// gn_finalize_kernel + gn_apply_walk_kernel (5.2 + 4.9 + 11.9 us per GroupNorm at 100 rows of the OISST shapes).
-// EXPERIMENT (DYF_GN_FUSED_SAMPLE=1), measured and not adopted: correct (tests/test_gpu_bench_forms.py and test_gpu_unet_resnet.py
-// pass with it on) but no faster where the chip is full -- OISST rollout at 300 rows 3 740 / 3 791 fields/s with it, 3 797 without,
-// 3 824 with DYF_GN_FUSED_REREAD=1 (both levels walked twice), same box: the three short launches it removes already overlap
-// with the other row groups' kernels -- and slower where it is not: one workgroup per sample is 16 workgroups at 16 rows
-// (595 against 730 fields/s).
-template <int MAXI, int THREADS, bool KEEP>
-__global__ __launch_bounds__(THREADS) void gn_fused_sample_kernel(GnActArgs a) {
-    __shared__ float part[THREADS / 64][64][2];  // [wave][group]
-    __shared__ float2 mr_s[64];
-    const int chunks = a.c >> 3, cpg = a.c / a.groups, cq = cpg >> 3;
-    const int n = blockIdx.x;
-    const int q = threadIdx.x & (chunks - 1), row = threadIdx.x / chunks, rows = THREADS / chunks;
-    const el16_t* xp = a.x + (size_t)n * a.hw * a.c + q * 8;
-    float s = 0.0f, ss = 0.0f;
-    auto add = [&](const uint4& u) {
-        const uint32_t w[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            const float lo = el16_lo(w[t]), hi = el16_hi(w[t]);
-            s += lo + hi;
-            ss = fmaf(lo, lo, fmaf(hi, hi, ss));
-        }
-    };
-    uint4 v[KEEP ? MAXI : 1];
-    if constexpr (KEEP) {
-#pragma unroll
-        for (int i = 0; i < MAXI; ++i) {
-            const int p = row + i * rows;
-            v[i] = p < a.hw ? *(const uint4*)(xp + (size_t)p * a.c) : make_uint4(0, 0, 0, 0);  // zeros add nothing to the sums
-        }
-#pragma unroll
-        for (int i = 0; i < MAXI; ++i) add(v[i]);
-    } else {
-        int p = row;
-        for (; p + 3 * rows < a.hw; p += 4 * rows) {  // four independent 16-B loads in flight
-            const uint4 v0 = *(const uint4*)(xp + (size_t)p * a.c), v1 = *(const uint4*)(xp + (size_t)(p + rows) * a.c);
-            const uint4 v2 = *(const uint4*)(xp + (size_t)(p + 2 * rows) * a.c), v3 = *(const uint4*)(xp + (size_t)(p + 3 * rows) * a.c);
-            add(v0); add(v1); add(v2); add(v3);
-        }
-        for (; p < a.hw; p += rows) add(*(const uint4*)(xp + (size_t)p * a.c));
-    }
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {  // lanes l and l ^ d hold the same group when d < cq or d >= chunks
-        if (d < cq || d >= chunks) {
-            s += __shfl_xor(s, d, 64);
-            ss += __shfl_xor(ss, d, 64);
-        }
-    }
-    const int l = threadIdx.x & 63;
-    const int g = (q * 8) / cpg;
-    if ((l & (cq - 1)) == 0 && (chunks >= 64 || l < chunks)) {  // exactly one lane of the wave holds group g
-        part[threadIdx.x >> 6][g][0] = s;
-        part[threadIdx.x >> 6][g][1] = ss;
-    }
-    __syncthreads();
-    if (threadIdx.x < a.groups) {
-        double ds = 0.0, dss = 0.0;
-        // chunks > 64: a wave covers 64 of the chunk columns only and holds a slot for the groups that overlap them
-        for (int w = 0; w < THREADS / 64; ++w) {
-            const int q0 = (w * 64) & (chunks - 1), q1 = chunks >= 64 ? q0 + 64 : chunks;
-            const int gq = threadIdx.x * cq;  // first chunk column of the group
-            if (gq < q1 && gq + cq > q0) {
-                ds += (double)part[w][threadIdx.x][0];
-                dss += (double)part[w][threadIdx.x][1];
-            }
-        }
-        const double inv = 1.0 / ((double)a.hw * cpg);
-        const double mean = ds * inv;
-        const double var = dss * inv - mean * mean;
-        mr_s[threadIdx.x] = make_float2((float)mean, rsqrtf(fmaxf((float)var, 0.0f) + 1e-5f));
-    }
-    __syncthreads();
-    const float2 ms = mr_s[g];
-    const float mean = ms.x, rstd = ms.y;
-    const float4 g0 = *(const float4*)(a.gamma + q * 8), g1 = *(const float4*)(a.gamma + q * 8 + 4);
-    const float4 b0 = *(const float4*)(a.beta + q * 8), b1 = *(const float4*)(a.beta + q * 8 + 4);
-    float A[8] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g1.z, g1.w};
-    float C[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
-#pragma unroll
-    for (int t = 0; t < 8; ++t) {
-        A[t] *= rstd;
-        C[t] = fmaf(-mean, A[t], C[t]);
-    }
-    if (a.film_a) {
-        const size_t fi = (size_t)n * a.film_stride + q * 8;
-        const float4 fa0 = *(const float4*)(a.film_a + fi), fa1 = *(const float4*)(a.film_a + fi + 4);
-        const float4 fc0 = *(const float4*)(a.film_c + fi), fc1 = *(const float4*)(a.film_c + fi + 4);
-        const float fa[8] = {fa0.x, fa0.y, fa0.z, fa0.w, fa1.x, fa1.y, fa1.z, fa1.w};
-        const float fc[8] = {fc0.x, fc0.y, fc0.z, fc0.w, fc1.x, fc1.y, fc1.z, fc1.w};
-#pragma unroll
-        for (int t = 0; t < 8; ++t) {
-            A[t] *= fa[t];
-            C[t] = fmaf(C[t], fa[t], fc[t]);
-        }
-    }
-    const RngKey key = drop_row_key(a.drop, n);
-    const uint32_t row0 = (uint32_t)((size_t)n * a.hw * a.c);
-    auto finish = [&](const uint4& xv4, const uint4& rv, int p) {  // p < hw
-        const size_t e0 = ((size_t)n * a.hw + p) * a.c + q * 8;
-        const uint32_t w[4] = {xv4.x, xv4.y, xv4.z, xv4.w};
-        float y[8];
-#pragma unroll
-        for (int t = 0; t < 8; ++t) {
-            const float xv = (t & 1) ? el16_hi(w[t >> 1]) : el16_lo(w[t >> 1]);
-            y[t] = fmaf(xv, A[t], C[t]);
-        }
-        act_drop<8>(y, (uint32_t)e0, row0, a.act, a.drop, key);
-        if (a.residual) {
-            const uint32_t rw[4] = {rv.x, rv.y, rv.z, rv.w};
-#pragma unroll
-            for (int t = 0; t < 8; ++t) y[t] += (t & 1) ? el16_hi(rw[t >> 1]) : el16_lo(rw[t >> 1]);
-        }
-        *(uint4*)(a.out + e0) = make_uint4(pack_el16x2(y[0], y[1]), pack_el16x2(y[2], y[3]), pack_el16x2(y[4], y[5]), pack_el16x2(y[6], y[7]));
-    };
-    constexpr int RB = 4;  // loads in flight
-    if constexpr (KEEP) {
-#pragma unroll
-        for (int i0 = 0; i0 < MAXI; i0 += RB) {
-            uint4 r[RB];
-            if (a.residual) {
-#pragma unroll
-                for (int j = 0; j < RB; ++j) {
-                    const int p = min(row + (i0 + j) * rows, a.hw - 1);
-                    r[j] = *(const uint4*)(a.residual + ((size_t)n * a.hw + p) * a.c + q * 8);
-                }
-            }
-#pragma unroll
-            for (int j = 0; j < RB; ++j) {
-                const int p = row + (i0 + j) * rows;
-                if (p < a.hw) finish(v[i0 + j], r[j], p);
-            }
-        }
-    } else {
-        // second walk over the sample: these 16-byte chunks were read by this workgroup a few microseconds ago (L2 hits)
-        for (int pb = row; pb < a.hw; pb += RB * rows) {
-            uint4 x4[RB], r[RB];
-#pragma unroll
-            for (int j = 0; j < RB; ++j) {
-                const int p = min(pb + j * rows, a.hw - 1);
-                x4[j] = *(const uint4*)(xp + (size_t)p * a.c);
-                if (a.residual) r[j] = *(const uint4*)(a.residual + ((size_t)n * a.hw + p) * a.c + q * 8);
-            }
-#pragma unroll
-            for (int j = 0; j < RB; ++j) {
-                const int p = pb + j * rows;
-                if (p < a.hw) finish(x4[j], r[j], p);
-            }
-        }
-    }
-}
-
 // Large planes (512^2: 2 048 slots per sample): the finalisation is too much to repeat in every workgroup of the apply pass --
 // one workgroup per (sample, group) does it once (fixed order: 128 slot lanes x 2 sums, then a tree over the lanes) and
 // gn_apply_walk_kernel runs.  (First form: one workgroup per sample, 16 slot lanes per sum: 27 us at 512^2, 6 % of that rollout.)
@@ -837,19 +675,6 @@ hipError_t launch_gn_act(const GnActArgs& a, hipStream_t s) {
         return hipGetLastError();
     }
     if (a.stats && (a.c % 8 == 0) && (cpg % 8 == 0) && a.groups <= 64) {
-        {
-            const int chunks = a.c >> 3, cq = cpg >> 3;
-            const bool fused = dyf_form("DYF_GN_FUSED_SAMPLE") && atoi(dyf_form("DYF_GN_FUSED_SAMPLE")) != 0;  // experiment, off
-            const long long per = (long long)a.hw * chunks;
-            const int reread = dyf_form("DYF_GN_FUSED_REREAD") ? atoi(dyf_form("DYF_GN_FUSED_REREAD")) : 0;  // experiment: 1 = never keep
-            if (fused && (chunks & (chunks - 1)) == 0 && (cq & (cq - 1)) == 0 && chunks <= 256 && per <= 1024 * 32) {
-                dyf_form_note("gn_fused_sample_kernel", a.n);
-                if (per <= 512 * 8 && !reread) hipLaunchKernelGGL((gn_fused_sample_kernel<8, 512, true>), dim3(a.n), dim3(512), 0, s, a);
-                else if (per <= 512 * 16 && !reread) hipLaunchKernelGGL((gn_fused_sample_kernel<16, 512, true>), dim3(a.n), dim3(512), 0, s, a);
-                else hipLaunchKernelGGL((gn_fused_sample_kernel<1, 1024, false>), dim3(a.n), dim3(1024), 0, s, a);
-                return hipGetLastError();
-            }
-        }
         dyf_form_note("gn_stats_kernel+gn_apply", a.n);
         const long long per_sample = (long long)a.hw * (a.c >> 3);
         // >= 4 passes of 256 lanes per workgroup, at most GN_MAX_BLOCKS workgroups per sample (their partials are added in order)
@@ -862,7 +687,7 @@ hipError_t launch_gn_act(const GnActArgs& a, hipStream_t s) {
         hipLaunchKernelGGL(gn_finalize_kernel, dim3((cnt + 255) / 256), dim3(256), 0, s, (const double*)a.stats, cnt, (int)bx,
                            1.0 / ((double)a.hw * cpg), mr);
         const int chunks = a.c >> 3;
-        const bool walk = !(dyf_form("DYF_GN_WALK") && atoi(dyf_form("DYF_GN_WALK")) == 0);
+        const bool walk = dyf_form_int("DYF_GN_WALK", 1) != 0;
         if (walk && (chunks & (chunks - 1)) == 0 && chunks <= 256 && a.n <= 65535) {
             const int rows = 256 / chunks;
             KernelProf kp("gn_apply_walk_kernel", s, (double)a.n * a.hw * a.c * 2.0 * (a.residual ? 3.0 : 2.0));
@@ -1642,7 +1467,7 @@ __global__ __launch_bounds__(256, 2) void linattn_fused_out_kernel(const el16_t*
 }
 
 bool linattn_fused_supported(int c) {
-    const bool on = !(dyf_form("DYF_LINATTN_FUSED") && atoi(dyf_form("DYF_LINATTN_FUSED")) == 0);
+    const bool on = dyf_form_int("DYF_LINATTN_FUSED", 1) != 0;
     return on && (c == 64 || c == 128);
 }
 
@@ -1679,8 +1504,7 @@ hipError_t launch_linear_attention_fused(const LinAttnFusedArgs& a, hipStream_t 
     // profiles/r05f_oisst_nb38).  Below 384 workgroups the launch halves / quarters the block (more, shorter chains; the merge
     // kernel takes any number of partials).  DYF_LINATTN_GPB = 32 / 16 / 8 forces a size (read per launch).
     const int ngroups = (a.hw + 31) / 32, BH = a.n * LA_HEADS;
-    int gpb = a.groups_per_block;
-    if (const char* ge = dyf_form("DYF_LINATTN_GPB")) gpb = atoi(ge);
+    int gpb = (int)dyf_form_int("DYF_LINATTN_GPB", a.groups_per_block);
     if (gpb != 32 && gpb != 16 && gpb != 8) {
         gpb = 32;
         // (measured, OISST rollouts with blocks of 32 only / this rule at 512: 38 rows 1 791 / 1 824 fields/s, 75 rows 2 651 / 2 758, 150 rows
@@ -1793,159 +1617,8 @@ __global__ __launch_bounds__(64) void attention_kernel(AttnArgs a) {
 // 136 B: conflict-free ds_read_b64).  Online softmax in fp32; the normaliser is accumulated BEFORE dropout.
 typedef __attribute__((ext_vector_type(16))) float fa_f32x16;
 
-__global__ __launch_bounds__(256) void flash_attention_kernel(AttnArgs a) {
-    __shared__ __attribute__((aligned(16))) el16_t Ks[64 * 32];   // [key][32 ch], 16-B chunk ^= (key >> 2) & 3
-    __shared__ __attribute__((aligned(16))) el16_t Vt[32 * 68];   // [ch][64 keys + 4 pad]
-    const int qblocks = (a.hw + 127) / 128;
-    const int bh = blockIdx.x / qblocks, qb = blockIdx.x % qblocks;
-    const int n = bh / a.heads, h = bh % a.heads;
-    const int C3 = 3 * a.heads * 32, hd = a.heads * 32, N = a.hw;
-    const el16_t* base = a.qkv + (size_t)n * N * C3;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, hi = lane >> 5;
-    const int q = qb * 128 + wave * 32 + l31;
-    const float scale = 0.17677669529663687f;  // 32^-1/2
-    // Q fragments (B operand of S^T): lane (q, hi) holds channels ks*16 + hi*8 .. +8
-    el16x8_t qf[2];
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-        uint4 v = make_uint4(0, 0, 0, 0);
-        if (q < N) v = *(const uint4*)(base + (size_t)q * C3 + h * 32 + ks * 16 + hi * 8);
-        qf[ks] = *(el16x8_t*)&v;
-    }
-    fa_f32x16 o;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) o[r] = 0.0f;
-    float m = -1.0e30f, l = 0.0f;   // running maximum in the log2 domain (scores are pre-multiplied by scale * log2 e)
-    const RngKey dkey = attn_drop_key(a.drop, n, (uint32_t)h);
-    const float c2 = scale * 1.4426950408889634f;
-
-    // K / V of the NEXT 64-key tile travel through registers: their global loads are issued right after the current tile has
-    // been written to LDS and land while it is being consumed (the un-prefetched form exposed one HBM/L2 round trip per tile:
-    // 4.2 ms for 4 x 4 heads x 16 384 tokens)
-    const int skey = tid >> 2, sch = tid & 3;   // staging role: thread -> (key, 16-B chunk of 8 channels)
-    uint4 kv_n = make_uint4(0, 0, 0, 0), vv_n = make_uint4(0, 0, 0, 0);
-    auto fetch = [&](int j0) {
-        const int j = j0 + skey;
-        kv_n = make_uint4(0, 0, 0, 0);
-        vv_n = kv_n;
-        if (j < N) {
-            kv_n = *(const uint4*)(base + (size_t)j * C3 + hd + h * 32 + sch * 8);
-            vv_n = *(const uint4*)(base + (size_t)j * C3 + 2 * hd + h * 32 + sch * 8);
-        }
-    };
-    fetch(0);
-
-    // one 32-key sub-tile; variant 1 (FAST): all 32 keys exist and no dropout on the probabilities; variant 2: all 32 keys and
-    // the query exist, dropout from the engine's generator with an even token count -- keys j, j + 1 of a register pair share
-    // one keep word (rng_keep hashes element pair (q*N + j) >> 1), so 8 hashes serve the lane's 16 probabilities and there are
-    // no per-element bounds or mode tests (the general form, variant 0, ran the 16 384-token attention of the 512^2
-    // configuration at 4.3 ms per NB = 4 call against 1.6 ms without dropout)
-    auto subtile = [&](int jb, int st, auto variant_c) {
-        constexpr int VARIANT = decltype(variant_c)::value;
-        constexpr bool FAST = VARIANT != 0;
-        fa_f32x16 sc;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) sc[r] = 0.0f;
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            const int key = st * 32 + l31;
-            const el16x8_t kf = *(const el16x8_t*)(Ks + key * 32 + (((ks * 2 + hi) ^ ((key >> 2) & 3)) << 3));
-            sc = DYF_MFMA_32x32x16(kf, qf[ks], sc, 0, 0, 0);
-        }
-        // lane (q, hi) now holds keys jb + (r&3) + 8(r>>2) + 4hi of query q
-        float tmax = -1.0e30f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            if (FAST) sc[r] *= c2;
-            else sc[r] = (jb + (r & 3) + 8 * (r >> 2) + 4 * hi) < N ? sc[r] * c2 : -1.0e30f;
-            tmax = fmaxf(tmax, sc[r]);
-        }
-        tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
-        const float mn = fmaxf(m, tmax);
-        const float alpha = __builtin_amdgcn_exp2f(m - mn);
-        m = mn;
-        float psum = 0.0f;
-        float p[16];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const float e = __builtin_amdgcn_exp2f(sc[r] - mn);
-            psum += e;
-            if (VARIANT == 1) p[r] = e;
-            else if (VARIANT == 2) p[r] = e;  // masked below, pair by pair
-            else {
-                const int j = jb + (r & 3) + 8 * (r >> 2) + 4 * hi;
-                p[r] = (j < N && q < N) ? attn_drop(e, a.drop, dkey, (uint32_t)bh, (uint32_t)q, (uint32_t)j, (uint32_t)N) : 0.0f;
-            }
-        }
-        if (VARIANT == 2) {
-            const uint32_t th = a.drop.thresh8;
-            const float dsc = a.drop.scale8;
-            const uint32_t e0 = (uint32_t)q * (uint32_t)N + (uint32_t)(jb + 4 * hi);  // a multiple of 4: N % 4 == 0, jb and 4*hi are
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {  // registers 4g .. 4g + 3: keys e0 + 8g + {0..3} = ONE quad word (common.h rng_keep8)
-                const uint32_t w = rng_quad_word((e0 + 8u * (uint32_t)g) >> 2, dkey);
-                p[4 * g] = (w & 0xffu) < th ? p[4 * g] * dsc : 0.0f;
-                p[4 * g + 1] = ((w >> 8) & 0xffu) < th ? p[4 * g + 1] * dsc : 0.0f;
-                p[4 * g + 2] = ((w >> 16) & 0xffu) < th ? p[4 * g + 2] * dsc : 0.0f;
-                p[4 * g + 3] = (w >> 24) < th ? p[4 * g + 3] * dsc : 0.0f;
-            }
-        }
-        psum += __shfl_xor(psum, 32, 64);
-        l = l * alpha + psum;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) o[r] *= alpha;
-#pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2) {
-            uint32_t pk[4];
-#pragma unroll
-            for (int t = 0; t < 4; ++t) pk[t] = pack_el16x2(p[s2 * 8 + 2 * t], p[s2 * 8 + 2 * t + 1]);
-            const el16x8_t pf = *(el16x8_t*)pk;
-            // V^T fragment: lane (d = l31, hi): keys st*32 + 16*s2 + 4*hi + {0..3} and + 8
-            const el16_t* vr = Vt + l31 * 68 + st * 32 + s2 * 16 + 4 * hi;
-            uint2 v0 = *(const uint2*)vr, v1 = *(const uint2*)(vr + 8);
-            uint32_t vw[4] = {v0.x, v0.y, v1.x, v1.y};
-            const el16x8_t vf = *(el16x8_t*)vw;
-            o = DYF_MFMA_32x32x16(vf, pf, o, 0, 0, 0);
-        }
-    };
-
-    for (int j0 = 0; j0 < N; j0 += 64) {
-        __syncthreads();  // every wave is done reading the previous tile
-        {   // stage K [64][32] and V^T [32][64] from the prefetched registers
-            *(uint4*)(Ks + skey * 32 + ((sch ^ ((skey >> 2) & 3)) << 3)) = kv_n;
-            const el16_t* ve = (const el16_t*)&vv_n;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) Vt[(sch * 8 + i) * 68 + skey] = ve[i];
-        }
-        if (j0 + 64 < N) fetch(j0 + 64);
-        __syncthreads();
-        const bool whole = j0 + 64 <= N;  // block-uniform
-        if (whole && a.drop.mode == 0) {
-            subtile(j0, 0, std::integral_constant<int, 1>{});
-            subtile(j0 + 32, 1, std::integral_constant<int, 1>{});
-        } else if (whole && a.drop.mode == 1 && (N & 3) == 0 && (qb + 1) * 128 <= N) {
-            subtile(j0, 0, std::integral_constant<int, 2>{});
-            subtile(j0 + 32, 1, std::integral_constant<int, 2>{});
-        } else {
-            subtile(j0, 0, std::integral_constant<int, 0>{});
-            if (j0 + 32 < N) subtile(j0 + 32, 1, std::integral_constant<int, 0>{});
-        }
-    }
-    if (q >= N) return;
-    // O^T[d][q]: lane (q, hi) holds d = (r&3) + 8(r>>2) + 4hi  -> four 8-byte stores of 4 consecutive channels
-    const float inv = 1.0f / l;
-    el16_t* op = a.out + ((size_t)n * N + q) * hd + h * 32;  // "b h (x y) d -> b (h d) x y"
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-        uint2 w;
-        w.x = pack_el16x2(o[g * 4 + 0] * inv, o[g * 4 + 1] * inv);
-        w.y = pack_el16x2(o[g * 4 + 2] * inv, o[g * 4 + 3] * inv);
-        *(uint2*)(op + 8 * g + 4 * hi) = w;
-    }
-}
-
 // ---- second form (round 3): the same data flow with the softmax's VALU work cut to what the exponentials need.
-// The first form is VALU-bound: per 32-key sub-tile a lane spends 16 scale multiplies, 16 max, 16 subtractions, 16 exp2, 16 adds,
+// The first form (retired) was VALU-bound: per 32-key sub-tile a lane spends 16 scale multiplies, 16 max, 16 subtractions, 16 exp2, 16 adds,
 // 16 rescales of O, 8 packs and two cross-lane exchanges (~370 issue cycles) next to 4 MFMAs (128 cycles).  Here:
 //   * Q is multiplied by scale * log2(e) ONCE, when its fragments are loaded;
 //   * the running maximum m enters through the MFMA's C operand: the score accumulators START at -m, so the MFMA delivers s - m
@@ -1960,57 +1633,26 @@ __global__ __launch_bounds__(256) void flash_attention_kernel(AttnArgs a) {
 // VARIANT 1: whole tile, no dropout; 2: whole tile, engine dropout with paired keep words; 0: general (partial tiles; dropout per
 // element when DROP).  DROP is the kernel's compile-time dropout switch: the no-dropout kernel carries no generator code at all
 // (register budget: 128 per lane for 4 waves per SIMD).
-// QB: 32-query blocks per wave.  QB = 2 (sequences of >= 512 tokens): a wave owns 64 queries -- two independent softmax chains
-// for the scheduler to interleave, and every K / V fragment read from LDS feeds two MFMAs.
+// QB: 32-query blocks per wave; the launcher instantiates QB = 1 only (a 64-query form, QB = 2, was measured and retired).
 typedef float fa_f32x2 __attribute__((ext_vector_type(2)));
-// kf0 / kf1 / vf0: this lane's LDS addresses of the K fragments (ks = 0, 1) and of the V^T fragment of sub-tile 0 (sub-tile st adds
-// a wave-uniform offset: the swizzle key (key >> 2) & 3 does not depend on st).  NEGM: the tuple -m lives in registers across the
-// loop and is the MFMA's C operand (kernels with the registers to spare); otherwise 16 moves per sub-tile rebuild it.
-#ifndef FA2_BIAS
-#define FA2_BIAS 0  // -DFA2_BIAS=1: -m from a third (bf16, k-slot 0) matrix instruction instead of 16 v_mov per sub-tile: measured
-                   // 1.162-1.186 vs 1.143 ms without dropout, 1.870 vs 1.903 ms with -- the kernel is not issue-bound; not kept
-#endif
 typedef __attribute__((ext_vector_type(4))) short fa_bf16x4;
-#ifndef FA2_PKMOV
-#define FA2_PKMOV 0  // measured: 1.184 ms with v_pk_mov_b32 vs 1.159 ms with the compiler's 16 v_mov_b32 (same box): not kept
-#endif
-template <int VARIANT, bool DROP, int QB, bool NEGM>
+// kf0 / kf1 / vf0: this lane's LDS addresses of the K fragments (ks = 0, 1) and of the V^T fragment of sub-tile 0 (sub-tile st adds
+// a wave-uniform offset: the swizzle key (key >> 2) & 3 does not depend on st).  The score accumulators start at -m: 16 moves per
+// sub-tile (a -m tuple resident in registers measured SLOWER for the 32-query no-dropout kernel, 1.24 vs 1.17 ms: 128 registers
+// leave the scheduler no slack at 4 waves per SIMD).
+template <int VARIANT, bool DROP, int QB>
 __device__ __forceinline__ void fa2_subtile(const AttnArgs& a, const el16_t* kf0, const el16_t* kf1, const el16_t* vf0, const el16x8_t (&qf)[QB][2],
-                                            fa_f32x16 (&o)[QB], fa_f32x16 (&negm)[QB], float (&m)[QB], fa_f32x2 (&l2)[QB], bool& first, int jb,
+                                            fa_f32x16 (&o)[QB], float (&m)[QB], fa_f32x2 (&l2)[QB], bool& first, int jb,
                                             int st, int q0, int N, int hi, RngKey dkey, uint32_t bh, fa_bf16x4 aone, fa_bf16x4 (&bm)[QB]) {
     fa_f32x16 sc[QB];
     {
         const el16x8_t k0 = *(const el16x8_t*)(kf0 + st * 1024), k1 = *(const el16x8_t*)(kf1 + st * 1024);
 #pragma unroll
         for (int b = 0; b < QB; ++b) {
-            if (NEGM) {
-                sc[b] = DYF_MFMA_32x32x16(k0, qf[b][0], negm[b], 0, 0, 0);
-#if FA2_BIAS
-            } else if (true) {
-                // the -m of every score comes from a THIRD matrix instruction (k-slot 0: 1 on the key side, -m on the query side, bf16)
-                // on the idle matrix pipe instead of 16 v_mov per sub-tile on the saturated vector pipe; m is kept bf16-exact
-                const fa_f32x16 zero = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-                sc[b] = __builtin_amdgcn_mfma_f32_32x32x8bf16_1k(aone, bm[b], zero, 0, 0, 0);
-                sc[b] = DYF_MFMA_32x32x16(k0, qf[b][0], sc[b], 0, 0, 0);
-#endif
-            } else {
-                // accumulator initialised with -m; -DFA2_PKMOV=1: two registers per instruction (v_pk_mov_b32) -- an experiment
-#if FA2_PKMOV
-                const fa_f32x2 nm2 = {-m[b], -m[b]};
+            const float nm = -m[b];  // accumulator initialised with -m
 #pragma unroll
-                for (int r = 0; r < 16; r += 2) {
-                    fa_f32x2 t;
-                    asm volatile("v_pk_mov_b32 %0, %1, %1" : "=v"(t) : "v"(nm2));
-                    sc[b][r] = t[0];
-                    sc[b][r + 1] = t[1];
-                }
-#else
-                const float nm = -m[b];
-#pragma unroll
-                for (int r = 0; r < 16; ++r) sc[b][r] = nm;
-#endif
-                sc[b] = DYF_MFMA_32x32x16(k0, qf[b][0], sc[b], 0, 0, 0);
-            }
+            for (int r = 0; r < 16; ++r) sc[b][r] = nm;
+            sc[b] = DYF_MFMA_32x32x16(k0, qf[b][0], sc[b], 0, 0, 0);
             sc[b] = DYF_MFMA_32x32x16(k1, qf[b][1], sc[b], 0, 0, 0);
         }
     }
@@ -2034,15 +1676,6 @@ __device__ __forceinline__ void fa2_subtile(const AttnArgs& a, const el16_t* kf0
         for (int b = 0; b < QB; ++b) {
             const float tm = fmaxf(tmax[b], __shfl_xor(tmax[b], 32, 64));  // both lanes of a query agree on the new maximum
             float delta = first ? tm : fmaxf(tm, 0.0f);                     // first sub-tile: m = the exact maximum (m was 0)
-#if FA2_BIAS
-            {   // m stays exactly representable in bf16 (round to nearest even): it travels as a bf16 MFMA operand
-                uint32_t u = __builtin_bit_cast(uint32_t, m[b] + delta);
-                u = (u + 0x7FFFu + ((u >> 16) & 1u)) & 0xFFFF0000u;
-                const float mn = __builtin_bit_cast(float, u);
-                delta = mn - m[b];
-                bm[b][0] = (short)(hi == 0 ? ((__builtin_bit_cast(uint32_t, -mn)) >> 16) : 0u);
-            }
-#endif
             // (first: O and l are still zero -- and a first maximum below -128 would make exp2(-delta) infinite: 0 * inf)
             const float alpha = first ? 1.0f : __builtin_amdgcn_exp2f(-delta);
             m[b] += delta;
@@ -2051,7 +1684,6 @@ __device__ __forceinline__ void fa2_subtile(const AttnArgs& a, const el16_t* kf0
             for (int r = 0; r < 16; ++r) {
                 o[b][r] *= alpha;
                 sc[b][r] -= delta;
-                if (NEGM) negm[b][r] = -m[b];
             }
         }
         first = false;
@@ -2062,11 +1694,7 @@ __device__ __forceinline__ void fa2_subtile(const AttnArgs& a, const el16_t* kf0
         float p[16];
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-#ifdef FA_EXP_NO_EXP
-            p[r] = sc[b][r] + 1.0f;  // timing experiment (wrong results): no exponentials
-#else
             p[r] = __builtin_amdgcn_exp2f(sc[b][r]);
-#endif
         }
         // the normaliser is accumulated BEFORE dropout (attention.py:69-70), two elements per instruction (v_pk_add_f32: a plain
         // wave64 VALU instruction occupies the SIMD for 4 cycles -- PMC: 4.6 cycles per VALU instruction, VALU busy 82 % of the
@@ -2116,20 +1744,9 @@ __device__ __forceinline__ void fa2_subtile(const AttnArgs& a, const el16_t* kf0
 // max -> 16 exp -> pack -> V-fragment read -> 2 MFMA of a sub-tile is latency, not issue, bound -- removing the exponentials AND the
 // V^T staging altogether moved 1.72 ms to 1.49 ms, while 3 instead of 2 resident waves per SIMD moved it to 1.24 ms.  Hence the
 // register diet (no second accumulator tuple, rolled sub-tile loop) and 4 waves per SIMD for the 32-query form.
-#ifndef FA2_MINW
-#define FA2_MINW 4
-#endif
-#ifndef FA2_MINW2
-#define FA2_MINW2 3
-#endif
+constexpr int FA2_MIN_WAVES = 4;
 template <bool DROP, int QB>
-__global__ __launch_bounds__(256, QB == 2 ? FA2_MINW2 : FA2_MINW) void flash_attention2_kernel(AttnArgs a) {
-    // NEGM (the -m tuple resident in registers) measured SLOWER for the 32-query no-dropout kernel (1.24 vs 1.17 ms: 128 registers
-    // leave the scheduler no slack at 4 waves per SIMD): off everywhere; -DFA2_NEGM=1 re-enables the experiment
-#ifndef FA2_NEGM
-#define FA2_NEGM 0
-#endif
-    constexpr bool NEGM = FA2_NEGM && !DROP && QB == 1;
+__global__ __launch_bounds__(256, FA2_MIN_WAVES) void flash_attention2_kernel(AttnArgs a) {
     __shared__ __attribute__((aligned(16))) el16_t Ks[64 * 32];   // [key][32 ch], 16-B chunk ^= (key >> 2) & 3
     __shared__ __attribute__((aligned(16))) el16_t Vt[32 * 68];   // [ch][64 keys + 4 pad]
     constexpr int QW = 32 * QB, QG = 4 * QW;   // queries per wave / per workgroup
@@ -2151,7 +1768,7 @@ __global__ __launch_bounds__(256, QB == 2 ? FA2_MINW2 : FA2_MINW) void flash_att
     const int q0 = qb * QG + wave * QW + l31;   // query of block 0; block b: + 32 b
     const float c2 = 0.17677669529663687f * 1.4426950408889634f;  // 32^-1/2 * log2(e): scores live in the log2 domain
     el16x8_t qf[QB][2];  // Q fragments (B operand of S^T), pre-multiplied by c2: lane (q, hi) holds channels ks*16 + hi*8 .. +8
-    fa_f32x16 o[QB], negm[QB];
+    fa_f32x16 o[QB];
     float m[QB];
     fa_f32x2 l2[QB];
     const el16_t* kf0 = Ks + l31 * 32 + (((0 + hi) ^ ((l31 >> 2) & 3)) << 3);
@@ -2169,14 +1786,14 @@ __global__ __launch_bounds__(256, QB == 2 ? FA2_MINW2 : FA2_MINW) void flash_att
             qf[b][ks] = *(el16x8_t*)w;
         }
 #pragma unroll
-        for (int r = 0; r < 16; ++r) o[b][r] = negm[b][r] = 0.0f;
+        for (int r = 0; r < 16; ++r) o[b][r] = 0.0f;
         m[b] = 0.0f;
         l2[b] = fa_f32x2{0.0f, 0.0f};
     }
     bool first = true;
     const RngKey dkey = DROP ? attn_drop_key(a.drop, n, (uint32_t)h) : RngKey{0u, 0u};
-    // bias operands of the third matrix instruction (32x32x8, lane (row / column, hi) holds k = 4 hi .. 4 hi + 3): k-slot 0 carries
-    // 1 on the key side and -m on the query side
+    // aone / bm: operands of a bias product this form no longer issues; unused, but dropping them changes the generated code
+    // (one more exec-mask instruction in the no-dropout kernel)
     const fa_bf16x4 aone = {(short)(hi == 0 ? 0x3F80 : 0), 0, 0, 0};
     fa_bf16x4 bm[QB];
 #pragma unroll
@@ -2195,35 +1812,28 @@ __global__ __launch_bounds__(256, QB == 2 ? FA2_MINW2 : FA2_MINW) void flash_att
     };
     fetch(0);
     for (int j0 = 0; j0 < N; j0 += 64) {
-#ifndef FA_EXP_NOSYNC
         __syncthreads();  // every wave is done reading the previous tile
-#endif
         {
             *(uint4*)(Ks + skey * 32 + ((sch ^ ((skey >> 2) & 3)) << 3)) = kv_n;
             const el16_t* ve = (const el16_t*)&vv_n;
-#ifdef FA_EXP_NO_VT
-            if (j0 == 0)  // timing experiment (wrong results): V^T staged once
-#endif
 #pragma unroll
             for (int i = 0; i < 8; ++i) Vt[(sch * 8 + i) * 68 + skey] = ve[i];
         }
         if (j0 + 64 < N) fetch(j0 + 64);
-#ifndef FA_EXP_NOSYNC
         __syncthreads();
-#endif
         const bool whole = j0 + 64 <= N;  // block-uniform
         // (the two sub-tiles of a tile run as a rolled loop: unrolled, the compiler interleaves them and needs > 128 registers)
         if (whole && !DROP) {
 #pragma nounroll
             for (int st = 0; st < 2; ++st)
-                fa2_subtile<1, false, QB, NEGM>(a, kf0, kf1, vf0, qf, o, negm, m, l2, first, j0 + 32 * st, st, q0, N, hi, dkey, (uint32_t)bh, aone, bm);
+                fa2_subtile<1, false, QB>(a, kf0, kf1, vf0, qf, o, m, l2, first, j0 + 32 * st, st, q0, N, hi, dkey, (uint32_t)bh, aone, bm);
         } else if (DROP && whole && a.drop.mode == 1 && (N & 3) == 0 && (qb + 1) * QG <= N) {
 #pragma nounroll
             for (int st = 0; st < 2; ++st)
-                fa2_subtile<2, DROP, QB, NEGM>(a, kf0, kf1, vf0, qf, o, negm, m, l2, first, j0 + 32 * st, st, q0, N, hi, dkey, (uint32_t)bh, aone, bm);
+                fa2_subtile<2, DROP, QB>(a, kf0, kf1, vf0, qf, o, m, l2, first, j0 + 32 * st, st, q0, N, hi, dkey, (uint32_t)bh, aone, bm);
         } else {
-            fa2_subtile<0, DROP, QB, NEGM>(a, kf0, kf1, vf0, qf, o, negm, m, l2, first, j0, 0, q0, N, hi, dkey, (uint32_t)bh, aone, bm);
-            if (j0 + 32 < N) fa2_subtile<0, DROP, QB, NEGM>(a, kf0, kf1, vf0, qf, o, negm, m, l2, first, j0 + 32, 1, q0, N, hi, dkey, (uint32_t)bh, aone, bm);
+            fa2_subtile<0, DROP, QB>(a, kf0, kf1, vf0, qf, o, m, l2, first, j0, 0, q0, N, hi, dkey, (uint32_t)bh, aone, bm);
+            if (j0 + 32 < N) fa2_subtile<0, DROP, QB>(a, kf0, kf1, vf0, qf, o, m, l2, first, j0 + 32, 1, q0, N, hi, dkey, (uint32_t)bh, aone, bm);
         }
     }
 #pragma unroll
@@ -2262,7 +1872,7 @@ __global__ __launch_bounds__(256, QB == 2 ? FA2_MINW2 : FA2_MINW) void flash_att
 //     sub-tile of the second form, and launches whose dropout layout the paired keep words cannot serve stay on the second form.
 
 // ---- fourth form (round 4): the third form's arithmetic as a SOFTWARE PIPELINE over 32-key sub-tiles.  Timing experiments on the
-// third form (tools/variants, wrong results: no bias product -4 %, no S^T products -17 %, no exponentials -12 %, no P V products
+// third form (since-retired experiment builds, wrong results: no bias product -4 %, no S^T products -17 %, no exponentials -12 %, no P V products
 // -8 %, no staging / barriers -15 %, the last two together -27 %) say that matrix, vector and staging time ADD in that kernel: a
 // wave issues in order, its softmax waits for its own S^T products and its P V products wait for its softmax.  Here
 //   * the scores of sub-tile i + 1 are computed WHILE the exponentials of sub-tile i are issued -- the matrix instructions of a
@@ -2278,9 +1888,6 @@ __global__ __launch_bounds__(256, QB == 2 ? FA2_MINW2 : FA2_MINW) void flash_att
 //   * a workgroup of eight waves (256 queries) stages every tile once for twice the queries: waves 0-3 carry K, waves 4-7 V.
 // When the lazy maximum moves (wave-uniform slow path, first sub-tile included) the scores already computed for sub-tile i + 1
 // are shifted by the same amount.  One 32-query block per wave.
-#ifndef FA4_MINW
-#define FA4_MINW 4
-#endif
 constexpr int FA4_VH = 64 * 16 + 64;        // el16 elements between the two channel halves of the V image (128 B of padding: the
                                            // two 16-lane groups of a half-wave then read different bank halves)
 constexpr int FA4_BUF = 64 * 32 + FA4_VH + 64 * 16;  // one K / V tile buffer: K [key][32 ch] (16-B chunk ^= (key >> 2) & 3), V images
@@ -2292,9 +1899,6 @@ __device__ __forceinline__ el16x8_t fa4_vfrag(const el16_t* v) {  // keys {0..3}
     uint2 w[2] = {__builtin_bit_cast(uint2, lo), __builtin_bit_cast(uint2, hi)};
     return *(el16x8_t*)w;
 }
-#ifndef FA4_MFMA_SUM
-#define FA4_MFMA_SUM 1
-#endif
 // sum of a lane's sixteen packed 16-bit values on the matrix pipe (see fa4_step)
 __device__ __forceinline__ float fa4_rowsum(const uint32_t (&pk)[8]) {
     typedef float fa_f32x4 __attribute__((ext_vector_type(4)));
@@ -2334,19 +1938,9 @@ __device__ __forceinline__ void fa4_step(const AttnArgs& a, fa_f32x16& sc_cur, f
     }
     float p[16];
 #pragma unroll
-#if defined(FA4_X_NOEXP)      // timing experiments (wrong results)
-    for (int r = 0; r < 16; ++r) p[r] = sc_cur[r] + 1.0f;
-#elif defined(FA4_X_MFMAONLY)
-    for (int r = 0; r < 16; ++r) p[r] = sc_cur[r];
-#else
     for (int r = 0; r < 16; ++r) p[r] = __builtin_amdgcn_exp2f(sc_cur[r]);
-#endif
     if (!TAIL) {
         const el16x8_t k0 = *(const el16x8_t*)kn0, k1 = *(const el16x8_t*)kn1;
-#if defined(FA4_X_NOQK)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) sc_next[r] = -m + (float)k0[0] + (float)k1[0];
-#else
         if (BIASED) {
             sc_next = DYF_MFMA_32x32x16(aone, bm, zero, 0, 0, 0);  // -m[q] in every (key, q) entry
             sc_next = DYF_MFMA_32x32x16(k0, qf[0], sc_next, 0, 0, 0);
@@ -2354,9 +1948,7 @@ __device__ __forceinline__ void fa4_step(const AttnArgs& a, fa_f32x16& sc_cur, f
             sc_next = DYF_MFMA_32x32x16(k0, qf[0], zero, 0, 0, 0);
         }
         sc_next = DYF_MFMA_32x32x16(k1, qf[1], sc_next, 0, 0, 0);
-#endif
     }
-#if FA4_MFMA_SUM
     // no dropout: the sub-tile's sum comes from the MATRIX pipe -- four 4x4x4 products of the packed probabilities with a tile of
     // ones give every lane the sum of its own sixteen values (block b = lane / 4, column j = lane % 4: D[b][i][j] = sum_k B[b][k][j]
     // for every row i), eight packed vector adds fewer per sub-tile; the sum is that of the ROUNDED probabilities, which is what
@@ -2372,18 +1964,6 @@ __device__ __forceinline__ void fa4_step(const AttnArgs& a, fa_f32x16& sc_cur, f
 #pragma unroll
         for (int r = 2; r < 16; r += 2) ts += fa_f32x2{p[r], p[r + 1]};
     }
-#elif FA4_SCALAR_SUM  // experiment: four scalar chains instead of packed adds
-    float s0 = p[0] + p[4], s1 = p[1] + p[5], s2 = p[2] + p[6], s3 = p[3] + p[7];
-    s0 += p[8]; s1 += p[9]; s2 += p[10]; s3 += p[11];
-    s0 += p[12]; s1 += p[13]; s2 += p[14]; s3 += p[15];
-    fa_f32x2 ts = fa_f32x2{s0 + s2, s1 + s3};
-#else
-    fa_f32x2 ts = fa_f32x2{p[0], p[1]};
-#if !defined(FA4_X_MFMAONLY)
-#pragma unroll
-    for (int r = 2; r < 16; r += 2) ts += fa_f32x2{p[r], p[r + 1]};
-#endif
-#endif
     const float tsum = ts.x + ts.y;
     // wave-uniform slow path; rare after the first sub-tiles.  (An un-biased instantiation entered with m != 0 -- the step right
     // after the one that moved m away from 0 -- also comes here: its next scores were computed without the bias product.)
@@ -2416,13 +1996,11 @@ __device__ __forceinline__ void fa4_step(const AttnArgs& a, fa_f32x16& sc_cur, f
             p[r] = __builtin_amdgcn_exp2f(raw[r] - mn);
             if (!TAIL) sc_next[r] -= BIASED ? delta : mn;  // computed with the old -m / without a bias product
         }
-#if FA4_MFMA_SUM
         if (!DROP) {
 #pragma unroll
             for (int t = 0; t < 8; ++t) pk[t] = pack_el16x2(p[2 * t], p[2 * t + 1]);
             ts = fa_f32x2{fa4_rowsum(pk), 0.0f};
         } else
-#endif
         {
             ts = fa_f32x2{p[0], p[1]};
 #pragma unroll
@@ -2446,24 +2024,10 @@ __device__ __forceinline__ void fa4_step(const AttnArgs& a, fa_f32x16& sc_cur, f
             p[4 * g + 3] = (w >> 24) < th ? p[4 * g + 3] : 0.0f;
         }
     }
-#if FA4_MFMA_SUM
     if (DROP) {
 #pragma unroll
         for (int t = 0; t < 8; ++t) pk[t] = pack_el16x2(p[2 * t], p[2 * t + 1]);
     }
-#else
-    uint32_t pk[8];
-#pragma unroll
-#if defined(FA4_X_MFMAONLY)
-    for (int t = 0; t < 8; ++t) pk[t] = __builtin_bit_cast(uint32_t, p[2 * t]);
-#else
-    for (int t = 0; t < 8; ++t) pk[t] = pack_el16x2(p[2 * t], p[2 * t + 1]);
-#endif
-#endif
-#if defined(FA4_X_NOPV)
-    o[0] += __builtin_bit_cast(float, pk[0] ^ pk[1] ^ pk[2] ^ pk[3]) + (float)vf0[0];
-    o[1] += __builtin_bit_cast(float, pk[4] ^ pk[5] ^ pk[6] ^ pk[7]) + (float)vf1[0];
-#else
     {
         uint32_t pw[4] = {pk[0], pk[1], pk[2], pk[3]};
         o = DYF_MFMA_32x32x16(vf0, *(el16x8_t*)pw, o, 0, 0, 0);
@@ -2472,13 +2036,13 @@ __device__ __forceinline__ void fa4_step(const AttnArgs& a, fa_f32x16& sc_cur, f
         uint32_t pw[4] = {pk[4], pk[5], pk[6], pk[7]};
         o = DYF_MFMA_32x32x16(vf1, *(el16x8_t*)pw, o, 0, 0, 0);
     }
-#endif
 }
 
 // Launch contract: DROP kernels need a.drop.mode == 1, an even token count and whole query blocks (launch_attention checks).
 // NW: waves per workgroup (4 or 8).
+constexpr int FA4_MIN_WAVES = 4;  // per SIMD
 template <bool DROP, int NW>
-__global__ __launch_bounds__(64 * NW, FA4_MINW) void flash_attention4_kernel(AttnArgs a) {
+__global__ __launch_bounds__(64 * NW, FA4_MIN_WAVES) void flash_attention4_kernel(AttnArgs a) {
     __shared__ __attribute__((aligned(16))) el16_t KV[3 * FA4_BUF];
     constexpr int QG = 32 * NW;
     const int qblocks = (a.hw + QG - 1) / QG;
@@ -2562,14 +2126,10 @@ __global__ __launch_bounds__(64 * NW, FA4_MINW) void flash_attention4_kernel(Att
     }
     // one 64-key tile; B: instantiation with / without bias products (a macro, not a lambda: nested closures kept their
     // captures in scratch memory)
-#if !defined(FA4_X_NOSTAGE)
 #define FA4_TILE_STAGE()                                                                                          \
     if (t > 0) __syncthreads(); /* every wave has left tile t - 1; tile t + 1 (written one tile ago) is visible */ \
     stage(c2b);                 /* tile t + 2 */                                                                   \
     fetch(64 * (t + 3));
-#else
-#define FA4_TILE_STAGE()
-#endif
     // sub-tile 0: next = (t, 1) in the same buffer; sub-tile 1: next = (t + 1, 0) (its scores are dropped after the last tile)
 #define FA4_TILE(B)                                                                                                                       \
     {                                                                                                                                     \
@@ -2616,39 +2176,26 @@ __global__ __launch_bounds__(64 * NW, FA4_MINW) void flash_attention4_kernel(Att
 
 hipError_t launch_attention(const AttnArgs& a, hipStream_t s) {
     // DYF_FLASH_ATTN: unset / 4 (/ 3: that kernel was retired in round 5) = flash_attention4_kernel (the pipelined form; falls back to
-    // flash_attention2_kernel for the dropout layouts it does not take), 2 = flash_attention2_kernel, 1 = the first flash form,
-    // 0 = the plain per-query kernel
-    const int flash = dyf_form("DYF_FLASH_ATTN") ? atoi(dyf_form("DYF_FLASH_ATTN")) : 4;
+    // flash_attention2_kernel for the dropout layouts it does not take), 2 = flash_attention2_kernel, 0 = the plain per-query kernel
+    const long long flash = dyf_form_int("DYF_FLASH_ATTN", 4);
     if (flash != 0 && a.hw <= 65535) {
         const int qblocks = (a.hw + 127) / 128;
-        // 64 queries per wave from 512 tokens on (DYF_FLASH_QB=1 keeps 32): shorter sequences would leave CUs without a workgroup
-        const int qb_env = dyf_form("DYF_FLASH_QB") ? atoi(dyf_form("DYF_FLASH_QB")) : 2;
-        // with dropout on the probabilities: DYF_FLASH_QB_DROP=2 selects the 64-query form (the second form spilled there)
-        const int qb_drop = dyf_form("DYF_FLASH_QB_DROP") ? atoi(dyf_form("DYF_FLASH_QB_DROP")) : 1;
         const bool drop = a.drop.mode != 0;
-        const bool qb2 = flash != 1 && a.hw >= 512 && (drop ? qb_drop == 2 && flash >= 3 : qb_env == 2);
-        const int qblocks2 = (a.hw + 255) / 256;
         // the fourth form: one 32-query block per wave, DYF_FLASH_NW = 8 (default) / 4 waves per workgroup; a sequence shorter than
         // 512 tokens stays on four waves (more workgroups)
-        const int nw_env = dyf_form("DYF_FLASH_NW") ? atoi(dyf_form("DYF_FLASH_NW")) : 8;
-        const int nw = nw_env == 16 && a.hw >= 2048 ? 16 : nw_env >= 8 && a.hw >= 512 ? 8 : 4;
+        const int nw = dyf_form_int("DYF_FLASH_NW", 8) >= 8 && a.hw >= 512 ? 8 : 4;
         const bool v4 = flash >= 3 && (!drop || (a.drop.mode == 1 && (a.hw & 3) == 0 && a.hw % (32 * nw) == 0));
         if (v4) {
-            dyf_form_note(nw == 16 ? "flash_attention4_kernel<NW=16>" : nw == 8 ? "flash_attention4_kernel<NW=8>" : "flash_attention4_kernel<NW=4>", a.n);
+            dyf_form_note(nw == 8 ? "flash_attention4_kernel<NW=8>" : "flash_attention4_kernel<NW=4>", a.n);
             const int qb4 = (a.hw + 32 * nw - 1) / (32 * nw);
-            if (nw == 16 && drop) hipLaunchKernelGGL((flash_attention4_kernel<true, 16>), dim3(a.n * a.heads * qb4), dim3(1024), 0, s, a);
-            else if (nw == 16) hipLaunchKernelGGL((flash_attention4_kernel<false, 16>), dim3(a.n * a.heads * qb4), dim3(1024), 0, s, a);
-            else if (nw == 8 && drop) hipLaunchKernelGGL((flash_attention4_kernel<true, 8>), dim3(a.n * a.heads * qb4), dim3(512), 0, s, a);
+            if (nw == 8 && drop) hipLaunchKernelGGL((flash_attention4_kernel<true, 8>), dim3(a.n * a.heads * qb4), dim3(512), 0, s, a);
             else if (nw == 8) hipLaunchKernelGGL((flash_attention4_kernel<false, 8>), dim3(a.n * a.heads * qb4), dim3(512), 0, s, a);
             else if (drop) hipLaunchKernelGGL((flash_attention4_kernel<true, 4>), dim3(a.n * a.heads * qb4), dim3(256), 0, s, a);
             else hipLaunchKernelGGL((flash_attention4_kernel<false, 4>), dim3(a.n * a.heads * qb4), dim3(256), 0, s, a);
             return hipGetLastError();
         }
-        const bool qb2v2 = qb2 && !drop;
-        dyf_form_note(flash == 1 ? "flash_attention_kernel" : qb2v2 ? "flash_attention2_kernel<QB=2>" : "flash_attention2_kernel<QB=1>", a.n);
-        if (flash == 1) hipLaunchKernelGGL(flash_attention_kernel, dim3(a.n * a.heads * qblocks), dim3(256), 0, s, a);
-        else if (qb2v2) hipLaunchKernelGGL((flash_attention2_kernel<false, 2>), dim3(a.n * a.heads * qblocks2), dim3(256), 0, s, a);
-        else if (drop) hipLaunchKernelGGL((flash_attention2_kernel<true, 1>), dim3(a.n * a.heads * qblocks), dim3(256), 0, s, a);
+        dyf_form_note("flash_attention2_kernel<QB=1>", a.n);
+        if (drop) hipLaunchKernelGGL((flash_attention2_kernel<true, 1>), dim3(a.n * a.heads * qblocks), dim3(256), 0, s, a);
         else hipLaunchKernelGGL((flash_attention2_kernel<false, 1>), dim3(a.n * a.heads * qblocks), dim3(256), 0, s, a);
         return hipGetLastError();
     }

@@ -129,7 +129,7 @@ dyf_status rconv(dyf_engine* e, const el16_t* s0, int c0, const el16_t* s1, int 
 
 // the plain 3x3 conv behind a nearest x2 upsample (output plane h x w) will run on the one form that folds the upsample into its gather
 bool rconv_nearest_fusable(dyf_engine* e, int c0, int n, int h, int w, int cout, const el16_t* wpk) {
-    if (dyf_form("DYF_FUSE_NEAREST") && atoi(dyf_form("DYF_FUSE_NEAREST")) == 0) return false;  // A/B + parity test
+    if (dyf_form_int("DYF_FUSE_NEAREST", 1) == 0) return false;  // A/B + parity test
     if (!e->cfg.enable_mfma || (h & 1) || (w & 1)) return false;
     ConvArgs a{};
     a.src0 = (const el16_t*)wpk;  // (any non-null pointer: the predicates look at shapes)
@@ -553,7 +553,7 @@ dyf_status rn_forward(dyf_engine* e, int which, const Source* srcs, int nsrc, in
                         el16_t** out) -> dyf_status {
         el16_t* t1 = pool.get();
         // GroupNorm statistics from the conv's fp32 accumulators where the kernel form produces them (conv_up_halo_kernel<5>)
-        const bool fuse_stats = !(dyf_form("DYF_GN_CONV_STATS") && atoi(dyf_form("DYF_GN_CONV_STATS")) == 0);
+        const bool fuse_stats = dyf_form_int("DYF_GN_CONV_STATS", 1) != 0;
         const bool ask = fuse_stats && gn_part_supported(b.cout, c.groups) &&
                          (size_t)nb * conv_halo5_gn_slots(hh, ww) * (b.cout / 8) * 2 <= r->gn_part_floats;
         int slots1 = 0, slots2 = 0;

@@ -194,7 +194,7 @@ dyf_status dyf_set_row_offset(dyf_engine* engine, uint32_t first_row);
  * gaps of one group are covered by the kernels of the others.  Row g*per + i of the call is row i of group g and draws the
  * masks / noise of global row (row offset + g*per + i): the generator streams are those of the ungrouped call.  Default: chosen
  * at dyf_engine_create from the architecture and max_batch (ResNet-UNet on planes <= 128 x 128, not batch_invariant: 3 groups from
- * 432 000 pixels x rows = 120 rows of 60 x 60, 2 from 230 400 = 64 rows; otherwise 1; environment DYF_ROW_GROUPS overrides).  Must be called before dyf_load_weights.
+ * 432 000 pixels x rows = 120 rows of 60 x 60, 2 from 230 400 = 64 rows; otherwise 1; the kernel-form switch DYF_ROW_GROUPS overrides).  Must be called before dyf_load_weights.
  * Calls with fewer than 32 rows, with injected masks / noise, and every other entry point run on the engine itself.
  * Three groups plus the caller's stream fill the 4 hardware queues of a HIP process: with other busy streams or other live engines
  * in the process two groups are the robust choice.

@@ -109,10 +109,9 @@ void dyf_debug_form_log(int32_t enable);
 int32_t dyf_debug_form_log_read(char* buf, int32_t cap);
 
 /* Kernel-form switches (tests/ and tools/ only).  The launchers choose between equivalent kernel forms from tile counts; the
- * parity tests force each form on small problems, the A/B tools flip one form at a time, a few keys are wrong-results timing
- * probes.  This call is the ONLY way to set them: libdyffusion_hip.so reads none of them from the environment (the only
- * environment variables it reads are DYF_VERBOSE -- print the engine's form policy at creation -- and DYF_RCCL_LIB -- the librccl
- * to dlopen).  Process-wide (per library: the bf16 and the fp16 build each hold their own table); read per launch / per engine
+ * parity tests force each form on small problems, the A/B tools flip one form at a time.  This call is the ONLY way to set them:
+ * libdyffusion_hip.so reads none of them from the environment (the only environment variables it reads are DYF_VERBOSE -- print
+ * the engine's form policy at creation -- and DYF_RCCL_LIB -- the librccl to dlopen).  Process-wide (per library: the bf16 and the fp16 build each hold their own table); read per launch / per engine
  * creation / per weight upload as DESIGN.md 7.1 lists.  key = the historic switch name ("DYF_IGEMM2_MIN_TILES", ...), value = its
  * text; value NULL removes the key, key NULL removes every key.  dyf_debug_forms writes "key=value;..." like
  * dyf_debug_form_log_read. */

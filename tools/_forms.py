@@ -7,7 +7,7 @@ import os
 # variables that are not kernel-form switches: the library's two user-facing ones, the python binding's, bench.py's, the tools' own
 NOT_FORMS = ("DYF_VERBOSE", "DYF_RCCL_LIB", "DYF_LIB", "DYF_LIB_F16", "DYF_BENCH_", "DYF_DIST_BACKEND", "DYF_CPU_THREADS",
              "DYF_ALLOW_BF16_LONG_ROLLOUT", "DYF_PMC_REGEX", "DYF_OISST_DTYPE", "DYF_NO_GRAPH", "DYF_SMALL_MAXB", "DYF_ORACLE_CACHE",
-             "DYF_WRITE_ORACLE_CACHE", "DYF_TEST_FORMS", "DYF_EXPERIMENT_BUILD")
+             "DYF_WRITE_ORACLE_CACHE", "DYF_TEST_FORMS")
 
 
 def forward_env_forms(verbose=True):
