@@ -6,9 +6,14 @@
 #include <string>
 #include <vector>
 
-// kernel-form log (common.h dyf_form_note; test seam dyf_debug_form_log*)
+// control side of the process-wide seams (seams.hip; the hot side is inline in common.h), reached through the test entry points of
+// include/dyffusion_hip_testing.h: kernel-form log, kernel-form switch table, named-kernel timing
 void dyf_form_log_enable(bool on);
 std::string dyf_form_log_text();
+void dyf_form_set(const char* key, const char* value);  // null key: clear all; null value: erase the key
+std::string dyf_form_text();
+void dyf_prof_arm(const char* name);  // nullptr disarms; pending records are dropped
+void dyf_prof_collect(double* total_ms, double* total_bytes, int* launches);  // after the stream has been synchronised; disarms
 
 struct ConvArgs {
     // input: channel-concatenation of up to two NHWC bf16 tensors (skip connections are never materialised)
@@ -23,7 +28,7 @@ struct ConvArgs {
     int cout;
     const el16_t* wpk;   // packed weights [cout][kh*kw][c0+c1] bf16
     const el16_t* wpk_frag;  // the same weights in MFMA fragment order (pack_conv_frag) for conv_igemm2, or null: looked up
-                             // in the registry (conv_register_frag) by launch_conv
+                             // in the registry (conv_register_frag) by conv_choose_form
     // fused x2 bilinear upsample in front of a 3x3/s1/p1 conv: sources are the LOW-res tensors (h, w), output is
     // (2h, 2w); wpk_up holds the phase-decomposed weights [4][cout][16][c0+c1] (pack_up2x_weights)
     int up2x;
@@ -82,25 +87,49 @@ struct ConvArgs {
 // floats of ConvArgs::up_border for an n x (2h x 2w) x cout output
 inline size_t conv_up_border_floats(int n, int h, int w, int cout) { return (size_t)n * (4 * (size_t)w + 4 * (size_t)h - 4) * cout; }
 
+// ================================================================================================ dispatch API (conv_dispatch.hip)
 // path: 0 direct (any shape), 1 implicit-GEMM MFMA (needs c0 % 64 == 0, c1 % 64 == 0, cout % 64 == 0)
 hipError_t conv_init();
 bool conv_mfma_supported(const ConvArgs& a);
+// Which kernel form a conv takes -- the performance policy -- is decided in ONE place: conv_choose_form returns a value, launches
+// nothing and touches no stream.  launch_conv* = choose, copy the choice's fields into the ConvArgs, call that form's launcher.
+enum class ConvForm { Invalid /* hipErrorInvalidValue */, None /* GnFused: no fused form fits */, Direct, Igemm128, Igemm256x64, UpHalo,
+                      Halo3, Rows3, Halo5, HaloS2, Enc0Stem, Igemm2, Skinny, Gn16 };
+enum class ConvWant { Plain, Stats /* GroupNorm statistics where the form produces them */, GnFused };
+struct ConvChoice {
+    ConvForm form;
+    const el16_t* frag;  // the form's fragment-ordered weights from the registries (wpk_up_frag / wpk_frag / enc0-stem argument), or null
+    int gn_slots;        // Stats: ConvArgs::gn_slots (0: the launch writes no statistics); GnFused: GnFuse::slots
+    int bm;              // GnFused on igemm2: GnFuse::bm (128 / 256), else 0
+};
+ConvChoice conv_choose_form(const ConvArgs& a, int path, ConvWant want);
 hipError_t launch_conv(const ConvArgs& a, int path, hipStream_t stream);
 // launch_conv for a conv whose output feeds a GroupNorm (a.gn_part != null): *gn_slots receives the partial-sum slots per sample
 // the launch wrote (0: this kernel form does not produce statistics -- the caller runs the statistics pass)
 hipError_t launch_conv_stats(const ConvArgs& a, int path, hipStream_t stream, int* gn_slots);
 // launch_conv for a conv followed by GroupNorm + FiLM + SiLU + Dropout (+ residual), a.gnf filled in except `slots`: *fused = the
-// launch did all of it (conv_up_halo_kernel<5, 2>, conv_igemm2_kernel<2, true>); false = NOTHING was launched (the shape / batch is
-// not served by a fused form: the caller runs the conv and the GroupNorm kernels)
+// launch did all of it (conv_gn16_kernel, conv_up_halo_kernel<5, 2>, conv_igemm2_kernel<2, true>); false = NOTHING was launched (the
+// shape / batch is not served by a fused form: the caller runs the conv and the GroupNorm kernels)
 hipError_t launch_conv_gn_fused(const ConvArgs& a, int path, hipStream_t stream, bool* fused);
+// upper bound of GnFuse::slots on an h x w plane over the fused forms (sizing of GnFuse::gran), 0 = never fused
 int conv_gn_fused_max_slots(int h, int w);
-bool conv_igemm2_tile2d(int ho, int wo);  // conv_igemm2_kernel tiles this output plane 2-D (TH x 16 pixel tiles inside one sample)
-int conv_igemm2_gn_slots_bm128(int ho, int wo);  // ... of its 128-pixel tile form (64-row statistics slabs)
-int conv_igemm2_gn_slots(int ho, int wo);  // slots per sample of the fused conv_igemm2_kernel<2> on an ho x wo output plane (0: not served)  // upper bound of GnFuse::slots on an h x w plane (sizing of GnFuse::gran), 0 = never fused
-int conv_halo5_gn_slots(int h, int w);  // slots per sample of conv_up_halo_kernel<5> on an h x w plane (sizing of gn_part)
+// launch_conv(a, 1, ...) of this plain 3x3 conv (no statistics, no fused GroupNorm) will run on conv_up_halo_kernel<5> -- the one form
+// that can take ConvArgs::up_nearest
+bool conv_plain3x3_takes_halo5(const ConvArgs& a);
+
+// ================================================================================================ per-form launchers and predicates
+// conv.hip: the direct kernel (any shape; hipErrorInvalidValue for up2x) and conv_igemm_kernel (<128,128> / <256,64> by cout % 128,
+// fused-upsample instantiation by up2x; split-K is the launcher's own choice)
+hipError_t launch_conv_direct(const ConvArgs& a, hipStream_t stream);
+hipError_t launch_conv_igemm(const ConvArgs& a, hipStream_t stream);
 void pack_up2x_weights(const float* w, int cout, int cin, el16_t* out);
+// sum of ConvArgs::splitk raw fp32 partials [split][m][cout] (in split order) + the conv epilogue, 4 channels per thread (conv.hip);
+// needs cout % 4 == 0
+hipError_t launch_conv_splitk_finish4(const ConvArgs& a, long long M, hipStream_t stream);
 // halo form of the fused x2-upsample conv (conv_up_halo.hip): 16x16 low-res tile x 4 phases x 64 channels per workgroup
 bool conv_up_halo_supported(const ConvArgs& a);
+hipError_t conv_up_halo_init();
+hipError_t launch_conv_up_halo(const ConvArgs& a, hipStream_t stream);
 void pack_up2x_frag(const el16_t* wpk_up, int cout, int cin, el16_t* out);
 bool plan_up_sparse_columns(const std::vector<uint8_t>& needed, int w, std::vector<int16_t>& cols, std::vector<int16_t>& cbase,
                             std::vector<int16_t>& cidx, std::vector<int16_t>& col_map, int& ntiles, int& nvalid0, int& nvalid1,
@@ -117,15 +146,10 @@ bool plan_up_sparse_columns_mixed(const std::vector<uint8_t>& needed, int w, int
 bool conv_halo_rows_up_supported(const ConvArgs& a);   // in addition to conv_up_halo_supported
 bool conv_halo_rows3_supported(const ConvArgs& a);     // in addition to conv_halo3_supported (h % 8 / w % 16 not needed)
 hipError_t conv_halo_rows_init();
-// sum of ConvArgs::splitk raw fp32 partials [split][m][cout] (in split order) + the conv epilogue, 4 channels per thread (conv.hip);
-// needs cout % 4 == 0
-hipError_t launch_conv_splitk_finish4(const ConvArgs& a, long long M, hipStream_t stream);
 hipError_t launch_conv_halo_rows_up(const ConvArgs& a, hipStream_t stream);  // main kernel only (after up_border_kernel)
 hipError_t launch_conv_halo_rows3(const ConvArgs& a, hipStream_t stream);
-hipError_t conv_up_halo_init();
-hipError_t launch_conv_up_halo(const ConvArgs& a, hipStream_t stream);
 // plain 3x3 / stride 1 / pad 1 conv on the halo kernel (conv_up_halo.hip, SP = 2): cout % 256 == 0, h % 8 == 0, w % 16 == 0;
-// ConvArgs::wpk_up_frag carries the pack_halo3_frag weights (looked up in the registry by launch_conv)
+// ConvArgs::wpk_up_frag carries the pack_halo3_frag weights (looked up in the registry by conv_choose_form)
 bool conv_halo3_supported(const ConvArgs& a);
 hipError_t launch_conv_halo3(const ConvArgs& a, hipStream_t stream);
 void pack_halo3_frag(const el16_t* wpk, int cout, int cin, el16_t* out);
@@ -136,9 +160,7 @@ hipError_t launch_conv_halo_s2(const ConvArgs& a, hipStream_t stream);
 void pack_halo_s2_frag(const el16_t* wpk, int cout, int cin, el16_t* out);
 // plain 3x3 / s1 / p1 conv with cout % 64 == 0 on ANY plane size (SP = 5: four pixel sub-tiles per workgroup, ragged edges)
 bool conv_halo5_supported(const ConvArgs& a);
-// launch_conv(a, 1, ...) of this plain 3x3 conv (no statistics, no fused GroupNorm) will run on conv_up_halo_kernel<5> -- the one form
-// that can take ConvArgs::up_nearest
-bool conv_plain3x3_takes_halo5(const ConvArgs& a);
+int conv_halo5_gn_slots(int h, int w);  // slots per sample of conv_up_halo_kernel<5> on an h x w plane (sizing of gn_part)
 hipError_t launch_conv_halo5(const ConvArgs& a, hipStream_t stream);
 void pack_halo3_frag64(const el16_t* wpk, int cout, int cin, el16_t* out);
 // the same convs WITH the fused GroupNorm epilogue on 16 x 16-pixel tiles, three workgroups per CU (conv_gn16.hip); fragments of
@@ -146,12 +168,6 @@ void pack_halo3_frag64(const el16_t* wpk, int cout, int cin, el16_t* out);
 bool conv_gn16_supported(const ConvArgs& a);
 int conv_gn16_slots(int h, int w);
 hipError_t launch_conv_gn16(const ConvArgs& a, hipStream_t stream);
-void conv_register_halo3_frag(const el16_t* wpk_dev, const el16_t* frag_dev);
-const el16_t* conv_lookup_halo3_frag(const el16_t* wpk_dev);
-// 3 x 3 convs with cout % 256 == 0 keep the 256-channel-block fragments (pack_halo3_frag) in the halo3 registry; their 64-channel-block
-// copy (pack_halo3_frag64, what conv_gn16_kernel streams) lives here
-void conv_register_frag64(const el16_t* wpk_dev, const el16_t* frag_dev);
-const el16_t* conv_lookup_frag64(const el16_t* wpk_dev);
 // enc0 on the fused stem (conv_enc0_stem.hip): persistent, weights resident in LDS, pixel fragments straight from global memory;
 // the fragments (pack_enc0_stem_frag) are registered in the halo3 registry under the composed weights' pointer
 bool conv_enc0_stem_supported(const ConvArgs& a);
@@ -163,11 +179,24 @@ bool conv_igemm2_supported(const ConvArgs& a);
 hipError_t conv_igemm2_init();
 hipError_t launch_conv_igemm2(const ConvArgs& a, hipStream_t stream);
 void pack_conv_frag(const el16_t* wpk, int cout, int taps, int cin, el16_t* out);
+bool conv_igemm2_tile2d(int ho, int wo);  // conv_igemm2_kernel tiles this output plane 2-D (TH x 16 pixel tiles inside one sample)
+int conv_igemm2_gn_slots(int ho, int wo);  // slots per sample of the fused conv_igemm2_kernel<2> on an ho x wo output plane (0: not served)
+int conv_igemm2_gn_slots_bm128(int ho, int wo);  // ... of its 128-pixel tile form (64-row statistics slabs)
 // small-M 1x1 / 2x2-s2 convs (conv_skinny.hip): 32 x 32 tiles, K split over the workgroup's four waves, one launch (replaces
 // conv_igemm_kernel<128,128> + split-K + conv_splitk_finish_kernel in the few-rows regime); fragments: pack_conv_frag
 bool conv_skinny_supported(const ConvArgs& a);
 hipError_t launch_conv_skinny(const ConvArgs& a, hipStream_t stream);
-// registry device-pointer(wpk) -> device-pointer(fragment-ordered copy); filled when weights are uploaded
-void conv_register_frag(const el16_t* wpk_dev, const el16_t* frag_dev);
-void conv_unregister_frag(const void* wpk_dev);
+
+// ================================================================================================ registries (conv_dispatch.hip)
+// device-pointer(wpk) -> device-pointer(fragment-ordered copy), one map per fragment order; filled when weights are uploaded, read by
+// conv_choose_form; conv_unregister_frag drops the pointer from all of them
+void conv_register_frag(const el16_t* wpk_dev, const el16_t* frag_dev);  // pack_conv_frag (igemm2, skinny)
 const el16_t* conv_lookup_frag(const el16_t* wpk_dev);
+// halo-kernel order: pack_halo3_frag (3x3, cout % 256 == 0), pack_halo3_frag64 (other 3x3), pack_halo_s2_frag, pack_enc0_stem_frag
+void conv_register_halo3_frag(const el16_t* wpk_dev, const el16_t* frag_dev);
+const el16_t* conv_lookup_halo3_frag(const el16_t* wpk_dev);
+// 3 x 3 convs with cout % 256 == 0 keep the 256-channel-block fragments (pack_halo3_frag) in the halo3 registry; their 64-channel-block
+// copy (pack_halo3_frag64, what conv_gn16_kernel streams) lives here
+void conv_register_frag64(const el16_t* wpk_dev, const el16_t* frag_dev);
+const el16_t* conv_lookup_frag64(const el16_t* wpk_dev);
+void conv_unregister_frag(const void* wpk_dev);

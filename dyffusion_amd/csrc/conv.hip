@@ -15,104 +15,16 @@
 //   * operands swapped (D^T = W X^T): an accumulator lane holds 4 consecutive channels of one pixel, so the epilogue --
 //     per-(sample, channel) affine (conv bias + BatchNorm + FiLM folded) -> activation -> dropout (+ residual) -> bf16 --
 //     runs straight out of the accumulators (v_permlane32_swap pairs lanes l / l+32 for 16-B stores): no LDS round trip.
-//   * dispatch (launch_conv): fused-upsample convs and plain 3x3-s1 / 4x4-s2 convs with 256-channel blocks -> the halo
-//     kernel (conv_up_halo.hip); other convs with cout % 128 == 0 and >= 384 tiles -> conv_igemm2_kernel (weights
+//   * dispatch (conv_dispatch.hip conv_choose_form): fused-upsample convs and plain 3x3-s1 / 4x4-s2 convs with 256-channel
+//     blocks -> the halo kernel (conv_up_halo.hip); other convs with cout % 128 == 0 and >= 384 tiles -> conv_igemm2_kernel (weights
 //     streamed in fragment order); the rest -> this file's conv_igemm_kernel; channels % 64 != 0 -> conv_direct_kernel.
 //   * blockIdx -> tile map is XCD-aware (block b runs on XCD b % 8): every XCD walks a contiguous range of tiles so
 //     the 3x3 / 4x4 halo re-reads of neighbouring tiles hit that XCD's own L2.
 #include "conv.h"
 
+#include <algorithm>
 #include <type_traits>
 
-#include <cstdlib>
-#include <deque>
-#include <map>
-#include <mutex>
-#include <string>
-
-// ---- kernel-form log (common.h): form name + "@rows" -> launches noted since it was enabled
-bool g_dyf_form_log_on = false;
-static std::mutex g_form_mu;
-static std::map<std::string, long long> g_form_log;
-void dyf_form_note_slow(const char* form, long long rows) {
-    std::lock_guard<std::mutex> lk(g_form_mu);
-    ++g_form_log[std::string(form) + "@" + std::to_string(rows)];
-}
-void dyf_form_log_enable(bool on) {
-    std::lock_guard<std::mutex> lk(g_form_mu);
-    g_form_log.clear();
-    g_dyf_form_log_on = on;
-}
-std::string dyf_form_log_text() {
-    std::lock_guard<std::mutex> lk(g_form_mu);
-    std::string t;
-    for (auto& kv : g_form_log) t += kv.first + "=" + std::to_string(kv.second) + ";";
-    return t;
-}
-// ---- kernel-form switches (common.h dyf_form): key -> value, set only through dyf_debug_set_form.  Values are interned and never
-// freed (a pointer handed out by dyf_form stays valid for the life of the process).
-int g_dyf_form_count = 0;
-static std::map<std::string, const char*> g_form_values;
-static std::deque<std::string> g_form_arena;
-const char* dyf_form_slow(const char* key) {
-    std::lock_guard<std::mutex> lk(g_form_mu);
-    auto it = g_form_values.find(key);
-    return it == g_form_values.end() ? nullptr : it->second;
-}
-void dyf_form_set(const char* key, const char* value) {
-    std::lock_guard<std::mutex> lk(g_form_mu);
-    if (!key) g_form_values.clear();
-    else if (!value) g_form_values.erase(key);
-    else {
-        g_form_arena.emplace_back(value);
-        g_form_values[key] = g_form_arena.back().c_str();
-    }
-    __atomic_store_n(&g_dyf_form_count, (int)g_form_values.size(), __ATOMIC_RELEASE);
-}
-std::string dyf_form_text() {
-    std::lock_guard<std::mutex> lk(g_form_mu);
-    std::string t;
-    for (auto& kv : g_form_values) t += kv.first + "=" + kv.second + ";";
-    return t;
-}
-// ---- named-kernel timing (common.h KernelProf): (start, stop, algorithmic bytes) of every launch of the armed name
-const char* g_dyf_prof_name = nullptr;
-static std::string g_prof_name_store;
-struct ProfRec { hipEvent_t e0, e1; double bytes; };
-static std::deque<ProfRec> g_prof_recs;
-void dyf_prof_begin(hipStream_t st, double bytes) {
-    std::lock_guard<std::mutex> lk(g_form_mu);  // (records of concurrent host threads interleave but stay whole; ONE armed name per process)
-    ProfRec r{nullptr, nullptr, bytes};
-    if (g_prof_recs.size() >= 16384 || hipEventCreate(&r.e0) != hipSuccess || hipEventCreate(&r.e1) != hipSuccess) return;
-    (void)hipEventRecord(r.e0, st);
-    g_prof_recs.push_back(r);
-}
-void dyf_prof_end(hipStream_t st) {
-    std::lock_guard<std::mutex> lk(g_form_mu);
-    if (!g_prof_recs.empty()) (void)hipEventRecord(g_prof_recs.back().e1, st);
-}
-static void prof_arm_locked(const char* name) {
-    for (auto& r : g_prof_recs) { (void)hipEventDestroy(r.e0); (void)hipEventDestroy(r.e1); }
-    g_prof_recs.clear();
-    g_prof_name_store = name ? name : "";
-    g_dyf_prof_name = name ? g_prof_name_store.c_str() : nullptr;
-}
-void dyf_prof_arm(const char* name) {  // nullptr disarms; pending records are dropped
-    std::lock_guard<std::mutex> lk(g_form_mu);
-    prof_arm_locked(name);
-}
-// after the stream has been synchronised: total ms, total bytes, launches of the armed name; disarms
-void dyf_prof_collect(double* total_ms, double* total_bytes, int* launches) {
-    std::lock_guard<std::mutex> lk(g_form_mu);
-    double ms = 0.0, by = 0.0;
-    int n = 0;
-    for (auto& r : g_prof_recs) {
-        float t = 0.0f;
-        if (hipEventElapsedTime(&t, r.e0, r.e1) == hipSuccess) { ms += t; by += r.bytes; ++n; }
-    }
-    *total_ms = ms; *total_bytes = by; *launches = n;
-    prof_arm_locked(nullptr);
-}
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 
 #define LDS_PTR(p) ((__attribute__((address_space(3))) void*)(p))
@@ -750,130 +662,14 @@ hipError_t conv_init() {
     return e;
 }
 
-// plain 3x3 / s1 convs with 64 or 128 (a multiple of 64 that is not one of 256) output channels on planes of any size: SP = 5 of the
-// halo kernel, when the 16 x 32 tiles cover the plane reasonably (>= 60 %) and the launch has enough of them
-static bool halo5_policy(const ConvArgs& a) {
-    if (!(!a.up2x && a.kh == 3 && a.kw == 3 && a.stride == 1 && a.cout % 64 == 0 && a.cout % 256 != 0 && a.out_f32 == nullptr &&
-          a.residual == nullptr))
-        return false;
-    if (dyf_form_int("DYF_HALO5", 1) == 0) return false;
-    const long long h5_min = dyf_form_int("DYF_HALO5_MIN_TILES", 64);
-    const long long nsel = a.n_sel > 0 ? a.n_sel : a.n;
-    ConvArgs b = a;
-    b.wpk_up_frag = conv_lookup_halo3_frag(b.wpk);
-    const long long ty = (a.h + 15) / 16, tx = (a.w + 31) / 32;
-    const long long tiles5 = nsel * ty * tx * (a.cout / 64);
-    const bool covers = 10ll * a.h * a.w >= 6ll * ty * 16 * tx * 32;
-    return b.wpk_up_frag && covers && tiles5 >= h5_min && conv_halo5_supported(b);
+// This file's two forms as plain launchers; which form a conv takes is decided in conv_dispatch.hip (conv_choose_form).
+hipError_t launch_conv_igemm(const ConvArgs& a, hipStream_t stream) {
+    if (a.cout % 128 == 0)
+        return a.up2x ? launch_igemm<128, 128, 2, 2, 1>(a, stream) : launch_igemm<128, 128, 2, 2, 0>(a, stream);
+    return a.up2x ? launch_igemm<256, 64, 4, 1, 1>(a, stream) : launch_igemm<256, 64, 4, 1, 0>(a, stream);
 }
 
-bool conv_plain3x3_takes_halo5(const ConvArgs& a) {
-    // (the forms launch_conv_stats tries BEFORE SP = 5 need up2x or cout % 256 == 0: a conv that passes halo5_policy reaches it)
-    return conv_mfma_supported(a) && a.gn_part == nullptr && a.gnf.gran == nullptr && halo5_policy(a);
-}
-
-hipError_t launch_conv(const ConvArgs& a, int path, hipStream_t stream) {
-    if (a.gn_part == nullptr) return launch_conv_stats(a, path, stream, nullptr);
-    ConvArgs b = a;  // statistics are only produced through launch_conv_stats (the caller must learn whether they were)
-    b.gn_part = nullptr;
-    return launch_conv_stats(b, path, stream, nullptr);
-}
-
-hipError_t launch_conv_stats(const ConvArgs& a_in, int path, hipStream_t stream, int* gn_slots) {
-    if (gn_slots) *gn_slots = 0;
-    ConvArgs a = a_in;
-    float* const gn_part = gn_slots ? a_in.gn_part : nullptr;
-    a.gn_part = nullptr;  // only the form below that produces statistics sees the buffer
-    a.gn_slots = 0;
-    const long long nsel = a.n_sel > 0 ? a.n_sel : a.n;  // rows the kernel form is chosen for (ConvArgs::n_sel)
-    // a fused nearest upsample exists in ONE form: refuse rather than read a low-resolution tensor as the full-size one
-    if (a.up_nearest && !(path == 1 && conv_mfma_supported(a) && halo5_policy(a) && a.h % 2 == 0 && a.w % 2 == 0 && a.c1 == 0)) return hipErrorInvalidValue;
-    if (path == 1 && conv_mfma_supported(a)) {
-        const bool use_halo = dyf_form_int("DYF_UP_HALO", 1) != 0;
-        // halo form from 32 x 32 low-res planes on; below that (dec2: 16 x 16, 2 tiles per image) the materialised upsample +
-        // plain 3x3 halo conv is still slightly ahead (7 715 vs 7 690 fields/s with DYF_HALO_MIN_PLANE=16: 640 workgroups of
-        // the fused form fill 1.25 rounds of the 512 resident ones)
-        const int halo_min = dyf_form_int("DYF_HALO_MIN_PLANE", 32);
-        if (a.up2x && a.up_cols)  // sparse-column form: only the halo kernel writes the compact output tensor
-            return conv_up_halo_supported(a) ? launch_conv_up_halo(a, stream) : hipErrorInvalidValue;
-        if (a.up2x && use_halo && a.h >= halo_min && a.w >= halo_min && conv_up_halo_supported(a)) return launch_conv_up_halo(a, stream);
-        // plain 3x3 / s1 convs with cout % 256 == 0 on 8x16-tileable planes: the halo kernel (one window DMA per chunk
-        // instead of one gather per tap); DYF_HALO3=0 disables, DYF_HALO3_MIN_TILES sets the smallest launch (measured at NB = 80,
-        // enc3 with 320 tiles 115 -> 94 us; round 4, with the rows forms: from 80 tiles on -- NS at 7 / 10 / 25 rows +3.4 / +5.7 /
-        // +2.5 % against the 256 of rounds 1-3, nothing lost at 4 or 80 rows; 64 costs 2.4 % at 4 rows)
-        if (!a.up2x && a.kh == 3 && a.kw == 3 && a.cout % 256 == 0 && a.out_f32 == nullptr && a.residual == nullptr) {
-            if (dyf_form_int("DYF_HALO3", 1) != 0) {
-                ConvArgs b = a;
-                b.wpk_up_frag = conv_lookup_halo3_frag(b.wpk);
-                const long long min_tiles3 = dyf_form_int("DYF_HALO3_MIN_TILES", 80);
-                const long long tiles3 = (nsel * a.h * a.w / 128) * (a.cout / 256);
-                const bool rows = dyf_form_int("DYF_HALO_ROWS", 1) != 0;
-                if (b.wpk_up_frag && tiles3 >= min_tiles3 && conv_halo3_supported(b))
-                    return rows && conv_halo_rows3_supported(b) ? launch_conv_halo_rows3(b, stream) : launch_conv_halo3(b, stream);
-            }
-        }
-        // 3x3 / s1 convs with 64 or 128 (any multiple of 64 that is not one of 256) output channels -- the ResNet-UNet levels --
-        // on planes of any size: SP = 5 of the halo kernel, when the 16 x 32 tiles cover the plane reasonably (>= 60 %: not
-        // 15 x 15).  DYF_HALO5=0 disables, DYF_HALO5_MIN_TILES sets the smallest launch (64 tiles since round 4: with the GroupNorm
-        // fused into this form a small launch also saves the three GroupNorm kernels behind the implicit-GEMM fallback -- OISST
-        // shapes at 38 / 75 rows +5.8 / +3 % against the 256 of round 3).
-        if (halo5_policy(a)) {
-            {
-                ConvArgs b = a;
-                b.wpk_up_frag = conv_lookup_halo3_frag(b.wpk);
-                {
-                    if (gn_part && a.act == ACT_NONE && a.drop.mode == 0) {  // statistics of the raw conv output
-                        b.gn_part = gn_part;
-                        b.gn_slots = conv_halo5_gn_slots(a.h, a.w);
-                        *gn_slots = b.gn_slots;
-                    }
-                    return launch_conv_halo5(b, stream);
-                }
-            }
-        }
-        if (a.pix_pitch0 == 16 && conv_enc0_stem_supported(a)) {  // enc0 on the fused stem: HBM-bound, its own persistent kernel
-            const el16_t* f = conv_lookup_halo3_frag(a.wpk);
-            if (f) return launch_conv_enc0_stem(a, f, stream);
-        }
-        if (!a.up2x && a.kh == 4 && a.kw == 4 && a.stride == 2 && a.cout % 128 == 0 && a.c1 == 0 && a.out_f32 == nullptr &&
-            a.residual == nullptr && a.pix_pitch0 == 0) {  // 4x4 / s2 convs: the same kernel on the space-to-depth view
-            if (dyf_form_int("DYF_HALO3", 1) != 0) {
-                ConvArgs b = a;
-                b.wpk_up_frag = conv_lookup_halo3_frag(b.wpk);
-                // (its own switch since round 5; DYF_HALO3_MIN_TILES still applies when unset)
-                const long long min_tiles3 = dyf_form_int("DYF_HALO_S2_MIN_TILES", dyf_form_int("DYF_HALO3_MIN_TILES", 80));
-                // cout % 256 == 0: 8 x 16 tiles x 256 channels; else 16 x 16 tiles x 128 channels
-                const long long tiles3 = a.cout % 256 == 0 ? (nsel * a.ho * a.wo / 128) * (a.cout / 256)
-                                                           : (nsel * a.ho * a.wo / 256) * (a.cout / 128);
-                if (b.wpk_up_frag && tiles3 >= min_tiles3 && conv_halo_s2_supported(b)) return launch_conv_halo_s2(b, stream);
-            }
-        }
-        const bool use_igemm2 = dyf_form_int("DYF_IGEMM2", 1) != 0;
-        if (!a.up2x && use_igemm2 && a.cout % 64 == 0) {  // cout % 128 == 0: 256 x 128 tiles, else 256 x 64
-            ConvArgs b = a;
-            if (!b.wpk_frag) b.wpk_frag = conv_lookup_frag(b.wpk);
-            // 256 x 128 tiles pay off once they fill the chip (2 workgroups x 256 CUs); below that the 128 x 128 form's
-            // finer tiles win (measured at NB = 50: dec2/enc2 with 400 tiles +9 %/+4 %, enc3 with 200 tiles -20 %)
-            const long long tiles2 = ((nsel * a.ho * a.wo + 255) / 256) * (a.cout % 128 == 0 ? a.cout / 128 : a.cout / 64);
-            const long long min_tiles = dyf_form_int("DYF_IGEMM2_MIN_TILES", 384);  // tests force the form on small problems
-            if (tiles2 >= min_tiles && conv_igemm2_supported(b)) return launch_conv_igemm2(b, stream);
-        }
-        // few rows: 1x1 / 2x2-s2 convs whose 128 x 128 tiles would not even fill a quarter of the chip (the split-K regime of
-        // launch_igemm) run on conv_skinny_kernel -- K split over the four waves of a 32 x 32 tile, one launch (DYF_SKINNY=0 disables)
-        if (!a.up2x && a.cout % 128 == 0) {
-            const bool skinny = dyf_form_int("DYF_SKINNY", 1) != 0;
-            const long long tiles128 = ((nsel * a.ho * a.wo + 127) / 128) * (a.cout / 128);
-            ConvArgs b = a;
-            if (!b.wpk_frag) b.wpk_frag = conv_lookup_frag(b.wpk);
-            // (64 tiles of 128 x 128: NS at 1 / 4 / 7 / 10 rows +10.6 / +4 / +2 / +1 %, nothing lost at 25 / 38; at 128 the 25- and
-            // 38-row rollouts lose 2.5 %)
-            const long long sk_max = dyf_form_int("DYF_SKINNY_MAX_TILES", 64);
-            if (skinny && tiles128 <= sk_max && conv_skinny_supported(b)) return launch_conv_skinny(b, stream);
-        }
-        if (a.cout % 128 == 0)
-            return a.up2x ? launch_igemm<128, 128, 2, 2, 1>(a, stream) : launch_igemm<128, 128, 2, 2, 0>(a, stream);
-        return a.up2x ? launch_igemm<256, 64, 4, 1, 1>(a, stream) : launch_igemm<256, 64, 4, 1, 0>(a, stream);
-    }
+hipError_t launch_conv_direct(const ConvArgs& a, hipStream_t stream) {
     if (a.up2x) return hipErrorInvalidValue;  // the direct kernel has no fused-upsample form: caller materialises
     const long long total = (long long)a.n * a.ho * a.wo * a.cout;
     const int threads = 256;
@@ -881,123 +677,6 @@ hipError_t launch_conv_stats(const ConvArgs& a_in, int path, hipStream_t stream,
     hipLaunchKernelGGL(conv_direct_kernel, dim3((unsigned)((total + threads - 1) / threads)), dim3(threads), 0, stream,
                        a, total);
     return hipGetLastError();
-}
-
-// ---- GroupNorm fused into the conv (gn_fused.h).  The form is used exactly where the un-fused launch would have taken
-// conv_up_halo_kernel<5> / conv_igemm2_kernel<2> (same tile thresholds), when a sample's slots are few enough to sweep.
-static const int GN_FUSE_MAX_SLOTS = 64;  // gn_fuse_sweep<16>: 4 slot classes x 16
-
-int conv_gn_fused_max_slots(int h, int w) {
-    int best = 0;
-    const int s5 = conv_halo5_gn_slots(h, w);
-    if (s5 <= GN_FUSE_MAX_SLOTS) best = s5;
-    const int s16 = conv_gn16_slots(h, w);
-    if (s16 <= GN_FUSE_MAX_SLOTS) best = std::max(best, s16);
-    const int si = conv_igemm2_gn_slots(h, w);
-    if (si > 0 && si <= GN_FUSE_MAX_SLOTS) best = std::max(best, si);
-    const int s128 = conv_igemm2_gn_slots_bm128(h, w);
-    if (s128 > 0 && s128 <= GN_FUSE_MAX_SLOTS) best = std::max(best, s128);
-    return best;
-}
-
-hipError_t launch_conv_gn_fused(const ConvArgs& a_in, int path, hipStream_t stream, bool* fused) {
-    *fused = false;
-    ConvArgs a = a_in;  // (DYF_GN_FUSED=0 is read per engine, dyf_engine_create: the caller then never asks)
-    a.gn_part = nullptr;
-    a.gn_slots = 0;
-    const GnFuse& G = a.gnf;
-    if (path != 1 || G.gran == nullptr || G.epoch == nullptr || a.act != ACT_SILU || a.drop.mode == 2 || a.out_el16 == nullptr ||
-        a.out_f32 != nullptr || a.up2x || !conv_mfma_supported(a))
-        return hipSuccess;
-    const int cpg = G.groups > 0 ? a.cout / G.groups : 0;
-    if (cpg < 8 || cpg % 8 != 0 || 64 % cpg != 0 || cpg * G.groups != a.cout) return hipSuccess;  // a group lies inside one 64-channel block
-    const long long nsel = a.n_sel > 0 ? a.n_sel : a.n;
-    if (a.kh == 3 && a.kw == 3 && a.stride == 1 && a.pad == 1 && a.cout % 256 == 0) {
-        // 256-channel level on SMALL planes (15 x 15 at OISST: one 16 x 16 tile per sample): conv_gn16_kernel with four 64-channel column
-        // blocks per sample instead of conv_igemm2_kernel<2, true>'s 256-pixel x 128-channel tiles -- half the K chain per workgroup,
-        // more than twice the workgroups (400 against 176 at 100 rows).  DYF_GN16_C256=0: off
-        const bool on = dyf_form_int("DYF_GN16", 1) != 0 && dyf_form_int("DYF_GN16_C256", 1) != 0;
-        ConvArgs b = a;
-        b.wpk_up_frag = conv_lookup_frag64(b.wpk);
-        const int slots16 = conv_gn16_slots(a.h, a.w);
-        const long long tiles16 = nsel * slots16 * (a.cout / 64);
-        const bool covers16 = 10ll * a.h * a.w >= 6ll * slots16 * 256 || dyf_form_int("DYF_GN16_ANY_PLANE", 0) != 0;
-        const long long max_plane = dyf_form_int("DYF_GN16_C256_MAX_PLANE", 1024);
-        const long long c256_min = dyf_form_int("DYF_GN16_MIN_TILES", 64);
-        if (on && b.wpk_up_frag && covers16 && (long long)a.h * a.w <= max_plane && tiles16 >= c256_min && slots16 <= GN_FUSE_MAX_SLOTS &&
-            slots16 <= G.max_slots && conv_gn16_supported(b)) {
-            b.gnf.slots = slots16;
-            *fused = true;
-            return launch_conv_gn16(b, stream);
-        }
-    }
-    if (a.kh == 3 && a.kw == 3 && a.stride == 1 && a.pad == 1 && a.cout % 64 == 0 && a.cout % 256 != 0) {
-        const bool h5 = dyf_form_int("DYF_HALO5", 1) != 0;
-        const long long h5_min = dyf_form_int("DYF_HALO5_MIN_TILES", 64);
-        ConvArgs b = a;
-        b.wpk_up_frag = conv_lookup_halo3_frag(b.wpk);
-        {   // 16 x 16 tiles, three workgroups per CU (conv_gn16.hip; DYF_GN16=0: the 16 x 32 form below)
-            const bool g16 = dyf_form_int("DYF_GN16", 1) != 0;
-            const long long g16_min = dyf_form_int("DYF_GN16_MIN_TILES", 64);
-            const int slots16 = conv_gn16_slots(a.h, a.w);
-            const long long tiles16 = nsel * slots16 * (a.cout / 64);
-            // (planes that fill less than 60 % of their tiles are left to the other forms; DYF_GN16_ANY_PLANE=1: the tests' tiny planes)
-            const bool covers16 = 10ll * a.h * a.w >= 6ll * slots16 * 256 || dyf_form_int("DYF_GN16_ANY_PLANE", 0) != 0;
-            if (g16 && b.wpk_up_frag && covers16 && tiles16 >= g16_min && slots16 <= GN_FUSE_MAX_SLOTS && slots16 <= G.max_slots &&
-                conv_gn16_supported(b)) {
-                b.gnf.slots = slots16;
-                *fused = true;
-                return launch_conv_gn16(b, stream);
-            }
-        }
-        const long long ty = (a.h + 15) / 16, tx = (a.w + 31) / 32;
-        const long long tiles5 = nsel * ty * tx * (a.cout / 64);
-        const bool covers = 10ll * a.h * a.w >= 6ll * ty * 16 * tx * 32;
-        const int slots = conv_halo5_gn_slots(a.h, a.w);
-        if (h5 && b.wpk_up_frag && covers && tiles5 >= h5_min && slots <= GN_FUSE_MAX_SLOTS && slots <= G.max_slots && conv_halo5_supported(b)) {
-            b.gnf.slots = slots;
-            *fused = true;
-            return launch_conv_halo5(b, stream);
-        }
-    }
-    const bool use_igemm2 = dyf_form_int("DYF_IGEMM2", 1) != 0;
-    if (use_igemm2 && a.cout % 128 == 0) {
-        ConvArgs b = a;
-        if (!b.wpk_frag) b.wpk_frag = conv_lookup_frag(b.wpk);
-        const long long tiles2 = ((nsel * a.ho * a.wo + 255) / 256) * (a.cout / 128);
-        // un-fused, the 256 x 128 tiles pay off from 384 tiles on (below that conv_igemm_kernel<128, 128> is ahead); fused, the form
-        // also saves the three GroupNorm launches behind it (statistics, finalise, apply: 15 us of launches at small batches): taken
-        // from 32 tiles on.  Measured at the end of round 4, OISST shapes, fields/s with the threshold at 256 (the first choice) /
-        // 64 / 16: 300 rows 4 154 / 4 165 / 4 181, 150 rows 3 568 / 3 626 / 3 631, 75 rows 2 360 / 2 494 / 2 479, 38 rows 1 548 /
-        // 1 619 / 1 654, 16 rows 811 / 811 / 791 (32: 818) -- DYF_GN_FUSE_MIN_TILES overrides, DYF_IGEMM2_MIN_TILES (tests) wins
-        const long long min_tiles = dyf_form_int("DYF_IGEMM2_MIN_TILES", dyf_form_int("DYF_GN_FUSE_MIN_TILES", 32));
-        const int slots = conv_igemm2_gn_slots(a.ho, a.wo);
-        // flattened-M tiles cut a sample into 128-row slabs at (n * plane) % 128: unless plane % 128 == 0 (or the tiles are 2-D) the
-        // fp32 partial sums of a sample are grouped by its POSITION in the launch, and (mean, 1/std) differ in the last bits between
-        // batch offsets / ranks -- not acceptable to a batch_invariant engine, which then takes the three-kernel path
-        const bool position_free = conv_igemm2_tile2d(a.ho, a.wo) || (a.ho * a.wo) % 128 == 0;
-        if (G.invariant && !position_free) return hipSuccess;
-        // few tiles: the 128-pixel tile form (half the K chain per wave, twice the workgroups) while the 256-pixel tiles would leave
-        // CUs idle -- DYF_IGEMM2_BM128_BELOW tiles (0 = never); not for batch_invariant engines whose planes are not slab-aligned
-        // (the same position argument as above, with 64-row slabs)
-        const long long bm128_below = dyf_form_int("DYF_IGEMM2_BM128_BELOW", 224);  // read per launch (parity test)
-        const int slots128 = conv_igemm2_gn_slots_bm128(a.ho, a.wo);
-        const bool free128 = (a.wo % 16 == 0 && a.ho % 8 == 0) || (a.ho * a.wo) % 64 == 0;
-        if (tiles2 >= min_tiles && tiles2 < bm128_below && slots128 > 0 && slots128 <= GN_FUSE_MAX_SLOTS && slots128 <= G.max_slots &&
-            (!G.invariant || free128) && conv_igemm2_supported(b)) {
-            b.gnf.slots = slots128;
-            b.gnf.bm = 128;
-            *fused = true;
-            return launch_conv_igemm2(b, stream);
-        }
-        if (tiles2 >= min_tiles && slots > 0 && slots <= GN_FUSE_MAX_SLOTS && slots <= G.max_slots && conv_igemm2_supported(b)) {
-            b.gnf.slots = slots;
-            b.gnf.bm = 256;
-            *fused = true;
-            return launch_conv_igemm2(b, stream);
-        }
-    }
-    return hipSuccess;
 }
 
 // Host-side weight transform for the fused x2-upsample conv (see the kernel header): w [cout][cin][3][3] fp32 ->

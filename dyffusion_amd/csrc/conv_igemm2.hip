@@ -17,10 +17,9 @@
 #include "conv.h"
 #include "gn_fused.h"
 
+#include <algorithm>
 #include <cstdlib>
-#include <mutex>
 #include <type_traits>
-#include <unordered_map>
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
 
@@ -709,51 +708,4 @@ hipError_t launch_conv_igemm2(const ConvArgs& a, hipStream_t stream) {
             hipLaunchKernelGGL(conv_igemm2_kernel<1>, dim3(tiles_m * tiles_n), dim3(256), LDS_TOTAL, stream, a, (int)M, tiles_m, tiles_n);
     }
     return hipGetLastError();
-}
-
-namespace {
-std::mutex g_frag_mu;
-std::unordered_map<const void*, const el16_t*> g_frag;
-std::unordered_map<const void*, const el16_t*> g_frag3;  // halo-kernel fragments of plain 3x3 convs
-std::unordered_map<const void*, const el16_t*> g_frag64; // pack_halo3_frag64 fragments of 3x3 convs whose g_frag3 entry is the 256-channel-block order
-}  // namespace
-
-void conv_register_frag(const el16_t* wpk_dev, const el16_t* frag_dev) {
-    std::lock_guard<std::mutex> lk(g_frag_mu);
-    g_frag[(const void*)wpk_dev] = frag_dev;
-}
-
-void conv_unregister_frag(const void* wpk_dev) {
-    std::lock_guard<std::mutex> lk(g_frag_mu);
-    g_frag.erase(wpk_dev);
-    g_frag3.erase(wpk_dev);
-    g_frag64.erase(wpk_dev);
-}
-
-void conv_register_frag64(const el16_t* wpk_dev, const el16_t* frag_dev) {
-    std::lock_guard<std::mutex> lk(g_frag_mu);
-    g_frag64[(const void*)wpk_dev] = frag_dev;
-}
-
-const el16_t* conv_lookup_frag64(const el16_t* wpk_dev) {
-    std::lock_guard<std::mutex> lk(g_frag_mu);
-    auto it = g_frag64.find((const void*)wpk_dev);
-    return it == g_frag64.end() ? nullptr : it->second;
-}
-
-void conv_register_halo3_frag(const el16_t* wpk_dev, const el16_t* frag_dev) {
-    std::lock_guard<std::mutex> lk(g_frag_mu);
-    g_frag3[(const void*)wpk_dev] = frag_dev;
-}
-
-const el16_t* conv_lookup_halo3_frag(const el16_t* wpk_dev) {
-    std::lock_guard<std::mutex> lk(g_frag_mu);
-    auto it = g_frag3.find((const void*)wpk_dev);
-    return it == g_frag3.end() ? nullptr : it->second;
-}
-
-const el16_t* conv_lookup_frag(const el16_t* wpk_dev) {
-    std::lock_guard<std::mutex> lk(g_frag_mu);
-    auto it = g_frag.find((const void*)wpk_dev);
-    return it == g_frag.end() ? nullptr : it->second;
 }

@@ -5,11 +5,6 @@
 // :140-163 + :480-494 (q_sample / _interpolate), :205-239 (predict_x_last) and src/models/unet_simple.py:164-197.
 #include "engine_internal.h"
 
-void dyf_form_set(const char* key, const char* value);  // conv.hip: the kernel-form switch table (common.h dyf_form)
-std::string dyf_form_text();
-void dyf_prof_arm(const char* name);  // conv.hip: named-kernel timing (common.h KernelProf)
-void dyf_prof_collect(double* total_ms, double* total_bytes, int* launches);
-
 #include <dlfcn.h>
 #include <mutex>
 #include <rccl/rccl.h>  // types only: the functions are resolved with dlsym (rccl_api below)
@@ -134,8 +129,7 @@ DropSpec make_input_drop(const dyf_engine* e, const Net& n, const FwdOpts& o) {
 }
 
 dyf_status run_conv(dyf_engine* e, const ConvArgs& a, hipStream_t st) {
-    const int path = (e->cfg.enable_mfma && conv_mfma_supported(a)) ? 1 : 0;
-    HIP_TRY(e, launch_conv(a, path, st));
+    HIP_TRY(e, launch_conv(a, conv_path(e, a), st));
     return DYF_OK;
 }
 
@@ -163,7 +157,7 @@ ConvArgs block_conv_args(const dyf_engine* e, const Net& n, const UBlock& b, int
     a.act = b.act;
     a.zero_page = e->ws.zero_page;
     a.splitk_ws = e->ws.splitk; a.splitk_cap = DYF_SPLITK_FLOATS;
-    a.n_sel = e->cfg.batch_invariant ? 2 * e->cfg.max_batch : 0;
+    a.n_sel = e->cfg.batch_invariant ? 2 * e->cfg.max_batch : 0;  // (NOT conv_form_rows: this path has never scaled by form_rows_scale)
     return a;
 }
 

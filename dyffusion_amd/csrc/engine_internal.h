@@ -221,6 +221,16 @@ inline dyf_status fail(dyf_engine* e, dyf_status st, const std::string& msg) {
             return fail(e, DYF_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_err));              \
     } while (0)
 
+// ------------------------------------------------------------------------------------------------ inputs of conv_choose_form
+// `path` of launch_conv* for a conv of this engine: the MFMA forms where the engine allows them and the shape is served
+inline int conv_path(const dyf_engine* e, const ConvArgs& a) { return (e->cfg.enable_mfma && conv_mfma_supported(a)) ? 1 : 0; }
+// ConvArgs::n_sel of an n-row launch, the rows its kernel form is chosen for: a batch_invariant engine pins the forms to 2 max_batch
+// rows; a row group shares the chip with the launches of its sibling groups and chooses by the tile count of all of them; 0 = n
+inline int conv_form_rows(const dyf_engine* e, int n) {
+    if (e->cfg.batch_invariant) return 2 * e->cfg.max_batch;
+    return e->form_rows_scale > 1 ? n * e->form_rows_scale : 0;
+}
+
 template <typename T>
 dyf_status dev_alloc(dyf_engine* e, T** out, size_t count) {
     void* p = nullptr;
@@ -258,7 +268,7 @@ dyf_status dev_upload(dyf_engine* e, T** out, const std::vector<T>& host) {
 }
 
 // packed conv weights [cout][taps][cin] bf16 -> device; layers the second implicit-GEMM form can run also get their
-// fragment-ordered copy, registered under the primary pointer (launch_conv looks it up)
+// fragment-ordered copy, registered under the primary pointer (conv_choose_form looks it up)
 inline dyf_status upload_conv_weights(dyf_engine* e, el16_t** out, const std::vector<el16_t>& pk, int cout, int taps, int cin) {
     dyf_status st = dev_upload(e, out, pk);
     if (st != DYF_OK) return st;

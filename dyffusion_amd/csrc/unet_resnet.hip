@@ -112,10 +112,8 @@ dyf_status rconv(dyf_engine* e, const el16_t* s0, int c0, const el16_t* s1, int 
     a.coef_a = coef_a; a.coef_c = coef_c; a.coef_stride = coef_stride; a.act = act; a.drop = drop;
     a.residual = residual; a.out_el16 = out;
     a.splitk_ws = e->ws.splitk; a.splitk_cap = DYF_SPLITK_FLOATS;
-    a.n_sel = e->cfg.batch_invariant ? 2 * e->cfg.max_batch : 0;
-    // a row group shares the chip with the launches of its sibling groups: choose the kernel form by the tile count of all of them
-    if (e->form_rows_scale > 1 && !e->cfg.batch_invariant) a.n_sel = n * e->form_rows_scale;
-    const int path = (e->cfg.enable_mfma && conv_mfma_supported(a)) ? 1 : 0;
+    a.n_sel = conv_form_rows(e, n);
+    const int path = conv_path(e, a);
     ProfScope prof(e, e->prof_layer == DYF_PROF_RESNET_BASE + DYF_PROF_RN_CONV3_L0 && k == 3 && stride == 1 && h == e->cfg.height &&
                           w == e->cfg.width && c0 + c1 == cout && residual == nullptr, n, st);
     if (gn_part && gn_slots) {
@@ -135,8 +133,7 @@ bool rconv_nearest_fusable(dyf_engine* e, int c0, int n, int h, int w, int cout,
     a.src0 = (const el16_t*)wpk;  // (any non-null pointer: the predicates look at shapes)
     a.c0 = c0; a.n = n; a.h = h; a.w = w; a.ho = h; a.wo = w; a.kh = 3; a.kw = 3; a.stride = 1; a.pad = 1; a.cout = cout; a.wpk = wpk;
     a.out_el16 = (el16_t*)wpk;
-    a.n_sel = e->cfg.batch_invariant ? 2 * e->cfg.max_batch : 0;
-    if (e->form_rows_scale > 1 && !e->cfg.batch_invariant) a.n_sel = n * e->form_rows_scale;
+    a.n_sel = conv_form_rows(e, n);
     return conv_plain3x3_takes_halo5(a);
 }
 
@@ -532,18 +529,16 @@ dyf_status rn_forward(dyf_engine* e, int which, const Source* srcs, int nsrc, in
         a.kh = 3; a.kw = 3; a.stride = 1; a.pad = 1; a.cout = cout; a.wpk = wpk;
         a.coef_a = r->ones; a.coef_c = bias; a.coef_stride = 0; a.coef_div = o.coef_div;
         a.act = ACT_SILU; a.drop = drop; a.residual = residual; a.out_el16 = out;
-        a.n_sel = e->cfg.batch_invariant ? 2 * e->cfg.max_batch : 0;
-        if (e->form_rows_scale > 1 && !e->cfg.batch_invariant) a.n_sel = nb * e->form_rows_scale;
+        a.n_sel = conv_form_rows(e, nb);
         a.gnf.gran = r->gn_gran; a.gnf.epoch = r->gn_epoch; a.gnf.conv_tag = (uint32_t)(gn_conv_idx + 1);
         a.gnf.max_slots = r->gn_max_slots; a.gnf.groups = c.groups; a.gnf.bias = bias; a.gnf.gamma = gamma; a.gnf.beta = beta;
         if (with_film) { a.gnf.film_a = o.coef_a + film_off; a.gnf.film_c = o.coef_c + film_off; a.gnf.film_stride = o.coef_stride; }
         a.gnf.err = e->gn_err_dev;
         a.gnf.invariant = e->cfg.batch_invariant ? 1 : 0;
         a.gnf.timeout_ticks = e->gn_timeout_ticks; a.gnf.test_tag_xor = e->gn_test_tag_xor;
-        const int path = (e->cfg.enable_mfma && conv_mfma_supported(a)) ? 1 : 0;
         ProfScope prof(e, e->prof_layer == DYF_PROF_RESNET_BASE + DYF_PROF_RN_CONV3_L0 && hh == e->cfg.height && ww == e->cfg.width &&
                               c0 + c1 == cout, nb, st);
-        HIP_TRY(e, launch_conv_gn_fused(a, path, st, fused));
+        HIP_TRY(e, launch_conv_gn_fused(a, conv_path(e, a), st, fused));
         if (*fused) ++gn_conv_idx;
         return DYF_OK;
     };

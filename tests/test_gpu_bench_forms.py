@@ -1,6 +1,6 @@
 """-m gpu: the kernel FORMS bench.py runs, held to the oracle.
 
-Kernel forms are chosen per launch from tile counts (csrc/conv.hip launch_conv): a full-size parity test at NB = 1..3 runs
+Kernel forms are chosen per launch from tile counts (csrc/conv_dispatch.hip conv_choose_form): a full-size parity test at NB = 1..3 runs
 the implicit-GEMM / split-K forms for enc1-enc3 and dec2, while bench.py at NB = 80 (paired interpolator launches: 160 rows)
 runs conv_up_halo_kernel<3/4> (stride-2 halo), conv_halo_rows_kernel<0/1/2>, the persistent conv_enc0_stem_kernel and no
 split-K.  These tests run BASELINE configs[1] exactly as bench.py builds it -- NB = 80 rows, hipGraph, paired launches -- on 80
