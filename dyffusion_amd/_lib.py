@@ -55,6 +55,13 @@ class BcArgs(C.Structure):
                 ("in_velocity_dev", C.c_void_p), ("vertex_y_dev", C.c_void_p), ("boundary_dev", C.c_void_p)]
 
 
+class ConvEx(C.Structure):
+    """dyf_conv_ex (include/dyffusion_hip_testing.h): the optional arguments of dyf_op_conv2d_ex; zero / NULL = absent."""
+    _fields_ = [("x1_dev", C.c_void_p), ("residual_dev", C.c_void_p), ("y_f32_dev", C.c_void_p), ("mask_dev", C.c_void_p),
+                ("c1", C.c_int32), ("coef_div", C.c_int32), ("n_sel", C.c_int32), ("drop_mode", C.c_int32),
+                ("drop_p", C.c_float), ("drop_site", C.c_int32), ("drop_row_offset", C.c_uint32), ("drop_forward", C.c_uint32)]
+
+
 BC_NAVIER_STOKES, BC_SPRING_MESH = 0, 1
 COMM_ID_BYTES = 128  # DYF_COMM_ID_BYTES (ncclUniqueId)
 TRAIN_BATCH_STATS, TRAIN_DROPOUT = 1, 2
@@ -99,6 +106,7 @@ SYMBOLS = [
     ("dyf_time_kernel_in_rollout", C.c_int, [_P, C.c_int32, C.c_int32, _P, C.POINTER(C.c_double), C.POINTER(C.c_int32),
                                              C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     ("dyf_op_conv2d", C.c_int, [_P, _P, _P] + [C.c_int32] * 9 + [_P, _P, C.c_int32, C.c_int32, _P, _P]),
+    ("dyf_op_conv2d_ex", C.c_int, [_P, _P, _P] + [C.c_int32] * 9 + [_P, _P, C.c_int32, C.c_int32, _P, C.POINTER(ConvEx), _P]),
     ("dyf_op_upconv2d", C.c_int, [_P, _P, _P] + [C.c_int32] * 5 + [_P, _P, C.c_int32, _P, _P]),
     ("dyf_op_linear_attention", C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P]),
     ("dyf_op_linear_attention_fused", C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P]),

@@ -1891,9 +1891,36 @@ dyf_status dyf_op_conv2d(dyf_engine* e, const uint16_t* x_dev, const float* w_ho
                          int32_t cin, int32_t cout, int32_t kh, int32_t kw, int32_t stride, int32_t pad,
                          const float* scale_dev, const float* shift_dev, int32_t act, int32_t path, uint16_t* y_dev,
                          void* stream) {
-    if (!e || !x_dev || !w_host || !y_dev) return fail(e, DYF_ERR_INVALID_ARGUMENT, "null argument");
-    if (n < 1 || h < 1 || w < 1 || cin < 1 || cout < 1 || kh < 1 || kw < 1 || stride < 1 || pad < 0)
+    return dyf_op_conv2d_ex(e, x_dev, w_host, n, h, w, cin, cout, kh, kw, stride, pad, scale_dev, shift_dev, act, path, y_dev, nullptr,
+                            stream);
+}
+
+dyf_status dyf_op_conv2d_ex(dyf_engine* e, const uint16_t* x_dev, const float* w_host, int32_t n, int32_t h, int32_t w,
+                            int32_t c0, int32_t cout, int32_t kh, int32_t kw, int32_t stride, int32_t pad,
+                            const float* scale_dev, const float* shift_dev, int32_t act, int32_t path, uint16_t* y_dev,
+                            const dyf_conv_ex* ex, void* stream) {
+    const dyf_conv_ex none{};
+    const dyf_conv_ex& x = ex ? *ex : none;
+    if (!e || !x_dev || !w_host || (!y_dev && !x.y_f32_dev)) return fail(e, DYF_ERR_INVALID_ARGUMENT, "null argument");
+    if (n < 1 || h < 1 || w < 1 || c0 < 1 || cout < 1 || kh < 1 || kw < 1 || stride < 1 || pad < 0)
         return fail(e, DYF_ERR_INVALID_ARGUMENT, "bad conv geometry");
+    // what ConvArgs cannot express is refused, never truncated
+    if (act < ACT_NONE || act > ACT_GELU) return fail(e, DYF_ERR_INVALID_ARGUMENT, "act outside 0..4");
+    if (x.c1 < 0 || (x.c1 > 0) != (x.x1_dev != nullptr)) return fail(e, DYF_ERR_INVALID_ARGUMENT, "second source: x1_dev and c1 > 0 go together");
+    if (x.coef_div < 0 || x.n_sel < 0) return fail(e, DYF_ERR_INVALID_ARGUMENT, "coef_div / n_sel must not be negative");
+    if (x.coef_div > 1 && !(scale_dev && shift_dev)) return fail(e, DYF_ERR_INVALID_ARGUMENT, "coef_div needs scale and shift");
+    if ((scale_dev == nullptr) != (shift_dev == nullptr)) return fail(e, DYF_ERR_INVALID_ARGUMENT, "scale and shift go together");
+    if (x.drop_mode < 0 || x.drop_mode > 2 || !(x.drop_p >= 0.0f && x.drop_p < 1.0f))
+        return fail(e, DYF_ERR_INVALID_ARGUMENT, "dropout: mode 0..2, 0 <= p < 1");
+    if (x.drop_mode == 2 && !x.mask_dev) return fail(e, DYF_ERR_INVALID_ARGUMENT, "dropout mode 2 needs the keep mask");
+    if (x.drop_mode == 1 && (n > 2 * e->cfg.max_batch || x.drop_site < 0))
+        return fail(e, DYF_ERR_INVALID_ARGUMENT, "dropout mode 1: more rows than the engine's row-key table (2 max_batch), or a negative site");
+    const int cin = c0 + x.c1;
+    const long long ho = ((long long)h + 2 * pad - kh) / stride + 1, wo = ((long long)w + 2 * pad - kw) / stride + 1;
+    if (h + 2 * pad < kh || w + 2 * pad < kw) return fail(e, DYF_ERR_INVALID_ARGUMENT, "kernel larger than the padded input");
+    // element indices of the epilogues (dropout streams, residual, stores) are 32 bit in every form
+    if ((long long)n * ho * wo * cout >= 0xFFFFFFF0ll || (long long)n * h * w * std::max(c0, x.c1) >= 0x7F000000ll / 2)
+        return fail(e, DYF_ERR_UNSUPPORTED, "tensor too large for the kernels' 32-bit element indices");
     HIP_TRY(e, hipSetDevice(e->cfg.device));
     hipStream_t st = (hipStream_t)stream;
     const int taps = kh * kw;
@@ -1904,7 +1931,8 @@ dyf_status dyf_op_conv2d(dyf_engine* e, const uint16_t* x_dev, const float* w_ho
                 pk[((size_t)co * taps + t) * cin + ci] = f32_to_el16(w_host[((size_t)co * cin + ci) * taps + t]);
     el16_t* wdev = nullptr;
     float *ones = nullptr, *zeros = nullptr;
-    const bool frag = cout % 64 == 0 && cin % 64 == 0 && taps <= 32;
+    const bool chan64 = cout % 64 == 0 && c0 % 64 == 0 && x.c1 % 64 == 0;
+    const bool frag = chan64 && taps <= 32;
     HIP_TRY(e, hipMalloc((void**)&wdev, 2 * pk.size() * sizeof(el16_t)));
     HIP_TRY(e, hipMemcpy(wdev, pk.data(), pk.size() * sizeof(el16_t), hipMemcpyHostToDevice));
     if (frag) {
@@ -1913,12 +1941,12 @@ dyf_status dyf_op_conv2d(dyf_engine* e, const uint16_t* x_dev, const float* w_ho
         HIP_TRY(e, hipMemcpy(wdev + pk.size(), pf.data(), pf.size() * sizeof(el16_t), hipMemcpyHostToDevice));
     }
     ConvArgs a{};
-    a.src0 = x_dev; a.c0 = cin; a.n = n; a.h = h; a.w = w;
-    a.ho = (h + 2 * pad - kh) / stride + 1; a.wo = (w + 2 * pad - kw) / stride + 1;
+    a.src0 = x_dev; a.c0 = c0; a.src1 = x.x1_dev; a.c1 = x.c1; a.n = n; a.h = h; a.w = w;
+    a.ho = (int)ho; a.wo = (int)wo;
     a.kh = kh; a.kw = kw; a.stride = stride; a.pad = pad; a.cout = cout; a.wpk = wdev;
     a.wpk_frag = frag ? wdev + pk.size() : nullptr;
     el16_t* h3dev = nullptr;  // halo form of plain 3x3 convs (looked up through the registry like the engine's own weights)
-    if (((taps == 9 && cout % 64 == 0) || (kh == 4 && kw == 4 && cout % 128 == 0)) && cin % 64 == 0) {
+    if (((taps == 9 && cout % 64 == 0) || (kh == 4 && kw == 4 && cout % 128 == 0)) && chan64) {
         std::vector<el16_t> pf((size_t)cout * 16 * cin * (taps == 9 ? 1 : 4));
         if (taps == 9 && cout % 256 == 0) pack_halo3_frag(pk.data(), cout, cin, pf.data());
         else if (taps == 9) pack_halo3_frag64(pk.data(), cout, cin, pf.data());
@@ -1927,7 +1955,8 @@ dyf_status dyf_op_conv2d(dyf_engine* e, const uint16_t* x_dev, const float* w_ho
         HIP_TRY(e, hipMemcpy(h3dev, pf.data(), pf.size() * sizeof(el16_t), hipMemcpyHostToDevice));
         conv_register_halo3_frag(wdev, h3dev);
     }
-    a.act = act; a.out_el16 = y_dev; a.zero_page = e->ws.zero_page;
+    a.act = act; a.out_el16 = y_dev; a.out_f32 = x.y_f32_dev; a.residual = x.residual_dev; a.zero_page = e->ws.zero_page;
+    a.coef_div = x.coef_div; a.n_sel = x.n_sel;
     a.splitk_ws = e->ws.splitk; a.splitk_cap = e->ws.splitk ? DYF_SPLITK_FLOATS : 0;  // the split-K forms, as in the engine's own launches
     if (scale_dev && shift_dev) {
         a.coef_a = scale_dev; a.coef_c = shift_dev; a.coef_stride = cout;
@@ -1939,8 +1968,29 @@ dyf_status dyf_op_conv2d(dyf_engine* e, const uint16_t* x_dev, const float* w_ho
         HIP_TRY(e, hipMemcpy(zeros, z0.data(), cout * sizeof(float), hipMemcpyHostToDevice));
         a.coef_a = ones; a.coef_c = zeros; a.coef_stride = 0;
     }
+    if (x.drop_mode != 0) {
+        a.drop.mode = x.drop_mode;
+        a.drop.scale = 1.0f / (1.0f - x.drop_p);
+        a.drop.thresh16 = keep_threshold16(x.drop_p);
+        a.drop.mask = x.drop_mode == 2 ? x.mask_dev : nullptr;
+    }
+    if (x.drop_mode == 1) {
+        // masks of the engine's generator at forward `drop_forward`, global rows drop_row_offset .. + n - 1, site `drop_site`: the
+        // counters are set, then the launch is armed exactly as dyf_op_attention_dropout does (which also advances the forward counter)
+        const uint32_t words[2] = {x.drop_forward, x.drop_row_offset};
+        HIP_TRY(e, hipDeviceSynchronize());
+        HIP_TRY(e, hipMemcpy(e->rng_state + 2, words, sizeof(words), hipMemcpyHostToDevice));
+        e->row_offset = x.drop_row_offset;
+        e->row_offset_known = true;
+        HIP_TRY(e, launch_rng_begin_forward(e->rng_state, e->row_keys, n, n, st));
+        a.drop.salt = rng_layer_salt((uint32_t)x.drop_site);
+        a.drop.row_keys = e->row_keys;
+    }
     dyf_status rs = DYF_OK;
-    if (path == 1 && !conv_mfma_supported(a)) {
+    // (GELU has no MFMA epilogue: launch_conv sends it to the direct kernel, as it does for the engine's own GELU convs)
+    ConvArgs geom = a;
+    geom.act = ACT_NONE;
+    if (path == 1 && !conv_mfma_supported(geom)) {
         rs = fail(e, DYF_ERR_UNSUPPORTED, "MFMA path needs cin % 64 == 0 and cout % 64 == 0");
     } else {
         hipError_t le = launch_conv(a, path, st);

@@ -475,6 +475,52 @@ class HipEngine:
                                             self._stream()))
         return y
 
+    def op_conv2d_ex(self, x: torch.Tensor, weight: torch.Tensor, stride: int, pad: int, scale: Optional[torch.Tensor] = None,
+                     shift: Optional[torch.Tensor] = None, act: int = 0, path: int = 1, *, x1: Optional[torch.Tensor] = None,
+                     residual: Optional[torch.Tensor] = None, out16: bool = True, out_f32: bool = False, coef_div: int = 0,
+                     n_sel: int = 0, mask: Optional[torch.Tensor] = None, p: float = 0.0, rng_site: Optional[int] = None,
+                     rng_row_offset: int = 0, rng_forward: int = 0):
+        """Test seam (dyf_op_conv2d_ex): op_conv2d over the rest of the conv argument block.  x (N,H,W,c0) and x1 (N,H,W,c1) in the
+        engine's 16-bit dtype, weight (Cout, c0 + c1, kh, kw); residual 16-bit of the output's shape; scale / shift of
+        ceil(N / coef_div) rows; mask: uint8 NHWC keep mask (dropout mode 2); rng_site: dropout mode 1 from the engine's generator at
+        that site, forward index and global row offset; act 0..4.  Returns the 16-bit output, the fp32 output, or (16-bit, fp32)."""
+        dt = self.torch_dtype
+        assert x.dtype == dt and x.is_cuda and x.is_contiguous() and (out16 or out_f32)
+        n, h, w, c0 = x.shape
+        c1 = 0
+        if x1 is not None:
+            assert x1.dtype == dt and x1.is_cuda and x1.is_contiguous() and x1.shape[:3] == x.shape[:3]
+            c1 = x1.shape[3]
+        cout, cin, kh, kw = weight.shape
+        assert cin == c0 + c1 and not (mask is not None and rng_site is not None)
+        wh = np.ascontiguousarray(weight.detach().to("cpu", torch.float32).numpy())
+        ho, wo = (h + 2 * pad - kh) // stride + 1, (w + 2 * pad - kw) // stride + 1
+        y = torch.empty((n, ho, wo, cout), dtype=dt, device=x.device) if out16 else None
+        y32 = torch.empty((n, ho, wo, cout), dtype=torch.float32, device=x.device) if out_f32 else None
+        if scale is not None:
+            rows = -(-n // coef_div) if coef_div > 1 else n
+            scale, shift = _f32c(scale, "scale"), _f32c(shift, "shift")
+            assert tuple(scale.shape) == (rows, cout) and tuple(shift.shape) == (rows, cout)
+        ex = L.ConvEx()
+        if x1 is not None:
+            ex.x1_dev, ex.c1 = x1.data_ptr(), c1
+        if residual is not None:
+            assert residual.dtype == dt and residual.is_cuda and residual.is_contiguous() and tuple(residual.shape) == (n, ho, wo, cout)
+            ex.residual_dev = residual.data_ptr()
+        if y32 is not None:
+            ex.y_f32_dev = y32.data_ptr()
+        ex.coef_div, ex.n_sel, ex.drop_p = int(coef_div), int(n_sel), float(p)
+        if mask is not None:
+            assert mask.dtype == torch.uint8 and mask.is_cuda and mask.is_contiguous() and tuple(mask.shape) == (n, ho, wo, cout)
+            ex.drop_mode, ex.mask_dev = 2, mask.data_ptr()
+        elif rng_site is not None:
+            ex.drop_mode, ex.drop_site, ex.drop_row_offset, ex.drop_forward = 1, int(rng_site), int(rng_row_offset), int(rng_forward)
+        self._check(self._lib.dyf_op_conv2d_ex(self._h, x.data_ptr(), wh.ctypes.data, n, h, w, c0, cout, kh, kw, stride, pad,
+                                               None if scale is None else scale.data_ptr(),
+                                               None if shift is None else shift.data_ptr(), act, path,
+                                               None if y is None else y.data_ptr(), C.byref(ex), self._stream()))
+        return (y, y32) if out16 and out_f32 else y if out16 else y32
+
     def criterion(self, pred: torch.Tensor, target: torch.Tensor, kind: str = "l1") -> float:
         """Mean L1 / MSE / smooth-L1 between two fp32 device tensors (get_loss, src/utilities/utils.py:201-212)."""
         name = kind.lower().strip().replace("-", "_")

@@ -48,6 +48,38 @@ dyf_status dyf_op_conv2d(dyf_engine* engine, const uint16_t* x_dev, const float*
                          const float* scale_dev, const float* shift_dev, int32_t act, int32_t path, uint16_t* y_dev,
                          void* stream);
 
+/* The same seam over the rest of the conv argument block (csrc/conv.h ConvArgs); dyf_op_conv2d is this call with ex = NULL.  A zero /
+ * NULL field of `ex` means "absent" and gives dyf_op_conv2d's behaviour.  16-bit tensors are bf16 or fp16 as the engine's build.
+ *   x1_dev, c1     second NHWC source (N,H,W,c1), concatenated on channels behind x_dev's `cin`: w_host is (Cout, cin + c1, kh, kw)
+ *   residual_dev   16-bit (N,Ho,Wo,Cout), added after activation and dropout
+ *   y_f32_dev      fp32 (N,Ho,Wo,Cout) output, instead of y_dev (which may then be NULL) or as well
+ *   coef_div       samples per row of scale / shift, which then hold ceil(N / coef_div) rows (0 / 1: one row per sample)
+ *   n_sel          batch rows the kernel FORM is chosen for (0: this launch's N)
+ *   drop_mode      0 none; 2: mask_dev = uint8 NHWC keep mask of the whole launch; 1: the engine's generator (dyf_seed) at dropout
+ *                  site drop_site, forward index drop_forward, global batch rows drop_row_offset .. + N - 1 (N <= 2 max_batch) -- sets
+ *                  the engine's forward counter and row offset, and advances the counter by one like a network forward.  Survivors are
+ *                  scaled by 1 / (1 - drop_p).
+ * act: 0 none, 1 relu, 2 leaky(0.2), 3 SiLU, 4 GELU (erf).  What the argument block cannot express is refused
+ * (DYF_ERR_INVALID_ARGUMENT / DYF_ERR_UNSUPPORTED), never truncated. */
+typedef struct {
+    const uint16_t* x1_dev;
+    const uint16_t* residual_dev;
+    float* y_f32_dev;
+    const uint8_t* mask_dev;
+    int32_t c1;
+    int32_t coef_div;
+    int32_t n_sel;
+    int32_t drop_mode;
+    float drop_p;
+    int32_t drop_site;
+    uint32_t drop_row_offset;
+    uint32_t drop_forward;
+} dyf_conv_ex;
+dyf_status dyf_op_conv2d_ex(dyf_engine* engine, const uint16_t* x_dev, const float* w_host, int32_t n, int32_t h,
+                            int32_t w, int32_t cin, int32_t cout, int32_t kh, int32_t kw, int32_t stride, int32_t pad,
+                            const float* scale_dev, const float* shift_dev, int32_t act, int32_t path, uint16_t* y_dev,
+                            const dyf_conv_ex* ex, void* stream);
+
 /* Upsample(x2, bilinear, align_corners=False) + Conv2d(3x3, pad 1) + epilogue in one kernel (phase-decomposed MFMA
  * implicit GEMM; unet_simple.py:40-52).  x_dev (N,H,W,Cin) bf16 -> y_dev (N,2H,2W,Cout) bf16. */
 dyf_status dyf_op_upconv2d(dyf_engine* engine, const uint16_t* x_dev, const float* w_host, int32_t n, int32_t h,

@@ -21,13 +21,43 @@ CASES = [
     (5, 4, 4, 512, 512, 2, 2, 0),       # tiles span several samples
     (1, 64, 64, 256, 64, 3, 1, 1),      # 256x64 tile variant
     (2, 9, 7, 64, 64, 3, 1, 1),
-    # plain 3x3 convs with 64 / 128 output channels on the halo kernel's SP = 5 form (>= 256 tiles of 16 x 32 pixels): the
-    # ResNet-UNet levels at the OISST plane sizes (ragged: 60 = 3*16 + 12 = 32 + 28), a plane narrower than a tile, two chunks
+    # plain 3x3 convs with 64 / 128 output channels on the halo kernel's SP = 5 form (>= 64 tiles of 16 x 32 pixels that cover >= 60 %
+    # of their pixels): the ResNet-UNet levels at the OISST plane sizes (ragged: 60 = 3*16 + 12 = 32 + 28), two chunks
     (32, 60, 60, 64, 64, 3, 1, 1),
     (70, 30, 30, 128, 128, 3, 1, 1),
+    # planes that fill less than 60 % of their 16 x 32 tiles are not SP = 5's (halo5_admits): 20 x 37 at 140 rows is 405 tiles of the
+    # second implicit-GEMM form, 17 x 9 at 300 rows stays on the 256 x 64 tiles
     (140, 20, 37, 64, 128, 3, 1, 1),
     (300, 17, 9, 128, 64, 3, 1, 1),
+    (64, 16, 20, 128, 64, 3, 1, 1),     # SP = 5 on a plane narrower than a tile (62 % covered), two chunks
 ]
+
+# The kernel form every case takes at path 1 (csrc/conv_dispatch.hip choose_plain), asserted from the form log, and the switches that
+# force the form a case is here for.  Below 65 tiles of 128 x 128 a conv with cout % 128 == 0 and 4 .. 32 K steps is the skinny
+# kernel's; the two cases that are here for the 128-row tiles of conv_igemm_kernel<128,128> switch skinny and split-K off.
+_SKINNY, _IG128, _IG256 = "conv_skinny_kernel", "conv_igemm_kernel<128,128>", "conv_igemm_kernel<256,64>"
+_PLAIN128 = {"DYF_SKINNY": 0, "DYF_SPLITK": 0}
+PATH1_FORMS = {
+    CASES[0]: (_SKINNY, {}), CASES[1]: (_SKINNY, {}), CASES[2]: (_IG256, {}), CASES[3]: (_IG256, {}),
+    CASES[4]: (_IG128, _PLAIN128), CASES[5]: (_IG128, _PLAIN128), CASES[6]: (_IG256, {}), CASES[7]: (_IG256, {}),
+    CASES[8]: ("conv_up_halo_kernel<5>", {}), CASES[9]: ("conv_up_halo_kernel<5>", {}), CASES[10]: ("conv_igemm2_kernel<2>", {}),
+    CASES[11]: (_IG256, {}), CASES[12]: ("conv_up_halo_kernel<5>", {}),
+}
+# notes a launcher adds next to its form's name (the SH3 gather of igemm2 on raster tiles)
+_ALSO = {"conv_igemm2_kernel<1>": {"conv_igemm2_kernel+sh3"}, "conv_igemm2_kernel<2>": {"conv_igemm2_kernel+sh3"}}
+
+
+def _form_log(engine_obj, fn):
+    engine_obj.form_log(True)
+    out = fn()
+    forms = engine_obj.form_log_read()
+    engine_obj.form_log(False)
+    return out, forms
+
+
+def _only_form(forms, expect):
+    conv = {k for k in forms if k.startswith("conv_")}
+    assert expect in conv and conv <= {expect} | _ALSO.get(expect, set()), (expect, sorted(forms))
 
 
 @pytest.fixture(scope="module")
@@ -52,16 +82,20 @@ def reference(x_nhwc, w, stride, pad, scale=None, shift=None, act=0):
 
 @pytest.mark.parametrize("path", [0, 1], ids=["direct", "mfma"])
 @pytest.mark.parametrize("case", CASES, ids=lambda c: "x".join(map(str, c)))
-def test_conv_matches_torch(engine, case, path):
+def test_conv_matches_torch(engine, case, path, form_switch):
     n, h, w, cin, cout, k, stride, pad = case
+    expect, switches = PATH1_FORMS[case] if path == 1 else ("conv_direct_kernel", {})
+    for key, value in switches.items():
+        form_switch.setenv(key, value)
     g = torch.Generator().manual_seed(hash(case) % 1000)
     x = torch.randn(n, h, w, cin, generator=g).to(torch.bfloat16)
     wt = torch.randn(cout, cin, k, k, generator=g) / (cin * k * k) ** 0.5
     scale = 1.0 + 0.3 * torch.randn(n, cout, generator=g)
     shift = 0.2 * torch.randn(n, cout, generator=g)
     for act, use_coef in [(0, False), (2, True), (1, True)]:
-        y = engine.op_conv2d(x.cuda(), wt, stride, pad, scale.cuda() if use_coef else None,
-                             shift.cuda() if use_coef else None, act=act, path=path)
+        y, forms = _form_log(engine, lambda: engine.op_conv2d(x.cuda(), wt, stride, pad, scale.cuda() if use_coef else None,
+                                                              shift.cuda() if use_coef else None, act=act, path=path))
+        _only_form(forms, expect)
         want = reference(x, wt, stride, pad, scale if use_coef else None, shift if use_coef else None, act)
         got = y.float().cpu()
         tol = 1.5 * 2 ** -8 * float(want.abs().max()) + 1e-3
@@ -102,11 +136,13 @@ def test_second_igemm_form_matches_torch(engine, case, form_switch):
     scale = 1.0 + 0.3 * torch.randn(n, cout, generator=g)
     shift = 0.2 * torch.randn(n, cout, generator=g)
     form_switch.setenv("DYF_IGEMM2_MIN_TILES", "1000000000")
-    first = engine.op_conv2d(x.cuda(), wt, stride, pad, scale.cuda(), shift.cuda(), act=2, path=1).float().cpu()
+    first, forms0 = _form_log(engine, lambda: engine.op_conv2d(x.cuda(), wt, stride, pad, scale.cuda(), shift.cuda(), act=2, path=1).float().cpu())
+    assert forms0 and not any(k.startswith("conv_igemm2") for k in forms0), sorted(forms0)
     form_switch.setenv("DYF_IGEMM2_MIN_TILES", "1")
     for act, use_coef in [(0, False), (2, True), (1, True)]:
-        y = engine.op_conv2d(x.cuda(), wt, stride, pad, scale.cuda() if use_coef else None,
-                             shift.cuda() if use_coef else None, act=act, path=1)
+        y, forms = _form_log(engine, lambda: engine.op_conv2d(x.cuda(), wt, stride, pad, scale.cuda() if use_coef else None,
+                                                              shift.cuda() if use_coef else None, act=act, path=1))
+        _only_form(forms, "conv_igemm2_kernel<2>" if cout % 128 == 0 else "conv_igemm2_kernel<1>")
         want = reference(x, wt, stride, pad, scale if use_coef else None, shift if use_coef else None, act)
         got = y.float().cpu()
         tol = 1.5 * 2 ** -8 * float(want.abs().max()) + 1e-3
@@ -132,6 +168,12 @@ HALO3_CASES = [(2, 16, 16, 64, 256, 3, 1, 1), (1, 32, 48, 128, 256, 3, 1, 1), (3
                (2, 32, 32, 64, 128, 4, 2, 1), (1, 64, 96, 128, 384, 4, 2, 1), (3, 128, 128, 64, 128, 4, 2, 1)]
 
 
+# the form of each case, as the comments above state (DYF_HALO_ROWS=0: 64 x 32 also tiles by 4 x 32, and is here for the 8 x 16 tiles)
+HALO3_FORMS = dict(zip(HALO3_CASES, ["conv_up_halo_kernel<2>"] * 4 + ["conv_halo_rows_kernel<2>"] * 2 + ["conv_up_halo_kernel<3>"] * 3 +
+                       ["conv_up_halo_kernel<4>"] * 3))
+HALO3_SWITCHES = {(1, 64, 32, 64, 256, 3, 1, 1): {"DYF_HALO_ROWS": 0}}
+
+
 @pytest.mark.parametrize("case", HALO3_CASES, ids=lambda c: "x".join(map(str, c)))
 def test_plain_convs_on_the_halo_kernel_match_torch(engine, case, form_switch):
     """conv_up_halo_kernel<2> / <3>: plain 3x3 / s1 / p1 and 4x4 / s2 / p1 convs (cout % 256 == 0) with the window in LDS
@@ -147,7 +189,10 @@ def test_plain_convs_on_the_halo_kernel_match_torch(engine, case, form_switch):
     other = engine.op_conv2d(x.cuda(), wt, stride, pad, scale.cuda(), shift.cuda(), act=1, path=1).float().cpu()
     form_switch.setenv("DYF_HALO3", "1")
     form_switch.setenv("DYF_HALO3_MIN_TILES", "1")
-    y = engine.op_conv2d(x.cuda(), wt, stride, pad, scale.cuda(), shift.cuda(), act=1, path=1).float().cpu()
+    for key, value in HALO3_SWITCHES.get(case, {}).items():
+        form_switch.setenv(key, value)
+    y, forms = _form_log(engine, lambda: engine.op_conv2d(x.cuda(), wt, stride, pad, scale.cuda(), shift.cuda(), act=1, path=1).float().cpu())
+    _only_form(forms, HALO3_FORMS[case])
     want = reference(x, wt, stride, pad, scale, shift, 1)
     tol = 1.5 * 2 ** -8 * float(want.abs().max()) + 1e-3
     assert max_abs(y, want) <= tol
@@ -200,14 +245,6 @@ def test_fused_upsample_conv_matches_torch(engine, case):
     for sl in [(slice(None), 0), (slice(None), -1), (slice(None), slice(None), 0), (slice(None), slice(None), -1)]:
         assert rel_rms(y[sl], want[sl]) <= 8e-3, (sl, rel_rms(y[sl], want[sl]))
     assert max_abs(y, want) <= 3 * 2 ** -8 * float(want.abs().max()) + 2e-3
-
-
-def _form_log(engine_obj, fn):
-    engine_obj.form_log(True)
-    out = fn()
-    forms = engine_obj.form_log_read()
-    engine_obj.form_log(False)
-    return out, forms
 
 
 # (n, h, w, cin, cout) of fused x2-upsample convs at FEW ROWS: the decoder shapes of unet_simple at one / two rows (dec3: 32 x 32
