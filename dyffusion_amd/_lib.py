@@ -11,8 +11,26 @@ LIB_PATH = os.environ.get("DYF_LIB") or os.path.join(_HERE, "lib", "libdyffusion
 # the fp16 build of the same sources (-DDYF_F16=1): same ABI, fp16 storage + v_mfma_*_f16 (BASELINE configs[4])
 LIB_PATH_F16 = os.environ.get("DYF_LIB_F16") or os.path.join(_HERE, "lib", "libdyffusion_hip_f16.so")
 DTYPES = {"bf16": 0, "bfloat16": 0, "fp16": 1, "float16": 1, "half": 1}
+# fp32 sampling (dyf_set_sample_precision(32)) is a mode of an engine, not a build of the library: such engines load the bf16 build
+FP32_NAMES = ("fp32", "float32", "32")
 
-DYF_ABI_VERSION = 8
+
+def canonical_dtype(dtype) -> str:
+    """"bf16" | "fp16" | "fp32" for every accepted spelling; ValueError for anything else."""
+    key = str(dtype).lower()
+    if key in FP32_NAMES:
+        return "fp32"
+    if key not in DTYPES:
+        raise ValueError(f"dtype {dtype!r}: expected one of {sorted(DTYPES) + list(FP32_NAMES)}")
+    return "fp16" if DTYPES[key] else "bf16"
+
+
+def storage_dtype(dtype) -> str:
+    """The 16-bit build an engine of `dtype` is served by ("fp32" engines: the default bf16 build)."""
+    d = canonical_dtype(dtype)
+    return "bf16" if d == "fp32" else d
+
+DYF_ABI_VERSION = 9
 DYF_OK, DYF_ERR_INVALID_ARGUMENT, DYF_ERR_UNSUPPORTED, DYF_ERR_HIP, DYF_ERR_STATE = range(5)
 NET_FORECASTER, NET_INTERPOLATOR = 0, 1
 ARCH_UNET_SIMPLE, ARCH_UNET_RESNET = 0, 1
@@ -118,6 +136,8 @@ SYMBOLS = [
     ("dyf_train_zero_grads", C.c_int, [_P, C.c_int32]),
     ("dyf_train_set_precision", C.c_int, [_P, C.c_int32]),
     ("dyf_train_precision", C.c_int32, [_P]),
+    ("dyf_set_sample_precision", C.c_int, [_P, C.c_int32]),
+    ("dyf_sample_precision", C.c_int32, [_P]),
     ("dyf_train_export", C.c_int, [_P, C.c_int32, C.c_int32, C.POINTER(C.c_char_p), C.POINTER(_P)]),
     ("dyf_criterion_grad", C.c_int, [_P, _P, _P, C.c_int64, C.c_int32, C.c_float, _P, _P]),
     ("dyf_train_conv_check", C.c_int, [_P] + [C.c_int32] * 9 + [C.c_uint32, C.POINTER(C.c_float)]),
@@ -154,8 +174,8 @@ _LIBS = {}
 
 
 def lib(dtype: str = "bf16") -> C.CDLL:
-    """The C-ABI library for `dtype`: "bf16" -> libdyffusion_hip.so, "fp16" -> libdyffusion_hip_f16.so."""
-    code = DTYPES[dtype]
+    """The C-ABI library for `dtype`: "bf16" (and "fp32") -> libdyffusion_hip.so, "fp16" -> libdyffusion_hip_f16.so."""
+    code = DTYPES[storage_dtype(dtype)]
     if code not in _LIBS:
         l = load_library(LIB_PATH_F16 if code else LIB_PATH)
         if l.dyf_dtype() != code:

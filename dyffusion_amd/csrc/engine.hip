@@ -382,6 +382,7 @@ void dyf_engine_destroy(dyf_engine* e) {
     if (e->s_log) (void)hipFree(e->s_log);
     if (e->cap_stream) (void)hipStreamDestroy(e->cap_stream);
     if (e->gn_err_host) (void)hipHostFree(e->gn_err_host);
+    f32_destroy(e);
     train_destroy(e);
     release_allocs(e->allocs);
     release_allocs(e->net_allocs[0]);
@@ -1003,6 +1004,19 @@ dyf_status dyf_debug_gn_fuse(dyf_engine* e, uint32_t timeout_ticks, int32_t forc
     return DYF_OK;
 }
 
+dyf_status dyf_set_sample_precision(dyf_engine* e, int32_t bits) {
+    if (!e) return DYF_ERR_INVALID_ARGUMENT;
+    if (bits != 16 && bits != 32) return fail(e, DYF_ERR_INVALID_ARGUMENT, "dyf_set_sample_precision: bits must be 16 or 32");
+    if (bits == 32) {
+        HIP_TRY(e, hipSetDevice(e->cfg.device));
+        dyf_status s = f32_prepare(e);
+        if (s != DYF_OK) return s;
+    }
+    e->sample_precision = bits;
+    return DYF_OK;
+}
+int32_t dyf_sample_precision(const dyf_engine* e) { return e ? e->sample_precision : -1; }
+
 dyf_status dyf_net_forward(dyf_engine* e, int32_t which, const float* inputs_dev, const float* time_dev,
                            const float* condition_dev, float* out_dev, int32_t nb, int32_t dropout_mode,
                            const uint8_t* const* masks_dev, void* stream) {
@@ -1023,13 +1037,17 @@ dyf_status dyf_net_forward(dyf_engine* e, int32_t which, const float* inputs_dev
         if (gs != DYF_OK) return gs;
     }
     hipStream_t st = (hipStream_t)stream;
-    dyf_status s = compute_coefs(e, n, time_dev, nb, e->ws.coef_a, e->ws.coef_c, st);
-    if (s != DYF_OK) return s;
+    const bool f32 = e->sample_precision == 32;  // the fp32 forwards of the two U-Nets run the time MLP themselves: no folded coefficient rows
+    if (!f32 || n.sc) {  // (SimpleConvNet's fp32 forward takes its FiLM from the coefficient rows: they are fp32)
+        dyf_status s = compute_coefs(e, n, time_dev, nb, e->ws.coef_a, e->ws.coef_c, st);
+        if (s != DYF_OK) return s;
+    }
     // channel order of the stem: unet_simple cat[inputs, condition] (unet_simple.py:184), unet.Unet cat[condition, x] (unet.py:269)
     Source srcs[2] = {{inputs_dev, n.cfg.in_channels}, {condition_dev, n.cfg.cond_channels}};
     if (n.rn && condition_dev) std::swap(srcs[0], srcs[1]);
     FwdOpts o{e->ws.coef_a, e->ws.coef_c, n.total_c, dropout_mode, masks_dev};
-    return net_forward(e, which, srcs, condition_dev ? 2 : 1, nb, o, out_dev, st);
+    o.time_dev = time_dev;
+    return (f32 ? f32_net_forward : net_forward)(e, which, srcs, condition_dev ? 2 : 1, nb, o, out_dev, st);
 }
 
 // ------------------------------------------------------------------------------------------------ sampler
@@ -1217,6 +1235,10 @@ dyf_status run_plan(dyf_engine* e, int nb, const uint8_t* const* masks, const fl
     const bool inject = masks != nullptr;
     const int i_mode = ph.hdr.interpolator_dropout ? (inject ? 2 : 1) : 0;
     const int f_mode = ph.hdr.forecaster_dropout ? (inject ? 2 : 1) : 0;
+    // the forward seam: the 16-bit forward of this library, or the fp32 one (dyf_set_sample_precision).  Everything else in this walk --
+    // sampler state, cold-sampling update, noisy condition, forecast stack, log -- is fp32 either way.
+    const bool f32 = e->sample_precision == 32;
+    auto* const forward = f32 ? f32_net_forward : net_forward;
 
     auto interp = [&](float t, const float* x_last, float* out) -> dyf_status {
         const int ti = I.table_of_time.at(t);
@@ -1227,14 +1249,16 @@ dyf_status run_plan(dyf_engine* e, int nb, const uint8_t* const* masks, const fl
             srcs[0] = {e->s_static, e->Cs}; srcs[1] = {e->s_init, e->wC}; srcs[2] = {x_last, e->C};
         }
         FwdOpts o{A, A + I.total_c, 0, i_mode, cur.take(i_mode == 2 && I.n_drop_sites > 0, I.n_drop_sites)};
-        return net_forward(e, DYF_NET_INTERPOLATOR, srcs, ns, nb, o, out, st);
+        o.time_value = t;
+        return forward(e, DYF_NET_INTERPOLATOR, srcs, ns, nb, o, out, st);
     };
 
     // Two interpolator calls with the same inputs and different times as ONE forward over 2 nb rows (rows [0, nb): t_a,
     // rows [nb, 2 nb): t_b): same arithmetic per row, but the small layers and the tile counts of the mid layers see twice
     // the batch.  The FiLM coefficient rows of the two times are staged next to each other; out: [2][nb][C][H][W].
     // Not with injected masks (their layout is one tensor per forward and site) and only for arch unet_simple.
-    const bool can_pair = !inject && !I.rn && !I.sc && e->pair_interp;
+    // fp32: one forward per interpolator call, in the un-paired order (next-step, current-step, then the refinement pass one by one)
+    const bool can_pair = !f32 && !inject && !I.rn && !I.sc && e->pair_interp;
     auto interp2 = [&](int step, float ta, float tb, const float* x_last, float* out2) -> dyf_status {
         const size_t row = (size_t)2 * I.total_c;
         const float* pair = e->ws.coef_pair;
@@ -1287,7 +1311,8 @@ dyf_status run_plan(dyf_engine* e, int nb, const uint8_t* const* masks, const fl
             const int ti = F.table_of_time.at(s.forecaster_time);
             const float* A = F.tables + (size_t)ti * 2 * F.total_c;
             FwdOpts o{A, A + F.total_c, 0, f_mode, cur.take(f_mode == 2 && F.n_drop_sites > 0, F.n_drop_sites)};
-            dyf_status r = net_forward(e, DYF_NET_FORECASTER, fs, nf, nb, o, e->s_x0hat, st);
+            o.time_value = s.forecaster_time;
+            dyf_status r = forward(e, DYF_NET_FORECASTER, fs, nf, nb, o, e->s_x0hat, st);
             if (r != DYF_OK) return r;
             LOG_COPY(0, e->s_x0hat);
         }
@@ -1394,7 +1419,7 @@ static dyf_status sample_into_stack(dyf_engine* e, const float* initial_dev, con
     const int H = e->cfg.height, W = e->cfg.width;
     e->last_groups = 0;
     const int G = (int)e->groups.size();
-    if (G > 1 && !e->log_on && masks_dev == nullptr && noise_dev == nullptr && nb >= 2 * e->group_min_rows) {
+    if (G > 1 && e->sample_precision != 32 && !e->log_on && masks_dev == nullptr && noise_dev == nullptr && nb >= 2 * e->group_min_rows) {
         // rows split over the groups: per = ceil(nb / g) rows each (the last one takes the remainder), every share on its own stream
         // Three concurrent groups + the caller's stream use all four hardware queues a HIP process gets: ONE more stream with work
         // (or a live graph) makes two groups share a queue and the 300-row OISST rollout drops from ~3 850 to ~3 100 fields/s, below
@@ -1453,7 +1478,8 @@ static dyf_status sample_into_stack(dyf_engine* e, const float* initial_dev, con
         dyf_status r = run_plan(e, nb, masks_dev, noise_dev, st);
         if (r != DYF_OK) return r;
     } else {
-        GraphEntry& g = e->graphs[nb];
+        const int gkey = graph_key(e, nb);  // a graph captured under the other precision is never replayed
+        GraphEntry& g = e->graphs[gkey];
         if (!g.exec) {
             HIP_TRY(e, hipStreamBeginCapture(e->cap_stream, hipStreamCaptureModeThreadLocal));
             dyf_status r = run_plan(e, nb, nullptr, nullptr, e->cap_stream);
@@ -1461,11 +1487,11 @@ static dyf_status sample_into_stack(dyf_engine* e, const float* initial_dev, con
             hipError_t ce = hipStreamEndCapture(e->cap_stream, &graph);
             if (r != DYF_OK) {
                 if (graph) (void)hipGraphDestroy(graph);
-                e->graphs.erase(nb);
+                e->graphs.erase(gkey);
                 return r;
             }
             if (ce != hipSuccess) {
-                e->graphs.erase(nb);
+                e->graphs.erase(gkey);
                 return fail(e, DYF_ERR_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(ce));
             }
             g.graph = graph;

@@ -128,7 +128,13 @@ struct dyf_engine {
     bool row_offset_known = false;
     uint32_t* row_keys = nullptr;   // device [2 max_batch][2]: per-row stream keys of the forward being launched (common.h)
     int stack_slots = 0;
-    std::map<int, dyf::GraphEntry> graphs;  // by batch size
+    std::map<int, dyf::GraphEntry> graphs;  // by (batch size, sampling precision): graph_key
+    // fp32 sampling (dyf_set_sample_precision): 16 = the library's 16-bit path, 32 = the fp32 forward of train.hip on a bump arena that
+    // the first switch to 32 allocates (max_batch rows of the larger network) and dyf_engine_destroy frees; rewound per forward
+    int sample_precision = 16;
+    void* f32_arena = nullptr;
+    size_t f32_bytes = 0, f32_used = 0;
+    bool f32_forward = false;  // an fp32 sampling forward is being launched (its convs take their split-K workspace from the arena)
     int fuse_min_plane = 32;           // smallest low-res plane side for which the fused form is used
     bool fuse_stem = true;             // DYF_FUSE_STEM=0: separate 1x1 stem kernel + plain enc0
     bool fuse_up2x = true;             // DYF_FUSE_UP2X=0 falls back to the materialised upsample (A/B testing)
@@ -331,13 +337,16 @@ struct Source {
 };
 
 struct FwdOpts {
-    const float* coef_a;      // [rows][total_c]
+    const float* coef_a;      // [rows][total_c] (16-bit forward: FiLM folded with the normalisation; the fp32 forward runs the time MLP)
     const float* coef_c;
     int coef_stride;          // 0: one row for the whole batch
     int dropout_mode;         // 0 off, 1 engine RNG, 2 injected
     const uint8_t* const* masks;  // [12] when dropout_mode == 2
     int src_rows = 0;         // rows of the source tensors (0: = nb); row r of the batch reads source row r % src_rows
     int coef_div = 0;         // batch rows per coefficient row (0/1: coef_stride semantics unchanged)
+    // fp32 forward (f32_net_forward): the time the coefficient rows stand for -- per row on the device, or one value for the batch
+    const float* time_dev = nullptr;
+    float time_value = 0.0f;
 };
 
 
@@ -348,6 +357,22 @@ namespace dyf {
 dyf_status train_store_weights(dyf_engine* e, int which, std::map<std::string, TensorView>& sd);
 dyf_status rn_train_store_weights(dyf_engine* e, int which, std::map<std::string, TensorView>& sd);  // arch unet.Unet
 void train_destroy(dyf_engine* e);
+// fp32 sampling forward (train.hip): net_forward's signature; the layer walk and the kernels of the recorded training forward on the
+// engine's bump arena -- no allocation, no synchronisation, bitwise repeatable, capturable
+dyf_status f32_net_forward(dyf_engine* e, int which, const Source* srcs, int nsrc, int nb, const FwdOpts& o, float* out_dev,
+                           hipStream_t st);
+dyf_status f32_prepare(dyf_engine* e);  // first switch to 32 bits: arena + split-K workspace
+void f32_destroy(dyf_engine* e);
+inline size_t f32_arena_block(size_t bytes) { return (std::max<size_t>(bytes, 256) + 255) / 256 * 256; }
+// bump allocation out of the arena (null: exhausted); f32_net_forward rewinds it at the start of every forward
+inline void* f32_arena_take(dyf_engine* e, size_t bytes) {
+    const size_t b = f32_arena_block(bytes);
+    if (!e->f32_arena || e->f32_used + b > e->f32_bytes) return nullptr;
+    void* p = (char*)e->f32_arena + e->f32_used;
+    e->f32_used += b;
+    return p;
+}
+inline int graph_key(const dyf_engine* e, int nb) { return e->sample_precision == 32 ? nb | (1 << 30) : nb; }
 }  // namespace dyf
 
 // ---- SimpleConvNet backbone (src/models/simple_conv_net.py), implemented in simple_conv_net.hip
@@ -358,6 +383,9 @@ dyf_status sc_load_weights(dyf_engine* e, Net& n, std::map<std::string, TensorVi
 dyf_status sc_forward(dyf_engine* e, int which, const Source* srcs, int nsrc, int nb, const FwdOpts& o, float* out_dev,
                       hipStream_t st);
 void sc_destroy(Net& n);
+dyf_status sc_f32_forward(dyf_engine* e, int which, const Source* srcs, int nsrc, int nb, const FwdOpts& o, float* out_dev,
+                          hipStream_t st);  // fp32 sampling (dyf_set_sample_precision(32))
+size_t sc_f32_arena_bytes(const dyf_engine* e, const Net& n, size_t nb);
 }  // namespace dyf
 
 // ---- ResNet-UNet backbone (src/models/unet.py), implemented in unet_resnet.hip

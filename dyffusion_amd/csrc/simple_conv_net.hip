@@ -17,6 +17,7 @@ struct SNet {
     int nk = 0;
     int ks[6] = {};
     el16_t* w[6] = {};          // [dim][k*k][cin] bf16
+    float* wf[6] = {};          // the same in fp32: the parameter copy of the fp32 sampling forward (sc_f32_forward)
     float *head_w = nullptr, *head_b = nullptr;
     el16_t* packed = nullptr;   // [max_batch][H][W][cin_total]
     el16_t* buf[2] = {};        // ping-pong activations [max_batch][H][W][dim]
@@ -39,6 +40,63 @@ __global__ void pack_inputs_kernel(const float* s0, const float* s1, const float
     else if (c < c0 + c1 + c2) v = s2[((size_t)b * c2 + (c - c0 - c1)) * hw + p];
     else v = s3[((size_t)b * c3 + (c - c0 - c1 - c2)) * hw + p];
     out[idx] = f32_to_el16(v);
+}
+
+// ---- fp32 twin of the forward (dyf_set_sample_precision(32)): the same layers on fp32 NHWC activations and fp32 weights
+__global__ void sc_f32_pack_kernel(const float* s0, const float* s1, const float* s2, const float* s3, int c0, int c1, int c2, int c3,
+                                   int n, int hw, float* out) {
+    const int ctot = c0 + c1 + c2 + c3;
+    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (long long)n * hw * ctot) return;
+    const int c = (int)(idx % ctot);
+    const long long pix = idx / ctot;
+    const int p = (int)(pix % hw), b = (int)(pix / hw);
+    float v;
+    if (c < c0) v = s0[((size_t)b * c0 + c) * hw + p];
+    else if (c < c0 + c1) v = s1[((size_t)b * c1 + (c - c0)) * hw + p];
+    else if (c < c0 + c1 + c2) v = s2[((size_t)b * c2 + (c - c0 - c1)) * hw + p];
+    else v = s3[((size_t)b * c3 + (c - c0 - c1 - c2)) * hw + p];
+    out[idx] = v;
+}
+
+// One block of SimpleConvNet: k x k 'same' conv -> (conv bias, eval BatchNorm, FiLM) as the affine (A, C) of the plan's coefficient
+// tables -> GELU -> Dropout -> + residual.  One thread per output element; the grids are 10 x 10.
+__global__ void sc_f32_block_kernel(const float* x, const float* w, const float* coef_a, const float* coef_c, int coef_stride, int n, int H,
+                                    int W, int k, int cin, int cout, int residual, DropSpec drop, float* y) {
+    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long long per = (long long)H * W * cout;
+    if (idx >= per * n) return;
+    const int co = (int)(idx % cout);
+    const long long pix = idx / cout;
+    const int px = (int)(pix % W), py = (int)((pix / W) % H), b = (int)(pix / ((long long)W * H));
+    const int pad = (k - 1) / 2;
+    float acc = 0.0f;
+    for (int ky = 0; ky < k; ++ky) {
+        const int iy = py + ky - pad;
+        if (iy < 0 || iy >= H) continue;
+        for (int kx = 0; kx < k; ++kx) {
+            const int ix = px + kx - pad;
+            if (ix < 0 || ix >= W) continue;
+            const float* xp = x + (((size_t)b * H + iy) * W + ix) * cin;
+            const float* wp = w + ((size_t)co * k * k + ky * k + kx) * cin;
+            for (int ci = 0; ci < cin; ++ci) acc = fmaf(xp[ci], wp[ci], acc);
+        }
+    }
+    float v = fmaf(acc, coef_a[(size_t)b * coef_stride + co], coef_c[(size_t)b * coef_stride + co]);
+    v = 0.5f * v * (1.0f + erff(v * 0.70710678118654752f));
+    v = drop_apply(v, (uint32_t)idx, (uint32_t)(b * per), drop, drop_row_key(drop, b));
+    if (residual) v += x[(size_t)pix * cin + co];
+    y[idx] = v;
+}
+
+__global__ void sc_f32_head_kernel(const float* x, const float* wgt, const float* bias, int n, int hw, int c, int cout, float* out) {
+    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (long long)n * hw * cout) return;
+    const int p = (int)(idx % hw), co = (int)((idx / hw) % cout), b = (int)(idx / ((long long)hw * cout));
+    const float* xp = x + ((size_t)b * hw + p) * c;
+    float acc = bias[co];
+    for (int ci = 0; ci < c; ++ci) acc = fmaf(xp[ci], wgt[(size_t)co * c + ci], acc);
+    out[idx] = acc;
 }
 
 }  // namespace
@@ -139,6 +197,11 @@ dyf_status sc_load_weights(dyf_engine* e, Net& n, std::map<std::string, TensorVi
                 for (int t = 0; t < taps; ++t)
                     pk[((size_t)co * taps + t) * cin + ci] = f32_to_el16(cw->data[((size_t)co * cin + ci) * taps + t]);
         UP(s->w[i], pk);
+        std::vector<float> pkf(pk.size());
+        for (int co = 0; co < d; ++co)
+            for (int ci = 0; ci < cin; ++ci)
+                for (int t = 0; t < taps; ++t) pkf[((size_t)co * taps + t) * cin + ci] = cw->data[((size_t)co * cin + ci) * taps + t];
+        UP(s->wf[i], pkf);
         const int off = i * (int)d;
         for (int ch = 0; ch < d; ++ch) {  // eval-mode BatchNorm2d folded with the conv bias: y = conv*a + c
             const double a = (double)nw->data[ch] / std::sqrt((double)rv->data[ch] + 1e-5);
@@ -221,6 +284,64 @@ dyf_status sc_forward(dyf_engine* e, int which, const Source* srcs, int nsrc, in
     HeadArgs h{};
     h.x = x; h.n = nb; h.hw = hw; h.c = n.dim; h.cout = n.cfg.out_channels; h.wgt = s->head_w; h.bias = s->head_b; h.out = out_dev;
     HIP_TRY(e, launch_head(h, st));
+    return DYF_OK;
+}
+
+// bytes one fp32 forward of `nb` rows takes from the sampling arena: the packed input and two ping-pong activations
+size_t sc_f32_arena_bytes(const dyf_engine* e, const Net& n, size_t nb) {
+    const size_t px = (size_t)e->cfg.height * e->cfg.width;
+    return f32_arena_block(nb * px * n.cin_total * sizeof(float)) + 2 * f32_arena_block(nb * px * n.dim * sizeof(float));
+}
+
+// sc_forward in fp32 (dyf_set_sample_precision(32)): layer for layer the walk above -- same coefficient tables (they are fp32), same
+// dropout sites, salts, thresholds and row keys, same mask layout -- on tensors out of the engine's fp32 arena
+dyf_status sc_f32_forward(dyf_engine* e, int which, const Source* srcs, int nsrc, int nb, const FwdOpts& o, float* out_dev,
+                          hipStream_t st) {
+    Net& n = e->net[which];
+    SNet* s = n.sc;
+    const int H = e->cfg.height, W = e->cfg.width, hw = H * W;
+    int ctot = 0;
+    const float* sp[4] = {nullptr, nullptr, nullptr, nullptr};
+    int sc[4] = {0, 0, 0, 0};
+    if (nsrc > 4) return fail(e, DYF_ERR_INVALID_ARGUMENT, "too many input tensors");
+    for (int i = 0; i < nsrc; ++i) {
+        sp[i] = srcs[i].p;
+        sc[i] = srcs[i].p ? srcs[i].ch : 0;
+        ctot += sc[i];
+    }
+    if (ctot != n.cin_total)
+        return fail(e, DYF_ERR_INVALID_ARGUMENT, "channel count of the network inputs does not match its configuration");
+    float* packed = (float*)f32_arena_take(e, (size_t)nb * hw * ctot * sizeof(float));
+    float* buf[2] = {(float*)f32_arena_take(e, (size_t)nb * hw * n.dim * sizeof(float)),
+                     (float*)f32_arena_take(e, (size_t)nb * hw * n.dim * sizeof(float))};
+    if (!packed || !buf[0] || !buf[1]) return fail(e, DYF_ERR_STATE, "fp32 sampling arena exhausted");
+    if (o.dropout_mode == 1 && n.cfg.dropout > 0.0f)
+        HIP_TRY(e, launch_rng_begin_forward(e->rng_state, e->row_keys, nb, nb, st));
+    const long long tot = (long long)nb * hw * ctot;
+    hipLaunchKernelGGL(sc_f32_pack_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, sp[0], sp[1], sp[2], sp[3], sc[0], sc[1],
+                       sc[2], sc[3], nb, hw, packed);
+    const float* x = packed;
+    int cin = ctot;
+    for (int i = 0; i < s->nk; ++i) {
+        DropSpec d{};
+        const float p = n.cfg.dropout;
+        d.mode = p > 0.0f ? o.dropout_mode : 0;
+        d.scale = 1.0f / (1.0f - p);
+        d.thresh16 = keep_threshold16(p);
+        d.salt = rng_layer_salt((uint32_t)i);
+        d.row_keys = e->row_keys;
+        d.mask = (d.mode == 2 && o.masks) ? o.masks[i] : nullptr;
+        if (d.mode == 2 && d.mask == nullptr) d.mode = 0;
+        const long long el = (long long)nb * hw * n.dim;
+        hipLaunchKernelGGL(sc_f32_block_kernel, dim3((unsigned)((el + 255) / 256)), dim3(256), 0, st, x, s->wf[i], o.coef_a + i * n.dim,
+                           o.coef_c + i * n.dim, o.coef_stride, nb, H, W, s->ks[i], cin, n.dim, cin == n.dim ? 1 : 0, d, buf[i & 1]);
+        x = buf[i & 1];
+        cin = n.dim;
+    }
+    const long long oel = (long long)nb * hw * n.cfg.out_channels;
+    hipLaunchKernelGGL(sc_f32_head_kernel, dim3((unsigned)((oel + 255) / 256)), dim3(256), 0, st, x, s->head_w, s->head_b, nb, hw, n.dim,
+                       n.cfg.out_channels, out_dev);
+    HIP_TRY(e, hipGetLastError());
     return DYF_OK;
 }
 

@@ -763,6 +763,7 @@ struct TNorm {
     uint32_t thresh16;
     RngKey salt;
     const uint32_t* row_keys;
+    const uint8_t* mask;                // injected keep mask of the whole NHWC output (sampling, dropout mode 2; drop = 0) or null
 };
 
 __device__ __forceinline__ float t_act(float u, int act) {
@@ -791,6 +792,18 @@ __global__ void t_dropout_map(const float* x, float* y, int n, long long per, fl
     const int b = (int)(i / per);
     const RngKey rk = rng_stream_key(RngKey{row_keys[2 * b], row_keys[2 * b + 1]}, salt);
     y[i] = rng_keep((uint32_t)(i - (long long)b * per), rk, thresh16) ? x[i] * scale : 0.0f;
+}
+
+// The same map with an injected uint8 keep mask of the tensor's layout (sampling, dropout mode 2)
+__global__ void t_mask_map(const float* x, float* y, long long total, float scale, const uint8_t* mask) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < total) y[i] = mask[i] ? x[i] * scale : 0.0f;
+}
+
+// one time value for every row of a sampling forward (it travels as a kernel argument, so a captured rollout keeps it)
+__global__ void t_fill(float v, int n, float* dst) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) dst[i] = v;
 }
 
 // Element-wise passes over an NHWC tape: four channels per lane when the channel count and the pointers allow (grid.y = sample, so no
@@ -850,7 +863,8 @@ __global__ void t_norm_fwd(TNorm a, const float* z, float* y) {
     const int idx = a.gn ? b * a.groups + c / (a.C / a.groups) : c;
     float v = (z[i] - a.mean[idx]) * a.rstd[idx] * a.gamma[c] + a.beta[c];
     if (a.ss) v = v * (1.0f + a.ss[(size_t)b * 2 * a.C + c]) + a.ss[(size_t)b * 2 * a.C + a.C + c];
-    y[i] = t_act(v, a.act) * t_keep(a, b, (uint32_t)(i - (long long)b * per));
+    const float keep = a.mask ? (a.mask[i] ? a.drop_scale : 0.0f) : t_keep(a, b, (uint32_t)(i - (long long)b * per));
+    y[i] = t_act(v, a.act) * keep;
 }
 __global__ __launch_bounds__(256) void t_norm_fwd4(TNorm a, const float* z, float* y) {
     const uint32_t per = (uint32_t)a.hw * (uint32_t)a.C;
@@ -867,7 +881,8 @@ __global__ __launch_bounds__(256) void t_norm_fwd4(TNorm a, const float* z, floa
     for (int k = 0; k < 4; ++k) {
         float v = (zv[k] - q.mu[k]) * q.rs[k] * q.ga[k] + q.be[k];
         if (a.ss) v = v * (1.0f + q.sc[k]) + q.sh[k];
-        r[k] = t_act(v, a.act) * t_keep_rk(a, rk, e + k);
+        const float keep = a.mask ? (a.mask[i + k] ? a.drop_scale : 0.0f) : t_keep_rk(a, rk, e + k);
+        r[k] = t_act(v, a.act) * keep;
     }
     *(float4*)(y + i) = make_float4(r[0], r[1], r[2], r[3]);
 }
@@ -1255,6 +1270,7 @@ void launch_bias_grad(const float* d, long long pixels, int C, float* db, hipStr
 
 constexpr size_t TRAIN_SPLITK_FLOATS = (size_t)16 << 20;  // 64 MB: 512 tiles x 128 x 64 partial sums and change
 float* splitk_ws(dyf_engine* e) {
+    if (e->f32_forward) return (float*)e->f32_arena;  // a sampling forward: the head of its arena (nothing is allocated inside a forward)
     TrainState* ts = e->train;
     if (ts && !ts->splitk_ws && talloc(e, ts->ws_owned, &ts->splitk_ws, TRAIN_SPLITK_FLOATS, false) != DYF_OK) ts->splitk_ws = nullptr;
     return ts ? ts->splitk_ws : nullptr;
@@ -1379,6 +1395,28 @@ TConv block_geom(const UBlock& b, int nb) {
     return TConv{nb, b.in_h, b.in_w, b.cin, b.out_h, b.out_w, b.cout, b.k, b.stride, b.pad};
 }
 
+// Where the tensors of one fp32 forward come from -- the ONLY thing the recorded (training) forward and the sampling forward differ in:
+//   recording  blocks of the caching allocator, owned by the tape until its backward has run;
+//   sampling   bump allocation out of the engine's fp32 arena (sized once by dyf_set_sample_precision(32) for max_batch rows of either
+//              network, f32_arena_bytes_needed), rewound at the start of every forward: no hipMalloc / hipFree / synchronisation
+//              inside a forward, so a whole rollout can be captured.  One stream orders the reuse.
+struct FwdMem {
+    dyf_engine* e;
+    std::vector<void*>* owner;  // the tape's block list, null = the arena
+    hipStream_t st;
+    bool recording() const { return owner != nullptr; }
+    template <typename T>
+    dyf_status get(T** out, size_t count, bool zero = false) {
+        if (owner) return talloc(e, *owner, out, count, zero);
+        const size_t bytes = f32_arena_block(count * sizeof(T));
+        if (!e->f32_arena || e->f32_used + bytes > e->f32_bytes) return fail(e, DYF_ERR_STATE, "fp32 sampling arena exhausted (dyf_set_sample_precision sizes it for max_batch rows)");
+        *out = (T*)((char*)e->f32_arena + e->f32_used);
+        e->f32_used += bytes;
+        if (zero) TK(hipMemsetAsync(*out, 0, bytes, st));
+        return DYF_OK;
+    }
+};
+
 }  // namespace
 
 #include "train_resnet.inc"  // recorded forward / backward of the ResNet-UNet (arch unet.Unet)
@@ -1493,46 +1531,64 @@ dyf_status dyf_train_set_precision(dyf_engine* e, int32_t bits) {
 }
 int32_t dyf_train_precision(const dyf_engine* e) { return e ? e->train_precision : -1; }
 
-dyf_status dyf_train_forward(dyf_engine* e, int32_t which, int32_t slot, const float* inputs_dev, const float* time_dev,
-                             const float* cond_dev, float* out_dev, int32_t nb, int32_t flags, void* stream) {
-    if (!e || which < 0 || which > 1 || slot < 0 || slot > 3 || !inputs_dev || !out_dev || nb < 1)
-        return fail(e, DYF_ERR_INVALID_ARGUMENT, "dyf_train_forward: bad arguments");
-    const TrainPrecisionScope precision(e->train_precision);
-    if (e->net[which].rn) {
-        TK(hipSetDevice(e->cfg.device));
-        if (e->train) {  // the slot now belongs to this forward: drop a unet_simple tape that may sit in it
-            tfree(e, e->train->tape[slot].owned);
-            e->train->tape[slot] = TTape{};
-        }
-        return rn_train_forward(e, which, slot, inputs_dev, time_dev, cond_dev, out_dev, nb, flags, (hipStream_t)stream);
-    }
-    if (e->net[which].sc) return fail(e, DYF_ERR_UNSUPPORTED, "training step: arch unet_simple and unet (SimpleConvNet is the CPU plumbing config)");
-    if (!e->train || !e->train->net[which].ready) return fail(e, DYF_ERR_STATE, "training needs arch unet_simple with loaded weights");
+}  // extern "C"
+
+namespace {
+
+struct UsForward {              // one fp32 forward of arch unet_simple
+    const Source* srcs;         // fp32 NCHW tensors, concatenated on the channel axis in this order
+    int nsrc;
+    const float* time_dev;      // [nb], or null: time_value for every row
+    float time_value;
+    int nb;
+    bool bn_batch;              // BatchNorm on batch statistics (module.train()); false: running statistics
+    int dropout_mode;           // 0 off, 1 engine generator, 2 injected keep masks
+    const uint8_t* const* masks;
+};
+
+// The layer walk of unet_simple.py:164-197 on the fp32 kernels; `t` receives what a backward needs (the sampling forward passes a
+// scratch tape and drops it).
+dyf_status us_forward(dyf_engine* e, int which, FwdMem& mem, TTape& t, const UsForward& f, float* out_dev, hipStream_t st) {
     Net& n = e->net[which];
     TNet& w = e->train->net[which];
-    if ((n.cfg.cond_channels > 0) != (cond_dev != nullptr)) return fail(e, DYF_ERR_INVALID_ARGUMENT, "condition must be given iff num_conditional_channels > 0");
-    if (n.cfg.with_time_emb && !time_dev) return fail(e, DYF_ERR_INVALID_ARGUMENT, "time must be given when with_time_emb");
-    TK(hipSetDevice(e->cfg.device));
-    hipStream_t st = (hipStream_t)stream;
-    e->train->stream = st;
-    TTape& t = e->train->tape[slot];
-    TK(hipStreamSynchronize(st));
-    tfree(e, t.owned);
-    t = TTape{};
-    t.net = which; t.nb = nb; t.flags = flags;
-    const bool bn_batch = flags & DYF_TRAIN_BATCH_STATS, drop_on = (flags & DYF_TRAIN_DROPOUT) && n.cfg.dropout > 0.0f;
-    const bool in_drop_on = (flags & DYF_TRAIN_DROPOUT) && n.cfg.input_dropout > 0.0f;
+    const int nb = f.nb;
+    const bool bn_batch = f.bn_batch;
+    // dropout: 1 = the engine's generator (per-row streams), 2 = injected keep masks in execution order -- dropout_input (when its
+    // p > 0) first, then the 12 blocks, as the 16-bit forward takes them (engine.hip make_drop); a site with p = 0 is no site
+    const int in_site = n.cfg.input_dropout > 0.0f ? 1 : 0;
+    const bool drop_on = f.dropout_mode == 1 && n.cfg.dropout > 0.0f, in_drop_on = f.dropout_mode == 1 && n.cfg.input_dropout > 0.0f;
+    const bool mask_on = f.dropout_mode == 2 && f.masks && n.cfg.dropout > 0.0f;
+    const uint8_t* in_mask = (f.dropout_mode == 2 && f.masks && in_site) ? f.masks[0] : nullptr;
     const int H = e->cfg.height, W = e->cfg.width, hw = H * W, cin = n.cin_total, C = n.cfg.out_channels;
+    Source src[3] = {{nullptr, 0}, {nullptr, 0}, {nullptr, 0}};  // NCHW sources in channel order
+    int ctot = 0;
+    for (int i = 0; i < f.nsrc && i < 3; ++i) {
+        src[i] = f.srcs[i];
+        if (!src[i].p) src[i].ch = 0;
+        ctot += src[i].ch;
+    }
+    if (ctot != cin) return fail(e, DYF_ERR_INVALID_ARGUMENT, "channel count of the network inputs does not match its configuration");
 #define TS(expr) do { dyf_status _s = (expr); if (_s != DYF_OK) return _s; } while (0)
-#define TA(ptr, count) TS(talloc(e, t.owned, &(ptr), (size_t)(count), false))
+#define TA(ptr, count) TS(mem.get(&(ptr), (size_t)(count)))
     if (drop_on || in_drop_on) {  // this forward's dropout streams (engine generator, keyed per global row); kept for the backward
         if (nb > 2 * e->cfg.max_batch) return fail(e, DYF_ERR_INVALID_ARGUMENT, "batch larger than the engine's row-key table");
         TK(launch_rng_begin_forward(e->rng_state, e->row_keys, nb, nb, st));
-        TS(talloc(e, t.owned, &t.row_keys, (size_t)2 * nb, false));
-        TK(hipMemcpyAsync(t.row_keys, e->row_keys, (size_t)2 * nb * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+        if (mem.recording()) {
+            TA(t.row_keys, (size_t)2 * nb);
+            TK(hipMemcpyAsync(t.row_keys, e->row_keys, (size_t)2 * nb * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+        } else {
+            t.row_keys = e->row_keys;  // nothing comes back for them: the engine's table of the forward being launched
+        }
     }
     // ---- time embedding chain: sinusoid -> Linear -> GELU -> Linear ; every block: SiLU -> Linear -> (scale | shift)
     if (n.cfg.with_time_emb) {
+        const float* time_dev = f.time_dev;
+        if (!time_dev) {  // one time for the whole batch (a sampling plan's step)
+            float* tv = nullptr;
+            TA(tv, nb);
+            hipLaunchKernelGGL(t_fill, dim3(nblk(nb)), dim3(256), 0, st, f.time_value, nb, tv);
+            time_dev = tv;
+        }
         TA(t.e0, nb * n.dim); TA(t.l1, nb * n.tdim); TA(t.gl, nb * n.tdim); TA(t.temb, nb * n.tdim);
         hipLaunchKernelGGL(t_sinusoid, dim3(nblk(nb * n.dim)), dim3(256), 0, st, time_dev, nb, n.dim, t.e0);
         hipLaunchKernelGGL(t_linear_fwd, dim3((unsigned)((n.tdim + 3) / 4), (unsigned)((nb + 15) / 16)), dim3(256), 0, st, t.e0, w.t_w1, w.t_b1, nb, n.dim, n.tdim, 0, t.l1);
@@ -1541,8 +1597,8 @@ dyf_status dyf_train_forward(dyf_engine* e, int32_t which, int32_t slot, const f
     }
     // ---- stem: cat -> outer resample -> 1x1 conv
     TA(t.x_in, (size_t)nb * hw * cin);
-    hipLaunchKernelGGL(t_nchw_cat_to_nhwc, dim3(nblk((long long)nb * hw * cin)), dim3(256), 0, st, inputs_dev, n.cfg.in_channels, cond_dev,
-                       n.cfg.cond_channels, (const float*)nullptr, 0, nb, hw, t.x_in);
+    hipLaunchKernelGGL(t_nchw_cat_to_nhwc, dim3(nblk((long long)nb * hw * cin)), dim3(256), 0, st, src[0].p, src[0].ch, src[1].p, src[1].ch, src[2].p,
+                       src[2].ch, nb, hw, t.x_in);
     if (n.uh != H || n.uw != W) {
         TA(t.x_up, (size_t)nb * n.uh * n.uw * cin);
         hipLaunchKernelGGL(t_resize_fwd, dim3(nblk((long long)nb * n.uh * n.uw * cin)), dim3(256), 0, st, t.x_in, nb, H, W, cin, n.uh, n.uw, n.cfg.outer_nearest, t.x_up);
@@ -1555,9 +1611,12 @@ dyf_status dyf_train_forward(dyf_engine* e, int32_t which, int32_t slot, const f
         const long long per = (long long)n.uh * n.uw * n.dim;
         hipLaunchKernelGGL(t_dropout_map, dim3(nblk(per * nb)), dim3(256), 0, st, t.s0, t.s0, nb, per, 1.0f / (1.0f - n.cfg.input_dropout),
                            keep_threshold16(n.cfg.input_dropout), rng_layer_salt(DYF_INPUT_DROP_SITE), t.row_keys);
+    } else if (in_mask) {
+        const long long total = (long long)nb * n.uh * n.uw * n.dim;
+        hipLaunchKernelGGL(t_mask_map, dim3(nblk(total)), dim3(256), 0, st, t.s0, t.s0, total, 1.0f / (1.0f - n.cfg.input_dropout), in_mask);
     }
     double *S = nullptr, *Q = nullptr;
-    TS(talloc(e, t.owned, &S, (size_t)nb * 1024 * 2));
+    TS(mem.get(&S, (size_t)nb * 1024 * 2, true));
     Q = S + (size_t)nb * 1024;
     // ---- the 12 blocks
     const float* x = t.s0;
@@ -1596,7 +1655,8 @@ dyf_status dyf_train_forward(dyf_engine* e, int32_t which, int32_t slot, const f
         const int kind = b.gn ? 2 : (bn_batch ? 0 : 1);
         if (kind != 1) {
             TK(hipMemsetAsync(S, 0, (size_t)nb * 1024 * 2 * sizeof(double), st));
-            const int ppb = std::max(16, (ohw + 255) / 256);
+            // (sampling: ONE workgroup per sample, so every sum meets its zero-filled slot once -- no order of atomics to depend on)
+            const int ppb = mem.recording() ? std::max(16, (ohw + 255) / 256) : ohw;
             hipLaunchKernelGGL(t_nc_sums, dim3((ohw + ppb - 1) / ppb, nb), dim3(256), 0, st, t.z[i], ohw, b.cout, ppb, S, Q);
         }
         hipLaunchKernelGGL(t_stats_finalize, dim3(nblk(std::max(nidx, b.cout))), dim3(256), 0, st, kind, S, Q, nb, ohw, b.cout, 8, w.blk[i].rmean,
@@ -1606,7 +1666,8 @@ dyf_status dyf_train_forward(dyf_engine* e, int32_t which, int32_t slot, const f
             hipLaunchKernelGGL(t_linear_fwd, dim3((unsigned)((2 * b.cout + 3) / 4), (unsigned)((nb + 15) / 16)), dim3(256), 0, st, t.temb, w.blk[i].fw, w.blk[i].fb, nb, n.tdim, 2 * b.cout, 1, t.ss[i]);
         }
         TNorm a{nb, ohw, b.cout, 8, b.gn ? 1 : 0, b.act, t.mean[i], t.rstd[i], w.blk[i].gamma, w.blk[i].beta, t.ss[i], drop_on ? 1 : 0,
-                1.0f / (1.0f - n.cfg.dropout), keep_threshold16(n.cfg.dropout), rng_layer_salt((uint32_t)i), t.row_keys};
+                1.0f / (1.0f - n.cfg.dropout), keep_threshold16(n.cfg.dropout), rng_layer_salt((uint32_t)i), t.row_keys,
+                mask_on ? f.masks[i + in_site] : nullptr};
         launch_t_norm_fwd(a, t.z[i], t.y[i], st);
         TK(hipGetLastError());
         x = t.y[i];
@@ -1629,6 +1690,130 @@ dyf_status dyf_train_forward(dyf_engine* e, int32_t which, int32_t slot, const f
 #undef TA
 #undef TS
     return DYF_OK;
+}
+
+}  // namespace
+
+namespace dyf {
+
+// Bytes one unet_simple forward of `nb` rows takes from the arena: the allocations of us_forward, block by block (the concatenation
+// a decoder block may have to materialise is always counted).
+static size_t us_arena_bytes(const dyf_engine* e, const Net& n, size_t nb) {
+    const size_t H = e->cfg.height, W = e->cfg.width, F = sizeof(float);
+    size_t b = 0;
+    auto add = [&](size_t bytes) { b += f32_arena_block(bytes); };
+    if (n.cfg.with_time_emb) { add(nb * F); add(nb * n.dim * F); for (int k = 0; k < 3; ++k) add(nb * n.tdim * F); }
+    add(nb * H * W * n.cin_total * F);
+    add(nb * n.uh * n.uw * n.cin_total * F);
+    add(nb * n.uh * n.uw * n.dim * F);
+    add(nb * 1024 * 2 * sizeof(double));
+    for (int i = 0; i < 12; ++i) {
+        const UBlock& k = n.blk[i];
+        if (k.transposed) {
+            add(nb * (k.in_h / 2 + 1) * (k.in_w / 2 + 1) * k.cin * F);  // cat[x, skip] at the low resolution
+            add(nb * k.in_h * k.in_w * k.cin * F);
+        }
+        add(nb * k.out_h * k.out_w * k.cout * F);
+        add(nb * k.out_h * k.out_w * k.cout * F);
+        add(std::max<size_t>(nb * 8, k.cout) * F);
+        add(std::max<size_t>(nb * 8, k.cout) * F);
+        add(nb * 2 * k.cout * F);
+    }
+    add(nb * 4 * n.blk[11].out_h * n.blk[11].out_w * n.cfg.out_channels * F);
+    add(nb * H * W * n.cfg.out_channels * F);
+    return b;
+}
+
+dyf_status f32_prepare(dyf_engine* e) {
+    size_t fwd = 0;
+    for (int w = 0; w < 2; ++w) {
+        const Net& n = e->net[w];
+        if (n.rn && !rn_f32_supported(e, n))
+            return fail(e, DYF_ERR_UNSUPPORTED, "fp32 sampling: the bottleneck Attention keeps its (tokens x tokens) probabilities -- at most 4096 tokens");
+        fwd = std::max(fwd, n.rn ? rn_arena_bytes(e, n, e->cfg.max_batch)
+                                 : n.sc ? sc_f32_arena_bytes(e, n, e->cfg.max_batch) : us_arena_bytes(e, n, e->cfg.max_batch));
+    }
+    if (e->f32_arena) return DYF_OK;
+    // [split-K partial sums of the matrix-core convs | the tensors of one forward]
+    const size_t bytes = TRAIN_SPLITK_FLOATS * sizeof(float) + fwd;
+    TK(hipMalloc(&e->f32_arena, bytes));
+    e->f32_bytes = bytes;
+    e->f32_used = 0;
+    return DYF_OK;
+}
+
+void f32_destroy(dyf_engine* e) {
+    if (e->f32_arena) (void)hipFree(e->f32_arena);
+    e->f32_arena = nullptr;
+    e->f32_bytes = e->f32_used = 0;
+}
+
+dyf_status f32_net_forward(dyf_engine* e, int which, const Source* srcs, int nsrc, int nb, const FwdOpts& o, float* out_dev,
+                           hipStream_t st) {
+    const Net& n = e->net[which];
+    if (!e->f32_arena || !n.loaded || (!n.sc && (!e->train || (!n.rn && !e->train->net[which].ready))))
+        return fail(e, DYF_ERR_STATE, "fp32 sampling needs loaded weights and dyf_set_sample_precision(32)");
+    if (nb < 1 || nb > e->cfg.max_batch || (o.src_rows > 0 && o.src_rows != nb))
+        return fail(e, DYF_ERR_INVALID_ARGUMENT, "fp32 sampling: one forward of at most max_batch rows, one source row per batch row");
+    if (n.sc) {  // SimpleConvNet: its own fp32 forward (simple_conv_net.hip), FiLM from the coefficient rows of `o`
+        e->f32_used = 0;
+        return sc_f32_forward(e, which, srcs, nsrc, nb, o, out_dev, st);
+    }
+    const TrainPrecisionScope precision(32);  // fp32 operands whatever dyf_train_set_precision says
+    struct Active {  // splitk_ws() hands out the arena's head while this forward is being launched
+        dyf_engine* e;
+        explicit Active(dyf_engine* x) : e(x) { e->f32_forward = true; }
+        ~Active() { e->f32_forward = false; }
+    } active(e);
+    e->train->stream = st;
+    e->f32_used = TRAIN_SPLITK_FLOATS * sizeof(float);
+    if (n.rn) return rn_f32_forward(e, which, srcs, nsrc, nb, o, out_dev, st);
+    TTape scratch{};
+    UsForward f{};
+    f.srcs = srcs; f.nsrc = nsrc; f.time_dev = o.time_dev; f.time_value = o.time_value; f.nb = nb;
+    f.bn_batch = false;
+    f.dropout_mode = o.dropout_mode; f.masks = o.masks;
+    FwdMem mem{e, nullptr, st};
+    return us_forward(e, which, mem, scratch, f, out_dev, st);
+}
+
+}  // namespace dyf
+
+extern "C" {
+
+dyf_status dyf_train_forward(dyf_engine* e, int32_t which, int32_t slot, const float* inputs_dev, const float* time_dev,
+                             const float* cond_dev, float* out_dev, int32_t nb, int32_t flags, void* stream) {
+    if (!e || which < 0 || which > 1 || slot < 0 || slot > 3 || !inputs_dev || !out_dev || nb < 1)
+        return fail(e, DYF_ERR_INVALID_ARGUMENT, "dyf_train_forward: bad arguments");
+    const TrainPrecisionScope precision(e->train_precision);
+    if (e->net[which].rn) {
+        TK(hipSetDevice(e->cfg.device));
+        if (e->train) {  // the slot now belongs to this forward: drop a unet_simple tape that may sit in it
+            tfree(e, e->train->tape[slot].owned);
+            e->train->tape[slot] = TTape{};
+        }
+        return rn_train_forward(e, which, slot, inputs_dev, time_dev, cond_dev, out_dev, nb, flags, (hipStream_t)stream);
+    }
+    if (e->net[which].sc) return fail(e, DYF_ERR_UNSUPPORTED, "training step: arch unet_simple and unet (SimpleConvNet is the CPU plumbing config)");
+    if (!e->train || !e->train->net[which].ready) return fail(e, DYF_ERR_STATE, "training needs arch unet_simple with loaded weights");
+    Net& n = e->net[which];
+    if ((n.cfg.cond_channels > 0) != (cond_dev != nullptr)) return fail(e, DYF_ERR_INVALID_ARGUMENT, "condition must be given iff num_conditional_channels > 0");
+    if (n.cfg.with_time_emb && !time_dev) return fail(e, DYF_ERR_INVALID_ARGUMENT, "time must be given when with_time_emb");
+    TK(hipSetDevice(e->cfg.device));
+    hipStream_t st = (hipStream_t)stream;
+    e->train->stream = st;
+    TTape& t = e->train->tape[slot];
+    TK(hipStreamSynchronize(st));
+    tfree(e, t.owned);
+    t = TTape{};
+    t.net = which; t.nb = nb; t.flags = flags;
+    Source srcs[2] = {{inputs_dev, n.cfg.in_channels}, {cond_dev, n.cfg.cond_channels}};
+    UsForward f{};
+    f.srcs = srcs; f.nsrc = cond_dev ? 2 : 1; f.time_dev = time_dev; f.nb = nb;
+    f.bn_batch = (flags & DYF_TRAIN_BATCH_STATS) != 0;
+    f.dropout_mode = (flags & DYF_TRAIN_DROPOUT) ? 1 : 0;
+    FwdMem mem{e, &t.owned, st};
+    return us_forward(e, which, mem, t, f, out_dev, st);
 }
 
 dyf_status dyf_train_backward(dyf_engine* e, int32_t slot, const float* dout_dev, float* dinputs_dev, int32_t param_grads, void* stream) {

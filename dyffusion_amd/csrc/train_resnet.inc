@@ -140,8 +140,11 @@ struct RDrop {               // dropout of one site: engine generator, stream ke
     uint32_t thresh16;
     RngKey salt;
     const uint32_t* row_keys;
+    const uint8_t* mask;     // sampling, dropout mode 2: the caller's keep mask of the site ([rows][per], the tensor's own layout)
+    uint32_t per;            // elements of one batch row at this site
 };
 __device__ __forceinline__ float r_keep(const RDrop& d, int b, uint32_t e_in_row) {
+    if (d.mask) return d.mask[(size_t)b * d.per + e_in_row] ? d.scale : 0.0f;
     if (!d.on) return 1.0f;
     const RngKey rk = rng_stream_key(RngKey{d.row_keys[2 * b], d.row_keys[2 * b + 1]}, d.salt);
     return rng_keep(e_in_row, rk, d.thresh16) ? d.scale : 0.0f;
@@ -616,6 +619,11 @@ struct RCtx {
     int site = 0;
     std::vector<void*>* tmp = nullptr;   // backward temporaries (gradients of activations), freed when the backward is done
     dyf_status err = DYF_OK;
+    FwdMem mem{};                        // where the forward's tensors come from: the tape's blocks, or the sampling arena
+    const uint8_t* const* masks = nullptr;  // sampling, dropout mode 2: one keep mask per site with p > 0, in execution order
+    // an op's adjoint: kept only by a recorded forward
+    template <typename F>
+    void back(F&& f) { if (mem.recording()) T.back.push_back(std::forward<F>(f)); }
 
     // DYF_TRAIN_DEBUG=1: synchronise after every recorded op and report the first failing one (debugging aid)
     dyf::RT* dbg(dyf::RT* y, const char* what) {
@@ -630,12 +638,12 @@ struct RCtx {
         T.ts.emplace_back();
         dyf::RT* t = &T.ts.back();
         t->n = n;
-        if (talloc(e, T.owned, &t->p, n, false) != DYF_OK) err = DYF_ERR_HIP;
+        if (mem.get(&t->p, n) != DYF_OK) err = DYF_ERR_HIP;
         return t;
     }
     float* fbuf(size_t n, bool zero = false) {  // forward-lifetime scratch kept for the backward
         float* p = nullptr;
-        if (talloc(e, T.owned, &p, n, zero) != DYF_OK) err = DYF_ERR_HIP;
+        if (mem.get(&p, n, zero) != DYF_OK) err = DYF_ERR_HIP;
         return p;
     }
     float* grad(dyf::RT* t) {  // gradient buffer of an activation (zero on first use)
@@ -654,10 +662,16 @@ struct RCtx {
         return p;
     }
     dyf::RParam& P(const std::string& k) { return W.P.at(k); }
-    RDrop drop(float p) {
+    RDrop drop(float p, size_t per) {
         RDrop d{};
         if (p <= 0.0f) return d;            // p = 0 layers draw nothing and consume no site (as the sampling path's DropCtx)
         const int s = site++;
+        if (masks) {                        // injected: the caller's mask of this site
+            d.scale = 1.0f / (1.0f - p);
+            d.mask = masks[s];
+            d.per = (uint32_t)per;
+            return d;
+        }
         if (!drop_on) return d;
         d.on = 1;
         d.scale = 1.0f / (1.0f - p);
@@ -683,7 +697,7 @@ struct RCtx {
         }
         dyf::RT* y = make((size_t)nb * ho * wo * cout);
         if (conv_fwd(e, g, x->p, wht, pb ? pb->w : nullptr, y->p, st) != DYF_OK) err = DYF_ERR_HIP;
-        T.back.push_back([=, this]() -> dyf_status {
+        back([=, this]() -> dyf_status {
             if (!y->g) return DYF_OK;  // nothing downstream needed this output
             dyf::RParam& qw = P(name + ".weight");
             if (param_grads) {
@@ -714,20 +728,21 @@ struct RCtx {
         const int G = c.groups, nidx = nb * G;
         float *mean = fbuf(nidx), *rstd = fbuf(nidx);
         double* S = nullptr;
-        if (talloc(e, T.owned, &S, (size_t)nb * C * 2, true) != DYF_OK) err = DYF_ERR_HIP;
+        if (mem.get(&S, (size_t)nb * C * 2, true) != DYF_OK) err = DYF_ERR_HIP;
         double* Q = S + (size_t)nb * C;
         // pixels per workgroup: about 2 048 workgroups per launch on these planes (16 pixels each left 14 400 workgroups of 60 x 60 x 64 rows
         // with four fp64 atomics per thread: 104 us per backward-sums launch, 10x its traffic time)
-        const int ppb = std::max(std::max(16, (hw + 255) / 256), (int)std::min<long long>(128, ((long long)hw * nb + 2047) / 2048));
+        // (sampling: ONE workgroup per sample -- every sum meets its zero-filled slot once, no order of atomics to depend on)
+        const int ppb = !mem.recording() ? hw : std::max(std::max(16, (hw + 255) / 256), (int)std::min<long long>(128, ((long long)hw * nb + 2047) / 2048));
         hipLaunchKernelGGL(t_nc_sums, dim3((hw + ppb - 1) / ppb, nb), dim3(256), 0, st, z->p, hw, C, ppb, S, Q);
         hipLaunchKernelGGL(t_stats_finalize, dim3(nblk(std::max(nidx, C))), dim3(256), 0, st, 2, S, Q, nb, hw, C, G, (float*)nullptr, (float*)nullptr,
                            mean, rstd);
-        const RDrop d = drop(p_drop);
+        const RDrop d = drop(p_drop, (size_t)hw * C);
         const TNorm a{nb, hw, C, G, 1, ACT_SILU, mean, rstd, P(name + ".weight").w, P(name + ".bias").w, ss ? ss->p : nullptr, d.on, d.scale,
-                      d.thresh16, d.salt, d.row_keys};
+                      d.thresh16, d.salt, d.row_keys, d.mask};
         dyf::RT* y = make(z->n);
         launch_t_norm_fwd(a, z->p, y->p, st);
-        T.back.push_back([=, this]() -> dyf_status {
+        back([=, this]() -> dyf_status {
             if (!y->g) return DYF_OK;
             double* R = nullptr;
             if (talloc(e, *tmp, &R, (size_t)nb * C * 4, true) != DYF_OK) return DYF_ERR_HIP;
@@ -750,7 +765,7 @@ struct RCtx {
     dyf::RT* linear(dyf::RT* x, int rows, int K, int O, const std::string& name, int pre) {
         dyf::RT* y = make((size_t)rows * O);
         hipLaunchKernelGGL(t_linear_fwd, dim3((unsigned)((O + 3) / 4), (unsigned)((rows + 15) / 16)), dim3(256), 0, st, x->p, P(name + ".weight").w, P(name + ".bias").w, rows, K, O, pre, y->p);
-        T.back.push_back([=, this]() -> dyf_status {
+        back([=, this]() -> dyf_status {
             if (!y->g) return DYF_OK;
             if (param_grads)
                 hipLaunchKernelGGL(t_linear_bwd_w, dim3(nblk((long long)O * K)), dim3(256), 0, st, x->p, y->g, rows, K, O, pre, P(name + ".weight").g,
@@ -768,7 +783,7 @@ struct RCtx {
         dyf::RT* y = make((size_t)nb * (2 * half + 1));
         const std::string name = "time_emb_mlp.0.weights";
         hipLaunchKernelGGL(t_learned_sinu_fwd, dim3(nblk((long long)nb * (2 * half + 1))), dim3(256), 0, st, time_dev, P(name).w, nb, half, y->p);
-        T.back.push_back([=, this]() -> dyf_status {
+        back([=, this]() -> dyf_status {
             if (!y->g || !param_grads) return DYF_OK;
             hipLaunchKernelGGL(t_learned_sinu_bwd, dim3(1), dim3(256), 0, st, time_dev, P(name).w, y->g, nb, half, P(name).g);
             return DYF_OK;
@@ -777,11 +792,12 @@ struct RCtx {
     }
     // ---- Dropout over a whole tensor (dropout_input / dropout_input_for_residual, unet.py:276-277); per = elements of one sample
     dyf::RT* dropout(dyf::RT* x, long long per, float p) {
-        const RDrop d = drop(p);
-        if (!d.on) return x;
+        const RDrop d = drop(p, (size_t)per);
+        if (!d.on && !d.mask) return x;
         dyf::RT* y = make(x->n);
-        hipLaunchKernelGGL(t_dropout_map, dim3(nblk((long long)x->n)), dim3(256), 0, st, x->p, y->p, nb, per, d.scale, d.thresh16, d.salt, d.row_keys);
-        T.back.push_back([=, this]() -> dyf_status {
+        if (d.mask) hipLaunchKernelGGL(t_mask_map, dim3(nblk((long long)x->n)), dim3(256), 0, st, x->p, y->p, (long long)x->n, d.scale, d.mask);
+        else hipLaunchKernelGGL(t_dropout_map, dim3(nblk((long long)x->n)), dim3(256), 0, st, x->p, y->p, nb, per, d.scale, d.thresh16, d.salt, d.row_keys);
+        back([=, this]() -> dyf_status {
             if (!y->g) return DYF_OK;
             float* dx = tbuf(x->n);  // the adjoint is the same keep map on the gradient
             hipLaunchKernelGGL(t_dropout_map, dim3(nblk((long long)x->n)), dim3(256), 0, st, y->g, dx, nb, per, d.scale, d.thresh16, d.salt, d.row_keys);
@@ -790,10 +806,29 @@ struct RCtx {
         });
         return dbg(y, "dropout");
     }
+    // ---- torch.cat of up to three NCHW sources on the channel axis -> NHWC
+    dyf::RT* inputs(const Source* src, int hw, int cin) {
+        dyf::RT* y = make((size_t)nb * hw * cin);
+        hipLaunchKernelGGL(t_nchw_cat_to_nhwc, dim3(nblk((long long)nb * hw * cin)), dim3(256), 0, st, src[0].p, src[0].ch, src[1].p, src[1].ch, src[2].p,
+                           src[2].ch, nb, hw, y->p);
+        return dbg(y, "inputs");
+    }
+    // ---- per-row time values: the caller's, or one value for the whole batch (a sampling plan's step)
+    const float* times(const float* time_dev, float value) {
+        if (time_dev) return time_dev;
+        float* tv = fbuf(nb);
+        hipLaunchKernelGGL(t_fill, dim3(nblk(nb)), dim3(256), 0, st, value, nb, tv);
+        return tv;
+    }
+    dyf::RT* sinusoid(const float* time_dev, int dim) {
+        dyf::RT* y = make((size_t)nb * dim);
+        hipLaunchKernelGGL(t_sinusoid, dim3(nblk(nb * dim)), dim3(256), 0, st, time_dev, nb, dim, y->p);
+        return dbg(y, "sinusoid");
+    }
     dyf::RT* gelu(dyf::RT* x) {
         dyf::RT* y = make(x->n);
         hipLaunchKernelGGL(t_gelu_fwd, dim3(nblk((long long)x->n)), dim3(256), 0, st, x->p, (long long)x->n, y->p);
-        T.back.push_back([=, this]() -> dyf_status {
+        back([=, this]() -> dyf_status {
             if (!y->g) return DYF_OK;
             float* d = tbuf(x->n);
             if (hipMemcpyAsync(d, y->g, x->n * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess) return DYF_ERR_HIP;
@@ -806,7 +841,7 @@ struct RCtx {
     dyf::RT* add(dyf::RT* a, dyf::RT* b) {
         dyf::RT* y = make(a->n);
         launch_t_sum2(a->p, b->p, (long long)a->n, y->p, st);
-        T.back.push_back([=, this]() -> dyf_status {
+        back([=, this]() -> dyf_status {
             if (!y->g) return DYF_OK;
             // y's gradient goes to both inputs: b gets a copy / an add first, then a may take the buffer over (y is done with it)
             if (b->g) {
@@ -830,7 +865,7 @@ struct RCtx {
         }
         dyf::RT* y = make((size_t)pixels * (ca + cb));
         launch_t_concat2(a->p, ca, b->p, cb, pixels, y->p, st);
-        T.back.push_back([=, this]() -> dyf_status {
+        back([=, this]() -> dyf_status {
             if (!y->g) return DYF_OK;
             hipLaunchKernelGGL(t_split2_acc, dim3(nblk(pixels * (ca + cb))), dim3(256), 0, st, y->g, ca, cb, pixels, grad(a), grad(b));
             return DYF_OK;
@@ -840,7 +875,7 @@ struct RCtx {
     dyf::RT* up2_nearest(dyf::RT* x, int h, int w, int C) {
         dyf::RT* y = make(x->n * 4);
         hipLaunchKernelGGL(t_up2n_fwd, dim3(nblk((long long)y->n)), dim3(256), 0, st, x->p, nb, h, w, C, y->p);
-        T.back.push_back([=, this]() -> dyf_status {
+        back([=, this]() -> dyf_status {
             if (!y->g) return DYF_OK;
             hipLaunchKernelGGL(t_up2n_bwd, dim3(nblk((long long)x->n)), dim3(256), 0, st, y->g, nb, h, w, C, grad(x));
             return DYF_OK;
@@ -849,11 +884,11 @@ struct RCtx {
     }
     dyf::RT* layernorm(dyf::RT* x, int hw, int C, const std::string& gname, float p_drop) {
         float2* stats = nullptr;
-        if (talloc(e, T.owned, &stats, (size_t)nb * hw, false) != DYF_OK) err = DYF_ERR_HIP;
-        const RDrop d = drop(p_drop);
+        if (mem.get(&stats, (size_t)nb * hw) != DYF_OK) err = DYF_ERR_HIP;
+        const RDrop d = drop(p_drop, (size_t)hw * C);
         dyf::RT* y = make(x->n);
         hipLaunchKernelGGL(t_ln_fwd, dim3(nblk((long long)nb * hw * 16)), dim3(256), 0, st, x->p, P(gname).w, nb, hw, C, d, y->p, stats);
-        T.back.push_back([=, this]() -> dyf_status {
+        back([=, this]() -> dyf_status {
             if (!y->g) return DYF_OK;
             if (param_grads) {
                 if (C <= 256 && 256 % C == 0)
@@ -887,7 +922,7 @@ struct RCtx {
         hipLaunchKernelGGL(t_la_outer_finish, dim3(nblk(mcount)), dim3(256), 0, st, part, nsplit, mcount, 1.0f / (float)hw, ctx);
         dyf::RT* y = make(tot);
         hipLaunchKernelGGL(t_la_out, dim3(pchunks, nb), dim3(256), 0, st, ctx, sq, hw, scale, y->p);
-        T.back.push_back([=, this]() -> dyf_status {
+        back([=, this]() -> dyf_status {
             if (!y->g) return DYF_OK;
             float* dctx = tbuf((size_t)nb * RH * RD * RD);
             float* dq = tbuf(qkv->n);
@@ -911,10 +946,10 @@ struct RCtx {
         const long long rows = (long long)nb * RH * N;
         const float scale = 1.0f / sqrtf((float)RD);
         float* Pm = fbuf((size_t)rows * N);
-        const RDrop d = drop(p_drop);
+        const RDrop d = drop(p_drop, (size_t)RH * N * N);
         dyf::RT* y = make((size_t)nb * N * RHID);
         hipLaunchKernelGGL(t_at_fwd, dim3(nblk(rows, 64)), dim3(64), 0, st, qkv->p, N, rows, scale, d, Pm, y->p);
-        T.back.push_back([=, this]() -> dyf_status {
+        back([=, this]() -> dyf_status {
             if (!y->g) return DYF_OK;
             float* dS = tbuf((size_t)rows * N);
             float* dq = tbuf(qkv->n);
@@ -945,6 +980,124 @@ RNames rn_names(const dyf_engine* e, const dyf_net_config& c) {
         if (l < r.nlev - 1 && !c.keep_spatial_dims) { h /= 2; w /= 2; }
     }
     return r;
+}
+
+
+// The allocations of RCtx's ops without their launches: what one forward of `nb` rows takes from the sampling arena.  Op by op the
+// same make / fbuf / mem.get calls as above, so rn_walk<RCount> sizes the arena that rn_walk<RCtx> then bumps through.
+struct RCount {
+    const dyf_net_config& c;
+    int nb;
+    size_t bytes = 0;
+    std::deque<dyf::RT> ts;
+    void take(size_t n, size_t el = sizeof(float)) { bytes += f32_arena_block(n * el); }
+    dyf::RT* make(size_t n) { ts.emplace_back(); ts.back().n = n; take(n); return &ts.back(); }
+    dyf::RT* conv(dyf::RT*, int h, int w, int cin, int cout, int k, int s, int p, const std::string&, bool, bool ws) {
+        const int ho = (h + 2 * p - k) / s + 1, wo = (w + 2 * p - k) / s + 1;
+        if (ws) { take((size_t)cout * k * k * cin); take((size_t)cout * k * k * cin); take(cout); }
+        return make((size_t)nb * ho * wo * cout);
+    }
+    dyf::RT* gn_act(dyf::RT* z, int, int C, const std::string&, dyf::RT*, float) {
+        take((size_t)nb * c.groups); take((size_t)nb * c.groups); take((size_t)nb * C * 2, sizeof(double));
+        return make(z->n);
+    }
+    dyf::RT* linear(dyf::RT*, int rows, int, int O, const std::string&, int) { return make((size_t)rows * O); }
+    dyf::RT* learned_sinu(const float*, int half) { return make((size_t)nb * (2 * half + 1)); }
+    dyf::RT* dropout(dyf::RT* x, long long, float p) { return p > 0.0f ? make(x->n) : x; }
+    dyf::RT* inputs(const Source*, int hw, int cin) { return make((size_t)nb * hw * cin); }
+    const float* times(const float*, float) { take(nb); return nullptr; }
+    dyf::RT* sinusoid(const float*, int dim) { return make((size_t)nb * dim); }
+    dyf::RT* gelu(dyf::RT* x) { return make(x->n); }
+    dyf::RT* add(dyf::RT* a, dyf::RT*) { return make(a->n); }
+    dyf::RT* cat(dyf::RT*, int ca, dyf::RT*, int cb, long long pixels) { return make((size_t)pixels * (ca + cb)); }
+    dyf::RT* up2_nearest(dyf::RT* x, int, int, int) { return make(x->n * 4); }
+    dyf::RT* layernorm(dyf::RT* x, int hw, int, const std::string&, float) { take((size_t)nb * hw, sizeof(float2)); return make(x->n); }
+    dyf::RT* linattn(dyf::RT*, int hw) {
+        const size_t tot = (size_t)nb * hw * RHID;
+        take(tot); take(tot); take((size_t)nb * RHID); take((size_t)nb * RHID); take((size_t)nb * RH * RD * RD);
+        take((size_t)2 * nb * ((hw + LA_PCHUNK - 1) / LA_PCHUNK) * RHID);
+        take((size_t)2 * ((hw + LA_CHUNK - 1) / LA_CHUNK) * nb * RH * RD * RD * 2);
+        return make(tot);
+    }
+    dyf::RT* attention(dyf::RT*, int N, float) { take((size_t)nb * RH * N * N); return make((size_t)nb * N * RHID); }
+};
+
+// The layer walk of unet.Unet.forward (unet.py:262-315), shared by the recorded forward, the sampling forward (both RCtx: they differ
+// in where RCtx::mem takes the tensors from) and the sizing of the sampling arena (RCount).  src: up to three NCHW sources in channel
+// order (condition first, unet.py:269).  Returns the NHWC output.
+template <typename Ctx>
+RT* rn_walk(Ctx& X, const dyf_net_config& c, const RNames& R, int nb, int H, int W, int cin_total, const Source* src, const float* time_dev_in,
+            float time_value, RT** x_in) {
+    const int hw = H * W;
+    const int cin = cin_total, dim = c.dim, tdim = 2 * c.dim;
+    // ---- inputs: torch.cat((condition, x), 1) (unet.py:269), NCHW -> NHWC
+    RT* xin = X.inputs(src, hw, cin);
+    *x_in = xin;
+    // ---- time embedding: sinusoid -> Linear -> GELU -> Linear (misc.py:54-67)
+    RT* temb = nullptr;
+    if (c.with_time_emb) {
+        const float* time_dev = X.times(time_dev_in, time_value);
+        RT* e0 = nullptr;
+        int tfeat = dim;
+        if (c.learned_sinusoidal_dim > 0) {  // LearnedSinusoidalPosEmb (misc.py:35-51): [t, sin(2 pi t w), cos(2 pi t w)], w learnable
+            tfeat = c.learned_sinusoidal_dim + 1;
+            e0 = X.learned_sinu(time_dev, c.learned_sinusoidal_dim / 2);
+        } else {
+            e0 = X.sinusoid(time_dev, dim);
+        }
+        temb = X.linear(X.gelu(X.linear(e0, nb, tfeat, tdim, "time_emb_mlp.1", 0)), nb, tdim, tdim, "time_emb_mlp.3", 0);
+    }
+    auto resblock = [&](const std::string& pre, RT* x, int cx, int cout, int hh, int ww) -> RT* {
+        RT* ss = temb ? X.linear(temb, nb, tdim, 2 * cout, pre + ".mlp.1", 1) : nullptr;
+        RT* h1 = X.gn_act(X.conv(x, hh, ww, cx, cout, 3, 1, 1, pre + ".block1.proj", true, true), hh * ww, cout, pre + ".block1.norm", ss, c.block_dropout1);
+        RT* h2 = c.single_conv_layer ? h1  // double_conv_layer=False: block2 = Identity
+                                     : X.gn_act(X.conv(h1, hh, ww, cout, cout, 3, 1, 1, pre + ".block2.proj", true, true), hh * ww, cout,
+                                                pre + ".block2.norm", nullptr, c.dropout);
+        RT* res = cx != cout ? X.conv(x, hh, ww, cx, cout, 1, 1, 0, pre + ".residual_conv", true, false) : x;
+        return X.add(h2, res);
+    };
+    auto attn = [&](const std::string& pre, RT* x, int C, int hh, int ww, bool linear) -> RT* {
+        RT* ln = X.layernorm(x, hh * ww, C, pre + ".fn.norm.g", linear ? c.attn_dropout : 0.0f);
+        RT* qkv = X.conv(ln, hh, ww, C, 3 * RHID, 1, 1, 0, pre + (linear ? ".fn.fn.to_qkv.1" : ".fn.fn.to_qkv"), false, false);
+        RT* core = linear ? X.linattn(qkv, hh * ww) : X.attention(qkv, hh * ww, c.attn_dropout);
+        return X.add(X.conv(core, hh, ww, RHID, C, 1, 1, 0, pre + ".fn.fn.to_out", true, false), x);
+    };
+    const int ks = c.init_kernel_size;
+    RT* x = X.conv(xin, H, W, cin, dim, ks, 1, c.init_padding, "init_conv", true, false);
+    RT* r0 = X.dropout(x, (long long)hw * dim, c.input_dropout);  // dropout_input_for_residual first, then dropout_input
+    x = X.dropout(x, (long long)hw * dim, c.input_dropout);
+    std::vector<std::pair<RT*, int>> skips;
+    for (int l = 0; l < R.nlev; ++l) {
+        const int hh = R.lev_h[l], ww = R.lev_w[l], dl = R.dims[l];
+        const std::string pre = "downs." + std::to_string(l);
+        x = resblock(pre + ".0", x, dl, dl, hh, ww);
+        skips.emplace_back(x, dl);
+        x = resblock(pre + ".1", x, dl, dl, hh, ww);
+        x = attn(pre + ".2", x, dl, hh, ww, true);
+        skips.emplace_back(x, dl);
+        if (l < R.nlev - 1 && !c.keep_spatial_dims) x = X.conv(x, hh, ww, dl, R.dims[l + 1], 4, 2, 1, pre + ".3", true, false);
+        else x = X.conv(x, hh, ww, dl, R.dims[l + 1], 3, 1, 1, pre + ".3", true, false);
+    }
+    {
+        const int hh = R.lev_h.back(), ww = R.lev_w.back(), dm = R.dims[R.nlev];
+        x = resblock("mid_block1", x, dm, dm, hh, ww);
+        x = attn("mid_attn", x, dm, hh, ww, false);
+        x = resblock("mid_block2", x, dm, dm, hh, ww);
+    }
+    for (int l = R.nlev - 1, u = 0; l >= 0; --l, ++u) {
+        const int hh = R.lev_h[l], ww = R.lev_w[l], dout = R.dims[l + 1], din = R.dims[l];
+        const std::string pre = "ups." + std::to_string(u);
+        auto s1 = skips.back(); skips.pop_back();
+        x = resblock(pre + ".0", X.cat(x, dout, s1.first, s1.second, (long long)nb * hh * ww), dout + din, dout, hh, ww);
+        auto s2 = skips.back(); skips.pop_back();
+        x = resblock(pre + ".1", X.cat(x, dout, s2.first, s2.second, (long long)nb * hh * ww), dout + din, dout, hh, ww);
+        x = attn(pre + ".2", x, dout, hh, ww, true);
+        if (l > 0 && !c.keep_spatial_dims) x = X.conv(X.up2_nearest(x, hh, ww, dout), 2 * hh, 2 * ww, dout, din, 3, 1, 1, pre + ".3.1", true, false);
+        else x = X.conv(x, hh, ww, dout, din, 3, 1, 1, pre + ".3", true, false);
+    }
+    x = resblock("final_res_block", X.cat(x, dim, r0, dim, (long long)nb * hw), 2 * dim, dim, H, W);
+    RT* y = X.conv(x, H, W, dim, c.out_channels, 1, 1, 0, "final_conv", true, false);
+    return y;
 }
 
 }  // namespace
@@ -1058,80 +1211,62 @@ dyf_status rn_train_forward(dyf_engine* e, int which, int slot, const float* inp
     RCtx* Xp = new RCtx{e, *wp, T, c, st, nb, drop_on};
     T.ctx = std::shared_ptr<void>(Xp, [](void* p) { delete (RCtx*)p; });
     RCtx& X = *Xp;
-    const int cin = n.cin_total, dim = c.dim, tdim = 2 * c.dim;
-    // ---- inputs: torch.cat((condition, x), 1) (unet.py:269), NCHW -> NHWC
-    RT* xin = X.make((size_t)nb * hw * cin);
-    T.x_in = xin;
-    hipLaunchKernelGGL(t_nchw_cat_to_nhwc, dim3(nblk((long long)nb * hw * cin)), dim3(256), 0, st, cond_dev, c.cond_channels, inputs_dev, c.in_channels,
-                       (const float*)nullptr, 0, nb, hw, xin->p);
-    X.dbg(xin, "inputs");
-    // ---- time embedding: sinusoid -> Linear -> GELU -> Linear (misc.py:54-67)
-    RT* temb = nullptr;
-    if (c.with_time_emb) {
-        RT* e0 = nullptr;
-        int tfeat = dim;
-        if (c.learned_sinusoidal_dim > 0) {  // LearnedSinusoidalPosEmb (misc.py:35-51): [t, sin(2 pi t w), cos(2 pi t w)], w learnable
-            tfeat = c.learned_sinusoidal_dim + 1;
-            e0 = X.learned_sinu(time_dev, c.learned_sinusoidal_dim / 2);
-        } else {
-            e0 = X.make((size_t)nb * dim);
-            hipLaunchKernelGGL(t_sinusoid, dim3(nblk(nb * dim)), dim3(256), 0, st, time_dev, nb, dim, e0->p);
-            X.dbg(e0, "sinusoid");
-        }
-        temb = X.linear(X.gelu(X.linear(e0, nb, tfeat, tdim, "time_emb_mlp.1", 0)), nb, tdim, tdim, "time_emb_mlp.3", 0);
-    }
-    auto resblock = [&](const std::string& pre, RT* x, int cx, int cout, int hh, int ww) -> RT* {
-        RT* ss = temb ? X.linear(temb, nb, tdim, 2 * cout, pre + ".mlp.1", 1) : nullptr;
-        RT* h1 = X.gn_act(X.conv(x, hh, ww, cx, cout, 3, 1, 1, pre + ".block1.proj", true, true), hh * ww, cout, pre + ".block1.norm", ss, c.block_dropout1);
-        RT* h2 = c.single_conv_layer ? h1  // double_conv_layer=False: block2 = Identity
-                                     : X.gn_act(X.conv(h1, hh, ww, cout, cout, 3, 1, 1, pre + ".block2.proj", true, true), hh * ww, cout,
-                                                pre + ".block2.norm", nullptr, c.dropout);
-        RT* res = cx != cout ? X.conv(x, hh, ww, cx, cout, 1, 1, 0, pre + ".residual_conv", true, false) : x;
-        return X.add(h2, res);
-    };
-    auto attn = [&](const std::string& pre, RT* x, int C, int hh, int ww, bool linear) -> RT* {
-        RT* ln = X.layernorm(x, hh * ww, C, pre + ".fn.norm.g", linear ? c.attn_dropout : 0.0f);
-        RT* qkv = X.conv(ln, hh, ww, C, 3 * RHID, 1, 1, 0, pre + (linear ? ".fn.fn.to_qkv.1" : ".fn.fn.to_qkv"), false, false);
-        RT* core = linear ? X.linattn(qkv, hh * ww) : X.attention(qkv, hh * ww, c.attn_dropout);
-        return X.add(X.conv(core, hh, ww, RHID, C, 1, 1, 0, pre + ".fn.fn.to_out", true, false), x);
-    };
-    const int ks = c.init_kernel_size;
-    RT* x = X.conv(xin, H, W, cin, dim, ks, 1, c.init_padding, "init_conv", true, false);
-    RT* r0 = X.dropout(x, (long long)hw * dim, c.input_dropout);  // dropout_input_for_residual first, then dropout_input
-    x = X.dropout(x, (long long)hw * dim, c.input_dropout);
-    std::vector<std::pair<RT*, int>> skips;
-    for (int l = 0; l < R.nlev; ++l) {
-        const int hh = R.lev_h[l], ww = R.lev_w[l], dl = R.dims[l];
-        const std::string pre = "downs." + std::to_string(l);
-        x = resblock(pre + ".0", x, dl, dl, hh, ww);
-        skips.emplace_back(x, dl);
-        x = resblock(pre + ".1", x, dl, dl, hh, ww);
-        x = attn(pre + ".2", x, dl, hh, ww, true);
-        skips.emplace_back(x, dl);
-        if (l < R.nlev - 1 && !c.keep_spatial_dims) x = X.conv(x, hh, ww, dl, R.dims[l + 1], 4, 2, 1, pre + ".3", true, false);
-        else x = X.conv(x, hh, ww, dl, R.dims[l + 1], 3, 1, 1, pre + ".3", true, false);
-    }
-    {
-        const int hh = R.lev_h.back(), ww = R.lev_w.back(), dm = R.dims[R.nlev];
-        x = resblock("mid_block1", x, dm, dm, hh, ww);
-        x = attn("mid_attn", x, dm, hh, ww, false);
-        x = resblock("mid_block2", x, dm, dm, hh, ww);
-    }
-    for (int l = R.nlev - 1, u = 0; l >= 0; --l, ++u) {
-        const int hh = R.lev_h[l], ww = R.lev_w[l], dout = R.dims[l + 1], din = R.dims[l];
-        const std::string pre = "ups." + std::to_string(u);
-        auto s1 = skips.back(); skips.pop_back();
-        x = resblock(pre + ".0", X.cat(x, dout, s1.first, s1.second, (long long)nb * hh * ww), dout + din, dout, hh, ww);
-        auto s2 = skips.back(); skips.pop_back();
-        x = resblock(pre + ".1", X.cat(x, dout, s2.first, s2.second, (long long)nb * hh * ww), dout + din, dout, hh, ww);
-        x = attn(pre + ".2", x, dout, hh, ww, true);
-        if (l > 0 && !c.keep_spatial_dims) x = X.conv(X.up2_nearest(x, hh, ww, dout), 2 * hh, 2 * ww, dout, din, 3, 1, 1, pre + ".3.1", true, false);
-        else x = X.conv(x, hh, ww, dout, din, 3, 1, 1, pre + ".3", true, false);
-    }
-    x = resblock("final_res_block", X.cat(x, dim, r0, dim, (long long)nb * hw), 2 * dim, dim, H, W);
-    RT* y = X.conv(x, H, W, dim, c.out_channels, 1, 1, 0, "final_conv", true, false);
+    Source src[3] = {{cond_dev, cond_dev ? c.cond_channels : 0}, {inputs_dev, c.in_channels}, {nullptr, 0}};
+    X.mem = FwdMem{e, &T.owned, st};
+    RT* y = rn_walk(X, c, R, nb, H, W, n.cin_total, src, time_dev, 0.0f, &T.x_in);
     T.out = y;
     if (X.err != DYF_OK) return fail(e, X.err, "training forward: allocation / launch failed");
+    hipLaunchKernelGGL(t_nhwc_to_nchw, dim3(nblk((long long)nb * hw * c.out_channels)), dim3(256), 0, st, y->p, nb, hw, c.out_channels, 0, c.out_channels, out_dev);
+    TK(hipGetLastError());
+    return DYF_OK;
+}
+
+// ---- fp32 sampling (dyf_set_sample_precision(32)): the same walk on the engine's bump arena, nothing recorded
+// bytes one forward of `nb` rows takes from the arena
+size_t rn_arena_bytes(const dyf_engine* e, const Net& n, int nb) {
+    const RNames R = rn_names(e, n.cfg);
+    RCount K{n.cfg, nb};
+    Source none[3] = {{nullptr, 0}, {nullptr, 0}, {nullptr, 0}};
+    RT* xi = nullptr;
+    RT* y = rn_walk(K, n.cfg, R, nb, e->cfg.height, e->cfg.width, n.cin_total, none, nullptr, 0.0f, &xi);
+    (void)y;
+    return K.bytes;
+}
+
+// the fp32 Attention core keeps its (tokens x tokens) probabilities, as the training step does
+bool rn_f32_supported(const dyf_engine* e, const Net& n) {
+    const RNames R = rn_names(e, n.cfg);
+    return (long long)R.lev_h.back() * R.lev_w.back() <= 4096;
+}
+
+dyf_status rn_f32_forward(dyf_engine* e, int which, const Source* srcs, int nsrc, int nb, const FwdOpts& o, float* out_dev, hipStream_t st) {
+    RTNet* wp = e->train ? e->train->rnet[which] : nullptr;
+    if (!wp || !wp->ready) return fail(e, DYF_ERR_STATE, "fp32 sampling needs loaded weights (dyf_load_weights)");
+    Net& n = e->net[which];
+    const dyf_net_config& c = n.cfg;
+    const RNames R = rn_names(e, c);
+    const int H = e->cfg.height, W = e->cfg.width, hw = H * W;
+    Source src[3] = {{nullptr, 0}, {nullptr, 0}, {nullptr, 0}};
+    int ctot = 0;
+    for (int i = 0; i < nsrc && i < 3; ++i) {
+        src[i] = srcs[i];
+        if (!src[i].p) src[i].ch = 0;
+        ctot += src[i].ch;
+    }
+    if (ctot != n.cin_total) return fail(e, DYF_ERR_INVALID_ARGUMENT, "channel count of the network inputs does not match its configuration");
+    const bool any_p = c.dropout > 0.0f || c.block_dropout1 > 0.0f || c.attn_dropout > 0.0f || c.input_dropout > 0.0f;
+    const bool drop_on = o.dropout_mode == 1 && any_p;
+    RTape T;  // scratch: a sampling forward leaves nothing behind
+    if (drop_on) {  // begin the forward in the generator exactly as the 16-bit path does; the keys are read from the engine's table
+        TK(launch_rng_begin_forward(e->rng_state, e->row_keys, nb, nb, st));
+        T.row_keys = e->row_keys;
+    }
+    RCtx X{e, *wp, T, c, st, nb, drop_on};
+    X.mem = FwdMem{e, nullptr, st};
+    X.masks = (o.dropout_mode == 2 && o.masks && any_p) ? o.masks : nullptr;
+    RT* xi = nullptr;
+    RT* y = rn_walk(X, c, R, nb, H, W, n.cin_total, src, o.time_dev, o.time_value, &xi);
+    if (X.err != DYF_OK) return fail(e, X.err, e->err.empty() ? "fp32 forward: allocation / launch failed" : e->err);
     hipLaunchKernelGGL(t_nhwc_to_nchw, dim3(nblk((long long)nb * hw * c.out_channels)), dim3(256), 0, st, y->p, nb, hw, c.out_channels, 0, c.out_channels, out_dev);
     TK(hipGetLastError());
     return DYF_OK;

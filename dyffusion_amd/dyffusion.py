@@ -101,8 +101,10 @@ class DYffusion(nn.Module):
 
         # ---- engine: forecaster + interpolator in one dyf_engine
         # dtype: 16-bit storage / MFMA operand format of the engine: "bf16" or "fp16"; None = the forecaster class's default
-        # (engine.default_dtype_for: bf16 for unet_simple -- BASELINE configs[1] --, fp16 for the ResNet-UNet -- configs[2], [4])
-        dtype = dtype or default_dtype_for(model)
+        # (engine.default_dtype_for: bf16 for unet_simple -- BASELINE configs[1] --, fp16 for the ResNet-UNet -- configs[2], [4]);
+        # "fp32" / "float32" / "32": reference-precision sampling (HipEngine.set_sample_precision(32); arch unet_simple).
+        # An unknown string is a ValueError here, not a KeyError at the first sample.
+        dtype = L.canonical_dtype(dtype or default_dtype_for(model))
         self._engine_opts = dict(max_batch=max_batch, use_graph=use_graph, enable_mfma=enable_mfma, dtype=dtype,
                                  batch_invariant=batch_invariant,  # batch_invariant: bit-identical rows under any batching / sharding
                                  row_groups=row_groups,  # concurrent row groups of a sampling call (None = engine default)

@@ -60,7 +60,8 @@ def default_dtype_for(net) -> str:
     SimpleConvNet backbones (BASELINE configs[1]: "bf16"), "fp16" for the ResNet-UNet `unet.Unet` (OISST, 512^2: ~60 16-bit
     roundings per forward and 93 chained forwards per rollout -- bf16's 8 mantissa bits give 4e-2 .. 5e-2 per field over the
     OISST rollout, fp16's 11 bits 6e-3 at the same MFMA rate and the same bytes).  A network class states
-    its default as `default_engine_dtype`; `net.engine_dtype = "bf16" | "fp16"` or `DYffusion(dtype=...)` override it."""
+    its default as `default_engine_dtype`; `net.engine_dtype = "bf16" | "fp16" | "fp32"` or `DYffusion(dtype=...)` override it
+    ("fp32": reference-precision sampling, dyf_set_sample_precision(32); arch unet_simple)."""
     return getattr(net, "engine_dtype", None) or getattr(net, "default_engine_dtype", "bf16")
 
 
@@ -96,12 +97,14 @@ class HipEngine:
                  batch_invariant: bool = False, row_groups: Optional[int] = None, train_precision=None):
         if not torch.cuda.is_available():
             raise EngineError("no GPU visible: the DYffusion HIP engine needs an MI355X (gfx950); there is no CPU fallback")
-        self.dtype = dtype
-        self._lib = L.lib(dtype)
+        # "fp32" / "float32" / "32": the default (bf16) build with dyf_set_sample_precision(32) -- every sampling forward in fp32
+        self.dtype = L.canonical_dtype(dtype)
+        storage = L.storage_dtype(dtype)
+        self._lib = L.lib(storage)
         self.device = torch.cuda.current_device() if device is None else int(device)
         self.height, self.width, self.max_batch = int(height), int(width), int(max_batch)
         cfg = L.EngineConfig(L.DYF_ABI_VERSION, self.device, self.height, self.width, self.max_batch, int(use_graph),
-                             int(enable_mfma), L.DTYPES[dtype], int(batch_invariant),
+                             int(enable_mfma), L.DTYPES[storage], int(batch_invariant),
                              (L.NetConfig * 2)(forecaster, interpolator))
         self.cfg = cfg
         h = C.c_void_p()
@@ -109,6 +112,12 @@ class HipEngine:
         if st != L.DYF_OK:
             _raise(st, self._lib.dyf_last_error(None).decode())
         self._h = h
+        if self.dtype == "fp32":
+            try:
+                self.set_sample_precision(32)
+            except Exception:
+                self.close()
+                raise
         if row_groups is not None:  # None: the engine's own default (dyf_engine_create, DYF_ROW_GROUPS)
             self._check(self._lib.dyf_set_row_groups(self._h, int(row_groups)))
         if train_precision is not None:
@@ -148,6 +157,15 @@ class HipEngine:
     def debug_gn_fuse(self, timeout_ticks: int = 0, force_timeout: bool = False):
         """Test hook (dyf_debug_gn_fuse): sweep bound in 100 MHz ticks, forced time-out of every granule sweep."""
         self._check(self._lib.dyf_debug_gn_fuse(self._h, int(timeout_ticks), int(force_timeout)))
+
+    def set_sample_precision(self, bits: int) -> None:
+        """dyf_set_sample_precision: 16 = the library's 16-bit path, 32 = fp32 forwards for net_forward / sample / sample_gather
+        (the first switch to 32 allocates the engine's fp32 arena; ValueError for any other value)."""
+        self._check(self._lib.dyf_set_sample_precision(self._h, int(bits)))
+
+    @property
+    def sample_precision(self) -> int:
+        return int(self._lib.dyf_sample_precision(self._h))
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
@@ -653,7 +671,7 @@ class HipEngine:
 
     @property
     def torch_dtype(self) -> torch.dtype:
-        return torch.float16 if L.DTYPES[self.dtype] else torch.bfloat16
+        return torch.float16 if L.DTYPES[L.storage_dtype(self.dtype)] else torch.bfloat16
 
     def op_attention(self, qkv: torch.Tensor, p_drop: float = 0.0) -> torch.Tensor:
         """Test seam: Attention core.  qkv (N,HW,384) in the engine's 16-bit dtype (to_qkv output) -> (N,HW,128); p_drop > 0:

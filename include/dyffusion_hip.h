@@ -12,7 +12,8 @@
  *   - plain C types only; every pointer named *_dev is DEVICE memory owned by the caller (e.g. a torch tensor's
  *     data_ptr()), everything else is HOST memory.  Tensors crossing the ABI are fp32, NCHW, contiguous -- the
  *     reference's layout.  Internally the engine keeps activations NHWC in a 16-bit format (bf16, or fp16 in the
- *     libdyffusion_hip_f16.so build) and accumulates in fp32.
+ *     libdyffusion_hip_f16.so build) and accumulates in fp32; dyf_set_sample_precision(32) switches an engine to fp32 activations
+ *     and weights (reference-precision rollouts, ABI 9).
  *   - the engine owns packed device weights, its workspace arena and captured hipGraphs; no allocation happens
  *     inside dyf_sample / dyf_net_forward after the first call for a given batch size.
  *   - one engine per (device, stream); calls on one engine are not re-entrant.
@@ -29,7 +30,7 @@
 extern "C" {
 #endif
 
-#define DYF_ABI_VERSION 8
+#define DYF_ABI_VERSION 9
 
 typedef struct dyf_engine dyf_engine;
 
@@ -194,13 +195,40 @@ dyf_status dyf_set_row_offset(dyf_engine* engine, uint32_t first_row);
  * gaps of one group are covered by the kernels of the others.  Row g*per + i of the call is row i of group g and draws the
  * masks / noise of global row (row offset + g*per + i): the generator streams are those of the ungrouped call.  Default: chosen
  * at dyf_engine_create from the architecture and max_batch (ResNet-UNet on planes <= 128 x 128, not batch_invariant: 3 groups from
- * 432 000 pixels x rows = 120 rows of 60 x 60, 2 from 230 400 = 64 rows; otherwise 1; the kernel-form switch DYF_ROW_GROUPS overrides).  Must be called before dyf_load_weights.
+ * 432 000 pixels x rows = 120 rows of 60 x 60, 2 from 230 400 = 64 rows; otherwise 1).  Must be called before dyf_load_weights.
  * Calls with fewer than 32 rows, with injected masks / noise, and every other entry point run on the engine itself.
  * Three groups plus the caller's stream fill the 4 hardware queues of a HIP process: with other busy streams or other live engines
  * in the process two groups are the robust choice.
  * dyf_row_groups returns the number of groups in effect (1 = none). */
 dyf_status dyf_set_row_groups(dyf_engine* engine, int32_t n_groups);
 int32_t dyf_row_groups(const dyf_engine* engine);
+
+/* Sampling precision (ABI 9).  bits = 16 (default): the library's own 16-bit path (bf16, or fp16 in the _f16 build), unchanged.
+ * bits = 32: every network forward of the calls that follow -- dyf_net_forward, dyf_sample, dyf_sample_gather -- runs in fp32: fp32
+ * NHWC activations, the fp32 parameter copy dyf_load_weights keeps (no training call needed), the convolutions on the fp32 matrix cores.
+ * unet_simple and unet.Unet run the layer walk and the kernels of dyf_train_forward without DYF_TRAIN_BATCH_STATS (BatchNorm on running
+ * statistics, GroupNorm per sample) -- one walk, recorded on a tape there, bumped through an arena here; SimpleConvNet has an fp32 forward
+ * of its own (csrc/simple_conv_net.hip).  The arena is allocated by the FIRST switch to 32 for max_batch rows of the larger network and
+ * freed by dyf_engine_destroy: nothing is allocated or synchronised inside a forward, the forward is bitwise repeatable (split-K sums are
+ * reduced through a workspace in a fixed order, GroupNorm sums by one workgroup per sample) and a rollout is captured and replayed with
+ * use_graph like the 16-bit one.  Both builds of the library implement it alike; it does not depend on dyf_engine_config.dtype.
+ * unet.Unet with more than 4096 bottleneck tokens (the fp32 Attention core keeps its probabilities): DYF_ERR_UNSUPPORTED.  Any other
+ * value of bits: DYF_ERR_INVALID_ARGUMENT.
+ *   - the plan walker is the 16-bit one (sampler state, cold-sampling update, noisy condition, forecast stack, log, dyf_get_sampler_state,
+ *     dyf_plan_forward_counts are shared); in fp32 there is no paired interpolator forward, no batched refinement and no row groups
+ *     (dyf_set_row_groups stays accepted, a call behaves as with one group).  Forward order, and so the order of the generator's forward
+ *     counter: forecaster, next-step interpolation, current-step interpolation; then the refinement pass one time after the other.
+ *   - dropout mode 1 starts every forward from the generator exactly as the 16-bit path does -- same site numbers (a layer with p = 0
+ *     is no site), same per-site salt, same 16-bit keep threshold, same global row keys: for equal seed, row offset and call sequence
+ *     an fp32 engine draws the keep bits of a 16-bit engine at every activation site.  The one exception is the attention-probability
+ *     site of unet.Unet: the 16-bit flash kernel keeps with k/256 granularity (rng_keep8, csrc/common.h), the fp32 path keeps nn.Dropout's
+ *     p through the 16-bit threshold, as the training path does -- same stream, a different threshold on it.
+ *   - dropout mode 2 applies the caller's uint8 keep masks, layout and site order as in the 16-bit path ((NB, 4, N, N) for the
+ *     attention probabilities).
+ *   - a graph captured under one precision is never replayed under the other.
+ * dyf_sample_precision returns 16 or 32. */
+dyf_status dyf_set_sample_precision(dyf_engine* engine, int32_t bits);
+int32_t dyf_sample_precision(const dyf_engine* engine);
 
 /* ---- engine-owned exchange of the ensemble-sharded path (one process per GPU; the reference has no inference collective) ------- */
 /* Ensemble members / batch items are independent rows for the whole rollout (_base_experiment.py:503-538 tiles them, row = n*B + b),
