@@ -26,9 +26,9 @@ struct ConvArgs {
     int ho, wo;          // output height / width
     int kh, kw, stride, pad;
     int cout;
-    const el16_t* wpk;   // packed weights [cout][kh*kw][c0+c1] bf16
-    const el16_t* wpk_frag;  // the same weights in MFMA fragment order (pack_conv_frag) for conv_igemm2, or null: looked up
-                             // in the registry (conv_register_frag) by conv_choose_form
+    const el16_t* wpk;   // packed weights [cout][kh*kw][c0+c1] bf16: ConvW::wpk, copied in by launch_conv*
+    const el16_t* wpk_frag;  // the same weights in MFMA fragment order (pack_conv_frag) for conv_igemm2 / conv_skinny: never an
+                             // input, written by the dispatcher from the chosen form's ConvW pointer
     // fused x2 bilinear upsample in front of a 3x3/s1/p1 conv: sources are the LOW-res tensors (h, w), output is
     // (2h, 2w); wpk_up holds the phase-decomposed weights [4][cout][16][c0+c1] (pack_up2x_weights)
     int up2x;
@@ -87,35 +87,49 @@ struct ConvArgs {
 // floats of ConvArgs::up_border for an n x (2h x 2w) x cout output
 inline size_t conv_up_border_floats(int n, int h, int w, int cout) { return (size_t)n * (4 * (size_t)w + 4 * (size_t)h - 4) * cout; }
 
+// One conv's weights on the device: the packed copy and its fragment-ordered copies, allocated and freed together (host only; never
+// a kernel argument).  upload_conv_weights (engine_internal.h) decides which orders a conv gets; an admission rule of
+// conv_dispatch.hip takes a pointer only under the order it streams.
+enum class HaloOrder { None, Halo3_256 /* pack_halo3_frag */, Halo3_64 /* pack_halo3_frag64 */, S2 /* pack_halo_s2_frag */,
+                       Enc0Stem /* pack_enc0_stem_frag */ };
+struct ConvW {
+    const el16_t* wpk = nullptr;     // [cout][taps][cin]
+    const el16_t* frag = nullptr;    // pack_conv_frag (igemm2, skinny) or null
+    const el16_t* halo = nullptr;    // halo-kernel order named by halo_order, or null
+    HaloOrder halo_order = HaloOrder::None;
+    const el16_t* frag64 = nullptr;  // pack_halo3_frag64 of a cout % 256 == 0 3x3 conv (conv_gn16_kernel) or null
+};
+
 // ================================================================================================ dispatch API (conv_dispatch.hip)
 // path: 0 direct (any shape), 1 implicit-GEMM MFMA (needs c0 % 64 == 0, c1 % 64 == 0, cout % 64 == 0)
 hipError_t conv_init();
 bool conv_mfma_supported(const ConvArgs& a);
 // Which kernel form a conv takes -- the performance policy -- is decided in ONE place: conv_choose_form returns a value, launches
 // nothing and touches no stream.  launch_conv* = choose, copy the choice's fields into the ConvArgs, call that form's launcher.
+// The weights travel beside the ConvArgs as the layer's ConvW (a.wpk of the argument is ignored: the launch reads w.wpk).
 enum class ConvForm { Invalid /* hipErrorInvalidValue */, None /* GnFused: no fused form fits */, Direct, Igemm128, Igemm256x64, UpHalo,
                       Halo3, Rows3, Halo5, HaloS2, Enc0Stem, Igemm2, Skinny, Gn16 };
 enum class ConvWant { Plain, Stats /* GroupNorm statistics where the form produces them */, GnFused };
 struct ConvChoice {
     ConvForm form;
-    const el16_t* frag;  // the form's fragment-ordered weights from the registries (wpk_up_frag / wpk_frag / enc0-stem argument), or null
+    const el16_t* frag;  // the form's fragment-ordered weights out of the ConvW (wpk_up_frag / wpk_frag / enc0-stem argument), or null
     int gn_slots;        // Stats: ConvArgs::gn_slots (0: the launch writes no statistics); GnFused: GnFuse::slots
     int bm;              // GnFused on igemm2: GnFuse::bm (128 / 256), else 0
 };
-ConvChoice conv_choose_form(const ConvArgs& a, int path, ConvWant want);
-hipError_t launch_conv(const ConvArgs& a, int path, hipStream_t stream);
+ConvChoice conv_choose_form(const ConvArgs& a, const ConvW& w, int path, ConvWant want);
+hipError_t launch_conv(const ConvArgs& a, const ConvW& w, int path, hipStream_t stream);
 // launch_conv for a conv whose output feeds a GroupNorm (a.gn_part != null): *gn_slots receives the partial-sum slots per sample
 // the launch wrote (0: this kernel form does not produce statistics -- the caller runs the statistics pass)
-hipError_t launch_conv_stats(const ConvArgs& a, int path, hipStream_t stream, int* gn_slots);
+hipError_t launch_conv_stats(const ConvArgs& a, const ConvW& w, int path, hipStream_t stream, int* gn_slots);
 // launch_conv for a conv followed by GroupNorm + FiLM + SiLU + Dropout (+ residual), a.gnf filled in except `slots`: *fused = the
 // launch did all of it (conv_gn16_kernel, conv_up_halo_kernel<5, 2>, conv_igemm2_kernel<2, true>); false = NOTHING was launched (the
 // shape / batch is not served by a fused form: the caller runs the conv and the GroupNorm kernels)
-hipError_t launch_conv_gn_fused(const ConvArgs& a, int path, hipStream_t stream, bool* fused);
+hipError_t launch_conv_gn_fused(const ConvArgs& a, const ConvW& w, int path, hipStream_t stream, bool* fused);
 // upper bound of GnFuse::slots on an h x w plane over the fused forms (sizing of GnFuse::gran), 0 = never fused
 int conv_gn_fused_max_slots(int h, int w);
-// launch_conv(a, 1, ...) of this plain 3x3 conv (no statistics, no fused GroupNorm) will run on conv_up_halo_kernel<5> -- the one form
+// launch_conv(a, w, 1, ...) of this plain 3x3 conv (no statistics, no fused GroupNorm) will run on conv_up_halo_kernel<5> -- the one form
 // that can take ConvArgs::up_nearest
-bool conv_plain3x3_takes_halo5(const ConvArgs& a);
+bool conv_plain3x3_takes_halo5(const ConvArgs& a, const ConvW& w);
 
 // ================================================================================================ per-form launchers and predicates
 // conv.hip: the direct kernel (any shape; hipErrorInvalidValue for up2x) and conv_igemm_kernel (<128,128> / <256,64> by cout % 128,
@@ -149,12 +163,12 @@ hipError_t conv_halo_rows_init();
 hipError_t launch_conv_halo_rows_up(const ConvArgs& a, hipStream_t stream);  // main kernel only (after up_border_kernel)
 hipError_t launch_conv_halo_rows3(const ConvArgs& a, hipStream_t stream);
 // plain 3x3 / stride 1 / pad 1 conv on the halo kernel (conv_up_halo.hip, SP = 2): cout % 256 == 0, h % 8 == 0, w % 16 == 0;
-// ConvArgs::wpk_up_frag carries the pack_halo3_frag weights (looked up in the registry by conv_choose_form)
+// ConvArgs::wpk_up_frag carries the pack_halo3_frag weights (ConvW::halo under HaloOrder::Halo3_256)
 bool conv_halo3_supported(const ConvArgs& a);
 hipError_t launch_conv_halo3(const ConvArgs& a, hipStream_t stream);
 void pack_halo3_frag(const el16_t* wpk, int cout, int cin, el16_t* out);
 // 4x4 / stride 2 / pad 1 conv on the halo kernel (SP = 3, space-to-depth view): cout % 256 == 0, single source, output plane
-// tiles by 8x16; fragments (pack_halo_s2_frag) share the halo3 registry
+// tiles by 8x16; fragments: pack_halo_s2_frag (HaloOrder::S2)
 bool conv_halo_s2_supported(const ConvArgs& a);
 hipError_t launch_conv_halo_s2(const ConvArgs& a, hipStream_t stream);
 void pack_halo_s2_frag(const el16_t* wpk, int cout, int cin, el16_t* out);
@@ -169,7 +183,7 @@ bool conv_gn16_supported(const ConvArgs& a);
 int conv_gn16_slots(int h, int w);
 hipError_t launch_conv_gn16(const ConvArgs& a, hipStream_t stream);
 // enc0 on the fused stem (conv_enc0_stem.hip): persistent, weights resident in LDS, pixel fragments straight from global memory;
-// the fragments (pack_enc0_stem_frag) are registered in the halo3 registry under the composed weights' pointer
+// the fragments (pack_enc0_stem_frag) are the composed weights' ConvW::halo under HaloOrder::Enc0Stem
 bool conv_enc0_stem_supported(const ConvArgs& a);
 hipError_t conv_enc0_stem_init();
 hipError_t launch_conv_enc0_stem(const ConvArgs& a, const el16_t* wfrag, hipStream_t stream);
@@ -187,16 +201,3 @@ int conv_igemm2_gn_slots_bm128(int ho, int wo);  // ... of its 128-pixel tile fo
 bool conv_skinny_supported(const ConvArgs& a);
 hipError_t launch_conv_skinny(const ConvArgs& a, hipStream_t stream);
 
-// ================================================================================================ registries (conv_dispatch.hip)
-// device-pointer(wpk) -> device-pointer(fragment-ordered copy), one map per fragment order; filled when weights are uploaded, read by
-// conv_choose_form; conv_unregister_frag drops the pointer from all of them
-void conv_register_frag(const el16_t* wpk_dev, const el16_t* frag_dev);  // pack_conv_frag (igemm2, skinny)
-const el16_t* conv_lookup_frag(const el16_t* wpk_dev);
-// halo-kernel order: pack_halo3_frag (3x3, cout % 256 == 0), pack_halo3_frag64 (other 3x3), pack_halo_s2_frag, pack_enc0_stem_frag
-void conv_register_halo3_frag(const el16_t* wpk_dev, const el16_t* frag_dev);
-const el16_t* conv_lookup_halo3_frag(const el16_t* wpk_dev);
-// 3 x 3 convs with cout % 256 == 0 keep the 256-channel-block fragments (pack_halo3_frag) in the halo3 registry; their 64-channel-block
-// copy (pack_halo3_frag64, what conv_gn16_kernel streams) lives here
-void conv_register_frag64(const el16_t* wpk_dev, const el16_t* frag_dev);
-const el16_t* conv_lookup_frag64(const el16_t* wpk_dev);
-void conv_unregister_frag(const void* wpk_dev);

@@ -1,49 +1,22 @@
-// Which kernel form a conv takes (host only, no kernels): the fragment registries the choice consults, one admission predicate per
-// form, conv_choose_form, and the three launch entry points of conv.h, which choose and then call the chosen form's launcher.
+// Which kernel form a conv takes (host only, no kernels): one admission predicate per form, which reads the layer's ConvW for the
+// fragment order the form streams, conv_choose_form, and the three launch entry points of conv.h, which choose and then call the
+// chosen form's launcher.
 // Parameters INSIDE a form (split-K factors, tile-row counts, igemm2's SH3 switch) stay with that form's launcher.
 #include "conv.h"
 
 #include <algorithm>
 #include <initializer_list>
-#include <mutex>
-#include <unordered_map>
-
-// ------------------------------------------------------------------------------------------------ fragment registries
-namespace {
-enum FragKind { FRAG_IGEMM2, FRAG_HALO3, FRAG_64, FRAG_KINDS };
-std::mutex g_frag_mu;
-std::unordered_map<const void*, const el16_t*> g_frag[FRAG_KINDS];
-
-void frag_put(FragKind k, const void* wpk_dev, const el16_t* frag_dev) {
-    std::lock_guard<std::mutex> lk(g_frag_mu);
-    g_frag[k][wpk_dev] = frag_dev;
-}
-const el16_t* frag_get(FragKind k, const void* wpk_dev) {
-    std::lock_guard<std::mutex> lk(g_frag_mu);
-    auto it = g_frag[k].find(wpk_dev);
-    return it == g_frag[k].end() ? nullptr : it->second;
-}
-}  // namespace
-
-void conv_register_frag(const el16_t* wpk_dev, const el16_t* frag_dev) { frag_put(FRAG_IGEMM2, wpk_dev, frag_dev); }
-const el16_t* conv_lookup_frag(const el16_t* wpk_dev) { return frag_get(FRAG_IGEMM2, wpk_dev); }
-void conv_register_halo3_frag(const el16_t* wpk_dev, const el16_t* frag_dev) { frag_put(FRAG_HALO3, wpk_dev, frag_dev); }
-const el16_t* conv_lookup_halo3_frag(const el16_t* wpk_dev) { return frag_get(FRAG_HALO3, wpk_dev); }
-void conv_register_frag64(const el16_t* wpk_dev, const el16_t* frag_dev) { frag_put(FRAG_64, wpk_dev, frag_dev); }
-const el16_t* conv_lookup_frag64(const el16_t* wpk_dev) { return frag_get(FRAG_64, wpk_dev); }
-void conv_unregister_frag(const void* wpk_dev) {
-    std::lock_guard<std::mutex> lk(g_frag_mu);
-    for (auto& m : g_frag) m.erase(wpk_dev);
-}
 
 // ------------------------------------------------------------------------------------------------ admission rules, one per form
 // Each returns the form's fragment-ordered weights when the form takes the conv, null when it does not.  They read the switch table
-// and the registries and nothing else; the ladders below fix the ORDER in which they are asked.
+// and the ConvW they were given and nothing else; the ladders below fix the ORDER in which they are asked.
 namespace {
 
 long long form_rows(const ConvArgs& a) { return a.n_sel > 0 ? a.n_sel : a.n; }  // rows the form is chosen for (ConvArgs::n_sel)
+// the ConvArgs a form's *_supported predicate is asked with: the pointer it would be launched with in place
 ConvArgs with_up_frag(ConvArgs a, const el16_t* f) { a.wpk_up_frag = f; return a; }
-ConvArgs with_frag(ConvArgs a) { if (!a.wpk_frag) a.wpk_frag = conv_lookup_frag(a.wpk); return a; }  // pack_conv_frag order
+ConvArgs with_frag(ConvArgs a, const ConvW& w) { a.wpk_frag = w.frag; return a; }  // pack_conv_frag order
+const el16_t* halo_of(const ConvW& w, HaloOrder order) { return w.halo_order == order ? w.halo : nullptr; }
 bool halo3_on() { return dyf_form_int("DYF_HALO3", 1) != 0; }  // the 3x3 / s1 and the 4x4 / s2 form of the 256-channel-block halo kernel
 bool igemm2_on() { return dyf_form_int("DYF_IGEMM2", 1) != 0; }
 
@@ -59,9 +32,9 @@ bool up_halo_admits(const ConvArgs& a) {
 // per tap); DYF_HALO3=0 disables, DYF_HALO3_MIN_TILES sets the smallest launch (measured at NB = 80, enc3 with 320 tiles 115 -> 94 us;
 // round 4, with the rows forms: from 80 tiles on -- NS at 7 / 10 / 25 rows +3.4 / +5.7 / +2.5 % against the 256 of rounds 1-3, nothing
 // lost at 4 or 80 rows; 64 costs 2.4 % at 4 rows)
-const el16_t* halo3_admits(const ConvArgs& a) {
+const el16_t* halo3_admits(const ConvArgs& a, const ConvW& w) {
     if (!(!a.up2x && a.kh == 3 && a.kw == 3 && a.cout % 256 == 0 && a.out_f32 == nullptr && a.residual == nullptr) || !halo3_on()) return nullptr;
-    const ConvArgs b = with_up_frag(a, conv_lookup_halo3_frag(a.wpk));
+    const ConvArgs b = with_up_frag(a, halo_of(w, HaloOrder::Halo3_256));
     const long long tiles3 = (form_rows(a) * a.h * a.w / 128) * (a.cout / 256);
     return b.wpk_up_frag && tiles3 >= dyf_form_int("DYF_HALO3_MIN_TILES", 80) && conv_halo3_supported(b) ? b.wpk_up_frag : nullptr;
 }
@@ -72,25 +45,25 @@ const el16_t* halo3_admits(const ConvArgs& a) {
 // fused into this form a small launch also saves the three GroupNorm kernels behind the implicit-GEMM fallback -- OISST shapes at
 // 38 / 75 rows +5.8 / +3 % against the 256 of round 3).  (A residual is only added by the fused-GroupNorm epilogue: the plain ladder
 // asks with residual == nullptr.)
-const el16_t* halo5_admits(const ConvArgs& a) {
+const el16_t* halo5_admits(const ConvArgs& a, const ConvW& w) {
     if (!(!a.up2x && a.kh == 3 && a.kw == 3 && a.stride == 1 && a.cout % 64 == 0 && a.cout % 256 != 0 && a.out_f32 == nullptr)) return nullptr;
     if (dyf_form_int("DYF_HALO5", 1) == 0) return nullptr;
-    const ConvArgs b = with_up_frag(a, conv_lookup_halo3_frag(a.wpk));
+    const ConvArgs b = with_up_frag(a, halo_of(w, HaloOrder::Halo3_64));
     const long long ty = (a.h + 15) / 16, tx = (a.w + 31) / 32;
     const long long tiles5 = form_rows(a) * ty * tx * (a.cout / 64);
     const bool covers = 10ll * a.h * a.w >= 6ll * ty * 16 * tx * 32;
     return b.wpk_up_frag && covers && tiles5 >= dyf_form_int("DYF_HALO5_MIN_TILES", 64) && conv_halo5_supported(b) ? b.wpk_up_frag : nullptr;
 }
 
-const el16_t* enc0_stem_admits(const ConvArgs& a) {  // enc0 on the fused stem: HBM-bound, its own persistent kernel
-    return a.pix_pitch0 == 16 && conv_enc0_stem_supported(a) ? conv_lookup_halo3_frag(a.wpk) : nullptr;
+const el16_t* enc0_stem_admits(const ConvArgs& a, const ConvW& w) {  // enc0 on the fused stem: HBM-bound, its own persistent kernel
+    return a.pix_pitch0 == 16 && conv_enc0_stem_supported(a) ? halo_of(w, HaloOrder::Enc0Stem) : nullptr;
 }
 
-const el16_t* halo_s2_admits(const ConvArgs& a) {  // 4x4 / s2 convs: the halo kernel on the space-to-depth view
+const el16_t* halo_s2_admits(const ConvArgs& a, const ConvW& w) {  // 4x4 / s2 convs: the halo kernel on the space-to-depth view
     if (!(!a.up2x && a.kh == 4 && a.kw == 4 && a.stride == 2 && a.cout % 128 == 0 && a.c1 == 0 && a.out_f32 == nullptr &&
           a.residual == nullptr && a.pix_pitch0 == 0) || !halo3_on())
         return nullptr;
-    const ConvArgs b = with_up_frag(a, conv_lookup_halo3_frag(a.wpk));
+    const ConvArgs b = with_up_frag(a, halo_of(w, HaloOrder::S2));
     // (its own switch since round 5; DYF_HALO3_MIN_TILES still applies when unset)
     const long long min_tiles3 = dyf_form_int("DYF_HALO_S2_MIN_TILES", dyf_form_int("DYF_HALO3_MIN_TILES", 80));
     // cout % 256 == 0: 8 x 16 tiles x 256 channels; else 16 x 16 tiles x 128 channels
@@ -106,9 +79,9 @@ long long igemm2_tiles(const ConvArgs& a) {
 
 // 256 x 128 tiles pay off once they fill the chip (2 workgroups x 256 CUs); below that the 128 x 128 form's finer tiles win
 // (measured at NB = 50: dec2/enc2 with 400 tiles +9 %/+4 %, enc3 with 200 tiles -20 %); tests force the form on small problems
-const el16_t* igemm2_admits(const ConvArgs& a) {
+const el16_t* igemm2_admits(const ConvArgs& a, const ConvW& w) {
     if (!(!a.up2x && igemm2_on() && a.cout % 64 == 0)) return nullptr;
-    const ConvArgs b = with_frag(a);
+    const ConvArgs b = with_frag(a, w);
     return igemm2_tiles(a) >= dyf_form_int("DYF_IGEMM2_MIN_TILES", 384) && conv_igemm2_supported(b) ? b.wpk_frag : nullptr;
 }
 
@@ -116,10 +89,10 @@ const el16_t* igemm2_admits(const ConvArgs& a) {
 // launch_conv_igemm) run on conv_skinny_kernel -- K split over the four waves of a 32 x 32 tile, one launch (DYF_SKINNY=0 disables).
 // (64 tiles of 128 x 128: NS at 1 / 4 / 7 / 10 rows +10.6 / +4 / +2 / +1 %, nothing lost at 25 / 38; at 128 the 25- and 38-row
 // rollouts lose 2.5 %)
-const el16_t* skinny_admits(const ConvArgs& a) {
+const el16_t* skinny_admits(const ConvArgs& a, const ConvW& w) {
     if (!(!a.up2x && a.cout % 128 == 0) || dyf_form_int("DYF_SKINNY", 1) == 0) return nullptr;
     const long long tiles128 = ((form_rows(a) * a.ho * a.wo + 127) / 128) * (a.cout / 128);
-    const ConvArgs b = with_frag(a);
+    const ConvArgs b = with_frag(a, w);
     return tiles128 <= dyf_form_int("DYF_SKINNY_MAX_TILES", 64) && conv_skinny_supported(b) ? b.wpk_frag : nullptr;
 }
 
@@ -132,11 +105,11 @@ bool gn_slots_fit(int slots, int max_slots) { return slots <= GN_FUSE_MAX_SLOTS 
 // DYF_GN16_ANY_PLANE=1: the tests' tiny planes) and the launch has DYF_GN16_MIN_TILES of them.
 // c256 -- the 256-channel level on SMALL planes (15 x 15 at OISST: one tile per sample): four 64-channel column blocks per sample
 // instead of conv_igemm2_kernel<2, true>'s 256-pixel x 128-channel tiles -- half the K chain per workgroup, more than twice the
-// workgroups (400 against 176 at 100 rows).  Its fragments are the frag64 registry's, planes above DYF_GN16_C256_MAX_PLANE pixels are
+// workgroups (400 against 176 at 100 rows).  Its fragments are ConvW::frag64, planes above DYF_GN16_C256_MAX_PLANE pixels are
 // left to igemm2, DYF_GN16_C256=0: off
-const el16_t* gn16_admits(const ConvArgs& a, bool c256) {
+const el16_t* gn16_admits(const ConvArgs& a, const ConvW& w, bool c256) {
     if (dyf_form_int("DYF_GN16", 1) == 0 || (c256 && dyf_form_int("DYF_GN16_C256", 1) == 0)) return nullptr;
-    const ConvArgs b = with_up_frag(a, c256 ? conv_lookup_frag64(a.wpk) : conv_lookup_halo3_frag(a.wpk));
+    const ConvArgs b = with_up_frag(a, c256 ? w.frag64 : halo_of(w, HaloOrder::Halo3_64));
     const int slots16 = conv_gn16_slots(a.h, a.w);
     const long long tiles16 = form_rows(a) * slots16 * (a.cout / 64);
     const bool covers16 = 10ll * a.h * a.w >= 6ll * slots16 * 256 || dyf_form_int("DYF_GN16_ANY_PLANE", 0) != 0;
@@ -150,10 +123,10 @@ const el16_t* gn16_admits(const ConvArgs& a, bool c256) {
 // from 32 tiles on.  Measured at the end of round 4, OISST shapes, fields/s with the threshold at 256 (the first choice) / 64 / 16:
 // 300 rows 4 154 / 4 165 / 4 181, 150 rows 3 568 / 3 626 / 3 631, 75 rows 2 360 / 2 494 / 2 479, 38 rows 1 548 / 1 619 / 1 654, 16 rows
 // 811 / 811 / 791 (32: 818) -- DYF_GN_FUSE_MIN_TILES overrides, DYF_IGEMM2_MIN_TILES (tests) wins
-const el16_t* igemm2_fused_admits(const ConvArgs& a, ConvChoice* c) {
+const el16_t* igemm2_fused_admits(const ConvArgs& a, const ConvW& w, ConvChoice* c) {
     const GnFuse& G = a.gnf;
     if (!(igemm2_on() && a.cout % 128 == 0)) return nullptr;
-    const ConvArgs b = with_frag(a);
+    const ConvArgs b = with_frag(a, w);
     if (!conv_igemm2_supported(b)) return nullptr;
     const long long tiles2 = igemm2_tiles(a);
     const long long min_tiles = dyf_form_int("DYF_IGEMM2_MIN_TILES", dyf_form_int("DYF_GN_FUSE_MIN_TILES", 32));
@@ -178,9 +151,9 @@ const el16_t* igemm2_fused_admits(const ConvArgs& a, ConvChoice* c) {
 }
 
 // ------------------------------------------------------------------------------------------------ the two ladders
-ConvChoice choose_plain(const ConvArgs& a, bool mfma, bool stats) {
+ConvChoice choose_plain(const ConvArgs& a, const ConvW& w, bool mfma, bool stats) {
     const ConvChoice invalid{ConvForm::Invalid, nullptr, 0, 0};
-    const el16_t* const h5 = mfma && a.residual == nullptr ? halo5_admits(a) : nullptr;
+    const el16_t* const h5 = mfma && a.residual == nullptr ? halo5_admits(a, w) : nullptr;
     // a fused nearest upsample exists in ONE form: refuse rather than read a low-resolution tensor as the full-size one
     if (a.up_nearest && !(h5 && a.h % 2 == 0 && a.w % 2 == 0 && a.c1 == 0)) return invalid;
     // the direct kernel has no fused-upsample form: caller materialises
@@ -188,21 +161,21 @@ ConvChoice choose_plain(const ConvArgs& a, bool mfma, bool stats) {
     // sparse-column form: only the halo kernel writes the compact output tensor
     if (a.up2x && a.up_cols) return conv_up_halo_supported(a) ? ConvChoice{ConvForm::UpHalo, nullptr, 0, 0} : invalid;
     if (up_halo_admits(a)) return {ConvForm::UpHalo, nullptr, 0, 0};
-    if (const el16_t* f = halo3_admits(a))  // its rows form where that serves the plane
+    if (const el16_t* f = halo3_admits(a, w))  // its rows form where that serves the plane
         return {dyf_form_int("DYF_HALO_ROWS", 1) != 0 && conv_halo_rows3_supported(a) ? ConvForm::Rows3 : ConvForm::Halo3, f, 0, 0};
     if (h5)  // with the statistics of the raw conv output where the caller asked for them
         return {ConvForm::Halo5, h5, stats && a.act == ACT_NONE && a.drop.mode == 0 ? conv_halo5_gn_slots(a.h, a.w) : 0, 0};
-    if (const el16_t* f = enc0_stem_admits(a)) return {ConvForm::Enc0Stem, f, 0, 0};
-    if (const el16_t* f = halo_s2_admits(a)) return {ConvForm::HaloS2, f, 0, 0};
-    if (const el16_t* f = igemm2_admits(a)) return {ConvForm::Igemm2, f, 0, 0};
-    if (const el16_t* f = skinny_admits(a)) return {ConvForm::Skinny, f, 0, 0};
+    if (const el16_t* f = enc0_stem_admits(a, w)) return {ConvForm::Enc0Stem, f, 0, 0};
+    if (const el16_t* f = halo_s2_admits(a, w)) return {ConvForm::HaloS2, f, 0, 0};
+    if (const el16_t* f = igemm2_admits(a, w)) return {ConvForm::Igemm2, f, 0, 0};
+    if (const el16_t* f = skinny_admits(a, w)) return {ConvForm::Skinny, f, 0, 0};
     return {a.cout % 128 == 0 ? ConvForm::Igemm128 : ConvForm::Igemm256x64, nullptr, 0, 0};
 }
 
 // The fused forms are used exactly where the un-fused launch would have taken conv_up_halo_kernel<5> / conv_igemm2_kernel<2> (same
 // tile rules), with conv_gn16_kernel in front of them.  (DYF_GN_FUSED=0 is read per engine, dyf_engine_create: the caller then
 // never asks)
-ConvChoice choose_gn_fused(const ConvArgs& a, bool mfma) {
+ConvChoice choose_gn_fused(const ConvArgs& a, const ConvW& w, bool mfma) {
     ConvChoice c{ConvForm::None, nullptr, 0, 0};
     const GnFuse& G = a.gnf;
     if (!mfma || G.gran == nullptr || G.epoch == nullptr || a.act != ACT_SILU || a.drop.mode == 2 || a.out_el16 == nullptr ||
@@ -212,11 +185,11 @@ ConvChoice choose_gn_fused(const ConvArgs& a, bool mfma) {
     if (cpg < 8 || cpg % 8 != 0 || 64 % cpg != 0 || cpg * G.groups != a.cout) return c;  // a group lies inside one 64-channel block
     const bool conv3 = a.kh == 3 && a.kw == 3 && a.stride == 1 && a.pad == 1;
     if (conv3 && a.cout % 64 == 0) {
-        if (const el16_t* f = gn16_admits(a, a.cout % 256 == 0)) return {ConvForm::Gn16, f, conv_gn16_slots(a.h, a.w), 0};
+        if (const el16_t* f = gn16_admits(a, w, a.cout % 256 == 0)) return {ConvForm::Gn16, f, conv_gn16_slots(a.h, a.w), 0};
         const int slots = conv_halo5_gn_slots(a.h, a.w);  // 16 x 32 tiles: conv_up_halo_kernel<5, 2>
-        if (const el16_t* f = gn_slots_fit(slots, G.max_slots) ? halo5_admits(a) : nullptr) return {ConvForm::Halo5, f, slots, 0};
+        if (const el16_t* f = gn_slots_fit(slots, G.max_slots) ? halo5_admits(a, w) : nullptr) return {ConvForm::Halo5, f, slots, 0};
     }
-    if ((c.frag = igemm2_fused_admits(a, &c))) c.form = ConvForm::Igemm2;
+    if ((c.frag = igemm2_fused_admits(a, w, &c))) c.form = ConvForm::Igemm2;
     return c;
 }
 
@@ -243,13 +216,13 @@ hipError_t launch_chosen(ConvArgs& a, const ConvChoice& c, hipStream_t stream) {
 
 }  // namespace
 
-ConvChoice conv_choose_form(const ConvArgs& a, int path, ConvWant want) {
+ConvChoice conv_choose_form(const ConvArgs& a, const ConvW& w, int path, ConvWant want) {
     const bool mfma = path == 1 && conv_mfma_supported(a);
-    return want == ConvWant::GnFused ? choose_gn_fused(a, mfma) : choose_plain(a, mfma, want == ConvWant::Stats);
+    return want == ConvWant::GnFused ? choose_gn_fused(a, w, mfma) : choose_plain(a, w, mfma, want == ConvWant::Stats);
 }
 
-bool conv_plain3x3_takes_halo5(const ConvArgs& a) {
-    return a.gn_part == nullptr && a.gnf.gran == nullptr && conv_choose_form(a, 1, ConvWant::Plain).form == ConvForm::Halo5;
+bool conv_plain3x3_takes_halo5(const ConvArgs& a, const ConvW& w) {
+    return a.gn_part == nullptr && a.gnf.gran == nullptr && conv_choose_form(a, w, 1, ConvWant::Plain).form == ConvForm::Halo5;
 }
 
 int conv_gn_fused_max_slots(int h, int w) {
@@ -259,16 +232,19 @@ int conv_gn_fused_max_slots(int h, int w) {
     return best;
 }
 
-hipError_t launch_conv(const ConvArgs& a, int path, hipStream_t stream) { return launch_conv_stats(a, path, stream, nullptr); }
+hipError_t launch_conv(const ConvArgs& a, const ConvW& w, int path, hipStream_t stream) {
+    return launch_conv_stats(a, w, path, stream, nullptr);
+}
 
 // (statistics are only produced when the caller can learn whether they were: gn_slots != null)
-hipError_t launch_conv_stats(const ConvArgs& a_in, int path, hipStream_t stream, int* gn_slots) {
+hipError_t launch_conv_stats(const ConvArgs& a_in, const ConvW& w, int path, hipStream_t stream, int* gn_slots) {
     if (gn_slots) *gn_slots = 0;
     ConvArgs a = a_in;
+    a.wpk = w.wpk;
     a.gn_part = nullptr;  // only a form that produces statistics sees the buffer
     a.gn_slots = 0;
     const bool stats = gn_slots != nullptr && a_in.gn_part != nullptr;
-    const ConvChoice c = conv_choose_form(a, path, stats ? ConvWant::Stats : ConvWant::Plain);
+    const ConvChoice c = conv_choose_form(a, w, path, stats ? ConvWant::Stats : ConvWant::Plain);
     if (c.gn_slots > 0) {
         a.gn_part = a_in.gn_part;
         a.gn_slots = c.gn_slots;
@@ -277,11 +253,12 @@ hipError_t launch_conv_stats(const ConvArgs& a_in, int path, hipStream_t stream,
     return launch_chosen(a, c, stream);
 }
 
-hipError_t launch_conv_gn_fused(const ConvArgs& a_in, int path, hipStream_t stream, bool* fused) {
+hipError_t launch_conv_gn_fused(const ConvArgs& a_in, const ConvW& w, int path, hipStream_t stream, bool* fused) {
     ConvArgs a = a_in;
+    a.wpk = w.wpk;
     a.gn_part = nullptr;
     a.gn_slots = 0;
-    const ConvChoice c = conv_choose_form(a, path, ConvWant::GnFused);
+    const ConvChoice c = conv_choose_form(a, w, path, ConvWant::GnFused);
     *fused = c.form != ConvForm::None;
     a.gnf.slots = c.gn_slots;
     if (c.bm) a.gnf.bm = c.bm;

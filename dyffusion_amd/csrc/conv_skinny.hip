@@ -126,7 +126,7 @@ __global__ __launch_bounds__(NW * 64) void conv_skinny_kernel_t(ConvArgs a, int 
 }
 
 // shapes the kernel takes: stride == kernel (1 or 2), pad 0, one source, 128-channel column blocks (the fragment layout of
-// pack_conv_frag), fragment copy registered
+// pack_conv_frag), fragment copy present (ConvW::frag)
 bool conv_skinny_supported(const ConvArgs& a) {
     if (a.up2x || a.wpk_frag == nullptr || a.pix_pitch0 != 0 || (a.c1 != 0 && a.src1 == nullptr)) return false;
     if (a.kh < 1 || a.kw < 1 || a.kh * a.kw > 16 || a.stride < 1 || a.pad < 0) return false;

@@ -128,18 +128,19 @@ DropSpec make_input_drop(const dyf_engine* e, const Net& n, const FwdOpts& o) {
     return d;
 }
 
-dyf_status run_conv(dyf_engine* e, const ConvArgs& a, hipStream_t st) {
-    HIP_TRY(e, launch_conv(a, conv_path(e, a), st));
+dyf_status run_conv(dyf_engine* e, const ConvArgs& a, const ConvW& w, hipStream_t st) {
+    HIP_TRY(e, launch_conv(a, w, conv_path(e, a), st));
     return DYF_OK;
 }
 
 // enc0 on the fused stem: a 4(kh) x 1 conv over "64-channel" pixels that are really 4 adjacent 16-channel pixels of the
 // zero-bordered stem16 tensor (stride 2, physical padding instead of pad=1).
-void fused_enc0_args(const dyf_engine* e, const Net& n, ConvArgs& a) {
+// Returns the composed weights the conv then runs with.
+const ConvW* fused_enc0_args(const dyf_engine* e, const Net& n, ConvArgs& a) {
     a.src0 = e->ws.stem16; a.c0 = 64; a.pix_pitch0 = 16;
     a.h = n.uh + 2; a.w = n.uw + 2;
     a.kh = 4; a.kw = 1; a.stride = 2; a.pad = 0;
-    a.wpk = n.enc0_fused_w;
+    return &n.enc0_fused_w;
 }
 
 // Fused x2-upsample conv pays ~7 extra K taps on every tile that touches an image border; on small planes most tiles
@@ -153,7 +154,6 @@ ConvArgs block_conv_args(const dyf_engine* e, const Net& n, const UBlock& b, int
     ConvArgs a{};
     a.n = nb; a.h = b.in_h; a.w = b.in_w; a.ho = b.out_h; a.wo = b.out_w;
     a.kh = b.k; a.kw = b.k; a.stride = b.stride; a.pad = b.pad; a.cout = b.cout;
-    a.wpk = b.wpk;
     a.act = b.act;
     a.zero_page = e->ws.zero_page;
     a.splitk_ws = e->ws.splitk; a.splitk_cap = DYF_SPLITK_FLOATS;
@@ -208,20 +208,21 @@ dyf_status net_forward(dyf_engine* e, int which, const Source* srcs, int nsrc, i
         const UBlock& b = n.blk[i];
         ConvArgs a = block_conv_args(e, n, b, nb);
         a.src0 = x; a.c0 = b.cin; a.src1 = nullptr; a.c1 = 0;
-        if (i == 0 && fused_stem) fused_enc0_args(e, n, a);
+        const ConvW* w = &b.wpk;
+        if (i == 0 && fused_stem) w = fused_enc0_args(e, n, a);
         if (!b.gn) {
             a.coef_a = o.coef_a + b.film_off; a.coef_c = o.coef_c + b.film_off; a.coef_stride = o.coef_stride;
             a.coef_div = o.coef_div;
             a.drop = make_drop(e, n, o, i);
             a.out_el16 = ws.enc[i];
-            dyf_status s = run_conv(e, a, st);
+            dyf_status s = run_conv(e, a, *w, st);
             if (s != DYF_OK) return s;
         } else {
             a.coef_a = b.static_a; a.coef_c = b.static_c; a.coef_stride = 0;
             a.act = ACT_NONE;
             a.drop = DropSpec{};
             a.out_f32 = ws.enc5_raw;
-            dyf_status s = run_conv(e, a, st);
+            dyf_status s = run_conv(e, a, *w, st);
             if (s != DYF_OK) return s;
             GroupNormArgs g{};
             g.x = ws.enc5_raw; g.n = nb; g.hw = b.out_h * b.out_w; g.c = b.cout; g.groups = 8;
@@ -271,7 +272,7 @@ dyf_status net_forward(dyf_engine* e, int which, const Source* srcs, int nsrc, i
                               (size_t)nb * lh * lw * b.cout * sizeof(float) <= (size_t)nb * b.in_h * b.in_w * b.cin * sizeof(el16_t);
         if (use_fused_up(e, b, f)) {
             if (prof) HIP_TRY(e, hipEventRecord(pe0, st));
-            HIP_TRY(e, launch_conv(f, 1, st));
+            HIP_TRY(e, launch_conv(f, b.wpk, 1, st));
             if (prof) HIP_TRY(e, hipEventRecord(pe1, st));
         } else if (commuted) {
             ConvArgs lo = a;
@@ -281,7 +282,7 @@ dyf_status net_forward(dyf_engine* e, int which, const Source* srcs, int nsrc, i
             lo.act = ACT_NONE; lo.drop = DropSpec{};
             lo.out_el16 = nullptr; lo.out_f32 = (float*)ws.up;  // (the materialised-upsample scratch is free in this form)
             if (prof) HIP_TRY(e, hipEventRecord(pe0, st));
-            dyf_status s = run_conv(e, lo, st);
+            dyf_status s = run_conv(e, lo, b.wpk, st);
             if (s != DYF_OK) return s;
             Up2xEpiArgs u{};
             u.lo = (const float*)ws.up; u.n = nb; u.h = lh; u.w = lw; u.c = b.cout;
@@ -295,7 +296,7 @@ dyf_status net_forward(dyf_engine* e, int which, const Source* srcs, int nsrc, i
             HIP_TRY(e, launch_up2x(u, st));
             a.src0 = ws.up; a.c0 = b.cin; a.src1 = nullptr; a.c1 = 0;
             if (prof) HIP_TRY(e, hipEventRecord(pe0, st));
-            dyf_status s = run_conv(e, a, st);
+            dyf_status s = run_conv(e, a, b.wpk, st);
             if (s != DYF_OK) return s;
             if (prof) HIP_TRY(e, hipEventRecord(pe1, st));
         }
@@ -706,14 +707,8 @@ static dyf_status load_weights_one(dyf_engine* e, int32_t which, int32_t n_tenso
         blk_off[i] = b.film_off;
         blk_cout[i] = b.cout;
         for (int c = 0; c < b.cout; ++c) blk_of[b.film_off + c] = i;
-        // pack [cout][cin][kh][kw] fp32 -> [cout][tap][cin] bf16 (K-contiguous rows for the implicit GEMM)
         const int taps = b.k * b.k;
-        std::vector<el16_t> pk((size_t)b.cout * taps * b.cin);
-        for (int co = 0; co < b.cout; ++co)
-            for (int ci = 0; ci < b.cin; ++ci)
-                for (int t = 0; t < taps; ++t)
-                    pk[((size_t)co * taps + t) * b.cin + ci] = f32_to_el16(cw->data[((size_t)co * b.cin + ci) * taps + t]);
-        { dyf_status _s = upload_conv_weights(e, &b.wpk, pk, b.cout, taps, b.cin); if (_s != DYF_OK) return _s; }
+        { dyf_status _s = upload_conv_weights(e, &b.wpk, pack_conv(cw->data, b.cout, b.cin, taps), b.cout, taps, b.cin); if (_s != DYF_OK) return _s; }
         if (i == 0 && b.k == 4 && n.cin_total + 1 <= 16 && b.cout % 64 == 0 && n.uh % 2 == 0 && n.uw % 2 == 0) {
             // compose_stem_enc0: W'[co][kh][kw][c] = sum_d Wenc0[co][d][kh][kw] * Winit[d][c]; channel cin_total carries
             // init_conv's bias (its input is the 1-inside-the-image indicator); channels up to 16 are zero
@@ -731,14 +726,7 @@ static dyf_status load_weights_one(dyf_engine* e, int32_t which, int32_t n_tenso
                             }
                         fw[((size_t)co * 16 + t) * 16 + c] = f32_to_el16((float)v);
                     }
-            { dyf_status _s = upload_conv_weights(e, &n.enc0_fused_w, fw, b.cout, 4, 64); if (_s != DYF_OK) return _s; }
-            if (b.cout == 64 || b.cout == 128) {  // fragments of the persistent enc0 kernel (conv_enc0_stem.hip)
-                std::vector<el16_t> pf(fw.size());
-                pack_enc0_stem_frag(fw.data(), b.cout, pf.data());
-                el16_t* frag = nullptr;
-                UP(frag, pf);
-                conv_register_halo3_frag(n.enc0_fused_w, frag);
-            }
+            { dyf_status _s = upload_conv_weights(e, &n.enc0_fused_w, fw, b.cout, 4, 64, /*enc0_stem=*/true); if (_s != DYF_OK) return _s; }
             n.stem_fused = true;
         }
         if (b.transposed && b.k == 3) {
@@ -1691,7 +1679,8 @@ dyf_status dyf_time_conv_layer(dyf_engine* e, int32_t which, int32_t layer, int3
     // same operands as in net_forward: whatever the last forward left in the workspace (realistic activations)
     a.src0 = b.transposed ? e->ws.up : (layer == 0 ? e->ws.stem : e->ws.enc[layer - 1]);
     a.c0 = b.cin;
-    if (layer == 0 && n.stem_fused && e->cfg.enable_mfma && e->fuse_stem && n.cfg.input_dropout == 0.0f) fused_enc0_args(e, n, a);
+    const ConvW* w = &b.wpk;
+    if (layer == 0 && n.stem_fused && e->cfg.enable_mfma && e->fuse_stem && n.cfg.input_dropout == 0.0f) w = fused_enc0_args(e, n, a);
     if (b.transposed && layer > 6) {  // fused x2-upsample form when net_forward uses it
         ConvArgs f = a;
         const UBlock& skipb = n.blk[11 - layer];
@@ -1713,12 +1702,12 @@ dyf_status dyf_time_conv_layer(dyf_engine* e, int32_t which, int32_t layer, int3
     HIP_TRY(e, hipEventCreate(&ev0));
     HIP_TRY(e, hipEventCreate(&ev1));
     for (int i = 0; i < 2; ++i) {
-        dyf_status s = run_conv(e, a, st);
+        dyf_status s = run_conv(e, a, *w, st);
         if (s != DYF_OK) return s;
     }
     HIP_TRY(e, hipEventRecord(ev0, st));
     for (int i = 0; i < iters; ++i) {
-        dyf_status s = run_conv(e, a, st);
+        dyf_status s = run_conv(e, a, *w, st);
         if (s != DYF_OK) return s;
     }
     HIP_TRY(e, hipEventRecord(ev1, st));
@@ -1949,49 +1938,25 @@ dyf_status dyf_op_conv2d_ex(dyf_engine* e, const uint16_t* x_dev, const float* w
         return fail(e, DYF_ERR_UNSUPPORTED, "tensor too large for the kernels' 32-bit element indices");
     HIP_TRY(e, hipSetDevice(e->cfg.device));
     hipStream_t st = (hipStream_t)stream;
-    const int taps = kh * kw;
-    std::vector<el16_t> pk((size_t)cout * taps * cin);
-    for (int co = 0; co < cout; ++co)
-        for (int ci = 0; ci < cin; ++ci)
-            for (int t = 0; t < taps; ++t)
-                pk[((size_t)co * taps + t) * cin + ci] = f32_to_el16(w_host[((size_t)co * cin + ci) * taps + t]);
-    el16_t* wdev = nullptr;
+    // the engine's own upload: every fragment order a layer of this shape would get, released with `tmp` below
+    std::vector<void*> tmp;
+    AllocScope scope(e, &tmp);
+    ConvW wts;
+    { dyf_status us = upload_conv_weights(e, &wts, pack_conv(w_host, cout, cin, kh * kw), cout, kh * kw, cin); if (us != DYF_OK) return us; }
     float *ones = nullptr, *zeros = nullptr;
-    const bool chan64 = cout % 64 == 0 && c0 % 64 == 0 && x.c1 % 64 == 0;
-    const bool frag = chan64 && taps <= 32;
-    HIP_TRY(e, hipMalloc((void**)&wdev, 2 * pk.size() * sizeof(el16_t)));
-    HIP_TRY(e, hipMemcpy(wdev, pk.data(), pk.size() * sizeof(el16_t), hipMemcpyHostToDevice));
-    if (frag) {
-        std::vector<el16_t> pf(pk.size());
-        pack_conv_frag(pk.data(), cout, taps, cin, pf.data());
-        HIP_TRY(e, hipMemcpy(wdev + pk.size(), pf.data(), pf.size() * sizeof(el16_t), hipMemcpyHostToDevice));
-    }
     ConvArgs a{};
     a.src0 = x_dev; a.c0 = c0; a.src1 = x.x1_dev; a.c1 = x.c1; a.n = n; a.h = h; a.w = w;
     a.ho = (int)ho; a.wo = (int)wo;
-    a.kh = kh; a.kw = kw; a.stride = stride; a.pad = pad; a.cout = cout; a.wpk = wdev;
-    a.wpk_frag = frag ? wdev + pk.size() : nullptr;
-    el16_t* h3dev = nullptr;  // halo form of plain 3x3 convs (looked up through the registry like the engine's own weights)
-    if (((taps == 9 && cout % 64 == 0) || (kh == 4 && kw == 4 && cout % 128 == 0)) && chan64) {
-        std::vector<el16_t> pf((size_t)cout * 16 * cin * (taps == 9 ? 1 : 4));
-        if (taps == 9 && cout % 256 == 0) pack_halo3_frag(pk.data(), cout, cin, pf.data());
-        else if (taps == 9) pack_halo3_frag64(pk.data(), cout, cin, pf.data());
-        else pack_halo_s2_frag(pk.data(), cout, cin, pf.data());
-        HIP_TRY(e, hipMalloc((void**)&h3dev, pf.size() * sizeof(el16_t)));
-        HIP_TRY(e, hipMemcpy(h3dev, pf.data(), pf.size() * sizeof(el16_t), hipMemcpyHostToDevice));
-        conv_register_halo3_frag(wdev, h3dev);
-    }
+    a.kh = kh; a.kw = kw; a.stride = stride; a.pad = pad; a.cout = cout;
     a.act = act; a.out_el16 = y_dev; a.out_f32 = x.y_f32_dev; a.residual = x.residual_dev; a.zero_page = e->ws.zero_page;
     a.coef_div = x.coef_div; a.n_sel = x.n_sel;
     a.splitk_ws = e->ws.splitk; a.splitk_cap = e->ws.splitk ? DYF_SPLITK_FLOATS : 0;  // the split-K forms, as in the engine's own launches
     if (scale_dev && shift_dev) {
         a.coef_a = scale_dev; a.coef_c = shift_dev; a.coef_stride = cout;
     } else {
-        std::vector<float> o1(cout, 1.0f), z0(cout, 0.0f);
-        HIP_TRY(e, hipMalloc((void**)&ones, cout * sizeof(float)));
-        HIP_TRY(e, hipMalloc((void**)&zeros, cout * sizeof(float)));
-        HIP_TRY(e, hipMemcpy(ones, o1.data(), cout * sizeof(float), hipMemcpyHostToDevice));
-        HIP_TRY(e, hipMemcpy(zeros, z0.data(), cout * sizeof(float), hipMemcpyHostToDevice));
+        dyf_status us = dev_upload(e, &ones, std::vector<float>(cout, 1.0f));
+        if (us == DYF_OK) us = dev_upload(e, &zeros, std::vector<float>(cout, 0.0f));
+        if (us != DYF_OK) return us;
         a.coef_a = ones; a.coef_c = zeros; a.coef_stride = 0;
     }
     if (x.drop_mode != 0) {
@@ -2019,17 +1984,11 @@ dyf_status dyf_op_conv2d_ex(dyf_engine* e, const uint16_t* x_dev, const float* w
     if (path == 1 && !conv_mfma_supported(geom)) {
         rs = fail(e, DYF_ERR_UNSUPPORTED, "MFMA path needs cin % 64 == 0 and cout % 64 == 0");
     } else {
-        hipError_t le = launch_conv(a, path, st);
+        hipError_t le = launch_conv(a, wts, path, st);
         if (le == hipSuccess) le = hipStreamSynchronize(st);
         if (le != hipSuccess) rs = fail(e, DYF_ERR_HIP, std::string("conv launch: ") + hipGetErrorString(le));
     }
-    if (h3dev) {
-        conv_unregister_frag(wdev);
-        (void)hipFree(h3dev);
-    }
-    (void)hipFree(wdev);
-    if (ones) (void)hipFree(ones);
-    if (zeros) (void)hipFree(zeros);
+    release_allocs(tmp);
     return rs;
 }
 
@@ -2053,7 +2012,7 @@ dyf_status dyf_op_upconv2d(dyf_engine* e, const uint16_t* x_dev, const float* w_
     }
     ConvArgs a{};
     a.src0 = x_dev; a.c0 = cin; a.n = n; a.h = h; a.w = w; a.ho = 2 * h; a.wo = 2 * w;
-    a.kh = 3; a.kw = 3; a.stride = 1; a.pad = 1; a.cout = cout; a.wpk = wdev; a.wpk_up = wdev; a.up2x = 1;
+    a.kh = 3; a.kw = 3; a.stride = 1; a.pad = 1; a.cout = cout; a.wpk_up = wdev; a.up2x = 1;
     a.wpk_up_frag = frag ? wdev + pu.size() : nullptr;
     a.act = act; a.out_el16 = y_dev;
     a.splitk_ws = e->ws.splitk; a.splitk_cap = e->ws.splitk ? DYF_SPLITK_FLOATS : 0;
@@ -2074,7 +2033,7 @@ dyf_status dyf_op_upconv2d(dyf_engine* e, const uint16_t* x_dev, const float* w_
     if (!conv_mfma_supported(a)) {
         rs = fail(e, DYF_ERR_UNSUPPORTED, "fused upsample conv needs cin % 64 == 0, cout % 64 == 0, w % 16 == 0, h % 8/16 == 0");
     } else {
-        hipError_t le = launch_conv(a, 1, st);
+        hipError_t le = launch_conv(a, ConvW{wdev}, 1, st);
         if (le == hipSuccess) le = hipStreamSynchronize(st);
         if (le != hipSuccess) rs = fail(e, DYF_ERR_HIP, std::string("upconv launch: ") + hipGetErrorString(le));
     }

@@ -31,7 +31,7 @@ struct UBlock {              // one UNetBlock (unet_simple.py:13-82)
     int film_off = 0;        // offset of this block's channels in the flattened coefficient table
     int in_h = 0, in_w = 0;  // conv input size (after the x2 upsample for decoder blocks)
     int out_h = 0, out_w = 0;
-    el16_t* wpk = nullptr;   // device [cout][k*k][cin]
+    ConvW wpk;               // device [cout][k*k][cin] and its fragment-ordered copies
     el16_t* wpk_up = nullptr;  // decoder 3x3 blocks: phase-decomposed weights of the fused x2-upsample conv
     el16_t* wpk_up_frag = nullptr;  // ... in MFMA fragment order (halo kernel)
     // last decoder block: column lists of the outputs the readout actually reads (plan_up_sparse_columns), or null
@@ -63,7 +63,7 @@ struct Net {
     el16_t* ro_wfrag = nullptr;  // readout weights as MFMA fragments (dim 64, <= 4 output channels)
     uint4 *ro_row_tab = nullptr, *ro_col_tab = nullptr;  // tap tables of the readout (launch_readout_tables), with ro_wfrag
     bool ro_tab_sparse = false;  // ... built for the compact (sparse-column) layout of the last decoder block's output
-    el16_t* enc0_fused_w = nullptr;  // [2dim][4][64]: enc0's 4x4 conv composed with init_conv (+ bias channel)
+    ConvW enc0_fused_w;  // [2dim][4][64]: enc0's 4x4 conv composed with init_conv (+ bias channel), with its stem fragments
     bool stem_fused = false;
     double flops_per_sample = 0.0;
     int n_drop_sites = 12;   // dropout sites with p > 0 per forward (mask-injection cursor); 12 UNetBlocks for unet_simple
@@ -256,12 +256,9 @@ struct AllocScope {
     ~AllocScope() { e->alloc_sink = prev; }
 };
 
-// free every allocation of `list` (and their registered fragment copies); the device must be idle
+// free every allocation of `list`; the device must be idle
 inline void release_allocs(std::vector<void*>& list) {
-    for (void* p : list) {
-        conv_unregister_frag(p);
-        (void)hipFree(p);
-    }
+    for (void* p : list) (void)hipFree(p);
     list.clear();
 }
 
@@ -273,50 +270,59 @@ dyf_status dev_upload(dyf_engine* e, T** out, const std::vector<T>& host) {
     return DYF_OK;
 }
 
-// packed conv weights [cout][taps][cin] bf16 -> device; layers the second implicit-GEMM form can run also get their
-// fragment-ordered copy, registered under the primary pointer (conv_choose_form looks it up)
-inline dyf_status upload_conv_weights(dyf_engine* e, el16_t** out, const std::vector<el16_t>& pk, int cout, int taps, int cin) {
-    dyf_status st = dev_upload(e, out, pk);
-    if (st != DYF_OK) return st;
-    if (cout % 64 == 0 && cin % 64 == 0 && taps <= 32 && (size_t)cout * taps * cin == pk.size()) {
-        std::vector<el16_t> pf(pk.size());
+// conv weights [cout][cin][kh][kw] fp32 -> [cout][tap][cin] 16 bit (K-contiguous rows for the implicit GEMM)
+inline std::vector<el16_t> pack_conv(const float* w, int cout, int cin, int taps) {
+    std::vector<el16_t> pk((size_t)cout * taps * cin);
+    for (int co = 0; co < cout; ++co)
+        for (int ci = 0; ci < cin; ++ci)
+            for (int t = 0; t < taps; ++t) pk[((size_t)co * taps + t) * cin + ci] = f32_to_el16(w[((size_t)co * cin + ci) * taps + t]);
+    return pk;
+}
+
+// packed conv weights [cout][taps][cin] -> device, with every fragment-ordered copy a kernel form of this shape streams: the ONE
+// place that decides which orders a conv gets (the admission rules of conv_dispatch.hip check the order they are handed).
+// enc0_stem: pk is enc0's 4x4 conv composed with init_conv, [cout][4][64]
+inline dyf_status upload_conv_weights(dyf_engine* e, ConvW* out, const std::vector<el16_t>& pk, int cout, int taps, int cin,
+                                      bool enc0_stem = false) {
+    *out = ConvW{};
+    auto up = [&](const el16_t** dst, const std::vector<el16_t>& host) {
+        el16_t* p = nullptr;
+        const dyf_status st = dev_upload(e, &p, host);
+        *dst = p;
+        return st;
+    };
+    dyf_status st = up(&out->wpk, pk);
+    if (st != DYF_OK || cout % 64 != 0 || cin % 64 != 0 || (size_t)cout * taps * cin != pk.size()) return st;
+    std::vector<el16_t> pf;
+    if (taps <= 32) {  // second implicit-GEMM form, skinny
+        pf.assign(pk.size(), el16_t{});
         pack_conv_frag(pk.data(), cout, taps, cin, pf.data());
-        el16_t* frag = nullptr;
-        st = dev_upload(e, &frag, pf);
-        if (st != DYF_OK) return st;
-        conv_register_frag(*out, frag);
+        if ((st = up(&out->frag, pf)) != DYF_OK) return st;
     }
-    if (taps == 16 && cout % 128 == 0 && cin % 64 == 0 && (size_t)cout * taps * cin == pk.size()) {  // halo form of 4x4 / s2
-        std::vector<el16_t> pf((size_t)cout * 16 * 4 * cin);
+    if (enc0_stem && (cout == 64 || cout == 128)) {  // the persistent enc0 kernel (conv_enc0_stem.hip)
+        pf.assign(pk.size(), el16_t{});
+        pack_enc0_stem_frag(pk.data(), cout, pf.data());
+        out->halo_order = HaloOrder::Enc0Stem;
+    } else if (taps == 16 && cout % 128 == 0) {  // halo form of 4x4 / s2
+        pf.assign((size_t)cout * 16 * 4 * cin, el16_t{});
         pack_halo_s2_frag(pk.data(), cout, cin, pf.data());
-        el16_t* frag = nullptr;
-        st = dev_upload(e, &frag, pf);
-        if (st != DYF_OK) return st;
-        conv_register_halo3_frag(*out, frag);
-    }
-    if (taps == 9 && cout % 64 == 0 && cout % 256 != 0 && cin % 64 == 0 && (size_t)cout * taps * cin == pk.size()) {
-        std::vector<el16_t> pf((size_t)cout * 16 * cin);  // halo form of plain 3x3 convs with 64 / 128 output channels (SP = 5)
+        out->halo_order = HaloOrder::S2;
+    } else if (taps == 9 && cout % 256 != 0) {  // halo form of plain 3x3 convs with 64 / 128 output channels (SP = 5)
+        pf.assign((size_t)cout * 16 * cin, el16_t{});
         pack_halo3_frag64(pk.data(), cout, cin, pf.data());
-        el16_t* frag = nullptr;
-        st = dev_upload(e, &frag, pf);
-        if (st != DYF_OK) return st;
-        conv_register_halo3_frag(*out, frag);
-    }
-    if (taps == 9 && cout % 256 == 0 && cin % 64 == 0 && (size_t)cout * taps * cin == pk.size()) {  // halo form of plain 3x3
-        std::vector<el16_t> pf((size_t)cout * 16 * cin);
+        out->halo_order = HaloOrder::Halo3_64;
+    } else if (taps == 9) {  // halo form of plain 3x3, cout % 256 == 0
+        pf.assign((size_t)cout * 16 * cin, el16_t{});
         pack_halo3_frag(pk.data(), cout, cin, pf.data());
-        el16_t* frag = nullptr;
-        st = dev_upload(e, &frag, pf);
-        if (st != DYF_OK) return st;
-        conv_register_halo3_frag(*out, frag);
+        out->halo_order = HaloOrder::Halo3_256;
+    }
+    if (out->halo_order != HaloOrder::None && (st = up(&out->halo, pf)) != DYF_OK) return st;
+    if (out->halo_order == HaloOrder::Halo3_256) {
         // ... and the 64-channel-block order for conv_gn16_kernel (the fused-GroupNorm 3 x 3 convs of the ResNet-UNet's 256-channel level)
         pack_halo3_frag64(pk.data(), cout, cin, pf.data());
-        el16_t* frag64 = nullptr;
-        st = dev_upload(e, &frag64, pf);
-        if (st != DYF_OK) return st;
-        conv_register_frag64(*out, frag64);
+        st = up(&out->frag64, pf);
     }
-    return DYF_OK;
+    return st;
 }
 
 // host view of one state_dict tensor (dyf_load_weights)

@@ -191,13 +191,8 @@ dyf_status sc_load_weights(dyf_engine* e, Net& n, std::map<std::string, TensorVi
         NEED(rm, P + ".norm.running_mean", d);
         NEED(rv, P + ".norm.running_var", d);
         const int taps = (int)(k * k);
-        std::vector<el16_t> pk((size_t)d * taps * cin);
-        for (int co = 0; co < d; ++co)
-            for (int ci = 0; ci < cin; ++ci)
-                for (int t = 0; t < taps; ++t)
-                    pk[((size_t)co * taps + t) * cin + ci] = f32_to_el16(cw->data[((size_t)co * cin + ci) * taps + t]);
-        UP(s->w[i], pk);
-        std::vector<float> pkf(pk.size());
+        UP(s->w[i], pack_conv(cw->data, (int)d, (int)cin, taps));
+        std::vector<float> pkf((size_t)d * taps * cin);
         for (int co = 0; co < d; ++co)
             for (int ci = 0; ci < cin; ++ci)
                 for (int t = 0; t < taps; ++t) pkf[((size_t)co * taps + t) * cin + ci] = cw->data[((size_t)co * cin + ci) * taps + t];
@@ -261,7 +256,6 @@ dyf_status sc_forward(dyf_engine* e, int which, const Source* srcs, int nsrc, in
         ConvArgs a{};
         a.src0 = x; a.c0 = cin; a.n = nb; a.h = H; a.w = W; a.ho = H; a.wo = W;
         a.kh = s->ks[i]; a.kw = s->ks[i]; a.stride = 1; a.pad = (s->ks[i] - 1) / 2; a.cout = n.dim;
-        a.wpk = s->w[i];
         a.coef_a = o.coef_a + i * n.dim; a.coef_c = o.coef_c + i * n.dim; a.coef_stride = o.coef_stride;
         a.act = ACT_GELU;
         DropSpec d{};
@@ -277,7 +271,7 @@ dyf_status sc_forward(dyf_engine* e, int which, const Source* srcs, int nsrc, in
         a.residual = (cin == n.dim) ? x : nullptr;  // simple_conv_net.py:52-54 (residual=True)
         a.out_el16 = s->buf[i & 1];
         a.zero_page = e->ws.zero_page;
-        HIP_TRY(e, launch_conv(a, 0, st));
+        HIP_TRY(e, launch_conv(a, ConvW{s->w[i]}, 0, st));  // path 0: the direct kernel reads the packed weights only
         x = s->buf[i & 1];
         cin = n.dim;
     }

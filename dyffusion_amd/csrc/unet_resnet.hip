@@ -18,7 +18,7 @@ struct RBlockW {  // ResnetBlock
     bool has_res = false;
     bool single = false;  // double_conv_layer=False: no second Block (unet.py:94)
     int film_off = 0;
-    el16_t *w1 = nullptr, *w2 = nullptr, *wr = nullptr;
+    ConvW w1, w2, wr;
     float *b1 = nullptr, *b2 = nullptr, *br = nullptr;
     float *g1 = nullptr, *be1 = nullptr, *g2 = nullptr, *be2 = nullptr;
 };
@@ -27,7 +27,7 @@ struct AttnW {
     int dim = 0;
     bool linear = true;
     float* ln_g = nullptr;
-    el16_t *wqkv = nullptr, *wout = nullptr;
+    ConvW wqkv, wout;
     el16_t *wqkv_frag = nullptr, *wout_frag = nullptr;  // fused LinearAttention (dim 64 / 128)
     float* bout = nullptr;
 };
@@ -35,7 +35,7 @@ struct AttnW {
 struct SampW {  // down / up sampling conv
     int cin = 0, cout = 0, k = 3, stride = 1, pad = 1;
     bool nearest_up = false;
-    el16_t* w = nullptr;
+    ConvW w;
     float* b = nullptr;
 };
 
@@ -101,14 +101,14 @@ struct DropCtx {  // walks the dropout sites in execution order (same order as t
 };
 
 dyf_status rconv(dyf_engine* e, const el16_t* s0, int c0, const el16_t* s1, int c1, int n, int h, int w, int k, int stride,
-                 int pad, int cout, const el16_t* wpk, const float* coef_a, const float* coef_c, int coef_stride, int act,
+                 int pad, int cout, const ConvW& wts, const float* coef_a, const float* coef_c, int coef_stride, int act,
                  const DropSpec& drop, const el16_t* residual, el16_t* out, hipStream_t st, float* gn_part = nullptr,
                  int* gn_slots = nullptr, int up_nearest = 0) {
     ConvArgs a{};
     a.src0 = s0; a.c0 = c0; a.src1 = s1; a.c1 = c1; a.n = n; a.h = h; a.w = w;
     a.up_nearest = up_nearest;  // s0 is the (h / 2) x (w / 2) tensor (only after rconv_nearest_fusable said yes)
     a.ho = (h + 2 * pad - k) / stride + 1; a.wo = (w + 2 * pad - k) / stride + 1;
-    a.kh = k; a.kw = k; a.stride = stride; a.pad = pad; a.cout = cout; a.wpk = wpk;
+    a.kh = k; a.kw = k; a.stride = stride; a.pad = pad; a.cout = cout;
     a.coef_a = coef_a; a.coef_c = coef_c; a.coef_stride = coef_stride; a.act = act; a.drop = drop;
     a.residual = residual; a.out_el16 = out;
     a.splitk_ws = e->ws.splitk; a.splitk_cap = DYF_SPLITK_FLOATS;
@@ -118,32 +118,23 @@ dyf_status rconv(dyf_engine* e, const el16_t* s0, int c0, const el16_t* s1, int 
                           w == e->cfg.width && c0 + c1 == cout && residual == nullptr, n, st);
     if (gn_part && gn_slots) {
         a.gn_part = gn_part;
-        HIP_TRY(e, launch_conv_stats(a, path, st, gn_slots));
+        HIP_TRY(e, launch_conv_stats(a, wts, path, st, gn_slots));
     } else {
-        HIP_TRY(e, launch_conv(a, path, st));
+        HIP_TRY(e, launch_conv(a, wts, path, st));
     }
     return DYF_OK;
 }
 
 // the plain 3x3 conv behind a nearest x2 upsample (output plane h x w) will run on the one form that folds the upsample into its gather
-bool rconv_nearest_fusable(dyf_engine* e, int c0, int n, int h, int w, int cout, const el16_t* wpk) {
+bool rconv_nearest_fusable(dyf_engine* e, int c0, int n, int h, int w, int cout, const ConvW& wts) {
     if (dyf_form_int("DYF_FUSE_NEAREST", 1) == 0) return false;  // A/B + parity test
     if (!e->cfg.enable_mfma || (h & 1) || (w & 1)) return false;
     ConvArgs a{};
-    a.src0 = (const el16_t*)wpk;  // (any non-null pointer: the predicates look at shapes)
-    a.c0 = c0; a.n = n; a.h = h; a.w = w; a.ho = h; a.wo = w; a.kh = 3; a.kw = 3; a.stride = 1; a.pad = 1; a.cout = cout; a.wpk = wpk;
-    a.out_el16 = (el16_t*)wpk;
+    a.src0 = wts.wpk;  // (any non-null pointer: the predicates look at shapes)
+    a.c0 = c0; a.n = n; a.h = h; a.w = w; a.ho = h; a.wo = w; a.kh = 3; a.kw = 3; a.stride = 1; a.pad = 1; a.cout = cout;
+    a.out_el16 = (el16_t*)wts.wpk;
     a.n_sel = conv_form_rows(e, n);
-    return conv_plain3x3_takes_halo5(a);
-}
-
-std::vector<el16_t> pack_conv(const float* w, int cout, int cin, int k) {
-    const int taps = k * k;
-    std::vector<el16_t> pk((size_t)cout * taps * cin);
-    for (int co = 0; co < cout; ++co)
-        for (int ci = 0; ci < cin; ++ci)
-            for (int t = 0; t < taps; ++t) pk[((size_t)co * taps + t) * cin + ci] = f32_to_el16(w[((size_t)co * cin + ci) * taps + t]);
-    return pk;
+    return conv_plain3x3_takes_halo5(a, wts);
 }
 
 // WeightStandardizedConv2d (unet.py:26-40): (w - mean) * rsqrt(var + 1e-5) per output channel, biased variance
@@ -429,10 +420,10 @@ dyf_status rn_load_weights(dyf_engine* e, Net& n, std::map<std::string, TensorVi
         dyf_status _s = upload_conv_weights(e, &(dst), (hostvec), (CO), (TAPS), (CI));         \
         if (_s != DYF_OK) return _s;                                                           \
     } while (0)
-        UPW(b.w1, pack_conv(standardize(w1->data, b.cout, b.cin * 9).data(), b.cout, b.cin, 3), b.cout, 9, b.cin);
+        UPW(b.w1, pack_conv(standardize(w1->data, b.cout, b.cin * 9).data(), b.cout, b.cin, 9), b.cout, 9, b.cin);
         UP(b.b1, vec(b1)); UP(b.g1, vec(g1)); UP(b.be1, vec(e1));
         if (!b.single) {
-            UPW(b.w2, pack_conv(standardize(w2->data, b.cout, b.cout * 9).data(), b.cout, b.cout, 3), b.cout, 9, b.cout);
+            UPW(b.w2, pack_conv(standardize(w2->data, b.cout, b.cout * 9).data(), b.cout, b.cout, 9), b.cout, 9, b.cout);
             UP(b.b2, vec(b2)); UP(b.g2, vec(g2)); UP(b.be2, vec(e2));
         }
         if (b.has_res) {
@@ -477,7 +468,7 @@ dyf_status rn_load_weights(dyf_engine* e, Net& n, std::map<std::string, TensorVi
         const std::string P = "downs." + std::to_string(l) + ".3";
         NEED(w, P + ".weight", (int64_t)s.cout, (int64_t)s.cin, (int64_t)s.k, (int64_t)s.k);
         NEED(b, P + ".bias", (int64_t)s.cout);
-        UPW(s.w, pack_conv(w->data, s.cout, s.cin, s.k), s.cout, s.k * s.k, s.cin);
+        UPW(s.w, pack_conv(w->data, s.cout, s.cin, s.k * s.k), s.cout, s.k * s.k, s.cin);
         UP(s.b, vec(b));
     }
     for (int u = 0; u < r->nlev; ++u) {
@@ -485,7 +476,7 @@ dyf_status rn_load_weights(dyf_engine* e, Net& n, std::map<std::string, TensorVi
         const std::string P = "ups." + std::to_string(u) + (s.nearest_up ? ".3.1" : ".3");
         NEED(w, P + ".weight", (int64_t)s.cout, (int64_t)s.cin, 3, 3);
         NEED(b, P + ".bias", (int64_t)s.cout);
-        UPW(s.w, pack_conv(w->data, s.cout, s.cin, 3), s.cout, 9, s.cin);
+        UPW(s.w, pack_conv(w->data, s.cout, s.cin, 9), s.cout, 9, s.cin);
         UP(s.b, vec(b));
     }
 #undef NEED
@@ -519,14 +510,14 @@ dyf_status rn_forward(dyf_engine* e, int which, const Source* srcs, int nsrc, in
     if (gn_fuse_on) HIP_TRY(e, launch_gn_epoch_bump(r->gn_epoch, st));
     // conv + GroupNorm(+FiLM) + SiLU + Dropout (+ residual) in ONE launch where a fused form serves the shape; *fused = false:
     // nothing was launched
-    auto conv_gn = [&](const el16_t* s0, int c0, const el16_t* s1, int c1, int hh, int ww, int cout, const el16_t* wpk,
+    auto conv_gn = [&](const el16_t* s0, int c0, const el16_t* s1, int c1, int hh, int ww, int cout, const ConvW& wts,
                        const float* bias, const float* gamma, const float* beta, bool with_film, int film_off, const DropSpec& drop,
                        const el16_t* residual, el16_t* out, bool* fused) -> dyf_status {
         *fused = false;
         if (!gn_fuse_on || gn_conv_idx >= 255) return DYF_OK;
         ConvArgs a{};
         a.src0 = s0; a.c0 = c0; a.src1 = s1; a.c1 = c1; a.n = nb; a.h = hh; a.w = ww; a.ho = hh; a.wo = ww;
-        a.kh = 3; a.kw = 3; a.stride = 1; a.pad = 1; a.cout = cout; a.wpk = wpk;
+        a.kh = 3; a.kw = 3; a.stride = 1; a.pad = 1; a.cout = cout;
         a.coef_a = r->ones; a.coef_c = bias; a.coef_stride = 0; a.coef_div = o.coef_div;
         a.act = ACT_SILU; a.drop = drop; a.residual = residual; a.out_el16 = out;
         a.n_sel = conv_form_rows(e, nb);
@@ -538,7 +529,7 @@ dyf_status rn_forward(dyf_engine* e, int which, const Source* srcs, int nsrc, in
         a.gnf.timeout_ticks = e->gn_timeout_ticks; a.gnf.test_tag_xor = e->gn_test_tag_xor;
         ProfScope prof(e, e->prof_layer == DYF_PROF_RESNET_BASE + DYF_PROF_RN_CONV3_L0 && hh == e->cfg.height && ww == e->cfg.width &&
                               c0 + c1 == cout, nb, st);
-        HIP_TRY(e, launch_conv_gn_fused(a, conv_path(e, a), st, fused));
+        HIP_TRY(e, launch_conv_gn_fused(a, wts, conv_path(e, a), st, fused));
         if (*fused) ++gn_conv_idx;
         return DYF_OK;
     };

@@ -624,3 +624,55 @@ def test_small_tile_fused_igemm_form_matches_the_large_tile_form_and_the_oracle(
     print(f"128-pixel tiles vs the fp32 oracle: {err:.3e}")
     assert err <= TOL["fp16"]
     eng.close()
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_reloaded_weights_reach_the_fragment_forms_and_engines_do_not_share_them(dtype, form_switch):
+    """A layer's packed weights and their fragment-ordered copies (halo order, 64-channel-block order, pack_conv_frag) are replaced
+    together by a reload and belong to one engine.  dim 64, mults (1, 2, 4) on 16 x 16 at 3 rows with the tile threshold of
+    conv_gn16_kernel forced down: every 3 x 3 conv streams fragments (64 / 128 channels: halo order; 256 channels: the 64-block copy),
+    the 1 x 1 projections of the bottleneck attention run on conv_skinny_kernel (pack_conv_frag).
+    a) engine A: forward with P1, load P2 into the same engine, forward: bit for bit the forward of a fresh engine built from P2, and
+       not the P1 result;  b) A (P2) and a second engine B (P1) alive at once reproduce their own outputs, A still does after
+       B.close();  c) the form log of A's forward after the reload shows the fragment forms -- no fused conv fell back."""
+    cfg = dict(dim=64, dim_mults=[1, 2, 4], with_time_emb=True, block_dropout=0.0, block_dropout1=0.0, attn_dropout=0.0,
+               resnet_block_groups=8, input_dropout=0.0, upsample_dims=None)
+    hw, nb = (16, 16), 3
+    P1, P2 = seeded_unet(64, (1, 2, 4), 2, 1, seed=21), seeded_unet(64, (1, 2, 4), 2, 1, seed=22)
+    g = torch.Generator().manual_seed(16)
+    x, t = torch.randn(nb, 2, *hw, generator=g).to(DEV), torch.tensor([1.0, 3.0, 6.0]).to(DEV)
+    form_switch.setenv("DYF_GN16_MIN_TILES", "1")
+    form_switch.setenv("DYF_GN16_ANY_PLANE", "1")
+
+    def engine_of(P):
+        net = mirror(P, cfg, 2, 0, 1, dtype)
+        net._own_engine(nb, hw)
+        return net
+
+    a = engine_of(P1)
+    y1 = a(x, time=t).cpu()
+    a.load_state_dict(P2, strict=True)
+    a._engine.form_log(True)
+    y2 = a(x, time=t).cpu()
+    forms = a._engine.form_log_read()
+    a._engine.form_log(False)
+    print(dtype, {k: forms[k] for k in sorted(forms)})
+    fresh = engine_of(P2)
+    assert fresh._engine is not a._engine
+    y2_fresh = fresh(x, time=t).cpu()
+    fresh._engine.close()
+    assert bool(torch.isfinite(y2).all()) and float(y2.std()) > 0
+    assert torch.equal(y2, y2_fresh), "a reload left something of the earlier weights behind"
+    assert not torch.equal(y2, y1)
+    b = engine_of(P1)
+    for _ in range(2):
+        assert torch.equal(b(x, time=t).cpu(), y1) and torch.equal(a(x, time=t).cpu(), y2)
+    b._engine.close()
+    assert torch.equal(a(x, time=t).cpu(), y2)
+    a._engine.close()
+    # every GroupNorm ran inside conv_gn16_kernel (halo order at 64 / 128 channels, 64-block order at 256), none on another fused form
+    # or on the three-kernel chain, and the 1 x 1 projections on a pack_conv_frag form
+    assert {k for k in forms if k.endswith("+gn_fused")} == {"conv_gn16_kernel+gn_fused"}, sorted(forms)
+    assert "gn_apply_part_kernel" not in forms and "gn_stats_kernel+gn_apply" not in forms, sorted(forms)
+    assert sum(forms["conv_gn16_kernel+gn_fused"].values()) == 30  # 15 ResnetBlocks (6 down, 2 mid, 6 up, 1 final) x 2 Blocks
+    assert any(k.startswith("conv_skinny_kernel") or k.startswith("conv_igemm2_kernel") for k in forms), sorted(forms)
