@@ -2121,4 +2121,12 @@ dyf_status dyf_op_attention_dropout(dyf_engine* e, const uint16_t* qkv_dev, int3
     return DYF_OK;
 }
 
+dyf_status dyf_op_attention_f32(dyf_engine* e, const float* qkv_dev, int32_t n, int32_t hw, float p, const uint8_t* mask_dev, int32_t form,
+                                float* out_dev, void* stream) {
+    if (!e || !qkv_dev || !out_dev || n < 1 || hw < 1 || p < 0.0f || p >= 1.0f || (form != 0 && form != 1) || (mask_dev && p <= 0.0f))
+        return fail(e, DYF_ERR_INVALID_ARGUMENT, "dyf_op_attention_f32: bad arguments");
+    HIP_TRY(e, hipSetDevice(e->cfg.device));
+    return f32_op_attention(e, qkv_dev, n, hw, p, mask_dev, form, out_dev, (hipStream_t)stream);
+}
+
 }  // extern "C"

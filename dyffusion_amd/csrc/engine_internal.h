@@ -369,6 +369,8 @@ dyf_status f32_net_forward(dyf_engine* e, int which, const Source* srcs, int nsr
                            hipStream_t st);
 dyf_status f32_prepare(dyf_engine* e);  // first switch to 32 bits: arena + split-K workspace
 void f32_destroy(dyf_engine* e);
+// the fp32 Attention core alone (dyf_op_attention_f32): form 0 = the probability-keeping kernel, 1 = the streaming kernel; synchronises
+dyf_status f32_op_attention(dyf_engine* e, const float* qkv, int nb, int N, float p, const uint8_t* mask, int form, float* out, hipStream_t st);
 inline size_t f32_arena_block(size_t bytes) { return (std::max<size_t>(bytes, 256) + 255) / 256 * 256; }
 // bump allocation out of the arena (null: exhausted); f32_net_forward rewinds it at the start of every forward
 inline void* f32_arena_take(dyf_engine* e, size_t bytes) {

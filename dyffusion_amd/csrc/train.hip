@@ -1729,7 +1729,7 @@ dyf_status f32_prepare(dyf_engine* e) {
     for (int w = 0; w < 2; ++w) {
         const Net& n = e->net[w];
         if (n.rn && !rn_f32_supported(e, n))
-            return fail(e, DYF_ERR_UNSUPPORTED, "fp32 sampling: the bottleneck Attention keeps its (tokens x tokens) probabilities -- at most 4096 tokens");
+            return fail(e, DYF_ERR_UNSUPPORTED, "fp32 sampling: the bottleneck Attention indexes its (4 x tokens x tokens) probabilities with 32 bits -- at most 32767 tokens");
         fwd = std::max(fwd, n.rn ? rn_arena_bytes(e, n, e->cfg.max_batch)
                                  : n.sc ? sc_f32_arena_bytes(e, n, e->cfg.max_batch) : us_arena_bytes(e, n, e->cfg.max_batch));
     }

@@ -494,6 +494,126 @@ __global__ void t_at_fwd(const float* qkv, int N, long long rows, float scale, R
     }
     for (int d = 0; d < RD; ++d) out[((size_t)n * N + i) * RHID + h * RD + d] = o[d];
 }
+
+// ---- the same core, streaming (a sampling forward of more than 4096 tokens: nothing of size N^2 is written).  Online softmax on the
+// fp32 matrix cores (mfma_f32_32x32x2f32: an exact k-ordered fp32 fma chain).  One wave per 32 queries, AS_NW waves per workgroup share
+// every 32-key K / V tile through LDS (double-buffered; the next tile's global loads fly under the current tile's MFMAs).
+//   S^T = K Q^T   16 MFMAs: A = K[key = l&31][d], B = Q[query = l&31][d] (16 registers, loaded once, pre-scaled as t_at_fwd does);
+//                 k-step s of lane half hi = l>>5 is channel d = 16 hi + s, so a lane's K fragment is 64 contiguous bytes of its key's
+//                 row (4 ds_read_b128; rows padded to 36 floats: the 16-lane groups of a b128 read then cover the 16 slots once).
+//   A lane owns query column l&31; accumulator r is key kr(r) = (r&3) + 8 (r>>2) + 4 hi.  Row max: in-lane + one exchange with the lane
+//   32 away.  The row sum stays a per-lane partial (both halves share the max) and is joined once after the last tile.
+//   O^T = V^T P^T 16 MFMAs: B = the S^T accumulators as they are (k-step r carries keys kr(r) of both halves), A = V[kr(r)][d = l&31]
+//                 (ds_read_b32 along a row: 32 banks).  O^T accumulator r is channel kr(r) of the lane's query.
+// Dropout is on the normalised probability: keep * scale multiplies p in P V only, never the running sum.  Element index and generator
+// are t_at_fwd's (r_keep, one keep word per element: a pair of an odd N straddles two queries, so nothing is shared across elements).
+// Keys >= N score -inf (p = 0 exactly) and their V rows are staged as zeros; tile 0 always holds key 0, so the running max is finite
+// from the first tile on and (-inf) - (-inf) never occurs.
+typedef __attribute__((ext_vector_type(16))) float as_f32x16;
+constexpr int AT_KEEP_P_MAX = 4096;    // most tokens t_at_fwd keeps its (tokens x tokens) probabilities for (the training step's limit)
+constexpr int AT_STREAM_MAX = 32767;   // most tokens of the streaming core: 4 N^2 <= 2^32 - 1, the dropout element index is uint32_t
+constexpr int AS_NW = 4;    // waves per workgroup: 128 queries
+constexpr int AS_KS = 36;   // floats per K row in LDS
+static_assert(AS_NW * 64 == 32 * (RD / 4), "one float4 of K and one of V per thread stage a 32-key tile");
+__device__ __forceinline__ int as_key(int r, int hi) { return (r & 3) + 8 * (r >> 2) + 4 * hi; }
+template <bool DROP>
+__global__ __launch_bounds__(64 * AS_NW) void t_at_stream_fwd(const float* __restrict__ qkv, int N, float scale, RDrop dr, float* __restrict__ out) {
+    __shared__ __attribute__((aligned(16))) float Ks[2][32 * AS_KS];
+    __shared__ __attribute__((aligned(16))) float Vs[2][32 * RD];
+    const int tid = threadIdx.x, l = tid & 63, lq = l & 31, hi = l >> 5;
+    const int h = blockIdx.y, n = blockIdx.z;
+    const int q0 = ((int)blockIdx.x * AS_NW + (tid >> 6)) * 32;
+    const bool active = q0 < N;  // wave-uniform: a wave past the last query only helps staging
+    const int qi = q0 + lq, qc = qi < N ? qi : N - 1;
+    const float* base = qkv + (size_t)n * N * 3 * RHID + h * RD;
+    float qf[16];
+    {
+        const float4* qp = (const float4*)(base + (size_t)qc * 3 * RHID + 16 * hi);
+        for (int c = 0; c < 4; ++c) {
+            const float4 v = qp[c];
+            qf[4 * c] = v.x * scale; qf[4 * c + 1] = v.y * scale; qf[4 * c + 2] = v.z * scale; qf[4 * c + 3] = v.w * scale;
+        }
+    }
+    // staging: thread -> (key tid>>3, channels 4 (tid&7) ..+3) of the tile
+    const int sk = tid >> 3, sc = (tid & 7) * 4;
+    float4 kreg, vreg;
+    auto fetch = [&](int kt) {
+        const int j = kt + sk;
+        kreg = vreg = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if (j < N) {
+            const float* p = base + (size_t)j * 3 * RHID + sc;
+            kreg = *(const float4*)(p + RHID);
+            vreg = *(const float4*)(p + 2 * RHID);
+        }
+    };
+    auto stage = [&](int b) {
+        *(float4*)(&Ks[b][sk * AS_KS + sc]) = kreg;
+        *(float4*)(&Vs[b][sk * RD + sc]) = vreg;
+    };
+    as_f32x16 o;
+    for (int r = 0; r < 16; ++r) o[r] = 0.0f;
+    float m = -INFINITY, lsum = 0.0f;
+    const uint32_t ebase = ((uint32_t)h * (uint32_t)N + (uint32_t)qc) * (uint32_t)N;
+    const int tiles = (N + 31) / 32;
+    fetch(0);
+    stage(0);
+    __syncthreads();
+    for (int t = 0; t < tiles; ++t) {
+        const int b = t & 1, kt = t * 32;
+        if (t + 1 < tiles) fetch(kt + 32);
+        if (active) {
+            as_f32x16 s;
+            for (int r = 0; r < 16; ++r) s[r] = 0.0f;
+            const float4* kp = (const float4*)(&Ks[b][lq * AS_KS + 16 * hi]);
+            for (int c = 0; c < 4; ++c) {
+                const float4 kv = kp[c];
+                s = __builtin_amdgcn_mfma_f32_32x32x2f32(kv.x, qf[4 * c], s, 0, 0, 0);
+                s = __builtin_amdgcn_mfma_f32_32x32x2f32(kv.y, qf[4 * c + 1], s, 0, 0, 0);
+                s = __builtin_amdgcn_mfma_f32_32x32x2f32(kv.z, qf[4 * c + 2], s, 0, 0, 0);
+                s = __builtin_amdgcn_mfma_f32_32x32x2f32(kv.w, qf[4 * c + 3], s, 0, 0, 0);
+            }
+            if (kt + 32 > N)  // the ragged last tile
+                for (int r = 0; r < 16; ++r)
+                    if (kt + as_key(r, hi) >= N) s[r] = -INFINITY;
+            float mx = s[0];
+            for (int r = 1; r < 16; ++r) mx = fmaxf(mx, s[r]);
+            mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+            float mn = fmaxf(m, mx);
+            if (mn == -INFINITY) mn = 0.0f;
+            const float alpha = __expf(m - mn);
+            m = mn;
+            float ps = 0.0f;
+            for (int r = 0; r < 16; ++r) {
+                const float p = __expf(s[r] - mn);
+                s[r] = p;
+                ps += p;
+            }
+            lsum = lsum * alpha + ps;
+            for (int r = 0; r < 16; ++r) o[r] *= alpha;
+            if (DROP)
+                for (int r = 0; r < 16; ++r) {
+                    const int j = kt + as_key(r, hi);
+                    s[r] = j < N ? s[r] * r_keep(dr, n, ebase + (uint32_t)j) : 0.0f;
+                }
+            const float* vp = &Vs[b][lq];
+            for (int r = 0; r < 16; ++r) o = __builtin_amdgcn_mfma_f32_32x32x2f32(vp[as_key(r, hi) * RD], s[r], o, 0, 0, 0);
+        }
+        if (t + 1 < tiles) stage(b ^ 1);
+        __syncthreads();
+    }
+    if (!active || qi >= N) return;
+    lsum += __shfl_xor(lsum, 32, 64);
+    const float inv = 1.0f / lsum;
+    float* op = out + ((size_t)n * N + qi) * RHID + h * RD + 4 * hi;
+    for (int g = 0; g < 4; ++g) *(float4*)(op + 8 * g) = make_float4(o[4 * g] * inv, o[4 * g + 1] * inv, o[4 * g + 2] * inv, o[4 * g + 3] * inv);
+}
+// the launch of the streaming core; d.on / d.mask select the dropout instantiation
+static inline void launch_t_at_stream_fwd(const float* qkv, int nb, int N, float scale, const RDrop& d, float* out, hipStream_t st) {
+    dyf_form_note("t_at_stream_fwd", nb);
+    const dim3 grid((unsigned)((N + 32 * AS_NW - 1) / (32 * AS_NW)), RH, (unsigned)nb);
+    if (d.on || d.mask) hipLaunchKernelGGL(t_at_stream_fwd<true>, grid, dim3(64 * AS_NW), 0, st, qkv, N, scale, d, out);
+    else hipLaunchKernelGGL(t_at_stream_fwd<false>, grid, dim3(64 * AS_NW), 0, st, qkv, N, scale, d, out);
+}
 // row pass of the backward: dS (n, h, N, N) = P * (dP - sum_j P dP), dP_ij = keep_ij * (dout_i . v_j); dq_i = scale * sum_j dS_ij k_j
 __global__ void t_at_bwd_row(const float* qkv, const float* P, const float* dout, int N, long long rows, float scale, RDrop dr, float* dS,
                              float* dqkv) {
@@ -945,6 +1065,12 @@ struct RCtx {
     dyf::RT* attention(dyf::RT* qkv, int N, float p_drop) {
         const long long rows = (long long)nb * RH * N;
         const float scale = 1.0f / sqrtf((float)RD);
+        if (!mem.recording() && N > AT_KEEP_P_MAX) {  // sampling past the kept-probabilities limit: the streaming core, no P, no adjoint
+            const RDrop d = drop(p_drop, (size_t)RH * N * N);
+            dyf::RT* y = make((size_t)nb * N * RHID);
+            launch_t_at_stream_fwd(qkv->p, nb, N, scale, d, y->p, st);
+            return dbg(y, "attention");
+        }
         float* Pm = fbuf((size_t)rows * N);
         const RDrop d = drop(p_drop, (size_t)RH * N * N);
         dyf::RT* y = make((size_t)nb * N * RHID);
@@ -1019,7 +1145,10 @@ struct RCount {
         take((size_t)2 * ((hw + LA_CHUNK - 1) / LA_CHUNK) * nb * RH * RD * RD * 2);
         return make(tot);
     }
-    dyf::RT* attention(dyf::RT*, int N, float) { take((size_t)nb * RH * N * N); return make((size_t)nb * N * RHID); }
+    dyf::RT* attention(dyf::RT*, int N, float) {  // (counts a sampling forward: past AT_KEEP_P_MAX the streaming core keeps no P)
+        if (N <= AT_KEEP_P_MAX) take((size_t)nb * RH * N * N);
+        return make((size_t)nb * N * RHID);
+    }
 };
 
 // The layer walk of unet.Unet.forward (unet.py:262-315), shared by the recorded forward, the sampling forward (both RCtx: they differ
@@ -1233,10 +1362,49 @@ size_t rn_arena_bytes(const dyf_engine* e, const Net& n, int nb) {
     return K.bytes;
 }
 
-// the fp32 Attention core keeps its (tokens x tokens) probabilities, as the training step does
+// past 4096 tokens the sampling forward takes the streaming Attention core, whose dropout element index (h N + i) N + j is uint32_t:
+// 4 N^2 <= 2^32 - 1, N <= 32 767
 bool rn_f32_supported(const dyf_engine* e, const Net& n) {
     const RNames R = rn_names(e, n.cfg);
-    return (long long)R.lev_h.back() * R.lev_w.back() <= 4096;
+    return (long long)R.lev_h.back() * R.lev_w.back() <= AT_STREAM_MAX;
+}
+
+// test seam (dyf_op_attention_f32): the fp32 Attention core alone.  form 0: t_at_fwd with scratch probabilities; form 1: the streaming
+// core at any supported N.  p > 0: the caller's keep mask (nb, 4, N, N), or the engine's generator armed as dyf_op_attention_dropout does.
+dyf_status f32_op_attention(dyf_engine* e, const float* qkv, int nb, int N, float p, const uint8_t* mask, int form, float* out, hipStream_t st) {
+    if (form == 0 && N > AT_KEEP_P_MAX)
+        return fail(e, DYF_ERR_UNSUPPORTED, "dyf_op_attention_f32: form 0 keeps its (tokens x tokens) probabilities -- at most 4096 tokens");
+    if (N > AT_STREAM_MAX)
+        return fail(e, DYF_ERR_UNSUPPORTED, "dyf_op_attention_f32: the dropout element index is 32 bits -- at most 32767 tokens");
+    RDrop d{};
+    if (p > 0.0f) {
+        d.scale = 1.0f / (1.0f - p);
+        if (mask) {
+            d.mask = mask;
+            d.per = (uint32_t)((size_t)RH * N * N);
+        } else {
+            if (nb > 2 * e->cfg.max_batch) return fail(e, DYF_ERR_INVALID_ARGUMENT, "more rows than the engine's row-key table (2 max_batch)");
+            TK(launch_rng_begin_forward(e->rng_state, e->row_keys, nb, nb, st));
+            d.on = 1;
+            d.thresh16 = keep_threshold16(p);
+            d.salt = rng_layer_salt(0u);
+            d.row_keys = e->row_keys;
+        }
+    }
+    const float scale = 1.0f / sqrtf((float)RD);
+    float* P = nullptr;
+    if (form == 0) {
+        const long long rows = (long long)nb * RH * N;
+        TK(hipMalloc(&P, (size_t)rows * N * sizeof(float)));
+        hipLaunchKernelGGL(t_at_fwd, dim3(nblk(rows, 64)), dim3(64), 0, st, qkv, N, rows, scale, d, P, out);
+    } else {
+        launch_t_at_stream_fwd(qkv, nb, N, scale, d, out, st);
+    }
+    hipError_t err = hipGetLastError();
+    if (err == hipSuccess) err = hipStreamSynchronize(st);
+    if (P) (void)hipFree(P);
+    if (err != hipSuccess) return fail(e, DYF_ERR_HIP, std::string("dyf_op_attention_f32: ") + hipGetErrorString(err));
+    return DYF_OK;
 }
 
 dyf_status rn_f32_forward(dyf_engine* e, int which, const Source* srcs, int nsrc, int nb, const FwdOpts& o, float* out_dev, hipStream_t st) {

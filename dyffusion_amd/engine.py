@@ -682,6 +682,19 @@ class HipEngine:
         self._check(self._lib.dyf_op_attention_dropout(self._h, qkv.data_ptr(), n, hw, float(p_drop), y.data_ptr(), self._stream()))
         return y
 
+    def op_attention_f32(self, qkv: torch.Tensor, p_drop: float = 0.0, mask: Optional[torch.Tensor] = None, form: int = 1) -> torch.Tensor:
+        """Test seam: the fp32 Attention core.  qkv (N,HW,384) fp32 -> (N,HW,128) fp32.  form 0: the kernel that keeps its
+        probabilities (HW <= 4096), form 1: the streaming kernel.  p_drop > 0: dropout on the probabilities, from `mask`
+        (N,4,HW,HW) uint8 if given, else from the engine's generator."""
+        assert qkv.dtype == torch.float32 and qkv.is_cuda and qkv.is_contiguous() and qkv.shape[2] == 384
+        n, hw, _ = qkv.shape
+        if mask is not None:
+            assert mask.dtype == torch.uint8 and mask.is_cuda and mask.is_contiguous() and tuple(mask.shape) == (n, 4, hw, hw)
+        y = torch.empty((n, hw, 128), dtype=torch.float32, device=qkv.device)
+        self._check(self._lib.dyf_op_attention_f32(self._h, qkv.data_ptr(), n, hw, float(p_drop), None if mask is None else mask.data_ptr(),
+                                                   int(form), y.data_ptr(), self._stream()))
+        return y
+
     def op_upconv2d(self, x_nhwc_bf16: torch.Tensor, weight: torch.Tensor, scale: Optional[torch.Tensor] = None,
                     shift: Optional[torch.Tensor] = None, act: int = 0) -> torch.Tensor:
         """Test seam: fused Upsample(x2, bilinear) + Conv2d(3x3, pad 1).  x (N,H,W,Cin) bf16 -> (N,2H,2W,Cout) bf16."""

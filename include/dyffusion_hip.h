@@ -212,8 +212,10 @@ int32_t dyf_row_groups(const dyf_engine* engine);
  * freed by dyf_engine_destroy: nothing is allocated or synchronised inside a forward, the forward is bitwise repeatable (split-K sums are
  * reduced through a workspace in a fixed order, GroupNorm sums by one workgroup per sample) and a rollout is captured and replayed with
  * use_graph like the 16-bit one.  Both builds of the library implement it alike; it does not depend on dyf_engine_config.dtype.
- * unet.Unet with more than 4096 bottleneck tokens (the fp32 Attention core keeps its probabilities): DYF_ERR_UNSUPPORTED.  Any other
- * value of bits: DYF_ERR_INVALID_ARGUMENT.
+ * unet.Unet: up to 4096 bottleneck tokens the fp32 Attention core is the training step's (it writes its probabilities into the arena),
+ * beyond that a streaming matrix-core kernel that writes nothing of size tokens^2 (the 512^2 configuration: 16 384 tokens); more than
+ * 32 767 tokens (4 tokens^2 probabilities per row no longer indexed by 32 bits): DYF_ERR_UNSUPPORTED.  The training step keeps its own
+ * limit of 4096 tokens.  Any other value of bits: DYF_ERR_INVALID_ARGUMENT.
  *   - the plan walker is the 16-bit one (sampler state, cold-sampling update, noisy condition, forecast stack, log, dyf_get_sampler_state,
  *     dyf_plan_forward_counts are shared); in fp32 there is no paired interpolator forward, no batched refinement and no row groups
  *     (dyf_set_row_groups stays accepted, a call behaves as with one group).  Forward order, and so the order of the generator's forward

@@ -109,6 +109,13 @@ dyf_status dyf_op_attention(dyf_engine* engine, const uint16_t* qkv_dev, int32_t
  * interpolator's bottleneck runs under MC dropout (n <= 2 max_batch rows). */
 dyf_status dyf_op_attention_dropout(dyf_engine* engine, const uint16_t* qkv_dev, int32_t n, int32_t hw, float p, uint16_t* out_dev,
                                     void* stream);
+/* The fp32 Attention core of fp32 sampling and the training step: qkv_dev (N,HW,384) fp32 -> out_dev (N,HW,128) fp32.  form 0: the
+ * kernel that keeps its (tokens x tokens) probabilities, in scratch memory here (HW <= 4096, else DYF_ERR_UNSUPPORTED); form 1: the
+ * streaming matrix-core kernel a sampling forward takes past 4096 tokens, at any HW <= 32 767.  p > 0 with mask_dev == NULL: dropout
+ * on the probabilities from the engine's generator, armed as dyf_op_attention_dropout arms it; mask_dev (N,4,HW,HW) uint8: the
+ * caller's keep mask, survivors scaled by 1 / (1 - p). */
+dyf_status dyf_op_attention_f32(dyf_engine* engine, const float* qkv_dev, int32_t n, int32_t hw, float p, const uint8_t* mask_dev,
+                                int32_t form, float* out_dev, void* stream);
 
 /* One training convolution (csrc/train_gemm.hip: fp32 matrix-core forward / dgrad / wgrad of nn.Conv2d on NHWC fp32 tensors) on
  * hash-random data against the plain VALU kernel of csrc/train.hip.  kind 0 forward, 1 data gradient, 2 weight gradient (the

@@ -1,5 +1,9 @@
 """Time the flash-attention core (dyf_op_attention: 4 heads x 32 dims) at the bottleneck of BASELINE configs[4]: 16 384 tokens
-(128 x 128), NB rows, without and with dropout on the probabilities.  usage: python tools/bench_attention.py [NB] [tokens] [p]"""
+(128 x 128), NB rows, without and with dropout on the probabilities.  usage: python tools/bench_attention.py [NB] [tokens] [p]
+--fp32: the fp32 core of fp32 sampling instead (dyf_op_attention_f32), no dropout: form 0 (keeps its probabilities, <= 4096 tokens)
+against form 1 (streaming, matrix cores), interleaved in one process; medians of the per-call times (form 0's call also allocates
+its scratch probabilities: the seam's hipMalloc sits between the two events).
+usage: python tools/bench_attention.py --fp32 [NB] [tokens]"""
 import os
 import sys
 
@@ -13,6 +17,8 @@ forward_env_forms()  # DYF_* switches of this run -> dyf_debug_set_form
 import dyffusion_amd as D  # noqa: E402
 from dyffusion_amd.engine import net_config  # noqa: E402
 
+fp32 = "--fp32" in sys.argv
+sys.argv = [a for a in sys.argv if a != "--fp32"]
 nb = int(sys.argv[1]) if len(sys.argv) > 1 else 4
 n = int(sys.argv[2]) if len(sys.argv) > 2 else 16384
 cfg = net_config(in_channels=3, cond_channels=2, out_channels=3, dim=64, with_time_emb=True, upsample_dims=(64, 64), dropout=0.0)
@@ -21,6 +27,27 @@ eng = D.HipEngine(cfg, cfg, 23, 11, max_batch=max(1, nb), use_graph=False)
 g = torch.Generator().manual_seed(0)
 qkv = torch.randn(nb, n, 384, generator=g).to(eng.torch_dtype).cuda()
 fl = nb * 4 * 2 * 2 * n * n * 32
+if fp32:
+    import statistics
+
+    q32 = torch.randn(nb, n, 384, generator=g).cuda()
+    forms = [1] if n > 4096 else [0, 1]
+    for f in forms * 3:  # warm-up: clocks up, both kernels loaded
+        y = eng.op_attention_f32(q32, form=f)
+    times = {f: [] for f in forms}
+    for _ in range(5 if n > 4096 else 15):  # interleaved: both forms see the same clocks (the seam synchronises: one call = one launch)
+        for f in forms:
+            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            ev0.record()
+            y = eng.op_attention_f32(q32, form=f)
+            ev1.record()
+            torch.cuda.synchronize()
+            times[f].append(ev0.elapsed_time(ev1))
+    for f in forms:
+        ms = statistics.median(times[f])
+        print(f"fp32 attention core form {f} ({'streaming' if f else 'keeps P'}) NB={nb}, {n} tokens: median {ms:.3f} ms (min {min(times[f]):.3f}, "
+              f"max {max(times[f]):.3f}), {fl / ms / 1e9:.1f} TFLOP/s = {fl / ms / 1e9 / 157:.3f} of the 157 TF fp32 matrix peak")
+    sys.exit(0)
 for pd in (0.0, p):
     for _ in range(10):  # the device idles in a low-power state: ten launches before the timed ones (measured: one warm-up launch
         y = eng.op_attention(qkv, pd)  # and ten timed ones read 0.84 ms where the steady state is 0.76 ms)

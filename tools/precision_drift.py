@@ -5,6 +5,7 @@ ONE JSON line: the per-horizon rel-RMS of the 16-bit fields against the fp32 fie
 
     python tools/precision_drift.py --config ns    --dtype bf16 [--rows 8]     # NS benchmark: 221x42, dim 64 @ 256^2, h = 16
     python tools/precision_drift.py --config oisst --dtype fp16 [--rows 8]     # OISST: 60x60, unet.Unet, T = 32, data+noise
+    python tools/precision_drift.py --config synth512 --dtype fp16 --rows 4    # 512x512x4, unet.Unet, h = 32: 16 384 bottleneck tokens
     python tools/precision_drift.py --small                                    # the 23x11 test pair (dim 64 @ 64^2, h = 4)
 
 Needs an MI355X.  Imports neither the oracle nor the reference: the fp32 engine is the yardstick.
@@ -63,6 +64,17 @@ def make(config, dtype, rows, attn_dropout=True):
                         schedule="before_t1_only", sampling_type="cold", refine_intermediate_predictions=True,
                         enable_interpolator_dropout=True, max_batch=rows, dtype=dtype)
         x0, c = torch.randn(rows, 3, *hw, generator=g), torch.rand(rows, 2, *hw, generator=g)
+    elif config == "synth512":  # the shapes of bench.py's config4_synth512 (fp32: the streaming Attention core, 16 384 tokens)
+        kw = dict(dim=64, dim_mults=(1, 2, 4), with_time_emb=True)
+        I = D.Unet(num_input_channels=8, num_output_channels=4, block_dropout=0.1, attn_dropout=0.1 if attn_dropout else 0.0, **kw)
+        F = D.Unet(num_input_channels=4, num_output_channels=4, **kw)
+        # conv gains halved: the h = 32 recursion of a random-init pair must stay inside fp16's range
+        F.load_state_dict(random_state(F, 0, 0.5))
+        I.load_state_dict(random_state(I, 1, 0.5))
+        m = D.DYffusion(F, D.InterpolatorHandle(I, 32), timesteps=32, forward_conditioning="none", interpolate_before_t1=True,
+                        refine_intermediate_predictions=False, enable_interpolator_dropout=True, max_batch=rows, dtype=dtype,
+                        allow_bf16_long_rollout=True)
+        x0, c = torch.randn(rows, 4, 512, 512, generator=g), None
     else:
         kw = dict(dim=64, dim_mults=(1, 2, 4), with_time_emb=True)
         # attn_dropout also covers the one site whose keep bits differ between the precisions (the attention probabilities: k/256
@@ -101,11 +113,11 @@ def rel_rms(a, b):
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
-    ap.add_argument("--config", choices=["ns", "oisst"], default="ns")
+    ap.add_argument("--config", choices=["ns", "oisst", "synth512"], default="ns")
     ap.add_argument("--small", action="store_true", help="the 23x11 test pair instead of --config")
     ap.add_argument("--dtype", choices=["bf16", "fp16"], default="bf16", help="the 16-bit engine compared with fp32")
     ap.add_argument("--rows", type=int, default=8, help="batch rows (ensemble members x batch) of the rollout")
-    ap.add_argument("--no-attention-dropout", action="store_true", help="oisst: attn_dropout = 0 in both networks")
+    ap.add_argument("--no-attention-dropout", action="store_true", help="oisst / synth512: attn_dropout = 0 in both networks")
     ap.add_argument("--seed", type=int, default=7)
     ap.add_argument("--reps", type=int, default=2, help="timed rollouts per engine (the best counts)")
     a = ap.parse_args()
