@@ -84,6 +84,16 @@ BC_NAVIER_STOKES, BC_SPRING_MESH = 0, 1
 COMM_ID_BYTES = 128  # DYF_COMM_ID_BYTES (ncclUniqueId)
 TRAIN_BATCH_STATS, TRAIN_DROPOUT = 1, 2
 
+
+class TrainOp(C.Structure):
+    """dyf_train_op (include/dyffusion_hip_testing.h): one recorded op of the ResNet-UNet training step for dyf_op_train_f32."""
+    _fields_ = [(k, C.c_int32) for k in ("op", "nb", "h", "w", "c", "c2", "k", "stride", "pad", "groups", "flags")] + [("p", C.c_float)]
+
+
+TRAIN_OPS = {"conv": 0, "gn_act": 1, "layernorm": 2, "linattn": 3, "attention": 4, "linear": 5, "learned_sinu": 6, "dropout": 7,
+             "gelu": 8, "add": 9, "cat": 10, "up2_nearest": 11}
+TOP_WS, TOP_BIAS, TOP_PRE, TOP_FILM, TOP_SAME = 1, 2, 4, 8, 16
+
 # every symbol include/dyffusion_hip.h and include/dyffusion_hip_testing.h declare: (name, restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = [
@@ -131,6 +141,7 @@ SYMBOLS = [
     ("dyf_op_attention", C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P]),
     ("dyf_op_attention_dropout", C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_float, _P, _P]),
     ("dyf_op_attention_f32", C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_float, _P, C.c_int32, _P, _P]),
+    ("dyf_op_train_f32", C.c_int, [_P, C.POINTER(TrainOp), C.POINTER(_P), C.POINTER(_P), _P, _P, C.POINTER(_P), C.POINTER(_P), _P]),
     ("dyf_criterion", C.c_int, [_P, _P, _P, C.c_int64, C.c_int32, _P, _P]),
     ("dyf_train_forward", C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int32, C.c_int32, _P]),
     ("dyf_train_backward", C.c_int, [_P, C.c_int32, _P, _P, C.c_int32, _P]),

@@ -2129,4 +2129,11 @@ dyf_status dyf_op_attention_f32(dyf_engine* e, const float* qkv_dev, int32_t n, 
     return f32_op_attention(e, qkv_dev, n, hw, p, mask_dev, form, out_dev, (hipStream_t)stream);
 }
 
+dyf_status dyf_op_train_f32(dyf_engine* e, const dyf_train_op* desc, const float* const* inputs_dev, const float* const* params_host,
+                            const float* dout_dev, float* y_dev, float* const* dinputs_dev, float* const* dparams_host, void* stream) {
+    if (!e || !desc || !inputs_dev || !dout_dev || !y_dev) return fail(e, DYF_ERR_INVALID_ARGUMENT, "dyf_op_train_f32: bad arguments");
+    HIP_TRY(e, hipSetDevice(e->cfg.device));
+    return f32_op_train(e, desc, inputs_dev, params_host, dout_dev, y_dev, dinputs_dev, dparams_host, (hipStream_t)stream);
+}
+
 }  // extern "C"

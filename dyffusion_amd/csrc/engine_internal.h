@@ -359,6 +359,7 @@ struct FwdOpts {
 }  // namespace dyf
 
 // ---- training step (train.hip)
+struct dyf_train_op;  // include/dyffusion_hip_testing.h
 namespace dyf {
 dyf_status train_store_weights(dyf_engine* e, int which, std::map<std::string, TensorView>& sd);
 dyf_status rn_train_store_weights(dyf_engine* e, int which, std::map<std::string, TensorView>& sd);  // arch unet.Unet
@@ -371,6 +372,9 @@ dyf_status f32_prepare(dyf_engine* e);  // first switch to 32 bits: arena + spli
 void f32_destroy(dyf_engine* e);
 // the fp32 Attention core alone (dyf_op_attention_f32): form 0 = the probability-keeping kernel, 1 = the streaming kernel; synchronises
 dyf_status f32_op_attention(dyf_engine* e, const float* qkv, int nb, int N, float p, const uint8_t* mask, int form, float* out, hipStream_t st);
+// one recorded op of the ResNet-UNet training step and its adjoint (dyf_op_train_f32, include/dyffusion_hip_testing.h); synchronises
+dyf_status f32_op_train(dyf_engine* e, const struct dyf_train_op* d, const float* const* inputs, const float* const* params, const float* dout,
+                        float* y, float* const* dinputs, float* const* dparams, hipStream_t st);
 inline size_t f32_arena_block(size_t bytes) { return (std::max<size_t>(bytes, 256) + 255) / 256 * 256; }
 // bump allocation out of the arena (null: exhausted); f32_net_forward rewinds it at the start of every forward
 inline void* f32_arena_take(dyf_engine* e, size_t bytes) {

@@ -16,6 +16,7 @@
 #include "train_internal.h"
 
 #include "../../include/dyffusion_hip.h"
+#include "../../include/dyffusion_hip_testing.h"  // dyf_train_op: the op seam of train_resnet.inc
 
 using namespace dyf;
 
@@ -983,6 +984,13 @@ __global__ void t_norm_bwd_combine(TNorm a, const double* A, const double* B, co
 }
 
 // dz = rstd * (gamma*dbn - (S1 + xhat*S2) / count)
+// gamma*dbn is rounded on its own (t_mul_rounded: never contracted into an fma with the subtraction), as the terms of S1 are: where
+// the two cancel -- a statistic over few elements; exactly, over one -- an fma would keep the product's rounding residue, times rstd
+// (316 at variance 0): 2e-5 of dy where the gradient is 0
+__device__ __forceinline__ float t_mul_rounded(float x, float y) {
+#pragma clang fp contract(off)
+    return x * y;
+}
 __global__ void t_norm_bwd_apply(TNorm a, const float* z, const float* dy, const float* S1, const float* S2, float inv_count, float* dz) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     const long long per = (long long)a.hw * a.C;
@@ -993,7 +1001,7 @@ __global__ void t_norm_bwd_apply(TNorm a, const float* z, const float* dy, const
     const float sc = a.ss ? a.ss[(size_t)b * 2 * a.C + c] : 0.0f, sh = a.ss ? a.ss[(size_t)b * 2 * a.C + a.C + c] : 0.0f;
     const float u = v * (1.0f + sc) + sh;
     const float dbn = dy[i] * t_keep(a, b, (uint32_t)(i - (long long)b * per)) * t_dact(u, a.act) * (1.0f + sc);
-    dz[i] = a.rstd[idx] * (a.gamma[c] * dbn - (S1[idx] + xh * S2[idx]) * inv_count);
+    dz[i] = a.rstd[idx] * (t_mul_rounded(a.gamma[c], dbn) - (S1[idx] + xh * S2[idx]) * inv_count);
 }
 __global__ __launch_bounds__(256) void t_norm_bwd_apply4(TNorm a, const float* z, const float* dy, const float* S1, const float* S2, float inv_count,
                                                          float* dz) {
@@ -1013,7 +1021,7 @@ __global__ __launch_bounds__(256) void t_norm_bwd_apply4(TNorm a, const float* z
         const float xh = (zv[k] - q.mu[k]) * q.rs[k], v = xh * q.ga[k] + q.be[k];
         const float u = v * (1.0f + q.sc[k]) + q.sh[k];
         const float dbn = dv[k] * t_keep_rk(a, rk, e + k) * t_dact(u, a.act) * (1.0f + q.sc[k]);
-        r[k] = q.rs[k] * (q.ga[k] * dbn - (q.s1[k] + xh * q.s2[k]) * inv_count);
+        r[k] = q.rs[k] * (t_mul_rounded(q.ga[k], dbn) - (q.s1[k] + xh * q.s2[k]) * inv_count);
     }
     *(float4*)(dz + i) = make_float4(r[0], r[1], r[2], r[3]);
 }

@@ -1233,15 +1233,19 @@ RT* rn_walk(Ctx& X, const dyf_net_config& c, const RNames& R, int nb, int H, int
 
 namespace dyf {
 
-// fp32 training copy of a ResNet-UNet's parameters (called by dyf_load_weights / dyf_train_load_weights for arch unet.Unet)
-dyf_status rn_train_store_weights(dyf_engine* e, int which, std::map<std::string, TensorView>& sd) {
-    if (!e->train) e->train = new TrainState();
-    if (!e->train->rnet[which]) e->train->rnet[which] = new RTNet();
-    RTNet& t = *e->train->rnet[which];
-    TK(hipDeviceSynchronize());
-    tfree(e, t.owned);
-    t.P.clear();
-    t.ready = false;
+// (co, ci, taps) -> [co][tap][ci] (a) and, when asked for, [tap][ci][co] (at): the training layouts of a conv weight and of its gradient
+static void rn_pack_conv(const float* host, int cout, int cin, int taps, std::vector<float>& a, std::vector<float>* at) {
+    for (int co = 0; co < cout; ++co)
+        for (int ci = 0; ci < cin; ++ci)
+            for (int tp = 0; tp < taps; ++tp) {
+                const float x = host[((size_t)co * cin + ci) * taps + tp];
+                a[((size_t)co * taps + tp) * cin + ci] = x;
+                if (at) (*at)[((size_t)tp * cin + ci) * cout + co] = x;
+            }
+}
+
+// every tensor of `sd` into `t` in its training layout, and one zeroed gradient arena behind them (the loader's and the op seam's)
+static dyf_status rn_fill_params(dyf_engine* e, RTNet& t, std::map<std::string, TensorView>& sd) {
     for (auto& kv : sd) {
         const TensorView& v = kv.second;
         RParam p;
@@ -1251,13 +1255,7 @@ dyf_status rn_train_store_weights(dyf_engine* e, int which, std::map<std::string
         if (is_conv) {  // (co, ci, kh, kw) -> [co][tap][ci]
             p.conv = 1; p.cout = (int)v.shape[0]; p.cin = (int)v.shape[1]; p.taps = (int)(v.shape[2] * v.shape[3]);
             std::vector<float> a(host.size()), at(host.size());
-            for (int co = 0; co < p.cout; ++co)
-                for (int ci = 0; ci < p.cin; ++ci)
-                    for (int tp = 0; tp < p.taps; ++tp) {
-                        const float x = host[((size_t)co * p.cin + ci) * p.taps + tp];
-                        a[((size_t)co * p.taps + tp) * p.cin + ci] = x;
-                        at[((size_t)tp * p.cin + ci) * p.cout + co] = x;
-                    }
+            rn_pack_conv(host.data(), p.cout, p.cin, p.taps, a, &at);
             dyf_status s = tupload(e, t.owned, &p.w, a);
             if (s == DYF_OK) s = tupload(e, t.owned, &p.wt, at);
             if (s != DYF_OK) return s;
@@ -1278,6 +1276,20 @@ dyf_status rn_train_store_weights(dyf_engine* e, int which, std::map<std::string
         kv.second.g = t.g_arena + off;
         off += (kv.second.n + 63) / 64 * 64;
     }
+    return DYF_OK;
+}
+
+// fp32 training copy of a ResNet-UNet's parameters (called by dyf_load_weights / dyf_train_load_weights for arch unet.Unet)
+dyf_status rn_train_store_weights(dyf_engine* e, int which, std::map<std::string, TensorView>& sd) {
+    if (!e->train) e->train = new TrainState();
+    if (!e->train->rnet[which]) e->train->rnet[which] = new RTNet();
+    RTNet& t = *e->train->rnet[which];
+    TK(hipDeviceSynchronize());
+    tfree(e, t.owned);
+    t.P.clear();
+    t.ready = false;
+    dyf_status s = rn_fill_params(e, t, sd);
+    if (s != DYF_OK) return s;
     TK(hipDeviceSynchronize());
     t.ready = true;
     return DYF_OK;
@@ -1440,6 +1452,14 @@ dyf_status rn_f32_forward(dyf_engine* e, int which, const Source* srcs, int nsrc
     return DYF_OK;
 }
 
+// the backward of a recorded forward: its closures in reverse (the training step's and the op seam's)
+static dyf_status rn_run_adjoints(RTape& T, RCtx& X) {
+    dyf_status r = DYF_OK;
+    for (auto it = T.back.rbegin(); it != T.back.rend() && r == DYF_OK; ++it) r = (*it)();
+    if (r == DYF_OK && X.err != DYF_OK) r = X.err;
+    return r;
+}
+
 dyf_status rn_train_backward(dyf_engine* e, int slot, const float* dout_dev, float* dinputs_dev, int param_grads, hipStream_t st) {
     RTape* tp = e->train ? e->train->rtape[slot] : nullptr;
     if (!tp || tp->net < 0 || !tp->out) return fail(e, DYF_ERR_STATE, "no forward recorded in this tape slot");
@@ -1457,9 +1477,7 @@ dyf_status rn_train_backward(dyf_engine* e, int slot, const float* dout_dev, flo
     for (auto& t : T.ts) t.g = nullptr;
     hipLaunchKernelGGL(t_nchw_to_nhwc, dim3(nblk((long long)T.nb * hw * c.out_channels)), dim3(256), 0, st, dout_dev, T.nb, hw, c.out_channels, X.grad(T.out));
     if (dinputs_dev) (void)X.grad(T.x_in);  // request the gradient of the network input
-    dyf_status r = DYF_OK;
-    for (auto it = T.back.rbegin(); it != T.back.rend() && r == DYF_OK; ++it) r = (*it)();
-    if (r == DYF_OK && X.err != DYF_OK) r = X.err;
+    dyf_status r = rn_run_adjoints(T, X);
     if (r == DYF_OK && dinputs_dev)
         hipLaunchKernelGGL(t_nhwc_to_nchw, dim3(nblk((long long)T.nb * hw * c.in_channels)), dim3(256), 0, st, T.x_in->g, T.nb, hw, n.cin_total, c.cond_channels,
                            c.in_channels, dinputs_dev);
@@ -1468,6 +1486,22 @@ dyf_status rn_train_backward(dyf_engine* e, int slot, const float* dout_dev, flo
     tfree(e, tmp);
     if (r != DYF_OK) return fail(e, r, "training backward failed");
     if (se != hipSuccess) return fail(e, DYF_ERR_HIP, std::string("training backward: ") + hipGetErrorString(se));
+    return DYF_OK;
+}
+
+// one parameter's gradient in its PyTorch layout (conv: (co, ci, kh, kw)) to `out`, on the device or the host
+static dyf_status rn_export_param(dyf_engine* e, std::vector<void*>& tmp, const RParam& p, float* out, bool dev) {
+    const float* src = p.g;
+    if (p.conv) {
+        float* un = nullptr;
+        dyf_status s = talloc(e, tmp, &un, p.n, false);
+        if (s != DYF_OK) return s;
+        hipLaunchKernelGGL(t_unpack_conv_r, dim3(nblk((long long)p.n)), dim3(256), 0, 0, p.g, p.cout, p.cin, p.taps, dev ? out : un);
+        src = un;
+        if (dev) return DYF_OK;
+    }
+    if (dev) TK(hipMemcpy(out, src, p.n * sizeof(float), hipMemcpyDeviceToDevice));
+    else { TK(hipDeviceSynchronize()); TK(hipMemcpy(out, src, p.n * sizeof(float), hipMemcpyDeviceToHost)); }
     return DYF_OK;
 }
 
@@ -1480,22 +1514,163 @@ dyf_status rn_train_export(dyf_engine* e, int which, int n_tensors, const char* 
     for (int i = 0; i < n_tensors; ++i) {
         auto it = t->P.find(names[i]);
         if (it == t->P.end()) { tfree(e, tmp); return fail(e, DYF_ERR_INVALID_ARGUMENT, std::string("no gradient for '") + names[i] + "'"); }
-        const RParam& p = it->second;
-        const float* src = p.g;
-        float* un = nullptr;
-        if (p.conv) {
-            dyf_status s = talloc(e, tmp, &un, p.n, false);
-            if (s != DYF_OK) { tfree(e, tmp); return s; }
-            hipLaunchKernelGGL(t_unpack_conv_r, dim3(nblk((long long)p.n)), dim3(256), 0, 0, p.g, p.cout, p.cin, p.taps, dev ? out[i] : un);
-            src = un;
-            if (dev) continue;
-        }
-        if (dev) TK(hipMemcpy(out[i], src, p.n * sizeof(float), hipMemcpyDeviceToDevice));
-        else { TK(hipDeviceSynchronize()); TK(hipMemcpy(out[i], src, p.n * sizeof(float), hipMemcpyDeviceToHost)); }
+        dyf_status s = rn_export_param(e, tmp, it->second, out[i], dev);
+        if (s != DYF_OK) { tfree(e, tmp); return s; }
     }
     TK(hipDeviceSynchronize());
     tfree(e, tmp);
     return DYF_OK;
+}
+
+// test seam (dyf_op_train_f32): ONE op of the recorded forward and its adjoint.  The op is the RCtx member function itself, recording on
+// a scratch tape over a scratch parameter set; the backward is rn_run_adjoints, the loop rn_train_backward runs -- no launch is restated
+// here.  Parameters arrive in PyTorch layouts on the host and go through rn_fill_params; the gradient buffers start from the caller's
+// contents (conv weights packed as the weights are) and leave through rn_export_param.
+dyf_status f32_op_train(dyf_engine* e, const dyf_train_op* dp, const float* const* inputs, const float* const* params, const float* dout,
+                        float* y_out, float* const* dinputs, float* const* dparams, hipStream_t st) {
+    const dyf_train_op& d = *dp;
+    auto refuse = [&](dyf_status s, const char* what) { return fail(e, s, std::string("dyf_op_train_f32: ") + what); };
+    if (d.nb < 1 || d.h < 1 || d.w < 1 || d.c < 1) return refuse(DYF_ERR_INVALID_ARGUMENT, "nb, h, w and c must be positive");
+    if (!(d.p >= 0.0f && d.p < 1.0f)) return refuse(DYF_ERR_INVALID_ARGUMENT, "p must be in [0, 1)");
+    const bool has_p = d.op == DYF_TOP_GN_ACT || d.op == DYF_TOP_LAYERNORM || d.op == DYF_TOP_ATTENTION || d.op == DYF_TOP_DROPOUT;
+    const bool has_c2 = d.op == DYF_TOP_CONV || d.op == DYF_TOP_LINEAR || d.op == DYF_TOP_CAT;
+    const int flags_ok = d.op == DYF_TOP_CONV ? (DYF_TOP_WS | DYF_TOP_BIAS) : d.op == DYF_TOP_GN_ACT ? DYF_TOP_FILM : d.op == DYF_TOP_LINEAR ? DYF_TOP_PRE
+                         : d.op == DYF_TOP_ADD ? DYF_TOP_SAME : 0;
+    if (d.op < DYF_TOP_CONV || d.op > DYF_TOP_UP2_NEAREST) return refuse(DYF_ERR_INVALID_ARGUMENT, "unknown op");
+    if (d.flags & ~flags_ok) return refuse(DYF_ERR_INVALID_ARGUMENT, "a flag this op does not take");
+    if (d.p > 0.0f && !has_p) return refuse(DYF_ERR_INVALID_ARGUMENT, "this op has no dropout");
+    if (has_c2 ? d.c2 < 1 : d.c2 != 0) return refuse(DYF_ERR_INVALID_ARGUMENT, "c2 must be positive for conv / linear / cat and 0 otherwise");
+    if (d.op == DYF_TOP_CONV ? (d.k < 1 || d.stride < 1 || d.pad < 0 || d.h + 2 * d.pad < d.k || d.w + 2 * d.pad < d.k) : (d.k != 0 || d.stride != 0 || d.pad != 0))
+        return refuse(DYF_ERR_INVALID_ARGUMENT, "k / stride / pad: a conv geometry with at least one output pixel, 0 for every other op");
+    if (d.op == DYF_TOP_GN_ACT ? (d.groups < 1 || d.c % d.groups != 0) : d.groups != 0)
+        return refuse(DYF_ERR_INVALID_ARGUMENT, "groups must divide c for gn_act and be 0 otherwise");
+    if ((d.op == DYF_TOP_LINEAR || d.op == DYF_TOP_LEARNED_SINU) && (d.h != 1 || d.w != 1)) return refuse(DYF_ERR_INVALID_ARGUMENT, "linear / learned_sinu take rows: h = w = 1");
+    const long long hw = (long long)d.h * d.w, px = hw * d.nb;
+    const long long cmax = std::max<long long>(std::max(d.c, d.c2), (d.op == DYF_TOP_LINATTN || d.op == DYF_TOP_ATTENTION) ? 3 * RHID : 0);
+    if (hw * cmax * 4 >= (1ll << 32) || px * cmax * 4 >= (1ll << 31)) return refuse(DYF_ERR_UNSUPPORTED, "tensor too large for the op seam (2^31 elements)");
+    if ((d.op == DYF_TOP_LINATTN || d.op == DYF_TOP_ATTENTION) && d.c != 3 * RHID) return refuse(DYF_ERR_INVALID_ARGUMENT, "the attention cores take qkv of 384 channels");
+    if (d.op == DYF_TOP_ATTENTION && hw > AT_KEEP_P_MAX) return refuse(DYF_ERR_UNSUPPORTED, "the Attention core keeps its (tokens x tokens) probabilities -- at most 4096 tokens");
+    if (d.p > 0.0f && d.nb > 2 * e->cfg.max_batch) return refuse(DYF_ERR_INVALID_ARGUMENT, "more rows than the engine's row-key table (2 max_batch)");
+
+    // inputs (floats each) and parameters (name, PyTorch shape) of the op
+    struct PS { std::string name; std::vector<int64_t> shape; };
+    std::vector<PS> ps;
+    std::vector<size_t> in_n;
+    const size_t xn = (size_t)px * d.c;
+    switch (d.op) {
+    case DYF_TOP_CONV:
+        in_n = {xn};
+        ps.push_back({"op.weight", {d.c2, d.c, d.k, d.k}});
+        if (d.flags & DYF_TOP_BIAS) ps.push_back({"op.bias", {d.c2}});
+        break;
+    case DYF_TOP_GN_ACT:
+        in_n = {xn};
+        if (d.flags & DYF_TOP_FILM) in_n.push_back((size_t)d.nb * 2 * d.c);
+        ps = {{"op.weight", {d.c}}, {"op.bias", {d.c}}};
+        break;
+    case DYF_TOP_LAYERNORM: in_n = {xn}; ps = {{"op.norm.g", {1, d.c, 1, 1}}}; break;
+    case DYF_TOP_LINEAR: in_n = {xn}; ps = {{"op.weight", {d.c2, d.c}}, {"op.bias", {d.c2}}}; break;
+    case DYF_TOP_LEARNED_SINU: in_n = {(size_t)d.nb}; ps = {{"time_emb_mlp.0.weights", {d.c}}}; break;
+    case DYF_TOP_ADD: in_n = {xn}; if (!(d.flags & DYF_TOP_SAME)) in_n.push_back(xn); break;
+    case DYF_TOP_CAT: in_n = {xn, (size_t)px * d.c2}; break;
+    default: in_n = {xn}; break;
+    }
+    for (size_t i = 0; i < in_n.size(); ++i)
+        if (!inputs[i]) return refuse(DYF_ERR_INVALID_ARGUMENT, "an input pointer is null");
+    for (size_t i = 0; i < ps.size(); ++i)
+        if (!params || !dparams || !params[i] || !dparams[i]) return refuse(DYF_ERR_INVALID_ARGUMENT, "a parameter or parameter-gradient pointer is null");
+
+    if (!e->train) e->train = new TrainState();
+    e->train->stream = st;
+    const TrainPrecisionScope precision(e->train_precision);
+    dyf_net_config c = e->net[0].cfg;
+    c.groups = d.groups;
+    RTNet W;
+    RTape T;
+    std::vector<void*> tmp;
+    auto done = [&](dyf_status s) {  // everything back to the engine's pool, whatever happened
+        const hipError_t se = hipDeviceSynchronize();
+        for (auto& t : T.ts) t.g = nullptr;
+        T.back.clear();
+        tfree(e, tmp);
+        tfree(e, T.owned);
+        tfree(e, W.owned);
+        if (s == DYF_OK && se != hipSuccess) return fail(e, DYF_ERR_HIP, std::string("dyf_op_train_f32: ") + hipGetErrorString(se));
+        return s;
+    };
+#define OPK(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) return done(fail(e, DYF_ERR_HIP, std::string("dyf_op_train_f32: " #expr ": ") + hipGetErrorString(_e))); } while (0)
+    {
+        std::map<std::string, TensorView> sd;
+        for (size_t i = 0; i < ps.size(); ++i) sd[ps[i].name] = TensorView{params[i], ps[i].shape};
+        dyf_status s = rn_fill_params(e, W, sd);
+        if (s != DYF_OK) return done(s);
+        std::vector<std::vector<float>> g0(ps.size());  // the caller's gradient contents, in the gradient buffers' layout
+        for (size_t i = 0; i < ps.size(); ++i) {
+            const RParam& p = W.P.at(ps[i].name);
+            g0[i].assign(dparams[i], dparams[i] + p.n);
+            if (p.conv) {
+                std::vector<float> a(p.n);
+                rn_pack_conv(g0[i].data(), p.cout, p.cin, p.taps, a, nullptr);
+                g0[i].swap(a);
+            }
+            OPK(hipMemcpyAsync(p.g, g0[i].data(), p.n * sizeof(float), hipMemcpyHostToDevice, st));
+        }
+        OPK(hipStreamSynchronize(st));
+    }
+    bool drop_on = false;
+    if (d.p > 0.0f) {  // a new forward of the generator, site 0 (as f32_op_attention)
+        OPK(launch_rng_begin_forward(e->rng_state, e->row_keys, d.nb, d.nb, st));
+        T.row_keys = e->row_keys;
+        drop_on = true;
+    }
+    RCtx X{e, W, T, c, st, d.nb, drop_on};
+    X.mem = FwdMem{e, &T.owned, st};
+    X.tmp = &tmp;
+    RT* in[2] = {nullptr, nullptr};
+    if (d.op != DYF_TOP_LEARNED_SINU)
+        for (size_t i = 0; i < in_n.size(); ++i) {
+            in[i] = X.make(in_n[i]);
+            if (X.err != DYF_OK) return done(refuse(X.err, "allocation failed"));
+            OPK(hipMemcpyAsync(in[i]->p, inputs[i], in_n[i] * sizeof(float), hipMemcpyDeviceToDevice, st));
+        }
+    RT* y = nullptr;
+    switch (d.op) {
+    case DYF_TOP_CONV: y = X.conv(in[0], d.h, d.w, d.c, d.c2, d.k, d.stride, d.pad, "op", (d.flags & DYF_TOP_BIAS) != 0, (d.flags & DYF_TOP_WS) != 0); break;
+    case DYF_TOP_GN_ACT: y = X.gn_act(in[0], (int)hw, d.c, "op", in[1], d.p); break;
+    case DYF_TOP_LAYERNORM: y = X.layernorm(in[0], (int)hw, d.c, "op.norm.g", d.p); break;
+    case DYF_TOP_LINATTN: y = X.linattn(in[0], (int)hw); break;
+    case DYF_TOP_ATTENTION: y = X.attention(in[0], (int)hw, d.p); break;
+    case DYF_TOP_LINEAR: y = X.linear(in[0], d.nb, d.c, d.c2, "op", (d.flags & DYF_TOP_PRE) ? 1 : 0); break;
+    case DYF_TOP_LEARNED_SINU: y = X.learned_sinu(inputs[0], d.c); break;
+    case DYF_TOP_DROPOUT: y = X.dropout(in[0], hw * d.c, d.p); break;
+    case DYF_TOP_GELU: y = X.gelu(in[0]); break;
+    case DYF_TOP_ADD: y = X.add(in[0], (d.flags & DYF_TOP_SAME) ? in[0] : in[1]); break;
+    case DYF_TOP_CAT: y = X.cat(in[0], d.c, in[1], d.c2, px); break;
+    default: y = X.up2_nearest(in[0], d.h, d.w, d.c); break;
+    }
+    if (X.err != DYF_OK || !y) return done(refuse(X.err != DYF_OK ? X.err : DYF_ERR_HIP, "forward: allocation / launch failed"));
+    OPK(hipGetLastError());
+    OPK(hipMemcpyAsync(y_out, y->p, y->n * sizeof(float), hipMemcpyDeviceToDevice, st));
+    // the backward, as rn_train_backward starts it: the output's gradient, then the closures in reverse
+    for (auto& t : T.ts) t.g = nullptr;
+    float* gy = X.grad(y);
+    if (X.err != DYF_OK) return done(refuse(X.err, "allocation failed"));
+    OPK(hipMemcpyAsync(gy, dout, y->n * sizeof(float), hipMemcpyDeviceToDevice, st));
+    dyf_status r = rn_run_adjoints(T, X);
+    if (r != DYF_OK) return done(refuse(r, "backward failed"));
+    OPK(hipGetLastError());
+    for (size_t i = 0; i < in_n.size() && dinputs; ++i) {
+        if (!dinputs[i] || !in[i]) continue;
+        if (in[i]->g) OPK(hipMemcpyAsync(dinputs[i], in[i]->g, in_n[i] * sizeof(float), hipMemcpyDeviceToDevice, st));
+        else OPK(hipMemsetAsync(dinputs[i], 0, in_n[i] * sizeof(float), st));
+    }
+    OPK(hipStreamSynchronize(st));
+    for (size_t i = 0; i < ps.size(); ++i) {
+        dyf_status s = rn_export_param(e, tmp, W.P.at(ps[i].name), dparams[i], false);
+        if (s != DYF_OK) return done(s);
+    }
+#undef OPK
+    return done(DYF_OK);
 }
 
 }  // namespace dyf

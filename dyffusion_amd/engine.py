@@ -695,6 +695,87 @@ class HipEngine:
                                                    int(form), y.data_ptr(), self._stream()))
         return y
 
+    def op_train(self, op: str, inputs, params=(), dout: Optional[torch.Tensor] = None, grads_in=None, *, k: int = 0, stride: int = 0,
+                 pad: int = 0, groups: int = 0, p: float = 0.0, ws: bool = False, pre: bool = False) -> Dict[str, object]:
+        """Test seam (dyf_op_train_f32): ONE recorded op of the ResNet-UNet training step and its adjoint, through the training step's
+        own launch code.  `inputs`: fp32 tensors on the device, activations NHWC (nb, h, w, c) -- rows (nb, c) for "linear", times (nb,)
+        for "learned_sinu"; "add" with one input is add(a, a).  `params`: fp32 tensors in PyTorch layouts, in the header's order (conv:
+        weight (c2, c, k, k) [, bias]; gn_act: weight, bias -- a second input is the FiLM (nb, 2c); layernorm: g; linear: weight (c2, c),
+        bias; learned_sinu: weights).  `dout`: gradient of the output (its shape).  `grads_in`: what the parameter-gradient buffers hold
+        before the op runs (default zeros): the kernels accumulate.  Returns {"y", "dinputs": [...], "dparams": [...]} (dparams on the
+        CPU).  p > 0 draws from the engine's generator: a new forward, site 0, rows row offset .. + nb - 1."""
+        ins = [_f32c(t, "input") for t in inputs]
+        x = ins[0]
+        nb = x.shape[0]
+        if op in ("linear", "learned_sinu"):
+            h = w = 1
+            c = x.shape[1] if op == "linear" else params[0].numel()
+        else:
+            if x.dim() != 4:
+                raise ValueError(f"{op}: inputs are NHWC (nb, h, w, c), got {tuple(x.shape)}")
+            _, h, w, c = x.shape
+        c2, flags = 0, 0
+        ps = [t.detach().to("cpu", torch.float32).contiguous() for t in params]
+        if op == "conv":
+            c2 = ps[0].shape[0]
+            if tuple(ps[0].shape) != (c2, c, k, k):
+                raise ValueError(f"conv weight must be (c2, {c}, {k}, {k}), got {tuple(ps[0].shape)}")
+            flags = (L.TOP_WS if ws else 0) | (L.TOP_BIAS if len(ps) > 1 else 0)
+            out_shape = (nb, (h + 2 * pad - k) // stride + 1, (w + 2 * pad - k) // stride + 1, c2)
+        elif op == "gn_act":
+            flags = L.TOP_FILM if len(ins) > 1 else 0
+            out_shape = tuple(x.shape)
+        elif op in ("linattn", "attention"):
+            out_shape = (nb, h, w, 128)
+        elif op == "linear":
+            c2, flags = ps[0].shape[0], (L.TOP_PRE if pre else 0)
+            out_shape = (nb, c2)
+        elif op == "learned_sinu":
+            out_shape = (nb, 2 * c + 1)
+        elif op == "add":
+            flags = L.TOP_SAME if len(ins) == 1 else 0
+            out_shape = tuple(x.shape)
+        elif op == "cat":
+            c2 = ins[1].shape[3]
+            out_shape = (nb, h, w, c + c2)
+        elif op == "up2_nearest":
+            out_shape = (nb, 2 * h, 2 * w, c)
+        elif op in ("layernorm", "dropout", "gelu"):
+            out_shape = tuple(x.shape)
+        else:
+            raise ValueError(f"unknown training op {op!r}")
+        want_in = {"gn_act": (1, 2), "add": (1, 2), "cat": (2, 2)}.get(op, (1, 1))
+        want_p = {"conv": (1, 2), "gn_act": (2, 2), "layernorm": (1, 1), "linear": (2, 2), "learned_sinu": (1, 1)}.get(op, (0, 0))
+        if not (want_in[0] <= len(ins) <= want_in[1]) or not (want_p[0] <= len(ps) <= want_p[1]):
+            raise ValueError(f"{op}: {len(ins)} inputs and {len(ps)} parameters")
+        expect = {"conv": [(nb, h, w, c)], "gn_act": [(nb, h, w, c), (nb, 2 * c)], "add": [tuple(x.shape)] * 2, "cat": [(nb, h, w, c), (nb, h, w, c2)],
+                  "linear": [(nb, c)], "learned_sinu": [(nb,)]}.get(op, [tuple(x.shape)])
+        for t, sh in zip(ins, expect):
+            if tuple(t.shape) != sh:
+                raise ValueError(f"{op}: an input has shape {tuple(t.shape)}, expected {sh}")
+        pshape = {"conv": [(c2, c, k, k), (c2,)], "gn_act": [(c,), (c,)], "layernorm": [(1, c, 1, 1)], "linear": [(c2, c), (c2,)],
+                  "learned_sinu": [(c,)]}.get(op, [])
+        for t, sh in zip(ps, pshape):
+            if t.numel() != int(np.prod(sh)):
+                raise ValueError(f"{op}: a parameter has shape {tuple(t.shape)}, expected {sh}")
+        if (op in ("linattn", "attention")) and c != 384:
+            raise ValueError("the attention cores take qkv of 384 channels")
+        dout = _f32c(dout, "dout")
+        if tuple(dout.shape) != out_shape:  # the C ABI reads / writes raw pointers
+            raise ValueError(f"dout must have the output's shape {out_shape}, got {tuple(dout.shape)}")
+        gs = [torch.zeros_like(t) for t in ps] if grads_in is None else [g.detach().to("cpu", torch.float32).contiguous().clone() for g in grads_in]
+        if [g.shape for g in gs] != [t.shape for t in ps]:
+            raise ValueError("grads_in must match params")
+        y = torch.empty(out_shape, dtype=torch.float32, device=x.device)
+        dins = [torch.empty_like(t) for t in ins]
+        desc = L.TrainOp(L.TRAIN_OPS[op], nb, h, w, c, c2, k, stride, pad, groups, flags, float(p))
+        arr = lambda ts: (C.c_void_p * max(len(ts), 1))(*[t.data_ptr() for t in ts])
+        self._check(self._lib.dyf_op_train_f32(self._h, C.byref(desc), arr(ins), arr(ps), dout.data_ptr(), y.data_ptr(), arr(dins), arr(gs),
+                                               self._stream()))
+        if op == "learned_sinu":
+            dins = [None]  # a time value has no gradient
+        return {"y": y, "dinputs": dins, "dparams": gs}
+
     def op_upconv2d(self, x_nhwc_bf16: torch.Tensor, weight: torch.Tensor, scale: Optional[torch.Tensor] = None,
                     shift: Optional[torch.Tensor] = None, act: int = 0) -> torch.Tensor:
         """Test seam: fused Upsample(x2, bilinear) + Conv2d(3x3, pad 1).  x (N,H,W,Cin) bf16 -> (N,2H,2W,Cout) bf16."""

@@ -126,6 +126,46 @@ dyf_status dyf_op_attention_f32(dyf_engine* engine, const float* qkv_dev, int32_
 dyf_status dyf_train_conv_check(dyf_engine* engine, int32_t kind, int32_t n, int32_t h, int32_t w, int32_t cin, int32_t cout,
                                 int32_t k, int32_t s, int32_t p, uint32_t seed, float* out_host);
 
+/* ONE recorded op of the ResNet-UNet training step (csrc/train_resnet.inc RCtx) and its adjoint, for float64 parity tests of the
+ * fp32 kernels.  The seam calls the RCtx member function itself on a scratch tape and then runs the recorded closures in reverse with
+ * the loop dyf_train_backward runs, so grid sizes, chunk counts and kernel choices are the training step's own.  Convs take their
+ * operand precision from dyf_train_set_precision like the step does.  Tensors are fp32, activations NHWC.
+ *   inputs_dev   device pointers of the op's inputs, dout_dev the gradient of its output, y_dev receives the output, dinputs_dev[i]
+ *                the gradient of input i (entries may be NULL; a time input has no gradient)
+ *   params_host  host pointers of the parameters in PyTorch layouts (packed by the code dyf_load_weights packs the training copy with)
+ *   dparams_host host pointers, IN/OUT: the gradient buffers start from these contents and the kernels accumulate into them (as the
+ *                two forecaster passes of a step meet in one buffer); conv weights in PyTorch layout through dyf_train_export's unpack
+ * op (inputs; parameters), hw = h * w:
+ *   CONV        x (nb,h,w,c); weight (c2,c,k,k) [, bias (c2) with DYF_TOP_BIAS] -> (nb,ho,wo,c2); DYF_TOP_WS = weight-standardised
+ *   GN_ACT      z (nb,hw,c) [, ss (nb,2c) = FiLM (scale | shift) with DYF_TOP_FILM]; weight (c), bias (c); `groups`; dropout p
+ *   LAYERNORM   x (nb,hw,c); g (1,c,1,1); dropout p
+ *   LINATTN     qkv (nb,hw,384) -> (nb,hw,128)
+ *   ATTENTION   qkv (nb,hw,384) -> (nb,hw,128), the form that keeps its probabilities (hw <= 4096); dropout p on the probabilities
+ *   LINEAR      x (nb,c); weight (c2,c), bias (c2) -> (nb,c2); DYF_TOP_PRE = SiLU on the input first
+ *   LEARNED_SINU time (nb); weights (c) -> (nb, 2c + 1)
+ *   DROPOUT     x (nb,h,w,c); p          GELU  x (nb,h,w,c)
+ *   ADD         a, b (nb,h,w,c); DYF_TOP_SAME = add(a, a): one input, one gradient
+ *   CAT         a (nb,h,w,c), b (nb,h,w,c2) -> (nb,h,w,c+c2)          UP2_NEAREST x (nb,h,w,c) -> (nb,2h,2w,c)
+ * p > 0 draws from the engine's generator armed as dyf_op_attention_f32 arms it: a new forward (dyf_seed resets the counter), site 0,
+ * global rows row offset .. + nb - 1, nb <= 2 max_batch; element index = the NHWC index inside the row ((h * N + i) * N + j for the
+ * Attention probabilities).  Fields an op does not use must be 0.  What the descriptor cannot express is refused
+ * (DYF_ERR_INVALID_ARGUMENT / DYF_ERR_UNSUPPORTED), never truncated.  Synchronises; everything allocated goes back to the engine. */
+typedef enum dyf_train_op_kind {
+    DYF_TOP_CONV = 0, DYF_TOP_GN_ACT = 1, DYF_TOP_LAYERNORM = 2, DYF_TOP_LINATTN = 3, DYF_TOP_ATTENTION = 4, DYF_TOP_LINEAR = 5,
+    DYF_TOP_LEARNED_SINU = 6, DYF_TOP_DROPOUT = 7, DYF_TOP_GELU = 8, DYF_TOP_ADD = 9, DYF_TOP_CAT = 10, DYF_TOP_UP2_NEAREST = 11
+} dyf_train_op_kind;
+#define DYF_TOP_WS 1
+#define DYF_TOP_BIAS 2
+#define DYF_TOP_PRE 4
+#define DYF_TOP_FILM 8
+#define DYF_TOP_SAME 16
+typedef struct dyf_train_op {
+    int32_t op, nb, h, w, c, c2, k, stride, pad, groups, flags;
+    float p;
+} dyf_train_op;
+dyf_status dyf_op_train_f32(dyf_engine* engine, const dyf_train_op* desc, const float* const* inputs_dev, const float* const* params_host,
+                            const float* dout_dev, float* y_dev, float* const* dinputs_dev, float* const* dparams_host, void* stream);
+
 /* Read back the output of UNetBlock `layer` (0..11: encoder then decoder blocks) of the most recent unet_simple forward
  * as fp32 NCHW (NB, cout, h, w) -- per-layer parity analysis against the oracle's taps (oracle/nets.py `taps=`).  The last
  * decoder block is returned dense; positions its sparse-column form did not compute are NaN. */
