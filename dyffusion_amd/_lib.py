@@ -86,13 +86,14 @@ TRAIN_BATCH_STATS, TRAIN_DROPOUT = 1, 2
 
 
 class TrainOp(C.Structure):
-    """dyf_train_op (include/dyffusion_hip_testing.h): one recorded op of the ResNet-UNet training step for dyf_op_train_f32."""
+    """dyf_train_op (include/dyffusion_hip_testing.h): one recorded op of the training step for dyf_op_train_f32."""
     _fields_ = [(k, C.c_int32) for k in ("op", "nb", "h", "w", "c", "c2", "k", "stride", "pad", "groups", "flags")] + [("p", C.c_float)]
 
 
 TRAIN_OPS = {"conv": 0, "gn_act": 1, "layernorm": 2, "linattn": 3, "attention": 4, "linear": 5, "learned_sinu": 6, "dropout": 7,
-             "gelu": 8, "add": 9, "cat": 10, "up2_nearest": 11}
+             "gelu": 8, "add": 9, "cat": 10, "up2_nearest": 11, "norm_act": 12, "up2_bilinear": 13, "resize": 14, "convt": 15}
 TOP_WS, TOP_BIAS, TOP_PRE, TOP_FILM, TOP_SAME = 1, 2, 4, 8, 16
+TOP_RUNNING, TOP_MASK, TOP_LEAKY, TOP_RELU, TOP_NEAREST, TOP_GRAD_IN = 32, 64, 128, 256, 512, 1024
 
 # every symbol include/dyffusion_hip.h and include/dyffusion_hip_testing.h declare: (name, restype, argtypes)
 _P = C.c_void_p

@@ -654,7 +654,7 @@ static dyf_status load_weights_one(dyf_engine* e, int32_t which, int32_t n_tenso
         n.ntables = 0;
         e->plan.set = false;
         if (e->is_group_child) return DYF_OK;  // row groups only sample: no fp32 training copy, no gradient buffers
-        return rn_train_store_weights(e, which, sd);  // fp32 copy in the training layout (train_resnet.inc)
+        return train_store_params(e, which, sd);  // fp32 copy in the training layout (train_resnet.inc)
     }
     std::string missing;
     auto get = [&](const std::string& key, std::vector<int64_t> want) -> const TensorView* {
@@ -861,7 +861,7 @@ static dyf_status load_weights_one(dyf_engine* e, int32_t which, int32_t n_tenso
     n.ntables = 0;
     e->plan.set = false;  // coefficient tables depend on the weights
     if (e->is_group_child) return DYF_OK;
-    return train_store_weights(e, which, sd);  // fp32 copy in the training layout (train.hip)
+    return train_store_params(e, which, sd);  // fp32 copy in the training layout (train_resnet.inc)
 }
 
 dyf_status dyf_net_flops(const dyf_engine* e, int32_t which, double* flops) {

@@ -172,7 +172,7 @@ struct dyf_engine {
     size_t s_log_floats = 0;
     int log_nb = 0;                  // batch rows of the logged call
     std::vector<uint8_t> log_has_cur;  // per step: slot 2 (x_interpolated_s) was defined at that step
-    dyf::TrainState* train = nullptr;  // training path (arch unet_simple), created by the first dyf_load_weights
+    dyf::TrainState* train = nullptr;  // fp32 path (training step, fp32 sampling; arch unet_simple and unet.Unet), created by the first dyf_load_weights
     bool last_dec5_sparse = false;  // the most recent unet_simple forward stored dec5 in the compact sparse-column layout
     bool poison_dec5 = false;       // DYF_POISON_DEC5=1 (test hook, read once at create): NaN-fill dec5's output before its conv
     // GroupNorm fused into the producing conv (gn_fused.h): host-visible error word (pinned, mapped) a timed-out granule sweep raises,
@@ -361,8 +361,7 @@ struct FwdOpts {
 // ---- training step (train.hip)
 struct dyf_train_op;  // include/dyffusion_hip_testing.h
 namespace dyf {
-dyf_status train_store_weights(dyf_engine* e, int which, std::map<std::string, TensorView>& sd);
-dyf_status rn_train_store_weights(dyf_engine* e, int which, std::map<std::string, TensorView>& sd);  // arch unet.Unet
+dyf_status train_store_params(dyf_engine* e, int which, std::map<std::string, TensorView>& sd);  // arch unet_simple and unet.Unet
 void train_destroy(dyf_engine* e);
 // fp32 sampling forward (train.hip): net_forward's signature; the layer walk and the kernels of the recorded training forward on the
 // engine's bump arena -- no allocation, no synchronisation, bitwise repeatable, capturable
@@ -372,7 +371,7 @@ dyf_status f32_prepare(dyf_engine* e);  // first switch to 32 bits: arena + spli
 void f32_destroy(dyf_engine* e);
 // the fp32 Attention core alone (dyf_op_attention_f32): form 0 = the probability-keeping kernel, 1 = the streaming kernel; synchronises
 dyf_status f32_op_attention(dyf_engine* e, const float* qkv, int nb, int N, float p, const uint8_t* mask, int form, float* out, hipStream_t st);
-// one recorded op of the ResNet-UNet training step and its adjoint (dyf_op_train_f32, include/dyffusion_hip_testing.h); synchronises
+// one recorded op of the training step and its adjoint (dyf_op_train_f32, include/dyffusion_hip_testing.h); synchronises
 dyf_status f32_op_train(dyf_engine* e, const struct dyf_train_op* d, const float* const* inputs, const float* const* params, const float* dout,
                         float* y, float* const* dinputs, float* const* dparams, hipStream_t st);
 inline size_t f32_arena_block(size_t bytes) { return (std::max<size_t>(bytes, 256) + 255) / 256 * 256; }

@@ -1,5 +1,7 @@
-// Training step of the forecaster objective on the GPU: forward WITH batch-statistics BatchNorm / dropout and the backward
-// pass of arch unet_simple.
+// The fp32 path on the GPU -- the training step of the forecaster objective (forward WITH batch-statistics BatchNorm / dropout, and the
+// backward pass) and fp32 sampling -- for arch unet_simple and unet.Unet: the kernels both share, the convolution
+// dispatch, the caching allocator and the C entry points.  The recorded ops, the two layer walks, the parameters and the backward are in
+// train_resnet.inc (#included below): ONE mechanism for both backbones.
 //
 // Replaces, for `DYffusion.p_losses` in training mode (src/diffusion/dyffusion.py:496-567, entered from
 // BaseDiffusion.forward, src/diffusion/_base_diffusion.py:81-106), what the reference gets from torch.autograd over
@@ -22,42 +24,12 @@ using namespace dyf;
 
 namespace dyf {
 
-struct TBlockW {            // fp32 parameters (and gradients) of one UNetBlock
-    float *w = nullptr, *wt = nullptr;   // conv weight [cout][tap][cin] and its [tap][cin][cout] transpose (forward)
-    float *b = nullptr, *gamma = nullptr, *beta = nullptr, *rmean = nullptr, *rvar = nullptr;
-    float *fw = nullptr, *fb = nullptr;  // FiLM head Linear(tdim -> 2 cout)
-    float *g_w = nullptr, *g_b = nullptr, *g_gamma = nullptr, *g_beta = nullptr, *g_fw = nullptr, *g_fb = nullptr;
-};
-
-struct TNet {
-    TBlockW blk[12];
-    float *t_w1 = nullptr, *t_b1 = nullptr, *t_w2 = nullptr, *t_b2 = nullptr, *g_t_w1 = nullptr, *g_t_b1 = nullptr,
-          *g_t_w2 = nullptr, *g_t_b2 = nullptr;
-    float *stem_w = nullptr, *stem_wt = nullptr, *stem_b = nullptr, *g_stem_w = nullptr, *g_stem_b = nullptr;  // [dim][cin]
-    float *ro_w = nullptr, *ro_wt = nullptr, *ro_b = nullptr, *g_ro_w = nullptr, *g_ro_b = nullptr;  // conv C: [dim][16][C]
-    std::vector<std::pair<float*, size_t>> grads;  // every gradient buffer (zeroing)
-    std::vector<void*> owned;
-    bool ready = false;
-};
-
-struct TTape {              // what one recorded forward leaves for its backward
-    int net = -1, nb = 0, flags = 0;
-    std::vector<void*> owned;
-    float *x_in = nullptr, *x_up = nullptr, *s0 = nullptr;
-    float *cin_ptr[12] = {}, *z[12] = {}, *y[12] = {}, *ss[12] = {}, *mean[12] = {}, *rstd[12] = {};
-    float *xlast = nullptr;      // input of the readout
-    float *e0 = nullptr, *l1 = nullptr, *gl = nullptr, *temb = nullptr, *silu = nullptr;  // time-MLP chain
-    uint32_t* row_keys = nullptr;
-};
-
-struct RTNet;   // ResNet-UNet training copy / tapes (train_resnet.inc)
-struct RTape;
+struct TrainNet;   // fp32 parameters and gradients of one network (train_resnet.inc)
+struct RTape;   // one recorded forward
 
 struct TrainState {
-    TNet net[2];
-    TTape tape[4];
-    RTNet* rnet[2] = {nullptr, nullptr};
-    RTape* rtape[4] = {nullptr, nullptr, nullptr, nullptr};
+    TrainNet* net[2] = {nullptr, nullptr};
+    RTape* tape[4] = {nullptr, nullptr, nullptr, nullptr};
     // caching allocator of the tapes / temporaries: blocks go back to the pool instead of hipFree (which synchronises the
     // device) and are handed out again by exact size -- after the first step a training step allocates nothing.  Everything
     // runs on one stream, so reuse is ordered behind the previous use.
@@ -1140,16 +1112,6 @@ inline void launch_t_concat2(const float* a, int ca, const float* b, int cb, lon
     if (t_vec4_ok(ca | cb, a, b, out)) hipLaunchKernelGGL(t_concat2<4>, dim3(nblk(total / 4)), dim3(256), 0, st, a, ca, b, cb, pixels, out);
     else hipLaunchKernelGGL(t_concat2<1>, dim3(nblk(total)), dim3(256), 0, st, a, ca, b, cb, pixels, out);
 }
-// split the gradient of cat[a, b]: da = d[..., :ca] (assign), db += d[..., ca:]
-__global__ void t_split2(const float* d, int ca, int cb, long long pixels, float* da, float* db) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    const int C = ca + cb;
-    if (i >= pixels * C) return;
-    const int c = (int)(i % C);
-    const long long p = i / C;
-    if (c < ca) da[p * ca + c] = d[i];
-    else db[p * cb + (c - ca)] += d[i];
-}
 template <int V>
 __global__ __launch_bounds__(256) void t_add(float* a, const float* b, long long n) {
     const long long i = ((long long)blockIdx.x * 256 + threadIdx.x) * V;
@@ -1215,16 +1177,20 @@ std::map<void*, size_t>& g_block_bytes() {  // size of every live training block
     static std::map<void*, size_t> m;
     return m;
 }
+// (at_least: any idle block that is large enough serves -- short-lived scratch of a size nothing else has, which would otherwise add a
+// block to the pool; it goes back under its own size)
 template <typename T>
-dyf_status talloc(dyf_engine* e, std::vector<void*>& owner, T** out, size_t count, bool zero = true) {
+dyf_status talloc(dyf_engine* e, std::vector<void*>& owner, T** out, size_t count, bool zero = true, bool at_least = false) {
     void* p = nullptr;
     const size_t bytes = (std::max<size_t>(count * sizeof(T), 256) + 255) / 256 * 256;
+    size_t have = bytes;  // the block's own size
     TrainState* ts = e->train;
-    auto it = ts ? ts->pool.find(bytes) : std::multimap<size_t, void*>::iterator();
+    auto it = !ts ? std::multimap<size_t, void*>::iterator() : at_least ? ts->pool.lower_bound(bytes) : ts->pool.find(bytes);
     if (ts && it != ts->pool.end()) {
         p = it->second;
+        have = it->first;
         ts->pool.erase(it);
-        ts->pool_bytes -= bytes;
+        ts->pool_bytes -= have;
     } else {
         TK(hipMalloc(&p, bytes));
     }
@@ -1236,7 +1202,7 @@ dyf_status talloc(dyf_engine* e, std::vector<void*>& owner, T** out, size_t coun
         if (poison) TK(hipMemsetAsync(p, 0xFF, bytes, ts ? ts->stream : nullptr));
     }
     owner.push_back(p);
-    g_block_bytes()[p] = bytes;
+    g_block_bytes()[p] = have;
     *out = (T*)p;
     return DYF_OK;
 }
@@ -1320,7 +1286,7 @@ dyf_status conv_dgrad(dyf_engine* e, const TConv& g, const float* dz, const floa
         dyf_form_int("DYF_TRAIN_CT_ROWS", 1) != 0) {
         const int wc = (g.w / 2 + 63) / 64;
         constexpr size_t lds = (size_t)(16 * 64 * 4 + 3 * CT_COLS * CT_PITCH) * sizeof(float);
-        if (!train_raise_dynamic_lds(t_conv_dgrad_smalln_s2_rows, (int)lds))
+        if (!train_raise_dynamic_lds<t_conv_dgrad_smalln_s2_rows>((int)lds))
             return fail(e, DYF_ERR_HIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed for t_conv_dgrad_smalln_s2_rows");
         // output row pairs per workgroup: as many as still leave ~2 048 workgroups
         const long long all_pairs = (long long)g.n * (g.h / 2) * wc;
@@ -1399,10 +1365,6 @@ dyf_status conv_wgrad(dyf_engine* e, const TConv& g, const float* dz, const floa
     return DYF_OK;
 }
 
-TConv block_geom(const UBlock& b, int nb) {
-    return TConv{nb, b.in_h, b.in_w, b.cin, b.out_h, b.out_w, b.cout, b.k, b.stride, b.pad};
-}
-
 // Where the tensors of one fp32 forward come from -- the ONLY thing the recorded (training) forward and the sampling forward differ in:
 //   recording  blocks of the caching allocator, owned by the tape until its backward has run;
 //   sampling   bump allocation out of the engine's fp32 arena (sized once by dyf_set_sample_precision(32) for max_batch rows of either
@@ -1427,15 +1389,24 @@ struct FwdMem {
 
 }  // namespace
 
-#include "train_resnet.inc"  // recorded forward / backward of the ResNet-UNet (arch unet.Unet)
+#include "train_resnet.inc"  // the recorded ops, the layer walks of both backbones, parameters, backward, op seam
 
 namespace dyf {
 
 void train_destroy(dyf_engine* e) {
     if (!e->train) return;
-    rn_train_destroy(e);
-    for (auto& n : e->train->net) tfree(e, n.owned);
-    for (auto& t : e->train->tape) tfree(e, t.owned);
+    for (TrainNet*& n : e->train->net)
+        if (n) {
+            tfree(e, n->owned);
+            delete n;
+            n = nullptr;
+        }
+    for (RTape*& t : e->train->tape)
+        if (t) {
+            tfree(e, t->owned);
+            delete t;
+            t = nullptr;
+        }
     tfree(e, e->train->ws_owned);
     for (auto& kv : e->train->pool) {
         g_block_bytes().erase(kv.second);
@@ -1445,89 +1416,16 @@ void train_destroy(dyf_engine* e) {
     e->train = nullptr;
 }
 
-// called by dyf_load_weights (arch unet_simple): keep an fp32 copy of the parameters in the training layout
-dyf_status train_store_weights(dyf_engine* e, int which, std::map<std::string, TensorView>& sd) {
-    if (!e->train) e->train = new TrainState();
-    TNet& t = e->train->net[which];
-    const Net& n = e->net[which];
-    TK(hipDeviceSynchronize());
-    tfree(e, t.owned);
-    t = TNet{};
-    auto V = [&](const std::string& k) { const TensorView& v = sd.at(k); return std::vector<float>(v.data, v.data + v.numel()); };
-    auto grad = [&](float** g, size_t cnt) -> dyf_status {
-        dyf_status s = talloc(e, t.owned, g, cnt);
-        if (s == DYF_OK) t.grads.emplace_back(*g, cnt);
-        return s;
-    };
-#define TS(expr) do { dyf_status _s = (expr); if (_s != DYF_OK) return _s; } while (0)
-    for (int i = 0; i < 12; ++i) {
-        const UBlock& b = n.blk[i];
-        TBlockW& w = t.blk[i];
-        const std::string pre = (i < 6 ? "input_ops." + std::to_string(i) : "output_ops." + std::to_string(i - 6));
-        const std::string conv = pre + ".ops." + (b.transposed ? "1" : "0"), norm = pre + ".ops." + (b.transposed ? "2" : "1");
-        const std::vector<float> cw = V(conv + ".weight");
-        const int taps = b.k * b.k;
-        std::vector<float> a((size_t)b.cout * taps * b.cin), at(a.size());
-        for (int co = 0; co < b.cout; ++co)
-            for (int ci = 0; ci < b.cin; ++ci)
-                for (int tp = 0; tp < taps; ++tp) {
-                    const float v = cw[((size_t)co * b.cin + ci) * taps + tp];
-                    a[((size_t)co * taps + tp) * b.cin + ci] = v;
-                    at[((size_t)tp * b.cin + ci) * b.cout + co] = v;
-                }
-        TS(tupload(e, t.owned, &w.w, a)); TS(tupload(e, t.owned, &w.wt, at));
-        TS(tupload(e, t.owned, &w.b, V(conv + ".bias")));
-        TS(tupload(e, t.owned, &w.gamma, V(norm + ".weight"))); TS(tupload(e, t.owned, &w.beta, V(norm + ".bias")));
-        if (!b.gn) { TS(tupload(e, t.owned, &w.rmean, V(norm + ".running_mean"))); TS(tupload(e, t.owned, &w.rvar, V(norm + ".running_var"))); }
-        TS(grad(&w.g_w, a.size())); TS(grad(&w.g_b, b.cout)); TS(grad(&w.g_gamma, b.cout)); TS(grad(&w.g_beta, b.cout));
-        if (n.cfg.with_time_emb) {
-            TS(tupload(e, t.owned, &w.fw, V(pre + ".time_mlp.1.weight"))); TS(tupload(e, t.owned, &w.fb, V(pre + ".time_mlp.1.bias")));
-            TS(grad(&w.g_fw, (size_t)2 * b.cout * n.tdim)); TS(grad(&w.g_fb, (size_t)2 * b.cout));
-        }
-    }
-    if (n.cfg.with_time_emb) {
-        TS(tupload(e, t.owned, &t.t_w1, V("time_emb_mlp.1.weight"))); TS(tupload(e, t.owned, &t.t_b1, V("time_emb_mlp.1.bias")));
-        TS(tupload(e, t.owned, &t.t_w2, V("time_emb_mlp.3.weight"))); TS(tupload(e, t.owned, &t.t_b2, V("time_emb_mlp.3.bias")));
-        TS(grad(&t.g_t_w1, (size_t)n.tdim * n.dim)); TS(grad(&t.g_t_b1, n.tdim)); TS(grad(&t.g_t_w2, (size_t)n.tdim * n.tdim)); TS(grad(&t.g_t_b2, n.tdim));
-    }
-    {
-        const std::vector<float> sw = V("init_conv.weight");  // [dim][cin] (1x1)
-        std::vector<float> swt(sw.size());
-        for (int d = 0; d < n.dim; ++d)
-            for (int c = 0; c < n.cin_total; ++c) swt[(size_t)c * n.dim + d] = sw[(size_t)d * n.cin_total + c];
-        TS(tupload(e, t.owned, &t.stem_w, sw)); TS(tupload(e, t.owned, &t.stem_wt, swt)); TS(tupload(e, t.owned, &t.stem_b, V("init_conv.bias")));
-        TS(grad(&t.g_stem_w, sw.size())); TS(grad(&t.g_stem_b, n.dim));
-    }
-    {   // readout ConvTranspose2d(dim -> C, k4, s2, p1) as the dgrad form of a conv C: (C ch, 2h x 2w) -> (dim ch, h x w):
-        // Wc[co = dim][tap][ci = C] = W_T[co][ci][ky][kx]
-        const std::vector<float> rw = V("readout.0.weight");
-        const int oc = n.cfg.out_channels;
-        std::vector<float> a((size_t)n.dim * 16 * oc), at(a.size());
-        for (int co = 0; co < n.dim; ++co)
-            for (int ci = 0; ci < oc; ++ci)
-                for (int tp = 0; tp < 16; ++tp) {
-                    const float v = rw[((size_t)co * oc + ci) * 16 + tp];
-                    a[((size_t)co * 16 + tp) * oc + ci] = v;
-                    at[((size_t)tp * oc + ci) * n.dim + co] = v;
-                }
-        TS(tupload(e, t.owned, &t.ro_w, a)); TS(tupload(e, t.owned, &t.ro_wt, at)); TS(tupload(e, t.owned, &t.ro_b, V("readout.0.bias")));
-        TS(grad(&t.g_ro_w, a.size())); TS(grad(&t.g_ro_b, oc));
-    }
-#undef TS
-    t.ready = true;
-    return DYF_OK;
-}
-
 }  // namespace dyf
 
 extern "C" {
 
 dyf_status dyf_train_zero_grads(dyf_engine* e, int32_t which) {
     if (!e || which < 0 || which > 1) return DYF_ERR_INVALID_ARGUMENT;
-    if (e->net[which].rn) { TK(hipSetDevice(e->cfg.device)); return rn_train_zero_grads(e, which); }
-    if (!e->train || !e->train->net[which].ready) return fail(e, DYF_ERR_STATE, "training needs arch unet_simple / unet with loaded weights");
+    TrainNet* t = e->train ? e->train->net[which] : nullptr;
+    if (!t || !t->ready) return fail(e, DYF_ERR_STATE, "training needs arch unet_simple / unet with loaded weights");
     TK(hipSetDevice(e->cfg.device));
-    for (auto& g : e->train->net[which].grads) TK(hipMemsetAsync(g.first, 0, g.second * sizeof(float), 0));
+    TK(hipMemsetAsync(t->g_arena, 0, t->g_arena_floats * sizeof(float), 0));
     TK(hipDeviceSynchronize());
     return DYF_OK;
 }
@@ -1541,196 +1439,7 @@ int32_t dyf_train_precision(const dyf_engine* e) { return e ? e->train_precision
 
 }  // extern "C"
 
-namespace {
-
-struct UsForward {              // one fp32 forward of arch unet_simple
-    const Source* srcs;         // fp32 NCHW tensors, concatenated on the channel axis in this order
-    int nsrc;
-    const float* time_dev;      // [nb], or null: time_value for every row
-    float time_value;
-    int nb;
-    bool bn_batch;              // BatchNorm on batch statistics (module.train()); false: running statistics
-    int dropout_mode;           // 0 off, 1 engine generator, 2 injected keep masks
-    const uint8_t* const* masks;
-};
-
-// The layer walk of unet_simple.py:164-197 on the fp32 kernels; `t` receives what a backward needs (the sampling forward passes a
-// scratch tape and drops it).
-dyf_status us_forward(dyf_engine* e, int which, FwdMem& mem, TTape& t, const UsForward& f, float* out_dev, hipStream_t st) {
-    Net& n = e->net[which];
-    TNet& w = e->train->net[which];
-    const int nb = f.nb;
-    const bool bn_batch = f.bn_batch;
-    // dropout: 1 = the engine's generator (per-row streams), 2 = injected keep masks in execution order -- dropout_input (when its
-    // p > 0) first, then the 12 blocks, as the 16-bit forward takes them (engine.hip make_drop); a site with p = 0 is no site
-    const int in_site = n.cfg.input_dropout > 0.0f ? 1 : 0;
-    const bool drop_on = f.dropout_mode == 1 && n.cfg.dropout > 0.0f, in_drop_on = f.dropout_mode == 1 && n.cfg.input_dropout > 0.0f;
-    const bool mask_on = f.dropout_mode == 2 && f.masks && n.cfg.dropout > 0.0f;
-    const uint8_t* in_mask = (f.dropout_mode == 2 && f.masks && in_site) ? f.masks[0] : nullptr;
-    const int H = e->cfg.height, W = e->cfg.width, hw = H * W, cin = n.cin_total, C = n.cfg.out_channels;
-    Source src[3] = {{nullptr, 0}, {nullptr, 0}, {nullptr, 0}};  // NCHW sources in channel order
-    int ctot = 0;
-    for (int i = 0; i < f.nsrc && i < 3; ++i) {
-        src[i] = f.srcs[i];
-        if (!src[i].p) src[i].ch = 0;
-        ctot += src[i].ch;
-    }
-    if (ctot != cin) return fail(e, DYF_ERR_INVALID_ARGUMENT, "channel count of the network inputs does not match its configuration");
-#define TS(expr) do { dyf_status _s = (expr); if (_s != DYF_OK) return _s; } while (0)
-#define TA(ptr, count) TS(mem.get(&(ptr), (size_t)(count)))
-    if (drop_on || in_drop_on) {  // this forward's dropout streams (engine generator, keyed per global row); kept for the backward
-        if (nb > 2 * e->cfg.max_batch) return fail(e, DYF_ERR_INVALID_ARGUMENT, "batch larger than the engine's row-key table");
-        TK(launch_rng_begin_forward(e->rng_state, e->row_keys, nb, nb, st));
-        if (mem.recording()) {
-            TA(t.row_keys, (size_t)2 * nb);
-            TK(hipMemcpyAsync(t.row_keys, e->row_keys, (size_t)2 * nb * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
-        } else {
-            t.row_keys = e->row_keys;  // nothing comes back for them: the engine's table of the forward being launched
-        }
-    }
-    // ---- time embedding chain: sinusoid -> Linear -> GELU -> Linear ; every block: SiLU -> Linear -> (scale | shift)
-    if (n.cfg.with_time_emb) {
-        const float* time_dev = f.time_dev;
-        if (!time_dev) {  // one time for the whole batch (a sampling plan's step)
-            float* tv = nullptr;
-            TA(tv, nb);
-            hipLaunchKernelGGL(t_fill, dim3(nblk(nb)), dim3(256), 0, st, f.time_value, nb, tv);
-            time_dev = tv;
-        }
-        TA(t.e0, nb * n.dim); TA(t.l1, nb * n.tdim); TA(t.gl, nb * n.tdim); TA(t.temb, nb * n.tdim);
-        hipLaunchKernelGGL(t_sinusoid, dim3(nblk(nb * n.dim)), dim3(256), 0, st, time_dev, nb, n.dim, t.e0);
-        hipLaunchKernelGGL(t_linear_fwd, dim3((unsigned)((n.tdim + 3) / 4), (unsigned)((nb + 15) / 16)), dim3(256), 0, st, t.e0, w.t_w1, w.t_b1, nb, n.dim, n.tdim, 0, t.l1);
-        hipLaunchKernelGGL(t_gelu_fwd, dim3(nblk((long long)nb * n.tdim)), dim3(256), 0, st, t.l1, (long long)nb * n.tdim, t.gl);
-        hipLaunchKernelGGL(t_linear_fwd, dim3((unsigned)((n.tdim + 3) / 4), (unsigned)((nb + 15) / 16)), dim3(256), 0, st, t.gl, w.t_w2, w.t_b2, nb, n.tdim, n.tdim, 0, t.temb);
-    }
-    // ---- stem: cat -> outer resample -> 1x1 conv
-    TA(t.x_in, (size_t)nb * hw * cin);
-    hipLaunchKernelGGL(t_nchw_cat_to_nhwc, dim3(nblk((long long)nb * hw * cin)), dim3(256), 0, st, src[0].p, src[0].ch, src[1].p, src[1].ch, src[2].p,
-                       src[2].ch, nb, hw, t.x_in);
-    if (n.uh != H || n.uw != W) {
-        TA(t.x_up, (size_t)nb * n.uh * n.uw * cin);
-        hipLaunchKernelGGL(t_resize_fwd, dim3(nblk((long long)nb * n.uh * n.uw * cin)), dim3(256), 0, st, t.x_in, nb, H, W, cin, n.uh, n.uw, n.cfg.outer_nearest, t.x_up);
-    } else {
-        t.x_up = t.x_in;
-    }
-    TA(t.s0, (size_t)nb * n.uh * n.uw * n.dim);
-    TS(conv_fwd(e, TConv{nb, n.uh, n.uw, cin, n.uh, n.uw, n.dim, 1, 1, 0}, t.x_up, w.stem_wt, w.stem_b, t.s0, st));
-    if (in_drop_on) {  // dropout_input (site DYF_INPUT_DROP_SITE), in place: the stem's conv needs its input only for the weight gradient
-        const long long per = (long long)n.uh * n.uw * n.dim;
-        hipLaunchKernelGGL(t_dropout_map, dim3(nblk(per * nb)), dim3(256), 0, st, t.s0, t.s0, nb, per, 1.0f / (1.0f - n.cfg.input_dropout),
-                           keep_threshold16(n.cfg.input_dropout), rng_layer_salt(DYF_INPUT_DROP_SITE), t.row_keys);
-    } else if (in_mask) {
-        const long long total = (long long)nb * n.uh * n.uw * n.dim;
-        hipLaunchKernelGGL(t_mask_map, dim3(nblk(total)), dim3(256), 0, st, t.s0, t.s0, total, 1.0f / (1.0f - n.cfg.input_dropout), in_mask);
-    }
-    double *S = nullptr, *Q = nullptr;
-    TS(mem.get(&S, (size_t)nb * 1024 * 2, true));
-    Q = S + (size_t)nb * 1024;
-    // ---- the 12 blocks
-    const float* x = t.s0;
-    const float* x2 = nullptr;  // second part of a pending torch.cat([x, x2]) (channels xc | x2c): the x2 upsample reads both parts
-    int xc = 0, x2c = 0;
-    int lh = n.uh, lw = n.uw;
-    for (int i = 0; i < 12; ++i) {
-        const UBlock& b = n.blk[i];
-        if (b.cout > 1024) return fail(e, DYF_ERR_UNSUPPORTED, "training path: more than 1024 channels per block");
-        const bool up2 = b.transposed && b.cin % 4 == 0 && b.in_h == 2 * lh && b.in_w == 2 * lw;
-        if (x2 && !(up2 && xc % 4 == 0 && x2c % 4 == 0)) {  // no consumer that reads two parts: materialise the concatenation
-            float* cat = nullptr;
-            TA(cat, (size_t)nb * lh * lw * (xc + x2c));
-            launch_t_concat2(x, xc, x2, x2c, (long long)nb * lh * lw, cat, st);
-            x = cat;
-            x2 = nullptr;
-        }
-        const float* cx = x;
-        if (b.transposed) {  // x2 bilinear upsample in front of the conv
-            float* u = nullptr;
-            TA(u, (size_t)nb * b.in_h * b.in_w * b.cin);
-            if (up2)
-                hipLaunchKernelGGL(t_up2x_fwd, dim3(nblk((long long)nb * b.in_h * b.in_w * (b.cin / 4))), dim3(256), 0, st, x, nb, lh, lw, b.cin / 4, u,
-                                   x2 ? xc / 4 : b.cin / 4, x2);
-            else
-                hipLaunchKernelGGL(t_resize_fwd, dim3(nblk((long long)nb * b.in_h * b.in_w * b.cin)), dim3(256), 0, st, x, nb, lh, lw, b.cin, b.in_h, b.in_w, 0, u);
-            cx = u;
-            x2 = nullptr;
-        }
-        t.cin_ptr[i] = (float*)cx;
-        const long long out_el = (long long)nb * b.out_h * b.out_w * b.cout;
-        TA(t.z[i], out_el); TA(t.y[i], out_el);
-        TS(conv_fwd(e, block_geom(b, nb), cx, w.blk[i].wt, w.blk[i].b, t.z[i], st));
-        const int ohw = b.out_h * b.out_w, nidx = b.gn ? nb * 8 : b.cout;
-        TA(t.mean[i], nidx); TA(t.rstd[i], nidx);
-        const int kind = b.gn ? 2 : (bn_batch ? 0 : 1);
-        if (kind != 1) {
-            TK(hipMemsetAsync(S, 0, (size_t)nb * 1024 * 2 * sizeof(double), st));
-            // (sampling: ONE workgroup per sample, so every sum meets its zero-filled slot once -- no order of atomics to depend on)
-            const int ppb = mem.recording() ? std::max(16, (ohw + 255) / 256) : ohw;
-            hipLaunchKernelGGL(t_nc_sums, dim3((ohw + ppb - 1) / ppb, nb), dim3(256), 0, st, t.z[i], ohw, b.cout, ppb, S, Q);
-        }
-        hipLaunchKernelGGL(t_stats_finalize, dim3(nblk(std::max(nidx, b.cout))), dim3(256), 0, st, kind, S, Q, nb, ohw, b.cout, 8, w.blk[i].rmean,
-                           w.blk[i].rvar, t.mean[i], t.rstd[i]);
-        if (n.cfg.with_time_emb) {
-            TA(t.ss[i], (size_t)nb * 2 * b.cout);
-            hipLaunchKernelGGL(t_linear_fwd, dim3((unsigned)((2 * b.cout + 3) / 4), (unsigned)((nb + 15) / 16)), dim3(256), 0, st, t.temb, w.blk[i].fw, w.blk[i].fb, nb, n.tdim, 2 * b.cout, 1, t.ss[i]);
-        }
-        TNorm a{nb, ohw, b.cout, 8, b.gn ? 1 : 0, b.act, t.mean[i], t.rstd[i], w.blk[i].gamma, w.blk[i].beta, t.ss[i], drop_on ? 1 : 0,
-                1.0f / (1.0f - n.cfg.dropout), keep_threshold16(n.cfg.dropout), rng_layer_salt((uint32_t)i), t.row_keys,
-                mask_on ? f.masks[i + in_site] : nullptr};
-        launch_t_norm_fwd(a, t.z[i], t.y[i], st);
-        TK(hipGetLastError());
-        x = t.y[i];
-        lh = b.out_h; lw = b.out_w;
-        if (i >= 6 && i < 11) {  // torch.cat([x, skip]) (unet_simple.py:176-177): left to the next block's upsample (two sources)
-            x2 = t.y[10 - i];
-            xc = b.cout;
-            x2c = n.blk[10 - i].cout;
-        }
-    }
-    t.xlast = (float*)x;
-    // ---- readout: ConvTranspose2d (dgrad form of conv C) + final resample
-    float *r = nullptr, *o = nullptr;
-    TA(r, (size_t)nb * 4 * lh * lw * C);
-    TS(conv_dgrad(e, TConv{nb, 2 * lh, 2 * lw, C, lh, lw, n.dim, 4, 2, 1}, x, w.ro_w, w.ro_b, r, st));
-    TA(o, (size_t)nb * hw * C);
-    hipLaunchKernelGGL(t_resize_fwd, dim3(nblk((long long)nb * hw * C)), dim3(256), 0, st, r, nb, 2 * lh, 2 * lw, C, H, W, n.cfg.outer_nearest, o);
-    hipLaunchKernelGGL(t_nhwc_to_nchw, dim3(nblk((long long)nb * hw * C)), dim3(256), 0, st, o, nb, hw, C, 0, C, out_dev);
-    TK(hipGetLastError());
-#undef TA
-#undef TS
-    return DYF_OK;
-}
-
-}  // namespace
-
 namespace dyf {
-
-// Bytes one unet_simple forward of `nb` rows takes from the arena: the allocations of us_forward, block by block (the concatenation
-// a decoder block may have to materialise is always counted).
-static size_t us_arena_bytes(const dyf_engine* e, const Net& n, size_t nb) {
-    const size_t H = e->cfg.height, W = e->cfg.width, F = sizeof(float);
-    size_t b = 0;
-    auto add = [&](size_t bytes) { b += f32_arena_block(bytes); };
-    if (n.cfg.with_time_emb) { add(nb * F); add(nb * n.dim * F); for (int k = 0; k < 3; ++k) add(nb * n.tdim * F); }
-    add(nb * H * W * n.cin_total * F);
-    add(nb * n.uh * n.uw * n.cin_total * F);
-    add(nb * n.uh * n.uw * n.dim * F);
-    add(nb * 1024 * 2 * sizeof(double));
-    for (int i = 0; i < 12; ++i) {
-        const UBlock& k = n.blk[i];
-        if (k.transposed) {
-            add(nb * (k.in_h / 2 + 1) * (k.in_w / 2 + 1) * k.cin * F);  // cat[x, skip] at the low resolution
-            add(nb * k.in_h * k.in_w * k.cin * F);
-        }
-        add(nb * k.out_h * k.out_w * k.cout * F);
-        add(nb * k.out_h * k.out_w * k.cout * F);
-        add(std::max<size_t>(nb * 8, k.cout) * F);
-        add(std::max<size_t>(nb * 8, k.cout) * F);
-        add(nb * 2 * k.cout * F);
-    }
-    add(nb * 4 * n.blk[11].out_h * n.blk[11].out_w * n.cfg.out_channels * F);
-    add(nb * H * W * n.cfg.out_channels * F);
-    return b;
-}
 
 dyf_status f32_prepare(dyf_engine* e) {
     size_t fwd = 0;
@@ -1738,8 +1447,7 @@ dyf_status f32_prepare(dyf_engine* e) {
         const Net& n = e->net[w];
         if (n.rn && !rn_f32_supported(e, n))
             return fail(e, DYF_ERR_UNSUPPORTED, "fp32 sampling: the bottleneck Attention indexes its (4 x tokens x tokens) probabilities with 32 bits -- at most 32767 tokens");
-        fwd = std::max(fwd, n.rn ? rn_arena_bytes(e, n, e->cfg.max_batch)
-                                 : n.sc ? sc_f32_arena_bytes(e, n, e->cfg.max_batch) : us_arena_bytes(e, n, e->cfg.max_batch));
+        fwd = std::max(fwd, n.sc ? sc_f32_arena_bytes(e, n, e->cfg.max_batch) : f32_walk_bytes(e, n, e->cfg.max_batch));
     }
     if (e->f32_arena) return DYF_OK;
     // [split-K partial sums of the matrix-core convs | the tensors of one forward]
@@ -1759,7 +1467,8 @@ void f32_destroy(dyf_engine* e) {
 dyf_status f32_net_forward(dyf_engine* e, int which, const Source* srcs, int nsrc, int nb, const FwdOpts& o, float* out_dev,
                            hipStream_t st) {
     const Net& n = e->net[which];
-    if (!e->f32_arena || !n.loaded || (!n.sc && (!e->train || (!n.rn && !e->train->net[which].ready))))
+    TrainNet* wp = e->train ? e->train->net[which] : nullptr;
+    if (!e->f32_arena || !n.loaded || (!n.sc && (!wp || !wp->ready)))
         return fail(e, DYF_ERR_STATE, "fp32 sampling needs loaded weights and dyf_set_sample_precision(32)");
     if (nb < 1 || nb > e->cfg.max_batch || (o.src_rows > 0 && o.src_rows != nb))
         return fail(e, DYF_ERR_INVALID_ARGUMENT, "fp32 sampling: one forward of at most max_batch rows, one source row per batch row");
@@ -1775,14 +1484,33 @@ dyf_status f32_net_forward(dyf_engine* e, int which, const Source* srcs, int nsr
     } active(e);
     e->train->stream = st;
     e->f32_used = TRAIN_SPLITK_FLOATS * sizeof(float);
-    if (n.rn) return rn_f32_forward(e, which, srcs, nsrc, nb, o, out_dev, st);
-    TTape scratch{};
-    UsForward f{};
-    f.srcs = srcs; f.nsrc = nsrc; f.time_dev = o.time_dev; f.time_value = o.time_value; f.nb = nb;
-    f.bn_batch = false;
-    f.dropout_mode = o.dropout_mode; f.masks = o.masks;
-    FwdMem mem{e, nullptr, st};
-    return us_forward(e, which, mem, scratch, f, out_dev, st);
+    const dyf_net_config& c = n.cfg;
+    const int hw = e->cfg.height * e->cfg.width;
+    Source src[3] = {{nullptr, 0}, {nullptr, 0}, {nullptr, 0}};  // NCHW sources in channel order
+    int ctot = 0;
+    for (int i = 0; i < nsrc && i < 3; ++i) {
+        src[i] = srcs[i];
+        if (!src[i].p) src[i].ch = 0;
+        ctot += src[i].ch;
+    }
+    if (ctot != n.cin_total) return fail(e, DYF_ERR_INVALID_ARGUMENT, "channel count of the network inputs does not match its configuration");
+    // dropout: 1 = the engine's generator (per-row streams), 2 = injected keep masks, one per site with p > 0 in execution order
+    const bool any_p = c.dropout > 0.0f || c.block_dropout1 > 0.0f || c.attn_dropout > 0.0f || c.input_dropout > 0.0f;
+    const bool drop_on = o.dropout_mode == 1 && any_p;
+    RTape T;  // scratch: a sampling forward leaves nothing behind
+    if (drop_on) {  // begin the forward in the generator exactly as the 16-bit path does; the keys are read from the engine's table
+        TK(launch_rng_begin_forward(e->rng_state, e->row_keys, nb, nb, st));
+        T.row_keys = e->row_keys;
+    }
+    RCtx X{e, *wp, T, c, st, nb, drop_on};
+    X.mem = FwdMem{e, nullptr, st};
+    X.masks = (o.dropout_mode == 2 && o.masks && any_p) ? o.masks : nullptr;
+    RT* xi = nullptr;
+    RT* y = net_walk(X, e, n, nb, src, o.time_dev, o.time_value, false, &xi);  // BatchNorm on its running statistics
+    if (X.err != DYF_OK) return fail(e, X.err, e->err.empty() ? "fp32 forward: allocation / launch failed" : e->err);
+    hipLaunchKernelGGL(t_nhwc_to_nchw, dim3(nblk((long long)nb * hw * c.out_channels)), dim3(256), 0, st, y->p, nb, hw, c.out_channels, 0, c.out_channels, out_dev);
+    TK(hipGetLastError());
+    return DYF_OK;
 }
 
 }  // namespace dyf
@@ -1794,280 +1522,30 @@ dyf_status dyf_train_forward(dyf_engine* e, int32_t which, int32_t slot, const f
     if (!e || which < 0 || which > 1 || slot < 0 || slot > 3 || !inputs_dev || !out_dev || nb < 1)
         return fail(e, DYF_ERR_INVALID_ARGUMENT, "dyf_train_forward: bad arguments");
     const TrainPrecisionScope precision(e->train_precision);
-    if (e->net[which].rn) {
-        TK(hipSetDevice(e->cfg.device));
-        if (e->train) {  // the slot now belongs to this forward: drop a unet_simple tape that may sit in it
-            tfree(e, e->train->tape[slot].owned);
-            e->train->tape[slot] = TTape{};
-        }
-        return rn_train_forward(e, which, slot, inputs_dev, time_dev, cond_dev, out_dev, nb, flags, (hipStream_t)stream);
-    }
     if (e->net[which].sc) return fail(e, DYF_ERR_UNSUPPORTED, "training step: arch unet_simple and unet (SimpleConvNet is the CPU plumbing config)");
-    if (!e->train || !e->train->net[which].ready) return fail(e, DYF_ERR_STATE, "training needs arch unet_simple with loaded weights");
-    Net& n = e->net[which];
-    if ((n.cfg.cond_channels > 0) != (cond_dev != nullptr)) return fail(e, DYF_ERR_INVALID_ARGUMENT, "condition must be given iff num_conditional_channels > 0");
-    if (n.cfg.with_time_emb && !time_dev) return fail(e, DYF_ERR_INVALID_ARGUMENT, "time must be given when with_time_emb");
     TK(hipSetDevice(e->cfg.device));
-    hipStream_t st = (hipStream_t)stream;
-    e->train->stream = st;
-    TTape& t = e->train->tape[slot];
-    TK(hipStreamSynchronize(st));
-    tfree(e, t.owned);
-    t = TTape{};
-    t.net = which; t.nb = nb; t.flags = flags;
-    Source srcs[2] = {{inputs_dev, n.cfg.in_channels}, {cond_dev, n.cfg.cond_channels}};
-    UsForward f{};
-    f.srcs = srcs; f.nsrc = cond_dev ? 2 : 1; f.time_dev = time_dev; f.nb = nb;
-    f.bn_batch = (flags & DYF_TRAIN_BATCH_STATS) != 0;
-    f.dropout_mode = (flags & DYF_TRAIN_DROPOUT) ? 1 : 0;
-    FwdMem mem{e, &t.owned, st};
-    return us_forward(e, which, mem, t, f, out_dev, st);
+    return train_forward(e, which, slot, inputs_dev, time_dev, cond_dev, out_dev, nb, flags, (hipStream_t)stream);
 }
 
 dyf_status dyf_train_backward(dyf_engine* e, int32_t slot, const float* dout_dev, float* dinputs_dev, int32_t param_grads, void* stream) {
     if (!e || slot < 0 || slot > 3 || !dout_dev) return fail(e, DYF_ERR_INVALID_ARGUMENT, "dyf_train_backward: bad arguments");
     const TrainPrecisionScope precision(e->train_precision);
-    if (e->train && e->train->rtape[slot] && e->train->tape[slot].net < 0) {  // the slot holds a ResNet-UNet forward
-        TK(hipSetDevice(e->cfg.device));
-        return rn_train_backward(e, slot, dout_dev, dinputs_dev, param_grads, (hipStream_t)stream);
-    }
-    if (!e->train || e->train->tape[slot].net < 0) return fail(e, DYF_ERR_STATE, "no forward recorded in this tape slot");
     TK(hipSetDevice(e->cfg.device));
-    hipStream_t st = (hipStream_t)stream;
-    e->train->stream = st;
-    TTape& t = e->train->tape[slot];
-    Net& n = e->net[t.net];
-    TNet& w = e->train->net[t.net];
-    const int nb = t.nb, H = e->cfg.height, W = e->cfg.width, hw = H * W, cin = n.cin_total, C = n.cfg.out_channels;
-    const bool bn_batch = t.flags & DYF_TRAIN_BATCH_STATS, drop_on = (t.flags & DYF_TRAIN_DROPOUT) && n.cfg.dropout > 0.0f;
-    std::vector<void*> tmp;
-#define TS(expr) do { dyf_status _s = (expr); if (_s != DYF_OK) { tfree(e, tmp); return _s; } } while (0)
-#define TA(ptr, count) TS(talloc(e, tmp, &(ptr), (size_t)(count), false))
-#define TZ(ptr, count) TS(talloc(e, tmp, &(ptr), (size_t)(count), true))
-    const int lh = n.blk[11].out_h, lw = n.blk[11].out_w;
-    // ---- final resample adjoint, readout
-    float *d_o = nullptr, *d_r = nullptr, *dx = nullptr;
-    TA(d_o, (size_t)nb * hw * C);
-    hipLaunchKernelGGL(t_nchw_to_nhwc, dim3(nblk((long long)nb * hw * C)), dim3(256), 0, st, dout_dev, nb, hw, C, d_o);
-    TZ(d_r, (size_t)nb * 4 * lh * lw * C);
-    hipLaunchKernelGGL(t_resize_bwd, dim3(nblk((long long)nb * hw * C)), dim3(256), 0, st, d_o, nb, 2 * lh, 2 * lw, C, H, W, n.cfg.outer_nearest, d_r);
-    const TConv gc{nb, 2 * lh, 2 * lw, C, lh, lw, n.dim, 4, 2, 1};
-    if (param_grads) {
-        TS(conv_wgrad(e, gc, t.xlast, d_r, w.g_ro_w, nullptr, st));
-        launch_bias_grad(d_r, (long long)nb * 4 * lh * lw, C, w.g_ro_b, st);
-    }
-    TA(dx, (size_t)nb * lh * lw * n.dim);
-    TS(conv_fwd(e, gc, d_r, w.ro_wt, nullptr, dx, st));
-    // ---- blocks, last to first
-    bool presplit = false;  // dy of the next (lower) block is already d y_i, its skip part already in dskip
-    float* dskip[5] = {};
-    for (int j = 0; j < 5; ++j) TZ(dskip[j], (size_t)nb * n.blk[j].out_h * n.blk[j].out_w * n.blk[j].cout);
-    float* dsilu = nullptr;
-    if (n.cfg.with_time_emb) TZ(dsilu, (size_t)nb * n.tdim);
-    double* R = nullptr;
-    TS(talloc(e, tmp, &R, (size_t)nb * 1024 * 4));
-    float *S1 = nullptr, *S2 = nullptr, *dss = nullptr;
-    TA(S1, std::max(1024, nb * 8)); TA(S2, std::max(1024, nb * 8)); TA(dss, (size_t)nb * 2 * 1024);
-    float* dy = dx;  // gradient w.r.t. the output of block i (for i < 11: the y part of the concat)
-    for (int i = 11; i >= 0; --i) {
-        const UBlock& b = n.blk[i];
-        const int ohw = b.out_h * b.out_w;
-        const long long out_el = (long long)nb * ohw * b.cout;
-        if (i >= 6 && i < 11 && presplit) {  // the upsample adjoint of block i + 1 already wrote the two parts
-            presplit = false;
-        } else if (i >= 6 && i < 11) {  // dy currently holds d cat[y_i, skip]: split
-            const UBlock& sk = n.blk[10 - i];
-            float* dyi = nullptr;
-            TA(dyi, out_el);
-            hipLaunchKernelGGL(t_split2, dim3(nblk((long long)nb * ohw * (b.cout + sk.cout))), dim3(256), 0, st, dy, b.cout, sk.cout, (long long)nb * ohw, dyi,
-                               dskip[10 - i]);
-            dy = dyi;
-        } else if (i < 5) {  // encoder outputs also feed the decoder through the skips
-            launch_t_add(dy, dskip[i], out_el, st);
-        }
-        TNorm a{nb, ohw, b.cout, 8, b.gn ? 1 : 0, b.act, t.mean[i], t.rstd[i], w.blk[i].gamma, w.blk[i].beta, t.ss[i], drop_on ? 1 : 0,
-                1.0f / (1.0f - n.cfg.dropout), keep_threshold16(n.cfg.dropout), rng_layer_salt((uint32_t)i), t.row_keys};
-        TK(hipMemsetAsync(R, 0, (size_t)nb * 1024 * 4 * sizeof(double), st));
-        double *A = R, *B = R + (size_t)nb * 1024, *Cc = R + (size_t)2 * nb * 1024, *Dd = R + (size_t)3 * nb * 1024;
-        const int ppb = std::max(16, (ohw + 255) / 256);
-        hipLaunchKernelGGL(t_norm_bwd_sums, dim3((ohw + ppb - 1) / ppb, nb), dim3(256), 0, st, a, t.z[i], dy, ppb, A, B, Cc, Dd);
-        const bool batch_stats = b.gn || bn_batch;
-        hipLaunchKernelGGL(t_norm_bwd_combine, dim3(nblk(std::max(nb * b.cout, nb * 8))), dim3(256), 0, st, a, A, B, Cc, Dd,
-                           param_grads ? w.blk[i].g_gamma : (float*)nullptr, param_grads ? w.blk[i].g_beta : (float*)nullptr,
-                           n.cfg.with_time_emb ? dss : (float*)nullptr, S1, S2, batch_stats ? 1 : 0);
-        float* dz = nullptr;
-        TA(dz, out_el);
-        const float inv_count = b.gn ? 1.0f / ((float)ohw * (b.cout / 8)) : 1.0f / ((float)nb * ohw);
-        launch_t_norm_bwd_apply(a, t.z[i], dy, S1, S2, inv_count, dz, st);
-        if (n.cfg.with_time_emb) {  // FiLM head: ss = W silu(temb) + b
-            if (param_grads)
-                hipLaunchKernelGGL(t_linear_bwd_w, dim3(nblk(2 * b.cout * n.tdim)), dim3(256), 0, st, t.temb, dss, nb, n.tdim, 2 * b.cout, 1, w.blk[i].g_fw,
-                                   w.blk[i].g_fb);
-            // d silu(temb) accumulated over the blocks (the SiLU derivative is applied once below)
-            hipLaunchKernelGGL(t_linear_bwd_x, dim3((unsigned)(nb * ((n.tdim + 15) / 16))), dim3(256), 0, st, t.temb, w.blk[i].fw, dss, nb, n.tdim, 2 * b.cout, 0, 1, dsilu);
-        }
-        const TConv g = block_geom(b, nb);
-        if (param_grads) TS(conv_wgrad(e, g, dz, t.cin_ptr[i], w.blk[i].g_w, w.blk[i].g_b, st));
-        float* dcx = nullptr;  // gradient w.r.t. the conv input (block 0's feeds the stem's 1x1 conv)
-        TA(dcx, (size_t)nb * b.in_h * b.in_w * b.cin);
-        TS(conv_dgrad(e, g, dz, w.blk[i].w, nullptr, dcx, st));
-        if (b.transposed) {  // adjoint of the x2 upsample
-            const int ph = b.in_h / 2, pw = b.in_w / 2;
-            float* dlow = nullptr;
-            if (b.cin % 4 == 0 && b.in_h == 2 * ph && b.in_w == 2 * pw) {
-                // the upsampled tensor of blocks 7..11 is cat[y_{i-1}, skip]: its gradient leaves as the two parts (no split pass)
-                const int ca = i >= 7 ? n.blk[i - 1].cout : b.cin, cb = b.cin - ca;
-                if (i >= 7 && ca % 4 == 0 && cb % 4 == 0 && cb == n.blk[11 - i].cout) {
-                    TA(dlow, (size_t)nb * ph * pw * ca);
-                    hipLaunchKernelGGL(t_up2x_bwd, dim3(nblk((long long)nb * ph * pw * (b.cin / 4))), dim3(256), 0, st, dcx, nb, ph, pw, b.cin / 4, dlow, ca / 4,
-                                       dskip[11 - i]);
-                    presplit = true;
-                } else {
-                    TA(dlow, (size_t)nb * ph * pw * b.cin);
-                    hipLaunchKernelGGL(t_up2x_bwd, dim3(nblk((long long)nb * ph * pw * (b.cin / 4))), dim3(256), 0, st, dcx, nb, ph, pw, b.cin / 4, dlow, b.cin / 4,
-                                       (float*)nullptr);
-                }
-            } else {
-                TZ(dlow, (size_t)nb * ph * pw * b.cin);
-                hipLaunchKernelGGL(t_resize_bwd, dim3(nblk((long long)nb * b.in_h * b.in_w * b.cin)), dim3(256), 0, st, dcx, nb, ph, pw, b.cin, b.in_h, b.in_w, 0, dlow);
-            }
-            dcx = dlow;
-        }
-        dy = dcx;  // gradient w.r.t. the previous tensor (block i-1's output, a concat for i in 7..11, the stem for i == 0)
-        TK(hipGetLastError());
-    }
-    // ---- stem
-    if ((t.flags & DYF_TRAIN_DROPOUT) && n.cfg.input_dropout > 0.0f) {  // adjoint of dropout_input: the same keep map on the gradient
-        const long long per = (long long)n.uh * n.uw * n.dim;
-        hipLaunchKernelGGL(t_dropout_map, dim3(nblk(per * nb)), dim3(256), 0, st, dy, (float*)dy, nb, per, 1.0f / (1.0f - n.cfg.input_dropout),
-                           keep_threshold16(n.cfg.input_dropout), rng_layer_salt(DYF_INPUT_DROP_SITE), t.row_keys);
-    }
-    const TConv gs{nb, n.uh, n.uw, cin, n.uh, n.uw, n.dim, 1, 1, 0};
-    if (param_grads) TS(conv_wgrad(e, gs, dy, t.x_up, w.g_stem_w, w.g_stem_b, st));
-    if (dinputs_dev) {
-        float* dxu = nullptr;
-        TA(dxu, (size_t)nb * n.uh * n.uw * cin);
-        TS(conv_dgrad(e, gs, dy, w.stem_w, nullptr, dxu, st));
-        float* dxi = dxu;
-        if (t.x_up != t.x_in) {
-            TZ(dxi, (size_t)nb * hw * cin);
-            hipLaunchKernelGGL(t_resize_bwd, dim3(nblk((long long)nb * n.uh * n.uw * cin)), dim3(256), 0, st, dxu, nb, H, W, cin, n.uh, n.uw, n.cfg.outer_nearest, dxi);
-        }
-        hipLaunchKernelGGL(t_nhwc_to_nchw, dim3(nblk((long long)nb * hw * n.cfg.in_channels)), dim3(256), 0, st, dxi, nb, hw, cin, 0, n.cfg.in_channels, dinputs_dev);
-    }
-    // ---- time MLP: dsilu = sum over blocks of dss . W_film ; temb -> SiLU is shared by all blocks
-    if (n.cfg.with_time_emb && param_grads) {
-        float *dtemb = nullptr, *dgl = nullptr;
-        TA(dtemb, (size_t)nb * n.tdim); TA(dgl, (size_t)nb * n.tdim);
-        hipLaunchKernelGGL(t_silu_bwd, dim3(nblk((long long)nb * n.tdim)), dim3(256), 0, st, t.temb, dsilu, (long long)nb * n.tdim, dtemb);
-        hipLaunchKernelGGL(t_linear_bwd_w, dim3(nblk(n.tdim * n.tdim)), dim3(256), 0, st, t.gl, dtemb, nb, n.tdim, n.tdim, 0, w.g_t_w2, w.g_t_b2);
-        hipLaunchKernelGGL(t_linear_bwd_x, dim3((unsigned)(nb * ((n.tdim + 15) / 16))), dim3(256), 0, st, t.gl, w.t_w2, dtemb, nb, n.tdim, n.tdim, 0, 0, dgl);
-        hipLaunchKernelGGL(t_gelu_bwd, dim3(nblk((long long)nb * n.tdim)), dim3(256), 0, st, t.l1, (long long)nb * n.tdim, dgl);
-        hipLaunchKernelGGL(t_linear_bwd_w, dim3(nblk(n.tdim * n.dim)), dim3(256), 0, st, t.e0, dgl, nb, n.dim, n.tdim, 0, w.g_t_w1, w.g_t_b1);
-        TK(hipGetLastError());
-    }
-    TK(hipStreamSynchronize(st));
-    tfree(e, tmp);
-#undef TA
-#undef TZ
-#undef TS
-    return DYF_OK;
+    return train_backward(e, slot, dout_dev, dinputs_dev, param_grads, (hipStream_t)stream);
 }
 
 // Copy gradients (and the updated BatchNorm running statistics) out, addressed by the reference's state_dict names, in
 // PyTorch's layouts: conv weights (cout, cin, kh, kw), ConvTranspose2d (cin, cout, kh, kw), Linear (out, in).
-// [co][tap][ci] -> (co, ci, tap), on the device
-__global__ void t_unpack_conv(const float* g, int cout, int cin, int taps, float* out) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (long long)cout * cin * taps) return;
-    const int tp = (int)(i % taps), ci = (int)((i / taps) % cin), co = (int)(i / ((long long)taps * cin));
-    out[i] = g[((size_t)co * taps + tp) * cin + ci];
-}
-static dyf_status train_export_impl(dyf_engine* e, int32_t which, int32_t n_tensors, const char* const* names, float* const* out_host, bool dev);
 dyf_status dyf_train_export(dyf_engine* e, int32_t which, int32_t n_tensors, const char* const* names, float* const* out_host) {
-    return train_export_impl(e, which, n_tensors, names, out_host, false);
+    if (!e || which < 0 || which > 1 || !names || !out_host) return fail(e, DYF_ERR_INVALID_ARGUMENT, "dyf_train_export: bad arguments");
+    TK(hipSetDevice(e->cfg.device));
+    return train_export(e, which, n_tensors, names, out_host, false);
 }
 // the same into DEVICE buffers (contiguous fp32, on the engine's GPU): no host round trip
 dyf_status dyf_train_export_dev(dyf_engine* e, int32_t which, int32_t n_tensors, const char* const* names, float* const* out_dev) {
-    return train_export_impl(e, which, n_tensors, names, out_dev, true);
-}
-static dyf_status train_export_impl(dyf_engine* e, int32_t which, int32_t n_tensors, const char* const* names, float* const* out_host, bool dev) {
-    if (!e || which < 0 || which > 1 || !names || !out_host) return fail(e, DYF_ERR_INVALID_ARGUMENT, "dyf_train_export: bad arguments");
-    if (e->net[which].rn) { TK(hipSetDevice(e->cfg.device)); return rn_train_export(e, which, n_tensors, names, out_host, dev); }
-    if (!e->train || !e->train->net[which].ready) return fail(e, DYF_ERR_STATE, "training needs arch unet_simple with loaded weights");
+    if (!e || which < 0 || which > 1 || !names || !out_dev) return fail(e, DYF_ERR_INVALID_ARGUMENT, "dyf_train_export: bad arguments");
     TK(hipSetDevice(e->cfg.device));
-    TK(hipDeviceSynchronize());
-    const Net& n = e->net[which];
-    const TNet& w = e->train->net[which];
-    auto pull = [&](const float* dev, size_t cnt) {
-        std::vector<float> h(cnt);
-        (void)hipMemcpy(h.data(), dev, cnt * sizeof(float), hipMemcpyDeviceToHost);
-        return h;
-    };
-    for (int q = 0; q < n_tensors; ++q) {
-        const std::string name = names[q];
-        float* out = out_host[q];
-        bool done = false;
-        auto flat = [&](const std::string& key, const float* dptr, size_t cnt) {
-            if (!done && name == key && dptr) {
-                if (dev) {
-                    (void)hipMemcpy(out, dptr, cnt * sizeof(float), hipMemcpyDeviceToDevice);
-                } else {
-                    const std::vector<float> h = pull(dptr, cnt);
-                    std::copy(h.begin(), h.end(), out);
-                }
-                done = true;
-            }
-        };
-        for (int i = 0; i < 12 && !done; ++i) {
-            const UBlock& b = n.blk[i];
-            const TBlockW& bw = w.blk[i];
-            const std::string pre = (i < 6 ? "input_ops." + std::to_string(i) : "output_ops." + std::to_string(i - 6));
-            const std::string conv = pre + ".ops." + (b.transposed ? "1" : "0"), norm = pre + ".ops." + (b.transposed ? "2" : "1");
-            if (name == conv + ".weight") {  // [co][tap][ci] -> (co, ci, kh, kw)
-                const int taps = b.k * b.k;
-                if (dev) {
-                    hipLaunchKernelGGL(t_unpack_conv, dim3(nblk((long long)b.cout * taps * b.cin)), dim3(256), 0, nullptr, bw.g_w, b.cout, b.cin, taps, out);
-                    done = true;
-                    continue;
-                }
-                const std::vector<float> h = pull(bw.g_w, (size_t)b.cout * taps * b.cin);
-                for (int co = 0; co < b.cout; ++co)
-                    for (int ci = 0; ci < b.cin; ++ci)
-                        for (int tp = 0; tp < taps; ++tp) out[((size_t)co * b.cin + ci) * taps + tp] = h[((size_t)co * taps + tp) * b.cin + ci];
-                done = true;
-            }
-            flat(conv + ".bias", bw.g_b, b.cout);
-            flat(norm + ".weight", bw.g_gamma, b.cout);
-            flat(norm + ".bias", bw.g_beta, b.cout);
-            flat(norm + ".running_mean", bw.rmean, b.cout);
-            flat(norm + ".running_var", bw.rvar, b.cout);
-            flat(pre + ".time_mlp.1.weight", bw.g_fw, (size_t)2 * b.cout * n.tdim);
-            flat(pre + ".time_mlp.1.bias", bw.g_fb, (size_t)2 * b.cout);
-        }
-        flat("time_emb_mlp.1.weight", w.g_t_w1, (size_t)n.tdim * n.dim);
-        flat("time_emb_mlp.1.bias", w.g_t_b1, n.tdim);
-        flat("time_emb_mlp.3.weight", w.g_t_w2, (size_t)n.tdim * n.tdim);
-        flat("time_emb_mlp.3.bias", w.g_t_b2, n.tdim);
-        flat("init_conv.weight", w.g_stem_w, (size_t)n.dim * n.cin_total);
-        flat("init_conv.bias", w.g_stem_b, n.dim);
-        flat("readout.0.bias", w.g_ro_b, n.cfg.out_channels);
-        if (!done && name == "readout.0.weight") {  // [co = dim][tap][ci = C] -> ConvTranspose2d (dim, C, 4, 4)
-            const int oc = n.cfg.out_channels;
-            if (dev) {
-                hipLaunchKernelGGL(t_unpack_conv, dim3(nblk((long long)n.dim * 16 * oc)), dim3(256), 0, nullptr, w.g_ro_w, n.dim, oc, 16, out);
-                continue;
-            }
-            const std::vector<float> h = pull(w.g_ro_w, (size_t)n.dim * 16 * oc);
-            for (int co = 0; co < n.dim; ++co)
-                for (int ci = 0; ci < oc; ++ci)
-                    for (int tp = 0; tp < 16; ++tp) out[((size_t)co * oc + ci) * 16 + tp] = h[((size_t)co * 16 + tp) * oc + ci];
-            done = true;
-        }
-        if (!done) return fail(e, DYF_ERR_INVALID_ARGUMENT, "dyf_train_export: unknown tensor '" + name + "'");
-    }
-    if (dev) TK(hipDeviceSynchronize());
-    return DYF_OK;
+    return train_export(e, which, n_tensors, names, out_dev, true);
 }
 
 // d(scale * mean-criterion(pred, target)) / d pred  (get_loss, src/utilities/utils.py:201-212; kinds as dyf_criterion)
@@ -2091,64 +1569,14 @@ __global__ void t_repack_conv(const float* raw, int cout, int cin, int taps, flo
     wt[((size_t)tp * cin + ci) * cout + co] = v;
 }
 
-// In-place refresh of an existing training copy (same shapes): one H2D copy per tensor, the two conv layouts written by a kernel.
-// Gradient buffers, tapes and every allocation stay as they are.
-static dyf_status train_refresh_weights(dyf_engine* e, int which, std::map<std::string, TensorView>& sd, bool dev) {
-    TNet& t = e->train->net[which];
-    const Net& n = e->net[which];
-    size_t stage_el = 0;
-    for (int i = 0; i < 12; ++i) stage_el = std::max(stage_el, (size_t)n.blk[i].cout * n.blk[i].cin * n.blk[i].k * n.blk[i].k);
-    stage_el = std::max(stage_el, (size_t)n.dim * 16 * n.cfg.out_channels);
-    stage_el = std::max(stage_el, (size_t)n.dim * n.cin_total);
-    std::vector<void*> tmp;
-    float* stage = nullptr;
-    dyf_status st0 = talloc(e, tmp, &stage, stage_el, false);
-    if (st0 != DYF_OK) return st0;
-    TK(hipDeviceSynchronize());
-    auto put = [&](float* dst, const std::string& key, size_t want) -> bool {
-        const TensorView& v = sd.at(key);
-        if ((size_t)v.numel() != want) throw std::out_of_range("size of " + key);
-        return hipMemcpy(dst, v.data, want * sizeof(float), dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice) == hipSuccess;
-    };
-    auto put_conv = [&](const std::string& key, int cout, int cin, int taps, float* w, float* wt) -> bool {
-        const size_t el = (size_t)cout * cin * taps;
-        if (dev) {  // the source is device memory: repack straight from it
-            const TensorView& v = sd.at(key);
-            if ((size_t)v.numel() != el) throw std::out_of_range("size of " + key);
-            hipLaunchKernelGGL(t_repack_conv, dim3(nblk((long long)el)), dim3(256), 0, nullptr, v.data, cout, cin, taps, w, wt);
-            return hipGetLastError() == hipSuccess;
-        }
-        if (!put(stage, key, el)) return false;
-        hipLaunchKernelGGL(t_repack_conv, dim3(nblk((long long)el)), dim3(256), 0, nullptr, stage, cout, cin, taps, w, wt);
-        return hipDeviceSynchronize() == hipSuccess;  // the staging buffer is overwritten by the next tensor
-    };
-    bool ok = true;
-    for (int i = 0; i < 12 && ok; ++i) {
-        const UBlock& b = n.blk[i];
-        TBlockW& w = t.blk[i];
-        const std::string pre = (i < 6 ? "input_ops." + std::to_string(i) : "output_ops." + std::to_string(i - 6));
-        const std::string conv = pre + ".ops." + (b.transposed ? "1" : "0"), norm = pre + ".ops." + (b.transposed ? "2" : "1");
-        ok = put_conv(conv + ".weight", b.cout, b.cin, b.k * b.k, w.w, w.wt) && put(w.b, conv + ".bias", b.cout) &&
-             put(w.gamma, norm + ".weight", b.cout) && put(w.beta, norm + ".bias", b.cout);
-        if (ok && !b.gn) ok = put(w.rmean, norm + ".running_mean", b.cout) && put(w.rvar, norm + ".running_var", b.cout);
-        if (ok && n.cfg.with_time_emb)
-            ok = put(w.fw, pre + ".time_mlp.1.weight", (size_t)2 * b.cout * n.tdim) && put(w.fb, pre + ".time_mlp.1.bias", (size_t)2 * b.cout);
-    }
-    if (ok && n.cfg.with_time_emb)
-        ok = put(t.t_w1, "time_emb_mlp.1.weight", (size_t)n.tdim * n.dim) && put(t.t_b1, "time_emb_mlp.1.bias", n.tdim) &&
-             put(t.t_w2, "time_emb_mlp.3.weight", (size_t)n.tdim * n.tdim) && put(t.t_b2, "time_emb_mlp.3.bias", n.tdim);
-    if (ok) ok = put_conv("init_conv.weight", n.dim, n.cin_total, 1, t.stem_w, t.stem_wt) && put(t.stem_b, "init_conv.bias", n.dim);
-    if (ok) ok = put_conv("readout.0.weight", n.dim, n.cfg.out_channels, 16, t.ro_w, t.ro_wt) && put(t.ro_b, "readout.0.bias", n.cfg.out_channels);
-    if (dev) (void)hipDeviceSynchronize();
-    tfree(e, tmp);
-    if (!ok) return fail(e, DYF_ERR_HIP, "dyf_train_load_weights: upload failed");
-    return DYF_OK;
-}
-
 // Refresh ONLY the training copy of a network's parameters (fp32, both conv layouts) -- what a training loop needs after every
 // optimizer.step().  dyf_load_weights also rebuilds everything the sampling path derives from the weights (BatchNorm folding,
 // phase-decomposed / fragment-ordered bf16 packs, FiLM tables: ~170 ms of host work for a unet_simple of dim 64); the sampling copy
 // is left as it is and must be reloaded with dyf_load_weights before the network is sampled again (the Python module tracks both).
+// One contract for both backbones: every tensor the copy holds must be in the caller's state_dict with its size (a missing one fails with
+// DYF_ERR_INVALID_ARGUMENT and leaves the copy unusable until dyf_load_weights), and the gradient buffers keep their contents.  (For
+// unet.Unet this call used to rebuild the copy through the host, which also zeroed the gradients: callers zero them with
+// dyf_train_zero_grads, as the Python module does after every export.)
 static dyf_status train_load_weights_impl(dyf_engine* e, int32_t which, int32_t n_tensors, const char* const* names,
                                           const float* const* data, const int64_t* const* shapes, const int32_t* ndims, bool dev);
 dyf_status dyf_train_load_weights(dyf_engine* e, int32_t which, int32_t n_tensors, const char* const* names, const float* const* data,
@@ -2166,27 +1594,8 @@ static dyf_status train_load_weights_impl(dyf_engine* e, int32_t which, int32_t 
         return fail(e, DYF_ERR_INVALID_ARGUMENT, "dyf_train_load_weights: bad arguments");
     TK(hipSetDevice(e->cfg.device));
     const Net& n = e->net[which];
-    if (n.rn && n.loaded) {  // ResNet-UNet: the training copy is rebuilt (device tensors are staged through the host)
-        std::map<std::string, TensorView> sd;
-        std::vector<std::vector<float>> stage;
-        if (dev) TK(hipDeviceSynchronize());
-        for (int i = 0; i < n_tensors; ++i) {
-            TensorView v;
-            v.shape.assign(shapes[i], shapes[i] + ndims[i]);
-            v.data = data[i];
-            if (dev) {
-                stage.emplace_back((size_t)v.numel());
-                TK(hipMemcpy(stage.back().data(), data[i], stage.back().size() * sizeof(float), hipMemcpyDeviceToHost));
-            }
-            sd[names[i]] = v;
-        }
-        if (dev) {
-            size_t k = 0;
-            for (int i = 0; i < n_tensors; ++i) sd[names[i]].data = stage[k++].data();
-        }
-        return rn_train_store_weights(e, which, sd);
-    }
-    if (n.rn || n.sc || !n.loaded || !e->train || !e->train->net[which].ready)
+    TrainNet* t = e->train ? e->train->net[which] : nullptr;
+    if (n.sc || !n.loaded || !t || !t->ready)
         return fail(e, DYF_ERR_STATE, "dyf_train_load_weights: arch unet_simple / unet with weights loaded once by dyf_load_weights");
     std::map<std::string, TensorView> sd;
     for (int i = 0; i < n_tensors; ++i) {
@@ -2195,13 +1604,42 @@ static dyf_status train_load_weights_impl(dyf_engine* e, int32_t which, int32_t 
         v.shape.assign(shapes[i], shapes[i] + ndims[i]);
         sd[names[i]] = v;
     }
-    // same tensors and shapes as the copy in place (dyf_load_weights validated those)
-    try {
-        return train_refresh_weights(e, which, sd, dev);
-    } catch (const std::exception& ex) {
-        e->train->net[which].ready = false;
-        return fail(e, DYF_ERR_INVALID_ARGUMENT, std::string("dyf_train_load_weights: state_dict does not match the loaded network: ") + ex.what());
+    // In place, the same tensors and shapes as the copy dyf_load_weights made: one copy per tensor, the two conv layouts written by a kernel
+    // (host tensors through one staging buffer).  Gradient buffers, tapes and every other allocation stay as they are.
+    size_t stage_el = 0;
+    for (auto& kv : t->P)
+        if (kv.second.conv && !dev) stage_el = std::max(stage_el, kv.second.n);
+    std::vector<void*> tmp;
+    float* stage = nullptr;
+    if (stage_el) {
+        dyf_status s = talloc(e, tmp, &stage, stage_el, false);
+        if (s != DYF_OK) return s;
     }
+    TK(hipDeviceSynchronize());
+    bool ok = true;
+    for (auto& kv : t->P) {
+        const RParam& p = kv.second;
+        auto it = sd.find(kv.first);
+        if (it == sd.end() || (size_t)it->second.numel() != p.n) {
+            tfree(e, tmp);
+            t->ready = false;
+            return fail(e, DYF_ERR_INVALID_ARGUMENT, "dyf_train_load_weights: state_dict does not match the loaded network: " + kv.first);
+        }
+        const float* src = it->second.data;
+        if (!p.conv) {
+            ok = hipMemcpy(p.w, src, p.n * sizeof(float), dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice) == hipSuccess;
+        } else {
+            if (!dev) ok = hipMemcpy(stage, src, p.n * sizeof(float), hipMemcpyHostToDevice) == hipSuccess;
+            hipLaunchKernelGGL(t_repack_conv, dim3(nblk((long long)p.n)), dim3(256), 0, nullptr, dev ? src : stage, p.cout, p.cin, p.taps, p.w, p.wt);
+            // (host tensors: the staging buffer is overwritten by the next one)
+            ok = ok && (dev ? hipGetLastError() : hipDeviceSynchronize()) == hipSuccess;
+        }
+        if (!ok) break;
+    }
+    if (dev) (void)hipDeviceSynchronize();
+    tfree(e, tmp);
+    if (!ok) return fail(e, DYF_ERR_HIP, "dyf_train_load_weights: upload failed");
+    return DYF_OK;
 }
 
 // Test seam (include/dyffusion_hip_testing.h): one training convolution on hash-random fp32 data through the fp32 matrix-core

@@ -347,7 +347,7 @@ bool thalo_conv3x3(const TConv& g, int mode, const float* A, const float* W, con
     const int per = (int)std::max<long long>(1, std::min<long long>(16, tiles * nblocks / htarget));
     const long long wgs = ((tiles + per - 1) / per + 7) / 8 * 8 * nblocks;  // whole groups of 8 tile ranges (XCD-aware order in the kernel)
     constexpr int XS = HP * 128 + 512;
-    if (!train_raise_dynamic_lds(t_halo3x3_16<64>, 2 * XS + 4 * 64 * 128)) return false;  // per device; the tap-by-tap form takes the layer
+    if (!train_raise_dynamic_lds<t_halo3x3_16<64>>(2 * XS + 4 * 64 * 128)) return false;  // per device; the tap-by-tap form takes the layer
     hipLaunchKernelGGL(t_halo3x3_16<64>, dim3((unsigned)wgs), dim3(256), 2 * XS + 4 * 64 * 128, st, g.h, g.w, CK, NC, A, wb, bias, C, tiles_x,
                        tiles_per_img, (int)tiles, per, nblocks);
     return true;

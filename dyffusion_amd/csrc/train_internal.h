@@ -34,15 +34,17 @@ __device__ __forceinline__ uint32_t pack_t16x2(float lo, float hi) {  // one v_c
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) is a PER-DEVICE attribute: the training launchers that need more than the 64 KB
 // default raise it once per (kernel, device) -- a process-wide flag left the second GPU of a process at the default, and its first
 // launch failed.  Returns false (and the launcher declines the shape) when the attribute cannot be set.
+// The kernel is the template ARGUMENT, so every kernel has a state of its own (keyed on the type of a function-pointer parameter, two
+// kernels of one signature -- two instantiations of one kernel template -- would share it, and the second would launch unraised).
 #include <atomic>
-template <typename K>
-static inline bool train_raise_dynamic_lds(K kernel, int bytes) {
-    static std::atomic<unsigned char> done[64];  // per instantiation (= per kernel); 0 not tried, 1 set, 2 failed
+template <auto Kernel>
+static inline bool train_raise_dynamic_lds(int bytes) {
+    static std::atomic<unsigned char> done[64];  // per kernel; 0 not tried, 1 set, 2 failed
     int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) == hipSuccess;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) == hipSuccess;
     unsigned char st = done[dev].load(std::memory_order_acquire);
     if (st == 0) {
-        st = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) == hipSuccess ? 1 : 2;
+        st = hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) == hipSuccess ? 1 : 2;
         done[dev].store(st, std::memory_order_release);
     }
     return st == 1;

@@ -6,10 +6,14 @@
 // keys, dropout on the probabilities), nearest x2 upsampling, 4x4 / stride-2 down convs, the 7x7 stem, the 1x1 head, skip
 // concatenations, the time MLP and the per-block FiLM heads.
 //
+// The same mechanism records arch unet_simple (src/models/unet_simple.py:13-82, 164-197; us_walk): BatchNorm2d on batch or running
+// statistics, the x2 bilinear upsample of a concatenation that is never written, the outer resample, the ConvTranspose2d readout.
+//
 // This file is #included by train.hip (it uses that file's kernels and helpers: convolutions on the fp32 matrix cores, the
-// GroupNorm / FiLM / dropout kernels, the dense layers, the caching allocator).  Everything is fp32, NHWC.  Structure: a small
+// normalisation / FiLM / dropout kernels, the dense layers, the caching allocator).  Everything is fp32, NHWC.  Structure: a small
 // tape -- every op of the forward pushes a closure that, given the gradient of its output, ACCUMULATES into the gradients of its
-// inputs and of its parameters; dyf_train_backward runs the closures in reverse.  The new kernels below are written for
+// inputs and of its parameters; dyf_train_backward runs the closures in reverse.  A layer walk is written once, as a template over
+// its context: RCtx launches (and records, or -- fp32 sampling -- bumps through the engine's arena), RCount sizes that arena.  The new kernels below are written for
 // correctness (one thread per output, plain loops): the convolutions, 97 % of the FLOPs, run on train_gemm.hip.
 #include <deque>
 #include <functional>
@@ -22,10 +26,11 @@ struct RParam {              // one parameter in its training layout, and its gr
     float* wt = nullptr;     // convs that are NOT weight-standardised: [tap][cin][cout] (forward layout)
     float* g = nullptr;
     size_t n = 0;
-    int conv = 0, cout = 0, cin = 0, taps = 0;
+    int conv = 0, cout = 0, cin = 0, taps = 0;   // conv: any 4-d weight as (cout, cin, kh, kw) -- a ConvTranspose2d (dim, C, 4, 4) is [dim][tap][C]
+    bool stat = false;       // a BatchNorm running statistic: no gradient; what leaves by its name is the (updated) statistic itself
 };
 
-struct RTNet {
+struct TrainNet {
     std::map<std::string, RParam> P;
     std::vector<void*> owned;
     float* g_arena = nullptr;     // every parameter's gradient buffer is a 256-byte-aligned slice of ONE block: zeroing the gradients is
@@ -37,6 +42,7 @@ struct RT {                  // an activation of the recorded forward and (durin
     float* p = nullptr;
     float* g = nullptr;
     size_t n = 0;
+    uint8_t need = 0;        // who wants its gradient: 0 whoever produced it, 1 only a caller that asked for the network input's, 2 nobody
 };
 
 struct RTape {
@@ -45,6 +51,7 @@ struct RTape {
     std::deque<RT> ts;                                         // stable addresses
     std::vector<std::function<dyf_status()>> back;             // run in reverse
     RT *out = nullptr, *x_in = nullptr;
+    int in_lo = 0;               // first channel of the caller's `inputs` inside x_in (unet.Unet concatenates the condition first)
     uint32_t* row_keys = nullptr;
     std::shared_ptr<void> ctx;   // the recording context the closures point into (RCtx), alive until the slot is re-recorded
 };
@@ -713,7 +720,7 @@ __global__ void t_split2_acc(const float* d, int ca, int cb, long long pixels, f
     else db[p * cb + (c - ca)] += d[i];
 }
 // [co][tap][ci] -> (co, ci, tap): PyTorch's conv-weight layout (gradient export)
-__global__ void t_unpack_conv_r(const float* g, int cout, int cin, int taps, float* out) {
+__global__ void t_unpack_conv(const float* g, int cout, int cin, int taps, float* out) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (long long)cout * cin * taps) return;
     const int tp = (int)(i % taps), ci = (int)((i / taps) % cin), co = (int)(i / ((long long)taps * cin));
@@ -730,13 +737,18 @@ __global__ void t_w_transpose(const float* w, int cout, int K, float* wt) {
 // ------------------------------------------------------------------------------------------------ the recording context
 struct RCtx {
     dyf_engine* e;
-    dyf::RTNet& W;
+    dyf::TrainNet& W;
     dyf::RTape& T;
     const dyf_net_config& c;
     hipStream_t st;
     int nb;
     bool drop_on, param_grads = true;
+    bool want_dinputs = false;           // the backward's caller asked for the gradient of the network input
     int site = 0;
+    double* sums = nullptr;              // the (S | Q) sums of the norm whose statistics are being taken (stat_sums), reused op after op
+    size_t sums_cap = 0, sums_hint = 0;  // (sums_hint: the largest request the walk expects, so that the block is taken once)
+    double* norm_bwd = nullptr;          // the sums of the norm adjoint that is running (A | B | Cc | Dd | S1 | S2): one block per backward,
+    size_t norm_bwd_doubles = 0;         // sized for the largest norm the forward recorded
     std::vector<void*>* tmp = nullptr;   // backward temporaries (gradients of activations), freed when the backward is done
     dyf_status err = DYF_OK;
     FwdMem mem{};                        // where the forward's tensors come from: the tape's blocks, or the sampling arena
@@ -781,8 +793,19 @@ struct RCtx {
         if (talloc(e, *tmp, &p, n, zero) != DYF_OK) err = DYF_ERR_HIP;
         return p;
     }
+    // does anything upstream of t take a gradient?  (the network input and what is resampled from it: only when the caller asked)
+    bool wants(const dyf::RT* t) const { return t->need == 0 || (t->need == 1 && want_dinputs); }
+    double* stat_sums(size_t n) {  // n zeroed doubles; one stream orders the reuse (the statistics are final before the next norm's memset)
+        if (n > sums_cap) {
+            sums_cap = std::max(n, sums_hint);
+            if (mem.get(&sums, sums_cap) != DYF_OK) err = DYF_ERR_HIP;
+        }
+        if (sums && hipMemsetAsync(sums, 0, n * sizeof(double), st) != hipSuccess) err = DYF_ERR_HIP;
+        return sums;
+    }
     dyf::RParam& P(const std::string& k) { return W.P.at(k); }
-    RDrop drop(float p, size_t per) {
+    // salt_site: the generator's site number when it is not the execution order (unet_simple: block i is site i, dropout_input site 12)
+    RDrop drop(float p, size_t per, int salt_site = -1) {
         RDrop d{};
         if (p <= 0.0f) return d;            // p = 0 layers draw nothing and consume no site (as the sampling path's DropCtx)
         const int s = site++;
@@ -796,7 +819,7 @@ struct RCtx {
         d.on = 1;
         d.scale = 1.0f / (1.0f - p);
         d.thresh16 = keep_threshold16(p);
-        d.salt = rng_layer_salt((uint32_t)s);
+        d.salt = rng_layer_salt((uint32_t)(salt_site >= 0 ? salt_site : s));
         d.row_keys = T.row_keys;
         return d;
     }
@@ -817,7 +840,7 @@ struct RCtx {
         }
         dyf::RT* y = make((size_t)nb * ho * wo * cout);
         if (conv_fwd(e, g, x->p, wht, pb ? pb->w : nullptr, y->p, st) != DYF_OK) err = DYF_ERR_HIP;
-        back([=, this]() -> dyf_status {
+        back([=]() -> dyf_status {
             if (!y->g) return DYF_OK;  // nothing downstream needed this output
             dyf::RParam& qw = P(name + ".weight");
             if (param_grads) {
@@ -832,7 +855,7 @@ struct RCtx {
                     if (r != DYF_OK) return r;
                 }
             }
-            if (x != T.x_in || T.x_in->g) {  // the network input needs a gradient only when the caller asked for it
+            if (wants(x)) {
                 float* dx = tbuf(x->n);
                 dyf_status r = conv_dgrad(e, g, y->g, wh, nullptr, dx, st);
                 if (r != DYF_OK) return r;
@@ -843,67 +866,94 @@ struct RCtx {
         return dbg(y, "conv");
     }
 
-    // ---- GroupNorm + FiLM + SiLU + Dropout (unet.Block, unet.py:58-76); ss (nb, 2C) = (scale | shift) or null
-    dyf::RT* gn_act(dyf::RT* z, int hw, int C, const std::string& name, dyf::RT* ss, float p_drop) {
-        const int G = c.groups, nidx = nb * G;
+    // ---- normalisation + FiLM + activation + Dropout: GroupNorm + SiLU of unet.Block (unet.py:58-76), BatchNorm2d / GroupNorm(8) +
+    // (Leaky)ReLU of UNetBlock (unet_simple.py:13-82).  kind 0: BatchNorm on batch statistics (updates name.running_mean / .running_var,
+    // momentum 0.1), 1: BatchNorm on the running statistics (no sums are taken), 2: GroupNorm(G).  ss (nb, 2C) = (scale | shift) or null.
+    // ppb_rec: pixels per workgroup of the sum kernels of a RECORDED forward, the caller's rule (norm_ppb_*); a sampling forward takes ONE
+    // workgroup per sample -- every sum meets its zero-filled slot once, no order of atomics to depend on.
+    dyf::RT* norm_act(dyf::RT* z, int hw, int C, const std::string& name, dyf::RT* ss, float p_drop, int kind, int G, int act, int ppb_rec,
+                      int salt_site = -1) {
+        const int gn = kind == 2 ? 1 : 0, nidx = gn ? nb * G : C;
         float *mean = fbuf(nidx), *rstd = fbuf(nidx);
-        double* S = nullptr;
-        if (mem.get(&S, (size_t)nb * C * 2, true) != DYF_OK) err = DYF_ERR_HIP;
-        double* Q = S + (size_t)nb * C;
-        // pixels per workgroup: about 2 048 workgroups per launch on these planes (16 pixels each left 14 400 workgroups of 60 x 60 x 64 rows
-        // with four fp64 atomics per thread: 104 us per backward-sums launch, 10x its traffic time)
-        // (sampling: ONE workgroup per sample -- every sum meets its zero-filled slot once, no order of atomics to depend on)
-        const int ppb = !mem.recording() ? hw : std::max(std::max(16, (hw + 255) / 256), (int)std::min<long long>(128, ((long long)hw * nb + 2047) / 2048));
-        hipLaunchKernelGGL(t_nc_sums, dim3((hw + ppb - 1) / ppb, nb), dim3(256), 0, st, z->p, hw, C, ppb, S, Q);
-        hipLaunchKernelGGL(t_stats_finalize, dim3(nblk(std::max(nidx, C))), dim3(256), 0, st, 2, S, Q, nb, hw, C, G, (float*)nullptr, (float*)nullptr,
-                           mean, rstd);
-        const RDrop d = drop(p_drop, (size_t)hw * C);
-        const TNorm a{nb, hw, C, G, 1, ACT_SILU, mean, rstd, P(name + ".weight").w, P(name + ".bias").w, ss ? ss->p : nullptr, d.on, d.scale,
+        const int ppb = mem.recording() ? ppb_rec : hw;
+        double *S = nullptr, *Q = nullptr;
+        if (kind != 1) {
+            S = stat_sums((size_t)nb * C * 2);
+            Q = S + (size_t)nb * C;
+            hipLaunchKernelGGL(t_nc_sums, dim3((hw + ppb - 1) / ppb, nb), dim3(256), 0, st, z->p, hw, C, ppb, S, Q);
+        }
+        hipLaunchKernelGGL(t_stats_finalize, dim3(nblk(std::max(nidx, C))), dim3(256), 0, st, kind, S, Q, nb, hw, C, G,
+                           gn ? (float*)nullptr : P(name + ".running_mean").w, gn ? (float*)nullptr : P(name + ".running_var").w, mean, rstd);
+        const RDrop d = drop(p_drop, (size_t)hw * C, salt_site);
+        const TNorm a{nb, hw, C, G, gn, act, mean, rstd, P(name + ".weight").w, P(name + ".bias").w, ss ? ss->p : nullptr, d.on, d.scale,
                       d.thresh16, d.salt, d.row_keys, d.mask};
         dyf::RT* y = make(z->n);
         launch_t_norm_fwd(a, z->p, y->p, st);
-        back([=, this]() -> dyf_status {
+        const size_t nS = ((size_t)std::max(nidx, C) + 3) / 4 * 4;  // floats of S1 and of S2 (16-byte aligned behind the doubles)
+        norm_bwd_doubles = std::max(norm_bwd_doubles, (size_t)nb * C * 4 + nS);
+        back([=]() -> dyf_status {
             if (!y->g) return DYF_OK;
-            double* R = nullptr;
-            if (talloc(e, *tmp, &R, (size_t)nb * C * 4, true) != DYF_OK) return DYF_ERR_HIP;
-            double *A = R, *B = R + (size_t)nb * C, *Cc = R + (size_t)2 * nb * C, *Dd = R + (size_t)3 * nb * C;
-            float *S1 = tbuf(std::max(nidx, C)), *S2 = tbuf(std::max(nidx, C));
+            if (!norm_bwd && talloc(e, *tmp, &norm_bwd, norm_bwd_doubles, false) != DYF_OK) return DYF_ERR_HIP;
+            double *A = norm_bwd, *B = A + (size_t)nb * C, *Cc = A + (size_t)2 * nb * C, *Dd = A + (size_t)3 * nb * C;
+            if (hipMemsetAsync(A, 0, (size_t)nb * C * 4 * sizeof(double), st) != hipSuccess) return DYF_ERR_HIP;
+            float *S1 = (float*)(A + (size_t)nb * C * 4), *S2 = S1 + nS;
             float* dss = ss ? tbuf((size_t)nb * 2 * C) : nullptr;
             hipLaunchKernelGGL(t_norm_bwd_sums, dim3((hw + ppb - 1) / ppb, nb), dim3(256), 0, st, a, z->p, y->g, ppb, A, B, Cc, Dd);
-            hipLaunchKernelGGL(t_norm_bwd_combine, dim3(nblk(std::max(nb * C, nidx))), dim3(256), 0, st, a, A, B, Cc, Dd,
-                               param_grads ? P(name + ".weight").g : (float*)nullptr, param_grads ? P(name + ".bias").g : (float*)nullptr, dss, S1, S2, 1);
+            // (running statistics: the norm is a fixed affine map, S1 = S2 = 0)
+            hipLaunchKernelGGL(t_norm_bwd_combine, dim3(nblk(std::max(nb * C, nb * G))), dim3(256), 0, st, a, A, B, Cc, Dd,
+                               param_grads ? P(name + ".weight").g : (float*)nullptr, param_grads ? P(name + ".bias").g : (float*)nullptr, dss, S1, S2,
+                               kind != 1 ? 1 : 0);
             float* dz = tbuf(z->n);
-            launch_t_norm_bwd_apply(a, z->p, y->g, S1, S2, 1.0f / ((float)hw * (C / G)), dz, st);
+            launch_t_norm_bwd_apply(a, z->p, y->g, S1, S2, gn ? 1.0f / ((float)hw * (C / G)) : 1.0f / ((float)nb * hw), dz, st);
             accum(z, dz);
             if (ss) accum(ss, dss);
             return DYF_OK;
         });
-        return dbg(y, "gn_act");
+        return dbg(y, "norm_act");
     }
 
-    // ---- y (rows, O) = Linear(f(x (rows, K))), f = SiLU when pre (FiLM heads: mlp = Sequential(SiLU, Linear), unet.py:93)
-    dyf::RT* linear(dyf::RT* x, int rows, int K, int O, const std::string& name, int pre) {
+    // ---- y (rows, O) = Linear(f(x (rows, K))), f = SiLU when pre (FiLM heads: mlp = Sequential(SiLU, Linear), unet.py:93).
+    // shared_silu: x is the alias silu_shared made; the adjoint adds its d silu(x) into x's gradient (zero on first use) and leaves silu' to it
+    dyf::RT* linear(dyf::RT* x, int rows, int K, int O, const std::string& name, int pre, bool shared_silu = false) {
         dyf::RT* y = make((size_t)rows * O);
         hipLaunchKernelGGL(t_linear_fwd, dim3((unsigned)((O + 3) / 4), (unsigned)((rows + 15) / 16)), dim3(256), 0, st, x->p, P(name + ".weight").w, P(name + ".bias").w, rows, K, O, pre, y->p);
-        back([=, this]() -> dyf_status {
+        back([=]() -> dyf_status {
             if (!y->g) return DYF_OK;
             if (param_grads)
                 hipLaunchKernelGGL(t_linear_bwd_w, dim3(nblk((long long)O * K)), dim3(256), 0, st, x->p, y->g, rows, K, O, pre, P(name + ".weight").g,
                                    P(name + ".bias").g);
-            float* dx = tbuf(x->n);
+            if (!wants(x)) return DYF_OK;
+            float* dx = shared_silu ? grad(x) : tbuf(x->n);
             hipLaunchKernelGGL(t_linear_bwd_x, dim3((unsigned)(rows * ((K + 15) / 16))), dim3(256), 0, st, x->p, P(name + ".weight").w, y->g, rows, K, O,
-                               pre, 0, dx);
-            accum(x, dx);
+                               shared_silu ? 0 : pre, shared_silu ? 1 : 0, dx);
+            if (!shared_silu) accum(x, dx);
             return DYF_OK;
         });
         return dbg(y, "linear");
+    }
+    // ---- SiLU(x) feeding several `linear(.., pre = 1, shared_silu)` heads (the 12 FiLM heads of unet_simple, unet_simple.py:29,66): an alias
+    // of x -- the heads apply the SiLU themselves -- whose gradient collects d silu(x) head by head; silu' is applied once, here.  x leads
+    // to parameters only (the time MLP), so without parameter gradients nothing is launched.
+    dyf::RT* silu_shared(dyf::RT* x) {
+        T.ts.emplace_back();
+        dyf::RT* y = &T.ts.back();
+        y->p = x->p;
+        y->n = x->n;
+        back([=]() -> dyf_status {
+            if (!y->g || !param_grads) return DYF_OK;
+            float* dx = tbuf(x->n);
+            hipLaunchKernelGGL(t_silu_bwd, dim3(nblk((long long)x->n)), dim3(256), 0, st, x->p, y->g, (long long)x->n, dx);
+            accum(x, dx);
+            return DYF_OK;
+        });
+        return y;
     }
     // ---- LearnedSinusoidalPosEmb features (rows, 2 half + 1) of the time values; the frequencies are a parameter
     dyf::RT* learned_sinu(const float* time_dev, int half) {
         dyf::RT* y = make((size_t)nb * (2 * half + 1));
         const std::string name = "time_emb_mlp.0.weights";
         hipLaunchKernelGGL(t_learned_sinu_fwd, dim3(nblk((long long)nb * (2 * half + 1))), dim3(256), 0, st, time_dev, P(name).w, nb, half, y->p);
-        back([=, this]() -> dyf_status {
+        back([=]() -> dyf_status {
             if (!y->g || !param_grads) return DYF_OK;
             hipLaunchKernelGGL(t_learned_sinu_bwd, dim3(1), dim3(256), 0, st, time_dev, P(name).w, y->g, nb, half, P(name).g);
             return DYF_OK;
@@ -911,17 +961,19 @@ struct RCtx {
         return dbg(y, "learned_sinu");
     }
     // ---- Dropout over a whole tensor (dropout_input / dropout_input_for_residual, unet.py:276-277); per = elements of one sample
-    dyf::RT* dropout(dyf::RT* x, long long per, float p) {
-        const RDrop d = drop(p, (size_t)per);
+    // in_place (unet_simple's dropout_input on the stem's output, unet_simple.py:116,168): x is overwritten and returned -- its producer must
+    // not need its own output for its adjoint (a conv does not) -- and the adjoint maps x's gradient where it lies
+    dyf::RT* dropout(dyf::RT* x, long long per, float p, bool in_place = false, int salt_site = -1) {
+        const RDrop d = drop(p, (size_t)per, salt_site);
         if (!d.on && !d.mask) return x;
-        dyf::RT* y = make(x->n);
+        dyf::RT* y = in_place ? x : make(x->n);
         if (d.mask) hipLaunchKernelGGL(t_mask_map, dim3(nblk((long long)x->n)), dim3(256), 0, st, x->p, y->p, (long long)x->n, d.scale, d.mask);
         else hipLaunchKernelGGL(t_dropout_map, dim3(nblk((long long)x->n)), dim3(256), 0, st, x->p, y->p, nb, per, d.scale, d.thresh16, d.salt, d.row_keys);
-        back([=, this]() -> dyf_status {
+        back([=]() -> dyf_status {
             if (!y->g) return DYF_OK;
-            float* dx = tbuf(x->n);  // the adjoint is the same keep map on the gradient
+            float* dx = in_place ? y->g : tbuf(x->n);  // the adjoint is the same keep map on the gradient
             hipLaunchKernelGGL(t_dropout_map, dim3(nblk((long long)x->n)), dim3(256), 0, st, y->g, dx, nb, per, d.scale, d.thresh16, d.salt, d.row_keys);
-            accum(x, dx);
+            if (!in_place) accum(x, dx);
             return DYF_OK;
         });
         return dbg(y, "dropout");
@@ -931,6 +983,7 @@ struct RCtx {
         dyf::RT* y = make((size_t)nb * hw * cin);
         hipLaunchKernelGGL(t_nchw_cat_to_nhwc, dim3(nblk((long long)nb * hw * cin)), dim3(256), 0, st, src[0].p, src[0].ch, src[1].p, src[1].ch, src[2].p,
                            src[2].ch, nb, hw, y->p);
+        y->need = 1;
         return dbg(y, "inputs");
     }
     // ---- per-row time values: the caller's, or one value for the whole batch (a sampling plan's step)
@@ -943,17 +996,16 @@ struct RCtx {
     dyf::RT* sinusoid(const float* time_dev, int dim) {
         dyf::RT* y = make((size_t)nb * dim);
         hipLaunchKernelGGL(t_sinusoid, dim3(nblk(nb * dim)), dim3(256), 0, st, time_dev, nb, dim, y->p);
+        y->need = 2;  // a function of the time values alone
         return dbg(y, "sinusoid");
     }
     dyf::RT* gelu(dyf::RT* x) {
         dyf::RT* y = make(x->n);
         hipLaunchKernelGGL(t_gelu_fwd, dim3(nblk((long long)x->n)), dim3(256), 0, st, x->p, (long long)x->n, y->p);
-        back([=, this]() -> dyf_status {
+        back([=]() -> dyf_status {
             if (!y->g) return DYF_OK;
-            float* d = tbuf(x->n);
-            if (hipMemcpyAsync(d, y->g, x->n * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess) return DYF_ERR_HIP;
-            hipLaunchKernelGGL(t_gelu_bwd, dim3(nblk((long long)x->n)), dim3(256), 0, st, x->p, (long long)x->n, d);
-            accum(x, d);
+            hipLaunchKernelGGL(t_gelu_bwd, dim3(nblk((long long)x->n)), dim3(256), 0, st, x->p, (long long)x->n, y->g);  // in place: y is done with it
+            accum(x, y->g);
             return DYF_OK;
         });
         return dbg(y, "gelu");
@@ -961,7 +1013,7 @@ struct RCtx {
     dyf::RT* add(dyf::RT* a, dyf::RT* b) {
         dyf::RT* y = make(a->n);
         launch_t_sum2(a->p, b->p, (long long)a->n, y->p, st);
-        back([=, this]() -> dyf_status {
+        back([=]() -> dyf_status {
             if (!y->g) return DYF_OK;
             // y's gradient goes to both inputs: b gets a copy / an add first, then a may take the buffer over (y is done with it)
             if (b->g) {
@@ -985,7 +1037,7 @@ struct RCtx {
         }
         dyf::RT* y = make((size_t)pixels * (ca + cb));
         launch_t_concat2(a->p, ca, b->p, cb, pixels, y->p, st);
-        back([=, this]() -> dyf_status {
+        back([=]() -> dyf_status {
             if (!y->g) return DYF_OK;
             hipLaunchKernelGGL(t_split2_acc, dim3(nblk(pixels * (ca + cb))), dim3(256), 0, st, y->g, ca, cb, pixels, grad(a), grad(b));
             return DYF_OK;
@@ -995,12 +1047,82 @@ struct RCtx {
     dyf::RT* up2_nearest(dyf::RT* x, int h, int w, int C) {
         dyf::RT* y = make(x->n * 4);
         hipLaunchKernelGGL(t_up2n_fwd, dim3(nblk((long long)y->n)), dim3(256), 0, st, x->p, nb, h, w, C, y->p);
-        back([=, this]() -> dyf_status {
+        back([=]() -> dyf_status {
             if (!y->g) return DYF_OK;
             hipLaunchKernelGGL(t_up2n_bwd, dim3(nblk((long long)x->n)), dim3(256), 0, st, y->g, nb, h, w, C, grad(x));
             return DYF_OK;
         });
         return dbg(y, "up2_nearest");
+    }
+    // ---- x2 bilinear upsample (align_corners=False) in front of a decoder conv (unet_simple.py:50-52) of x (nb, h, w, ca) or, with x2
+    // (nb, h, w, cb), of a torch.cat([x, x2]) (:176-177) that is never written: the gather reads both parts and its adjoint writes the two
+    // gradients, no concat tensor and no split pass.  Channel counts that are no multiples of 4 and target sizes other than (2h, 2w) take the
+    // general resample, on the concatenation made by `cat`.
+    dyf::RT* up2_bilinear(dyf::RT* x, int ca, dyf::RT* x2, int cb, int h, int w, int oh, int ow) {
+        const int C = ca + (x2 ? cb : 0);
+        const bool up2 = C % 4 == 0 && oh == 2 * h && ow == 2 * w;
+        if (x->n != (size_t)nb * h * w * ca || (x2 && x2->n != (size_t)nb * h * w * cb)) {  // (a skip of another plane: never read past it)
+            err = DYF_ERR_INVALID_ARGUMENT;
+            return make((size_t)nb * oh * ow * C);
+        }
+        if (x2 && !(up2 && ca % 4 == 0 && cb % 4 == 0)) {
+            x = cat(x, ca, x2, cb, (long long)nb * h * w);
+            x2 = nullptr;
+        }
+        const int Ca4 = x2 ? ca / 4 : C / 4;
+        dyf::RT* y = make((size_t)nb * oh * ow * C);
+        if (up2) hipLaunchKernelGGL(t_up2x_fwd, dim3(nblk((long long)nb * oh * ow * (C / 4))), dim3(256), 0, st, x->p, nb, h, w, C / 4, y->p, Ca4, x2 ? x2->p : (const float*)nullptr);
+        else hipLaunchKernelGGL(t_resize_fwd, dim3(nblk((long long)y->n)), dim3(256), 0, st, x->p, nb, h, w, C, oh, ow, 0, y->p);
+        back([=]() -> dyf_status {
+            if (!y->g) return DYF_OK;
+            if (!up2) {
+                hipLaunchKernelGGL(t_resize_bwd, dim3(nblk((long long)y->n)), dim3(256), 0, st, y->g, nb, h, w, C, oh, ow, 0, grad(x));
+                return DYF_OK;
+            }
+            float *dx = tbuf(x->n), *dx2 = x2 ? tbuf(x2->n) : nullptr;  // the kernel writes every element of both
+            hipLaunchKernelGGL(t_up2x_bwd, dim3(nblk((long long)nb * h * w * (C / 4))), dim3(256), 0, st, y->g, nb, h, w, C / 4, dx, Ca4, dx2);
+            accum(x, dx);
+            if (x2) accum(x2, dx2);
+            return DYF_OK;
+        });
+        return dbg(y, "up2_bilinear");
+    }
+    // ---- F.interpolate(size=(oh, ow)), bilinear (align_corners=False) or nearest: unet_simple's outer resample; the identity when the sizes match
+    dyf::RT* resize(dyf::RT* x, int h, int w, int C, int oh, int ow, int nearest) {
+        if (h == oh && w == ow) return x;
+        dyf::RT* y = make((size_t)nb * oh * ow * C);
+        y->need = x->need;
+        hipLaunchKernelGGL(t_resize_fwd, dim3(nblk((long long)y->n)), dim3(256), 0, st, x->p, nb, h, w, C, oh, ow, nearest, y->p);
+        back([=]() -> dyf_status {
+            if (!y->g || !wants(x)) return DYF_OK;
+            hipLaunchKernelGGL(t_resize_bwd, dim3(nblk((long long)y->n)), dim3(256), 0, st, y->g, nb, h, w, C, oh, ow, nearest, grad(x));
+            return DYF_OK;
+        });
+        return dbg(y, "resize");
+    }
+    // ---- ConvTranspose2d(cin -> C, 4, stride 2, pad 1), unet_simple's readout (unet_simple.py:136), as the DATA GRADIENT of the conv C -> cin
+    // (4 x 4 / 2 / 1) whose [cin][tap][C] weight the packed (cin, C, 4, 4) tensor is; the adjoint is that conv's weight gradient with x in the
+    // place of dz, and its forward (the transposed pack) for the gradient of x
+    dyf::RT* conv_transpose4s2(dyf::RT* x, int h, int w, int cin, int C, const std::string& name) {
+        const TConv g{nb, 2 * h, 2 * w, C, h, w, cin, 4, 2, 1};
+        dyf::RT* y = make((size_t)nb * 4 * h * w * C);
+        if (conv_dgrad(e, g, x->p, P(name + ".weight").w, P(name + ".bias").w, y->p, st) != DYF_OK) err = DYF_ERR_HIP;
+        back([=]() -> dyf_status {
+            if (!y->g) return DYF_OK;
+            dyf::RParam& qw = P(name + ".weight");
+            if (param_grads) {
+                dyf_status r = conv_wgrad(e, g, x->p, y->g, qw.g, nullptr, st);
+                if (r != DYF_OK) return r;
+                launch_bias_grad(y->g, (long long)nb * 4 * h * w, C, P(name + ".bias").g, st);
+            }
+            if (!wants(x)) return DYF_OK;
+            float* dx = tbuf(x->n);
+            dyf_status r = conv_fwd(e, g, y->g, qw.wt, nullptr, dx, st);
+            if (r != DYF_OK) return r;
+            accum(x, dx);
+            return DYF_OK;
+        });
+        return dbg(y, "conv_transpose4s2");
     }
     dyf::RT* layernorm(dyf::RT* x, int hw, int C, const std::string& gname, float p_drop) {
         float2* stats = nullptr;
@@ -1008,7 +1130,7 @@ struct RCtx {
         const RDrop d = drop(p_drop, (size_t)hw * C);
         dyf::RT* y = make(x->n);
         hipLaunchKernelGGL(t_ln_fwd, dim3(nblk((long long)nb * hw * 16)), dim3(256), 0, st, x->p, P(gname).w, nb, hw, C, d, y->p, stats);
-        back([=, this]() -> dyf_status {
+        back([=]() -> dyf_status {
             if (!y->g) return DYF_OK;
             if (param_grads) {
                 if (C <= 256 && 256 % C == 0)
@@ -1042,7 +1164,7 @@ struct RCtx {
         hipLaunchKernelGGL(t_la_outer_finish, dim3(nblk(mcount)), dim3(256), 0, st, part, nsplit, mcount, 1.0f / (float)hw, ctx);
         dyf::RT* y = make(tot);
         hipLaunchKernelGGL(t_la_out, dim3(pchunks, nb), dim3(256), 0, st, ctx, sq, hw, scale, y->p);
-        back([=, this]() -> dyf_status {
+        back([=]() -> dyf_status {
             if (!y->g) return DYF_OK;
             float* dctx = tbuf((size_t)nb * RH * RD * RD);
             float* dq = tbuf(qkv->n);
@@ -1075,7 +1197,7 @@ struct RCtx {
         const RDrop d = drop(p_drop, (size_t)RH * N * N);
         dyf::RT* y = make((size_t)nb * N * RHID);
         hipLaunchKernelGGL(t_at_fwd, dim3(nblk(rows, 64)), dim3(64), 0, st, qkv->p, N, rows, scale, d, Pm, y->p);
-        back([=, this]() -> dyf_status {
+        back([=]() -> dyf_status {
             if (!y->g) return DYF_OK;
             float* dS = tbuf((size_t)rows * N);
             float* dq = tbuf(qkv->n);
@@ -1123,13 +1245,17 @@ struct RCount {
         if (ws) { take((size_t)cout * k * k * cin); take((size_t)cout * k * k * cin); take(cout); }
         return make((size_t)nb * ho * wo * cout);
     }
-    dyf::RT* gn_act(dyf::RT* z, int, int C, const std::string&, dyf::RT*, float) {
-        take((size_t)nb * c.groups); take((size_t)nb * c.groups); take((size_t)nb * C * 2, sizeof(double));
+    size_t sums_cap = 0, sums_hint = 0;
+    dyf::RT* norm_act(dyf::RT* z, int, int C, const std::string&, dyf::RT*, float, int kind, int G, int, int, int = -1) {
+        const size_t nidx = kind == 2 ? (size_t)nb * G : (size_t)C;
+        take(nidx); take(nidx);
+        if (kind != 1 && (size_t)nb * C * 2 > sums_cap) { sums_cap = std::max((size_t)nb * C * 2, sums_hint); take(sums_cap, sizeof(double)); }
         return make(z->n);
     }
-    dyf::RT* linear(dyf::RT*, int rows, int, int O, const std::string&, int) { return make((size_t)rows * O); }
+    dyf::RT* linear(dyf::RT*, int rows, int, int O, const std::string&, int, bool = false) { return make((size_t)rows * O); }
+    dyf::RT* silu_shared(dyf::RT* x) { return x; }
     dyf::RT* learned_sinu(const float*, int half) { return make((size_t)nb * (2 * half + 1)); }
-    dyf::RT* dropout(dyf::RT* x, long long, float p) { return p > 0.0f ? make(x->n) : x; }
+    dyf::RT* dropout(dyf::RT* x, long long, float p, bool in_place = false, int = -1) { return p > 0.0f && !in_place ? make(x->n) : x; }
     dyf::RT* inputs(const Source*, int hw, int cin) { return make((size_t)nb * hw * cin); }
     const float* times(const float*, float) { take(nb); return nullptr; }
     dyf::RT* sinusoid(const float*, int dim) { return make((size_t)nb * dim); }
@@ -1137,6 +1263,13 @@ struct RCount {
     dyf::RT* add(dyf::RT* a, dyf::RT*) { return make(a->n); }
     dyf::RT* cat(dyf::RT*, int ca, dyf::RT*, int cb, long long pixels) { return make((size_t)pixels * (ca + cb)); }
     dyf::RT* up2_nearest(dyf::RT* x, int, int, int) { return make(x->n * 4); }
+    dyf::RT* up2_bilinear(dyf::RT* x, int ca, dyf::RT* x2, int cb, int h, int w, int oh, int ow) {
+        const int C = ca + (x2 ? cb : 0);
+        if (x2 && !(C % 4 == 0 && oh == 2 * h && ow == 2 * w && ca % 4 == 0 && cb % 4 == 0)) cat(x, ca, x2, cb, (long long)nb * h * w);
+        return make((size_t)nb * oh * ow * C);
+    }
+    dyf::RT* resize(dyf::RT* x, int h, int w, int C, int oh, int ow, int) { return h == oh && w == ow ? x : make((size_t)nb * oh * ow * C); }
+    dyf::RT* conv_transpose4s2(dyf::RT*, int h, int w, int, int C, const std::string&) { return make((size_t)nb * 4 * h * w * C); }
     dyf::RT* layernorm(dyf::RT* x, int hw, int, const std::string&, float) { take((size_t)nb * hw, sizeof(float2)); return make(x->n); }
     dyf::RT* linattn(dyf::RT*, int hw) {
         const size_t tot = (size_t)nb * hw * RHID;
@@ -1150,6 +1283,12 @@ struct RCount {
         return make((size_t)nb * N * RHID);
     }
 };
+
+// Pixels per workgroup of the norm sums of a RECORDED forward (norm_act's ppb_rec), one rule per backbone.  unet.Unet: about 2 048
+// workgroups per launch on its planes (16 pixels each left 14 400 workgroups of 60 x 60 x 64 rows with four fp64 atomics per thread: 104 us
+// per backward-sums launch, 10x its traffic time).  unet_simple: at most 256 workgroups per sample.
+inline int rn_norm_ppb(int hw, int nb) { return std::max(std::max(16, (hw + 255) / 256), (int)std::min<long long>(128, ((long long)hw * nb + 2047) / 2048)); }
+inline int us_norm_ppb(int hw) { return std::max(16, (hw + 255) / 256); }
 
 // The layer walk of unet.Unet.forward (unet.py:262-315), shared by the recorded forward, the sampling forward (both RCtx: they differ
 // in where RCtx::mem takes the tensors from) and the sizing of the sampling arena (RCount).  src: up to three NCHW sources in channel
@@ -1178,10 +1317,12 @@ RT* rn_walk(Ctx& X, const dyf_net_config& c, const RNames& R, int nb, int H, int
     }
     auto resblock = [&](const std::string& pre, RT* x, int cx, int cout, int hh, int ww) -> RT* {
         RT* ss = temb ? X.linear(temb, nb, tdim, 2 * cout, pre + ".mlp.1", 1) : nullptr;
-        RT* h1 = X.gn_act(X.conv(x, hh, ww, cx, cout, 3, 1, 1, pre + ".block1.proj", true, true), hh * ww, cout, pre + ".block1.norm", ss, c.block_dropout1);
+        const int ppb = rn_norm_ppb(hh * ww, nb);
+        RT* h1 = X.norm_act(X.conv(x, hh, ww, cx, cout, 3, 1, 1, pre + ".block1.proj", true, true), hh * ww, cout, pre + ".block1.norm", ss,
+                            c.block_dropout1, 2, c.groups, ACT_SILU, ppb);
         RT* h2 = c.single_conv_layer ? h1  // double_conv_layer=False: block2 = Identity
-                                     : X.gn_act(X.conv(h1, hh, ww, cout, cout, 3, 1, 1, pre + ".block2.proj", true, true), hh * ww, cout,
-                                                pre + ".block2.norm", nullptr, c.dropout);
+                                     : X.norm_act(X.conv(h1, hh, ww, cout, cout, 3, 1, 1, pre + ".block2.proj", true, true), hh * ww, cout,
+                                                  pre + ".block2.norm", nullptr, c.dropout, 2, c.groups, ACT_SILU, ppb);
         RT* res = cx != cout ? X.conv(x, hh, ww, cx, cout, 1, 1, 0, pre + ".residual_conv", true, false) : x;
         return X.add(h2, res);
     };
@@ -1229,6 +1370,66 @@ RT* rn_walk(Ctx& X, const dyf_net_config& c, const RNames& R, int nb, int H, int
     return y;
 }
 
+// The layer walk of unet_simple's UNet.forward (unet_simple.py:164-197), used as rn_walk is: cat -> outer resample -> 1x1 stem ->
+// dropout_input -> 6 encoder and 6 decoder UNetBlocks (conv -> norm -> FiLM -> activation -> dropout; a decoder block upsamples x2 first, and
+// the skip a decoder block's output is concatenated with is left to the next block's upsample) -> ConvTranspose2d readout -> outer resample.
+// src: the NCHW sources in channel order.  bn_batch: BatchNorm on batch statistics (module.train()).
+template <typename Ctx>
+RT* us_walk(Ctx& X, const Net& n, int nb, int H, int W, const Source* src, const float* time_dev_in, float time_value, bool bn_batch, RT** x_in) {
+    const dyf_net_config& c = n.cfg;
+    RT* film = nullptr;  // SiLU(time embedding), what every block's FiLM head starts from
+    if (c.with_time_emb) {
+        const float* time_dev = X.times(time_dev_in, time_value);
+        RT* e0 = X.sinusoid(time_dev, n.dim);
+        film = X.silu_shared(X.linear(X.gelu(X.linear(e0, nb, n.dim, n.tdim, "time_emb_mlp.1", 0)), nb, n.tdim, n.tdim, "time_emb_mlp.3", 0));
+    }
+    RT* xin = X.inputs(src, H * W, n.cin_total);
+    *x_in = xin;
+    RT* x = X.conv(X.resize(xin, H, W, n.cin_total, n.uh, n.uw, c.outer_nearest), n.uh, n.uw, n.cin_total, n.dim, 1, 1, 0, "init_conv", true, false);
+    x = X.dropout(x, (long long)n.uh * n.uw * n.dim, c.input_dropout, true, (int)DYF_INPUT_DROP_SITE);
+    RT *y[12], *skip = nullptr;
+    int lh = n.uh, lw = n.uw;
+    for (int i = 0; i < 12; ++i) X.sums_hint = std::max(X.sums_hint, (size_t)nb * 2 * n.blk[i].cout);
+    for (int i = 0; i < 12; ++i) {
+        const UBlock& b = n.blk[i];
+        const std::string pre = i < 6 ? "input_ops." + std::to_string(i) : "output_ops." + std::to_string(i - 6);
+        const std::string conv = pre + ".ops." + (b.transposed ? "1" : "0"), norm = pre + ".ops." + (b.transposed ? "2" : "1");
+        if (b.transposed) x = X.up2_bilinear(x, skip ? n.blk[i - 1].cout : b.cin, skip, skip ? n.blk[11 - i].cout : 0, lh, lw, b.in_h, b.in_w);
+        RT* z = X.conv(x, b.in_h, b.in_w, b.cin, b.cout, b.k, b.stride, b.pad, conv, true, false);
+        RT* ss = film ? X.linear(film, nb, n.tdim, 2 * b.cout, pre + ".time_mlp.1", 1, true) : nullptr;
+        const int ohw = b.out_h * b.out_w;
+        x = y[i] = X.norm_act(z, ohw, b.cout, norm, ss, c.dropout, b.gn ? 2 : bn_batch ? 0 : 1, 8, b.act, us_norm_ppb(ohw), i);
+        lh = b.out_h; lw = b.out_w;
+        skip = i >= 6 && i < 11 ? y[10 - i] : nullptr;  // torch.cat([x, skip]) (:176-177)
+    }
+    return X.resize(X.conv_transpose4s2(x, lh, lw, n.dim, c.out_channels, "readout.0"), 2 * lh, 2 * lw, c.out_channels, H, W, c.outer_nearest);
+}
+
+// ---- the one place that tells the two backbones apart: which walk, the order of its sources, what a recorded forward cannot serve
+// the training step's sources in the order the backbone concatenates them (unet.Unet: (condition, x), unet.py:269; unet_simple: (x,
+// condition)); returns the first channel of `inputs` inside the concatenation
+inline int net_sources(const Net& n, const float* inputs_dev, const float* cond_dev, Source src[3]) {
+    src[0] = {inputs_dev, n.cfg.in_channels};
+    src[1] = {cond_dev, cond_dev ? n.cfg.cond_channels : 0};
+    src[2] = {nullptr, 0};
+    if (n.rn) std::swap(src[0], src[1]);
+    return n.rn ? src[0].ch : 0;
+}
+// null, or why the net's forward cannot be recorded: unet.Unet's bottleneck Attention keeps its (tokens x tokens) probabilities for the backward
+inline const char* net_record_refusal(const dyf_engine* e, const Net& n) {
+    if (!n.rn) return nullptr;
+    const RNames R = rn_names(e, n.cfg);
+    return (long long)R.lev_h.back() * R.lev_w.back() <= AT_KEEP_P_MAX
+               ? nullptr
+               : "training step: the bottleneck Attention keeps its (tokens x tokens) probabilities -- at most 4096 tokens";
+}
+template <typename Ctx>
+RT* net_walk(Ctx& X, const dyf_engine* e, const Net& n, int nb, const Source* src, const float* time_dev, float time_value, bool bn_batch, RT** x_in) {
+    const int H = e->cfg.height, W = e->cfg.width;
+    if (n.rn) return rn_walk(X, n.cfg, rn_names(e, n.cfg), nb, H, W, n.cin_total, src, time_dev, time_value, x_in);
+    return us_walk(X, n, nb, H, W, src, time_dev, time_value, bn_batch, x_in);
+}
+
 }  // namespace
 
 namespace dyf {
@@ -1245,14 +1446,16 @@ static void rn_pack_conv(const float* host, int cout, int cin, int taps, std::ve
 }
 
 // every tensor of `sd` into `t` in its training layout, and one zeroed gradient arena behind them (the loader's and the op seam's)
-static dyf_status rn_fill_params(dyf_engine* e, RTNet& t, std::map<std::string, TensorView>& sd) {
+static dyf_status rn_fill_params(dyf_engine* e, TrainNet& t, std::map<std::string, TensorView>& sd) {
+    auto ends_with = [](const std::string& s, const char* tail) { const size_t k = strlen(tail); return s.size() > k && s.compare(s.size() - k, k, tail) == 0; };
     for (auto& kv : sd) {
         const TensorView& v = kv.second;
         RParam p;
         p.n = (size_t)v.numel();
+        p.stat = ends_with(kv.first, ".running_mean") || ends_with(kv.first, ".running_var");
         std::vector<float> host(v.data, v.data + v.numel());
-        const bool is_conv = v.shape.size() == 4 && !(kv.first.size() > 7 && kv.first.compare(kv.first.size() - 7, 7, ".norm.g") == 0);
-        if (is_conv) {  // (co, ci, kh, kw) -> [co][tap][ci]
+        const bool is_conv = v.shape.size() == 4 && !ends_with(kv.first, ".norm.g");
+        if (is_conv) {  // (co, ci, kh, kw) -> [co][tap][ci]; unet_simple's readout ConvTranspose2d (dim, C, 4, 4) -> [dim][tap][C] (RCtx::conv_transpose4s2)
             p.conv = 1; p.cout = (int)v.shape[0]; p.cin = (int)v.shape[1]; p.taps = (int)(v.shape[2] * v.shape[3]);
             std::vector<float> a(host.size()), at(host.size());
             rn_pack_conv(host.data(), p.cout, p.cin, p.taps, a, &at);
@@ -1266,24 +1469,25 @@ static dyf_status rn_fill_params(dyf_engine* e, RTNet& t, std::map<std::string, 
         t.P[kv.first] = p;
     }
     size_t total = 0;
-    for (auto& kv : t.P) total += (kv.second.n + 63) / 64 * 64;
+    for (auto& kv : t.P) total += kv.second.stat ? 0 : (kv.second.n + 63) / 64 * 64;
     t.g_arena = nullptr;
     t.g_arena_floats = total;
     dyf_status gs = talloc(e, t.owned, &t.g_arena, total, true);
     if (gs != DYF_OK) return gs;
     size_t off = 0;
     for (auto& kv : t.P) {
+        if (kv.second.stat) continue;
         kv.second.g = t.g_arena + off;
         off += (kv.second.n + 63) / 64 * 64;
     }
     return DYF_OK;
 }
 
-// fp32 training copy of a ResNet-UNet's parameters (called by dyf_load_weights / dyf_train_load_weights for arch unet.Unet)
-dyf_status rn_train_store_weights(dyf_engine* e, int which, std::map<std::string, TensorView>& sd) {
+// fp32 training copy of a network's parameters (called by dyf_load_weights for arch unet_simple and unet.Unet)
+dyf_status train_store_params(dyf_engine* e, int which, std::map<std::string, TensorView>& sd) {
     if (!e->train) e->train = new TrainState();
-    if (!e->train->rnet[which]) e->train->rnet[which] = new RTNet();
-    RTNet& t = *e->train->rnet[which];
+    if (!e->train->net[which]) e->train->net[which] = new TrainNet();
+    TrainNet& t = *e->train->net[which];
     TK(hipDeviceSynchronize());
     tfree(e, t.owned);
     t.P.clear();
@@ -1295,54 +1499,29 @@ dyf_status rn_train_store_weights(dyf_engine* e, int which, std::map<std::string
     return DYF_OK;
 }
 
-void rn_train_destroy(dyf_engine* e) {
-    if (!e->train) return;
-    for (int w = 0; w < 2; ++w)
-        if (e->train->rnet[w]) {
-            tfree(e, e->train->rnet[w]->owned);
-            delete e->train->rnet[w];
-            e->train->rnet[w] = nullptr;
-        }
-    for (int s = 0; s < 4; ++s)
-        if (e->train->rtape[s]) {
-            tfree(e, e->train->rtape[s]->owned);
-            delete e->train->rtape[s];
-            e->train->rtape[s] = nullptr;
-        }
-}
-
-dyf_status rn_train_zero_grads(dyf_engine* e, int which) {
-    RTNet* t = e->train ? e->train->rnet[which] : nullptr;
-    if (!t || !t->ready) return fail(e, DYF_ERR_STATE, "training needs loaded weights");
-    TK(hipMemsetAsync(t->g_arena, 0, t->g_arena_floats * sizeof(float), 0));
-    TK(hipDeviceSynchronize());
-    return DYF_OK;
-}
-
-dyf_status rn_train_forward(dyf_engine* e, int which, int slot, const float* inputs_dev, const float* time_dev, const float* cond_dev,
-                            float* out_dev, int nb, int flags, hipStream_t st) {
-    RTNet* wp = e->train ? e->train->rnet[which] : nullptr;
-    if (!wp || !wp->ready) return fail(e, DYF_ERR_STATE, "training needs loaded weights (dyf_load_weights)");
+// the recorded forward of either backbone into tape `slot` (dyf_train_forward)
+dyf_status train_forward(dyf_engine* e, int which, int slot, const float* inputs_dev, const float* time_dev, const float* cond_dev, float* out_dev,
+                         int nb, int flags, hipStream_t st) {
+    TrainNet* wp = e->train ? e->train->net[which] : nullptr;
+    if (!wp || !wp->ready) return fail(e, DYF_ERR_STATE, "training needs arch unet_simple / unet with loaded weights (dyf_load_weights)");
     Net& n = e->net[which];
     const dyf_net_config& c = n.cfg;
     if ((c.cond_channels > 0) != (cond_dev != nullptr)) return fail(e, DYF_ERR_INVALID_ARGUMENT, "condition must be given iff num_conditional_channels > 0");
     if (c.with_time_emb && !time_dev) return fail(e, DYF_ERR_INVALID_ARGUMENT, "time must be given when with_time_emb");
-    const RNames R = rn_names(e, c);
-    const int H = e->cfg.height, W = e->cfg.width, hw = H * W;
-    if ((long long)R.lev_h.back() * R.lev_w.back() > 4096)
-        return fail(e, DYF_ERR_UNSUPPORTED, "training step: the bottleneck Attention keeps its (tokens x tokens) probabilities -- at most 4096 tokens");
+    if (const char* why = net_record_refusal(e, n)) return fail(e, DYF_ERR_UNSUPPORTED, why);
+    const int hw = e->cfg.height * e->cfg.width;
     e->train->stream = st;
-    if (!e->train->rtape[slot]) e->train->rtape[slot] = new RTape();
-    RTape& T = *e->train->rtape[slot];
+    if (!e->train->tape[slot]) e->train->tape[slot] = new RTape();
+    RTape& T = *e->train->tape[slot];
     TK(hipStreamSynchronize(st));
     tfree(e, T.owned);
     T.back.clear();
     T.ctx.reset();
     T.ts.clear();
-    T.net = which; T.nb = nb; T.flags = flags; T.row_keys = nullptr;
+    T.net = which; T.nb = nb; T.flags = flags; T.row_keys = nullptr; T.out = nullptr;
     const bool any_p = c.dropout > 0.0f || c.block_dropout1 > 0.0f || c.attn_dropout > 0.0f || c.input_dropout > 0.0f;
     const bool drop_on = (flags & DYF_TRAIN_DROPOUT) && any_p;
-    if (drop_on) {
+    if (drop_on) {  // this forward's dropout streams (engine generator, keyed per global row); a copy of the keys stays for the backward
         if (nb > 2 * e->cfg.max_batch) return fail(e, DYF_ERR_INVALID_ARGUMENT, "batch larger than the engine's row-key table");
         TK(launch_rng_begin_forward(e->rng_state, e->row_keys, nb, nb, st));
         dyf_status s = talloc(e, T.owned, &T.row_keys, (size_t)2 * nb, false);
@@ -1352,9 +1531,10 @@ dyf_status rn_train_forward(dyf_engine* e, int which, int slot, const float* inp
     RCtx* Xp = new RCtx{e, *wp, T, c, st, nb, drop_on};
     T.ctx = std::shared_ptr<void>(Xp, [](void* p) { delete (RCtx*)p; });
     RCtx& X = *Xp;
-    Source src[3] = {{cond_dev, cond_dev ? c.cond_channels : 0}, {inputs_dev, c.in_channels}, {nullptr, 0}};
+    Source src[3];
+    T.in_lo = net_sources(n, inputs_dev, cond_dev, src);
     X.mem = FwdMem{e, &T.owned, st};
-    RT* y = rn_walk(X, c, R, nb, H, W, n.cin_total, src, time_dev, 0.0f, &T.x_in);
+    RT* y = net_walk(X, e, n, nb, src, time_dev, 0.0f, (flags & DYF_TRAIN_BATCH_STATS) != 0, &T.x_in);
     T.out = y;
     if (X.err != DYF_OK) return fail(e, X.err, "training forward: allocation / launch failed");
     hipLaunchKernelGGL(t_nhwc_to_nchw, dim3(nblk((long long)nb * hw * c.out_channels)), dim3(256), 0, st, y->p, nb, hw, c.out_channels, 0, c.out_channels, out_dev);
@@ -1363,14 +1543,12 @@ dyf_status rn_train_forward(dyf_engine* e, int which, int slot, const float* inp
 }
 
 // ---- fp32 sampling (dyf_set_sample_precision(32)): the same walk on the engine's bump arena, nothing recorded
-// bytes one forward of `nb` rows takes from the arena
-size_t rn_arena_bytes(const dyf_engine* e, const Net& n, int nb) {
-    const RNames R = rn_names(e, n.cfg);
+// bytes one forward of `nb` rows takes from the arena: the walk itself, counting
+size_t f32_walk_bytes(const dyf_engine* e, const Net& n, int nb) {
     RCount K{n.cfg, nb};
     Source none[3] = {{nullptr, 0}, {nullptr, 0}, {nullptr, 0}};
     RT* xi = nullptr;
-    RT* y = rn_walk(K, n.cfg, R, nb, e->cfg.height, e->cfg.width, n.cin_total, none, nullptr, 0.0f, &xi);
-    (void)y;
+    (void)net_walk(K, e, n, nb, none, nullptr, 0.0f, false, &xi);
     return K.bytes;
 }
 
@@ -1419,39 +1597,6 @@ dyf_status f32_op_attention(dyf_engine* e, const float* qkv, int nb, int N, floa
     return DYF_OK;
 }
 
-dyf_status rn_f32_forward(dyf_engine* e, int which, const Source* srcs, int nsrc, int nb, const FwdOpts& o, float* out_dev, hipStream_t st) {
-    RTNet* wp = e->train ? e->train->rnet[which] : nullptr;
-    if (!wp || !wp->ready) return fail(e, DYF_ERR_STATE, "fp32 sampling needs loaded weights (dyf_load_weights)");
-    Net& n = e->net[which];
-    const dyf_net_config& c = n.cfg;
-    const RNames R = rn_names(e, c);
-    const int H = e->cfg.height, W = e->cfg.width, hw = H * W;
-    Source src[3] = {{nullptr, 0}, {nullptr, 0}, {nullptr, 0}};
-    int ctot = 0;
-    for (int i = 0; i < nsrc && i < 3; ++i) {
-        src[i] = srcs[i];
-        if (!src[i].p) src[i].ch = 0;
-        ctot += src[i].ch;
-    }
-    if (ctot != n.cin_total) return fail(e, DYF_ERR_INVALID_ARGUMENT, "channel count of the network inputs does not match its configuration");
-    const bool any_p = c.dropout > 0.0f || c.block_dropout1 > 0.0f || c.attn_dropout > 0.0f || c.input_dropout > 0.0f;
-    const bool drop_on = o.dropout_mode == 1 && any_p;
-    RTape T;  // scratch: a sampling forward leaves nothing behind
-    if (drop_on) {  // begin the forward in the generator exactly as the 16-bit path does; the keys are read from the engine's table
-        TK(launch_rng_begin_forward(e->rng_state, e->row_keys, nb, nb, st));
-        T.row_keys = e->row_keys;
-    }
-    RCtx X{e, *wp, T, c, st, nb, drop_on};
-    X.mem = FwdMem{e, nullptr, st};
-    X.masks = (o.dropout_mode == 2 && o.masks && any_p) ? o.masks : nullptr;
-    RT* xi = nullptr;
-    RT* y = rn_walk(X, c, R, nb, H, W, n.cin_total, src, o.time_dev, o.time_value, &xi);
-    if (X.err != DYF_OK) return fail(e, X.err, e->err.empty() ? "fp32 forward: allocation / launch failed" : e->err);
-    hipLaunchKernelGGL(t_nhwc_to_nchw, dim3(nblk((long long)nb * hw * c.out_channels)), dim3(256), 0, st, y->p, nb, hw, c.out_channels, 0, c.out_channels, out_dev);
-    TK(hipGetLastError());
-    return DYF_OK;
-}
-
 // the backward of a recorded forward: its closures in reverse (the training step's and the op seam's)
 static dyf_status rn_run_adjoints(RTape& T, RCtx& X) {
     dyf_status r = DYF_OK;
@@ -1460,8 +1605,8 @@ static dyf_status rn_run_adjoints(RTape& T, RCtx& X) {
     return r;
 }
 
-dyf_status rn_train_backward(dyf_engine* e, int slot, const float* dout_dev, float* dinputs_dev, int param_grads, hipStream_t st) {
-    RTape* tp = e->train ? e->train->rtape[slot] : nullptr;
+dyf_status train_backward(dyf_engine* e, int slot, const float* dout_dev, float* dinputs_dev, int param_grads, hipStream_t st) {
+    RTape* tp = e->train ? e->train->tape[slot] : nullptr;
     if (!tp || tp->net < 0 || !tp->out) return fail(e, DYF_ERR_STATE, "no forward recorded in this tape slot");
     RTape& T = *tp;
     Net& n = e->net[T.net];
@@ -1472,14 +1617,18 @@ dyf_status rn_train_backward(dyf_engine* e, int slot, const float* dout_dev, flo
     X.st = st;
     X.tmp = &tmp;
     X.param_grads = param_grads != 0;
+    X.want_dinputs = dinputs_dev != nullptr;
+    X.norm_bwd = nullptr;
     X.err = DYF_OK;
     const int hw = e->cfg.height * e->cfg.width;
     for (auto& t : T.ts) t.g = nullptr;
-    hipLaunchKernelGGL(t_nchw_to_nhwc, dim3(nblk((long long)T.nb * hw * c.out_channels)), dim3(256), 0, st, dout_dev, T.nb, hw, c.out_channels, X.grad(T.out));
-    if (dinputs_dev) (void)X.grad(T.x_in);  // request the gradient of the network input
+    T.out->g = X.tbuf(T.out->n);
+    if (X.err != DYF_OK) { tfree(e, tmp); return fail(e, X.err, "training backward: allocation failed"); }
+    hipLaunchKernelGGL(t_nchw_to_nhwc, dim3(nblk((long long)T.nb * hw * c.out_channels)), dim3(256), 0, st, dout_dev, T.nb, hw, c.out_channels, T.out->g);
     dyf_status r = rn_run_adjoints(T, X);
+    if (r == DYF_OK && dinputs_dev && !T.x_in->g) r = DYF_ERR_STATE;  // every walk's first conv reaches the network input
     if (r == DYF_OK && dinputs_dev)
-        hipLaunchKernelGGL(t_nhwc_to_nchw, dim3(nblk((long long)T.nb * hw * c.in_channels)), dim3(256), 0, st, T.x_in->g, T.nb, hw, n.cin_total, c.cond_channels,
+        hipLaunchKernelGGL(t_nhwc_to_nchw, dim3(nblk((long long)T.nb * hw * c.in_channels)), dim3(256), 0, st, T.x_in->g, T.nb, hw, n.cin_total, T.in_lo,
                            c.in_channels, dinputs_dev);
     hipError_t se = hipStreamSynchronize(st);
     for (auto& t : T.ts) t.g = nullptr;
@@ -1489,15 +1638,15 @@ dyf_status rn_train_backward(dyf_engine* e, int slot, const float* dout_dev, flo
     return DYF_OK;
 }
 
-// one parameter's gradient in its PyTorch layout (conv: (co, ci, kh, kw)) to `out`, on the device or the host
-static dyf_status rn_export_param(dyf_engine* e, std::vector<void*>& tmp, const RParam& p, float* out, bool dev) {
-    const float* src = p.g;
+// what leaves by one parameter's name, in its PyTorch layout (conv: (co, ci, kh, kw)), to `out` on the device or the host: its gradient, or
+// -- a BatchNorm running statistic -- the statistic as the recorded forwards updated it
+// (stage: p.n floats of device scratch for the unpacked copy of a conv weight on its way to the host; the copy below is synchronous, so one
+// block serves a whole export)
+static dyf_status rn_export_param(dyf_engine* e, float* stage, const RParam& p, float* out, bool dev) {
+    const float* src = p.stat ? p.w : p.g;
     if (p.conv) {
-        float* un = nullptr;
-        dyf_status s = talloc(e, tmp, &un, p.n, false);
-        if (s != DYF_OK) return s;
-        hipLaunchKernelGGL(t_unpack_conv_r, dim3(nblk((long long)p.n)), dim3(256), 0, 0, p.g, p.cout, p.cin, p.taps, dev ? out : un);
-        src = un;
+        hipLaunchKernelGGL(t_unpack_conv, dim3(nblk((long long)p.n)), dim3(256), 0, 0, p.g, p.cout, p.cin, p.taps, dev ? out : stage);
+        src = stage;
         if (dev) return DYF_OK;
     }
     if (dev) TK(hipMemcpy(out, src, p.n * sizeof(float), hipMemcpyDeviceToDevice));
@@ -1505,16 +1654,25 @@ static dyf_status rn_export_param(dyf_engine* e, std::vector<void*>& tmp, const 
     return DYF_OK;
 }
 
-// gradients by state_dict name in PyTorch layouts (conv: (co, ci, kh, kw))
-dyf_status rn_train_export(dyf_engine* e, int which, int n_tensors, const char* const* names, float* const* out, bool dev) {
-    RTNet* t = e->train ? e->train->rnet[which] : nullptr;
-    if (!t || !t->ready) return fail(e, DYF_ERR_STATE, "training needs loaded weights");
+// gradients (and running statistics) by state_dict name in PyTorch layouts (dyf_train_export, dyf_train_export_dev)
+dyf_status train_export(dyf_engine* e, int which, int n_tensors, const char* const* names, float* const* out, bool dev) {
+    TrainNet* t = e->train ? e->train->net[which] : nullptr;
+    if (!t || !t->ready) return fail(e, DYF_ERR_STATE, "training needs arch unet_simple / unet with loaded weights");
     TK(hipDeviceSynchronize());
     std::vector<void*> tmp;
+    size_t stage_n = 0;
     for (int i = 0; i < n_tensors; ++i) {
         auto it = t->P.find(names[i]);
-        if (it == t->P.end()) { tfree(e, tmp); return fail(e, DYF_ERR_INVALID_ARGUMENT, std::string("no gradient for '") + names[i] + "'"); }
-        dyf_status s = rn_export_param(e, tmp, it->second, out[i], dev);
+        if (it == t->P.end()) return fail(e, DYF_ERR_INVALID_ARGUMENT, std::string("dyf_train_export: unknown tensor '") + names[i] + "'");
+        if (it->second.conv && !dev) stage_n = std::max(stage_n, it->second.n);
+    }
+    float* stage = nullptr;
+    if (stage_n) {  // (after a backward the pool holds that backward's temporaries: one of them serves, no block is added)
+        dyf_status s = talloc(e, tmp, &stage, stage_n, false, true);
+        if (s != DYF_OK) return s;
+    }
+    for (int i = 0; i < n_tensors; ++i) {
+        dyf_status s = rn_export_param(e, stage, t->P.at(names[i]), out[i], dev);
         if (s != DYF_OK) { tfree(e, tmp); return s; }
     }
     TK(hipDeviceSynchronize());
@@ -1523,7 +1681,7 @@ dyf_status rn_train_export(dyf_engine* e, int which, int n_tensors, const char* 
 }
 
 // test seam (dyf_op_train_f32): ONE op of the recorded forward and its adjoint.  The op is the RCtx member function itself, recording on
-// a scratch tape over a scratch parameter set; the backward is rn_run_adjoints, the loop rn_train_backward runs -- no launch is restated
+// a scratch tape over a scratch parameter set; the backward is rn_run_adjoints, the loop train_backward runs -- no launch is restated
 // here.  Parameters arrive in PyTorch layouts on the host and go through rn_fill_params; the gradient buffers start from the caller's
 // contents (conv weights packed as the weights are) and leave through rn_export_param.
 dyf_status f32_op_train(dyf_engine* e, const dyf_train_op* dp, const float* const* inputs, const float* const* params, const float* dout,
@@ -1532,22 +1690,30 @@ dyf_status f32_op_train(dyf_engine* e, const dyf_train_op* dp, const float* cons
     auto refuse = [&](dyf_status s, const char* what) { return fail(e, s, std::string("dyf_op_train_f32: ") + what); };
     if (d.nb < 1 || d.h < 1 || d.w < 1 || d.c < 1) return refuse(DYF_ERR_INVALID_ARGUMENT, "nb, h, w and c must be positive");
     if (!(d.p >= 0.0f && d.p < 1.0f)) return refuse(DYF_ERR_INVALID_ARGUMENT, "p must be in [0, 1)");
-    const bool has_p = d.op == DYF_TOP_GN_ACT || d.op == DYF_TOP_LAYERNORM || d.op == DYF_TOP_ATTENTION || d.op == DYF_TOP_DROPOUT;
-    const bool has_c2 = d.op == DYF_TOP_CONV || d.op == DYF_TOP_LINEAR || d.op == DYF_TOP_CAT;
+    const bool has_p = d.op == DYF_TOP_GN_ACT || d.op == DYF_TOP_NORM_ACT || d.op == DYF_TOP_LAYERNORM || d.op == DYF_TOP_ATTENTION || d.op == DYF_TOP_DROPOUT;
+    const bool has_c2 = d.op == DYF_TOP_CONV || d.op == DYF_TOP_LINEAR || d.op == DYF_TOP_CAT || d.op == DYF_TOP_CONVT;
     const int flags_ok = d.op == DYF_TOP_CONV ? (DYF_TOP_WS | DYF_TOP_BIAS) : d.op == DYF_TOP_GN_ACT ? DYF_TOP_FILM : d.op == DYF_TOP_LINEAR ? DYF_TOP_PRE
-                         : d.op == DYF_TOP_ADD ? DYF_TOP_SAME : 0;
-    if (d.op < DYF_TOP_CONV || d.op > DYF_TOP_UP2_NEAREST) return refuse(DYF_ERR_INVALID_ARGUMENT, "unknown op");
+                         : d.op == DYF_TOP_ADD ? DYF_TOP_SAME
+                         : d.op == DYF_TOP_NORM_ACT ? (DYF_TOP_FILM | DYF_TOP_RUNNING | DYF_TOP_MASK | DYF_TOP_LEAKY | DYF_TOP_RELU)
+                         : d.op == DYF_TOP_UP2_BILINEAR ? DYF_TOP_GRAD_IN : d.op == DYF_TOP_RESIZE ? DYF_TOP_NEAREST : 0;
+    if (d.op < DYF_TOP_CONV || d.op > DYF_TOP_CONVT) return refuse(DYF_ERR_INVALID_ARGUMENT, "unknown op");
     if (d.flags & ~flags_ok) return refuse(DYF_ERR_INVALID_ARGUMENT, "a flag this op does not take");
     if (d.p > 0.0f && !has_p) return refuse(DYF_ERR_INVALID_ARGUMENT, "this op has no dropout");
-    if (has_c2 ? d.c2 < 1 : d.c2 != 0) return refuse(DYF_ERR_INVALID_ARGUMENT, "c2 must be positive for conv / linear / cat and 0 otherwise");
-    if (d.op == DYF_TOP_CONV ? (d.k < 1 || d.stride < 1 || d.pad < 0 || d.h + 2 * d.pad < d.k || d.w + 2 * d.pad < d.k) : (d.k != 0 || d.stride != 0 || d.pad != 0))
-        return refuse(DYF_ERR_INVALID_ARGUMENT, "k / stride / pad: a conv geometry with at least one output pixel, 0 for every other op");
-    if (d.op == DYF_TOP_GN_ACT ? (d.groups < 1 || d.c % d.groups != 0) : d.groups != 0)
-        return refuse(DYF_ERR_INVALID_ARGUMENT, "groups must divide c for gn_act and be 0 otherwise");
+    if (d.op == DYF_TOP_UP2_BILINEAR ? d.c2 < 0 : has_c2 ? d.c2 < 1 : d.c2 != 0)
+        return refuse(DYF_ERR_INVALID_ARGUMENT, "c2 must be positive for conv / linear / cat / convt, 0 or the second source's channels for up2_bilinear, 0 otherwise");
+    if (d.op == DYF_TOP_CONV ? (d.k < 1 || d.stride < 1 || d.pad < 0 || d.h + 2 * d.pad < d.k || d.w + 2 * d.pad < d.k)
+        : d.op == DYF_TOP_RESIZE ? (d.k < 1 || d.stride < 1 || d.pad != 0) : (d.k != 0 || d.stride != 0 || d.pad != 0))
+        return refuse(DYF_ERR_INVALID_ARGUMENT, "k / stride / pad: a conv geometry with at least one output pixel, the output size of a resize, 0 for every other op");
+    if (d.op == DYF_TOP_GN_ACT ? (d.groups < 1 || d.c % d.groups != 0) : d.op == DYF_TOP_NORM_ACT ? (d.groups < 0 || (d.groups > 0 && d.c % d.groups != 0)) : d.groups != 0)
+        return refuse(DYF_ERR_INVALID_ARGUMENT, "groups must divide c for gn_act / norm_act (norm_act: 0 = BatchNorm) and be 0 otherwise");
+    if (d.op == DYF_TOP_NORM_ACT && (((d.flags & DYF_TOP_RUNNING) && d.groups > 0) || ((d.flags & DYF_TOP_LEAKY) && (d.flags & DYF_TOP_RELU)) || ((d.flags & DYF_TOP_MASK) && !(d.p > 0.0f))))
+        return refuse(DYF_ERR_INVALID_ARGUMENT, "norm_act: running statistics are BatchNorm's, one activation, a mask needs p > 0");
+    if ((d.flags & DYF_TOP_GRAD_IN) && (d.c2 < 1 || !dinputs || !dinputs[1])) return refuse(DYF_ERR_INVALID_ARGUMENT, "up2_bilinear: a gradient to start from needs the second source and its gradient buffer");
     if ((d.op == DYF_TOP_LINEAR || d.op == DYF_TOP_LEARNED_SINU) && (d.h != 1 || d.w != 1)) return refuse(DYF_ERR_INVALID_ARGUMENT, "linear / learned_sinu take rows: h = w = 1");
     const long long hw = (long long)d.h * d.w, px = hw * d.nb;
-    const long long cmax = std::max<long long>(std::max(d.c, d.c2), (d.op == DYF_TOP_LINATTN || d.op == DYF_TOP_ATTENTION) ? 3 * RHID : 0);
-    if (hw * cmax * 4 >= (1ll << 32) || px * cmax * 4 >= (1ll << 31)) return refuse(DYF_ERR_UNSUPPORTED, "tensor too large for the op seam (2^31 elements)");
+    const long long cmax = std::max<long long>(d.c + d.c2, (d.op == DYF_TOP_LINATTN || d.op == DYF_TOP_ATTENTION) ? 3 * RHID : 0);
+    const long long ohw = d.op == DYF_TOP_RESIZE ? (long long)d.k * d.stride : hw;  // the larger plane of the op (x2 upsamples: the 4 below)
+    if (std::max(hw, ohw) * cmax * 4 >= (1ll << 32) || std::max(hw, ohw) * d.nb * cmax * 4 >= (1ll << 31)) return refuse(DYF_ERR_UNSUPPORTED, "tensor too large for the op seam (2^31 elements)");
     if ((d.op == DYF_TOP_LINATTN || d.op == DYF_TOP_ATTENTION) && d.c != 3 * RHID) return refuse(DYF_ERR_INVALID_ARGUMENT, "the attention cores take qkv of 384 channels");
     if (d.op == DYF_TOP_ATTENTION && hw > AT_KEEP_P_MAX) return refuse(DYF_ERR_UNSUPPORTED, "the Attention core keeps its (tokens x tokens) probabilities -- at most 4096 tokens");
     if (d.p > 0.0f && d.nb > 2 * e->cfg.max_batch) return refuse(DYF_ERR_INVALID_ARGUMENT, "more rows than the engine's row-key table (2 max_batch)");
@@ -1573,10 +1739,21 @@ dyf_status f32_op_train(dyf_engine* e, const dyf_train_op* dp, const float* cons
     case DYF_TOP_LEARNED_SINU: in_n = {(size_t)d.nb}; ps = {{"time_emb_mlp.0.weights", {d.c}}}; break;
     case DYF_TOP_ADD: in_n = {xn}; if (!(d.flags & DYF_TOP_SAME)) in_n.push_back(xn); break;
     case DYF_TOP_CAT: in_n = {xn, (size_t)px * d.c2}; break;
+    case DYF_TOP_NORM_ACT:
+        in_n = {xn};
+        if (d.flags & DYF_TOP_FILM) in_n.push_back((size_t)d.nb * 2 * d.c);
+        ps = {{"op.weight", {d.c}}, {"op.bias", {d.c}}};
+        if (d.groups == 0) { ps.push_back({"op.running_mean", {d.c}}); ps.push_back({"op.running_var", {d.c}}); }
+        break;
+    case DYF_TOP_UP2_BILINEAR: in_n = {xn}; if (d.c2) in_n.push_back((size_t)px * d.c2); break;
+    case DYF_TOP_CONVT: in_n = {xn}; ps = {{"op.weight", {d.c, d.c2, 4, 4}}, {"op.bias", {d.c2}}}; break;
     default: in_n = {xn}; break;
     }
     for (size_t i = 0; i < in_n.size(); ++i)
         if (!inputs[i]) return refuse(DYF_ERR_INVALID_ARGUMENT, "an input pointer is null");
+    // norm_act with DYF_TOP_MASK: the caller's keep mask follows the inputs; the forward alone runs (the adjoints draw from the generator)
+    const uint8_t* mask = (d.flags & DYF_TOP_MASK) ? (const uint8_t*)inputs[in_n.size()] : nullptr;
+    if ((d.flags & DYF_TOP_MASK) && !mask) return refuse(DYF_ERR_INVALID_ARGUMENT, "the mask pointer is null");
     for (size_t i = 0; i < ps.size(); ++i)
         if (!params || !dparams || !params[i] || !dparams[i]) return refuse(DYF_ERR_INVALID_ARGUMENT, "a parameter or parameter-gradient pointer is null");
 
@@ -1585,7 +1762,7 @@ dyf_status f32_op_train(dyf_engine* e, const dyf_train_op* dp, const float* cons
     const TrainPrecisionScope precision(e->train_precision);
     dyf_net_config c = e->net[0].cfg;
     c.groups = d.groups;
-    RTNet W;
+    TrainNet W;
     RTape T;
     std::vector<void*> tmp;
     auto done = [&](dyf_status s) {  // everything back to the engine's pool, whatever happened
@@ -1607,6 +1784,7 @@ dyf_status f32_op_train(dyf_engine* e, const dyf_train_op* dp, const float* cons
         std::vector<std::vector<float>> g0(ps.size());  // the caller's gradient contents, in the gradient buffers' layout
         for (size_t i = 0; i < ps.size(); ++i) {
             const RParam& p = W.P.at(ps[i].name);
+            if (p.stat) continue;  // no gradient: the updated statistic leaves in its place
             g0[i].assign(dparams[i], dparams[i] + p.n);
             if (p.conv) {
                 std::vector<float> a(p.n);
@@ -1618,7 +1796,7 @@ dyf_status f32_op_train(dyf_engine* e, const dyf_train_op* dp, const float* cons
         OPK(hipStreamSynchronize(st));
     }
     bool drop_on = false;
-    if (d.p > 0.0f) {  // a new forward of the generator, site 0 (as f32_op_attention)
+    if (d.p > 0.0f && !mask) {  // a new forward of the generator, site 0 (as f32_op_attention)
         OPK(launch_rng_begin_forward(e->rng_state, e->row_keys, d.nb, d.nb, st));
         T.row_keys = e->row_keys;
         drop_on = true;
@@ -1626,6 +1804,7 @@ dyf_status f32_op_train(dyf_engine* e, const dyf_train_op* dp, const float* cons
     RCtx X{e, W, T, c, st, d.nb, drop_on};
     X.mem = FwdMem{e, &T.owned, st};
     X.tmp = &tmp;
+    X.masks = mask ? &mask : nullptr;
     RT* in[2] = {nullptr, nullptr};
     if (d.op != DYF_TOP_LEARNED_SINU)
         for (size_t i = 0; i < in_n.size(); ++i) {
@@ -1636,7 +1815,14 @@ dyf_status f32_op_train(dyf_engine* e, const dyf_train_op* dp, const float* cons
     RT* y = nullptr;
     switch (d.op) {
     case DYF_TOP_CONV: y = X.conv(in[0], d.h, d.w, d.c, d.c2, d.k, d.stride, d.pad, "op", (d.flags & DYF_TOP_BIAS) != 0, (d.flags & DYF_TOP_WS) != 0); break;
-    case DYF_TOP_GN_ACT: y = X.gn_act(in[0], (int)hw, d.c, "op", in[1], d.p); break;
+    case DYF_TOP_GN_ACT: y = X.norm_act(in[0], (int)hw, d.c, "op", in[1], d.p, 2, d.groups, ACT_SILU, rn_norm_ppb((int)hw, d.nb)); break;
+    case DYF_TOP_NORM_ACT:
+        y = X.norm_act(in[0], (int)hw, d.c, "op", in[1], d.p, d.groups > 0 ? 2 : (d.flags & DYF_TOP_RUNNING) ? 1 : 0, d.groups,
+                       (d.flags & DYF_TOP_LEAKY) ? ACT_LEAKY : (d.flags & DYF_TOP_RELU) ? ACT_RELU : ACT_SILU, us_norm_ppb((int)hw));
+        break;
+    case DYF_TOP_UP2_BILINEAR: y = X.up2_bilinear(in[0], d.c, in[1], d.c2, d.h, d.w, 2 * d.h, 2 * d.w); break;
+    case DYF_TOP_RESIZE: y = X.resize(in[0], d.h, d.w, d.c, d.k, d.stride, (d.flags & DYF_TOP_NEAREST) ? 1 : 0); break;
+    case DYF_TOP_CONVT: y = X.conv_transpose4s2(in[0], d.h, d.w, d.c, d.c2, "op"); break;
     case DYF_TOP_LAYERNORM: y = X.layernorm(in[0], (int)hw, d.c, "op.norm.g", d.p); break;
     case DYF_TOP_LINATTN: y = X.linattn(in[0], (int)hw); break;
     case DYF_TOP_ATTENTION: y = X.attention(in[0], (int)hw, d.p); break;
@@ -1651,22 +1837,33 @@ dyf_status f32_op_train(dyf_engine* e, const dyf_train_op* dp, const float* cons
     if (X.err != DYF_OK || !y) return done(refuse(X.err != DYF_OK ? X.err : DYF_ERR_HIP, "forward: allocation / launch failed"));
     OPK(hipGetLastError());
     OPK(hipMemcpyAsync(y_out, y->p, y->n * sizeof(float), hipMemcpyDeviceToDevice, st));
-    // the backward, as rn_train_backward starts it: the output's gradient, then the closures in reverse
+    // the backward, as train_backward starts it: the output's gradient, then the closures in reverse
     for (auto& t : T.ts) t.g = nullptr;
-    float* gy = X.grad(y);
-    if (X.err != DYF_OK) return done(refuse(X.err, "allocation failed"));
-    OPK(hipMemcpyAsync(gy, dout, y->n * sizeof(float), hipMemcpyDeviceToDevice, st));
-    dyf_status r = rn_run_adjoints(T, X);
-    if (r != DYF_OK) return done(refuse(r, "backward failed"));
-    OPK(hipGetLastError());
-    for (size_t i = 0; i < in_n.size() && dinputs; ++i) {
+    if (y == in[0]) {  // a resize to the same size is the identity: so is its adjoint
+        X.grad(y);
+        OPK(hipMemcpyAsync(y->g, dout, y->n * sizeof(float), hipMemcpyDeviceToDevice, st));
+    } else if (!mask) {
+        float* gy = X.grad(y);
+        if (d.flags & DYF_TOP_GRAD_IN) {  // the second source's gradient starts from the caller's
+            float* g1 = X.grad(in[1]);
+            if (X.err == DYF_OK) OPK(hipMemcpyAsync(g1, dinputs[1], in_n[1] * sizeof(float), hipMemcpyDeviceToDevice, st));
+        }
+        if (X.err != DYF_OK) return done(refuse(X.err, "allocation failed"));
+        OPK(hipMemcpyAsync(gy, dout, y->n * sizeof(float), hipMemcpyDeviceToDevice, st));
+        dyf_status r = rn_run_adjoints(T, X);
+        if (r != DYF_OK) return done(refuse(r, "backward failed"));
+        OPK(hipGetLastError());
+    }
+    for (size_t i = 0; i < in_n.size() && dinputs && !mask; ++i) {
         if (!dinputs[i] || !in[i]) continue;
         if (in[i]->g) OPK(hipMemcpyAsync(dinputs[i], in[i]->g, in_n[i] * sizeof(float), hipMemcpyDeviceToDevice, st));
         else OPK(hipMemsetAsync(dinputs[i], 0, in_n[i] * sizeof(float), st));
     }
     OPK(hipStreamSynchronize(st));
+    float* stage = X.tbuf(ps.empty() ? 1 : W.P.at(ps[0].name).n);  // (a conv weight is its op's first parameter)
+    if (X.err != DYF_OK) return done(refuse(X.err, "allocation failed"));
     for (size_t i = 0; i < ps.size(); ++i) {
-        dyf_status s = rn_export_param(e, tmp, W.P.at(ps[i].name), dparams[i], false);
+        dyf_status s = rn_export_param(e, stage, W.P.at(ps[i].name), dparams[i], false);
         if (s != DYF_OK) return done(s);
     }
 #undef OPK

@@ -696,14 +696,21 @@ class HipEngine:
         return y
 
     def op_train(self, op: str, inputs, params=(), dout: Optional[torch.Tensor] = None, grads_in=None, *, k: int = 0, stride: int = 0,
-                 pad: int = 0, groups: int = 0, p: float = 0.0, ws: bool = False, pre: bool = False) -> Dict[str, object]:
-        """Test seam (dyf_op_train_f32): ONE recorded op of the ResNet-UNet training step and its adjoint, through the training step's
-        own launch code.  `inputs`: fp32 tensors on the device, activations NHWC (nb, h, w, c) -- rows (nb, c) for "linear", times (nb,)
+                 pad: int = 0, groups: int = 0, p: float = 0.0, ws: bool = False, pre: bool = False, act: str = "silu", running: bool = False,
+                 mask: Optional[torch.Tensor] = None, size=None, nearest: bool = False, skip_grad: Optional[torch.Tensor] = None) -> Dict[str, object]:
+        """Test seam (dyf_op_train_f32): ONE recorded op of the training step (either backbone) and its adjoint, through the training
+        step's own launch code.  `inputs`: fp32 tensors on the device, activations NHWC (nb, h, w, c) -- rows (nb, c) for "linear", times (nb,)
         for "learned_sinu"; "add" with one input is add(a, a).  `params`: fp32 tensors in PyTorch layouts, in the header's order (conv:
         weight (c2, c, k, k) [, bias]; gn_act: weight, bias -- a second input is the FiLM (nb, 2c); layernorm: g; linear: weight (c2, c),
         bias; learned_sinu: weights).  `dout`: gradient of the output (its shape).  `grads_in`: what the parameter-gradient buffers hold
         before the op runs (default zeros): the kernels accumulate.  Returns {"y", "dinputs": [...], "dparams": [...]} (dparams on the
-        CPU).  p > 0 draws from the engine's generator: a new forward, site 0, rows row offset .. + nb - 1."""
+        CPU).  p > 0 draws from the engine's generator: a new forward, site 0, rows row offset .. + nb - 1.
+        unet_simple's ops: "norm_act" (gn_act's inputs; params weight, bias and -- groups = 0, BatchNorm2d -- running_mean, running_var, whose
+        "dparams" entries return the UPDATED statistics; `running`: normalise by them; `act` "silu" | "leaky" | "relu"; `mask`: a uint8 keep
+        mask (nb, h, w, c) instead of the generator -- forward only, "dinputs" is None), "up2_bilinear" (one source, or two standing for
+        their concatenation; `skip_grad`: the gradient the second source already has), "resize" (`size` = (oh, ow), which travels in the
+        descriptor's k and stride fields; `nearest`), "convt"
+        (ConvTranspose2d(c, c2, 4, 2, 1): weight (c, c2, 4, 4), bias)."""
         ins = [_f32c(t, "input") for t in inputs]
         x = ins[0]
         nb = x.shape[0]
@@ -742,18 +749,35 @@ class HipEngine:
             out_shape = (nb, 2 * h, 2 * w, c)
         elif op in ("layernorm", "dropout", "gelu"):
             out_shape = tuple(x.shape)
+        elif op == "norm_act":
+            flags = ((L.TOP_FILM if len(ins) > 1 else 0) | (L.TOP_RUNNING if running else 0) | (L.TOP_MASK if mask is not None else 0)
+                     | {"silu": 0, "leaky": L.TOP_LEAKY, "relu": L.TOP_RELU}[act])
+            out_shape = tuple(x.shape)
+        elif op == "up2_bilinear":
+            c2 = ins[1].shape[3] if len(ins) > 1 else 0
+            flags = L.TOP_GRAD_IN if skip_grad is not None else 0
+            out_shape = (nb, 2 * h, 2 * w, c + c2)
+        elif op == "resize":
+            k, stride = int(size[0]), int(size[1])  # the descriptor has no size fields: a resize carries (oh, ow) in k and stride
+            flags = L.TOP_NEAREST if nearest else 0
+            out_shape = (nb, k, stride, c)
+        elif op == "convt":
+            c2 = ps[0].shape[1]
+            out_shape = (nb, 2 * h, 2 * w, c2)
         else:
             raise ValueError(f"unknown training op {op!r}")
-        want_in = {"gn_act": (1, 2), "add": (1, 2), "cat": (2, 2)}.get(op, (1, 1))
-        want_p = {"conv": (1, 2), "gn_act": (2, 2), "layernorm": (1, 1), "linear": (2, 2), "learned_sinu": (1, 1)}.get(op, (0, 0))
+        want_in = {"gn_act": (1, 2), "norm_act": (1, 2), "up2_bilinear": (1, 2), "add": (1, 2), "cat": (2, 2)}.get(op, (1, 1))
+        want_p = {"conv": (1, 2), "gn_act": (2, 2), "norm_act": (2, 2) if groups else (4, 4), "convt": (2, 2), "layernorm": (1, 1), "linear": (2, 2),
+                  "learned_sinu": (1, 1)}.get(op, (0, 0))
         if not (want_in[0] <= len(ins) <= want_in[1]) or not (want_p[0] <= len(ps) <= want_p[1]):
             raise ValueError(f"{op}: {len(ins)} inputs and {len(ps)} parameters")
-        expect = {"conv": [(nb, h, w, c)], "gn_act": [(nb, h, w, c), (nb, 2 * c)], "add": [tuple(x.shape)] * 2, "cat": [(nb, h, w, c), (nb, h, w, c2)],
+        expect = {"conv": [(nb, h, w, c)], "gn_act": [(nb, h, w, c), (nb, 2 * c)], "norm_act": [(nb, h, w, c), (nb, 2 * c)],
+                  "up2_bilinear": [(nb, h, w, c), (nb, h, w, c2)], "add": [tuple(x.shape)] * 2, "cat": [(nb, h, w, c), (nb, h, w, c2)],
                   "linear": [(nb, c)], "learned_sinu": [(nb,)]}.get(op, [tuple(x.shape)])
         for t, sh in zip(ins, expect):
             if tuple(t.shape) != sh:
                 raise ValueError(f"{op}: an input has shape {tuple(t.shape)}, expected {sh}")
-        pshape = {"conv": [(c2, c, k, k), (c2,)], "gn_act": [(c,), (c,)], "layernorm": [(1, c, 1, 1)], "linear": [(c2, c), (c2,)],
+        pshape = {"conv": [(c2, c, k, k), (c2,)], "gn_act": [(c,), (c,)], "norm_act": [(c,)] * 4, "convt": [(c, c2, 4, 4), (c2,)], "layernorm": [(1, c, 1, 1)], "linear": [(c2, c), (c2,)],
                   "learned_sinu": [(c,)]}.get(op, [])
         for t, sh in zip(ps, pshape):
             if t.numel() != int(np.prod(sh)):
@@ -768,12 +792,22 @@ class HipEngine:
             raise ValueError("grads_in must match params")
         y = torch.empty(out_shape, dtype=torch.float32, device=x.device)
         dins = [torch.empty_like(t) for t in ins]
+        if skip_grad is not None:
+            dins[1] = _f32c(skip_grad, "skip_grad").clone()
+            if dins[1].shape != ins[1].shape:
+                raise ValueError("skip_grad must have the second source's shape")
+        if mask is not None:
+            if mask.dtype != torch.uint8 or not mask.is_cuda or not mask.is_contiguous() or tuple(mask.shape) != tuple(x.shape):
+                raise ValueError("mask: a contiguous uint8 tensor of the input's shape on the device")
+            ins = ins + [mask]  # follows the inputs in the pointer array
         desc = L.TrainOp(L.TRAIN_OPS[op], nb, h, w, c, c2, k, stride, pad, groups, flags, float(p))
         arr = lambda ts: (C.c_void_p * max(len(ts), 1))(*[t.data_ptr() for t in ts])
         self._check(self._lib.dyf_op_train_f32(self._h, C.byref(desc), arr(ins), arr(ps), dout.data_ptr(), y.data_ptr(), arr(dins), arr(gs),
                                                self._stream()))
         if op == "learned_sinu":
             dins = [None]  # a time value has no gradient
+        if mask is not None:
+            dins = None    # forward only
         return {"y": y, "dinputs": dins, "dparams": gs}
 
     def op_upconv2d(self, x_nhwc_bf16: torch.Tensor, weight: torch.Tensor, scale: Optional[torch.Tensor] = None,

@@ -126,7 +126,7 @@ dyf_status dyf_op_attention_f32(dyf_engine* engine, const float* qkv_dev, int32_
 dyf_status dyf_train_conv_check(dyf_engine* engine, int32_t kind, int32_t n, int32_t h, int32_t w, int32_t cin, int32_t cout,
                                 int32_t k, int32_t s, int32_t p, uint32_t seed, float* out_host);
 
-/* ONE recorded op of the ResNet-UNet training step (csrc/train_resnet.inc RCtx) and its adjoint, for float64 parity tests of the
+/* ONE recorded op of the training step of either backbone (csrc/train_resnet.inc RCtx) and its adjoint, for float64 parity tests of the
  * fp32 kernels.  The seam calls the RCtx member function itself on a scratch tape and then runs the recorded closures in reverse with
  * the loop dyf_train_backward runs, so grid sizes, chunk counts and kernel choices are the training step's own.  Convs take their
  * operand precision from dyf_train_set_precision like the step does.  Tensors are fp32, activations NHWC.
@@ -146,19 +146,36 @@ dyf_status dyf_train_conv_check(dyf_engine* engine, int32_t kind, int32_t n, int
  *   DROPOUT     x (nb,h,w,c); p          GELU  x (nb,h,w,c)
  *   ADD         a, b (nb,h,w,c); DYF_TOP_SAME = add(a, a): one input, one gradient
  *   CAT         a (nb,h,w,c), b (nb,h,w,c2) -> (nb,h,w,c+c2)          UP2_NEAREST x (nb,h,w,c) -> (nb,2h,2w,c)
+ *   NORM_ACT    unet_simple's UNetBlock norm: GN_ACT's inputs; weight (c), bias (c) and, with groups = 0 (BatchNorm2d), running_mean (c),
+ *               running_var (c), whose dparams entries RECEIVE the statistics as the forward left them.  groups > 0: GroupNorm; groups = 0:
+ *               batch statistics (running statistics updated, momentum 0.1), DYF_TOP_RUNNING: normalise by the running statistics.  SiLU, or
+ *               DYF_TOP_LEAKY (slope 0.2) / DYF_TOP_RELU; dropout p from the generator, or with DYF_TOP_MASK from a uint8 keep mask (nb,h,w,c)
+ *               that follows the inputs in inputs_dev -- the sampling path's injected masks: the forward alone runs, no gradient is written.
+ *               Sum kernels on unet_simple's grid (GN_ACT: the ResNet-UNet's)
+ *   UP2_BILINEAR x (nb,h,w,c) [, x2 (nb,h,w,c2): the upsample of cat([x, x2]) without the concat] -> (nb,2h,2w,c+c2), bilinear
+ *               align_corners=False; DYF_TOP_GRAD_IN: dinputs_dev[1] is IN/OUT, the gradient x2 already has from another consumer
+ *   RESIZE      x (nb,h,w,c) -> (nb,k,stride,c): F.interpolate(size=(k, stride)), bilinear align_corners=False or DYF_TOP_NEAREST
+ *   CONVT       x (nb,h,w,c); weight (c,c2,4,4), bias (c2) -> (nb,2h,2w,c2): ConvTranspose2d(c, c2, 4, stride 2, padding 1)
  * p > 0 draws from the engine's generator armed as dyf_op_attention_f32 arms it: a new forward (dyf_seed resets the counter), site 0,
  * global rows row offset .. + nb - 1, nb <= 2 max_batch; element index = the NHWC index inside the row ((h * N + i) * N + j for the
  * Attention probabilities).  Fields an op does not use must be 0.  What the descriptor cannot express is refused
  * (DYF_ERR_INVALID_ARGUMENT / DYF_ERR_UNSUPPORTED), never truncated.  Synchronises; everything allocated goes back to the engine. */
 typedef enum dyf_train_op_kind {
     DYF_TOP_CONV = 0, DYF_TOP_GN_ACT = 1, DYF_TOP_LAYERNORM = 2, DYF_TOP_LINATTN = 3, DYF_TOP_ATTENTION = 4, DYF_TOP_LINEAR = 5,
-    DYF_TOP_LEARNED_SINU = 6, DYF_TOP_DROPOUT = 7, DYF_TOP_GELU = 8, DYF_TOP_ADD = 9, DYF_TOP_CAT = 10, DYF_TOP_UP2_NEAREST = 11
+    DYF_TOP_LEARNED_SINU = 6, DYF_TOP_DROPOUT = 7, DYF_TOP_GELU = 8, DYF_TOP_ADD = 9, DYF_TOP_CAT = 10, DYF_TOP_UP2_NEAREST = 11,
+    DYF_TOP_NORM_ACT = 12, DYF_TOP_UP2_BILINEAR = 13, DYF_TOP_RESIZE = 14, DYF_TOP_CONVT = 15
 } dyf_train_op_kind;
 #define DYF_TOP_WS 1
 #define DYF_TOP_BIAS 2
 #define DYF_TOP_PRE 4
 #define DYF_TOP_FILM 8
 #define DYF_TOP_SAME 16
+#define DYF_TOP_RUNNING 32
+#define DYF_TOP_MASK 64
+#define DYF_TOP_LEAKY 128
+#define DYF_TOP_RELU 256
+#define DYF_TOP_NEAREST 512
+#define DYF_TOP_GRAD_IN 1024
 typedef struct dyf_train_op {
     int32_t op, nb, h, w, c, c2, k, stride, pad, groups, flags;
     float p;

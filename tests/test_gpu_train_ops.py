@@ -1,5 +1,5 @@
-"""-m gpu: every op the ResNet-UNet training step records (csrc/train_resnet.inc RCtx: forward kernels and the recorded adjoints),
-ONE op at a time through the training step's own launch code (dyf_op_train_f32), against float64 torch on the CPU.
+"""-m gpu: every op the training step records for either backbone (csrc/train_resnet.inc RCtx: forward kernels and the recorded
+adjoints), ONE op at a time through the training step's own launch code (dyf_op_train_f32), against float64 torch on the CPU.
 
 The end-to-end training tests hold a gradient to 1e-3 of the GLOBAL gradient norm at toy sizes; here every output and every gradient
 is held on its own, at the shapes where the launch geometry changes: LinearAttention across the 32-pixel chunks (a last chunk of one
@@ -19,6 +19,14 @@ pixel shapes: dq and dk of LinearAttention at hw = 1 (the k-softmax over one pix
 output does not depend on q), dq and dk of Attention at N = 1 (a softmax over one key is constant), dz and dgamma of GroupNorm at
 C = 8, hw = 1 (groups of ONE element: xhat = 0).  The last one found the normalisation backward keeping an fma's rounding residue
 times rstd = 316 (2e-5 of dy instead of 0): t_norm_bwd_apply now rounds gamma * dbn as the group sums round it.
+
+unet_simple's ops (norm_act, up2_bilinear, resize, convt) run at the shapes where their launches change: BatchNorm on batch and on running
+statistics and GroupNorm(8) at 8 / 24 / 64 channels on 1 x 1, 3 x 5 and 15 x 15 planes (BatchNorm over ONE value, nb = 1 at 1 x 1, has
+xhat = 0: dz and dgamma are zero as above) and on one 65 x 65 plane, where a workgroup of the sum kernels takes 17 pixels; the updated
+running statistics are compared like a gradient.  An injected keep mask is the sampling path's dropout: those cases run the forward alone;
+dropout from the generator, with its gradients, has a case per kind.  The x2 upsample runs with one source and with the two that stand
+for a concatenation, also onto a gradient the second source already has; the readout also at 4096 pixels, where the step's small-channel
+matrix-core forms take its two weight-side products.
 """
 import pytest
 import torch
@@ -55,10 +63,18 @@ def check(eng, op, args, cid, accumulate=False):
     base = case.run(torch.float32, keep=keep, grads_in=gin)
     if case.p > 0.0:
         eng.seed(T.SEED)  # the forward counter restarts: the op draws the masks of forward 0, site 0
-    r = eng.op_train(case.op, [t.to(DEV) for t in case.ins], case.params, case.dout.to(DEV), gin, **case.kw)
+    extra = {}
+    if case.mask is not None:
+        extra["mask"] = case.mask.to(DEV)
+    if case.skip_grad is not None:
+        extra["skip_grad"] = case.skip_grad.to(DEV)
+    r = eng.op_train(case.op, [t.to(DEV) for t in case.ins], case.params, case.dout.to(DEV), gin, **case.kw, **extra)
     got = {"y": r["y"].cpu()}
-    got.update({"d" + n: t.cpu() for n, t in zip(case.in_names, r["dinputs"]) if t is not None})
-    got.update({"d" + n: t for n, t in zip(case.p_names, r["dparams"])})
+    if case.mask is None:  # (an injected mask: the forward alone ran)
+        got.update({"d" + n: t.cpu() for n, t in zip(case.in_names, r["dinputs"]) if t is not None})
+        got.update({"d" + n: t for n, t in zip(case.p_names, r["dparams"])})
+    if case.stats is not None:  # the running statistics as the forward left them
+        got.update(zip(("running_mean", "running_var"), r["dparams"][len(case.p_names):]))
     if case.split_qkv:
         d = got.pop("dx")
         got.update(dq=d[..., :128], dk=d[..., 128:256], dv=d[..., 256:])
@@ -66,7 +82,7 @@ def check(eng, op, args, cid, accumulate=False):
     errs, fp32 = {}, {}
     for k, w in want.items():
         assert bool(torch.isfinite(got[k]).all()), k
-        others = [v.reshape(-1) for n, v in want.items() if n != k and n != "y"]
+        others = [v.reshape(-1) for n, v in want.items() if n != k and n.startswith("d")]
         if others and rms(w) <= ZERO * rms(torch.cat(others)):  # zero in float64: absolute, against the op's other gradients
             errs[k] = float(got[k].abs().max()) / rms(torch.cat(others))
             fp32[k] = float(base[k].abs().max()) / rms(torch.cat(others))
@@ -122,9 +138,32 @@ def test_small_ops(eng, args, request):
     check(eng, "small", args, request.node.callspec.id)
 
 
+@pytest.mark.parametrize("args", cases("norm_act"))
+def test_norm_act(eng, args, request):
+    check(eng, "norm_act", args, request.node.callspec.id)
+
+
+@pytest.mark.parametrize("args", cases("up2_bilinear"))
+def test_up2_bilinear(eng, args, request):
+    errs = check(eng, "up2_bilinear", args, request.node.callspec.id)
+    assert ("dx2" in errs) == (args[3] > 0)  # both source gradients were compared
+
+
+@pytest.mark.parametrize("args", cases("resize"))
+def test_resize(eng, args, request):
+    check(eng, "resize", args, request.node.callspec.id)
+
+
+@pytest.mark.parametrize("args", cases("convt"))
+def test_conv_transpose4s2(eng, args, request):
+    check(eng, "convt", args, request.node.callspec.id)
+
+
 ACCUMULATE = [("conv", (3, 1, 1, 24, 40, 1, 1, 11, 13, 3, 0)), ("conv", (1, 1, 0, 128, 64, 0, 1, 11, 13, 3, 0)), ("conv", (7, 1, 3, 3, 8, 0, 1, 11, 13, 1, 0)),
               ("gn_act", (24, 35, 3, 1, 0.2)), ("layernorm", (24, 33, 3, 0.1)), ("layernorm", (64, 33, 3, 0.0)), ("linear", (5, 17, 6, 1)),
-              ("small", ("learned_sinu", 5))]
+              ("small", ("learned_sinu", 5)), ("norm_act", ("bn_batch", 24, 3, 5, 3, 1, 0.1, "relu", "gen")),
+              ("norm_act", ("bn_running", 24, 15, 15, 3, 1, 0.0, "leaky", "mask")), ("norm_act", ("gn8", 64, 3, 5, 3, 0, 0.0, "relu", "mask")),
+              ("convt", (64, 3, 11, 13, 3)), ("convt", (8, 1, 4, 4, 1))]
 
 
 @pytest.mark.parametrize("op,args", ACCUMULATE, ids=[f"{op}-{'-'.join(str(a) for a in args)}" for op, args in ACCUMULATE])

@@ -144,6 +144,72 @@ def test_small_ops_are_torchs():
     close(F.gelu(T.learned_sinu(t, fw)), nets.time_embedding(P, "e", t, 0), "learned_sinu")
 
 
+# ---- unet_simple's ops
+@pytest.mark.parametrize("kind", T.US_KINDS)
+@pytest.mark.parametrize("C,act,film,p", [(8, "leaky", 0, 0.0), (24, "relu", 1, 0.1), (64, "leaky", 1, 0.0)])
+def test_norm_act_is_the_oracles_block_tail(kind, C, act, film, p):
+    """BatchNorm2d / GroupNorm(8) -> FiLM -> (Leaky)ReLU -> Dropout against torch.nn.functional and the oracle's unet_simple layer
+    functions (nets._norm, nets.film); the running statistics against torch.nn.BatchNorm2d(momentum=0.1)."""
+    z, gamma, beta = r64(3, 5, 7, C, seed=1, scale=1.5).requires_grad_(), (1 + r64(C, seed=2, scale=0.3)).requires_grad_(), r64(C, seed=3).requires_grad_()
+    rmean, rvar = r64(C, seed=4, scale=0.5), 0.5 + torch.rand(C, dtype=torch.float64, generator=torch.Generator().manual_seed(5))
+    temb = r64(3, 16, seed=6)
+    P = {"n.weight": gamma, "n.bias": beta, "n.running_mean": rmean, "n.running_var": rvar,
+         "t.1.weight": r64(2 * C, 16, seed=7, scale=0.2).requires_grad_(), "t.1.bias": r64(2 * C, seed=8, scale=0.2).requires_grad_()}
+    keep = (torch.rand(3, 5, 7, C, generator=torch.Generator().manual_seed(9)) >= p).double() if p else None
+    want = nets._norm(P, "n", nchw(z), "gn" if kind == "gn8" else "bn", kind == "bn_batch")
+    if film:
+        scale, shift = nets.film(P, "t", temb)
+        want = want * (scale + 1) + shift
+    want = nhwc(F.leaky_relu(want, nets.LEAKY_SLOPE) if act == "leaky" else F.relu(want))
+    if p:
+        want = want * keep / (1 - p)
+    ss = T.linear(temb, P["t.1.weight"], P["t.1.bias"], True) if film else None
+    got = T.norm_act(z, gamma, beta, rmean, rvar, 8 if kind == "gn8" else 0, kind == "bn_running", act, ss, keep, p)
+    close(got, want, "norm_act")
+    grads_close(got, want, [z, gamma, beta] + ([P["t.1.weight"], P["t.1.bias"]] if film else []), "norm_act")
+    if kind == "bn_batch":
+        bn = torch.nn.BatchNorm2d(C, momentum=0.1).double().train()
+        with torch.no_grad():
+            bn.running_mean.copy_(rmean)
+            bn.running_var.copy_(rvar)
+            bn(nchw(z))
+        m, v = T.bn_running_update(z.detach(), rmean, rvar)
+        close(m, bn.running_mean, "running_mean")
+        close(v, bn.running_var, "running_var")
+
+
+@pytest.mark.parametrize("h,w,oh,ow", [(11, 13, 16, 16), (16, 16, 11, 13), (5, 4, 10, 8), (1, 1, 2, 2), (7, 9, 7, 9)])
+def test_resize_and_up2_are_interpolate(h, w, oh, ow):
+    x = r64(2, h, w, 8, seed=h * w, scale=1.5).requires_grad_()
+    for nearest in (False, True):
+        want = nhwc(F.interpolate(nchw(x), size=(oh, ow), mode="nearest" if nearest else "bilinear"))
+        got = T.resize(x, oh, ow, nearest)
+        close(got, want, "resize")
+        grads_close(got, want, [x], "resize")
+    if (oh, ow) == (2 * h, 2 * w):
+        a, b = x[..., :3], x[..., 3:]
+        want = nhwc(F.interpolate(torch.cat([nchw(a), nchw(b)], 1), scale_factor=2, mode="bilinear"))
+        close(T.up2_bilinear(a, b), want, "up2_bilinear of two sources")
+        close(T.up2_bilinear(x), want, "up2_bilinear")
+        grads_close(T.up2_bilinear(a, b), want, [x], "up2_bilinear")
+
+
+def test_resize_is_the_oracles_explicit_formula():
+    """nets.bilinear_resize_explicit is written in float32 (its weights are float32 numbers): on float64 data it is held to float32's eps."""
+    x = r64(2, 11, 13, 5, seed=3)
+    err = rel_rms(T.resize(x, 16, 16), nhwc(nets.bilinear_resize_explicit(nchw(x), 16, 16)).double())
+    assert err <= 1e-6, err
+
+
+@pytest.mark.parametrize("d,C,h,w", [(8, 1, 4, 4), (8, 3, 11, 13), (64, 3, 5, 7)])
+def test_conv_transpose4s2_is_conv_transpose2d(d, C, h, w):
+    x, wt, b = r64(2, h, w, d, seed=1).requires_grad_(), r64(d, C, 4, 4, seed=2, scale=0.2).requires_grad_(), r64(C, seed=3).requires_grad_()
+    want = nhwc(F.conv_transpose2d(nchw(x), wt, b, stride=2, padding=1))
+    got = T.conv_transpose4s2(x, wt, b)
+    close(got, want, "conv_transpose4s2")
+    grads_close(got, want, [x, wt, b], "conv_transpose4s2")
+
+
 # ---- the bound bites: each mutant, on the inputs of the GPU cases it can show at, misses TOL by at least 10 x in some compared tensor
 def _where(op, pred):
     return [pytest.param(op, args, id=f"{op}-{cid}") for cid, args in T.specs(op) if pred(args)]
@@ -160,6 +226,13 @@ MUTANTS = {
     # at hw = 1) has no unbiased variance
     "unbiased": _where("layernorm", lambda a: True) + _where("gn_act", lambda a: 1 < a[1] * (a[0] // 8) <= 1000) + _where("conv", lambda a: a[5]),
     "quad_group": _where("gn_act", lambda a: a[0] == 24),
+    # unet_simple's ops.  Per-sample statistics differ from the batch's wherever there is more than one sample and more than one pixel
+    "per_sample_count": _where("norm_act", lambda a: a[0] == "bn_batch" and a[4] > 1 and a[2] * a[3] > 1),
+    # cnt / (cnt - 1) moves the statistic's variance term by 1 / (cnt - 1): shown at every batch-statistics case of more than one value
+    "biased_running_var": _where("norm_act", lambda a: a[0] == "bn_batch" and 1 < a[4] * a[2] * a[3] <= 2000),
+    "skip_half_dropped": _where("up2_bilinear", lambda a: a[3] > 0),
+    "no_half_pixel": _where("resize", lambda a: (a[0], a[1]) != (a[2], a[3]) and not a[4]),
+    "taps_transposed": _where("convt", lambda a: True),
 }
 
 

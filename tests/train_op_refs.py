@@ -1,4 +1,4 @@
-"""Plain references of the ops the ResNet-UNet training step records (dyffusion_amd/csrc/train_resnet.inc RCtx), and the cases
+"""Plain references of the ops the training step records for either backbone (dyffusion_amd/csrc/train_resnet.inc RCtx), and the cases
 tests/test_gpu_train_ops.py runs them at -- test infrastructure, no GPU.
 
 Every op is a pure torch function of a few lines, NHWC in and out like the engine's op seam (HipEngine.op_train); it computes in the
@@ -114,6 +114,84 @@ def up2_nearest(x):
     return x.repeat_interleave(2, 1).repeat_interleave(2, 2)
 
 
+# ---- unet_simple's ops (unet_simple.py:13-82, 164-197)
+def _act(v, act):
+    return v * torch.sigmoid(v) if act == "silu" else torch.where(v > 0, v, 0.2 * v) if act == "leaky" else v.clamp_min(0)
+
+
+def norm_act(z, gamma, beta, rmean=None, rvar=None, groups=0, running=False, act="leaky", ss=None, keep=None, p=0.0, mutant=None):
+    """UNetBlock after its conv: BatchNorm2d (batch statistics, or `running`) or GroupNorm(groups), biased variance, eps 1e-5 -> FiLM ->
+    activation -> Dropout: z (nb,h,w,C)."""
+    nb, h, w, C = z.shape
+    if groups:
+        zg = z.reshape(nb, h * w, groups, C // groups)
+        idx = torch.arange(C) // (C // groups)
+        mean, var = zg.mean((1, 3))[:, None, None, idx], zg.var((1, 3), unbiased=False)[:, None, None, idx]
+    elif running:
+        mean, var = rmean, rvar
+    elif mutant == "per_sample_count":  # the batch's 1 / (nb hw) taken per sample: every sample normalised by its own statistics
+        mean, var = z.mean((1, 2), keepdim=True), z.var((1, 2), unbiased=False, keepdim=True)
+    else:
+        mean, var = z.mean((0, 1, 2)), z.var((0, 1, 2), unbiased=False)
+    v = (z - mean) * (var + 1e-5).rsqrt() * gamma + beta
+    if ss is not None:
+        v = v * (1 + ss[:, None, None, :C]) + ss[:, None, None, C:]
+    y = _act(v, act)
+    return y if keep is None else y * keep * (1.0 / (1.0 - p))
+
+
+def bn_running_update(z, rmean, rvar, mutant=None):
+    """What a training-mode BatchNorm2d(momentum=0.1) forward leaves in its buffers: the batch mean and the UNBIASED batch variance (one
+    value per channel has none: the biased one, 0)."""
+    cnt = z.shape[0] * z.shape[1] * z.shape[2]
+    var = z.var((0, 1, 2), unbiased=False)
+    if cnt > 1 and mutant != "biased_running_var":
+        var = var * cnt / (cnt - 1)
+    return 0.9 * rmean + 0.1 * z.mean((0, 1, 2)), 0.9 * rvar + 0.1 * var
+
+
+def _resample_matrix(n_in, n_out, nearest, dtype, mutant=None):
+    """(n_out, n_in) weights of F.interpolate along one axis: bilinear with align_corners=False, or nearest."""
+    M = torch.zeros(n_out, n_in, dtype=dtype)
+    dst = torch.arange(n_out)
+    if nearest:
+        M[dst, (dst.to(dtype) * (n_in / n_out)).floor().long().clamp_max(n_in - 1)] = 1
+        return M
+    src = dst.to(dtype) * (n_in / n_out) if mutant == "no_half_pixel" else ((dst.to(dtype) + 0.5) * (n_in / n_out) - 0.5).clamp_min(0)
+    i0 = src.floor().long().clamp_max(n_in - 1)
+    lam = src - i0
+    M[dst, i0] += 1 - lam
+    M[dst, (i0 + 1).clamp_max(n_in - 1)] += lam
+    return M
+
+
+def resize(x, oh, ow, nearest=False, mutant=None):
+    """F.interpolate(size=(oh, ow)) on NHWC as two matrix products."""
+    _, h, w, _ = x.shape
+    rows = torch.einsum("oh,bhwc->bowc", _resample_matrix(h, oh, nearest, x.dtype, mutant), x)
+    return torch.einsum("pw,bowc->bopc", _resample_matrix(w, ow, nearest, x.dtype, mutant), rows)
+
+
+def up2_bilinear(x, x2=None, mutant=None):
+    """Upsample(scale_factor=2, bilinear) of x, or of cat([x, x2]) on the channels."""
+    if x2 is not None:
+        if mutant == "skip_half_dropped":  # the gradient of the second source never written
+            x2 = x2.detach() + 0 * x2
+        x = torch.cat([x, x2], -1)
+    return resize(x, 2 * x.shape[1], 2 * x.shape[2])
+
+
+def conv_transpose4s2(x, w, b, mutant=None):
+    """ConvTranspose2d(cin, C, 4, stride 2, padding 1) as a scatter over taps: x (nb,h,w,cin), w (cin,C,4,4) -> (nb,2h,2w,C)."""
+    nb, h, wd, _ = x.shape
+    y = torch.zeros(nb, 2 * h + 2, 2 * wd + 2, w.shape[1], dtype=x.dtype)
+    for ky in range(4):
+        for kx in range(4):
+            tap = w[:, :, kx, ky] if mutant == "taps_transposed" else w[:, :, ky, kx]
+            y[:, ky:ky + 2 * h:2, kx:kx + 2 * wd:2] = y[:, ky:ky + 2 * h:2, kx:kx + 2 * wd:2] + x @ tap
+    return y[:, 1:2 * h + 1, 1:2 * wd + 1] + b
+
+
 # ----------------------------------------------------------------------------------------------------------------- the cases
 class Case:
     """One op at one shape: fp32 CPU inputs / parameters / output gradient, the arguments of HipEngine.op_train, and the reference."""
@@ -124,11 +202,14 @@ class Case:
         self.in_names, self.p_names, self.split_qkv = in_names, p_names, split_qkv
         self.dout = None
         self.grad_inputs = [True] * len(ins)  # a time input has no gradient
+        self.stats = None       # norm_act on batch statistics: (ins, params, mutant) -> {"running_mean", "running_var"} after the forward
+        self.mask = None        # an injected uint8 keep mask: the forward alone runs
+        self.skip_grad = None   # up2_bilinear: the gradient its second source already has
 
     def run(self, dtype=torch.float64, keep=None, mutant=None, grads_in=None):
         """-> {"y", "d<input>", ..., "d<param>", ...} in `dtype` by torch.autograd; parameter gradients start from `grads_in`."""
         ins = [t.to(dtype).requires_grad_(g) for t, g in zip(self.ins, self.grad_inputs)]
-        ps = [t.to(dtype).requires_grad_(True) for t in self.params]
+        ps = [t.to(dtype).requires_grad_(i < len(self.p_names)) for i, t in enumerate(self.params)]  # running statistics come last
         kw = {}
         if keep is not None:
             kw["keep"] = keep.to(dtype)
@@ -151,11 +232,19 @@ class Case:
         if self.split_qkv:
             d = out.pop("dx")
             out.update(dq=d[..., :HID], dk=d[..., HID:2 * HID], dv=d[..., 2 * HID:])
+        if self.skip_grad is not None:
+            out["dx2"] = out["dx2"] + self.skip_grad.to(dtype)
+        if self.stats is not None:
+            out.update(self.stats([t.detach() for t in ins], [t.detach() for t in ps], mutant))
+        if self.mask is not None:
+            out = {k: v for k, v in out.items() if not k.startswith("d")}
         return out
 
 
 def engine_keep(case):
     """The keep mask the engine draws for `case` (dyf_seed(SEED), first forward, site 0, rows ROW_OFFSET ..), rebuilt on the host."""
+    if case.mask is not None:
+        return case.mask.double()
     if case.keep_shape is None:
         return None
     rows = [rng_host.row_mask_nhwc(case.keep_shape, case.p, SEED, 0, 0, ROW_OFFSET + r) for r in range(case.ins[0].shape[0])]
@@ -185,6 +274,10 @@ CONV_LAYERS = [(7, 1, 3, 3, 8, 0, 1), (7, 1, 3, 3, 64, 0, 1), (3, 1, 1, 8, 8, 1,
                (3, 1, 1, 128, 64, 1, 1), (1, 1, 0, 16, 8, 0, 1), (1, 1, 0, 128, 64, 0, 1), (1, 1, 0, 64, 1, 0, 1)]
 CONV_GRIDS = [(11, 13), (16, 16)]
 LINEAR = [(1, 16, 4, 0), (5, 17, 6, 1), (17, 256, 130, 1), (33, 64, 512, 0)]
+# unet_simple: (C, activation) -- both activations of a UNetBlock at the channel count that straddles quads
+US_NORM_C, US_PLANES = [(8, "leaky"), (24, "leaky"), (24, "relu"), (64, "relu")], [(1, 1), (3, 5), (15, 15)]
+US_KINDS = ("bn_batch", "bn_running", "gn8")
+UP2_PLANES, UP2_SOURCES = [(1, 1), (2, 3), (5, 4), (16, 16)], [(4, 0), (12, 0), (4, 8), (8, 4)]
 
 
 def conv_form(ci, co):
@@ -214,6 +307,23 @@ def specs(op):
         S.append(("k3s1p1-8to8-ws-var0-11x13-nb3-valu", (3, 1, 1, 8, 8, 1, 1, 11, 13, 3, 1)))
     elif op == "linear":
         S = [(f"rows{r}-K{k}-O{o}-pre{pre}", (r, k, o, pre)) for r, k, o, pre in LINEAR]
+    elif op == "norm_act":  # (kind, C, h, w, nb, film, p, act, drop): drop "mask" = an injected keep mask (forward only), "gen" = the generator
+        S = [(f"{kind}-C{c}-{act}-{h}x{w}-nb{nb}-{'film' if f else 'plain'}-p{p}", (kind, c, h, w, nb, f, p, act, "mask"))
+             for kind in US_KINDS for c, act in US_NORM_C for h, w in US_PLANES for nb in (1, 3) for f in (0, 1) for p in (0.0, 0.1)]
+        S += [(f"{kind}-C8-leaky-65x65-nb2-film-p0.0", (kind, 8, 65, 65, 2, 1, 0.0, "leaky", "mask")) for kind in US_KINDS]  # 17 pixels per workgroup
+        # dropout from the generator, with its gradients: the quad (8, 64) and the straddling (24) channel paths of the adjoint's kernels
+        S += [(f"{kind}-C{c}-{act}-{h}x{w}-nb3-{'film' if f else 'plain'}-p0.1-gen", (kind, c, h, w, 3, f, 0.1, act, "gen"))
+              for kind in US_KINDS for c, act, h, w, f in ((24, "relu", 3, 5, 1), (8, "leaky", 15, 15, 0), (64, "relu", 3, 5, 1))]
+    elif op == "up2_bilinear":  # (h, w, ca, cb, nb, skip_grad)
+        S = [(f"{h}x{w}-{ca}+{cb}-nb{nb}", (h, w, ca, cb, nb, 0)) for h, w in UP2_PLANES for ca, cb in UP2_SOURCES for nb in (1, 3)]
+        S += [(f"{h}x{w}-{ca}+{cb}-nb3-onto-skip-grad", (h, w, ca, cb, 3, 1)) for h, w in ((5, 4), (16, 16)) for ca, cb in ((4, 8), (8, 4))]
+        S += [("5x4-3+3-nb3-fallback", (5, 4, 3, 3, 3, 0)), ("5x4-3+3-nb3-fallback-onto-skip-grad", (5, 4, 3, 3, 3, 1)), ("5x4-6+0-nb3-fallback", (5, 4, 6, 0, 3, 0))]
+    elif op == "resize":  # (h, w, oh, ow, nearest)
+        S = [(f"{h}x{w}-to-{oh}x{ow}-{'nearest' if n else 'bilinear'}", (h, w, oh, ow, n)) for h, w, oh, ow in ((11, 13, 16, 16), (16, 16, 11, 13)) for n in (0, 1)]
+        S.append(("11x13-identity", (11, 13, 11, 13, 0)))
+    elif op == "convt":  # (dim, C, h, w, nb)
+        S = [(f"{d}to{c}-{h}x{w}-nb{nb}", (d, c, h, w, nb)) for d in (8, 64) for c in (1, 3) for h, w in ((4, 4), (11, 13)) for nb in (1, 3)]
+        S.append(("64to3-64x64-nb1", (64, 3, 64, 64, 1)))  # 4096 pixels: the small-channel matrix-core forms of the real step's readout
     elif op == "small":
         S = [("learned_sinu-half8", ("learned_sinu", 8)), ("learned_sinu-half5", ("learned_sinu", 5)), ("dropout-3x5x7", ("dropout",)),
              ("gelu", ("gelu",)), ("add-a-b", ("add", 0)), ("add-a-a", ("add", 1)), ("cat-8+24", ("cat", 8, 24)), ("cat-3+5", ("cat", 3, 5)),
@@ -274,6 +384,43 @@ def build(op, args):
         c = Case(None, op, [_rn(g, rows, K)], [_rn(g, O, K, scale=1.5 / math.sqrt(K)), _rn(g, O, scale=0.5)],
                  lambda i, ps: linear(i[0], ps[0], ps[1], bool(pre)), dict(pre=bool(pre)), p_names=("weight", "bias"))
         c.dout = torch.randn(rows, O, generator=g)
+    elif op == "norm_act":
+        kind, C, h, w, nb, f, p, act, drop = args
+        g = _gen(9, US_KINDS.index(kind), C, h, w, nb, f)
+        z = _rn(g, nb, h, w, C)
+        ins = [z] + ([_rn(g, nb, 2 * C, scale=0.5)] if f else [])
+        params = [1.0 + _rn(g, C, scale=0.5), _rn(g, C, scale=0.5)]
+        bn = kind != "gn8"
+        if bn:
+            params += [_rn(g, C, scale=0.5), 0.5 + torch.rand(C, generator=g)]
+        groups, running = (0 if bn else 8), kind == "bn_running"
+        c = Case(None, op, ins, params,
+                 lambda i, ps, **kw: norm_act(i[0], ps[0], ps[1], *(ps[2:] if bn else (None, None)), groups, running, act, i[1] if f else None, p=p, **kw),
+                 dict(groups=groups, p=p, act=act, running=running), p, (h, w, C) if p and drop == "gen" else None, ("z", "ss")[:len(ins)], ("gamma", "beta"))
+        if kind == "bn_batch":
+            c.stats = lambda i, ps, mutant: dict(zip(("running_mean", "running_var"), bn_running_update(i[0], ps[2], ps[3], mutant)))
+        if p and drop == "mask":
+            c.mask = (torch.rand(nb, h, w, C, generator=g) >= p).to(torch.uint8)
+        c.dout = torch.randn(z.shape, generator=g)
+    elif op == "up2_bilinear":
+        h, w, ca, cb, nb, sg = args
+        g = _gen(10, h, w, ca, cb, nb)
+        ins = [_rn(g, nb, h, w, ca)] + ([_rn(g, nb, h, w, cb)] if cb else [])
+        c = Case(None, op, ins, [], lambda i, ps, **kw: up2_bilinear(*i, **kw), in_names=("x", "x2")[:len(ins)])
+        c.dout = torch.randn(nb, 2 * h, 2 * w, ca + cb, generator=g)
+        if sg:
+            c.skip_grad = torch.randn(ins[1].shape, generator=g)
+    elif op == "resize":
+        h, w, oh, ow, near = args
+        g = _gen(11, h, w, oh, ow, near)
+        c = Case(None, op, [_rn(g, 3, h, w, 5)], [], lambda i, ps, **kw: resize(i[0], oh, ow, bool(near), **kw), dict(size=(oh, ow), nearest=bool(near)))
+        c.dout = torch.randn(3, oh, ow, 5, generator=g)
+    elif op == "convt":
+        d, C, h, w, nb = args
+        g = _gen(12, d, C, h, w, nb)
+        c = Case(None, op, [_rn(g, nb, h, w, d)], [_rn(g, d, C, 4, 4, scale=1.5 / math.sqrt(4 * d)), _rn(g, C, scale=0.5)],
+                 lambda i, ps, **kw: conv_transpose4s2(i[0], ps[0], ps[1], **kw), p_names=("weight", "bias"))
+        c.dout = torch.randn(nb, 2 * h, 2 * w, C, generator=g)
     elif args[0] == "learned_sinu":
         half = args[1]
         g = _gen(7, half)
