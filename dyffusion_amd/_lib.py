@@ -91,7 +91,8 @@ class TrainOp(C.Structure):
 
 
 TRAIN_OPS = {"conv": 0, "gn_act": 1, "layernorm": 2, "linattn": 3, "attention": 4, "linear": 5, "learned_sinu": 6, "dropout": 7,
-             "gelu": 8, "add": 9, "cat": 10, "up2_nearest": 11, "norm_act": 12, "up2_bilinear": 13, "resize": 14, "convt": 15}
+             "gelu": 8, "add": 9, "cat": 10, "up2_nearest": 11, "norm_act": 12, "up2_bilinear": 13, "resize": 14, "convt": 15,
+             "attention_stream": 16}
 TOP_WS, TOP_BIAS, TOP_PRE, TOP_FILM, TOP_SAME = 1, 2, 4, 8, 16
 TOP_RUNNING, TOP_MASK, TOP_LEAKY, TOP_RELU, TOP_NEAREST, TOP_GRAD_IN = 32, 64, 128, 256, 512, 1024
 

@@ -523,8 +523,13 @@ constexpr int AS_NW = 4;    // waves per workgroup: 128 queries
 constexpr int AS_KS = 36;   // floats per K row in LDS
 static_assert(AS_NW * 64 == 32 * (RD / 4), "one float4 of K and one of V per thread stage a 32-key tile");
 __device__ __forceinline__ int as_key(int r, int hi) { return (r & 3) + 8 * (r >> 2) + 4 * hi; }
-template <bool DROP>
-__global__ __launch_bounds__(64 * AS_NW) void t_at_stream_fwd(const float* __restrict__ qkv, int N, float scale, RDrop dr, float* __restrict__ out) {
+// LSE (a recorded forward past the kept-probabilities limit): also writes the query's softmax statistics (m, 1 / l) to lse (n, h, N, 2), all
+// the streaming backward keeps besides out.  (The pair, not the log-sum-exp m + log l: at scores of 50 one ulp of that sum is 4e-6, a common
+// factor on the whole row of P = exp(s - L) that dq = sum_j dS_ij k_j amplifies by |k| / spread(k) -- 1e-5 on the "rising" draw of the
+// tests; exp(s - m) / l is the forward's own normalisation.)  The sampling instantiation (LSE = false) computes what it always did.
+template <bool DROP, bool LSE>
+__global__ __launch_bounds__(64 * AS_NW) void t_at_stream_fwd(const float* __restrict__ qkv, int N, float scale, RDrop dr, float* __restrict__ out,
+                                                              float* __restrict__ lse) {
     __shared__ __attribute__((aligned(16))) float Ks[2][32 * AS_KS];
     __shared__ __attribute__((aligned(16))) float Vs[2][32 * RD];
     const int tid = threadIdx.x, l = tid & 63, lq = l & 31, hi = l >> 5;
@@ -611,15 +616,250 @@ __global__ __launch_bounds__(64 * AS_NW) void t_at_stream_fwd(const float* __res
     if (!active || qi >= N) return;
     lsum += __shfl_xor(lsum, 32, 64);
     const float inv = 1.0f / lsum;
+    if constexpr (LSE) {
+        if (hi == 0) ((float2*)lse)[((size_t)n * RH + h) * N + qi] = make_float2(m, inv);
+    }
     float* op = out + ((size_t)n * N + qi) * RHID + h * RD + 4 * hi;
     for (int g = 0; g < 4; ++g) *(float4*)(op + 8 * g) = make_float4(o[4 * g] * inv, o[4 * g + 1] * inv, o[4 * g + 2] * inv, o[4 * g + 3] * inv);
 }
 // the launch of the streaming core; d.on / d.mask select the dropout instantiation
-static inline void launch_t_at_stream_fwd(const float* qkv, int nb, int N, float scale, const RDrop& d, float* out, hipStream_t st) {
+// (lse: where a recorded forward keeps its softmax statistics; null = sampling)
+static inline void launch_t_at_stream_fwd(const float* qkv, int nb, int N, float scale, const RDrop& d, float* out, hipStream_t st, float* lse = nullptr) {
     dyf_form_note("t_at_stream_fwd", nb);
     const dim3 grid((unsigned)((N + 32 * AS_NW - 1) / (32 * AS_NW)), RH, (unsigned)nb);
-    if (d.on || d.mask) hipLaunchKernelGGL(t_at_stream_fwd<true>, grid, dim3(64 * AS_NW), 0, st, qkv, N, scale, d, out);
-    else hipLaunchKernelGGL(t_at_stream_fwd<false>, grid, dim3(64 * AS_NW), 0, st, qkv, N, scale, d, out);
+    const bool dropping = d.on || d.mask;
+    if (lse) {
+        if (dropping) hipLaunchKernelGGL((t_at_stream_fwd<true, true>), grid, dim3(64 * AS_NW), 0, st, qkv, N, scale, d, out, lse);
+        else hipLaunchKernelGGL((t_at_stream_fwd<false, true>), grid, dim3(64 * AS_NW), 0, st, qkv, N, scale, d, out, lse);
+    } else if (dropping) hipLaunchKernelGGL((t_at_stream_fwd<true, false>), grid, dim3(64 * AS_NW), 0, st, qkv, N, scale, d, out, lse);
+    else hipLaunchKernelGGL((t_at_stream_fwd<false, false>), grid, dim3(64 * AS_NW), 0, st, qkv, N, scale, d, out, lse);
+}
+
+// ---- the streaming backward (a recorded forward that took t_at_stream_fwd<.., LSE>): the scores are recomputed per 32 x 32 tile on the
+// same fma chain as the forward, P = exp(s - m) / l with the saved statistics, and
+//   dP_ij = keep_ij (dout_i . v_j)        D_i = sum_j P_ij dP_ij                dS_ij = P_ij (dP_ij - D_i)
+//   dq_i = scale sum_j dS_ij k_j          dk_j = scale sum_i dS_ij q_i          dv_j = sum_i P_ij keep_ij dout_i
+// D is summed from the recomputed P and dP in a first sweep over the keys, not taken as dout_i . out_i: equal in exact arithmetic, but in
+// fp32 the rounding of out leaves noise of 1e-7 |dout| |out| in dS where it is exactly 0 (one key: P = 1, dS = 0, as t_at_bwd_row gives
+// it).  keep enters as a select and the dropout scale 1 / (1 - p) multiplies the finished sums, so dP - D is one subtraction of two values
+// the kernels compute alike (D counts without the scale).
+// Nothing of size N^2 is written and there are no atomics: a wave owns its 32 output rows, so the gradients are bitwise repeatable.
+// Two kernels with the forward's lane maps (accumulator r of a lane is row as_key(r, hi), the lane's column is l & 31) and staging:
+//   t_at_stream_bwd_dq   one wave per 32 queries: Q (pre-scaled), dout, (m, 1 / l) in registers; K / V tiles through double-buffered LDS, twice.
+//                        S^T = K Q^T and dP^T = V dout^T leave a lane with its query's column: the first sweep sums D (a per-lane partial,
+//                        joined with the lane 32 away as the forward joins its row sum) and writes it (n, h, N); in the second the dS^T
+//                        accumulators are the B operand of dq^T = K^T dS^T (A = K[as_key(r, hi)][d = l & 31], a column read of the tile).
+//   t_at_stream_bwd_dkv  the mirror image, one wave per 32 keys: K, V in registers; Q (pre-scaled at staging as the forward pre-scales it:
+//                        dk then needs no final scale), dout, (m, 1 / l), D tiles through LDS.  S = Q K^T and dP = dout V^T leave a lane with its
+//                        key's column; P keep and dS are the B operands of dv^T = dout^T (P keep) and dk^T = Q^T dS.
+// Rows of a staged tile past N are zeros and their P / dS are set to exactly 0; waves past the last query / key only help staging.
+// Dropout: r_keep on element (h N + i) N + j of the row's stream, as the forward (never evaluated past N: an injected mask ends there).
+template <bool DROP>
+__global__ __launch_bounds__(64 * AS_NW) void t_at_stream_bwd_dq(const float* __restrict__ qkv, const float* __restrict__ dout, const float* __restrict__ lse, int N,
+                                                                 float scale, RDrop dr, float* __restrict__ Dm, float* __restrict__ dqkv) {
+    __shared__ __attribute__((aligned(16))) float Ks[2][32 * AS_KS];
+    __shared__ __attribute__((aligned(16))) float Vs[2][32 * AS_KS];
+    const int tid = threadIdx.x, l = tid & 63, lq = l & 31, hi = l >> 5;
+    const int h = blockIdx.y, n = blockIdx.z;
+    const int q0 = ((int)blockIdx.x * AS_NW + (tid >> 6)) * 32;
+    const bool active = q0 < N;
+    const int qi = q0 + lq, qc = qi < N ? qi : N - 1;
+    const float* base = qkv + (size_t)n * N * 3 * RHID + h * RD;
+    float qf[16], gf[16];
+    {
+        const float4* qp = (const float4*)(base + (size_t)qc * 3 * RHID + 16 * hi);
+        const float4* gp = (const float4*)(dout + ((size_t)n * N + qc) * RHID + h * RD + 16 * hi);
+        for (int c = 0; c < 4; ++c) {
+            const float4 v = qp[c], g = gp[c];
+            qf[4 * c] = v.x * scale; qf[4 * c + 1] = v.y * scale; qf[4 * c + 2] = v.z * scale; qf[4 * c + 3] = v.w * scale;
+            gf[4 * c] = g.x; gf[4 * c + 1] = g.y; gf[4 * c + 2] = g.z; gf[4 * c + 3] = g.w;
+        }
+    }
+    const size_t stat = ((size_t)n * RH + h) * N + qc;
+    const float2 mil = ((const float2*)lse)[stat];  // (m, 1 / l) of the lane's query
+    float Dq = 0.0f;
+    const int sk = tid >> 3, sc = (tid & 7) * 4;
+    float4 kreg, vreg;
+    auto fetch = [&](int kt) {
+        const int j = kt + sk;
+        kreg = vreg = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if (j < N) {
+            const float* p = base + (size_t)j * 3 * RHID + sc;
+            kreg = *(const float4*)(p + RHID);
+            vreg = *(const float4*)(p + 2 * RHID);
+        }
+    };
+    auto stage = [&](int b) {
+        *(float4*)(&Ks[b][sk * AS_KS + sc]) = kreg;
+        *(float4*)(&Vs[b][sk * AS_KS + sc]) = vreg;
+    };
+    as_f32x16 acc;
+    for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
+    const uint32_t ebase = ((uint32_t)h * (uint32_t)N + (uint32_t)qc) * (uint32_t)N;
+    const int tiles = (N + 31) / 32;
+    for (int sweep = 0; sweep < 2; ++sweep) {  // 0: D, 1: dq (the last barrier of sweep 0 frees buffer 0 for the first stage of sweep 1)
+        float dpart = 0.0f;
+        fetch(0);
+        stage(0);
+        __syncthreads();
+        for (int t = 0; t < tiles; ++t) {
+            const int b = t & 1, kt = t * 32;
+            if (t + 1 < tiles) fetch(kt + 32);
+            if (active) {
+                as_f32x16 s, dp;
+                for (int r = 0; r < 16; ++r) s[r] = dp[r] = 0.0f;
+                const float4* kp = (const float4*)(&Ks[b][lq * AS_KS + 16 * hi]);
+                const float4* vp = (const float4*)(&Vs[b][lq * AS_KS + 16 * hi]);
+                for (int c = 0; c < 4; ++c) {
+                    const float4 kv = kp[c];
+                    s = __builtin_amdgcn_mfma_f32_32x32x2f32(kv.x, qf[4 * c], s, 0, 0, 0);
+                    s = __builtin_amdgcn_mfma_f32_32x32x2f32(kv.y, qf[4 * c + 1], s, 0, 0, 0);
+                    s = __builtin_amdgcn_mfma_f32_32x32x2f32(kv.z, qf[4 * c + 2], s, 0, 0, 0);
+                    s = __builtin_amdgcn_mfma_f32_32x32x2f32(kv.w, qf[4 * c + 3], s, 0, 0, 0);
+                    const float4 vv = vp[c];
+                    dp = __builtin_amdgcn_mfma_f32_32x32x2f32(vv.x, gf[4 * c], dp, 0, 0, 0);
+                    dp = __builtin_amdgcn_mfma_f32_32x32x2f32(vv.y, gf[4 * c + 1], dp, 0, 0, 0);
+                    dp = __builtin_amdgcn_mfma_f32_32x32x2f32(vv.z, gf[4 * c + 2], dp, 0, 0, 0);
+                    dp = __builtin_amdgcn_mfma_f32_32x32x2f32(vv.w, gf[4 * c + 3], dp, 0, 0, 0);
+                }
+                for (int r = 0; r < 16; ++r) {
+                    const int j = kt + as_key(r, hi);
+                    const bool valid = j < N;  // a key past N: P = 0 exactly
+                    bool keep = valid;
+                    if (DROP) keep = valid && r_keep(dr, n, ebase + (uint32_t)j) != 0.0f;
+                    const float p = valid ? __expf(s[r] - mil.x) * mil.y : 0.0f, g = keep ? dp[r] : 0.0f;
+                    if (sweep == 0) dpart = fmaf(p, g, dpart);
+                    else s[r] = p * (g - Dq);
+                }
+                if (sweep == 1) {
+                    const float* kc = &Ks[b][lq];
+                    for (int r = 0; r < 16; ++r) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(kc[as_key(r, hi) * AS_KS], s[r], acc, 0, 0, 0);
+                }
+            }
+            if (t + 1 < tiles) stage(b ^ 1);
+            __syncthreads();
+        }
+        if (sweep == 0) {
+            Dq = dpart + __shfl_xor(dpart, 32, 64);  // (a + b = b + a: both halves hold the same bits)
+            if (active && hi == 0 && qi < N) Dm[stat] = Dq;
+        }
+    }
+    if (!active || qi >= N) return;
+    const float so = DROP ? scale * dr.scale : scale;
+    float* op = dqkv + ((size_t)n * N + qi) * 3 * RHID + h * RD + 4 * hi;
+    for (int g = 0; g < 4; ++g) *(float4*)(op + 8 * g) = make_float4(acc[4 * g] * so, acc[4 * g + 1] * so, acc[4 * g + 2] * so, acc[4 * g + 3] * so);
+}
+template <bool DROP>
+__global__ __launch_bounds__(64 * AS_NW) void t_at_stream_bwd_dkv(const float* __restrict__ qkv, const float* __restrict__ dout, const float* __restrict__ lse,
+                                                                  const float* __restrict__ Dm, int N, float scale, RDrop dr, float* __restrict__ dqkv) {
+    __shared__ __attribute__((aligned(16))) float Qs[2][32 * AS_KS];
+    __shared__ __attribute__((aligned(16))) float Gs[2][32 * AS_KS];
+    __shared__ float Ss[2][3][32];  // per query of the tile: m, 1 / l, D
+    const int tid = threadIdx.x, l = tid & 63, lq = l & 31, hi = l >> 5;
+    const int h = blockIdx.y, n = blockIdx.z;
+    const int k0 = ((int)blockIdx.x * AS_NW + (tid >> 6)) * 32;
+    const bool active = k0 < N;
+    const int kj = k0 + lq, kc = kj < N ? kj : N - 1;
+    const float* base = qkv + (size_t)n * N * 3 * RHID + h * RD;
+    const float* gbase = dout + (size_t)n * N * RHID + h * RD;
+    const size_t srow = ((size_t)n * RH + h) * N;
+    float kf[16], vf[16];
+    {
+        const float4* kp = (const float4*)(base + (size_t)kc * 3 * RHID + RHID + 16 * hi);
+        const float4* vp = (const float4*)(base + (size_t)kc * 3 * RHID + 2 * RHID + 16 * hi);
+        for (int c = 0; c < 4; ++c) {
+            const float4 k = kp[c], v = vp[c];
+            kf[4 * c] = k.x; kf[4 * c + 1] = k.y; kf[4 * c + 2] = k.z; kf[4 * c + 3] = k.w;
+            vf[4 * c] = v.x; vf[4 * c + 1] = v.y; vf[4 * c + 2] = v.z; vf[4 * c + 3] = v.w;
+        }
+    }
+    // staging: thread -> (query tid>>3, channels 4 (tid&7) ..+3) of the tile; threads 0..31 its m, 32..63 its 1 / l, 64..95 its D
+    const int sq = tid >> 3, sc = (tid & 7) * 4;
+    float4 qreg, greg;
+    float sreg = 0.0f;
+    auto fetch = [&](int qt) {
+        const int i = qt + sq;
+        qreg = greg = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if (i < N) {
+            const float4 v = *(const float4*)(base + (size_t)i * 3 * RHID + sc);
+            qreg = make_float4(v.x * scale, v.y * scale, v.z * scale, v.w * scale);
+            greg = *(const float4*)(gbase + (size_t)i * RHID + sc);
+        }
+        if (tid < 96) {
+            const int ii = qt + (tid & 31);
+            sreg = ii >= N ? 0.0f : tid < 64 ? lse[2 * (srow + ii) + (tid >> 5)] : Dm[srow + ii];
+        }
+    };
+    auto stage = [&](int b) {
+        *(float4*)(&Qs[b][sq * AS_KS + sc]) = qreg;
+        *(float4*)(&Gs[b][sq * AS_KS + sc]) = greg;
+        if (tid < 96) Ss[b][tid >> 5][tid & 31] = sreg;
+    };
+    as_f32x16 dk, dv;
+    for (int r = 0; r < 16; ++r) dk[r] = dv[r] = 0.0f;
+    const int tiles = (N + 31) / 32;
+    fetch(0);
+    stage(0);
+    __syncthreads();
+    for (int t = 0; t < tiles; ++t) {
+        const int b = t & 1, qt = t * 32;
+        if (t + 1 < tiles) fetch(qt + 32);
+        if (active) {
+            as_f32x16 s, dp;
+            for (int r = 0; r < 16; ++r) s[r] = dp[r] = 0.0f;
+            const float4* qp = (const float4*)(&Qs[b][lq * AS_KS + 16 * hi]);
+            const float4* gp = (const float4*)(&Gs[b][lq * AS_KS + 16 * hi]);
+            for (int c = 0; c < 4; ++c) {
+                const float4 qv = qp[c];
+                s = __builtin_amdgcn_mfma_f32_32x32x2f32(qv.x, kf[4 * c], s, 0, 0, 0);
+                s = __builtin_amdgcn_mfma_f32_32x32x2f32(qv.y, kf[4 * c + 1], s, 0, 0, 0);
+                s = __builtin_amdgcn_mfma_f32_32x32x2f32(qv.z, kf[4 * c + 2], s, 0, 0, 0);
+                s = __builtin_amdgcn_mfma_f32_32x32x2f32(qv.w, kf[4 * c + 3], s, 0, 0, 0);
+                const float4 gv = gp[c];
+                dp = __builtin_amdgcn_mfma_f32_32x32x2f32(gv.x, vf[4 * c], dp, 0, 0, 0);
+                dp = __builtin_amdgcn_mfma_f32_32x32x2f32(gv.y, vf[4 * c + 1], dp, 0, 0, 0);
+                dp = __builtin_amdgcn_mfma_f32_32x32x2f32(gv.z, vf[4 * c + 2], dp, 0, 0, 0);
+                dp = __builtin_amdgcn_mfma_f32_32x32x2f32(gv.w, vf[4 * c + 3], dp, 0, 0, 0);
+            }
+            for (int r = 0; r < 16; ++r) {
+                const int ir = as_key(r, hi), i = qt + ir;
+                const bool valid = i < N;  // a query past N: P = 0 exactly
+                bool keep = valid;
+                if (DROP) keep = valid && r_keep(dr, n, ((uint32_t)h * (uint32_t)N + (uint32_t)i) * (uint32_t)N + (uint32_t)kc) != 0.0f;
+                const float p = valid ? __expf(s[r] - Ss[b][0][ir]) * Ss[b][1][ir] : 0.0f, g = keep ? dp[r] : 0.0f;
+                s[r] = keep ? p : 0.0f;
+                dp[r] = p * (g - Ss[b][2][ir]);
+            }
+            const float *gc = &Gs[b][lq], *qc = &Qs[b][lq];
+            for (int r = 0; r < 16; ++r) {
+                dv = __builtin_amdgcn_mfma_f32_32x32x2f32(gc[as_key(r, hi) * AS_KS], s[r], dv, 0, 0, 0);
+                dk = __builtin_amdgcn_mfma_f32_32x32x2f32(qc[as_key(r, hi) * AS_KS], dp[r], dk, 0, 0, 0);
+            }
+        }
+        if (t + 1 < tiles) stage(b ^ 1);
+        __syncthreads();
+    }
+    if (!active || kj >= N) return;
+    const float so = DROP ? dr.scale : 1.0f;
+    float* op = dqkv + ((size_t)n * N + kj) * 3 * RHID + RHID + h * RD + 4 * hi;
+    for (int g = 0; g < 4; ++g) {
+        *(float4*)(op + 8 * g) = make_float4(dk[4 * g] * so, dk[4 * g + 1] * so, dk[4 * g + 2] * so, dk[4 * g + 3] * so);
+        *(float4*)(op + RHID + 8 * g) = make_float4(dv[4 * g] * so, dv[4 * g + 1] * so, dv[4 * g + 2] * so, dv[4 * g + 3] * so);
+    }
+}
+// the two launches of the streaming backward: D (n, h, N) is written by the first and read by the second (one stream orders them)
+static inline void launch_t_at_stream_bwd(const float* qkv, const float* dout, const float* lse, int nb, int N, float scale,
+                                          const RDrop& d, float* Dm, float* dqkv, hipStream_t st) {
+    dyf_form_note("t_at_stream_bwd_dq", nb);
+    dyf_form_note("t_at_stream_bwd_dkv", nb);
+    const dim3 grid((unsigned)((N + 32 * AS_NW - 1) / (32 * AS_NW)), RH, (unsigned)nb);
+    if (d.on || d.mask) {
+        hipLaunchKernelGGL(t_at_stream_bwd_dq<true>, grid, dim3(64 * AS_NW), 0, st, qkv, dout, lse, N, scale, d, Dm, dqkv);
+        hipLaunchKernelGGL(t_at_stream_bwd_dkv<true>, grid, dim3(64 * AS_NW), 0, st, qkv, dout, lse, Dm, N, scale, d, dqkv);
+    } else {
+        hipLaunchKernelGGL(t_at_stream_bwd_dq<false>, grid, dim3(64 * AS_NW), 0, st, qkv, dout, lse, N, scale, d, Dm, dqkv);
+        hipLaunchKernelGGL(t_at_stream_bwd_dkv<false>, grid, dim3(64 * AS_NW), 0, st, qkv, dout, lse, Dm, N, scale, d, dqkv);
+    }
 }
 // row pass of the backward: dS (n, h, N, N) = P * (dP - sum_j P dP), dP_ij = keep_ij * (dout_i . v_j); dq_i = scale * sum_j dS_ij k_j
 __global__ void t_at_bwd_row(const float* qkv, const float* P, const float* dout, int N, long long rows, float scale, RDrop dr, float* dS,
@@ -1184,7 +1424,9 @@ struct RCtx {
         return dbg(y, "linattn");
     }
     // Attention core on qkv (nb, N, 384) -> (nb, N, 128), dropout on the probabilities
-    dyf::RT* attention(dyf::RT* qkv, int N, float p_drop) {
+    // A recorded forward of N >= DYF_TRAIN_ATTN_STREAM_MIN tokens (kernel-form switch, default AT_KEEP_P_MAX + 1; `streaming`: the op seam's
+    // ATTENTION_STREAM) keeps the softmax statistics (m, 1 / l) per (row, head, token) instead of the probabilities and records the streaming adjoint.
+    dyf::RT* attention(dyf::RT* qkv, int N, float p_drop, bool streaming = false) {
         const long long rows = (long long)nb * RH * N;
         const float scale = 1.0f / sqrtf((float)RD);
         if (!mem.recording() && N > AT_KEEP_P_MAX) {  // sampling past the kept-probabilities limit: the streaming core, no P, no adjoint
@@ -1193,6 +1435,24 @@ struct RCtx {
             launch_t_at_stream_fwd(qkv->p, nb, N, scale, d, y->p, st);
             return dbg(y, "attention");
         }
+        const long long stream_min = dyf_form_int("DYF_TRAIN_ATTN_STREAM_MIN", AT_KEEP_P_MAX + 1);
+        if (mem.recording() && (streaming || N > AT_KEEP_P_MAX || N >= stream_min)) {
+            float* L = fbuf((size_t)2 * rows);
+            const RDrop d = drop(p_drop, (size_t)RH * N * N);
+            dyf::RT* y = make((size_t)nb * N * RHID);
+            launch_t_at_stream_fwd(qkv->p, nb, N, scale, d, y->p, st, L);
+            back([=]() -> dyf_status {
+                if (!y->g) return DYF_OK;
+                float* D = tbuf((size_t)rows);
+                float* dq = tbuf(qkv->n);  // both kernels together write every element
+                if (err != DYF_OK) return err;
+                launch_t_at_stream_bwd(qkv->p, y->g, L, nb, N, scale, d, D, dq, st);
+                accum(qkv, dq);
+                return DYF_OK;
+            });
+            return dbg(y, "attention");
+        }
+        dyf_form_note("t_at_fwd", nb);
         float* Pm = fbuf((size_t)rows * N);
         const RDrop d = drop(p_drop, (size_t)RH * N * N);
         dyf::RT* y = make((size_t)nb * N * RHID);
@@ -1278,7 +1538,9 @@ struct RCount {
         take((size_t)2 * ((hw + LA_CHUNK - 1) / LA_CHUNK) * nb * RH * RD * RD * 2);
         return make(tot);
     }
-    dyf::RT* attention(dyf::RT*, int N, float) {  // (counts a sampling forward: past AT_KEEP_P_MAX the streaming core keeps no P)
+    // (counts a sampling forward: past AT_KEEP_P_MAX the streaming core keeps no P.  A recorded forward takes its blocks from the caching
+    // allocator instead: P and dS, or -- the streaming pair -- the softmax statistics (2 nb * 4 * N floats) and the row sums D (nb * 4 * N))
+    dyf::RT* attention(dyf::RT*, int N, float) {
         if (N <= AT_KEEP_P_MAX) take((size_t)nb * RH * N * N);
         return make((size_t)nb * N * RHID);
     }
@@ -1415,13 +1677,14 @@ inline int net_sources(const Net& n, const float* inputs_dev, const float* cond_
     if (n.rn) std::swap(src[0], src[1]);
     return n.rn ? src[0].ch : 0;
 }
-// null, or why the net's forward cannot be recorded: unet.Unet's bottleneck Attention keeps its (tokens x tokens) probabilities for the backward
+// null, or why the net's forward cannot be recorded: past AT_KEEP_P_MAX tokens unet.Unet's bottleneck Attention records the streaming
+// pair, whose dropout element index (h N + i) N + j is uint32_t as in sampling (rn_f32_supported)
 inline const char* net_record_refusal(const dyf_engine* e, const Net& n) {
     if (!n.rn) return nullptr;
     const RNames R = rn_names(e, n.cfg);
-    return (long long)R.lev_h.back() * R.lev_w.back() <= AT_KEEP_P_MAX
+    return (long long)R.lev_h.back() * R.lev_w.back() <= AT_STREAM_MAX
                ? nullptr
-               : "training step: the bottleneck Attention keeps its (tokens x tokens) probabilities -- at most 4096 tokens";
+               : "training step: the bottleneck Attention indexes its (4 x tokens x tokens) probabilities with 32 bits -- at most 32767 tokens";
 }
 template <typename Ctx>
 RT* net_walk(Ctx& X, const dyf_engine* e, const Net& n, int nb, const Source* src, const float* time_dev, float time_value, bool bn_batch, RT** x_in) {
@@ -1690,13 +1953,14 @@ dyf_status f32_op_train(dyf_engine* e, const dyf_train_op* dp, const float* cons
     auto refuse = [&](dyf_status s, const char* what) { return fail(e, s, std::string("dyf_op_train_f32: ") + what); };
     if (d.nb < 1 || d.h < 1 || d.w < 1 || d.c < 1) return refuse(DYF_ERR_INVALID_ARGUMENT, "nb, h, w and c must be positive");
     if (!(d.p >= 0.0f && d.p < 1.0f)) return refuse(DYF_ERR_INVALID_ARGUMENT, "p must be in [0, 1)");
-    const bool has_p = d.op == DYF_TOP_GN_ACT || d.op == DYF_TOP_NORM_ACT || d.op == DYF_TOP_LAYERNORM || d.op == DYF_TOP_ATTENTION || d.op == DYF_TOP_DROPOUT;
+    const bool has_p = d.op == DYF_TOP_GN_ACT || d.op == DYF_TOP_NORM_ACT || d.op == DYF_TOP_LAYERNORM || d.op == DYF_TOP_ATTENTION || d.op == DYF_TOP_DROPOUT ||
+                       d.op == DYF_TOP_ATTENTION_STREAM;
     const bool has_c2 = d.op == DYF_TOP_CONV || d.op == DYF_TOP_LINEAR || d.op == DYF_TOP_CAT || d.op == DYF_TOP_CONVT;
     const int flags_ok = d.op == DYF_TOP_CONV ? (DYF_TOP_WS | DYF_TOP_BIAS) : d.op == DYF_TOP_GN_ACT ? DYF_TOP_FILM : d.op == DYF_TOP_LINEAR ? DYF_TOP_PRE
                          : d.op == DYF_TOP_ADD ? DYF_TOP_SAME
                          : d.op == DYF_TOP_NORM_ACT ? (DYF_TOP_FILM | DYF_TOP_RUNNING | DYF_TOP_MASK | DYF_TOP_LEAKY | DYF_TOP_RELU)
                          : d.op == DYF_TOP_UP2_BILINEAR ? DYF_TOP_GRAD_IN : d.op == DYF_TOP_RESIZE ? DYF_TOP_NEAREST : 0;
-    if (d.op < DYF_TOP_CONV || d.op > DYF_TOP_CONVT) return refuse(DYF_ERR_INVALID_ARGUMENT, "unknown op");
+    if (d.op < DYF_TOP_CONV || d.op > DYF_TOP_ATTENTION_STREAM) return refuse(DYF_ERR_INVALID_ARGUMENT, "unknown op");
     if (d.flags & ~flags_ok) return refuse(DYF_ERR_INVALID_ARGUMENT, "a flag this op does not take");
     if (d.p > 0.0f && !has_p) return refuse(DYF_ERR_INVALID_ARGUMENT, "this op has no dropout");
     if (d.op == DYF_TOP_UP2_BILINEAR ? d.c2 < 0 : has_c2 ? d.c2 < 1 : d.c2 != 0)
@@ -1711,11 +1975,13 @@ dyf_status f32_op_train(dyf_engine* e, const dyf_train_op* dp, const float* cons
     if ((d.flags & DYF_TOP_GRAD_IN) && (d.c2 < 1 || !dinputs || !dinputs[1])) return refuse(DYF_ERR_INVALID_ARGUMENT, "up2_bilinear: a gradient to start from needs the second source and its gradient buffer");
     if ((d.op == DYF_TOP_LINEAR || d.op == DYF_TOP_LEARNED_SINU) && (d.h != 1 || d.w != 1)) return refuse(DYF_ERR_INVALID_ARGUMENT, "linear / learned_sinu take rows: h = w = 1");
     const long long hw = (long long)d.h * d.w, px = hw * d.nb;
-    const long long cmax = std::max<long long>(d.c + d.c2, (d.op == DYF_TOP_LINATTN || d.op == DYF_TOP_ATTENTION) ? 3 * RHID : 0);
+    const bool attn_core = d.op == DYF_TOP_LINATTN || d.op == DYF_TOP_ATTENTION || d.op == DYF_TOP_ATTENTION_STREAM;
+    const long long cmax = std::max<long long>(d.c + d.c2, attn_core ? 3 * RHID : 0);
     const long long ohw = d.op == DYF_TOP_RESIZE ? (long long)d.k * d.stride : hw;  // the larger plane of the op (x2 upsamples: the 4 below)
     if (std::max(hw, ohw) * cmax * 4 >= (1ll << 32) || std::max(hw, ohw) * d.nb * cmax * 4 >= (1ll << 31)) return refuse(DYF_ERR_UNSUPPORTED, "tensor too large for the op seam (2^31 elements)");
-    if ((d.op == DYF_TOP_LINATTN || d.op == DYF_TOP_ATTENTION) && d.c != 3 * RHID) return refuse(DYF_ERR_INVALID_ARGUMENT, "the attention cores take qkv of 384 channels");
+    if (attn_core && d.c != 3 * RHID) return refuse(DYF_ERR_INVALID_ARGUMENT, "the attention cores take qkv of 384 channels");
     if (d.op == DYF_TOP_ATTENTION && hw > AT_KEEP_P_MAX) return refuse(DYF_ERR_UNSUPPORTED, "the Attention core keeps its (tokens x tokens) probabilities -- at most 4096 tokens");
+    if (d.op == DYF_TOP_ATTENTION_STREAM && hw > AT_STREAM_MAX) return refuse(DYF_ERR_UNSUPPORTED, "the streaming Attention core indexes its (4 x tokens x tokens) probabilities with 32 bits -- at most 32767 tokens");
     if (d.p > 0.0f && d.nb > 2 * e->cfg.max_batch) return refuse(DYF_ERR_INVALID_ARGUMENT, "more rows than the engine's row-key table (2 max_batch)");
 
     // inputs (floats each) and parameters (name, PyTorch shape) of the op
@@ -1826,6 +2092,7 @@ dyf_status f32_op_train(dyf_engine* e, const dyf_train_op* dp, const float* cons
     case DYF_TOP_LAYERNORM: y = X.layernorm(in[0], (int)hw, d.c, "op.norm.g", d.p); break;
     case DYF_TOP_LINATTN: y = X.linattn(in[0], (int)hw); break;
     case DYF_TOP_ATTENTION: y = X.attention(in[0], (int)hw, d.p); break;
+    case DYF_TOP_ATTENTION_STREAM: y = X.attention(in[0], (int)hw, d.p, true); break;
     case DYF_TOP_LINEAR: y = X.linear(in[0], d.nb, d.c, d.c2, "op", (d.flags & DYF_TOP_PRE) ? 1 : 0); break;
     case DYF_TOP_LEARNED_SINU: y = X.learned_sinu(inputs[0], d.c); break;
     case DYF_TOP_DROPOUT: y = X.dropout(in[0], hw * d.c, d.p); break;

@@ -710,7 +710,8 @@ class HipEngine:
         mask (nb, h, w, c) instead of the generator -- forward only, "dinputs" is None), "up2_bilinear" (one source, or two standing for
         their concatenation; `skip_grad`: the gradient the second source already has), "resize" (`size` = (oh, ow), which travels in the
         descriptor's k and stride fields; `nearest`), "convt"
-        (ConvTranspose2d(c, c2, 4, 2, 1): weight (c, c2, 4, 4), bias)."""
+        (ConvTranspose2d(c, c2, 4, 2, 1): weight (c, c2, 4, 4), bias).
+        "attention_stream": "attention" in the streaming form a recorded forward takes past 4096 tokens, at any h * w <= 32 767."""
         ins = [_f32c(t, "input") for t in inputs]
         x = ins[0]
         nb = x.shape[0]
@@ -732,7 +733,7 @@ class HipEngine:
         elif op == "gn_act":
             flags = L.TOP_FILM if len(ins) > 1 else 0
             out_shape = tuple(x.shape)
-        elif op in ("linattn", "attention"):
+        elif op in ("linattn", "attention", "attention_stream"):
             out_shape = (nb, h, w, 128)
         elif op == "linear":
             c2, flags = ps[0].shape[0], (L.TOP_PRE if pre else 0)
@@ -782,7 +783,7 @@ class HipEngine:
         for t, sh in zip(ps, pshape):
             if t.numel() != int(np.prod(sh)):
                 raise ValueError(f"{op}: a parameter has shape {tuple(t.shape)}, expected {sh}")
-        if (op in ("linattn", "attention")) and c != 384:
+        if (op in ("linattn", "attention", "attention_stream")) and c != 384:
             raise ValueError("the attention cores take qkv of 384 channels")
         dout = _f32c(dout, "dout")
         if tuple(dout.shape) != out_shape:  # the C ABI reads / writes raw pointers

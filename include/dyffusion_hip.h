@@ -214,8 +214,8 @@ int32_t dyf_row_groups(const dyf_engine* engine);
  * use_graph like the 16-bit one.  Both builds of the library implement it alike; it does not depend on dyf_engine_config.dtype.
  * unet.Unet: up to 4096 bottleneck tokens the fp32 Attention core is the training step's (it writes its probabilities into the arena),
  * beyond that a streaming matrix-core kernel that writes nothing of size tokens^2 (the 512^2 configuration: 16 384 tokens); more than
- * 32 767 tokens (4 tokens^2 probabilities per row no longer indexed by 32 bits): DYF_ERR_UNSUPPORTED.  The training step keeps its own
- * limit of 4096 tokens.  Any other value of bits: DYF_ERR_INVALID_ARGUMENT.
+ * 32 767 tokens (4 tokens^2 probabilities per row no longer indexed by 32 bits): DYF_ERR_UNSUPPORTED.  The training step has the same
+ * bound (dyf_train_forward).  Any other value of bits: DYF_ERR_INVALID_ARGUMENT.
  *   - the plan walker is the 16-bit one (sampler state, cold-sampling update, noisy condition, forecast stack, log, dyf_get_sampler_state,
  *     dyf_plan_forward_counts are shared); in fp32 there is no paired interpolator forward, no batched refinement and no row groups
  *     (dyf_set_row_groups stays accepted, a call behaves as with one group).  Forward order, and so the order of the generator's forward
@@ -273,7 +273,10 @@ dyf_status dyf_get_sampler_state(dyf_engine* engine, int32_t what, float* out_de
  * when dinputs_dev != NULL, w.r.t. its `inputs` (NB,in_channels,H,W) -- the frozen interpolator is differentiated through.
  * flags: DYF_TRAIN_BATCH_STATS = BatchNorm with batch statistics (+ running-statistics update, momentum 0.1; module.train()),
  * otherwise running statistics (frozen / eval network); DYF_TRAIN_DROPOUT = Dropout layers active (engine generator, same
- * streams as sampling; the backward re-derives the masks).  All arithmetic fp32. */
+ * streams as sampling; the backward re-derives the masks).  All arithmetic fp32.
+ * unet.Unet: up to 4096 bottleneck tokens the Attention keeps its (tokens x tokens) probabilities for the backward; beyond that the
+ * forward keeps the softmax statistics (max, 1 / sum) per (row, head, token) and the backward recomputes the scores tile by tile (nothing of size tokens^2 is
+ * written; gradients are bitwise repeatable); more than 32 767 tokens: DYF_ERR_UNSUPPORTED, as in fp32 sampling. */
 #define DYF_TRAIN_BATCH_STATS 1
 #define DYF_TRAIN_DROPOUT 2
 dyf_status dyf_train_forward(dyf_engine* engine, int32_t net, int32_t slot, const float* inputs_dev, const float* time_dev,

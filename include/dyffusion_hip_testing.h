@@ -141,6 +141,8 @@ dyf_status dyf_train_conv_check(dyf_engine* engine, int32_t kind, int32_t n, int
  *   LAYERNORM   x (nb,hw,c); g (1,c,1,1); dropout p
  *   LINATTN     qkv (nb,hw,384) -> (nb,hw,128)
  *   ATTENTION   qkv (nb,hw,384) -> (nb,hw,128), the form that keeps its probabilities (hw <= 4096); dropout p on the probabilities
+ *   ATTENTION_STREAM the same op, always in the streaming form a recorded forward takes past 4096 tokens (t_at_stream_fwd keeping the
+ *               softmax statistics, t_at_stream_bwd_dq / _dkv recomputing the scores per tile), at any hw <= 32 767; dropout p
  *   LINEAR      x (nb,c); weight (c2,c), bias (c2) -> (nb,c2); DYF_TOP_PRE = SiLU on the input first
  *   LEARNED_SINU time (nb); weights (c) -> (nb, 2c + 1)
  *   DROPOUT     x (nb,h,w,c); p          GELU  x (nb,h,w,c)
@@ -163,7 +165,7 @@ dyf_status dyf_train_conv_check(dyf_engine* engine, int32_t kind, int32_t n, int
 typedef enum dyf_train_op_kind {
     DYF_TOP_CONV = 0, DYF_TOP_GN_ACT = 1, DYF_TOP_LAYERNORM = 2, DYF_TOP_LINATTN = 3, DYF_TOP_ATTENTION = 4, DYF_TOP_LINEAR = 5,
     DYF_TOP_LEARNED_SINU = 6, DYF_TOP_DROPOUT = 7, DYF_TOP_GELU = 8, DYF_TOP_ADD = 9, DYF_TOP_CAT = 10, DYF_TOP_UP2_NEAREST = 11,
-    DYF_TOP_NORM_ACT = 12, DYF_TOP_UP2_BILINEAR = 13, DYF_TOP_RESIZE = 14, DYF_TOP_CONVT = 15
+    DYF_TOP_NORM_ACT = 12, DYF_TOP_UP2_BILINEAR = 13, DYF_TOP_RESIZE = 14, DYF_TOP_CONVT = 15, DYF_TOP_ATTENTION_STREAM = 16
 } dyf_train_op_kind;
 #define DYF_TOP_WS 1
 #define DYF_TOP_BIAS 2

@@ -3,7 +3,14 @@
 --fp32: the fp32 core of fp32 sampling instead (dyf_op_attention_f32), no dropout: form 0 (keeps its probabilities, <= 4096 tokens)
 against form 1 (streaming, matrix cores), interleaved in one process; medians of the per-call times (form 0's call also allocates
 its scratch probabilities: the seam's hipMalloc sits between the two events).
-usage: python tools/bench_attention.py --fp32 [NB] [tokens]"""
+usage: python tools/bench_attention.py --fp32 [NB] [tokens]
+--fp32-train: the recorded fp32 Attention of the training step, forward + backward through the one-op seam (dyf_op_train_f32):
+"attention" (keeps its probabilities: t_at_fwd + t_at_bwd_row / _col) against "attention_stream" (t_at_stream_fwd keeping the softmax statistics +
+t_at_stream_bwd_dq / _dkv), interleaved in one process, medians, at N = 1024 and 4096 for NB = 1 and 4, and "attention_stream" alone at
+N = 16 384, NB = 1; and the device memory the engine holds after one call of each form (hipMemGetInfo around a fresh engine: its caching
+pool's high-water mark).  These are SEAM WALL TIMES: they include the seam's allocations, copies and synchronisation, so they compare the
+two forms with each other and nothing else.
+usage: python tools/bench_attention.py --fp32-train"""
 import os
 import sys
 
@@ -18,11 +25,56 @@ import dyffusion_amd as D  # noqa: E402
 from dyffusion_amd.engine import net_config  # noqa: E402
 
 fp32 = "--fp32" in sys.argv
-sys.argv = [a for a in sys.argv if a != "--fp32"]
+fp32_train = "--fp32-train" in sys.argv
+sys.argv = [a for a in sys.argv if a not in ("--fp32", "--fp32-train")]
 nb = int(sys.argv[1]) if len(sys.argv) > 1 else 4
 n = int(sys.argv[2]) if len(sys.argv) > 2 else 16384
 cfg = net_config(in_channels=3, cond_channels=2, out_channels=3, dim=64, with_time_emb=True, upsample_dims=(64, 64), dropout=0.0)
 p = float(sys.argv[3]) if len(sys.argv) > 3 else 0.1
+if fp32_train:
+    import statistics
+    import time
+
+    def used_mib():
+        free, total = torch.cuda.mem_get_info()
+        return (total - free) / 2 ** 20
+
+    def engine(rows):
+        e = D.HipEngine(cfg, cfg, 23, 11, max_batch=rows, use_graph=False)
+        e.train_set_precision(32)
+        return e
+
+    print("seam wall times (allocation, copies and synchronisation of the op seam included): comparable between the two forms only")
+    for tokens, rows in ((1024, 1), (1024, 4), (4096, 1), (4096, 4), (16384, 1)):
+        ops = ["attention_stream"] if tokens > 4096 else ["attention", "attention_stream"]
+        gq = torch.Generator().manual_seed(tokens + rows)
+        q = (torch.randn(rows, 1, tokens, 384, generator=gq) * 1.5).cuda()
+        dy = torch.randn(rows, 1, tokens, 128, generator=gq).cuda()
+        mem = {}
+        for op in ops:  # a fresh engine per form: what its pool holds after one call
+            torch.cuda.synchronize()
+            base = used_mib()
+            e = engine(rows)
+            at_rest = used_mib()
+            e.op_train(op, [q], [], dy)
+            mem[op] = (used_mib() - at_rest, at_rest - base)
+            e.close()
+        e = engine(rows)
+        for op in ops * 2:
+            e.op_train(op, [q], [], dy)
+        times = {op: [] for op in ops}
+        for _ in range(3 if tokens > 4096 else 7):
+            for op in ops:
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                e.op_train(op, [q], [], dy)
+                torch.cuda.synchronize()
+                times[op].append((time.perf_counter() - t0) * 1e3)
+        e.close()
+        for op in ops:
+            print(f"fp32 training {op:16s} NB={rows}, {tokens:5d} tokens: forward + backward median {statistics.median(times[op]):9.3f} ms "
+                  f"(min {min(times[op]):.3f}, max {max(times[op]):.3f}); engine pool after one call {mem[op][0]:8.1f} MiB")
+    sys.exit(0)
 eng = D.HipEngine(cfg, cfg, 23, 11, max_batch=max(1, nb), use_graph=False)
 g = torch.Generator().manual_seed(0)
 qkv = torch.randn(nb, n, 384, generator=g).to(eng.torch_dtype).cuda()
