@@ -96,6 +96,15 @@ TRAIN_OPS = {"conv": 0, "gn_act": 1, "layernorm": 2, "linattn": 3, "attention": 
 TOP_WS, TOP_BIAS, TOP_PRE, TOP_FILM, TOP_SAME = 1, 2, 4, 8, 16
 TOP_RUNNING, TOP_MASK, TOP_LEAKY, TOP_RELU, TOP_NEAREST, TOP_GRAD_IN = 32, 64, 128, 256, 512, 1024
 
+
+class OptimConfig(C.Structure):
+    """dyf_optim_config (include/dyffusion_hip.h): the engine-resident AdamW / EMA step."""
+    _fields_ = [("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double), ("weight_decay", C.c_double),
+                ("max_grad_norm", C.c_double), ("ema", C.c_int32)]
+
+
+OPTIM_WEIGHT, OPTIM_GRAD, OPTIM_EXP_AVG, OPTIM_EXP_AVG_SQ, OPTIM_EMA, OPTIM_WEIGHT_FWD = range(6)
+
 # every symbol include/dyffusion_hip.h and include/dyffusion_hip_testing.h declare: (name, restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = [
@@ -153,6 +162,15 @@ SYMBOLS = [
     ("dyf_set_sample_precision", C.c_int, [_P, C.c_int32]),
     ("dyf_sample_precision", C.c_int32, [_P]),
     ("dyf_train_export", C.c_int, [_P, C.c_int32, C.c_int32, C.POINTER(C.c_char_p), C.POINTER(_P)]),
+    ("dyf_optim_create", C.c_int, [_P, C.c_int32, C.POINTER(OptimConfig)]),
+    ("dyf_optim_destroy", C.c_int, [_P, C.c_int32]),
+    ("dyf_optim_step", C.c_int, [_P, C.c_int32, C.c_double, C.c_double, _P]),
+    ("dyf_optim_last", C.c_int, [_P, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int32)]),
+    ("dyf_optim_get_step", C.c_int, [_P, C.c_int32, C.POINTER(C.c_int64)]),
+    ("dyf_optim_set_step", C.c_int, [_P, C.c_int32, C.c_int64]),
+    ("dyf_optim_export", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_char_p), C.POINTER(_P), C.c_int32]),
+    ("dyf_optim_import", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_char_p), C.POINTER(_P), C.c_int32]),
+    ("dyf_optim_swap_ema", C.c_int, [_P, C.c_int32, _P]),
     ("dyf_criterion_grad", C.c_int, [_P, _P, _P, C.c_int64, C.c_int32, C.c_float, _P, _P]),
     ("dyf_train_conv_check", C.c_int, [_P] + [C.c_int32] * 9 + [C.c_uint32, C.POINTER(C.c_float)]),
     ("dyf_apply_boundary_conditions", C.c_int, [_P, C.POINTER(BcArgs), _P, _P]),

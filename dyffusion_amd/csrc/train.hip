@@ -1393,10 +1393,13 @@ struct FwdMem {
 
 namespace dyf {
 
+TrainNet* train_net(dyf_engine* e, int which) { return e && e->train ? e->train->net[which] : nullptr; }
+
 void train_destroy(dyf_engine* e) {
     if (!e->train) return;
     for (TrainNet*& n : e->train->net)
         if (n) {
+            optim_destroy(*n);
             tfree(e, n->owned);
             delete n;
             n = nullptr;
@@ -1560,13 +1563,14 @@ dyf_status dyf_criterion_grad(dyf_engine* e, const float* pred_dev, const float*
 }
 
 // [co][ci][taps] (PyTorch conv weight) -> w [co][tap][ci] and wt [tap][ci][co], on the device
+// (wt null: a buffer that has only the first layout -- a gradient, an optimizer moment, the EMA shadow)
 __global__ void t_repack_conv(const float* raw, int cout, int cin, int taps, float* w, float* wt) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (long long)cout * cin * taps) return;
     const int tp = (int)(i % taps), ci = (int)((i / taps) % cin), co = (int)(i / ((long long)taps * cin));
     const float v = raw[i];
     w[((size_t)co * taps + tp) * cin + ci] = v;
-    wt[((size_t)tp * cin + ci) * cout + co] = v;
+    if (wt) wt[((size_t)tp * cin + ci) * cout + co] = v;
 }
 
 // Refresh ONLY the training copy of a network's parameters (fp32, both conv layouts) -- what a training loop needs after every
@@ -1640,6 +1644,83 @@ static dyf_status train_load_weights_impl(dyf_engine* e, int32_t which, int32_t 
     tfree(e, tmp);
     if (!ok) return fail(e, DYF_ERR_HIP, "dyf_train_load_weights: upload failed");
     return DYF_OK;
+}
+
+// [tap][ci][co] (the forward-layout copy of a conv weight) -> [co][ci][taps] (PyTorch)
+__global__ void t_unpack_conv_fwd(const float* wt, int cout, int cin, int taps, float* out) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (long long)cout * cin * taps) return;
+    const int tp = (int)(i % taps), ci = (int)((i / taps) % cin), co = (int)(i / ((long long)taps * cin));
+    out[i] = wt[((size_t)tp * cin + ci) * cout + co];
+}
+
+// ---- engine-resident optimizer (train_optim.hip): its tensors by state_dict name in PyTorch layouts.  The layout conversions are the
+// training copy's own: rn_export_param on the way out, t_repack_conv on the way in.
+// the buffer of `kind` that belongs to parameter p, in p's training layout (null: that kind does not exist for it)
+static float* optim_buffer(const TrainNet& t, const RParam& p, int kind) {
+    if (kind == DYF_OPTIM_WEIGHT) return p.w;
+    if (kind == DYF_OPTIM_WEIGHT_FWD) return p.conv ? p.wt : nullptr;
+    if (p.stat || !p.g) return nullptr;
+    if (kind == DYF_OPTIM_GRAD) return p.g;
+    const TrainOptim* o = t.optim;
+    const size_t off = (size_t)(p.g - t.g_arena);
+    if (!o) return nullptr;
+    return kind == DYF_OPTIM_EXP_AVG ? o->m + off : kind == DYF_OPTIM_EXP_AVG_SQ ? o->v + off : (kind == DYF_OPTIM_EMA && o->shadow) ? o->shadow + off : nullptr;
+}
+static dyf_status optim_transfer(dyf_engine* e, int32_t which, int32_t kind, int32_t n_tensors, const char* const* names, float* const* out,
+                                 const float* const* in, bool dev) {
+    if (!e || which < 0 || which > 1 || kind < DYF_OPTIM_WEIGHT || kind > DYF_OPTIM_WEIGHT_FWD || (kind == DYF_OPTIM_WEIGHT_FWD && !out) || n_tensors < 0 || !names || (!out && !in))
+        return fail(e, DYF_ERR_INVALID_ARGUMENT, "dyf_optim_export / dyf_optim_import: bad arguments");
+    TK(hipSetDevice(e->cfg.device));
+    TrainNet* t = train_net(e, which);
+    if (!t || !t->ready) return fail(e, DYF_ERR_STATE, "training needs arch unet_simple / unet with loaded weights");
+    if (kind >= DYF_OPTIM_EXP_AVG && kind <= DYF_OPTIM_EMA && !t->optim) return fail(e, DYF_ERR_STATE, "no optimizer for this network (dyf_optim_create)");
+    size_t stage_n = 0;
+    for (int i = 0; i < n_tensors; ++i) {
+        auto it = t->P.find(names[i]);
+        if (it == t->P.end() || !optim_buffer(*t, it->second, kind) || !(out ? (const void*)out[i] : (const void*)in[i]))
+            return fail(e, DYF_ERR_INVALID_ARGUMENT, std::string("dyf_optim_export / dyf_optim_import: no such tensor of this kind: '") + names[i] + "'");
+        if (it->second.conv && !dev) stage_n = std::max(stage_n, it->second.n);
+    }
+    TK(hipDeviceSynchronize());
+    std::vector<void*> tmp;
+    float* stage = nullptr;
+    if (stage_n) {
+        dyf_status s = talloc(e, tmp, &stage, stage_n, false, true);
+        if (s != DYF_OK) return s;
+    }
+    dyf_status s = DYF_OK;
+    for (int i = 0; i < n_tensors && s == DYF_OK; ++i) {
+        const RParam& p = t->P.at(names[i]);
+        float* buf = optim_buffer(*t, p, kind);
+        if (out && kind == DYF_OPTIM_WEIGHT_FWD) {
+            hipLaunchKernelGGL(t_unpack_conv_fwd, dim3(nblk((long long)p.n)), dim3(256), 0, nullptr, buf, p.cout, p.cin, p.taps, dev ? out[i] : stage);
+            if (!dev && (hipDeviceSynchronize() != hipSuccess || hipMemcpy(out[i], stage, p.n * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)) s = DYF_ERR_HIP;
+        } else if (out) {
+            s = rn_export_param(e, stage, p, out[i], dev, buf);
+        } else if (!p.conv) {
+            if (hipMemcpy(buf, in[i], p.n * sizeof(float), dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice) != hipSuccess) s = DYF_ERR_HIP;
+        } else {
+            if (!dev && hipMemcpy(stage, in[i], p.n * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) s = DYF_ERR_HIP;
+            hipLaunchKernelGGL(t_repack_conv, dim3(nblk((long long)p.n)), dim3(256), 0, nullptr, dev ? in[i] : stage, p.cout, p.cin, p.taps, buf,
+                               kind == DYF_OPTIM_WEIGHT ? p.wt : nullptr);
+            if ((dev ? hipGetLastError() : hipDeviceSynchronize()) != hipSuccess) s = DYF_ERR_HIP;  // (the staging buffer is reused)
+        }
+    }
+    const hipError_t se = hipDeviceSynchronize();
+    tfree(e, tmp);
+    if (s == DYF_ERR_HIP || (s == DYF_OK && se != hipSuccess)) return fail(e, DYF_ERR_HIP, "dyf_optim_export / dyf_optim_import: a copy failed");
+    return s;
+}
+dyf_status dyf_optim_export(dyf_engine* e, int32_t which, int32_t kind, int32_t n_tensors, const char* const* names, float* const* out,
+                            int32_t on_device) {
+    if (!out) return fail(e, DYF_ERR_INVALID_ARGUMENT, "dyf_optim_export: bad arguments");
+    return optim_transfer(e, which, kind, n_tensors, names, out, nullptr, on_device != 0);
+}
+dyf_status dyf_optim_import(dyf_engine* e, int32_t which, int32_t kind, int32_t n_tensors, const char* const* names, const float* const* data,
+                            int32_t on_device) {
+    if (!data) return fail(e, DYF_ERR_INVALID_ARGUMENT, "dyf_optim_import: bad arguments");
+    return optim_transfer(e, which, kind, n_tensors, names, nullptr, data, on_device != 0);
 }
 
 // Test seam (include/dyffusion_hip_testing.h): one training convolution on hash-random fp32 data through the fp32 matrix-core

@@ -50,7 +50,73 @@ static inline bool train_raise_dynamic_lds(int bytes) {
     return st == 1;
 }
 
+#include <map>
+#include <string>
+#include <vector>
+
+#include "../../include/dyffusion_hip.h"  // dyf_status, dyf_engine
+
 namespace dyf {
+
+struct RParam {              // one parameter in its training layout, and its gradient (same layout)
+    float* w = nullptr;      // conv: [cout][tap][cin]; Linear: [out][in]; vectors as stored
+    float* wt = nullptr;     // every conv: [tap][cin][cout] (forward layout; a weight-standardised conv derives its own pair per use)
+    float* g = nullptr;
+    size_t n = 0;
+    int conv = 0, cout = 0, cin = 0, taps = 0;   // conv: any 4-d weight as (cout, cin, kh, kw) -- a ConvTranspose2d (dim, C, 4, 4) is [dim][tap][C]
+    bool stat = false;       // a BatchNorm running statistic: no gradient; what leaves by its name is the (updated) statistic itself
+};
+
+struct TrainOptim;  // engine-resident AdamW / EMA state of one network (train_optim.hip)
+
+struct TrainNet {
+    std::map<std::string, RParam> P;
+    std::vector<void*> owned;
+    float* g_arena = nullptr;     // every parameter's gradient buffer is a 256-byte-aligned slice of ONE block: zeroing the gradients is
+    size_t g_arena_floats = 0;    // one memset instead of one per parameter (~270 per network and step)
+    bool ready = false;
+    TrainOptim* optim = nullptr;  // dyf_optim_create; survives a reload of the weights (optim_rebind), destroyed with the engine
+};
+
+// ---- engine-resident optimizer (train_optim.hip)
+// One entry of the update kernel's chunk table: OPT_CHUNK consecutive elements (fewer at a tensor's end) of ONE parameter.
+struct OptChunk {
+    float* w;            // the parameter's master weights (training layout)
+    float* wt;           // its [tap][cin][cout] copy, or null
+    long long off;       // offset of the parameter's slice in g_arena -- and in the m, v and shadow arenas, which share its offsets
+    int begin, count;    // the chunk's element range inside the parameter
+    int cout, rest;      // wt: element i of w is wt[(i % rest) * cout + i / rest], rest = taps * cin
+};
+constexpr int OPT_CHUNK = 4096;        // elements per chunk: 16 KB of each of w, g, m, v, shadow
+constexpr int OPT_MAX_PARTIALS = 1024; // workgroups of the sum-of-squares launch = partial sums the update launch re-reduces
+
+struct OptStatus {       // what a step leaves for the host: written by workgroup 0 of the update launch
+    double grad_norm;
+    int skipped, pad;
+};
+
+struct TrainOptim {
+    double beta1 = 0.9, beta2 = 0.999, eps = 1e-8, weight_decay = 0.0, max_grad_norm = 0.0;  // doubles, as torch.optim holds them
+    bool ema = false;
+    size_t floats = 0;               // = TrainNet::g_arena_floats the arenas below were sized for
+    uint64_t layout = 0;             // hash of every parameter's (name, arena offset, n): the state belongs to exactly this layout
+    float *m = nullptr, *v = nullptr, *shadow = nullptr;   // one block: [m | v | shadow]
+    OptChunk* chunks = nullptr;      // device
+    int n_chunks = 0;
+    double* partials = nullptr;      // device [OPT_MAX_PARTIALS]
+    OptStatus* status_dev = nullptr;
+    OptStatus* status_host = nullptr;  // pinned: copied behind every step, read when the host next needs the outcome
+    hipEvent_t status_ready = nullptr;
+    bool pending = false;            // a step was launched whose outcome (skipped or not) the host has not read yet
+    long long steps = 0;             // applied steps the host knows of (torch's state["step"])
+    double last_norm = 0.0;
+    int last_skipped = 0;
+};
+
+void optim_destroy(TrainNet& t);                      // frees everything; t.optim = nullptr
+dyf_status optim_rebind(dyf_engine* e, TrainNet& t);   // after the parameter copy was rebuilt: new chunk table over the new pointers
+dyf_status optim_resolve(dyf_engine* e, TrainOptim& o);  // waits for the pending step's status and books it
+TrainNet* train_net(dyf_engine* e, int which);         // train.hip: the network's training copy, or null
 
 struct TConv {  // geometry of one nn.Conv2d on NHWC fp32 tensors: x (n, h, w, cin) -> y (n, ho, wo, cout), k x k / stride s / pad p
     int n, h, w, cin, ho, wo, cout, k, s, p;

@@ -21,22 +21,7 @@
 
 namespace dyf {
 
-struct RParam {              // one parameter in its training layout, and its gradient (same layout)
-    float* w = nullptr;      // conv: [cout][tap][cin]; Linear: [out][in]; vectors as stored
-    float* wt = nullptr;     // convs that are NOT weight-standardised: [tap][cin][cout] (forward layout)
-    float* g = nullptr;
-    size_t n = 0;
-    int conv = 0, cout = 0, cin = 0, taps = 0;   // conv: any 4-d weight as (cout, cin, kh, kw) -- a ConvTranspose2d (dim, C, 4, 4) is [dim][tap][C]
-    bool stat = false;       // a BatchNorm running statistic: no gradient; what leaves by its name is the (updated) statistic itself
-};
-
-struct TrainNet {
-    std::map<std::string, RParam> P;
-    std::vector<void*> owned;
-    float* g_arena = nullptr;     // every parameter's gradient buffer is a 256-byte-aligned slice of ONE block: zeroing the gradients is
-    size_t g_arena_floats = 0;    // one memset instead of one per parameter (~270 per network and step)
-    bool ready = false;
-};
+// RParam / TrainNet (one parameter in its training layout; the parameters and gradients of one network): train_internal.h
 
 struct RT {                  // an activation of the recorded forward and (during the backward) its gradient
     float* p = nullptr;
@@ -1752,10 +1737,22 @@ dyf_status train_store_params(dyf_engine* e, int which, std::map<std::string, Te
     if (!e->train->net[which]) e->train->net[which] = new TrainNet();
     TrainNet& t = *e->train->net[which];
     TK(hipDeviceSynchronize());
+    // an engine-resident optimizer keeps its state across a reload of the same network (the sampling copy is refreshed through here after
+    // optimizer steps): the gradients accumulated so far move to the new arena, the chunk table is rebuilt over the new pointers
+    float* keep_g = nullptr;
+    const size_t keep_n = t.optim && t.ready ? t.g_arena_floats : 0;
+    if (keep_n) {
+        TK(hipMalloc(&keep_g, keep_n * sizeof(float)));
+        TK(hipMemcpy(keep_g, t.g_arena, keep_n * sizeof(float), hipMemcpyDeviceToDevice));
+    }
     tfree(e, t.owned);
     t.P.clear();
     t.ready = false;
     dyf_status s = rn_fill_params(e, t, sd);
+    if (s == DYF_OK) s = optim_rebind(e, t);
+    if (s == DYF_OK && keep_g && t.optim && hipMemcpy(t.g_arena, keep_g, keep_n * sizeof(float), hipMemcpyDeviceToDevice) != hipSuccess)
+        s = fail(e, DYF_ERR_HIP, "dyf_load_weights: moving the accumulated gradients failed");
+    if (keep_g) (void)hipFree(keep_g);
     if (s != DYF_OK) return s;
     TK(hipDeviceSynchronize());
     t.ready = true;
@@ -1905,10 +1902,11 @@ dyf_status train_backward(dyf_engine* e, int slot, const float* dout_dev, float*
 // -- a BatchNorm running statistic -- the statistic as the recorded forwards updated it
 // (stage: p.n floats of device scratch for the unpacked copy of a conv weight on its way to the host; the copy below is synchronous, so one
 // block serves a whole export)
-static dyf_status rn_export_param(dyf_engine* e, float* stage, const RParam& p, float* out, bool dev) {
-    const float* src = p.stat ? p.w : p.g;
+// (from: another buffer in the parameter's training layout -- its weights, or its slice of an optimizer arena; dyf_optim_export)
+static dyf_status rn_export_param(dyf_engine* e, float* stage, const RParam& p, float* out, bool dev, const float* from = nullptr) {
+    const float* src = from ? from : p.stat ? p.w : p.g;
     if (p.conv) {
-        hipLaunchKernelGGL(t_unpack_conv, dim3(nblk((long long)p.n)), dim3(256), 0, 0, p.g, p.cout, p.cin, p.taps, dev ? out : stage);
+        hipLaunchKernelGGL(t_unpack_conv, dim3(nblk((long long)p.n)), dim3(256), 0, 0, src, p.cout, p.cin, p.taps, dev ? out : stage);
         src = stage;
         if (dev) return DYF_OK;
     }

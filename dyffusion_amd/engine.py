@@ -131,6 +131,7 @@ class HipEngine:
         self.train_step_id = 0    # bumped by every p_losses / get_loss training forward: a loss of an older step cannot run backward
         self.plan_valid = False   # cleared by load_weights: the plan's FiLM tables are functions of the weights
         self.weights_version = 0
+        self._before_close = []   # callbacks run by close() while the engine is still alive (optim.EngineAdamW)
 
     # ------------------------------------------------------------------ plumbing
     def _check(self, st: int):
@@ -169,8 +170,12 @@ class HipEngine:
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
-            self._lib.dyf_engine_destroy(self._h)
-            self._h = C.c_void_p()
+            try:
+                for cb in list(getattr(self, "_before_close", ())):  # an EngineAdamW moves its resident state to the host first
+                    cb(self)
+            finally:  # whatever a callback raised, the engine goes
+                self._lib.dyf_engine_destroy(self._h)
+                self._h = C.c_void_p()
 
     def __del__(self):
         try:
@@ -630,6 +635,74 @@ class HipEngine:
         self._check(self._lib.dyf_train_export(self._h, net, len(names), cn, cp))
         return {k: torch.from_numpy(b) for k, b in zip(names, bufs)}
 
+    # ------------------------------------------------------------------ engine-resident optimizer (csrc/train_optim.hip)
+    def optim_create(self, net: int, *, beta1: float, beta2: float, eps: float, weight_decay: float, max_grad_norm: float, ema: bool):
+        """dyf_optim_create: AdamW state (zero) and, with `ema`, a shadow copy of the current weights for network `net`."""
+        cfg = L.OptimConfig(float(beta1), float(beta2), float(eps), float(weight_decay), float(max_grad_norm), int(bool(ema)))
+        self._check(self._lib.dyf_optim_create(self._h, net, C.byref(cfg)))
+
+    def optim_destroy(self, net: int):
+        self._check(self._lib.dyf_optim_destroy(self._h, net))
+
+    def optim_step(self, net: int, lr: float, ema_decay_now: float = 0.0):
+        """dyf_optim_step: two launches on the current stream.  Nothing launched here is waited for; the call first reads the
+        PREVIOUS step's outcome (its status copy was queued behind that step), so the host runs at most one step ahead."""
+        self._check(self._lib.dyf_optim_step(self._h, net, float(lr), float(ema_decay_now), self._stream()))
+
+    def optim_last(self, net: int):
+        """(gradient norm before clipping, skipped) of the most recent step; waits for that step."""
+        norm, skipped = C.c_double(0.0), C.c_int32(0)
+        self._check(self._lib.dyf_optim_last(self._h, net, C.byref(norm), C.byref(skipped)))
+        return norm.value, bool(skipped.value)
+
+    def optim_get_step(self, net: int) -> int:
+        n = C.c_int64(0)
+        self._check(self._lib.dyf_optim_get_step(self._h, net, C.byref(n)))
+        return int(n.value)
+
+    def optim_set_step(self, net: int, step: int):
+        self._check(self._lib.dyf_optim_set_step(self._h, net, C.c_int64(int(step))))
+
+    def optim_export(self, net: int, kind: int, names_shapes: Dict[str, tuple], device: Optional[torch.device] = None) -> Dict[str, torch.Tensor]:
+        """dyf_optim_export: tensors of `kind` (L.OPTIM_*) by state_dict name in PyTorch layouts -> fp32 tensors on the CPU, or --
+        `device` = this engine's GPU -- written there device-to-device."""
+        names = list(names_shapes)
+        if not names:
+            return {}
+        cn = (C.c_char_p * len(names))(*[k.encode() for k in names])
+        if device is not None and torch.device(device).type == "cuda":
+            outs = [torch.empty(names_shapes[k], dtype=torch.float32, device=device) for k in names]
+            cp = (C.c_void_p * len(names))(*[o.data_ptr() for o in outs])
+            torch.cuda.current_stream().synchronize()
+            self._check(self._lib.dyf_optim_export(self._h, net, int(kind), len(names), cn, cp, 1))
+            return dict(zip(names, outs))
+        bufs = [np.empty(names_shapes[k], dtype=np.float32) for k in names]
+        cp = (C.c_void_p * len(names))(*[b.ctypes.data for b in bufs])
+        self._check(self._lib.dyf_optim_export(self._h, net, int(kind), len(names), cn, cp, 0))
+        return {k: torch.from_numpy(b) for k, b in zip(names, bufs)}
+
+    def optim_import(self, net: int, kind: int, tensors: Dict[str, torch.Tensor]):
+        """dyf_optim_import: the reverse of `optim_export`; tensors that all live on this engine's GPU are read in place.  Shapes are
+        the caller's responsibility as far as the element count goes: each tensor must have its parameter's number of elements."""
+        names = list(tensors)
+        if not names:
+            return
+        cn = (C.c_char_p * len(names))(*[k.encode() for k in names])
+        vals = [tensors[k].detach() for k in names]
+        if all(v.is_cuda and v.device.index == self.device for v in vals):
+            keep = [v.to(torch.float32).contiguous() for v in vals]
+            cp = (C.c_void_p * len(names))(*[t.data_ptr() for t in keep])
+            torch.cuda.current_stream().synchronize()
+            self._check(self._lib.dyf_optim_import(self._h, net, int(kind), len(names), cn, cp, 1))
+            return
+        keep = [np.ascontiguousarray(v.to("cpu", torch.float32).numpy()) for v in vals]
+        cp = (C.c_void_p * len(names))(*[a.ctypes.data for a in keep])
+        self._check(self._lib.dyf_optim_import(self._h, net, int(kind), len(names), cn, cp, 0))
+
+    def optim_swap_ema(self, net: int):
+        """dyf_optim_swap_ema: weights <-> EMA shadow in place (both conv layouts), on the current stream."""
+        self._check(self._lib.dyf_optim_swap_ema(self._h, net, self._stream()))
+
     def criterion_grad(self, pred: torch.Tensor, target: torch.Tensor, kind: str, scale: float) -> torch.Tensor:
         name = kind.lower().strip().replace("-", "_")
         code = 0 if name in ("l1", "mae", "mean_absolute_error") else 1 if name in ("l2", "mse", "mean_squared_error") else 2
@@ -883,9 +956,19 @@ def upload_weights(net, eng: "HipEngine", slot: int) -> None:
     net._uploaded_version = net._train_version = (id(eng), state_version(net))
 
 
+def resident_optimizer(net):
+    """The `optim.EngineAdamW` attached to `net` (its weights are updated on the engine), or None."""
+    return net.__dict__.get("_engine_optim")
+
+
 def sync_weights(net, eng: "HipEngine", slot: int) -> None:
     """Before SAMPLING / inference: re-upload a network whose parameters or buffers were modified since the last full upload
-    (optimizer.step(), `p.data = ...` swaps; see `state_version` for what is detected)."""
+    (optimizer.step(), `p.data = ...` swaps; see `state_version` for what is detected).  With an engine-resident optimizer the
+    module is first brought up to date from the engine (`EngineAdamW.pull`), which changes its version marks: the sampling copy
+    is then refreshed by the same mechanism."""
+    opt = resident_optimizer(net)
+    if opt is not None:
+        opt.pull()
     if getattr(net, "_uploaded_version", None) != (id(eng), state_version(net)):
         upload_weights(net, eng, slot)
 
@@ -894,6 +977,9 @@ def sync_train_weights(net, eng: "HipEngine", slot: int) -> None:
     """Before a TRAINING step: refresh only the engine's fp32 training copy (dyf_train_load_weights, ~10x cheaper than the full
     upload, which re-derives every packed 16-bit layout of the sampling path); the sampling copy is brought up to date by
     `sync_weights` when the network is next sampled."""
+    opt = resident_optimizer(net)
+    if opt is not None and opt.engine_is_ahead(eng):
+        return  # the engine's training copy IS the current state (resident steps / BatchNorm updates the module has not pulled yet)
     ver = (id(eng), state_version(net))
     if getattr(net, "_train_version", None) == ver:
         return
@@ -907,7 +993,12 @@ def sync_train_weights(net, eng: "HipEngine", slot: int) -> None:
 def collect_train_results(net, eng: "HipEngine", slot: int, n_forwards: int) -> None:
     """After dyf_train_backward: add the engine's parameter gradients of network `slot` to `param.grad`, clear them in the
     engine, and bring the BatchNorm buffers to what module.train() leaves (running statistics after `n_forwards` momentum
-    updates, num_batches_tracked)."""
+    updates, num_batches_tracked).  With an engine-resident optimizer attached (`optim.EngineAdamW`) nothing is exported: the
+    gradients stay, and accumulate, in the engine; the optimizer books the BatchNorm updates for its next `pull()`."""
+    opt = resident_optimizer(net)
+    if opt is not None:
+        opt.after_backward(eng, slot, n_forwards)
+        return
     sd = net.state_dict(keep_vars=True)
     shapes = {k: tuple(v.shape) for k, v in sd.items() if isinstance(v, torch.nn.Parameter)}
     on_gpu = all(v.is_cuda and v.device.index == eng.device for v in sd.values() if torch.is_tensor(v) and v.is_floating_point())

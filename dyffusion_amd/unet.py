@@ -11,7 +11,7 @@ import torch
 from torch import Tensor, nn
 
 from . import _lib as L
-from .engine import (EngineLoss, HipEngine, collect_train_results, default_dtype_for, mark_weights_modified, resnet_net_config,
+from .engine import (EngineLoss, HipEngine, collect_train_results, default_dtype_for, mark_weights_modified, resident_optimizer, resnet_net_config,
                      sync_train_weights, sync_weights, upload_weights)
 from .unet_simple import _AttrDict
 
@@ -157,7 +157,16 @@ class Unet(nn.Module):
         sample / training step re-uploads them."""
         mark_weights_modified(self)
 
+    def state_dict(self, *args, **kwargs):
+        opt = resident_optimizer(self)
+        if opt is not None:  # engine-resident optimizer steps: the engine holds the current weights
+            opt.pull()
+        return super().state_dict(*args, **kwargs)
+
     def load_state_dict(self, state_dict, strict: bool = True, **kw):
+        opt = resident_optimizer(self)
+        if opt is not None:
+            opt.pull()
         res = super().load_state_dict(state_dict, strict=strict, **kw)
         if self._engine is not None:
             upload_weights(self, self._engine, self._engine_slot)
@@ -168,6 +177,9 @@ class Unet(nn.Module):
         if self._engine is None or (self._engine_key != "attached" and
                                     (self._engine_key[0] != key[0] or self._engine_key[1] < nb)):
             cfg = self.engine_net_config()
+            opt = resident_optimizer(self)
+            if opt is not None and self._engine is not None:  # its state moves to the host side, and into the new engine later
+                opt.release_engine(self._engine)
             # row_groups=1: this engine serves net_forward / the training step, never dyf_sample -- the default row groups would
             # cost a workspace and a packed weight copy each for nothing
             self._engine = HipEngine(cfg, cfg, hw[0], hw[1], max_batch=nb, use_graph=False, dtype=default_dtype_for(self),

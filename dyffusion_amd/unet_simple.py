@@ -12,7 +12,7 @@ import torch
 from torch import Tensor, nn
 
 from . import _lib as L
-from .engine import (EngineLoss, default_dtype_for, mark_weights_modified, HipEngine, collect_train_results, net_config, sync_train_weights, sync_weights,
+from .engine import (EngineLoss, default_dtype_for, mark_weights_modified, resident_optimizer, HipEngine, collect_train_results, net_config, sync_train_weights, sync_weights,
                      upload_weights)
 
 
@@ -111,7 +111,16 @@ class UNet(nn.Module):
         sample / training step re-uploads them."""
         mark_weights_modified(self)
 
+    def state_dict(self, *args, **kwargs):
+        opt = resident_optimizer(self)
+        if opt is not None:  # engine-resident optimizer steps: the engine holds the current weights
+            opt.pull()
+        return super().state_dict(*args, **kwargs)
+
     def load_state_dict(self, state_dict, strict: bool = True, **kw):
+        opt = resident_optimizer(self)
+        if opt is not None:
+            opt.pull()
         res = super().load_state_dict(state_dict, strict=strict, **kw)
         if self._engine is not None:
             upload_weights(self, self._engine, self._engine_slot)
@@ -122,6 +131,9 @@ class UNet(nn.Module):
         if self._engine is None or (self._engine_key != "attached" and
                                     (self._engine_key[0] != key[0] or self._engine_key[1] < nb)):
             cfg = self.engine_net_config()
+            opt = resident_optimizer(self)
+            if opt is not None and self._engine is not None:  # its state moves to the host side, and into the new engine later
+                opt.release_engine(self._engine)
             self._engine = HipEngine(cfg, cfg, hw[0], hw[1], max_batch=nb, use_graph=False, dtype=default_dtype_for(self),
                                      train_precision=getattr(self, "train_precision", None))
             self._engine_slot = L.NET_FORECASTER

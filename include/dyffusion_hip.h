@@ -312,6 +312,47 @@ dyf_status dyf_train_export(dyf_engine* engine, int32_t net, int32_t n_tensors, 
 dyf_status dyf_criterion_grad(dyf_engine* engine, const float* pred_dev, const float* target_dev, int64_t count, int32_t kind,
                               float scale, float* dpred_dev, void* stream);
 
+/* ---- engine-resident optimizer: AdamW with global gradient-norm clipping and a weight EMA (additions to ABI 9) --------------- */
+/* The last third of a training iteration on the engine's own copies: fp32 master weights, gradients (what dyf_train_backward
+ * accumulated), exp_avg / exp_avg_sq and -- optionally -- an EMA shadow of the weights never leave the GPU.  What the reference does with
+ * torch.optim.AdamW + `gradient_clip_val` (Lightning: torch.nn.utils.clip_grad_norm_) + LitEma (src/models/modules/ema.py).
+ *   create   one optimizer per network slot (0 / 1); arch unet_simple and unet.Unet with loaded weights (SimpleConvNet:
+ *            DYF_ERR_UNSUPPORTED, no weights: DYF_ERR_STATE).  State starts at zero, the shadow as a copy of the current weights.
+ *            Creating again replaces the optimizer.  It survives dyf_load_weights of the same network and goes with the engine.
+ *   step     two launches on `stream`, no host synchronisation: (1) sum of squares of all gradients, one double per workgroup;
+ *            (2) every workgroup re-reduces those partial sums in one fixed order (the norm is bitwise the same in every workgroup
+ *            and every run), then, chunk by chunk: g *= min(1, max_grad_norm / (norm + 1e-6)); p *= 1 - lr * weight_decay;
+ *            m += (1 - beta1)(g - m); v = beta2 v + (1 - beta2) g g; p += (-(lr / bc1) m) / (sqrt(v) / sqrt(bc2) + eps);
+ *            shadow -= (1 - ema_decay_now)(shadow - p); g = 0 -- each in the roundings of torch's fp32 CPU kernels (no contraction
+ *            beyond theirs).  Both layouts of a conv weight are written by the same lane.
+ *            BatchNorm running statistics are no parameters and do not move.  A non-finite norm skips the step: only g = 0 is
+ *            written, and the step count is not advanced.  bc1 / bc2 = 1 - beta^t come from the host (double), t = applied steps + 1;
+ *            the outcome of a step is copied to the host behind it and read when the host next needs it (the next step, dyf_optim_last,
+ *            dyf_optim_get_step).  ema_decay_now: the caller evaluates LitEma's warm-up min(decay, (1 + n) / (10 + n)).
+ *   last     gradient norm (before clipping) and skipped flag of the most recent step; waits for that step.
+ *   export / import   by state_dict name in PyTorch layouts, host or device pointers (on_device), `kind` below; running statistics
+ *            ("*.running_mean/var") travel as DYF_OPTIM_WEIGHT only.  Importing gradients REPLACES them.  DYF_OPTIM_WEIGHT_FWD reads a conv
+ *            weight from its second ([tap][cin][cout]) copy: the two copies must never disagree, and a test can see that they do not.
+ *   swap_ema weights <-> shadow in place, both conv layouts (validation through the EMA weights; calling it twice restores bitwise). */
+typedef struct dyf_optim_config {
+    double beta1, beta2, eps, weight_decay;   /* doubles, as torch.optim holds them: 1 - beta^t is evaluated in double */
+    double max_grad_norm;  /* <= 0: no clipping (the norm is still computed) */
+    int32_t ema;           /* keep an EMA shadow */
+} dyf_optim_config;
+typedef enum dyf_optim_kind { DYF_OPTIM_WEIGHT = 0, DYF_OPTIM_GRAD = 1, DYF_OPTIM_EXP_AVG = 2, DYF_OPTIM_EXP_AVG_SQ = 3, DYF_OPTIM_EMA = 4,
+                              DYF_OPTIM_WEIGHT_FWD = 5 /* export only, conv weights only: read from the forward-layout copy */ } dyf_optim_kind;
+dyf_status dyf_optim_create(dyf_engine* engine, int32_t net, const dyf_optim_config* config);
+dyf_status dyf_optim_destroy(dyf_engine* engine, int32_t net);
+dyf_status dyf_optim_step(dyf_engine* engine, int32_t net, double lr, double ema_decay_now, void* stream);
+dyf_status dyf_optim_last(dyf_engine* engine, int32_t net, double* grad_norm_out, int32_t* skipped_out);
+dyf_status dyf_optim_get_step(dyf_engine* engine, int32_t net, int64_t* step_out);
+dyf_status dyf_optim_set_step(dyf_engine* engine, int32_t net, int64_t step);
+dyf_status dyf_optim_export(dyf_engine* engine, int32_t net, int32_t kind, int32_t n_tensors, const char* const* names, float* const* out,
+                            int32_t on_device);
+dyf_status dyf_optim_import(dyf_engine* engine, int32_t net, int32_t kind, int32_t n_tensors, const char* const* names,
+                            const float* const* data, int32_t on_device);
+dyf_status dyf_optim_swap_ema(dyf_engine* engine, int32_t net, void* stream);
+
 /* ---- boundary conditions of the physical-systems benchmark -------------------------------------------------------------- */
 /* Replaces PhysicalSystemsBenchmarkDataModule.boundary_conditions (src/datamodules/physical_systems_benchmark.py:245-297:
  * a Python loop over batch elements with boolean-mask writes), which _evaluation_step applies to every predicted field
