@@ -30,6 +30,19 @@ def storage_dtype(dtype) -> str:
     d = canonical_dtype(dtype)
     return "bf16" if d == "fp32" else d
 
+
+# dyf_set_attention_dropout: how a 16-bit engine draws the dropout of unet.Unet's Attention probabilities (include/dyffusion_hip.h)
+ATTN_DROPOUT_FAST, ATTN_DROPOUT_EXACT = 0, 1
+ATTN_DROPOUT_MODES = {"fast": ATTN_DROPOUT_FAST, "exact": ATTN_DROPOUT_EXACT}
+
+
+def attention_dropout_mode(mode) -> int:
+    """"fast" | "exact" -> DYF_ATTN_DROPOUT_FAST / DYF_ATTN_DROPOUT_EXACT; ValueError for anything else."""
+    if not isinstance(mode, str) or mode not in ATTN_DROPOUT_MODES:
+        raise ValueError(f"attention_dropout {mode!r}: expected one of {sorted(ATTN_DROPOUT_MODES)}")
+    return ATTN_DROPOUT_MODES[mode]
+
+
 DYF_ABI_VERSION = 9
 DYF_OK, DYF_ERR_INVALID_ARGUMENT, DYF_ERR_UNSUPPORTED, DYF_ERR_HIP, DYF_ERR_STATE = range(5)
 NET_FORECASTER, NET_INTERPOLATOR = 0, 1
@@ -161,6 +174,8 @@ SYMBOLS = [
     ("dyf_train_precision", C.c_int32, [_P]),
     ("dyf_set_sample_precision", C.c_int, [_P, C.c_int32]),
     ("dyf_sample_precision", C.c_int32, [_P]),
+    ("dyf_set_attention_dropout", C.c_int, [_P, C.c_int32]),
+    ("dyf_attention_dropout", C.c_int32, [_P]),
     ("dyf_train_export", C.c_int, [_P, C.c_int32, C.c_int32, C.POINTER(C.c_char_p), C.POINTER(_P)]),
     ("dyf_optim_create", C.c_int, [_P, C.c_int32, C.POINTER(OptimConfig)]),
     ("dyf_optim_destroy", C.c_int, [_P, C.c_int32]),

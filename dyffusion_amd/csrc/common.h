@@ -201,7 +201,8 @@ __device__ __host__ __forceinline__ uint32_t keep_threshold16(float p) {
 // threshold.  The keep probability is then k / 256 with k = floor((1 - p) * 256) (>= 1) -- within 2^-8 of 1 - p -- and the survivors are
 // scaled by 256 / k instead of 1 / (1 - p): E[mask * scale] = 1 EXACTLY, as for nn.Dropout; what differs from the reference is the
 // drop rate itself by < 0.4 % absolute (p = 0.1: 0.1016), invisible next to the Monte-Carlo spread of the ensemble it generates.
-// Every other dropout site keeps the 16-bit pair form below (threshold resolution 2^-16).
+// Every other dropout site keeps the 16-bit pair form below (threshold resolution 2^-16) -- and so does this site in the engine's
+// opt-in EXACT mode (DropSpec::attn_exact, dyf_set_attention_dropout): rng_keep on element (h * N + i) * N + j of the row's stream.
 __device__ __host__ __forceinline__ uint32_t keep_threshold8(float p) {
     const float keep = (1.0f - p) * 256.0f;
     const uint32_t k = keep >= 256.0f ? 256u : (uint32_t)keep;
@@ -234,6 +235,10 @@ struct DropSpec {
     const uint8_t* mask;      // device NHWC uint8 keep mask of the whole launch (mode 2)
     uint32_t thresh8;         // quad form (attention probabilities, mode 1): keep threshold k of 256 and the matching scale 256 / k
     float scale8;
+    // attention probabilities, mode 1: 0 = the quad form above, 1 = the EXACT form (dyf_set_attention_dropout) -- the row's site key
+    // without a head fold, element (h * N + i) * N + j, 16-bit slice of pair word e >> 1 against thresh16, survivors scaled by `scale`:
+    // bit for bit rng_keep on the (4, N, N) tensor, i.e. the stream of the fp32 / training path.  Read by launch_attention only.
+    uint32_t attn_exact;
 };
 
 // stream key of launch row `n` (batch row inside this launch)

@@ -570,6 +570,7 @@ dyf_status dyf_set_row_groups(dyf_engine* e, int32_t n_groups) {
             return fail(e, cs, "row group engine: " + g_create_error);
         }
         c->is_group_child = true;
+        c->attn_dropout_exact = e->attn_dropout_exact;
         // kernel forms of a group's launches are chosen by the tile count of all n_groups concurrent launches (OISST 300 rows:
         // 3 680 -> 3 750 fields/s; the 100-row shares otherwise fall below the tile thresholds of the large-batch forms)
         c->form_rows_scale = dyf_form_int("DYF_GROUP_FORM_SCALE", 1) != 0 ? n_groups : 1;
@@ -1004,6 +1005,20 @@ dyf_status dyf_set_sample_precision(dyf_engine* e, int32_t bits) {
     return DYF_OK;
 }
 int32_t dyf_sample_precision(const dyf_engine* e) { return e ? e->sample_precision : -1; }
+
+dyf_status dyf_set_attention_dropout(dyf_engine* e, int32_t mode) {
+    if (!e) return DYF_ERR_INVALID_ARGUMENT;
+    if (mode != DYF_ATTN_DROPOUT_FAST && mode != DYF_ATTN_DROPOUT_EXACT)
+        return fail(e, DYF_ERR_INVALID_ARGUMENT, "dyf_set_attention_dropout: mode must be DYF_ATTN_DROPOUT_FAST (0) or DYF_ATTN_DROPOUT_EXACT (1)");
+    if (mode == DYF_ATTN_DROPOUT_EXACT)
+        for (const Net& n : e->net)
+            if (rn_bottleneck_tokens(n) > ATTN_EXACT_MAX_TOKENS)
+                return fail(e, DYF_ERR_UNSUPPORTED, "dyf_set_attention_dropout: the exact form indexes the (4 x tokens x tokens) probabilities of a row with 32 bits -- at most 32767 bottleneck tokens");
+    e->attn_dropout_exact = mode;  // captured graphs are keyed by the mode (graph_key): nothing to drop
+    for (dyf_engine* c : e->groups) c->attn_dropout_exact = mode;
+    return DYF_OK;
+}
+int32_t dyf_attention_dropout(const dyf_engine* e) { return e ? e->attn_dropout_exact : -1; }
 
 dyf_status dyf_net_forward(dyf_engine* e, int32_t which, const float* inputs_dev, const float* time_dev,
                            const float* condition_dev, float* out_dev, int32_t nb, int32_t dropout_mode,
@@ -1466,7 +1481,7 @@ static dyf_status sample_into_stack(dyf_engine* e, const float* initial_dev, con
         dyf_status r = run_plan(e, nb, masks_dev, noise_dev, st);
         if (r != DYF_OK) return r;
     } else {
-        const int gkey = graph_key(e, nb);  // a graph captured under the other precision is never replayed
+        const int gkey = graph_key(e, nb);  // a graph captured under the other precision / attention-dropout mode is never replayed
         GraphEntry& g = e->graphs[gkey];
         if (!g.exec) {
             HIP_TRY(e, hipStreamBeginCapture(e->cap_stream, hipStreamCaptureModeThreadLocal));
@@ -2100,6 +2115,8 @@ dyf_status dyf_op_attention(dyf_engine* e, const uint16_t* qkv_dev, int32_t n, i
 
 dyf_status dyf_op_attention_dropout(dyf_engine* e, const uint16_t* qkv_dev, int32_t n, int32_t hw, float p, uint16_t* out_dev, void* stream) {
     if (!e || !qkv_dev || !out_dev || n < 1 || hw < 1 || p < 0.0f || p >= 1.0f) return fail(e, DYF_ERR_INVALID_ARGUMENT, "dyf_op_attention: bad arguments");
+    if (p > 0.0f && e->attn_dropout_exact && hw > ATTN_EXACT_MAX_TOKENS)  // before anything is launched
+        return fail(e, DYF_ERR_UNSUPPORTED, "dyf_op_attention_dropout: the exact form of the probability dropout takes at most 32767 tokens");
     HIP_TRY(e, hipSetDevice(e->cfg.device));
     hipStream_t st = (hipStream_t)stream;
     AttnArgs a{};
@@ -2112,6 +2129,7 @@ dyf_status dyf_op_attention_dropout(dyf_engine* e, const uint16_t* qkv_dev, int3
         a.drop.thresh16 = keep_threshold16(p);
         a.drop.thresh8 = keep_threshold8(p);
         a.drop.scale8 = 256.0f / (float)a.drop.thresh8;
+        a.drop.attn_exact = e->attn_dropout_exact ? 1u : 0u;
         a.drop.salt = rng_layer_salt(0u);
         a.drop.row_keys = e->row_keys;
     }

@@ -128,10 +128,13 @@ struct dyf_engine {
     bool row_offset_known = false;
     uint32_t* row_keys = nullptr;   // device [2 max_batch][2]: per-row stream keys of the forward being launched (common.h)
     int stack_slots = 0;
-    std::map<int, dyf::GraphEntry> graphs;  // by (batch size, sampling precision): graph_key
+    std::map<int, dyf::GraphEntry> graphs;  // by (batch size, sampling precision, attention-dropout mode): graph_key
     // fp32 sampling (dyf_set_sample_precision): 16 = the library's 16-bit path, 32 = the fp32 forward of train.hip on a bump arena that
     // the first switch to 32 allocates (max_batch rows of the larger network) and dyf_engine_destroy frees; rewound per forward
     int sample_precision = 16;
+    // dyf_set_attention_dropout: 0 = the quad form of the 16-bit Attention probability dropout, 1 = the exact form (the fp32 path's keep
+    // bits, common.h DropSpec::attn_exact); row-group children carry their parent's value
+    int attn_dropout_exact = 0;
     void* f32_arena = nullptr;
     size_t f32_bytes = 0, f32_used = 0;
     bool f32_forward = false;  // an fp32 sampling forward is being launched (its convs take their split-K workspace from the arena)
@@ -383,7 +386,9 @@ inline void* f32_arena_take(dyf_engine* e, size_t bytes) {
     e->f32_used += b;
     return p;
 }
-inline int graph_key(const dyf_engine* e, int nb) { return e->sample_precision == 32 ? nb | (1 << 30) : nb; }
+inline int graph_key(const dyf_engine* e, int nb) {
+    return nb | (e->sample_precision == 32 ? 1 << 30 : 0) | (e->attn_dropout_exact ? 1 << 29 : 0);
+}
 }  // namespace dyf
 
 // ---- SimpleConvNet backbone (src/models/simple_conv_net.py), implemented in simple_conv_net.hip
@@ -407,4 +412,5 @@ dyf_status rn_load_weights(dyf_engine* e, Net& n, std::map<std::string, TensorVi
 dyf_status rn_forward(dyf_engine* e, int which, const Source* srcs, int nsrc, int nb, const FwdOpts& o, float* out_dev,
                       hipStream_t st);
 void rn_destroy(Net& n);
+long long rn_bottleneck_tokens(const Net& n);  // tokens of the mid-block Attention (0: not a configured ResNet-UNet)
 }  // namespace dyf

@@ -97,6 +97,9 @@ struct AttnArgs {
     DropSpec drop;          // on the probabilities; element index ((n*heads + h)*hw + i)*hw + j
     el16_t* out;            // [n][hw][heads*32]
 };
+// most tokens of the EXACT probability dropout (DropSpec::attn_exact): its element index (h * hw + i) * hw + j < 4 hw^2 is 32 bits --
+// the bound of the fp32 path's streaming core; the quad form keys per head and serves 65535.  Beyond it: hipErrorInvalidValue.
+constexpr int ATTN_EXACT_MAX_TOKENS = 32767;
 hipError_t launch_attention(const AttnArgs& a, hipStream_t s);
 
 // final 1x1 conv to the output channels -> NCHW fp32 (unet.py:244-245, :309)

@@ -1541,10 +1541,19 @@ __device__ __forceinline__ RngKey attn_drop_key(const DropSpec& d, int n, uint32
     if (d.mode == 1) k.k0 = fmix32(k.k0 + (h + 1u) * 0x9E3779B9u);
     return k;
 }
+// EXACT form (DropSpec::attn_exact, mode 1 only): keep bit of element (head h, query i, key j) of the row's (4, N, N) probabilities on
+// the row's site key (drop_row_key, NO head fold) -- rng_keep of the fp32 / training path (train_resnet.inc r_keep).  The element
+// index stays below 2^32 for N <= 32767 (launch_attention checks); nothing is shared between neighbouring elements, so any N is served.
+__device__ __forceinline__ bool attn_keep_exact(const DropSpec& d, RngKey key, uint32_t h, uint32_t i, uint32_t j, uint32_t n) {
+    return rng_keep((h * n + i) * n + j, key, d.thresh16);
+}
 // element (query i, key j) of head-sample bh: RNG stream keyed per bh (i*N + j stays below 2^32 for N <= 65535);
-// injected masks are indexed as the (b, h, i, j) tensor the reference's nn.Dropout sees
+// injected masks are indexed as the (b, h, i, j) tensor the reference's nn.Dropout sees.  EXACT: `key` is the row's site key and
+// `bh` arrives as the head h alone.
+template <bool EXACT = false>
 __device__ __forceinline__ float attn_drop(float p, const DropSpec& d, RngKey key, uint32_t bh, uint32_t i, uint32_t j,
                                            uint32_t n) {
+    if constexpr (EXACT) return attn_keep_exact(d, key, bh, i, j, n) ? p * d.scale : 0.0f;
     if (d.mode == 0) return p;
     if (d.mode == 1) return rng_keep8(i * n + j, key, d.thresh8) ? p * d.scale8 : 0.0f;  // quad form (common.h)
     return d.mask[((size_t)bh * n + i) * n + j] != 0 ? p * d.scale : 0.0f;
@@ -1553,6 +1562,8 @@ __device__ __forceinline__ float attn_drop(float p, const DropSpec& d, RngKey ke
 __device__ __forceinline__ float attn_drop_scale(const DropSpec& d) { return d.mode == 1 ? d.scale8 : d.scale; }
 
 // One thread per query, keys/values of the head streamed through LDS in tiles of 64, online softmax in fp32.
+// EXACT: the exact form of the probability dropout (launched only with a.drop.mode == 1 and a.drop.attn_exact set).
+template <bool EXACT>
 __global__ __launch_bounds__(64) void attention_kernel(AttnArgs a) {
     __shared__ float ks[64][33], vs[64][33];
     const int qtiles = (a.hw + 63) / 64;
@@ -1570,7 +1581,7 @@ __global__ __launch_bounds__(64) void attention_kernel(AttnArgs a) {
         o[c] = 0.0f;
     }
     float m = -3.0e38f, l = 0.0f;
-    const RngKey key = attn_drop_key(a.drop, n, (uint32_t)h);
+    const RngKey key = EXACT ? drop_row_key(a.drop, n) : attn_drop_key(a.drop, n, (uint32_t)h);
     for (int j0 = 0; j0 < a.hw; j0 += 64) {
         __syncthreads();
         for (int t = threadIdx.x; t < 64 * 32; t += 64) {
@@ -1594,7 +1605,7 @@ __global__ __launch_bounds__(64) void attention_kernel(AttnArgs a) {
             }
             const float pr = __expf(sc - m);
             l += pr;  // the softmax normaliser is computed BEFORE dropout (attention.py:69-70)
-            const float pd = live ? attn_drop(pr, a.drop, key, (uint32_t)bh, (uint32_t)i, (uint32_t)(j0 + jj), (uint32_t)a.hw) : 0.0f;
+            const float pd = live ? attn_drop<EXACT>(pr, a.drop, key, (uint32_t)(EXACT ? h : bh), (uint32_t)i, (uint32_t)(j0 + jj), (uint32_t)a.hw) : 0.0f;
 #pragma unroll
             for (int c = 0; c < 32; ++c) o[c] = fmaf(pd, vs[jj][c], o[c]);
         }
@@ -1632,15 +1643,17 @@ typedef __attribute__((ext_vector_type(16))) float fa_f32x16;
 // dropout on the probabilities).
 // VARIANT 1: whole tile, no dropout; 2: whole tile, engine dropout with paired keep words; 0: general (partial tiles; dropout per
 // element when DROP).  DROP is the kernel's compile-time dropout switch: the no-dropout kernel carries no generator code at all
-// (register budget: 128 per lane for 4 waves per SIMD).
+// (register budget: 128 per lane for 4 waves per SIMD).  DROP = FA_DROP_EXACT: the exact form, per element on every tile (VARIANT 0:
+// an odd N puts the two elements of a pair word on different queries, so nothing is shared between elements).
 // QB: 32-query blocks per wave; the launcher instantiates QB = 1 only (a 64-query form, QB = 2, was measured and retired).
+constexpr int FA_DROP_OFF = 0, FA_DROP_QUAD = 1 /* quad form or injected masks */, FA_DROP_EXACT = 2;
 typedef float fa_f32x2 __attribute__((ext_vector_type(2)));
 typedef __attribute__((ext_vector_type(4))) short fa_bf16x4;
 // kf0 / kf1 / vf0: this lane's LDS addresses of the K fragments (ks = 0, 1) and of the V^T fragment of sub-tile 0 (sub-tile st adds
 // a wave-uniform offset: the swizzle key (key >> 2) & 3 does not depend on st).  The score accumulators start at -m: 16 moves per
 // sub-tile (a -m tuple resident in registers measured SLOWER for the 32-query no-dropout kernel, 1.24 vs 1.17 ms: 128 registers
 // leave the scheduler no slack at 4 waves per SIMD).
-template <int VARIANT, bool DROP, int QB>
+template <int VARIANT, int DROP, int QB>
 __device__ __forceinline__ void fa2_subtile(const AttnArgs& a, const el16_t* kf0, const el16_t* kf1, const el16_t* vf0, const el16x8_t (&qf)[QB][2],
                                             fa_f32x16 (&o)[QB], float (&m)[QB], fa_f32x2 (&l2)[QB], bool& first, int jb,
                                             int st, int q0, int N, int hi, RngKey dkey, uint32_t bh, fa_bf16x4 aone, fa_bf16x4 (&bm)[QB]) {
@@ -1717,6 +1730,10 @@ __device__ __forceinline__ void fa2_subtile(const AttnArgs& a, const el16_t* kf0
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int j = jb + (r & 3) + 8 * (r >> 2) + 4 * hi;
+                if constexpr (DROP == FA_DROP_EXACT) {  // dkey: the row's site key, bh: the head
+                    p[r] = j < N && q < N && attn_keep_exact(a.drop, dkey, bh, (uint32_t)q, (uint32_t)j, (uint32_t)N) ? p[r] : 0.0f;
+                    continue;
+                }
                 const bool keep = j < N && q < N &&
                                   (a.drop.mode == 1 ? rng_keep8((uint32_t)q * (uint32_t)N + (uint32_t)j, dkey, a.drop.thresh8)
                                                     : (a.drop.mask[((size_t)bh * N + q) * N + j] != 0));
@@ -1745,7 +1762,7 @@ __device__ __forceinline__ void fa2_subtile(const AttnArgs& a, const el16_t* kf0
 // V^T staging altogether moved 1.72 ms to 1.49 ms, while 3 instead of 2 resident waves per SIMD moved it to 1.24 ms.  Hence the
 // register diet (no second accumulator tuple, rolled sub-tile loop) and 4 waves per SIMD for the 32-query form.
 constexpr int FA2_MIN_WAVES = 4;
-template <bool DROP, int QB>
+template <int DROP, int QB>
 __global__ __launch_bounds__(256, FA2_MIN_WAVES) void flash_attention2_kernel(AttnArgs a) {
     __shared__ __attribute__((aligned(16))) el16_t Ks[64 * 32];   // [key][32 ch], 16-B chunk ^= (key >> 2) & 3
     __shared__ __attribute__((aligned(16))) el16_t Vt[32 * 68];   // [ch][64 keys + 4 pad]
@@ -1791,7 +1808,8 @@ __global__ __launch_bounds__(256, FA2_MIN_WAVES) void flash_attention2_kernel(At
         l2[b] = fa_f32x2{0.0f, 0.0f};
     }
     bool first = true;
-    const RngKey dkey = DROP ? attn_drop_key(a.drop, n, (uint32_t)h) : RngKey{0u, 0u};
+    const RngKey dkey = DROP == FA_DROP_EXACT ? drop_row_key(a.drop, n) : DROP ? attn_drop_key(a.drop, n, (uint32_t)h) : RngKey{0u, 0u};
+    const uint32_t dbh = DROP == FA_DROP_EXACT ? (uint32_t)h : (uint32_t)bh;  // what the sub-tiles index the keep bits with
     // aone / bm: operands of a bias product this form no longer issues; unused, but dropping them changes the generated code
     // (one more exec-mask instruction in the no-dropout kernel)
     const fa_bf16x4 aone = {(short)(hi == 0 ? 0x3F80 : 0), 0, 0, 0};
@@ -1826,14 +1844,14 @@ __global__ __launch_bounds__(256, FA2_MIN_WAVES) void flash_attention2_kernel(At
         if (whole && !DROP) {
 #pragma nounroll
             for (int st = 0; st < 2; ++st)
-                fa2_subtile<1, false, QB>(a, kf0, kf1, vf0, qf, o, m, l2, first, j0 + 32 * st, st, q0, N, hi, dkey, (uint32_t)bh, aone, bm);
-        } else if (DROP && whole && a.drop.mode == 1 && (N & 3) == 0 && (qb + 1) * QG <= N) {
+                fa2_subtile<1, false, QB>(a, kf0, kf1, vf0, qf, o, m, l2, first, j0 + 32 * st, st, q0, N, hi, dkey, dbh, aone, bm);
+        } else if (DROP == FA_DROP_QUAD && whole && a.drop.mode == 1 && (N & 3) == 0 && (qb + 1) * QG <= N) {
 #pragma nounroll
             for (int st = 0; st < 2; ++st)
-                fa2_subtile<2, DROP, QB>(a, kf0, kf1, vf0, qf, o, m, l2, first, j0 + 32 * st, st, q0, N, hi, dkey, (uint32_t)bh, aone, bm);
+                fa2_subtile<2, DROP, QB>(a, kf0, kf1, vf0, qf, o, m, l2, first, j0 + 32 * st, st, q0, N, hi, dkey, dbh, aone, bm);
         } else {
-            fa2_subtile<0, DROP, QB>(a, kf0, kf1, vf0, qf, o, m, l2, first, j0, 0, q0, N, hi, dkey, (uint32_t)bh, aone, bm);
-            if (j0 + 32 < N) fa2_subtile<0, DROP, QB>(a, kf0, kf1, vf0, qf, o, m, l2, first, j0 + 32, 1, q0, N, hi, dkey, (uint32_t)bh, aone, bm);
+            fa2_subtile<0, DROP, QB>(a, kf0, kf1, vf0, qf, o, m, l2, first, j0, 0, q0, N, hi, dkey, dbh, aone, bm);
+            if (j0 + 32 < N) fa2_subtile<0, DROP, QB>(a, kf0, kf1, vf0, qf, o, m, l2, first, j0 + 32, 1, q0, N, hi, dkey, dbh, aone, bm);
         }
     }
 #pragma unroll
@@ -1843,7 +1861,7 @@ __global__ __launch_bounds__(256, FA2_MIN_WAVES) void flash_attention2_kernel(At
         const int q = q0 + 32 * b;
         if (q >= N) continue;
         // O^T[d][q]: lane (q, hi) holds d = (r&3) + 8(r>>2) + 4hi  -> four 8-byte stores of 4 consecutive channels
-        const float inv = (DROP ? attn_drop_scale(a.drop) : 1.0f) / l;
+        const float inv = (DROP == FA_DROP_EXACT ? a.drop.scale : DROP ? attn_drop_scale(a.drop) : 1.0f) / l;
         el16_t* op = a.out + ((size_t)n * N + q) * hd + h * 32;  // "b h (x y) d -> b (h d) x y"
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
@@ -1921,7 +1939,7 @@ __device__ __forceinline__ float fa4_rowsum(const uint32_t (&pk)[8]) {
 #endif
     return acc[0];
 }
-template <bool DROP, bool BIASED, bool TAIL>
+template <int DROP, bool BIASED, bool TAIL>
 __device__ __forceinline__ void fa4_step(const AttnArgs& a, fa_f32x16& sc_cur, fa_f32x16& sc_next, const el16_t* kc0, const el16_t* kc1,
                                          const el16_t* kn0, const el16_t* kn1, const el16_t* vc, const el16x8_t (&qf)[2], fa_f32x16& o, float& m,
                                          fa_f32x2& l2, el16x8_t& bm, const el16x8_t aone, bool& first, bool& biased, int jb, int q, int N, int hi,
@@ -2009,7 +2027,24 @@ __device__ __forceinline__ void fa4_step(const AttnArgs& a, fa_f32x16& sc_cur, f
         first = false;
     }
     l2 += ts;  // the normaliser is accumulated BEFORE dropout (attention.py:69-70)
-    if (DROP) {
+    if (DROP == FA_DROP_EXACT) {
+        // EXACT form (common.h rng_keep on element (h N + q) N + j): the lane's element base (h N + q) N + jb + 4 hi is a multiple of 4
+        // (N % 4 == 0), so register group g (keys jb + 4 hi + 8 g + {0..3}) is the two consecutive pair words base / 2 + 4 g + {0, 1}.
+        // What arrives as `q` is the Weyl value of pair ((h N + q) N + 4 hi) / 2; the sub-tile adds (jb / 2) * RNG_WEYL (scalar), group g
+        // and the second word the constants (4 g + {0, 1}) * RNG_WEYL: EIGHT hashes per 16 probabilities, 16-bit slices against thresh16
+        const uint32_t th = a.drop.thresh16;
+        const uint32_t w0 = (uint32_t)q + (uint32_t)(jb >> 1) * RNG_WEYL;
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const uint32_t wa = rng_pair_mix(w0 + (4u * (uint32_t)g) * RNG_WEYL, dkey);
+            const uint32_t wb = rng_pair_mix(w0 + (4u * (uint32_t)g + 1u) * RNG_WEYL, dkey);
+            // selected and packed group by group, and the groups kept apart for the scheduler: interleaved, the eight hashes next to
+            // sixteen live probabilities spill at NW = 4 (4 / 8 registers, bf16 / fp16 build) under the 128-register bound
+            pk[2 * g] = pack_el16x2((wa & 0xffffu) < th ? p[4 * g] : 0.0f, (wa >> 16) < th ? p[4 * g + 1] : 0.0f);
+            pk[2 * g + 1] = pack_el16x2((wb & 0xffffu) < th ? p[4 * g + 2] : 0.0f, (wb >> 16) < th ? p[4 * g + 3] : 0.0f);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    } else if (DROP) {
         const uint32_t th = a.drop.thresh8;
         // QUAD form (common.h rng_keep8): element q * N + jb + 4 hi is a multiple of 4 (N % 4 == 0) -> quad index / 4; what arrives as
         // `q` is the Weyl value of the lane's quad (q * N + 4 hi) / 4, the sub-tile adds (jb / 4) * RNG_WEYL (scalar) and register group g
@@ -2024,7 +2059,7 @@ __device__ __forceinline__ void fa4_step(const AttnArgs& a, fa_f32x16& sc_cur, f
             p[4 * g + 3] = (w >> 24) < th ? p[4 * g + 3] : 0.0f;
         }
     }
-    if (DROP) {
+    if (DROP && DROP != FA_DROP_EXACT) {
 #pragma unroll
         for (int t = 0; t < 8; ++t) pk[t] = pack_el16x2(p[2 * t], p[2 * t + 1]);
     }
@@ -2038,10 +2073,10 @@ __device__ __forceinline__ void fa4_step(const AttnArgs& a, fa_f32x16& sc_cur, f
     }
 }
 
-// Launch contract: DROP kernels need a.drop.mode == 1, an even token count and whole query blocks (launch_attention checks).
-// NW: waves per workgroup (4 or 8).
+// Launch contract: DROP kernels need a.drop.mode == 1, a token count that is a multiple of 4 and whole query blocks (launch_attention
+// checks).  DROP: FA_DROP_OFF / FA_DROP_QUAD / FA_DROP_EXACT (at most 32767 tokens).  NW: waves per workgroup (4 or 8).
 constexpr int FA4_MIN_WAVES = 4;  // per SIMD
-template <bool DROP, int NW>
+template <int DROP, int NW>
 __global__ __launch_bounds__(64 * NW, FA4_MIN_WAVES) void flash_attention4_kernel(AttnArgs a) {
     __shared__ __attribute__((aligned(16))) el16_t KV[3 * FA4_BUF];
     constexpr int QG = 32 * NW;
@@ -2083,9 +2118,12 @@ __global__ __launch_bounds__(64 * NW, FA4_MIN_WAVES) void flash_attention4_kerne
 #pragma unroll
     for (int r = 0; r < 16; ++r) o[r] = scA[r] = scB[r] = 0.0f;
     bool first = true, biased = false;
-    const RngKey dkey = DROP ? attn_drop_key(a.drop, n, (uint32_t)h) : RngKey{0u, 0u};
-    // DROP: what the steps receive as "q" is the Weyl value of the lane's first keep-word pair, (q0 * N + 4 hi) / 2
-    const int qarg = DROP ? (int)rng_weyl(((uint32_t)q0 * (uint32_t)N + 4u * (uint32_t)hi) >> 2, dkey) : q0;
+    const RngKey dkey = DROP == FA_DROP_EXACT ? drop_row_key(a.drop, n) : DROP ? attn_drop_key(a.drop, n, (uint32_t)h) : RngKey{0u, 0u};
+    // DROP: what the steps receive as "q" is the Weyl value of the lane's first keep word: quad (q0 * N + 4 hi) / 4 of the head's stream,
+    // or (exact form) pair ((h * N + q0) * N + 4 hi) / 2 of the row's
+    const int qarg = DROP == FA_DROP_EXACT ? (int)rng_weyl((((uint32_t)h * (uint32_t)N + (uint32_t)q0) * (uint32_t)N + 4u * (uint32_t)hi) >> 1, dkey)
+                     : DROP            ? (int)rng_weyl(((uint32_t)q0 * (uint32_t)N + 4u * (uint32_t)hi) >> 2, dkey)
+                                       : q0;
 
     // staging role: thread -> (key, 16-B chunk of 8 channels); NW = 4: every thread carries its K and its V piece, NW = 8: the
     // threads of waves 0-3 carry K, those of waves 4-7 V.  Rows beyond the sequence are CLAMPED to the last row (finite values;
@@ -2155,15 +2193,15 @@ __global__ __launch_bounds__(64 * NW, FA4_MIN_WAVES) void flash_attention4_kerne
         if (T > 0) __syncthreads();
         const int j0 = 64 * T;
         const el16_t* B0 = KV + c0;
-        fa4_step<false, true, true>(a, scA, scB, B0 + kf0, B0 + kf1, B0 + kf0, B0 + kf1, B0 + vf0, qf, o, m, l2, bm, aone, first, biased, j0, q0, N, hi, dkey);
+        fa4_step<FA_DROP_OFF, true, true>(a, scA, scB, B0 + kf0, B0 + kf1, B0 + kf0, B0 + kf1, B0 + vf0, qf, o, m, l2, bm, aone, first, biased, j0, q0, N, hi, dkey);
         if (j0 + 32 < N)
-            fa4_step<false, true, true>(a, scA, scB, B0 + 1024 + kf0, B0 + 1024 + kf1, B0 + kf0, B0 + kf1, B0 + vf0 + 32 * 16, qf, o, m, l2, bm, aone, first, biased, j0 + 32, q0, N, hi, dkey);
+            fa4_step<FA_DROP_OFF, true, true>(a, scA, scB, B0 + 1024 + kf0, B0 + 1024 + kf1, B0 + kf0, B0 + kf1, B0 + vf0 + 32 * 16, qf, o, m, l2, bm, aone, first, biased, j0 + 32, q0, N, hi, dkey);
     }
     const float ll = l2.x + l2.y;
     const float l = ll + __shfl_xor(ll, 32, 64);
     if (q0 >= N) return;
     // O^T[d][q]: lane (q, hi) holds d = (r&3) + 8(r>>2) + 4hi  -> four 8-byte stores of 4 consecutive channels
-    const float inv = (DROP ? attn_drop_scale(a.drop) : 1.0f) / l;
+    const float inv = (DROP == FA_DROP_EXACT ? a.drop.scale : DROP ? attn_drop_scale(a.drop) : 1.0f) / l;
     el16_t* op = a.out + ((size_t)n * N + q0) * hd + h * 32;  // "b h (x y) d -> b (h d) x y"
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
@@ -2178,6 +2216,10 @@ hipError_t launch_attention(const AttnArgs& a, hipStream_t s) {
     // DYF_FLASH_ATTN: unset / 4 (/ 3: that kernel was retired in round 5) = flash_attention4_kernel (the pipelined form; falls back to
     // flash_attention2_kernel for the dropout layouts it does not take), 2 = flash_attention2_kernel, 0 = the plain per-query kernel
     const long long flash = dyf_form_int("DYF_FLASH_ATTN", 4);
+    // the exact form of the probability dropout (DropSpec::attn_exact; engine generator only): instantiations of their own, noted in
+    // the form log as "<kernel>,exact>" / "<exact>"; its element index (h N + i) N + j is 32 bits: at most ATTN_EXACT_MAX_TOKENS tokens
+    const bool exact = a.drop.mode == 1 && a.drop.attn_exact != 0;
+    if (exact && a.hw > ATTN_EXACT_MAX_TOKENS) return hipErrorInvalidValue;
     if (flash != 0 && a.hw <= 65535) {
         const int qblocks = (a.hw + 127) / 128;
         const bool drop = a.drop.mode != 0;
@@ -2186,21 +2228,37 @@ hipError_t launch_attention(const AttnArgs& a, hipStream_t s) {
         const int nw = dyf_form_int("DYF_FLASH_NW", 8) >= 8 && a.hw >= 512 ? 8 : 4;
         const bool v4 = flash >= 3 && (!drop || (a.drop.mode == 1 && (a.hw & 3) == 0 && a.hw % (32 * nw) == 0));
         if (v4) {
-            dyf_form_note(nw == 8 ? "flash_attention4_kernel<NW=8>" : "flash_attention4_kernel<NW=4>", a.n);
             const int qb4 = (a.hw + 32 * nw - 1) / (32 * nw);
-            if (nw == 8 && drop) hipLaunchKernelGGL((flash_attention4_kernel<true, 8>), dim3(a.n * a.heads * qb4), dim3(512), 0, s, a);
-            else if (nw == 8) hipLaunchKernelGGL((flash_attention4_kernel<false, 8>), dim3(a.n * a.heads * qb4), dim3(512), 0, s, a);
-            else if (drop) hipLaunchKernelGGL((flash_attention4_kernel<true, 4>), dim3(a.n * a.heads * qb4), dim3(256), 0, s, a);
-            else hipLaunchKernelGGL((flash_attention4_kernel<false, 4>), dim3(a.n * a.heads * qb4), dim3(256), 0, s, a);
+            if (exact) {
+                dyf_form_note(nw == 8 ? "flash_attention4_kernel<NW=8,exact>" : "flash_attention4_kernel<NW=4,exact>", a.n);
+                if (nw == 8) hipLaunchKernelGGL((flash_attention4_kernel<FA_DROP_EXACT, 8>), dim3(a.n * a.heads * qb4), dim3(512), 0, s, a);
+                else hipLaunchKernelGGL((flash_attention4_kernel<FA_DROP_EXACT, 4>), dim3(a.n * a.heads * qb4), dim3(256), 0, s, a);
+                return hipGetLastError();
+            }
+            dyf_form_note(nw == 8 ? "flash_attention4_kernel<NW=8>" : "flash_attention4_kernel<NW=4>", a.n);
+            if (nw == 8 && drop) hipLaunchKernelGGL((flash_attention4_kernel<FA_DROP_QUAD, 8>), dim3(a.n * a.heads * qb4), dim3(512), 0, s, a);
+            else if (nw == 8) hipLaunchKernelGGL((flash_attention4_kernel<FA_DROP_OFF, 8>), dim3(a.n * a.heads * qb4), dim3(512), 0, s, a);
+            else if (drop) hipLaunchKernelGGL((flash_attention4_kernel<FA_DROP_QUAD, 4>), dim3(a.n * a.heads * qb4), dim3(256), 0, s, a);
+            else hipLaunchKernelGGL((flash_attention4_kernel<FA_DROP_OFF, 4>), dim3(a.n * a.heads * qb4), dim3(256), 0, s, a);
+            return hipGetLastError();
+        }
+        if (exact) {
+            dyf_form_note("flash_attention2_kernel<QB=1,exact>", a.n);
+            hipLaunchKernelGGL((flash_attention2_kernel<FA_DROP_EXACT, 1>), dim3(a.n * a.heads * qblocks), dim3(256), 0, s, a);
             return hipGetLastError();
         }
         dyf_form_note("flash_attention2_kernel<QB=1>", a.n);
-        if (drop) hipLaunchKernelGGL((flash_attention2_kernel<true, 1>), dim3(a.n * a.heads * qblocks), dim3(256), 0, s, a);
-        else hipLaunchKernelGGL((flash_attention2_kernel<false, 1>), dim3(a.n * a.heads * qblocks), dim3(256), 0, s, a);
+        if (drop) hipLaunchKernelGGL((flash_attention2_kernel<FA_DROP_QUAD, 1>), dim3(a.n * a.heads * qblocks), dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((flash_attention2_kernel<FA_DROP_OFF, 1>), dim3(a.n * a.heads * qblocks), dim3(256), 0, s, a);
         return hipGetLastError();
     }
     const int qtiles = (a.hw + 63) / 64;
-    hipLaunchKernelGGL(attention_kernel, dim3(a.n * a.heads * qtiles), dim3(64), 0, s, a);
+    if (exact) {
+        dyf_form_note("attention_kernel<exact>", a.n);
+        hipLaunchKernelGGL(attention_kernel<true>, dim3(a.n * a.heads * qtiles), dim3(64), 0, s, a);
+    } else {
+        hipLaunchKernelGGL(attention_kernel<false>, dim3(a.n * a.heads * qtiles), dim3(64), 0, s, a);
+    }
     return hipGetLastError();
 }
 

@@ -90,6 +90,7 @@ struct DropCtx {  // walks the dropout sites in execution order (same order as t
         d.thresh16 = keep_threshold16(p);
         d.thresh8 = keep_threshold8(p);
         d.scale8 = 256.0f / (float)d.thresh8;
+        d.attn_exact = e->attn_dropout_exact ? 1u : 0u;  // read by launch_attention only (dyf_set_attention_dropout)
         d.salt = rng_layer_salt((uint32_t)site++);
         d.row_keys = e->row_keys;
         if (d.mode == 2) {
@@ -482,6 +483,11 @@ dyf_status rn_load_weights(dyf_engine* e, Net& n, std::map<std::string, TensorVi
 #undef NEED
 #undef UP
     return DYF_OK;
+}
+
+long long rn_bottleneck_tokens(const Net& n) {
+    const RNet* r = n.rn;
+    return r && r->nlev > 0 ? (long long)r->lev_h[r->nlev - 1] * r->lev_w[r->nlev - 1] : 0;
 }
 
 // ------------------------------------------------------------------------------------------------ forward

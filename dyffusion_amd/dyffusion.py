@@ -34,7 +34,7 @@ class DYffusion(nn.Module):
                  enable_forecaster_dropout: bool = False, max_batch: int = 64, use_graph: bool = True,
                  enable_mfma: bool = True, loss_function: str = "mean_squared_error", dtype: Optional[str] = None,
                  batch_invariant: bool = False, row_groups: Optional[int] = None, allow_bf16_long_rollout: bool = False,
-                 train_precision=None, **kwargs):
+                 train_precision=None, attention_dropout: str = "fast", **kwargs):
         super().__init__()
         if model is None:
             raise ValueError("Arg ``model`` is missing... Please provide a backbone model for the diffusion model (e.g. a Unet)")
@@ -110,7 +110,11 @@ class DYffusion(nn.Module):
                                  row_groups=row_groups,  # concurrent row groups of a sampling call (None = engine default)
                                  # operand precision of the training step's convolutions: the reference's `trainer.precision`
                                  # (32 default; 16 / "16-mixed" / "bf16-mixed": HipEngine.train_set_precision)
-                                 train_precision=train_precision)
+                                 train_precision=train_precision,
+                                 # 16-bit dropout of unet.Unet's Attention probabilities: "fast" (quad form) or "exact" (nn.Dropout's
+                                 # rate on the fp32 path's keep bits; HipEngine.set_attention_dropout).  ValueError for another string.
+                                 attention_dropout=attention_dropout)
+        L.attention_dropout_mode(attention_dropout)
         self.allow_bf16_long_rollout = bool(allow_bf16_long_rollout)
         self._engine: Optional[HipEngine] = None
         self._plan_key = None
@@ -258,6 +262,13 @@ class DYffusion(nn.Module):
         self._seed = int(seed)
         if self._engine is not None:
             self._engine.seed(self._seed)
+
+    def set_attention_dropout(self, mode: str):
+        """"fast" | "exact" (HipEngine.set_attention_dropout) on the live engine; survives engine re-creation, like the seed."""
+        L.attention_dropout_mode(mode)
+        self._engine_opts["attention_dropout"] = mode
+        if self._engine is not None:
+            self._engine.set_attention_dropout(mode)
 
     def set_row_offset(self, first_row: int):
         """Global index of batch row 0 of the tensors this object is given (ensemble sharding, distributed.py)."""

@@ -94,7 +94,9 @@ def parse_train_precision(precision) -> int:
 class HipEngine:
     def __init__(self, forecaster: L.NetConfig, interpolator: L.NetConfig, height: int, width: int, max_batch: int,
                  device: Optional[int] = None, use_graph: bool = True, enable_mfma: bool = True, dtype: str = "bf16",
-                 batch_invariant: bool = False, row_groups: Optional[int] = None, train_precision=None):
+                 batch_invariant: bool = False, row_groups: Optional[int] = None, train_precision=None,
+                 attention_dropout: str = "fast"):
+        attn_mode = L.attention_dropout_mode(attention_dropout)  # ValueError before anything is created
         if not torch.cuda.is_available():
             raise EngineError("no GPU visible: the DYffusion HIP engine needs an MI355X (gfx950); there is no CPU fallback")
         # "fp32" / "float32" / "32": the default (bf16) build with dyf_set_sample_precision(32) -- every sampling forward in fp32
@@ -120,6 +122,12 @@ class HipEngine:
                 raise
         if row_groups is not None:  # None: the engine's own default (dyf_engine_create, DYF_ROW_GROUPS)
             self._check(self._lib.dyf_set_row_groups(self._h, int(row_groups)))
+        if attn_mode != L.ATTN_DROPOUT_FAST:
+            try:
+                self.set_attention_dropout(attention_dropout)
+            except Exception:
+                self.close()
+                raise
         if train_precision is not None:
             self.train_set_precision(train_precision)
         self._plan_keepalive = None
@@ -167,6 +175,17 @@ class HipEngine:
     @property
     def sample_precision(self) -> int:
         return int(self._lib.dyf_sample_precision(self._h))
+
+    def set_attention_dropout(self, mode: str) -> None:
+        """dyf_set_attention_dropout: how the 16-bit path draws the dropout of unet.Unet's Attention probabilities under the engine's
+        generator.  "fast" (default): the quad form, keep probability floor((1 - p) * 256) / 256 on a stream of its own; "exact":
+        nn.Dropout(p) on the keep bits of the fp32 / training path (at most 32 767 bottleneck tokens: NotImplementedError beyond).
+        Applies to every 16-bit forward that follows, `op_attention(p_drop=...)` included; ValueError for any other string."""
+        self._check(self._lib.dyf_set_attention_dropout(self._h, L.attention_dropout_mode(mode)))
+
+    @property
+    def attention_dropout(self) -> str:
+        return "exact" if int(self._lib.dyf_attention_dropout(self._h)) == L.ATTN_DROPOUT_EXACT else "fast"
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
@@ -748,7 +767,7 @@ class HipEngine:
 
     def op_attention(self, qkv: torch.Tensor, p_drop: float = 0.0) -> torch.Tensor:
         """Test seam: Attention core.  qkv (N,HW,384) in the engine's 16-bit dtype (to_qkv output) -> (N,HW,128); p_drop > 0:
-        dropout on the probabilities from the engine's generator."""
+        dropout on the probabilities from the engine's generator, in the engine's `attention_dropout` mode."""
         assert qkv.dtype == self.torch_dtype and qkv.is_cuda and qkv.is_contiguous() and qkv.shape[2] == 384
         n, hw, _ = qkv.shape
         y = torch.empty((n, hw, 128), dtype=qkv.dtype, device=qkv.device)

@@ -53,6 +53,9 @@ def _attention(dim: int, linear: bool) -> nn.Module:
 
 class Unet(nn.Module):
     default_engine_dtype = "fp16"  # engine.default_dtype_for: the ResNet-UNet is held to 1e-2 per field in fp16 (bf16: 4e-2 .. 5e-2)
+    # standalone engine option, next to `engine_dtype`: "fast" | "exact" dropout of the Attention probabilities in the 16-bit path
+    # (HipEngine.set_attention_dropout); `net.engine_attention_dropout = "exact"` takes effect at the next forward
+    engine_attention_dropout = "fast"
 
     def __init__(self, dim, init_dim=None, dim_mults=(1, 2, 4, 8), num_conditions: int = 0, resnet_block_groups=8,
                  with_time_emb: bool = False, block_dropout: float = 0.0, block_dropout1: float = 0.0,
@@ -183,9 +186,12 @@ class Unet(nn.Module):
             # row_groups=1: this engine serves net_forward / the training step, never dyf_sample -- the default row groups would
             # cost a workspace and a packed weight copy each for nothing
             self._engine = HipEngine(cfg, cfg, hw[0], hw[1], max_batch=nb, use_graph=False, dtype=default_dtype_for(self),
-                                     row_groups=1, train_precision=getattr(self, "train_precision", None))
+                                     row_groups=1, train_precision=getattr(self, "train_precision", None),
+                                     attention_dropout=self.engine_attention_dropout)
             self._engine_slot, self._engine_key = L.NET_FORECASTER, key
             upload_weights(self, self._engine, self._engine_slot)
+        elif self._engine_key != "attached" and self._engine.attention_dropout != self.engine_attention_dropout:
+            self._engine.set_attention_dropout(self.engine_attention_dropout)  # (an attached engine follows its owner's option)
         return self._engine
 
     # ------------------------------------------------------------------ reference API

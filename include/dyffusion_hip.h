@@ -222,15 +222,36 @@ int32_t dyf_row_groups(const dyf_engine* engine);
  *     counter: forecaster, next-step interpolation, current-step interpolation; then the refinement pass one time after the other.
  *   - dropout mode 1 starts every forward from the generator exactly as the 16-bit path does -- same site numbers (a layer with p = 0
  *     is no site), same per-site salt, same 16-bit keep threshold, same global row keys: for equal seed, row offset and call sequence
- *     an fp32 engine draws the keep bits of a 16-bit engine at every activation site.  The one exception is the attention-probability
- *     site of unet.Unet: the 16-bit flash kernel keeps with k/256 granularity (rng_keep8, csrc/common.h), the fp32 path keeps nn.Dropout's
- *     p through the 16-bit threshold, as the training path does -- same stream, a different threshold on it.
+ *     an fp32 engine draws the keep bits of a 16-bit engine at every activation site.  The one exception holds in the 16-bit engine's
+ *     DEFAULT attention-dropout mode only (DYF_ATTN_DROPOUT_FAST, dyf_set_attention_dropout below): there the attention-probability site
+ *     of unet.Unet draws from a head-folded stream of its own with k/256 granularity (rng_keep8, csrc/common.h), while the fp32 path keeps
+ *     nn.Dropout's p through the 16-bit threshold on the row's site stream, as the training path does.  With DYF_ATTN_DROPOUT_EXACT a
+ *     16-bit engine draws the fp32 engine's keep bits at EVERY site.
  *   - dropout mode 2 applies the caller's uint8 keep masks, layout and site order as in the 16-bit path ((NB, 4, N, N) for the
  *     attention probabilities).
  *   - a graph captured under one precision is never replayed under the other.
  * dyf_sample_precision returns 16 or 32. */
 dyf_status dyf_set_sample_precision(dyf_engine* engine, int32_t bits);
 int32_t dyf_sample_precision(const dyf_engine* engine);
+
+/* Dropout on the softmax probabilities of unet.Unet's Attention (attention.py:70) in the 16-bit path, engine generator (dropout mode 1).
+ * Added without an ABI bump: two functions and two constants, no struct changes layout.
+ *   DYF_ATTN_DROPOUT_FAST (0, default)  the quad form: one keep word per four probabilities on a stream keyed per (row, head), keep
+ *       probability floor((1 - p) * 256) / 256 (p = 0.1 drops 10.16 %), survivors scaled by 256 / k so the expectation is exact; up to
+ *       65 535 tokens.
+ *   DYF_ATTN_DROPOUT_EXACT (1)          nn.Dropout(p) on the stream of the fp32 and training paths, bit for bit: the row's site key,
+ *       element (h * N + i) * N + j of the row's (4, N, N) probabilities, 16-bit slice of its pair word against floor((1 - p) * 65536),
+ *       survivors scaled by 1 / (1 - p).  For equal seed, row offset and call sequence the engine then draws, at every dropout site, the
+ *       keep bits of an fp32 engine -- and of tests/rng_host.py's host restatement.  At most 32 767 tokens (4 N^2 <= 2^32 - 1).
+ * The mode applies to every 16-bit forward that follows -- dyf_net_forward, dyf_sample, dyf_sample_gather, the eval-mode loss, the
+ * dyf_op_attention_dropout seam -- and to the row groups; injected masks (mode 2), fp32 sampling and the training step do not depend on
+ * it.  A graph captured under one mode is never replayed under the other.  Engines without a unet.Unet network accept the call without
+ * effect.  DYF_ERR_INVALID_ARGUMENT: any other mode; DYF_ERR_UNSUPPORTED (the mode stays as it was): DYF_ATTN_DROPOUT_EXACT on an
+ * engine whose unet.Unet has more than 32 767 bottleneck tokens.  dyf_attention_dropout returns the mode in effect. */
+#define DYF_ATTN_DROPOUT_FAST 0
+#define DYF_ATTN_DROPOUT_EXACT 1
+dyf_status dyf_set_attention_dropout(dyf_engine* engine, int32_t mode);
+int32_t dyf_attention_dropout(const dyf_engine* engine);
 
 /* ---- engine-owned exchange of the ensemble-sharded path (one process per GPU; the reference has no inference collective) ------- */
 /* Ensemble members / batch items are independent rows for the whole rollout (_base_experiment.py:503-538 tiles them, row = n*B + b),

@@ -106,7 +106,8 @@ dyf_status dyf_op_linear_attention_fused(dyf_engine* engine, const uint16_t* xn_
 dyf_status dyf_op_attention(dyf_engine* engine, const uint16_t* qkv_dev, int32_t n, int32_t hw, uint16_t* out_dev,
                             void* stream);
 /* ... with nn.Dropout(p) on the softmax probabilities (attention.py:70), masks from the engine's generator: the form the
- * interpolator's bottleneck runs under MC dropout (n <= 2 max_batch rows). */
+ * interpolator's bottleneck runs under MC dropout (n <= 2 max_batch rows).  Follows the engine's dyf_set_attention_dropout mode; in
+ * the exact mode more than 32 767 tokens are refused with DYF_ERR_UNSUPPORTED before anything is launched. */
 dyf_status dyf_op_attention_dropout(dyf_engine* engine, const uint16_t* qkv_dev, int32_t n, int32_t hw, float p, uint16_t* out_dev,
                                     void* stream);
 /* The fp32 Attention core of fp32 sampling and the training step: qkv_dev (N,HW,384) fp32 -> out_dev (N,HW,128) fp32.  form 0: the

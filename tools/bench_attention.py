@@ -10,7 +10,11 @@ t_at_stream_bwd_dq / _dkv), interleaved in one process, medians, at N = 1024 and
 N = 16 384, NB = 1; and the device memory the engine holds after one call of each form (hipMemGetInfo around a fresh engine: its caching
 pool's high-water mark).  These are SEAM WALL TIMES: they include the seam's allocations, copies and synchronisation, so they compare the
 two forms with each other and nothing else.
-usage: python tools/bench_attention.py --fp32-train"""
+usage: python tools/bench_attention.py --fp32-train
+--exact-dropout: the 16-bit core WITH dropout on the probabilities in the engine's two attention-dropout modes (HipEngine.set_attention_dropout):
+"fast" (the quad form, default) against "exact" (nn.Dropout's rate on the fp32 path's keep bits), interleaved in one process, medians of
+the per-call times (the seam synchronises: one call = one launch); the kernel each mode ran is read from the form log.
+usage: python tools/bench_attention.py --exact-dropout [--fp16] [NB] [tokens] [p]"""
 import os
 import sys
 
@@ -26,7 +30,9 @@ from dyffusion_amd.engine import net_config  # noqa: E402
 
 fp32 = "--fp32" in sys.argv
 fp32_train = "--fp32-train" in sys.argv
-sys.argv = [a for a in sys.argv if a not in ("--fp32", "--fp32-train")]
+exact_dropout = "--exact-dropout" in sys.argv
+dtype16 = "fp16" if "--fp16" in sys.argv else "bf16"  # --fp16: the fp16 build of the library (16-bit cores only)
+sys.argv = [a for a in sys.argv if a not in ("--fp32", "--fp32-train", "--exact-dropout", "--fp16")]
 nb = int(sys.argv[1]) if len(sys.argv) > 1 else 4
 n = int(sys.argv[2]) if len(sys.argv) > 2 else 16384
 cfg = net_config(in_channels=3, cond_channels=2, out_channels=3, dim=64, with_time_emb=True, upsample_dims=(64, 64), dropout=0.0)
@@ -75,7 +81,7 @@ if fp32_train:
             print(f"fp32 training {op:16s} NB={rows}, {tokens:5d} tokens: forward + backward median {statistics.median(times[op]):9.3f} ms "
                   f"(min {min(times[op]):.3f}, max {max(times[op]):.3f}); engine pool after one call {mem[op][0]:8.1f} MiB")
     sys.exit(0)
-eng = D.HipEngine(cfg, cfg, 23, 11, max_batch=max(1, nb), use_graph=False)
+eng = D.HipEngine(cfg, cfg, 23, 11, max_batch=max(1, nb), use_graph=False, dtype=dtype16)
 g = torch.Generator().manual_seed(0)
 qkv = torch.randn(nb, n, 384, generator=g).to(eng.torch_dtype).cuda()
 fl = nb * 4 * 2 * 2 * n * n * 32
@@ -99,6 +105,33 @@ if fp32:
         ms = statistics.median(times[f])
         print(f"fp32 attention core form {f} ({'streaming' if f else 'keeps P'}) NB={nb}, {n} tokens: median {ms:.3f} ms (min {min(times[f]):.3f}, "
               f"max {max(times[f]):.3f}), {fl / ms / 1e9:.1f} TFLOP/s = {fl / ms / 1e9 / 157:.3f} of the 157 TF fp32 matrix peak")
+    sys.exit(0)
+if exact_dropout:
+    import statistics
+
+    modes = ["fast", "exact"]
+    kernel = {}
+    for mode in modes * 5:  # warm-up: clocks up, both kernels loaded
+        eng.set_attention_dropout(mode)
+        eng.form_log(True)
+        y = eng.op_attention(qkv, p)
+        kernel[mode] = ", ".join(sorted(eng.form_log_read()))
+    eng.form_log(False)
+    times = {mode: [] for mode in modes}
+    for _ in range(15 if n > 4096 else 50):  # interleaved: both modes see the same clocks
+        for mode in modes:
+            eng.set_attention_dropout(mode)
+            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            ev0.record()
+            y = eng.op_attention(qkv, p)
+            ev1.record()
+            torch.cuda.synchronize()
+            times[mode].append(ev0.elapsed_time(ev1))
+    med = {mode: statistics.median(times[mode]) for mode in modes}
+    for mode in modes:
+        print(f"attention core NB={nb}, {n} tokens, dropout p={p}, {eng.dtype}, {mode:5s} ({kernel[mode]}): median {med[mode] * 1e3:.1f} us "
+              f"(min {min(times[mode]) * 1e3:.1f}, max {max(times[mode]) * 1e3:.1f}), {fl / med[mode] / 1e9:.1f} TFLOP/s")
+    print(f"exact / fast = {med['exact'] / med['fast']:.3f}")
     sys.exit(0)
 for pd in (0.0, p):
     for _ in range(10):  # the device idles in a low-power state: ten launches before the timed ones (measured: one warm-up launch

@@ -7,6 +7,8 @@ ONE JSON line: the per-horizon rel-RMS of the 16-bit fields against the fp32 fie
     python tools/precision_drift.py --config oisst --dtype fp16 [--rows 8]     # OISST: 60x60, unet.Unet, T = 32, data+noise
     python tools/precision_drift.py --config synth512 --dtype fp16 --rows 4    # 512x512x4, unet.Unet, h = 32: 16 384 bottleneck tokens
     python tools/precision_drift.py --small                                    # the 23x11 test pair (dim 64 @ 64^2, h = 4)
+    python tools/precision_drift.py --config oisst --dtype fp16 --attention-dropout exact   # the 16-bit engine in its exact
+                                                # attention-dropout mode: the fp32 engine's keep bits at EVERY site, rounding alone is left
 
 Needs an MI355X.  Imports neither the oracle nor the reference: the fp32 engine is the yardstick.
 """
@@ -50,8 +52,9 @@ def random_state(net, seed, conv_gain=1.0):
     return sd
 
 
-def make(config, dtype, rows, attn_dropout=True):
-    """(DYffusion, initial condition, static condition or None) of `config` on an engine of `dtype`; same weights for every dtype."""
+def make(config, dtype, rows, attn_dropout=True, attn_mode="fast"):
+    """(DYffusion, initial condition, static condition or None) of `config` on an engine of `dtype`; same weights for every dtype.
+    attn_mode: DYffusion(attention_dropout=...) -- how the 16-bit engine draws the dropout of unet.Unet's Attention probabilities."""
     g = torch.Generator().manual_seed(3)
     if config in ("ns", "small"):
         hw, up, h = ((221, 42), [256, 256], 16) if config == "ns" else ((23, 11), [64, 64], 4)
@@ -73,12 +76,13 @@ def make(config, dtype, rows, attn_dropout=True):
         I.load_state_dict(random_state(I, 1, 0.5))
         m = D.DYffusion(F, D.InterpolatorHandle(I, 32), timesteps=32, forward_conditioning="none", interpolate_before_t1=True,
                         refine_intermediate_predictions=False, enable_interpolator_dropout=True, max_batch=rows, dtype=dtype,
-                        allow_bf16_long_rollout=True)
+                        allow_bf16_long_rollout=True, attention_dropout=attn_mode)
         x0, c = torch.randn(rows, 4, 512, 512, generator=g), None
     else:
         kw = dict(dim=64, dim_mults=(1, 2, 4), with_time_emb=True)
-        # attn_dropout also covers the one site whose keep bits differ between the precisions (the attention probabilities: k/256
-        # granularity in the 16-bit flash kernel, nn.Dropout's p in fp32); --no-attention-dropout leaves rounding as the only difference
+        # attn_dropout also covers the one site whose keep bits differ between the precisions in the 16-bit engine's default mode (the
+        # attention probabilities: the quad form's own stream and k/256 granularity, nn.Dropout's p in fp32); --no-attention-dropout, or
+        # --attention-dropout exact with the site left on, leaves rounding as the only difference
         F = D.Unet(num_input_channels=1, num_output_channels=1, num_conditional_channels=1, block_dropout=0.3,
                    attn_dropout=0.1 if attn_dropout else 0.0, **kw)
         I = D.Unet(num_input_channels=2, num_output_channels=1, num_conditional_channels=0, block_dropout=0.6, block_dropout1=0.2,
@@ -87,7 +91,7 @@ def make(config, dtype, rows, attn_dropout=True):
         I.load_state_dict(random_state(I, 1, 0.5))
         m = D.DYffusion(F, D.InterpolatorHandle(I, 7), timesteps=7, forward_conditioning="data+noise", interpolate_before_t1=True,
                         additional_interpolation_steps=25, refine_intermediate_predictions=False, max_batch=rows, dtype=dtype,
-                        allow_bf16_long_rollout=True)
+                        allow_bf16_long_rollout=True, attention_dropout=attn_mode)
         x0, c = torch.randn(rows, 1, 60, 60, generator=g), None
     return m, x0.cuda(), None if c is None else c.cuda()
 
@@ -118,14 +122,17 @@ def main():
     ap.add_argument("--dtype", choices=["bf16", "fp16"], default="bf16", help="the 16-bit engine compared with fp32")
     ap.add_argument("--rows", type=int, default=8, help="batch rows (ensemble members x batch) of the rollout")
     ap.add_argument("--no-attention-dropout", action="store_true", help="oisst / synth512: attn_dropout = 0 in both networks")
+    ap.add_argument("--attention-dropout", choices=["fast", "exact"], default="fast",
+                    help="oisst / synth512: attention-dropout mode of the 16-bit engine (exact: the fp32 engine's keep bits)")
     ap.add_argument("--seed", type=int, default=7)
     ap.add_argument("--reps", type=int, default=2, help="timed rollouts per engine (the best counts)")
     a = ap.parse_args()
     config = "small" if a.small else a.config
-    res = dict(config=config, dtype=a.dtype, rows=a.rows, seed=a.seed, attention_dropout=not a.no_attention_dropout)
+    res = dict(config=config, dtype=a.dtype, rows=a.rows, seed=a.seed, attention_dropout=not a.no_attention_dropout,
+               attention_dropout_mode=a.attention_dropout)
     fields, times = {}, {}
     for dtype in ("fp32", a.dtype):  # one engine at a time: the fp32 arena of a full-size pair is several GB
-        m, x0, c = make(config, dtype, a.rows, not a.no_attention_dropout)
+        m, x0, c = make(config, dtype, a.rows, not a.no_attention_dropout, a.attention_dropout)
         fields[dtype], times[dtype] = rollout(m, x0, c, a.seed, a.reps)
         fields[dtype] = {k: v.cpu() for k, v in fields[dtype].items()}
         nf, ni = m._engine.forward_counts()
