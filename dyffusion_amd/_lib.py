@@ -172,6 +172,8 @@ SYMBOLS = [
     ("dyf_train_zero_grads", C.c_int, [_P, C.c_int32]),
     ("dyf_train_set_precision", C.c_int, [_P, C.c_int32]),
     ("dyf_train_precision", C.c_int32, [_P]),
+    ("dyf_train_set_deterministic", C.c_int, [_P, C.c_int32]),
+    ("dyf_train_deterministic", C.c_int32, [_P]),
     ("dyf_set_sample_precision", C.c_int, [_P, C.c_int32]),
     ("dyf_sample_precision", C.c_int32, [_P]),
     ("dyf_set_attention_dropout", C.c_int, [_P, C.c_int32]),

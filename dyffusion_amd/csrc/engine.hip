@@ -1797,7 +1797,15 @@ dyf_status dyf_criterion(dyf_engine* e, const float* pred_dev, const float* targ
         dyf_status s = dev_alloc(e, &e->metric_sums, 4);
         if (s != DYF_OK) return s;
     }
-    HIP_TRY(e, launch_criterion_sum(pred_dev, target_dev, count, kind, e->metric_sums, st));
+    if (e->train_deterministic) {  // dyf_train_set_deterministic: per-workgroup partial sums added in a fixed order, no atomics
+        if (!e->criterion_partials) {
+            dyf_status s = dev_alloc(e, &e->criterion_partials, CRITERION_MAX_BLOCKS);
+            if (s != DYF_OK) return s;
+        }
+        HIP_TRY(e, launch_criterion_sum_det(pred_dev, target_dev, count, kind, e->criterion_partials, e->metric_sums, st));
+    } else {
+        HIP_TRY(e, launch_criterion_sum(pred_dev, target_dev, count, kind, e->metric_sums, st));
+    }
     double h = 0.0;
     HIP_TRY(e, hipMemcpyAsync(&h, e->metric_sums, sizeof(h), hipMemcpyDeviceToHost, st));
     HIP_TRY(e, hipStreamSynchronize(st));

@@ -162,6 +162,8 @@ struct dyf_engine {
     std::vector<dyf_engine*> groups;
     bool is_group_child = false;
     int train_precision = 0;  // dyf_train_set_precision: 0 = DYF_TRAIN_OPERANDS decides (default fp32), 32, 16
+    int train_deterministic = 0;  // dyf_train_set_deterministic: 1 = no sum of the training step is merged with atomics
+    double* criterion_partials = nullptr;  // deterministic dyf_criterion: one partial sum per workgroup (device, CRITERION_MAX_BLOCKS)
     int form_rows_scale = 1;             // child: kernel forms are chosen for this many times the rows of a launch (the siblings' share)
     hipStream_t group_stream = nullptr;  // child: the stream its share runs on
     hipEvent_t group_done = nullptr;     // child: recorded behind its share

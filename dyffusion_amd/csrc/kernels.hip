@@ -1628,7 +1628,50 @@ hipError_t launch_criterion_sum(const float* p, const float* t, long long count,
     hipError_t e = hipMemsetAsync(sum, 0, sizeof(double), s);
     if (e != hipSuccess) return e;
     const unsigned grid = (unsigned)std::max<long long>(1, std::min<long long>((count / 4 + 1023) / 1024, 2048));
+    dyf_form_note("criterion_sum_kernel:atomic", 0);
     hipLaunchKernelGGL(criterion_sum_kernel, dim3(grid), dim3(256), 0, s, p, t, count, kind, sum);
+    return hipGetLastError();
+}
+
+// The same terms without atomics: the four wave sums of a workgroup meet in LDS and leave, added in wave order, as partials[blockIdx.x];
+// criterion_finish_kernel (one wave) adds the partials: lane l takes l, l + 64, ... in order, then the lanes' sums in lane order.
+__global__ __launch_bounds__(256) void criterion_partial_kernel(const float* p, const float* t, long long count, int kind, double* partials) {
+    __shared__ float wsum[4];
+    const long long n4 = count >> 2;
+    float acc = 0.0f;
+    auto term = [&](float d) {
+        const float ad = fabsf(d);
+        return kind == 0 ? ad : kind == 1 ? d * d : (ad < 1.0f ? 0.5f * d * d : ad - 0.5f);
+    };
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
+        const float4 a = ((const float4*)p)[i], b = ((const float4*)t)[i];
+        acc += term(a.x - b.x) + term(a.y - b.y) + term(a.z - b.z) + term(a.w - b.w);
+    }
+    if (blockIdx.x == 0 && threadIdx.x < (count & 3)) acc += term(p[n4 * 4 + threadIdx.x] - t[n4 * 4 + threadIdx.x]);
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) acc += __shfl_xor(acc, d, 64);
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) partials[blockIdx.x] = (double)wsum[0] + (double)wsum[1] + (double)wsum[2] + (double)wsum[3];
+}
+__global__ __launch_bounds__(64) void criterion_finish_kernel(const double* partials, int n, double* sum) {
+    __shared__ double lane_sum[64];
+    double a = 0.0;
+    for (int i = threadIdx.x; i < n; i += 64) a += partials[i];
+    lane_sum[threadIdx.x] = a;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double s = 0.0;
+        for (int l = 0; l < 64; ++l) s += lane_sum[l];
+        *sum = s;
+    }
+}
+
+hipError_t launch_criterion_sum_det(const float* p, const float* t, long long count, int kind, double* partials, double* sum, hipStream_t s) {
+    const unsigned grid = (unsigned)std::max<long long>(1, std::min<long long>((count / 4 + 1023) / 1024, CRITERION_MAX_BLOCKS));
+    dyf_form_note("criterion_sum_kernel:det", 0);
+    hipLaunchKernelGGL(criterion_partial_kernel, dim3(grid), dim3(256), 0, s, p, t, count, kind, partials);
+    hipLaunchKernelGGL(criterion_finish_kernel, dim3(1), dim3(64), 0, s, partials, (int)grid, sum);
     return hipGetLastError();
 }
 

@@ -181,6 +181,44 @@ __global__ void t_resize_bwd(const float* dout, int n, int ih, int iw, int C, in
     atomicAdd(base + ((size_t)y1 * iw + x1) * C, g * ly * lx);
 }
 
+// The same adjoint as a GATHER (deterministic mode): one thread per INPUT element walks the output pixels whose stencil touches it --
+// rows, then columns, in index order -- with the forward's own bilinear_coord, and adds the terms the scatter above would have sent.
+// Output row oy reads input rows around (oy + 0.5) ih / oh - 0.5, so input row iy is touched from source coordinates in (iy - 1, iy + 1):
+// that range of oy plus one row of slack each way (every candidate is tested), the clamped borders taking the rest of the plane.
+__device__ __forceinline__ void resize_adj_range(int i, int in_size, int out_size, int& o0, int& o1) {
+    const float inv = (float)out_size / (float)in_size;
+    o0 = i == 0 ? 0 : max(0, (int)floorf(((float)i - 0.5f) * inv - 0.5f) - 1);
+    o1 = i == in_size - 1 ? out_size - 1 : min(out_size - 1, (int)ceilf(((float)i + 1.5f) * inv - 0.5f) + 1);
+}
+__global__ void t_resize_bwd_gather(const float* dout, int n, int ih, int iw, int C, int oh, int ow, int nearest, float* din) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (long long)n * ih * iw * C) return;
+    const int c = (int)(i % C);
+    const long long p = i / C;
+    const int ix = (int)(p % iw), iy = (int)((p / iw) % ih), b = (int)(p / ((long long)iw * ih));
+    int oy0, oy1, ox0, ox1;
+    resize_adj_range(iy, ih, oh, oy0, oy1);
+    resize_adj_range(ix, iw, ow, ox0, ox1);
+    const float* base = dout + (size_t)b * oh * ow * C + c;
+    float acc = 0.0f;
+    for (int oy = oy0; oy <= oy1; ++oy) {
+        int y0, y1, x0, x1;
+        float ly, lx;
+        bilinear_coord(oy, (float)ih / (float)oh, ih, y0, y1, ly, nearest != 0);
+        if (y0 != iy && y1 != iy) continue;
+        for (int ox = ox0; ox <= ox1; ++ox) {
+            bilinear_coord(ox, (float)iw / (float)ow, iw, x0, x1, lx, nearest != 0);
+            if (x0 != ix && x1 != ix) continue;
+            const float g = base[((size_t)oy * ow + ox) * C];
+            if (y0 == iy && x0 == ix) acc += g * (1.0f - ly) * (1.0f - lx);
+            if (y0 == iy && x1 == ix) acc += g * (1.0f - ly) * lx;
+            if (y1 == iy && x0 == ix) acc += g * ly * (1.0f - lx);
+            if (y1 == iy && x1 == ix) acc += g * ly * lx;
+        }
+    }
+    din[i] += acc;
+}
+
 // ------------------------------------------------------------------------------------------------ convolution (fp32, NHWC)
 
 // y[n,oy,ox,co] = b[co] + sum_{tap,ci} x[n, oy*s-p+ky, ox*s-p+kx, ci] * wt[tap][ci][co]
@@ -370,6 +408,9 @@ __global__ __launch_bounds__(256) void t_conv_dgrad_smalln(TConv g, const float*
 
 // dw[co][tap][ci] += sum_{n,oy,ox} dz[n,oy,ox,co] * x[n,oy*s-p+ky,ox*s-p+kx,ci].  One workgroup = a 16 x 16 (co, ci) tile of
 // one tap over a slice of the output pixels; slices are merged with atomics.  db[co] += sum dz (tap 0 / ci-tile 0 only).
+// DET (deterministic mode): no atomics -- slice s stores its sums to slab s of the workspace (dw = its base, slab = [cout taps cin | cout],
+// db = the base of the bias part); with ONE slice the workgroup owns its elements and adds to the real dw / db itself.
+template <bool DET>
 __global__ __launch_bounds__(256) void t_conv_wgrad(TConv g, const float* dz, const float* x, float* dw, float* db, int pix_per_block) {
     const int taps = g.k * g.k;
     const int co_tiles = (g.cout + 15) / 16, ci_tiles = (g.cin + 15) / 16;
@@ -408,8 +449,18 @@ __global__ __launch_bounds__(256) void t_conv_wgrad(TConv g, const float* dz, co
         }
         __syncthreads();
     }
-    if (co < g.cout && ci < g.cin) atomicAdd(dw + ((size_t)co * taps + tap) * g.cin + ci, acc);
-    if (db && tap == 0 && cit == 0 && tci == 0 && co < g.cout) atomicAdd(db + co, accb);
+    if (!DET) {
+        if (co < g.cout && ci < g.cin) atomicAdd(dw + ((size_t)co * taps + tap) * g.cin + ci, acc);
+        if (db && tap == 0 && cit == 0 && tci == 0 && co < g.cout) atomicAdd(db + co, accb);
+    } else {
+        const bool single = (int)gridDim.x == taps * co_tiles * ci_tiles;
+        const size_t off = single ? 0 : (size_t)slice * ((size_t)g.cout * taps * g.cin + g.cout);
+        if (co < g.cout && ci < g.cin) {
+            float* o = dw + off + ((size_t)co * taps + tap) * g.cin + ci;
+            *o = single ? *o + acc : acc;
+        }
+        if (db && tap == 0 && cit == 0 && tci == 0 && co < g.cout) db[off + co] = single ? db[off + co] + accb : accb;
+    }
 }
 
 // The same sums for STRIDE 2 with one thread per result pixel: wave w of a workgroup owns the pixels of parity class
@@ -586,7 +637,9 @@ __global__ __launch_bounds__(256) void t_conv_wgrad_smallc(TConv g, const float*
 // predicated to zero.  (The form above keeps taps x cin sums per lane and feeds them from scalar loads, one pixel at a time: 2.5 ms per
 // launch for the readout's 4 x 4 x 3 at 32 rows, 1.0 ms for the 7 x 7 x 2 init conv -- its traffic time is ~0.1 ms.)  wo even.
 typedef __attribute__((ext_vector_type(16))) float tw_f32x16;
-template <int NT>
+// DET (deterministic mode): no atomics -- wave v = 4 blockIdx.x + wave stores its sums to slab v of the workspace (dw = its base, slab =
+// [cout nacc | cout], db = the base of the bias part, always given); empty waves store zeros, so every slab is complete.
+template <int NT, bool DET = false>
 __global__ __launch_bounds__(256) void t_conv_wgrad_smallc_mfma(TConv g, const float* __restrict__ dz, const float* __restrict__ x,
                                                                 float* __restrict__ dw, float* __restrict__ db, int pairs_per_wave) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -655,6 +708,12 @@ __global__ __launch_bounds__(256) void t_conv_wgrad_smallc_mfma(TConv g, const f
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int co = cob + c * 32 + 8 * (r >> 2) + 4 * hi + (r & 3);
+                if (DET) {
+                    const size_t off = (size_t)(blockIdx.x * 4 + wave) * ((size_t)g.cout * nacc + g.cout);
+                    if (j < nacc) dw[off + (size_t)co * nacc + j] = acc[c][t][r];
+                    else if (j == nacc) db[off + co] = acc[c][t][r];
+                    continue;
+                }
                 if (j < nacc) atomicAdd(dw + (size_t)co * nacc + j, acc[c][t][r]);   // dw[co][tap][ci]
                 else if (j == nacc && db) atomicAdd(db + co, acc[c][t][r]);
             }
@@ -664,6 +723,9 @@ __global__ __launch_bounds__(256) void t_conv_wgrad_smallc_mfma(TConv g, const f
 
 // ------------------------------------------------------------------------------------------------ normalisation + FiLM + act + dropout
 // per-(sample, channel) sums over the plane: S[n][c] = sum z, Q[n][c] = sum z^2   (fp64 accumulators, zero-initialised)
+// DET (deterministic mode): no atomics -- pixel range r = blockIdx.x stores to slab r of (S | Q) = the workspace, slabs 2 n C doubles apart
+// (one range: S / Q themselves, each slot stored once)
+template <bool DET>
 __global__ __launch_bounds__(256) void t_nc_sums(const float* z, int hw, int C, int px_per_block, double* S, double* Q) {
     const int b = blockIdx.y;
     const int p0 = blockIdx.x * px_per_block, p1 = min(p0 + px_per_block, hw);
@@ -686,6 +748,12 @@ __global__ __launch_bounds__(256) void t_nc_sums(const float* z, int hw, int C, 
                 s += red[0][j * C + c];
                 q += red[1][j * C + c];
             }
+        }
+        if (DET) {
+            const size_t o = (size_t)blockIdx.x * 2 * gridDim.y * C + (size_t)b * C + c;
+            S[o] = s;
+            Q[o] = q;
+            continue;
         }
         atomicAdd(S + (size_t)b * C + c, s);
         atomicAdd(Q + (size_t)b * C + c, q);
@@ -874,6 +942,8 @@ inline void launch_t_norm_fwd(const TNorm& a, const float* z, float* y, hipStrea
 
 // backward reductions, per (sample, channel) over the plane:
 //   A = sum dpre * v (dscale), B = sum dpre (dshift), Cc = sum dbn * xhat, Dd = sum dbn,  dbn = dpre * (1 + scale)
+// DET: as t_nc_sums -- slabs of (A | B | Cc | Dd), 4 n C doubles apart
+template <bool DET>
 __global__ __launch_bounds__(256) void t_norm_bwd_sums(TNorm a, const float* z, const float* dy, int px_per_block, double* A, double* B,
                                                        double* Cc, double* Dd) {
     const int b = blockIdx.y;
@@ -910,6 +980,14 @@ __global__ __launch_bounds__(256) void t_norm_bwd_sums(TNorm a, const float* z, 
                 scx += red[2][j * a.C + c];
                 sd += red[3][j * a.C + c];
             }
+        }
+        if (DET) {
+            const size_t o = (size_t)blockIdx.x * 4 * gridDim.y * a.C + (size_t)b * a.C + c;
+            A[o] = sa;
+            B[o] = sb;
+            Cc[o] = scx;
+            Dd[o] = sd;
+            continue;
         }
         atomicAdd(A + (size_t)b * a.C + c, sa);
         atomicAdd(B + (size_t)b * a.C + c, sb);
@@ -1162,6 +1240,30 @@ __global__ __launch_bounds__(256) void t_bias_grad_rows(const float* d, long lon
         }
     }
 }
+// deterministic mode, any channel count: the layout of t_bias_grad_rows (256 / C pixel groups per workgroup, threads past them idle), the
+// groups meet in LDS in index order and the workgroup's sums go to slab blockIdx.x of the workspace (C floats per slab)
+__global__ __launch_bounds__(256) void t_bias_grad_slab(const float* d, long long pixels, int C, int rows_per_block, float* ws) {
+    __shared__ float red[256];
+    const long long p0 = (long long)blockIdx.x * rows_per_block, p1 = p0 + rows_per_block < pixels ? p0 + rows_per_block : pixels;
+    if (C <= 256) {
+        const int c = threadIdx.x % C, sub = threadIdx.x / C, step = 256 / C;
+        float s = 0.0f;
+        if (sub < step)
+            for (long long p = p0 + sub; p < p1; p += step) s += d[p * C + c];
+        red[threadIdx.x] = s;
+        __syncthreads();
+        if (sub == 0) {
+            for (int k = 1; k < step; ++k) s += red[k * C + c];
+            ws[(size_t)blockIdx.x * C + c] = s;
+        }
+    } else {
+        for (int c = threadIdx.x; c < C; c += 256) {
+            float s = 0.0f;
+            for (long long p = p0; p < p1; ++p) s += d[p * C + c];
+            ws[(size_t)blockIdx.x * C + c] = s;
+        }
+    }
+}
 // d(mean criterion)/d pred * scale: kind 0 L1 (sign), 1 MSE, 2 smooth-L1 (beta 1)
 __global__ void t_criterion_grad(const float* pred, const float* target, long long n, int kind, float scale, float* d) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1237,17 +1339,37 @@ void tfree(dyf_engine* e, std::vector<void*>& owner) {  // back to the pool (tra
     }
 }
 
-void launch_bias_grad(const float* d, long long pixels, int C, float* db, hipStream_t st) {
-    const long long total = pixels * C, per = std::max<long long>(4096, (total + 1023) / 1024);
-    hipLaunchKernelGGL(t_bias_grad, dim3((unsigned)((total + per - 1) / per)), dim3(256), (size_t)C * sizeof(float), st, d, pixels, C, per, db);
-}
-
 constexpr size_t TRAIN_SPLITK_FLOATS = (size_t)16 << 20;  // 64 MB: 512 tiles x 128 x 64 partial sums and change
 float* splitk_ws(dyf_engine* e) {
     if (e->f32_forward) return (float*)e->f32_arena;  // a sampling forward: the head of its arena (nothing is allocated inside a forward)
     TrainState* ts = e->train;
     if (ts && !ts->splitk_ws && talloc(e, ts->ws_owned, &ts->splitk_ws, TRAIN_SPLITK_FLOATS, false) != DYF_OK) ts->splitk_ws = nullptr;
     return ts ? ts->splitk_ws : nullptr;
+}
+
+// db[c] += sum_p d[p][c]: the coalesced-rows form where the channel count allows, the LDS sweep otherwise; deterministic mode: slabs
+dyf_status launch_bias_grad(dyf_engine* e, const float* d, long long pixels, int C, float* db, hipStream_t st) {
+    const int rpb = (int)std::max<long long>(64, (pixels + 1023) / 1024);
+    if (train_det()) {
+        float* ws = splitk_ws(e);
+        if (!ws || (size_t)C > TRAIN_SPLITK_FLOATS) return fail(e, DYF_ERR_STATE, "deterministic bias gradient: no workspace");
+        const long long max_slabs = (long long)(TRAIN_SPLITK_FLOATS / (size_t)C);
+        const long long rows = std::max<long long>(rpb, (pixels + max_slabs - 1) / max_slabs);
+        if (rows > 0x7fffffffll) return fail(e, DYF_ERR_UNSUPPORTED, "deterministic bias gradient: tensor too large");
+        const int slabs = (int)((pixels + rows - 1) / rows);
+        dyf_form_note("t_bias_grad:det", 0);
+        hipLaunchKernelGGL(t_bias_grad_slab, dim3((unsigned)slabs), dim3(256), 0, st, d, pixels, C, (int)rows, ws);
+        det_reduce(ws, slabs, C, C, db, st);
+    } else if (256 % C == 0 || C % 256 == 0) {
+        dyf_form_note("t_bias_grad_rows:atomic", 0);
+        hipLaunchKernelGGL(t_bias_grad_rows, dim3((unsigned)((pixels + rpb - 1) / rpb)), dim3(256), 0, st, d, pixels, C, rpb, db);
+    } else {
+        const long long total = pixels * C, per = std::max<long long>(4096, (total + 1023) / 1024);
+        dyf_form_note("t_bias_grad:atomic", 0);
+        hipLaunchKernelGGL(t_bias_grad, dim3((unsigned)((total + per - 1) / per)), dim3(256), (size_t)C * sizeof(float), st, d, pixels, C, per, db);
+    }
+    TK(hipGetLastError());
+    return DYF_OK;
 }
 
 // DYF_TRAIN_MFMA=0 keeps the plain VALU kernels (A/B and a second implementation for the tests)
@@ -1315,32 +1437,47 @@ dyf_status conv_dgrad(dyf_engine* e, const TConv& g, const float* dz, const floa
 }
 dyf_status conv_wgrad(dyf_engine* e, const TConv& g, const float* dz, const float* x, float* dw, float* db, hipStream_t st) {
     const long long M = (long long)g.n * g.ho * g.wo;
-    if (train_mfma() && tgemm_conv_wgrad(g, dz, x, dw, st)) {
-        if (db) {
-            if (256 % g.cout == 0 || g.cout % 256 == 0) {
-                const int rpb = (int)std::max<long long>(64, (M + 1023) / 1024);
-                hipLaunchKernelGGL(t_bias_grad_rows, dim3((unsigned)((M + rpb - 1) / rpb)), dim3(256), 0, st, dz, M, g.cout, rpb, db);
-            } else {
-                launch_bias_grad(dz, M, g.cout, db, st);
-            }
-        }
+    const bool det = train_det();
+    float* ws = det ? splitk_ws(e) : nullptr;   // the slabs of the deterministic forms
+    if (det && !ws) return fail(e, DYF_ERR_STATE, "deterministic weight gradient: no workspace");
+    if (train_mfma() && tgemm_conv_wgrad(g, dz, x, dw, ws, TRAIN_SPLITK_FLOATS, st)) {
         TK(hipGetLastError());
-        return DYF_OK;
+        return db ? launch_bias_grad(e, dz, M, g.cout, db, st) : DYF_OK;
     }
     const bool small = dyf_form_int("DYF_TRAIN_SMALLC", 1) != 0;
-    if (small && g.cout % 64 == 0 && M >= 4096 && g.wo % 2 == 0 && g.k * g.k * g.cin + 1 <= 128 && g.cin <= 8 &&
+    const int nacc = g.k * g.k * g.cin;
+    if (small && g.cout % 64 == 0 && M >= 4096 && g.wo % 2 == 0 && nacc + 1 <= 128 && g.cin <= 8 &&
         dyf_form_int("DYF_TRAIN_SMALLC_MFMA", 1) != 0) {  // read per call: tests run both forms
         const long long pairs = M / 2;
-        const int ppw = (int)std::max<long long>(64, (pairs + 2047) / 2048);  // ~2 048 waves per 64-channel block
+        int ppw = (int)std::max<long long>(64, (pairs + 2047) / 2048);  // ~2 048 waves per 64-channel block
+        const size_t slab = (size_t)g.cout * nacc + g.cout;
+        // deterministic mode: one slab per wave -- at most 512 of them, and as many as the workspace holds
+        const long long max_waves = det ? std::min<long long>(512, (long long)(TRAIN_SPLITK_FLOATS / slab)) : 0;
+        if (det && max_waves >= 4) ppw = (int)std::max<long long>(ppw, (pairs + 4 * (max_waves / 4) - 1) / (4 * (max_waves / 4)));
         const dim3 grid((unsigned)((pairs + 4ll * ppw - 1) / (4ll * ppw)), (unsigned)(g.cout / 64));
-        if (g.k * g.k * g.cin + 1 <= 64)
-            hipLaunchKernelGGL(t_conv_wgrad_smallc_mfma<2>, grid, dim3(256), 0, st, g, dz, x, dw, db, ppw);
-        else
-            hipLaunchKernelGGL(t_conv_wgrad_smallc_mfma<4>, grid, dim3(256), 0, st, g, dz, x, dw, db, ppw);
-        TK(hipGetLastError());
-        return DYF_OK;
+        if (det && max_waves >= 4) {
+            dyf_form_note("t_conv_wgrad_smallc_mfma:det", g.n);
+            float* wsb = ws + (size_t)g.cout * nacc;
+            if (nacc + 1 <= 64)
+                hipLaunchKernelGGL((t_conv_wgrad_smallc_mfma<2, true>), grid, dim3(256), 0, st, g, dz, x, ws, wsb, ppw);
+            else
+                hipLaunchKernelGGL((t_conv_wgrad_smallc_mfma<4, true>), grid, dim3(256), 0, st, g, dz, x, ws, wsb, ppw);
+            det_reduce(ws, (int)grid.x * 4, (long long)slab, (long long)g.cout * nacc, dw, st);
+            if (db) det_reduce(wsb, (int)grid.x * 4, (long long)slab, g.cout, db, st);
+            TK(hipGetLastError());
+            return DYF_OK;
+        }
+        if (!det) {
+            dyf_form_note("t_conv_wgrad_smallc_mfma:atomic", g.n);
+            if (nacc + 1 <= 64)
+                hipLaunchKernelGGL(t_conv_wgrad_smallc_mfma<2>, grid, dim3(256), 0, st, g, dz, x, dw, db, ppw);
+            else
+                hipLaunchKernelGGL(t_conv_wgrad_smallc_mfma<4>, grid, dim3(256), 0, st, g, dz, x, dw, db, ppw);
+            TK(hipGetLastError());
+            return DYF_OK;
+        }
     }
-    if (small && g.cout % 64 == 0 && M >= 4096) {
+    if (!det && small && g.cout % 64 == 0 && M >= 4096) {  // (deterministic mode: the tiled kernel below takes these shapes)
         const int cob = g.cout / 64;
         const long long blocks = std::max<long long>(1, std::min<long long>(M / 512, 1024 / cob));  // >= 512 pixels per workgroup
         const int ppb = (int)((M + blocks - 1) / blocks);
@@ -1352,15 +1489,33 @@ dyf_status conv_wgrad(dyf_engine* e, const TConv& g, const float* dz, const floa
         SMALLC(7, 1) SMALLC(7, 2)  // the ResNet-UNet's 7 x 7 init conv on 1-2 input channels (98 sums per lane)
 #undef SMALLC
         if (launched) {
+            dyf_form_note("t_conv_wgrad_smallc:atomic", g.n);
             TK(hipGetLastError());
             return DYF_OK;
         }
     }
     const int tiles = g.k * g.k * ((g.cout + 15) / 16) * ((g.cin + 15) / 16);
     long long slices = std::max<long long>(1, std::min<long long>((M + 255) / 256, (4096 + tiles - 1) / tiles));
-    const int ppb = (int)(((M + slices - 1) / slices + 15) / 16 * 16);
+    const size_t slab = (size_t)g.cout * nacc + g.cout;
+    if (det) slices = std::max<long long>(1, std::min<long long>(slices, (long long)(TRAIN_SPLITK_FLOATS / slab)));
+    const long long ppl = ((M + slices - 1) / slices + 15) / 16 * 16;
+    if (ppl > 0x7fffffffll) return fail(e, DYF_ERR_UNSUPPORTED, "weight gradient: too many pixels per slice");
+    const int ppb = (int)ppl;
     slices = (M + ppb - 1) / ppb;
-    hipLaunchKernelGGL(t_conv_wgrad, dim3((unsigned)(tiles * slices)), dim3(256), 0, st, g, dz, x, dw, db, ppb);
+    if (det) {
+        dyf_form_note("t_conv_wgrad:det", g.n);
+        if (slices > 1) {
+            float* wsb = ws + (size_t)g.cout * nacc;
+            hipLaunchKernelGGL(t_conv_wgrad<true>, dim3((unsigned)(tiles * slices)), dim3(256), 0, st, g, dz, x, ws, db ? wsb : (float*)nullptr, ppb);
+            det_reduce(ws, (int)slices, (long long)slab, (long long)g.cout * nacc, dw, st);
+            if (db) det_reduce(wsb, (int)slices, (long long)slab, g.cout, db, st);
+        } else {
+            hipLaunchKernelGGL(t_conv_wgrad<true>, dim3((unsigned)tiles), dim3(256), 0, st, g, dz, x, dw, db, ppb);
+        }
+    } else {
+        dyf_form_note("t_conv_wgrad:atomic", g.n);
+        hipLaunchKernelGGL(t_conv_wgrad<false>, dim3((unsigned)(tiles * slices)), dim3(256), 0, st, g, dz, x, dw, db, ppb);
+    }
     TK(hipGetLastError());
     return DYF_OK;
 }
@@ -1440,6 +1595,13 @@ dyf_status dyf_train_set_precision(dyf_engine* e, int32_t bits) {
 }
 int32_t dyf_train_precision(const dyf_engine* e) { return e ? e->train_precision : -1; }
 
+dyf_status dyf_train_set_deterministic(dyf_engine* e, int32_t on) {
+    if (!e || (on != 0 && on != 1)) return fail(e, DYF_ERR_INVALID_ARGUMENT, "dyf_train_set_deterministic: on must be 0 or 1");
+    e->train_deterministic = on;
+    return DYF_OK;
+}
+int32_t dyf_train_deterministic(const dyf_engine* e) { return e ? e->train_deterministic : -1; }
+
 }  // extern "C"
 
 namespace dyf {
@@ -1480,6 +1642,7 @@ dyf_status f32_net_forward(dyf_engine* e, int which, const Source* srcs, int nsr
         return sc_f32_forward(e, which, srcs, nsrc, nb, o, out_dev, st);
     }
     const TrainPrecisionScope precision(32);  // fp32 operands whatever dyf_train_set_precision says
+    const TrainDetScope det(0);               // and the default kernel forms whatever dyf_train_set_deterministic says
     struct Active {  // splitk_ws() hands out the arena's head while this forward is being launched
         dyf_engine* e;
         explicit Active(dyf_engine* x) : e(x) { e->f32_forward = true; }
@@ -1525,6 +1688,7 @@ dyf_status dyf_train_forward(dyf_engine* e, int32_t which, int32_t slot, const f
     if (!e || which < 0 || which > 1 || slot < 0 || slot > 3 || !inputs_dev || !out_dev || nb < 1)
         return fail(e, DYF_ERR_INVALID_ARGUMENT, "dyf_train_forward: bad arguments");
     const TrainPrecisionScope precision(e->train_precision);
+    const TrainDetScope det(e->train_deterministic);
     if (e->net[which].sc) return fail(e, DYF_ERR_UNSUPPORTED, "training step: arch unet_simple and unet (SimpleConvNet is the CPU plumbing config)");
     TK(hipSetDevice(e->cfg.device));
     return train_forward(e, which, slot, inputs_dev, time_dev, cond_dev, out_dev, nb, flags, (hipStream_t)stream);
@@ -1803,13 +1967,13 @@ dyf_status dyf_train_conv_check(dyf_engine* e, int32_t kind, int32_t n, int32_t 
         } else {
             // kind 3: whatever conv_wgrad picks for the shape (the small-channel forms sit behind it, not behind tgemm_conv_wgrad)
             if (kind == 3) { CK(conv_wgrad(e, g, z, x, got, nullptr, st)); took = true; }
-            else took = tgemm_conv_wgrad(g, z, x, got, st);
+            else took = tgemm_conv_wgrad(g, z, x, got, splitk_ws(e), TRAIN_SPLITK_FLOATS, st);
             const long long M = (long long)n * ho * wo;
             const int tiles = k * k * ((cout + 15) / 16) * ((cin + 15) / 16);
             long long slices = std::max<long long>(1, std::min<long long>((M + 255) / 256, (4096 + tiles - 1) / tiles));
             const int ppb = (int)(((M + slices - 1) / slices + 15) / 16 * 16);
             slices = (M + ppb - 1) / ppb;
-            hipLaunchKernelGGL(t_conv_wgrad, dim3((unsigned)(tiles * slices)), dim3(256), 0, st, g, z, x, ref, (float*)nullptr, ppb);
+            hipLaunchKernelGGL(t_conv_wgrad<false>, dim3((unsigned)(tiles * slices)), dim3(256), 0, st, g, z, x, ref, (float*)nullptr, ppb);
         }
         TK(hipGetLastError());
         res[2] = took ? 1.0f : 0.0f;

@@ -9,7 +9,8 @@
 //   forward   M = output pixels, N = cout, K = (tap, ci):  A = x at the tap's shifted pixel (zero outside), B = wt[tap][ci][co]
 //   dgrad     M = input pixels,  N = cin,  K = (tap, co):  A = dz at ((iy + p - ky) / s, ..) where divisible, B = w[co][tap][ci]
 //   wgrad     M = cout, N = cin, K = output pixels (one tap per workgroup, pixel range split over workgroups, merged with
-//             atomics like the kernel it replaces):  A = dz[pixel][co], B = x at the tap's shifted pixel
+//             atomics like the kernel it replaces; in the deterministic mode, TG_WGRAD_DET, through one slab of the workspace per
+//             pixel range and t_det_reduce):  A = dz[pixel][co], B = x at the tap's shifted pixel
 // Both operand tiles sit in LDS as [row][16 k] with k permuted to [k even | k odd] (a lane of the 32x32x2 MFMA needs
 // k = 2j + (lane >> 5) for j = 0..7: two ds_read_b128), rows 20 floats apart (conflict-free for the b128 lane groups).
 // Global loads are 16-byte vectors along the contiguous axis of each operand (channels), issued for stage s + 1 before the
@@ -24,7 +25,7 @@ typedef __attribute__((ext_vector_type(16))) float f32x16;
 namespace {
 
 constexpr int GM = 128, GN = 64, GK = 16, LDR = 20;
-enum { TG_FWD = 0, TG_DGRAD = 1, TG_WGRAD = 2 };
+enum { TG_FWD = 0, TG_DGRAD = 1, TG_WGRAD = 2, TG_WGRAD_DET = 3 };  // _DET: the weight gradient of the deterministic mode (slabs, no atomics)
 
 template <int MODE>
 __global__ __launch_bounds__(256) void t_gemm_mfma(dyf::TConv g, const float* __restrict__ Ap, const float* __restrict__ Bp,
@@ -32,6 +33,7 @@ __global__ __launch_bounds__(256) void t_gemm_mfma(dyf::TConv g, const float* __
 #if defined(__HIP_DEVICE_COMPILE__)
     __shared__ __attribute__((aligned(16))) float As[2][GM * LDR];
     __shared__ __attribute__((aligned(16))) float Bs[2][GN * LDR];
+    constexpr bool WG = MODE == TG_WGRAD || MODE == TG_WGRAD_DET;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l31 = lane & 31, hi = lane >> 5;
     const int wm = wave >> 1, wn = wave & 1;
@@ -43,7 +45,7 @@ __global__ __launch_bounds__(256) void t_gemm_mfma(dyf::TConv g, const float* __
     int tap = 0;
     long long kbeg = 0, kend = 0;  // wgrad: pixel range of this workgroup
     int nstage, st0 = 0;  // stages [st0, st0 + nstage) of the K axis
-    if (MODE == TG_WGRAD) {
+    if (WG) {
         tap = blockIdx.z % taps;
         kbeg = (long long)(blockIdx.z / taps) * split_len;
         kend = kbeg + split_len < opix ? kbeg + split_len : opix;
@@ -67,7 +69,7 @@ __global__ __launch_bounds__(256) void t_gemm_mfma(dyf::TConv g, const float* __
         const int s = tid + 256 * i;
         a_b[i] = a_y[i] = a_x[i] = 0;
         a_ok[i] = false;
-        if (MODE != TG_WGRAD) {
+        if (!WG) {
             const long long m = (long long)tm * GM + (s >> 2);
             a_ok[i] = m < M;
             const int pw = MODE == TG_FWD ? g.wo : g.w, ph = MODE == TG_FWD ? g.ho : g.h;
@@ -83,7 +85,7 @@ __global__ __launch_bounds__(256) void t_gemm_mfma(dyf::TConv g, const float* __
     // wgrad: (ox, oy, b) of this thread's B pixel, carried from stage to stage (the stages of a launch are loaded in order) instead
     // of three 64-bit divisions per stage
     int w_ox = 0, w_oy = 0, w_b = 0;
-    if (MODE == TG_WGRAD) {
+    if (WG) {
         const unsigned pix0 = (unsigned)(kbeg + b_k);
         w_ox = (int)(pix0 % (unsigned)g.wo);
         w_oy = (int)((pix0 / (unsigned)g.wo) % (unsigned)g.ho);
@@ -92,7 +94,7 @@ __global__ __launch_bounds__(256) void t_gemm_mfma(dyf::TConv g, const float* __
 
     float4 ra[2], rb;
     auto load = [&](int stage) {
-        if (MODE != TG_WGRAD) {
+        if (!WG) {
             const int k0 = stage * GK;
             const int tp = k0 / CK, c0 = k0 - tp * CK;
             const int ky = tp / g.k, kx = tp - ky * g.k;
@@ -143,7 +145,7 @@ __global__ __launch_bounds__(256) void t_gemm_mfma(dyf::TConv g, const float* __
     };
     // element k of a row lives at (k & 1) * 8 + (k >> 1)
     auto store = [&](int buf) {
-        if (MODE != TG_WGRAD) {
+        if (!WG) {
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
                 const int s = tid + 256 * i;
@@ -199,15 +201,18 @@ __global__ __launch_bounds__(256) void t_gemm_mfma(dyf::TConv g, const float* __
 
     // ---- epilogue: lane (l31, hi), register r of accumulator i: row wm*64 + i*32 + 8*(r/4) + 4*hi + r%4, column wn*32 + l31
     const int n = tn * GN + wn * 32 + l31;
-    const float bv = (MODE != TG_WGRAD && bias) ? bias[n] : 0.0f;
+    const float bv = (!WG && bias) ? bias[n] : 0.0f;
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const long long m = (long long)tm * GM + wm * 64 + i * 32 + 8 * (r >> 2) + 4 * hi + (r & 3);
             if (m >= M) continue;
-            if (MODE == TG_WGRAD) {
-                atomicAdd(Cp + ((size_t)m * taps + tap) * g.cin + n, acc[i][r]);
+            if (WG) {
+                const size_t o = ((size_t)m * taps + tap) * g.cin + n;
+                if (MODE == TG_WGRAD) atomicAdd(Cp + o, acc[i][r]);
+                else if ((int)gridDim.z == taps) Cp[o] += acc[i][r];  // one pixel range: Cp = dw, this workgroup owns the element
+                else Cp[(size_t)(blockIdx.z / taps) * g.cout * taps * g.cin + o] = acc[i][r];  // Cp = workspace, slab = pixel range
             } else {
                 const int NC = MODE == TG_FWD ? g.cout : g.cin;
                 // split-K: raw partial sums to Cp[split][m][n] (the workspace); t_splitk_finish adds them in split order
@@ -233,6 +238,7 @@ __global__ __launch_bounds__(256) void t_gemm_mfma16(dyf::TConv g, const float* 
 #if defined(__HIP_DEVICE_COMPILE__)
     __shared__ __attribute__((aligned(16))) t16_t As[2][GM * LDR16];
     __shared__ __attribute__((aligned(16))) t16_t Bs[2][GN * LDR16];
+    constexpr bool WG = MODE == TG_WGRAD || MODE == TG_WGRAD_DET;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l31 = lane & 31, hi = lane >> 5;
     const int wm = wave >> 1, wn = wave & 1;
@@ -248,7 +254,7 @@ __global__ __launch_bounds__(256) void t_gemm_mfma16(dyf::TConv g, const float* 
     int tap = 0;
     long long kbeg = 0, kend = 0;
     int nstage, st0 = 0;
-    if (MODE == TG_WGRAD) {
+    if (WG) {
         tap = blockIdx.z % taps;
         kbeg = (long long)(blockIdx.z / taps) * split_len;
         kend = kbeg + split_len < opix ? kbeg + split_len : opix;
@@ -266,7 +272,7 @@ __global__ __launch_bounds__(256) void t_gemm_mfma16(dyf::TConv g, const float* 
         const int s = tid + 256 * i;
         a_b[i] = a_y[i] = a_x[i] = 0;
         a_ok[i] = false;
-        if (MODE != TG_WGRAD) {
+        if (!WG) {
             const long long m = (long long)tm * GM + (s >> 3);
             a_ok[i] = m < M;
             const bool pm = MODE == TG_DGRAD && pmode;
@@ -280,7 +286,7 @@ __global__ __launch_bounds__(256) void t_gemm_mfma16(dyf::TConv g, const float* 
     }
     const int sh = (g.s & (g.s - 1)) == 0 ? __builtin_ctz((unsigned)g.s) : -1;  // (as in t_gemm_mfma)
     int w_ox[2] = {0, 0}, w_oy[2] = {0, 0}, w_b[2] = {0, 0};
-    if (MODE == TG_WGRAD) {
+    if (WG) {
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             const unsigned pix0 = (unsigned)(kbeg + ((tid + 256 * i) >> 4));
@@ -291,7 +297,7 @@ __global__ __launch_bounds__(256) void t_gemm_mfma16(dyf::TConv g, const float* 
     }
     float4 ra[4], rb[2];
     auto load = [&](int stage) {
-        if (MODE != TG_WGRAD) {
+        if (!WG) {
             const int k0 = stage * GK16;
             const int tq = k0 / CK, c0 = k0 - tq * CK;
             const bool pm = MODE == TG_DGRAD && pmode;
@@ -351,7 +357,7 @@ __global__ __launch_bounds__(256) void t_gemm_mfma16(dyf::TConv g, const float* 
         }
     };
     auto store = [&](int buf) {
-        if (MODE != TG_WGRAD) {
+        if (!WG) {
 #pragma unroll
             for (int i = 0; i < 4; ++i) {  // 4 consecutive k of one row: one 8-byte store
                 const int s = tid + 256 * i;
@@ -400,15 +406,18 @@ __global__ __launch_bounds__(256) void t_gemm_mfma16(dyf::TConv g, const float* 
         __syncthreads();
     }
     const int n = tn * GN + wn * 32 + l31;
-    const float bv = (MODE != TG_WGRAD && bias) ? bias[n] : 0.0f;
+    const float bv = (!WG && bias) ? bias[n] : 0.0f;
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const long long m = (long long)tm * GM + wm * 64 + i * 32 + 8 * (r >> 2) + 4 * hi + (r & 3);
             if (m >= M) continue;
-            if (MODE == TG_WGRAD) {
-                atomicAdd(Cp + ((size_t)m * taps + tap) * g.cin + n, acc[i][r]);
+            if (WG) {
+                const size_t o = ((size_t)m * taps + tap) * g.cin + n;
+                if (MODE == TG_WGRAD) atomicAdd(Cp + o, acc[i][r]);
+                else if ((int)gridDim.z == taps) Cp[o] += acc[i][r];  // one pixel range: Cp = dw, this workgroup owns the element
+                else Cp[(size_t)(blockIdx.z / taps) * g.cout * taps * g.cin + o] = acc[i][r];  // Cp = workspace, slab = pixel range
             } else {
                 const int NC = MODE == TG_FWD ? g.cout : g.cin;
                 if (MODE == TG_DGRAD && pmode) {
@@ -431,9 +440,27 @@ __global__ void t_splitk_finish(const float* ws, int splits, long long MN, int N
     y[i] = s;
 }
 
+// deterministic mode: dst[i] += the slabs' partial sums, in slab order
+template <typename T>
+__global__ void t_det_reduce(const T* ws, int splits, long long stride, long long n, T* dst) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    T s = ws[i];
+    for (int z = 1; z < splits; ++z) s += ws[(size_t)z * stride + i];
+    dst[i] += s;
+}
+
 }  // namespace
 
 namespace dyf {
+
+thread_local int g_train_det = 0;
+void det_reduce(const float* ws, int splits, long long stride, long long n, float* dst, hipStream_t st) {
+    hipLaunchKernelGGL(t_det_reduce<float>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, ws, splits, stride, n, dst);
+}
+void det_reduce(const double* ws, int splits, long long stride, long long n, double* dst, hipStream_t st) {
+    hipLaunchKernelGGL(t_det_reduce<double>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, ws, splits, stride, n, dst);
+}
 
 // 16-bit operands: the training convs round their operands to bf16 (both builds: train_internal.h) while staging them (t_gemm_mfma16,
 // train_halo16.hip) -- chosen per engine by dyf_train_set_precision(16) (the reference's `trainer.precision=16`), or, for engines
@@ -506,18 +533,34 @@ bool tgemm_conv_dgrad(const TConv& g, const float* dz, const float* w, const flo
 }
 
 // dw += ... (the caller accumulates the bias gradient separately)
-bool tgemm_conv_wgrad(const TConv& g, const float* dz, const float* x, float* dw, hipStream_t st) {
+bool tgemm_conv_wgrad(const TConv& g, const float* dz, const float* x, float* dw, float* ws, size_t ws_floats, hipStream_t st) {
     if (g.cin % GN != 0 || g.cout % 4 != 0) return false;
     const long long pix = (long long)g.n * g.ho * g.wo;
     const int taps = g.k * g.k, mt = (g.cout + GM - 1) / GM, nt = g.cin / GN;
     // enough workgroups to fill the chip, at least 256 pixels per split
     long long splits = std::max<long long>(1, std::min<long long>((pix + 255) / 256, (2048 + (long long)mt * nt * taps - 1) / ((long long)mt * nt * taps)));
     const bool h16 = train_operands16();
-    if (h16 && thalo_wgrad3x3(g, dz, x, dw, st)) return true;
+    if (h16 && thalo_wgrad3x3(g, dz, x, dw, ws, ws_floats, st)) return true;
     const int gk = h16 ? GK16 : GK;
+    const bool det = train_det();
+    const size_t slab = (size_t)g.cout * taps * g.cin;
+    // deterministic mode: as many pixel ranges as slabs fit the workspace, down to one (then every element of dw has one owner)
+    if (det) splits = std::min<long long>(splits, ws ? (long long)(ws_floats / slab) : 1);
+    if (splits < 1) splits = 1;
     int len = (int)(((pix + splits - 1) / splits + gk - 1) / gk * gk);
     splits = (pix + len - 1) / len;
     if ((long long)taps * splits > 65535) return false;
+    if (det) {
+        float* C = splits > 1 ? ws : dw;
+        dyf_form_note(h16 ? "t_gemm_mfma16<wgrad>:det" : "t_gemm_mfma<wgrad>:det", g.n);
+        if (h16)
+            hipLaunchKernelGGL(t_gemm_mfma16<TG_WGRAD_DET>, dim3(mt, nt, (unsigned)(taps * splits)), dim3(256), 0, st, g, dz, x, nullptr, C, len, 0);
+        else
+            hipLaunchKernelGGL(t_gemm_mfma<TG_WGRAD_DET>, dim3(mt, nt, (unsigned)(taps * splits)), dim3(256), 0, st, g, dz, x, nullptr, C, len);
+        if (splits > 1) det_reduce(ws, (int)splits, (long long)slab, (long long)slab, dw, st);
+        return true;
+    }
+    dyf_form_note(h16 ? "t_gemm_mfma16<wgrad>:atomic" : "t_gemm_mfma<wgrad>:atomic", g.n);
     if (h16)
         hipLaunchKernelGGL(t_gemm_mfma16<TG_WGRAD>, dim3(mt, nt, (unsigned)(taps * splits)), dim3(256), 0, st, g, dz, x, nullptr, dw, len, 0);
     else

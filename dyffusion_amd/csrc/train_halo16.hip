@@ -202,6 +202,8 @@ __global__ __launch_bounds__(256, BN == 64 ? 2 : 1) void t_halo3x3_16(int h, int
 constexpr int DZ_PITCH = 256;   // [co][8 rows x 16 columns] 16-bit: 16 chunks of 8 pixels
 constexpr int XT_PITCH = 768;   // [ci][10 halo rows x 4 blocks of 8 columns (x0 - 8 ... x0 + 23)]: 40 chunks, pitch 48 (swizzle room)
 
+// (DET: the deterministic mode's instantiation -- every tile range writes its own slab of dw-shaped partial sums, no atomics)
+template <bool DET>
 __global__ __launch_bounds__(256, 2) void t_wgrad3x3_16(int h, int w, int cin, int cout, const float* __restrict__ dz,
                                                         const float* __restrict__ x, float* __restrict__ dw, int tiles_x,
                                                         int tiles_per_img, int tiles_total, int tiles_per_wg) {
@@ -309,7 +311,10 @@ __global__ __launch_bounds__(256, 2) void t_wgrad3x3_16(int h, int w, int cin, i
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int co = co0 + wm * 32 + 8 * (r >> 2) + 4 * hi + (r & 3);
-            atomicAdd(dw + ((size_t)co * 9 + tap) * cin + ci, acc[tap][r]);
+            const size_t o = ((size_t)co * 9 + tap) * cin + ci;
+            if (!DET) atomicAdd(dw + o, acc[tap][r]);
+            else if (gridDim.x == 1) dw[o] += acc[tap][r];  // one tile range: this workgroup owns the element
+            else dw[(size_t)blockIdx.x * cout * 9 * cin + o] = acc[tap][r];  // dw = workspace, slab = tile range
         }
 #endif
 }
@@ -354,7 +359,7 @@ bool thalo_conv3x3(const TConv& g, int mode, const float* A, const float* W, con
 }
 
 // dw += the weight gradient (all nine taps per workgroup)
-bool thalo_wgrad3x3(const TConv& g, const float* dz, const float* x, float* dw, hipStream_t st) {
+bool thalo_wgrad3x3(const TConv& g, const float* dz, const float* x, float* dw, float* ws, size_t ws_floats, hipStream_t st) {
     if (!halo16_enabled() || g.k != 3 || g.s != 1 || g.p != 1 || g.ho != g.h || g.wo != g.w) return false;
     if (g.cin % 64 != 0 || g.cout % 64 != 0) return false;
     const int tiles_x = (g.w + TW - 1) / TW, tiles_per_img = tiles_x * ((g.h + TH - 1) / TH);
@@ -365,10 +370,22 @@ bool thalo_wgrad3x3(const TConv& g, const float* dz, const float* x, float* dw, 
     // more than they balance -- us per launch with 256 / 512 / 1 024 / 2 048 workgroups: 16 x 256^2 x 128 -> 64 439 / 314 / 383 / 430,
     // 64 x 60^2 x 128 -> 128 201 / 173 / 234 / 327, 32 x 64^2 x 256 -> 256 361 / 250 / 298 / 379
     long long splits = std::max<long long>(1, std::min<long long>(tiles / 4, (512 + pairs - 1) / pairs));
+    const bool det = train_det();
+    const size_t slab = (size_t)g.cout * 9 * g.cin;
+    // deterministic mode: as many tile ranges as slabs fit the workspace, down to one (then every element of dw has one owner)
+    if (det) splits = std::max<long long>(1, std::min<long long>(splits, ws ? (long long)(ws_floats / slab) : 1));
     const int per = (int)((tiles + splits - 1) / splits);
     splits = (tiles + per - 1) / per;
     dyf_form_note("t_wgrad3x3_16", g.n);
-    hipLaunchKernelGGL(t_wgrad3x3_16, dim3((unsigned)splits, g.cout / 64, g.cin / 64), dim3(256), 0, st, g.h, g.w, g.cin, g.cout, dz, x, dw,
+    if (det) {
+        dyf_form_note("t_wgrad3x3_16:det", g.n);
+        hipLaunchKernelGGL(t_wgrad3x3_16<true>, dim3((unsigned)splits, g.cout / 64, g.cin / 64), dim3(256), 0, st, g.h, g.w, g.cin, g.cout, dz, x,
+                           splits > 1 ? ws : dw, tiles_x, tiles_per_img, (int)tiles, per);
+        if (splits > 1) det_reduce(ws, (int)splits, (long long)slab, (long long)slab, dw, st);
+        return true;
+    }
+    dyf_form_note("t_wgrad3x3_16:atomic", g.n);
+    hipLaunchKernelGGL(t_wgrad3x3_16<false>, dim3((unsigned)splits, g.cout / 64, g.cin / 64), dim3(256), 0, st, g.h, g.w, g.cin, g.cout, dz, x, dw,
                        tiles_x, tiles_per_img, (int)tiles, per);
     return true;
 }

@@ -134,16 +134,32 @@ struct TrainPrecisionScope {
     ~TrainPrecisionScope() { g_train_precision = prev; }
 };
 
+// Deterministic training mode for the calls of THIS thread: set by the training entry points from the engine's
+// dyf_train_set_deterministic (the reference's trainer.deterministic).  On: no launcher may merge a floating-point sum with atomics --
+// every cross-workgroup sum writes one slab of partial sums per contributor to the split-K workspace, and det_reduce adds the slabs in
+// index order to the destination (a second launch: no tickets, no waiting between workgroups).  Sampling never reads it (scope 0).
+extern thread_local int g_train_det;
+inline bool train_det() { return g_train_det != 0; }
+struct TrainDetScope {
+    int prev;
+    explicit TrainDetScope(int on) : prev(g_train_det) { g_train_det = on; }
+    ~TrainDetScope() { g_train_det = prev; }
+};
+// dst[i] += ws[0 * stride + i] + ws[1 * stride + i] + ... + ws[(splits - 1) * stride + i], i < n, summed in that order (train_gemm.hip)
+void det_reduce(const float* ws, int splits, long long stride, long long n, float* dst, hipStream_t st);
+void det_reduce(const double* ws, int splits, long long stride, long long n, double* dst, hipStream_t st);
+
 bool tgemm_conv_fwd(const TConv& g, const float* x, const float* wt, const float* bias, float* y, float* ws, size_t ws_floats,
                     hipStream_t st);
 bool tgemm_conv_dgrad(const TConv& g, const float* dz, const float* w, const float* bias, float* dx, float* ws, size_t ws_floats,
                       hipStream_t st);
-bool tgemm_conv_wgrad(const TConv& g, const float* dz, const float* x, float* dw, hipStream_t st);
+// (ws / ws_floats: the slabs of the deterministic mode; unused otherwise)
+bool tgemm_conv_wgrad(const TConv& g, const float* dz, const float* x, float* dw, float* ws, size_t ws_floats, hipStream_t st);
 
 // 3 x 3 / stride 1 / pad 1 layers with 16-bit operands, tile + halo staged once (train_halo16.hip); false: shape not covered.
 // mode 0: forward (A = x, W = wt[tap][ci][co]); mode 1: data gradient (A = dz, W = w[co][tap][ci]); ws receives the 16-bit weights
 bool thalo_conv3x3(const TConv& g, int mode, const float* A, const float* W, const float* bias, float* C, float* ws, size_t ws_floats,
                    hipStream_t st);
-bool thalo_wgrad3x3(const TConv& g, const float* dz, const float* x, float* dw, hipStream_t st);
+bool thalo_wgrad3x3(const TConv& g, const float* dz, const float* x, float* dw, float* ws, size_t ws_floats, hipStream_t st);
 
 }  // namespace dyf

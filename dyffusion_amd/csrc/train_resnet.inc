@@ -32,6 +32,7 @@ struct RT {                  // an activation of the recorded forward and (durin
 
 struct RTape {
     int net = -1, nb = 0, flags = 0;
+    int det = 0;                 // the deterministic mode the forward was recorded under: its backward runs under the same
     std::vector<void*> owned;
     std::deque<RT> ts;                                         // stable addresses
     std::vector<std::function<dyf_status()>> back;             // run in reverse
@@ -215,6 +216,25 @@ __global__ __launch_bounds__(256) void t_ln_bwd_g_rows(const float* x, const flo
     if (sub == 0) {
         for (int j = 1; j < nsub; ++j) a += red[j * C + c];
         atomicAdd(gg + c, (float)a);
+    }
+}
+// deterministic mode: the same sums per workgroup (any chunk of pixels), stored to slab blockIdx.x of the workspace (C floats per slab)
+__global__ __launch_bounds__(256) void t_ln_bwd_g_slab(const float* x, const float* dy, const float2* stats, int n, int hw, int C, RDrop dr, int chunk, float* ws) {
+    __shared__ double red[256];
+    const int c = threadIdx.x % C, sub = threadIdx.x / C, nsub = 256 / C;
+    const long long total = (long long)n * hw, i0 = (long long)blockIdx.x * chunk, i1 = i0 + chunk < total ? i0 + chunk : total;
+    double a = 0.0;
+    for (long long i = i0 + sub; i < i1; i += nsub) {
+        const int b = (int)(i / hw);
+        const uint32_t e = (uint32_t)((i - (long long)b * hw) * C + c);
+        const float2 st = stats[i];
+        a += (double)(dy[(size_t)i * C + c] * r_keep(dr, b, e) * (x[(size_t)i * C + c] - st.x) * st.y);
+    }
+    red[threadIdx.x] = a;
+    __syncthreads();
+    if (sub == 0) {
+        for (int j = 1; j < nsub; ++j) a += red[j * C + c];
+        ws[(size_t)blockIdx.x * C + c] = (float)a;
     }
 }
 __global__ __launch_bounds__(256) void t_ln_bwd_g(const float* x, const float* dy, const float2* stats, int n, int hw, int C, RDrop dr, float* gg) {
@@ -1020,6 +1040,22 @@ struct RCtx {
     }
     // does anything upstream of t take a gradient?  (the network input and what is resampled from it: only when the caller asked)
     bool wants(const dyf::RT* t) const { return t->need == 0 || (t->need == 1 && want_dinputs); }
+    // deterministic mode: pixels per workgroup of a norm's sum kernels -- the caller's rule, more where the slabs (slab_doubles each)
+    // of all pixel ranges would not fit the workspace
+    static int det_norm_ppb(int hw, int ppb, size_t slab_doubles) {
+        const long long max_slabs = std::max<long long>(1, (long long)(TRAIN_SPLITK_FLOATS / 2 / slab_doubles));
+        return (int)std::max<long long>(ppb, (hw + max_slabs - 1) / max_slabs);
+    }
+    // the adjoint of a resample: the scatter with atomics, or (deterministic mode) the gather
+    void resize_bwd(const float* dout, int h, int w, int C, int oh, int ow, int nearest, float* din) {
+        if (train_det()) {
+            dyf_form_note("t_resize_bwd:det", nb);
+            hipLaunchKernelGGL(t_resize_bwd_gather, dim3(nblk((long long)nb * h * w * C)), dim3(256), 0, st, dout, nb, h, w, C, oh, ow, nearest, din);
+        } else {
+            dyf_form_note("t_resize_bwd:atomic", nb);
+            hipLaunchKernelGGL(t_resize_bwd, dim3(nblk((long long)nb * oh * ow * C)), dim3(256), 0, st, dout, nb, h, w, C, oh, ow, nearest, din);
+        }
+    }
     double* stat_sums(size_t n) {  // n zeroed doubles; one stream orders the reuse (the statistics are final before the next norm's memset)
         if (n > sums_cap) {
             sums_cap = std::max(n, sums_hint);
@@ -1105,7 +1141,22 @@ struct RCtx {
         if (kind != 1) {
             S = stat_sums((size_t)nb * C * 2);
             Q = S + (size_t)nb * C;
-            hipLaunchKernelGGL(t_nc_sums, dim3((hw + ppb - 1) / ppb, nb), dim3(256), 0, st, z->p, hw, C, ppb, S, Q);
+            if (train_det()) {  // slabs of (S | Q) per pixel range, added in range order
+                double* ws = (double*)splitk_ws(e);
+                const int dppb = det_norm_ppb(hw, ppb, (size_t)nb * C * 2);
+                const int slabs = (hw + dppb - 1) / dppb;
+                if (!ws) err = DYF_ERR_STATE;
+                dyf_form_note("t_nc_sums:det", nb);
+                if (ws && slabs > 1) {
+                    hipLaunchKernelGGL(t_nc_sums<true>, dim3(slabs, nb), dim3(256), 0, st, z->p, hw, C, dppb, ws, ws + (size_t)nb * C);
+                    det_reduce(ws, slabs, (long long)nb * C * 2, (long long)nb * C * 2, S, st);
+                } else if (ws) {
+                    hipLaunchKernelGGL(t_nc_sums<true>, dim3(1, nb), dim3(256), 0, st, z->p, hw, C, dppb, S, Q);
+                }
+            } else {
+                dyf_form_note("t_nc_sums:atomic", nb);
+                hipLaunchKernelGGL(t_nc_sums<false>, dim3((hw + ppb - 1) / ppb, nb), dim3(256), 0, st, z->p, hw, C, ppb, S, Q);
+            }
         }
         hipLaunchKernelGGL(t_stats_finalize, dim3(nblk(std::max(nidx, C))), dim3(256), 0, st, kind, S, Q, nb, hw, C, G,
                            gn ? (float*)nullptr : P(name + ".running_mean").w, gn ? (float*)nullptr : P(name + ".running_var").w, mean, rstd);
@@ -1123,7 +1174,23 @@ struct RCtx {
             if (hipMemsetAsync(A, 0, (size_t)nb * C * 4 * sizeof(double), st) != hipSuccess) return DYF_ERR_HIP;
             float *S1 = (float*)(A + (size_t)nb * C * 4), *S2 = S1 + nS;
             float* dss = ss ? tbuf((size_t)nb * 2 * C) : nullptr;
-            hipLaunchKernelGGL(t_norm_bwd_sums, dim3((hw + ppb - 1) / ppb, nb), dim3(256), 0, st, a, z->p, y->g, ppb, A, B, Cc, Dd);
+            if (train_det()) {  // (as the forward's sums)
+                double* ws = (double*)splitk_ws(e);
+                const size_t nC = (size_t)nb * C;
+                const int dppb = det_norm_ppb(hw, ppb, nC * 4);
+                const int slabs = (hw + dppb - 1) / dppb;
+                if (!ws) return DYF_ERR_STATE;
+                dyf_form_note("t_norm_bwd_sums:det", nb);
+                if (slabs > 1) {
+                    hipLaunchKernelGGL(t_norm_bwd_sums<true>, dim3(slabs, nb), dim3(256), 0, st, a, z->p, y->g, dppb, ws, ws + nC, ws + 2 * nC, ws + 3 * nC);
+                    det_reduce(ws, slabs, (long long)nC * 4, (long long)nC * 4, A, st);
+                } else {
+                    hipLaunchKernelGGL(t_norm_bwd_sums<true>, dim3(1, nb), dim3(256), 0, st, a, z->p, y->g, dppb, A, B, Cc, Dd);
+                }
+            } else {
+                dyf_form_note("t_norm_bwd_sums:atomic", nb);
+                hipLaunchKernelGGL(t_norm_bwd_sums<false>, dim3((hw + ppb - 1) / ppb, nb), dim3(256), 0, st, a, z->p, y->g, ppb, A, B, Cc, Dd);
+            }
             // (running statistics: the norm is a fixed affine map, S1 = S2 = 0)
             hipLaunchKernelGGL(t_norm_bwd_combine, dim3(nblk(std::max(nb * C, nb * G))), dim3(256), 0, st, a, A, B, Cc, Dd,
                                param_grads ? P(name + ".weight").g : (float*)nullptr, param_grads ? P(name + ".bias").g : (float*)nullptr, dss, S1, S2,
@@ -1301,7 +1368,7 @@ struct RCtx {
         back([=]() -> dyf_status {
             if (!y->g) return DYF_OK;
             if (!up2) {
-                hipLaunchKernelGGL(t_resize_bwd, dim3(nblk((long long)y->n)), dim3(256), 0, st, y->g, nb, h, w, C, oh, ow, 0, grad(x));
+                resize_bwd(y->g, h, w, C, oh, ow, 0, grad(x));
                 return DYF_OK;
             }
             float *dx = tbuf(x->n), *dx2 = x2 ? tbuf(x2->n) : nullptr;  // the kernel writes every element of both
@@ -1320,7 +1387,7 @@ struct RCtx {
         hipLaunchKernelGGL(t_resize_fwd, dim3(nblk((long long)y->n)), dim3(256), 0, st, x->p, nb, h, w, C, oh, ow, nearest, y->p);
         back([=]() -> dyf_status {
             if (!y->g || !wants(x)) return DYF_OK;
-            hipLaunchKernelGGL(t_resize_bwd, dim3(nblk((long long)y->n)), dim3(256), 0, st, y->g, nb, h, w, C, oh, ow, nearest, grad(x));
+            resize_bwd(y->g, h, w, C, oh, ow, nearest, grad(x));
             return DYF_OK;
         });
         return dbg(y, "resize");
@@ -1338,7 +1405,8 @@ struct RCtx {
             if (param_grads) {
                 dyf_status r = conv_wgrad(e, g, x->p, y->g, qw.g, nullptr, st);
                 if (r != DYF_OK) return r;
-                launch_bias_grad(y->g, (long long)nb * 4 * h * w, C, P(name + ".bias").g, st);
+                r = launch_bias_grad(e, y->g, (long long)nb * 4 * h * w, C, P(name + ".bias").g, st);
+                if (r != DYF_OK) return r;
             }
             if (!wants(x)) return DYF_OK;
             float* dx = tbuf(x->n);
@@ -1358,11 +1426,22 @@ struct RCtx {
         back([=]() -> dyf_status {
             if (!y->g) return DYF_OK;
             if (param_grads) {
-                if (C <= 256 && 256 % C == 0)
+                if (C <= 256 && 256 % C == 0 && train_det()) {  // slabs of C sums per pixel chunk, added in chunk order
+                    float* ws = splitk_ws(e);
+                    if (!ws) return DYF_ERR_STATE;
+                    const long long total = (long long)nb * hw;
+                    const long long slabs0 = std::min<long long>(1024, (total + LN_GCHUNK - 1) / LN_GCHUNK);
+                    const int chunk = (int)((total + slabs0 - 1) / slabs0), slabs = (int)((total + chunk - 1) / chunk);
+                    dyf_form_note("t_ln_bwd_g_rows:det", nb);
+                    hipLaunchKernelGGL(t_ln_bwd_g_slab, dim3((unsigned)slabs), dim3(256), 0, st, x->p, y->g, stats, nb, hw, C, d, chunk, ws);
+                    det_reduce(ws, slabs, C, C, P(gname).g, st);
+                } else if (C <= 256 && 256 % C == 0) {
+                    dyf_form_note("t_ln_bwd_g_rows:atomic", nb);
                     hipLaunchKernelGGL(t_ln_bwd_g_rows, dim3((unsigned)(((long long)nb * hw + LN_GCHUNK - 1) / LN_GCHUNK)), dim3(256), 0, st, x->p, y->g, stats,
                                        nb, hw, C, d, P(gname).g);
-                else
+                } else {
                     hipLaunchKernelGGL(t_ln_bwd_g, dim3(C), dim3(256), 0, st, x->p, y->g, stats, nb, hw, C, d, P(gname).g);
+                }
             }
             hipLaunchKernelGGL(t_ln_bwd_x, dim3(nblk((long long)nb * hw * 16)), dim3(256), 0, st, x->p, P(gname).w, y->g, stats, nb, hw, C, d, grad(x));
             return DYF_OK;
@@ -1779,6 +1858,7 @@ dyf_status train_forward(dyf_engine* e, int which, int slot, const float* inputs
     T.ctx.reset();
     T.ts.clear();
     T.net = which; T.nb = nb; T.flags = flags; T.row_keys = nullptr; T.out = nullptr;
+    T.det = train_det() ? 1 : 0;
     const bool any_p = c.dropout > 0.0f || c.block_dropout1 > 0.0f || c.attn_dropout > 0.0f || c.input_dropout > 0.0f;
     const bool drop_on = (flags & DYF_TRAIN_DROPOUT) && any_p;
     if (drop_on) {  // this forward's dropout streams (engine generator, keyed per global row); a copy of the keys stays for the backward
@@ -1869,6 +1949,7 @@ dyf_status train_backward(dyf_engine* e, int slot, const float* dout_dev, float*
     RTape* tp = e->train ? e->train->tape[slot] : nullptr;
     if (!tp || tp->net < 0 || !tp->out) return fail(e, DYF_ERR_STATE, "no forward recorded in this tape slot");
     RTape& T = *tp;
+    const TrainDetScope det(T.det);  // the mode its forward was recorded under
     Net& n = e->net[T.net];
     const dyf_net_config& c = n.cfg;
     e->train->stream = st;
@@ -2024,6 +2105,7 @@ dyf_status f32_op_train(dyf_engine* e, const dyf_train_op* dp, const float* cons
     if (!e->train) e->train = new TrainState();
     e->train->stream = st;
     const TrainPrecisionScope precision(e->train_precision);
+    const TrainDetScope det(e->train_deterministic);
     dyf_net_config c = e->net[0].cfg;
     c.groups = d.groups;
     TrainNet W;

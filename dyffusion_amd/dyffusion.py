@@ -14,7 +14,8 @@ import torch
 from torch import Tensor, nn
 
 from . import _lib as L
-from .engine import EngineLoss, HipEngine, collect_train_results, default_dtype_for, sync_train_weights, sync_weights
+from .engine import (EngineLoss, HipEngine, collect_train_results, default_dtype_for, resolve_train_deterministic, sync_train_weights,
+                     sync_weights)
 from .unet_simple import UNet, _AttrDict  # noqa: F401
 
 Step = Union[int, float]
@@ -34,7 +35,7 @@ class DYffusion(nn.Module):
                  enable_forecaster_dropout: bool = False, max_batch: int = 64, use_graph: bool = True,
                  enable_mfma: bool = True, loss_function: str = "mean_squared_error", dtype: Optional[str] = None,
                  batch_invariant: bool = False, row_groups: Optional[int] = None, allow_bf16_long_rollout: bool = False,
-                 train_precision=None, attention_dropout: str = "fast", **kwargs):
+                 train_precision=None, attention_dropout: str = "fast", train_deterministic=None, **kwargs):
         super().__init__()
         if model is None:
             raise ValueError("Arg ``model`` is missing... Please provide a backbone model for the diffusion model (e.g. a Unet)")
@@ -113,8 +114,13 @@ class DYffusion(nn.Module):
                                  train_precision=train_precision,
                                  # 16-bit dropout of unet.Unet's Attention probabilities: "fast" (quad form) or "exact" (nn.Dropout's
                                  # rate on the fp32 path's keep bits; HipEngine.set_attention_dropout).  ValueError for another string.
-                                 attention_dropout=attention_dropout)
+                                 attention_dropout=attention_dropout,
+                                 # the reference's `trainer.deterministic`: True / False, or None = follow
+                                 # torch.use_deterministic_algorithms (HipEngine.train_set_deterministic)
+                                 train_deterministic=train_deterministic)
         L.attention_dropout_mode(attention_dropout)
+        resolve_train_deterministic(train_deterministic)
+        self.train_deterministic = train_deterministic
         self.allow_bf16_long_rollout = bool(allow_bf16_long_rollout)
         self._engine: Optional[HipEngine] = None
         self._plan_key = None
@@ -269,6 +275,13 @@ class DYffusion(nn.Module):
         self._engine_opts["attention_dropout"] = mode
         if self._engine is not None:
             self._engine.set_attention_dropout(mode)
+
+    def train_set_deterministic(self, value):
+        """True | False | None (HipEngine.train_set_deterministic) on the live engine; survives engine re-creation, like the seed."""
+        resolve_train_deterministic(value)
+        self._engine_opts["train_deterministic"] = self.train_deterministic = value
+        if self._engine is not None:
+            self._engine.train_set_deterministic(value)
 
     def set_row_offset(self, first_row: int):
         """Global index of batch row 0 of the tensors this object is given (ensemble sharding, distributed.py)."""

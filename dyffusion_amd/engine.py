@@ -91,12 +91,25 @@ def parse_train_precision(precision) -> int:
     raise ValueError(f"train precision {precision!r}: expected 32 / '32-true' or 16 / '16-mixed' / 'bf16-mixed'")
 
 
+def resolve_train_deterministic(setting) -> bool:
+    """The deterministic training mode a `train_deterministic` setting asks for right now (dyf_train_set_deterministic; the reference's
+    `trainer.deterministic`): True / False fix it; None follows `torch.are_deterministic_algorithms_enabled()` -- what Lightning's
+    `Trainer(deterministic=True)` sets -- and is read again at every training forward.  Anything else is a ValueError."""
+    if setting is None:
+        return bool(torch.are_deterministic_algorithms_enabled())
+    if isinstance(setting, bool):
+        return setting
+    raise ValueError(f"train_deterministic {setting!r}: expected True, False or None (None follows torch.use_deterministic_algorithms)")
+
+
 class HipEngine:
     def __init__(self, forecaster: L.NetConfig, interpolator: L.NetConfig, height: int, width: int, max_batch: int,
                  device: Optional[int] = None, use_graph: bool = True, enable_mfma: bool = True, dtype: str = "bf16",
                  batch_invariant: bool = False, row_groups: Optional[int] = None, train_precision=None,
-                 attention_dropout: str = "fast"):
+                 attention_dropout: str = "fast", train_deterministic=None):
         attn_mode = L.attention_dropout_mode(attention_dropout)  # ValueError before anything is created
+        resolve_train_deterministic(train_deterministic)
+        self._train_deterministic = train_deterministic  # True / False / None (follow torch): applied before every training call
         if not torch.cuda.is_available():
             raise EngineError("no GPU visible: the DYffusion HIP engine needs an MI355X (gfx950); there is no CPU fallback")
         # "fp32" / "float32" / "32": the default (bf16) build with dyf_set_sample_precision(32) -- every sampling forward in fp32
@@ -130,6 +143,7 @@ class HipEngine:
                 raise
         if train_precision is not None:
             self.train_set_precision(train_precision)
+        self._sync_train_deterministic()
         self._plan_keepalive = None
         self.n_out_slots = 0
         self._tape_net = {}       # tape slot -> network of the recorded training forward
@@ -579,6 +593,7 @@ class HipEngine:
         if pred.shape != target.shape:
             raise ValueError(f"shape mismatch: {tuple(pred.shape)} vs {tuple(target.shape)}")
         out = C.c_double(0.0)
+        self._sync_train_deterministic()
         self._check(self._lib.dyf_criterion(self._h, pred.data_ptr(), target.data_ptr(), pred.numel(), code, C.byref(out),
                                             self._stream()))
         return out.value
@@ -602,6 +617,7 @@ class HipEngine:
         flags = (L.TRAIN_BATCH_STATS if batch_stats else 0) | (L.TRAIN_DROPOUT if dropout else 0)
         self._tape_net[slot] = net
         self._tape_nb[slot] = nb
+        self._sync_train_deterministic()
         self._check(self._lib.dyf_train_forward(self._h, net, slot, inputs.data_ptr(), None if time is None else time.data_ptr(),
                                                 None if condition is None else condition.data_ptr(), out.data_ptr(), nb, flags,
                                                 self._stream()))
@@ -633,6 +649,25 @@ class HipEngine:
     @property
     def train_precision(self) -> int:
         return int(self._lib.dyf_train_precision(self._h))
+
+    def train_set_deterministic(self, value) -> None:
+        """Deterministic training mode (dyf_train_set_deterministic; the reference's `trainer.deterministic`): True = no sum of the
+        recorded forward, its backward or the criterion is merged with atomics, so identical steps are bitwise equal; False = the
+        default atomic forms; None = follow `torch.are_deterministic_algorithms_enabled()`, read at every training forward
+        (`resolve_train_deterministic`).  Sampling never reads it."""
+        resolve_train_deterministic(value)
+        self._train_deterministic = value
+        self._sync_train_deterministic()
+
+    def _sync_train_deterministic(self) -> None:
+        want = int(resolve_train_deterministic(self._train_deterministic))
+        if int(self._lib.dyf_train_deterministic(self._h)) != want:
+            self._check(self._lib.dyf_train_set_deterministic(self._h, want))
+
+    @property
+    def train_deterministic(self) -> bool:
+        self._sync_train_deterministic()
+        return bool(self._lib.dyf_train_deterministic(self._h))
 
     def train_zero_grads(self, net: int):
         self._check(self._lib.dyf_train_zero_grads(self._h, net))
@@ -895,6 +930,7 @@ class HipEngine:
             ins = ins + [mask]  # follows the inputs in the pointer array
         desc = L.TrainOp(L.TRAIN_OPS[op], nb, h, w, c, c2, k, stride, pad, groups, flags, float(p))
         arr = lambda ts: (C.c_void_p * max(len(ts), 1))(*[t.data_ptr() for t in ts])
+        self._sync_train_deterministic()
         self._check(self._lib.dyf_op_train_f32(self._h, C.byref(desc), arr(ins), arr(ps), dout.data_ptr(), y.data_ptr(), arr(dins), arr(gs),
                                                self._stream()))
         if op == "learned_sinu":

@@ -56,6 +56,9 @@ class Unet(nn.Module):
     # standalone engine option, next to `engine_dtype`: "fast" | "exact" dropout of the Attention probabilities in the 16-bit path
     # (HipEngine.set_attention_dropout); `net.engine_attention_dropout = "exact"` takes effect at the next forward
     engine_attention_dropout = "fast"
+    # deterministic training mode of a standalone network's own engine (HipEngine.train_set_deterministic): True / False, or None =
+    # follow torch.use_deterministic_algorithms; `net.train_deterministic = True` takes effect at the next forward
+    train_deterministic = None
 
     def __init__(self, dim, init_dim=None, dim_mults=(1, 2, 4, 8), num_conditions: int = 0, resnet_block_groups=8,
                  with_time_emb: bool = False, block_dropout: float = 0.0, block_dropout1: float = 0.0,
@@ -187,11 +190,13 @@ class Unet(nn.Module):
             # cost a workspace and a packed weight copy each for nothing
             self._engine = HipEngine(cfg, cfg, hw[0], hw[1], max_batch=nb, use_graph=False, dtype=default_dtype_for(self),
                                      row_groups=1, train_precision=getattr(self, "train_precision", None),
-                                     attention_dropout=self.engine_attention_dropout)
+                                     attention_dropout=self.engine_attention_dropout, train_deterministic=self.train_deterministic)
             self._engine_slot, self._engine_key = L.NET_FORECASTER, key
             upload_weights(self, self._engine, self._engine_slot)
         elif self._engine_key != "attached" and self._engine.attention_dropout != self.engine_attention_dropout:
             self._engine.set_attention_dropout(self.engine_attention_dropout)  # (an attached engine follows its owner's option)
+        if self._engine_key != "attached" and self._engine._train_deterministic is not self.train_deterministic:
+            self._engine.train_set_deterministic(self.train_deterministic)
         return self._engine
 
     # ------------------------------------------------------------------ reference API

@@ -36,6 +36,10 @@ def _block_params(cin: int, cout: int, kernel: int, decoder: bool, time_dim: Opt
 
 
 class UNet(nn.Module):
+    # deterministic training mode of a standalone network's own engine (HipEngine.train_set_deterministic): True / False, or None =
+    # follow torch.use_deterministic_algorithms; `net.train_deterministic = True` takes effect at the next forward
+    train_deterministic = None
+
     def __init__(self, dim: int, with_time_emb: bool = False, outer_sample_mode: str = "bilinear",
                  upsample_dims: Optional[Sequence[int]] = (256, 256), dropout: float = 0.0, input_dropout: float = 0.0,
                  num_input_channels: int = None, num_output_channels: int = None, num_conditional_channels: int = 0,
@@ -135,10 +139,13 @@ class UNet(nn.Module):
             if opt is not None and self._engine is not None:  # its state moves to the host side, and into the new engine later
                 opt.release_engine(self._engine)
             self._engine = HipEngine(cfg, cfg, hw[0], hw[1], max_batch=nb, use_graph=False, dtype=default_dtype_for(self),
-                                     train_precision=getattr(self, "train_precision", None))
+                                     train_precision=getattr(self, "train_precision", None),
+                                     train_deterministic=self.train_deterministic)
             self._engine_slot = L.NET_FORECASTER
             self._engine_key = key
             upload_weights(self, self._engine, self._engine_slot)
+        elif self._engine_key != "attached" and self._engine._train_deterministic is not self.train_deterministic:
+            self._engine.train_set_deterministic(self.train_deterministic)  # (an attached engine follows its owner's option)
         return self._engine
 
     # ------------------------------------------------------------------ reference API

@@ -316,6 +316,17 @@ dyf_status dyf_train_zero_grads(dyf_engine* engine, int32_t net);
  * should run under the same setting. */
 dyf_status dyf_train_set_precision(dyf_engine* engine, int32_t bits);
 int32_t dyf_train_precision(const dyf_engine* engine);
+/* Deterministic training mode (ABI 9) -- the reference's `trainer.deterministic` (Lightning; src/configs/trainer/default.yaml:18
+ * "deterministic: True"): on = 1 makes every floating-point sum of a recorded forward, of its backward and of the criterion independent
+ * of the arrival order of workgroups and waves, so two identical steps give bitwise equal losses, gradients and running statistics.  The
+ * weight / bias gradients, the BatchNorm / GroupNorm sums of both passes, the LayerNorm gain gradient and the loss value, which the
+ * default mode merges with atomics, go as one slab of partial sums per contributor to the step's split-K workspace (64 MB, no further
+ * memory) and are added in index order by a second launch; the adjoint of the outer resample becomes a gather (csrc/train.hip,
+ * csrc/train_gemm.hip, csrc/train_halo16.hip).  on = 0 (the default) keeps the atomic forms, whose gradients differ from run to run in
+ * the last bits.  Applies to the dyf_train_forward / dyf_train_backward / dyf_criterion / dyf_criterion_grad calls that follow (a
+ * backward runs under the setting its forward was recorded with); neither sampling path reads it. */
+dyf_status dyf_train_set_deterministic(dyf_engine* engine, int32_t on);
+int32_t dyf_train_deterministic(const dyf_engine* engine);
 /* Copy gradients out by the reference's state_dict names (PyTorch layouts), HOST fp32 buffers; "*.running_mean/var" return the
  * updated BatchNorm statistics. */
 /* Refresh only the TRAINING copy of a network's parameters (after optimizer.step()): same arguments as dyf_load_weights, which
