@@ -108,6 +108,7 @@ TRAIN_OPS = {"conv": 0, "gn_act": 1, "layernorm": 2, "linattn": 3, "attention": 
              "attention_stream": 16}
 TOP_WS, TOP_BIAS, TOP_PRE, TOP_FILM, TOP_SAME = 1, 2, 4, 8, 16
 TOP_RUNNING, TOP_MASK, TOP_LEAKY, TOP_RELU, TOP_NEAREST, TOP_GRAD_IN = 32, 64, 128, 256, 512, 1024
+TOP_ACT_GELU, TOP_RESIDUAL = 2048, 4096
 
 
 class OptimConfig(C.Structure):

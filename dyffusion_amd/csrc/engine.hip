@@ -646,7 +646,11 @@ static dyf_status load_weights_one(dyf_engine* e, int32_t which, int32_t n_tenso
         v.shape.assign(shapes[i], shapes[i] + ndims[i]);
         sd[names[i]] = v;
     }
-    if (n.sc) return sc_load_weights(e, n, sd);
+    if (n.sc) {
+        dyf_status ss = sc_load_weights(e, n, sd);
+        if (ss != DYF_OK || e->is_group_child) return ss;
+        return train_store_params(e, which, sd);  // fp32 copy in the training layout, by the reference's state_dict names (train_resnet.inc)
+    }
     if (n.rn) {
         dyf_status rs = rn_load_weights(e, n, sd);
         if (rs != DYF_OK) return rs;

@@ -177,7 +177,7 @@ struct dyf_engine {
     size_t s_log_floats = 0;
     int log_nb = 0;                  // batch rows of the logged call
     std::vector<uint8_t> log_has_cur;  // per step: slot 2 (x_interpolated_s) was defined at that step
-    dyf::TrainState* train = nullptr;  // fp32 path (training step, fp32 sampling; arch unet_simple and unet.Unet), created by the first dyf_load_weights
+    dyf::TrainState* train = nullptr;  // fp32 path (training step, fp32 sampling), created by the first dyf_load_weights
     bool last_dec5_sparse = false;  // the most recent unet_simple forward stored dec5 in the compact sparse-column layout
     bool poison_dec5 = false;       // DYF_POISON_DEC5=1 (test hook, read once at create): NaN-fill dec5's output before its conv
     // GroupNorm fused into the producing conv (gn_fused.h): host-visible error word (pinned, mapped) a timed-out granule sweep raises,
@@ -366,7 +366,7 @@ struct FwdOpts {
 // ---- training step (train.hip)
 struct dyf_train_op;  // include/dyffusion_hip_testing.h
 namespace dyf {
-dyf_status train_store_params(dyf_engine* e, int which, std::map<std::string, TensorView>& sd);  // arch unet_simple and unet.Unet
+dyf_status train_store_params(dyf_engine* e, int which, std::map<std::string, TensorView>& sd);  // every arch
 void train_destroy(dyf_engine* e);
 // fp32 sampling forward (train.hip): net_forward's signature; the layer walk and the kernels of the recorded training forward on the
 // engine's bump arena -- no allocation, no synchronisation, bitwise repeatable, capturable

@@ -1,7 +1,7 @@
 // The fp32 path on the GPU -- the training step of the forecaster objective (forward WITH batch-statistics BatchNorm / dropout, and the
-// backward pass) and fp32 sampling -- for arch unet_simple and unet.Unet: the kernels both share, the convolution
-// dispatch, the caching allocator and the C entry points.  The recorded ops, the two layer walks, the parameters and the backward are in
-// train_resnet.inc (#included below): ONE mechanism for both backbones.
+// backward pass) for all three backbones, and fp32 sampling for arch unet_simple and unet.Unet: the kernels they share,
+// the convolution dispatch, the caching allocator and the C entry points.  The recorded ops, the three layer walks, the parameters and the
+// backward are in train_resnet.inc (#included below): ONE mechanism for every backbone.
 //
 // Replaces, for `DYffusion.p_losses` in training mode (src/diffusion/dyffusion.py:496-567, entered from
 // BaseDiffusion.forward, src/diffusion/_base_diffusion.py:81-106), what the reference gets from torch.autograd over
@@ -807,11 +807,17 @@ struct TNorm {
     const uint8_t* mask;                // injected keep mask of the whole NHWC output (sampling, dropout mode 2; drop = 0) or null
 };
 
+// EXT: the instantiations SimpleConvNet's blocks take (simple_conv_net.py:38-55) -- exact (erf) GELU as common.h's apply_act defines it,
+// derivative Phi(u) + u phi(u), and (forward kernels) the block's residual operand.  EXT = false is the code the two UNets have always run.
+template <bool EXT = false>
 __device__ __forceinline__ float t_act(float u, int act) {
+    if (EXT && act == ACT_GELU) return 0.5f * u * (1.0f + erff(u * 0.70710678118654752f));
     if (act == ACT_SILU) return u / (1.0f + expf(-u));
     return act == ACT_RELU ? fmaxf(u, 0.0f) : act == ACT_LEAKY ? (u > 0.0f ? u : 0.2f * u) : u;
 }
+template <bool EXT = false>
 __device__ __forceinline__ float t_dact(float u, int act) {
+    if (EXT && act == ACT_GELU) return 0.5f * (1.0f + erff(u * 0.70710678118654752f)) + u * 0.3989422804014327f * expf(-0.5f * u * u);
     if (act == ACT_SILU) {
         const float sg = 1.0f / (1.0f + expf(-u));
         return sg * (1.0f + u * (1.0f - sg));
@@ -896,7 +902,8 @@ __device__ __forceinline__ float t_keep_rk(const TNorm& a, const RngKey& rk, uin
     if (!a.drop) return 1.0f;
     return rng_keep(e_in_row, rk, a.thresh16) ? a.drop_scale : 0.0f;
 }
-__global__ void t_norm_fwd(TNorm a, const float* z, float* y) {
+template <bool EXT>
+__device__ __forceinline__ void t_norm_fwd_body(const TNorm& a, const float* z, float* y, const float* r) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     const long long per = (long long)a.hw * a.C;
     if (i >= per * a.n) return;
@@ -905,16 +912,19 @@ __global__ void t_norm_fwd(TNorm a, const float* z, float* y) {
     float v = (z[i] - a.mean[idx]) * a.rstd[idx] * a.gamma[c] + a.beta[c];
     if (a.ss) v = v * (1.0f + a.ss[(size_t)b * 2 * a.C + c]) + a.ss[(size_t)b * 2 * a.C + a.C + c];
     const float keep = a.mask ? (a.mask[i] ? a.drop_scale : 0.0f) : t_keep(a, b, (uint32_t)(i - (long long)b * per));
-    y[i] = t_act(v, a.act) * keep;
+    if (EXT) y[i] = t_act<true>(v, a.act) * keep + (r ? r[i] : 0.0f);
+    else y[i] = t_act(v, a.act) * keep;
 }
-__global__ __launch_bounds__(256) void t_norm_fwd4(TNorm a, const float* z, float* y) {
+template <bool EXT>
+__device__ __forceinline__ void t_norm_fwd4_body(const TNorm& a, const float* z, float* y, const float* r) {
     const uint32_t per = (uint32_t)a.hw * (uint32_t)a.C;
     const uint32_t e = (blockIdx.x * 256u + threadIdx.x) * 4u;
     if (e >= per) return;
     const int b = blockIdx.y, c = (int)(e % (uint32_t)a.C);
     const size_t i = (size_t)b * per + e;
-    float zv[4], r[4];
+    float zv[4], rv[4] = {0.0f, 0.0f, 0.0f, 0.0f}, o[4];
     t_f4(z + i, zv);
+    if (EXT && r) t_f4(r + i, rv);
     TNormQuad q;
     t_norm_quad(a, b, c, nullptr, nullptr, q);
     const RngKey rk = t_row_stream(a, b);
@@ -923,10 +933,16 @@ __global__ __launch_bounds__(256) void t_norm_fwd4(TNorm a, const float* z, floa
         float v = (zv[k] - q.mu[k]) * q.rs[k] * q.ga[k] + q.be[k];
         if (a.ss) v = v * (1.0f + q.sc[k]) + q.sh[k];
         const float keep = a.mask ? (a.mask[i + k] ? a.drop_scale : 0.0f) : t_keep_rk(a, rk, e + k);
-        r[k] = t_act(v, a.act) * keep;
+        if (EXT) o[k] = t_act<true>(v, a.act) * keep + rv[k];
+        else o[k] = t_act(v, a.act) * keep;
     }
-    *(float4*)(y + i) = make_float4(r[0], r[1], r[2], r[3]);
+    *(float4*)(y + i) = make_float4(o[0], o[1], o[2], o[3]);
 }
+__global__ void t_norm_fwd(TNorm a, const float* z, float* y) { t_norm_fwd_body<false>(a, z, y, nullptr); }
+__global__ __launch_bounds__(256) void t_norm_fwd4(TNorm a, const float* z, float* y) { t_norm_fwd4_body<false>(a, z, y, nullptr); }
+// y = keep * act(..) + r with GELU among the activations (r null: no residual): SimpleConvNet's block in the same launch
+__global__ void t_norm_fwd_ext(TNorm a, const float* z, float* y, const float* r) { t_norm_fwd_body<true>(a, z, y, r); }
+__global__ __launch_bounds__(256) void t_norm_fwd4_ext(TNorm a, const float* z, float* y, const float* r) { t_norm_fwd4_body<true>(a, z, y, r); }
 inline bool t_vec4_ok(int C, const void* p0, const void* p1 = nullptr, const void* p2 = nullptr) {
     return (C & 3) == 0 && (((uintptr_t)p0 | (uintptr_t)p1 | (uintptr_t)p2) & 15) == 0;
 }
@@ -934,16 +950,21 @@ inline bool t_norm_vec4_ok(const TNorm& a) {
     return (a.C & 3) == 0 && (long long)a.hw * a.C < (1ll << 32) && a.n <= 65535 &&
            (((uintptr_t)a.mean | (uintptr_t)a.rstd | (uintptr_t)a.gamma | (uintptr_t)a.beta | (uintptr_t)a.ss) & 15) == 0;
 }
-inline void launch_t_norm_fwd(const TNorm& a, const float* z, float* y, hipStream_t st) {
+inline bool t_norm_ext(const TNorm& a, const float* r = nullptr) { return a.act == ACT_GELU || r != nullptr; }
+inline void launch_t_norm_fwd(const TNorm& a, const float* z, float* y, hipStream_t st, const float* r = nullptr) {
     const long long per = (long long)a.hw * a.C;
-    if (t_norm_vec4_ok(a) && t_vec4_ok(a.C, z, y)) hipLaunchKernelGGL(t_norm_fwd4, dim3(nblk(per / 4), a.n), dim3(256), 0, st, a, z, y);
+    const bool v4 = t_norm_vec4_ok(a) && t_vec4_ok(a.C, z, y, r);
+    if (t_norm_ext(a, r)) {
+        if (v4) hipLaunchKernelGGL(t_norm_fwd4_ext, dim3(nblk(per / 4), a.n), dim3(256), 0, st, a, z, y, r);
+        else hipLaunchKernelGGL(t_norm_fwd_ext, dim3(nblk(per * a.n)), dim3(256), 0, st, a, z, y, r);
+    } else if (v4) hipLaunchKernelGGL(t_norm_fwd4, dim3(nblk(per / 4), a.n), dim3(256), 0, st, a, z, y);
     else hipLaunchKernelGGL(t_norm_fwd, dim3(nblk(per * a.n)), dim3(256), 0, st, a, z, y);
 }
 
 // backward reductions, per (sample, channel) over the plane:
 //   A = sum dpre * v (dscale), B = sum dpre (dshift), Cc = sum dbn * xhat, Dd = sum dbn,  dbn = dpre * (1 + scale)
 // DET: as t_nc_sums -- slabs of (A | B | Cc | Dd), 4 n C doubles apart
-template <bool DET>
+template <bool DET, bool EXT = false>
 __global__ __launch_bounds__(256) void t_norm_bwd_sums(TNorm a, const float* z, const float* dy, int px_per_block, double* A, double* B,
                                                        double* Cc, double* Dd) {
     const int b = blockIdx.y;
@@ -959,7 +980,7 @@ __global__ __launch_bounds__(256) void t_norm_bwd_sums(TNorm a, const float* z, 
         for (int p = p0 + sub; p < p1; p += nsub) {
             const long long e = (long long)p * a.C + c;
             const float xh = (z[(size_t)b * per + e] - mu) * rs, v = xh * ga + be, u = v * (1.0f + sc) + sh;
-            const float dpre = dy[(size_t)b * per + e] * t_keep(a, b, (uint32_t)e) * t_dact(u, a.act);
+            const float dpre = dy[(size_t)b * per + e] * t_keep(a, b, (uint32_t)e) * t_dact<EXT>(u, a.act);
             const float dbn = dpre * (1.0f + sc);
             sa += (double)dpre * v;
             sb += dpre;
@@ -1041,6 +1062,7 @@ __device__ __forceinline__ float t_mul_rounded(float x, float y) {
 #pragma clang fp contract(off)
     return x * y;
 }
+template <bool EXT = false>
 __global__ void t_norm_bwd_apply(TNorm a, const float* z, const float* dy, const float* S1, const float* S2, float inv_count, float* dz) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     const long long per = (long long)a.hw * a.C;
@@ -1050,9 +1072,10 @@ __global__ void t_norm_bwd_apply(TNorm a, const float* z, const float* dy, const
     const float xh = (z[i] - a.mean[idx]) * a.rstd[idx], v = xh * a.gamma[c] + a.beta[c];
     const float sc = a.ss ? a.ss[(size_t)b * 2 * a.C + c] : 0.0f, sh = a.ss ? a.ss[(size_t)b * 2 * a.C + a.C + c] : 0.0f;
     const float u = v * (1.0f + sc) + sh;
-    const float dbn = dy[i] * t_keep(a, b, (uint32_t)(i - (long long)b * per)) * t_dact(u, a.act) * (1.0f + sc);
+    const float dbn = dy[i] * t_keep(a, b, (uint32_t)(i - (long long)b * per)) * t_dact<EXT>(u, a.act) * (1.0f + sc);
     dz[i] = a.rstd[idx] * (t_mul_rounded(a.gamma[c], dbn) - (S1[idx] + xh * S2[idx]) * inv_count);
 }
+template <bool EXT = false>
 __global__ __launch_bounds__(256) void t_norm_bwd_apply4(TNorm a, const float* z, const float* dy, const float* S1, const float* S2, float inv_count,
                                                          float* dz) {
     const uint32_t per = (uint32_t)a.hw * (uint32_t)a.C;
@@ -1070,7 +1093,7 @@ __global__ __launch_bounds__(256) void t_norm_bwd_apply4(TNorm a, const float* z
     for (int k = 0; k < 4; ++k) {
         const float xh = (zv[k] - q.mu[k]) * q.rs[k], v = xh * q.ga[k] + q.be[k];
         const float u = v * (1.0f + q.sc[k]) + q.sh[k];
-        const float dbn = dv[k] * t_keep_rk(a, rk, e + k) * t_dact(u, a.act) * (1.0f + q.sc[k]);
+        const float dbn = dv[k] * t_keep_rk(a, rk, e + k) * t_dact<EXT>(u, a.act) * (1.0f + q.sc[k]);
         r[k] = q.rs[k] * (t_mul_rounded(q.ga[k], dbn) - (q.s1[k] + xh * q.s2[k]) * inv_count);
     }
     *(float4*)(dz + i) = make_float4(r[0], r[1], r[2], r[3]);
@@ -1078,9 +1101,12 @@ __global__ __launch_bounds__(256) void t_norm_bwd_apply4(TNorm a, const float* z
 inline void launch_t_norm_bwd_apply(const TNorm& a, const float* z, const float* dy, const float* S1, const float* S2, float inv_count, float* dz,
                                     hipStream_t st) {
     const long long per = (long long)a.hw * a.C;
-    if (t_norm_vec4_ok(a) && t_vec4_ok(a.C, z, dy, dz) && t_vec4_ok(0, S1, S2))
-        hipLaunchKernelGGL(t_norm_bwd_apply4, dim3(nblk(per / 4), a.n), dim3(256), 0, st, a, z, dy, S1, S2, inv_count, dz);
-    else hipLaunchKernelGGL(t_norm_bwd_apply, dim3(nblk(per * a.n)), dim3(256), 0, st, a, z, dy, S1, S2, inv_count, dz);
+    const bool v4 = t_norm_vec4_ok(a) && t_vec4_ok(a.C, z, dy, dz) && t_vec4_ok(0, S1, S2);
+    if (t_norm_ext(a)) {  // GELU: the instantiations with its derivative
+        if (v4) hipLaunchKernelGGL(t_norm_bwd_apply4<true>, dim3(nblk(per / 4), a.n), dim3(256), 0, st, a, z, dy, S1, S2, inv_count, dz);
+        else hipLaunchKernelGGL(t_norm_bwd_apply<true>, dim3(nblk(per * a.n)), dim3(256), 0, st, a, z, dy, S1, S2, inv_count, dz);
+    } else if (v4) hipLaunchKernelGGL(t_norm_bwd_apply4<false>, dim3(nblk(per / 4), a.n), dim3(256), 0, st, a, z, dy, S1, S2, inv_count, dz);
+    else hipLaunchKernelGGL(t_norm_bwd_apply<false>, dim3(nblk(per * a.n)), dim3(256), 0, st, a, z, dy, S1, S2, inv_count, dz);
 }
 
 // ------------------------------------------------------------------------------------------------ small dense layers (time MLP, FiLM heads)
@@ -1581,7 +1607,7 @@ extern "C" {
 dyf_status dyf_train_zero_grads(dyf_engine* e, int32_t which) {
     if (!e || which < 0 || which > 1) return DYF_ERR_INVALID_ARGUMENT;
     TrainNet* t = e->train ? e->train->net[which] : nullptr;
-    if (!t || !t->ready) return fail(e, DYF_ERR_STATE, "training needs arch unet_simple / unet with loaded weights");
+    if (!t || !t->ready) return fail(e, DYF_ERR_STATE, "training needs loaded weights (dyf_load_weights)");
     TK(hipSetDevice(e->cfg.device));
     TK(hipMemsetAsync(t->g_arena, 0, t->g_arena_floats * sizeof(float), 0));
     TK(hipDeviceSynchronize());
@@ -1683,20 +1709,26 @@ dyf_status f32_net_forward(dyf_engine* e, int which, const Source* srcs, int nsr
 
 extern "C" {
 
+// operand precision of a recorded forward of network `which` and of its backward: the engine's setting; SimpleConvNet records in fp32
+// whatever the tests' operand switch says (an engine SET to 16 bits is refused by train_forward)
+static int train_precision_for(const dyf_engine* e, int which) {
+    return which >= 0 && which <= 1 && e->net[which].sc && e->train_precision != 16 ? 32 : e->train_precision;
+}
+
 dyf_status dyf_train_forward(dyf_engine* e, int32_t which, int32_t slot, const float* inputs_dev, const float* time_dev,
                              const float* cond_dev, float* out_dev, int32_t nb, int32_t flags, void* stream) {
     if (!e || which < 0 || which > 1 || slot < 0 || slot > 3 || !inputs_dev || !out_dev || nb < 1)
         return fail(e, DYF_ERR_INVALID_ARGUMENT, "dyf_train_forward: bad arguments");
-    const TrainPrecisionScope precision(e->train_precision);
+    const TrainPrecisionScope precision(train_precision_for(e, which));
     const TrainDetScope det(e->train_deterministic);
-    if (e->net[which].sc) return fail(e, DYF_ERR_UNSUPPORTED, "training step: arch unet_simple and unet (SimpleConvNet is the CPU plumbing config)");
     TK(hipSetDevice(e->cfg.device));
     return train_forward(e, which, slot, inputs_dev, time_dev, cond_dev, out_dev, nb, flags, (hipStream_t)stream);
 }
 
 dyf_status dyf_train_backward(dyf_engine* e, int32_t slot, const float* dout_dev, float* dinputs_dev, int32_t param_grads, void* stream) {
     if (!e || slot < 0 || slot > 3 || !dout_dev) return fail(e, DYF_ERR_INVALID_ARGUMENT, "dyf_train_backward: bad arguments");
-    const TrainPrecisionScope precision(e->train_precision);
+    const RTape* tape = e->train ? e->train->tape[slot] : nullptr;
+    const TrainPrecisionScope precision(train_precision_for(e, tape ? tape->net : -1));
     TK(hipSetDevice(e->cfg.device));
     return train_backward(e, slot, dout_dev, dinputs_dev, param_grads, (hipStream_t)stream);
 }
@@ -1763,8 +1795,8 @@ static dyf_status train_load_weights_impl(dyf_engine* e, int32_t which, int32_t 
     TK(hipSetDevice(e->cfg.device));
     const Net& n = e->net[which];
     TrainNet* t = e->train ? e->train->net[which] : nullptr;
-    if (n.sc || !n.loaded || !t || !t->ready)
-        return fail(e, DYF_ERR_STATE, "dyf_train_load_weights: arch unet_simple / unet with weights loaded once by dyf_load_weights");
+    if (!n.loaded || !t || !t->ready)
+        return fail(e, DYF_ERR_STATE, "dyf_train_load_weights: weights must have been loaded once by dyf_load_weights");
     std::map<std::string, TensorView> sd;
     for (int i = 0; i < n_tensors; ++i) {
         TensorView v;
@@ -1837,7 +1869,7 @@ static dyf_status optim_transfer(dyf_engine* e, int32_t which, int32_t kind, int
         return fail(e, DYF_ERR_INVALID_ARGUMENT, "dyf_optim_export / dyf_optim_import: bad arguments");
     TK(hipSetDevice(e->cfg.device));
     TrainNet* t = train_net(e, which);
-    if (!t || !t->ready) return fail(e, DYF_ERR_STATE, "training needs arch unet_simple / unet with loaded weights");
+    if (!t || !t->ready) return fail(e, DYF_ERR_STATE, "training needs loaded weights (dyf_load_weights)");
     if (kind >= DYF_OPTIM_EXP_AVG && kind <= DYF_OPTIM_EMA && !t->optim) return fail(e, DYF_ERR_STATE, "no optimizer for this network (dyf_optim_create)");
     size_t stage_n = 0;
     for (int i = 0; i < n_tensors; ++i) {

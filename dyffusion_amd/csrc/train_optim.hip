@@ -278,7 +278,6 @@ dyf_status dyf_optim_create(dyf_engine* e, int32_t which, const dyf_optim_config
     if (!e || which < 0 || which > 1 || !c) return fail(e, DYF_ERR_INVALID_ARGUMENT, "dyf_optim_create: bad arguments");
     if (!(c->beta1 >= 0.0 && c->beta1 < 1.0) || !(c->beta2 >= 0.0 && c->beta2 < 1.0) || !(c->eps >= 0.0) || !(c->weight_decay >= 0.0))
         return fail(e, DYF_ERR_INVALID_ARGUMENT, "dyf_optim_create: betas in [0, 1), eps >= 0, weight_decay >= 0");
-    if (e->net[which].sc) return fail(e, DYF_ERR_UNSUPPORTED, "optimizer: arch unet_simple and unet (SimpleConvNet has no engine training step)");
     TrainNet* t = train_net(e, which);
     if (!t || !t->ready || !e->net[which].loaded) return fail(e, DYF_ERR_STATE, "optimizer: the network needs loaded weights (dyf_load_weights)");
     HIP_TRY(e, hipSetDevice(e->cfg.device));

@@ -1132,8 +1132,9 @@ struct RCtx {
     // momentum 0.1), 1: BatchNorm on the running statistics (no sums are taken), 2: GroupNorm(G).  ss (nb, 2C) = (scale | shift) or null.
     // ppb_rec: pixels per workgroup of the sum kernels of a RECORDED forward, the caller's rule (norm_ppb_*); a sampling forward takes ONE
     // workgroup per sample -- every sum meets its zero-filled slot once, no order of atomics to depend on.
+    // res: SimpleConvNet's residual (simple_conv_net.py:52-54), y = keep * act(..) + res in the same launch; the adjoint hands y's gradient on to it
     dyf::RT* norm_act(dyf::RT* z, int hw, int C, const std::string& name, dyf::RT* ss, float p_drop, int kind, int G, int act, int ppb_rec,
-                      int salt_site = -1) {
+                      int salt_site = -1, dyf::RT* res = nullptr) {
         const int gn = kind == 2 ? 1 : 0, nidx = gn ? nb * G : C;
         float *mean = fbuf(nidx), *rstd = fbuf(nidx);
         const int ppb = mem.recording() ? ppb_rec : hw;
@@ -1164,7 +1165,7 @@ struct RCtx {
         const TNorm a{nb, hw, C, G, gn, act, mean, rstd, P(name + ".weight").w, P(name + ".bias").w, ss ? ss->p : nullptr, d.on, d.scale,
                       d.thresh16, d.salt, d.row_keys, d.mask};
         dyf::RT* y = make(z->n);
-        launch_t_norm_fwd(a, z->p, y->p, st);
+        launch_t_norm_fwd(a, z->p, y->p, st, res ? res->p : nullptr);
         const size_t nS = ((size_t)std::max(nidx, C) + 3) / 4 * 4;  // floats of S1 and of S2 (16-byte aligned behind the doubles)
         norm_bwd_doubles = std::max(norm_bwd_doubles, (size_t)nb * C * 4 + nS);
         back([=]() -> dyf_status {
@@ -1174,6 +1175,7 @@ struct RCtx {
             if (hipMemsetAsync(A, 0, (size_t)nb * C * 4 * sizeof(double), st) != hipSuccess) return DYF_ERR_HIP;
             float *S1 = (float*)(A + (size_t)nb * C * 4), *S2 = S1 + nS;
             float* dss = ss ? tbuf((size_t)nb * 2 * C) : nullptr;
+            const bool gelu = a.act == ACT_GELU;  // the instantiations with its derivative
             if (train_det()) {  // (as the forward's sums)
                 double* ws = (double*)splitk_ws(e);
                 const size_t nC = (size_t)nb * C;
@@ -1181,15 +1183,17 @@ struct RCtx {
                 const int slabs = (hw + dppb - 1) / dppb;
                 if (!ws) return DYF_ERR_STATE;
                 dyf_form_note("t_norm_bwd_sums:det", nb);
+                auto* kern = gelu ? t_norm_bwd_sums<true, true> : t_norm_bwd_sums<true, false>;
                 if (slabs > 1) {
-                    hipLaunchKernelGGL(t_norm_bwd_sums<true>, dim3(slabs, nb), dim3(256), 0, st, a, z->p, y->g, dppb, ws, ws + nC, ws + 2 * nC, ws + 3 * nC);
+                    hipLaunchKernelGGL(kern, dim3(slabs, nb), dim3(256), 0, st, a, z->p, y->g, dppb, ws, ws + nC, ws + 2 * nC, ws + 3 * nC);
                     det_reduce(ws, slabs, (long long)nC * 4, (long long)nC * 4, A, st);
                 } else {
-                    hipLaunchKernelGGL(t_norm_bwd_sums<true>, dim3(1, nb), dim3(256), 0, st, a, z->p, y->g, dppb, A, B, Cc, Dd);
+                    hipLaunchKernelGGL(kern, dim3(1, nb), dim3(256), 0, st, a, z->p, y->g, dppb, A, B, Cc, Dd);
                 }
             } else {
                 dyf_form_note("t_norm_bwd_sums:atomic", nb);
-                hipLaunchKernelGGL(t_norm_bwd_sums<false>, dim3((hw + ppb - 1) / ppb, nb), dim3(256), 0, st, a, z->p, y->g, ppb, A, B, Cc, Dd);
+                auto* kern = gelu ? t_norm_bwd_sums<false, true> : t_norm_bwd_sums<false, false>;
+                hipLaunchKernelGGL(kern, dim3((hw + ppb - 1) / ppb, nb), dim3(256), 0, st, a, z->p, y->g, ppb, A, B, Cc, Dd);
             }
             // (running statistics: the norm is a fixed affine map, S1 = S2 = 0)
             hipLaunchKernelGGL(t_norm_bwd_combine, dim3(nblk(std::max(nb * C, nb * G))), dim3(256), 0, st, a, A, B, Cc, Dd,
@@ -1199,6 +1203,8 @@ struct RCtx {
             launch_t_norm_bwd_apply(a, z->p, y->g, S1, S2, gn ? 1.0f / ((float)hw * (C / G)) : 1.0f / ((float)nb * hw), dz, st);
             accum(z, dz);
             if (ss) accum(ss, dss);
+            // y's gradient reaches the residual unchanged, and y is done with it: the buffer itself becomes (the first contribution to) res's gradient
+            if (res && wants(res)) accum(res, y->g);
             return DYF_OK;
         });
         return dbg(y, "norm_act");
@@ -1570,7 +1576,7 @@ struct RCount {
         return make((size_t)nb * ho * wo * cout);
     }
     size_t sums_cap = 0, sums_hint = 0;
-    dyf::RT* norm_act(dyf::RT* z, int, int C, const std::string&, dyf::RT*, float, int kind, int G, int, int, int = -1) {
+    dyf::RT* norm_act(dyf::RT* z, int, int C, const std::string&, dyf::RT*, float, int kind, int G, int, int, int = -1, dyf::RT* = nullptr) {
         const size_t nidx = kind == 2 ? (size_t)nb * G : (size_t)C;
         take(nidx); take(nidx);
         if (kind != 1 && (size_t)nb * C * 2 > sums_cap) { sums_cap = std::max((size_t)nb * C * 2, sums_hint); take(sums_cap, sizeof(double)); }
@@ -1731,9 +1737,38 @@ RT* us_walk(Ctx& X, const Net& n, int nb, int H, int W, const Source* src, const
     return X.resize(X.conv_transpose4s2(x, lh, lw, n.dim, c.out_channels, "readout.0"), 2 * lh, 2 * lw, c.out_channels, H, W, c.outer_nearest);
 }
 
-// ---- the one place that tells the two backbones apart: which walk, the order of its sources, what a recorded forward cannot serve
+// The layer walk of SimpleConvNet.forward (simple_conv_net.py:112-131), used as the two above are: cat (inputs, condition) -> per kernel size
+// [Conv2d(k, 'same') -> BatchNorm2d -> FiLM -> GELU -> Dropout -> + block input where cin == dim] (:38-55) -> 1 x 1 head.  A block is a conv
+// and ONE norm_act (GELU, the residual in the same launch).  Dropout site i = block i with salt rng_layer_salt(i), as sc_forward /
+// sc_f32_forward draw them: MC dropout and training share their streams.  Kernel sizes travel in cfg.n_mults / dim_mults.
+template <typename Ctx>
+RT* sc_walk(Ctx& X, const Net& n, int nb, int H, int W, const Source* src, const float* time_dev_in, float time_value, bool bn_batch, RT** x_in) {
+    const dyf_net_config& c = n.cfg;
+    const int hw = H * W;
+    RT* film = nullptr;  // SiLU(time embedding), what every block's FiLM head starts from
+    if (c.with_time_emb) {
+        const float* time_dev = X.times(time_dev_in, time_value);
+        RT* e0 = X.sinusoid(time_dev, n.dim);
+        film = X.silu_shared(X.linear(X.gelu(X.linear(e0, nb, n.dim, n.tdim, "time_emb_mlp.1", 0)), nb, n.tdim, n.tdim, "time_emb_mlp.3", 0));
+    }
+    RT* x = X.inputs(src, hw, n.cin_total);
+    *x_in = x;
+    X.sums_hint = std::max(X.sums_hint, (size_t)nb * 2 * n.dim);
+    int cin = n.cin_total;
+    for (int i = 0; i < c.n_mults; ++i) {
+        const int k = c.dim_mults[i];
+        const std::string pre = "convs." + std::to_string(i);
+        RT* z = X.conv(x, H, W, cin, n.dim, k, 1, (k - 1) / 2, pre + ".conv", true, false);
+        RT* ss = film ? X.linear(film, nb, n.tdim, 2 * n.dim, pre + ".time_mlp.1", 1, true) : nullptr;
+        x = X.norm_act(z, hw, n.dim, pre + ".norm", ss, c.dropout, bn_batch ? 0 : 1, 8, ACT_GELU, us_norm_ppb(hw), i, cin == n.dim ? x : nullptr);
+        cin = n.dim;
+    }
+    return X.conv(x, H, W, n.dim, c.out_channels, 1, 1, 0, "head", true, false);
+}
+
+// ---- the one place that tells the backbones apart: which walk, the order of its sources, what a recorded forward cannot serve
 // the training step's sources in the order the backbone concatenates them (unet.Unet: (condition, x), unet.py:269; unet_simple: (x,
-// condition)); returns the first channel of `inputs` inside the concatenation
+// condition), and SimpleConvNet as unet_simple, simple_conv_net.py:121); returns the first channel of `inputs` inside the concatenation
 inline int net_sources(const Net& n, const float* inputs_dev, const float* cond_dev, Source src[3]) {
     src[0] = {inputs_dev, n.cfg.in_channels};
     src[1] = {cond_dev, cond_dev ? n.cfg.cond_channels : 0};
@@ -1754,6 +1789,7 @@ template <typename Ctx>
 RT* net_walk(Ctx& X, const dyf_engine* e, const Net& n, int nb, const Source* src, const float* time_dev, float time_value, bool bn_batch, RT** x_in) {
     const int H = e->cfg.height, W = e->cfg.width;
     if (n.rn) return rn_walk(X, n.cfg, rn_names(e, n.cfg), nb, H, W, n.cin_total, src, time_dev, time_value, x_in);
+    if (n.sc) return sc_walk(X, n, nb, H, W, src, time_dev, time_value, bn_batch, x_in);
     return us_walk(X, n, nb, H, W, src, time_dev, time_value, bn_batch, x_in);
 }
 
@@ -1810,7 +1846,7 @@ static dyf_status rn_fill_params(dyf_engine* e, TrainNet& t, std::map<std::strin
     return DYF_OK;
 }
 
-// fp32 training copy of a network's parameters (called by dyf_load_weights for arch unet_simple and unet.Unet)
+// fp32 training copy of a network's parameters (called by dyf_load_weights for every arch)
 dyf_status train_store_params(dyf_engine* e, int which, std::map<std::string, TensorView>& sd) {
     if (!e->train) e->train = new TrainState();
     if (!e->train->net[which]) e->train->net[which] = new TrainNet();
@@ -1842,12 +1878,14 @@ dyf_status train_store_params(dyf_engine* e, int which, std::map<std::string, Te
 dyf_status train_forward(dyf_engine* e, int which, int slot, const float* inputs_dev, const float* time_dev, const float* cond_dev, float* out_dev,
                          int nb, int flags, hipStream_t st) {
     TrainNet* wp = e->train ? e->train->net[which] : nullptr;
-    if (!wp || !wp->ready) return fail(e, DYF_ERR_STATE, "training needs arch unet_simple / unet with loaded weights (dyf_load_weights)");
+    if (!wp || !wp->ready) return fail(e, DYF_ERR_STATE, "training needs loaded weights (dyf_load_weights)");
     Net& n = e->net[which];
     const dyf_net_config& c = n.cfg;
     if ((c.cond_channels > 0) != (cond_dev != nullptr)) return fail(e, DYF_ERR_INVALID_ARGUMENT, "condition must be given iff num_conditional_channels > 0");
     if (c.with_time_emb && !time_dev) return fail(e, DYF_ERR_INVALID_ARGUMENT, "time must be given when with_time_emb");
     if (const char* why = net_record_refusal(e, n)) return fail(e, DYF_ERR_UNSUPPORTED, why);
+    if (n.sc && e->train_precision == 16)
+        return fail(e, DYF_ERR_UNSUPPORTED, "training step: SimpleConvNet records in fp32 -- 16-bit conv operands (dyf_train_set_precision(16)) are not supported for it");
     const int hw = e->cfg.height * e->cfg.width;
     e->train->stream = st;
     if (!e->train->tape[slot]) e->train->tape[slot] = new RTape();
@@ -1999,7 +2037,7 @@ static dyf_status rn_export_param(dyf_engine* e, float* stage, const RParam& p, 
 // gradients (and running statistics) by state_dict name in PyTorch layouts (dyf_train_export, dyf_train_export_dev)
 dyf_status train_export(dyf_engine* e, int which, int n_tensors, const char* const* names, float* const* out, bool dev) {
     TrainNet* t = e->train ? e->train->net[which] : nullptr;
-    if (!t || !t->ready) return fail(e, DYF_ERR_STATE, "training needs arch unet_simple / unet with loaded weights");
+    if (!t || !t->ready) return fail(e, DYF_ERR_STATE, "training needs loaded weights (dyf_load_weights)");
     TK(hipDeviceSynchronize());
     std::vector<void*> tmp;
     size_t stage_n = 0;
@@ -2037,7 +2075,7 @@ dyf_status f32_op_train(dyf_engine* e, const dyf_train_op* dp, const float* cons
     const bool has_c2 = d.op == DYF_TOP_CONV || d.op == DYF_TOP_LINEAR || d.op == DYF_TOP_CAT || d.op == DYF_TOP_CONVT;
     const int flags_ok = d.op == DYF_TOP_CONV ? (DYF_TOP_WS | DYF_TOP_BIAS) : d.op == DYF_TOP_GN_ACT ? DYF_TOP_FILM : d.op == DYF_TOP_LINEAR ? DYF_TOP_PRE
                          : d.op == DYF_TOP_ADD ? DYF_TOP_SAME
-                         : d.op == DYF_TOP_NORM_ACT ? (DYF_TOP_FILM | DYF_TOP_RUNNING | DYF_TOP_MASK | DYF_TOP_LEAKY | DYF_TOP_RELU)
+                         : d.op == DYF_TOP_NORM_ACT ? (DYF_TOP_FILM | DYF_TOP_RUNNING | DYF_TOP_MASK | DYF_TOP_LEAKY | DYF_TOP_RELU | DYF_TOP_ACT_GELU | DYF_TOP_RESIDUAL)
                          : d.op == DYF_TOP_UP2_BILINEAR ? DYF_TOP_GRAD_IN : d.op == DYF_TOP_RESIZE ? DYF_TOP_NEAREST : 0;
     if (d.op < DYF_TOP_CONV || d.op > DYF_TOP_ATTENTION_STREAM) return refuse(DYF_ERR_INVALID_ARGUMENT, "unknown op");
     if (d.flags & ~flags_ok) return refuse(DYF_ERR_INVALID_ARGUMENT, "a flag this op does not take");
@@ -2049,7 +2087,7 @@ dyf_status f32_op_train(dyf_engine* e, const dyf_train_op* dp, const float* cons
         return refuse(DYF_ERR_INVALID_ARGUMENT, "k / stride / pad: a conv geometry with at least one output pixel, the output size of a resize, 0 for every other op");
     if (d.op == DYF_TOP_GN_ACT ? (d.groups < 1 || d.c % d.groups != 0) : d.op == DYF_TOP_NORM_ACT ? (d.groups < 0 || (d.groups > 0 && d.c % d.groups != 0)) : d.groups != 0)
         return refuse(DYF_ERR_INVALID_ARGUMENT, "groups must divide c for gn_act / norm_act (norm_act: 0 = BatchNorm) and be 0 otherwise");
-    if (d.op == DYF_TOP_NORM_ACT && (((d.flags & DYF_TOP_RUNNING) && d.groups > 0) || ((d.flags & DYF_TOP_LEAKY) && (d.flags & DYF_TOP_RELU)) || ((d.flags & DYF_TOP_MASK) && !(d.p > 0.0f))))
+    if (d.op == DYF_TOP_NORM_ACT && (((d.flags & DYF_TOP_RUNNING) && d.groups > 0) || (!!(d.flags & DYF_TOP_LEAKY) + !!(d.flags & DYF_TOP_RELU) + !!(d.flags & DYF_TOP_ACT_GELU) > 1) || ((d.flags & DYF_TOP_MASK) && !(d.p > 0.0f))))
         return refuse(DYF_ERR_INVALID_ARGUMENT, "norm_act: running statistics are BatchNorm's, one activation, a mask needs p > 0");
     if ((d.flags & DYF_TOP_GRAD_IN) && (d.c2 < 1 || !dinputs || !dinputs[1])) return refuse(DYF_ERR_INVALID_ARGUMENT, "up2_bilinear: a gradient to start from needs the second source and its gradient buffer");
     if ((d.op == DYF_TOP_LINEAR || d.op == DYF_TOP_LEARNED_SINU) && (d.h != 1 || d.w != 1)) return refuse(DYF_ERR_INVALID_ARGUMENT, "linear / learned_sinu take rows: h = w = 1");
@@ -2087,6 +2125,7 @@ dyf_status f32_op_train(dyf_engine* e, const dyf_train_op* dp, const float* cons
     case DYF_TOP_NORM_ACT:
         in_n = {xn};
         if (d.flags & DYF_TOP_FILM) in_n.push_back((size_t)d.nb * 2 * d.c);
+        if (d.flags & DYF_TOP_RESIDUAL) in_n.push_back(xn);
         ps = {{"op.weight", {d.c}}, {"op.bias", {d.c}}};
         if (d.groups == 0) { ps.push_back({"op.running_mean", {d.c}}); ps.push_back({"op.running_var", {d.c}}); }
         break;
@@ -2151,7 +2190,7 @@ dyf_status f32_op_train(dyf_engine* e, const dyf_train_op* dp, const float* cons
     X.mem = FwdMem{e, &T.owned, st};
     X.tmp = &tmp;
     X.masks = mask ? &mask : nullptr;
-    RT* in[2] = {nullptr, nullptr};
+    RT* in[3] = {nullptr, nullptr, nullptr};
     if (d.op != DYF_TOP_LEARNED_SINU)
         for (size_t i = 0; i < in_n.size(); ++i) {
             in[i] = X.make(in_n[i]);
@@ -2162,10 +2201,13 @@ dyf_status f32_op_train(dyf_engine* e, const dyf_train_op* dp, const float* cons
     switch (d.op) {
     case DYF_TOP_CONV: y = X.conv(in[0], d.h, d.w, d.c, d.c2, d.k, d.stride, d.pad, "op", (d.flags & DYF_TOP_BIAS) != 0, (d.flags & DYF_TOP_WS) != 0); break;
     case DYF_TOP_GN_ACT: y = X.norm_act(in[0], (int)hw, d.c, "op", in[1], d.p, 2, d.groups, ACT_SILU, rn_norm_ppb((int)hw, d.nb)); break;
-    case DYF_TOP_NORM_ACT:
-        y = X.norm_act(in[0], (int)hw, d.c, "op", in[1], d.p, d.groups > 0 ? 2 : (d.flags & DYF_TOP_RUNNING) ? 1 : 0, d.groups,
-                       (d.flags & DYF_TOP_LEAKY) ? ACT_LEAKY : (d.flags & DYF_TOP_RELU) ? ACT_RELU : ACT_SILU, us_norm_ppb((int)hw));
+    case DYF_TOP_NORM_ACT: {
+        const bool film = (d.flags & DYF_TOP_FILM) != 0;
+        y = X.norm_act(in[0], (int)hw, d.c, "op", film ? in[1] : nullptr, d.p, d.groups > 0 ? 2 : (d.flags & DYF_TOP_RUNNING) ? 1 : 0, d.groups,
+                       (d.flags & DYF_TOP_LEAKY) ? ACT_LEAKY : (d.flags & DYF_TOP_RELU) ? ACT_RELU : (d.flags & DYF_TOP_ACT_GELU) ? ACT_GELU : ACT_SILU,
+                       us_norm_ppb((int)hw), -1, (d.flags & DYF_TOP_RESIDUAL) ? in[film ? 2 : 1] : nullptr);
         break;
+    }
     case DYF_TOP_UP2_BILINEAR: y = X.up2_bilinear(in[0], d.c, in[1], d.c2, d.h, d.w, 2 * d.h, 2 * d.w); break;
     case DYF_TOP_RESIZE: y = X.resize(in[0], d.h, d.w, d.c, d.k, d.stride, (d.flags & DYF_TOP_NEAREST) ? 1 : 0); break;
     case DYF_TOP_CONVT: y = X.conv_transpose4s2(in[0], d.h, d.w, d.c, d.c2, "op"); break;

@@ -528,7 +528,7 @@ class DYffusion(nn.Module):
         eval mode with its Dropout active (:154-160: `self.training or enable_interpolator_dropout`); both loss terms; the
         second term is differentiated THROUGH the interpolator.  Returns the reference's dict ("train/" prefix); `out["loss"]`
         is a scalar tensor whose `.backward()` runs the engine's backward pass and ACCUMULATES into `param.grad` of the
-        forecaster's parameters (so `torch.optim` / Lightning's `training_step` work unchanged).  arch unet_simple, fp32."""
+        forecaster's parameters (so `torch.optim` / Lightning's `training_step` work unchanged).  Every backbone; fp32 tensors."""
         lam1, lam2 = self.hparams.lambda_reconstruction, self.hparams.lambda_reconstruction2
         kind = self.hparams.loss_function
         eng = self._ensure_engine(xt_last.shape[-2:], xt_last.shape[0], sync=False)

@@ -598,7 +598,7 @@ class HipEngine:
                                             self._stream()))
         return out.value
 
-    # ------------------------------------------------------------------ training step (arch unet_simple, fp32)
+    # ------------------------------------------------------------------ training step (every arch, fp32 tensors)
     def train_forward(self, net: int, slot: int, inputs: torch.Tensor, time: Optional[torch.Tensor],
                       condition: Optional[torch.Tensor], batch_stats: bool, dropout: bool) -> torch.Tensor:
         """One RECORDED forward (tape `slot`, 0..3): batch-statistics BatchNorm iff `batch_stats`, Dropout iff `dropout`."""
@@ -824,7 +824,8 @@ class HipEngine:
 
     def op_train(self, op: str, inputs, params=(), dout: Optional[torch.Tensor] = None, grads_in=None, *, k: int = 0, stride: int = 0,
                  pad: int = 0, groups: int = 0, p: float = 0.0, ws: bool = False, pre: bool = False, act: str = "silu", running: bool = False,
-                 mask: Optional[torch.Tensor] = None, size=None, nearest: bool = False, skip_grad: Optional[torch.Tensor] = None) -> Dict[str, object]:
+                 mask: Optional[torch.Tensor] = None, size=None, nearest: bool = False, skip_grad: Optional[torch.Tensor] = None,
+                 residual: Optional[torch.Tensor] = None) -> Dict[str, object]:
         """Test seam (dyf_op_train_f32): ONE recorded op of the training step (either backbone) and its adjoint, through the training
         step's own launch code.  `inputs`: fp32 tensors on the device, activations NHWC (nb, h, w, c) -- rows (nb, c) for "linear", times (nb,)
         for "learned_sinu"; "add" with one input is add(a, a).  `params`: fp32 tensors in PyTorch layouts, in the header's order (conv:
@@ -838,8 +839,15 @@ class HipEngine:
         their concatenation; `skip_grad`: the gradient the second source already has), "resize" (`size` = (oh, ow), which travels in the
         descriptor's k and stride fields; `nearest`), "convt"
         (ConvTranspose2d(c, c2, 4, 2, 1): weight (c, c2, 4, 4), bias).
-        "attention_stream": "attention" in the streaming form a recorded forward takes past 4096 tokens, at any h * w <= 32 767."""
+        "attention_stream": "attention" in the streaming form a recorded forward takes past 4096 tokens, at any h * w <= 32 767.
+        SimpleConvNet's block: "norm_act" with `act` "gelu" and `residual` (nb, h, w, c), added behind activation and dropout in the same
+        launch; its gradient is the last entry of "dinputs"."""
         ins = [_f32c(t, "input") for t in inputs]
+        n_plain = len(ins)  # inputs without the residual, which follows them in the pointer array
+        if residual is not None:
+            if op != "norm_act":
+                raise ValueError("residual: norm_act only")
+            ins.append(_f32c(residual, "residual"))
         x = ins[0]
         nb = x.shape[0]
         if op in ("linear", "learned_sinu"):
@@ -878,8 +886,9 @@ class HipEngine:
         elif op in ("layernorm", "dropout", "gelu"):
             out_shape = tuple(x.shape)
         elif op == "norm_act":
-            flags = ((L.TOP_FILM if len(ins) > 1 else 0) | (L.TOP_RUNNING if running else 0) | (L.TOP_MASK if mask is not None else 0)
-                     | {"silu": 0, "leaky": L.TOP_LEAKY, "relu": L.TOP_RELU}[act])
+            flags = ((L.TOP_FILM if n_plain > 1 else 0) | (L.TOP_RUNNING if running else 0) | (L.TOP_MASK if mask is not None else 0)
+                     | (L.TOP_RESIDUAL if residual is not None else 0)
+                     | {"silu": 0, "leaky": L.TOP_LEAKY, "relu": L.TOP_RELU, "gelu": L.TOP_ACT_GELU}[act])
             out_shape = tuple(x.shape)
         elif op == "up2_bilinear":
             c2 = ins[1].shape[3] if len(ins) > 1 else 0
@@ -897,11 +906,13 @@ class HipEngine:
         want_in = {"gn_act": (1, 2), "norm_act": (1, 2), "up2_bilinear": (1, 2), "add": (1, 2), "cat": (2, 2)}.get(op, (1, 1))
         want_p = {"conv": (1, 2), "gn_act": (2, 2), "norm_act": (2, 2) if groups else (4, 4), "convt": (2, 2), "layernorm": (1, 1), "linear": (2, 2),
                   "learned_sinu": (1, 1)}.get(op, (0, 0))
-        if not (want_in[0] <= len(ins) <= want_in[1]) or not (want_p[0] <= len(ps) <= want_p[1]):
+        if not (want_in[0] <= n_plain <= want_in[1]) or not (want_p[0] <= len(ps) <= want_p[1]):
             raise ValueError(f"{op}: {len(ins)} inputs and {len(ps)} parameters")
         expect = {"conv": [(nb, h, w, c)], "gn_act": [(nb, h, w, c), (nb, 2 * c)], "norm_act": [(nb, h, w, c), (nb, 2 * c)],
                   "up2_bilinear": [(nb, h, w, c), (nb, h, w, c2)], "add": [tuple(x.shape)] * 2, "cat": [(nb, h, w, c), (nb, h, w, c2)],
                   "linear": [(nb, c)], "learned_sinu": [(nb,)]}.get(op, [tuple(x.shape)])
+        if residual is not None:
+            expect = expect[:n_plain] + [(nb, h, w, c)]
         for t, sh in zip(ins, expect):
             if tuple(t.shape) != sh:
                 raise ValueError(f"{op}: an input has shape {tuple(t.shape)}, expected {sh}")

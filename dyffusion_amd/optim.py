@@ -42,8 +42,9 @@ def ema_decay_at(decay: float, num_updates: int) -> float:
 
 
 class EngineAdamW(torch.optim.Optimizer):
-    """AdamW whose state and arithmetic live in the HIP engine.  `owner`: a `DYffusion` in training mode (its forecaster is
-    trained, the interpolator stays frozen) or a `UNet` / `Unet` trained through its own `get_loss` (stage 1).
+    """AdamW whose state and arithmetic live in the HIP engine.  `owner`: a `DYffusion` in training mode (its forecaster -- any of the
+    three backbones -- is trained, the interpolator stays frozen) or a `UNet` / `Unet` trained through its own `get_loss` (stage 1; a
+    stand-alone `SimpleConvNet` is refused: its stage 1 trains through `param.grad` and torch.optim).
 
     While attached, `loss.backward()` leaves the gradients in the engine, where they accumulate until `step()`; `param.grad` stays
     None.  After a step the torch module is stale until `pull()`, which runs by itself before anything reads the module (sampling,
@@ -54,8 +55,9 @@ class EngineAdamW(torch.optim.Optimizer):
                  max_grad_norm: Optional[float] = None, ema_decay: Optional[float] = None):
         from .simple_conv_net import SimpleConvNet
         net = getattr(owner, "model", owner) if hasattr(owner, "p_losses") else owner
-        if isinstance(net, SimpleConvNet):
-            raise NotImplementedError("EngineAdamW: SimpleConvNet has no engine training step (arch unet_simple and unet.Unet)")
+        if isinstance(owner, SimpleConvNet):  # (as a DYffusion's forecaster it is trained resident like the other backbones)
+            raise NotImplementedError("EngineAdamW: a stand-alone SimpleConvNet (stage 1) trains through param.grad and torch.optim; "
+                                      "the engine-resident optimizer serves it as the forecaster of a DYffusion")
         if not (isinstance(net, torch.nn.Module) and hasattr(net, "engine_net_config") and hasattr(net, "_train_backward")):
             raise TypeError(f"EngineAdamW: owner must be a DYffusion, a UNet or a Unet, got {type(owner).__name__}")
         if not lr >= 0.0:

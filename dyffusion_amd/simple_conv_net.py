@@ -23,7 +23,11 @@ def _conv_block(cin: int, cout: int, k: int, time_dim: Optional[int], dropout: f
 
 
 class SimpleConvNet(UNet):
-    """Engine plumbing (attach_engine / load_state_dict / forward / MC-dropout scope) is shared with `UNet`."""
+    """Engine plumbing (attach_engine / load_state_dict / forward / MC-dropout scope) is shared with `UNet`, and so is the training
+    path: `get_loss` in train mode records the fp32 forward on the engine (csrc/train_resnet.inc sc_walk: batch-statistics BatchNorm
+    with running-statistics update, Dropout active) and `loss.backward()` runs its backward into `param.grad`; as the forecaster
+    of a `DYffusion` it is also served by the engine-resident `dyffusion_amd.EngineAdamW` (which refuses a stand-alone SimpleConvNet).  fp32 conv operands only: `train_precision=16` is
+    refused (NotImplementedError) at the first training forward."""
 
     def __init__(self, dim: int, with_time_emb: bool = False, net_normalization: str = "batch_norm",
                  kernel_sizes: Sequence[int] = (7, 3, 3), keep_spatial_shape: bool = True, residual: bool = True,

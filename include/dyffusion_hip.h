@@ -287,8 +287,8 @@ dyf_status dyf_ensemble_metrics(dyf_engine* engine, const float* preds_dev, cons
 typedef enum dyf_sampler_state { DYF_STATE_X0_HAT = 0, DYF_STATE_X_S = 1, DYF_STATE_X_NEXT = 2 } dyf_sampler_state;
 dyf_status dyf_get_sampler_state(dyf_engine* engine, int32_t what, float* out_dev, int32_t nb, void* stream);
 
-/* ---- training step: DYffusion.p_losses in training mode (dyffusion.py:496-567; arch unet_simple) ---------------------------- */
-/* What the reference gets from torch.autograd over unet_simple.py.  A forward is RECORDED in one of four tape slots (the
+/* ---- training step: DYffusion.p_losses in training mode (dyffusion.py:496-567; every arch) -------------------------------- */
+/* What the reference gets from torch.autograd over unet_simple.py / unet.py / simple_conv_net.py.  A forward is RECORDED in one of four tape slots (the
  * objective runs up to two interpolator and two forecaster forwards); dyf_train_backward consumes a slot: gradient of a
  * scalar loss w.r.t. the network's parameters (accumulated into the engine's gradient buffers when param_grads != 0) and,
  * when dinputs_dev != NULL, w.r.t. its `inputs` (NB,in_channels,H,W) -- the frozen interpolator is differentiated through.
@@ -297,7 +297,8 @@ dyf_status dyf_get_sampler_state(dyf_engine* engine, int32_t what, float* out_de
  * streams as sampling; the backward re-derives the masks).  All arithmetic fp32.
  * unet.Unet: up to 4096 bottleneck tokens the Attention keeps its (tokens x tokens) probabilities for the backward; beyond that the
  * forward keeps the softmax statistics (max, 1 / sum) per (row, head, token) and the backward recomputes the scores tile by tile (nothing of size tokens^2 is
- * written; gradients are bitwise repeatable); more than 32 767 tokens: DYF_ERR_UNSUPPORTED, as in fp32 sampling. */
+ * written; gradients are bitwise repeatable); more than 32 767 tokens: DYF_ERR_UNSUPPORTED, as in fp32 sampling.
+ * SimpleConvNet records with fp32 conv operands only: after dyf_train_set_precision(16) its dyf_train_forward returns DYF_ERR_UNSUPPORTED. */
 #define DYF_TRAIN_BATCH_STATS 1
 #define DYF_TRAIN_DROPOUT 2
 dyf_status dyf_train_forward(dyf_engine* engine, int32_t net, int32_t slot, const float* inputs_dev, const float* time_dev,
@@ -348,8 +349,7 @@ dyf_status dyf_criterion_grad(dyf_engine* engine, const float* pred_dev, const f
 /* The last third of a training iteration on the engine's own copies: fp32 master weights, gradients (what dyf_train_backward
  * accumulated), exp_avg / exp_avg_sq and -- optionally -- an EMA shadow of the weights never leave the GPU.  What the reference does with
  * torch.optim.AdamW + `gradient_clip_val` (Lightning: torch.nn.utils.clip_grad_norm_) + LitEma (src/models/modules/ema.py).
- *   create   one optimizer per network slot (0 / 1); arch unet_simple and unet.Unet with loaded weights (SimpleConvNet:
- *            DYF_ERR_UNSUPPORTED, no weights: DYF_ERR_STATE).  State starts at zero, the shadow as a copy of the current weights.
+ *   create   one optimizer per network slot (0 / 1); any arch with loaded weights (no weights: DYF_ERR_STATE).  State starts at zero, the shadow as a copy of the current weights.
  *            Creating again replaces the optimizer.  It survives dyf_load_weights of the same network and goes with the engine.
  *   step     two launches on `stream`, no host synchronisation: (1) sum of squares of all gradients, one double per workgroup;
  *            (2) every workgroup re-reduces those partial sums in one fixed order (the norm is bitwise the same in every workgroup

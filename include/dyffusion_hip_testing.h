@@ -154,7 +154,9 @@ dyf_status dyf_train_conv_check(dyf_engine* engine, int32_t kind, int32_t n, int
  *               batch statistics (running statistics updated, momentum 0.1), DYF_TOP_RUNNING: normalise by the running statistics.  SiLU, or
  *               DYF_TOP_LEAKY (slope 0.2) / DYF_TOP_RELU; dropout p from the generator, or with DYF_TOP_MASK from a uint8 keep mask (nb,h,w,c)
  *               that follows the inputs in inputs_dev -- the sampling path's injected masks: the forward alone runs, no gradient is written.
- *               Sum kernels on unet_simple's grid (GN_ACT: the ResNet-UNet's)
+ *               Sum kernels on unet_simple's grid (GN_ACT: the ResNet-UNet's).  SimpleConvNet's block: DYF_TOP_ACT_GELU = exact (erf) GELU as the
+ *               activation; DYF_TOP_RESIDUAL = one more input r (nb,h,w,c) behind the FiLM (in front of a mask), y = keep * act(..) + r in the
+ *               same launch, and one more returned gradient (dinputs_dev entry of r)
  *   UP2_BILINEAR x (nb,h,w,c) [, x2 (nb,h,w,c2): the upsample of cat([x, x2]) without the concat] -> (nb,2h,2w,c+c2), bilinear
  *               align_corners=False; DYF_TOP_GRAD_IN: dinputs_dev[1] is IN/OUT, the gradient x2 already has from another consumer
  *   RESIZE      x (nb,h,w,c) -> (nb,k,stride,c): F.interpolate(size=(k, stride)), bilinear align_corners=False or DYF_TOP_NEAREST
@@ -179,6 +181,8 @@ typedef enum dyf_train_op_kind {
 #define DYF_TOP_RELU 256
 #define DYF_TOP_NEAREST 512
 #define DYF_TOP_GRAD_IN 1024
+#define DYF_TOP_ACT_GELU 2048
+#define DYF_TOP_RESIDUAL 4096
 typedef struct dyf_train_op {
     int32_t op, nb, h, w, c, c2, k, stride, pad, groups, flags;
     float p;
