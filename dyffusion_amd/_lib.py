@@ -111,6 +111,25 @@ TOP_RUNNING, TOP_MASK, TOP_LEAKY, TOP_RELU, TOP_NEAREST, TOP_GRAD_IN = 32, 64, 1
 TOP_ACT_GELU, TOP_RESIDUAL = 2048, 4096
 
 
+class SampleOp(C.Structure):
+    """dyf_sample_op (include/dyffusion_hip_testing.h): one 16-bit sampling kernel's launch for dyf_op_sample16."""
+    _fields_ = [(k, C.c_int32) for k in ("op", "nb", "h", "w", "c", "c2", "k", "pad", "groups", "act", "flags", "film_stride", "film_div",
+                                         "part_slots", "nsrc")] + [("ch", C.c_int32 * 4), ("drop_mode", C.c_int32), ("drop_p", C.c_float),
+                                                                   ("drop_site", C.c_int32), ("drop_row_offset", C.c_uint32), ("drop_forward", C.c_uint32)]
+
+
+class SampleTensors(C.Structure):
+    """dyf_sample_tensors: the device pointers of one dyf_op_sample16 call; NULL = absent."""
+    _fields_ = [("x", C.c_void_p * 4), ("residual", C.c_void_p), ("film_a", C.c_void_p), ("film_c", C.c_void_p), ("part", C.c_void_p),
+                ("mask", C.c_void_p), ("y", C.c_void_p)]
+
+
+SAMPLE_OPS = {"gn_act": 0, "layernorm_c": 1, "head": 2, "up2_nearest": 3, "drop16": 4, "stem_conv": 5, "groupnorm_f32": 6, "up2_bilinear": 7,
+              "up2_epilogue": 8}
+SOP_NO_STATS = 1
+ACTS = {"none": 0, "relu": 1, "leaky": 2, "silu": 3, "gelu": 4}
+
+
 class OptimConfig(C.Structure):
     """dyf_optim_config (include/dyffusion_hip.h): the engine-resident AdamW / EMA step."""
     _fields_ = [("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double), ("weight_decay", C.c_double),
@@ -167,6 +186,7 @@ SYMBOLS = [
     ("dyf_op_attention_dropout", C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_float, _P, _P]),
     ("dyf_op_attention_f32", C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_float, _P, C.c_int32, _P, _P]),
     ("dyf_op_train_f32", C.c_int, [_P, C.POINTER(TrainOp), C.POINTER(_P), C.POINTER(_P), _P, _P, C.POINTER(_P), C.POINTER(_P), _P]),
+    ("dyf_op_sample16", C.c_int, [_P, C.POINTER(SampleOp), C.POINTER(SampleTensors), C.POINTER(_P), _P]),
     ("dyf_criterion", C.c_int, [_P, _P, _P, C.c_int64, C.c_int32, _P, _P]),
     ("dyf_train_forward", C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int32, C.c_int32, _P]),
     ("dyf_train_backward", C.c_int, [_P, C.c_int32, _P, _P, C.c_int32, _P]),

@@ -1929,6 +1929,37 @@ dyf_status dyf_debug_read_block_output(dyf_engine* e, int32_t which, int32_t lay
     return DYF_OK;
 }
 
+// Dropout of the op seams (dyf_conv_ex's fields; dyf_sample_op carries the same): the checks, and the arming of a launch's DropSpec.
+static dyf_status op_drop_check(dyf_engine* e, int n, int mode, float p, const uint8_t* mask, int site) {
+    if (mode < 0 || mode > 2 || !(p >= 0.0f && p < 1.0f)) return fail(e, DYF_ERR_INVALID_ARGUMENT, "dropout: mode 0..2, 0 <= p < 1");
+    if (mode == 2 && !mask) return fail(e, DYF_ERR_INVALID_ARGUMENT, "dropout mode 2 needs the keep mask");
+    if (mode == 1 && (n > 2 * e->cfg.max_batch || site < 0))
+        return fail(e, DYF_ERR_INVALID_ARGUMENT, "dropout mode 1: more rows than the engine's row-key table (2 max_batch), or a negative site");
+    return DYF_OK;
+}
+static dyf_status op_drop_arm(dyf_engine* e, int n, int mode, float p, const uint8_t* mask, int site, uint32_t row_offset, uint32_t forward,
+                              hipStream_t st, DropSpec* d) {
+    if (mode != 0) {
+        d->mode = mode;
+        d->scale = 1.0f / (1.0f - p);
+        d->thresh16 = keep_threshold16(p);
+        d->mask = mode == 2 ? mask : nullptr;
+    }
+    if (mode == 1) {
+        // masks of the engine's generator at forward `forward`, global rows row_offset .. + n - 1, site `site`: the counters are
+        // set, then the launch is armed exactly as dyf_op_attention_dropout does (which also advances the forward counter)
+        const uint32_t words[2] = {forward, row_offset};
+        HIP_TRY(e, hipDeviceSynchronize());
+        HIP_TRY(e, hipMemcpy(e->rng_state + 2, words, sizeof(words), hipMemcpyHostToDevice));
+        e->row_offset = row_offset;
+        e->row_offset_known = true;
+        HIP_TRY(e, launch_rng_begin_forward(e->rng_state, e->row_keys, n, n, st));
+        d->salt = rng_layer_salt((uint32_t)site);
+        d->row_keys = e->row_keys;
+    }
+    return DYF_OK;
+}
+
 dyf_status dyf_op_conv2d(dyf_engine* e, const uint16_t* x_dev, const float* w_host, int32_t n, int32_t h, int32_t w,
                          int32_t cin, int32_t cout, int32_t kh, int32_t kw, int32_t stride, int32_t pad,
                          const float* scale_dev, const float* shift_dev, int32_t act, int32_t path, uint16_t* y_dev,
@@ -1952,11 +1983,7 @@ dyf_status dyf_op_conv2d_ex(dyf_engine* e, const uint16_t* x_dev, const float* w
     if (x.coef_div < 0 || x.n_sel < 0) return fail(e, DYF_ERR_INVALID_ARGUMENT, "coef_div / n_sel must not be negative");
     if (x.coef_div > 1 && !(scale_dev && shift_dev)) return fail(e, DYF_ERR_INVALID_ARGUMENT, "coef_div needs scale and shift");
     if ((scale_dev == nullptr) != (shift_dev == nullptr)) return fail(e, DYF_ERR_INVALID_ARGUMENT, "scale and shift go together");
-    if (x.drop_mode < 0 || x.drop_mode > 2 || !(x.drop_p >= 0.0f && x.drop_p < 1.0f))
-        return fail(e, DYF_ERR_INVALID_ARGUMENT, "dropout: mode 0..2, 0 <= p < 1");
-    if (x.drop_mode == 2 && !x.mask_dev) return fail(e, DYF_ERR_INVALID_ARGUMENT, "dropout mode 2 needs the keep mask");
-    if (x.drop_mode == 1 && (n > 2 * e->cfg.max_batch || x.drop_site < 0))
-        return fail(e, DYF_ERR_INVALID_ARGUMENT, "dropout mode 1: more rows than the engine's row-key table (2 max_batch), or a negative site");
+    { dyf_status ds = op_drop_check(e, n, x.drop_mode, x.drop_p, x.mask_dev, x.drop_site); if (ds != DYF_OK) return ds; }
     const int cin = c0 + x.c1;
     const long long ho = ((long long)h + 2 * pad - kh) / stride + 1, wo = ((long long)w + 2 * pad - kw) / stride + 1;
     if (h + 2 * pad < kh || w + 2 * pad < kw) return fail(e, DYF_ERR_INVALID_ARGUMENT, "kernel larger than the padded input");
@@ -1986,24 +2013,7 @@ dyf_status dyf_op_conv2d_ex(dyf_engine* e, const uint16_t* x_dev, const float* w
         if (us != DYF_OK) return us;
         a.coef_a = ones; a.coef_c = zeros; a.coef_stride = 0;
     }
-    if (x.drop_mode != 0) {
-        a.drop.mode = x.drop_mode;
-        a.drop.scale = 1.0f / (1.0f - x.drop_p);
-        a.drop.thresh16 = keep_threshold16(x.drop_p);
-        a.drop.mask = x.drop_mode == 2 ? x.mask_dev : nullptr;
-    }
-    if (x.drop_mode == 1) {
-        // masks of the engine's generator at forward `drop_forward`, global rows drop_row_offset .. + n - 1, site `drop_site`: the
-        // counters are set, then the launch is armed exactly as dyf_op_attention_dropout does (which also advances the forward counter)
-        const uint32_t words[2] = {x.drop_forward, x.drop_row_offset};
-        HIP_TRY(e, hipDeviceSynchronize());
-        HIP_TRY(e, hipMemcpy(e->rng_state + 2, words, sizeof(words), hipMemcpyHostToDevice));
-        e->row_offset = x.drop_row_offset;
-        e->row_offset_known = true;
-        HIP_TRY(e, launch_rng_begin_forward(e->rng_state, e->row_keys, n, n, st));
-        a.drop.salt = rng_layer_salt((uint32_t)x.drop_site);
-        a.drop.row_keys = e->row_keys;
-    }
+    { dyf_status ds = op_drop_arm(e, n, x.drop_mode, x.drop_p, x.mask_dev, x.drop_site, x.drop_row_offset, x.drop_forward, st, &a.drop); if (ds != DYF_OK) return ds; }
     dyf_status rs = DYF_OK;
     // (GELU has no MFMA epilogue: launch_conv sends it to the direct kernel, as it does for the engine's own GELU convs)
     ConvArgs geom = a;
@@ -2164,6 +2174,151 @@ dyf_status dyf_op_train_f32(dyf_engine* e, const dyf_train_op* desc, const float
     if (!e || !desc || !inputs_dev || !dout_dev || !y_dev) return fail(e, DYF_ERR_INVALID_ARGUMENT, "dyf_op_train_f32: bad arguments");
     HIP_TRY(e, hipSetDevice(e->cfg.device));
     return f32_op_train(e, desc, inputs_dev, params_host, dout_dev, y_dev, dinputs_dev, dparams_host, (hipStream_t)stream);
+}
+
+dyf_status dyf_op_sample16(dyf_engine* e, const dyf_sample_op* desc, const dyf_sample_tensors* t, const float* const* params_host, void* stream) {
+    if (!e || !desc || !t || !t->x[0] || !t->y) return fail(e, DYF_ERR_INVALID_ARGUMENT, "dyf_op_sample16: null argument");
+    const dyf_sample_op& d = *desc;
+    if (d.op < DYF_SOP_GN_ACT || d.op > DYF_SOP_UP2_EPILOGUE) return fail(e, DYF_ERR_INVALID_ARGUMENT, "dyf_op_sample16: unknown op");
+    if (d.nb < 1 || d.h < 1 || d.w < 1 || d.c < 1 || d.c2 < 0 || d.k < 0 || d.pad < 0 || d.groups < 0 || d.film_stride < 0 || d.film_div < 0 ||
+        d.part_slots < 0 || d.nsrc < 0 || (d.flags & ~DYF_SOP_NO_STATS))
+        return fail(e, DYF_ERR_INVALID_ARGUMENT, "dyf_op_sample16: bad geometry or flags");
+    const int op = d.op;
+    const bool gn = op == DYF_SOP_GN_ACT, gnf = op == DYF_SOP_GROUPNORM_F32, epi = op == DYF_SOP_UP2_EPILOGUE, stem = op == DYF_SOP_STEM_CONV;
+    const bool up = op == DYF_SOP_UP2_NEAREST || op == DYF_SOP_UP2_BILINEAR || epi;
+    const bool drops = gn || gnf || epi || op == DYF_SOP_LAYERNORM_C || op == DYF_SOP_DROP16;
+    // fields an op does not use must be 0 / NULL: what the launcher's argument struct cannot express is refused, never dropped
+    const int nparams = (op == DYF_SOP_LAYERNORM_C) ? 1 : (gn || gnf || stem || op == DYF_SOP_HEAD) ? 2 : 0;
+    if (nparams && !params_host) return fail(e, DYF_ERR_INVALID_ARGUMENT, "dyf_op_sample16: the op takes parameters");
+    for (int i = 0; i < nparams; ++i)
+        if (!params_host[i]) return fail(e, DYF_ERR_INVALID_ARGUMENT, "dyf_op_sample16: null parameter");
+    if (!drops && (d.drop_mode != 0 || t->mask)) return fail(e, DYF_ERR_INVALID_ARGUMENT, "dyf_op_sample16: the op has no dropout");
+    if (!(gn || gnf) && d.groups != 0) return fail(e, DYF_ERR_INVALID_ARGUMENT, "dyf_op_sample16: groups on an op without groups");
+    if (!(gn || gnf || epi) && (d.act != 0 || t->film_a || t->film_c || d.film_stride || d.film_div))
+        return fail(e, DYF_ERR_INVALID_ARGUMENT, "dyf_op_sample16: activation / FiLM on an op without them");
+    if (!gn && (t->residual || t->part || d.part_slots || d.flags)) return fail(e, DYF_ERR_INVALID_ARGUMENT, "dyf_op_sample16: residual / part / flags belong to GN_ACT");
+    if (!stem && (d.nsrc || d.k || d.pad || d.ch[0] || d.ch[1] || d.ch[2] || d.ch[3])) return fail(e, DYF_ERR_INVALID_ARGUMENT, "dyf_op_sample16: nsrc / ch / k / pad belong to STEM_CONV");
+    if (!(stem || op == DYF_SOP_HEAD || op == DYF_SOP_UP2_BILINEAR) && d.c2 != 0) return fail(e, DYF_ERR_INVALID_ARGUMENT, "dyf_op_sample16: c2 on an op with one channel count");
+    if ((t->film_a == nullptr) != (t->film_c == nullptr)) return fail(e, DYF_ERR_INVALID_ARGUMENT, "dyf_op_sample16: film_a and film_c go together");
+    if (d.act < ACT_NONE || d.act > (gnf ? ACT_GELU : ACT_SILU)) return fail(e, DYF_ERR_UNSUPPORTED, "dyf_op_sample16: activation outside what the kernels' epilogue dispatches");
+    if (t->film_a && d.film_stride != 0 && d.film_stride < d.c) return fail(e, DYF_ERR_INVALID_ARGUMENT, "dyf_op_sample16: film_stride below c");
+    if (t->film_a && (d.c % 4 == 0) && (d.film_stride % 4 != 0)) return fail(e, DYF_ERR_INVALID_ARGUMENT, "dyf_op_sample16: film rows are read 16 bytes at a time (film_stride % 4)");
+    if (!t->film_a && (d.film_stride || d.film_div)) return fail(e, DYF_ERR_INVALID_ARGUMENT, "dyf_op_sample16: film_stride / film_div without rows");
+    if (gn && d.film_div > 1) return fail(e, DYF_ERR_UNSUPPORTED, "dyf_op_sample16: GN_ACT has one FiLM row per sample");
+    if (gn && t->film_a && d.film_stride == 0) return fail(e, DYF_ERR_INVALID_ARGUMENT, "dyf_op_sample16: GN_ACT needs film_stride >= c");
+    { dyf_status ds = op_drop_check(e, d.nb, d.drop_mode, d.drop_p, t->mask, d.drop_site); if (ds != DYF_OK) return ds; }
+    const long long hw = (long long)d.h * d.w;
+    const long long cout = (op == DYF_SOP_HEAD || stem) ? d.c2 : op == DYF_SOP_UP2_BILINEAR ? d.c + d.c2 : d.c;
+    // element indices (dropout streams, stores) are 32 bit in every kernel here
+    if ((long long)d.nb * hw * (up ? 4 : 1) * std::max<long long>(cout, d.c) >= 0x7F000000ll) return fail(e, DYF_ERR_UNSUPPORTED, "dyf_op_sample16: tensor too large for the kernels' 32-bit element indices");
+    if ((gn || gnf) && (d.groups < 1 || d.c % d.groups != 0)) return fail(e, DYF_ERR_INVALID_ARGUMENT, "dyf_op_sample16: groups must divide c");
+    if (gn && ((t->part != nullptr) != (d.part_slots > 0))) return fail(e, DYF_ERR_INVALID_ARGUMENT, "dyf_op_sample16: part and part_slots go together");
+    if (gn && t->part && (!gn_part_supported(d.c, d.groups) || d.nb > 65535)) return fail(e, DYF_ERR_UNSUPPORTED, "dyf_op_sample16: conv-epilogue partials are not taken at this shape (gn_part_supported)");
+    if (op == DYF_SOP_HEAD && d.c2 < 1) return fail(e, DYF_ERR_INVALID_ARGUMENT, "dyf_op_sample16: HEAD needs c2 output channels");
+    if (op == DYF_SOP_DROP16 && (hw * d.c) % 2 != 0) return fail(e, DYF_ERR_INVALID_ARGUMENT, "dyf_op_sample16: DROP16 draws one keep word per PAIR: odd row");
+    if (op == DYF_SOP_UP2_BILINEAR && ((d.c2 > 0) != (t->x[1] != nullptr))) return fail(e, DYF_ERR_INVALID_ARGUMENT, "dyf_op_sample16: x[1] and c2 > 0 go together");
+    if (epi && (d.c % 4 != 0)) return fail(e, DYF_ERR_UNSUPPORTED, "dyf_op_sample16: UP2_EPILOGUE takes channels four at a time");
+    if (epi && !t->film_a) return fail(e, DYF_ERR_INVALID_ARGUMENT, "dyf_op_sample16: UP2_EPILOGUE needs its coefficient rows");
+    if (stem) {
+        int sum = 0;
+        if (d.nsrc < 1 || d.nsrc > 4) return fail(e, DYF_ERR_INVALID_ARGUMENT, "dyf_op_sample16: STEM_CONV takes 1..4 sources");
+        for (int i = 0; i < 4; ++i) {
+            if ((i < d.nsrc) != (d.ch[i] > 0) || (i < d.nsrc) != (t->x[i] != nullptr)) return fail(e, DYF_ERR_INVALID_ARGUMENT, "dyf_op_sample16: sources and their channel counts go together");
+            sum += d.ch[i];
+        }
+        if (sum != d.c || d.c2 < 1 || d.k < 1 || d.pad >= d.k) return fail(e, DYF_ERR_INVALID_ARGUMENT, "dyf_op_sample16: STEM_CONV: c = sum of ch, c2 >= 1, 0 <= pad < k");
+        if (d.c > DYF_MAX_IN_CH) return fail(e, DYF_ERR_UNSUPPORTED, "dyf_op_sample16: more input channels than a network stem takes");
+        if ((long long)d.k * d.k * d.c * d.c2 * 4 > 160 * 1024) return fail(e, DYF_ERR_UNSUPPORTED, "dyf_op_sample16: stem weights beyond the LDS");
+    }
+    HIP_TRY(e, hipSetDevice(e->cfg.device));
+    hipStream_t st = (hipStream_t)stream;
+    std::vector<void*> tmp;
+    dyf_status rs = DYF_OK;
+    hipError_t le = hipSuccess;
+    {
+        AllocScope scope(e, &tmp);
+        auto upf = [&](const float** dst, const float* host, size_t n) {
+            float* p = nullptr;
+            const dyf_status us = dev_upload(e, &p, std::vector<float>(host, host + n));
+            *dst = p;
+            return us;
+        };
+        DropSpec drop{};
+        const float *p0 = nullptr, *p1 = nullptr;
+        if (nparams >= 1 && !stem && op != DYF_SOP_HEAD) rs = upf(&p0, params_host[0], (size_t)d.c);
+        if (rs == DYF_OK && nparams >= 2 && !stem && op != DYF_SOP_HEAD) rs = upf(&p1, params_host[1], (size_t)d.c);
+        if (rs == DYF_OK && drops) rs = op_drop_arm(e, d.nb, d.drop_mode, d.drop_p, t->mask, d.drop_site, d.drop_row_offset, d.drop_forward, st, &drop);
+        if (rs != DYF_OK) {
+        } else if (gn) {
+            GnActArgs a{};
+            a.x = (const el16_t*)t->x[0]; a.n = d.nb; a.hw = (int)hw; a.c = d.c; a.groups = d.groups; a.gamma = p0; a.beta = p1;
+            a.film_a = t->film_a; a.film_c = t->film_c; a.film_stride = d.film_stride; a.act = d.act; a.drop = drop;
+            a.residual = t->residual; a.out = (el16_t*)t->y; a.part = t->part; a.part_slots = d.part_slots;
+            if (!(d.flags & DYF_SOP_NO_STATS)) rs = dev_alloc(e, &a.stats, gn_stats_doubles((size_t)d.nb, (size_t)d.groups));
+            if (rs == DYF_OK) le = launch_gn_act(a, st);
+        } else if (op == DYF_SOP_LAYERNORM_C) {
+            LayerNormArgs a{};
+            a.x = (const el16_t*)t->x[0]; a.pixels = (long long)d.nb * hw; a.hw = (int)hw; a.c = d.c; a.g = p0; a.drop = drop; a.out = (el16_t*)t->y;
+            le = launch_layernorm_c(a, st);
+        } else if (op == DYF_SOP_HEAD) {
+            HeadArgs a{};
+            a.x = (const el16_t*)t->x[0]; a.n = d.nb; a.hw = (int)hw; a.c = d.c; a.cout = d.c2; a.out = (float*)t->y;
+            rs = upf(&a.wgt, params_host[0], (size_t)d.c2 * d.c);
+            if (rs == DYF_OK) rs = upf(&a.bias, params_host[1], (size_t)d.c2);
+            if (rs == DYF_OK) le = launch_head(a, st);
+        } else if (op == DYF_SOP_UP2_NEAREST) {
+            le = launch_up2x_nearest((const el16_t*)t->x[0], d.nb, d.h, d.w, d.c, (el16_t*)t->y, st);
+        } else if (op == DYF_SOP_DROP16) {
+            le = launch_drop16((const el16_t*)t->x[0], (el16_t*)t->y, d.nb, hw * d.c, drop, st);
+        } else if (stem) {
+            // the weight upload's own packing (unet_resnet.hip rn_load_weights): [tap][cin][dim] fp32, and the hi / lo fragments of
+            // the MFMA form where stem_frag_steps takes the shape
+            StemConvArgs a{};
+            for (int i = 0; i < d.nsrc; ++i) { a.src[i] = (const float*)t->x[i]; a.ch[i] = d.ch[i]; }
+            a.nsrc = d.nsrc; a.cin = d.c; a.n = d.nb; a.h = d.h; a.w = d.w; a.k = d.k; a.pad = d.pad; a.dim = d.c2; a.out = (el16_t*)t->y;
+            const std::vector<float> pk = pack_stem_weights(params_host[0], d.c2, d.c, d.k);
+            rs = upf(&a.wgt, pk.data(), pk.size());
+            if (rs == DYF_OK) rs = upf(&a.bias, params_host[1], (size_t)d.c2);
+            a.ksteps = d.c2 == 64 ? stem_frag_steps(d.k, d.c) : 0;
+            if (rs == DYF_OK && a.ksteps > 0) {
+                std::vector<el16_t> pf((size_t)a.ksteps * 2 * 2 * 64 * 8);
+                pack_stem_frag(pk.data(), d.k, d.c, d.c2, pf.data());
+                el16_t* wf = nullptr;
+                rs = dev_upload(e, &wf, pf);
+                a.wfrag = wf;
+            }
+            if (rs == DYF_OK) le = launch_stem_conv(a, st);
+        } else if (gnf) {
+            GroupNormArgs a{};
+            a.x = (const float*)t->x[0]; a.n = d.nb; a.hw = (int)hw; a.c = d.c; a.groups = d.groups; a.gamma = p0; a.beta = p1;
+            a.film_a = t->film_a; a.film_c = t->film_c; a.film_stride = d.film_stride; a.film_div = d.film_div; a.act = d.act; a.drop = drop;
+            a.out = (el16_t*)t->y;
+            if (!t->film_a) {  // the kernels always apply a FiLM row: ones / zeros, broadcast
+                rs = upf(&a.film_a, std::vector<float>((size_t)d.c, 1.0f).data(), (size_t)d.c);
+                if (rs == DYF_OK) rs = upf(&a.film_c, std::vector<float>((size_t)d.c, 0.0f).data(), (size_t)d.c);
+                a.film_stride = 0;
+            }
+            if (rs == DYF_OK) le = launch_groupnorm(a, st);
+        } else if (op == DYF_SOP_UP2_BILINEAR) {
+            Up2xArgs a{};
+            a.src0 = (const el16_t*)t->x[0]; a.src1 = (const el16_t*)t->x[1]; a.c0 = d.c; a.c1 = d.c2; a.n = d.nb; a.h = d.h; a.w = d.w;
+            a.out = (el16_t*)t->y;
+            le = launch_up2x(a, st);
+        } else {
+            Up2xEpiArgs a{};
+            a.lo = (const float*)t->x[0]; a.n = d.nb; a.h = d.h; a.w = d.w; a.c = d.c; a.coef_a = t->film_a; a.coef_c = t->film_c;
+            a.coef_stride = d.film_stride; a.coef_div = d.film_div; a.act = d.act; a.drop = drop; a.out = (el16_t*)t->y;
+            le = launch_up2x_epilogue(a, st);
+        }
+    }
+    if (rs == DYF_OK) {
+        if (le == hipSuccess) le = hipStreamSynchronize(st);
+        if (le != hipSuccess) rs = fail(e, DYF_ERR_HIP, std::string("dyf_op_sample16: ") + hipGetErrorString(le));
+    } else {
+        (void)hipDeviceSynchronize();  // (release_allocs needs an idle device)
+    }
+    release_allocs(tmp);
+    return rs;
 }
 
 }  // extern "C"

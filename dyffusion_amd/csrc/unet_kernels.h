@@ -2,6 +2,8 @@
 #pragma once
 #include "common.h"
 
+#include <vector>
+
 // init_conv: k x k (7x7, pad 3) conv of the channel-concatenated NCHW fp32 inputs -> NHWC bf16 (unet.py:149-151, :273)
 struct StemConvArgs {
     const float* src[4];
@@ -21,6 +23,14 @@ int stem_frag_steps(int k, int cin);
 // [tap][cin][dim] fp32 -> A fragments of the MFMA stem: [channel][step of the channel][32-channel block][hi/lo part][lane][8] 16-bit
 void pack_stem_frag(const float* wgt, int k, int cin, int dim, el16_t* out);
 hipError_t launch_stem_conv(const StemConvArgs& a, hipStream_t s);
+// init_conv.weight (dim,cin,k,k) -> StemConvArgs::wgt's order [tap][cin][dim] (the weight upload and the op seam pack with this)
+inline std::vector<float> pack_stem_weights(const float* w, int dim, int cin, int k) {
+    std::vector<float> pk((size_t)k * k * cin * dim);
+    for (int co = 0; co < dim; ++co)
+        for (int ci = 0; ci < cin; ++ci)
+            for (int t = 0; t < k * k; ++t) pk[((size_t)t * cin + ci) * dim + co] = w[((size_t)co * cin + ci) * k * k + t];
+    return pk;
+}
 
 // K5: GroupNorm(G) + FiLM + SiLU + Dropout (+ residual) of unet.Block (unet.py:58-76) on a bf16 NHWC tensor
 struct GnActArgs {

@@ -368,11 +368,7 @@ dyf_status rn_load_weights(dyf_engine* e, Net& n, std::map<std::string, TensorVi
         const int64_t ks = c.init_kernel_size;
         NEED(sw, "init_conv.weight", d, (int64_t)n.cin_total, ks, ks);
         NEED(sb, "init_conv.bias", d);
-        std::vector<float> pk((size_t)ks * ks * n.cin_total * d);  // [tap][cin][dim]
-        for (int co = 0; co < d; ++co)
-            for (int ci = 0; ci < n.cin_total; ++ci)
-                for (int t = 0; t < ks * ks; ++t)
-                    pk[((size_t)t * n.cin_total + ci) * d + co] = sw->data[((size_t)co * n.cin_total + ci) * ks * ks + t];
+        const std::vector<float> pk = pack_stem_weights(sw->data, (int)d, n.cin_total, (int)ks);  // [tap][cin][dim]
         UP(r->stem_w, pk); UP(r->stem_b, vec(sb));
         r->stem_ksteps = d == 64 ? stem_frag_steps((int)ks, n.cin_total) : 0;
         if (r->stem_ksteps > 0) {  // MFMA stem: weights as 16-bit hi/lo A fragments, channel-major K

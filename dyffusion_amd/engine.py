@@ -950,6 +950,107 @@ class HipEngine:
             dins = None    # forward only
         return {"y": y, "dinputs": dins, "dparams": gs}
 
+    def op_sample(self, op: str, xs, params=(), *, groups: int = 0, act: str = "none", k: int = 0, pad: int = 0,
+                  film_a: Optional[torch.Tensor] = None, film_c: Optional[torch.Tensor] = None, film_div: int = 0,
+                  residual: Optional[torch.Tensor] = None, part: Optional[torch.Tensor] = None, stats: bool = True,
+                  mask: Optional[torch.Tensor] = None, p: float = 0.0, rng_site: Optional[int] = None, rng_row_offset: int = 0,
+                  rng_forward: int = 0) -> torch.Tensor:
+        """Test seam (dyf_op_sample16): ONE 16-bit sampling kernel between the convs, through its launcher.  `op`: "gn_act",
+        "layernorm_c", "head", "up2_nearest", "drop16", "stem_conv", "groupnorm_f32", "up2_bilinear", "up2_epilogue".  `xs`: the device
+        tensor(s): NHWC (nb, h, w, c) in the engine's 16-bit dtype; fp32 NHWC for "groupnorm_f32" / "up2_epilogue"; up to four fp32 NCHW
+        sources for "stem_conv"; two 16-bit sources for the "up2_bilinear" of a concatenation.  `params`: fp32 tensors in PyTorch
+        layouts (gn_act / groupnorm_f32: gamma, beta; layernorm_c: g; head: weight (cout, c), bias; stem_conv: weight (dim, cin, k, k),
+        bias).  film_a / film_c: fp32 device rows (rows, stride) with stride >= c (up2_epilogue: its coefficient rows), `film_div` samples
+        per row; residual: 16-bit of x's shape; part: fp32 (nb, slots, c / 8, 2) conv-epilogue partials; stats=False: no statistics
+        scratch; mask: uint8 keep mask of the output's shape, or rng_site: the engine's generator.  Returns the output: 16-bit NHWC, or
+        fp32 NCHW for "head"."""
+        if op not in L.SAMPLE_OPS:
+            raise ValueError(f"unknown sampling op {op!r}")
+        xs = [xs] if torch.is_tensor(xs) else list(xs)
+        dt = self.torch_dtype
+        f32_in = op in ("stem_conv", "groupnorm_f32", "up2_epilogue")
+        for t in xs:
+            if t.dtype != (torch.float32 if f32_in else dt) or not t.is_cuda or not t.is_contiguous() or t.dim() != 4:
+                raise ValueError(f"{op}: inputs are contiguous 4-d device tensors of dtype {torch.float32 if f32_in else dt}")
+        if not 1 <= len(xs) <= (4 if op == "stem_conv" else 2 if op == "up2_bilinear" else 1):
+            raise ValueError(f"{op}: {len(xs)} inputs")
+        x = xs[0]
+        ps = [np.ascontiguousarray(t.detach().to("cpu", torch.float32).numpy()) for t in params]
+        desc, tens = L.SampleOp(), L.SampleTensors()
+        desc.op, desc.groups, desc.act, desc.film_div = L.SAMPLE_OPS[op], int(groups), L.ACTS[act], int(film_div)
+        desc.flags = 0 if stats else L.SOP_NO_STATS
+        if op == "stem_conv":
+            nb, _, h, w = x.shape
+            c = sum(t.shape[1] for t in xs)
+            desc.nsrc, desc.k, desc.pad = len(xs), int(k), int(pad)
+            for i, t in enumerate(xs):
+                if (t.shape[0], t.shape[2], t.shape[3]) != (nb, h, w):
+                    raise ValueError("stem_conv: the sources share (nb, h, w)")
+                desc.ch[i] = t.shape[1]
+            if len(ps) != 2 or ps[0].shape[1:] != (c, k, k) or ps[1].shape != (ps[0].shape[0],):
+                raise ValueError("stem_conv: params are weight (dim, cin, k, k) and bias (dim)")
+            desc.c2 = ps[0].shape[0]
+            out_shape, out_dt = (nb, h, w, desc.c2), dt
+        else:
+            nb, h, w, c = x.shape
+            want = {"gn_act": [(c,), (c,)], "groupnorm_f32": [(c,), (c,)], "layernorm_c": [(c,)]}.get(op, [])
+            out_shape, out_dt = (nb, h, w, c), dt
+            if op == "head":
+                if len(ps) != 2 or ps[0].ndim != 2 or ps[0].shape[1] != c:
+                    raise ValueError("head: params are weight (cout, c) and bias (cout)")
+                desc.c2 = ps[0].shape[0]
+                want = [(desc.c2, c), (desc.c2,)]
+                out_shape, out_dt = (nb, desc.c2, h, w), torch.float32
+            elif op == "up2_bilinear":
+                if len(xs) == 2:
+                    if xs[1].shape[:3] != x.shape[:3]:
+                        raise ValueError("up2_bilinear: the sources share (nb, h, w)")
+                    desc.c2 = xs[1].shape[3]
+                out_shape = (nb, 2 * h, 2 * w, c + desc.c2)
+            elif op in ("up2_nearest", "up2_epilogue"):
+                out_shape = (nb, 2 * h, 2 * w, c)
+            if len(ps) != len(want) or any(t.size != int(np.prod(sh)) for t, sh in zip(ps, want)):
+                raise ValueError(f"{op}: parameters must have the shapes {want}")
+        desc.nb, desc.h, desc.w, desc.c = nb, h, w, c
+        for i, t in enumerate(xs):
+            tens.x[i] = t.data_ptr()
+        keep = []  # tensors the call reads: alive until it returns
+        if (film_a is None) != (film_c is None):
+            raise ValueError("film_a and film_c go together")
+        if film_a is not None:
+            film_a, film_c = _f32c(film_a, "film_a"), _f32c(film_c, "film_c")
+            rows = -(-nb // film_div) if film_div > 1 else nb
+            if film_a.dim() != 2 or film_a.shape != film_c.shape or film_a.shape[0] != rows or film_a.shape[1] < c:
+                raise ValueError(f"film rows must be ({rows}, >= {c}) fp32")
+            desc.film_stride = film_a.shape[1]
+            tens.film_a, tens.film_c = film_a.data_ptr(), film_c.data_ptr()
+            keep += [film_a, film_c]
+        if residual is not None:
+            if residual.dtype != dt or not residual.is_cuda or not residual.is_contiguous() or tuple(residual.shape) != tuple(x.shape):
+                raise ValueError("residual: a contiguous 16-bit device tensor of the input's shape")
+            tens.residual = residual.data_ptr()
+        if part is not None:
+            part = _f32c(part, "part")
+            if part.dim() != 4 or part.shape[0] != nb or part.shape[2] * 8 != c or part.shape[3] != 2:
+                raise ValueError("part: fp32 (nb, slots, c / 8, 2)")
+            desc.part_slots = part.shape[1]
+            tens.part = part.data_ptr()
+            keep.append(part)
+        desc.drop_p = float(p)
+        if mask is not None and rng_site is not None:
+            raise ValueError("mask or rng_site, not both")
+        if mask is not None:
+            if mask.dtype != torch.uint8 or not mask.is_cuda or not mask.is_contiguous() or tuple(mask.shape) != out_shape:
+                raise ValueError("mask: a contiguous uint8 device tensor of the output's shape")
+            desc.drop_mode, tens.mask = 2, mask.data_ptr()
+        elif rng_site is not None:
+            desc.drop_mode, desc.drop_site, desc.drop_row_offset, desc.drop_forward = 1, int(rng_site), int(rng_row_offset), int(rng_forward)
+        y = torch.empty(out_shape, dtype=out_dt, device=x.device)
+        tens.y = y.data_ptr()
+        arr = (C.c_void_p * max(len(ps), 1))(*[t.ctypes.data for t in ps])
+        self._check(self._lib.dyf_op_sample16(self._h, C.byref(desc), C.byref(tens), arr, self._stream()))
+        return y
+
     def op_upconv2d(self, x_nhwc_bf16: torch.Tensor, weight: torch.Tensor, scale: Optional[torch.Tensor] = None,
                     shift: Optional[torch.Tensor] = None, act: int = 0) -> torch.Tensor:
         """Test seam: fused Upsample(x2, bilinear) + Conv2d(3x3, pad 1).  x (N,H,W,Cin) bf16 -> (N,2H,2W,Cout) bf16."""

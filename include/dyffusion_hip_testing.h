@@ -190,6 +190,61 @@ typedef struct dyf_train_op {
 dyf_status dyf_op_train_f32(dyf_engine* engine, const dyf_train_op* desc, const float* const* inputs_dev, const float* const* params_host,
                             const float* dout_dev, float* y_dev, float* const* dinputs_dev, float* const* dparams_host, void* stream);
 
+/* ONE 16-bit sampling kernel between the convs (csrc/unet_kernels.hip, csrc/kernels.hip), for float64 parity tests.  The seam fills the
+ * launcher's own argument struct and calls the LAUNCHER, never a kernel: form choice, grid sizes and the DYF_* form switches are the
+ * engine's.  Scratch is provided as a forward provides it (GnActArgs::stats: gn_stats_doubles(nb, groups) doubles).  hw = h * w.
+ *   desc        op kind, geometry, flags; fields an op does not use must be 0
+ *   t           device pointers.  16-bit tensors are bit patterns of the build's element type (bf16 or fp16), NHWC; a NULL entry = absent
+ *   params_host host pointers of the parameters, fp32, PyTorch layouts
+ * op (tensors; parameters):
+ *   GN_ACT        launch_gn_act: x[0] 16-bit (nb,hw,c); gamma (c), beta (c); `groups`; act 0..3.  Optional: film_a / film_c fp32 rows of
+ *                 film_stride >= c floats per sample (y * film_a + film_c); residual 16-bit (nb,hw,c), added after the dropout; part fp32
+ *                 [nb][part_slots][c / 8][2] = the (sum, sum of squares) partials a conv epilogue leaves per 8-channel octet, in place of
+ *                 a statistics pass (shapes gn_part_supported rejects: DYF_ERR_UNSUPPORTED); DYF_SOP_NO_STATS: GnActArgs::stats = NULL
+ *                 (reaches gn_act_kernel, or gn_apply_part_kernel at any slot count); dropout
+ *   LAYERNORM_C   launch_layernorm_c: x[0] 16-bit (nb,hw,c); g (c); dropout
+ *   HEAD          launch_head: x[0] 16-bit (nb,hw,c); weight (c2,c), bias (c2) -> y fp32 NCHW (nb,c2,h,w)
+ *   UP2_NEAREST   launch_up2x_nearest: x[0] 16-bit (nb,h,w,c) -> (nb,2h,2w,c)
+ *   DROP16        launch_drop16: x[0] 16-bit (nb,h,w,c), h * w * c even; dropout
+ *   STEM_CONV     launch_stem_conv: x[0..nsrc-1] fp32 NCHW (nb,ch[i],h,w), c = sum of ch; weight (c2,c,k,k), bias (c2), packed by the code
+ *                 the weight upload uses (pack_stem_frag included when stem_frag_steps takes the shape); taps reach from -pad to k-1-pad
+ *                 -> y 16-bit (nb,h,w,c2)
+ *   GROUPNORM_F32 launch_groupnorm: x[0] fp32 (nb,hw,c); gamma, beta; `groups`; act 0..4; film rows as GN_ACT with film_div samples per
+ *                 row (absent: ones / zeros); dropout -> y 16-bit
+ *   UP2_BILINEAR  launch_up2x: x[0] 16-bit (nb,h,w,c) [, x[1] (nb,h,w,c2): the upsample of the concatenation] -> (nb,2h,2w,c+c2)
+ *   UP2_EPILOGUE  launch_up2x_epilogue: x[0] fp32 (nb,h,w,c), c % 4 == 0; film_a / film_c = the coefficient rows (stride film_stride,
+ *                 film_div samples per row); act 0..3; dropout -> y 16-bit (nb,2h,2w,c) = drop(act(lerp(x) * a + c))
+ * Dropout (ops that end in one): drop_mode 2 = mask, a uint8 keep mask of the output's shape; 1 = the engine's generator at site
+ * drop_site, forward index drop_forward, global rows drop_row_offset .. + nb - 1 (nb <= 2 max_batch), armed by the code dyf_conv_ex's
+ * fields are armed by.  Survivors are scaled by 1 / (1 - drop_p).  Every tensor must stay below the kernels' 32-bit element indices.
+ * What the descriptor cannot express is refused (DYF_ERR_INVALID_ARGUMENT / DYF_ERR_UNSUPPORTED), never truncated.  Synchronises;
+ * everything allocated goes back to the engine. */
+typedef enum dyf_sample_op_kind {
+    DYF_SOP_GN_ACT = 0, DYF_SOP_LAYERNORM_C = 1, DYF_SOP_HEAD = 2, DYF_SOP_UP2_NEAREST = 3, DYF_SOP_DROP16 = 4, DYF_SOP_STEM_CONV = 5,
+    DYF_SOP_GROUPNORM_F32 = 6, DYF_SOP_UP2_BILINEAR = 7, DYF_SOP_UP2_EPILOGUE = 8
+} dyf_sample_op_kind;
+#define DYF_SOP_NO_STATS 1
+typedef struct dyf_sample_op {
+    int32_t op, nb, h, w, c, c2, k, pad, groups, act, flags;
+    int32_t film_stride, film_div, part_slots;
+    int32_t nsrc, ch[4];
+    int32_t drop_mode;
+    float drop_p;
+    int32_t drop_site;
+    uint32_t drop_row_offset, drop_forward;
+} dyf_sample_op;
+typedef struct dyf_sample_tensors {
+    const void* x[4];
+    const uint16_t* residual;
+    const float* film_a;
+    const float* film_c;
+    const float* part;
+    const uint8_t* mask;
+    void* y;
+} dyf_sample_tensors;
+dyf_status dyf_op_sample16(dyf_engine* engine, const dyf_sample_op* desc, const dyf_sample_tensors* t, const float* const* params_host,
+                           void* stream);
+
 /* Read back the output of UNetBlock `layer` (0..11: encoder then decoder blocks) of the most recent unet_simple forward
  * as fp32 NCHW (NB, cout, h, w) -- per-layer parity analysis against the oracle's taps (oracle/nets.py `taps=`).  The last
  * decoder block is returned dense; positions its sparse-column form did not compute are NaN. */
