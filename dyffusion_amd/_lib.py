@@ -44,6 +44,7 @@ def attention_dropout_mode(mode) -> int:
 
 
 DYF_ABI_VERSION = 9
+DYF_TRAIN_PRECISION_BF16X3 = 48  # dyf_train_set_precision: bf16x3 (hi/lo bf16 operand pairs, three MFMAs per product)
 DYF_OK, DYF_ERR_INVALID_ARGUMENT, DYF_ERR_UNSUPPORTED, DYF_ERR_HIP, DYF_ERR_STATE = range(5)
 NET_FORECASTER, NET_INTERPOLATOR = 0, 1
 ARCH_UNET_SIMPLE, ARCH_UNET_RESNET = 0, 1

@@ -161,7 +161,7 @@ struct dyf_engine {
     // overlap: tails of under-filled launches and launch gaps of one group are covered by the others
     std::vector<dyf_engine*> groups;
     bool is_group_child = false;
-    int train_precision = 0;  // dyf_train_set_precision: 0 = DYF_TRAIN_OPERANDS decides (default fp32), 32, 16
+    int train_precision = 0;  // dyf_train_set_precision: 0 = DYF_TRAIN_OPERANDS decides (default fp32), 32, 16, 48 (bf16x3)
     int train_deterministic = 0;  // dyf_train_set_deterministic: 1 = no sum of the training step is merged with atomics
     double* criterion_partials = nullptr;  // deterministic dyf_criterion: one partial sum per workgroup (device, CRITERION_MAX_BLOCKS)
     int form_rows_scale = 1;             // child: kernel forms are chosen for this many times the rows of a launch (the siblings' share)

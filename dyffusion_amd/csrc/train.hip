@@ -1615,7 +1615,8 @@ dyf_status dyf_train_zero_grads(dyf_engine* e, int32_t which) {
 }
 
 dyf_status dyf_train_set_precision(dyf_engine* e, int32_t bits) {
-    if (!e || (bits != 0 && bits != 16 && bits != 32)) return fail(e, DYF_ERR_INVALID_ARGUMENT, "dyf_train_set_precision: bits must be 0, 16 or 32");
+    if (!e || (bits != 0 && bits != 16 && bits != 32 && bits != DYF_TRAIN_PRECISION_BF16X3))
+        return fail(e, DYF_ERR_INVALID_ARGUMENT, "dyf_train_set_precision: bits must be 0, 16, 32 or 48 (DYF_TRAIN_PRECISION_BF16X3)");
     e->train_precision = bits;
     return DYF_OK;
 }
@@ -1710,7 +1711,7 @@ dyf_status f32_net_forward(dyf_engine* e, int which, const Source* srcs, int nsr
 extern "C" {
 
 // operand precision of a recorded forward of network `which` and of its backward: the engine's setting; SimpleConvNet records in fp32
-// whatever the tests' operand switch says (an engine SET to 16 bits is refused by train_forward)
+// whatever the tests' operand switch says, and under bf16x3 (48) too (an engine SET to 16 bits is refused by train_forward)
 static int train_precision_for(const dyf_engine* e, int which) {
     return which >= 0 && which <= 1 && e->net[which].sc && e->train_precision != 16 ? 32 : e->train_precision;
 }
@@ -1975,7 +1976,7 @@ dyf_status dyf_train_conv_check(dyf_engine* e, int32_t kind, int32_t n, int32_t 
     if (const long long k2 = dyf_form_int("DYF_TRAIN_CHECK_DZ_EXP2", 0))
         hipLaunchKernelGGL(t_scale_exp2, dim3(nblk(nz)), dim3(256), 0, st, z, nz, -(int)k2);
     const TrainPrecisionScope precision(e->train_precision);
-    if (train_operands16()) {
+    if (train_operands16()) {  // (not under bf16x3: its forms are held against the fp32 kernels on unrounded operands)
         hipLaunchKernelGGL(t_round16, dim3(nblk(nx)), dim3(256), 0, st, x, nx);
         hipLaunchKernelGGL(t_round16, dim3(nblk(nz)), dim3(256), 0, st, z, nz);
         hipLaunchKernelGGL(t_round16, dim3(nblk(nw)), dim3(256), 0, st, wgt, nw);

@@ -232,12 +232,22 @@ __global__ __launch_bounds__(256) void t_gemm_mfma(dyf::TConv g, const float* __
 // usual mixed-precision trade; the default stays fp32 (1e-6 parity with autograd over the oracle).
 constexpr int GK16 = 32, LDR16 = 40;  // K stage, LDS row pitch in 16-bit elements
 
-template <int MODE>
+// ---- bf16x3 (SPLIT; dyf_train_set_precision(48) / DYF_TRAIN_OPERANDS=bf16x3): every operand value v is staged as TWO bf16 images,
+// hi = bf16(v) and lo = bf16(v - hi) (the subtraction is exact in fp32: hi shares v's exponent and leading 8 bits), and a fragment
+// pair issues three MFMAs into the same accumulators -- a_lo b_hi, a_hi b_lo, then a_hi b_hi; the dropped a_lo b_lo term is 2^-16
+// of the product.  hi + lo carries 16 mantissa bits of v, so a product is off by <= ~2^-16 instead of bf16's 2^-8: rel-RMS 4.5e-6
+// against float64 on the conv cases of tests/train_op_refs.py (one term: 2.4e-3), inside the project's fp32 bound of 1e-5.  Global
+// traffic is that of the 16-bit form (the operands are fp32 in HBM either way), the matrix work 3/16 of the fp32 instruction's.
+// LDS: both images of both operands, still double-buffered = 60 KB per workgroup (30 KB unsplit) -> two workgroups per CU of the
+// 160 KB; a single-buffered 30 KB variant would add a barrier per stage to a kernel that is bound by its operand loads.
+
+template <int MODE, bool SPLIT = false>
 __global__ __launch_bounds__(256) void t_gemm_mfma16(dyf::TConv g, const float* __restrict__ Ap, const float* __restrict__ Bp,
                                                      const float* __restrict__ bias, float* __restrict__ Cp, int split_len, int pmode) {
 #if defined(__HIP_DEVICE_COMPILE__)
-    __shared__ __attribute__((aligned(16))) t16_t As[2][GM * LDR16];
-    __shared__ __attribute__((aligned(16))) t16_t Bs[2][GN * LDR16];
+    constexpr int ALO = GM * LDR16, BLO = GN * LDR16;  // SPLIT: the lo image follows the hi image of the same buffer
+    __shared__ __attribute__((aligned(16))) t16_t As[2][SPLIT ? 2 * GM * LDR16 : GM * LDR16];
+    __shared__ __attribute__((aligned(16))) t16_t Bs[2][SPLIT ? 2 * GN * LDR16 : GN * LDR16];
     constexpr bool WG = MODE == TG_WGRAD || MODE == TG_WGRAD_DET;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l31 = lane & 31, hi = lane >> 5;
@@ -361,21 +371,43 @@ __global__ __launch_bounds__(256) void t_gemm_mfma16(dyf::TConv g, const float* 
 #pragma unroll
             for (int i = 0; i < 4; ++i) {  // 4 consecutive k of one row: one 8-byte store
                 const int s = tid + 256 * i;
-                *(uint2*)&As[buf][(s >> 3) * LDR16 + 4 * (s & 7)] = make_uint2(pack_t16x2(ra[i].x, ra[i].y), pack_t16x2(ra[i].z, ra[i].w));
+                if constexpr (SPLIT) {
+                    const uint32_t h0 = pack_t16x2(ra[i].x, ra[i].y), h1 = pack_t16x2(ra[i].z, ra[i].w);
+                    *(uint2*)&As[buf][(s >> 3) * LDR16 + 4 * (s & 7)] = make_uint2(h0, h1);
+                    *(uint2*)&As[buf][ALO + (s >> 3) * LDR16 + 4 * (s & 7)] =
+                        make_uint2(pack_t16x2_lo(ra[i].x, ra[i].y, h0), pack_t16x2_lo(ra[i].z, ra[i].w, h1));
+                } else
+                    *(uint2*)&As[buf][(s >> 3) * LDR16 + 4 * (s & 7)] = make_uint2(pack_t16x2(ra[i].x, ra[i].y), pack_t16x2(ra[i].z, ra[i].w));
             }
         } else {
 #pragma unroll
             for (int i = 0; i < 4; ++i) {  // 4 consecutive rows (cout) of one k (pixel)
                 const int s = tid + 256 * i, k = s >> 5;
                 t16_t* d = &As[buf][((s & 31) * 4) * LDR16 + k];
-                d[0] = f32_to_t16(ra[i].x); d[LDR16] = f32_to_t16(ra[i].y); d[2 * LDR16] = f32_to_t16(ra[i].z); d[3 * LDR16] = f32_to_t16(ra[i].w);
+                if constexpr (SPLIT) {
+                    const t16_t hx = f32_to_t16(ra[i].x), hy = f32_to_t16(ra[i].y), hz = f32_to_t16(ra[i].z), hw = f32_to_t16(ra[i].w);
+                    d[0] = hx; d[LDR16] = hy; d[2 * LDR16] = hz; d[3 * LDR16] = hw;
+                    d += ALO;
+                    d[0] = f32_to_t16_lo(ra[i].x, hx); d[LDR16] = f32_to_t16_lo(ra[i].y, hy);
+                    d[2 * LDR16] = f32_to_t16_lo(ra[i].z, hz); d[3 * LDR16] = f32_to_t16_lo(ra[i].w, hw);
+                } else {
+                    d[0] = f32_to_t16(ra[i].x); d[LDR16] = f32_to_t16(ra[i].y); d[2 * LDR16] = f32_to_t16(ra[i].z); d[3 * LDR16] = f32_to_t16(ra[i].w);
+                }
             }
         }
 #pragma unroll
         for (int i = 0; i < 2; ++i) {  // 4 consecutive columns n of one k
             const int s = tid + 256 * i, bk = s >> 4, bnq = s & 15;
             t16_t* d = &Bs[buf][(bnq * 4) * LDR16 + bk];
-            d[0] = f32_to_t16(rb[i].x); d[LDR16] = f32_to_t16(rb[i].y); d[2 * LDR16] = f32_to_t16(rb[i].z); d[3 * LDR16] = f32_to_t16(rb[i].w);
+            if constexpr (SPLIT) {
+                const t16_t hx = f32_to_t16(rb[i].x), hy = f32_to_t16(rb[i].y), hz = f32_to_t16(rb[i].z), hw = f32_to_t16(rb[i].w);
+                d[0] = hx; d[LDR16] = hy; d[2 * LDR16] = hz; d[3 * LDR16] = hw;
+                d += BLO;
+                d[0] = f32_to_t16_lo(rb[i].x, hx); d[LDR16] = f32_to_t16_lo(rb[i].y, hy);
+                d[2 * LDR16] = f32_to_t16_lo(rb[i].z, hz); d[3 * LDR16] = f32_to_t16_lo(rb[i].w, hw);
+            } else {
+                d[0] = f32_to_t16(rb[i].x); d[LDR16] = f32_to_t16(rb[i].y); d[2 * LDR16] = f32_to_t16(rb[i].z); d[3 * LDR16] = f32_to_t16(rb[i].w);
+            }
         }
     };
 
@@ -399,6 +431,14 @@ __global__ __launch_bounds__(256) void t_gemm_mfma16(dyf::TConv g, const float* 
         for (int ks = 0; ks < 2; ++ks) {
             const t16x8_t a0 = *(const t16x8_t*)(ar0 + ks * 16), a1 = *(const t16x8_t*)(ar1 + ks * 16);
             const t16x8_t b = *(const t16x8_t*)(br + ks * 16);
+            if constexpr (SPLIT) {  // the two cross terms first, then hi x hi
+                const t16x8_t a0l = *(const t16x8_t*)(ar0 + ALO + ks * 16), a1l = *(const t16x8_t*)(ar1 + ALO + ks * 16);
+                const t16x8_t bl = *(const t16x8_t*)(br + BLO + ks * 16);
+                acc[0] = T16_MFMA_32x32x16(a0l, b, acc[0], 0, 0, 0);
+                acc[1] = T16_MFMA_32x32x16(a1l, b, acc[1], 0, 0, 0);
+                acc[0] = T16_MFMA_32x32x16(a0, bl, acc[0], 0, 0, 0);
+                acc[1] = T16_MFMA_32x32x16(a1, bl, acc[1], 0, 0, 0);
+            }
             acc[0] = T16_MFMA_32x32x16(a0, b, acc[0], 0, 0, 0);
             acc[1] = T16_MFMA_32x32x16(a1, b, acc[1], 0, 0, 0);
         }
@@ -468,9 +508,17 @@ void det_reduce(const double* ws, int splits, long long stride, long long n, dou
 thread_local int g_train_precision = 0;
 bool train_operands16() {
     if (g_train_precision == 16) return true;
-    if (g_train_precision == 32) return false;
+    if (g_train_precision != 0) return false;  // 32, and 48 (bf16x3: train_operands_split)
     const char* v = dyf_form("DYF_TRAIN_OPERANDS");
     return v && (!strcmp(v, "bf16") || !strcmp(v, "16"));
+}
+// bf16x3: the same dispatch rules as the 16-bit forms, every operand staged as a (hi, lo) pair of bf16 and three MFMAs per product --
+// dyf_train_set_precision(48), or DYF_TRAIN_OPERANDS=bf16x3 | 48 for engines that did not say
+bool train_operands_split() {
+    if (g_train_precision == 48) return true;
+    if (g_train_precision != 0) return false;
+    const char* v = dyf_form("DYF_TRAIN_OPERANDS");
+    return v && (!strcmp(v, "bf16x3") || !strcmp(v, "48"));
 }
 
 // split-K plan of a forward / dgrad launch: (splits, stages per split); splits == 1 -> no split
@@ -490,12 +538,16 @@ bool tgemm_conv_fwd(const TConv& g, const float* x, const float* wt, const float
                     hipStream_t st) {
     if (g.cin % GK != 0 || g.cout % GN != 0) return false;
     const long long M = (long long)g.n * g.ho * g.wo, mt = (M + GM - 1) / GM;
-    const bool h16 = train_operands16() && g.cin % GK16 == 0;
+    const bool sp = train_operands_split();
+    const bool h16 = (sp || train_operands16()) && g.cin % GK16 == 0;
     if (h16 && thalo_conv3x3(g, 0, x, wt, bias, y, ws, ws_floats, st)) return true;
     int splits, len;
     plan_splitk(mt * (g.cout / GN), g.k * g.k * g.cin / (h16 ? GK16 : GK), splits, len);
     if (splits > 1 && (ws == nullptr || (size_t)splits * M * g.cout > ws_floats)) { splits = 1; len = 0; }
-    if (h16)
+    if (h16 && sp) {
+        dyf_form_note("t_gemm_mfma16x3<forward>", g.n);
+        hipLaunchKernelGGL((t_gemm_mfma16<TG_FWD, true>), dim3((unsigned)mt, g.cout / GN, splits), dim3(256), 0, st, g, x, wt, bias, splits > 1 ? ws : y, len, 0);
+    } else if (h16)
         hipLaunchKernelGGL(t_gemm_mfma16<TG_FWD>, dim3((unsigned)mt, g.cout / GN, splits), dim3(256), 0, st, g, x, wt, bias, splits > 1 ? ws : y, len, 0);
     else
         hipLaunchKernelGGL(t_gemm_mfma<TG_FWD>, dim3((unsigned)mt, g.cout / GN, splits), dim3(256), 0, st, g, x, wt, bias, splits > 1 ? ws : y, len);
@@ -508,22 +560,29 @@ bool tgemm_conv_dgrad(const TConv& g, const float* dz, const float* w, const flo
                       hipStream_t st) {
     if (g.cout % GK != 0 || g.cin % GN != 0) return false;
     const long long M = (long long)g.n * g.h * g.w, mt = (M + GM - 1) / GM;
-    const bool h16 = train_operands16() && g.cout % GK16 == 0;
+    const bool sp = train_operands_split();
+    const bool h16 = (sp || train_operands16()) && g.cout % GK16 == 0;
     if (h16 && thalo_conv3x3(g, 1, dz, w, bias, dx, ws, ws_floats, st)) return true;
     {   // 4 x 4 / stride 2 / pad 1: one launch slice per parity class of the input pixels (see the kernel); small planes keep split-K
         const bool pclass = dyf_form_int("DYF_TRAIN_DGRAD_PARITY", 1) != 0;  // per call: tests flip it
         const long long mq = ((long long)g.n * g.h * g.w / 4 + GM - 1) / GM;
         if (h16 && pclass && g.k == 4 && g.s == 2 && g.p == 1 && g.h % 2 == 0 && g.w % 2 == 0 && g.ho == g.h / 2 && g.wo == g.w / 2 &&
             mq * (g.cin / GN) >= 64 && mq <= 0x7fffffffll) {
-            dyf_form_note("t_gemm_mfma16:dgrad_parity", g.n);
-            hipLaunchKernelGGL(t_gemm_mfma16<TG_DGRAD>, dim3((unsigned)mq, g.cin / GN, 4), dim3(256), 0, st, g, dz, w, bias, dx, 0, 1);
+            dyf_form_note(sp ? "t_gemm_mfma16x3:dgrad_parity" : "t_gemm_mfma16:dgrad_parity", g.n);
+            if (sp)
+                hipLaunchKernelGGL((t_gemm_mfma16<TG_DGRAD, true>), dim3((unsigned)mq, g.cin / GN, 4), dim3(256), 0, st, g, dz, w, bias, dx, 0, 1);
+            else
+                hipLaunchKernelGGL(t_gemm_mfma16<TG_DGRAD>, dim3((unsigned)mq, g.cin / GN, 4), dim3(256), 0, st, g, dz, w, bias, dx, 0, 1);
             return true;
         }
     }
     int splits, len;
     plan_splitk(mt * (g.cin / GN), g.k * g.k * g.cout / (h16 ? GK16 : GK), splits, len);
     if (splits > 1 && (ws == nullptr || (size_t)splits * M * g.cin > ws_floats)) { splits = 1; len = 0; }
-    if (h16)
+    if (h16 && sp) {
+        dyf_form_note("t_gemm_mfma16x3<dgrad>", g.n);
+        hipLaunchKernelGGL((t_gemm_mfma16<TG_DGRAD, true>), dim3((unsigned)mt, g.cin / GN, splits), dim3(256), 0, st, g, dz, w, bias, splits > 1 ? ws : dx, len, 0);
+    } else if (h16)
         hipLaunchKernelGGL(t_gemm_mfma16<TG_DGRAD>, dim3((unsigned)mt, g.cin / GN, splits), dim3(256), 0, st, g, dz, w, bias, splits > 1 ? ws : dx, len, 0);
     else
         hipLaunchKernelGGL(t_gemm_mfma<TG_DGRAD>, dim3((unsigned)mt, g.cin / GN, splits), dim3(256), 0, st, g, dz, w, bias, splits > 1 ? ws : dx, len);
@@ -539,7 +598,8 @@ bool tgemm_conv_wgrad(const TConv& g, const float* dz, const float* x, float* dw
     const int taps = g.k * g.k, mt = (g.cout + GM - 1) / GM, nt = g.cin / GN;
     // enough workgroups to fill the chip, at least 256 pixels per split
     long long splits = std::max<long long>(1, std::min<long long>((pix + 255) / 256, (2048 + (long long)mt * nt * taps - 1) / ((long long)mt * nt * taps)));
-    const bool h16 = train_operands16();
+    const bool sp = train_operands_split();
+    const bool h16 = sp || train_operands16();
     if (h16 && thalo_wgrad3x3(g, dz, x, dw, ws, ws_floats, st)) return true;
     const int gk = h16 ? GK16 : GK;
     const bool det = train_det();
@@ -552,16 +612,20 @@ bool tgemm_conv_wgrad(const TConv& g, const float* dz, const float* x, float* dw
     if ((long long)taps * splits > 65535) return false;
     if (det) {
         float* C = splits > 1 ? ws : dw;
-        dyf_form_note(h16 ? "t_gemm_mfma16<wgrad>:det" : "t_gemm_mfma<wgrad>:det", g.n);
-        if (h16)
+        dyf_form_note(sp ? "t_gemm_mfma16x3<wgrad>:det" : h16 ? "t_gemm_mfma16<wgrad>:det" : "t_gemm_mfma<wgrad>:det", g.n);
+        if (sp)
+            hipLaunchKernelGGL((t_gemm_mfma16<TG_WGRAD_DET, true>), dim3(mt, nt, (unsigned)(taps * splits)), dim3(256), 0, st, g, dz, x, nullptr, C, len, 0);
+        else if (h16)
             hipLaunchKernelGGL(t_gemm_mfma16<TG_WGRAD_DET>, dim3(mt, nt, (unsigned)(taps * splits)), dim3(256), 0, st, g, dz, x, nullptr, C, len, 0);
         else
             hipLaunchKernelGGL(t_gemm_mfma<TG_WGRAD_DET>, dim3(mt, nt, (unsigned)(taps * splits)), dim3(256), 0, st, g, dz, x, nullptr, C, len);
         if (splits > 1) det_reduce(ws, (int)splits, (long long)slab, (long long)slab, dw, st);
         return true;
     }
-    dyf_form_note(h16 ? "t_gemm_mfma16<wgrad>:atomic" : "t_gemm_mfma<wgrad>:atomic", g.n);
-    if (h16)
+    dyf_form_note(sp ? "t_gemm_mfma16x3<wgrad>:atomic" : h16 ? "t_gemm_mfma16<wgrad>:atomic" : "t_gemm_mfma<wgrad>:atomic", g.n);
+    if (sp)
+        hipLaunchKernelGGL((t_gemm_mfma16<TG_WGRAD, true>), dim3(mt, nt, (unsigned)(taps * splits)), dim3(256), 0, st, g, dz, x, nullptr, dw, len, 0);
+    else if (h16)
         hipLaunchKernelGGL(t_gemm_mfma16<TG_WGRAD>, dim3(mt, nt, (unsigned)(taps * splits)), dim3(256), 0, st, g, dz, x, nullptr, dw, len, 0);
     else
         hipLaunchKernelGGL(t_gemm_mfma<TG_WGRAD>, dim3(mt, nt, (unsigned)(taps * splits)), dim3(256), 0, st, g, dz, x, nullptr, dw, len);

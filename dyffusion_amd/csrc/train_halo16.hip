@@ -16,6 +16,17 @@
 //                  both operands are transposed on the way into LDS ([channel][pixel], 8 pixels = one 16-byte fragment); the
 //                  tap's column shift of +-1 pixel is a 2-byte shift of the fragment, made in registers (v_alignbyte) from
 //                  the aligned fragment and its neighbour; nine accumulators (one per tap) per wave
+//
+// bf16x3 (dyf_train_set_precision(48); train_gemm.hip has the arithmetic): the PASS form -- the same kernels run once per operand image
+// that has to be staged, a pass staging the hi image bf16(v) or the lo image bf16(v - hi) of an operand:
+//   forward / data gradient   two passes: A_lo W_hi (assigns C, with the bias: nothing of what C held before survives), then ONE pass for
+//                             A_hi W_lo + A_hi W_hi (NW = 2: the halo's hi image is staged once and meets an 18-step weight stream, lo
+//                             taps then hi taps, in the same accumulators) with the accumulating epilogue (C += acc);
+//                             t_pack_w16<true> writes the weight images in one launch
+//   weight gradient           three passes: dz_lo x_hi, dz_hi x_lo, dz_hi x_hi, each added onto dw the way the 16-bit form adds its one
+//                             term (atomics; deterministic mode: the owner's += or slabs + det_reduce per pass -- no atomics)
+// The fp32 activations are read twice (forward / data gradient) or three times (weight gradient) instead of once; a fused form (both
+// images of halo and weights in LDS, three MFMAs per step) needs 156 KB of the 160 KB for the forward kernel and is the follow-up.
 #include "train_internal.h"
 
 #include <cstdlib>
@@ -36,6 +47,9 @@ __device__ __forceinline__ int hkey(int hp) { return ((hp >> 1) - (int)((unsigne
 // ---------------------------------------------------------------------------------------------- weights -> 16 bit, [n][tap][k]
 // mode 0 (forward):  src = wt[tap][ci][co]            -> dst[co][tap][ci]
 // mode 1 (dgrad):    src = w[co][tap][ci], mirrored   -> dst[ci][8 - tap][co]
+// BOTH (bf16x3): dst[0 .. total) = the hi image as above, then a second image [n][18][k] of 2 x total elements: taps 0-8 the lo image,
+// taps 9-17 the hi image again (one weight stream of 18 steps per chunk for t_halo3x3_16<.., NW = 2>)
+template <bool BOTH = false>
 __global__ void t_pack_w16(const float* __restrict__ src, int cin, int cout, int mode, t16_t* __restrict__ dst) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     const long long total = (long long)cin * cout * 9;
@@ -48,6 +62,11 @@ __global__ void t_pack_w16(const float* __restrict__ src, int cin, int cout, int
     if (mode == 0) v = src[((size_t)tap * cin + k) * cout + n];
     else v = src[((size_t)k * 9 + (8 - tap)) * cin + n];
     dst[i] = f32_to_t16(v);
+    if (BOTH) {
+        t16_t* both = dst + total + ((size_t)n * 18 + tap) * CK + k;
+        both[0] = f32_to_t16_lo(v, f32_to_t16(v));
+        both[(size_t)9 * CK] = f32_to_t16(v);
+    }
 }
 
 // ---------------------------------------------------------------------------------------------- forward / data gradient
@@ -61,7 +80,21 @@ __global__ void t_pack_w16(const float* __restrict__ src, int cin, int cout, int
 //   is always enough -- halo loads and the epilogue's stores in between only make the wait longer, never too short.
 #define LDS_PTR(p) ((__attribute__((address_space(3))) void*)(p))
 
-template <int BN>
+// the 16-bit image of a pair of fp32 values: hi = bf16(v), or (LO, a bf16x3 pass) lo = bf16(v - hi)
+template <bool LO>
+__device__ __forceinline__ uint32_t cvt_t16x2(float a, float b) {
+    const uint32_t hi = pack_t16x2(a, b);
+    return LO ? pack_t16x2_lo(a, b, hi) : hi;
+}
+template <bool LO>
+__device__ __forceinline__ t16_t cvt_t16(float v) {
+    const t16_t hi = f32_to_t16(v);
+    return LO ? f32_to_t16_lo(v, hi) : hi;
+}
+
+// ALO: the halo is staged as its lo image; ACC: the epilogue adds onto C (no bias) instead of assigning; NW = 2: Wb is [n][18][k], the
+// lo and the hi image of the weights, and a chunk runs 18 steps (nine taps against each) on ONE staged halo -- the bf16x3 passes
+template <int BN, bool ALO = false, bool ACC = false, int NW = 1>
 __global__ __launch_bounds__(256, BN == 64 ? 2 : 1) void t_halo3x3_16(int h, int w, int CK, int NC, const float* __restrict__ A,
                                                                       const t16_t* __restrict__ Wb, const float* __restrict__ bias,
                                                                       float* __restrict__ C, int tiles_x, int tiles_per_img,
@@ -82,7 +115,7 @@ __global__ __launch_bounds__(256, BN == 64 ? 2 : 1) void t_halo3x3_16(int h, int
     const int t_beg = wg * tiles_per_wg, t_end = min(t_beg + tiles_per_wg, tiles_total);
     if (t_beg >= tiles_total) return;  // (the grid is rounded up to whole groups of 8 tile ranges)
     const int nchunks = CK >> 6;
-    const auto rsrc_w = __builtin_amdgcn_make_buffer_rsrc((void*)Wb, 0, (int)(unsigned)((size_t)NC * 9 * CK * 2), 0x00020000);
+    const auto rsrc_w = __builtin_amdgcn_make_buffer_rsrc((void*)Wb, 0, (int)(unsigned)((size_t)NC * 9 * NW * CK * 2), 0x00020000);
 
     // weight DMA: instruction j of this wave fills rows (wave * BI + j) * 8 ... + 8 of the step's image
     unsigned w_voff[BI];
@@ -90,7 +123,7 @@ __global__ __launch_bounds__(256, BN == 64 ? 2 : 1) void t_halo3x3_16(int h, int
     for (int j = 0; j < BI; ++j) {
         const int n = (wave * BI + j) * 8 + (lane >> 3);
         const int c = (lane & 7) ^ ((n >> 1) & 7);
-        w_voff[j] = (unsigned)((size_t)(n0 + n) * 9 * CK + c * 8) * 2u;
+        w_voff[j] = (unsigned)((size_t)(n0 + n) * 9 * NW * CK + c * 8) * 2u;
     }
     int is_tap = 0, is_chunk = 0, is_slot = 0;  // the step the next issue_b requests (runs past the end: harmless re-fetches)
     auto issue_b = [&]() {
@@ -98,7 +131,7 @@ __global__ __launch_bounds__(256, BN == 64 ? 2 : 1) void t_halo3x3_16(int h, int
 #pragma unroll
         for (int j = 0; j < BI; ++j)
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_w, LDS_PTR(Bring + is_slot * B_BYTES + (wave * BI + j) * 1024), 16, w_voff[j], soff, 0, 0);
-        if (++is_tap == 9) { is_tap = 0; if (++is_chunk == nchunks) is_chunk = 0; }
+        if (++is_tap == 9 * NW) { is_tap = 0; if (++is_chunk == nchunks) is_chunk = 0; }
         if (++is_slot == RING) is_slot = 0;
     };
 
@@ -125,7 +158,8 @@ __global__ __launch_bounds__(256, BN == 64 ? 2 : 1) void t_halo3x3_16(int h, int
             const int hp = idx >> 4, q = idx & 15;
             if (idx < HP * 16)
                 *(uint2*)(Xs + hp * 128 + (((q >> 1) ^ hkey(hp)) << 4) + (q & 1) * 8) =
-                    make_uint2(pack_t16x2(hv[j].x, hv[j].y), pack_t16x2(hv[j].z, hv[j].w));
+                    ALO ? make_uint2(cvt_t16x2<true>(hv[j].x, hv[j].y), cvt_t16x2<true>(hv[j].z, hv[j].w))
+                        : make_uint2(pack_t16x2(hv[j].x, hv[j].y), pack_t16x2(hv[j].z, hv[j].w));
         }
     };
 
@@ -149,12 +183,13 @@ __global__ __launch_bounds__(256, BN == 64 ? 2 : 1) void t_halo3x3_16(int h, int
             const bool has_next = !last || tile + 1 < t_end;
             const char* Xs = smem + xbuf * XS_BYTES;
 #pragma unroll
-            for (int tap = 0; tap < 9; ++tap) {
+            for (int wtap = 0; wtap < 9 * NW; ++wtap) {
+                const int tap = wtap % 9;  // (NW = 2: the spatial tap of weight-stream step wtap)
                 // (a raw s_barrier: __syncthreads() is a fence, and the compiler drains vmcnt to 0 in front of it -- the whole ring)
                 asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"((RING - 2) * BI) : "memory");
                 __builtin_amdgcn_s_barrier();
                 __builtin_amdgcn_sched_barrier(0);
-                if (tap == 0 && has_next) halo_load(last ? tile + 1 : tile, last ? 0 : chunk + 1);
+                if (wtap == 0 && has_next) halo_load(last ? tile + 1 : tile, last ? 0 : chunk + 1);
                 issue_b();
                 const int hp = hp00 + (tap / 3) * HW + (tap % 3);
                 const char* ap = Xs + hp * 128;
@@ -173,7 +208,7 @@ __global__ __launch_bounds__(256, BN == 64 ? 2 : 1) void t_halo3x3_16(int h, int
                 }
                 if (++slot == RING) slot = 0;
             }
-            // the other halo buffer was last read a whole chunk (nine barriers) ago
+            // the other halo buffer was last read a whole chunk (nine barriers or more) ago
             if (has_next) halo_store(xbuf ^ 1);
             xbuf ^= 1;
         }
@@ -183,12 +218,16 @@ __global__ __launch_bounds__(256, BN == 64 ? 2 : 1) void t_halo3x3_16(int h, int
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
             const int n = n0 + t * 32 + l31;
-            const float bv = bias ? bias[n] : 0.0f;
+            const float bv = (ACC || !bias) ? 0.0f : bias[n];
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int i = 8 * (r >> 2) + 4 * hi + (r & 3);
                 const int y = y0 + 2 * wave + (i >> 4), x = x0 + (i & 15);
-                if (y < h && x < w) C[(((size_t)img * h + y) * w + x) * NC + n] = acc[t][r] + bv;
+                if constexpr (ACC) {
+                    if (y < h && x < w) C[(((size_t)img * h + y) * w + x) * NC + n] += acc[t][r];
+                } else {
+                    if (y < h && x < w) C[(((size_t)img * h + y) * w + x) * NC + n] = acc[t][r] + bv;
+                }
                 acc[t][r] = 0.0f;
             }
         }
@@ -202,8 +241,9 @@ __global__ __launch_bounds__(256, BN == 64 ? 2 : 1) void t_halo3x3_16(int h, int
 constexpr int DZ_PITCH = 256;   // [co][8 rows x 16 columns] 16-bit: 16 chunks of 8 pixels
 constexpr int XT_PITCH = 768;   // [ci][10 halo rows x 4 blocks of 8 columns (x0 - 8 ... x0 + 23)]: 40 chunks, pitch 48 (swizzle room)
 
-// (DET: the deterministic mode's instantiation -- every tile range writes its own slab of dw-shaped partial sums, no atomics)
-template <bool DET>
+// (DET: the deterministic mode's instantiation -- every tile range writes its own slab of dw-shaped partial sums, no atomics;
+//  ZLO / XLO: dz / x is staged as its lo image -- the bf16x3 passes)
+template <bool DET, bool ZLO = false, bool XLO = false>
 __global__ __launch_bounds__(256, 2) void t_wgrad3x3_16(int h, int w, int cin, int cout, const float* __restrict__ dz,
                                                         const float* __restrict__ x, float* __restrict__ dw, int tiles_x,
                                                         int tiles_per_img, int tiles_total, int tiles_per_wg) {
@@ -243,12 +283,15 @@ __global__ __launch_bounds__(256, 2) void t_wgrad3x3_16(int h, int w, int cin, i
                 v[j] = make_float4(0.f, 0.f, 0.f, 0.f);
                 if (yy < h && xx < w) v[j] = *(const float4*)(dz + (((size_t)img * h + yy) * w + xx) * cout + co0 + cq * 4);
             }
-#define PACK8(F) u32x4{pack_t16x2(v[0].F, v[1].F), pack_t16x2(v[2].F, v[3].F), pack_t16x2(v[4].F, v[5].F), pack_t16x2(v[6].F, v[7].F)}
+#define PACK8(F) u32x4{CVT2(v[0].F, v[1].F), CVT2(v[2].F, v[3].F), CVT2(v[4].F, v[5].F), CVT2(v[6].F, v[7].F)}
+#define CVT2 cvt_t16x2<ZLO>
             const int r0 = cq * 4;
             *(u32x4*)(Dz + (r0 + 0) * DZ_PITCH + ((pg ^ ((r0 + 0) & 15)) << 4)) = PACK8(x);
             *(u32x4*)(Dz + (r0 + 1) * DZ_PITCH + ((pg ^ ((r0 + 1) & 15)) << 4)) = PACK8(y);
             *(u32x4*)(Dz + (r0 + 2) * DZ_PITCH + ((pg ^ ((r0 + 2) & 15)) << 4)) = PACK8(z);
             *(u32x4*)(Dz + (r0 + 3) * DZ_PITCH + ((pg ^ ((r0 + 3) & 15)) << 4)) = PACK8(w);
+#undef CVT2
+#define CVT2 cvt_t16x2<XLO>
         }
         // x, the two full blocks of every halo row (columns x0 ... x0 + 15): 20 chunks x 16 channel quads = 320 tasks
 #pragma unroll 1
@@ -269,6 +312,7 @@ __global__ __launch_bounds__(256, 2) void t_wgrad3x3_16(int h, int w, int cin, i
             *(u32x4*)(Xt + (r0 + 3) * XT_PITCH + ((ch ^ ((r0 + 3) & 15)) << 4)) = PACK8(w);
         }
 #undef PACK8
+#undef CVT2
         // x, the edge columns x0 - 1 (last element of block 0) and x0 + 16 (first element of block 3): 20 x 16 single-pixel tasks
 #pragma unroll 1
         for (int tk = tid; tk < 320; tk += 256) {
@@ -277,10 +321,10 @@ __global__ __launch_bounds__(256, 2) void t_wgrad3x3_16(int h, int w, int cin, i
             float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
             if ((unsigned)yy < (unsigned)h && (unsigned)xx < (unsigned)w) v = *(const float4*)(x + (((size_t)img * h + yy) * w + xx) * cin + ci0 + cq * 4);
             const int r0 = cq * 4, ch = hy * 4 + (side ? 3 : 0), eo = side ? 0 : 14;
-            *(t16_t*)(Xt + (r0 + 0) * XT_PITCH + ((ch ^ ((r0 + 0) & 15)) << 4) + eo) = f32_to_t16(v.x);
-            *(t16_t*)(Xt + (r0 + 1) * XT_PITCH + ((ch ^ ((r0 + 1) & 15)) << 4) + eo) = f32_to_t16(v.y);
-            *(t16_t*)(Xt + (r0 + 2) * XT_PITCH + ((ch ^ ((r0 + 2) & 15)) << 4) + eo) = f32_to_t16(v.z);
-            *(t16_t*)(Xt + (r0 + 3) * XT_PITCH + ((ch ^ ((r0 + 3) & 15)) << 4) + eo) = f32_to_t16(v.w);
+            *(t16_t*)(Xt + (r0 + 0) * XT_PITCH + ((ch ^ ((r0 + 0) & 15)) << 4) + eo) = cvt_t16<XLO>(v.x);
+            *(t16_t*)(Xt + (r0 + 1) * XT_PITCH + ((ch ^ ((r0 + 1) & 15)) << 4) + eo) = cvt_t16<XLO>(v.y);
+            *(t16_t*)(Xt + (r0 + 2) * XT_PITCH + ((ch ^ ((r0 + 2) & 15)) << 4) + eo) = cvt_t16<XLO>(v.z);
+            *(t16_t*)(Xt + (r0 + 3) * XT_PITCH + ((ch ^ ((r0 + 3) & 15)) << 4) + eo) = cvt_t16<XLO>(v.w);
         }
         __syncthreads();
         // 8 k-steps of 16 pixels (tile row y; lanes hi = 0 / 1 take columns 0-7 / 8-15)
@@ -334,7 +378,8 @@ bool thalo_conv3x3(const TConv& g, int mode, const float* A, const float* W, con
     const int CK = mode ? g.cout : g.cin, NC = mode ? g.cin : g.cout;
     if (CK % 64 != 0 || NC % 64 != 0) return false;
     const size_t welems = (size_t)CK * NC * 9;
-    if (ws == nullptr || welems > ws_floats * 2) return false;
+    const bool sp = train_operands_split();  // bf16x3: the workspace holds the hi image and the [lo | hi] image of the weights
+    if (ws == nullptr || welems * (sp ? 3 : 1) > ws_floats * 2) return false;
     const int tiles_x = (g.w + TW - 1) / TW, tiles_per_img = tiles_x * ((g.h + TH - 1) / TH);
     const long long tiles = (long long)g.n * tiles_per_img;
     // 64-channel column blocks (two workgroups per CU) also where 128 divides: NS B=32 step 110 -> 109 ms, ResNet-UNet B=64 144 -> 141 ms;
@@ -342,8 +387,10 @@ bool thalo_conv3x3(const TConv& g, int mode, const float* A, const float* W, con
     constexpr int bn = 64;
     if (tiles * (NC / bn) < 192 || tiles > 0x7fffffffll) return false;  // small planes: the split-K forms of train_gemm.hip  // small planes: the split-K forms of train_gemm.hip
     t16_t* wb = (t16_t*)ws;
-    dyf_form_note(mode ? "t_halo3x3_16:dgrad" : "t_halo3x3_16:forward", g.n);
-    hipLaunchKernelGGL(t_pack_w16, dim3((unsigned)((welems + 255) / 256)), dim3(256), 0, st, W, g.cin, g.cout, mode, wb);
+    if (sp) dyf_form_note(mode ? "t_halo3x3_16x3:dgrad" : "t_halo3x3_16x3:forward", g.n);
+    else dyf_form_note(mode ? "t_halo3x3_16:dgrad" : "t_halo3x3_16:forward", g.n);
+    if (sp) hipLaunchKernelGGL(t_pack_w16<true>, dim3((unsigned)((welems + 255) / 256)), dim3(256), 0, st, W, g.cin, g.cout, mode, wb);
+    else hipLaunchKernelGGL(t_pack_w16<false>, dim3((unsigned)((welems + 255) / 256)), dim3(256), 0, st, W, g.cin, g.cout, mode, wb);
     const int nblocks = NC / bn;
     // a workgroup streams several tiles (prefetch runs across tile boundaries)
     // (measured, us per launch with ~512 / 1 024 / 2 048 / 4 096 workgroups: 64 x 60^2 x 64 -> 64 49 / 52 / 55 / 56, 64 x 30^2 x 256 -> 128 data
@@ -352,6 +399,15 @@ bool thalo_conv3x3(const TConv& g, int mode, const float* A, const float* W, con
     const int per = (int)std::max<long long>(1, std::min<long long>(16, tiles * nblocks / htarget));
     const long long wgs = ((tiles + per - 1) / per + 7) / 8 * 8 * nblocks;  // whole groups of 8 tile ranges (XCD-aware order in the kernel)
     constexpr int XS = HP * 128 + 512;
+    if (sp) {  // A_lo W_hi assigns (with the bias); A_hi [W_lo | W_hi] accumulates, both weight images against one staged halo
+        constexpr int lds = 2 * XS + 4 * 64 * 128;
+        if (!train_raise_dynamic_lds<t_halo3x3_16<64, true, false>>(lds) || !train_raise_dynamic_lds<t_halo3x3_16<64, false, true, 2>>(lds)) return false;
+        hipLaunchKernelGGL((t_halo3x3_16<64, true, false>), dim3((unsigned)wgs), dim3(256), lds, st, g.h, g.w, CK, NC, A, wb, bias, C, tiles_x,
+                           tiles_per_img, (int)tiles, per, nblocks);
+        hipLaunchKernelGGL((t_halo3x3_16<64, false, true, 2>), dim3((unsigned)wgs), dim3(256), lds, st, g.h, g.w, CK, NC, A, wb + welems, bias, C, tiles_x,
+                           tiles_per_img, (int)tiles, per, nblocks);
+        return true;
+    }
     if (!train_raise_dynamic_lds<t_halo3x3_16<64>>(2 * XS + 4 * 64 * 128)) return false;  // per device; the tap-by-tap form takes the layer
     hipLaunchKernelGGL(t_halo3x3_16<64>, dim3((unsigned)wgs), dim3(256), 2 * XS + 4 * 64 * 128, st, g.h, g.w, CK, NC, A, wb, bias, C, tiles_x,
                        tiles_per_img, (int)tiles, per, nblocks);
@@ -376,6 +432,25 @@ bool thalo_wgrad3x3(const TConv& g, const float* dz, const float* x, float* dw, 
     if (det) splits = std::max<long long>(1, std::min<long long>(splits, ws ? (long long)(ws_floats / slab) : 1));
     const int per = (int)((tiles + splits - 1) / splits);
     splits = (tiles + per - 1) / per;
+    if (train_operands_split()) {  // dz_lo x_hi, dz_hi x_lo, dz_hi x_hi: each pass adds onto dw as the one-term form does
+        dyf_form_note("t_wgrad3x3_16x3", g.n);
+        dyf_form_note(det ? "t_wgrad3x3_16x3:det" : "t_wgrad3x3_16x3:atomic", g.n);
+        const dim3 grid((unsigned)splits, g.cout / 64, g.cin / 64);
+        float* C = det && splits > 1 ? ws : dw;
+#define WGRAD_PASS(ZLO, XLO)                                                                                                                    \
+    do {                                                                                                                                        \
+        if (det) hipLaunchKernelGGL((t_wgrad3x3_16<true, ZLO, XLO>), grid, dim3(256), 0, st, g.h, g.w, g.cin, g.cout, dz, x, C, tiles_x,     \
+                                    tiles_per_img, (int)tiles, per);                                                                            \
+        else hipLaunchKernelGGL((t_wgrad3x3_16<false, ZLO, XLO>), grid, dim3(256), 0, st, g.h, g.w, g.cin, g.cout, dz, x, C, tiles_x,        \
+                                tiles_per_img, (int)tiles, per);                                                                                \
+        if (det && splits > 1) det_reduce(ws, (int)splits, (long long)slab, (long long)slab, dw, st);                                           \
+    } while (0)
+        WGRAD_PASS(true, false);
+        WGRAD_PASS(false, true);
+        WGRAD_PASS(false, false);
+#undef WGRAD_PASS
+        return true;
+    }
     dyf_form_note("t_wgrad3x3_16", g.n);
     if (det) {
         dyf_form_note("t_wgrad3x3_16:det", g.n);

@@ -31,6 +31,12 @@ __device__ __forceinline__ uint32_t pack_t16x2(float lo, float hi) {  // one v_c
 #endif
 }
 
+// bf16x3: the lo image of a value whose hi image (its bf16 rounding) is `hi`: bf16(v - hi), the subtraction exact in fp32
+__device__ __forceinline__ uint32_t pack_t16x2_lo(float a, float b, uint32_t hi) {
+    return pack_t16x2(a - __builtin_bit_cast(float, hi << 16), b - __builtin_bit_cast(float, hi & 0xffff0000u));
+}
+__device__ __host__ __forceinline__ t16_t f32_to_t16_lo(float v, t16_t hi) { return f32_to_t16(v - t16_to_f32(hi)); }
+
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) is a PER-DEVICE attribute: the training launchers that need more than the 64 KB
 // default raise it once per (kernel, device) -- a process-wide flag left the second GPU of a process at the default, and its first
 // launch failed.  Returns false (and the launcher declines the shape) when the attribute cannot be set.
@@ -128,6 +134,9 @@ struct TConv {  // geometry of one nn.Conv2d on NHWC fp32 tensors: x (n, h, w, c
 // dyf_train_set_precision (0 = the DYF_TRAIN_OPERANDS environment variable decides: unset / fp32 -> fp32 operands).
 extern thread_local int g_train_precision;
 bool train_operands16();
+// bf16x3 (dyf_train_set_precision(48), or DYF_TRAIN_OPERANDS=bf16x3 where the engine did not say): the convs the 16-bit dispatch takes stage
+// every operand as hi = bf16(v), lo = bf16(v - hi) and compute a_lo b_hi + a_hi b_lo + a_hi b_hi (train_gemm.hip, train_halo16.hip)
+bool train_operands_split();
 struct TrainPrecisionScope {
     int prev;
     explicit TrainPrecisionScope(int p) : prev(g_train_precision) { g_train_precision = p; }

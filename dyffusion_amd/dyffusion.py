@@ -110,7 +110,7 @@ class DYffusion(nn.Module):
                                  batch_invariant=batch_invariant,  # batch_invariant: bit-identical rows under any batching / sharding
                                  row_groups=row_groups,  # concurrent row groups of a sampling call (None = engine default)
                                  # operand precision of the training step's convolutions: the reference's `trainer.precision`
-                                 # (32 default; 16 / "16-mixed" / "bf16-mixed": HipEngine.train_set_precision)
+                                 # (32 default; 16 / "16-mixed" / "bf16-mixed"; 48 / "bf16x3": HipEngine.train_set_precision)
                                  train_precision=train_precision,
                                  # 16-bit dropout of unet.Unet's Attention probabilities: "fast" (quad form) or "exact" (nn.Dropout's
                                  # rate on the fp32 path's keep bits; HipEngine.set_attention_dropout).  ValueError for another string.

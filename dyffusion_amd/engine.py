@@ -80,6 +80,9 @@ def parse_train_precision(precision) -> int:
     key = str(precision).lower()
     if key in ("32", "32-true", "fp32", "float32"):
         return 32
+    if key in ("bf16x3", "48"):
+        # fp32-grade convs on the 16-bit matrix cores: each operand a (hi, lo) pair of bf16, three MFMAs per product; all else as under 32
+        return L.DYF_TRAIN_PRECISION_BF16X3
     if key in ("16", "16-mixed", "bf16", "bf16-mixed", "fp16", "fp16-mixed"):
         # every 16-bit request runs as bf16-mixed (csrc/train_internal.h): the engine has no GradScaler, and fp16 gradient operands
         # without one lose the gradient at real batch sizes (dL/dout ~ 1 / numel).  An explicit fp16 request is told so once.
@@ -88,7 +91,7 @@ def parse_train_precision(precision) -> int:
             warnings.warn("train precision 'fp16-mixed' runs as bf16-mixed: the engine rounds its training conv operands to bf16 "
                           "(no loss scaling needed); fp16 operands are not offered", stacklevel=2)
         return 16
-    raise ValueError(f"train precision {precision!r}: expected 32 / '32-true' or 16 / '16-mixed' / 'bf16-mixed'")
+    raise ValueError(f"train precision {precision!r}: expected 32 / '32-true', 16 / '16-mixed' / 'bf16-mixed' or 48 / 'bf16x3'")
 
 
 def resolve_train_deterministic(setting) -> bool:
@@ -643,7 +646,9 @@ class HipEngine:
         """Operand precision of the training convolutions (dyf_train_set_precision; the reference's Lightning `trainer.precision`):
         32 / "32" / "32-true" = fp32 operands (default), 16 / "16-mixed" / "bf16-mixed" = operands rounded to bf16 while staged (fp32
         tensors, master weights and accumulation) -- bf16 on fp16 engines too: the reference's precision=16 is fp16 + GradScaler, and
-        fp16 gradient operands without a loss scale underflow at real batch sizes (`parse_train_precision`); None = not set (fp32)."""
+        fp16 gradient operands without a loss scale underflow at real batch sizes (`parse_train_precision`); 48 / "bf16x3" = fp32-grade convs on the 16-bit matrix cores: the convs the 16-bit
+        dispatch takes split each operand into a (hi, lo) pair of bf16 and sum three MFMA terms, everything else exactly as under 32
+        (SimpleConvNet keeps fp32 operands); None = not set (fp32)."""
         self._check(self._lib.dyf_train_set_precision(self._h, parse_train_precision(precision)))
 
     @property

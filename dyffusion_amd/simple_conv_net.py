@@ -27,7 +27,7 @@ class SimpleConvNet(UNet):
     path: `get_loss` in train mode records the fp32 forward on the engine (csrc/train_resnet.inc sc_walk: batch-statistics BatchNorm
     with running-statistics update, Dropout active) and `loss.backward()` runs its backward into `param.grad`; as the forecaster
     of a `DYffusion` it is also served by the engine-resident `dyffusion_amd.EngineAdamW` (which refuses a stand-alone SimpleConvNet).  fp32 conv operands only: `train_precision=16` is
-    refused (NotImplementedError) at the first training forward."""
+    refused (NotImplementedError) at the first training forward; under `train_precision="bf16x3"` it keeps recording with fp32 operands."""
 
     def __init__(self, dim: int, with_time_emb: bool = False, net_normalization: str = "batch_norm",
                  kernel_sizes: Sequence[int] = (7, 3, 3), keep_spatial_shape: bool = True, residual: bool = True,

@@ -313,8 +313,17 @@ dyf_status dyf_train_zero_grads(dyf_engine* engine, int32_t net);
  * csrc/train_gemm.hip).  Lightning's precision=16 is fp16 + a GradScaler; this engine answers the same request with bf16 operands,
  * which need no loss scale (with mean-reduced losses dL/dout is ~1e-6..1e-7 at real batch sizes, below fp16's normal range).
  * 0 = not set (fp32 operands; the tests' kernel-form switch DYF_TRAIN_OPERANDS of dyffusion_hip_testing.h can select 16-bit operands
- * for such engines).  Applies to the dyf_train_forward / dyf_train_backward calls that follow; a recorded forward and its backward
- * should run under the same setting. */
+ * or bf16x3 operands for such engines).  Applies to the dyf_train_forward / dyf_train_backward calls that follow; a recorded forward and
+ * its backward should run under the same setting.
+ * 48 = DYF_TRAIN_PRECISION_BF16X3, "bf16x3": fp32-grade convolutions on the 16-bit matrix cores (what
+ * torch.set_float32_matmul_precision("high") asks of other back ends).  The convs the 16-bit dispatch takes (the same channel rules as
+ * under 16) stage each fp32 operand value v as TWO bf16 values, hi = bf16(v) and lo = bf16(v - hi), and accumulate
+ * a_lo b_hi + a_hi b_lo + a_hi b_hi in fp32: a product is good to ~2^-16 (rel-RMS 4.5e-6 of a conv against float64, inside the 1e-5
+ * the fp32 kernels are held to; one bf16 term: 2.4e-3).  Nothing else is rounded, and everything else is exactly as under 32: tensors,
+ * master weights, accumulation, statistics, every Linear and attention contraction, and every conv outside those channel rules (fp32
+ * kernels).  SimpleConvNet keeps recording with fp32 conv operands under 48, as under 0 and 32 (only 16 is refused for it).  The
+ * sampling paths do not read the setting. */
+#define DYF_TRAIN_PRECISION_BF16X3 48
 dyf_status dyf_train_set_precision(dyf_engine* engine, int32_t bits);
 int32_t dyf_train_precision(const dyf_engine* engine);
 /* Deterministic training mode (ABI 9) -- the reference's `trainer.deterministic` (Lightning; src/configs/trainer/default.yaml:18

@@ -1,6 +1,6 @@
 """One training convolution through the test seam (dyf_train_conv_check), a few times -- for rocprofv3 (kernel time, HBM counters) of the
 16-bit-operand tile + halo kernels (csrc/train_halo16.hip).  usage: python tools/bench_train_conv.py [kind n h w cin cout k s p] [reps]
-kind 0 forward, 1 data gradient, 2 weight gradient; default: the NS decoder's last conv at 16 rows (forward, 16 x 256^2 x 128 -> 64)."""
+kind 0 forward, 1 data gradient, 2 weight gradient; DYF_TRAIN_OPERANDS=bf16x3 in the environment times the three-term forms; default: the NS decoder's last conv at 16 rows (forward, 16 x 256^2 x 128 -> 64)."""
 import os
 import sys
 

@@ -95,7 +95,7 @@ def main():
     ap.add_argument("--config", choices=["ns", "oisst"], default="ns")
     ap.add_argument("--small", action="store_true", help="the 23x11 test pair instead of --config")
     ap.add_argument("--rows", type=int, default=None, help="batch rows of the step (ns 32, oisst 64, small 3)")
-    ap.add_argument("--precision", type=int, choices=[32, 16], default=32, help="operand precision of the training convs")
+    ap.add_argument("--precision", type=int, choices=[32, 16, 48], default=32, help="operand precision of the training convs (48 = bf16x3)")
     ap.add_argument("--seed", type=int, default=7)
     ap.add_argument("--reps", type=int, default=5, help="timed steps per mode")
     a = ap.parse_args()
