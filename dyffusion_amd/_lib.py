@@ -116,18 +116,21 @@ class SampleOp(C.Structure):
     """dyf_sample_op (include/dyffusion_hip_testing.h): one 16-bit sampling kernel's launch for dyf_op_sample16."""
     _fields_ = [(k, C.c_int32) for k in ("op", "nb", "h", "w", "c", "c2", "k", "pad", "groups", "act", "flags", "film_stride", "film_div",
                                          "part_slots", "nsrc")] + [("ch", C.c_int32 * 4), ("drop_mode", C.c_int32), ("drop_p", C.c_float),
-                                                                   ("drop_site", C.c_int32), ("drop_row_offset", C.c_uint32), ("drop_forward", C.c_uint32)]
+                                                                   ("drop_site", C.c_int32), ("drop_row_offset", C.c_uint32), ("drop_forward", C.c_uint32)] + \
+               [(k, C.c_int32) for k in ("oh", "ow", "nearest", "src_rows", "iw_store")] + [("tau", C.c_float)]
 
 
 class SampleTensors(C.Structure):
     """dyf_sample_tensors: the device pointers of one dyf_op_sample16 call; NULL = absent."""
     _fields_ = [("x", C.c_void_p * 4), ("residual", C.c_void_p), ("film_a", C.c_void_p), ("film_c", C.c_void_p), ("part", C.c_void_p),
-                ("mask", C.c_void_p), ("y", C.c_void_p)]
+                ("mask", C.c_void_p), ("y", C.c_void_p), ("col_map", C.c_void_p), ("y2", C.c_void_p), ("y3", C.c_void_p)]
 
 
 SAMPLE_OPS = {"gn_act": 0, "layernorm_c": 1, "head": 2, "up2_nearest": 3, "drop16": 4, "stem_conv": 5, "groupnorm_f32": 6, "up2_bilinear": 7,
-              "up2_epilogue": 8}
-SOP_NO_STATS = 1
+              "up2_epilogue": 8, "readout": 9, "readout_tables": 10, "stem": 11, "stem16": 12, "rng_begin": 13, "rng_clone": 14, "time_mlp": 15,
+              "film": 16, "cold_update": 17, "noisy_condition": 18}
+SOP_NO_STATS, SOP_NO_TABLES, SOP_FOLD_RNG, SOP_COUNTERS_ONLY = 1, 2, 4, 8
+RNG_STATE_WORDS = 8  # DYF_RNG_STATE_WORDS (csrc/kernels.h)
 ACTS = {"none": 0, "relu": 1, "leaky": 2, "silu": 3, "gelu": 4}
 
 

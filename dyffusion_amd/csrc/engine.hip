@@ -826,23 +826,10 @@ static dyf_status load_weights_one(dyf_engine* e, int32_t which, int32_t n_tenso
         const int64_t oc = n.cfg.out_channels;
         NEED(rw, "readout.0.weight", d, oc, 4, 4);
         NEED(rb, "readout.0.bias", oc);
-        std::vector<float> pk((size_t)16 * n.dim * oc);
-        for (int ci = 0; ci < n.dim; ++ci)
-            for (int co = 0; co < oc; ++co)
-                for (int t = 0; t < 16; ++t) pk[((size_t)t * n.dim + ci) * oc + co] = rw->data[((size_t)ci * oc + co) * 16 + t];
+        const std::vector<float> pk = pack_readout_weights(rw->data, n.dim, (int)oc);
         UP(n.ro_w, pk); UP(n.ro_b, vec(rb));
-        if (n.dim == 64 && oc <= 4) {  // MFMA fragments: lane (m = lane & 15, kg = lane >> 4) of (tap, half): W[tap][half*32 + kg*8 + e][m]
-            std::vector<el16_t> wf((size_t)16 * 2 * 64 * 8, 0);
-            for (int t = 0; t < 16; ++t)
-                for (int h2 = 0; h2 < 2; ++h2)
-                    for (int lane = 0; lane < 64; ++lane) {
-                        const int m = lane & 15, kg = lane >> 4;
-                        for (int el = 0; el < 8; ++el)
-                            if (m < oc)
-                                wf[(((size_t)t * 2 + h2) * 64 + lane) * 8 + el] =
-                                    f32_to_el16(pk[((size_t)t * n.dim + h2 * 32 + kg * 8 + el) * oc + m]);
-                    }
-            UP(n.ro_wfrag, wf);
+        if (n.dim == 64 && oc <= 4) {  // MFMA fragments (kernels.h pack_readout_frag)
+            UP(n.ro_wfrag, pack_readout_frag(pk, (int)oc));
             // tap tables of the readout for this engine's geometry and the storage layout of the last decoder block's output
             // (compact when its sparse column lists were planned above)
             const UBlock& lb = n.blk[11];
@@ -2176,10 +2163,225 @@ dyf_status dyf_op_train_f32(dyf_engine* e, const dyf_train_op* desc, const float
     return f32_op_train(e, desc, inputs_dev, params_host, dout_dev, y_dev, dinputs_dev, dparams_host, (hipStream_t)stream);
 }
 
+// dyf_op_sample16 for the launchers around the networks (READOUT .. NOISY_CONDITION, csrc/kernels.hip): the same rules -- the
+// launcher's own argument struct, the upload's own packing, what the descriptor cannot express is refused.
+static dyf_status sample_op_net(dyf_engine* e, const dyf_sample_op& d, const dyf_sample_tensors& t, const float* const* params_host, hipStream_t st) {
+    const int op = d.op;
+    auto bad = [&](const char* m) { return fail(e, DYF_ERR_INVALID_ARGUMENT, std::string("dyf_op_sample16: ") + m); };
+    auto unsup = [&](const char* m) { return fail(e, DYF_ERR_UNSUPPORTED, std::string("dyf_op_sample16: ") + m); };
+    const bool readout = op == DYF_SOP_READOUT, tables = op == DYF_SOP_READOUT_TABLES, stem = op == DYF_SOP_STEM, stem16 = op == DYF_SOP_STEM16;
+    const bool begin = op == DYF_SOP_RNG_BEGIN, clone = op == DYF_SOP_RNG_CLONE, tmlp = op == DYF_SOP_TIME_MLP, film = op == DYF_SOP_FILM;
+    const bool cold = op == DYF_SOP_COLD_UPDATE, noisy = op == DYF_SOP_NOISY_CONDITION;
+    if (!t.y) return bad("null output");
+    if (d.k || d.pad || d.groups || d.act || d.film_stride || d.film_div || d.part_slots || t.residual || t.film_a || t.film_c || t.part)
+        return bad("k / pad / groups / act / FiLM rows / residual / part belong to the kernels between the convs");
+    const int allowed = readout ? DYF_SOP_NO_TABLES : stem16 ? DYF_SOP_FOLD_RNG : clone ? DYF_SOP_COUNTERS_ONLY : 0;
+    if (d.flags & ~allowed) return bad("a flag the op does not take");
+    const bool fold = stem16 && (d.flags & DYF_SOP_FOLD_RNG);
+    if (!stem && (d.drop_mode != 0 || t.mask || d.drop_p != 0.0f || d.drop_site != 0)) return bad("the op has no dropout");
+    if (!(stem || fold || begin) && d.drop_forward != 0) return bad("drop_forward on an op that starts no forward");
+    if (!(stem || fold || begin || clone || noisy) && d.drop_row_offset != 0) return bad("drop_row_offset on an op without batch rows of the generator");
+    if (!(readout || tables || stem || stem16) && (d.oh || d.ow || d.nearest)) return bad("oh / ow / nearest on an op without a resample");
+    if (!(readout || tables) && (d.iw_store || t.col_map)) return bad("iw_store / col_map belong to the readout");
+    if (!(stem || stem16 || begin) && d.src_rows) return bad("src_rows on an op without source rows");
+    if (!noisy && d.tau != 0.0f) return bad("tau belongs to NOISY_CONDITION");
+    if (!(stem || stem16 || film) && (d.nsrc || d.ch[0] || d.ch[1] || d.ch[2] || d.ch[3])) return bad("nsrc / ch on an op without sources or blocks");
+    if (!(stem16 || begin || tables || film || cold) && (t.y2 || t.y3)) return bad("y2 / y3 on an op with one output");
+    if (d.nb < 1 || d.h < 0 || d.w < 0 || d.c < 0 || d.c2 < 0 || d.oh < 0 || d.ow < 0 || d.src_rows < 0 || d.iw_store < 0 || d.nsrc < 0 || d.nsrc > 4 ||
+        (d.nearest != 0 && d.nearest != 1))
+        return bad("bad geometry");
+    const int nparams = (readout || stem) ? 2 : tmlp ? (d.c2 > 0 ? 5 : 4) : film ? 4 : 0;
+    if (nparams && !params_host) return bad("the op takes parameters");
+    for (int i = 0; i < nparams; ++i)
+        if (!params_host[i]) return bad("null parameter");
+    int ctot = 0;
+    for (int i = 0; i < 4; ++i) {
+        if ((stem || stem16 || film) && ((i < d.nsrc) != (d.ch[i] > 0))) return bad("nsrc and ch go together");
+        ctot += d.ch[i];
+    }
+    const long long hw = (long long)d.h * d.w;
+    if (readout || tables) {
+        if (d.h < 1 || d.w < 1 || d.oh < 1 || d.ow < 1) return bad("READOUT: (h, w) -> (oh, ow)");
+        if ((d.iw_store > 0) != (t.col_map != nullptr) || d.iw_store > d.w) return bad("READOUT: iw_store (1..w) and col_map go together");
+        if (tables ? (d.nb != 1 || d.c || d.c2 || !t.y2 || t.y3 || t.x[0]) : (d.c < 1 || d.c2 < 1 || !t.x[0])) return bad("READOUT: channels / tensors");
+        if (readout && d.c2 > DYF_MAX_OUT_CH) return unsup("more output channels than the readout takes");
+        if (readout && (size_t)16 * d.c * d.c2 * sizeof(float) > 64 * 1024) return unsup("readout weights beyond the LDS of the VALU forms");
+        const long long iws = d.iw_store > 0 ? d.iw_store : d.w;
+        if ((long long)d.nb * d.oh * d.ow >= (1ll << 30) || (long long)d.nb * d.h * iws * std::max(d.c, 64) * 2 >= 0x7F000000ll)
+            return unsup("tensor too large for the kernels' 32-bit indices");
+    } else if (stem || stem16) {
+        if (d.h < 1 || d.w < 1 || d.oh < 1 || d.ow < 1 || d.nsrc < 1 || ctot != d.c) return bad("STEM: (h, w) -> (oh, ow), c = sum of ch");
+        for (int i = 0; i < 4; ++i)
+            if ((i < d.nsrc) != (t.x[i] != nullptr)) return bad("STEM: sources and their channel counts go together");
+        if (d.src_rows > d.nb) return bad("STEM: src_rows above nb");
+        if (stem ? (d.c2 < 1 || d.c > DYF_MAX_IN_CH) : (d.c2 != 0 || d.c > 15)) return unsup("STEM: c2 = dim and c <= 32 (STEM); c <= 15 and no c2 (STEM16)");
+        if ((long long)d.nb * (d.oh + 2) * (d.ow + 2) * std::max(d.c2, 16) >= 0x7F000000ll || hw * d.c * d.nb >= 0x7F000000ll)
+            return unsup("tensor too large for the kernels' 32-bit indices");
+        if (fold ? (!t.y2 || !t.y3) : (t.y2 || t.y3)) return bad("STEM16: y2 / y3 go with DYF_SOP_FOLD_RNG");
+        if (fold && d.nb > 2 * e->cfg.max_batch) return bad("more rows than the engine's row-key table (2 max_batch)");
+    } else if (begin) {
+        if (!t.y2 || t.y3 || d.nb > 2 * e->cfg.max_batch || d.src_rows > d.nb || d.h || d.w || d.c || d.c2) return bad("RNG_BEGIN: nb <= 2 max_batch rows, y and y2");
+    } else if (clone) {
+        if (!t.x[0] || d.nb != 1 || d.h || d.w || d.c || d.c2) return bad("RNG_CLONE: source and destination state");
+    } else if (tmlp) {
+        if (!t.x[0] || d.h || d.w || d.c < 4 || d.c % 2 != 0 || d.c > 4096 || d.c2 > 4096) return bad("TIME_MLP: times, an even dim of 4 .. 4096");
+    } else if (film) {
+        if (d.h || d.w || d.c < 1 || d.c2 || d.nsrc < 1 || !t.y2 || t.y3 || d.nb > 65535) return bad("FILM: c = tdim, 1..4 blocks, y and y2");
+    } else {
+        if (!t.x[0] || d.h < 1 || d.w < 1 || d.c < 1 || d.c2 || t.y3 || hw * d.c >= 0x7F000000ll || (long long)d.nb * hw * d.c >= (1ll << 38))
+            return bad("COLD_UPDATE / NOISY_CONDITION: (nb, h, w, c) floats");
+        if (cold ? !t.x[1] : (t.y2 != nullptr)) return bad("COLD_UPDATE needs x_next; NOISY_CONDITION has one output");
+    }
+    dyf_status ds = DYF_OK;
+    if (stem) { ds = op_drop_check(e, d.nb, d.drop_mode, d.drop_p, t.mask, d.drop_site); if (ds != DYF_OK) return ds; }
+    std::vector<int16_t> cmap;
+    if (t.col_map) {  // a stored column outside the compact row would be read out of bounds
+        cmap.resize((size_t)d.w);
+        HIP_TRY(e, hipMemcpy(cmap.data(), t.col_map, cmap.size() * sizeof(int16_t), hipMemcpyDeviceToHost));
+        for (int16_t v : cmap)
+            if (v < -1 || v >= d.iw_store) return bad("READOUT: col_map entry outside the stored columns");
+    }
+    std::vector<void*> tmp;
+    dyf_status rs = DYF_OK;
+    hipError_t le = hipSuccess;
+    {
+        AllocScope scope(e, &tmp);
+        auto upf = [&](const float** dst, const float* host, size_t n) {
+            float* p = nullptr;
+            const dyf_status us = dev_upload(e, &p, std::vector<float>(host, host + n));
+            *dst = p;
+            return us;
+        };
+        auto upi = [&](const int** dst, const std::vector<int>& host) {
+            int* p = nullptr;
+            const dyf_status us = dev_upload(e, &p, host);
+            *dst = p;
+            return us;
+        };
+        // forward index and row offset of the generator, set as op_drop_arm sets them
+        auto set_counters = [&](bool forward_too) -> dyf_status {
+            const uint32_t words[2] = {d.drop_forward, d.drop_row_offset};
+            HIP_TRY(e, hipDeviceSynchronize());
+            if (forward_too) {
+                HIP_TRY(e, hipMemcpy(e->rng_state + 2, words, sizeof(words), hipMemcpyHostToDevice));
+            } else {
+                HIP_TRY(e, hipMemcpy(e->rng_state + 3, words + 1, sizeof(uint32_t), hipMemcpyHostToDevice));
+            }
+            e->row_offset = d.drop_row_offset;
+            e->row_offset_known = true;
+            return DYF_OK;
+        };
+        if (readout || tables) {
+            ReadoutArgs a{};
+            a.x = (const el16_t*)t.x[0]; a.n = d.nb; a.ih = d.h; a.iw = d.w; a.cin = d.c; a.cout = d.c2; a.oh = d.oh; a.ow = d.ow;
+            a.nearest = d.nearest; a.iw_store = d.iw_store > 0 ? d.iw_store : d.w; a.col_map = t.col_map; a.out = (float*)t.y;
+            if (tables) {
+                a.row_tab = (const uint4*)t.y; a.col_tab = (const uint4*)t.y2;
+                le = launch_readout_tables(a, st);
+            } else {
+                const std::vector<float> pk = pack_readout_weights(params_host[0], d.c, d.c2);
+                rs = upf(&a.wgt, pk.data(), pk.size());
+                if (rs == DYF_OK) rs = upf(&a.bias, params_host[1], (size_t)d.c2);
+                if (rs == DYF_OK && d.c == 64 && d.c2 <= 4) {  // as the weight upload: fragments, and the tap tables with them
+                    el16_t* wf = nullptr;
+                    rs = dev_upload(e, &wf, pack_readout_frag(pk, d.c2));
+                    a.wfrag = wf;
+                    if (rs == DYF_OK && !(d.flags & DYF_SOP_NO_TABLES)) {
+                        uint4 *rt = nullptr, *ct = nullptr;
+                        rs = dev_alloc(e, &rt, (size_t)2 * d.oh);
+                        if (rs == DYF_OK) rs = dev_alloc(e, &ct, (size_t)2 * d.ow);
+                        a.row_tab = rt; a.col_tab = ct;
+                        if (rs == DYF_OK) le = launch_readout_tables(a, st);
+                    }
+                }
+                if (rs == DYF_OK && le == hipSuccess) {
+                    le = launch_readout(a, st);
+                    if (le == hipErrorInvalidValue && a.col_map) rs = unsup("launch_readout refuses a compact input without fragments");
+                }
+            }
+        } else if (stem || stem16) {
+            StemArgs a{};
+            for (int i = 0; i < d.nsrc; ++i) { a.src[i] = (const float*)t.x[i]; a.ch[i] = d.ch[i]; }
+            a.nsrc = d.nsrc; a.cin = d.c; a.n = d.nb; a.src_rows = d.src_rows; a.h = d.h; a.w = d.w; a.uh = d.oh; a.uw = d.ow;
+            a.resample = (d.oh != d.h || d.ow != d.w) ? 1 : 0;  // as net_forward
+            a.nearest = d.nearest; a.dim = d.c2; a.out = (el16_t*)t.y;
+            if (stem) {
+                rs = upf(&a.wgt, params_host[0], (size_t)d.c2 * d.c);
+                if (rs == DYF_OK) rs = upf(&a.bias, params_host[1], (size_t)d.c2);
+                if (rs == DYF_OK) rs = op_drop_arm(e, d.nb, d.drop_mode, d.drop_p, t.mask, d.drop_site, d.drop_row_offset, d.drop_forward, st, &a.drop);
+                if (rs == DYF_OK) le = launch_stem(a, st);
+            } else {
+                if (fold) {
+                    rs = set_counters(true);
+                    a.rng_state = e->rng_state; a.rng_row_keys = e->row_keys; a.rng_rows = d.nb; a.rng_rows_per_fwd = d.src_rows > 0 ? d.src_rows : d.nb;
+                }
+                if (rs == DYF_OK) le = launch_stem16(a, st);
+            }
+        } else if (begin) {
+            rs = set_counters(true);
+            if (rs == DYF_OK) le = launch_rng_begin_forward(e->rng_state, e->row_keys, d.nb, d.src_rows > 0 ? d.src_rows : d.nb, st);
+        } else if (clone) {
+            le = launch_rng_clone((uint32_t*)t.y, (const uint32_t*)t.x[0], d.drop_row_offset, (d.flags & DYF_SOP_COUNTERS_ONLY) != 0, st);
+        } else if (tmlp) {
+            TimeMlpArgs a{};
+            const size_t td = (size_t)2 * d.c, nfeat = d.c2 > 0 ? (size_t)2 * d.c2 + 1 : (size_t)d.c;
+            a.time = (const float*)t.x[0]; a.rows = d.nb; a.dim = d.c; a.silu_out = (float*)t.y;
+            rs = upf(&a.w1, params_host[0], td * nfeat);
+            if (rs == DYF_OK) rs = upf(&a.b1, params_host[1], td);
+            if (rs == DYF_OK) rs = upf(&a.w2, params_host[2], td * td);
+            if (rs == DYF_OK) rs = upf(&a.b2, params_host[3], td);
+            if (rs == DYF_OK && d.c2 > 0) { rs = upf(&a.learned_w, params_host[4], (size_t)d.c2); a.learned_half = d.c2; }
+            if (rs == DYF_OK) le = launch_time_mlp(a, st);
+        } else if (film) {
+            FilmArgs a{};
+            a.silu = (const float*)t.x[0]; a.rows = d.nb; a.tdim = d.c; a.total_c = ctot; a.coef_a = (float*)t.y; a.coef_c = (float*)t.y2;
+            std::vector<int> blk_of((size_t)ctot), blk_off((size_t)d.nsrc), blk_cout((size_t)d.nsrc);
+            for (int i = 0, off = 0; i < d.nsrc; off += d.ch[i], ++i) {  // the tables of the weight upload (film_off = running sum of cout)
+                blk_off[i] = off;
+                blk_cout[i] = d.ch[i];
+                for (int c = 0; c < d.ch[i]; ++c) blk_of[off + c] = i;
+            }
+            rs = upf(&a.wf, params_host[0], (size_t)2 * ctot * d.c);
+            if (rs == DYF_OK) rs = upf(&a.bf, params_host[1], (size_t)2 * ctot);
+            if (rs == DYF_OK) rs = upf(&a.norm_a, params_host[2], (size_t)ctot);
+            if (rs == DYF_OK) rs = upf(&a.norm_c, params_host[3], (size_t)ctot);
+            if (rs == DYF_OK) rs = upi(&a.blk_of, blk_of);
+            if (rs == DYF_OK) rs = upi(&a.blk_off, blk_off);
+            if (rs == DYF_OK) rs = upi(&a.blk_cout, blk_cout);
+            if (rs == DYF_OK) le = launch_film(a, st);
+        } else if (cold) {
+            le = launch_cold_update((float*)t.y, (const float*)t.x[0], (const float*)t.x[1], (long long)d.nb * hw * d.c, st, (float*)t.y2);
+        } else {
+            if (!t.x[1]) rs = set_counters(false);
+            if (rs == DYF_OK)
+                le = launch_noisy_condition((float*)t.y, (const float*)t.x[0], (const float*)t.x[1], d.tau, (long long)d.nb * hw * d.c, (int)(hw * d.c),
+                                            e->rng_state, st);
+        }
+    }
+    if (rs == DYF_OK) {
+        if (le == hipSuccess) le = hipStreamSynchronize(st);
+        if (le == hipSuccess && (fold || begin)) {  // the row-key table and the generator state the launch left
+            le = hipMemcpy(fold ? t.y2 : t.y, e->row_keys, (size_t)2 * d.nb * sizeof(uint32_t), hipMemcpyDeviceToDevice);
+            if (le == hipSuccess) le = hipMemcpy(fold ? t.y3 : t.y2, e->rng_state, DYF_RNG_STATE_WORDS * sizeof(uint32_t), hipMemcpyDeviceToDevice);
+        }
+        if (le != hipSuccess) rs = fail(e, DYF_ERR_HIP, std::string("dyf_op_sample16: ") + hipGetErrorString(le));
+    } else {
+        (void)hipDeviceSynchronize();  // (release_allocs needs an idle device)
+    }
+    release_allocs(tmp);
+    return rs;
+}
+
 dyf_status dyf_op_sample16(dyf_engine* e, const dyf_sample_op* desc, const dyf_sample_tensors* t, const float* const* params_host, void* stream) {
+    if (e && desc && t && desc->op >= DYF_SOP_READOUT && desc->op <= DYF_SOP_NOISY_CONDITION) {
+        HIP_TRY(e, hipSetDevice(e->cfg.device));
+        return sample_op_net(e, *desc, *t, params_host, (hipStream_t)stream);
+    }
     if (!e || !desc || !t || !t->x[0] || !t->y) return fail(e, DYF_ERR_INVALID_ARGUMENT, "dyf_op_sample16: null argument");
     const dyf_sample_op& d = *desc;
     if (d.op < DYF_SOP_GN_ACT || d.op > DYF_SOP_UP2_EPILOGUE) return fail(e, DYF_ERR_INVALID_ARGUMENT, "dyf_op_sample16: unknown op");
+    if (d.oh || d.ow || d.nearest || d.src_rows || d.iw_store || d.tau != 0.0f || t->col_map || t->y2 || t->y3)
+        return fail(e, DYF_ERR_INVALID_ARGUMENT, "dyf_op_sample16: oh / ow / nearest / src_rows / iw_store / tau / col_map / y2 / y3 belong to the launchers around the networks");
     if (d.nb < 1 || d.h < 1 || d.w < 1 || d.c < 1 || d.c2 < 0 || d.k < 0 || d.pad < 0 || d.groups < 0 || d.film_stride < 0 || d.film_div < 0 ||
         d.part_slots < 0 || d.nsrc < 0 || (d.flags & ~DYF_SOP_NO_STATS))
         return fail(e, DYF_ERR_INVALID_ARGUMENT, "dyf_op_sample16: bad geometry or flags");

@@ -2,6 +2,8 @@
 #pragma once
 #include "common.h"
 
+#include <vector>
+
 #define DYF_MAX_IN_CH 32   // max channels entering the network stem (inputs + condition)
 #define DYF_MAX_OUT_CH 8   // max output channels of the readout
 
@@ -130,6 +132,27 @@ struct ReadoutArgs {
 hipError_t launch_readout(const ReadoutArgs& a, hipStream_t s);
 // fills a.row_tab (oh entries of 32 B) / a.col_tab (ow entries) for the geometry and col_map of `a` (device pointers, writable)
 hipError_t launch_readout_tables(const ReadoutArgs& a, hipStream_t s);
+// readout.0.weight (cin,cout,4,4) -> ReadoutArgs::wgt's order [tap][cin][cout] (the weight upload and the op seam pack with these two)
+inline std::vector<float> pack_readout_weights(const float* w, int cin, int cout) {
+    std::vector<float> pk((size_t)16 * cin * cout);
+    for (int ci = 0; ci < cin; ++ci)
+        for (int co = 0; co < cout; ++co)
+            for (int t = 0; t < 16; ++t) pk[((size_t)t * cin + ci) * cout + co] = w[((size_t)ci * cout + co) * 16 + t];
+    return pk;
+}
+// [tap][64][cout <= 4] fp32 -> ReadoutArgs::wfrag: lane (m = lane & 15, kg = lane >> 4) of (tap, half) holds W[tap][half*32 + kg*8 + e][m]
+inline std::vector<el16_t> pack_readout_frag(const std::vector<float>& pk, int cout) {
+    std::vector<el16_t> wf((size_t)16 * 2 * 64 * 8, 0);
+    for (int t = 0; t < 16; ++t)
+        for (int h2 = 0; h2 < 2; ++h2)
+            for (int lane = 0; lane < 64; ++lane) {
+                const int m = lane & 15, kg = lane >> 4;
+                for (int el = 0; el < 8; ++el)
+                    if (m < cout)
+                        wf[(((size_t)t * 2 + h2) * 64 + lane) * 8 + el] = f32_to_el16(pk[((size_t)t * 64 + h2 * 32 + kg * 8 + el) * cout + m]);
+            }
+    return wf;
+}
 
 // K10: sampler elementwise (dyffusion.py:381-391, :219-227)
 hipError_t launch_cold_update(float* x_s, const float* x_cur, const float* x_next, long long count, hipStream_t s, float* copy = nullptr);

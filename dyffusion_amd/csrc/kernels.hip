@@ -173,6 +173,7 @@ __global__ __launch_bounds__(256) void stem_kernel(StemArgs a) {
 
 hipError_t launch_stem(const StemArgs& a, hipStream_t s) {
     const long long total = (long long)a.n * a.uh * a.uw;
+    dyf_form_note("stem_kernel", a.n);
     hipLaunchKernelGGL(stem_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), (size_t)a.cin * 256 * sizeof(float),
                        s, a);
     return hipGetLastError();
@@ -1300,6 +1301,7 @@ hipError_t launch_readout(const ReadoutArgs& a, hipStream_t s) {
         const unsigned blocks = (unsigned)((halves + 7) / 8);
 #define RW_CASE(C)                                                                                      \
         if (a.cout == C) {                                                                              \
+            dyf_form_note("readout_regw_kernel<" #C ">", a.n);                                          \
             hipLaunchKernelGGL(readout_regw_kernel<C>, dim3(blocks), dim3(256), 0, s, a, per);          \
             return hipGetLastError();                                                                   \
         }
@@ -1310,11 +1312,13 @@ hipError_t launch_readout(const ReadoutArgs& a, hipStream_t s) {
     const int lanes = (a.cin % 8 == 0) ? a.cin / 8 : 0;
 #define RO_CASE(L)                                                                                                   \
     if (lanes == L) {                                                                                                \
+        dyf_form_note("readout_sliced_kernel<" #L ">", a.n);                                                         \
         hipLaunchKernelGGL(readout_sliced_kernel<L>, dim3((unsigned)((total * L + 255) / 256)), dim3(256), lds, s, a); \
         return hipGetLastError();                                                                                    \
     }
     RO_CASE(1) RO_CASE(2) RO_CASE(4) RO_CASE(8) RO_CASE(16)
 #undef RO_CASE
+    dyf_form_note("readout_kernel", a.n);
     hipLaunchKernelGGL(readout_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), lds, s, a);
     return hipGetLastError();
 }

@@ -959,7 +959,7 @@ class HipEngine:
                   film_a: Optional[torch.Tensor] = None, film_c: Optional[torch.Tensor] = None, film_div: int = 0,
                   residual: Optional[torch.Tensor] = None, part: Optional[torch.Tensor] = None, stats: bool = True,
                   mask: Optional[torch.Tensor] = None, p: float = 0.0, rng_site: Optional[int] = None, rng_row_offset: int = 0,
-                  rng_forward: int = 0) -> torch.Tensor:
+                  rng_forward: int = 0, **net):
         """Test seam (dyf_op_sample16): ONE 16-bit sampling kernel between the convs, through its launcher.  `op`: "gn_act",
         "layernorm_c", "head", "up2_nearest", "drop16", "stem_conv", "groupnorm_f32", "up2_bilinear", "up2_epilogue".  `xs`: the device
         tensor(s): NHWC (nb, h, w, c) in the engine's 16-bit dtype; fp32 NHWC for "groupnorm_f32" / "up2_epilogue"; up to four fp32 NCHW
@@ -968,10 +968,15 @@ class HipEngine:
         bias).  film_a / film_c: fp32 device rows (rows, stride) with stride >= c (up2_epilogue: its coefficient rows), `film_div` samples
         per row; residual: 16-bit of x's shape; part: fp32 (nb, slots, c / 8, 2) conv-epilogue partials; stats=False: no statistics
         scratch; mask: uint8 keep mask of the output's shape, or rng_site: the engine's generator.  Returns the output: 16-bit NHWC, or
-        fp32 NCHW for "head"."""
+        fp32 NCHW for "head".  The launchers around the networks ("readout" .. "noisy_condition") take their own keywords:
+        HipEngine._op_sample_net."""
         if op not in L.SAMPLE_OPS:
             raise ValueError(f"unknown sampling op {op!r}")
         xs = [xs] if torch.is_tensor(xs) else list(xs)
+        if L.SAMPLE_OPS[op] >= L.SAMPLE_OPS["readout"]:
+            return self._op_sample_net(op, xs, params, mask=mask, p=p, rng_site=rng_site, rng_row_offset=rng_row_offset, rng_forward=rng_forward, **net)
+        if net:
+            raise ValueError(f"{op}: unknown arguments {sorted(net)}")
         dt = self.torch_dtype
         f32_in = op in ("stem_conv", "groupnorm_f32", "up2_epilogue")
         for t in xs:
@@ -1055,6 +1060,152 @@ class HipEngine:
         arr = (C.c_void_p * max(len(ps), 1))(*[t.ctypes.data for t in ps])
         self._check(self._lib.dyf_op_sample16(self._h, C.byref(desc), C.byref(tens), arr, self._stream()))
         return y
+
+    def _op_sample_net(self, op, xs, params, *, mask=None, p=0.0, rng_site=None, rng_row_offset=0, rng_forward=0, out_hw=None, in_hw=None,
+                       nearest=False, src_rows=0, nb=None, col_map=None, tables=True, fold_rng=False, counters_only=False, dst=None, tau=0.0,
+                       blocks=(), copy=False, iw_store=None):
+        """dyf_op_sample16 for the launchers around the networks (csrc/kernels.hip).  Device tensors, parameters fp32 in PyTorch layouts.
+          readout         xs = [x 16-bit (nb, ih, iw_store, cin)], params = [weight (cin, cout, 4, 4), bias]; out_hw = the native grid;
+                          col_map: int16 device tensor (iw,) of a compact input; tables=False: launch without the tap tables -> fp32 NCHW
+          readout_tables  in_hw, out_hw, nearest, col_map with iw_store = the compact width -> (row_tab, col_tab) int32 (oh | ow, 8): four
+                          byte offsets, four weight bit patterns
+          stem / stem16   xs = 1..4 fp32 NCHW sources of src_rows (or nb) rows; out_hw = (uh, uw); params = [weight (dim, cin), bias] for
+                          stem; nb: output rows (default: the sources'); stem: mask / rng_site dropout -> 16-bit NHWC; stem16:
+                          (nb, uh + 2, uw + 2, 16), with fold_rng also the row-key table (nb, 2) and the generator state (8,), int32 bit patterns
+          rng_begin       nb rows, src_rows per forward, rng_forward, rng_row_offset -> (row-key table, state)
+          rng_clone       xs = [source state int32 (8,)], dst = destination state (not modified), rng_row_offset = row_add -> the new destination
+          time_mlp        xs = [times fp32 (rows,)], params = [w1, b1, w2, b2 (, learned weights)] -> fp32 (rows, 2 dim)
+          film            xs = [SiLU rows fp32 (rows, tdim)] or [] with nb = rows; params = [wf, bf, norm_a, norm_c]; blocks = cout per block
+                          -> (coef_a, coef_c)
+          cold_update     xs = [x_s, x_cur, x_next] fp32 of one shape (nb, ...); copy -> (new x_s, copy or None)
+          noisy_condition xs = [cond (nb, c, h, w)] or [cond, noise]; tau; rng_row_offset -> fp32"""
+        given = {k for k, v, d in (("mask", mask, None), ("p", p, 0.0), ("rng_site", rng_site, None), ("rng_row_offset", rng_row_offset, 0),
+                                   ("rng_forward", rng_forward, 0), ("out_hw", out_hw, None), ("in_hw", in_hw, None), ("nearest", nearest, False),
+                                   ("src_rows", src_rows, 0), ("nb", nb, None), ("col_map", col_map, None), ("tables", tables, True),
+                                   ("fold_rng", fold_rng, False), ("counters_only", counters_only, False), ("dst", dst, None), ("tau", tau, 0.0),
+                                   ("blocks", blocks, ()), ("copy", copy, False), ("iw_store", iw_store, None)) if v is not d and v != d}
+        takes = {"readout": {"out_hw", "nearest", "col_map", "tables"}, "readout_tables": {"in_hw", "out_hw", "nearest", "col_map", "iw_store"},
+                 "stem": {"out_hw", "nearest", "src_rows", "nb", "mask", "p", "rng_site", "rng_row_offset", "rng_forward"},
+                 "stem16": {"out_hw", "nearest", "src_rows", "nb", "fold_rng", "rng_row_offset", "rng_forward"},
+                 "rng_begin": {"nb", "src_rows", "rng_row_offset", "rng_forward"}, "rng_clone": {"dst", "rng_row_offset", "counters_only"},
+                 "time_mlp": set(), "film": {"blocks", "nb"}, "cold_update": {"copy"}, "noisy_condition": {"tau", "rng_row_offset"}}[op]
+        if given - takes:
+            raise ValueError(f"{op}: does not take {sorted(given - takes)}")
+        dev = torch.device("cuda", self.device)
+        ps = [np.ascontiguousarray(t.detach().to("cpu", torch.float32).numpy()) for t in params]
+        desc, tens = L.SampleOp(), L.SampleTensors()
+        desc.op = L.SAMPLE_OPS[op]
+        for t in xs:
+            if not t.is_cuda or not t.is_contiguous():
+                raise ValueError(f"{op}: inputs are contiguous device tensors")
+        dt = self.torch_dtype
+        i32 = lambda *shape: torch.zeros(shape, dtype=torch.int32, device=dev)
+        f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+        want = lambda t, d, n: t.dtype == d and t.dim() == n
+        outs = None
+        if op in ("readout", "readout_tables"):
+            desc.oh, desc.ow, desc.nearest = int(out_hw[0]), int(out_hw[1]), int(bool(nearest))
+            if col_map is not None:
+                if col_map.dtype != torch.int16 or not col_map.is_cuda or not col_map.is_contiguous() or col_map.dim() != 1:
+                    raise ValueError(f"{op}: col_map is a contiguous int16 device vector")
+                tens.col_map = col_map.data_ptr()
+            if op == "readout":
+                if len(xs) != 1 or not want(xs[0], dt, 4) or len(ps) != 2 or ps[0].ndim != 4 or ps[0].shape[0] != xs[0].shape[3] or ps[0].shape[2:] != (4, 4):
+                    raise ValueError("readout: x 16-bit (nb, ih, iw_store, cin), weight (cin, cout, 4, 4), bias (cout)")
+                desc.nb, desc.h, iws, desc.c = xs[0].shape
+                desc.c2 = ps[0].shape[1]
+                desc.w = iws if col_map is None else col_map.numel()
+                desc.iw_store = 0 if col_map is None else iws
+                desc.flags = 0 if tables else L.SOP_NO_TABLES
+                outs = [f32(desc.nb, desc.c2, desc.oh, desc.ow)]
+            else:
+                desc.nb, desc.h, desc.w = 1, int(in_hw[0]), int(in_hw[1])
+                desc.iw_store = 0 if col_map is None else int(iw_store)
+                outs = [i32(desc.oh, 8), i32(desc.ow, 8)]
+        elif op in ("stem", "stem16"):
+            if not 1 <= len(xs) <= 4 or any(not want(t, torch.float32, 4) or t.shape[0] != xs[0].shape[0] or t.shape[2:] != xs[0].shape[2:] for t in xs):
+                raise ValueError(f"{op}: 1..4 fp32 NCHW sources of one (rows, h, w)")
+            rows, _, desc.h, desc.w = xs[0].shape
+            desc.nb = rows if nb is None else int(nb)
+            desc.src_rows = int(src_rows)
+            if (desc.src_rows if desc.src_rows > 0 else desc.nb) != rows:
+                raise ValueError(f"{op}: the sources hold src_rows (or nb) rows")
+            desc.nsrc, desc.c = len(xs), sum(t.shape[1] for t in xs)
+            for i, t in enumerate(xs):
+                desc.ch[i] = t.shape[1]
+            desc.oh, desc.ow, desc.nearest = int(out_hw[0]), int(out_hw[1]), int(bool(nearest))
+            if op == "stem":
+                if len(ps) != 2 or ps[0].ndim != 2 or ps[0].shape[1] != desc.c or ps[1].shape != (ps[0].shape[0],):
+                    raise ValueError("stem: params are weight (dim, cin) and bias (dim)")
+                desc.c2 = ps[0].shape[0]
+                outs = [torch.empty((desc.nb, desc.oh, desc.ow, desc.c2), dtype=dt, device=dev)]
+                desc.drop_p = float(p)
+                if mask is not None and rng_site is not None:
+                    raise ValueError("mask or rng_site, not both")
+                if mask is not None:
+                    if mask.dtype != torch.uint8 or not mask.is_cuda or not mask.is_contiguous() or tuple(mask.shape) != tuple(outs[0].shape):
+                        raise ValueError("mask: a contiguous uint8 device tensor of the output's shape")
+                    desc.drop_mode, tens.mask = 2, mask.data_ptr()
+                elif rng_site is not None:
+                    desc.drop_mode, desc.drop_site, desc.drop_row_offset, desc.drop_forward = 1, int(rng_site), int(rng_row_offset), int(rng_forward)
+            else:
+                outs = [torch.empty((desc.nb, desc.oh + 2, desc.ow + 2, 16), dtype=dt, device=dev)]
+                if fold_rng:
+                    desc.flags, desc.drop_row_offset, desc.drop_forward = L.SOP_FOLD_RNG, int(rng_row_offset), int(rng_forward)
+                    outs += [i32(desc.nb, 2), i32(L.RNG_STATE_WORDS)]
+        elif op == "rng_begin":
+            desc.nb, desc.src_rows, desc.drop_row_offset, desc.drop_forward = int(nb), int(src_rows), int(rng_row_offset), int(rng_forward)
+            outs = [i32(desc.nb, 2), i32(L.RNG_STATE_WORDS)]
+        elif op == "rng_clone":
+            if len(xs) != 1 or dst is None or any(t.dtype != torch.int32 or tuple(t.shape) != (L.RNG_STATE_WORDS,) for t in (xs[0], dst)):
+                raise ValueError("rng_clone: source and destination states are int32 (8,)")
+            desc.nb, desc.drop_row_offset, desc.flags = 1, int(rng_row_offset), L.SOP_COUNTERS_ONLY if counters_only else 0
+            outs = [dst.clone()]
+        elif op == "time_mlp":
+            if len(xs) != 1 or not want(xs[0], torch.float32, 1) or len(ps) not in (4, 5) or ps[2].ndim != 2:
+                raise ValueError("time_mlp: times fp32 (rows,), params w1, b1, w2, b2 (, learned weights)")
+            desc.nb, desc.c = xs[0].shape[0], ps[2].shape[0] // 2
+            desc.c2 = ps[4].size if len(ps) == 5 else 0
+            nfeat = 2 * desc.c2 + 1 if desc.c2 else desc.c
+            if [t.shape for t in ps[:4]] != [(2 * desc.c, nfeat), (2 * desc.c,), (2 * desc.c, 2 * desc.c), (2 * desc.c,)]:
+                raise ValueError("time_mlp: parameter shapes")
+            outs = [f32(desc.nb, 2 * desc.c)]
+        elif op == "film":
+            total = sum(blocks)
+            if len(ps) != 4 or ps[0].ndim != 2 or [t.shape for t in ps] != [(2 * total, ps[0].shape[1]), (2 * total,), (total,), (total,)] or not 1 <= len(blocks) <= 4:
+                raise ValueError("film: params wf (2 total, tdim), bf, norm_a, norm_c; 1..4 blocks")
+            desc.c = ps[0].shape[1]
+            if xs and (len(xs) != 1 or not want(xs[0], torch.float32, 2) or xs[0].shape[1] != desc.c):
+                raise ValueError("film: SiLU rows fp32 (rows, tdim)")
+            desc.nb = xs[0].shape[0] if xs else int(nb)
+            desc.nsrc = len(blocks)
+            for i, c in enumerate(blocks):
+                desc.ch[i] = int(c)
+            outs = [f32(desc.nb, total), f32(desc.nb, total)]
+        elif op == "cold_update":
+            if len(xs) != 3 or any(not want(t, torch.float32, 4) or t.shape != xs[0].shape for t in xs):
+                raise ValueError("cold_update: x_s, x_cur, x_next fp32 of one 4-d shape")
+            desc.nb, desc.c, desc.h, desc.w = xs[0].shape
+            outs = [xs[0].clone()] + ([torch.empty_like(xs[0])] if copy else [])
+            xs = xs[1:]
+        elif op == "noisy_condition":
+            if not 1 <= len(xs) <= 2 or any(not want(t, torch.float32, 4) or t.shape != xs[0].shape for t in xs):
+                raise ValueError("noisy_condition: cond (and noise) fp32 (nb, c, h, w)")
+            desc.nb, desc.c, desc.h, desc.w = xs[0].shape
+            desc.tau, desc.drop_row_offset = float(tau), int(rng_row_offset)
+            outs = [torch.empty_like(xs[0])]
+        for i, t in enumerate(xs):
+            tens.x[i] = t.data_ptr()
+        tens.y = outs[0].data_ptr()
+        if len(outs) > 1:
+            tens.y2 = outs[1].data_ptr()
+        if len(outs) > 2:
+            tens.y3 = outs[2].data_ptr()
+        arr = (C.c_void_p * max(len(ps), 1))(*[t.ctypes.data for t in ps])
+        self._check(self._lib.dyf_op_sample16(self._h, C.byref(desc), C.byref(tens), arr, self._stream()))
+        if op == "cold_update":
+            return outs[0], (outs[1] if copy else None)
+        return outs[0] if len(outs) == 1 else tuple(outs)
 
     def op_upconv2d(self, x_nhwc_bf16: torch.Tensor, weight: torch.Tensor, scale: Optional[torch.Tensor] = None,
                     shift: Optional[torch.Tensor] = None, act: int = 0) -> torch.Tensor:

@@ -214,6 +214,32 @@ dyf_status dyf_op_train_f32(dyf_engine* engine, const dyf_train_op* desc, const 
  *   UP2_BILINEAR  launch_up2x: x[0] 16-bit (nb,h,w,c) [, x[1] (nb,h,w,c2): the upsample of the concatenation] -> (nb,2h,2w,c+c2)
  *   UP2_EPILOGUE  launch_up2x_epilogue: x[0] fp32 (nb,h,w,c), c % 4 == 0; film_a / film_c = the coefficient rows (stride film_stride,
  *                 film_div samples per row); act 0..3; dropout -> y 16-bit (nb,2h,2w,c) = drop(act(lerp(x) * a + c))
+ * The launchers around the networks (csrc/kernels.hip), same rules; x[0] may be NULL where an op lists no input:
+ *   READOUT       launch_readout: x[0] 16-bit (nb,h,iw_store,c) = the decoder output on the (h, w) grid; weight (c,c2,4,4), bias (c2),
+ *                 packed by the code the weight upload uses (pack_readout_weights, and pack_readout_frag + the tap tables of
+ *                 launch_readout_tables exactly when the upload builds them: c == 64, c2 <= 4); (oh, ow) = the native grid; `nearest`;
+ *                 iw_store / col_map: compact columns (col_map device int16 [w]: column -> stored column, -1 = not stored), both or
+ *                 neither; DYF_SOP_NO_TABLES: launch without the tap tables -> y fp32 NCHW (nb,c2,oh,ow)
+ *   READOUT_TABLES launch_readout_tables for (h, w) -> (oh, ow), `nearest`, iw_store / col_map -> y = row_tab (oh entries of 8 words:
+ *                 four byte offsets, four weights), y2 = col_tab (ow entries)
+ *   STEM          launch_stem: x[0..nsrc-1] fp32 NCHW (src_rows or nb, ch[i], h, w), c = sum of ch, resampled to (oh, ow) (`nearest` or
+ *                 bilinear; oh == h and ow == w: identity); weight (c2,c), bias (c2); src_rows: rows the sources hold (0: nb), output row
+ *                 r reads source row r % src_rows; dropout as below -> y 16-bit (nb,oh,ow,c2)
+ *   STEM16        launch_stem16, c <= 15, no parameters -> y 16-bit (nb,oh+2,ow+2,16); DYF_SOP_FOLD_RNG: the start of a forward folded
+ *                 into the launch (StemArgs::rng_state / rng_row_keys of the engine, nb <= 2 max_batch rows, src_rows or nb rows per
+ *                 forward) -> y2 = the row-key table (2 nb words), y3 = the generator state (DYF_RNG_STATE_WORDS words) afterwards
+ *   RNG_BEGIN     launch_rng_begin_forward over nb rows, src_rows (0: nb) rows per forward, from forward index drop_forward and row
+ *                 offset drop_row_offset (set as generator dropout sets them) -> y = the row-key table, y2 = the state afterwards
+ *   RNG_CLONE     launch_rng_clone: x[0] = source state, y = destination state (IN/OUT), DYF_RNG_STATE_WORDS device words each; row_add =
+ *                 drop_row_offset; DYF_SOP_COUNTERS_ONLY
+ *   TIME_MLP      launch_time_mlp: x[0] fp32 (nb) times; c = dim; w1 (2c, c or 2 c2 + 1), b1, w2 (2c,2c), b2 [, learned weights (c2): c2 =
+ *                 learned_half > 0] -> y fp32 (nb, 2c)
+ *   FILM          launch_film: x[0] fp32 (nb, c) SiLU rows or NULL (no time embedding); nsrc blocks of ch[i] channels, total = their sum;
+ *                 wf (2 total, c), bf (2 total), norm_a (total), norm_c (total); block tables built as the weight upload builds them
+ *                 -> y = coef_a, y2 = coef_c, fp32 (nb, total)
+ *   COLD_UPDATE   launch_cold_update over nb * h * w * c floats: y = x_s (IN/OUT), x[0] = x_cur, x[1] = x_next, y2 = copy or NULL
+ *   NOISY_CONDITION launch_noisy_condition over nb rows of h * w * c floats: x[0] = cond, x[1] = noise or NULL (the engine's generator:
+ *                 rows drop_row_offset .., the NEXT field of the stream -- dyf_seed resets the noise-call counter); `tau` -> y
  * Dropout (ops that end in one): drop_mode 2 = mask, a uint8 keep mask of the output's shape; 1 = the engine's generator at site
  * drop_site, forward index drop_forward, global rows drop_row_offset .. + nb - 1 (nb <= 2 max_batch), armed by the code dyf_conv_ex's
  * fields are armed by.  Survivors are scaled by 1 / (1 - drop_p).  Every tensor must stay below the kernels' 32-bit element indices.
@@ -221,9 +247,14 @@ dyf_status dyf_op_train_f32(dyf_engine* engine, const dyf_train_op* desc, const 
  * everything allocated goes back to the engine. */
 typedef enum dyf_sample_op_kind {
     DYF_SOP_GN_ACT = 0, DYF_SOP_LAYERNORM_C = 1, DYF_SOP_HEAD = 2, DYF_SOP_UP2_NEAREST = 3, DYF_SOP_DROP16 = 4, DYF_SOP_STEM_CONV = 5,
-    DYF_SOP_GROUPNORM_F32 = 6, DYF_SOP_UP2_BILINEAR = 7, DYF_SOP_UP2_EPILOGUE = 8
+    DYF_SOP_GROUPNORM_F32 = 6, DYF_SOP_UP2_BILINEAR = 7, DYF_SOP_UP2_EPILOGUE = 8, DYF_SOP_READOUT = 9, DYF_SOP_READOUT_TABLES = 10,
+    DYF_SOP_STEM = 11, DYF_SOP_STEM16 = 12, DYF_SOP_RNG_BEGIN = 13, DYF_SOP_RNG_CLONE = 14, DYF_SOP_TIME_MLP = 15, DYF_SOP_FILM = 16,
+    DYF_SOP_COLD_UPDATE = 17, DYF_SOP_NOISY_CONDITION = 18
 } dyf_sample_op_kind;
 #define DYF_SOP_NO_STATS 1
+#define DYF_SOP_NO_TABLES 2
+#define DYF_SOP_FOLD_RNG 4
+#define DYF_SOP_COUNTERS_ONLY 8
 typedef struct dyf_sample_op {
     int32_t op, nb, h, w, c, c2, k, pad, groups, act, flags;
     int32_t film_stride, film_div, part_slots;
@@ -232,6 +263,8 @@ typedef struct dyf_sample_op {
     float drop_p;
     int32_t drop_site;
     uint32_t drop_row_offset, drop_forward;
+    int32_t oh, ow, nearest, src_rows, iw_store;
+    float tau;
 } dyf_sample_op;
 typedef struct dyf_sample_tensors {
     const void* x[4];
@@ -241,6 +274,9 @@ typedef struct dyf_sample_tensors {
     const float* part;
     const uint8_t* mask;
     void* y;
+    const int16_t* col_map;
+    void* y2;
+    void* y3;
 } dyf_sample_tensors;
 dyf_status dyf_op_sample16(dyf_engine* engine, const dyf_sample_op* desc, const dyf_sample_tensors* t, const float* const* params_host,
                            void* stream);

@@ -71,6 +71,30 @@ def mask_nchw(nb, shape_hwc, p, seed, fwd, layer, row_offset=0):
     return torch.from_numpy(np.stack(rows, 0).astype(np.uint8)).permute(0, 3, 1, 2).contiguous()
 
 
+NOISE_SALT = 0x4E6F6973  # csrc/kernels.hip noisy_condition_kernel: the noise stream's row keys take seed_hi ^ this
+
+
+def noise_words(seed, call, grow, n):
+    """The two hashed words per element of the engine's noise field number `call` (the noise-call counter, 0 after dyf_seed) for global
+    batch row `grow`: a row key on (seed_lo, seed_hi ^ NOISE_SALT, call, grow), then w0 = fmix32(e * 0x9E3779B1 + k0), w1 = fmix32(w0 ^ k1)
+    for element e = 0 .. n - 1 of the row."""
+    k0, k1 = row_key((seed & 0xFFFFFFFF) | ((((seed >> 32) & 0xFFFFFFFF) ^ NOISE_SALT) << 32), call, grow)
+    e = np.arange(n, dtype=np.uint64)
+    w0 = fmix32((e * np.uint64(0x9E3779B1) + k0) & M32)
+    return w0, fmix32(w0 ^ k1)
+
+
+def noise_field(seed, call, grow, n, dtype=np.float64):
+    """Box-Muller on those words -- what noisy_condition_kernel draws without injected noise, a function of (seed, call counter,
+    global row): u = ((w >> 8) + 0.5) / 2^24, z = sqrt(-2 ln u1) cos(2 pi u2).  float64: the statement; float32: the kernel's own steps
+    (u rounded to fp32 -- 25 significant bits do not fit -- and an fp32 angle)."""
+    w0, w1 = noise_words(seed, call, grow, n)
+    f = np.dtype(dtype).type
+    u1 = ((w0 >> np.uint64(8)).astype(dtype) + f(0.5)) * f(1.0 / 16777216.0)
+    u2 = ((w1 >> np.uint64(8)).astype(dtype) + f(0.5)) * f(1.0 / 16777216.0)
+    return np.sqrt(f(-2.0) * np.log(u1)) * np.cos(f(6.283185307179586) * u2)
+
+
 def unet_simple_site_shapes(dim, uh, uw):
     """(H, W, C) of the 12 dropout sites (UNetBlock outputs) of unet_simple at a uh x uw resampled grid."""
     d = dim

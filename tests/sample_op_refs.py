@@ -179,6 +179,9 @@ class Built:
     def __init__(self, op, xs, params, kw, fn, kind="r16", form=None, quiet=(), switch=None, gen=None, p=0.0, keep=None):
         self.op, self.xs, self.params, self.kw, self.fn, self.kind = op, xs, params, kw, fn, kind
         self.form, self.quiet, self.switch, self.gen, self.p, self.keep = form, quiet, dict(switch or {}), gen, p, keep
+        # seed: dyf_seed(SEED) first (generator ops without a dropout); repeat: the op runs that often in a row and every call's outputs
+        # are compared; rows: the batch rows the launcher notes its form for
+        self.seed, self.repeat, self.rows = gen is not None, 1, xs[0].shape[0] if xs else 0
 
     def ref(self, dtype=torch.float64, mutant=None):
         c = lambda t: None if t is None else t.to(dtype)
@@ -474,3 +477,385 @@ INVISIBLE = {
     "layernorm_c": [("vec-C64-hw33", "no_eps")],
     "up2_epilogue": [("C64-1x1", "border_mirrored")],
 }
+
+
+# =================================================================================== the launchers around the networks (csrc/kernels.hip)
+# readout, readout tables, the two stems, time MLP and FiLM heads, the sampler's elementwise kernels and the generator's bookkeeping, through
+# the same seam.  An op here may return several tensors: Built.kind is then a tuple, one kind per output ("eq": integers, equal).
+NET_OPS = ("readout", "stem", "stem16", "time_mlp", "film", "cold_update", "noisy_condition", "rng_begin", "rng_clone")
+READOUT_MUTANTS = ("border_mirrored", "border_clamped", "parity_swapped", "not_flipped", "no_bias")
+TAU = 0.3
+
+
+def outputs(v):
+    return list(v) if isinstance(v, (tuple, list)) else [v]
+
+
+def nearest_floor_is_exact(n_in, n_out):
+    """bilinear_coord's nearest mode floors (float)dst * ((float)n_in / (float)n_out) in fp32: does that equal floor(dst n_in / n_out) for every dst?"""
+    dst = np.arange(n_out)
+    f32 = np.floor(dst.astype(np.float32) * (np.float32(n_in) / np.float32(n_out))).astype(np.int64)
+    return bool(np.array_equal(np.minimum(f32, n_in - 1), (dst * n_in) // n_out))
+
+
+def readout_taps(n_in, n_out, nearest, dtype=torch.float64):
+    """The readout's stencil along one axis, from the resample matrix alone: output o reads neighbours u of the transposed conv's 2 n_in
+    grid with weights M[o, u]; u gathers input i through kernel tap k = u + 1 - 2 i in 0..3, i.e. i = (u + 1) >> 1 (k = 0 or 1) and
+    i - 1 (k = 2 or 3).  -> (idx (n_out, 4) long: the input index of tap k, possibly -1 or n_in = outside; wgt (n_out, 4))."""
+    M = T._resample_matrix(2 * n_in, n_out, nearest, dtype)
+    idx, wgt = torch.full((n_out, 4), -1, dtype=torch.long), torch.zeros(n_out, 4, dtype=dtype)
+    for o in range(n_out):
+        for u in M[o].nonzero().flatten().tolist():
+            for i in ((u + 1) >> 1, ((u + 1) >> 1) - 1):
+                k = u + 1 - 2 * i
+                idx[o, k], wgt[o, k] = i, wgt[o, k] + M[o, u]
+    return idx, wgt
+
+
+def _tap_gather(idx, wgt, n, mutant):
+    """-> (index inside the image, effective weight): a tap outside the image contributes nothing -- or, for the mutants, is mirrored / clamped in."""
+    out = (idx < 0) | (idx >= n)
+    if mutant == "border_mirrored":
+        g = torch.where(idx < 0, -idx, torch.where(idx >= n, 2 * n - 2 - idx, idx)).clamp(0, n - 1)
+        return g, wgt
+    if mutant == "border_clamped":
+        return idx.clamp(0, n - 1), wgt
+    return idx.clamp(0, n - 1), wgt * (~out).to(wgt.dtype)
+
+
+def readout_stencil(x, w, b, oh, ow, nearest, mutant=None):
+    """The readout as the kernels evaluate it: 16 (kh, kw) taps per native pixel, each one 64-channel contraction times its bilinear weight."""
+    nb, ih, iw, _ = x.shape
+    (iy, wy), (ix, wx) = readout_taps(ih, oh, nearest, x.dtype), readout_taps(iw, ow, nearest, x.dtype)
+    (gy, wy), (gx, wx) = _tap_gather(iy, wy, ih, mutant), _tap_gather(ix, wx, iw, mutant)
+    if mutant == "parity_swapped":
+        w = w[:, :, [1, 0, 3, 2]][:, :, :, [1, 0, 3, 2]]
+    if mutant == "not_flipped":
+        w = w.flip(2, 3)
+    xg = x[:, gy][:, :, :, gx]  # (nb, oh, kh, ow, kw, cin)
+    y = torch.einsum("nyhxwc,cohw,yh,xw->noyx", xg, w, wy, wx)
+    return y if mutant == "no_bias" else y + b[None, :, None, None]
+
+
+def readout(x, w, b, oh, ow, nearest, mutant=None):
+    """ConvTranspose2d(k4, s2, p1) and the final resample: x NHWC (nb, ih, iw, cin), w (cin, cout, 4, 4) -> NCHW (nb, cout, oh, ow)."""
+    if mutant is not None:  # ("stencil": the stencil statement itself, nothing edited)
+        return readout_stencil(x, w, b, oh, ow, nearest, None if mutant == "stencil" else mutant)
+    y = torch.nn.functional.conv_transpose2d(x.permute(0, 3, 1, 2), w, b, stride=2, padding=1)
+    return T.resize(y.permute(0, 2, 3, 1), oh, ow, nearest).permute(0, 3, 1, 2)
+
+
+def readout_columns(iw, ow, nearest):
+    """The input columns the reference stencil reads with a non-zero weight -> (sorted stored columns, col_map (iw,) int16: -1 = not stored)."""
+    idx, wgt = readout_taps(iw, ow, nearest)
+    used = sorted({int(i) for i, g in zip(idx.flatten().tolist(), wgt.flatten().tolist()) if g != 0 and 0 <= i < iw})
+    cmap = torch.full((iw,), -1, dtype=torch.int16)
+    cmap[used] = torch.arange(len(used), dtype=torch.int16)
+    return used, cmap
+
+
+def stem(srcs, w, b, uh, uw, nearest=False, src_rows=0, nb=None, keep=None, p=0.0, mutant=None):
+    """cat of NCHW sources (row r of the output reads source row r % src_rows) -> resample to (uh, uw) -> 1x1 conv -> Dropout: NHWC.
+    w = None: the resample alone (the fused stem)."""
+    if mutant == "second_source_offset" and len(srcs) > 1:  # the second source's channels start one channel late
+        srcs = [srcs[0], srcs[1].roll(1, 1)] + list(srcs[2:])
+    x = torch.cat(srcs, 1)
+    nb = x.shape[0] if nb is None else nb
+    rows = torch.arange(nb) % (src_rows if src_rows > 0 else nb)
+    if mutant == "src_rows_ignored":  # row r read as row r: past the rows the sources hold
+        x = torch.cat([x, torch.zeros(nb - x.shape[0], *x.shape[1:], dtype=x.dtype)])
+        rows = torch.arange(nb)
+    y = T.resize(x[rows].permute(0, 2, 3, 1), uh, uw, nearest)
+    if w is None:
+        return y
+    y = y @ w.T
+    return _drop(y if mutant == "no_bias" else y + b, keep, p)
+
+
+def stem16(srcs, uh, uw, nearest=False, src_rows=0, nb=None, mutant=None):
+    """The fused stem's tensor: (nb, uh + 2, uw + 2, 16), zero border, channels = the resampled sources, then 1 (slot cin), then zeros."""
+    y = stem(srcs, None, None, uh, uw, nearest, src_rows, nb, mutant=mutant)
+    cin = y.shape[-1]
+    out = torch.zeros(y.shape[0], uh + 2, uw + 2, 16, dtype=y.dtype)
+    out[:, 1:-1, 1:-1, :cin] = y
+    if mutant != "no_bias_slot":
+        out[:, 1:-1, 1:-1, cin] = 1
+    return out
+
+
+def time_mlp(t, w1, b1, w2, b2, learned=None, mutant=None):
+    """oracle/nets.py time_embedding, and the SiLU every block's time_mlp starts with: (rows,) -> (rows, 2 dim)."""
+    tt = t[:, None]
+    sc = (lambda a: torch.cat([a.cos(), a.sin()], -1)) if mutant == "sincos_swapped" else (lambda a: torch.cat([a.sin(), a.cos()], -1))
+    if learned is not None:
+        e = torch.cat([tt, sc(tt * learned[None, :] * 2 * math.pi)], -1)
+    else:
+        half = w1.shape[1] // 2
+        freqs = torch.exp(torch.arange(half, dtype=t.dtype) * (-math.log(10000.0) / (half if mutant == "half_for_half_minus_1" else half - 1)))
+        e = sc(tt * freqs[None, :])
+    h = torch.nn.functional.gelu(e @ w1.T + b1, approximate="tanh" if mutant == "tanh_gelu" else "none")
+    return torch.nn.functional.silu(h @ w2.T + b2)
+
+
+def film(silu, wf, bf, norm_a, norm_c, blocks, rows, mutant=None):
+    """oracle/nets.py film per block (Linear -> chunk(scale, shift)), folded with the block's norm: a = norm_a (1 + scale),
+    c = norm_c (1 + scale) + shift; wf holds, per block, its scale rows then its shift rows.  silu None: scale = shift = 0."""
+    A, Cc, off = [], [], 0
+    for co in blocks:
+        r0 = off if mutant == "blk_off_single" else 2 * off
+        if silu is None:
+            scale = shift = torch.zeros(rows, co, dtype=norm_a.dtype)
+        else:
+            ss = silu @ wf[r0:r0 + 2 * co].T + bf[r0:r0 + 2 * co]
+            scale, shift = (ss[:, co:], ss[:, :co]) if mutant == "rows_swapped" else (ss[:, :co], ss[:, co:])
+        A.append(norm_a[off:off + co] * (1 + scale))
+        Cc.append(norm_c[off:off + co] * (1 + scale) + shift)
+        off += co
+    return torch.cat(A, 1), torch.cat(Cc, 1)
+
+
+def gen_noise(shape, call, dtype=torch.float64):
+    """The field the engine's generator draws at noise call `call` (dyf_seed(SEED), rows ROW_OFFSET ..), rebuilt on the host."""
+    n = int(np.prod(shape[1:]))
+    npdt = np.float64 if dtype == torch.float64 else np.float32
+    return torch.from_numpy(np.stack([rng_host.noise_field(SEED, call, ROW_OFFSET + r, n, npdt) for r in range(shape[0])])).reshape(shape)
+
+
+def begin_keys(fwd0, row0, rows, per):
+    """(row-key table (rows, 2), generator state afterwards) of a forward start over `rows` launch rows, `per` rows per forward."""
+    keys = np.array([[int(k) for k in rng_host.row_key(SEED, fwd0 + r // per, row0 + r % per)] for r in range(rows)], dtype=np.uint32)
+    state = np.array([SEED & 0xFFFFFFFF, SEED >> 32, fwd0 + -(-rows // per), row0, 0, 0, 0, 0], dtype=np.uint32)
+    return torch.from_numpy(keys.view(np.int32)), torch.from_numpy(state.view(np.int32))
+
+
+RO_GEOM = {"ident": ((2, 3), (4, 6)), "down": ((6, 8), (5, 7)), "up": ((2, 2), (9, 11)), "one": ((1, 1), (3, 3))}
+RO_FORMS = {  # switches / tables -> the form launch_readout notes ({co}: the output channels)
+    "dma": ({}, True, "readout_dma_kernel"), "nodma": ({"DYF_READOUT_DMA": "0"}, True, "readout_mfma_kernel"), "notab": ({}, False, "readout_mfma_kernel"),
+    "regw": ({"DYF_READOUT_MFMA": "0"}, True, "readout_regw_kernel<{co}>"),
+    "sliced": ({"DYF_READOUT_MFMA": "0", "DYF_READOUT_REGW": "0"}, True, "readout_sliced_kernel<8>")}
+RO_QUIET = ("readout_dma_kernel", "readout_mfma_kernel", "readout_kernel") + tuple(f"readout_regw_kernel<{c}>" for c in (1, 2, 3, 4)) + \
+    tuple(f"readout_sliced_kernel<{c}>" for c in (1, 2, 4, 8, 16))
+STEM_QUIET = ("stem_kernel", "stem16_kernel", "stem16_rows_kernel")
+
+
+def net_specs(op):
+    S = []
+    if op == "readout":
+        def ro(cid, geom, form, co, cin=64, nb=3, **kw):
+            (ih, iw), (oh, ow) = geom
+            sw, tab, name = RO_FORMS[form] if form in RO_FORMS else ({}, True, form)
+            S.append((cid, dict(cin=cin, co=co, nb=nb, ih=ih, iw=iw, oh=oh, ow=ow, switch=sw, tables=tab, form=name.format(co=co), **kw)))
+        # every form on every geometry, bilinear and nearest; nb = 3: 72 / 105 / 297 / 27 pixels, the ragged last 16-pixel group spans
+        # samples (27: an odd count, and half-waves 4..7 of the register-weight form start past the end)
+        for gi, (g, geom) in enumerate(RO_GEOM.items()):
+            for fi, form in enumerate(RO_FORMS):
+                for near in (0, 1):
+                    ro(f"{form}-{g}{'-nearest' if near else ''}", geom, form, 1 + (gi + fi + near) % 4, nearest=near)
+        for form in RO_FORMS:  # 73 728 pixels: 4608 groups on 4096 waves, groups_per_wave = 2
+            ro(f"{form}-big", ((8, 8), (192, 192)), form, 3, nb=2)
+        for co in (1, 2, 3, 4):
+            ro(f"regw-down-co{co}", RO_GEOM["down"], "regw", co)
+        for cin, co in ((8, 8), (16, 5), (32, 8), (128, 3)):
+            ro(f"sliced-cin{cin}-co{co}", RO_GEOM["down"], f"readout_sliced_kernel<{cin // 8}>", co, cin=cin)
+            ro(f"sliced-cin{cin}-co{co}-up-nearest", RO_GEOM["up"], f"readout_sliced_kernel<{cin // 8}>", co, cin=cin, nearest=1)
+        for cin, co in ((12, 3), (24, 8)):
+            ro(f"generic-cin{cin}-co{co}", RO_GEOM["down"], "readout_kernel", co, cin=cin)
+            ro(f"generic-cin{cin}-co{co}-up", RO_GEOM["up"], "readout_kernel", co, cin=cin)
+        for form in ("dma", "notab", "nodma"):  # compact columns: 3 native columns read 8 of 16 decoder columns
+            ro(f"{form}-compact", ((6, 16), (5, 3)), form, 3, compact=1)
+        ro("dma-compact-nearest", ((6, 16), (5, 3)), "dma", 2, compact=1, nearest=1)
+        ro("regw-switch-compact", ((6, 16), (5, 3)), "regw", 3, compact=1, form_override="readout_dma_kernel")  # a compact input stays on the MFMA forms
+    elif op == "stem16":
+        def s16(cid, ch, hw, uhw, form, nb=2, **kw):
+            S.append((cid, dict(ch=ch, h=hw[0], w=hw[1], uh=uhw[0], uw=uhw[1], nb=nb, form=form, **kw)))
+        R, K = "stem16_rows_kernel", "stem16_kernel"
+        s16("rows-2lane-uw254-c8", (8,), (5, 40), (8, 254), R)                  # the smallest width the rows form takes
+        for uh in (7, 8, 9):                                                      # a border-only last block, rows 8-9, rows 8-10
+            s16(f"rows-1lane-uw256-c3-uh{uh}", (3,), (5, 40), (uh, 256), R)
+            s16(f"rows-2lane-uw256-c9-uh{uh}", (5, 4), (5, 40), (uh, 256), R)
+        s16("rows-1lane-uw256-c8", (8,), (5, 40), (8, 256), R)                    # the bias slot in the second half
+        s16("rows-2lane-uw256-c15", (15,), (5, 40), (8, 256), R)
+        s16("rows-1lane-uw256-c8-2src", (5, 3), (5, 40), (8, 256), R)
+        s16("rows-1lane-uw256-c8-3src", (3, 3, 2), (5, 40), (8, 256), R)
+        s16("rows-1lane-uw256-c8-4src", (3, 2, 2, 1), (5, 40), (8, 256), R)
+        s16("rows-2lane-uw256-c9-4src", (3, 3, 2, 1), (5, 40), (8, 256), R)
+        s16("rows-1lane-uw256-c3-nearest", (3,), (5, 40), (8, 256), R, nearest=1)
+        s16("rows-2lane-uw256-c9-nearest", (5, 4), (5, 40), (7, 256), R, nearest=1)
+        s16("rows-1lane-uw256-c8-srcrows1", (8,), (5, 40), (8, 256), R, src_rows=1)
+        s16("rows-2lane-uw254-c8-srcrows1", (5, 3), (5, 40), (9, 254), R, src_rows=1)
+        s16("rows-1lane-uw256-c8-fold", (8,), (5, 40), (8, 256), R, nb=4, src_rows=2, fold=1)
+        s16("plain-lds-c15-w80", (15,), (5, 80), (8, 256), K)                     # 10 x 80 x 16 floats of rows: past 48 KB
+        s16("plain-h12-uh8", (3,), (12, 40), (8, 256), K)                         # downsampled rows: more than ST_ROWS + 2 source rows
+        s16("plain-norows-c8", (8,), (5, 40), (8, 256), K, switch={"DYF_STEM16_ROWS": "0"})
+        s16("plain-ident-5x7-c3", (3,), (5, 7), (5, 7), K, nb=3)
+        s16("plain-up-3x5-c9-4src", (3, 3, 2, 1), (3, 5), (7, 9), K, nb=3)
+        s16("plain-down-9x11-c15", (15,), (9, 11), (4, 6), K, nb=3)
+        s16("plain-up-3x5-c5-nearest", (4, 1), (3, 5), (6, 15), K, nb=3, nearest=1)
+        s16("plain-up-3x5-c8-srcrows1", (8,), (3, 5), (7, 9), K, src_rows=1)
+        s16("plain-up-3x5-c3-fold", (3,), (3, 5), (7, 9), K, nb=3, fold=1)
+    elif op == "stem":
+        def st(cid, dim, ch, hw, uhw, nb=3, **kw):
+            S.append((cid, dict(dim=dim, ch=ch, h=hw[0], w=hw[1], uh=uhw[0], uw=uhw[1], nb=nb, **kw)))
+        for dim in (8, 12, 64):                                                   # 297 pixels: the second workgroup ends mid-way; 12: scalar stores
+            st(f"d{dim}-up-3x5-c5", dim, (3, 2), (3, 5), (9, 11))
+        st("d64-ident-5x7-c3", 64, (3,), (5, 7), (5, 7))
+        st("d12-down-9x11-c9-4src", 12, (3, 3, 2, 1), (9, 11), (4, 6))
+        st("d64-up-3x5-c6-3src-nearest", 64, (3, 2, 1), (3, 5), (6, 15), nearest=1)
+        st("d8-up-3x5-c32", 8, (32,), (3, 5), (9, 11))
+        st("d64-up-3x5-c5-maskdrop", 64, (3, 2), (3, 5), (9, 11), drop="mask")
+        st("d12-up-3x5-c5-gendrop", 12, (3, 2), (3, 5), (9, 11), drop="gen")
+        st("d64-up-3x5-c5-gendrop", 64, (3, 2), (3, 5), (9, 11), drop="gen")
+        st("d64-up-3x5-c5-srcrows2-nb5", 64, (3, 2), (3, 5), (9, 11), nb=5, src_rows=2)
+        st("d12-ident-5x7-c5-srcrows1-nb3", 12, (3, 2), (5, 7), (5, 7), src_rows=1)
+    elif op == "time_mlp":
+        S = [("sinu-d32", dict(dim=32)), ("sinu-d64", dict(dim=64)), ("learned8-d32", dict(dim=32, lh=8)), ("learned5-d64", dict(dim=64, lh=5))]
+    elif op == "film":
+        S = [(f"b8+24+64-rows{r}{'-notime' if nt else ''}", dict(blocks=(8, 24, 64), rows=r, notime=nt)) for r in (1, 3) for nt in (0, 1)]
+        S.append(("b64-rows3", dict(blocks=(64,), rows=3, notime=0)))
+    elif op == "cold_update":
+        S = [("3x3x9x11", dict(copy=0)), ("3x3x9x11-copy", dict(copy=1))]         # 891 floats: the fourth workgroup ends mid-way
+    elif op == "noisy_condition":
+        S = [("3x3x9x11-injected", dict(gen=0)), ("3x3x9x11-generator-2calls", dict(gen=1))]  # rows of 297 floats, global rows 5..7
+    elif op == "rng_begin":
+        S = [("rows5-per2", dict(rows=5, per=2)), ("rows3", dict(rows=3, per=0)), ("rows8-per4", dict(rows=8, per=4))]
+    elif op == "rng_clone":
+        S = [("full-rowadd7", dict(counters=0)), ("counters-only", dict(counters=1))]
+    return S
+
+
+def net_build(op, a, dtname):
+    dt = DTYPES[dtname]
+    r16 = lambda t: round16(t, dt)
+    if op == "readout":
+        cin, co, nb, ih, iw, oh, ow, near = a["cin"], a["co"], a["nb"], a["ih"], a["iw"], a["oh"], a["ow"], bool(a.get("nearest"))
+        g = _gen(20, cin, co, nb, ih, iw, oh, ow)
+        # 16-bit activations and 16-bit weights: the fp32-weight forms and the MFMA forms then see the same numbers
+        x = r16(_rn(g, nb, ih, iw, cin, scale=1.5))
+        w, b = r16(_rn(g, cin, co, 4, 4, scale=1.5 / math.sqrt(4 * cin))).float(), _rn(g, co, scale=0.5).float()
+        kw = dict(out_hw=(oh, ow), nearest=near, tables=a["tables"])
+        xs, fn = [x], (lambda c, m: readout(c(x), c(w), c(b), oh, ow, near, m))
+        if a.get("compact"):
+            used, cmap = readout_columns(iw, ow, near)
+            kw["col_map"] = cmap
+            xs = [x[:, :, used].contiguous()]
+            xw = x[:, :, [min(j, len(used) - 1) for j in range(iw)]]  # col_map ignored: decoder column j read at stored column j
+            fn = lambda c, m: readout(c(xw if m == "col_map_ignored" else x), c(w), c(b), oh, ow, near, None if m == "col_map_ignored" else m)
+        big = nb * oh * ow > 4096
+        b_ = Built(op, xs, [w, b], kw, fn, kind="f32", form=a.get("form_override", a["form"]), quiet=RO_QUIET, switch=a["switch"])
+        b_.stencil = not big  # (the 16-tap gather of the big case would hold 75 M doubles)
+        return b_
+    if op in ("stem", "stem16"):
+        ch, h, w, uh, uw, nb, near, sr = a["ch"], a["h"], a["w"], a["uh"], a["uw"], a["nb"], bool(a.get("nearest")), a.get("src_rows", 0)
+        g = _gen(21 if op == "stem" else 22, sum(ch), len(ch), h, w, uh, uw, nb, sr, a.get("dim", 0))
+        srcs = [_rn(g, sr if sr else nb, c, h, w, scale=1.5).float() for c in ch]
+        kw = dict(out_hw=(uh, uw), nearest=near, src_rows=sr, nb=nb)
+        if op == "stem":
+            dim = a["dim"]
+            wt, b = _rn(g, dim, sum(ch), scale=1.5 / math.sqrt(sum(ch))).float(), _rn(g, dim, scale=0.5).float()
+            keep, gen = _drop_kw(g, a.get("drop"), (nb, uh, uw, dim), P_DROP, kw)
+            fn = lambda c, m: stem([c(s) for s in srcs], c(wt), c(b), uh, uw, near, sr, nb, c(keep), P_DROP, m)
+            out = Built(op, srcs, [wt, b], kw, fn, form="stem_kernel", quiet=STEM_QUIET, gen=gen, p=P_DROP, keep=keep)
+        else:
+            fn = lambda c, m: stem16([c(s) for s in srcs], uh, uw, near, sr, nb, m)
+            kind = "r16"
+            if a.get("fold"):
+                kw.update(fold_rng=True, rng_row_offset=ROW_OFFSET, rng_forward=FORWARD)
+                keys, state = begin_keys(FORWARD, ROW_OFFSET, nb, sr if sr else nb)
+                fn, kind = (lambda c, m: (stem16([c(s) for s in srcs], uh, uw, near, sr, nb, m), keys, state)), ("r16", "eq", "eq")
+            out = Built(op, srcs, [], kw, fn, kind=kind, form=a["form"], quiet=STEM_QUIET, switch=a.get("switch"))
+            out.seed, out.cin = bool(a.get("fold")), sum(ch)
+        out.rows = nb
+        return out
+    if op == "time_mlp":
+        dim, lh = a["dim"], a.get("lh", 0)
+        g = _gen(23, dim, lh)
+        # the sampler's times: 0, fractions of a step, whole steps up to the horizon of 64
+        t = torch.tensor([0.0, 0.25, 1.0 / 3.0, 0.999, 1.0, 7.5, 33.0, 63.9, 64.0], dtype=torch.float64).float()
+        nfeat = 2 * lh + 1 if lh else dim
+        ps = [_rn(g, 2 * dim, nfeat, scale=1.0 / math.sqrt(nfeat)).float(), _rn(g, 2 * dim, scale=0.3).float(),
+              _rn(g, 2 * dim, 2 * dim, scale=1.0 / math.sqrt(2 * dim)).float(), _rn(g, 2 * dim, scale=0.3).float()]
+        if lh:
+            ps.append(_rn(g, lh, scale=LEARNED_SCALE).float())
+        return Built(op, [t], ps, {}, lambda c, m: time_mlp(c(t), *[c(q) for q in ps[:4]], learned=c(ps[4]) if lh else None, mutant=m), kind="f32")
+    if op == "film":
+        blocks, rows, tdim = a["blocks"], a["rows"], 64
+        total = sum(blocks)
+        g = _gen(24, total, rows, a["notime"])
+        silu = None if a["notime"] else _rn(g, rows, tdim, scale=0.7).float()
+        ps = [_rn(g, 2 * total, tdim, scale=1.0 / math.sqrt(tdim)).float(), _rn(g, 2 * total, scale=0.3).float(),
+              (1.0 + _rn(g, total, scale=0.3)).float(), _rn(g, total, scale=0.5).float()]
+        out = Built(op, [] if silu is None else [silu], ps, dict(blocks=blocks, nb=rows), lambda c, m: film(c(silu), *[c(q) for q in ps], blocks, rows, m),
+                    kind=("f32", "f32"))
+        out.rows = rows
+        return out
+    if op == "cold_update":
+        g = _gen(25, a["copy"])
+        xs = [_rn(g, 3, 3, 9, 11, scale=1.5).float() for _ in range(3)]
+        fn = lambda c, m: (c(xs[0]) - c(xs[1]) + c(xs[2]),) * (2 if a["copy"] else 1)
+        return Built(op, xs, [], dict(copy=bool(a["copy"])), fn, kind=("f32", "f32") if a["copy"] else ("f32",))
+    if op == "noisy_condition":
+        g = _gen(26, a["gen"])
+        cond, tau = _rn(g, 3, 3, 9, 11, scale=1.5).float(), float(np.float32(TAU))
+        mix = lambda c, z: tau * c(cond) + (1.0 - tau) * z
+        if not a["gen"]:
+            noise = _rn(g, 3, 3, 9, 11).float()
+            return Built(op, [cond, noise], [], dict(tau=tau), lambda c, m: mix(c, c(noise)), kind="f32")
+        # two calls in a row: the second draws the NEXT field of the stream
+        fn = lambda c, m: tuple(mix(c, gen_noise(cond.shape, 0 if m == "same_field_twice" else call, c(cond).dtype)) for call in (0, 1))
+        out = Built(op, [cond], [], dict(tau=tau, rng_row_offset=ROW_OFFSET), fn, kind=("f32", "f32"))
+        out.seed, out.repeat = True, 2
+        return out
+    if op == "rng_begin":
+        rows, per = a["rows"], a["per"]
+        out = Built(op, [], [], dict(nb=rows, src_rows=per, rng_row_offset=ROW_OFFSET, rng_forward=FORWARD),
+                    lambda c, m: begin_keys(FORWARD, ROW_OFFSET, rows, per if per else rows), kind=("eq", "eq"))
+        out.seed, out.rows = True, rows
+        return out
+    if op == "rng_clone":
+        src, dst = torch.arange(1, 9, dtype=torch.int32) * 1000003, torch.arange(11, 19, dtype=torch.int32)
+        want = dst.clone()
+        if a["counters"]:
+            want[2], want[4] = src[2], src[4]
+        else:
+            want = src.clone()
+            want[3] += 7
+        return Built(op, [src], [], dict(dst=dst, rng_row_offset=7, counters_only=bool(a["counters"])), lambda c, m: want, kind="eq")
+    raise ValueError(op)
+
+
+LEARNED_SCALE = 0.05  # learned frequencies: 2 pi t w stays below ~60 rad at t = 64, where an fp32 angle still resolves 4e-6 rad
+
+NET_MUTANTS = {
+    "readout": [(c, m) for c in ("dma-down", "nodma-down", "notab-down", "regw-down", "sliced-down", "dma-up-nearest", "sliced-cin32-co8", "generic-cin12-co3",
+                                 "dma-compact") for m in READOUT_MUTANTS]
+    + [(c, m) for c in ("dma-ident", "regw-up", "dma-one") for m in ("parity_swapped", "not_flipped", "no_bias", "border_clamped")]
+    + [(c, "col_map_ignored") for c in ("dma-compact", "notab-compact", "nodma-compact", "dma-compact-nearest")],
+    "stem": [(c, m) for c in ("d8-up-3x5-c5", "d12-up-3x5-c5", "d64-up-3x5-c5", "d12-down-9x11-c9-4src") for m in ("second_source_offset", "no_bias")]
+    + [(c, "src_rows_ignored") for c in ("d64-up-3x5-c5-srcrows2-nb5", "d12-ident-5x7-c5-srcrows1-nb3")],
+    "stem16": [(c, m) for c in ("rows-2lane-uw256-c9-uh8", "rows-1lane-uw256-c8-2src", "rows-2lane-uw256-c9-4src", "plain-up-3x5-c9-4src")
+               for m in ("second_source_offset", "no_bias_slot")]
+    + [(c, "no_bias_slot") for c in ("rows-1lane-uw256-c3-uh8", "rows-1lane-uw256-c8", "rows-2lane-uw256-c15", "plain-ident-5x7-c3")]
+    + [(c, "src_rows_ignored") for c in ("rows-1lane-uw256-c8-srcrows1", "rows-2lane-uw254-c8-srcrows1", "plain-up-3x5-c8-srcrows1")],
+    "time_mlp": [(c, m) for c in ("sinu-d32", "sinu-d64") for m in ("tanh_gelu", "sincos_swapped", "half_for_half_minus_1")]
+    + [(c, m) for c in ("learned8-d32", "learned5-d64") for m in ("tanh_gelu", "sincos_swapped")],
+    "film": [(c, m) for c in ("b8+24+64-rows1", "b8+24+64-rows3") for m in ("rows_swapped", "blk_off_single")] + [("b64-rows3", "rows_swapped")],
+    "noisy_condition": [("3x3x9x11-generator-2calls", "same_field_twice")],
+}
+NET_INVISIBLE = {
+    "readout": [("dma-one", "border_mirrored"), ("dma-ident", "border_mirrored")],  # (one input row: its mirror is the clamp; identity: see the test)
+    "film": [("b64-rows3", "blk_off_single")],                                      # the first block's offset is 0
+}
+MUTANTS.update(NET_MUTANTS)
+INVISIBLE.update(NET_INVISIBLE)
+_specs_between, _build_between = specs, build
+
+
+def specs(op):  # noqa: F811 -- both halves behind the one name the tests use
+    return net_specs(op) if op in NET_OPS else _specs_between(op)
+
+
+def build(op, a, dtname):  # noqa: F811
+    return net_build(op, a, dtname) if op in NET_OPS else _build_between(op, a, dtname)
+
+
+OPS = OPS + NET_OPS

@@ -117,3 +117,33 @@ def test_joint_structure_the_epilogues_consume():
         b = streams[(5, 40, l)]
         for lag in (1, 2, 31, 32):
             assert abs(np.corrcoef(a[lag:], b[:-lag])[0, 1]) < 0.02
+
+
+def test_noise_mirror_is_a_standard_normal():
+    """The Box-Muller mirror of the engine's noise field (R.noise_field): mean, variance and fourth moment of 2^20 draws within 4
+    standard errors of a normal's (standard errors 1 / sqrt(n), sqrt(2 / n), sqrt(96 / n)); the fp32 steps of the kernel stay within
+    half the fp32 bound of the float64 statement; no draw is infinite (u = ((w >> 8) + 0.5) / 2^24 is never 0)."""
+    n = 1 << 20
+    z = R.noise_field(20261019, 0, 5, n)
+    assert z.dtype == np.float64 and np.isfinite(z).all()
+    m1, m2, m4 = z.mean(), (z ** 2).mean(), (z ** 4).mean()
+    print(f"noise mirror: mean {m1:.3e}, variance {m2:.5f}, fourth moment {m4:.4f} over {n} draws")
+    assert abs(m1) < 4 / np.sqrt(n) and abs(m2 - 1.0) < 4 * np.sqrt(2.0 / n) and abs(m4 - 3.0) < 4 * np.sqrt(96.0 / n)
+    z32 = R.noise_field(20261019, 0, 5, n, np.float32)
+    err = np.sqrt(((z32.astype(np.float64) - z) ** 2).mean() / (z ** 2).mean())
+    print(f"noise mirror: fp32 steps against float64, rel-RMS {err:.3e}")
+    assert z32.dtype == np.float32 and err <= 0.5e-5
+    for lag in (1, 2, 256):
+        assert abs(np.corrcoef(z[lag:], z[:-lag])[0, 1]) < 4 / np.sqrt(n)
+
+
+def test_noise_mirror_draws_distinct_fields_per_call_and_row():
+    """Distinct (call, row) -> distinct, uncorrelated fields; the same (seed, call, row) -> the same field; the dropout stream of the
+    same (seed, counter, row) is another stream (the salt on seed_hi)."""
+    n = 1 << 16
+    base = R.noise_field(7, 0, 0, n)
+    assert np.array_equal(base, R.noise_field(7, 0, 0, n))
+    for other in (R.noise_field(7, 1, 0, n), R.noise_field(7, 0, 1, n), R.noise_field(8, 0, 0, n), R.noise_field(7 + (1 << 32), 0, 0, n)):
+        assert not np.array_equal(base, other)
+        assert abs(np.corrcoef(base, other)[0, 1]) < 4 / np.sqrt(n)
+    assert tuple(int(v) for v in R.row_key(7 | (R.NOISE_SALT << 32), 0, 0)) != tuple(int(v) for v in R.row_key(7, 0, 0))
