@@ -13,22 +13,30 @@ LIB_PATH_F16 = os.environ.get("DYF_LIB_F16") or os.path.join(_HERE, "lib", "libd
 DTYPES = {"bf16": 0, "bfloat16": 0, "fp16": 1, "float16": 1, "half": 1}
 # fp32 sampling (dyf_set_sample_precision(32)) is a mode of an engine, not a build of the library: such engines load the bf16 build
 FP32_NAMES = ("fp32", "float32", "32")
+# bf16x3 sampling (dyf_set_sample_precision(48)): the fp32 forward with (hi, lo) bf16 conv operands -- likewise a mode of a bf16-build engine
+BF16X3_NAMES = ("bf16x3", "48")
 
 
 def canonical_dtype(dtype) -> str:
-    """"bf16" | "fp16" | "fp32" for every accepted spelling; ValueError for anything else."""
+    """"bf16" | "fp16" | "fp32" | "bf16x3" for every accepted spelling; ValueError for anything else."""
     key = str(dtype).lower()
     if key in FP32_NAMES:
         return "fp32"
+    if key in BF16X3_NAMES:
+        return "bf16x3"
     if key not in DTYPES:
-        raise ValueError(f"dtype {dtype!r}: expected one of {sorted(DTYPES) + list(FP32_NAMES)}")
+        raise ValueError(f"dtype {dtype!r}: expected one of {sorted(DTYPES) + list(FP32_NAMES) + list(BF16X3_NAMES)}")
     return "fp16" if DTYPES[key] else "bf16"
 
 
 def storage_dtype(dtype) -> str:
-    """The 16-bit build an engine of `dtype` is served by ("fp32" engines: the default bf16 build)."""
+    """The 16-bit build an engine of `dtype` is served by ("fp32" and "bf16x3" engines: the default bf16 build)."""
     d = canonical_dtype(dtype)
-    return "bf16" if d == "fp32" else d
+    return "bf16" if d in ("fp32", "bf16x3") else d
+
+
+# dyf_set_sample_precision: bits an engine of a canonical dtype is switched to at creation (absent: it stays at 16)
+SAMPLE_PRECISION_BITS = {"fp32": 32, "bf16x3": 48}
 
 
 # dyf_set_attention_dropout: how a 16-bit engine draws the dropout of unet.Unet's Attention probabilities (include/dyffusion_hip.h)
@@ -45,6 +53,7 @@ def attention_dropout_mode(mode) -> int:
 
 DYF_ABI_VERSION = 9
 DYF_TRAIN_PRECISION_BF16X3 = 48  # dyf_train_set_precision: bf16x3 (hi/lo bf16 operand pairs, three MFMAs per product)
+DYF_SAMPLE_PRECISION_BF16X3 = 48  # dyf_set_sample_precision: the fp32 sampling forward with those conv operands
 DYF_OK, DYF_ERR_INVALID_ARGUMENT, DYF_ERR_UNSUPPORTED, DYF_ERR_HIP, DYF_ERR_STATE = range(5)
 NET_FORECASTER, NET_INTERPOLATOR = 0, 1
 ARCH_UNET_SIMPLE, ARCH_UNET_RESNET = 0, 1
@@ -110,6 +119,7 @@ TRAIN_OPS = {"conv": 0, "gn_act": 1, "layernorm": 2, "linattn": 3, "attention": 
 TOP_WS, TOP_BIAS, TOP_PRE, TOP_FILM, TOP_SAME = 1, 2, 4, 8, 16
 TOP_RUNNING, TOP_MASK, TOP_LEAKY, TOP_RELU, TOP_NEAREST, TOP_GRAD_IN = 32, 64, 128, 256, 512, 1024
 TOP_ACT_GELU, TOP_RESIDUAL = 2048, 4096
+TOP_SAMPLE = 8192  # conv: the forward alone, launched as a sampling forward launches it
 
 
 class SampleOp(C.Structure):
@@ -248,7 +258,7 @@ _LIBS = {}
 
 
 def lib(dtype: str = "bf16") -> C.CDLL:
-    """The C-ABI library for `dtype`: "bf16" (and "fp32") -> libdyffusion_hip.so, "fp16" -> libdyffusion_hip_f16.so."""
+    """The C-ABI library for `dtype`: "bf16" (and "fp32", "bf16x3") -> libdyffusion_hip.so, "fp16" -> libdyffusion_hip_f16.so."""
     code = DTYPES[storage_dtype(dtype)]
     if code not in _LIBS:
         l = load_library(LIB_PATH_F16 if code else LIB_PATH)

@@ -986,8 +986,9 @@ dyf_status dyf_debug_gn_fuse(dyf_engine* e, uint32_t timeout_ticks, int32_t forc
 
 dyf_status dyf_set_sample_precision(dyf_engine* e, int32_t bits) {
     if (!e) return DYF_ERR_INVALID_ARGUMENT;
-    if (bits != 16 && bits != 32) return fail(e, DYF_ERR_INVALID_ARGUMENT, "dyf_set_sample_precision: bits must be 16 or 32");
-    if (bits == 32) {
+    if (bits != 16 && bits != 32 && bits != DYF_SAMPLE_PRECISION_BF16X3)
+        return fail(e, DYF_ERR_INVALID_ARGUMENT, "dyf_set_sample_precision: bits must be 16, 32 or 48 (DYF_SAMPLE_PRECISION_BF16X3)");
+    if (bits != 16) {  // 32 and 48 share the fp32 walk and its arena
         HIP_TRY(e, hipSetDevice(e->cfg.device));
         dyf_status s = f32_prepare(e);
         if (s != DYF_OK) return s;
@@ -1031,7 +1032,7 @@ dyf_status dyf_net_forward(dyf_engine* e, int32_t which, const float* inputs_dev
         if (gs != DYF_OK) return gs;
     }
     hipStream_t st = (hipStream_t)stream;
-    const bool f32 = e->sample_precision == 32;  // the fp32 forwards of the two U-Nets run the time MLP themselves: no folded coefficient rows
+    const bool f32 = sample_f32_walk(e);  // the fp32 forwards of the two U-Nets run the time MLP themselves: no folded coefficient rows
     if (!f32 || n.sc) {  // (SimpleConvNet's fp32 forward takes its FiLM from the coefficient rows: they are fp32)
         dyf_status s = compute_coefs(e, n, time_dev, nb, e->ws.coef_a, e->ws.coef_c, st);
         if (s != DYF_OK) return s;
@@ -1231,7 +1232,7 @@ dyf_status run_plan(dyf_engine* e, int nb, const uint8_t* const* masks, const fl
     const int f_mode = ph.hdr.forecaster_dropout ? (inject ? 2 : 1) : 0;
     // the forward seam: the 16-bit forward of this library, or the fp32 one (dyf_set_sample_precision).  Everything else in this walk --
     // sampler state, cold-sampling update, noisy condition, forecast stack, log -- is fp32 either way.
-    const bool f32 = e->sample_precision == 32;
+    const bool f32 = sample_f32_walk(e);  // 32, and 48 (bf16x3 conv operands on the same walk)
     auto* const forward = f32 ? f32_net_forward : net_forward;
 
     auto interp = [&](float t, const float* x_last, float* out) -> dyf_status {
@@ -1413,7 +1414,7 @@ static dyf_status sample_into_stack(dyf_engine* e, const float* initial_dev, con
     const int H = e->cfg.height, W = e->cfg.width;
     e->last_groups = 0;
     const int G = (int)e->groups.size();
-    if (G > 1 && e->sample_precision != 32 && !e->log_on && masks_dev == nullptr && noise_dev == nullptr && nb >= 2 * e->group_min_rows) {
+    if (G > 1 && !sample_f32_walk(e) && !e->log_on && masks_dev == nullptr && noise_dev == nullptr && nb >= 2 * e->group_min_rows) {
         // rows split over the groups: per = ceil(nb / g) rows each (the last one takes the remainder), every share on its own stream
         // Three concurrent groups + the caller's stream use all four hardware queues a HIP process gets: ONE more stream with work
         // (or a live graph) makes two groups share a queue and the 300-row OISST rollout drops from ~3 850 to ~3 100 fields/s, below

@@ -130,7 +130,8 @@ struct dyf_engine {
     int stack_slots = 0;
     std::map<int, dyf::GraphEntry> graphs;  // by (batch size, sampling precision, attention-dropout mode): graph_key
     // fp32 sampling (dyf_set_sample_precision): 16 = the library's 16-bit path, 32 = the fp32 forward of train.hip on a bump arena that
-    // the first switch to 32 allocates (max_batch rows of the larger network) and dyf_engine_destroy frees; rewound per forward
+    // the first switch to 32 allocates (max_batch rows of the larger network) and dyf_engine_destroy frees; rewound per forward;
+    // 48 (DYF_SAMPLE_PRECISION_BF16X3) = that forward with bf16x3 conv operands (sample_f32_walk)
     int sample_precision = 16;
     // dyf_set_attention_dropout: 0 = the quad form of the 16-bit Attention probability dropout, 1 = the exact form (the fp32 path's keep
     // bits, common.h DropSpec::attn_exact); row-group children carry their parent's value
@@ -388,8 +389,11 @@ inline void* f32_arena_take(dyf_engine* e, size_t bytes) {
     e->f32_used += b;
     return p;
 }
+// the sampling precisions that run the fp32 layer walk (f32_net_forward): 32, and 48 = the same walk with bf16x3 conv operands
+inline bool sample_f32_walk(const dyf_engine* e) { return e->sample_precision == 32 || e->sample_precision == 48; }
 inline int graph_key(const dyf_engine* e, int nb) {
-    return nb | (e->sample_precision == 32 ? 1 << 30 : 0) | (e->attn_dropout_exact ? 1 << 29 : 0);
+    // (bits 30 / 28: the sampling precisions 32 / 48 -- a graph captured under 16, 32 or 48 never replays under another)
+    return nb | (e->sample_precision == 32 ? 1 << 30 : 0) | (e->sample_precision == 48 ? 1 << 28 : 0) | (e->attn_dropout_exact ? 1 << 29 : 0);
 }
 }  // namespace dyf
 

@@ -1668,7 +1668,10 @@ dyf_status f32_net_forward(dyf_engine* e, int which, const Source* srcs, int nsr
         e->f32_used = 0;
         return sc_f32_forward(e, which, srcs, nsrc, nb, o, out_dev, st);
     }
-    const TrainPrecisionScope precision(32);  // fp32 operands whatever dyf_train_set_precision says
+    // the operands of dyf_set_sample_precision -- fp32, or bf16x3 (48) in the convs the 16-bit dispatch takes -- whatever
+    // dyf_train_set_precision says
+    const TrainPrecisionScope precision(e->sample_precision == DYF_SAMPLE_PRECISION_BF16X3 ? DYF_TRAIN_PRECISION_BF16X3 : 32);
+    const SampleForwardScope sampling(1);
     const TrainDetScope det(0);               // and the default kernel forms whatever dyf_train_set_deterministic says
     struct Active {  // splitk_ws() hands out the arena's head while this forward is being launched
         dyf_engine* e;

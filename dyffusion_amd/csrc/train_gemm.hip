@@ -506,6 +506,7 @@ void det_reduce(const double* ws, int splits, long long stride, long long n, dou
 // train_halo16.hip) -- chosen per engine by dyf_train_set_precision(16) (the reference's `trainer.precision=16`), or, for engines
 // that did not say (0), by the tests' kernel-form switch DYF_TRAIN_OPERANDS=bf16 | 16 (dyf_debug_set_form; read per call).  Otherwise fp32.
 thread_local int g_train_precision = 0;
+thread_local int g_sample_forward = 0;
 bool train_operands16() {
     if (g_train_precision == 16) return true;
     if (g_train_precision != 0) return false;  // 32, and 48 (bf16x3: train_operands_split)

@@ -25,8 +25,10 @@
 //                             t_pack_w16<true> writes the weight images in one launch
 //   weight gradient           three passes: dz_lo x_hi, dz_hi x_lo, dz_hi x_hi, each added onto dw the way the 16-bit form adds its one
 //                             term (atomics; deterministic mode: the owner's += or slabs + det_reduce per pass -- no atomics)
-// The fp32 activations are read twice (forward / data gradient) or three times (weight gradient) instead of once; a fused form (both
-// images of halo and weights in LDS, three MFMAs per step) needs 156 KB of the 160 KB for the forward kernel and is the follow-up.
+// The fp32 activations are read twice (forward / data gradient) or three times (weight gradient) instead of once.  The forward of a
+// SAMPLING forward (dyf_set_sample_precision(48)) takes the fused form instead -- t_halo3x3_16<.., NW = 2, FUSE>: both images of the halo
+// in LDS, one launch, one read of the activations, no read-modify-write of C; the training step keeps the PASS form (moving it over is
+// the follow-up).
 #include "train_internal.h"
 
 #include <cstdlib>
@@ -94,7 +96,14 @@ __device__ __forceinline__ t16_t cvt_t16(float v) {
 
 // ALO: the halo is staged as its lo image; ACC: the epilogue adds onto C (no bias) instead of assigning; NW = 2: Wb is [n][18][k], the
 // lo and the hi image of the weights, and a chunk runs 18 steps (nine taps against each) on ONE staged halo -- the bf16x3 passes
-template <int BN, bool ALO = false, bool ACC = false, int NW = 1>
+// FUSE (with NW = 2, the sampling forward of dyf_set_sample_precision(48)): all three bf16x3 terms in ONE launch.  halo_store writes the
+// hi AND the lo image of the staged float4s (the lo image XS_BYTES behind the hi one, same swizzle); the nine lo-weight steps meet A_hi,
+// the nine hi-weight steps meet A_lo and A_hi -- two MFMAs on one B fragment -- and the one assigning epilogue carries the bias.
+// ONE halo buffer (2 images + ring = 79 872 B, two workgroups per CU as the other forms): the next halo is written behind one more
+// barrier at the chunk's end, when every wave has read the last tap.  Chosen by measurement over two halo buffers (126 976 B, one
+// workgroup per CU, the hand-over of the 16-bit form): the NS rollout of 8 rows (h = 16, 60 forwards) takes 0.1720 s with one buffer,
+// 0.1836 s with two and 0.1957 s on the two-launch PASS form (medians of five, one call).
+template <int BN, bool ALO = false, bool ACC = false, int NW = 1, bool FUSE = false>
 __global__ __launch_bounds__(256, BN == 64 ? 2 : 1) void t_halo3x3_16(int h, int w, int CK, int NC, const float* __restrict__ A,
                                                                       const t16_t* __restrict__ Wb, const float* __restrict__ bias,
                                                                       float* __restrict__ C, int tiles_x, int tiles_per_img,
@@ -103,8 +112,10 @@ __global__ __launch_bounds__(256, BN == 64 ? 2 : 1) void t_halo3x3_16(int h, int
     constexpr int NT = BN / 32, RING = 4, BI = BN / 32;  // BI: DMA instructions per wave and step (BN rows x 128 B over 4 waves)
     constexpr int XS_BYTES = HP * 128 + 512, B_BYTES = BN * 128;
     constexpr int HV = (HP * 16 + 255) / 256;  // 12 halo float4 per thread (the last one: wave 0 only)
-    extern __shared__ __attribute__((aligned(16))) char smem[];  // 2 halo buffers + the weight ring
-    char* const Bring = smem + 2 * XS_BYTES;
+    static_assert(!FUSE || (NW == 2 && !ALO && !ACC), "the fused form: both weight images, hi and lo halo, assigning epilogue");
+    constexpr int BUF_BYTES = (FUSE ? 2 : 1) * XS_BYTES, NBUF = FUSE ? 1 : 2;  // a halo buffer: one image, FUSE: hi then lo
+    extern __shared__ __attribute__((aligned(16))) char smem[];  // the halo buffers + the weight ring
+    char* const Bring = smem + NBUF * BUF_BYTES;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l31 = lane & 31, hi = lane >> 5;
     // XCD-aware order (workgroup id % 8 = XCD, each with its own L2): the column blocks of one tile range follow one another on the
@@ -151,15 +162,22 @@ __global__ __launch_bounds__(256, BN == 64 ? 2 : 1) void t_halo3x3_16(int h, int
         }
     };
     auto halo_store = [&](int buf) {
-        char* Xs = smem + buf * XS_BYTES;
+        char* Xs = smem + buf * BUF_BYTES;
 #pragma unroll
         for (int j = 0; j < HV; ++j) {
             const int idx = tid + 256 * j;
             const int hp = idx >> 4, q = idx & 15;
-            if (idx < HP * 16)
-                *(uint2*)(Xs + hp * 128 + (((q >> 1) ^ hkey(hp)) << 4) + (q & 1) * 8) =
-                    ALO ? make_uint2(cvt_t16x2<true>(hv[j].x, hv[j].y), cvt_t16x2<true>(hv[j].z, hv[j].w))
-                        : make_uint2(pack_t16x2(hv[j].x, hv[j].y), pack_t16x2(hv[j].z, hv[j].w));
+            if (idx < HP * 16) {
+                char* dst = Xs + hp * 128 + (((q >> 1) ^ hkey(hp)) << 4) + (q & 1) * 8;
+                if constexpr (FUSE) {  // both images from the same registers
+                    const uint32_t h0 = pack_t16x2(hv[j].x, hv[j].y), h1 = pack_t16x2(hv[j].z, hv[j].w);
+                    *(uint2*)dst = make_uint2(h0, h1);
+                    *(uint2*)(dst + XS_BYTES) = make_uint2(pack_t16x2_lo(hv[j].x, hv[j].y, h0), pack_t16x2_lo(hv[j].z, hv[j].w, h1));
+                } else {
+                    *(uint2*)dst = ALO ? make_uint2(cvt_t16x2<true>(hv[j].x, hv[j].y), cvt_t16x2<true>(hv[j].z, hv[j].w))
+                                       : make_uint2(pack_t16x2(hv[j].x, hv[j].y), pack_t16x2(hv[j].z, hv[j].w));
+                }
+            }
         }
     };
 
@@ -181,7 +199,7 @@ __global__ __launch_bounds__(256, BN == 64 ? 2 : 1) void t_halo3x3_16(int h, int
         for (int chunk = 0; chunk < nchunks; ++chunk) {
             const bool last = chunk + 1 == nchunks;
             const bool has_next = !last || tile + 1 < t_end;
-            const char* Xs = smem + xbuf * XS_BYTES;
+            const char* Xs = smem + xbuf * BUF_BYTES;
 #pragma unroll
             for (int wtap = 0; wtap < 9 * NW; ++wtap) {
                 const int tap = wtap % 9;  // (NW = 2: the spatial tap of weight-stream step wtap)
@@ -199,18 +217,34 @@ __global__ __launch_bounds__(256, BN == 64 ? 2 : 1) void t_halo3x3_16(int h, int
                 for (int ks = 0; ks < 4; ++ks) {
                     const int c16 = ks * 2 + hi;
                     const t16x8_t a = *(const t16x8_t*)(ap + ((c16 ^ akey) << 4));
+                    t16x8_t a_lo = a;
+                    if constexpr (FUSE)
+                        if (wtap >= 9) a_lo = *(const t16x8_t*)(ap + XS_BYTES + ((c16 ^ akey) << 4));  // (wtap: unrolled, a constant)
 #pragma unroll
                     for (int t = 0; t < NT; ++t) {
                         const int n = t * 32 + l31;
                         const t16x8_t b = *(const t16x8_t*)(bp + n * 128 + ((c16 ^ ((n >> 1) & 7)) << 4));
+                        if constexpr (FUSE)
+                            if (wtap >= 9) acc[t] = T16_MFMA_32x32x16(a_lo, b, acc[t], 0, 0, 0);  // A_lo W_hi: the hi-weight steps
                         acc[t] = T16_MFMA_32x32x16(a, b, acc[t], 0, 0, 0);
                     }
                 }
                 if (++slot == RING) slot = 0;
             }
-            // the other halo buffer was last read a whole chunk (nine barriers or more) ago
-            if (has_next) halo_store(xbuf ^ 1);
-            xbuf ^= 1;
+            if constexpr (FUSE) {
+                // one halo buffer: every wave must have read the chunk's last tap before the next halo overwrites it (the fragments
+                // are in registers once lgkmcnt is 0); the next step's barrier publishes the new images
+                if (has_next) {
+                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                    __builtin_amdgcn_s_barrier();
+                    __builtin_amdgcn_sched_barrier(0);
+                    halo_store(0);
+                }
+            } else {
+                // the other halo buffer was last read a whole chunk (nine barriers or more) ago
+                if (has_next) halo_store(xbuf ^ 1);
+                xbuf ^= 1;
+            }
         }
         // D[i][j]: lane j = l31 holds output channel n0 + 32 t + l31, register r the pixel i = 8 (r >> 2) + 4 hi + (r & 3) of the block
         const int img = tile / tiles_per_img, t_in = tile - img * tiles_per_img;
@@ -367,6 +401,13 @@ bool halo16_enabled() {
     return dyf_form_int("DYF_TRAIN_HALO16", 1) != 0;  // =0: the tap-by-tap implicit GEMM of train_gemm.hip for these layers too (A/B)
 }
 
+// the fused bf16x3 forward (FUSE above): taken only by a forward that a sampling forward launches (SampleForwardScope) -- the recorded
+// training forward and every data gradient keep the PASS form.  DYF_SAMPLE_HALO_FUSED=0 sends sampling to the PASS form too (A/B, and a
+// second implementation for the tests).
+bool halo16_fused_form(int mode) {
+    return mode == 0 && dyf::g_sample_forward && dyf_form_int("DYF_SAMPLE_HALO_FUSED", 1) != 0;
+}
+
 }  // namespace
 
 namespace dyf {
@@ -387,7 +428,9 @@ bool thalo_conv3x3(const TConv& g, int mode, const float* A, const float* W, con
     constexpr int bn = 64;
     if (tiles * (NC / bn) < 192 || tiles > 0x7fffffffll) return false;  // small planes: the split-K forms of train_gemm.hip  // small planes: the split-K forms of train_gemm.hip
     t16_t* wb = (t16_t*)ws;
-    if (sp) dyf_form_note(mode ? "t_halo3x3_16x3:dgrad" : "t_halo3x3_16x3:forward", g.n);
+    const bool fuse = sp && halo16_fused_form(mode);
+    if (fuse) dyf_form_note("t_halo3x3_16x3f:forward", g.n);
+    else if (sp) dyf_form_note(mode ? "t_halo3x3_16x3:dgrad" : "t_halo3x3_16x3:forward", g.n);
     else dyf_form_note(mode ? "t_halo3x3_16:dgrad" : "t_halo3x3_16:forward", g.n);
     if (sp) hipLaunchKernelGGL(t_pack_w16<true>, dim3((unsigned)((welems + 255) / 256)), dim3(256), 0, st, W, g.cin, g.cout, mode, wb);
     else hipLaunchKernelGGL(t_pack_w16<false>, dim3((unsigned)((welems + 255) / 256)), dim3(256), 0, st, W, g.cin, g.cout, mode, wb);
@@ -399,6 +442,13 @@ bool thalo_conv3x3(const TConv& g, int mode, const float* A, const float* W, con
     const int per = (int)std::max<long long>(1, std::min<long long>(16, tiles * nblocks / htarget));
     const long long wgs = ((tiles + per - 1) / per + 7) / 8 * 8 * nblocks;  // whole groups of 8 tile ranges (XCD-aware order in the kernel)
     constexpr int XS = HP * 128 + 512;
+    if (fuse) {  // one launch on the [lo | hi] weight stream: C is assigned, whatever it held
+        constexpr int lds = 2 * XS + 4 * 64 * 128;
+        if (!train_raise_dynamic_lds<t_halo3x3_16<64, false, false, 2, true>>(lds)) return false;
+        hipLaunchKernelGGL((t_halo3x3_16<64, false, false, 2, true>), dim3((unsigned)wgs), dim3(256), lds, st, g.h, g.w, CK, NC, A, wb + welems, bias, C,
+                           tiles_x, tiles_per_img, (int)tiles, per, nblocks);
+        return true;
+    }
     if (sp) {  // A_lo W_hi assigns (with the bias); A_hi [W_lo | W_hi] accumulates, both weight images against one staged halo
         constexpr int lds = 2 * XS + 4 * 64 * 128;
         if (!train_raise_dynamic_lds<t_halo3x3_16<64, true, false>>(lds) || !train_raise_dynamic_lds<t_halo3x3_16<64, false, true, 2>>(lds)) return false;

@@ -142,6 +142,15 @@ struct TrainPrecisionScope {
     explicit TrainPrecisionScope(int p) : prev(g_train_precision) { g_train_precision = p; }
     ~TrainPrecisionScope() { g_train_precision = prev; }
 };
+// "The convs of THIS thread are launched by a sampling forward" (f32_net_forward under dyf_set_sample_precision(48), and the op seam's
+// DYF_TOP_SAMPLE): the dispatchers have no engine pointer, so forms that only sampling takes read this -- the fused bf16x3 halo forward
+// of train_halo16.hip.  Recorded (training) forwards and every backward run with it clear and keep their forms bit for bit.
+extern thread_local int g_sample_forward;
+struct SampleForwardScope {
+    int prev;
+    explicit SampleForwardScope(int on) : prev(g_sample_forward) { g_sample_forward = on; }
+    ~SampleForwardScope() { g_sample_forward = prev; }
+};
 
 // Deterministic training mode for the calls of THIS thread: set by the training entry points from the engine's
 // dyf_train_set_deterministic (the reference's trainer.deterministic).  On: no launcher may merge a floating-point sum with atomics --

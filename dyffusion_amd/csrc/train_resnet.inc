@@ -2073,7 +2073,9 @@ dyf_status f32_op_train(dyf_engine* e, const dyf_train_op* dp, const float* cons
     const bool has_p = d.op == DYF_TOP_GN_ACT || d.op == DYF_TOP_NORM_ACT || d.op == DYF_TOP_LAYERNORM || d.op == DYF_TOP_ATTENTION || d.op == DYF_TOP_DROPOUT ||
                        d.op == DYF_TOP_ATTENTION_STREAM;
     const bool has_c2 = d.op == DYF_TOP_CONV || d.op == DYF_TOP_LINEAR || d.op == DYF_TOP_CAT || d.op == DYF_TOP_CONVT;
-    const int flags_ok = d.op == DYF_TOP_CONV ? (DYF_TOP_WS | DYF_TOP_BIAS) : d.op == DYF_TOP_GN_ACT ? DYF_TOP_FILM : d.op == DYF_TOP_LINEAR ? DYF_TOP_PRE
+    if ((d.flags & DYF_TOP_SAMPLE) && d.op != DYF_TOP_CONV) return refuse(DYF_ERR_UNSUPPORTED, "DYF_TOP_SAMPLE: conv only");
+    const bool sample = (d.flags & DYF_TOP_SAMPLE) != 0;  // the forward alone, launched the way a sampling forward launches it
+    const int flags_ok = d.op == DYF_TOP_CONV ? (DYF_TOP_WS | DYF_TOP_BIAS | DYF_TOP_SAMPLE) : d.op == DYF_TOP_GN_ACT ? DYF_TOP_FILM : d.op == DYF_TOP_LINEAR ? DYF_TOP_PRE
                          : d.op == DYF_TOP_ADD ? DYF_TOP_SAME
                          : d.op == DYF_TOP_NORM_ACT ? (DYF_TOP_FILM | DYF_TOP_RUNNING | DYF_TOP_MASK | DYF_TOP_LEAKY | DYF_TOP_RELU | DYF_TOP_ACT_GELU | DYF_TOP_RESIDUAL)
                          : d.op == DYF_TOP_UP2_BILINEAR ? DYF_TOP_GRAD_IN : d.op == DYF_TOP_RESIZE ? DYF_TOP_NEAREST : 0;
@@ -2143,8 +2145,11 @@ dyf_status f32_op_train(dyf_engine* e, const dyf_train_op* dp, const float* cons
 
     if (!e->train) e->train = new TrainState();
     e->train->stream = st;
-    const TrainPrecisionScope precision(e->train_precision);
-    const TrainDetScope det(e->train_deterministic);
+    // DYF_TOP_SAMPLE: the operands of dyf_set_sample_precision (16 has no fp32 walk: fp32 operands), the default kernel forms and the
+    // sampling-forward scope, as f32_net_forward sets them
+    const TrainPrecisionScope precision(!sample ? e->train_precision : e->sample_precision == DYF_SAMPLE_PRECISION_BF16X3 ? DYF_TRAIN_PRECISION_BF16X3 : 32);
+    const TrainDetScope det(sample ? 0 : e->train_deterministic);
+    const SampleForwardScope sampling(sample ? 1 : 0);
     dyf_net_config c = e->net[0].cfg;
     c.groups = d.groups;
     TrainNet W;
@@ -2231,7 +2236,7 @@ dyf_status f32_op_train(dyf_engine* e, const dyf_train_op* dp, const float* cons
     if (y == in[0]) {  // a resize to the same size is the identity: so is its adjoint
         X.grad(y);
         OPK(hipMemcpyAsync(y->g, dout, y->n * sizeof(float), hipMemcpyDeviceToDevice, st));
-    } else if (!mask) {
+    } else if (!mask && !sample) {
         float* gy = X.grad(y);
         if (d.flags & DYF_TOP_GRAD_IN) {  // the second source's gradient starts from the caller's
             float* g1 = X.grad(in[1]);
@@ -2243,12 +2248,13 @@ dyf_status f32_op_train(dyf_engine* e, const dyf_train_op* dp, const float* cons
         if (r != DYF_OK) return done(refuse(r, "backward failed"));
         OPK(hipGetLastError());
     }
-    for (size_t i = 0; i < in_n.size() && dinputs && !mask; ++i) {
+    for (size_t i = 0; i < in_n.size() && dinputs && !mask && !sample; ++i) {
         if (!dinputs[i] || !in[i]) continue;
         if (in[i]->g) OPK(hipMemcpyAsync(dinputs[i], in[i]->g, in_n[i] * sizeof(float), hipMemcpyDeviceToDevice, st));
         else OPK(hipMemsetAsync(dinputs[i], 0, in_n[i] * sizeof(float), st));
     }
     OPK(hipStreamSynchronize(st));
+    if (sample) return done(DYF_OK);  // no adjoint ran: no gradient is written
     float* stage = X.tbuf(ps.empty() ? 1 : W.P.at(ps[0].name).n);  // (a conv weight is its op's first parameter)
     if (X.err != DYF_OK) return done(refuse(X.err, "allocation failed"));
     for (size_t i = 0; i < ps.size(); ++i) {

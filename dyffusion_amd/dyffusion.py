@@ -104,6 +104,7 @@ class DYffusion(nn.Module):
         # dtype: 16-bit storage / MFMA operand format of the engine: "bf16" or "fp16"; None = the forecaster class's default
         # (engine.default_dtype_for: bf16 for unet_simple -- BASELINE configs[1] --, fp16 for the ResNet-UNet -- configs[2], [4]);
         # "fp32" / "float32" / "32": reference-precision sampling (HipEngine.set_sample_precision(32); arch unet_simple).
+        # "bf16x3" / "48": the same at reference precision on the bf16 matrix cores (set_sample_precision(48): hi / lo bf16 conv operands).
         # An unknown string is a ValueError here, not a KeyError at the first sample.
         dtype = L.canonical_dtype(dtype or default_dtype_for(model))
         self._engine_opts = dict(max_batch=max_batch, use_graph=use_graph, enable_mfma=enable_mfma, dtype=dtype,
@@ -313,6 +314,7 @@ class DYffusion(nn.Module):
         ni = len(refine) + sum(1 for st in steps if st["i_next"] is not None) + \
             sum(1 for st in steps if cold and st["i_cur"] is not None and not (st["is_last"] and not hp.use_cold_sampling_for_last_step))
         resnet = any(eng.cfg.net[k].arch == L.ARCH_UNET_RESNET for k in (L.NET_FORECASTER, L.NET_INTERPOLATOR))
+        # (eng.dtype "fp32" and "bf16x3" are reference-precision modes of the bf16 build: never refused)
         if eng.dtype == "bf16" and resnet and nf + ni > BF16_RESNET_MAX_FORWARDS \
                 and not (self.allow_bf16_long_rollout or os.environ.get("DYF_ALLOW_BF16_LONG_ROLLOUT") == "1"):
             raise NotImplementedError(

@@ -60,8 +60,9 @@ def default_dtype_for(net) -> str:
     SimpleConvNet backbones (BASELINE configs[1]: "bf16"), "fp16" for the ResNet-UNet `unet.Unet` (OISST, 512^2: ~60 16-bit
     roundings per forward and 93 chained forwards per rollout -- bf16's 8 mantissa bits give 4e-2 .. 5e-2 per field over the
     OISST rollout, fp16's 11 bits 6e-3 at the same MFMA rate and the same bytes).  A network class states
-    its default as `default_engine_dtype`; `net.engine_dtype = "bf16" | "fp16" | "fp32"` or `DYffusion(dtype=...)` override it
-    ("fp32": reference-precision sampling, dyf_set_sample_precision(32); arch unet_simple)."""
+    its default as `default_engine_dtype`; `net.engine_dtype = "bf16" | "fp16" | "fp32" | "bf16x3"` or `DYffusion(dtype=...)` override it
+    ("fp32": reference-precision sampling, dyf_set_sample_precision(32); "bf16x3": the same forward with (hi, lo) bf16 conv operands on
+    the bf16 matrix cores, dyf_set_sample_precision(48))."""
     return getattr(net, "engine_dtype", None) or getattr(net, "default_engine_dtype", "bf16")
 
 
@@ -116,6 +117,7 @@ class HipEngine:
         if not torch.cuda.is_available():
             raise EngineError("no GPU visible: the DYffusion HIP engine needs an MI355X (gfx950); there is no CPU fallback")
         # "fp32" / "float32" / "32": the default (bf16) build with dyf_set_sample_precision(32) -- every sampling forward in fp32
+        # "bf16x3" / "48": the same with dyf_set_sample_precision(48) -- that forward with (hi, lo) bf16 conv operands on the bf16 matrix cores
         self.dtype = L.canonical_dtype(dtype)
         storage = L.storage_dtype(dtype)
         self._lib = L.lib(storage)
@@ -130,9 +132,9 @@ class HipEngine:
         if st != L.DYF_OK:
             _raise(st, self._lib.dyf_last_error(None).decode())
         self._h = h
-        if self.dtype == "fp32":
+        if self.dtype in L.SAMPLE_PRECISION_BITS:
             try:
-                self.set_sample_precision(32)
+                self.set_sample_precision(L.SAMPLE_PRECISION_BITS[self.dtype])
             except Exception:
                 self.close()
                 raise
@@ -185,8 +187,9 @@ class HipEngine:
         self._check(self._lib.dyf_debug_gn_fuse(self._h, int(timeout_ticks), int(force_timeout)))
 
     def set_sample_precision(self, bits: int) -> None:
-        """dyf_set_sample_precision: 16 = the library's 16-bit path, 32 = fp32 forwards for net_forward / sample / sample_gather
-        (the first switch to 32 allocates the engine's fp32 arena; ValueError for any other value)."""
+        """dyf_set_sample_precision: 16 = the library's 16-bit path, 32 = fp32 forwards for net_forward / sample / sample_gather,
+        48 = those forwards with bf16x3 conv operands (hi / lo bf16 pairs, three MFMAs per product: reference precision on the bf16
+        matrix cores).  The first switch to 32 or 48 allocates the engine's fp32 arena; ValueError for any other value."""
         self._check(self._lib.dyf_set_sample_precision(self._h, int(bits)))
 
     @property
@@ -830,7 +833,7 @@ class HipEngine:
     def op_train(self, op: str, inputs, params=(), dout: Optional[torch.Tensor] = None, grads_in=None, *, k: int = 0, stride: int = 0,
                  pad: int = 0, groups: int = 0, p: float = 0.0, ws: bool = False, pre: bool = False, act: str = "silu", running: bool = False,
                  mask: Optional[torch.Tensor] = None, size=None, nearest: bool = False, skip_grad: Optional[torch.Tensor] = None,
-                 residual: Optional[torch.Tensor] = None) -> Dict[str, object]:
+                 residual: Optional[torch.Tensor] = None, sample: bool = False) -> Dict[str, object]:
         """Test seam (dyf_op_train_f32): ONE recorded op of the training step (either backbone) and its adjoint, through the training
         step's own launch code.  `inputs`: fp32 tensors on the device, activations NHWC (nb, h, w, c) -- rows (nb, c) for "linear", times (nb,)
         for "learned_sinu"; "add" with one input is add(a, a).  `params`: fp32 tensors in PyTorch layouts, in the header's order (conv:
@@ -846,7 +849,11 @@ class HipEngine:
         (ConvTranspose2d(c, c2, 4, 2, 1): weight (c, c2, 4, 4), bias).
         "attention_stream": "attention" in the streaming form a recorded forward takes past 4096 tokens, at any h * w <= 32 767.
         SimpleConvNet's block: "norm_act" with `act` "gelu" and `residual` (nb, h, w, c), added behind activation and dropout in the same
-        launch; its gradient is the last entry of "dinputs"."""
+        launch; its gradient is the last entry of "dinputs".
+        `sample` ("conv" only): the forward alone, launched the way a sampling forward launches it -- operands from `sample_precision`,
+        the forms only sampling takes; "dinputs" and "dparams" are None."""
+        if sample and op != "conv":
+            raise NotImplementedError("sample=True: conv only")
         ins = [_f32c(t, "input") for t in inputs]
         n_plain = len(ins)  # inputs without the residual, which follows them in the pointer array
         if residual is not None:
@@ -868,7 +875,7 @@ class HipEngine:
             c2 = ps[0].shape[0]
             if tuple(ps[0].shape) != (c2, c, k, k):
                 raise ValueError(f"conv weight must be (c2, {c}, {k}, {k}), got {tuple(ps[0].shape)}")
-            flags = (L.TOP_WS if ws else 0) | (L.TOP_BIAS if len(ps) > 1 else 0)
+            flags = (L.TOP_WS if ws else 0) | (L.TOP_BIAS if len(ps) > 1 else 0) | (L.TOP_SAMPLE if sample else 0)
             out_shape = (nb, (h + 2 * pad - k) // stride + 1, (w + 2 * pad - k) // stride + 1, c2)
         elif op == "gn_act":
             flags = L.TOP_FILM if len(ins) > 1 else 0
@@ -953,6 +960,8 @@ class HipEngine:
             dins = [None]  # a time value has no gradient
         if mask is not None:
             dins = None    # forward only
+        if sample:
+            dins = gs = None
         return {"y": y, "dinputs": dins, "dparams": gs}
 
     def op_sample(self, op: str, xs, params=(), *, groups: int = 0, act: str = "none", k: int = 0, pad: int = 0,

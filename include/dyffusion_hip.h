@@ -229,8 +229,17 @@ int32_t dyf_row_groups(const dyf_engine* engine);
  *     16-bit engine draws the fp32 engine's keep bits at EVERY site.
  *   - dropout mode 2 applies the caller's uint8 keep masks, layout and site order as in the 16-bit path ((NB, 4, N, N) for the
  *     attention probabilities).
- *   - a graph captured under one precision is never replayed under the other.
- * dyf_sample_precision returns 16 or 32. */
+ *   - a graph captured under one precision is never replayed under another.
+ * bits = 48 = DYF_SAMPLE_PRECISION_BF16X3, "bf16x3": the fp32 sampling forward of bits = 32 with the convolution operands of
+ * dyf_train_set_precision(48).  The convs of unet_simple and unet.Unet that the 16-bit training dispatch takes (its channel rules) stage
+ * each fp32 operand value v as hi = bf16(v), lo = bf16(v - hi) and accumulate a_lo b_hi + a_hi b_lo + a_hi b_hi in fp32 on the bf16 matrix
+ * cores (4.5e-6 rel-RMS of a conv against float64; a rollout stays inside the 1e-4 per field that bits = 32 is held to).  Everything else
+ * is exactly as under 32: fp32 activations and weights, statistics, Linear, attention, stems, readout, every conv outside those rules, the
+ * arena and its sizing (the first switch to 32 OR 48 allocates it; its head also holds the 16-bit weight images of a launch), the
+ * generator's sites and keep bits, injected masks and noise, the 32 767-token bound, one row group.  SimpleConvNet keeps fp32 conv
+ * operands under 48 (its forward is bitwise the one under 32).  Accepted by both builds of the library.
+ * dyf_sample_precision returns 16, 32 or 48. */
+#define DYF_SAMPLE_PRECISION_BF16X3 48
 dyf_status dyf_set_sample_precision(dyf_engine* engine, int32_t bits);
 int32_t dyf_sample_precision(const dyf_engine* engine);
 
@@ -322,7 +331,7 @@ dyf_status dyf_train_zero_grads(dyf_engine* engine, int32_t net);
  * the fp32 kernels are held to; one bf16 term: 2.4e-3).  Nothing else is rounded, and everything else is exactly as under 32: tensors,
  * master weights, accumulation, statistics, every Linear and attention contraction, and every conv outside those channel rules (fp32
  * kernels).  SimpleConvNet keeps recording with fp32 conv operands under 48, as under 0 and 32 (only 16 is refused for it).  The
- * sampling paths do not read the setting. */
+ * sampling paths do not read the setting (they have their own: dyf_set_sample_precision). */
 #define DYF_TRAIN_PRECISION_BF16X3 48
 dyf_status dyf_train_set_precision(dyf_engine* engine, int32_t bits);
 int32_t dyf_train_precision(const dyf_engine* engine);

@@ -138,6 +138,10 @@ dyf_status dyf_train_conv_check(dyf_engine* engine, int32_t kind, int32_t n, int
  *                two forecaster passes of a step meet in one buffer); conv weights in PyTorch layout through dyf_train_export's unpack
  * op (inputs; parameters), hw = h * w:
  *   CONV        x (nb,h,w,c); weight (c2,c,k,k) [, bias (c2) with DYF_TOP_BIAS] -> (nb,ho,wo,c2); DYF_TOP_WS = weight-standardised
+ *               DYF_TOP_SAMPLE: the forward alone, launched the way a sampling forward launches it -- operand precision from
+ *               dyf_sample_precision (48: bf16x3; 16 and 32: fp32 operands), the default kernel forms, the sampling-forward scope of
+ *               csrc/train_internal.h set (the forms only sampling takes); no adjoint runs and no gradient is written.  Every other op
+ *               refuses the flag (DYF_ERR_UNSUPPORTED)
  *   GN_ACT      z (nb,hw,c) [, ss (nb,2c) = FiLM (scale | shift) with DYF_TOP_FILM]; weight (c), bias (c); `groups`; dropout p
  *   LAYERNORM   x (nb,hw,c); g (1,c,1,1); dropout p
  *   LINATTN     qkv (nb,hw,384) -> (nb,hw,128)
@@ -183,6 +187,7 @@ typedef enum dyf_train_op_kind {
 #define DYF_TOP_GRAD_IN 1024
 #define DYF_TOP_ACT_GELU 2048
 #define DYF_TOP_RESIDUAL 4096
+#define DYF_TOP_SAMPLE 8192
 typedef struct dyf_train_op {
     int32_t op, nb, h, w, c, c2, k, stride, pad, groups, flags;
     float p;

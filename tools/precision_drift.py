@@ -9,6 +9,11 @@ ONE JSON line: the per-horizon rel-RMS of the 16-bit fields against the fp32 fie
     python tools/precision_drift.py --small                                    # the 23x11 test pair (dim 64 @ 64^2, h = 4)
     python tools/precision_drift.py --config oisst --dtype fp16 --attention-dropout exact   # the 16-bit engine in its exact
                                                 # attention-dropout mode: the fp32 engine's keep bits at EVERY site, rounding alone is left
+    python tools/precision_drift.py --config ns --dtype bf16x3 [--rows 8]      # the bf16x3 sampling mode (dyf_set_sample_precision(48))
+                                                # against fp32: the same keep bits at every site, the conv operands alone differ
+    python tools/precision_drift.py --config ns --dtype bf16x3 --halo-ab 3     # and the forms of its 3 x 3 halo convs against each other
+                                                # (DYF_SAMPLE_HALO_FUSED = 1 fused, 0 the two-launch PASS form): one engine and one captured
+                                                # graph per form, replayed in turn, 3 rounds -> "halo_ab" {form: [seconds, ...]}
 
 Needs an MI355X.  Imports neither the oracle nor the reference: the fp32 engine is the yardstick.
 """
@@ -111,6 +116,31 @@ def rollout(m, x0, c, seed, reps):
     return out, best
 
 
+def halo_ab(config, a, forms):
+    """Seconds per rollout of a bf16x3 engine under each value of DYF_SAMPLE_HALO_FUSED: the switch is read when a conv is launched, so
+    every form gets an engine of its own that captures its rollout under it; the captured graphs are then replayed in turn."""
+    from dyffusion_amd import _lib
+    engines = {}
+    for form in forms:
+        _lib.set_form("DYF_SAMPLE_HALO_FUSED", form)
+        m, x0, c = make(config, "bf16x3", a.rows, not a.no_attention_dropout, a.attention_dropout)
+        rollout(m, x0, c, a.seed, 1)  # capture + one replay
+        engines[form] = (m, x0, c)
+    _lib.set_form("DYF_SAMPLE_HALO_FUSED", None)
+    times = {form: [] for form in forms}
+    for _ in range(a.halo_ab):
+        for form in forms:
+            m, x0, c = engines[form]
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            m.sample(x0, **({} if c is None else dict(static_condition=c)))
+            torch.cuda.synchronize()
+            times[form].append(time.perf_counter() - t0)
+    for m, _, _ in engines.values():
+        m._engine.close()
+    return times
+
+
 def rel_rms(a, b):
     return float(((a - b).double().pow(2).mean() / b.double().pow(2).mean()).sqrt())
 
@@ -119,7 +149,11 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--config", choices=["ns", "oisst", "synth512"], default="ns")
     ap.add_argument("--small", action="store_true", help="the 23x11 test pair instead of --config")
-    ap.add_argument("--dtype", choices=["bf16", "fp16"], default="bf16", help="the 16-bit engine compared with fp32")
+    ap.add_argument("--dtype", choices=["bf16", "fp16", "bf16x3"], default="bf16",
+                    help="the engine compared with fp32: 16-bit storage, or bf16x3 (fp32 forward, hi / lo bf16 conv operands)")
+    ap.add_argument("--halo-ab", type=int, default=0, metavar="ROUNDS",
+                    help="--dtype bf16x3: time the halo-conv forms against each other, ROUNDS rollouts each, alternating")
+    ap.add_argument("--halo-forms", default="1,0", help="values of DYF_SAMPLE_HALO_FUSED --halo-ab compares (1 fused, 0 PASS)")
     ap.add_argument("--rows", type=int, default=8, help="batch rows (ensemble members x batch) of the rollout")
     ap.add_argument("--no-attention-dropout", action="store_true", help="oisst / synth512: attn_dropout = 0 in both networks")
     ap.add_argument("--attention-dropout", choices=["fast", "exact"], default="fast",
@@ -144,6 +178,8 @@ def main():
     res["worst_rel_rms"] = max(res["rel_rms"].values())
     res["seconds_16bit"], res["seconds_fp32"] = times[a.dtype], times["fp32"]
     res["fp32_over_16bit_time"] = times["fp32"] / times[a.dtype]
+    if a.halo_ab > 0 and a.dtype == "bf16x3":
+        res["halo_ab"] = halo_ab(config, a, [f.strip() for f in a.halo_forms.split(",")])
     print(json.dumps(res))
 
 
