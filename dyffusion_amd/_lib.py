@@ -139,7 +139,7 @@ class SampleTensors(C.Structure):
 SAMPLE_OPS = {"gn_act": 0, "layernorm_c": 1, "head": 2, "up2_nearest": 3, "drop16": 4, "stem_conv": 5, "groupnorm_f32": 6, "up2_bilinear": 7,
               "up2_epilogue": 8, "readout": 9, "readout_tables": 10, "stem": 11, "stem16": 12, "rng_begin": 13, "rng_clone": 14, "time_mlp": 15,
               "film": 16, "cold_update": 17, "noisy_condition": 18}
-SOP_NO_STATS, SOP_NO_TABLES, SOP_FOLD_RNG, SOP_COUNTERS_ONLY = 1, 2, 4, 8
+SOP_NO_STATS, SOP_NO_TABLES, SOP_FOLD_RNG, SOP_COUNTERS_ONLY, SOP_PAIR_ONCE, SOP_STEM_PITCH8 = 1, 2, 4, 8, 16, 32
 RNG_STATE_WORDS = 8  # DYF_RNG_STATE_WORDS (csrc/kernels.h)
 ACTS = {"none": 0, "relu": 1, "leaky": 2, "silu": 3, "gelu": 4}
 

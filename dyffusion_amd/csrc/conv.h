@@ -21,8 +21,12 @@ struct ConvArgs {
     const el16_t* src1;
     int c0, c1;          // channels taken from src0 / src1 (c1 == 0: single source)
     int pix_pitch0;      // elements between consecutive pixels of src0 (0: = c0).  The fused stem feeds enc0 a 16-channel
-                         // tensor and declares c0 = 64: one K chunk then spans 4 horizontally adjacent pixels
+                         // tensor and declares c0 = 64: one K chunk then spans 4 horizontally adjacent pixels.  8: the 8-channel stem
+                         // (same declaration; conv_enc0_stem_kernel alone reads it: conv_choose_form answers Invalid otherwise)
     int n, h, w;         // input batch / height / width
+    int src0_rows;       // samples held by src0 (0: = n).  n = m * src0_rows: sample r of the output reads sample r % src0_rows (a paired
+                         // interpolator launch on a stem written once, StemArgs::distinct_only).  Only conv_enc0_stem_kernel
+                         // understands it: conv_choose_form answers Invalid when another form would take the conv
     int ho, wo;          // output height / width
     int kh, kw, stride, pad;
     int cout;
@@ -98,6 +102,7 @@ struct ConvW {
     const el16_t* halo = nullptr;    // halo-kernel order named by halo_order, or null
     HaloOrder halo_order = HaloOrder::None;
     const el16_t* frag64 = nullptr;  // pack_halo3_frag64 of a cout % 256 == 0 3x3 conv (conv_gn16_kernel) or null
+    const el16_t* enc0_p8 = nullptr; // pack_enc0_stem_frag8 beside HaloOrder::Enc0Stem (nets of at most 8 input channels) or null
 };
 
 // ================================================================================================ dispatch API (conv_dispatch.hip)
@@ -188,6 +193,8 @@ bool conv_enc0_stem_supported(const ConvArgs& a);
 hipError_t conv_enc0_stem_init();
 hipError_t launch_conv_enc0_stem(const ConvArgs& a, const el16_t* wfrag, hipStream_t stream);
 void pack_enc0_stem_frag(const el16_t* wpk, int cout, el16_t* out);
+// ... for the 8-channel stem (ConvArgs::pix_pitch0 == 8): 9 k-steps, out holds 9 * cout * 16 elements; cin <= 8 = the nets' input channels
+void pack_enc0_stem_frag8(const el16_t* wpk, int cout, int cin, el16_t* out);
 // second implicit-GEMM form (conv_igemm2.hip): 256 px x 128 ch per workgroup, weights streamed in fragment order
 bool conv_igemm2_supported(const ConvArgs& a);
 hipError_t conv_igemm2_init();

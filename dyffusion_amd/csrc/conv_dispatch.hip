@@ -56,7 +56,8 @@ const el16_t* halo5_admits(const ConvArgs& a, const ConvW& w) {
 }
 
 const el16_t* enc0_stem_admits(const ConvArgs& a, const ConvW& w) {  // enc0 on the fused stem: HBM-bound, its own persistent kernel
-    return a.pix_pitch0 == 16 && conv_enc0_stem_supported(a) ? halo_of(w, HaloOrder::Enc0Stem) : nullptr;
+    if (!conv_enc0_stem_supported(a) || !halo_of(w, HaloOrder::Enc0Stem)) return nullptr;
+    return a.pix_pitch0 == 8 ? w.enc0_p8 : w.halo;  // (supported: pitch 16 or 8)
 }
 
 const el16_t* halo_s2_admits(const ConvArgs& a, const ConvW& w) {  // 4x4 / s2 convs: the halo kernel on the space-to-depth view
@@ -218,7 +219,10 @@ hipError_t launch_chosen(ConvArgs& a, const ConvChoice& c, hipStream_t stream) {
 
 ConvChoice conv_choose_form(const ConvArgs& a, const ConvW& w, int path, ConvWant want) {
     const bool mfma = path == 1 && conv_mfma_supported(a);
-    return want == ConvWant::GnFused ? choose_gn_fused(a, w, mfma) : choose_plain(a, w, mfma, want == ConvWant::Stats);
+    const ConvChoice c = want == ConvWant::GnFused ? choose_gn_fused(a, w, mfma) : choose_plain(a, w, mfma, want == ConvWant::Stats);
+    // a source that holds fewer samples than the output (ConvArgs::src0_rows), or the 8-channel stem, is read correctly by one form only
+    if (((a.src0_rows > 0 && a.src0_rows != a.n) || a.pix_pitch0 == 8) && c.form != ConvForm::Enc0Stem) return {ConvForm::Invalid, nullptr, 0, 0};
+    return c;
 }
 
 bool conv_plain3x3_takes_halo5(const ConvArgs& a, const ConvW& w) {

@@ -136,8 +136,8 @@ dyf_status run_conv(dyf_engine* e, const ConvArgs& a, const ConvW& w, hipStream_
 // enc0 on the fused stem: a 4(kh) x 1 conv over "64-channel" pixels that are really 4 adjacent 16-channel pixels of the
 // zero-bordered stem16 tensor (stride 2, physical padding instead of pad=1).
 // Returns the composed weights the conv then runs with.
-const ConvW* fused_enc0_args(const dyf_engine* e, const Net& n, ConvArgs& a) {
-    a.src0 = e->ws.stem16; a.c0 = 64; a.pix_pitch0 = 16;
+const ConvW* fused_enc0_args(const dyf_engine* e, const Net& n, ConvArgs& a, int pitch = 16) {
+    a.src0 = e->ws.stem16; a.c0 = 64; a.pix_pitch0 = pitch;  // (8: the 8-channel stem, net_forward)
     a.h = n.uh + 2; a.w = n.uw + 2;
     a.kh = 4; a.kw = 1; a.stride = 2; a.pad = 0;
     return &n.enc0_fused_w;
@@ -195,8 +195,32 @@ dyf_status net_forward(dyf_engine* e, int which, const Source* srcs, int nsrc, i
     if (rng_in_stem) {
         sa.rng_state = e->rng_state; sa.rng_row_keys = e->row_keys; sa.rng_rows = nb; sa.rng_rows_per_fwd = o.src_rows > 0 ? o.src_rows : nb;
     }
+    // Two forms of the encoder entry that only the persistent enc0 kernel reads, decided up front (conv_choose_form launches nothing)
+    // and taken when enc0 will run on that kernel WITH them; every other case -- few rows, DYF_ENC0_STEM=0, more copies of a row than
+    // the kernel holds coefficient rows for -- keeps the full 16-channel stem tensor:
+    //  * the 8-channel stem (nets of at most 8 input channels), with DYF_STEM_PITCH=8.  Not the default: enc0's fp32 sums then run in
+    //    another order, and the 60 chained forwards of a rollout carry that to the fields (docs/DESIGN_HISTORY.md, last section);
+    //  * a paired launch (src_rows < nb: rows r and r + src_rows have the same inputs) writes and reads each distinct stem row once
+    //    (StemArgs::distinct_only, ConvArgs::src0_rows; DYF_STEM_PAIR_ONCE=0: never).
+    bool pair_once = false;
+    int stem_pitch = 16;
+    if (fused_stem && !n.blk[0].gn) {
+        const int want_pitch = dyf_form_int("DYF_STEM_PITCH", 16) == 8 && n.cin_total <= 8 && n.enc0_fused_w.enc0_p8 ? 8 : 16;
+        const int want_rows = o.src_rows > 0 && o.src_rows < nb && dyf_form_int("DYF_STEM_PAIR_ONCE", 1) != 0 ? o.src_rows : 0;
+        if (want_pitch == 8 || want_rows > 0) {
+            ConvArgs a0 = block_conv_args(e, n, n.blk[0], nb);
+            const ConvW* w0 = fused_enc0_args(e, n, a0, want_pitch);
+            a0.src0_rows = want_rows; a0.wpk = w0->wpk; a0.out_el16 = ws.enc[0];
+            if (conv_choose_form(a0, *w0, conv_path(e, a0), ConvWant::Plain).form == ConvForm::Enc0Stem) {
+                stem_pitch = want_pitch;
+                pair_once = want_rows > 0;
+            }
+        }
+    }
     if (fused_stem) {
         sa.out = ws.stem16;
+        sa.out_pitch = ws.stem16_pitch = stem_pitch;
+        sa.distinct_only = pair_once ? 1 : 0;
         HIP_TRY(e, launch_stem16(sa, st));
     } else {
         sa.out = ws.stem;
@@ -209,7 +233,8 @@ dyf_status net_forward(dyf_engine* e, int which, const Source* srcs, int nsrc, i
         ConvArgs a = block_conv_args(e, n, b, nb);
         a.src0 = x; a.c0 = b.cin; a.src1 = nullptr; a.c1 = 0;
         const ConvW* w = &b.wpk;
-        if (i == 0 && fused_stem) w = fused_enc0_args(e, n, a);
+        if (i == 0 && fused_stem) w = fused_enc0_args(e, n, a, stem_pitch);
+        if (i == 0 && pair_once) a.src0_rows = o.src_rows;
         if (!b.gn) {
             a.coef_a = o.coef_a + b.film_off; a.coef_c = o.coef_c + b.film_off; a.coef_stride = o.coef_stride;
             a.coef_div = o.coef_div;
@@ -731,7 +756,7 @@ static dyf_status load_weights_one(dyf_engine* e, int32_t which, int32_t n_tenso
                             }
                         fw[((size_t)co * 16 + t) * 16 + c] = f32_to_el16((float)v);
                     }
-            { dyf_status _s = upload_conv_weights(e, &n.enc0_fused_w, fw, b.cout, 4, 64, /*enc0_stem=*/true); if (_s != DYF_OK) return _s; }
+            { dyf_status _s = upload_conv_weights(e, &n.enc0_fused_w, fw, b.cout, 4, 64, /*enc0_stem=*/true, n.cin_total); if (_s != DYF_OK) return _s; }
             n.stem_fused = true;
         }
         if (b.transposed && b.k == 3) {
@@ -1687,7 +1712,11 @@ dyf_status dyf_time_conv_layer(dyf_engine* e, int32_t which, int32_t layer, int3
     a.src0 = b.transposed ? e->ws.up : (layer == 0 ? e->ws.stem : e->ws.enc[layer - 1]);
     a.c0 = b.cin;
     const ConvW* w = &b.wpk;
-    if (layer == 0 && n.stem_fused && e->cfg.enable_mfma && e->fuse_stem && n.cfg.input_dropout == 0.0f) w = fused_enc0_args(e, n, a);
+    if (layer == 0 && n.stem_fused && e->cfg.enable_mfma && e->fuse_stem && n.cfg.input_dropout == 0.0f) {
+        w = fused_enc0_args(e, n, a, e->ws.stem16_pitch);  // the stem tensor as the last forward left it, when this batch runs that form
+        a.out_el16 = e->ws.enc[0];
+        if (a.pix_pitch0 != 16 && conv_choose_form(a, *w, conv_path(e, a), ConvWant::Plain).form != ConvForm::Enc0Stem) w = fused_enc0_args(e, n, a);
+    }
     if (b.transposed && layer > 6) {  // fused x2-upsample form when net_forward uses it
         ConvArgs f = a;
         const UBlock& skipb = n.blk[11 - layer];
@@ -2176,7 +2205,7 @@ static dyf_status sample_op_net(dyf_engine* e, const dyf_sample_op& d, const dyf
     if (!t.y) return bad("null output");
     if (d.k || d.pad || d.groups || d.act || d.film_stride || d.film_div || d.part_slots || t.residual || t.film_a || t.film_c || t.part)
         return bad("k / pad / groups / act / FiLM rows / residual / part belong to the kernels between the convs");
-    const int allowed = readout ? DYF_SOP_NO_TABLES : stem16 ? DYF_SOP_FOLD_RNG : clone ? DYF_SOP_COUNTERS_ONLY : 0;
+    const int allowed = readout ? DYF_SOP_NO_TABLES : stem16 ? (DYF_SOP_FOLD_RNG | DYF_SOP_PAIR_ONCE | DYF_SOP_STEM_PITCH8) : clone ? DYF_SOP_COUNTERS_ONLY : 0;
     if (d.flags & ~allowed) return bad("a flag the op does not take");
     const bool fold = stem16 && (d.flags & DYF_SOP_FOLD_RNG);
     if (!stem && (d.drop_mode != 0 || t.mask || d.drop_p != 0.0f || d.drop_site != 0)) return bad("the op has no dropout");
@@ -2215,6 +2244,8 @@ static dyf_status sample_op_net(dyf_engine* e, const dyf_sample_op& d, const dyf
         for (int i = 0; i < 4; ++i)
             if ((i < d.nsrc) != (t.x[i] != nullptr)) return bad("STEM: sources and their channel counts go together");
         if (d.src_rows > d.nb) return bad("STEM: src_rows above nb");
+        if ((d.flags & DYF_SOP_STEM_PITCH8) && d.c > 8) return unsup("STEM16: the 8-channel stem takes at most 8 channels");
+        if ((d.flags & DYF_SOP_PAIR_ONCE) && d.src_rows < 1) return bad("STEM16: DYF_SOP_PAIR_ONCE writes the src_rows distinct rows");
         if (stem ? (d.c2 < 1 || d.c > DYF_MAX_IN_CH) : (d.c2 != 0 || d.c > 15)) return unsup("STEM: c2 = dim and c <= 32 (STEM); c <= 15 and no c2 (STEM16)");
         if ((long long)d.nb * (d.oh + 2) * (d.ow + 2) * std::max(d.c2, 16) >= 0x7F000000ll || hw * d.c * d.nb >= 0x7F000000ll)
             return unsup("tensor too large for the kernels' 32-bit indices");
@@ -2306,6 +2337,8 @@ static dyf_status sample_op_net(dyf_engine* e, const dyf_sample_op& d, const dyf
             a.nsrc = d.nsrc; a.cin = d.c; a.n = d.nb; a.src_rows = d.src_rows; a.h = d.h; a.w = d.w; a.uh = d.oh; a.uw = d.ow;
             a.resample = (d.oh != d.h || d.ow != d.w) ? 1 : 0;  // as net_forward
             a.nearest = d.nearest; a.dim = d.c2; a.out = (el16_t*)t.y;
+            a.distinct_only = (d.flags & DYF_SOP_PAIR_ONCE) ? 1 : 0;
+            a.out_pitch = (d.flags & DYF_SOP_STEM_PITCH8) ? 8 : 16;
             if (stem) {
                 rs = upf(&a.wgt, params_host[0], (size_t)d.c2 * d.c);
                 if (rs == DYF_OK) rs = upf(&a.bias, params_host[1], (size_t)d.c2);

@@ -63,7 +63,7 @@ struct Net {
     el16_t* ro_wfrag = nullptr;  // readout weights as MFMA fragments (dim 64, <= 4 output channels)
     uint4 *ro_row_tab = nullptr, *ro_col_tab = nullptr;  // tap tables of the readout (launch_readout_tables), with ro_wfrag
     bool ro_tab_sparse = false;  // ... built for the compact (sparse-column) layout of the last decoder block's output
-    ConvW enc0_fused_w;  // [2dim][4][64]: enc0's 4x4 conv composed with init_conv (+ bias channel), with its stem fragments
+    ConvW enc0_fused_w;  // [2dim][4][64]: enc0's 4x4 conv composed with init_conv (+ bias channel), with its stem fragments (16- and 8-channel stem)
     bool stem_fused = false;
     double flops_per_sample = 0.0;
     int n_drop_sites = 12;   // dropout sites with p > 0 per forward (mask-injection cursor); 12 UNetBlocks for unet_simple
@@ -78,6 +78,7 @@ struct Net {
 struct Workspace {
     el16_t* stem = nullptr;
     el16_t* stem16 = nullptr;  // fused stem: [nb][uh+2][uw+2][16]
+    int stem16_pitch = 16;     // channels per pixel the last fused-stem launch wrote (8: [rows][uh+2][uw+2][8], net_forward)
     el16_t* enc[6] = {};
     float* enc5_raw = nullptr;
     el16_t* up = nullptr;
@@ -287,9 +288,10 @@ inline std::vector<el16_t> pack_conv(const float* w, int cout, int cin, int taps
 
 // packed conv weights [cout][taps][cin] -> device, with every fragment-ordered copy a kernel form of this shape streams: the ONE
 // place that decides which orders a conv gets (the admission rules of conv_dispatch.hip check the order they are handed).
-// enc0_stem: pk is enc0's 4x4 conv composed with init_conv, [cout][4][64]
+// enc0_stem: pk is enc0's 4x4 conv composed with init_conv, [cout][4][64]; enc0_stem_cin: the net's input channels (<= 8: also the
+// fragments of the 8-channel stem)
 inline dyf_status upload_conv_weights(dyf_engine* e, ConvW* out, const std::vector<el16_t>& pk, int cout, int taps, int cin,
-                                      bool enc0_stem = false) {
+                                      bool enc0_stem = false, int enc0_stem_cin = 0) {
     *out = ConvW{};
     auto up = [&](const el16_t** dst, const std::vector<el16_t>& host) {
         el16_t* p = nullptr;
@@ -307,6 +309,12 @@ inline dyf_status upload_conv_weights(dyf_engine* e, ConvW* out, const std::vect
     }
     if (enc0_stem && (cout == 64 || cout == 128)) {  // the persistent enc0 kernel (conv_enc0_stem.hip)
         pf.assign(pk.size(), el16_t{});
+        if (enc0_stem_cin >= 1 && enc0_stem_cin <= 8) {
+            pf.assign((size_t)9 * cout * 16, el16_t{});
+            pack_enc0_stem_frag8(pk.data(), cout, enc0_stem_cin, pf.data());
+            if ((st = up(&out->enc0_p8, pf)) != DYF_OK) return st;
+            pf.assign(pk.size(), el16_t{});
+        }
         pack_enc0_stem_frag(pk.data(), cout, pf.data());
         out->halo_order = HaloOrder::Enc0Stem;
     } else if (taps == 16 && cout % 128 == 0) {  // halo form of 4x4 / s2

@@ -47,6 +47,11 @@ struct StemArgs {
     int n, h, w;            // native grid
     int src_rows;           // rows held by the source tensors (0: = n); output row r reads source row r % src_rows, so
                             // one launch can run the same inputs under several FiLM rows (paired interpolator calls)
+    int out_pitch;          // fused-stem form only: channels per output pixel, 16 (or 0) or 8.  8 (cin <= 8): [rows][uh+2][uw+2][8], channels
+                            // cin..7 zero and NO bias slot (conv_enc0_stem_kernel<.., P8> carries init_conv's bias in a k-step of its own)
+    int distinct_only;      // fused-stem form only: write just the src_rows distinct rows of the output (rows r >= src_rows would be
+                            // copies of row r % src_rows; conv_enc0_stem_kernel then reads each once, ConvArgs::src0_rows).  n stays
+                            // the forward's row count.  0: all n rows
     int uh, uw;             // resampled grid (== h, w when there is no outer resampling)
     int resample;           // 0: identity, 1: resample to (uh, uw)
     int nearest;            // outer_sample_mode: 0 bilinear (align_corners=False), 1 nearest
@@ -64,8 +69,11 @@ struct StemArgs {
 hipError_t launch_stem(const StemArgs& a, hipStream_t s);
 // Fused-stem form: only the outer resample, written as a zero-bordered [n][uh+2][uw+2][16] bf16 tensor whose channel
 // `cin` is 1 inside the image (carries init_conv's bias through the composed enc0 weights); the 1x1 conv itself is
-// folded into the first encoder block's weights (engine.hip: compose_stem_enc0).
+// folded into the first encoder block's weights (engine.hip: compose_stem_enc0).  StemArgs::out_pitch == 8: 8-channel pixels without
+// the bias slot (hipErrorInvalidValue when cin > 8).
 hipError_t launch_stem16(const StemArgs& a, hipStream_t s);
+// rows of the stem16 tensor a launch writes
+inline __host__ __device__ int stem16_out_rows(const StemArgs& a) { return a.distinct_only && a.src_rows > 0 ? a.src_rows : a.n; }
 
 // K2 (materialised form): bilinear x2 upsample of cat[src0, src1] (NHWC bf16) -> NHWC bf16
 struct Up2xArgs {

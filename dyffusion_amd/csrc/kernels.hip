@@ -199,7 +199,7 @@ __global__ __launch_bounds__(256) void stem16_kernel(StemArgs a) {
     stem_rng_begin(a);
     const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
     const int ph = a.uh + 2, pw = a.uw + 2;
-    const long long total = (long long)a.n * ph * pw;
+    const long long total = (long long)stem16_out_rows(a) * ph * pw;
     if (idx >= total) return;
     const int n = (int)(idx / ((long long)ph * pw));
     const int rem = (int)(idx % ((long long)ph * pw));
@@ -229,13 +229,17 @@ __global__ __launch_bounds__(256) void stem16_kernel(StemArgs a) {
                 const float top = p[o00] * (1.0f - lx) + p[o01] * lx;
                 const float bot = p[o10] * (1.0f - lx) + p[o11] * lx;
                 val = top * (1.0f - ly) + bot * ly;
-            } else if (k == a.cin) {
+            } else if (k == a.cin && a.out_pitch != 8) {
                 val = 1.0f;  // carries init_conv's bias through the composed enc0 weights
             }
             v[k] = val;
         }
 #pragma unroll
         for (int k = 0; k < 8; ++k) w[k] = pack_el16x2(v[2 * k], v[2 * k + 1]);
+    }
+    if (a.out_pitch == 8) {  // (cin <= 8: w[4..7] are zero)
+        *(uint4*)(a.out + (size_t)idx * 8) = make_uint4(w[0], w[1], w[2], w[3]);
+        return;
     }
     uint4* o = (uint4*)(a.out + (size_t)idx * 16);
     o[0] = make_uint4(w[0], w[1], w[2], w[3]);
@@ -310,7 +314,8 @@ __global__ __launch_bounds__(512) void stem16_rows_kernel(StemArgs a, int nblk) 
         }
     }
     __syncthreads();
-    uint4* oblk = (uint4*)(a.out + (((size_t)n * ph + py0) * pw) * 16);
+    const bool p8 = a.out_pitch == 8;  // 8-channel pixels: one 16-byte chunk each, no bias slot
+    uint4* oblk = (uint4*)(a.out + (((size_t)n * ph + py0) * pw) * (p8 ? 8 : 16));
     if (a.cin <= 8 && (a.uw & 63) == 0) {
         // At most 8 input channels (the NS nets: 8): channels 8-15 of a pixel are constants (the bias slot, zeros), so only ONE lane per
         // pixel does arithmetic -- the loop is instruction-bound -- and the pixel's two 16-byte halves pass through a per-wave
@@ -321,7 +326,8 @@ __global__ __launch_bounds__(512) void stem16_rows_kernel(StemArgs a, int nblk) 
         const uint4 half1 = a.cin == 8 ? make_uint4(pack_el16x2(1.0f, 0.0f), 0, 0, 0) : zero4;  // slot cin = 1 (init_conv's bias)
         for (int i = threadIdx.x; i < (py1 - py0) * 4; i += 512) {  // the two zero border pixels of every row
             const int rr = i >> 2, q = i & 3;
-            oblk[(size_t)rr * 2 * pw + (q < 2 ? q : 2 * pw - 4 + q)] = zero4;
+            if (!p8) oblk[(size_t)rr * 2 * pw + (q < 2 ? q : 2 * pw - 4 + q)] = zero4;
+            else if (q < 2) oblk[(size_t)rr * pw + (q ? pw - 1 : 0)] = zero4;
         }
         const int total_in = (py1 - py0) * a.uw;
         int r = 0, j = threadIdx.x;  // interior pixel (row r of the block, column j)
@@ -352,11 +358,17 @@ __global__ __launch_bounds__(512) void stem16_rows_kernel(StemArgs a, int nblk) 
                         const float top = t00[e] * (1.0f - lx) + t01[e] * lx;
                         const float bot = t10[e] * (1.0f - lx) + t11[e] * lx;
                         float val = top * (1.0f - ly) + bot * ly;
-                        if (k >= a.cin) val = k == a.cin ? 1.0f : 0.0f;
+                        if (k >= a.cin) val = k == a.cin && !p8 ? 1.0f : 0.0f;
                         v[k] = val;
                     }
                 }
                 w = make_uint4(pack_el16x2(v[0], v[1]), pack_el16x2(v[2], v[3]), pack_el16x2(v[4], v[5]), pack_el16x2(v[6], v[7]));
+            }
+            if (p8) {  // the pixel IS its first half: a wave stores 1 KB for its 64 consecutive pixels straight from the registers
+                oblk[(size_t)r * pw + 1 + j] = w;
+                j += 512;
+                while (j >= a.uw) { j -= a.uw; ++r; }
+                continue;
             }
             *(uint4*)(stg + lane * 32) = w;
             *(uint4*)(stg + lane * 32 + 16) = yt.w ? half1 : zero4;
@@ -368,10 +380,12 @@ __global__ __launch_bounds__(512) void stem16_rows_kernel(StemArgs a, int nblk) 
         }
         return;
     }
-    const int total = (py1 - py0) * 2 * pw;
-    int r = 0, j = threadIdx.x;  // item i = r * 2 pw + j, advanced without a division (512 <= 2 pw is checked by the launcher)
+    // items: 16-byte chunks, two per pixel (one at pitch 8)
+    const int per_row = p8 ? pw : 2 * pw, total = (py1 - py0) * per_row;
+    int r = 0, j = threadIdx.x;  // item i = r * per_row + j, advanced without a division (512 <= 2 pw is checked by the launcher)
+    while (j >= per_row) { j -= per_row; ++r; }
     for (int i = threadIdx.x; i < total; i += 512) {
-        const int px = j >> 1, half = j & 1;
+        const int px = p8 ? j : j >> 1, half = p8 ? 0 : j & 1;
         const int4 xt = xtab[px], yt = ytab[r];
         uint32_t w[4] = {0, 0, 0, 0};
         if (xt.w && yt.w) {
@@ -398,7 +412,7 @@ __global__ __launch_bounds__(512) void stem16_rows_kernel(StemArgs a, int nblk) 
                     const float top = t00[e] * (1.0f - lx) + t01[e] * lx;
                     const float bot = t10[e] * (1.0f - lx) + t11[e] * lx;
                     float val = top * (1.0f - ly) + bot * ly;
-                    if (k >= a.cin) val = k == a.cin ? 1.0f : 0.0f;  // slot cin carries init_conv's bias through the composed enc0 weights
+                    if (k >= a.cin) val = k == a.cin && !p8 ? 1.0f : 0.0f;  // slot cin carries init_conv's bias through the composed enc0 weights
                     v[4 * q2 + e] = val;
                 }
             }
@@ -407,7 +421,7 @@ __global__ __launch_bounds__(512) void stem16_rows_kernel(StemArgs a, int nblk) 
         }
         oblk[i] = make_uint4(w[0], w[1], w[2], w[3]);
         j += 512;
-        if (j >= 2 * pw) { j -= 2 * pw; ++r; }
+        while (j >= per_row) { j -= per_row; ++r; }
     }
 }
 
@@ -415,18 +429,20 @@ hipError_t launch_stem16(const StemArgs& a, hipStream_t s) {
     const int cp = (a.cin + 3) / 4 * 4;  // cin <= 15 (the fused stem's bias channel is slot cin)
     const size_t lds = (size_t)(ST_ROWS + 2) * a.w * cp * sizeof(float) + (size_t)(a.uw + 2 + ST_ROWS) * 16 + 8 * 2048;  // rows + stencil tables + per-wave output tiles
     const bool rows = dyf_form_int("DYF_STEM16_ROWS", 1) != 0;  // read per launch: the parity test flips it
+    const int rows_out = stem16_out_rows(a), pitch = a.out_pitch == 8 ? 8 : 16;
+    if ((a.out_pitch != 0 && a.out_pitch != 8 && a.out_pitch != 16) || (pitch == 8 && a.cin > 8)) return hipErrorInvalidValue;
     if (rows && lds <= 48 * 1024 && cp <= 16 && a.h <= a.uh && 2 * (a.uw + 2) >= 512) {
         const int nblk = (a.uh + 2 + ST_ROWS - 1) / ST_ROWS;
-        const dim3 grid((unsigned)(a.n * nblk)), block(512);
-        dyf_form_note("stem16_rows_kernel", a.n);
-        KernelProf kp("stem16_rows_kernel", s, (double)(a.src_rows ? a.src_rows : a.n) * a.h * a.w * a.cin * 4.0 + (double)a.n * (a.uh + 2) * (a.uw + 2) * 16 * 2.0);
+        const dim3 grid((unsigned)(rows_out * nblk)), block(512);
+        dyf_form_note("stem16_rows_kernel", a.n);  // (the rows of the forward the launch serves, written or not)
+        KernelProf kp("stem16_rows_kernel", s, (double)(a.src_rows ? a.src_rows : a.n) * a.h * a.w * a.cin * 4.0 + (double)rows_out * (a.uh + 2) * (a.uw + 2) * pitch * 2.0);
         if (cp == 4) hipLaunchKernelGGL(stem16_rows_kernel<4>, grid, block, lds, s, a, nblk);
         else if (cp == 8) hipLaunchKernelGGL(stem16_rows_kernel<8>, grid, block, lds, s, a, nblk);
         else if (cp == 12) hipLaunchKernelGGL(stem16_rows_kernel<12>, grid, block, lds, s, a, nblk);
         else hipLaunchKernelGGL(stem16_rows_kernel<16>, grid, block, lds, s, a, nblk);
         return hipGetLastError();
     }
-    const long long total = (long long)a.n * (a.uh + 2) * (a.uw + 2);
+    const long long total = (long long)rows_out * (a.uh + 2) * (a.uw + 2);
     dyf_form_note("stem16_kernel", a.n);
     hipLaunchKernelGGL(stem16_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, a);
     return hipGetLastError();

@@ -1072,7 +1072,7 @@ class HipEngine:
 
     def _op_sample_net(self, op, xs, params, *, mask=None, p=0.0, rng_site=None, rng_row_offset=0, rng_forward=0, out_hw=None, in_hw=None,
                        nearest=False, src_rows=0, nb=None, col_map=None, tables=True, fold_rng=False, counters_only=False, dst=None, tau=0.0,
-                       blocks=(), copy=False, iw_store=None):
+                       blocks=(), copy=False, iw_store=None, pair_once=False, pitch=16):
         """dyf_op_sample16 for the launchers around the networks (csrc/kernels.hip).  Device tensors, parameters fp32 in PyTorch layouts.
           readout         xs = [x 16-bit (nb, ih, iw_store, cin)], params = [weight (cin, cout, 4, 4), bias]; out_hw = the native grid;
                           col_map: int16 device tensor (iw,) of a compact input; tables=False: launch without the tap tables -> fp32 NCHW
@@ -1080,7 +1080,9 @@ class HipEngine:
                           byte offsets, four weight bit patterns
           stem / stem16   xs = 1..4 fp32 NCHW sources of src_rows (or nb) rows; out_hw = (uh, uw); params = [weight (dim, cin), bias] for
                           stem; nb: output rows (default: the sources'); stem: mask / rng_site dropout -> 16-bit NHWC; stem16:
-                          (nb, uh + 2, uw + 2, 16), with fold_rng also the row-key table (nb, 2) and the generator state (8,), int32 bit patterns
+                          (nb, uh + 2, uw + 2, 16), with fold_rng also the row-key table (nb, 2) and the generator state (8,), int32 bit patterns;
+                          pair_once (needs src_rows): only the src_rows distinct rows are written -> (src_rows, uh + 2, uw + 2, 16);
+                          pitch=8 (at most 8 channels): 8-channel pixels without the bias slot -> (rows, uh + 2, uw + 2, 8)
           rng_begin       nb rows, src_rows per forward, rng_forward, rng_row_offset -> (row-key table, state)
           rng_clone       xs = [source state int32 (8,)], dst = destination state (not modified), rng_row_offset = row_add -> the new destination
           time_mlp        xs = [times fp32 (rows,)], params = [w1, b1, w2, b2 (, learned weights)] -> fp32 (rows, 2 dim)
@@ -1092,10 +1094,11 @@ class HipEngine:
                                    ("rng_forward", rng_forward, 0), ("out_hw", out_hw, None), ("in_hw", in_hw, None), ("nearest", nearest, False),
                                    ("src_rows", src_rows, 0), ("nb", nb, None), ("col_map", col_map, None), ("tables", tables, True),
                                    ("fold_rng", fold_rng, False), ("counters_only", counters_only, False), ("dst", dst, None), ("tau", tau, 0.0),
-                                   ("blocks", blocks, ()), ("copy", copy, False), ("iw_store", iw_store, None)) if v is not d and v != d}
+                                   ("blocks", blocks, ()), ("copy", copy, False), ("iw_store", iw_store, None),
+                                   ("pair_once", pair_once, False), ("pitch", pitch, 16)) if v is not d and v != d}
         takes = {"readout": {"out_hw", "nearest", "col_map", "tables"}, "readout_tables": {"in_hw", "out_hw", "nearest", "col_map", "iw_store"},
                  "stem": {"out_hw", "nearest", "src_rows", "nb", "mask", "p", "rng_site", "rng_row_offset", "rng_forward"},
-                 "stem16": {"out_hw", "nearest", "src_rows", "nb", "fold_rng", "rng_row_offset", "rng_forward"},
+                 "stem16": {"out_hw", "nearest", "src_rows", "nb", "fold_rng", "rng_row_offset", "rng_forward", "pair_once", "pitch"},
                  "rng_begin": {"nb", "src_rows", "rng_row_offset", "rng_forward"}, "rng_clone": {"dst", "rng_row_offset", "counters_only"},
                  "time_mlp": set(), "film": {"blocks", "nb"}, "cold_update": {"copy"}, "noisy_condition": {"tau", "rng_row_offset"}}[op]
         if given - takes:
@@ -1158,9 +1161,14 @@ class HipEngine:
                 elif rng_site is not None:
                     desc.drop_mode, desc.drop_site, desc.drop_row_offset, desc.drop_forward = 1, int(rng_site), int(rng_row_offset), int(rng_forward)
             else:
-                outs = [torch.empty((desc.nb, desc.oh + 2, desc.ow + 2, 16), dtype=dt, device=dev)]
+                if pair_once and desc.src_rows < 1:
+                    raise ValueError("stem16: pair_once writes the src_rows distinct rows: give src_rows")
+                if pitch not in (8, 16) or (pitch == 8 and desc.c > 8):
+                    raise ValueError("stem16: pitch is 16, or 8 for at most 8 channels")
+                outs = [torch.empty((desc.src_rows if pair_once else desc.nb, desc.oh + 2, desc.ow + 2, int(pitch)), dtype=dt, device=dev)]
+                desc.flags = (L.SOP_PAIR_ONCE if pair_once else 0) | (L.SOP_STEM_PITCH8 if pitch == 8 else 0)
                 if fold_rng:
-                    desc.flags, desc.drop_row_offset, desc.drop_forward = L.SOP_FOLD_RNG, int(rng_row_offset), int(rng_forward)
+                    desc.flags, desc.drop_row_offset, desc.drop_forward = desc.flags | L.SOP_FOLD_RNG, int(rng_row_offset), int(rng_forward)
                     outs += [i32(desc.nb, 2), i32(L.RNG_STATE_WORDS)]
         elif op == "rng_begin":
             desc.nb, desc.src_rows, desc.drop_row_offset, desc.drop_forward = int(nb), int(src_rows), int(rng_row_offset), int(rng_forward)

@@ -232,8 +232,10 @@ dyf_status dyf_op_train_f32(dyf_engine* engine, const dyf_train_op* desc, const 
  *                 r reads source row r % src_rows; dropout as below -> y 16-bit (nb,oh,ow,c2)
  *   STEM16        launch_stem16, c <= 15, no parameters -> y 16-bit (nb,oh+2,ow+2,16); DYF_SOP_FOLD_RNG: the start of a forward folded
  *                 into the launch (StemArgs::rng_state / rng_row_keys of the engine, nb <= 2 max_batch rows, src_rows or nb rows per
- *                 forward) -> y2 = the row-key table (2 nb words), y3 = the generator state (DYF_RNG_STATE_WORDS words) afterwards
- *   RNG_BEGIN     launch_rng_begin_forward over nb rows, src_rows (0: nb) rows per forward, from forward index drop_forward and row
+ *                 forward) -> y2 = the row-key table (2 nb words), y3 = the generator state (DYF_RNG_STATE_WORDS words) afterwards;
+ *                 DYF_SOP_PAIR_ONCE (src_rows > 0): StemArgs::distinct_only -> y holds the src_rows distinct rows only;
+ *                 DYF_SOP_STEM_PITCH8 (c <= 8): StemArgs::out_pitch = 8 -> y 16-bit (rows,oh+2,ow+2,8), no bias slot
+ *   RNG_BEGIN    launch_rng_begin_forward over nb rows, src_rows (0: nb) rows per forward, from forward index drop_forward and row
  *                 offset drop_row_offset (set as generator dropout sets them) -> y = the row-key table, y2 = the state afterwards
  *   RNG_CLONE     launch_rng_clone: x[0] = source state, y = destination state (IN/OUT), DYF_RNG_STATE_WORDS device words each; row_add =
  *                 drop_row_offset; DYF_SOP_COUNTERS_ONLY
@@ -260,6 +262,8 @@ typedef enum dyf_sample_op_kind {
 #define DYF_SOP_NO_TABLES 2
 #define DYF_SOP_FOLD_RNG 4
 #define DYF_SOP_COUNTERS_ONLY 8
+#define DYF_SOP_PAIR_ONCE 16
+#define DYF_SOP_STEM_PITCH8 32
 typedef struct dyf_sample_op {
     int32_t op, nb, h, w, c, c2, k, pad, groups, act, flags;
     int32_t film_stride, film_div, part_slots;
