@@ -391,6 +391,8 @@ static void destroy_groups(dyf_engine* e) {
     e->last_groups = 0;
 }
 
+static void traj_release(dyf_engine* e);
+
 void dyf_engine_destroy(dyf_engine* e) {
     if (!e) return;
     (void)hipSetDevice(e->cfg.device);
@@ -408,6 +410,7 @@ void dyf_engine_destroy(dyf_engine* e) {
     if (e->s_log) (void)hipFree(e->s_log);
     if (e->cap_stream) (void)hipStreamDestroy(e->cap_stream);
     if (e->gn_err_host) (void)hipHostFree(e->gn_err_host);
+    traj_release(e);
     f32_destroy(e);
     train_destroy(e);
     release_allocs(e->allocs);
@@ -1784,6 +1787,81 @@ dyf_status dyf_ensemble_metrics(dyf_engine* e, const float* preds_dev, const flo
     out_host[0] = mse;
     out_host[1] = std::sqrt(h[1] / (double)n_points) / std::sqrt(mse);
     out_host[2] = h[2] / (double)n_points;
+    return DYF_OK;
+}
+
+// the engine-owned buffers of dyf_trajectory_metrics; the device must be idle with respect to them (dyf_engine_destroy, or a regrow
+// after the events below have been waited for)
+static void traj_release(dyf_engine* e) {
+    if (e->traj_pending) (void)hipEventSynchronize(e->traj_done);
+    if (e->traj_tab) (void)hipFree((void*)e->traj_tab);
+    if (e->traj_stage) (void)hipHostFree((void*)e->traj_stage);
+    if (e->traj_partials) (void)hipFree(e->traj_partials);
+    if (e->traj_uploaded) (void)hipEventDestroy(e->traj_uploaded);
+    if (e->traj_done) (void)hipEventDestroy(e->traj_done);
+    e->traj_tab = e->traj_stage = nullptr;
+    e->traj_partials = nullptr;
+    e->traj_uploaded = e->traj_done = nullptr;
+    e->traj_cap = 0;
+    e->traj_partials_count = 0;
+    e->traj_pending = false;
+}
+
+dyf_status dyf_trajectory_metrics(dyf_engine* e, int32_t n_segments, const float* const* preds_dev, const float* const* targets_dev,
+                                  int32_t n_members, int64_t n_points, int64_t member_stride, double* out_dev, double* accum_dev,
+                                  void* stream) {
+    if (!e || !preds_dev || !targets_dev || !out_dev) return fail(e, DYF_ERR_INVALID_ARGUMENT, "null argument");
+    if (n_segments < 1 || n_segments > 65535) return fail(e, DYF_ERR_INVALID_ARGUMENT, "n_segments outside [1, 65535]");
+    if (n_members < 1 || n_members > 15360) return fail(e, DYF_ERR_INVALID_ARGUMENT, "n_members outside [1, 15360]");
+    if (n_points < 1) return fail(e, DYF_ERR_INVALID_ARGUMENT, "n_points must be positive");
+    if (member_stride < n_points) return fail(e, DYF_ERR_INVALID_ARGUMENT, "member_stride must be at least n_points");
+    for (int32_t s = 0; s < n_segments; ++s)
+        if (!preds_dev[s] || !targets_dev[s]) return fail(e, DYF_ERR_INVALID_ARGUMENT, "null segment pointer");
+    const long long blocks = trajectory_metrics_blocks(n_members, n_points);
+    if (blocks < 1 || blocks > 0xffffffLL) return fail(e, DYF_ERR_INVALID_ARGUMENT, "n_points beyond 2^24 - 1 workgroups per segment");
+    HIP_TRY(e, hipSetDevice(e->cfg.device));
+    hipStream_t st = (hipStream_t)stream;
+    if (!e->traj_uploaded) {
+        HIP_TRY(e, hipEventCreateWithFlags(&e->traj_uploaded, hipEventDisableTiming));
+        HIP_TRY(e, hipEventCreateWithFlags(&e->traj_done, hipEventDisableTiming));
+    }
+    const size_t need = (size_t)n_segments * (size_t)blocks * 3;
+    if (n_segments > e->traj_cap || need > e->traj_partials_count) {  // grow: nothing of an earlier call may still read the old buffers
+        if (e->traj_pending) HIP_TRY(e, hipEventSynchronize(e->traj_done));
+        if (n_segments > e->traj_cap) {
+            if (e->traj_tab) (void)hipFree((void*)e->traj_tab);
+            if (e->traj_stage) (void)hipHostFree((void*)e->traj_stage);
+            e->traj_tab = e->traj_stage = nullptr;
+            e->traj_cap = 0;
+            const size_t bytes = (size_t)2 * n_segments * sizeof(float*);
+            HIP_TRY(e, hipMalloc((void**)&e->traj_tab, bytes));
+            HIP_TRY(e, hipHostMalloc((void**)&e->traj_stage, bytes));
+            e->traj_cap = n_segments;
+        }
+        if (need > e->traj_partials_count) {
+            if (e->traj_partials) (void)hipFree(e->traj_partials);
+            e->traj_partials = nullptr;
+            e->traj_partials_count = 0;
+            HIP_TRY(e, hipMalloc((void**)&e->traj_partials, need * sizeof(double)));
+            e->traj_partials_count = need;
+        }
+    }
+    if (e->traj_pending) {
+        HIP_TRY(e, hipEventSynchronize(e->traj_uploaded));   // the staging is free again once the previous table has been copied out of it
+        HIP_TRY(e, hipStreamWaitEvent(st, e->traj_done, 0));  // table and partials: behind the previous call, whichever stream it ran on
+    }
+    for (int32_t s = 0; s < n_segments; ++s) {
+        e->traj_stage[s] = preds_dev[s];
+        e->traj_stage[n_segments + s] = targets_dev[s];
+    }
+    HIP_TRY(e, hipMemcpyAsync((void*)e->traj_tab, (const void*)e->traj_stage, (size_t)2 * n_segments * sizeof(float*), hipMemcpyHostToDevice, st));
+    HIP_TRY(e, hipEventRecord(e->traj_uploaded, st));
+    const hipError_t le = launch_trajectory_metrics(e->traj_tab, e->traj_tab + n_segments, n_segments, n_members, n_points, member_stride,
+                                                    e->traj_partials, out_dev, accum_dev, st);
+    const hipError_t re = hipEventRecord(e->traj_done, st);  // recorded even behind a failed launch: traj_uploaded is pending
+    e->traj_pending = true;
+    HIP_TRY(e, le);
+    HIP_TRY(e, re);
     return DYF_OK;
 }
 

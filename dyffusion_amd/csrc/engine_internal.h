@@ -146,6 +146,16 @@ struct dyf_engine {
     hipStream_t cap_stream = nullptr;  // capture never runs on the caller's (possibly legacy default) stream
     // dyf_time_layer_in_rollout: events recorded around the conv of block prof_layer while a rollout runs eagerly
     double* metric_sums = nullptr;  // dyf_ensemble_metrics accumulators (device)
+    // dyf_trajectory_metrics: device table [2][traj_cap] of segment pointers (predictions, then targets), its pinned host staging, the
+    // per-workgroup partial sums (grown on demand), and two events: traj_uploaded behind the table's copy (the host waits for it before
+    // it rewrites the staging), traj_done behind the second launch (the next call's stream waits for it before it rewrites the table)
+    const float** traj_tab = nullptr;
+    const float** traj_stage = nullptr;
+    int traj_cap = 0;
+    double* traj_partials = nullptr;
+    size_t traj_partials_count = 0;
+    hipEvent_t traj_uploaded = nullptr, traj_done = nullptr;
+    bool traj_pending = false;  // the two events have been recorded
     int prof_layer = -1;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_ev;
     std::vector<int> prof_rows;

@@ -198,6 +198,14 @@ constexpr int CRITERION_MAX_BLOCKS = 2048;
 hipError_t launch_criterion_sum_det(const float* p, const float* t, long long count, int kind, double* partials, double* sum, hipStream_t s);
 hipError_t launch_ensemble_metrics(const float* preds, const float* targets, int n_members, long long n_points, double* sums,
                                    hipStream_t s);
+// the same per-point quantities per segment (dyf_trajectory_metrics), without atomics: launch 1 writes one {se, var, crps} partial per
+// workgroup to partials[n_segments][trajectory_metrics_blocks()][3], launch 2 (one wave per segment) adds a segment's partials in a
+// fixed order and writes out[3][n_segments] = {mse, ssr, crps} (accum[3][n_segments] += out when given).  preds_tab / targets_tab:
+// device arrays of n_segments pointers; member n of segment s starts at preds_tab[s] + n * member_stride.
+long long trajectory_metrics_blocks(int n_members, long long n_points);  // workgroups per segment; 0 = n_members beyond 15 360
+hipError_t launch_trajectory_metrics(const float* const* preds_tab, const float* const* targets_tab, int n_segments, int n_members,
+                                     long long n_points, long long member_stride, double* partials, double* out, double* accum,
+                                     hipStream_t s);
 
 // dyf_sample_gather: all-gather receive layout [world][slots][nb][row floats] -> [slots][total_rows][row] in global row order;
 // rank r owns the contiguous block of rows shard(r) (the first total_rows % world ranks one extra), its padding rows are dropped

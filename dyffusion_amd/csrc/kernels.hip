@@ -1714,6 +1714,203 @@ hipError_t launch_ensemble_metrics(const float* preds, const float* targets, int
     return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------------------ trajectory metrics
+// The per-point quantities of ensemble_metrics_kernel per SEGMENT (dyf_trajectory_metrics: one segment = one horizon step of a test
+// trajectory, evaluate_ensemble_prediction(..., mean_over_samples=False), evaluation.py:44-45,92-96,112), with no atomics: blockIdx.y
+// is the segment, a workgroup's four wave sums meet in LDS and leave, added in wave order, as partials[segment][blockIdx.x][3];
+// trajectory_metrics_finish_kernel adds a segment's partials.  A segment's sums depend on its own points alone (the split into
+// workgroups is a function of n_members and n_points), so they are the same bits whichever segments share the call.  Member n of a
+// segment starts n * member_stride elements behind the segment's pointer; the pointers are only 4-byte aligned (an (N, S, ...) tensor
+// with an odd n_points), so every load is a dword, consecutive lanes on consecutive addresses.
+__device__ __forceinline__ void trajectory_block_sum(float se, float var, float crps, double* wsum /* LDS, [4][3] */, double* partial) {
+    double d0 = se, d1 = var, d2 = crps;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        d0 += __shfl_xor(d0, off, 64);
+        d1 += __shfl_xor(d1, off, 64);
+        d2 += __shfl_xor(d2, off, 64);
+    }
+    const int tid = threadIdx.x;
+    __syncthreads();  // wsum lies over the staged members: every wave is done reading them
+    if ((tid & 63) == 0) {
+        wsum[(tid >> 6) * 3 + 0] = d0;
+        wsum[(tid >> 6) * 3 + 1] = d1;
+        wsum[(tid >> 6) * 3 + 2] = d2;
+    }
+    __syncthreads();
+    if (tid < 3) partial[tid] = ((wsum[tid] + wsum[3 + tid]) + wsum[6 + tid]) + wsum[9 + tid];
+}
+
+__global__ __launch_bounds__(256) void trajectory_metrics_kernel(const float* const* preds_tab, const float* const* targets_tab,
+                                                                 int n_members, long long n_points, long long member_stride,
+                                                                 double* partials) {
+    extern __shared__ double traj_lds[];  // [n_members][256] floats; the first 96 bytes again for the four wave sums (64 members fill 64 KB)
+    float* xs = (float*)traj_lds;
+    const float* preds = preds_tab[blockIdx.y];
+    const float* targets = targets_tab[blockIdx.y];
+    const int tid = threadIdx.x;
+    const long long p = (long long)blockIdx.x * 256 + tid;
+    float se = 0.0f, var = 0.0f, crps = 0.0f;
+    if (p < n_points) {
+        const float y = targets[p];
+        float sum = 0.0f, sabs = 0.0f;
+        for (int n = 0; n < n_members; ++n) {
+            const float x = preds[(long long)n * member_stride + p];
+            xs[n * 256 + tid] = x;
+            sum += x;
+            sabs += fabsf(x - y);
+        }
+        const float inv = 1.0f / (float)n_members;
+        const float mean = sum * inv;
+        float m2 = 0.0f, pair = 0.0f;
+        for (int n = 0; n < n_members; ++n) {
+            const float x = xs[n * 256 + tid];
+            m2 += (x - mean) * (x - mean);
+            for (int m = n + 1; m < n_members; ++m) pair += fabsf(x - xs[m * 256 + tid]);
+        }
+        se = (mean - y) * (mean - y);
+        var = m2 * inv;
+        crps = sabs * inv - pair * inv * inv;
+    }
+    trajectory_block_sum(se, var, crps, traj_lds, partials + ((long long)blockIdx.y * gridDim.x + blockIdx.x) * 3);
+}
+
+// more than 64 members: the split of ensemble_metrics_tiled_kernel (P points per workgroup, 256 / P threads share a point)
+__global__ __launch_bounds__(256) void trajectory_metrics_tiled_kernel(const float* const* preds_tab, const float* const* targets_tab,
+                                                                       int n_members, long long n_points, long long member_stride,
+                                                                       double* partials, int P) {
+    extern __shared__ double traj_lds[];  // floats: [n_members][P] members (the first 96 bytes again for the wave sums), then [2][256] partials
+    float* xs = (float*)traj_lds;
+    float* red = xs + (size_t)n_members * P;
+    const float* preds = preds_tab[blockIdx.y];
+    const float* targets = targets_tab[blockIdx.y];
+    const int tid = threadIdx.x, T = 256 / P;
+    const int pi = tid % P, sh = tid / P;
+    const long long p0 = (long long)blockIdx.x * P, p = p0 + pi;
+    const bool live = p < n_points;
+    for (int i = tid; i < n_members * P; i += 256) {  // staging: consecutive threads -> consecutive points of one member
+        const int n = i / P, q = i - n * P;
+        xs[i] = p0 + q < n_points ? preds[(long long)n * member_stride + p0 + q] : 0.0f;
+    }
+    __syncthreads();
+    const float y = live ? targets[p] : 0.0f;
+    float sum = 0.0f, sabs = 0.0f;
+    for (int n = sh; n < n_members; n += T) {
+        const float x = xs[n * P + pi];
+        sum += x;
+        sabs += fabsf(x - y);
+    }
+    red[tid] = sum;
+    red[256 + tid] = sabs;
+    __syncthreads();
+    float tsum = 0.0f, tabs = 0.0f;
+    for (int k = 0; k < T; ++k) {  // every share adds the T partials in the same order: all hold the same mean
+        tsum += red[k * P + pi];
+        tabs += red[256 + k * P + pi];
+    }
+    const float inv = 1.0f / (float)n_members;
+    const float mean = tsum * inv;
+    __syncthreads();
+    float m2 = 0.0f;
+    double pair = 0.0;  // up to N^2 / 2 terms per point: rows in fp32, the sum of rows in fp64
+    for (int n = sh; n < n_members; n += T) {
+        const float x = xs[n * P + pi];
+        m2 += (x - mean) * (x - mean);
+        float row = 0.0f;
+        for (int m = n + 1; m < n_members; ++m) row += fabsf(x - xs[m * P + pi]);
+        pair += (double)row;
+    }
+    red[tid] = m2;
+    red[256 + tid] = (float)pair;
+    __syncthreads();
+    float se = 0.0f, var = 0.0f, crps = 0.0f;
+    if (live && sh == 0) {
+        float tm2 = 0.0f, tpair = 0.0f;
+        for (int k = 0; k < T; ++k) {
+            tm2 += red[k * P + pi];
+            tpair += red[256 + k * P + pi];
+        }
+        se = (mean - y) * (mean - y);
+        var = tm2 * inv;
+        crps = tabs * inv - tpair * inv * inv;
+    }
+    trajectory_block_sum(se, var, crps, traj_lds, partials + ((long long)blockIdx.y * gridDim.x + blockIdx.x) * 3);
+}
+
+// One wave per segment: lane l adds the partials l, l + 64, ... in order, then lane 0 the lanes' sums in lane order; division as
+// dyf_ensemble_metrics does it on the host.  accum is read and written by this wave alone (ordered by the stream).
+__global__ __launch_bounds__(64) void trajectory_metrics_finish_kernel(const double* partials, long long n_blocks, long long n_points,
+                                                                       int n_segments, double* out, double* accum) {
+    __shared__ double lane_sum[3][64];
+    const int seg = blockIdx.x, lane = threadIdx.x;
+    const double* part = partials + (long long)seg * n_blocks * 3;
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0;
+    for (long long i = lane; i < n_blocks; i += 64) {
+        a0 += part[i * 3 + 0];
+        a1 += part[i * 3 + 1];
+        a2 += part[i * 3 + 2];
+    }
+    lane_sum[0][lane] = a0;
+    lane_sum[1][lane] = a1;
+    lane_sum[2][lane] = a2;
+    __syncthreads();
+    if (lane == 0) {
+        double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+        for (int l = 0; l < 64; ++l) {
+            s0 += lane_sum[0][l];
+            s1 += lane_sum[1][l];
+            s2 += lane_sum[2][l];
+        }
+        const double mse = s0 / (double)n_points;
+        const double ssr = sqrt(s1 / (double)n_points) / sqrt(mse);
+        const double crps = s2 / (double)n_points;
+        out[seg] = mse;
+        out[(long long)n_segments + seg] = ssr;
+        out[2LL * n_segments + seg] = crps;
+        if (accum) {
+            accum[seg] += mse;
+            accum[(long long)n_segments + seg] += ssr;
+            accum[2LL * n_segments + seg] += crps;
+        }
+    }
+}
+
+// points per workgroup: 256 up to 64 members, beyond that the largest power of two with n_members * P floats <= 60 KB (0 = none)
+static int trajectory_metrics_tile(int n_members) {
+    if (n_members <= 64) return 256;
+    int P = 128;
+    while (P > 1 && (size_t)n_members * P * sizeof(float) > 60 * 1024) P >>= 1;
+    return (size_t)n_members * P * sizeof(float) > 60 * 1024 ? 0 : P;
+}
+
+long long trajectory_metrics_blocks(int n_members, long long n_points) {
+    const int P = trajectory_metrics_tile(n_members);
+    return P ? (n_points + P - 1) / P : 0;
+}
+
+hipError_t launch_trajectory_metrics(const float* const* preds_tab, const float* const* targets_tab, int n_segments, int n_members,
+                                     long long n_points, long long member_stride, double* partials, double* out, double* accum,
+                                     hipStream_t s) {
+    const int P = trajectory_metrics_tile(n_members);
+    const long long blocks = trajectory_metrics_blocks(n_members, n_points);
+    // 256 * blocks threads along x stay below 2^32
+    if (P == 0 || blocks < 1 || blocks > 0xffffffLL || n_segments < 1 || n_segments > 65535) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)blocks, (unsigned)n_segments);
+    if (n_members > 64) {
+        const size_t lds = ((size_t)n_members * P + 2 * 256) * sizeof(float);
+        hipLaunchKernelGGL(trajectory_metrics_tiled_kernel, grid, dim3(256), lds, s, preds_tab, targets_tab, n_members, n_points,
+                           member_stride, partials, P);
+    } else {
+        hipLaunchKernelGGL(trajectory_metrics_kernel, grid, dim3(256), (size_t)n_members * 256 * sizeof(float), s, preds_tab,
+                           targets_tab, n_members, n_points, member_stride, partials);
+    }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(trajectory_metrics_finish_kernel, dim3((unsigned)n_segments), dim3(64), 0, s, partials, blocks, n_points,
+                       n_segments, out, accum);
+    return hipGetLastError();
+}
+
 // ------------------------------------------------------------------------------------------------ exchange unpack
 __global__ __launch_bounds__(256) void gather_unpack_kernel(const float4* recv, float4* out, int world, int slots, int nb, int total_rows,
                                                             long long row4) {

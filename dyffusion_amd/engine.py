@@ -498,6 +498,58 @@ class HipEngine:
                                                    self._stream()))
         return out[0], out[1], out[2]
 
+    def trajectory_metrics(self, preds, targets, accum: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Per-segment (mse, ssr, crps) on the device (dyf_trajectory_metrics): the curves of the reference's
+        `evaluate_ensemble_prediction(..., mean_over_samples=False)`.  `preds` is a list of T contiguous (N, ...) tensors with
+        `targets` the list of the T matching (...) tensors, or one (N, S, ...) tensor with `targets` (S, ...): that form is read in
+        place, member stride S * points.  Non-contiguous or non-fp32 inputs are made contiguous fp32 first.  Returns a float64
+        device tensor (3, T), rows mse / ssr / crps; `accum` (float64, (3, T), on the device) += it.  No synchronisation: the
+        two launches are enqueued on the current stream."""
+        if torch.is_tensor(preds) != torch.is_tensor(targets):
+            raise ValueError("preds and targets must both be lists or both be tensors")
+        if torch.is_tensor(preds):
+            if preds.dim() < 2 or preds.shape[1:] != targets.shape:
+                raise ValueError(f"predictions.shape[1:] ({tuple(preds.shape[1:])}) != targets.shape ({tuple(targets.shape)})")
+            preds, targets = preds.contiguous().float(), targets.contiguous().float()
+            n, nseg = preds.shape[0], preds.shape[1]
+            if n < 1 or nseg < 1 or targets.numel() < 1:
+                raise ValueError("empty predictions")
+            points = targets.numel() // nseg
+            stride = nseg * points
+            p_ptrs = [preds.data_ptr() + 4 * s * points for s in range(nseg)]
+            t_ptrs = [targets.data_ptr() + 4 * s * points for s in range(nseg)]
+            keep = (preds, targets)
+        else:
+            preds, targets = list(preds), list(targets)
+            if len(preds) != len(targets):
+                raise ValueError(f"{len(preds)} prediction segments but {len(targets)} target segments")
+            nseg = len(preds)
+            if nseg < 1:
+                raise ValueError("no segments")
+            for p, t in zip(preds, targets):
+                if p.dim() < 1 or p.shape[1:] != t.shape:
+                    raise ValueError(f"predictions.shape[1:] ({tuple(p.shape[1:])}) != targets.shape ({tuple(t.shape)})")
+                if p.shape != preds[0].shape:
+                    raise ValueError(f"segments differ in shape: {tuple(p.shape)} and {tuple(preds[0].shape)}")
+            preds = [p.contiguous().float() for p in preds]
+            targets = [t.contiguous().float() for t in targets]
+            n, points = preds[0].shape[0], targets[0].numel()
+            stride = points
+            p_ptrs, t_ptrs = [p.data_ptr() for p in preds], [t.data_ptr() for t in targets]
+            keep = (preds, targets)
+        dev = keep[0].device if torch.is_tensor(keep[0]) else keep[0][0].device
+        if dev.type != "cuda":
+            raise ValueError("trajectory_metrics works on GPU tensors (the HIP engine computes them)")
+        if accum is not None and (accum.dtype != torch.float64 or tuple(accum.shape) != (3, nseg) or not accum.is_contiguous()
+                                  or accum.device != dev):
+            raise ValueError(f"accum must be a contiguous float64 (3, {nseg}) tensor on {dev}")
+        out = torch.empty(3, nseg, dtype=torch.float64, device=dev)
+        self._check(self._lib.dyf_trajectory_metrics(self._h, nseg, (C.c_void_p * nseg)(*p_ptrs), (C.c_void_p * nseg)(*t_ptrs), n,
+                                                     points, stride, out.data_ptr(), accum.data_ptr() if accum is not None else None,
+                                                     self._stream()))
+        del keep  # held until the launches were enqueued; the caching allocator orders any reuse behind them on this stream
+        return out
+
     def time_layer_in_rollout(self, layer: int, nb: int):
         """(average ms, launches) of decoder block `layer`'s conv over one eagerly launched rollout of the current plan."""
         ms, cnt = C.c_double(), C.c_int32()

@@ -120,7 +120,8 @@ class MultiHorizonForecastingDYffusion(nn.Module):
     time)` and `get_boundary_condition_kwargs(batch, batch_idx, split)` (e.g. built on `PhysicalSystemsBoundaryConditions`)."""
 
     def __init__(self, model: DYffusion, num_predictions: int = 1, window: int = 1, horizon: Optional[int] = None,
-                 autoregressive_steps: int = 0, prediction_horizon: Optional[int] = None, datamodule=None):
+                 autoregressive_steps: int = 0, prediction_horizon: Optional[int] = None, datamodule=None,
+                 datamodule_config: Optional[Dict[str, Any]] = None):
         super().__init__()
         assert autoregressive_steps >= 0, f"Autoregressive steps must be >= 0, but is {autoregressive_steps}"
         if autoregressive_steps > 0:
@@ -131,6 +132,8 @@ class MultiHorizonForecastingDYffusion(nn.Module):
         self.horizon = horizon or model.hparams.timesteps
         self._prediction_horizon = prediction_horizon
         self._datamodule = datamodule
+        self.datamodule_config = dict(datamodule_config or {})
+        self._test_metrics_aggregate = None  # TrajectoryMetricsAccumulator of the physical-systems test epoch (first test_step)
         self._predict_step_outputs = []
 
     # ---- forecasting_multi_horizon.py:45-100
@@ -276,9 +279,26 @@ class MultiHorizonForecastingDYffusion(nn.Module):
         self.__dict__.setdefault("_validation_step_outputs", []).append(results)
         return results
 
+    @property
+    def _physical_systems_test(self) -> bool:  # forecasting_multi_horizon.py:232,263
+        return "PhysicalSystemsBenchmarkDataModule" in self.datamodule_config.get("_target_", "None")
+
     def test_step(self, batch: Dict[str, Any], batch_idx: int = 0, dataloader_idx: int = None, **kwargs):
+        """forecasting_multi_horizon.py:231-260.  For a PhysicalSystemsBenchmarkDataModule every test batch is one instance: its
+        CRPS / SSR / MSE curves over t1..t{prediction_horizon} (`mean_over_samples=False`) are computed on the device and added
+        to the epoch's sums there; the fields are returned but not kept (the reference discards them unused)."""
         results = self.evaluation_step(batch, batch_idx, split="test", **kwargs)
-        self.__dict__.setdefault("_test_step_outputs", []).append(results)
+        if not self._physical_systems_test:
+            self.__dict__.setdefault("_test_step_outputs", []).append(results)
+            return results
+        from .metrics import TrajectoryMetricsAccumulator
+        if self._test_metrics_aggregate is None:
+            self._test_metrics_aggregate = TrajectoryMetricsAccumulator(self.model._engine)
+        timesteps = range(1, self.prediction_horizon + 1)
+        targets = [results[f"t{t}_targets"] for t in timesteps]
+        preds = [results[f"t{t}_preds"] for t in timesteps]
+        preds = [p if p.dim() == y.dim() + 1 else p.unsqueeze(0) for p, y in zip(preds, targets)]  # one member: no ensemble axis
+        self._test_metrics_aggregate.update(preds, targets)
         return results
 
     def _eval_ensemble_predictions(self, outputs, split: str) -> Dict[str, float]:
@@ -303,8 +323,19 @@ class MultiHorizonForecastingDYffusion(nn.Module):
         return self._eval_ensemble_predictions(outs, split="val")
 
     def on_test_epoch_end(self, calc_ensemble_metrics: bool = True) -> Dict[str, float]:
+        """Pooled per-horizon metrics of the kept outputs, or for a PhysicalSystemsBenchmarkDataModule
+        (forecasting_multi_horizon.py:262-279) the instance-averaged curves under `test/{set/}{N}ens_mems/avg/{m}` and
+        `.../t{i}/{m}` (one device-to-host copy), without the pooled ones; {} when no test_step ran since the last call."""
         outs, self.__dict__["_test_step_outputs"] = self.__dict__.get("_test_step_outputs", []), []
-        return self._eval_ensemble_predictions(outs, split="test") if calc_ensemble_metrics else {}
+        if not self._physical_systems_test:
+            return self._eval_ensemble_predictions(outs, split="test") if calc_ensemble_metrics else {}
+        from .metrics import trajectory_metric_keys
+        agg = self._test_metrics_aggregate
+        if agg is None or agg.count == 0:
+            return {}
+        curves = agg.compute()
+        agg.reset()
+        return trajectory_metric_keys(self.ensemble_logging_infix("test"), curves, getattr(self.datamodule, "test_set_name", "") or "")
 
     def predict_step(self, batch: Dict[str, Any], batch_idx: int = 0, dataloader_idx: int = None, **kwargs) -> None:
         results = self.evaluation_step(batch, batch_idx, split="predict", as_numpy=True, **kwargs)

@@ -1,23 +1,34 @@
 """On-device ensemble metrics: the surface of `src/utilities/evaluation.py` and of
 `BaseExperiment._eval_ensemble_predictions` (`_base_experiment.py:617-640`) on GPU tensors, so the forecast stack never
 makes the reference's `.cpu().numpy()` round trip.  The reductions run in `ensemble_metrics_kernel` (kernels.hip) through
-`dyf_ensemble_metrics`; there is no CPU fallback."""
+`dyf_ensemble_metrics`, and per segment (`mean_over_samples=False`, the test epoch of the physical-systems benchmark) in
+`trajectory_metrics_kernel` through `dyf_trajectory_metrics`; there is no CPU fallback."""
 from collections import defaultdict
-from typing import Dict, Optional
+from typing import Dict, Optional, Sequence
 
+import numpy as np
 import torch
 from torch import Tensor
 
 from .engine import HipEngine
 
+METRIC_ROWS = ("mse", "ssr", "crps")  # row order of the (3, T) tensors of HipEngine.trajectory_metrics
 
-def evaluate_ensemble_prediction(predictions: Tensor, targets: Tensor, engine: HipEngine) -> Dict[str, float]:
-    """evaluation.py:10-80 with ensemble_dim=0, mean_over_samples=True: predictions (n_members, n_samples, *),
-    targets (n_samples, *), both on the engine's GPU -> {"ssr", "crps", "mse"}."""
+
+def evaluate_ensemble_prediction(predictions: Tensor, targets: Tensor, engine: HipEngine, mean_over_samples: bool = True,
+                                 also_per_member_metrics: bool = False) -> Dict[str, object]:
+    """evaluation.py:10-80 with ensemble_dim=0: predictions (n_members, n_samples, *), targets (n_samples, *), both on the
+    engine's GPU -> {"ssr", "crps", "mse"}: host floats over all samples, or with `mean_over_samples=False` float64 device
+    tensors of length n_samples (one value per sample, nothing synchronised)."""
+    if also_per_member_metrics:
+        raise NotImplementedError("also_per_member_metrics=True (the reference never passes it)")
     if predictions.shape[1] != targets.shape[0]:
         raise AssertionError(f"predictions.shape[1] ({predictions.shape[1]}) != targets.shape[0] ({targets.shape[0]})")
     if not predictions.is_cuda or not targets.is_cuda:
         raise ValueError("dyffusion_amd.metrics works on GPU tensors (the HIP engine computes them)")
+    if not mean_over_samples:
+        curves = engine.trajectory_metrics(predictions, targets)
+        return {"ssr": curves[1], "crps": curves[2], "mse": curves[0]}
     mse, ssr, crps = engine.ensemble_metrics(predictions, targets)
     return {"ssr": ssr, "crps": crps, "mse": mse}
 
@@ -39,4 +50,55 @@ def eval_ensemble_predictions(results: Dict[str, Tensor], engine: HipEngine, spl
             acc[f"{split}/{infix}avg/{m}"].append(v)
     for k, v in acc.items():
         out[k] = float(sum(v) / len(v))
+    return out
+
+
+class TrajectoryMetricsAccumulator:
+    """The test epoch of a PhysicalSystemsBenchmarkDataModule (forecasting_multi_horizon.py:231-279): every test instance gives
+    the curves mse / ssr / crps over its T horizon steps, the epoch reports their mean over instances.  The sum of the curves
+    stays on the device ((3, T) float64, added to by the kernel itself); `compute()` makes the only device-to-host copy."""
+
+    def __init__(self, engine: HipEngine):
+        self._engine = engine
+        self.reset()
+
+    def reset(self) -> None:
+        self._sum: Optional[Tensor] = None
+        self.count = 0
+
+    def update(self, preds_list: Sequence[Tensor], targets_list: Sequence[Tensor]) -> Tensor:
+        """One instance: T (N, B, C, H, W) forecasts and their T (B, C, H, W) targets -> its (3, T) curves (device, float64)."""
+        preds_list, targets_list = list(preds_list), list(targets_list)
+        if self._sum is not None and len(preds_list) != self._sum.shape[1]:
+            raise ValueError(f"{len(preds_list)} horizon steps, but the accumulated curves have {self._sum.shape[1]}")
+        if self._sum is None:
+            if not preds_list:
+                raise ValueError("no segments")
+            self._sum = torch.zeros(3, len(preds_list), dtype=torch.float64, device=preds_list[0].device)
+        curves = self._engine.trajectory_metrics(preds_list, targets_list, accum=self._sum)
+        self.count += 1
+        return curves
+
+    def compute(self) -> Dict[str, np.ndarray]:
+        """{metric: (T,) float64 array}: the mean over the instances seen since the last reset ({} before the first update)."""
+        if self._sum is None or self.count == 0:
+            return {}
+        mean = self._sum.cpu().numpy() / float(self.count)
+        return {m: mean[i] for i, m in enumerate(METRIC_ROWS)}
+
+
+def trajectory_metric_keys(stem: str, curves: Dict[str, np.ndarray], test_set_name: str = "") -> Dict[str, float]:
+    """What the reference's `on_test_epoch_end` leaves in the logger for a PhysicalSystemsBenchmarkDataModule
+    (forecasting_multi_horizon.py:262-279): `test/{set/}{stem}avg/{m}`, the curve's mean over horizons, and per horizon step
+    `test/{set/}{stem}t{i}/{m}`, i = 1..T (the summary keys of save_arrays_as_line_plot, wandb_callbacks.py:141-146).  `stem` is
+    the ensemble infix (`"{N}ens_mems/"`), `test_set_name` the datamodule's (empty: no `{set/}` level)."""
+    split_name = f"{test_set_name}/" if len(test_set_name) > 0 else ""
+    key_stem = f"test/{split_name}{stem}"
+    out: Dict[str, float] = {}
+    for m, v in curves.items():
+        v = np.asarray(v, dtype=np.float64)
+        out[f"{key_stem}avg/{m}"] = float(v.mean())
+    for m, v in curves.items():
+        for i, y in enumerate(np.asarray(v, dtype=np.float64), start=1):
+            out[f"{key_stem}/t{i}/{m}".replace("//", "/")] = float(y)
     return out

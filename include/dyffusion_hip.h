@@ -290,6 +290,17 @@ dyf_status dyf_sample_gather(dyf_engine* engine, const float* initial_dev, const
 dyf_status dyf_ensemble_metrics(dyf_engine* engine, const float* preds_dev, const float* targets_dev, int32_t n_members,
                                 int64_t n_points, double* out_host, void* stream);   /* n_members <= 15 360: up to 64 members a workgroup stages
                                 * [N][256 points] in LDS; beyond that fewer points per workgroup, several threads per point */
+/* The same three metrics per SEGMENT, on the device: the curves of evaluate_ensemble_prediction(..., mean_over_samples=False)
+ * over a trajectory (N, T, B, C, H, W) with the horizon on the sample axis (forecasting_multi_horizon.py:231-260).  Segment s has
+ * n_members x n_points predictions, member n starting at preds_dev[s] + n * member_stride (elements, member_stride >= n_points:
+ * n_points for one (N, B, C, H, W) stack per horizon, S * n_points for one (N, S, ...) tensor), and n_points targets at
+ * targets_dev[s].  preds_dev / targets_dev are HOST arrays of n_segments device pointers (4-byte alignment suffices); the engine
+ * uploads them.  out_dev (device, [3][n_segments]) receives mse, ssr, crps of every segment; accum_dev (device, [3][n_segments],
+ * or NULL) += out.  Two launches on `stream`, no atomics: a segment's values do not depend on the other segments of the call, and
+ * identical calls give identical bits.  Does NOT synchronise.  n_members in [1, 15360], n_segments in [1, 65535]. */
+dyf_status dyf_trajectory_metrics(dyf_engine* engine, int32_t n_segments, const float* const* preds_dev,
+                                  const float* const* targets_dev, int32_t n_members, int64_t n_points, int64_t member_stride,
+                                  double* out_dev, double* accum_dev, void* stream);
 /* Copy one (NB,C,H,W) field of the sampler's state after the most recent dyf_sample call: what sample_loop returns
  * beside the intermediates (dyffusion.py:424-426): (x0_hat, ., x_s), or (x_s, ., x_interpolated_s_next) when the sampling
  * schedule stops before T-1. */
