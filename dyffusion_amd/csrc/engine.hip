@@ -441,7 +441,7 @@ dyf_status dyf_engine_create(const dyf_engine_config* cfg, dyf_engine** out_engi
     e->fuse_stem = dyf_form_int("DYF_FUSE_STEM", e->fuse_stem) != 0;
     e->pair_interp = dyf_form_int("DYF_PAIR_INTERP", e->pair_interp) != 0;
     e->poison_dec5 = dyf_form_int("DYF_POISON_DEC5", e->poison_dec5) != 0;
-    if (conv_init() != hipSuccess || linattn_fused_init() != hipSuccess || hipStreamCreateWithFlags(&e->cap_stream, hipStreamNonBlocking) != hipSuccess) {
+    if (conv_init() != hipSuccess || linattn_fused_init() != hipSuccess || readout_init() != hipSuccess || hipStreamCreateWithFlags(&e->cap_stream, hipStreamNonBlocking) != hipSuccess) {
         delete e;
         return fail(nullptr, DYF_ERR_HIP, "engine initialisation failed (conv_init / stream create)");
     }

@@ -138,6 +138,8 @@ struct ReadoutArgs {
     const uint4* col_tab;
 };
 hipError_t launch_readout(const ReadoutArgs& a, hipStream_t s);
+// once per process, outside any stream capture: the dynamic-LDS cap of the row-staged body of the DMA form (kernels.hip)
+hipError_t readout_init();
 // fills a.row_tab (oh entries of 32 B) / a.col_tab (ow entries) for the geometry and col_map of `a` (device pointers, writable)
 hipError_t launch_readout_tables(const ReadoutArgs& a, hipStream_t s);
 // readout.0.weight (cin,cout,4,4) -> ReadoutArgs::wgt's order [tap][cin][cout] (the weight upload and the op seam pack with these two)

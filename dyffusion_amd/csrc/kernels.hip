@@ -1165,17 +1165,21 @@ hipError_t launch_readout_tables(const ReadoutArgs& a, hipStream_t s) {
     return hipGetLastError();
 }
 
-// The same arithmetic with the gather staged through LDS by DMA and the tap coordinates from tables.  Measured per paired launch
-// (160 rows): 256 us (register shuffles) -> 247 (DMA staging, two-deep batch pipeline) -> 239 (tap tables).  Tried and slower: a
-// vertical-strip form that stages every input row segment once (2.9x less gather traffic: 284 us) -- the kernel is bound by none
-// of gather bytes, shuffles or latency alone but by the LDS pipe serving 64 fragment reads per 16 pixels for an MFMA whose 16
-// result rows hold 3 output channels.  readout_mfma_kernel loads with a coalesced lane map (a quad of
-// lanes = 64 contiguous bytes of one pixel) and moves every 16-byte piece to its MFMA lane with four ds_bpermute: 128 shuffles
-// per 16 pixels, and the LDS pipe -- not the gather -- sets its time.  Here `buffer_load ... lds` writes the quads straight into
-// a per-wave staging area (lane i fetches piece (i & 3) ^ (pixel & 3) of pixel i >> 2 into slot i: the swizzle keeps the
-// fragment reads conflict-free) and the MFMA lane (pixel p, k-group g) reads its operand back with ONE ds_read_b128 from slot
-// 4p + (g ^ (p & 3)).  Taps outside the image get the out-of-range offset (DMA writes zeros).  Only the 4 non-zero rows of the
-// weight fragments are kept in LDS (8 KB + 4 x 8 KB staging per workgroup: four workgroups per CU as before).
+// The DMA form: the same arithmetic as readout_mfma_kernel with the tap coordinates from tables and the decoder tensor brought
+// into LDS by `buffer_load ... lds`.  It has two bodies that compute the same words (tests/test_gpu_readout_rows.py); launch_readout
+// notes the form readout_dma_kernel for both, and `+rows` / `+gather` beside it.
+//   GATHER BODY (this kernel; DYF_READOUT_ROWS=0, and stored rows wider than the rows body's LDS plan): per output pixel, 16 taps x
+//   128 B gathered into a per-wave staging area (lane i fetches piece (i & 3) ^ (pixel & 3) of pixel i >> 2 into slot i: the swizzle
+//   keeps the fragment reads conflict-free; the MFMA lane (pixel p, k-group g) reads its operand back with ONE ds_read_b128 from slot
+//   4p + (g ^ (p & 3))), one MFMA pair per tap whose 16 result rows hold <= 4 output channels.  Taps outside the image get the
+//   out-of-range offset (DMA writes zeros).  8 KB of weight rows + 4 x 8 KB staging per workgroup, four workgroups per CU.  At the NS
+//   geometry it gathers 19 MB per image from a 3.4 MB tensor and is bound by the LDS pipe serving 64 fragment reads per 16 pixels:
+//   240 us per paired 160-row launch, 124 us per 80 rows.  A vertical-strip variant that gathered every input row segment once PER
+//   OUTPUT PIXEL STRIP (284 us) still contracted per output pixel and tap.
+//   ROWS BODY (readout_dma_rows_kernel below, the default): the contraction depends on the decoder pixel and the tap only, so every
+//   decoder row is staged once per band of output rows and contracted once per pixel and kernel row (4 MFMA pairs per 16 decoder
+//   pixels instead of 16 per 16 output pixels), and the 16 products of an output pixel are blended from LDS in the gather body's
+//   order.  One coalesced pass over the tensor (plus the rows neighbouring bands share): 178 / 88 us for the same launches.
 __global__ __launch_bounds__(256, 4) void readout_dma_kernel(ReadoutArgs a, int groups_per_wave) {
 #if defined(__HIP_DEVICE_COMPILE__)
     extern __shared__ __attribute__((aligned(16))) char rd_smem[];
@@ -1284,6 +1288,233 @@ __global__ __launch_bounds__(256, 4) void readout_dma_kernel(ReadoutArgs a, int 
 #endif
 }
 
+// ROWS BODY of the readout_dma_kernel form: the same numbers, word for word, without the per-output-pixel gather.  The per-tap
+// contraction d = MFMA(w_tap, x_pixel) of the gather body depends on the decoder pixel and the tap only, so here every decoder row
+// is staged ONCE per band (whole rows by `buffer_load ... lds`, 1 KB tiles of 8 pixels, swizzled) and contracted ONCE per pixel: for
+// kernel row kh the four kw taps are stacked into the 16 rows of one A fragment (row 4 kw + c), so one MFMA pair per 16 pixels
+// leaves z[pixel p][kh][kw = kg][c = 0..3] in lane (p, kg) -- the same dot products by the same instruction over the same K order.
+// Wave w contracts the 16-pixel groups w and w + 4 for all four kh (8 A fragments in registers): every fragment is read once.
+// A workgroup owns one image x one band of `band` output rows (<= RR_MAXQ * 256 pixels, partial sums in registers) and streams the
+// band's decoder rows in DESCENDING order: the input rows of kh = 0..3 of an output row never increase (tests/
+// test_readout_rows_premise.py), so blending row by row, kh ascending inside a row, IS the gather body's tap order
+// kh = 0..3, kw = 0..3.  A tap with valid offsets is blended whatever its weight; a tap at an invalid column is fmaf(0, 0, out) as in
+// the gather body; invalid rows below the image (a suffix of kh) are one fmaf(0, 0, out) after the stream (it can only turn -0
+// into +0, and repeating it changes nothing); invalid rows above it come first, when out is still +0.
+// LDS: z [4 kh][4 kw][16 G columns] float4 = 4 G KB (G = 16-pixel groups of a stored row) + 3 staging buffers of 2 G tiles of
+// 1 KB (one tile = one wave's DMA instruction; wave w issues tiles w, w + 4, ..): 28 + 42 = 70 KB at the NS compact width 104
+// (G = 7), two workgroups per CU; rows k + 1 and k + 2 are in flight while row k is contracted and blended.  80 KB at most:
+// stored rows of up to 128 columns (launch_readout sends wider ones to the gather body); readout_init raises the kernel's
+// dynamic-LDS cap once per process.  The workgroups of a launch all do the same work and two are resident per CU, so the launch
+// takes whole rounds of 512: launch_readout picks the band that minimises rounds x decoder rows per band (readout_rows_band).
+// Resources (gfx950, -Rpass-analysis=kernel-resource-usage): 236 VGPRs + 12 AGPRs, no scratch, 70 KB of LDS at the NS width: two
+// workgroups (8 waves) per CU.
+#define RR_MAXQ 4
+#define RR_NOCOL 0xFFFFFFFFu
+#define RR_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
+// Every LDS access behind the first DMA is an asm statement that waits for itself: the compiler puts a vmcnt(0) in front of an LDS
+// read it can see while an LDS-DMA is pending (it cannot tell the buffers apart), which would drain the row in flight.
+typedef __attribute__((ext_vector_type(4))) unsigned ro_u32x4;
+// both K halves of the fragments of two 16-pixel groups
+__device__ __forceinline__ void rr_read_frags(unsigned a0, unsigned a1, unsigned b0, unsigned b1, ro_u32x4& x0, ro_u32x4& x1, ro_u32x4& y0, ro_u32x4& y1) {
+    asm volatile("ds_read_b128 %0, %4\n\tds_read_b128 %1, %5\n\tds_read_b128 %2, %6\n\tds_read_b128 %3, %7\n\ts_waitcnt lgkmcnt(0)"
+                 : "=&v"(x0), "=&v"(x1), "=&v"(y0), "=&v"(y1) : "v"(a0), "v"(a1), "v"(b0), "v"(b1) : "memory");
+}
+__device__ __forceinline__ void rr_read_z4(unsigned a0, unsigned a1, unsigned a2, unsigned a3, ro_f32x4& z0, ro_f32x4& z1, ro_f32x4& z2, ro_f32x4& z3) {
+    asm volatile("ds_read_b128 %0, %4\n\tds_read_b128 %1, %5\n\tds_read_b128 %2, %6\n\tds_read_b128 %3, %7\n\ts_waitcnt lgkmcnt(0)"
+                 : "=&v"(z0), "=&v"(z1), "=&v"(z2), "=&v"(z3) : "v"(a0), "v"(a1), "v"(a2), "v"(a3) : "memory");
+}
+__device__ __forceinline__ void rr_write_z(unsigned addr, ro_f32x4 d) { asm volatile("ds_write_b128 %0, %1" : : "v"(addr), "v"(d) : "memory"); }
+
+__global__ __launch_bounds__(256) void readout_dma_rows_kernel(ReadoutArgs a, int band, int nbands, int G) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    extern __shared__ __attribute__((aligned(16))) char rr_smem[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int p = lane & 15, kg = lane >> 4;
+    const int n = (int)blockIdx.x / nbands, oy0 = ((int)blockIdx.x - n * nbands) * band;
+    const int rows_here = (a.oh - oy0 < band ? a.oh - oy0 : band);
+    const int rowbytes = a.iw_store * 128, WC = G * 16;
+    const unsigned z0 = (unsigned)(size_t)(__attribute__((address_space(3))) char*)rr_smem;  // LDS byte addresses
+    const unsigned stage0 = z0 + (unsigned)(G * 4096);
+    char* stage = rr_smem + G * 4096;
+    const int stage_sz = G * 2048;
+    const int tiles = (a.iw_store + 7) / 8;                            // 1 KB tiles of a stored row (<= 2 G)
+    const int ntile = wave < tiles ? (tiles - wave + 3) / 4 : 0;     // DMA instructions of this wave per row (<= 4)
+    // A fragments of kernel row kh: lane (m = 4 kw + c, kg) takes lane (c, kg) of tap (kh, kw)
+    uint4 A[4][2];
+#pragma unroll
+    for (int kh = 0; kh < 4; ++kh)
+#pragma unroll
+        for (int h = 0; h < 2; ++h) A[kh][h] = ((const uint4*)a.wfrag)[((kh * 4 + (p >> 2)) * 2 + h) * 64 + kg * 16 + (p & 3)];
+    // decoder rows of the band (byte offsets inside a sample, multiples of rowbytes): lane l looks at output row l (band <= 64)
+    int rhi = -1, rlo = 0x7FFFFFFF;
+    if (lane < rows_here) {
+        const uint4 o = a.row_tab[2 * (oy0 + lane)];
+        const int ov[4] = {(int)o.x, (int)o.y, (int)o.z, (int)o.w};
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (ov[k] >= 0) {
+                rhi = ov[k] > rhi ? ov[k] : rhi;
+                rlo = ov[k] < rlo ? ov[k] : rlo;
+            }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const int h2 = __shfl_xor(rhi, off, 64), l2 = __shfl_xor(rlo, off, 64);
+        rhi = h2 > rhi ? h2 : rhi;
+        rlo = l2 < rlo ? l2 : rlo;
+    }
+    rhi = __builtin_amdgcn_readfirstlane(rhi);
+    rlo = __builtin_amdgcn_readfirstlane(rlo);
+    // this thread's output pixels: pixel tid + 256 q of the band, row-major
+    int ro[RR_MAXQ][4];
+    unsigned zc[RR_MAXQ][4];  // byte offset of the stored column inside a z line, or RR_NOCOL
+    float rw[RR_MAXQ][4], cw[RR_MAXQ][4], out[RR_MAXQ][4];
+    const int npix = rows_here * a.ow;
+#pragma unroll
+    for (int q = 0; q < RR_MAXQ; ++q) {
+        const int pix = tid + 256 * q;
+        const bool ok = pix < npix;
+        const int oyl = ok ? pix / a.ow : 0, ox = ok ? pix - oyl * a.ow : 0;
+        const uint4 rto = a.row_tab[2 * (oy0 + oyl)], rtw = a.row_tab[2 * (oy0 + oyl) + 1];
+        const uint4 cto = a.col_tab[2 * ox], ctw = a.col_tab[2 * ox + 1];
+        ro[q][0] = ok ? (int)rto.x : -2; ro[q][1] = ok ? (int)rto.y : -2; ro[q][2] = ok ? (int)rto.z : -2; ro[q][3] = ok ? (int)rto.w : -2;
+        zc[q][0] = (int)cto.x >= 0 ? cto.x >> 3 : RR_NOCOL; zc[q][1] = (int)cto.y >= 0 ? cto.y >> 3 : RR_NOCOL;  // (js * 128 -> js * 16)
+        zc[q][2] = (int)cto.z >= 0 ? cto.z >> 3 : RR_NOCOL; zc[q][3] = (int)cto.w >= 0 ? cto.w >> 3 : RR_NOCOL;
+        rw[q][0] = __uint_as_float(rtw.x); rw[q][1] = __uint_as_float(rtw.y); rw[q][2] = __uint_as_float(rtw.z); rw[q][3] = __uint_as_float(rtw.w);
+        cw[q][0] = __uint_as_float(ctw.x); cw[q][1] = __uint_as_float(ctw.y); cw[q][2] = __uint_as_float(ctw.z); cw[q][3] = __uint_as_float(ctw.w);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) out[q][c] = 0.0f;
+    }
+    const size_t xbytes = (size_t)a.n * a.ih * a.iw_store * 64 * sizeof(el16_t);
+    const auto rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)a.x, 0, (int)(unsigned)xbytes, 0x00020000);
+    const unsigned nbase = (unsigned)n * (unsigned)a.ih * (unsigned)rowbytes;
+    // staging image: a tile is 8 whole pixels (1 KB, contiguous in x: one DMA instruction reads full 128-B lines), pixel pl's piece c
+    // (16 B, c = 4 half + kg) in slot 8 pl + (c ^ pl) -- the 16 lanes a ds_read_b128 serves together then fall on 16 different slots
+    const int lp = lane >> 3;                 // pixel of its tile this lane FETCHES
+    const unsigned piece_off = (unsigned)(((lane & 7) ^ lp) * 16);
+    const unsigned rd_base = (unsigned)((p >> 3) * 1024 + (p & 7) * 128);
+    const unsigned rd_off0 = rd_base + (unsigned)((kg ^ (p & 7)) * 16), rd_off1 = rd_base + (unsigned)(((4 + kg) ^ (p & 7)) * 16);
+    const unsigned zw = z0 + (unsigned)((kg * WC + p) * 16);  // this lane's D of group 0, kh = 0: z[0][kw = kg][p]
+    // row at byte offset rb (rb < rlo: none, every lane out of range: the waits below count ntile instructions per row) -> buffer b:
+    // tile wave + 4 t; pad pixels of a ragged last tile get the out-of-range offset (DMA writes zeros); the pad tiles of a ragged
+    // last group are never written -- the z columns contracted from them are never blended
+    auto issue = [&](int rb, int b) {
+        for (int t = 0; t < ntile; ++t) {
+            const int tile = wave + 4 * t, px = tile * 8 + lp;
+            const bool ok = rb >= rlo && px < a.iw_store;
+            const unsigned vo = ok ? nbase + (unsigned)rb + (unsigned)(px * 128) + piece_off : 0xFFFFFFFFu;
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)(stage + b * stage_sz + tile * 1024), 16, vo, 0, 0, 0);
+        }
+    };
+    if (rhi >= 0) {
+        issue(rhi, 0);
+        issue(rhi - rowbytes, 1);
+        int b = 0;
+        for (int rb = rhi; rb >= rlo; rb -= rowbytes) {
+            // row rb has landed (this wave's pieces; the barrier makes that every wave's): only the instructions of the next row may be out
+            switch (ntile) {
+                case 0: break;
+                case 1: asm volatile("s_waitcnt vmcnt(1)" ::: "memory"); break;
+                case 2: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
+                case 3: asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); break;
+                default: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
+            }
+            RR_BARRIER();  // ... and every wave is done with z (blend of the previous row) and with the buffer refilled next
+            issue(rb - 2 * rowbytes, b == 0 ? 2 : b - 1);
+            if (wave < G) {
+                const bool two = wave + 4 < G;  // (no second group: its reads repeat the first)
+                const unsigned st = stage0 + (unsigned)(b * stage_sz + wave * 2048), st2 = st + (two ? 4 * 2048u : 0u);
+                ro_u32x4 x0, x1, y0, y1;
+                rr_read_frags(st + rd_off0, st + rd_off1, st2 + rd_off0, st2 + rd_off1, x0, x1, y0, y1);
+#pragma unroll
+                for (int kh = 0; kh < 4; ++kh) {
+                    ro_f32x4 d = {0.0f, 0.0f, 0.0f, 0.0f};
+                    d = DYF_MFMA_16x16x32(__builtin_bit_cast(el16x8_t, A[kh][0]), __builtin_bit_cast(el16x8_t, x0), d, 0, 0, 0);
+                    d = DYF_MFMA_16x16x32(__builtin_bit_cast(el16x8_t, A[kh][1]), __builtin_bit_cast(el16x8_t, x1), d, 0, 0, 0);
+                    rr_write_z(zw + (unsigned)(kh * 4 * WC * 16 + wave * 256), d);
+                }
+                if (two) {
+#pragma unroll
+                    for (int kh = 0; kh < 4; ++kh) {
+                        ro_f32x4 d = {0.0f, 0.0f, 0.0f, 0.0f};
+                        d = DYF_MFMA_16x16x32(__builtin_bit_cast(el16x8_t, A[kh][0]), __builtin_bit_cast(el16x8_t, y0), d, 0, 0, 0);
+                        d = DYF_MFMA_16x16x32(__builtin_bit_cast(el16x8_t, A[kh][1]), __builtin_bit_cast(el16x8_t, y1), d, 0, 0, 0);
+                        rr_write_z(zw + (unsigned)(kh * 4 * WC * 16 + (wave + 4) * 256), d);
+                    }
+                }
+            }
+            RR_BARRIER();
+#pragma unroll
+            for (int q = 0; q < RR_MAXQ; ++q)
+#pragma unroll
+                for (int kh = 0; kh < 4; ++kh)
+                    if (ro[q][kh] == rb) {
+                        ro_f32x4 zv[4];
+                        const unsigned zr = z0 + (unsigned)(kh * 4 * WC * 16);
+                        rr_read_z4(zr + (zc[q][0] != RR_NOCOL ? zc[q][0] : 0u), zr + (unsigned)(WC * 16) + (zc[q][1] != RR_NOCOL ? zc[q][1] : 0u),
+                                   zr + (unsigned)(2 * WC * 16) + (zc[q][2] != RR_NOCOL ? zc[q][2] : 0u),
+                                   zr + (unsigned)(3 * WC * 16) + (zc[q][3] != RR_NOCOL ? zc[q][3] : 0u), zv[0], zv[1], zv[2], zv[3]);
+#pragma unroll
+                        for (int kw = 0; kw < 4; ++kw) {
+                            const bool ok = zc[q][kw] != RR_NOCOL;  // an invalid column: fmaf(0, 0, out), as in the gather body
+                            const float bw = ok ? rw[q][kh] * cw[q][kw] : 0.0f;
+#pragma unroll
+                            for (int c = 0; c < 4; ++c) out[q][c] = fmaf(bw, ok ? zv[kw][c] : 0.0f, out[q][c]);
+                        }
+                    }
+            b = b == 2 ? 0 : b + 1;
+        }
+    }
+    const size_t cs = (size_t)a.oh * a.ow;
+#pragma unroll
+    for (int q = 0; q < RR_MAXQ; ++q) {
+        const int pix = tid + 256 * q;
+        if (pix < npix) {
+            if (ro[q][3] == -1) {  // kernel rows below the image: the gather body's fmaf(0, 0, out)
+#pragma unroll
+                for (int c = 0; c < 4; ++c) out[q][c] = fmaf(0.0f, 0.0f, out[q][c]);
+            }
+            float* o = a.out + ((size_t)n * a.cout * a.oh + oy0) * a.ow + pix;
+            o[0] = out[q][0] + a.bias[0];
+            if (a.cout > 1) o[cs] = out[q][1] + a.bias[1];
+            if (a.cout > 2) o[2 * cs] = out[q][2] + a.bias[2];
+            if (a.cout > 3) o[3 * cs] = out[q][3] + a.bias[3];
+        }
+    }
+#endif
+}
+
+// LDS plan of the rows body for stored rows of iw_store columns: bytes and G (16-pixel groups)
+static size_t readout_rows_lds(int iw_store, int* G) {
+    *G = (iw_store + 15) / 16;
+    return (size_t)*G * 4096 + (size_t)3 * *G * 2048;
+}
+// Output rows per workgroup: at most RR_MAXQ * 256 pixels and 64 rows, at least 8 (or oh); among those the band with the least
+// rounds (of 2 workgroups on each of 256 CUs) x decoder rows streamed per band (band * ih / oh and the rows its ends share with
+// the neighbours) -- 19 rows (12 bands) for the 80-image NS launch, 14 (16 bands) for the paired one
+static int readout_rows_band(const ReadoutArgs& a) {
+    int cap = RR_MAXQ * 256 / a.ow;
+    cap = cap > 64 ? 64 : cap;
+    cap = cap > a.oh ? a.oh : cap;
+    int best = cap;
+    double best_cost = 0.0;
+    for (int band = cap; band >= (cap < 8 ? cap : 8); --band) {
+        const long long wgs = (long long)a.n * ((a.oh + band - 1) / band);
+        const double cost = (double)((wgs + 511) / 512) * ((double)band * a.ih / a.oh + 3.0);
+        if (band == cap || cost < best_cost) {
+            best = band;
+            best_cost = cost;
+        }
+    }
+    return best;
+}
+#define RR_LDS_MAX (80 * 1024)
+
+// Raise the dynamic-LDS cap of the rows body once per process (not legal inside a stream capture).
+hipError_t readout_init() {
+    return hipFuncSetAttribute((const void*)readout_dma_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, RR_LDS_MAX);
+}
+
 hipError_t launch_readout(const ReadoutArgs& a, hipStream_t s) {
     const long long total = (long long)a.n * a.oh * a.ow;
     const bool regw = dyf_form_int("DYF_READOUT_REGW", 1) != 0;
@@ -1301,7 +1532,15 @@ hipError_t launch_readout(const ReadoutArgs& a, hipStream_t s) {
         dyf_form_note(dma ? "readout_dma_kernel" : "readout_mfma_kernel", a.n);
         KernelProf kp(dma ? "readout_dma_kernel" : "readout_mfma_kernel", s,
                       (double)a.n * a.ih * a.iw_store * a.cin * 2.0 + (double)a.n * a.cout * a.oh * a.ow * 4.0);
-        if (dma)
+        // rows body (DYF_READOUT_ROWS=0: the gather body) wherever its LDS plan fits; decided from `a` alone
+        int G = 0;
+        const size_t rows_lds = readout_rows_lds(a.iw_store, &G);
+        const bool rows = dma && dyf_form_int("DYF_READOUT_ROWS", 1) != 0 && rows_lds <= RR_LDS_MAX && a.ow <= RR_MAXQ * 256;
+        if (dma) dyf_form_note(rows ? "readout_dma_kernel+rows" : "readout_dma_kernel+gather", a.n);
+        if (rows) {
+            const int band = readout_rows_band(a), nbands = (a.oh + band - 1) / band;
+            hipLaunchKernelGGL(readout_dma_rows_kernel, dim3((unsigned)(a.n * nbands)), dim3(256), rows_lds, s, a, band, nbands, G);
+        } else if (dma)
             hipLaunchKernelGGL(readout_dma_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 8192 + 4 * 8192, s, a, per);
         else
             hipLaunchKernelGGL(readout_mfma_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 32768, s, a, per);
