@@ -1797,36 +1797,41 @@ static void traj_release(dyf_engine* e) {
     if (e->traj_tab) (void)hipFree((void*)e->traj_tab);
     if (e->traj_stage) (void)hipHostFree((void*)e->traj_stage);
     if (e->traj_partials) (void)hipFree(e->traj_partials);
+    if (e->ens_size_partials) (void)hipFree(e->ens_size_partials);
     if (e->traj_uploaded) (void)hipEventDestroy(e->traj_uploaded);
     if (e->traj_done) (void)hipEventDestroy(e->traj_done);
     e->traj_tab = e->traj_stage = nullptr;
-    e->traj_partials = nullptr;
+    e->traj_partials = e->ens_size_partials = nullptr;
     e->traj_uploaded = e->traj_done = nullptr;
     e->traj_cap = 0;
-    e->traj_partials_count = 0;
+    e->traj_partials_count = e->ens_size_partials_count = 0;
     e->traj_pending = false;
 }
 
-dyf_status dyf_trajectory_metrics(dyf_engine* e, int32_t n_segments, const float* const* preds_dev, const float* const* targets_dev,
-                                  int32_t n_members, int64_t n_points, int64_t member_stride, double* out_dev, double* accum_dev,
-                                  void* stream) {
+// The checks the segment-wise metric entries share; beyond `max_members` the answer is `beyond` (invalid, or unsupported).
+static dyf_status traj_check_args(dyf_engine* e, int32_t n_segments, const float* const* preds_dev, const float* const* targets_dev,
+                                  int32_t n_members, int32_t max_members, dyf_status beyond, int64_t n_points, int64_t member_stride,
+                                  const double* out_dev) {
     if (!e || !preds_dev || !targets_dev || !out_dev) return fail(e, DYF_ERR_INVALID_ARGUMENT, "null argument");
     if (n_segments < 1 || n_segments > 65535) return fail(e, DYF_ERR_INVALID_ARGUMENT, "n_segments outside [1, 65535]");
-    if (n_members < 1 || n_members > 15360) return fail(e, DYF_ERR_INVALID_ARGUMENT, "n_members outside [1, 15360]");
+    if (n_members < 1 || n_members > max_members)
+        return fail(e, n_members < 1 ? DYF_ERR_INVALID_ARGUMENT : beyond, "n_members outside [1, " + std::to_string(max_members) + "]");
     if (n_points < 1) return fail(e, DYF_ERR_INVALID_ARGUMENT, "n_points must be positive");
     if (member_stride < n_points) return fail(e, DYF_ERR_INVALID_ARGUMENT, "member_stride must be at least n_points");
     for (int32_t s = 0; s < n_segments; ++s)
         if (!preds_dev[s] || !targets_dev[s]) return fail(e, DYF_ERR_INVALID_ARGUMENT, "null segment pointer");
-    const long long blocks = trajectory_metrics_blocks(n_members, n_points);
-    if (blocks < 1 || blocks > 0xffffffLL) return fail(e, DYF_ERR_INVALID_ARGUMENT, "n_points beyond 2^24 - 1 workgroups per segment");
-    HIP_TRY(e, hipSetDevice(e->cfg.device));
-    hipStream_t st = (hipStream_t)stream;
+    return DYF_OK;
+}
+
+// Grow the pointer table and `*partials` (to `need` doubles) where they are too small, order this call behind the previous one and
+// upload the segment pointers through the pinned staging; the caller launches on `st` and ends with traj_finish.
+static dyf_status traj_upload(dyf_engine* e, int32_t n_segments, const float* const* preds_dev, const float* const* targets_dev,
+                              double** partials, size_t* partials_count, size_t need, hipStream_t st) {
     if (!e->traj_uploaded) {
         HIP_TRY(e, hipEventCreateWithFlags(&e->traj_uploaded, hipEventDisableTiming));
         HIP_TRY(e, hipEventCreateWithFlags(&e->traj_done, hipEventDisableTiming));
     }
-    const size_t need = (size_t)n_segments * (size_t)blocks * 3;
-    if (n_segments > e->traj_cap || need > e->traj_partials_count) {  // grow: nothing of an earlier call may still read the old buffers
+    if (n_segments > e->traj_cap || need > *partials_count) {  // grow: nothing of an earlier call may still read the old buffers
         if (e->traj_pending) HIP_TRY(e, hipEventSynchronize(e->traj_done));
         if (n_segments > e->traj_cap) {
             if (e->traj_tab) (void)hipFree((void*)e->traj_tab);
@@ -1838,12 +1843,12 @@ dyf_status dyf_trajectory_metrics(dyf_engine* e, int32_t n_segments, const float
             HIP_TRY(e, hipHostMalloc((void**)&e->traj_stage, bytes));
             e->traj_cap = n_segments;
         }
-        if (need > e->traj_partials_count) {
-            if (e->traj_partials) (void)hipFree(e->traj_partials);
-            e->traj_partials = nullptr;
-            e->traj_partials_count = 0;
-            HIP_TRY(e, hipMalloc((void**)&e->traj_partials, need * sizeof(double)));
-            e->traj_partials_count = need;
+        if (need > *partials_count) {
+            if (*partials) (void)hipFree(*partials);
+            *partials = nullptr;
+            *partials_count = 0;
+            HIP_TRY(e, hipMalloc((void**)partials, need * sizeof(double)));
+            *partials_count = need;
         }
     }
     if (e->traj_pending) {
@@ -1856,13 +1861,48 @@ dyf_status dyf_trajectory_metrics(dyf_engine* e, int32_t n_segments, const float
     }
     HIP_TRY(e, hipMemcpyAsync((void*)e->traj_tab, (const void*)e->traj_stage, (size_t)2 * n_segments * sizeof(float*), hipMemcpyHostToDevice, st));
     HIP_TRY(e, hipEventRecord(e->traj_uploaded, st));
-    const hipError_t le = launch_trajectory_metrics(e->traj_tab, e->traj_tab + n_segments, n_segments, n_members, n_points, member_stride,
-                                                    e->traj_partials, out_dev, accum_dev, st);
+    return DYF_OK;
+}
+
+static dyf_status traj_finish(dyf_engine* e, hipError_t launched, hipStream_t st) {
     const hipError_t re = hipEventRecord(e->traj_done, st);  // recorded even behind a failed launch: traj_uploaded is pending
     e->traj_pending = true;
-    HIP_TRY(e, le);
+    HIP_TRY(e, launched);
     HIP_TRY(e, re);
     return DYF_OK;
+}
+
+dyf_status dyf_trajectory_metrics(dyf_engine* e, int32_t n_segments, const float* const* preds_dev, const float* const* targets_dev,
+                                  int32_t n_members, int64_t n_points, int64_t member_stride, double* out_dev, double* accum_dev,
+                                  void* stream) {
+    dyf_status cs = traj_check_args(e, n_segments, preds_dev, targets_dev, n_members, 15360, DYF_ERR_INVALID_ARGUMENT, n_points,
+                                    member_stride, out_dev);
+    if (cs != DYF_OK) return cs;
+    const long long blocks = trajectory_metrics_blocks(n_members, n_points);
+    if (blocks < 1 || blocks > 0xffffffLL) return fail(e, DYF_ERR_INVALID_ARGUMENT, "n_points beyond 2^24 - 1 workgroups per segment");
+    HIP_TRY(e, hipSetDevice(e->cfg.device));
+    hipStream_t st = (hipStream_t)stream;
+    cs = traj_upload(e, n_segments, preds_dev, targets_dev, &e->traj_partials, &e->traj_partials_count,
+                     (size_t)n_segments * (size_t)blocks * 3, st);
+    if (cs != DYF_OK) return cs;
+    return traj_finish(e, launch_trajectory_metrics(e->traj_tab, e->traj_tab + n_segments, n_segments, n_members, n_points, member_stride,
+                                                    e->traj_partials, out_dev, accum_dev, st), st);
+}
+
+dyf_status dyf_ensemble_size_metrics(dyf_engine* e, int32_t n_segments, const float* const* preds_dev, const float* const* targets_dev,
+                                     int32_t n_members, int64_t n_points, int64_t member_stride, double* out_dev, double* accum_dev,
+                                     void* stream) {
+    dyf_status cs = traj_check_args(e, n_segments, preds_dev, targets_dev, n_members, ENSEMBLE_SIZE_MAX_MEMBERS, DYF_ERR_UNSUPPORTED,
+                                    n_points, member_stride, out_dev);
+    if (cs != DYF_OK) return cs;
+    const int groups = ensemble_size_metrics_groups(n_members, n_points);
+    HIP_TRY(e, hipSetDevice(e->cfg.device));
+    hipStream_t st = (hipStream_t)stream;
+    cs = traj_upload(e, n_segments, preds_dev, targets_dev, &e->ens_size_partials, &e->ens_size_partials_count,
+                     (size_t)n_segments * (size_t)groups * (size_t)n_members * 4, st);
+    if (cs != DYF_OK) return cs;
+    return traj_finish(e, launch_ensemble_size_metrics(e->traj_tab, e->traj_tab + n_segments, n_segments, n_members, n_points,
+                                                       member_stride, e->ens_size_partials, out_dev, accum_dev, st), st);
 }
 
 dyf_status dyf_apply_boundary_conditions(dyf_engine* e, const dyf_bc_args* bc, float* preds_dev, void* stream) {

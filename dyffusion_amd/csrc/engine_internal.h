@@ -154,6 +154,8 @@ struct dyf_engine {
     int traj_cap = 0;
     double* traj_partials = nullptr;
     size_t traj_partials_count = 0;
+    double* ens_size_partials = nullptr;  // dyf_ensemble_size_metrics: its own partials, behind the same table, staging and events
+    size_t ens_size_partials_count = 0;
     hipEvent_t traj_uploaded = nullptr, traj_done = nullptr;
     bool traj_pending = false;  // the two events have been recorded
     int prof_layer = -1;

@@ -208,6 +208,15 @@ long long trajectory_metrics_blocks(int n_members, long long n_points);  // work
 hipError_t launch_trajectory_metrics(const float* const* preds_tab, const float* const* targets_tab, int n_segments, int n_members,
                                      long long n_points, long long member_stride, double* partials, double* out, double* accum,
                                      hipStream_t s);
+// the metrics of every prefix predictions[:n], n = 1..n_members, of every segment (dyf_ensemble_size_metrics), without atomics:
+// launch 1 leaves partials[n_segments][ensemble_size_metrics_groups()][n_members][4] (a workgroup walks several tiles), launch 2
+// adds a segment's partials in workgroup order and writes out[4][n_segments][n_members] = {mse, ssr, crps, mse_per_mem}
+// (accum += out when given).  Pointer tables and member_stride as launch_trajectory_metrics.
+constexpr int ENSEMBLE_SIZE_MAX_MEMBERS = 256;
+int ensemble_size_metrics_groups(int n_members, long long n_points);  // workgroups per segment (at most 64); 0 = n_members beyond the limit
+hipError_t launch_ensemble_size_metrics(const float* const* preds_tab, const float* const* targets_tab, int n_segments, int n_members,
+                                        long long n_points, long long member_stride, double* partials, double* out, double* accum,
+                                        hipStream_t s);
 
 // dyf_sample_gather: all-gather receive layout [world][slots][nb][row floats] -> [slots][total_rows][row] in global row order;
 // rank r owns the contiguous block of rows shard(r) (the first total_rows % world ranks one extra), its padding rows are dropped

@@ -2150,6 +2150,169 @@ hipError_t launch_trajectory_metrics(const float* const* preds_tab, const float*
     return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------------------ ensemble-size metrics
+// The metrics of EVERY prefix predictions[:n], n = 1..N, of every segment in one pass (dyf_ensemble_size_metrics:
+// evaluate_ensemble_prediction_for_varying_members, evaluation.py:145-156, and its mse_per_mem).  A thread owns one point and walks
+// the members in storage order with running recurrences in fp32: Welford's mean / M2 (M2 is exactly 0 after one member), the sum of
+// |x - y|, and the pair term, which grows by row_n = sum_{m<n} |x_n - x_m| -- all N prefix scores for the pair work of one.  After
+// member n the point contributes {(mean - y)^2, M2 / n, sabs / n - pair / n^2, (x_n - y)^2} to prefix n.
+//   Staging: members in fours, xs[quad][thread] as float4, so the pair loop reads four members per ds_read_b128 on consecutive
+// 16-byte slots (conflict-free) and is bound by its two VALU operations per pair, not by LDS reads.  A thread reads only what it
+// wrote: the staging needs no barrier.
+//   Reduction: an LDS transpose per quad, not fp64 shuffles per n.  The 16 fp32 values of a quad (4 members x 4 quantities) go to
+// the wave's own [16][68]-float scratch (rows padded by 16 bytes: the ds_read_b128 lane groups meet no bank twice); lane l then
+// adds columns 16 (l & 3) .. + 15 of row l >> 2 in fp64, in column order, two xor-shuffles join the four quarters, and lanes with
+// l & 3 == 0 add the sum to the wave's fp64 accumulator in LDS.  Per quad and lane that is 16 conversions and 18 fp64 additions,
+// against 16 x 6 shuffle steps for the butterfly form.
+//   Tiles: workgroup b of a segment takes the tiles b, b + G, ... with G = ensemble_size_metrics_groups(n_members, n_points), so the
+// partials are [n_segments][G][n_members][4] doubles whatever n_points is; the waves' accumulators are added in wave order, and
+// ensemble_size_metrics_finish_kernel adds a segment's G partials in workgroup order.  Nothing depends on the other segments of the
+// call or on the layout, and there are no atomics.  blockDim.x = 256 up to 64 members, 64 (one wave) beyond.
+constexpr int ENS_SIZE_MAX_GROUPS = 64;     // workgroups per segment
+constexpr int ENS_SIZE_SCRATCH_ROW = 68;    // floats per row of the transpose scratch
+typedef const __attribute__((address_space(1))) float* ens_size_gptr;  // the table's pointers are global memory: global, not flat, loads
+
+__global__ __launch_bounds__(256) void ensemble_size_metrics_kernel(const float* const* preds_tab, const float* const* targets_tab,
+                                                                    int n_members, long long n_points, long long member_stride,
+                                                                    long long n_tiles, double* partials) {
+    extern __shared__ double ens_size_lds[];  // [waves][quads * 16] fp64 accumulators, [quads][P] float4 members, [waves][16][68] + [quads * 4] floats
+    const int P = blockDim.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n_waves = P >> 6;
+    const int n_quads = (n_members + 3) >> 2;
+    double* acc = ens_size_lds + (size_t)wave * n_quads * 16;
+    float4* xs = (float4*)(ens_size_lds + (size_t)n_waves * n_quads * 16);
+    float* scratch = (float*)(xs + (size_t)n_quads * P) + (size_t)wave * 16 * ENS_SIZE_SCRATCH_ROW;
+    float* invs = (float*)(xs + (size_t)n_quads * P) + (size_t)n_waves * 16 * ENS_SIZE_SCRATCH_ROW;  // 1 / (n + 1), n < 4 * quads
+    const ens_size_gptr preds = (ens_size_gptr)preds_tab[blockIdx.y], targets = (ens_size_gptr)targets_tab[blockIdx.y];
+    for (int i = tid; i < n_quads * 4; i += P) invs[i] = 1.0f / (float)(i + 1);
+    for (int i = lane; i < n_quads * 16; i += 64) acc[i] = 0.0;
+    __syncthreads();
+    for (long long tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const long long p = tile * P + tid;
+        const bool live = p < n_points;
+        const long long pc = live ? p : n_points - 1;  // every lane loads a valid address and takes part in the transpose
+        const float y = live ? targets[pc] : 0.0f;
+        const ens_size_gptr column = preds + pc;
+        for (int q0 = 0; q0 < n_quads; q0 += 4) {  // 16 dword loads in flight per lane, then their four LDS writes
+            float v[16];
+#pragma unroll
+            for (int i = 0; i < 16; ++i) v[i] = column[(long long)min(4 * q0 + i, n_members - 1) * member_stride];
+#pragma unroll
+            for (int i = 0; i < 16; ++i)
+                if (!live || 4 * q0 + i >= n_members) v[i] = 0.0f;  // a dead lane's values are all zeros, and so are its contributions
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+                if (q0 + u < n_quads) xs[(size_t)(q0 + u) * P + tid] = make_float4(v[4 * u], v[4 * u + 1], v[4 * u + 2], v[4 * u + 3]);
+        }
+        float mean = 0.0f, m2 = 0.0f, sabs = 0.0f, pair = 0.0f;
+        for (int q = 0; q < n_quads; ++q) {
+            const float4 xq = xs[(size_t)q * P + tid];
+            const float x[4] = {xq.x, xq.y, xq.z, xq.w};
+            float row[4] = {0.0f, fabsf(x[1] - x[0]), fabsf(x[2] - x[0]) + fabsf(x[2] - x[1]),
+                            (fabsf(x[3] - x[0]) + fabsf(x[3] - x[1])) + fabsf(x[3] - x[2])};
+#pragma unroll 2
+            for (int m = 0; m < q; ++m) {
+                const float4 o = xs[(size_t)m * P + tid];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) row[j] += (fabsf(x[j] - o.x) + fabsf(x[j] - o.y)) + (fabsf(x[j] - o.z) + fabsf(x[j] - o.w));
+            }
+            const float4 iq = ((const float4*)invs)[q];
+            const float invq[4] = {iq.x, iq.y, iq.z, iq.w};
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {  // members past n_members (zeros) run the recurrences too: nothing reads their prefixes
+                const float inv = invq[j];
+                const float d = x[j] - mean;
+                mean += d * inv;
+                m2 += d * (x[j] - mean);
+                sabs += fabsf(x[j] - y);
+                pair += row[j];
+                float* col = scratch + (j * 4) * ENS_SIZE_SCRATCH_ROW + lane;
+                col[0] = (mean - y) * (mean - y);
+                col[ENS_SIZE_SCRATCH_ROW] = m2 * inv;
+                col[2 * ENS_SIZE_SCRATCH_ROW] = sabs * inv - pair * inv * inv;
+                col[3 * ENS_SIZE_SCRATCH_ROW] = (x[j] - y) * (x[j] - y);
+            }
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  // the wave's LDS operations complete in order: only the compiler is held
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            const float4* part = (const float4*)(scratch + (lane >> 2) * ENS_SIZE_SCRATCH_ROW + (lane & 3) * 16);
+            double s = 0.0;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const float4 f = part[i];
+                s += (double)f.x;
+                s += (double)f.y;
+                s += (double)f.z;
+                s += (double)f.w;
+            }
+            s += __shfl_xor(s, 1, 64);
+            s += __shfl_xor(s, 2, 64);
+            if ((lane & 3) == 0) acc[q * 16 + (lane >> 2)] += s;
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  // the next quad rewrites the scratch behind these reads
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        }
+    }
+    __syncthreads();
+    double* out = partials + ((long long)blockIdx.y * gridDim.x + blockIdx.x) * n_members * 4;
+    for (int i = tid; i < n_members * 4; i += P) {  // i = member * 4 + quantity = quad * 16 + scratch row
+        double s = ens_size_lds[i];
+        for (int w = 1; w < n_waves; ++w) s += ens_size_lds[(size_t)w * n_quads * 16 + i];
+        out[i] = s;
+    }
+}
+
+// One workgroup per segment, thread n = prefix n + 1: adds the G partials in workgroup order, divides, writes out[4][n_segments][N] =
+// {mse, ssr, crps, mse_per_mem}.  accum is read and written by this thread alone (ordered by the stream).
+__global__ __launch_bounds__(256) void ensemble_size_metrics_finish_kernel(const double* partials, int n_groups, int n_members,
+                                                                           long long n_points, int n_segments, double* out,
+                                                                           double* accum) {
+    const int seg = blockIdx.x, n = threadIdx.x;
+    if (n >= n_members) return;
+    const double* part = partials + ((long long)seg * n_groups * n_members + n) * 4;
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+    for (int g = 0; g < n_groups; ++g, part += (long long)n_members * 4) {
+        s0 += part[0];
+        s1 += part[1];
+        s2 += part[2];
+        s3 += part[3];
+    }
+    const double mse = s0 / (double)n_points;
+    const double v[4] = {mse, sqrt(s1 / (double)n_points) / sqrt(mse), s2 / (double)n_points, s3 / (double)n_points};
+    const long long plane = (long long)n_segments * n_members, at = (long long)seg * n_members + n;
+    for (int k = 0; k < 4; ++k) {
+        out[k * plane + at] = v[k];
+        if (accum) accum[k * plane + at] += v[k];
+    }
+}
+
+static int ensemble_size_metrics_threads(int n_members) { return n_members <= 64 ? 256 : 64; }
+
+int ensemble_size_metrics_groups(int n_members, long long n_points) {
+    if (n_members < 1 || n_members > ENSEMBLE_SIZE_MAX_MEMBERS || n_points < 1) return 0;
+    const int P = ensemble_size_metrics_threads(n_members);
+    return (int)std::min<long long>((n_points + P - 1) / P, ENS_SIZE_MAX_GROUPS);
+}
+
+hipError_t launch_ensemble_size_metrics(const float* const* preds_tab, const float* const* targets_tab, int n_segments, int n_members,
+                                        long long n_points, long long member_stride, double* partials, double* out, double* accum,
+                                        hipStream_t s) {
+    const int groups = ensemble_size_metrics_groups(n_members, n_points);
+    if (groups < 1 || n_segments < 1 || n_segments > 65535) return hipErrorInvalidValue;
+    const int P = ensemble_size_metrics_threads(n_members), waves = P / 64, quads = (n_members + 3) / 4;
+    const size_t lds = (size_t)waves * quads * 16 * sizeof(double) + (size_t)quads * P * 4 * sizeof(float) +
+                       (size_t)waves * 16 * ENS_SIZE_SCRATCH_ROW * sizeof(float) + (size_t)quads * 4 * sizeof(float);  // at most 89.25 KB (64 members)
+    hipError_t e = hipFuncSetAttribute((const void*)ensemble_size_metrics_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
+    if (e != hipSuccess) return e;
+    dyf_form_note(P == 256 ? "ensemble_size_metrics_kernel:lds_transpose" : "ensemble_size_metrics_kernel:lds_transpose+wave", 0);
+    hipLaunchKernelGGL(ensemble_size_metrics_kernel, dim3((unsigned)groups, (unsigned)n_segments), dim3(P), lds, s, preds_tab, targets_tab,
+                       n_members, n_points, member_stride, (n_points + P - 1) / P, partials);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(ensemble_size_metrics_finish_kernel, dim3((unsigned)n_segments), dim3(256), 0, s, partials, groups, n_members,
+                       n_points, n_segments, out, accum);
+    return hipGetLastError();
+}
+
 // ------------------------------------------------------------------------------------------------ exchange unpack
 __global__ __launch_bounds__(256) void gather_unpack_kernel(const float4* recv, float4* out, int world, int slots, int nb, int total_rows,
                                                             long long row4) {

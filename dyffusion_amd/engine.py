@@ -498,13 +498,10 @@ class HipEngine:
                                                    self._stream()))
         return out[0], out[1], out[2]
 
-    def trajectory_metrics(self, preds, targets, accum: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """Per-segment (mse, ssr, crps) on the device (dyf_trajectory_metrics): the curves of the reference's
-        `evaluate_ensemble_prediction(..., mean_over_samples=False)`.  `preds` is a list of T contiguous (N, ...) tensors with
-        `targets` the list of the T matching (...) tensors, or one (N, S, ...) tensor with `targets` (S, ...): that form is read in
-        place, member stride S * points.  Non-contiguous or non-fp32 inputs are made contiguous fp32 first.  Returns a float64
-        device tensor (3, T), rows mse / ssr / crps; `accum` (float64, (3, T), on the device) += it.  No synchronisation: the
-        two launches are enqueued on the current stream."""
+    @staticmethod
+    def _segments(preds, targets, what: str):
+        """The two input forms of the segment-wise metrics -> (n_members, n_segments, points, member_stride, prediction pointers,
+        target pointers, the tensors to keep alive until the launches are enqueued, device)."""
         if torch.is_tensor(preds) != torch.is_tensor(targets):
             raise ValueError("preds and targets must both be lists or both be tensors")
         if torch.is_tensor(preds):
@@ -539,7 +536,17 @@ class HipEngine:
             keep = (preds, targets)
         dev = keep[0].device if torch.is_tensor(keep[0]) else keep[0][0].device
         if dev.type != "cuda":
-            raise ValueError("trajectory_metrics works on GPU tensors (the HIP engine computes them)")
+            raise ValueError(f"{what} works on GPU tensors (the HIP engine computes them)")
+        return n, nseg, points, stride, p_ptrs, t_ptrs, keep, dev
+
+    def trajectory_metrics(self, preds, targets, accum: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Per-segment (mse, ssr, crps) on the device (dyf_trajectory_metrics): the curves of the reference's
+        `evaluate_ensemble_prediction(..., mean_over_samples=False)`.  `preds` is a list of T contiguous (N, ...) tensors with
+        `targets` the list of the T matching (...) tensors, or one (N, S, ...) tensor with `targets` (S, ...): that form is read in
+        place, member stride S * points.  Non-contiguous or non-fp32 inputs are made contiguous fp32 first.  Returns a float64
+        device tensor (3, T), rows mse / ssr / crps; `accum` (float64, (3, T), on the device) += it.  No synchronisation: the
+        two launches are enqueued on the current stream."""
+        n, nseg, points, stride, p_ptrs, t_ptrs, keep, dev = self._segments(preds, targets, "trajectory_metrics")
         if accum is not None and (accum.dtype != torch.float64 or tuple(accum.shape) != (3, nseg) or not accum.is_contiguous()
                                   or accum.device != dev):
             raise ValueError(f"accum must be a contiguous float64 (3, {nseg}) tensor on {dev}")
@@ -548,6 +555,24 @@ class HipEngine:
                                                      points, stride, out.data_ptr(), accum.data_ptr() if accum is not None else None,
                                                      self._stream()))
         del keep  # held until the launches were enqueued; the caching allocator orders any reuse behind them on this stream
+        return out
+
+    def ensemble_size_metrics(self, preds, targets, accum: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The metrics as a function of the ensemble size, one pass on the device (dyf_ensemble_size_metrics): for every segment
+        and n = 1..N the mse / ssr / crps of `preds[:n]` (the reference's `evaluate_ensemble_prediction_for_varying_members`)
+        and every member's own mse.  Inputs as `trajectory_metrics`: a list of T (N, ...) tensors with T (...) targets, or one
+        (N, S, ...) tensor with (S, ...) targets, read in place.  Returns a float64 device tensor (4, T, N), planes mse / ssr /
+        crps (entry n - 1 = the first n members) / mse_per_mem; `accum` (float64, (4, T, N), on the device) += it.  At most 256
+        members (NotImplementedError beyond).  No synchronisation."""
+        n, nseg, points, stride, p_ptrs, t_ptrs, keep, dev = self._segments(preds, targets, "ensemble_size_metrics")
+        if accum is not None and (accum.dtype != torch.float64 or tuple(accum.shape) != (4, nseg, n) or not accum.is_contiguous()
+                                  or accum.device != dev):
+            raise ValueError(f"accum must be a contiguous float64 (4, {nseg}, {n}) tensor on {dev}")
+        out = torch.empty(4, nseg, n, dtype=torch.float64, device=dev)
+        self._check(self._lib.dyf_ensemble_size_metrics(self._h, nseg, (C.c_void_p * nseg)(*p_ptrs), (C.c_void_p * nseg)(*t_ptrs), n,
+                                                        points, stride, out.data_ptr(),
+                                                        accum.data_ptr() if accum is not None else None, self._stream()))
+        del keep  # as in trajectory_metrics
         return out
 
     def time_layer_in_rollout(self, layer: int, nb: int):

@@ -121,7 +121,7 @@ class MultiHorizonForecastingDYffusion(nn.Module):
 
     def __init__(self, model: DYffusion, num_predictions: int = 1, window: int = 1, horizon: Optional[int] = None,
                  autoregressive_steps: int = 0, prediction_horizon: Optional[int] = None, datamodule=None,
-                 datamodule_config: Optional[Dict[str, Any]] = None):
+                 datamodule_config: Optional[Dict[str, Any]] = None, ensemble_size_curves: bool = False):
         super().__init__()
         assert autoregressive_steps >= 0, f"Autoregressive steps must be >= 0, but is {autoregressive_steps}"
         if autoregressive_steps > 0:
@@ -133,6 +133,8 @@ class MultiHorizonForecastingDYffusion(nn.Module):
         self._prediction_horizon = prediction_horizon
         self._datamodule = datamodule
         self.datamodule_config = dict(datamodule_config or {})
+        # also report the metrics of the first n members, n = 1..N-1, at the end of validation / test epochs ({n}ens_mems/ keys)
+        self.ensemble_size_curves = ensemble_size_curves
         self._test_metrics_aggregate = None  # TrajectoryMetricsAccumulator of the physical-systems test epoch (first test_step)
         self._predict_step_outputs = []
 
@@ -293,7 +295,7 @@ class MultiHorizonForecastingDYffusion(nn.Module):
             return results
         from .metrics import TrajectoryMetricsAccumulator
         if self._test_metrics_aggregate is None:
-            self._test_metrics_aggregate = TrajectoryMetricsAccumulator(self.model._engine)
+            self._test_metrics_aggregate = TrajectoryMetricsAccumulator(self.model._engine, by_size=self.ensemble_size_curves)
         timesteps = range(1, self.prediction_horizon + 1)
         targets = [results[f"t{t}_targets"] for t in timesteps]
         preds = [results[f"t{t}_preds"] for t in timesteps]
@@ -305,8 +307,9 @@ class MultiHorizonForecastingDYffusion(nn.Module):
         """_base_experiment.py:569-640: concatenate the steps' outputs (predictions (N, B, ...) along B, targets along their batch
         axis) and evaluate CRPS / spread-skill ratio / ensemble-mean MSE per horizon and on average -- with
         `dyffusion_amd.metrics` (ensemble_metrics_kernel), not after a `.cpu().numpy()` round trip.  Returns what the reference
-        logs: `{split}/{N}ens_mems/t{k}/{crps|ssr|mse}` and `.../avg/...`."""
-        from .metrics import eval_ensemble_predictions
+        logs: `{split}/{N}ens_mems/t{k}/{crps|ssr|mse}` and `.../avg/...`; with `ensemble_size_curves` also the same keys for the
+        first n members, n = 1..N-1 (ensemble_size_metrics_kernel)."""
+        from .metrics import eval_ensemble_predictions, eval_ensemble_size_curves
         n = self.hparams.num_predictions
         if n <= 1 or not outputs:  # use_ensemble_predictions(split), :497-498
             return {}
@@ -316,7 +319,10 @@ class MultiHorizonForecastingDYffusion(nn.Module):
                 continue
             axis = 1 if (first.shape[0] == n and first.dim() >= 2 and "targets" not in key and "true" not in key) else 0
             results[key] = torch.cat([o[key] for o in outputs], dim=axis)
-        return eval_ensemble_predictions(results, self.model._engine, split=split, infix=self.ensemble_logging_infix(split))
+        out = eval_ensemble_predictions(results, self.model._engine, split=split, infix=self.ensemble_logging_infix(split))
+        if self.ensemble_size_curves:
+            out.update(eval_ensemble_size_curves(results, self.model._engine, split=split))
+        return out
 
     def on_validation_epoch_end(self) -> Dict[str, float]:
         outs, self.__dict__["_validation_step_outputs"] = self.__dict__.get("_validation_step_outputs", []), []
@@ -329,13 +335,18 @@ class MultiHorizonForecastingDYffusion(nn.Module):
         outs, self.__dict__["_test_step_outputs"] = self.__dict__.get("_test_step_outputs", []), []
         if not self._physical_systems_test:
             return self._eval_ensemble_predictions(outs, split="test") if calc_ensemble_metrics else {}
-        from .metrics import trajectory_metric_keys
+        from .metrics import trajectory_metric_keys, trajectory_size_curve_keys
         agg = self._test_metrics_aggregate
         if agg is None or agg.count == 0:
             return {}
         curves = agg.compute()
         agg.reset()
-        return trajectory_metric_keys(self.ensemble_logging_infix("test"), curves, getattr(self.datamodule, "test_set_name", "") or "")
+        by_size = curves.pop("by_size", None)
+        set_name = getattr(self.datamodule, "test_set_name", "") or ""
+        out = trajectory_metric_keys(self.ensemble_logging_infix("test"), curves, set_name)
+        if by_size is not None:
+            out.update(trajectory_size_curve_keys(by_size, set_name))
+        return out
 
     def predict_step(self, batch: Dict[str, Any], batch_idx: int = 0, dataloader_idx: int = None, **kwargs) -> None:
         results = self.evaluation_step(batch, batch_idx, split="predict", as_numpy=True, **kwargs)

@@ -301,6 +301,18 @@ dyf_status dyf_ensemble_metrics(dyf_engine* engine, const float* preds_dev, cons
 dyf_status dyf_trajectory_metrics(dyf_engine* engine, int32_t n_segments, const float* const* preds_dev,
                                   const float* const* targets_dev, int32_t n_members, int64_t n_points, int64_t member_stride,
                                   double* out_dev, double* accum_dev, void* stream);
+/* The metrics as a function of the ensemble size, in one pass: for every segment and every n = 1..n_members the mse, ssr and crps of
+ * the ensemble made of the FIRST n members (evaluate_ensemble_prediction_for_varying_members, evaluation.py:145-156), and every
+ * member's own mse (mse_per_mem, evaluation.py:53-60).  Segments, member_stride and the two host arrays of device pointers as in
+ * dyf_trajectory_metrics.  out_dev (device, [4][n_segments][n_members]) receives mse, ssr, crps (entry n - 1 = prefix n) and
+ * mse_per_mem; accum_dev (device, the same shape, or NULL) += out.  The pair term of prefix n is that of prefix n - 1 plus
+ * sum_{m<n} |x_n - x_m|, mean and variance are Welford's (ssr[0] is exactly 0): all prefixes cost the pair work of one score.  Two
+ * launches on `stream`, no atomics, partial sums in an engine-owned workspace of at most 64 x n_members x 4 doubles per segment: a
+ * segment's values depend neither on the other segments nor on the layout, and identical calls give identical bits.  Does NOT
+ * synchronise.  n_members in [1, 256] (DYF_ERR_UNSUPPORTED beyond), n_segments in [1, 65535].  (Additive: no ABI change.) */
+dyf_status dyf_ensemble_size_metrics(dyf_engine* engine, int32_t n_segments, const float* const* preds_dev,
+                                     const float* const* targets_dev, int32_t n_members, int64_t n_points, int64_t member_stride,
+                                     double* out_dev, double* accum_dev, void* stream);
 /* Copy one (NB,C,H,W) field of the sampler's state after the most recent dyf_sample call: what sample_loop returns
  * beside the intermediates (dyffusion.py:424-426): (x0_hat, ., x_s), or (x_s, ., x_interpolated_s_next) when the sampling
  * schedule stops before T-1. */
