@@ -190,6 +190,8 @@ SYMBOLS = [
     ("dyf_ensemble_metrics", C.c_int, [_P, _P, _P, C.c_int32, C.c_int64, C.POINTER(C.c_double), _P]),
     ("dyf_trajectory_metrics", C.c_int, [_P, C.c_int32, C.POINTER(_P), C.POINTER(_P), C.c_int32, C.c_int64, C.c_int64, _P, _P, _P]),
     ("dyf_ensemble_size_metrics", C.c_int, [_P, C.c_int32, C.POINTER(_P), C.POINTER(_P), C.c_int32, C.c_int64, C.c_int64, _P, _P, _P]),
+    ("dyf_ensemble_scores", C.c_int, [_P, C.c_int32, C.POINTER(_P), C.POINTER(_P), C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int32,
+                                      C.c_int64, _P, _P, _P]),
     ("dyf_time_layer_in_rollout", C.c_int, [_P, C.c_int32, C.c_int32, _P, C.POINTER(C.c_double), C.POINTER(C.c_int32)]),
     ("dyf_time_kernel_in_rollout", C.c_int, [_P, C.c_int32, C.c_int32, _P, C.POINTER(C.c_double), C.POINTER(C.c_int32),
                                              C.POINTER(C.c_double), C.POINTER(C.c_double)]),

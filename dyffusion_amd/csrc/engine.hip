@@ -1798,13 +1798,14 @@ static void traj_release(dyf_engine* e) {
     if (e->traj_stage) (void)hipHostFree((void*)e->traj_stage);
     if (e->traj_partials) (void)hipFree(e->traj_partials);
     if (e->ens_size_partials) (void)hipFree(e->ens_size_partials);
+    if (e->ens_scores_partials) (void)hipFree(e->ens_scores_partials);
     if (e->traj_uploaded) (void)hipEventDestroy(e->traj_uploaded);
     if (e->traj_done) (void)hipEventDestroy(e->traj_done);
     e->traj_tab = e->traj_stage = nullptr;
-    e->traj_partials = e->ens_size_partials = nullptr;
+    e->traj_partials = e->ens_size_partials = e->ens_scores_partials = nullptr;
     e->traj_uploaded = e->traj_done = nullptr;
     e->traj_cap = 0;
-    e->traj_partials_count = e->ens_size_partials_count = 0;
+    e->traj_partials_count = e->ens_size_partials_count = e->ens_scores_partials_count = 0;
     e->traj_pending = false;
 }
 
@@ -1903,6 +1904,29 @@ dyf_status dyf_ensemble_size_metrics(dyf_engine* e, int32_t n_segments, const fl
     if (cs != DYF_OK) return cs;
     return traj_finish(e, launch_ensemble_size_metrics(e->traj_tab, e->traj_tab + n_segments, n_segments, n_members, n_points,
                                                        member_stride, e->ens_size_partials, out_dev, accum_dev, st), st);
+}
+
+dyf_status dyf_ensemble_scores(dyf_engine* e, int32_t n_segments, const float* const* preds_dev, const float* const* targets_dev,
+                               int32_t n_members, int64_t n_points, int64_t member_stride, int64_t n_outer, int32_t n_groups,
+                               int64_t n_inner, double* out_dev, double* accum_dev, void* stream) {
+    dyf_status cs = traj_check_args(e, n_segments, preds_dev, targets_dev, n_members, 15360, DYF_ERR_INVALID_ARGUMENT, n_points,
+                                    member_stride, out_dev);
+    if (cs != DYF_OK) return cs;
+    if (n_outer < 1 || n_groups < 1 || n_inner < 1) return fail(e, DYF_ERR_INVALID_ARGUMENT, "n_outer, n_groups and n_inner must be positive");
+    // n_outer * n_groups * n_inner == n_points, without forming a product that could overflow
+    if (n_points % n_outer != 0 || (n_points / n_outer) % n_groups != 0 || n_points / n_outer / n_groups != n_inner)
+        return fail(e, DYF_ERR_INVALID_ARGUMENT, "n_outer * n_groups * n_inner must equal n_points");
+    const long long blocks = ensemble_scores_blocks(n_members, n_outer, n_groups, n_inner);
+    if (blocks < 1)
+        return fail(e, DYF_ERR_UNSUPPORTED, "more than 2^24 - 1 = " + std::to_string(ENSEMBLE_SCORES_MAX_BLOCKS) +
+                                                " workgroups per segment (n_outer * n_groups * ceil(n_inner / points per workgroup))");
+    HIP_TRY(e, hipSetDevice(e->cfg.device));
+    hipStream_t st = (hipStream_t)stream;
+    cs = traj_upload(e, n_segments, preds_dev, targets_dev, &e->ens_scores_partials, &e->ens_scores_partials_count,
+                     (size_t)n_segments * (size_t)blocks * ENSEMBLE_SCORES_PARTIAL, st);
+    if (cs != DYF_OK) return cs;
+    return traj_finish(e, launch_ensemble_scores(e->traj_tab, e->traj_tab + n_segments, n_segments, n_members, member_stride, n_outer,
+                                                 n_groups, n_inner, e->ens_scores_partials, out_dev, accum_dev, st), st);
 }
 
 dyf_status dyf_apply_boundary_conditions(dyf_engine* e, const dyf_bc_args* bc, float* preds_dev, void* stream) {

@@ -217,6 +217,18 @@ int ensemble_size_metrics_groups(int n_members, long long n_points);  // workgro
 hipError_t launch_ensemble_size_metrics(const float* const* preds_tab, const float* const* targets_tab, int n_segments, int n_members,
                                         long long n_points, long long member_stride, double* partials, double* out, double* accum,
                                         hipStream_t s);
+// five scores per (segment, group) of the points viewed as row-major (n_outer, n_groups, n_inner) (dyf_ensemble_scores), without
+// atomics: launch 1 writes ENSEMBLE_SCORES_PARTIAL doubles per workgroup to partials[n_segments][ensemble_scores_blocks()][9] (a
+// workgroup's tile lies inside one (outer, group) slab), launch 2 (one wave per (segment, group)) joins a group's partials in a
+// fixed order and writes out[5][n_segments][n_groups] = {mse, ssr, crps, nll, corr} (accum += out when given).  Pointer tables and
+// member_stride as launch_trajectory_metrics.
+constexpr int ENSEMBLE_SCORES_PARTIAL = 9;
+constexpr long long ENSEMBLE_SCORES_MAX_BLOCKS = 0xffffffLL;  // workgroups per segment: 256 threads each, below 2^32 threads along x
+// workgroups per segment = n_outer * n_groups * ceil(n_inner / tile); 0 = n_members beyond 15 360, -1 = beyond ENSEMBLE_SCORES_MAX_BLOCKS
+long long ensemble_scores_blocks(int n_members, long long n_outer, int n_groups, long long n_inner);
+hipError_t launch_ensemble_scores(const float* const* preds_tab, const float* const* targets_tab, int n_segments, int n_members,
+                                  long long member_stride, long long n_outer, int n_groups, long long n_inner, double* partials,
+                                  double* out, double* accum, hipStream_t s);
 
 // dyf_sample_gather: all-gather receive layout [world][slots][nb][row floats] -> [slots][total_rows][row] in global row order;
 // rank r owns the contiguous block of rows shard(r) (the first total_rows % world ranks one extra), its padding rows are dropped

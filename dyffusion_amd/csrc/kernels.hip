@@ -2313,6 +2313,298 @@ hipError_t launch_ensemble_size_metrics(const float* const* preds_tab, const flo
     return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------------------ ensemble scores
+// Five scores per (segment, GROUP) in one pass (dyf_ensemble_scores: evaluate_ensemble_mse / _spread_skill_ratio / _crps / _nll with
+// mean_dims and evaluate_ensemble_corr, evaluation.py:83-142).  A segment's points are row-major (n_outer, n_groups, n_inner) and
+// point p belongs to group (p / n_inner) % n_groups.  Work mapping: blockIdx.x = slab * tiles_per_slab + tile with slab = outer *
+// n_groups + group, so a workgroup's tile lies inside one (outer, group) slab and its partial belongs to one group; blockIdx.y is the
+// segment.  Per point mean, se, var and crps are the fp32 expressions of trajectory_metrics_kernel (the two kernels below are its
+// two forms with the slab index map; where 1 / N is inexact the last bit of crps depends on how its two products are contracted, so
+// that one expression is written the way the compiler leaves it in either form there, and the pooled call equals
+// dyf_trajectory_metrics to the fp64 sums' rounding), nll = 0.5 log(2 pi var) + se / (2 var) in fp32 with the accurate logf; no
+// clamp: one member has var = 0 and a NaN nll, as numpy.
+//   Correlation: a workgroup leaves the mean of its points' ensemble means and targets and their CENTRED second moments about
+// those (fp64, from the fp32 mean and y; a second round over values the threads still hold), and the finish kernel joins the
+// workgroups' moments pairwise (Chan et al.).  The raw moments sum(m), sum(m^2), ... would give the same correlation on ordinary
+// data, but for a group whose means or targets are constant their difference is rounding noise, not the exact zero that makes
+// numpy's corrcoef NaN; here a constant c gives workgroup means of exactly c (up to 256 copies of a 24-bit value add exactly in
+// fp64), deviations, M2 and co-moment of exactly 0 at every join, and corr = 0 / 0.
+//   partials[n_segments][blocks][9] = {sum se, sum var, sum crps, sum nll, mean of m, mean of y, M2 m, M2 y, co-moment}; the live
+// points of a tile follow from the geometry.  ensemble_scores_finish_kernel (one wave per (segment, group)) walks the group's
+// partials in (outer, tile) order: lane l takes entries l, l + 64, ..., lane 0 joins the lanes in lane order.  No atomics; a group's
+// result depends on its own points, n_members and (n_outer, n_inner) alone.
+template <int K>
+__device__ __forceinline__ void scores_block_sum(double (&v)[K], double* wsum /* LDS, [4][K] */) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+#pragma unroll
+        for (int k = 0; k < K; ++k) v[k] += __shfl_xor(v[k], off, 64);
+    }
+    const int tid = threadIdx.x;
+    __syncthreads();  // wsum lies over the staged members (and over the sums of the round before): every wave is done reading them
+    if ((tid & 63) == 0) {
+#pragma unroll
+        for (int k = 0; k < K; ++k) wsum[(tid >> 6) * K + k] = v[k];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < K; ++k) v[k] = ((wsum[k] + wsum[K + k]) + wsum[2 * K + k]) + wsum[3 * K + k];  // every thread: the workgroup's sum
+}
+
+// `holds`: this thread carries a live point's values (the others add zeros); n_live: the live points of the tile (>= 1).
+__device__ __forceinline__ void scores_block_partial(bool holds, float mean, float y, float se, float var, float crps, int n_live,
+                                                     double* wsum, double* partial) {
+    double v[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    if (holds) {
+        const float nll = 0.5f * logf(6.2831853071795865f * var) + se / (2.0f * var);
+        v[0] = se;
+        v[1] = var;
+        v[2] = crps;
+        v[3] = nll;
+        v[4] = mean;
+        v[5] = y;
+    }
+    scores_block_sum<6>(v, wsum);
+    const double mm = v[4] / (double)n_live, my = v[5] / (double)n_live;
+    double c[3] = {0.0, 0.0, 0.0};
+    if (holds) {
+        const double dm = (double)mean - mm, dy = (double)y - my;
+        c[0] = dm * dm;
+        c[1] = dy * dy;
+        c[2] = dm * dy;
+    }
+    scores_block_sum<3>(c, wsum);
+    if (threadIdx.x == 0) {
+        partial[0] = v[0];
+        partial[1] = v[1];
+        partial[2] = v[2];
+        partial[3] = v[3];
+        partial[4] = mm;
+        partial[5] = my;
+        partial[6] = c[0];
+        partial[7] = c[1];
+        partial[8] = c[2];
+    }
+}
+
+__global__ __launch_bounds__(256) void ensemble_scores_kernel(const float* const* preds_tab, const float* const* targets_tab,
+                                                              int n_members, long long member_stride, long long n_inner,
+                                                              unsigned tiles_per_slab, double* partials) {
+    extern __shared__ double scores_lds[];  // [n_members][256] floats; the first 192 bytes again for the wave sums
+    float* xs = (float*)scores_lds;
+    const float* preds = preds_tab[blockIdx.y];
+    const float* targets = targets_tab[blockIdx.y];
+    const int tid = threadIdx.x;
+    const unsigned slab = blockIdx.x / tiles_per_slab, tile = blockIdx.x - slab * tiles_per_slab;
+    const long long q = (long long)tile * 256 + tid;  // within the slab
+    const long long p = (long long)slab * n_inner + q;
+    const bool live = q < n_inner;
+    float se = 0.0f, var = 0.0f, crps = 0.0f, mean = 0.0f, y = 0.0f;
+    if (live) {
+        y = targets[p];
+        float sum = 0.0f, sabs = 0.0f;
+        for (int n = 0; n < n_members; ++n) {
+            const float x = preds[(long long)n * member_stride + p];
+            xs[n * 256 + tid] = x;
+            sum += x;
+            sabs += fabsf(x - y);
+        }
+        const float inv = 1.0f / (float)n_members;
+        mean = sum * inv;
+        float m2 = 0.0f, pair = 0.0f;
+        for (int n = 0; n < n_members; ++n) {
+            const float x = xs[n * 256 + tid];
+            m2 += (x - mean) * (x - mean);
+            for (int m = n + 1; m < n_members; ++m) pair += fabsf(x - xs[m * 256 + tid]);
+        }
+        se = (mean - y) * (mean - y);
+        var = m2 * inv;
+        crps = fmaf(sabs, inv, -(pair * inv * inv));  // trajectory_metrics_kernel's sabs * inv - pair * inv * inv as the compiler contracts it there
+    }
+    const int n_live = n_inner - (long long)tile * 256 < 256 ? (int)(n_inner - (long long)tile * 256) : 256;
+    scores_block_partial(live, mean, y, se, var, crps, n_live, scores_lds,
+                         partials + ((long long)blockIdx.y * gridDim.x + blockIdx.x) * ENSEMBLE_SCORES_PARTIAL);
+}
+
+// more than 64 members: the split of trajectory_metrics_tiled_kernel (P points per workgroup, 256 / P threads share a point)
+__global__ __launch_bounds__(256) void ensemble_scores_tiled_kernel(const float* const* preds_tab, const float* const* targets_tab,
+                                                                    int n_members, long long member_stride, long long n_inner,
+                                                                    unsigned tiles_per_slab, double* partials, int P) {
+    extern __shared__ double scores_lds[];  // floats: [n_members][P] members (the first 192 bytes again for the wave sums), then [2][256] partials
+    float* xs = (float*)scores_lds;
+    float* red = xs + (size_t)n_members * P;
+    const float* preds = preds_tab[blockIdx.y];
+    const float* targets = targets_tab[blockIdx.y];
+    const int tid = threadIdx.x, T = 256 / P;
+    const int pi = tid % P, sh = tid / P;
+    const unsigned slab = blockIdx.x / tiles_per_slab, tile = blockIdx.x - slab * tiles_per_slab;
+    const long long q0 = (long long)tile * P;            // within the slab
+    const long long p0 = (long long)slab * n_inner + q0;
+    const bool live = q0 + pi < n_inner;
+    for (int i = tid; i < n_members * P; i += 256) {  // staging: consecutive threads -> consecutive points of one member
+        const int n = i / P, q = i - n * P;
+        xs[i] = q0 + q < n_inner ? preds[(long long)n * member_stride + p0 + q] : 0.0f;
+    }
+    __syncthreads();
+    const float y = live ? targets[p0 + pi] : 0.0f;
+    float sum = 0.0f, sabs = 0.0f;
+    for (int n = sh; n < n_members; n += T) {
+        const float x = xs[n * P + pi];
+        sum += x;
+        sabs += fabsf(x - y);
+    }
+    red[tid] = sum;
+    red[256 + tid] = sabs;
+    __syncthreads();
+    float tsum = 0.0f, tabs = 0.0f;
+    for (int k = 0; k < T; ++k) {  // every share adds the T partials in the same order: all hold the same mean
+        tsum += red[k * P + pi];
+        tabs += red[256 + k * P + pi];
+    }
+    const float inv = 1.0f / (float)n_members;
+    const float mean = tsum * inv;
+    __syncthreads();
+    float m2 = 0.0f;
+    double pair = 0.0;  // up to N^2 / 2 terms per point: rows in fp32, the sum of rows in fp64
+    for (int n = sh; n < n_members; n += T) {
+        const float x = xs[n * P + pi];
+        m2 += (x - mean) * (x - mean);
+        float row = 0.0f;
+        for (int m = n + 1; m < n_members; ++m) row += fabsf(x - xs[m * P + pi]);
+        pair += (double)row;
+    }
+    red[tid] = m2;
+    red[256 + tid] = (float)pair;
+    __syncthreads();
+    float se = 0.0f, var = 0.0f, crps = 0.0f;
+    const bool holds = live && sh == 0;
+    if (holds) {
+        float tm2 = 0.0f, tpair = 0.0f;
+        for (int k = 0; k < T; ++k) {
+            tm2 += red[k * P + pi];
+            tpair += red[256 + k * P + pi];
+        }
+        se = (mean - y) * (mean - y);
+        var = tm2 * inv;
+        {
+#pragma clang fp contract(off)  // ... and trajectory_metrics_tiled_kernel's as the compiler leaves it there: two products, one subtraction
+            crps = tabs * inv - tpair * inv * inv;
+        }
+    }
+    const int n_live = n_inner - q0 < P ? (int)(n_inner - q0) : P;
+    scores_block_partial(holds, mean, y, se, var, crps, n_live, scores_lds,
+                         partials + ((long long)blockIdx.y * gridDim.x + blockIdx.x) * ENSEMBLE_SCORES_PARTIAL);
+}
+
+struct scores_moments {
+    double n, mm, my, m2m, m2y, c;  // points, the two means, the centred second moments and the co-moment about them
+};
+__device__ __forceinline__ void scores_join(scores_moments& a, const scores_moments& b) {
+    if (b.n == 0.0) return;
+    if (a.n == 0.0) {
+        a = b;
+        return;
+    }
+    const double n = a.n + b.n, dm = b.mm - a.mm, dy = b.my - a.my, f = a.n * b.n / n, w = b.n / n;
+    a.m2m += b.m2m + dm * dm * f;
+    a.m2y += b.m2y + dy * dy * f;
+    a.c += b.c + dm * dy * f;
+    a.mm += dm * w;
+    a.my += dy * w;
+    a.n = n;
+}
+
+// One wave per (segment, group): blockIdx.x the group, blockIdx.y the segment.  accum is read and written by this wave alone
+// (ordered by the stream).
+__global__ __launch_bounds__(64) void ensemble_scores_finish_kernel(const double* partials, long long n_blocks, long long n_outer,
+                                                                    int n_groups, long long n_inner, long long tiles_per_slab,
+                                                                    int tile_points, int n_segments, double* out, double* accum) {
+    __shared__ double lane_state[10][64];
+    const int g = blockIdx.x, seg = blockIdx.y, lane = threadIdx.x;
+    const double* part = partials + (long long)seg * n_blocks * ENSEMBLE_SCORES_PARTIAL;
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+    scores_moments mo = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    const long long count = n_outer * tiles_per_slab;
+    for (long long j = lane; j < count; j += 64) {
+        const long long o = j / tiles_per_slab, t = j - o * tiles_per_slab;
+        const double* b = part + ((o * n_groups + g) * tiles_per_slab + t) * ENSEMBLE_SCORES_PARTIAL;
+        a0 += b[0];
+        a1 += b[1];
+        a2 += b[2];
+        a3 += b[3];
+        const long long left = n_inner - t * tile_points;
+        const scores_moments bm = {(double)(left < tile_points ? left : (long long)tile_points), b[4], b[5], b[6], b[7], b[8]};
+        scores_join(mo, bm);
+    }
+    lane_state[0][lane] = a0;
+    lane_state[1][lane] = a1;
+    lane_state[2][lane] = a2;
+    lane_state[3][lane] = a3;
+    lane_state[4][lane] = mo.n;
+    lane_state[5][lane] = mo.mm;
+    lane_state[6][lane] = mo.my;
+    lane_state[7][lane] = mo.m2m;
+    lane_state[8][lane] = mo.m2y;
+    lane_state[9][lane] = mo.c;
+    __syncthreads();
+    if (lane == 0) {
+        double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+        scores_moments all = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        for (int l = 0; l < 64; ++l) {
+            s0 += lane_state[0][l];
+            s1 += lane_state[1][l];
+            s2 += lane_state[2][l];
+            s3 += lane_state[3][l];
+            const scores_moments lm = {lane_state[4][l], lane_state[5][l], lane_state[6][l], lane_state[7][l], lane_state[8][l],
+                                       lane_state[9][l]};
+            scores_join(all, lm);
+        }
+        const double n = (double)n_outer * (double)n_inner;
+        const double mse = s0 / n;
+        const double v[5] = {mse, sqrt(s1 / n) / sqrt(mse), s2 / n, s3 / n, (all.c / n) / sqrt((all.m2m / n) * (all.m2y / n))};
+        const long long plane = (long long)n_segments * n_groups, at = (long long)seg * n_groups + g;
+        for (int k = 0; k < 5; ++k) {
+            out[k * plane + at] = v[k];
+            if (accum) accum[k * plane + at] += v[k];
+        }
+    }
+}
+
+long long ensemble_scores_blocks(int n_members, long long n_outer, int n_groups, long long n_inner) {
+    const int P = n_members >= 1 ? trajectory_metrics_tile(n_members) : 0;
+    if (P == 0 || n_outer < 1 || n_groups < 1 || n_inner < 1) return 0;
+    const long long tiles = (n_inner + P - 1) / P;
+    if (tiles > ENSEMBLE_SCORES_MAX_BLOCKS || n_outer > ENSEMBLE_SCORES_MAX_BLOCKS / tiles ||
+        (long long)n_groups > ENSEMBLE_SCORES_MAX_BLOCKS / (tiles * n_outer))
+        return -1;
+    return tiles * n_outer * n_groups;
+}
+
+hipError_t launch_ensemble_scores(const float* const* preds_tab, const float* const* targets_tab, int n_segments, int n_members,
+                                  long long member_stride, long long n_outer, int n_groups, long long n_inner, double* partials,
+                                  double* out, double* accum, hipStream_t s) {
+    const long long blocks = ensemble_scores_blocks(n_members, n_outer, n_groups, n_inner);
+    if (blocks < 1 || n_segments < 1 || n_segments > 65535) return hipErrorInvalidValue;
+    const int P = trajectory_metrics_tile(n_members);
+    const long long tiles = (n_inner + P - 1) / P;
+    const dim3 grid((unsigned)blocks, (unsigned)n_segments);
+    if (n_members > 64) {
+        const size_t lds = ((size_t)n_members * P + 2 * 256) * sizeof(float);
+        dyf_form_note("ensemble_scores_kernel:slab+tiled", 0);
+        hipLaunchKernelGGL(ensemble_scores_tiled_kernel, grid, dim3(256), lds, s, preds_tab, targets_tab, n_members, member_stride,
+                           n_inner, (unsigned)tiles, partials, P);
+    } else {
+        dyf_form_note("ensemble_scores_kernel:slab", 0);
+        hipLaunchKernelGGL(ensemble_scores_kernel, grid, dim3(256), (size_t)n_members * 256 * sizeof(float), s, preds_tab, targets_tab,
+                           n_members, member_stride, n_inner, (unsigned)tiles, partials);
+    }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(ensemble_scores_finish_kernel, dim3((unsigned)n_groups, (unsigned)n_segments), dim3(64), 0, s, partials, blocks,
+                       n_outer, n_groups, n_inner, tiles, P, n_segments, out, accum);
+    return hipGetLastError();
+}
+
 // ------------------------------------------------------------------------------------------------ exchange unpack
 __global__ __launch_bounds__(256) void gather_unpack_kernel(const float4* recv, float4* out, int world, int slots, int nb, int total_rows,
                                                             long long row4) {

@@ -1,6 +1,7 @@
 """Thin object wrapper over the C ABI (one HipEngine = one dyf_engine).  PyTorch is only used for device memory
 and streams here: every tensor crosses the boundary as a raw device pointer (`tensor.data_ptr()`)."""
 import ctypes as C
+import operator
 from typing import Dict, List, Optional, Sequence
 
 import numpy as np
@@ -572,6 +573,34 @@ class HipEngine:
         self._check(self._lib.dyf_ensemble_size_metrics(self._h, nseg, (C.c_void_p * nseg)(*p_ptrs), (C.c_void_p * nseg)(*t_ptrs), n,
                                                         points, stride, out.data_ptr(),
                                                         accum.data_ptr() if accum is not None else None, self._stream()))
+        del keep  # as in trajectory_metrics
+        return out
+
+    def ensemble_scores(self, preds, targets, group_shape: Optional[Sequence[int]] = None,
+                        accum: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Five scores per (segment, group), one pass on the device (dyf_ensemble_scores).  Inputs as `trajectory_metrics`: a list
+        of T (N, ...) tensors with T (...) targets, or one (N, S, ...) tensor with (S, ...) targets, read in place.  `group_shape`
+        = (outer, groups, inner) views one segment's points as row-major (outer, groups, inner), point p in group
+        (p // inner) % groups; None pools the segment, (1, 1, points).  Returns a float64 device tensor (5, T, G), planes mse / ssr
+        / crps / nll / corr (`dyffusion_amd.metrics.SCORE_ROWS`); `accum` (float64, (5, T, G), on the device) += it.  IEEE
+        behaviour as numpy: one member gives a NaN nll, a group with constant ensemble means or targets a NaN corr.  No
+        synchronisation."""
+        n, nseg, points, stride, p_ptrs, t_ptrs, keep, dev = self._segments(preds, targets, "ensemble_scores")
+        if group_shape is None:
+            group_shape = (1, 1, points)
+        try:
+            outer, groups, inner = (operator.index(v) for v in group_shape)
+        except (TypeError, ValueError):
+            raise ValueError(f"group_shape must be (outer, groups, inner) integers, not {group_shape!r}") from None
+        if min(outer, groups, inner) < 1 or outer * groups * inner != points:
+            raise ValueError(f"group_shape {(outer, groups, inner)} must be positive with product {points}, a segment's points")
+        if accum is not None and (accum.dtype != torch.float64 or tuple(accum.shape) != (5, nseg, groups) or not accum.is_contiguous()
+                                  or accum.device != dev):
+            raise ValueError(f"accum must be a contiguous float64 (5, {nseg}, {groups}) tensor on {dev}")
+        out = torch.empty(5, nseg, groups, dtype=torch.float64, device=dev)
+        self._check(self._lib.dyf_ensemble_scores(self._h, nseg, (C.c_void_p * nseg)(*p_ptrs), (C.c_void_p * nseg)(*t_ptrs), n, points,
+                                                  stride, outer, groups, inner, out.data_ptr(),
+                                                  accum.data_ptr() if accum is not None else None, self._stream()))
         del keep  # as in trajectory_metrics
         return out
 

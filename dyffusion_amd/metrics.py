@@ -3,9 +3,12 @@
 makes the reference's `.cpu().numpy()` round trip.  The reductions run in `ensemble_metrics_kernel` (kernels.hip) through
 `dyf_ensemble_metrics`, and per segment (`mean_over_samples=False`, the test epoch of the physical-systems benchmark) in
 `trajectory_metrics_kernel` through `dyf_trajectory_metrics`; as a function of the ensemble size (the first n members, n = 1..N, and
-every member's own MSE) in `ensemble_size_metrics_kernel` through `dyf_ensemble_size_metrics`.  There is no CPU fallback."""
+every member's own MSE) in `ensemble_size_metrics_kernel` through `dyf_ensemble_size_metrics`; per variable, per sample or over any
+other contiguous run of kept axes (`mean_dims`), together with the Gaussian NLL and the correlation, in `ensemble_scores_kernel`
+through `dyf_ensemble_scores`.  There is no CPU fallback."""
+import math
 from collections import defaultdict
-from typing import Dict, Optional, Sequence
+from typing import Dict, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -15,6 +18,7 @@ from .engine import HipEngine
 
 METRIC_ROWS = ("mse", "ssr", "crps")  # row order of the (3, T) tensors of HipEngine.trajectory_metrics
 SIZE_ROWS = METRIC_ROWS + ("mse_per_mem",)  # plane order of the (4, T, N) tensors of HipEngine.ensemble_size_metrics
+SCORE_ROWS = ("mse", "ssr", "crps", "nll", "corr")  # plane order of the (5, T, G) tensors of HipEngine.ensemble_scores
 
 
 def evaluate_ensemble_prediction(predictions: Tensor, targets: Tensor, engine: HipEngine, mean_over_samples: bool = True,
@@ -89,10 +93,150 @@ def eval_ensemble_size_curves(results: Dict[str, Tensor], engine: HipEngine, spl
     return out
 
 
-def eval_ensemble_predictions(results: Dict[str, Tensor], engine: HipEngine, split: str = "val",
-                              infix: Optional[str] = None) -> Dict[str, float]:
+def mean_dims_to_group_shape(shape: Sequence[int], mean_dims) -> Optional[Tuple[int, int, Tuple[int, int, int]]]:
+    """`mean_dims` (axes of `targets`, as numpy takes them: None, an int or a sequence, negatives from the end) on a target of
+    `shape` -> None when every axis is averaged, else (a, b, (outer, groups, inner)): the kept axes must be ONE contiguous run
+    [a..b], which is the row-major view outer = prod(shape[:a]), groups = prod(shape[a:b+1]), inner = prod(shape[b+1:]) of
+    `HipEngine.ensemble_scores`.  Kept axes with a gap are refused (NotImplementedError)."""
+    nd = len(shape)
+    if mean_dims is None:
+        return None
+    dims = (mean_dims,) if isinstance(mean_dims, int) else tuple(mean_dims)
+    for d in dims:
+        if not isinstance(d, int) or not -nd <= d < nd:
+            raise ValueError(f"mean_dims {mean_dims!r}: axis {d!r} is out of bounds for targets of dimension {nd}")
+    averaged = {d % nd for d in dims}
+    if len(averaged) != len(dims):
+        raise ValueError(f"mean_dims {mean_dims!r}: repeated axis")
+    kept = [d for d in range(nd) if d not in averaged]
+    if not kept:
+        return None
+    a, b = kept[0], kept[-1]
+    if kept != list(range(a, b + 1)):
+        raise NotImplementedError(f"mean_dims {mean_dims!r} keeps the axes {kept} of targets: the kept axes must be one contiguous run "
+                                  "[a..b] (outer = prod(shape[:a]), groups = prod(shape[a:b+1]), inner = prod(shape[b+1:]))")
+    return a, b, (math.prod(shape[:a]), math.prod(shape[a:b + 1]), math.prod(shape[b + 1:]))
+
+
+def _scores(predictions, targets, engine: HipEngine, mean_dims) -> Dict[str, object]:
+    """One `ensemble_scores` call -> {score: host float | float64 device tensor}, in SCORE_ROWS order.  `predictions` /
+    `targets` are one (N, B, ...) / (B, ...) pair, or equally long lists of such pairs of one shape (several horizons): those go
+    through as the segments of the one call and lead the result's shape."""
+    many = not torch.is_tensor(predictions)
+    plist, tlist = (list(predictions), list(targets)) if many else ([predictions], [targets])
+    if many and (len(plist) != len(tlist) or not plist):
+        raise ValueError(f"{len(plist)} prediction horizons but {len(tlist)} target horizons")
+    for p, t in zip(plist, tlist):
+        if p.shape[1] != t.shape[0]:
+            raise AssertionError(f"predictions.shape[1] ({p.shape[1]}) != targets.shape[0] ({t.shape[0]})")
+        if not p.is_cuda or not t.is_cuda:
+            raise ValueError("dyffusion_amd.metrics works on GPU tensors (the HIP engine computes them)")
+    shape = tuple(tlist[0].shape)
+    grouped = mean_dims_to_group_shape(shape, mean_dims)
+    if grouped is None:
+        pooled = engine.ensemble_scores(plist, tlist)[:, :, 0].cpu().numpy()  # (5, T)
+        return {m: (pooled[i] if many else float(pooled[i, 0])) for i, m in enumerate(SCORE_ROWS)}
+    a, b, group_shape = grouped
+    out = engine.ensemble_scores(plist, tlist, group_shape=group_shape)  # (5, T, G)
+    out = out.reshape(5, len(plist), *shape[a:b + 1]) if many else out.reshape(5, *shape[a:b + 1])
+    return {m: out[i] for i, m in enumerate(SCORE_ROWS)}
+
+
+def evaluate_ensemble_scores(predictions, targets, engine: HipEngine, mean_dims=None) -> Dict[str, object]:
+    """All five scores of evaluation.py's `mean_dims` surface in one pass of `ensemble_scores_kernel`: {"mse", "ssr", "crps", "nll",
+    "corr"}.  predictions (n_members, n_samples, *), targets (n_samples, *), on the engine's GPU.  `mean_dims` are the axes of
+    `targets` to average over, as in the reference: None or all axes gives host floats; otherwise the kept axes must be one
+    contiguous run [a..b] (`mean_dims_to_group_shape`; (0, 2, 3) on (B, C, H, W) is per channel, (1, 2, 3) per sample) and every
+    score is a float64 device tensor of shape targets.shape[a:b+1], nothing synchronised; other sets raise NotImplementedError.
+    Lists of equally shaped horizons go through as the segments of one call and give a leading axis (host arrays when pooled).
+    "corr" is the correlation over the points of a group, which the reference only has for all axes."""
+    return _scores(predictions, targets, engine, mean_dims)
+
+
+def evaluate_ensemble_mse(predictions, targets, engine: HipEngine, mean_dims=None):
+    """evaluation.py:133-136: the MSE of the ensemble mean over `mean_dims` (see `evaluate_ensemble_scores`)."""
+    return _scores(predictions, targets, engine, mean_dims)["mse"]
+
+
+def evaluate_ensemble_spread_skill_ratio(predictions, targets, engine: HipEngine, skill_metric=None, mean_dims=None):
+    """evaluation.py:99-120: sqrt(mean over `mean_dims` of the members' population variance) / skill, the skill being the RMSE of the
+    ensemble mean over the same axes unless `skill_metric` (a number, or anything that broadcasts against the result) is given."""
+    s = _scores(predictions, targets, engine, mean_dims)
+    if skill_metric is None:
+        return s["ssr"]
+    if torch.is_tensor(s["ssr"]):
+        return s["ssr"] * torch.sqrt(s["mse"]) / torch.as_tensor(skill_metric, dtype=torch.float64, device=s["ssr"].device)
+    spread = s["ssr"] * np.sqrt(s["mse"])
+    return spread / (skill_metric.cpu().numpy() if torch.is_tensor(skill_metric) else skill_metric)
+
+
+def evaluate_ensemble_nll(predictions, targets, engine: HipEngine, mean_dims=None):
+    """evaluation.py:123-130: the Gaussian negative log-likelihood 0.5 log(2 pi var) + (y - mean)^2 / (2 var), averaged over
+    `mean_dims`.  It takes the ENSEMBLE (n_members, n_samples, *): the kernel computes the ensemble mean and the population variance
+    (np.var over the members, evaluation.py:76) that the reference's function is handed.  One member has var = 0: NaN, as numpy."""
+    return _scores(predictions, targets, engine, mean_dims)["nll"]
+
+
+def evaluate_ensemble_crps(predictions, targets, engine: HipEngine, mean_over_samples: bool = True):
+    """evaluation.py:83-96: the ensemble CRPS over all axes (a host float), or with `mean_over_samples=False` per sample: a float64
+    device tensor (n_samples,), nothing synchronised."""
+    nd = targets.dim() if torch.is_tensor(targets) else targets[0].dim()
+    return _scores(predictions, targets, engine, None if mean_over_samples else tuple(range(1, nd)))["crps"]
+
+
+def evaluate_ensemble_corr(predictions, targets, engine: HipEngine):
+    """evaluation.py:139-142: the Pearson correlation of the ensemble mean with the targets over all points (a host float; NaN
+    where either is constant, as np.corrcoef)."""
+    return _scores(predictions, targets, engine, None)["corr"]
+
+
+def _horizon_pairs(results: Dict[str, Tensor]):
+    """(prefix, predictions key, targets key) of every `t{k}_preds` / `t{k}_targets` pair, in the order of `results`."""
+    for key in [k for k in results if k.endswith("preds")]:
+        prefix = key.split("_")[0] if key != "preds" else ""
+        tkey = f"{prefix}_targets" if prefix else "targets"
+        if tkey in results:
+            yield prefix, key, tkey
+
+
+def _eval_extended(results: Dict[str, Tensor], engine: HipEngine, stem: str, extended: bool, per_channel: bool) -> Dict[str, float]:
+    """The keys that `extended` / `per_channel` add to `eval_ensemble_predictions`; horizons of equal shape are the segments of one
+    `ensemble_scores` call per flag."""
+    shapes: Dict[tuple, list] = {}
+    for prefix, key, tkey in _horizon_pairs(results):
+        shapes.setdefault((tuple(results[key].shape), tuple(results[tkey].shape)), []).append((prefix, key, tkey))
+    out: Dict[str, float] = {}
+    acc = defaultdict(list)
+    for (_, tshape), members in shapes.items():
+        plist, tlist = [results[k] for _, k, _ in members], [results[t] for _, _, t in members]
+        if extended:
+            pooled = engine.ensemble_scores(plist, tlist).cpu().numpy()  # (5, segments, 1)
+            for s, (prefix, _, _) in enumerate(members):
+                for m in ("nll", "corr"):
+                    v = float(pooled[SCORE_ROWS.index(m), s, 0])
+                    out[f"{stem}{prefix}/{m}"] = v
+                    acc[f"{stem}avg/{m}"].append(v)
+        if per_channel:  # targets (B, C, ...); without a channel axis (at most two axes) the one channel is everything
+            b, c = (tshape[0], tshape[1]) if len(tshape) >= 3 else (1, 1)
+            per_c = engine.ensemble_scores(plist, tlist, group_shape=(b, c, math.prod(tshape) // (b * c))).cpu().numpy()
+            for s, (prefix, _, _) in enumerate(members):
+                for j in range(c):
+                    for i, m in enumerate(SCORE_ROWS):
+                        v = float(per_c[i, s, j])
+                        out[f"{stem}{prefix}/c{j}/{m}"] = v
+                        acc[f"{stem}avg/c{j}/{m}"].append(v)
+    for k, v in acc.items():
+        out[k] = float(sum(v) / len(v))
+    return out
+
+
+def eval_ensemble_predictions(results: Dict[str, Tensor], engine: HipEngine, split: str = "val", infix: Optional[str] = None,
+                              extended: bool = False, per_channel: bool = False) -> Dict[str, float]:
     """_base_experiment.py:617-640: per-horizon metrics `{split}/{infix}t{k}/{m}` for every `t{k}_preds`/`t{k}_targets`
-    pair of an evaluation step's output, plus their average over horizons `{split}/{infix}avg/{m}`."""
+    pair of an evaluation step's output, plus their average over horizons `{split}/{infix}avg/{m}`.  `extended` adds
+    `{split}/{infix}t{k}/nll` and `/corr` with their `avg`; `per_channel` adds `{split}/{infix}t{k}/c{j}/{m}` for the five scores
+    of SCORE_ROWS and every channel j of (B, C, ...) targets, and `{split}/{infix}avg/c{j}/{m}` (both from `ensemble_scores_kernel`;
+    the keys above keep their values and their kernel)."""
     infix = "" if infix is None else infix
     out: Dict[str, float] = {}
     acc = defaultdict(list)
@@ -106,6 +250,8 @@ def eval_ensemble_predictions(results: Dict[str, Tensor], engine: HipEngine, spl
             acc[f"{split}/{infix}avg/{m}"].append(v)
     for k, v in acc.items():
         out[k] = float(sum(v) / len(v))
+    if extended or per_channel:
+        out.update(_eval_extended(results, engine, f"{split}/{infix}", extended, per_channel))
     return out
 
 

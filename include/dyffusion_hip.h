@@ -313,6 +313,28 @@ dyf_status dyf_trajectory_metrics(dyf_engine* engine, int32_t n_segments, const 
 dyf_status dyf_ensemble_size_metrics(dyf_engine* engine, int32_t n_segments, const float* const* preds_dev,
                                      const float* const* targets_dev, int32_t n_members, int64_t n_points, int64_t member_stride,
                                      double* out_dev, double* accum_dev, void* stream);
+/* Five scores per (segment, GROUP) in one pass: the mean_dims surface of evaluation.py (evaluate_ensemble_mse,
+ * evaluate_ensemble_spread_skill_ratio, evaluate_ensemble_crps, evaluate_ensemble_nll, evaluate_ensemble_corr; :83-142).  Segments,
+ * member_stride and the two host arrays of device pointers as in dyf_trajectory_metrics.  The n_points points of a segment are viewed
+ * as row-major (n_outer, n_groups, n_inner), n_outer * n_groups * n_inner == n_points: point p belongs to group
+ * (p / n_inner) % n_groups; (1, 1, n_points) pools the segment, (B, C, H * W) on a (B, C, H, W) target is the per-channel score,
+ * (1, B, C * H * W) the per-sample score.  out_dev (device, [5][n_segments][n_groups]) receives per group
+ *   mse   mean of (ensemble mean - y)^2            ssr   sqrt(mean population variance) / sqrt(mse)
+ *   crps  mean of the ensemble CRPS                nll   mean of 0.5 log(2 pi var) + (mean - y)^2 / (2 var): the Gaussian NLL under the
+ *   corr  Pearson correlation of the ensemble mean with y                                                ensemble mean and variance
+ * accum_dev (device, the same shape, or NULL) += out.  mean, var and crps per point are the fp32 expressions of
+ * dyf_trajectory_metrics, nll is fp32 with the accurate logarithm, sums over points and the correlation's moments (centred per
+ * workgroup, joined pairwise) are fp64.  IEEE behaviour as numpy, nothing is clamped: one member has var = 0 and a NaN nll, a group
+ * whose ensemble means or targets are constant has a NaN corr.  Two launches on `stream`, no atomics, partial sums in an
+ * engine-owned workspace of 9 doubles per workgroup: a group's values depend on its own points, n_members, n_outer and n_inner
+ * alone -- not on the other groups or segments, nor on the layout -- and identical calls give identical bits.  Does NOT
+ * synchronise.  n_members in [1, 15360], n_segments in [1, 65535]; a segment takes n_outer * n_groups * ceil(n_inner / P)
+ * workgroups, P = 256 points up to 64 members (beyond: the largest power of two with n_members * P * 4 <= 60 KB), and at most
+ * 2^24 - 1 of them: DYF_ERR_UNSUPPORTED beyond.  A geometry whose product is not n_points is DYF_ERR_INVALID_ARGUMENT.
+ * (Additive: no ABI change.) */
+dyf_status dyf_ensemble_scores(dyf_engine* engine, int32_t n_segments, const float* const* preds_dev,
+                               const float* const* targets_dev, int32_t n_members, int64_t n_points, int64_t member_stride,
+                               int64_t n_outer, int32_t n_groups, int64_t n_inner, double* out_dev, double* accum_dev, void* stream);
 /* Copy one (NB,C,H,W) field of the sampler's state after the most recent dyf_sample call: what sample_loop returns
  * beside the intermediates (dyffusion.py:424-426): (x0_hat, ., x_s), or (x_s, ., x_interpolated_s_next) when the sampling
  * schedule stops before T-1. */
