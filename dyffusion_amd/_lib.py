@@ -103,6 +103,24 @@ class ConvEx(C.Structure):
                 ("drop_p", C.c_float), ("drop_site", C.c_int32), ("drop_row_offset", C.c_uint32), ("drop_forward", C.c_uint32)]
 
 
+class ConvGn(C.Structure):
+    """dyf_conv_gn (include/dyffusion_hip_testing.h): one 3x3 conv in front of a GroupNorm for dyf_op_conv_gn."""
+    _fields_ = [(k, C.c_int32) for k in ("n", "h", "w", "c0", "c1", "cout", "groups", "want", "act", "coef_div", "n_sel", "invariant",
+                                         "film_stride", "drop_mode")] + \
+               [("drop_p", C.c_float), ("drop_site", C.c_int32), ("drop_row_offset", C.c_uint32), ("drop_forward", C.c_uint32)] + \
+               [(k, C.c_int32) for k in ("conv_tag", "max_slots", "new_forward")]
+
+
+class ConvGnTensors(C.Structure):
+    """dyf_conv_gn_tensors: the device pointers of one dyf_op_conv_gn call; NULL = absent."""
+    _fields_ = [(k, C.c_void_p) for k in ("x0", "x1", "residual", "film_a", "film_c", "mask", "y", "gran", "epoch", "part")] + \
+               [("gran_granules", C.c_int64), ("part_floats", C.c_int64)]
+
+
+class ConvGnResult(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("fused", "slots", "bm", "slow_sweep")]
+
+
 BC_NAVIER_STOKES, BC_SPRING_MESH = 0, 1
 COMM_ID_BYTES = 128  # DYF_COMM_ID_BYTES (ncclUniqueId)
 TRAIN_BATCH_STATS, TRAIN_DROPOUT = 1, 2
@@ -197,6 +215,7 @@ SYMBOLS = [
                                              C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     ("dyf_op_conv2d", C.c_int, [_P, _P, _P] + [C.c_int32] * 9 + [_P, _P, C.c_int32, C.c_int32, _P, _P]),
     ("dyf_op_conv2d_ex", C.c_int, [_P, _P, _P] + [C.c_int32] * 9 + [_P, _P, C.c_int32, C.c_int32, _P, C.POINTER(ConvEx), _P]),
+    ("dyf_op_conv_gn", C.c_int, [_P, C.POINTER(ConvGn), C.POINTER(ConvGnTensors), _P, _P, _P, _P, C.POINTER(ConvGnResult), _P]),
     ("dyf_op_upconv2d", C.c_int, [_P, _P, _P] + [C.c_int32] * 5 + [_P, _P, C.c_int32, _P, _P]),
     ("dyf_op_linear_attention", C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P]),
     ("dyf_op_linear_attention_fused", C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P]),

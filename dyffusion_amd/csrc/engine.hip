@@ -2188,6 +2188,124 @@ dyf_status dyf_op_conv2d_ex(dyf_engine* e, const uint16_t* x_dev, const float* w
     return rs;
 }
 
+// The 3x3 convs in front of a GroupNorm through launch_conv_gn_fused (want 0: the ConvArgs of rn_forward's conv_gn) or launch_conv_stats
+// (want 1: those of rconv with a gn_part buffer).  The sweeps' error words are the call's own, never the engine's.
+dyf_status dyf_op_conv_gn(dyf_engine* e, const dyf_conv_gn* desc, const dyf_conv_gn_tensors* t, const float* w_host, const float* bias_host,
+                          const float* gamma_host, const float* beta_host, dyf_conv_gn_result* out, void* stream) {
+    auto bad = [&](const char* m) { return fail(e, DYF_ERR_INVALID_ARGUMENT, std::string("dyf_op_conv_gn: ") + m); };
+    auto unsup = [&](const char* m) { return fail(e, DYF_ERR_UNSUPPORTED, std::string("dyf_op_conv_gn: ") + m); };
+    if (!e || !desc || !t || !out || !w_host || !bias_host || !t->x0 || !t->y) return bad("null argument");
+    const dyf_conv_gn& d = *desc;
+    *out = dyf_conv_gn_result{};
+    if (d.want != 0 && d.want != 1) return bad("want: 0 fused, 1 stats");
+    const bool fuse = d.want == 0;
+    if (d.n < 1 || d.h < 1 || d.w < 1 || d.c0 < 1 || d.c1 < 0 || d.cout < 1) return bad("bad conv geometry");
+    if ((d.c1 > 0) != (t->x1 != nullptr)) return bad("second source: x1 and c1 > 0 go together");
+    if (d.n_sel < 0 || d.coef_div < 0) return bad("coef_div / n_sel must not be negative");
+    if (d.cout % 8 != 0) return unsup("the statistics are kept per 8-channel octet (cout % 8)");
+    if (fuse) {
+        if (!gamma_host || !beta_host || !t->gran || !t->epoch) return bad("the fused entry needs gamma, beta, gran and epoch");
+        if (d.groups < 1) return bad("groups must be positive");
+        if (d.act < ACT_NONE || d.act > ACT_GELU) return bad("act outside 0..4");
+        if (d.conv_tag < 1 || d.conv_tag > 255) return bad("conv_tag is the 8-bit index of a conv inside its forward: 1..255");
+        if (d.max_slots < 1) return bad("max_slots must be positive");
+        if ((t->film_a == nullptr) != (t->film_c == nullptr)) return bad("film_a and film_c go together");
+        if (t->film_a ? d.film_stride < d.cout : d.film_stride != 0) return bad("film_stride: >= cout with FiLM rows, 0 without");
+        if (d.coef_div > 1 && !t->film_a) return bad("coef_div without FiLM rows");
+        if (d.invariant != 0 && d.invariant != 1) return bad("invariant: 0 or 1");
+        if (t->part || t->part_floats) return bad("part belongs to want 1");
+        if ((long long)d.n * d.max_slots * (d.cout / 8) * 2 > t->gran_granules) return bad("gran holds fewer than n * max_slots * (cout / 8) * 2 granules");
+        dyf_status ds = op_drop_check(e, d.n, d.drop_mode, d.drop_p, t->mask, d.drop_site);
+        if (ds != DYF_OK) return ds;
+    } else {
+        if (d.groups || d.act || d.coef_div || d.invariant || d.film_stride || d.drop_mode || d.drop_p != 0.0f || d.drop_site || d.drop_row_offset ||
+            d.drop_forward || d.conv_tag || d.max_slots || d.new_forward || t->residual || t->film_a || t->film_c || t->mask || t->gran || t->epoch ||
+            t->gran_granules || gamma_host || beta_host)
+            return bad("want 1 takes the geometry, n_sel, the sources, y and part: every other field must be 0 / NULL");
+        if (!t->part) return bad("want 1 needs part");
+        // the one form that writes statistics leaves conv_halo5_gn_slots slots per sample
+        if ((long long)d.n * conv_halo5_gn_slots(d.h, d.w) * (d.cout / 8) * 2 > t->part_floats) return bad("part holds fewer than n * slots * (cout / 8) * 2 floats");
+    }
+    const int cin = d.c0 + d.c1;
+    if ((long long)d.n * d.h * d.w * d.cout >= 0xFFFFFFF0ll || (long long)d.n * d.h * d.w * std::max(d.c0, d.c1) >= 0x7F000000ll / 2)
+        return unsup("tensor too large for the kernels' 32-bit element indices");
+    HIP_TRY(e, hipSetDevice(e->cfg.device));
+    hipStream_t st = (hipStream_t)stream;
+    uint32_t *err_host = nullptr, *err_dev = nullptr;
+    if (fuse) {  // this call's error words: host-visible like the engine's (gn_fused.h GnFuse::err)
+        HIP_TRY(e, hipHostMalloc((void**)&err_host, 64, hipHostMallocMapped));
+        memset(err_host, 0, 64);
+        if (hipHostGetDevicePointer((void**)&err_dev, err_host, 0) != hipSuccess) {
+            (void)hipHostFree(err_host);
+            return fail(e, DYF_ERR_HIP, "dyf_op_conv_gn: no device alias of the error words");
+        }
+    }
+    std::vector<void*> tmp;
+    dyf_status rs = [&]() -> dyf_status {
+        AllocScope scope(e, &tmp);
+        ConvW wts;
+        dyf_status us = upload_conv_weights(e, &wts, pack_conv(w_host, d.cout, cin, 9), d.cout, 9, cin);
+        float *ones = nullptr, *bias = nullptr, *gamma = nullptr, *beta = nullptr;
+        if (us == DYF_OK) us = dev_upload(e, &ones, std::vector<float>(d.cout, 1.0f));
+        if (us == DYF_OK) us = dev_upload(e, &bias, std::vector<float>(bias_host, bias_host + d.cout));
+        if (us == DYF_OK && fuse) us = dev_upload(e, &gamma, std::vector<float>(gamma_host, gamma_host + d.cout));
+        if (us == DYF_OK && fuse) us = dev_upload(e, &beta, std::vector<float>(beta_host, beta_host + d.cout));
+        if (us != DYF_OK) return us;
+        ConvArgs a{};
+        a.src0 = t->x0; a.c0 = d.c0; a.src1 = t->x1; a.c1 = d.c1; a.n = d.n; a.h = d.h; a.w = d.w; a.ho = d.h; a.wo = d.w;
+        a.kh = 3; a.kw = 3; a.stride = 1; a.pad = 1; a.cout = d.cout;
+        a.coef_a = ones; a.coef_c = bias; a.coef_stride = 0;
+        a.out_el16 = t->y;
+        a.n_sel = d.n_sel;
+        if (!fuse) {  // rconv with a gn_part buffer
+            a.act = ACT_NONE;
+            a.splitk_ws = e->ws.splitk; a.splitk_cap = e->ws.splitk ? DYF_SPLITK_FLOATS : 0;
+            a.gn_part = t->part;
+            int slots = 0;
+            HIP_TRY(e, launch_conv_stats(a, wts, conv_path(e, a), st, &slots));
+            HIP_TRY(e, hipStreamSynchronize(st));
+            out->fused = 1;
+            out->slots = slots;
+            return DYF_OK;
+        }
+        // rn_forward's conv_gn
+        a.coef_div = d.coef_div;
+        a.act = d.act; a.residual = t->residual;
+        us = op_drop_arm(e, d.n, d.drop_mode, d.drop_p, t->mask, d.drop_site, d.drop_row_offset, d.drop_forward, st, &a.drop);
+        if (us != DYF_OK) return us;
+        a.gnf.gran = t->gran; a.gnf.epoch = t->epoch; a.gnf.conv_tag = (uint32_t)d.conv_tag;
+        a.gnf.max_slots = d.max_slots; a.gnf.groups = d.groups; a.gnf.bias = bias; a.gnf.gamma = gamma; a.gnf.beta = beta;
+        if (t->film_a) { a.gnf.film_a = t->film_a; a.gnf.film_c = t->film_c; a.gnf.film_stride = d.film_stride; }
+        a.gnf.err = err_dev;
+        a.gnf.invariant = d.invariant;
+        const int path = conv_path(e, a);
+        {  // what the entry point is about to choose, for the report (conv_choose_form launches nothing; launch_conv_gn_fused asks it the same way)
+            ConvArgs q = a;
+            q.wpk = wts.wpk;
+            const ConvChoice c = conv_choose_form(q, wts, path, ConvWant::GnFused);
+            out->slots = c.form != ConvForm::None && c.form != ConvForm::Invalid ? c.gn_slots : 0;
+            out->bm = c.bm;
+        }
+        if (d.new_forward) HIP_TRY(e, launch_gn_epoch_bump(t->epoch, st));
+        bool fused = false;
+        HIP_TRY(e, launch_conv_gn_fused(a, wts, path, st, &fused));
+        HIP_TRY(e, hipStreamSynchronize(st));
+        out->fused = fused ? 1 : 0;
+        if (!fused) out->slots = out->bm = 0;
+        return DYF_OK;
+    }();
+    if (rs != DYF_OK) (void)hipDeviceSynchronize();  // (a failed launch: nothing of `tmp` may still be read when it is freed)
+    release_allocs(tmp);
+    if (err_host) {
+        const bool timed_out = ((volatile uint32_t*)err_host)[0] != 0u;
+        out->slow_sweep = ((volatile uint32_t*)err_host)[1] != 0u ? 1 : 0;
+        (void)hipHostFree(err_host);
+        if (rs == DYF_OK && timed_out)
+            rs = fail(e, DYF_ERR_STATE, "dyf_op_conv_gn: a granule sweep timed out waiting for its sample's statistics (the output is NaN-poisoned)");
+    }
+    return rs;
+}
+
 dyf_status dyf_op_upconv2d(dyf_engine* e, const uint16_t* x_dev, const float* w_host, int32_t n, int32_t h, int32_t w,
                            int32_t cin, int32_t cout, const float* scale_dev, const float* shift_dev, int32_t act,
                            uint16_t* y_dev, void* stream) {

@@ -689,6 +689,91 @@ class HipEngine:
                                                None if y is None else y.data_ptr(), C.byref(ex), self._stream()))
         return (y, y32) if out16 and out_f32 else y if out16 else y32
 
+    def op_conv_gn(self, x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, gamma: Optional[torch.Tensor] = None,
+                   beta: Optional[torch.Tensor] = None, *, groups: int = 0, want: str = "fused", x1: Optional[torch.Tensor] = None,
+                   residual: Optional[torch.Tensor] = None, film_a: Optional[torch.Tensor] = None, film_c: Optional[torch.Tensor] = None,
+                   coef_div: int = 0, n_sel: int = 0, invariant: bool = False, act: int = 3, gran: Optional[torch.Tensor] = None,
+                   epoch: Optional[torch.Tensor] = None, conv_tag: int = 0, max_slots: int = 0, new_forward: bool = False,
+                   part: Optional[torch.Tensor] = None, y: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None,
+                   p: float = 0.0, rng_site: Optional[int] = None, rng_row_offset: int = 0, rng_forward: int = 0):
+        """Test seam (dyf_op_conv_gn): one 3x3 conv in front of a GroupNorm through the entry point a ResnetBlock calls it by.
+        want="fused": launch_conv_gn_fused -- conv + bias -> GroupNorm(groups, gamma, beta) -> FiLM rows (film_a, film_c: fp32 device
+        (ceil(N / coef_div), stride >= cout)) -> SiLU -> Dropout -> + residual.  `gran` (int64 device, N * max_slots * (cout / 8) * 2
+        words) and `epoch` (int32 device, one word) are the CALLER's: zeroed once, kept across calls; a (forward, conv_tag) pair must
+        not repeat on one buffer, new_forward starts the next forward.  want="stats": launch_conv_stats -- y = conv + bias and the
+        per-octet partials in `part` (fp32 device (N, slots, cout / 8, 2), sized for the largest slot count).  x / x1 / residual: 16-bit
+        NHWC; weight (cout, c0 + c1, 3, 3) as it is (not standardised here); `y`: an output tensor to write into (else a new one).
+        Returns (y, info) with info = dict(fused, slots, bm, slow_sweep); fused == 0: nothing was launched and y is untouched."""
+        dt = self.torch_dtype
+        if want not in ("fused", "stats"):
+            raise ValueError(f"want: 'fused' or 'stats', not {want!r}")
+        if x.dtype != dt or not x.is_cuda or not x.is_contiguous() or x.dim() != 4:
+            raise ValueError(f"x: a contiguous NHWC device tensor of dtype {dt}")
+        n, h, w, c0 = x.shape
+        c1 = 0
+        desc, tens, res = L.ConvGn(), L.ConvGnTensors(), L.ConvGnResult()
+        if x1 is not None:
+            if x1.dtype != dt or not x1.is_cuda or not x1.is_contiguous() or x1.shape[:3] != x.shape[:3]:
+                raise ValueError("x1: a contiguous 16-bit device tensor over x's (N, H, W)")
+            c1 = x1.shape[3]
+            tens.x1 = x1.data_ptr()
+        cout = weight.shape[0]
+        if tuple(weight.shape) != (cout, c0 + c1, 3, 3):
+            raise ValueError(f"weight must be ({cout}, {c0 + c1}, 3, 3)")
+        host = lambda t_: None if t_ is None else np.ascontiguousarray(t_.detach().to("cpu", torch.float32).numpy()).reshape(-1)
+        wh, bh, gh, beh = host(weight), host(bias), host(gamma), host(beta)
+        if any(v is not None and v.size != cout for v in (bh, gh, beh)) or bh is None:
+            raise ValueError(f"bias / gamma / beta hold {cout} values")
+        if y is None:
+            y = torch.empty((n, h, w, cout), dtype=dt, device=x.device)
+        elif y.dtype != dt or not y.is_cuda or not y.is_contiguous() or tuple(y.shape) != (n, h, w, cout):
+            raise ValueError("y: a contiguous 16-bit device tensor (N, H, W, cout)")
+        desc.n, desc.h, desc.w, desc.c0, desc.c1, desc.cout = n, h, w, c0, c1, cout
+        desc.want, desc.n_sel = (0 if want == "fused" else 1), int(n_sel)
+        tens.x0, tens.y = x.data_ptr(), y.data_ptr()
+        keep = []  # tensors the call reads: alive until it returns
+        if want == "fused":
+            desc.groups, desc.act, desc.coef_div, desc.invariant = int(groups), int(act), int(coef_div), int(bool(invariant))
+            desc.conv_tag, desc.max_slots, desc.new_forward = int(conv_tag), int(max_slots), int(bool(new_forward))
+            if gran is None or epoch is None or gran.dtype != torch.int64 or epoch.dtype != torch.int32 or not gran.is_cuda or not epoch.is_cuda \
+                    or not gran.is_contiguous() or epoch.numel() < 1:
+                raise ValueError("gran: int64 device words, epoch: an int32 device word, both owned by the caller")
+            tens.gran, tens.epoch, tens.gran_granules = gran.data_ptr(), epoch.data_ptr(), gran.numel()
+            if (film_a is None) != (film_c is None):
+                raise ValueError("film_a and film_c go together")
+            if film_a is not None:
+                film_a, film_c = _f32c(film_a, "film_a"), _f32c(film_c, "film_c")
+                rows = -(-n // coef_div) if coef_div > 1 else n
+                if film_a.dim() != 2 or film_a.shape != film_c.shape or film_a.shape[0] != rows:
+                    raise ValueError(f"film rows must be ({rows}, stride) fp32")
+                desc.film_stride = film_a.shape[1]
+                tens.film_a, tens.film_c = film_a.data_ptr(), film_c.data_ptr()
+                keep += [film_a, film_c]
+            if residual is not None:
+                if residual.dtype != dt or not residual.is_cuda or not residual.is_contiguous() or tuple(residual.shape) != (n, h, w, cout):
+                    raise ValueError("residual: a contiguous 16-bit device tensor of the output's shape")
+                tens.residual = residual.data_ptr()
+            desc.drop_p = float(p)
+            if mask is not None and rng_site is not None:
+                raise ValueError("mask or rng_site, not both")
+            if mask is not None:
+                if mask.dtype != torch.uint8 or not mask.is_cuda or not mask.is_contiguous() or tuple(mask.shape) != (n, h, w, cout):
+                    raise ValueError("mask: a contiguous uint8 device tensor of the output's shape")
+                desc.drop_mode, tens.mask = 2, mask.data_ptr()
+            elif rng_site is not None:
+                desc.drop_mode, desc.drop_site, desc.drop_row_offset, desc.drop_forward = 1, int(rng_site), int(rng_row_offset), int(rng_forward)
+        else:
+            if part is None or part.dtype != torch.float32 or not part.is_cuda or not part.is_contiguous():
+                raise ValueError("want='stats' needs part: a contiguous fp32 device tensor")
+            if any(v is not None for v in (gamma, beta, residual, film_a, film_c, gran, epoch, mask, rng_site)) or groups or coef_div or invariant \
+                    or conv_tag or max_slots or new_forward or p:
+                raise ValueError("want='stats' takes the sources, weight, bias, n_sel, part and y")
+            tens.part, tens.part_floats = part.data_ptr(), part.numel()
+        fp = lambda a_: None if a_ is None else a_.ctypes.data
+        self._check(self._lib.dyf_op_conv_gn(self._h, C.byref(desc), C.byref(tens), fp(wh), fp(bh), fp(gh), fp(beh), C.byref(res), self._stream()))
+        del keep
+        return y, dict(fused=res.fused, slots=res.slots, bm=res.bm, slow_sweep=res.slow_sweep)
+
     def criterion(self, pred: torch.Tensor, target: torch.Tensor, kind: str = "l1") -> float:
         """Mean L1 / MSE / smooth-L1 between two fp32 device tensors (get_loss, src/utilities/utils.py:201-212)."""
         name = kind.lower().strip().replace("-", "_")

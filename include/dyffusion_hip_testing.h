@@ -80,6 +80,59 @@ dyf_status dyf_op_conv2d_ex(dyf_engine* engine, const uint16_t* x_dev, const flo
                             const float* scale_dev, const float* shift_dev, int32_t act, int32_t path, uint16_t* y_dev,
                             const dyf_conv_ex* ex, void* stream);
 
+/* The 3x3 convs that feed a GroupNorm, through the two entry points a ResnetBlock calls them by (csrc/conv.h): want 0 =
+ * launch_conv_gn_fused -- conv + bias -> GroupNorm -> FiLM -> SiLU -> Dropout (-> + residual) in ONE launch (csrc/gn_fused.h), want 1 =
+ * launch_conv_stats -- y = conv + bias, 16 bit, and the per-octet (sum, sum of squares) partials its epilogue leaves for GN_ACT.  The
+ * seam fills the ConvArgs as the ResNet-UNet forward fills them (3x3, stride 1, pad 1; coef_a = ones, coef_c = bias), uploads the weights
+ * with the engine's own upload (every fragment order a layer of this shape gets) and calls the ENTRY POINT, never a form's launcher:
+ * form choice, slots per sample and the tile height are the ladder's.  The weights are taken as they are (a caller that wants
+ * weight standardisation passes standardised weights, as the weight upload would).
+ *   desc      n, h, w, c0, c1 (second source behind the first, 0 = none), cout, groups; act (3 = SiLU, what the forward asks with: any
+ *             other value is handed to the ladder, which then fuses nothing); coef_div (samples per FiLM row), n_sel, invariant
+ *             (GnFuse::invariant), film_stride (floats per FiLM row, >= cout); dropout fields as dyf_conv_ex's -- mode 2 is handed to the
+ *             ladder: the fused forms take no injected mask; conv_tag 1..255 and max_slots (slot stride of `gran`); new_forward != 0 bumps
+ *             the epoch word first, as the head of a forward does.  want 1 uses n .. cout and n_sel; every other field must be 0
+ *   t         device tensors, 16-bit NHWC: x0 (n,h,w,c0), x1 (n,h,w,c1), residual and y (n,h,w,cout); film_a / film_c fp32
+ *             (ceil(n / coef_div) rows of film_stride); mask uint8 (n,h,w,cout) for mode 2.  gran: n * max_slots * (cout / 8) * 2
+ *             8-byte granules and epoch: one 32-bit word, both allocated by the CALLER, zeroed once and kept across calls -- the caller
+ *             owns the tag protocol (a (forward, conv_tag) pair must not repeat on one buffer); gran_granules = the buffer's capacity.
+ *             part (want 1): fp32 [n][slots][cout / 8][2], part_floats = its capacity (the seam refuses a buffer the launch could overrun)
+ *   host      weight (cout, c0 + c1, 3, 3), bias, gamma, beta (cout) fp32 (gamma / beta NULL for want 1)
+ *   out       fused: 0 = NOTHING was launched (want 1: always 1, the conv ran); slots: GnFuse::slots / the partial-sum slots per sample
+ *             (0: the form wrote no statistics); bm: GnFuse::bm (128 / 256 on the implicit-GEMM forms, else 0); slow_sweep: a sweep
+ *             needed more than 1 024 passes (the result is still correct)
+ * The sweeps' error words are the CALL's own (pinned, mapped, freed on return), never the engine's: a test cannot downgrade a live
+ * engine.  A sweep that timed out makes the call fail with DYF_ERR_STATE (its output is NaN-poisoned).  What the descriptor cannot
+ * express is refused (DYF_ERR_INVALID_ARGUMENT / DYF_ERR_UNSUPPORTED), never truncated.  Synchronises. */
+typedef struct dyf_conv_gn {
+    int32_t n, h, w, c0, c1, cout, groups;
+    int32_t want, act;
+    int32_t coef_div, n_sel, invariant, film_stride;
+    int32_t drop_mode;
+    float drop_p;
+    int32_t drop_site;
+    uint32_t drop_row_offset, drop_forward;
+    int32_t conv_tag, max_slots, new_forward;
+} dyf_conv_gn;
+typedef struct dyf_conv_gn_tensors {
+    const uint16_t* x0;
+    const uint16_t* x1;
+    const uint16_t* residual;
+    const float* film_a;
+    const float* film_c;
+    const uint8_t* mask;
+    uint16_t* y;
+    unsigned long long* gran;
+    uint32_t* epoch;
+    float* part;
+    int64_t gran_granules, part_floats;
+} dyf_conv_gn_tensors;
+typedef struct dyf_conv_gn_result {
+    int32_t fused, slots, bm, slow_sweep;
+} dyf_conv_gn_result;
+dyf_status dyf_op_conv_gn(dyf_engine* engine, const dyf_conv_gn* desc, const dyf_conv_gn_tensors* t, const float* weight_host,
+                          const float* bias_host, const float* gamma_host, const float* beta_host, dyf_conv_gn_result* out, void* stream);
+
 /* Upsample(x2, bilinear, align_corners=False) + Conv2d(3x3, pad 1) + epilogue in one kernel (phase-decomposed MFMA
  * implicit GEMM; unet_simple.py:40-52).  x_dev (N,H,W,Cin) bf16 -> y_dev (N,2H,2W,Cout) bf16. */
 dyf_status dyf_op_upconv2d(dyf_engine* engine, const uint16_t* x_dev, const float* w_host, int32_t n, int32_t h,
