@@ -103,6 +103,12 @@ class ConvEx(C.Structure):
                 ("drop_p", C.c_float), ("drop_site", C.c_int32), ("drop_row_offset", C.c_uint32), ("drop_forward", C.c_uint32)]
 
 
+class UpconvSparse(C.Structure):
+    """dyf_upconv_sparse (include/dyffusion_hip_testing.h): the needed-column mask of dyf_op_upconv2d_ex and the plan it reports."""
+    _fields_ = [("needed_host", C.c_void_p), ("col_map_host", C.c_void_p)] + \
+               [(k, C.c_int32) for k in ("planned", "ntiles", "npad", "nvalid0", "nvalid1", "wo_store")] + [("mix", C.c_int32 * 3)]
+
+
 class ConvGn(C.Structure):
     """dyf_conv_gn (include/dyffusion_hip_testing.h): one 3x3 conv in front of a GroupNorm for dyf_op_conv_gn."""
     _fields_ = [(k, C.c_int32) for k in ("n", "h", "w", "c0", "c1", "cout", "groups", "want", "act", "coef_div", "n_sel", "invariant",
@@ -217,6 +223,7 @@ SYMBOLS = [
     ("dyf_op_conv2d_ex", C.c_int, [_P, _P, _P] + [C.c_int32] * 9 + [_P, _P, C.c_int32, C.c_int32, _P, C.POINTER(ConvEx), _P]),
     ("dyf_op_conv_gn", C.c_int, [_P, C.POINTER(ConvGn), C.POINTER(ConvGnTensors), _P, _P, _P, _P, C.POINTER(ConvGnResult), _P]),
     ("dyf_op_upconv2d", C.c_int, [_P, _P, _P] + [C.c_int32] * 5 + [_P, _P, C.c_int32, _P, _P]),
+    ("dyf_op_upconv2d_ex", C.c_int, [_P, _P, _P] + [C.c_int32] * 5 + [_P, _P, C.c_int32, _P, C.POINTER(ConvEx), C.POINTER(UpconvSparse), _P]),
     ("dyf_op_linear_attention", C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P]),
     ("dyf_op_linear_attention_fused", C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P]),
     ("dyf_op_attention", C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P]),

@@ -639,6 +639,46 @@ dyf_status dyf_set_row_offset(dyf_engine* e, uint32_t first_row) {
     return DYF_OK;
 }
 
+// Column lists of the sparse halo form for a fused x2-upsample conv whose low-res plane is lh x lw: `needed` marks the 2 lw output
+// columns somebody reads.  One planner order for the weight upload (the last decoder block) and the op seam (dyf_op_upconv2d_ex);
+// the switches are read per call.  planned = false: the launch stays dense.
+struct UpSparsePlan {
+    std::vector<int16_t> cols, cbase, cidx, cmap;
+    int ntiles = 0, npad = 0, nvalid0 = 0, nvalid1 = 0, wo_store = 0;
+    int mix[3] = {0, 0, 0};
+    bool planned = false;
+};
+static UpSparsePlan plan_up_sparse(const std::vector<uint8_t>& needed, int lh, int lw) {
+    UpSparsePlan p;
+    int nt = 0, nv0 = 0, nv1 = 0;
+    // list tiles of 32 slots for the rows form of the halo kernel (conv_halo_rows.hip), 16 for conv_up_halo_kernel<1>
+    const bool rows_env = dyf_form_int("DYF_HALO_ROWS", 1) != 0;
+    int slots = rows_env && lh % 4 == 0 ? conv_halo_rows_slots() : 16;
+    int mix[3] = {0, 0, 0};
+    // mixed list tiling (no padded MFMA lanes: 52 entries = 3 x 16 + 4) first; DYF_SPARSE_MIXED=0: uniform tiles only
+    const bool mixed_env = dyf_form_int("DYF_SPARSE_MIXED", 1) != 0;
+    if (mixed_env && slots == conv_halo_rows_slots() &&
+        plan_up_sparse_columns_mixed(needed, lw, lh, p.cols, p.cbase, p.cidx, p.cmap, mix, nv0, nv1)) {
+        p.planned = true;
+        nt = mix[0] + mix[1] + mix[2];
+    }
+    if (!p.planned) {
+        mix[0] = mix[1] = mix[2] = 0;
+        p.planned = plan_up_sparse_columns(needed, lw, p.cols, p.cbase, p.cidx, p.cmap, nt, nv0, nv1, slots);
+        if (!p.planned && slots != 16) {
+            slots = 16;
+            p.planned = plan_up_sparse_columns(needed, lw, p.cols, p.cbase, p.cidx, p.cmap, nt, nv0, nv1, slots);
+        }
+    }
+    if (p.planned) {
+        p.ntiles = nt; p.npad = nt * slots; p.nvalid0 = nv0; p.nvalid1 = nv1;
+        p.mix[0] = mix[0]; p.mix[1] = mix[1]; p.mix[2] = mix[2];
+        if (mix[0] | mix[1] | mix[2]) p.npad = 32 * mix[0] + 16 * mix[1] + 4 * mix[2];
+        p.wo_store = nv0 + nv1;
+    }
+    return p;
+}
+
 static dyf_status load_weights_one(dyf_engine* e, int32_t which, int32_t n_tensors, const char* const* names,
                                    const float* const* data, const int64_t* const* shapes, const int32_t* ndims);
 
@@ -793,38 +833,16 @@ static dyf_status load_weights_one(dyf_engine* e, int32_t which, int32_t n_tenso
                         }
                     }
                 }
-                std::vector<int16_t> cols, cbase, cidx, cmap;
-                int nt = 0, nv0 = 0, nv1 = 0;
                 // the compact tensor is read by the MFMA form of the readout only (dim 64, <= 4 output channels)
-                // list tiles of 32 slots for the rows form of the halo kernel (conv_halo_rows.hip), 16 for conv_up_halo_kernel<1>
-                const bool rows_env = dyf_form_int("DYF_HALO_ROWS", 1) != 0;
-                int slots = rows_env && (b.out_h / 2) % 4 == 0 ? conv_halo_rows_slots() : 16;
-                bool planned = false;
-                int mix[3] = {0, 0, 0};
-                // mixed list tiling (no padded MFMA lanes: 52 entries = 3 x 16 + 4) first; DYF_SPARSE_MIXED=0: uniform tiles only
-                const bool mixed_env = dyf_form_int("DYF_SPARSE_MIXED", 1) != 0;
-                if (n.dim == 64 && n.cfg.out_channels <= 4 && mixed_env && slots == conv_halo_rows_slots() &&
-                    plan_up_sparse_columns_mixed(needed, iw / 2, b.out_h / 2, cols, cbase, cidx, cmap, mix, nv0, nv1)) {
-                    planned = true;
-                    nt = mix[0] + mix[1] + mix[2];
-                }
-                if (!planned && n.dim == 64 && n.cfg.out_channels <= 4) {
-                    mix[0] = mix[1] = mix[2] = 0;
-                    planned = plan_up_sparse_columns(needed, iw / 2, cols, cbase, cidx, cmap, nt, nv0, nv1, slots);
-                    if (!planned && slots != 16) {
-                        slots = 16;
-                        planned = plan_up_sparse_columns(needed, iw / 2, cols, cbase, cidx, cmap, nt, nv0, nv1, slots);
-                    }
-                }
-                if (planned) {
-                    UP(b.up_cols, cols);
-                    UP(b.up_cbase, cbase);
-                    UP(b.up_cidx, cidx);
-                    UP(b.up_col_map, cmap);
-                    b.up_ntiles = nt; b.up_npad = nt * slots; b.up_nvalid0 = nv0; b.up_nvalid1 = nv1;
-                    b.up_mix[0] = mix[0]; b.up_mix[1] = mix[1]; b.up_mix[2] = mix[2];
-                    if (mix[0] | mix[1] | mix[2]) b.up_npad = 32 * mix[0] + 16 * mix[1] + 4 * mix[2];
-                    b.up_wo_store = nv0 + nv1;
+                const UpSparsePlan sp = n.dim == 64 && n.cfg.out_channels <= 4 ? plan_up_sparse(needed, b.out_h / 2, iw / 2) : UpSparsePlan{};
+                if (sp.planned) {
+                    UP(b.up_cols, sp.cols);
+                    UP(b.up_cbase, sp.cbase);
+                    UP(b.up_cidx, sp.cidx);
+                    UP(b.up_col_map, sp.cmap);
+                    b.up_ntiles = sp.ntiles; b.up_npad = sp.npad; b.up_nvalid0 = sp.nvalid0; b.up_nvalid1 = sp.nvalid1;
+                    b.up_mix[0] = sp.mix[0]; b.up_mix[1] = sp.mix[1]; b.up_mix[2] = sp.mix[2];
+                    b.up_wo_store = sp.wo_store;
                 }
             }
         }
@@ -2355,6 +2373,117 @@ dyf_status dyf_op_upconv2d(dyf_engine* e, const uint16_t* x_dev, const float* w_
     (void)hipFree(border);
     if (ones) (void)hipFree(ones);
     if (zeros) (void)hipFree(zeros);
+    return rs;
+}
+
+// The fused x2-upsample conv with the ConvArgs of a decoder block of net_forward (second source = the skip, the engine's split-K
+// workspace, a border scratch of its own, sparse column lists from plan_up_sparse) through launch_conv: the form is the ladder's.
+dyf_status dyf_op_upconv2d_ex(dyf_engine* e, const uint16_t* x_dev, const float* w_host, int32_t n, int32_t h, int32_t w, int32_t c0,
+                              int32_t cout, const float* scale_dev, const float* shift_dev, int32_t act, uint16_t* y_dev,
+                              const dyf_conv_ex* ex, dyf_upconv_sparse* sparse, void* stream) {
+    auto bad = [&](const char* m) { return fail(e, DYF_ERR_INVALID_ARGUMENT, std::string("dyf_op_upconv2d_ex: ") + m); };
+    auto unsup = [&](const char* m) { return fail(e, DYF_ERR_UNSUPPORTED, std::string("dyf_op_upconv2d_ex: ") + m); };
+    const dyf_conv_ex none{};
+    const dyf_conv_ex& x = ex ? *ex : none;
+    if (!e || !x_dev || !w_host || (!y_dev && !x.y_f32_dev)) return bad("null argument");
+    if (n < 1 || h < 1 || w < 1 || c0 < 1 || cout < 1) return bad("bad conv geometry");
+    if (act < ACT_NONE || act > ACT_GELU) return bad("act outside 0..4");
+    if (x.c1 < 0 || (x.c1 > 0) != (x.x1_dev != nullptr)) return bad("second source: x1_dev and c1 > 0 go together");
+    if (x.coef_div < 0 || x.n_sel < 0) return bad("coef_div / n_sel must not be negative");
+    if (x.coef_div > 1 && !(scale_dev && shift_dev)) return bad("coef_div needs scale and shift");
+    if ((scale_dev == nullptr) != (shift_dev == nullptr)) return bad("scale and shift go together");
+    if (sparse) {
+        sparse->planned = sparse->ntiles = sparse->npad = sparse->nvalid0 = sparse->nvalid1 = sparse->wo_store = 0;
+        sparse->mix[0] = sparse->mix[1] = sparse->mix[2] = 0;
+        if (!sparse->needed_host || !sparse->col_map_host) return bad("sparse: needed_host and col_map_host (2 w entries each)");
+        if (!y_dev || x.y_f32_dev || x.residual_dev) return bad("sparse: the compact tensor is the 16-bit output, without residual");
+        if (2 * (long long)w > 0x3FFF) return unsup("sparse: list entries are 14-bit columns");
+    }
+    { dyf_status ds = op_drop_check(e, n, x.drop_mode, x.drop_p, x.mask_dev, x.drop_site); if (ds != DYF_OK) return ds; }
+    const int cin = c0 + x.c1;
+    // element indices of the epilogues (dropout streams, stores) and the gathers' byte offsets are 32 bit in every form
+    if ((long long)n * 2 * h * 2 * w * cout >= 0xFFFFFFF0ll || (long long)n * h * w * std::max(c0, x.c1) >= 0x7F000000ll / 2)
+        return unsup("tensor too large for the kernels' 32-bit element indices");
+    HIP_TRY(e, hipSetDevice(e->cfg.device));
+    hipStream_t st = (hipStream_t)stream;
+    std::vector<void*> tmp;
+    dyf_status rs = [&]() -> dyf_status {
+        AllocScope scope(e, &tmp);
+        ConvW wts;
+        dyf_status us = upload_conv_weights(e, &wts, pack_conv(w_host, cout, cin, 9), cout, 9, cin);
+        if (us != DYF_OK) return us;
+        ConvArgs a{};
+        a.src0 = x_dev; a.c0 = c0; a.src1 = x.x1_dev; a.c1 = x.c1; a.n = n; a.h = h; a.w = w; a.ho = 2 * h; a.wo = 2 * w;
+        a.kh = 3; a.kw = 3; a.stride = 1; a.pad = 1; a.cout = cout;
+        a.act = act; a.out_el16 = y_dev; a.out_f32 = x.y_f32_dev; a.residual = x.residual_dev; a.zero_page = e->ws.zero_page;
+        a.coef_div = x.coef_div; a.n_sel = x.n_sel;
+        a.splitk_ws = e->ws.splitk; a.splitk_cap = e->ws.splitk ? DYF_SPLITK_FLOATS : 0;
+        {   // the decoder block's upload: phase-decomposed weights, and their fragment order where the halo forms can stream it
+            std::vector<el16_t> pu((size_t)4 * cout * 16 * cin);
+            pack_up2x_weights(w_host, cout, cin, pu.data());
+            el16_t *wu = nullptr, *wf = nullptr;
+            us = dev_upload(e, &wu, pu);
+            if (us == DYF_OK && cin % 64 == 0 && cout % 64 == 0) {
+                std::vector<el16_t> pf(pu.size());
+                pack_up2x_frag(pu.data(), cout, cin, pf.data());
+                us = dev_upload(e, &wf, pf);
+            }
+            if (us != DYF_OK) return us;
+            a.up2x = 1; a.wpk_up = wu; a.wpk_up_frag = wf;
+        }
+        {   // the border scratch, every float a NaN: a ring pixel the border kernel leaves out reaches the output
+            float* border = nullptr;
+            const size_t fl = conv_up_border_floats(n, h, w, cout);
+            us = dev_alloc(e, &border, fl);
+            if (us != DYF_OK) return us;
+            HIP_TRY(e, hipMemset(border, 0xFF, std::max<size_t>(fl * sizeof(float), 256)));
+            a.up_border = border;
+        }
+        if (scale_dev && shift_dev) {
+            a.coef_a = scale_dev; a.coef_c = shift_dev; a.coef_stride = cout;
+        } else {
+            float *ones = nullptr, *zeros = nullptr;
+            us = dev_upload(e, &ones, std::vector<float>(cout, 1.0f));
+            if (us == DYF_OK) us = dev_upload(e, &zeros, std::vector<float>(cout, 0.0f));
+            if (us != DYF_OK) return us;
+            a.coef_a = ones; a.coef_c = zeros; a.coef_stride = 0;
+        }
+        if (!conv_mfma_supported(a)) return unsup("needs c0 % 64 == 0, c1 % 64 == 0, cout % 64 == 0, w % 16 == 0, h % 8 (cout % 128 == 0) or 16, act 0..3");
+        if (sparse) {  // the last decoder block's column lists
+            const UpSparsePlan sp = a.wpk_up_frag ? plan_up_sparse(std::vector<uint8_t>(sparse->needed_host, sparse->needed_host + 2 * (size_t)w), h, w) : UpSparsePlan{};
+            if (sp.planned) {
+                int16_t *cols = nullptr, *cbase = nullptr, *cidx = nullptr;
+                us = dev_upload(e, &cols, sp.cols);
+                if (us == DYF_OK) us = dev_upload(e, &cbase, sp.cbase);
+                if (us == DYF_OK) us = dev_upload(e, &cidx, sp.cidx);
+                if (us != DYF_OK) return us;
+                a.up_cols = cols; a.up_cbase = cbase; a.up_cidx = cidx;
+                a.up_ntiles = sp.ntiles; a.up_npad = sp.npad; a.up_nvalid0 = sp.nvalid0; a.up_nvalid1 = sp.nvalid1; a.up_wo_store = sp.wo_store;
+                a.up_mix[0] = sp.mix[0]; a.up_mix[1] = sp.mix[1]; a.up_mix[2] = sp.mix[2];
+                // (net_forward: a launch the sparse form does not take stays dense)
+                if (!conv_up_halo_supported(a)) {
+                    a.up_cols = a.up_cbase = a.up_cidx = nullptr;
+                    a.up_ntiles = a.up_npad = a.up_nvalid0 = a.up_nvalid1 = a.up_wo_store = 0;
+                    a.up_mix[0] = a.up_mix[1] = a.up_mix[2] = 0;
+                }
+            }
+            if (a.up_cols) {
+                if (sp.cmap.size() != 2 * (size_t)w) return fail(e, DYF_ERR_STATE, "dyf_op_upconv2d_ex: the planner's col_map is not 2 w long");
+                sparse->planned = 1; sparse->ntiles = sp.ntiles; sparse->npad = sp.npad; sparse->nvalid0 = sp.nvalid0; sparse->nvalid1 = sp.nvalid1;
+                sparse->wo_store = sp.wo_store;
+                sparse->mix[0] = sp.mix[0]; sparse->mix[1] = sp.mix[1]; sparse->mix[2] = sp.mix[2];
+                std::copy(sp.cmap.begin(), sp.cmap.end(), sparse->col_map_host);
+            }
+        }
+        us = op_drop_arm(e, n, x.drop_mode, x.drop_p, x.mask_dev, x.drop_site, x.drop_row_offset, x.drop_forward, st, &a.drop);
+        if (us != DYF_OK) return us;
+        hipError_t le = launch_conv(a, wts, 1, st);
+        if (le == hipSuccess) le = hipStreamSynchronize(st);
+        if (le != hipSuccess) return fail(e, DYF_ERR_HIP, std::string("dyf_op_upconv2d_ex launch: ") + hipGetErrorString(le));
+        return DYF_OK;
+    }();
+    if (rs != DYF_OK) (void)hipDeviceSynchronize();  // (a failed launch: nothing of `tmp` may still be read when it is freed)
+    release_allocs(tmp);
     return rs;
 }
 

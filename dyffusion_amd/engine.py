@@ -1431,6 +1431,70 @@ class HipEngine:
                                               self._stream()))
         return y
 
+    def op_upconv2d_ex(self, x: torch.Tensor, weight: torch.Tensor, scale: Optional[torch.Tensor] = None,
+                       shift: Optional[torch.Tensor] = None, act: int = 0, *, x1: Optional[torch.Tensor] = None, coef_div: int = 0,
+                       n_sel: int = 0, mask: Optional[torch.Tensor] = None, p: float = 0.0, rng_site: Optional[int] = None,
+                       rng_row_offset: int = 0, rng_forward: int = 0, residual: Optional[torch.Tensor] = None, out_f32: bool = False,
+                       needed: Optional[torch.Tensor] = None, fill: Optional[float] = None):
+        """Test seam (dyf_op_upconv2d_ex): the fused Upsample(x2, bilinear) + Conv2d(3x3, pad 1) with the argument block of a decoder
+        block, through the ladder.  x (N,H,W,c0) and x1 (N,H,W,c1: the skip) in the engine's 16-bit dtype, weight (Cout, c0 + c1, 3, 3),
+        scale / shift of ceil(N / coef_div) rows, mask: uint8 keep mask of the DENSE output shape (dropout mode 2), rng_site: dropout
+        mode 1.  needed: uint8 / bool over the 2W output columns -> the seam plans the sparse column lists and the result is
+        (y, plan): plan["planned"] == 1: y is the compact (N,2H,wo_store,Cout) tensor and plan["col_map"] its int16 column map;
+        0: the planner declined and y is dense.  fill: the output buffer holds this value before the launch.  Without `needed` the
+        result is y, or (y, y_f32) with out_f32."""
+        dt = self.torch_dtype
+        assert x.dtype == dt and x.is_cuda and x.is_contiguous()
+        n, h, w, c0 = x.shape
+        c1 = 0
+        if x1 is not None:
+            assert x1.dtype == dt and x1.is_cuda and x1.is_contiguous() and x1.shape[:3] == x.shape[:3]
+            c1 = x1.shape[3]
+        cout, cin, kh, kw = weight.shape
+        assert cin == c0 + c1 and (kh, kw) == (3, 3) and not (mask is not None and rng_site is not None)
+        wh = np.ascontiguousarray(weight.detach().to("cpu", torch.float32).numpy())
+        shape = (n, 2 * h, 2 * w, cout)
+        y = torch.empty(shape, dtype=dt, device=x.device)
+        y32 = torch.empty(shape, dtype=torch.float32, device=x.device) if out_f32 else None
+        if fill is not None:
+            y.fill_(fill)
+        if scale is not None:
+            rows = -(-n // coef_div) if coef_div > 1 else n
+            scale, shift = _f32c(scale, "scale"), _f32c(shift, "shift")
+            assert tuple(scale.shape) == (rows, cout) and tuple(shift.shape) == (rows, cout)
+        ex = L.ConvEx()
+        if x1 is not None:
+            ex.x1_dev, ex.c1 = x1.data_ptr(), c1
+        if residual is not None:
+            assert residual.dtype == dt and residual.is_cuda and residual.is_contiguous() and tuple(residual.shape) == shape
+            ex.residual_dev = residual.data_ptr()
+        if y32 is not None:
+            ex.y_f32_dev = y32.data_ptr()
+        ex.coef_div, ex.n_sel, ex.drop_p = int(coef_div), int(n_sel), float(p)
+        if mask is not None:
+            assert mask.dtype == torch.uint8 and mask.is_cuda and mask.is_contiguous() and tuple(mask.shape) == shape
+            ex.drop_mode, ex.mask_dev = 2, mask.data_ptr()
+        elif rng_site is not None:
+            ex.drop_mode, ex.drop_site, ex.drop_row_offset, ex.drop_forward = 1, int(rng_site), int(rng_row_offset), int(rng_forward)
+        sp = None
+        if needed is not None:
+            need = np.ascontiguousarray(needed.detach().to("cpu").numpy().astype(np.uint8))
+            assert need.shape == (2 * w,)
+            cmap = np.full(2 * w, -1, dtype=np.int16)
+            sp = L.UpconvSparse()
+            sp.needed_host, sp.col_map_host = need.ctypes.data, cmap.ctypes.data
+        self._check(self._lib.dyf_op_upconv2d_ex(self._h, x.data_ptr(), wh.ctypes.data, n, h, w, c0, cout,
+                                                 None if scale is None else scale.data_ptr(), None if shift is None else shift.data_ptr(),
+                                                 act, y.data_ptr(), C.byref(ex), None if sp is None else C.byref(sp), self._stream()))
+        if sp is None:
+            return (y, y32) if out_f32 else y
+        plan = dict(planned=int(sp.planned), ntiles=int(sp.ntiles), npad=int(sp.npad), nvalid0=int(sp.nvalid0), nvalid1=int(sp.nvalid1),
+                    wo_store=int(sp.wo_store), mix=[int(v) for v in sp.mix], col_map=torch.from_numpy(cmap.copy()))
+        if plan["planned"]:
+            ws = plan["wo_store"]
+            return y.reshape(-1)[:n * 2 * h * ws * cout].reshape(n, 2 * h, ws, cout), plan
+        return y, plan
+
 
 class EngineLoss(torch.autograd.Function):
     """Scalar loss whose backward is the engine's backward pass: `owner._train_backward(upstream)` runs dyf_train_backward and

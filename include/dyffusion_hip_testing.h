@@ -139,6 +139,31 @@ dyf_status dyf_op_upconv2d(dyf_engine* engine, const uint16_t* x_dev, const floa
                            int32_t w, int32_t cin, int32_t cout, const float* scale_dev, const float* shift_dev,
                            int32_t act, uint16_t* y_dev, void* stream);
 
+/* The same fused conv with the argument block of a decoder block of the network forward (csrc/engine.hip net_forward): up2x = 1, the
+ * phase-decomposed weights (pack_up2x_weights) and their fragment order (pack_up2x_frag), the engine's split-K workspace and a border
+ * scratch of the call's own, pre-filled with 0xFF bytes (fp32 NaN: a ring pixel the border kernel leaves out reaches the output) --
+ * through launch_conv, never a form's launcher: the form is the ladder's.  16-bit tensors are bf16 or fp16 as the engine's build.
+ *   x_dev (N,H,W,c0), w_host (Cout, c0 + c1, 3, 3), scale / shift (ceil(N / coef_div), Cout) device fp32 or both NULL, act 0..3
+ *   ex       dyf_conv_ex: x1_dev / c1 (the skip tensor, behind x_dev's channels), coef_div, n_sel, dropout modes 1 and 2 (mask_dev: uint8
+ *            (N,2H,2W,Cout), the DENSE shape also for a sparse launch); residual_dev and y_f32_dev are handed to the ladder as they are
+ *   sparse   NULL: every column.  Else needed_host = uint8 [2W], the output columns somebody reads: the seam plans the column lists with
+ *            the code the weight upload plans the last decoder block with (same planner order, same switches) and reports the plan:
+ *            planned (0: the planner declined, or the sparse form does not take the launch -- the launch is DENSE, as in the engine),
+ *            ntiles, npad, mix[3], nvalid0 / nvalid1, wo_store, and col_map_host = int16 [2W] (output column -> column of the compact
+ *            tensor, -1 = not stored; written only when planned).  A sparse call takes no residual and no fp32 output.
+ *   y_dev    room for (N,2H,2W,Cout); with planned != 0 the launch writes the compact (N,2H,wo_store,Cout) tensor at its start.
+ * What the arguments cannot express is refused (DYF_ERR_INVALID_ARGUMENT / DYF_ERR_UNSUPPORTED), never truncated; tensors past the
+ * kernels' 32-bit element indices are refused.  Synchronises and frees what it allocated. */
+typedef struct dyf_upconv_sparse {
+    const uint8_t* needed_host;
+    int16_t* col_map_host;
+    int32_t planned, ntiles, npad, nvalid0, nvalid1, wo_store;
+    int32_t mix[3];
+} dyf_upconv_sparse;
+dyf_status dyf_op_upconv2d_ex(dyf_engine* engine, const uint16_t* x_dev, const float* w_host, int32_t n, int32_t h, int32_t w,
+                              int32_t c0, int32_t cout, const float* scale_dev, const float* shift_dev, int32_t act, uint16_t* y_dev,
+                              const dyf_conv_ex* ex, dyf_upconv_sparse* sparse, void* stream);
+
 /* LinearAttention core (attention.py:28-49, 4 heads of 32 channels): qkv_dev (N,HW,384) bf16 = to_qkv output ->
  * out_dev (N,HW,128) bf16 = softmax_d(q)*scale . (softmax_n(k) . v^T / HW), the input of to_out.  Runs the pixel-parallel
  * MFMA kernels the ResNet-UNet uses. */
