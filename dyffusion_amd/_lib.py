@@ -127,6 +127,13 @@ class ConvGnResult(C.Structure):
     _fields_ = [(k, C.c_int32) for k in ("fused", "slots", "bm", "slow_sweep")]
 
 
+class ProductsSpec(C.Structure):
+    """dyf_products_spec (include/dyffusion_hip.h): the planes dyf_ensemble_products writes, in this order."""
+    _fields_ = [("mean", C.c_int32), ("std", C.c_int32), ("min", C.c_int32), ("max", C.c_int32),
+                ("n_quantiles", C.c_int32), ("quantiles", C.c_double * 16), ("n_thresholds", C.c_int32), ("thresholds", C.c_float * 16)]
+
+
+MAX_PRODUCT_QUANTILES = MAX_PRODUCT_THRESHOLDS = 16  # DYF_MAX_PRODUCT_QUANTILES / DYF_MAX_PRODUCT_THRESHOLDS
 BC_NAVIER_STOKES, BC_SPRING_MESH = 0, 1
 COMM_ID_BYTES = 128  # DYF_COMM_ID_BYTES (ncclUniqueId)
 TRAIN_BATCH_STATS, TRAIN_DROPOUT = 1, 2
@@ -216,6 +223,9 @@ SYMBOLS = [
     ("dyf_ensemble_size_metrics", C.c_int, [_P, C.c_int32, C.POINTER(_P), C.POINTER(_P), C.c_int32, C.c_int64, C.c_int64, _P, _P, _P]),
     ("dyf_ensemble_scores", C.c_int, [_P, C.c_int32, C.POINTER(_P), C.POINTER(_P), C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int32,
                                       C.c_int64, _P, _P, _P]),
+    ("dyf_ensemble_products", C.c_int, [_P, C.c_int32, C.POINTER(_P), C.c_int32, C.c_int64, C.c_int64, C.POINTER(ProductsSpec), _P, _P]),
+    ("dyf_rank_histogram", C.c_int, [_P, C.c_int32, C.POINTER(_P), C.POINTER(_P), C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int32,
+                                     C.c_int64, _P, _P, _P]),
     ("dyf_time_layer_in_rollout", C.c_int, [_P, C.c_int32, C.c_int32, _P, C.POINTER(C.c_double), C.POINTER(C.c_int32)]),
     ("dyf_time_kernel_in_rollout", C.c_int, [_P, C.c_int32, C.c_int32, _P, C.POINTER(C.c_double), C.POINTER(C.c_int32),
                                              C.POINTER(C.c_double), C.POINTER(C.c_double)]),

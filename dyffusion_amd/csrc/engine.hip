@@ -1817,13 +1817,14 @@ static void traj_release(dyf_engine* e) {
     if (e->traj_partials) (void)hipFree(e->traj_partials);
     if (e->ens_size_partials) (void)hipFree(e->ens_size_partials);
     if (e->ens_scores_partials) (void)hipFree(e->ens_scores_partials);
+    if (e->rank_hist_partials) (void)hipFree(e->rank_hist_partials);
     if (e->traj_uploaded) (void)hipEventDestroy(e->traj_uploaded);
     if (e->traj_done) (void)hipEventDestroy(e->traj_done);
     e->traj_tab = e->traj_stage = nullptr;
-    e->traj_partials = e->ens_size_partials = e->ens_scores_partials = nullptr;
+    e->traj_partials = e->ens_size_partials = e->ens_scores_partials = e->rank_hist_partials = nullptr;
     e->traj_uploaded = e->traj_done = nullptr;
     e->traj_cap = 0;
-    e->traj_partials_count = e->ens_size_partials_count = e->ens_scores_partials_count = 0;
+    e->traj_partials_count = e->ens_size_partials_count = e->ens_scores_partials_count = e->rank_hist_partials_count = 0;
     e->traj_pending = false;
 }
 
@@ -1945,6 +1946,72 @@ dyf_status dyf_ensemble_scores(dyf_engine* e, int32_t n_segments, const float* c
     if (cs != DYF_OK) return cs;
     return traj_finish(e, launch_ensemble_scores(e->traj_tab, e->traj_tab + n_segments, n_segments, n_members, member_stride, n_outer,
                                                  n_groups, n_inner, e->ens_scores_partials, out_dev, accum_dev, st), st);
+}
+
+dyf_status dyf_ensemble_products(dyf_engine* e, int32_t n_segments, const float* const* preds_dev, int32_t n_members, int64_t n_points,
+                                 int64_t member_stride, const dyf_products_spec* spec, float* out_dev, void* stream) {
+    if (!e || !preds_dev || !spec || !out_dev) return fail(e, DYF_ERR_INVALID_ARGUMENT, "null argument");
+    if (n_segments < 1 || n_members < 1) return fail(e, DYF_ERR_INVALID_ARGUMENT, "n_segments and n_members must be positive");
+    if (n_segments > 65535) return fail(e, DYF_ERR_UNSUPPORTED, "n_segments outside [1, 65535]");
+    if (n_members > 15360) return fail(e, DYF_ERR_UNSUPPORTED, "n_members outside [1, 15360]");
+    if (n_points < 1) return fail(e, DYF_ERR_INVALID_ARGUMENT, "n_points must be positive");
+    if (member_stride < n_points) return fail(e, DYF_ERR_INVALID_ARGUMENT, "member_stride must be at least n_points");
+    for (int32_t s = 0; s < n_segments; ++s)
+        if (!preds_dev[s]) return fail(e, DYF_ERR_INVALID_ARGUMENT, "null segment pointer");
+    if (spec->n_quantiles < 0 || spec->n_quantiles > DYF_MAX_PRODUCT_QUANTILES || spec->n_thresholds < 0 ||
+        spec->n_thresholds > DYF_MAX_PRODUCT_THRESHOLDS)
+        return fail(e, DYF_ERR_INVALID_ARGUMENT, "at most 16 quantiles and 16 thresholds");
+    for (int32_t v : {spec->mean, spec->std, spec->min, spec->max})
+        if (v != 0 && v != 1) return fail(e, DYF_ERR_INVALID_ARGUMENT, "mean / std / min / max are 0 or 1");
+    EnsembleProductsParams pr = {};
+    pr.mean = spec->mean, pr.std = spec->std, pr.min = spec->min, pr.max = spec->max;
+    pr.n_quantiles = spec->n_quantiles, pr.n_thresholds = spec->n_thresholds;
+    if (pr.mean + pr.std + pr.min + pr.max + pr.n_quantiles + pr.n_thresholds == 0)
+        return fail(e, DYF_ERR_INVALID_ARGUMENT, "no product is asked for");
+    for (int k = 0; k < pr.n_quantiles; ++k) {  // numpy's "linear": the virtual index (N - 1) q in double, its fraction in fp32
+        const double q = spec->quantiles[k];
+        if (!(q >= 0.0 && q <= 1.0)) return fail(e, DYF_ERR_INVALID_ARGUMENT, "quantile probabilities lie in [0, 1]");
+        const double h = (double)(n_members - 1) * q;
+        const int lo = std::min((int)std::floor(h), n_members - 1);
+        pr.lo[k] = lo;
+        pr.hi[k] = std::min(lo + 1, n_members - 1);
+        pr.frac[k] = (float)(h - (double)lo);
+    }
+    for (int k = 0; k < pr.n_thresholds; ++k) {
+        if (spec->thresholds[k] != spec->thresholds[k]) return fail(e, DYF_ERR_INVALID_ARGUMENT, "a threshold is NaN");
+        pr.thresholds[k] = spec->thresholds[k];
+    }
+    const long long blocks = ensemble_products_blocks(n_members, n_points);
+    if (blocks < 1 || blocks > ENSEMBLE_PRODUCTS_MAX_BLOCKS)
+        return fail(e, DYF_ERR_UNSUPPORTED, "n_points beyond 2^24 - 1 workgroups per segment");
+    HIP_TRY(e, hipSetDevice(e->cfg.device));
+    hipStream_t st = (hipStream_t)stream;
+    // the pointer table has a predictions and a targets half: the second is not read here
+    dyf_status cs = traj_upload(e, n_segments, preds_dev, preds_dev, &e->traj_partials, &e->traj_partials_count, 0, st);
+    if (cs != DYF_OK) return cs;
+    return traj_finish(e, launch_ensemble_products(e->traj_tab, n_segments, n_members, n_points, member_stride, pr, out_dev, st), st);
+}
+
+dyf_status dyf_rank_histogram(dyf_engine* e, int32_t n_segments, const float* const* preds_dev, const float* const* targets_dev,
+                              int32_t n_members, int64_t n_points, int64_t member_stride, int64_t n_outer, int32_t n_groups,
+                              int64_t n_inner, double* out_dev, double* accum_dev, void* stream) {
+    dyf_status cs = traj_check_args(e, n_segments, preds_dev, targets_dev, n_members, RANK_HISTOGRAM_MAX_MEMBERS, DYF_ERR_UNSUPPORTED,
+                                    n_points, member_stride, out_dev);
+    if (cs != DYF_OK) return cs;
+    if (n_outer < 1 || n_groups < 1 || n_inner < 1) return fail(e, DYF_ERR_INVALID_ARGUMENT, "n_outer, n_groups and n_inner must be positive");
+    if (n_points % n_outer != 0 || (n_points / n_outer) % n_groups != 0 || n_points / n_outer / n_groups != n_inner)
+        return fail(e, DYF_ERR_INVALID_ARGUMENT, "n_outer * n_groups * n_inner must equal n_points");
+    const int chunks = rank_histogram_chunks(n_members, n_outer, n_groups, n_inner);
+    if (chunks < 1)
+        return fail(e, DYF_ERR_UNSUPPORTED, "more than 2^24 - 1 = " + std::to_string(ENSEMBLE_SCORES_MAX_BLOCKS) +
+                                                " tiles per segment (n_outer * n_groups * ceil(n_inner / 256))");
+    HIP_TRY(e, hipSetDevice(e->cfg.device));
+    hipStream_t st = (hipStream_t)stream;
+    cs = traj_upload(e, n_segments, preds_dev, targets_dev, &e->rank_hist_partials, &e->rank_hist_partials_count,
+                     (size_t)n_segments * (size_t)n_groups * (size_t)chunks * (size_t)(n_members + 1), st);
+    if (cs != DYF_OK) return cs;
+    return traj_finish(e, launch_rank_histogram(e->traj_tab, e->traj_tab + n_segments, n_segments, n_members, member_stride, n_outer,
+                                                n_groups, n_inner, e->rank_hist_partials, out_dev, accum_dev, st), st);
 }
 
 dyf_status dyf_apply_boundary_conditions(dyf_engine* e, const dyf_bc_args* bc, float* preds_dev, void* stream) {

@@ -229,6 +229,33 @@ long long ensemble_scores_blocks(int n_members, long long n_outer, int n_groups,
 hipError_t launch_ensemble_scores(const float* const* preds_tab, const float* const* targets_tab, int n_segments, int n_members,
                                   long long member_stride, long long n_outer, int n_groups, long long n_inner, double* partials,
                                   double* out, double* accum, hipStream_t s);
+// forecast products per point (dyf_ensemble_products; ensemble_products.hip): out[n_segments][planes][n_points] fp32, the planes
+// asked for in the order mean, std, min, max, quantiles, exceedances.  A quantile is given by the order statistics lo <= hi it lies
+// between and the fp32 fraction (the host computes them from (n_members - 1) q in double).  One launch, no workspace, no atomics.
+constexpr int ENSEMBLE_PRODUCTS_MAX_QUANTILES = 16;   // DYF_MAX_PRODUCT_QUANTILES
+constexpr int ENSEMBLE_PRODUCTS_MAX_THRESHOLDS = 16;  // DYF_MAX_PRODUCT_THRESHOLDS
+constexpr long long ENSEMBLE_PRODUCTS_MAX_BLOCKS = 0xffffffLL;  // workgroups per segment, as ENSEMBLE_SCORES_MAX_BLOCKS
+struct EnsembleProductsParams {
+    int mean, std, min, max;  // 0 / 1
+    int n_quantiles, n_thresholds;
+    int lo[ENSEMBLE_PRODUCTS_MAX_QUANTILES], hi[ENSEMBLE_PRODUCTS_MAX_QUANTILES];
+    float frac[ENSEMBLE_PRODUCTS_MAX_QUANTILES];
+    float thresholds[ENSEMBLE_PRODUCTS_MAX_THRESHOLDS];
+};
+long long ensemble_products_blocks(int n_members, long long n_points);  // workgroups per segment; 0 = n_members beyond 15 360
+hipError_t launch_ensemble_products(const float* const* preds_tab, int n_segments, int n_members, long long n_points,
+                                    long long member_stride, const EnsembleProductsParams& pr, float* out, hipStream_t s);
+// the rank histogram per (segment, group) of the geometry of launch_ensemble_scores (dyf_rank_histogram; ensemble_products.hip),
+// without atomics: launch 1 leaves partials[n_segments][n_groups][rank_histogram_chunks()][n_members + 1], launch 2 adds a group's
+// chunks in chunk order and writes out[n_segments][n_groups][n_members + 1] (accum += out when given).
+constexpr int RANK_HISTOGRAM_MAX_MEMBERS = 1024;
+constexpr int RANK_HISTOGRAM_MAX_CHUNKS = 256;  // partial histograms per (segment, group)
+// partial histograms per group = min(n_outer * ceil(n_inner / 256), 256); 0 = bad arguments or n_members beyond the limit, -1 = the
+// geometry is beyond the workgroup limit of ensemble_scores_blocks
+int rank_histogram_chunks(int n_members, long long n_outer, int n_groups, long long n_inner);
+hipError_t launch_rank_histogram(const float* const* preds_tab, const float* const* targets_tab, int n_segments, int n_members,
+                                 long long member_stride, long long n_outer, int n_groups, long long n_inner, double* partials,
+                                 double* out, double* accum, hipStream_t s);
 
 // dyf_sample_gather: all-gather receive layout [world][slots][nb][row floats] -> [slots][total_rows][row] in global row order;
 // rank r owns the contiguous block of rows shard(r) (the first total_rows % world ranks one extra), its padding rows are dropped

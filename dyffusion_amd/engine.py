@@ -604,6 +604,76 @@ class HipEngine:
         del keep  # as in trajectory_metrics
         return out
 
+    def ensemble_products(self, preds, mean: bool = True, std: bool = True, min: bool = False, max: bool = False,
+                          quantiles: Sequence[float] = (), exceed: Sequence[float] = ()):
+        """Forecast fields per grid point, reduced over the members on the device (dyf_ensemble_products): the ensemble mean, the
+        population standard deviation, min / max, the `quantiles` (probabilities in [0, 1], numpy's "linear" method) and the
+        exceedance probabilities P(x > t) for t in `exceed`.  `preds` is one (N, ...) fp32 device tensor -> `fields` (K, ...), or a
+        list of T equally shaped (N, ...) tensors, read in place as the segments of one call -> (T, K, ...).  Returns (fields,
+        names): fp32 on the device, the K planes in the order of `names`, e.g. ["mean", "std", "q0.05", "q0.5", "q0.95", "gt0.5"].
+        Non-contiguous or non-fp32 inputs are made contiguous fp32 first.  A point with a NaN member is NaN in every plane but the
+        exceedances.  At most 16 quantiles and 16 thresholds.  No synchronisation: one launch on the current stream."""
+        one = torch.is_tensor(preds)
+        plist = [preds] if one else list(preds)
+        if not plist:
+            raise ValueError("no segments")
+        for p in plist:
+            if not torch.is_tensor(p) or p.dim() < 1 or p.shape[0] < 1 or p.numel() < 1:
+                raise ValueError("ensemble_products takes (N, ...) tensors with at least one member and one point")
+            if p.shape != plist[0].shape:
+                raise ValueError(f"segments differ in shape: {tuple(p.shape)} and {tuple(plist[0].shape)}")
+        for p in plist:
+            if p.device.type != "cuda":
+                raise ValueError("ensemble_products works on GPU tensors (the HIP engine computes them)")
+        try:
+            qs, ts = [float(q) for q in quantiles], [float(t) for t in exceed]
+        except (TypeError, ValueError):
+            raise ValueError(f"quantiles and exceed must be sequences of numbers, not {quantiles!r} / {exceed!r}") from None
+        if len(qs) > L.MAX_PRODUCT_QUANTILES or len(ts) > L.MAX_PRODUCT_THRESHOLDS:
+            raise ValueError(f"at most {L.MAX_PRODUCT_QUANTILES} quantiles and {L.MAX_PRODUCT_THRESHOLDS} thresholds")
+        spec = L.ProductsSpec(mean=int(bool(mean)), std=int(bool(std)), min=int(bool(min)), max=int(bool(max)),
+                                 n_quantiles=len(qs), n_thresholds=len(ts))
+        for k, q in enumerate(qs):
+            spec.quantiles[k] = q
+        for k, t in enumerate(ts):
+            spec.thresholds[k] = t
+        names = [m for m, on in (("mean", mean), ("std", std), ("min", min), ("max", max)) if on]
+        names += [f"q{q:g}" for q in qs] + [f"gt{t:g}" for t in ts]
+        keep = [p.contiguous().float() for p in plist]
+        n, nseg, shape = keep[0].shape[0], len(keep), tuple(keep[0].shape[1:])
+        points = keep[0].numel() // n
+        out = torch.empty(nseg, len(names), *shape, dtype=torch.float32, device=keep[0].device)
+        self._check(self._lib.dyf_ensemble_products(self._h, nseg, (C.c_void_p * nseg)(*[p.data_ptr() for p in keep]), n, points, points,
+                                                    C.byref(spec), out.data_ptr(), self._stream()))
+        del keep  # as in trajectory_metrics
+        return (out[0] if one else out), names
+
+    def rank_histogram(self, preds, targets, group_shape: Optional[Sequence[int]] = None,
+                       accum: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The rank histogram (Talagrand diagram) per (segment, group) on the device (dyf_rank_histogram).  Inputs and `group_shape`
+        as `ensemble_scores`.  Returns a float64 device tensor (T, G, N + 1): bin r counts the points whose target has r members
+        below it; a target tied with e members gives 1 / (e + 1) to each of the e + 1 bins it could fall in; points with a NaN
+        target or member are left out.  `accum` (float64, (T, G, N + 1), on the device) += it.  At most 1024 members
+        (NotImplementedError beyond).  No synchronisation."""
+        n, nseg, points, stride, p_ptrs, t_ptrs, keep, dev = self._segments(preds, targets, "rank_histogram")
+        if group_shape is None:
+            group_shape = (1, 1, points)
+        try:
+            outer, groups, inner = (operator.index(v) for v in group_shape)
+        except (TypeError, ValueError):
+            raise ValueError(f"group_shape must be (outer, groups, inner) integers, not {group_shape!r}") from None
+        if min(outer, groups, inner) < 1 or outer * groups * inner != points:
+            raise ValueError(f"group_shape {(outer, groups, inner)} must be positive with product {points}, a segment's points")
+        if accum is not None and (accum.dtype != torch.float64 or tuple(accum.shape) != (nseg, groups, n + 1) or not accum.is_contiguous()
+                                  or accum.device != dev):
+            raise ValueError(f"accum must be a contiguous float64 ({nseg}, {groups}, {n + 1}) tensor on {dev}")
+        out = torch.empty(nseg, groups, n + 1, dtype=torch.float64, device=dev)
+        self._check(self._lib.dyf_rank_histogram(self._h, nseg, (C.c_void_p * nseg)(*p_ptrs), (C.c_void_p * nseg)(*t_ptrs), n, points,
+                                                 stride, outer, groups, inner, out.data_ptr(),
+                                                 accum.data_ptr() if accum is not None else None, self._stream()))
+        del keep  # as in trajectory_metrics
+        return out
+
     def time_layer_in_rollout(self, layer: int, nb: int):
         """(average ms, launches) of decoder block `layer`'s conv over one eagerly launched rollout of the current plan."""
         ms, cnt = C.c_double(), C.c_int32()

@@ -122,7 +122,8 @@ class MultiHorizonForecastingDYffusion(nn.Module):
     def __init__(self, model: DYffusion, num_predictions: int = 1, window: int = 1, horizon: Optional[int] = None,
                  autoregressive_steps: int = 0, prediction_horizon: Optional[int] = None, datamodule=None,
                  datamodule_config: Optional[Dict[str, Any]] = None, ensemble_size_curves: bool = False,
-                 extended_metrics: bool = False):
+                 extended_metrics: bool = False, predict_products: Optional[Dict[str, Any]] = None, keep_members: bool = True,
+                 rank_histogram: bool = False):
         super().__init__()
         assert autoregressive_steps >= 0, f"Autoregressive steps must be >= 0, but is {autoregressive_steps}"
         if autoregressive_steps > 0:
@@ -138,6 +139,15 @@ class MultiHorizonForecastingDYffusion(nn.Module):
         self.ensemble_size_curves = ensemble_size_curves
         # also report nll / corr and the five scores per channel at the end of validation / pooled test epochs (c{j}/ keys)
         self.extended_metrics = extended_metrics
+        # keyword arguments of HipEngine.ensemble_products (mean, std, min, max, quantiles, exceed): predict_step also returns the
+        # forecast fields `t{k}_preds_{name}` (B, C, H, W), reduced over the members on the device; with keep_members=False the
+        # (N, B, C, H, W) member stack `t{k}_preds` is then not copied to the host
+        self.predict_products = None if predict_products is None else dict(predict_products)
+        if not keep_members and self.predict_products is None:
+            raise ValueError("keep_members=False needs predict_products: predict_step would return no prediction at all")
+        self.keep_members = keep_members
+        # also report the rank histogram of every horizon and its reliability index at the end of validation / test epochs
+        self.rank_histogram = rank_histogram
         self._test_metrics_aggregate = None  # TrajectoryMetricsAccumulator of the physical-systems test epoch (first test_step)
         self._predict_step_outputs = []
 
@@ -231,7 +241,9 @@ class MultiHorizonForecastingDYffusion(nn.Module):
                          prediction_horizon: Optional[int] = None, as_numpy: bool = False) -> Dict[str, Any]:
         """Returns {"t{k}_targets": (B, C, H, W), "t{k}_preds": (N, B, C, H, W)} for k = 1..prediction_horizon (torch tensors on
         the GPU, or numpy arrays like the reference with `as_numpy`).  `boundary_conditions(preds=, targets=, metadata=, time=)`
-        is applied to every predicted field before it is returned / fed back, exactly where the reference applies it."""
+        is applied to every predicted field before it is returned / fed back, exactly where the reference applies it.  With
+        `predict_products` and `as_numpy` also "t{k}_preds_{name}": (B, C, H, W), the forecast fields of the members after the
+        boundary conditions (HipEngine.ensemble_products), and without `keep_members` no "t{k}_preds"."""
         dynamics = batch["dynamics"].clone()
         b = dynamics.shape[0]
         h = self.true_horizon
@@ -263,9 +275,15 @@ class MultiHorizonForecastingDYffusion(nn.Module):
                 targets = dynamics[:, self.window + total_h - 1]
                 if boundary_conditions is not None:
                     p = boundary_conditions(preds=p, targets=targets, metadata=batch.get("metadata", None), time=total_t)
+                products = self.predict_products if as_numpy else None
                 if return_outputs:
                     out[f"t{total_h}_targets"] = conv(targets)
-                    out[f"t{total_h}_preds"] = conv(p)
+                    if products is None or self.keep_members:
+                        out[f"t{total_h}_preds"] = conv(p)
+                    if products is not None:  # one member: no ensemble axis
+                        fields, names = self.model._engine.ensemble_products(p if p.dim() == targets.dim() + 1 else p.unsqueeze(0), **products)
+                        for name, field in zip(names, fields.cpu().numpy()):
+                            out[f"t{total_h}_preds_{name}"] = field
                 if t_step in self.horizon_range[-self.window:]:  # forecasting_multi_horizon.py:194-197
                     ar_window.append(p.reshape(-1, *p.shape[-3:]))
             if ar_step < n_outer - 1:  # "(N B) window c h w -> (N B) (window c) h w": already ensemble-tiled (:218-220)
@@ -298,7 +316,8 @@ class MultiHorizonForecastingDYffusion(nn.Module):
             return results
         from .metrics import TrajectoryMetricsAccumulator
         if self._test_metrics_aggregate is None:
-            self._test_metrics_aggregate = TrajectoryMetricsAccumulator(self.model._engine, by_size=self.ensemble_size_curves)
+            self._test_metrics_aggregate = TrajectoryMetricsAccumulator(self.model._engine, by_size=self.ensemble_size_curves,
+                                                                        rank_histogram=self.rank_histogram)
         timesteps = range(1, self.prediction_horizon + 1)
         targets = [results[f"t{t}_targets"] for t in timesteps]
         preds = [results[f"t{t}_preds"] for t in timesteps]
@@ -312,8 +331,9 @@ class MultiHorizonForecastingDYffusion(nn.Module):
         `dyffusion_amd.metrics` (ensemble_metrics_kernel), not after a `.cpu().numpy()` round trip.  Returns what the reference
         logs: `{split}/{N}ens_mems/t{k}/{crps|ssr|mse}` and `.../avg/...`; with `ensemble_size_curves` also the same keys for the
         first n members, n = 1..N-1 (ensemble_size_metrics_kernel), and with `extended_metrics` `.../t{k}/{nll|corr}` and the five
-        scores per channel `.../t{k}/c{j}/{m}` (ensemble_scores_kernel)."""
-        from .metrics import eval_ensemble_predictions, eval_ensemble_size_curves
+        scores per channel `.../t{k}/c{j}/{m}` (ensemble_scores_kernel), and with `rank_histogram` `.../t{k}/rank_hist` (an (N + 1,)
+        array of frequencies) and `.../t{k}/reliability_index` (rank_histogram_kernel)."""
+        from .metrics import eval_ensemble_predictions, eval_ensemble_size_curves, eval_rank_histograms
         n = self.hparams.num_predictions
         if n <= 1 or not outputs:  # use_ensemble_predictions(split), :497-498
             return {}
@@ -327,6 +347,8 @@ class MultiHorizonForecastingDYffusion(nn.Module):
                                         extended=self.extended_metrics, per_channel=self.extended_metrics)
         if self.ensemble_size_curves:
             out.update(eval_ensemble_size_curves(results, self.model._engine, split=split))
+        if self.rank_histogram:
+            out.update(eval_rank_histograms(results, self.model._engine, split=split, infix=self.ensemble_logging_infix(split)))
         return out
 
     def on_validation_epoch_end(self) -> Dict[str, float]:
@@ -347,10 +369,18 @@ class MultiHorizonForecastingDYffusion(nn.Module):
         curves = agg.compute()
         agg.reset()
         by_size = curves.pop("by_size", None)
+        rank_hist = curves.pop("rank_hist", None)
         set_name = getattr(self.datamodule, "test_set_name", "") or ""
         out = trajectory_metric_keys(self.ensemble_logging_infix("test"), curves, set_name)
         if by_size is not None:
             out.update(trajectory_size_curve_keys(by_size, set_name))
+        if rank_hist is not None:  # (T, N + 1) frequencies of the histograms summed over the instances
+            from .metrics import rank_histogram_frequencies
+            stem = f"test/{set_name + '/' if set_name else ''}{self.ensemble_logging_infix('test')}"
+            ri = rank_histogram_frequencies(rank_hist)[1]
+            out[f"{stem}avg/rank_hist"], out[f"{stem}avg/reliability_index"] = rank_hist.mean(axis=0), float(ri.mean())
+            for i in range(rank_hist.shape[0]):
+                out[f"{stem}t{i + 1}/rank_hist"], out[f"{stem}t{i + 1}/reliability_index"] = rank_hist[i], float(ri[i])
         return out
 
     def predict_step(self, batch: Dict[str, Any], batch_idx: int = 0, dataloader_idx: int = None, **kwargs) -> None:

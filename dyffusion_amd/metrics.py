@@ -5,7 +5,9 @@ makes the reference's `.cpu().numpy()` round trip.  The reductions run in `ensem
 `trajectory_metrics_kernel` through `dyf_trajectory_metrics`; as a function of the ensemble size (the first n members, n = 1..N, and
 every member's own MSE) in `ensemble_size_metrics_kernel` through `dyf_ensemble_size_metrics`; per variable, per sample or over any
 other contiguous run of kept axes (`mean_dims`), together with the Gaussian NLL and the correlation, in `ensemble_scores_kernel`
-through `dyf_ensemble_scores`.  There is no CPU fallback."""
+through `dyf_ensemble_scores`.  The forecast fields themselves (mean, spread, quantiles, exceedance probabilities per grid point) come
+from `ensemble_products_kernel` through `dyf_ensemble_products`, the rank histogram from `rank_histogram_kernel` through
+`dyf_rank_histogram`.  There is no CPU fallback."""
 import math
 from collections import defaultdict
 from typing import Dict, Optional, Sequence, Tuple
@@ -190,6 +192,74 @@ def evaluate_ensemble_corr(predictions, targets, engine: HipEngine):
     return _scores(predictions, targets, engine, None)["corr"]
 
 
+def ensemble_products(preds, engine: HipEngine, **spec) -> Dict[str, Tensor]:
+    """The forecast fields of an ensemble, reduced over the members on the device: {name: tensor} with the names and keyword
+    arguments of `HipEngine.ensemble_products` (`mean`, `std`, `min`, `max`, `quantiles`, `exceed`).  `preds` (N, ...) gives fields
+    of shape (...); a list of T such tensors gives (T, ...) per name."""
+    fields, names = engine.ensemble_products(preds, **spec)
+    return {name: (fields[k] if torch.is_tensor(preds) else fields[:, k]) for k, name in enumerate(names)}
+
+
+def rank_histogram_frequencies(bins):
+    """Bins (..., N + 1) of `HipEngine.rank_histogram` (a float64 tensor or array) -> (frequencies, reliability index): the bins
+    divided by their sum, and sum_i |f_i - 1 / (N + 1)|, 0 for a flat histogram (NaN where no point counted)."""
+    freq = bins / bins.sum(-1, keepdims=True) if isinstance(bins, np.ndarray) else bins / bins.sum(dim=-1, keepdim=True)
+    return freq, abs(freq - 1.0 / bins.shape[-1]).sum(-1)
+
+
+def evaluate_rank_histogram(predictions, targets, engine: HipEngine, mean_dims=None) -> Dict[str, object]:
+    """The rank histogram of the targets among the members: {"rank_hist": frequencies (..., N + 1), "reliability_index": sum_i |f_i -
+    1 / (N + 1)|}.  predictions (n_members, n_samples, *), targets (n_samples, *), on the engine's GPU; `mean_dims` as in
+    `evaluate_ensemble_scores`: None or all axes pools every point (a host array and a float), otherwise the kept axes lead the
+    result (float64 device tensors, nothing synchronised).  Lists of equally shaped horizons go through as the segments of one
+    call and give a leading axis."""
+    many = not torch.is_tensor(predictions)
+    plist, tlist = (list(predictions), list(targets)) if many else ([predictions], [targets])
+    if many and (len(plist) != len(tlist) or not plist):
+        raise ValueError(f"{len(plist)} prediction horizons but {len(tlist)} target horizons")
+    for p, t in zip(plist, tlist):
+        if p.shape[1] != t.shape[0]:
+            raise AssertionError(f"predictions.shape[1] ({p.shape[1]}) != targets.shape[0] ({t.shape[0]})")
+        if not p.is_cuda or not t.is_cuda:
+            raise ValueError("dyffusion_amd.metrics works on GPU tensors (the HIP engine computes them)")
+    shape = tuple(tlist[0].shape)
+    grouped = mean_dims_to_group_shape(shape, mean_dims)
+    if grouped is None:
+        bins = engine.rank_histogram(plist, tlist)[:, 0].cpu().numpy()  # (T, N + 1)
+        freq, ri = rank_histogram_frequencies(bins)
+        return {"rank_hist": freq if many else freq[0], "reliability_index": ri if many else float(ri[0])}
+    a, b, group_shape = grouped
+    bins = engine.rank_histogram(plist, tlist, group_shape=group_shape)  # (T, G, N + 1)
+    bins = bins.reshape(len(plist), *shape[a:b + 1], bins.shape[-1])
+    freq, ri = rank_histogram_frequencies(bins if many else bins[0])
+    return {"rank_hist": freq, "reliability_index": ri}
+
+
+def eval_rank_histograms(results: Dict[str, Tensor], engine: HipEngine, split: str = "val", infix: Optional[str] = None) -> Dict[str, object]:
+    """`{split}/{infix}t{k}/rank_hist` (a float64 array (N + 1,) of frequencies) and `.../t{k}/reliability_index` (a float) for every
+    `t{k}_preds` / `t{k}_targets` pair of an evaluation step's output, and `{split}/{infix}avg/...`, their means over the horizons;
+    horizons of equal shape are the segments of one `rank_histogram` call."""
+    infix = "" if infix is None else infix
+    shapes: Dict[tuple, list] = {}
+    for prefix, key, tkey in _horizon_pairs(results):
+        shapes.setdefault((tuple(results[key].shape), tuple(results[tkey].shape)), []).append((prefix, key, tkey))
+    out: Dict[str, object] = {}
+    hists, indices = [], []
+    for members in shapes.values():
+        bins = engine.rank_histogram([results[k] for _, k, _ in members], [results[t] for _, _, t in members])[:, 0].cpu().numpy()
+        freq, ri = rank_histogram_frequencies(bins)
+        for s, (prefix, _, _) in enumerate(members):
+            out[f"{split}/{infix}{prefix}/rank_hist"] = freq[s]
+            out[f"{split}/{infix}{prefix}/reliability_index"] = float(ri[s])
+            hists.append(freq[s])
+            indices.append(float(ri[s]))
+    if hists and all(h.shape == hists[0].shape for h in hists):
+        out[f"{split}/{infix}avg/rank_hist"] = np.mean(hists, axis=0)
+    if indices:
+        out[f"{split}/{infix}avg/reliability_index"] = float(sum(indices) / len(indices))
+    return out
+
+
 def _horizon_pairs(results: Dict[str, Tensor]):
     """(prefix, predictions key, targets key) of every `t{k}_preds` / `t{k}_targets` pair, in the order of `results`."""
     for key in [k for k in results if k.endswith("preds")]:
@@ -260,14 +330,16 @@ class TrajectoryMetricsAccumulator:
     the curves mse / ssr / crps over its T horizon steps, the epoch reports their mean over instances.  The sum of the curves
     stays on the device ((3, T) float64, added to by the kernel itself); `compute()` makes the only device-to-host copy."""
 
-    def __init__(self, engine: HipEngine, by_size: bool = False):
+    def __init__(self, engine: HipEngine, by_size: bool = False, rank_histogram: bool = False):
         self._engine = engine
         self._by_size = by_size  # also the (4, T, N) sum of the ensemble-size curves (HipEngine.ensemble_size_metrics)
+        self._rank_histogram = rank_histogram  # also the (T, 1, N + 1) sum of the pooled rank histograms (HipEngine.rank_histogram)
         self.reset()
 
     def reset(self) -> None:
         self._sum: Optional[Tensor] = None
         self._size_sum: Optional[Tensor] = None
+        self._hist_sum: Optional[Tensor] = None
         self.count = 0
 
     def update(self, preds_list: Sequence[Tensor], targets_list: Sequence[Tensor]) -> Tensor:
@@ -287,18 +359,28 @@ class TrajectoryMetricsAccumulator:
             elif n != self._size_sum.shape[2]:
                 raise ValueError(f"{n} members, but the accumulated ensemble-size curves have {self._size_sum.shape[2]}")
             self._engine.ensemble_size_metrics(preds_list, targets_list, accum=self._size_sum)
+        if self._rank_histogram:
+            n = preds_list[0].shape[0]
+            if self._hist_sum is None:
+                self._hist_sum = torch.zeros(len(preds_list), 1, n + 1, dtype=torch.float64, device=preds_list[0].device)
+            elif n + 1 != self._hist_sum.shape[2]:
+                raise ValueError(f"{n} members, but the accumulated rank histograms have {self._hist_sum.shape[2] - 1}")
+            self._engine.rank_histogram(preds_list, targets_list, accum=self._hist_sum)
         self.count += 1
         return curves
 
     def compute(self) -> Dict[str, np.ndarray]:
         """{metric: (T,) float64 array}: the mean over the instances seen since the last reset ({} before the first update); with
-        `by_size` also "by_size": the (4, T, N) mean of the ensemble-size curves (planes SIZE_ROWS)."""
+        `by_size` also "by_size": the (4, T, N) mean of the ensemble-size curves (planes SIZE_ROWS); with `rank_histogram` also
+        "rank_hist": the (T, N + 1) frequencies of the rank histograms summed over the instances."""
         if self._sum is None or self.count == 0:
             return {}
         mean = self._sum.cpu().numpy() / float(self.count)
         out = {m: mean[i] for i, m in enumerate(METRIC_ROWS)}
         if self._size_sum is not None:
             out["by_size"] = self._size_sum.cpu().numpy() / float(self.count)
+        if self._hist_sum is not None:
+            out["rank_hist"] = rank_histogram_frequencies(self._hist_sum[:, 0].cpu().numpy())[0]
         return out
 
 

@@ -335,6 +335,54 @@ dyf_status dyf_ensemble_size_metrics(dyf_engine* engine, int32_t n_segments, con
 dyf_status dyf_ensemble_scores(dyf_engine* engine, int32_t n_segments, const float* const* preds_dev,
                                const float* const* targets_dev, int32_t n_members, int64_t n_points, int64_t member_stride,
                                int64_t n_outer, int32_t n_groups, int64_t n_inner, double* out_dev, double* accum_dev, void* stream);
+/* Forecast products per grid point: what an ensemble forecast delivers -- the ensemble mean, the spread, the extremes, quantiles and
+ * exceedance probabilities -- reduced over the members on the device, K fields out for N members in (the reference hands back the
+ * member stack; numpy's np.mean / np.std / np.min / np.max / np.quantile(method="linear") / (x > t).mean() over the member axis
+ * are what the fields are held to).  Segments, member_stride and the host array of device pointers as in dyf_trajectory_metrics
+ * (there are no targets).  out_dev (device, [n_segments][K][n_points] fp32) receives the K planes asked for, in the fixed order
+ * mean, std, min, max, the quantiles in the order given, the exceedances in the order given.  Per point, members x_0 .. x_{N-1}:
+ *   mean, std    the fp32 expressions of dyf_trajectory_metrics: the sum in member order, mean = sum * (1 / N), var = sum (x - mean)^2
+ *                * (1 / N) (population), std = sqrtf(var); where several threads share a point their partial sums are joined in a
+ *                fixed order
+ *   min, max     exact
+ *   quantile q   numpy's default ("linear", type 7) on the sorted members: h = (N - 1) q in double on the host, lo = floor(h), hi =
+ *                min(lo + 1, N - 1), the fraction h - lo rounded to fp32; value = x_(lo) + frac * (x_(hi) - x_(lo)) in fp32 without
+ *                contraction, and x_(lo) itself when frac == 0: q = 0 and q = 1 are the min and max planes, the median of an odd
+ *                ensemble is a member.  The order statistics are selected by counting ranks (no sort)
+ *   exceedance t (float)#{n : x_n > t} / (float)N, strict
+ * A point with a NaN member has NaN in its mean, std, min, max and quantile planes (as numpy); an exceedance counts the comparisons
+ * that are true; its neighbours are untouched.  Infinities are specified for min, max and exceedance only; the sign of a zero order
+ * statistic is unspecified.  K == 0, a flag that is not 0 / 1, a probability outside [0, 1] or NaN, a NaN threshold, or counts
+ * above the two maxima: DYF_ERR_INVALID_ARGUMENT.  One launch on `stream`, no atomics, no workspace: a point's outputs depend on
+ * its own members alone -- not on the layout, the segment or the other points -- and identical calls give identical bits.  Does
+ * NOT synchronise.  n_members in [1, 15360], n_segments in [1, 65535], at most 2^24 - 1 workgroups per segment (256 points each up
+ * to 64 members; beyond: the largest power of two P <= 128 with n_members * P * 4 <= 60 KB): DYF_ERR_UNSUPPORTED beyond.
+ * (Additive: no ABI change.) */
+#define DYF_MAX_PRODUCT_QUANTILES  16
+#define DYF_MAX_PRODUCT_THRESHOLDS 16
+typedef struct dyf_products_spec {
+    int32_t mean, std, min, max;                 /* 0 / 1 each */
+    int32_t n_quantiles;  double quantiles[DYF_MAX_PRODUCT_QUANTILES];    /* probabilities in [0, 1] */
+    int32_t n_thresholds; float  thresholds[DYF_MAX_PRODUCT_THRESHOLDS];  /* P(x > threshold) */
+} dyf_products_spec;
+dyf_status dyf_ensemble_products(dyf_engine* engine, int32_t n_segments, const float* const* preds_dev, int32_t n_members,
+                                 int64_t n_points, int64_t member_stride, const dyf_products_spec* spec, float* out_dev, void* stream);
+/* The rank histogram (Talagrand diagram) per (segment, GROUP): where the truth falls among the members, the companion of the
+ * spread-skill ratio.  Segments, member_stride, the two host arrays of device pointers and the group geometry (n_outer, n_groups,
+ * n_inner) exactly as in dyf_ensemble_scores; a geometry whose product is not n_points is DYF_ERR_INVALID_ARGUMENT.  out_dev
+ * (device, [n_segments][n_groups][n_members + 1] doubles) receives the bins; accum_dev (device, the same shape, or NULL) += out.
+ * For a point with target y, b = #{n : x_n < y} and e = #{n : x_n == y}: each of the bins b .. b + e receives 1 / (e + 1), the
+ * uniform split of ties (a boundary-condition pixel, where every member equals the target, spreads over all bins).  A point whose
+ * target or any member is NaN contributes nothing: the bins of a group sum to its number of NaN-free points, and without ties every
+ * bin is an integer.  Two launches on `stream`, no atomics: a group's points are cut into tiles of 256 consecutive points of one
+ * (outer, group) slab, min(tiles of the group, 256) workgroups walk them and each leaves one partial histogram in an engine-owned
+ * workspace -- at most n_segments x n_groups x 256 x (n_members + 1) doubles, grown on demand -- which the second launch adds in a
+ * fixed order: a group's bins depend on its own points, n_members, n_outer and n_inner alone, and identical calls give identical
+ * bits.  Does NOT synchronise.  n_members in [1, 1024] (DYF_ERR_UNSUPPORTED beyond), n_segments in [1, 65535]; n_outer * n_groups *
+ * ceil(n_inner / 256) is at most 2^24 - 1 as for dyf_ensemble_scores: DYF_ERR_UNSUPPORTED beyond.  (Additive: no ABI change.) */
+dyf_status dyf_rank_histogram(dyf_engine* engine, int32_t n_segments, const float* const* preds_dev, const float* const* targets_dev,
+                              int32_t n_members, int64_t n_points, int64_t member_stride, int64_t n_outer, int32_t n_groups,
+                              int64_t n_inner, double* out_dev, double* accum_dev, void* stream);
 /* Copy one (NB,C,H,W) field of the sampler's state after the most recent dyf_sample call: what sample_loop returns
  * beside the intermediates (dyffusion.py:424-426): (x0_hat, ., x_s), or (x_s, ., x_interpolated_s_next) when the sampling
  * schedule stops before T-1. */
