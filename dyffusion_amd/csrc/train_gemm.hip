@@ -548,9 +548,10 @@ bool tgemm_conv_fwd(const TConv& g, const float* x, const float* wt, const float
     if (h16 && sp) {
         dyf_form_note("t_gemm_mfma16x3<forward>", g.n);
         hipLaunchKernelGGL((t_gemm_mfma16<TG_FWD, true>), dim3((unsigned)mt, g.cout / GN, splits), dim3(256), 0, st, g, x, wt, bias, splits > 1 ? ws : y, len, 0);
-    } else if (h16)
+    } else if (h16) {
+        dyf_form_note("t_gemm_mfma16<forward>", g.n);
         hipLaunchKernelGGL(t_gemm_mfma16<TG_FWD>, dim3((unsigned)mt, g.cout / GN, splits), dim3(256), 0, st, g, x, wt, bias, splits > 1 ? ws : y, len, 0);
-    else
+    } else
         hipLaunchKernelGGL(t_gemm_mfma<TG_FWD>, dim3((unsigned)mt, g.cout / GN, splits), dim3(256), 0, st, g, x, wt, bias, splits > 1 ? ws : y, len);
     if (splits > 1)
         hipLaunchKernelGGL(t_splitk_finish, dim3((unsigned)((M * g.cout + 255) / 256)), dim3(256), 0, st, ws, splits, M * g.cout, g.cout, bias, y);
@@ -583,9 +584,10 @@ bool tgemm_conv_dgrad(const TConv& g, const float* dz, const float* w, const flo
     if (h16 && sp) {
         dyf_form_note("t_gemm_mfma16x3<dgrad>", g.n);
         hipLaunchKernelGGL((t_gemm_mfma16<TG_DGRAD, true>), dim3((unsigned)mt, g.cin / GN, splits), dim3(256), 0, st, g, dz, w, bias, splits > 1 ? ws : dx, len, 0);
-    } else if (h16)
+    } else if (h16) {
+        dyf_form_note("t_gemm_mfma16<dgrad>", g.n);
         hipLaunchKernelGGL(t_gemm_mfma16<TG_DGRAD>, dim3((unsigned)mt, g.cin / GN, splits), dim3(256), 0, st, g, dz, w, bias, splits > 1 ? ws : dx, len, 0);
-    else
+    } else
         hipLaunchKernelGGL(t_gemm_mfma<TG_DGRAD>, dim3((unsigned)mt, g.cin / GN, splits), dim3(256), 0, st, g, dz, w, bias, splits > 1 ? ws : dx, len);
     if (splits > 1)
         hipLaunchKernelGGL(t_splitk_finish, dim3((unsigned)((M * g.cin + 255) / 256)), dim3(256), 0, st, ws, splits, M * g.cin, g.cin, bias, dx);
