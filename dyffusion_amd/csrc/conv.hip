@@ -21,6 +21,7 @@
 //   * blockIdx -> tile map is XCD-aware (block b runs on XCD b % 8): every XCD walks a contiguous range of tiles so
 //     the 3x3 / 4x4 halo re-reads of neighbouring tiles hit that XCD's own L2.
 #include "conv.h"
+#include "conv_epilogue.h"
 
 #include <algorithm>
 #include <type_traits>
@@ -459,9 +460,8 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_kernel(ConvArgs a, int M, i
 
     // ---- epilogue straight from the accumulators.  The operands are swapped (D^T = W X^T), so lane (l31, hi) of
     // accumulator (i, j) holds PIXEL l31 of pixel sub-tile i and CHANNELS j*32 + 8*g + 4*hi + {0..3} (g = register group):
-    // affine / activation / dropout / residual run in registers, register groups 2*g2 and 2*g2+1 are packed to bf16 and
-    // exchanged between lanes l and l+32 (v_permlane32_swap) so that every lane stores 8 consecutive channels (16 B).
-    // No LDS round trip, no barrier; (activation, dropout mode) are wave-uniform and dispatched once.
+    // the layout of the shared step (conv_epilogue.h) -- affine / activation / dropout / residual in registers, 16-bit pack, exchange
+    // between lanes l and l+32 -- after which every lane stores 8 consecutive channels (16 B); fp32 output leaves before the pack.
     auto epilogue = [&](auto act_c, auto mode_c) {
         constexpr int ACT = decltype(act_c)::value, MODE = decltype(mode_c)::value;
 #pragma unroll
@@ -486,51 +486,27 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_kernel(ConvArgs a, int M, i
 #pragma unroll
                 for (int g2 = 0; g2 < 2; ++g2) {
                     const int cg0 = j * 32 + 16 * g2;  // + 4*hi: own channels of group 2*g2; + 8: group 2*g2+1
-                    const float4 ca0 = *(const float4*)(a.coef_a + cb + cg0), ca1 = *(const float4*)(a.coef_a + cb + cg0 + 8);
-                    const float4 cc0 = *(const float4*)(a.coef_c + cb + cg0), cc1 = *(const float4*)(a.coef_c + cb + cg0 + 8);
-                    const float ps = drop_prescale<ACT, MODE>(a.drop);  // dropout scale folded into the affine
-                    const float ca[8] = {ca0.x * ps, ca0.y * ps, ca0.z * ps, ca0.w * ps, ca1.x * ps, ca1.y * ps, ca1.z * ps, ca1.w * ps};
-                    const float cc[8] = {cc0.x * ps, cc0.y * ps, cc0.z * ps, cc0.w * ps, cc1.x * ps, cc1.y * ps, cc1.z * ps, cc1.w * ps};
+                    float ca[8], cc[8], v[8];
+                    epi_coef(a.coef_a + cb + cg0, a.coef_c + cb + cg0, drop_prescale<ACT, MODE>(a.drop), ca, cc);
                     const uint32_t e0 = ob + cg0 + 4 * hi;
-                    float v[8];
-#pragma unroll
-                    for (int t = 0; t < 8; ++t) v[t] = fmaf(acc[i][j][8 * g2 + t], ca[t], cc[t]);
-                    act_drop_fixed<4, ACT, MODE, true>(v, e0, row0, a.drop, key);
-                    act_drop_fixed<4, ACT, MODE, true>(v + 4, e0 + 8, row0, a.drop, key);
+                    epi_values<ACT, MODE>(acc[i][j], 8 * g2, ca, cc, e0, row0, a.drop, key, v);
                     if (a.residual) {
                         const uint2 r0 = valid ? *(const uint2*)(a.residual + (size_t)e0) : make_uint2(0, 0);
                         const uint2 r1 = valid ? *(const uint2*)(a.residual + (size_t)e0 + 8) : make_uint2(0, 0);
-                        const uint32_t rw[4] = {r0.x, r0.y, r1.x, r1.y};
-#pragma unroll
-                        for (int t = 0; t < 8; ++t)
-                            v[t] += (t & 1) ? el16_hi(rw[t >> 1]) : el16_lo(rw[t >> 1]);
+                        epi_add_residual(v, r0, r1);
                     }
                     if (a.out_f32 && valid) {
                         *(float4*)(a.out_f32 + (size_t)e0) = make_float4(v[0], v[1], v[2], v[3]);
                         *(float4*)(a.out_f32 + (size_t)e0 + 8) = make_float4(v[4], v[5], v[6], v[7]);
                     }
                     if (a.out_el16) {
-                        uint32_t p0 = pack_el16x2(v[0], v[1]), p1 = pack_el16x2(v[2], v[3]);
-                        uint32_t q0 = pack_el16x2(v[4], v[5]), q1 = pack_el16x2(v[6], v[7]);
-                        const auto s0 = __builtin_amdgcn_permlane32_swap(p0, q0, false, false);
-                        const auto s1 = __builtin_amdgcn_permlane32_swap(p1, q1, false, false);
-                        // lanes 0-31: channels cg0 + 0..7 (own group 2*g2 + partner's); lanes 32-63: cg0 + 8..15
-                        uint4 o;
-                        o.x = s0[0]; o.y = s1[0]; o.z = s0[1]; o.w = s1[1];
+                        const uint4 o = epi_pack_swap(v);
                         if (valid) *(uint4*)(a.out_el16 + (size_t)(ob + cg0 + 8 * hi)) = o;
                     }
                 }
         }
     };
-    auto by_mode = [&](auto act_c) {
-        if (a.drop.mode == 0) epilogue(act_c, std::integral_constant<int, 0>{});
-        else if (a.drop.mode == 1) epilogue(act_c, std::integral_constant<int, 1>{});
-        else epilogue(act_c, std::integral_constant<int, 2>{});
-    };
-    if (a.act == ACT_RELU) by_mode(std::integral_constant<int, ACT_RELU>{});
-    else if (a.act == ACT_LEAKY) by_mode(std::integral_constant<int, ACT_LEAKY>{});
-    else if (a.act == ACT_SILU) by_mode(std::integral_constant<int, ACT_SILU>{});
-    else by_mode(std::integral_constant<int, ACT_NONE>{});
+    epi_dispatch(a.act, a.drop.mode, epilogue);
 #endif
 }
 

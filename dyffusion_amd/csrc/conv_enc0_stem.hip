@@ -28,6 +28,7 @@
 // the 16 taps, computed from (oy, ox) without a load, against the composed per-tap bias weights -- the same 16-bit values times the
 // same ones, so only the order of the fp32 sums differs from the 16-channel form.
 #include "conv.h"
+#include "conv_epilogue.h"
 
 #include <type_traits>
 typedef __attribute__((ext_vector_type(16))) float f32x16;
@@ -149,21 +150,10 @@ __global__ __launch_bounds__(512) void conv_enc0_stem_kernel(ConvArgs a, const e
 #pragma unroll
             for (int g2 = 0; g2 < 2; ++g2) {
                 const int cg0 = nt * 32 + 16 * g2;
-                const float4 ca0 = *(const float4*)(coefl + cg0 + 4 * hi), ca1 = *(const float4*)(coefl + cg0 + 4 * hi + 8);
-                const float4 cc0 = *(const float4*)(coefl + NT * 32 + cg0 + 4 * hi), cc1 = *(const float4*)(coefl + NT * 32 + cg0 + 4 * hi + 8);
-                const float ca[8] = {ca0.x, ca0.y, ca0.z, ca0.w, ca1.x, ca1.y, ca1.z, ca1.w};
-                const float cc[8] = {cc0.x, cc0.y, cc0.z, cc0.w, cc1.x, cc1.y, cc1.z, cc1.w};
+                float ca[8], cc[8];  // the row's table in LDS is already scaled
+                epi_coef(coefl + cg0 + 4 * hi, coefl + NT * 32 + cg0 + 4 * hi, 1.0f, ca, cc);
                 const uint32_t e0 = ob + cg0 + 4 * hi;
-                float v[8];
-#pragma unroll
-                for (int i = 0; i < 8; ++i) v[i] = fmaf(acc[nt][8 * g2 + i], ca[i], cc[i]);
-                act_drop_fixed<4, ACT, MODE, true>(v, e0, row0, a.drop, key);
-                act_drop_fixed<4, ACT, MODE, true>(v + 4, e0 + 8, row0, a.drop, key);
-                const uint32_t p0 = pack_el16x2(v[0], v[1]), p1 = pack_el16x2(v[2], v[3]);
-                const uint32_t q0 = pack_el16x2(v[4], v[5]), q1 = pack_el16x2(v[6], v[7]);
-                const auto s0 = __builtin_amdgcn_permlane32_swap(p0, q0, false, false);
-                const auto s1 = __builtin_amdgcn_permlane32_swap(p1, q1, false, false);
-                o2[g2].x = s0[0]; o2[g2].y = s1[0]; o2[g2].z = s0[1]; o2[g2].w = s1[1];
+                o2[g2] = epi_step<ACT, MODE>(acc[nt], 8 * g2, ca, cc, e0, row0, a.drop, key);
             }
             *(uint4*)(ostage + l31 * OROW + (nt * 32 + 8 * hi) * 2) = o2[0];
             *(uint4*)(ostage + l31 * OROW + (nt * 32 + 16 + 8 * hi) * 2) = o2[1];
@@ -196,15 +186,7 @@ __global__ __launch_bounds__(512) void conv_enc0_stem_kernel(ConvArgs a, const e
             tile(t + E0_WAVES, xb, act_c, mode_c);
         }
     };
-    auto by_mode = [&](auto act_c) {
-        if (a.drop.mode == 0) run(act_c, std::integral_constant<int, 0>{});
-        else if (a.drop.mode == 1) run(act_c, std::integral_constant<int, 1>{});
-        else run(act_c, std::integral_constant<int, 2>{});
-    };
-    if (a.act == ACT_RELU) by_mode(std::integral_constant<int, ACT_RELU>{});
-    else if (a.act == ACT_LEAKY) by_mode(std::integral_constant<int, ACT_LEAKY>{});
-    else if (a.act == ACT_SILU) by_mode(std::integral_constant<int, ACT_SILU>{});
-    else by_mode(std::integral_constant<int, ACT_NONE>{});
+    epi_dispatch(a.act, a.drop.mode, run);
 #endif
 }
 

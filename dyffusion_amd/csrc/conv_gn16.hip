@@ -22,6 +22,7 @@
 //     epilogue runs straight out of the accumulators.
 // The K loop is plain HIP (no hand-placed asm): with 12 waves per CU the scheduler has other waves to issue while one waits.
 #include "conv.h"
+#include "conv_epilogue.h"
 #include "gn_fused.h"
 
 #include <algorithm>
@@ -298,8 +299,8 @@ __global__ __launch_bounds__(256, 3) void conv_gn16_kernel(ConvArgs a, int tiles
         cfC[lane] = ac.y;
     }
     __syncthreads();
-    // Phase C: y * A + C -> SiLU -> dropout -> (+ residual) -> 16-bit; groups 2 g2 and 2 g2 + 1 are packed and exchanged between lanes
-    // l and l + 32 (v_permlane32_swap), after which every lane owns 8 consecutive channels = one 16-byte store
+    // Phase C: y * A + C -> SiLU -> dropout (the pre-hashed keep bits) -> (+ residual) -> 16-bit rows of 8 consecutive channels, one
+    // 16-byte store per lane (conv_epilogue.h)
     auto fused = [&](auto mode_c) {
         constexpr int MODE = decltype(mode_c)::value;
         // 32-channel half outermost, pixel tiles, then the two 16-channel groups of the half: the two 32-byte pieces of a pixel's 64-byte
@@ -315,12 +316,9 @@ __global__ __launch_bounds__(256, 3) void conv_gn16_kernel(ConvArgs a, int tiles
                     // (A, C) of this lane's 8 channels of the 16-channel group, from LDS per use: 16 live registers instead of 64 beside
                     // the accumulators and the prefetched residual
                     const int cgl = nt * 32 + 16 * g2 + 4 * hi;
-                    const float4 a0 = *(const float4*)(cfA + cgl), a1 = *(const float4*)(cfA + cgl + 8);
-                    const float4 c0 = *(const float4*)(cfC + cgl), c1 = *(const float4*)(cfC + cgl + 8);
-                    const float ca[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
-                    const float cc[8] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w};
+                    float ca[8], cc[8], v[8];
+                    epi_coef(cfA + cgl, cfC + cgl, 1.0f, ca, cc);
                     const int cg0 = nt * 32 + 16 * g2;
-                    float v[8];
 #pragma unroll
                     for (int t = 0; t < 8; ++t) v[t] = act_fixed<ACT_SILU>(fmaf(acc[nt][mt][8 * g2 + t], ca[t], cc[t]));
                     if constexpr (MODE == 1) {
@@ -328,18 +326,8 @@ __global__ __launch_bounds__(256, 3) void conv_gn16_kernel(ConvArgs a, int tiles
 #pragma unroll
                         for (int t = 0; t < 8; ++t) v[t] = ((kb >> t) & 1u) ? v[t] * a.drop.scale : 0.0f;
                     }
-                    if (has_res) {
-                        const uint2 r0 = rq[s][2 * g2], r1 = rq[s][2 * g2 + 1];
-                        const uint32_t rw[4] = {r0.x, r0.y, r1.x, r1.y};
-#pragma unroll
-                        for (int t = 0; t < 8; ++t) v[t] += (t & 1) ? el16_hi(rw[t >> 1]) : el16_lo(rw[t >> 1]);
-                    }
-                    uint32_t p0 = pack_el16x2(v[0], v[1]), p1 = pack_el16x2(v[2], v[3]);
-                    uint32_t q0 = pack_el16x2(v[4], v[5]), q1 = pack_el16x2(v[6], v[7]);
-                    const auto s0 = __builtin_amdgcn_permlane32_swap(p0, q0, false, false);
-                    const auto s1 = __builtin_amdgcn_permlane32_swap(p1, q1, false, false);
-                    uint4 o;
-                    o.x = s0[0]; o.y = s1[0]; o.z = s0[1]; o.w = s1[1];
+                    if (has_res) epi_add_residual(v, rq[s][2 * g2], rq[s][2 * g2 + 1]);
+                    const uint4 o = epi_pack_swap(v);
                     if (st_ok) *(uint4*)(a.out_el16 + (size_t)(o0 + mt * mt_stride + cg0 + 8 * hi)) = o;
                 }
             }

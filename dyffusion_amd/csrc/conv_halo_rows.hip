@@ -16,6 +16,7 @@
 // rows; the weight ring (6 sets, 5 mini-slots ahead) is the one of conv_up_halo_kernel, addressed (tap, ks) directly; the 6
 // row fragments of super-slot s + 1 are read, two per mini-slot, during super-slot s.
 #include "conv.h"
+#include "conv_epilogue.h"
 
 #include <algorithm>
 #include <cmath>
@@ -355,12 +356,7 @@ __device__ __forceinline__ void conv_halo_rows_body(const ConvArgs& a, int tiles
 #pragma unroll
                 for (int g2 = 0; g2 < 2; ++g2) {
                     const int cg0 = nt * 32 + 16 * g2;
-                    const float4 ca0 = *(const float4*)(a.coef_a + ci_base + cg0), ca1 = *(const float4*)(a.coef_a + ci_base + cg0 + 8);
-                    const float4 cc0 = *(const float4*)(a.coef_c + ci_base + cg0), cc1 = *(const float4*)(a.coef_c + ci_base + cg0 + 8);
-                    ca[nt][g2][0] = ca0.x * ps; ca[nt][g2][1] = ca0.y * ps; ca[nt][g2][2] = ca0.z * ps; ca[nt][g2][3] = ca0.w * ps;
-                    ca[nt][g2][4] = ca1.x * ps; ca[nt][g2][5] = ca1.y * ps; ca[nt][g2][6] = ca1.z * ps; ca[nt][g2][7] = ca1.w * ps;
-                    cc[nt][g2][0] = cc0.x * ps; cc[nt][g2][1] = cc0.y * ps; cc[nt][g2][2] = cc0.z * ps; cc[nt][g2][3] = cc0.w * ps;
-                    cc[nt][g2][4] = cc1.x * ps; cc[nt][g2][5] = cc1.y * ps; cc[nt][g2][6] = cc1.z * ps; cc[nt][g2][7] = cc1.w * ps;
+                    epi_coef(a.coef_a + ci_base + cg0, a.coef_c + ci_base + cg0, ps, ca[nt][g2], cc[nt][g2]);
                 }
             const uint32_t pstride = (uint32_t)((H::PLAIN ? 1 : 2) * a.cout);     // elements between the row's consecutive pixels
             const uint32_t row_base = store0 - (uint32_t)l31 * pstride;             // pixel 0 of this wave's tile row 0
@@ -373,17 +369,7 @@ __device__ __forceinline__ void conv_halo_rows_body(const ConvArgs& a, int tiles
                     for (int g2 = 0; g2 < 2; ++g2) {
                         const int cg0 = nt * 32 + 16 * g2;
                         const uint32_t e0 = o0 + t * t_stride + cg0 + 4 * hi;
-                        float v[8];
-#pragma unroll
-                        for (int q = 0; q < 8; ++q) v[q] = fmaf(acc[nt][t][8 * g2 + q], ca[nt][g2][q], cc[nt][g2][q]);
-                        act_drop_fixed<4, ACT, MODE, true>(v, e0, row0, a.drop, key);
-                        act_drop_fixed<4, ACT, MODE, true>(v + 4, e0 + 8, row0, a.drop, key);
-                        uint32_t p0 = pack_el16x2(v[0], v[1]), p1 = pack_el16x2(v[2], v[3]);
-                        uint32_t q0 = pack_el16x2(v[4], v[5]), q1 = pack_el16x2(v[6], v[7]);
-                        const auto s0 = __builtin_amdgcn_permlane32_swap(p0, q0, false, false);
-                        const auto s1 = __builtin_amdgcn_permlane32_swap(p1, q1, false, false);
-                        uint4 o;
-                        o.x = s0[0]; o.y = s1[0]; o.z = s0[1]; o.w = s1[1];
+                        const uint4 o = epi_step<ACT, MODE>(acc[nt][t], 8 * g2, ca[nt][g2], cc[nt][g2], e0, row0, a.drop, key);
                         *(uint4*)(ost + l31 * H::OROW + (cg0 + 8 * hi) * 2) = o;
                     }
 #pragma unroll
@@ -409,12 +395,7 @@ __device__ __forceinline__ void conv_halo_rows_body(const ConvArgs& a, int tiles
 #pragma unroll
                 for (int g2 = 0; g2 < 2; ++g2) {
                     const int cg0 = nt * 32 + 16 * g2;
-                    const float4 ca0 = *(const float4*)(a.coef_a + ci_base + cg0), ca1 = *(const float4*)(a.coef_a + ci_base + cg0 + 8);
-                    const float4 cc0 = *(const float4*)(a.coef_c + ci_base + cg0), cc1 = *(const float4*)(a.coef_c + ci_base + cg0 + 8);
-                    ca[nt][g2][0] = ca0.x * ps; ca[nt][g2][1] = ca0.y * ps; ca[nt][g2][2] = ca0.z * ps; ca[nt][g2][3] = ca0.w * ps;
-                    ca[nt][g2][4] = ca1.x * ps; ca[nt][g2][5] = ca1.y * ps; ca[nt][g2][6] = ca1.z * ps; ca[nt][g2][7] = ca1.w * ps;
-                    cc[nt][g2][0] = cc0.x * ps; cc[nt][g2][1] = cc0.y * ps; cc[nt][g2][2] = cc0.z * ps; cc[nt][g2][3] = cc0.w * ps;
-                    cc[nt][g2][4] = cc1.x * ps; cc[nt][g2][5] = cc1.y * ps; cc[nt][g2][6] = cc1.z * ps; cc[nt][g2][7] = cc1.w * ps;
+                    epi_coef(a.coef_a + ci_base + cg0, a.coef_c + ci_base + cg0, ps, ca[nt][g2], cc[nt][g2]);
                 }
             // compact output row of this wave's tile row 0, column 0, channel block tn
             const uint32_t row_base = (uint32_t)((n_img * a.ho + 2 * ty0 + wpy) * a.up_wo_store) * (uint32_t)a.cout + (uint32_t)(tn * 64);
@@ -428,16 +409,7 @@ __device__ __forceinline__ void conv_halo_rows_body(const ConvArgs& a, int tiles
                     for (int g2 = 0; g2 < 2; ++g2) {
                         const int cg0 = nt * 32 + 16 * g2;
                         const uint32_t e0 = o0 + t * t_stride + cg0 + 4 * hi;  // dropout stream: dense position
-                        float v[8];
-#pragma unroll
-                        for (int q = 0; q < 8; ++q) v[q] = fmaf(acc[nt][t][8 * g2 + q], ca[nt][g2][q], cc[nt][g2][q]);
-                        act_drop_fixed<4, ACT, MODE, true>(v, e0, row0, a.drop, key);
-                        act_drop_fixed<4, ACT, MODE, true>(v + 4, e0 + 8, row0, a.drop, key);
-                        uint32_t p0 = pack_el16x2(v[0], v[1]), p1 = pack_el16x2(v[2], v[3]);
-                        uint32_t q0 = pack_el16x2(v[4], v[5]), q1 = pack_el16x2(v[6], v[7]);
-                        const auto s0 = __builtin_amdgcn_permlane32_swap(p0, q0, false, false);
-                        const auto s1 = __builtin_amdgcn_permlane32_swap(p1, q1, false, false);
-                        o[nt][g2].x = s0[0]; o[nt][g2].y = s1[0]; o[nt][g2].z = s0[1]; o[nt][g2].w = s1[1];
+                        o[nt][g2] = epi_step<ACT, MODE>(acc[nt][t], 8 * g2, ca[nt][g2], cc[nt][g2], e0, row0, a.drop, key);
                     }
 #pragma unroll
                 for (int h = 0; h < 2; ++h) {
@@ -474,12 +446,7 @@ __device__ __forceinline__ void conv_halo_rows_body(const ConvArgs& a, int tiles
 #pragma unroll
                 for (int g2 = 0; g2 < 2; ++g2) {
                     const int cg0 = nt * 32 + 16 * g2;
-                    const float4 ca0 = *(const float4*)(a.coef_a + ci_base + cg0), ca1 = *(const float4*)(a.coef_a + ci_base + cg0 + 8);
-                    const float4 cc0 = *(const float4*)(a.coef_c + ci_base + cg0), cc1 = *(const float4*)(a.coef_c + ci_base + cg0 + 8);
-                    ca[nt][g2][0] = ca0.x * ps; ca[nt][g2][1] = ca0.y * ps; ca[nt][g2][2] = ca0.z * ps; ca[nt][g2][3] = ca0.w * ps;
-                    ca[nt][g2][4] = ca1.x * ps; ca[nt][g2][5] = ca1.y * ps; ca[nt][g2][6] = ca1.z * ps; ca[nt][g2][7] = ca1.w * ps;
-                    cc[nt][g2][0] = cc0.x * ps; cc[nt][g2][1] = cc0.y * ps; cc[nt][g2][2] = cc0.z * ps; cc[nt][g2][3] = cc0.w * ps;
-                    cc[nt][g2][4] = cc1.x * ps; cc[nt][g2][5] = cc1.y * ps; cc[nt][g2][6] = cc1.z * ps; cc[nt][g2][7] = cc1.w * ps;
+                    epi_coef(a.coef_a + ci_base + cg0, a.coef_c + ci_base + cg0, ps, ca[nt][g2], cc[nt][g2]);
                 }
             const int rpx = lane >> 3, rch = lane & 7;  // read-back role: (slot 8 k + rpx, 16-byte chunk)
 #pragma unroll
@@ -490,17 +457,7 @@ __device__ __forceinline__ void conv_halo_rows_body(const ConvArgs& a, int tiles
                     for (int g2 = 0; g2 < 2; ++g2) {
                         const int cg0 = nt * 32 + 16 * g2;
                         const uint32_t e0 = o0 + t * t_stride + cg0 + 4 * hi;  // dropout stream: dense position
-                        float v[8];
-#pragma unroll
-                        for (int q = 0; q < 8; ++q) v[q] = fmaf(acc[nt][t][8 * g2 + q], ca[nt][g2][q], cc[nt][g2][q]);
-                        act_drop_fixed<4, ACT, MODE, true>(v, e0, row0, a.drop, key);
-                        act_drop_fixed<4, ACT, MODE, true>(v + 4, e0 + 8, row0, a.drop, key);
-                        uint32_t p0 = pack_el16x2(v[0], v[1]), p1 = pack_el16x2(v[2], v[3]);
-                        uint32_t q0 = pack_el16x2(v[4], v[5]), q1 = pack_el16x2(v[6], v[7]);
-                        const auto s0 = __builtin_amdgcn_permlane32_swap(p0, q0, false, false);
-                        const auto s1 = __builtin_amdgcn_permlane32_swap(p1, q1, false, false);
-                        uint4 o;
-                        o.x = s0[0]; o.y = s1[0]; o.z = s0[1]; o.w = s1[1];
+                        const uint4 o = epi_step<ACT, MODE>(acc[nt][t], 8 * g2, ca[nt][g2], cc[nt][g2], e0, row0, a.drop, key);
                         *(uint4*)(ost + l31 * H::OROW + (cg0 + 8 * hi) * 2) = o;
                     }
 #pragma unroll
@@ -526,12 +483,7 @@ __device__ __forceinline__ void conv_halo_rows_body(const ConvArgs& a, int tiles
 #pragma unroll
             for (int g2 = 0; g2 < 2; ++g2) {
                 const int cg0 = nt * 32 + 16 * g2;
-                const float4 ca0 = *(const float4*)(a.coef_a + ci_base + cg0), ca1 = *(const float4*)(a.coef_a + ci_base + cg0 + 8);
-                const float4 cc0 = *(const float4*)(a.coef_c + ci_base + cg0), cc1 = *(const float4*)(a.coef_c + ci_base + cg0 + 8);
-                ca[g2][0] = ca0.x * ps; ca[g2][1] = ca0.y * ps; ca[g2][2] = ca0.z * ps; ca[g2][3] = ca0.w * ps;
-                ca[g2][4] = ca1.x * ps; ca[g2][5] = ca1.y * ps; ca[g2][6] = ca1.z * ps; ca[g2][7] = ca1.w * ps;
-                cc[g2][0] = cc0.x * ps; cc[g2][1] = cc0.y * ps; cc[g2][2] = cc0.z * ps; cc[g2][3] = cc0.w * ps;
-                cc[g2][4] = cc1.x * ps; cc[g2][5] = cc1.y * ps; cc[g2][6] = cc1.z * ps; cc[g2][7] = cc1.w * ps;
+                epi_coef(a.coef_a + ci_base + cg0, a.coef_c + ci_base + cg0, ps, ca[g2], cc[g2]);
             }
 #pragma unroll
             for (int t = 0; t < TR; ++t) {
@@ -540,32 +492,14 @@ __device__ __forceinline__ void conv_halo_rows_body(const ConvArgs& a, int tiles
                     const int cg0 = nt * 32 + 16 * g2;
                     const uint32_t obase = o0 + t * t_stride + cg0;
                     const uint32_t e0 = obase + 4 * hi;
-                    float v[8];
-#pragma unroll
-                    for (int q = 0; q < 8; ++q) v[q] = fmaf(acc[nt][t][8 * g2 + q], ca[g2][q], cc[g2][q]);
-                    act_drop_fixed<4, ACT, MODE, true>(v, e0, row0, a.drop, key);
-                    act_drop_fixed<4, ACT, MODE, true>(v + 4, e0 + 8, row0, a.drop, key);
-                    uint32_t p0 = pack_el16x2(v[0], v[1]), p1 = pack_el16x2(v[2], v[3]);
-                    uint32_t q0 = pack_el16x2(v[4], v[5]), q1 = pack_el16x2(v[6], v[7]);
-                    const auto s0 = __builtin_amdgcn_permlane32_swap(p0, q0, false, false);
-                    const auto s1 = __builtin_amdgcn_permlane32_swap(p1, q1, false, false);
-                    uint4 o;
-                    o.x = s0[0]; o.y = s1[0]; o.z = s0[1]; o.w = s1[1];
+                    const uint4 o = epi_step<ACT, MODE>(acc[nt][t], 8 * g2, ca[g2], cc[g2], e0, row0, a.drop, key);
                     const uint32_t sbase = store0 + t * st_stride + cg0;
                     if (SP != 1 || lane_valid) *(uint4*)(a.out_el16 + (size_t)(sbase + 8 * hi)) = o;
                 }
             }
         }
     };
-    auto by_mode = [&](auto act_c) {
-        if (a.drop.mode == 0) epilogue(act_c, std::integral_constant<int, 0>{});
-        else if (a.drop.mode == 1) epilogue(act_c, std::integral_constant<int, 1>{});
-        else epilogue(act_c, std::integral_constant<int, 2>{});
-    };
-    if (a.act == ACT_RELU) by_mode(std::integral_constant<int, ACT_RELU>{});
-    else if (a.act == ACT_LEAKY) by_mode(std::integral_constant<int, ACT_LEAKY>{});
-    else if (a.act == ACT_SILU) by_mode(std::integral_constant<int, ACT_SILU>{});
-    else by_mode(std::integral_constant<int, ACT_NONE>{});
+    epi_dispatch(a.act, a.drop.mode, epilogue);
 #undef HKEY
 #endif
 }

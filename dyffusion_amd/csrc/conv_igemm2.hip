@@ -15,6 +15,7 @@
 // In-order completion of vector-memory loads makes the per-step wait free: the gather of step s+1 is issued BEFORE the
 // weight loads of step s, so by the time the last of those has been consumed the gather has landed.
 #include "conv.h"
+#include "conv_epilogue.h"
 #include "gn_fused.h"
 
 #include <algorithm>
@@ -508,48 +509,30 @@ __global__ __launch_bounds__(256, 2) void conv_igemm2_kernel(ConvArgs a, int M, 
             const int mt = step >> 2, nt = (step >> 1) & 1, g2 = step & 1;
             if (step + 1 < 4 * MT) load_coef(step + 1, cf[(step + 1) & 1]);
             if (gnf_res && step + 1 < 4 * MT) load_res(step + 1, rs[(step + 1) & 1]);
-            const float4 ca0 = cf[step & 1][0], ca1 = cf[step & 1][1], cc0 = cf[step & 1][2], cc1 = cf[step & 1][3];
             const bool valid = valid_[mt];
             const uint32_t ob = ob_[mt], row0 = row0_[mt];
             const RngKey key = key_[mt];
             {
-                {
-                    const int cg0 = nt * 32 + 16 * g2;  // + 4*hi: own channels of group 2*g2; + 8: group 2*g2+1
-                    const float ca[8] = {ca0.x * ps, ca0.y * ps, ca0.z * ps, ca0.w * ps, ca1.x * ps, ca1.y * ps, ca1.z * ps, ca1.w * ps};
-                    const float cc[8] = {cc0.x * ps, cc0.y * ps, cc0.z * ps, cc0.w * ps, cc1.x * ps, cc1.y * ps, cc1.z * ps, cc1.w * ps};
-                    const uint32_t e0 = ob + cg0 + 4 * hi;
-                    float v[8];
-#pragma unroll
-                    for (int t = 0; t < 8; ++t) v[t] = fmaf(acc[mt][nt][8 * g2 + t], ca[t], cc[t]);
-                    act_drop_fixed<4, ACT, MODE, true>(v, e0, row0, a.drop, key);
-                    act_drop_fixed<4, ACT, MODE, true>(v + 4, e0 + 8, row0, a.drop, key);
-                    if (gnf_res) {
-                        const uint32_t rw[4] = {rs[step & 1][0].x, rs[step & 1][0].y, rs[step & 1][1].x, rs[step & 1][1].y};
-#pragma unroll
-                        for (int t = 0; t < 8; ++t)
-                            v[t] += (t & 1) ? el16_hi(rw[t >> 1]) : el16_lo(rw[t >> 1]);
-                    } else if (!FAST && a.residual) {
-                        const uint2 r0 = valid ? *(const uint2*)(a.residual + (size_t)e0) : make_uint2(0, 0);
-                        const uint2 r1 = valid ? *(const uint2*)(a.residual + (size_t)e0 + 8) : make_uint2(0, 0);
-                        const uint32_t rw[4] = {r0.x, r0.y, r1.x, r1.y};
-#pragma unroll
-                        for (int t = 0; t < 8; ++t)
-                            v[t] += (t & 1) ? el16_hi(rw[t >> 1]) : el16_lo(rw[t >> 1]);
-                    }
-                    if (!FAST && a.out_f32 && valid) {
-                        *(float4*)(a.out_f32 + (size_t)e0) = make_float4(v[0], v[1], v[2], v[3]);
-                        *(float4*)(a.out_f32 + (size_t)e0 + 8) = make_float4(v[4], v[5], v[6], v[7]);
-                    }
-                    if (FAST || a.out_el16) {
-                        uint32_t p0 = pack_el16x2(v[0], v[1]), p1 = pack_el16x2(v[2], v[3]);
-                        uint32_t q0 = pack_el16x2(v[4], v[5]), q1 = pack_el16x2(v[6], v[7]);
-                        const auto s0 = __builtin_amdgcn_permlane32_swap(p0, q0, false, false);
-                        const auto s1 = __builtin_amdgcn_permlane32_swap(p1, q1, false, false);
-                        uint4 o;
-                        o.x = s0[0]; o.y = s1[0]; o.z = s0[1]; o.w = s1[1];
-                        if (STAGED) ostage[step & 3] = o;
-                        else if (FULL || valid) *(uint4*)(a.out_el16 + (size_t)(ob + cg0 + 8 * hi)) = o;
-                    }
+                const int cg0 = nt * 32 + 16 * g2;  // + 4*hi: own channels of group 2*g2; + 8: group 2*g2+1
+                float ca[8], cc[8], v[8];
+                epi_coef(cf[step & 1][0], cf[step & 1][1], cf[step & 1][2], cf[step & 1][3], ps, ca, cc);
+                const uint32_t e0 = ob + cg0 + 4 * hi;
+                epi_values<ACT, MODE>(acc[mt][nt], 8 * g2, ca, cc, e0, row0, a.drop, key, v);
+                if (gnf_res) {
+                    epi_add_residual(v, rs[step & 1][0], rs[step & 1][1]);
+                } else if (!FAST && a.residual) {
+                    const uint2 r0 = valid ? *(const uint2*)(a.residual + (size_t)e0) : make_uint2(0, 0);
+                    const uint2 r1 = valid ? *(const uint2*)(a.residual + (size_t)e0 + 8) : make_uint2(0, 0);
+                    epi_add_residual(v, r0, r1);
+                }
+                if (!FAST && a.out_f32 && valid) {
+                    *(float4*)(a.out_f32 + (size_t)e0) = make_float4(v[0], v[1], v[2], v[3]);
+                    *(float4*)(a.out_f32 + (size_t)e0 + 8) = make_float4(v[4], v[5], v[6], v[7]);
+                }
+                if (FAST || a.out_el16) {
+                    const uint4 o = epi_pack_swap(v);
+                    if (STAGED) ostage[step & 3] = o;
+                    else if (FULL || valid) *(uint4*)(a.out_el16 + (size_t)(ob + cg0 + 8 * hi)) = o;
                 }
             }
             if (STAGED && (step & 3) == 3) {
@@ -579,20 +562,12 @@ __global__ __launch_bounds__(256, 2) void conv_igemm2_kernel(ConvArgs a, int M, 
         else if (tile_full) epilogue(act_c, mode_c, std::true_type{}, std::false_type{});
         else epilogue(act_c, mode_c, std::false_type{}, std::false_type{});
     };
-    auto by_mode = [&](auto act_c) {
-        if (a.drop.mode == 0) by_full(act_c, std::integral_constant<int, 0>{});
-        else if (a.drop.mode == 1) by_full(act_c, std::integral_constant<int, 1>{});
-        else by_full(act_c, std::integral_constant<int, 2>{});
-    };
     if constexpr (GNF) {  // SiLU, dropout off or from the engine's generator (the launcher checks)
         if (a.drop.mode == 1) by_full(std::integral_constant<int, ACT_SILU>{}, std::integral_constant<int, 1>{});
         else by_full(std::integral_constant<int, ACT_SILU>{}, std::integral_constant<int, 0>{});
         return;
     }
-    if (a.act == ACT_RELU) by_mode(std::integral_constant<int, ACT_RELU>{});
-    else if (a.act == ACT_LEAKY) by_mode(std::integral_constant<int, ACT_LEAKY>{});
-    else if (a.act == ACT_SILU) by_mode(std::integral_constant<int, ACT_SILU>{});
-    else by_mode(std::integral_constant<int, ACT_NONE>{});
+    epi_dispatch(a.act, a.drop.mode, by_full);
 #endif
 }
 

@@ -28,6 +28,7 @@
 // wave tiles, 1 workgroup/CU 1105 -> this form 1200 (dense upsample, corrections in-kernel) / 1310 (plain 3x3) -> corrections
 // moved to the ring kernel.
 #include "conv.h"
+#include "conv_epilogue.h"
 #include "gn_fused.h"
 
 #include <algorithm>
@@ -459,8 +460,8 @@ __global__ __launch_bounds__(256, 2) void conv_up_halo_kernel(ConvArgs a, int ti
 #undef ISSUE_B
 
     // ---- epilogue straight from the accumulators.  Lane (l31, hi) of tile (nt, mt) holds pixel l31 of pixel tile mt and
-    // channels half*32 + 8*g + 4*hi + {0..3} (g = register group r >> 2).  Groups 2*g2 and 2*g2+1 are packed to bf16 and
-    // exchanged between lanes l and l+32 (v_permlane32_swap), after which every lane owns 8 consecutive channels = 16 B.
+    // channels half*32 + 8*g + 4*hi + {0..3} (g = register group r >> 2): the layout of the shared step (conv_epilogue.h), which
+    // leaves every lane with 8 consecutive channels = 16 B.
     const RngKey key = drop_row_key(a.drop, n_img);
     const uint32_t row0 = (uint32_t)n_img * (uint32_t)(a.ho * a.wo * a.cout);  // dropout streams are per batch row
     // channel block of this wave: the 64 channels of column block tn (upsample forms: one phase per wave), or (plain form)
@@ -562,12 +563,7 @@ __global__ __launch_bounds__(256, 2) void conv_up_halo_kernel(ConvArgs a, int ti
 #pragma unroll
                 for (int g2 = 0; g2 < 2; ++g2) {
                     const int cg0 = nt * 32 + 16 * g2 + 4 * hi;
-                    const float4 a0 = *(const float4*)(cfA + cg0), a1 = *(const float4*)(cfA + cg0 + 8);
-                    const float4 c0 = *(const float4*)(cfC + cg0), c1 = *(const float4*)(cfC + cg0 + 8);
-                    ca[g2][0] = a0.x; ca[g2][1] = a0.y; ca[g2][2] = a0.z; ca[g2][3] = a0.w;
-                    ca[g2][4] = a1.x; ca[g2][5] = a1.y; ca[g2][6] = a1.z; ca[g2][7] = a1.w;
-                    cc[g2][0] = c0.x; cc[g2][1] = c0.y; cc[g2][2] = c0.z; cc[g2][3] = c0.w;
-                    cc[g2][4] = c1.x; cc[g2][5] = c1.y; cc[g2][6] = c1.z; cc[g2][7] = c1.w;
+                    epi_coef(cfA + cg0, cfC + cg0, 1.0f, ca[g2], cc[g2]);
                 }
 #pragma unroll
                 for (int mt = 0; mt < 4; ++mt) {
@@ -579,22 +575,9 @@ __global__ __launch_bounds__(256, 2) void conv_up_halo_kernel(ConvArgs a, int ti
                         const int cg0 = nt * 32 + 16 * g2;
                         const uint32_t e0 = o0 + mt * mt_stride + cg0 + 4 * hi;
                         float v[8];
-#pragma unroll
-                        for (int t = 0; t < 8; ++t) v[t] = fmaf(acc[nt][mt][8 * g2 + t], ca[g2][t], cc[g2][t]);
-                        act_drop_fixed<4, ACT_SILU, MODE, true>(v, e0, row0, a.drop, key);
-                        act_drop_fixed<4, ACT_SILU, MODE, true>(v + 4, e0 + 8, row0, a.drop, key);
-                        if (has_res) {
-                            const uint2 r0 = rq[s & 1][2 * g2], r1 = rq[s & 1][2 * g2 + 1];
-                            const uint32_t rw[4] = {r0.x, r0.y, r1.x, r1.y};
-#pragma unroll
-                            for (int t = 0; t < 8; ++t) v[t] += (t & 1) ? el16_hi(rw[t >> 1]) : el16_lo(rw[t >> 1]);
-                        }
-                        uint32_t p0 = pack_el16x2(v[0], v[1]), p1 = pack_el16x2(v[2], v[3]);
-                        uint32_t q0 = pack_el16x2(v[4], v[5]), q1 = pack_el16x2(v[6], v[7]);
-                        const auto s0 = __builtin_amdgcn_permlane32_swap(p0, q0, false, false);
-                        const auto s1 = __builtin_amdgcn_permlane32_swap(p1, q1, false, false);
-                        uint4 o;
-                        o.x = s0[0]; o.y = s1[0]; o.z = s0[1]; o.w = s1[1];
+                        epi_values<ACT_SILU, MODE>(acc[nt][mt], 8 * g2, ca[g2], cc[g2], e0, row0, a.drop, key, v);
+                        if (has_res) epi_add_residual(v, rq[s & 1][2 * g2], rq[s & 1][2 * g2 + 1]);
+                        const uint4 o = epi_pack_swap(v);
                         if (st_ok) *(uint4*)(a.out_el16 + (size_t)(o0 + mt * mt_stride + cg0 + 8 * hi)) = o;
                     }
                 }
@@ -619,12 +602,7 @@ __global__ __launch_bounds__(256, 2) void conv_up_halo_kernel(ConvArgs a, int ti
 #pragma unroll
                 for (int g2 = 0; g2 < 2; ++g2) {
                     const int cg0 = nt * 32 + 16 * g2;
-                    const float4 ca0 = *(const float4*)(a.coef_a + ci_base + cg0), ca1 = *(const float4*)(a.coef_a + ci_base + cg0 + 8);
-                    const float4 cc0 = *(const float4*)(a.coef_c + ci_base + cg0), cc1 = *(const float4*)(a.coef_c + ci_base + cg0 + 8);
-                    ca[nt][g2][0] = ca0.x * ps; ca[nt][g2][1] = ca0.y * ps; ca[nt][g2][2] = ca0.z * ps; ca[nt][g2][3] = ca0.w * ps;
-                    ca[nt][g2][4] = ca1.x * ps; ca[nt][g2][5] = ca1.y * ps; ca[nt][g2][6] = ca1.z * ps; ca[nt][g2][7] = ca1.w * ps;
-                    cc[nt][g2][0] = cc0.x * ps; cc[nt][g2][1] = cc0.y * ps; cc[nt][g2][2] = cc0.z * ps; cc[nt][g2][3] = cc0.w * ps;
-                    cc[nt][g2][4] = cc1.x * ps; cc[nt][g2][5] = cc1.y * ps; cc[nt][g2][6] = cc1.z * ps; cc[nt][g2][7] = cc1.w * ps;
+                    epi_coef(a.coef_a + ci_base + cg0, a.coef_c + ci_base + cg0, ps, ca[nt][g2], cc[nt][g2]);
                 }
             const uint32_t tile_base = o0 - (uint32_t)(px_r * a.wo + px_x) * (uint32_t)a.cout;  // pixel (row 0, column 0) of pixel tile 0
             const int rpx = lane >> 3, rch = lane & 7;  // read-back role: (pixel 8 k + rpx, 16-byte chunk)
@@ -636,17 +614,7 @@ __global__ __launch_bounds__(256, 2) void conv_up_halo_kernel(ConvArgs a, int ti
                     for (int g2 = 0; g2 < 2; ++g2) {
                         const int cg0 = nt * 32 + 16 * g2;
                         const uint32_t e0 = o0 + mt * mt_stride + cg0 + 4 * hi;
-                        float v[8];
-#pragma unroll
-                        for (int t = 0; t < 8; ++t) v[t] = fmaf(acc[nt][mt][8 * g2 + t], ca[nt][g2][t], cc[nt][g2][t]);
-                        act_drop_fixed<4, ACT, MODE, true>(v, e0, row0, a.drop, key);
-                        act_drop_fixed<4, ACT, MODE, true>(v + 4, e0 + 8, row0, a.drop, key);
-                        uint32_t p0 = pack_el16x2(v[0], v[1]), p1 = pack_el16x2(v[2], v[3]);
-                        uint32_t q0 = pack_el16x2(v[4], v[5]), q1 = pack_el16x2(v[6], v[7]);
-                        const auto s0 = __builtin_amdgcn_permlane32_swap(p0, q0, false, false);
-                        const auto s1 = __builtin_amdgcn_permlane32_swap(p1, q1, false, false);
-                        uint4 o;
-                        o.x = s0[0]; o.y = s1[0]; o.z = s0[1]; o.w = s1[1];
+                        const uint4 o = epi_step<ACT, MODE>(acc[nt][mt], 8 * g2, ca[nt][g2], cc[nt][g2], e0, row0, a.drop, key);
                         *(uint4*)(ost + l31 * H::OROW + (cg0 + 8 * hi) * 2) = o;
                     }
 #pragma unroll
@@ -732,18 +700,10 @@ __global__ __launch_bounds__(256, 2) void conv_up_halo_kernel(ConvArgs a, int ti
 #pragma unroll
             for (int g2 = 0; g2 < 2; ++g2) {
                 const int cg0 = nt * 32 + 16 * g2;  // + 4*hi: own channels of group 2*g2; + 8: group 2*g2+1
-                float4 ca0, ca1, cc0, cc1;
-                if constexpr (SP == 5) {
-                    ca0 = k4a[4 * nt + 2 * g2]; ca1 = k4a[4 * nt + 2 * g2 + 1];
-                    cc0 = k4c[4 * nt + 2 * g2]; cc1 = k4c[4 * nt + 2 * g2 + 1];
-                } else {
-                    ca0 = *(const float4*)(a.coef_a + ci_base + cg0); ca1 = *(const float4*)(a.coef_a + ci_base + cg0 + 8);
-                    cc0 = *(const float4*)(a.coef_c + ci_base + cg0); cc1 = *(const float4*)(a.coef_c + ci_base + cg0 + 8);
-                }
-                ca[g2][0] = ca0.x * ps; ca[g2][1] = ca0.y * ps; ca[g2][2] = ca0.z * ps; ca[g2][3] = ca0.w * ps;
-                ca[g2][4] = ca1.x * ps; ca[g2][5] = ca1.y * ps; ca[g2][6] = ca1.z * ps; ca[g2][7] = ca1.w * ps;
-                cc[g2][0] = cc0.x * ps; cc[g2][1] = cc0.y * ps; cc[g2][2] = cc0.z * ps; cc[g2][3] = cc0.w * ps;
-                cc[g2][4] = cc1.x * ps; cc[g2][5] = cc1.y * ps; cc[g2][6] = cc1.z * ps; cc[g2][7] = cc1.w * ps;
+                if constexpr (SP == 5)
+                    epi_coef(k4a[4 * nt + 2 * g2], k4a[4 * nt + 2 * g2 + 1], k4c[4 * nt + 2 * g2], k4c[4 * nt + 2 * g2 + 1], ps, ca[g2], cc[g2]);
+                else
+                    epi_coef(a.coef_a + ci_base + cg0, a.coef_c + ci_base + cg0, ps, ca[g2], cc[g2]);
             }
 #pragma unroll
             for (int mt = 0; mt < 4; ++mt) {
@@ -752,19 +712,7 @@ __global__ __launch_bounds__(256, 2) void conv_up_halo_kernel(ConvArgs a, int ti
                     const int cg0 = nt * 32 + 16 * g2;
                     const uint32_t obase = o0 + mt * mt_stride + cg0;
                     const uint32_t e0 = obase + 4 * hi;
-                    float v[8];
-#pragma unroll
-                    for (int t = 0; t < 8; ++t) v[t] = fmaf(acc[nt][mt][8 * g2 + t], ca[g2][t], cc[g2][t]);
-                    act_drop_fixed<4, ACT, MODE, true>(v, e0, row0, a.drop, key);
-                    act_drop_fixed<4, ACT, MODE, true>(v + 4, e0 + 8, row0, a.drop, key);
-                    uint32_t p0 = pack_el16x2(v[0], v[1]), p1 = pack_el16x2(v[2], v[3]);
-                    uint32_t q0 = pack_el16x2(v[4], v[5]), q1 = pack_el16x2(v[6], v[7]);
-                    const auto s0 = __builtin_amdgcn_permlane32_swap(p0, q0, false, false);
-                    const auto s1 = __builtin_amdgcn_permlane32_swap(p1, q1, false, false);
-                    // lanes 0-31: {own group 2*g2, partner's group 2*g2} = channels cg0 + 0..7;
-                    // lanes 32-63: {partner's group 2*g2+1, own group 2*g2+1} = channels cg0 + 8..15
-                    uint4 o;
-                    o.x = s0[0]; o.y = s1[0]; o.z = s0[1]; o.w = s1[1];
+                    const uint4 o = epi_step<ACT, MODE>(acc[nt][mt], 8 * g2, ca[g2], cc[g2], e0, row0, a.drop, key);
                     const uint32_t sbase = store0 + mt * smt_stride + cg0;
                     if ((SP != 1 && SP != 5) || (lane_valid && (SP != 5 || orow0 + 2 * mt < a.ho)))
                         *(uint4*)(a.out_el16 + (size_t)(sbase + 8 * hi)) = o;
@@ -772,19 +720,11 @@ __global__ __launch_bounds__(256, 2) void conv_up_halo_kernel(ConvArgs a, int ti
             }
         }
     };
-    auto by_mode = [&](auto act_c) {
-        if (a.drop.mode == 0) epilogue(act_c, std::integral_constant<int, 0>{});
-        else if (a.drop.mode == 1) epilogue(act_c, std::integral_constant<int, 1>{});
-        else epilogue(act_c, std::integral_constant<int, 2>{});
-    };
     if constexpr (PLAIN_EPI) {
         epilogue(std::integral_constant<int, ACT_NONE>{}, std::integral_constant<int, 0>{});
         return;
     }
-    if (a.act == ACT_RELU) by_mode(std::integral_constant<int, ACT_RELU>{});
-    else if (a.act == ACT_LEAKY) by_mode(std::integral_constant<int, ACT_LEAKY>{});
-    else if (a.act == ACT_SILU) by_mode(std::integral_constant<int, ACT_SILU>{});
-    else by_mode(std::integral_constant<int, ACT_NONE>{});
+    epi_dispatch(a.act, a.drop.mode, epilogue);
 #endif
 }
 

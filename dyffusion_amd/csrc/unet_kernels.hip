@@ -1,5 +1,6 @@
 // HBM/LDS-bound kernels of the ResNet-UNet backbone (src/models/unet.py + modules/attention.py) for gfx950.
 #include "unet_kernels.h"
+#include "conv_epilogue.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -189,8 +190,8 @@ __global__ __launch_bounds__(256) void stem_mfma_kernel(StemConvArgs a, int gps)
                 for (int i = 0; i < TS * 8; ++i) v[i] = nv[i];
             }
         }
-        // lane (pixel, hi) holds channels rb*32 + 8 (r >> 2) + 4 hi + (r & 3); groups 2 g2 / 2 g2 + 1 are exchanged between
-        // lanes p and p + 32 so that every lane stores 8 consecutive channels (as in the conv epilogues)
+        // lane (pixel, hi) holds channels rb*32 + 8 (r >> 2) + 4 hi + (r & 3): the conv epilogues' layout and their 16-byte rows
+        // (conv_epilogue.h)
         el16_t* op = a.out + ((size_t)n * plane + rem) * a.dim + hi * 8;
 #pragma unroll
         for (int rb = 0; rb < 2; ++rb)
@@ -198,14 +199,9 @@ __global__ __launch_bounds__(256) void stem_mfma_kernel(StemConvArgs a, int gps)
             for (int g2 = 0; g2 < 2; ++g2) {
                 const int cb = rb * 32 + g2 * 16 + 4 * hi;
                 const float4 ba = *(const float4*)(a.bias + cb), bb = *(const float4*)(a.bias + cb + 8);
-                const uint32_t p0 = pack_el16x2(acc[rb][g2 * 8 + 0] + ba.x, acc[rb][g2 * 8 + 1] + ba.y);
-                const uint32_t p1 = pack_el16x2(acc[rb][g2 * 8 + 2] + ba.z, acc[rb][g2 * 8 + 3] + ba.w);
-                const uint32_t q0 = pack_el16x2(acc[rb][g2 * 8 + 4] + bb.x, acc[rb][g2 * 8 + 5] + bb.y);
-                const uint32_t q1 = pack_el16x2(acc[rb][g2 * 8 + 6] + bb.z, acc[rb][g2 * 8 + 7] + bb.w);
-                const auto s0 = __builtin_amdgcn_permlane32_swap(p0, q0, false, false);
-                const auto s1 = __builtin_amdgcn_permlane32_swap(p1, q1, false, false);
-                uint4 o;
-                o.x = s0[0]; o.y = s1[0]; o.z = s0[1]; o.w = s1[1];
+                const float y[8] = {acc[rb][g2 * 8 + 0] + ba.x, acc[rb][g2 * 8 + 1] + ba.y, acc[rb][g2 * 8 + 2] + ba.z, acc[rb][g2 * 8 + 3] + ba.w,
+                                    acc[rb][g2 * 8 + 4] + bb.x, acc[rb][g2 * 8 + 5] + bb.y, acc[rb][g2 * 8 + 6] + bb.z, acc[rb][g2 * 8 + 7] + bb.w};
+                const uint4 o = epi_pack_swap(y);
                 if (pvalid) *(uint4*)(op + rb * 32 + g2 * 16) = o;
             }
     }
@@ -1137,17 +1133,14 @@ __global__ __launch_bounds__(256) void linattn_out_mfma_kernel(LinAttnArgs a, co
             acc = DYF_MFMA_32x32x16(al[s], la_frag(qh), acc, 0, 0, 0);
             acc = DYF_MFMA_32x32x16(ah[s], la_frag(ql), acc, 0, 0, 0);
         }
-        // lane (p, hi) holds rows e = 8 (r >> 2) + 4 hi + (r & 3); register groups 2 g2 / 2 g2 + 1 are exchanged between lanes
-        // p and p + 32 so that every lane stores 8 consecutive channels
+        // lane (p, hi) holds rows e = 8 (r >> 2) + 4 hi + (r & 3): the conv epilogues' layout and their 16-byte rows (conv_epilogue.h)
         el16_t* op = a.out + ((size_t)n * a.hw + p) * hd + h * 32 + hi * 8;
 #pragma unroll
         for (int g2 = 0; g2 < 2; ++g2) {
-            const uint32_t p0 = pack_el16x2(acc[g2 * 8 + 0] * qn, acc[g2 * 8 + 1] * qn), p1 = pack_el16x2(acc[g2 * 8 + 2] * qn, acc[g2 * 8 + 3] * qn);
-            const uint32_t q0 = pack_el16x2(acc[g2 * 8 + 4] * qn, acc[g2 * 8 + 5] * qn), q1 = pack_el16x2(acc[g2 * 8 + 6] * qn, acc[g2 * 8 + 7] * qn);
-            const auto s0 = __builtin_amdgcn_permlane32_swap(p0, q0, false, false);
-            const auto s1 = __builtin_amdgcn_permlane32_swap(p1, q1, false, false);
-            uint4 o;
-            o.x = s0[0]; o.y = s1[0]; o.z = s0[1]; o.w = s1[1];
+            float y[8];
+#pragma unroll
+            for (int t = 0; t < 8; ++t) y[t] = acc[g2 * 8 + t] * qn;
+            const uint4 o = epi_pack_swap(y);
             if (valid) *(uint4*)(op + g2 * 16) = o;
         }
     }

@@ -1,7 +1,8 @@
 """-m gpu: every conv kernel FORM of the plain ladder (csrc/conv_dispatch.hip choose_plain) against a float64 reference, with the
 kernel form pinned by the form log, over the whole conv argument block (csrc/conv.h ConvArgs) through dyf_op_conv2d_ex.
 
-Each form has its own operand gather and its own copy of the epilogue, so every feature of the argument block -- second source,
+Each form has its own operand gather and, around the epilogue step they share (csrc/conv_epilogue.h), its own output addressing, staging
+and store path, so every feature of the argument block -- second source,
 residual, fp32 output, coef_div, SiLU / GELU, injected and generated dropout masks, n_sel -- is driven on every form, in both builds
 (bf16, fp16).  Where a form's admission rule turns a feature away, the test names the form the ladder falls to and checks that one.
 
