@@ -1843,6 +1843,15 @@ static dyf_status traj_check_args(dyf_engine* e, int32_t n_segments, const float
     return DYF_OK;
 }
 
+// The (n_outer, n_groups, n_inner) view of a segment's points that the grouped entries share.
+static dyf_status traj_check_groups(dyf_engine* e, int64_t n_points, int64_t n_outer, int32_t n_groups, int64_t n_inner) {
+    if (n_outer < 1 || n_groups < 1 || n_inner < 1) return fail(e, DYF_ERR_INVALID_ARGUMENT, "n_outer, n_groups and n_inner must be positive");
+    // n_outer * n_groups * n_inner == n_points, without forming a product that could overflow
+    if (n_points % n_outer != 0 || (n_points / n_outer) % n_groups != 0 || n_points / n_outer / n_groups != n_inner)
+        return fail(e, DYF_ERR_INVALID_ARGUMENT, "n_outer * n_groups * n_inner must equal n_points");
+    return DYF_OK;
+}
+
 // Grow the pointer table and `*partials` (to `need` doubles) where they are too small, order this call behind the previous one and
 // upload the segment pointers through the pinned staging; the caller launches on `st` and ends with traj_finish.
 static dyf_status traj_upload(dyf_engine* e, int32_t n_segments, const float* const* preds_dev, const float* const* targets_dev,
@@ -1931,10 +1940,8 @@ dyf_status dyf_ensemble_scores(dyf_engine* e, int32_t n_segments, const float* c
     dyf_status cs = traj_check_args(e, n_segments, preds_dev, targets_dev, n_members, 15360, DYF_ERR_INVALID_ARGUMENT, n_points,
                                     member_stride, out_dev);
     if (cs != DYF_OK) return cs;
-    if (n_outer < 1 || n_groups < 1 || n_inner < 1) return fail(e, DYF_ERR_INVALID_ARGUMENT, "n_outer, n_groups and n_inner must be positive");
-    // n_outer * n_groups * n_inner == n_points, without forming a product that could overflow
-    if (n_points % n_outer != 0 || (n_points / n_outer) % n_groups != 0 || n_points / n_outer / n_groups != n_inner)
-        return fail(e, DYF_ERR_INVALID_ARGUMENT, "n_outer * n_groups * n_inner must equal n_points");
+    cs = traj_check_groups(e, n_points, n_outer, n_groups, n_inner);
+    if (cs != DYF_OK) return cs;
     const long long blocks = ensemble_scores_blocks(n_members, n_outer, n_groups, n_inner);
     if (blocks < 1)
         return fail(e, DYF_ERR_UNSUPPORTED, "more than 2^24 - 1 = " + std::to_string(ENSEMBLE_SCORES_MAX_BLOCKS) +
@@ -1998,9 +2005,8 @@ dyf_status dyf_rank_histogram(dyf_engine* e, int32_t n_segments, const float* co
     dyf_status cs = traj_check_args(e, n_segments, preds_dev, targets_dev, n_members, RANK_HISTOGRAM_MAX_MEMBERS, DYF_ERR_UNSUPPORTED,
                                     n_points, member_stride, out_dev);
     if (cs != DYF_OK) return cs;
-    if (n_outer < 1 || n_groups < 1 || n_inner < 1) return fail(e, DYF_ERR_INVALID_ARGUMENT, "n_outer, n_groups and n_inner must be positive");
-    if (n_points % n_outer != 0 || (n_points / n_outer) % n_groups != 0 || n_points / n_outer / n_groups != n_inner)
-        return fail(e, DYF_ERR_INVALID_ARGUMENT, "n_outer * n_groups * n_inner must equal n_points");
+    cs = traj_check_groups(e, n_points, n_outer, n_groups, n_inner);
+    if (cs != DYF_OK) return cs;
     const int chunks = rank_histogram_chunks(n_members, n_outer, n_groups, n_inner);
     if (chunks < 1)
         return fail(e, DYF_ERR_UNSUPPORTED, "more than 2^24 - 1 = " + std::to_string(ENSEMBLE_SCORES_MAX_BLOCKS) +

@@ -12,7 +12,7 @@
 //   up to 64 members   256 points per workgroup, one thread per point.  The members are staged in fours, xs[quad][thread] as float4
 //                      (ensemble_size_metrics_kernel's layout: ds_read_b128 on consecutive 16-byte slots, conflict-free); the slots
 //                      past n_members hold NaN, which no comparison below counts.  A thread reads only what it wrote: no barrier.
-//   beyond             P = ensemble_products_tile() points per workgroup, T = 256 / P threads per point, xs[member][P]; thread share k
+//   beyond             P = ensemble_tile_points() points per workgroup, T = 256 / P threads per point, xs[member][P]; thread share k
 //                      takes the members k, k + T, ...; partial sums / extremes / counts of the T shares are joined by every share
 //                      in share order (ensemble_metrics_tiled_kernel's join), so the result does not depend on which thread asks.
 // mean = sum * (1 / N) with the sum in member order, var = sum (x - mean)^2 * (1 / N), std = sqrtf(var): the fp32 expressions of
@@ -238,23 +238,14 @@ __global__ __launch_bounds__(256) void ensemble_products_tiled_kernel(const floa
     }
 }
 
-// points per workgroup: 256 up to 64 members, beyond that the largest power of two <= 128 with n_members * P floats <= 60 KB (the
-// rule of the metrics kernels; 0 = none, n_members beyond 15 360)
-static int ensemble_products_tile(int n_members) {
-    if (n_members <= 64) return 256;
-    int P = 128;
-    while (P > 1 && (size_t)n_members * P * sizeof(float) > 60 * 1024) P >>= 1;
-    return (size_t)n_members * P * sizeof(float) > 60 * 1024 ? 0 : P;
-}
-
 long long ensemble_products_blocks(int n_members, long long n_points) {
-    const int P = n_members >= 1 ? ensemble_products_tile(n_members) : 0;
+    const int P = ensemble_tile_points(n_members);
     return P && n_points >= 1 ? (n_points + P - 1) / P : 0;
 }
 
 hipError_t launch_ensemble_products(const float* const* preds_tab, int n_segments, int n_members, long long n_points,
                                     long long member_stride, const EnsembleProductsParams& pr, float* out, hipStream_t s) {
-    const int P = n_members >= 1 ? ensemble_products_tile(n_members) : 0;
+    const int P = ensemble_tile_points(n_members);
     const long long blocks = ensemble_products_blocks(n_members, n_points);
     const int n_planes = pr.mean + pr.std + pr.min + pr.max + pr.n_quantiles + pr.n_thresholds;
     // 256 * blocks threads along x stay below 2^32
@@ -375,10 +366,7 @@ __global__ __launch_bounds__(256) void rank_histogram_finish_kernel(const double
 int rank_histogram_chunks(int n_members, long long n_outer, int n_groups, long long n_inner) {
     if (n_members < 1 || n_members > RANK_HISTOGRAM_MAX_MEMBERS || n_outer < 1 || n_groups < 1 || n_inner < 1) return 0;
     const long long tiles = (n_inner + 255) / 256;
-    // the workgroup limit of dyf_ensemble_scores on the same geometry: n_outer * n_groups * tiles <= 2^24 - 1
-    if (tiles > ENSEMBLE_SCORES_MAX_BLOCKS || n_outer > ENSEMBLE_SCORES_MAX_BLOCKS / tiles ||
-        (long long)n_groups > ENSEMBLE_SCORES_MAX_BLOCKS / (tiles * n_outer))
-        return -1;
+    if (!ensemble_geometry_fits(n_outer, n_groups, tiles)) return -1;  // the workgroup limit of dyf_ensemble_scores on this geometry
     return (int)std::min<long long>(tiles * n_outer, RANK_HISTOGRAM_MAX_CHUNKS);
 }
 

@@ -191,13 +191,23 @@ hipError_t launch_nhwc_to_nchw_f32(const el16_t* src, int n, int h, int w, int w
 hipError_t launch_rng_clone(uint32_t* dst, const uint32_t* src, uint32_t row_add, bool counters_only, hipStream_t s);
 hipError_t launch_rng_begin_forward(uint32_t* rng_state, uint32_t* row_keys, int rows, int rows_per_fwd, hipStream_t s);
 hipError_t launch_fill_f32(float* p, float v, long long count, hipStream_t s);
-// on-device ensemble metrics (evaluation.py:10-118): sums[3] (fp64, device) = {sum (mean-y)^2, sum var, sum crps}; n_members <= 64 (one KB of LDS per member)
 // sum of the criterion terms |p-t| (kind 0), (p-t)^2 (1), smooth-L1 (2) over `count` fp32 elements -> *sum (device double)
 hipError_t launch_criterion_sum(const float* p, const float* t, long long count, int kind, double* sum, hipStream_t s);
 // the same sum without atomics (deterministic training mode): one partial per workgroup to partials[CRITERION_MAX_BLOCKS], added in
 // workgroup order by a second launch
 constexpr int CRITERION_MAX_BLOCKS = 2048;
 hipError_t launch_criterion_sum_det(const float* p, const float* t, long long count, int kind, double* partials, double* sum, hipStream_t s);
+// points per workgroup of the ensemble kernels that stage a point's members in LDS: 256 up to 64 members (one KB of LDS per member),
+// beyond that the largest power of two <= 128 with n_members * P floats <= 60 KB; 0 = none (no member, or more than 15 360)
+inline int ensemble_tile_points(int n_members) {
+    if (n_members < 1) return 0;
+    if (n_members <= 64) return 256;
+    int P = 128;
+    while (P > 1 && (size_t)n_members * P * sizeof(float) > 60 * 1024) P >>= 1;
+    return (size_t)n_members * P * sizeof(float) > 60 * 1024 ? 0 : P;
+}
+// on-device ensemble metrics (evaluation.py:10-118): sums[3] (fp64, device) = {sum (mean-y)^2, sum var, sum crps} over n_points
+// points, member n at preds + n * n_points; up to 15 360 members (ensemble_tile_points)
 hipError_t launch_ensemble_metrics(const float* preds, const float* targets, int n_members, long long n_points, double* sums,
                                    hipStream_t s);
 // the same per-point quantities per segment (dyf_trajectory_metrics), without atomics: launch 1 writes one {se, var, crps} partial per
@@ -224,6 +234,11 @@ hipError_t launch_ensemble_size_metrics(const float* const* preds_tab, const flo
 // member_stride as launch_trajectory_metrics.
 constexpr int ENSEMBLE_SCORES_PARTIAL = 9;
 constexpr long long ENSEMBLE_SCORES_MAX_BLOCKS = 0xffffffLL;  // workgroups per segment: 256 threads each, below 2^32 threads along x
+// n_outer * n_groups * tiles <= ENSEMBLE_SCORES_MAX_BLOCKS (all three positive), without forming a product that could overflow
+inline bool ensemble_geometry_fits(long long n_outer, int n_groups, long long tiles) {
+    return tiles <= ENSEMBLE_SCORES_MAX_BLOCKS && n_outer <= ENSEMBLE_SCORES_MAX_BLOCKS / tiles &&
+           (long long)n_groups <= ENSEMBLE_SCORES_MAX_BLOCKS / (tiles * n_outer);
+}
 // workgroups per segment = n_outer * n_groups * ceil(n_inner / tile); 0 = n_members beyond 15 360, -1 = beyond ENSEMBLE_SCORES_MAX_BLOCKS
 long long ensemble_scores_blocks(int n_members, long long n_outer, int n_groups, long long n_inner);
 hipError_t launch_ensemble_scores(const float* const* preds_tab, const float* const* targets_tab, int n_segments, int n_members,

@@ -1740,75 +1740,70 @@ hipError_t launch_fill_f32(float* p, float v, long long count, hipStream_t s) {
 }
 
 // ------------------------------------------------------------------------------------------------ ensemble metrics
-// On-device form of src/utilities/evaluation.py:10-118 (evaluate_ensemble_prediction): for every grid point p of the
-// (B, C, H, W) target the N ensemble members are reduced to
-//   (mean_n x_n - y)^2                     -> "mse" of the ensemble mean            (evaluation.py:43-45)
-//   var_n x_n  (population variance)       -> spread^2 of the spread-skill ratio    (evaluation.py:107-116)
-//   mean_n |x_n - y| - 1/(2 N^2) sum_{n,m} |x_n - x_m|  -> CRPS of the empirical ensemble CDF (xskillscore/properscoring
-//                                            crps_ensemble, evaluation.py:83-95)
-// and summed over points in fp64 (one atomic per wave and quantity).  HBM-bound: every prediction is read exactly once
-// (members staged in LDS, [N][256] floats); the O(N^2) pair term runs out of LDS.
-__global__ __launch_bounds__(256) void ensemble_metrics_kernel(const float* preds, const float* targets, int n_members,
-                                                               long long n_points, double* sums) {
-    extern __shared__ float xs[];  // [n_members][256]
+// On-device form of src/utilities/evaluation.py:10-118 (evaluate_ensemble_prediction).  Three entries reduce the N members x_n of a
+// grid point with target y to the same four fp32 values, through the two helpers below:
+//   mean = (sum_n x_n) / N
+//   se   = (mean - y)^2                                 -> "mse" of the ensemble mean           (evaluation.py:43-45)
+//   var  = (sum_n (x_n - mean)^2) / N  (population)     -> spread^2 of the spread-skill ratio   (evaluation.py:107-116)
+//   crps = mean_n |x_n - y| - 1/(2 N^2) sum_{n,m} |x_n - x_m|  -> CRPS of the empirical ensemble CDF (xskillscore/properscoring
+//          crps_ensemble, evaluation.py:83-95); `pair` below is the sum over n < m, half the sum over ordered pairs
+// and differ in what they do with them: dyf_ensemble_metrics (this section) sums over all points with fp64 atomics,
+// dyf_trajectory_metrics per segment and dyf_ensemble_scores per (segment, group) in a fixed order.  HBM-bound: every prediction is
+// read exactly once (members staged in LDS); the O(N^2) pair term runs out of LDS.
+//   Contraction is written out, not left to the compiler, so that the three entries hold the same bits for the same point whatever
+// surrounds the helper (tests/test_gpu_ensemble_scores.py::test_pooled compares two of them bitwise): with 1 / N = inv,
+//   both forms    m2 = fmaf(x - mean, x - mean, m2);  mean = sum * inv;  se = (mean - y) * (mean - y);  var = m2 * inv
+//   one thread    crps = fmaf(sabs, inv, -(pair * inv * inv))
+//   tiled         crps = sabs * inv - pair * inv * inv   (two rounded products, one subtraction)
+// and nothing else is fused.
+struct ensemble_point {
+    float mean, y, se, var, crps;
+};
+
+// Up to 64 members, one thread per point: `preds` is the point's first member, member n lies n * member_stride behind it.  The
+// members are staged as xs[n * 256 + tid]; a thread reads only what it wrote, so there is no barrier.
+__device__ __forceinline__ ensemble_point ensemble_point_reduce(const float* preds, long long member_stride, float y, int n_members,
+                                                                float* xs /* LDS, [n_members][256] */) {
+#pragma clang fp contract(off)
     const int tid = threadIdx.x;
-    const long long p = (long long)blockIdx.x * 256 + tid;
-    const bool live = p < n_points;
-    float se = 0.0f, var = 0.0f, crps = 0.0f;
-    if (live) {
-        const float y = targets[p];
-        float sum = 0.0f, sabs = 0.0f;
-        for (int n = 0; n < n_members; ++n) {
-            const float x = preds[(size_t)n * n_points + p];
-            xs[n * 256 + tid] = x;
-            sum += x;
-            sabs += fabsf(x - y);
-        }
-        const float inv = 1.0f / (float)n_members;
-        const float mean = sum * inv;
-        float m2 = 0.0f, pair = 0.0f;
-        for (int n = 0; n < n_members; ++n) {
-            const float x = xs[n * 256 + tid];
-            m2 += (x - mean) * (x - mean);
-            for (int m = n + 1; m < n_members; ++m) pair += fabsf(x - xs[m * 256 + tid]);
-        }
-        se = (mean - y) * (mean - y);
-        var = m2 * inv;
-        crps = sabs * inv - pair * inv * inv;  // sum over ordered pairs = 2 * pair; 0.5 * 2 * pair / N^2
+    float sum = 0.0f, sabs = 0.0f;
+    for (int n = 0; n < n_members; ++n) {
+        const float x = preds[(long long)n * member_stride];
+        xs[n * 256 + tid] = x;
+        sum += x;
+        sabs += fabsf(x - y);
     }
-    // wave reduction in fp64, then one atomic per wave
-    double d0 = se, d1 = var, d2 = crps;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        d0 += __shfl_xor(d0, off, 64);
-        d1 += __shfl_xor(d1, off, 64);
-        d2 += __shfl_xor(d2, off, 64);
+    const float inv = 1.0f / (float)n_members;
+    const float mean = sum * inv;
+    float m2 = 0.0f, pair = 0.0f;
+    for (int n = 0; n < n_members; ++n) {
+        const float x = xs[n * 256 + tid];
+        m2 = fmaf(x - mean, x - mean, m2);
+        for (int m = n + 1; m < n_members; ++m) pair += fabsf(x - xs[m * 256 + tid]);
     }
-    if ((tid & 63) == 0) {
-        atomicAdd(sums + 0, d0);
-        atomicAdd(sums + 1, d1);
-        atomicAdd(sums + 2, d2);
-    }
+    return {mean, y, (mean - y) * (mean - y), m2 * inv, fmaf(sabs, inv, -(pair * inv * inv))};
 }
 
 // More than 64 members (the reference has no cap, evaluation.py:10-80): the [N][256] staging tile no longer fits the 64 KB of LDS,
-// so a workgroup takes P < 256 points (N * P floats staged) and T = 256 / P threads share a point: thread (point pi = tid % P,
-// share sh = tid / P) owns the members n = sh, sh + T, ...; the shares' partial sums meet in LDS and are added in share order.
-// The O(N^2) pair term is then spread over all 256 threads.  Same definitions as ensemble_metrics_kernel.
-__global__ __launch_bounds__(256) void ensemble_metrics_tiled_kernel(const float* preds, const float* targets, int n_members,
-                                                                     long long n_points, double* sums, int P) {
-    extern __shared__ float xs[];        // [n_members][P] members, then [3][256] partials
-    float* red = xs + (size_t)n_members * P;
+// so a workgroup takes P = ensemble_tile_points() < 256 points (N * P floats staged) and T = 256 / P threads share a point: thread
+// (point pi = tid % P, share sh = tid / P) owns the members n = sh, sh + T, ...; the shares' partial sums meet in LDS and are added
+// in share order.  The O(N^2) pair term is then spread over all 256 threads.  `preds` / `targets` are the tile's first point, of which
+// the first n_live (1..P) exist.  EVERY thread of the workgroup calls this (it holds barriers); `holds` is set for share 0 of a live
+// point, whose se / var / crps are the point's -- every other thread gets zeros there (mean and y are the point's in all its shares).
+__device__ __forceinline__ ensemble_point ensemble_point_reduce_tiled(const float* preds, long long member_stride, int n_live,
+                                                                      const float* targets, int n_members, int P,
+                                                                      float* xs /* LDS, [n_members][P] */,
+                                                                      float* red /* LDS, [2][256] */, bool& holds) {
+#pragma clang fp contract(off)
     const int tid = threadIdx.x, T = 256 / P;
     const int pi = tid % P, sh = tid / P;
-    const long long p0 = (long long)blockIdx.x * P, p = p0 + pi;
-    const bool live = p < n_points;
+    const bool live = pi < n_live;
     for (int i = tid; i < n_members * P; i += 256) {  // staging: consecutive threads -> consecutive points of one member
         const int n = i / P, q = i - n * P;
-        xs[i] = p0 + q < n_points ? preds[(size_t)n * n_points + p0 + q] : 0.0f;
+        xs[i] = q < n_live ? preds[(long long)n * member_stride + q] : 0.0f;
     }
     __syncthreads();
-    const float y = live ? targets[p] : 0.0f;
+    const float y = live ? targets[pi] : 0.0f;
     float sum = 0.0f, sabs = 0.0f;
     for (int n = sh; n < n_members; n += T) {
         const float x = xs[n * P + pi];
@@ -1830,7 +1825,7 @@ __global__ __launch_bounds__(256) void ensemble_metrics_tiled_kernel(const float
     double pair = 0.0;  // up to N^2 / 2 terms per point: rows in fp32, the sum of rows in fp64
     for (int n = sh; n < n_members; n += T) {
         const float x = xs[n * P + pi];
-        m2 += (x - mean) * (x - mean);
+        m2 = fmaf(x - mean, x - mean, m2);
         float row = 0.0f;
         for (int m = n + 1; m < n_members; ++m) row += fabsf(x - xs[m * P + pi]);
         pair += (double)row;
@@ -1838,29 +1833,77 @@ __global__ __launch_bounds__(256) void ensemble_metrics_tiled_kernel(const float
     red[tid] = m2;
     red[256 + tid] = (float)pair;
     __syncthreads();
-    float se = 0.0f, var = 0.0f, crps = 0.0f;
-    if (live && sh == 0) {
+    ensemble_point pt = {mean, y, 0.0f, 0.0f, 0.0f};
+    holds = live && sh == 0;
+    if (holds) {
         float tm2 = 0.0f, tpair = 0.0f;
         for (int k = 0; k < T; ++k) {
             tm2 += red[k * P + pi];
             tpair += red[256 + k * P + pi];
         }
-        se = (mean - y) * (mean - y);
-        var = tm2 * inv;
-        crps = tabs * inv - tpair * inv * inv;
+        pt.se = (mean - y) * (mean - y);
+        pt.var = tm2 * inv;
+        pt.crps = tabs * inv - tpair * inv * inv;
     }
-    double d0 = se, d1 = var, d2 = crps;
+    return pt;
+}
+
+// The workgroup's sums of K values per thread, in fp64 and a fixed order: a wave butterfly, then the four wave sums meet in LDS
+// (ensemble_wave_sums) and ensemble_block_total adds those of value k in wave order.
+template <int K>
+__device__ __forceinline__ void ensemble_wave_sums(double (&v)[K], double* wsum /* LDS, [4][K] */) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+#pragma unroll
+        for (int k = 0; k < K; ++k) v[k] += __shfl_xor(v[k], off, 64);
+    }
+    const int tid = threadIdx.x;
+    __syncthreads();  // wsum lies over the staged members (and over the sums of the round before): every wave is done reading them
+    if ((tid & 63) == 0) {
+#pragma unroll
+        for (int k = 0; k < K; ++k) wsum[(tid >> 6) * K + k] = v[k];
+    }
+    __syncthreads();
+}
+template <int K>
+__device__ __forceinline__ double ensemble_block_total(const double* wsum, int k) {
+    return ((wsum[k] + wsum[K + k]) + wsum[2 * K + k]) + wsum[3 * K + k];
+}
+
+// dyf_ensemble_metrics: one segment, flat points, member stride n_points; {se, var, crps} summed over all points in fp64, wave
+// butterfly and one atomic per wave and quantity (unordered).
+__device__ __forceinline__ void ensemble_atomic_sum(const ensemble_point& pt, double* sums) {
+    double d0 = pt.se, d1 = pt.var, d2 = pt.crps;
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
         d0 += __shfl_xor(d0, off, 64);
         d1 += __shfl_xor(d1, off, 64);
         d2 += __shfl_xor(d2, off, 64);
     }
-    if ((tid & 63) == 0) {
+    if ((threadIdx.x & 63) == 0) {
         atomicAdd(sums + 0, d0);
         atomicAdd(sums + 1, d1);
         atomicAdd(sums + 2, d2);
     }
+}
+
+__global__ __launch_bounds__(256) void ensemble_metrics_kernel(const float* preds, const float* targets, int n_members,
+                                                               long long n_points, double* sums) {
+    extern __shared__ float xs[];  // [n_members][256]
+    const long long p = (long long)blockIdx.x * 256 + threadIdx.x;
+    ensemble_point pt = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    if (p < n_points) pt = ensemble_point_reduce(preds + p, n_points, targets[p], n_members, xs);
+    ensemble_atomic_sum(pt, sums);
+}
+
+__global__ __launch_bounds__(256) void ensemble_metrics_tiled_kernel(const float* preds, const float* targets, int n_members,
+                                                                     long long n_points, double* sums, int P) {
+    extern __shared__ float xs[];  // [n_members][P] members, then [2][256] partials
+    const long long p0 = (long long)blockIdx.x * P;
+    const int n_live = n_points - p0 < P ? (int)(n_points - p0) : P;
+    bool holds;
+    ensemble_atomic_sum(ensemble_point_reduce_tiled(preds + p0, n_points, n_live, targets + p0, n_members, P, xs,
+                                                    xs + (size_t)n_members * P, holds), sums);
 }
 
 // Reduction of the training criterion (src/utilities/utils.py:201-212, reduction = "mean"): sum over all elements of
@@ -1936,144 +1979,57 @@ hipError_t launch_criterion_sum_det(const float* p, const float* t, long long co
 
 hipError_t launch_ensemble_metrics(const float* preds, const float* targets, int n_members, long long n_points, double* sums,
                                    hipStream_t s) {
-    const size_t lds = (size_t)n_members * 256 * sizeof(float);
     hipError_t e = hipMemsetAsync(sums, 0, 3 * sizeof(double), s);
     if (e != hipSuccess) return e;
-    if (n_members > 64) {  // points per workgroup: the largest power of two with n_members * P floats <= 60 KB
-        int P = 128;
-        while (P > 1 && (size_t)n_members * P * sizeof(float) > 60 * 1024) P >>= 1;
-        if ((size_t)n_members * P * sizeof(float) > 60 * 1024) return hipErrorInvalidValue;  // > 15 360 members
-        const size_t lds2 = ((size_t)n_members * P + 2 * 256) * sizeof(float);
-        hipLaunchKernelGGL(ensemble_metrics_tiled_kernel, dim3((unsigned)((n_points + P - 1) / P)), dim3(256), lds2, s, preds, targets,
-                           n_members, n_points, sums, P);
-        return hipGetLastError();
-    }
-    hipLaunchKernelGGL(ensemble_metrics_kernel, dim3((unsigned)((n_points + 255) / 256)), dim3(256), lds, s, preds, targets,
-                       n_members, n_points, sums);
+    const int P = ensemble_tile_points(n_members);
+    if (P == 0) return hipErrorInvalidValue;  // > 15 360 members
+    const dim3 grid((unsigned)((n_points + P - 1) / P));
+    if (n_members > 64)
+        hipLaunchKernelGGL(ensemble_metrics_tiled_kernel, grid, dim3(256), ((size_t)n_members * P + 2 * 256) * sizeof(float), s, preds,
+                           targets, n_members, n_points, sums, P);
+    else
+        hipLaunchKernelGGL(ensemble_metrics_kernel, grid, dim3(256), (size_t)n_members * 256 * sizeof(float), s, preds, targets,
+                           n_members, n_points, sums);
     return hipGetLastError();
 }
 
 // ------------------------------------------------------------------------------------------------ trajectory metrics
-// The per-point quantities of ensemble_metrics_kernel per SEGMENT (dyf_trajectory_metrics: one segment = one horizon step of a test
+// The per-point values of ensemble_point_reduce summed per SEGMENT (dyf_trajectory_metrics: one segment = one horizon step of a test
 // trajectory, evaluate_ensemble_prediction(..., mean_over_samples=False), evaluation.py:44-45,92-96,112), with no atomics: blockIdx.y
-// is the segment, a workgroup's four wave sums meet in LDS and leave, added in wave order, as partials[segment][blockIdx.x][3];
+// is the segment, the workgroup's sums (ensemble_wave_sums, ensemble_block_total) leave as partials[segment][blockIdx.x][3] and
 // trajectory_metrics_finish_kernel adds a segment's partials.  A segment's sums depend on its own points alone (the split into
 // workgroups is a function of n_members and n_points), so they are the same bits whichever segments share the call.  Member n of a
 // segment starts n * member_stride elements behind the segment's pointer; the pointers are only 4-byte aligned (an (N, S, ...) tensor
 // with an odd n_points), so every load is a dword, consecutive lanes on consecutive addresses.
-__device__ __forceinline__ void trajectory_block_sum(float se, float var, float crps, double* wsum /* LDS, [4][3] */, double* partial) {
-    double d0 = se, d1 = var, d2 = crps;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        d0 += __shfl_xor(d0, off, 64);
-        d1 += __shfl_xor(d1, off, 64);
-        d2 += __shfl_xor(d2, off, 64);
-    }
+__device__ __forceinline__ void trajectory_block_partial(const ensemble_point& pt, double* wsum, double* partials) {
+    double v[3] = {pt.se, pt.var, pt.crps};
+    ensemble_wave_sums<3>(v, wsum);
     const int tid = threadIdx.x;
-    __syncthreads();  // wsum lies over the staged members: every wave is done reading them
-    if ((tid & 63) == 0) {
-        wsum[(tid >> 6) * 3 + 0] = d0;
-        wsum[(tid >> 6) * 3 + 1] = d1;
-        wsum[(tid >> 6) * 3 + 2] = d2;
-    }
-    __syncthreads();
-    if (tid < 3) partial[tid] = ((wsum[tid] + wsum[3 + tid]) + wsum[6 + tid]) + wsum[9 + tid];
+    if (tid < 3) partials[((long long)blockIdx.y * gridDim.x + blockIdx.x) * 3 + tid] = ensemble_block_total<3>(wsum, tid);
 }
 
 __global__ __launch_bounds__(256) void trajectory_metrics_kernel(const float* const* preds_tab, const float* const* targets_tab,
                                                                  int n_members, long long n_points, long long member_stride,
                                                                  double* partials) {
     extern __shared__ double traj_lds[];  // [n_members][256] floats; the first 96 bytes again for the four wave sums (64 members fill 64 KB)
-    float* xs = (float*)traj_lds;
-    const float* preds = preds_tab[blockIdx.y];
-    const float* targets = targets_tab[blockIdx.y];
-    const int tid = threadIdx.x;
-    const long long p = (long long)blockIdx.x * 256 + tid;
-    float se = 0.0f, var = 0.0f, crps = 0.0f;
-    if (p < n_points) {
-        const float y = targets[p];
-        float sum = 0.0f, sabs = 0.0f;
-        for (int n = 0; n < n_members; ++n) {
-            const float x = preds[(long long)n * member_stride + p];
-            xs[n * 256 + tid] = x;
-            sum += x;
-            sabs += fabsf(x - y);
-        }
-        const float inv = 1.0f / (float)n_members;
-        const float mean = sum * inv;
-        float m2 = 0.0f, pair = 0.0f;
-        for (int n = 0; n < n_members; ++n) {
-            const float x = xs[n * 256 + tid];
-            m2 += (x - mean) * (x - mean);
-            for (int m = n + 1; m < n_members; ++m) pair += fabsf(x - xs[m * 256 + tid]);
-        }
-        se = (mean - y) * (mean - y);
-        var = m2 * inv;
-        crps = sabs * inv - pair * inv * inv;
-    }
-    trajectory_block_sum(se, var, crps, traj_lds, partials + ((long long)blockIdx.y * gridDim.x + blockIdx.x) * 3);
+    const long long p = (long long)blockIdx.x * 256 + threadIdx.x;
+    ensemble_point pt = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    if (p < n_points)
+        pt = ensemble_point_reduce(preds_tab[blockIdx.y] + p, member_stride, targets_tab[blockIdx.y][p], n_members, (float*)traj_lds);
+    trajectory_block_partial(pt, traj_lds, partials);
 }
 
-// more than 64 members: the split of ensemble_metrics_tiled_kernel (P points per workgroup, 256 / P threads share a point)
 __global__ __launch_bounds__(256) void trajectory_metrics_tiled_kernel(const float* const* preds_tab, const float* const* targets_tab,
                                                                        int n_members, long long n_points, long long member_stride,
                                                                        double* partials, int P) {
     extern __shared__ double traj_lds[];  // floats: [n_members][P] members (the first 96 bytes again for the wave sums), then [2][256] partials
     float* xs = (float*)traj_lds;
-    float* red = xs + (size_t)n_members * P;
-    const float* preds = preds_tab[blockIdx.y];
-    const float* targets = targets_tab[blockIdx.y];
-    const int tid = threadIdx.x, T = 256 / P;
-    const int pi = tid % P, sh = tid / P;
-    const long long p0 = (long long)blockIdx.x * P, p = p0 + pi;
-    const bool live = p < n_points;
-    for (int i = tid; i < n_members * P; i += 256) {  // staging: consecutive threads -> consecutive points of one member
-        const int n = i / P, q = i - n * P;
-        xs[i] = p0 + q < n_points ? preds[(long long)n * member_stride + p0 + q] : 0.0f;
-    }
-    __syncthreads();
-    const float y = live ? targets[p] : 0.0f;
-    float sum = 0.0f, sabs = 0.0f;
-    for (int n = sh; n < n_members; n += T) {
-        const float x = xs[n * P + pi];
-        sum += x;
-        sabs += fabsf(x - y);
-    }
-    red[tid] = sum;
-    red[256 + tid] = sabs;
-    __syncthreads();
-    float tsum = 0.0f, tabs = 0.0f;
-    for (int k = 0; k < T; ++k) {  // every share adds the T partials in the same order: all hold the same mean
-        tsum += red[k * P + pi];
-        tabs += red[256 + k * P + pi];
-    }
-    const float inv = 1.0f / (float)n_members;
-    const float mean = tsum * inv;
-    __syncthreads();
-    float m2 = 0.0f;
-    double pair = 0.0;  // up to N^2 / 2 terms per point: rows in fp32, the sum of rows in fp64
-    for (int n = sh; n < n_members; n += T) {
-        const float x = xs[n * P + pi];
-        m2 += (x - mean) * (x - mean);
-        float row = 0.0f;
-        for (int m = n + 1; m < n_members; ++m) row += fabsf(x - xs[m * P + pi]);
-        pair += (double)row;
-    }
-    red[tid] = m2;
-    red[256 + tid] = (float)pair;
-    __syncthreads();
-    float se = 0.0f, var = 0.0f, crps = 0.0f;
-    if (live && sh == 0) {
-        float tm2 = 0.0f, tpair = 0.0f;
-        for (int k = 0; k < T; ++k) {
-            tm2 += red[k * P + pi];
-            tpair += red[256 + k * P + pi];
-        }
-        se = (mean - y) * (mean - y);
-        var = tm2 * inv;
-        crps = tabs * inv - tpair * inv * inv;
-    }
-    trajectory_block_sum(se, var, crps, traj_lds, partials + ((long long)blockIdx.y * gridDim.x + blockIdx.x) * 3);
+    const long long p0 = (long long)blockIdx.x * P;
+    const int n_live = n_points - p0 < P ? (int)(n_points - p0) : P;
+    bool holds;
+    const ensemble_point pt = ensemble_point_reduce_tiled(preds_tab[blockIdx.y] + p0, member_stride, n_live, targets_tab[blockIdx.y] + p0,
+                                                          n_members, P, xs, xs + (size_t)n_members * P, holds);
+    trajectory_block_partial(pt, traj_lds, partials);
 }
 
 // One wave per segment: lane l adds the partials l, l + 64, ... in order, then lane 0 the lanes' sums in lane order; division as
@@ -2114,23 +2070,15 @@ __global__ __launch_bounds__(64) void trajectory_metrics_finish_kernel(const dou
     }
 }
 
-// points per workgroup: 256 up to 64 members, beyond that the largest power of two with n_members * P floats <= 60 KB (0 = none)
-static int trajectory_metrics_tile(int n_members) {
-    if (n_members <= 64) return 256;
-    int P = 128;
-    while (P > 1 && (size_t)n_members * P * sizeof(float) > 60 * 1024) P >>= 1;
-    return (size_t)n_members * P * sizeof(float) > 60 * 1024 ? 0 : P;
-}
-
 long long trajectory_metrics_blocks(int n_members, long long n_points) {
-    const int P = trajectory_metrics_tile(n_members);
+    const int P = ensemble_tile_points(n_members);
     return P ? (n_points + P - 1) / P : 0;
 }
 
 hipError_t launch_trajectory_metrics(const float* const* preds_tab, const float* const* targets_tab, int n_segments, int n_members,
                                      long long n_points, long long member_stride, double* partials, double* out, double* accum,
                                      hipStream_t s) {
-    const int P = trajectory_metrics_tile(n_members);
+    const int P = ensemble_tile_points(n_members);
     const long long blocks = trajectory_metrics_blocks(n_members, n_points);
     // 256 * blocks threads along x stay below 2^32
     if (P == 0 || blocks < 1 || blocks > 0xffffffLL || n_segments < 1 || n_segments > 65535) return hipErrorInvalidValue;
@@ -2318,11 +2266,9 @@ hipError_t launch_ensemble_size_metrics(const float* const* preds_tab, const flo
 // mean_dims and evaluate_ensemble_corr, evaluation.py:83-142).  A segment's points are row-major (n_outer, n_groups, n_inner) and
 // point p belongs to group (p / n_inner) % n_groups.  Work mapping: blockIdx.x = slab * tiles_per_slab + tile with slab = outer *
 // n_groups + group, so a workgroup's tile lies inside one (outer, group) slab and its partial belongs to one group; blockIdx.y is the
-// segment.  Per point mean, se, var and crps are the fp32 expressions of trajectory_metrics_kernel (the two kernels below are its
-// two forms with the slab index map; where 1 / N is inexact the last bit of crps depends on how its two products are contracted, so
-// that one expression is written the way the compiler leaves it in either form there, and the pooled call equals
-// dyf_trajectory_metrics to the fp64 sums' rounding), nll = 0.5 log(2 pi var) + se / (2 var) in fp32 with the accurate logf; no
-// clamp: one member has var = 0 and a NaN nll, as numpy.
+// segment.  To the per-point values of ensemble_point_reduce (pooled, (1, 1, n_points), the tiles, the block sums and the finish
+// order are those of dyf_trajectory_metrics, and mse / ssr / crps its bits) this adds nll = 0.5 log(2 pi var) + se / (2 var) in fp32
+// with the accurate logf; no clamp: one member has var = 0 and a NaN nll, as numpy.
 //   Correlation: a workgroup leaves the mean of its points' ensemble means and targets and their CENTRED second moments about
 // those (fp64, from the fp32 mean and y; a second round over values the threads still hold), and the finish kernel joins the
 // workgroups' moments pairwise (Chan et al.).  The raw moments sum(m), sum(m^2), ... would give the same correlation on ordinary
@@ -2333,48 +2279,35 @@ hipError_t launch_ensemble_size_metrics(const float* const* preds_tab, const flo
 // points of a tile follow from the geometry.  ensemble_scores_finish_kernel (one wave per (segment, group)) walks the group's
 // partials in (outer, tile) order: lane l takes entries l, l + 64, ..., lane 0 joins the lanes in lane order.  No atomics; a group's
 // result depends on its own points, n_members and (n_outer, n_inner) alone.
-template <int K>
-__device__ __forceinline__ void scores_block_sum(double (&v)[K], double* wsum /* LDS, [4][K] */) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-#pragma unroll
-        for (int k = 0; k < K; ++k) v[k] += __shfl_xor(v[k], off, 64);
-    }
-    const int tid = threadIdx.x;
-    __syncthreads();  // wsum lies over the staged members (and over the sums of the round before): every wave is done reading them
-    if ((tid & 63) == 0) {
-#pragma unroll
-        for (int k = 0; k < K; ++k) wsum[(tid >> 6) * K + k] = v[k];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < K; ++k) v[k] = ((wsum[k] + wsum[K + k]) + wsum[2 * K + k]) + wsum[3 * K + k];  // every thread: the workgroup's sum
-}
 
 // `holds`: this thread carries a live point's values (the others add zeros); n_live: the live points of the tile (>= 1).
-__device__ __forceinline__ void scores_block_partial(bool holds, float mean, float y, float se, float var, float crps, int n_live,
-                                                     double* wsum, double* partial) {
+__device__ __forceinline__ void scores_block_partial(bool holds, const ensemble_point& pt, int n_live, double* wsum, double* partials) {
     double v[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     if (holds) {
-        const float nll = 0.5f * logf(6.2831853071795865f * var) + se / (2.0f * var);
-        v[0] = se;
-        v[1] = var;
-        v[2] = crps;
+        const float nll = 0.5f * logf(6.2831853071795865f * pt.var) + pt.se / (2.0f * pt.var);
+        v[0] = pt.se;
+        v[1] = pt.var;
+        v[2] = pt.crps;
         v[3] = nll;
-        v[4] = mean;
-        v[5] = y;
+        v[4] = pt.mean;
+        v[5] = pt.y;
     }
-    scores_block_sum<6>(v, wsum);
+    ensemble_wave_sums<6>(v, wsum);
+#pragma unroll
+    for (int k = 0; k < 6; ++k) v[k] = ensemble_block_total<6>(wsum, k);  // every thread: the workgroup's sums
     const double mm = v[4] / (double)n_live, my = v[5] / (double)n_live;
     double c[3] = {0.0, 0.0, 0.0};
     if (holds) {
-        const double dm = (double)mean - mm, dy = (double)y - my;
+        const double dm = (double)pt.mean - mm, dy = (double)pt.y - my;
         c[0] = dm * dm;
         c[1] = dy * dy;
         c[2] = dm * dy;
     }
-    scores_block_sum<3>(c, wsum);
+    ensemble_wave_sums<3>(c, wsum);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) c[k] = ensemble_block_total<3>(wsum, k);
     if (threadIdx.x == 0) {
+        double* partial = partials + ((long long)blockIdx.y * gridDim.x + blockIdx.x) * ENSEMBLE_SCORES_PARTIAL;
         partial[0] = v[0];
         partial[1] = v[1];
         partial[2] = v[2];
@@ -2391,109 +2324,30 @@ __global__ __launch_bounds__(256) void ensemble_scores_kernel(const float* const
                                                               int n_members, long long member_stride, long long n_inner,
                                                               unsigned tiles_per_slab, double* partials) {
     extern __shared__ double scores_lds[];  // [n_members][256] floats; the first 192 bytes again for the wave sums
-    float* xs = (float*)scores_lds;
-    const float* preds = preds_tab[blockIdx.y];
-    const float* targets = targets_tab[blockIdx.y];
-    const int tid = threadIdx.x;
     const unsigned slab = blockIdx.x / tiles_per_slab, tile = blockIdx.x - slab * tiles_per_slab;
-    const long long q = (long long)tile * 256 + tid;  // within the slab
+    const long long q = (long long)tile * 256 + threadIdx.x;  // within the slab
     const long long p = (long long)slab * n_inner + q;
     const bool live = q < n_inner;
-    float se = 0.0f, var = 0.0f, crps = 0.0f, mean = 0.0f, y = 0.0f;
-    if (live) {
-        y = targets[p];
-        float sum = 0.0f, sabs = 0.0f;
-        for (int n = 0; n < n_members; ++n) {
-            const float x = preds[(long long)n * member_stride + p];
-            xs[n * 256 + tid] = x;
-            sum += x;
-            sabs += fabsf(x - y);
-        }
-        const float inv = 1.0f / (float)n_members;
-        mean = sum * inv;
-        float m2 = 0.0f, pair = 0.0f;
-        for (int n = 0; n < n_members; ++n) {
-            const float x = xs[n * 256 + tid];
-            m2 += (x - mean) * (x - mean);
-            for (int m = n + 1; m < n_members; ++m) pair += fabsf(x - xs[m * 256 + tid]);
-        }
-        se = (mean - y) * (mean - y);
-        var = m2 * inv;
-        crps = fmaf(sabs, inv, -(pair * inv * inv));  // trajectory_metrics_kernel's sabs * inv - pair * inv * inv as the compiler contracts it there
-    }
+    ensemble_point pt = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    if (live)
+        pt = ensemble_point_reduce(preds_tab[blockIdx.y] + p, member_stride, targets_tab[blockIdx.y][p], n_members, (float*)scores_lds);
     const int n_live = n_inner - (long long)tile * 256 < 256 ? (int)(n_inner - (long long)tile * 256) : 256;
-    scores_block_partial(live, mean, y, se, var, crps, n_live, scores_lds,
-                         partials + ((long long)blockIdx.y * gridDim.x + blockIdx.x) * ENSEMBLE_SCORES_PARTIAL);
+    scores_block_partial(live, pt, n_live, scores_lds, partials);
 }
 
-// more than 64 members: the split of trajectory_metrics_tiled_kernel (P points per workgroup, 256 / P threads share a point)
 __global__ __launch_bounds__(256) void ensemble_scores_tiled_kernel(const float* const* preds_tab, const float* const* targets_tab,
                                                                     int n_members, long long member_stride, long long n_inner,
                                                                     unsigned tiles_per_slab, double* partials, int P) {
     extern __shared__ double scores_lds[];  // floats: [n_members][P] members (the first 192 bytes again for the wave sums), then [2][256] partials
     float* xs = (float*)scores_lds;
-    float* red = xs + (size_t)n_members * P;
-    const float* preds = preds_tab[blockIdx.y];
-    const float* targets = targets_tab[blockIdx.y];
-    const int tid = threadIdx.x, T = 256 / P;
-    const int pi = tid % P, sh = tid / P;
     const unsigned slab = blockIdx.x / tiles_per_slab, tile = blockIdx.x - slab * tiles_per_slab;
     const long long q0 = (long long)tile * P;            // within the slab
     const long long p0 = (long long)slab * n_inner + q0;
-    const bool live = q0 + pi < n_inner;
-    for (int i = tid; i < n_members * P; i += 256) {  // staging: consecutive threads -> consecutive points of one member
-        const int n = i / P, q = i - n * P;
-        xs[i] = q0 + q < n_inner ? preds[(long long)n * member_stride + p0 + q] : 0.0f;
-    }
-    __syncthreads();
-    const float y = live ? targets[p0 + pi] : 0.0f;
-    float sum = 0.0f, sabs = 0.0f;
-    for (int n = sh; n < n_members; n += T) {
-        const float x = xs[n * P + pi];
-        sum += x;
-        sabs += fabsf(x - y);
-    }
-    red[tid] = sum;
-    red[256 + tid] = sabs;
-    __syncthreads();
-    float tsum = 0.0f, tabs = 0.0f;
-    for (int k = 0; k < T; ++k) {  // every share adds the T partials in the same order: all hold the same mean
-        tsum += red[k * P + pi];
-        tabs += red[256 + k * P + pi];
-    }
-    const float inv = 1.0f / (float)n_members;
-    const float mean = tsum * inv;
-    __syncthreads();
-    float m2 = 0.0f;
-    double pair = 0.0;  // up to N^2 / 2 terms per point: rows in fp32, the sum of rows in fp64
-    for (int n = sh; n < n_members; n += T) {
-        const float x = xs[n * P + pi];
-        m2 += (x - mean) * (x - mean);
-        float row = 0.0f;
-        for (int m = n + 1; m < n_members; ++m) row += fabsf(x - xs[m * P + pi]);
-        pair += (double)row;
-    }
-    red[tid] = m2;
-    red[256 + tid] = (float)pair;
-    __syncthreads();
-    float se = 0.0f, var = 0.0f, crps = 0.0f;
-    const bool holds = live && sh == 0;
-    if (holds) {
-        float tm2 = 0.0f, tpair = 0.0f;
-        for (int k = 0; k < T; ++k) {
-            tm2 += red[k * P + pi];
-            tpair += red[256 + k * P + pi];
-        }
-        se = (mean - y) * (mean - y);
-        var = tm2 * inv;
-        {
-#pragma clang fp contract(off)  // ... and trajectory_metrics_tiled_kernel's as the compiler leaves it there: two products, one subtraction
-            crps = tabs * inv - tpair * inv * inv;
-        }
-    }
     const int n_live = n_inner - q0 < P ? (int)(n_inner - q0) : P;
-    scores_block_partial(holds, mean, y, se, var, crps, n_live, scores_lds,
-                         partials + ((long long)blockIdx.y * gridDim.x + blockIdx.x) * ENSEMBLE_SCORES_PARTIAL);
+    bool holds;
+    const ensemble_point pt = ensemble_point_reduce_tiled(preds_tab[blockIdx.y] + p0, member_stride, n_live, targets_tab[blockIdx.y] + p0,
+                                                          n_members, P, xs, xs + (size_t)n_members * P, holds);
+    scores_block_partial(holds, pt, n_live, scores_lds, partials);
 }
 
 struct scores_moments {
@@ -2571,12 +2425,10 @@ __global__ __launch_bounds__(64) void ensemble_scores_finish_kernel(const double
 }
 
 long long ensemble_scores_blocks(int n_members, long long n_outer, int n_groups, long long n_inner) {
-    const int P = n_members >= 1 ? trajectory_metrics_tile(n_members) : 0;
+    const int P = ensemble_tile_points(n_members);
     if (P == 0 || n_outer < 1 || n_groups < 1 || n_inner < 1) return 0;
     const long long tiles = (n_inner + P - 1) / P;
-    if (tiles > ENSEMBLE_SCORES_MAX_BLOCKS || n_outer > ENSEMBLE_SCORES_MAX_BLOCKS / tiles ||
-        (long long)n_groups > ENSEMBLE_SCORES_MAX_BLOCKS / (tiles * n_outer))
-        return -1;
+    if (!ensemble_geometry_fits(n_outer, n_groups, tiles)) return -1;
     return tiles * n_outer * n_groups;
 }
 
@@ -2585,7 +2437,7 @@ hipError_t launch_ensemble_scores(const float* const* preds_tab, const float* co
                                   double* out, double* accum, hipStream_t s) {
     const long long blocks = ensemble_scores_blocks(n_members, n_outer, n_groups, n_inner);
     if (blocks < 1 || n_segments < 1 || n_segments > 65535) return hipErrorInvalidValue;
-    const int P = trajectory_metrics_tile(n_members);
+    const int P = ensemble_tile_points(n_members);
     const long long tiles = (n_inner + P - 1) / P;
     const dim3 grid((unsigned)blocks, (unsigned)n_segments);
     if (n_members > 64) {

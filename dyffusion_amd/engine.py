@@ -540,6 +540,27 @@ class HipEngine:
             raise ValueError(f"{what} works on GPU tensors (the HIP engine computes them)")
         return n, nseg, points, stride, p_ptrs, t_ptrs, keep, dev
 
+    @staticmethod
+    def _accum_ptr(accum: Optional[torch.Tensor], shape: tuple, dev):
+        if accum is None:
+            return None
+        if accum.dtype != torch.float64 or tuple(accum.shape) != shape or not accum.is_contiguous() or accum.device != dev:
+            raise ValueError(f"accum must be a contiguous float64 {shape} tensor on {dev}")
+        return accum.data_ptr()
+
+    @staticmethod
+    def _group_shape(group_shape: Optional[Sequence[int]], points: int):
+        """(outer, groups, inner) of one segment's `points`; None pools the segment."""
+        if group_shape is None:
+            group_shape = (1, 1, points)
+        try:
+            outer, groups, inner = (operator.index(v) for v in group_shape)
+        except (TypeError, ValueError):
+            raise ValueError(f"group_shape must be (outer, groups, inner) integers, not {group_shape!r}") from None
+        if min(outer, groups, inner) < 1 or outer * groups * inner != points:
+            raise ValueError(f"group_shape {(outer, groups, inner)} must be positive with product {points}, a segment's points")
+        return outer, groups, inner
+
     def trajectory_metrics(self, preds, targets, accum: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Per-segment (mse, ssr, crps) on the device (dyf_trajectory_metrics): the curves of the reference's
         `evaluate_ensemble_prediction(..., mean_over_samples=False)`.  `preds` is a list of T contiguous (N, ...) tensors with
@@ -548,13 +569,10 @@ class HipEngine:
         device tensor (3, T), rows mse / ssr / crps; `accum` (float64, (3, T), on the device) += it.  No synchronisation: the
         two launches are enqueued on the current stream."""
         n, nseg, points, stride, p_ptrs, t_ptrs, keep, dev = self._segments(preds, targets, "trajectory_metrics")
-        if accum is not None and (accum.dtype != torch.float64 or tuple(accum.shape) != (3, nseg) or not accum.is_contiguous()
-                                  or accum.device != dev):
-            raise ValueError(f"accum must be a contiguous float64 (3, {nseg}) tensor on {dev}")
+        accum_ptr = self._accum_ptr(accum, (3, nseg), dev)
         out = torch.empty(3, nseg, dtype=torch.float64, device=dev)
         self._check(self._lib.dyf_trajectory_metrics(self._h, nseg, (C.c_void_p * nseg)(*p_ptrs), (C.c_void_p * nseg)(*t_ptrs), n,
-                                                     points, stride, out.data_ptr(), accum.data_ptr() if accum is not None else None,
-                                                     self._stream()))
+                                                     points, stride, out.data_ptr(), accum_ptr, self._stream()))
         del keep  # held until the launches were enqueued; the caching allocator orders any reuse behind them on this stream
         return out
 
@@ -566,13 +584,10 @@ class HipEngine:
         crps (entry n - 1 = the first n members) / mse_per_mem; `accum` (float64, (4, T, N), on the device) += it.  At most 256
         members (NotImplementedError beyond).  No synchronisation."""
         n, nseg, points, stride, p_ptrs, t_ptrs, keep, dev = self._segments(preds, targets, "ensemble_size_metrics")
-        if accum is not None and (accum.dtype != torch.float64 or tuple(accum.shape) != (4, nseg, n) or not accum.is_contiguous()
-                                  or accum.device != dev):
-            raise ValueError(f"accum must be a contiguous float64 (4, {nseg}, {n}) tensor on {dev}")
+        accum_ptr = self._accum_ptr(accum, (4, nseg, n), dev)
         out = torch.empty(4, nseg, n, dtype=torch.float64, device=dev)
         self._check(self._lib.dyf_ensemble_size_metrics(self._h, nseg, (C.c_void_p * nseg)(*p_ptrs), (C.c_void_p * nseg)(*t_ptrs), n,
-                                                        points, stride, out.data_ptr(),
-                                                        accum.data_ptr() if accum is not None else None, self._stream()))
+                                                        points, stride, out.data_ptr(), accum_ptr, self._stream()))
         del keep  # as in trajectory_metrics
         return out
 
@@ -586,21 +601,11 @@ class HipEngine:
         behaviour as numpy: one member gives a NaN nll, a group with constant ensemble means or targets a NaN corr.  No
         synchronisation."""
         n, nseg, points, stride, p_ptrs, t_ptrs, keep, dev = self._segments(preds, targets, "ensemble_scores")
-        if group_shape is None:
-            group_shape = (1, 1, points)
-        try:
-            outer, groups, inner = (operator.index(v) for v in group_shape)
-        except (TypeError, ValueError):
-            raise ValueError(f"group_shape must be (outer, groups, inner) integers, not {group_shape!r}") from None
-        if min(outer, groups, inner) < 1 or outer * groups * inner != points:
-            raise ValueError(f"group_shape {(outer, groups, inner)} must be positive with product {points}, a segment's points")
-        if accum is not None and (accum.dtype != torch.float64 or tuple(accum.shape) != (5, nseg, groups) or not accum.is_contiguous()
-                                  or accum.device != dev):
-            raise ValueError(f"accum must be a contiguous float64 (5, {nseg}, {groups}) tensor on {dev}")
+        outer, groups, inner = self._group_shape(group_shape, points)
+        accum_ptr = self._accum_ptr(accum, (5, nseg, groups), dev)
         out = torch.empty(5, nseg, groups, dtype=torch.float64, device=dev)
         self._check(self._lib.dyf_ensemble_scores(self._h, nseg, (C.c_void_p * nseg)(*p_ptrs), (C.c_void_p * nseg)(*t_ptrs), n, points,
-                                                  stride, outer, groups, inner, out.data_ptr(),
-                                                  accum.data_ptr() if accum is not None else None, self._stream()))
+                                                  stride, outer, groups, inner, out.data_ptr(), accum_ptr, self._stream()))
         del keep  # as in trajectory_metrics
         return out
 
@@ -656,21 +661,11 @@ class HipEngine:
         target or member are left out.  `accum` (float64, (T, G, N + 1), on the device) += it.  At most 1024 members
         (NotImplementedError beyond).  No synchronisation."""
         n, nseg, points, stride, p_ptrs, t_ptrs, keep, dev = self._segments(preds, targets, "rank_histogram")
-        if group_shape is None:
-            group_shape = (1, 1, points)
-        try:
-            outer, groups, inner = (operator.index(v) for v in group_shape)
-        except (TypeError, ValueError):
-            raise ValueError(f"group_shape must be (outer, groups, inner) integers, not {group_shape!r}") from None
-        if min(outer, groups, inner) < 1 or outer * groups * inner != points:
-            raise ValueError(f"group_shape {(outer, groups, inner)} must be positive with product {points}, a segment's points")
-        if accum is not None and (accum.dtype != torch.float64 or tuple(accum.shape) != (nseg, groups, n + 1) or not accum.is_contiguous()
-                                  or accum.device != dev):
-            raise ValueError(f"accum must be a contiguous float64 ({nseg}, {groups}, {n + 1}) tensor on {dev}")
+        outer, groups, inner = self._group_shape(group_shape, points)
+        accum_ptr = self._accum_ptr(accum, (nseg, groups, n + 1), dev)
         out = torch.empty(nseg, groups, n + 1, dtype=torch.float64, device=dev)
         self._check(self._lib.dyf_rank_histogram(self._h, nseg, (C.c_void_p * nseg)(*p_ptrs), (C.c_void_p * nseg)(*t_ptrs), n, points,
-                                                 stride, outer, groups, inner, out.data_ptr(),
-                                                 accum.data_ptr() if accum is not None else None, self._stream()))
+                                                 stride, outer, groups, inner, out.data_ptr(), accum_ptr, self._stream()))
         del keep  # as in trajectory_metrics
         return out
 

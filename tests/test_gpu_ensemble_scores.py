@@ -9,7 +9,7 @@ fewer beyond (64 at 65 and at 130 members).  So inner 153 is one partial tile pe
 
 Bounds: mse / ssr / crps rel 2e-5, the project's bound for these fp32 per-point expressions; nll |got - ref| <= 2e-5 x the mean
 over the group's points of |nll_p| (fp32 per point as well, and the mean itself can be near zero); corr abs 1e-6 (the moments are
-fp64; the ensemble mean under them is a sequential fp32 sum of up to 130 members).  One member: nll is NaN and ssr exactly 0."""
+fp64; the ensemble mean under them is an fp32 sum of up to 130 members in sequence, or of 2000 in 64 shares).  One member: nll is NaN and ssr exactly 0."""
 import ctypes as C
 
 import numpy as np
@@ -110,10 +110,11 @@ def test_groups_match_the_reference(n, t, shape, axes):
         assert alone[:, :, 0] == pytest.approx(got[:, :, g].cpu().numpy(), rel=1e-12, abs=0.0, nan_ok=True), g
 
 
-# 1 / N is inexact for 6, 20, 65 and 130 members: there a product contracted differently from trajectory_metrics_kernel's would show
+# 1 / N is inexact for 6, 20, 65, 130 and 2000 members: there a product contracted differently in the two entries would show.
+# 2000 members on 7 points: 4 points per workgroup, the 64 shares of a point fill a wave (the share-order walks run to k = 63).
 @pytest.mark.parametrize("n,t,shape", [(8, 2, (2, 3, 17, 9)), (65, 2, (2, 165)), (1, 1, (2, 3, 8, 8)), (6, 2, (4, 3, 5, 7)),
-                                       (20, 3, (3, 2, 16, 16)), (130, 1, (1, 2, 11, 23))],
-                         ids=["N8", "N65", "N1", "N6-odd", "N20", "N130"])
+                                       (20, 3, (3, 2, 16, 16)), (130, 1, (1, 2, 11, 23)), (2000, 1, (7,))],
+                         ids=["N8", "N65", "N1", "N6-odd", "N20", "N130", "N2000"])
 def test_pooled(n, t, shape):
     eng = _engine()
     preds, truth, _, ref, scale = _case(n, t, shape, None)
@@ -124,9 +125,8 @@ def test_pooled(n, t, shape):
     points = truth[0].numel()
     assert _same_bits(eng.ensemble_scores(pl, tl, group_shape=(1, 1, points)), got)
     assert _same_bits(eng.ensemble_scores(preds.cuda(), truth.cuda()), got)
-    # planes 0-2 are the per-point expressions of trajectory_metrics_kernel, added in fp64
-    whole = eng.trajectory_metrics(pl, tl).cpu().numpy()
-    assert got[:3, :, 0].cpu().numpy() == pytest.approx(whole, rel=1e-12, abs=0.0)
+    # planes 0-2 are dyf_trajectory_metrics bit for bit: the same per-point helper, tiles, block sum and finish order
+    assert _same_bits(got[:3, :, 0], eng.trajectory_metrics(pl, tl))
 
 
 def test_permuting_the_channels_permutes_the_outputs():

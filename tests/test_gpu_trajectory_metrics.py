@@ -66,6 +66,7 @@ CASES = [  # N, segments, points per segment, both layouts
     (64, 2, (330,), True),          # LDS edge of the small form
     (65, 2, (330,), True),          # tiled form
     (256, 3, (253,), False),        # tiled form, small P
+    (2000, 1, (7,), False),         # tiled form, 4 points per workgroup: the 64 shares of a point fill a wave
     (5, 130, (70,), False),         # more segments than a wave has lanes
     (3, 1, (255,), False),          # below / exactly / one past the 256-thread tile
     (3, 1, (256,), False),
