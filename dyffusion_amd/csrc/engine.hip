@@ -1818,13 +1818,15 @@ static void traj_release(dyf_engine* e) {
     if (e->ens_size_partials) (void)hipFree(e->ens_size_partials);
     if (e->ens_scores_partials) (void)hipFree(e->ens_scores_partials);
     if (e->rank_hist_partials) (void)hipFree(e->rank_hist_partials);
+    if (e->energy_partials) (void)hipFree(e->energy_partials);
     if (e->traj_uploaded) (void)hipEventDestroy(e->traj_uploaded);
     if (e->traj_done) (void)hipEventDestroy(e->traj_done);
     e->traj_tab = e->traj_stage = nullptr;
-    e->traj_partials = e->ens_size_partials = e->ens_scores_partials = e->rank_hist_partials = nullptr;
+    e->traj_partials = e->ens_size_partials = e->ens_scores_partials = e->rank_hist_partials = e->energy_partials = nullptr;
     e->traj_uploaded = e->traj_done = nullptr;
     e->traj_cap = 0;
     e->traj_partials_count = e->ens_size_partials_count = e->ens_scores_partials_count = e->rank_hist_partials_count = 0;
+    e->energy_partials_count = 0;
     e->traj_pending = false;
 }
 
@@ -2018,6 +2020,29 @@ dyf_status dyf_rank_histogram(dyf_engine* e, int32_t n_segments, const float* co
     if (cs != DYF_OK) return cs;
     return traj_finish(e, launch_rank_histogram(e->traj_tab, e->traj_tab + n_segments, n_segments, n_members, member_stride, n_outer,
                                                 n_groups, n_inner, e->rank_hist_partials, out_dev, accum_dev, st), st);
+}
+
+dyf_status dyf_energy_score(dyf_engine* e, int32_t n_segments, const float* const* preds_dev, const float* const* targets_dev,
+                            int32_t n_members, int64_t n_points, int64_t member_stride, int64_t n_outer, int32_t n_groups,
+                            int64_t n_inner, double* out_dev, double* member_out_dev, double* pair_out_dev, double* accum_dev,
+                            void* stream) {
+    dyf_status cs = traj_check_args(e, n_segments, preds_dev, targets_dev, n_members, ENERGY_SCORE_MAX_MEMBERS, DYF_ERR_UNSUPPORTED,
+                                    n_points, member_stride, out_dev);
+    if (cs != DYF_OK) return cs;
+    cs = traj_check_groups(e, n_points, n_outer, n_groups, n_inner);
+    if (cs != DYF_OK) return cs;
+    EnergyScorePlan plan;
+    if (energy_score_plan(n_segments, n_members, n_outer, n_groups, n_inner, &plan) != 0)
+        return fail(e, DYF_ERR_UNSUPPORTED, "workspace beyond 2^27 = " + std::to_string(ENERGY_SCORE_MAX_WORKSPACE) +
+                                                " doubles (n_segments * (n_outer * n_groups * chunks + n_groups) * n_members * (n_members + 1))");
+    HIP_TRY(e, hipSetDevice(e->cfg.device));
+    hipStream_t st = (hipStream_t)stream;
+    cs = traj_upload(e, n_segments, preds_dev, targets_dev, &e->energy_partials, &e->energy_partials_count,
+                     (size_t)(plan.partial_doubles + plan.mean_doubles), st);
+    if (cs != DYF_OK) return cs;
+    return traj_finish(e, launch_energy_score(e->traj_tab, e->traj_tab + n_segments, n_segments, n_members, member_stride, n_outer,
+                                              n_groups, n_inner, e->energy_partials, out_dev, member_out_dev, pair_out_dev, accum_dev,
+                                              st), st);
 }
 
 dyf_status dyf_apply_boundary_conditions(dyf_engine* e, const dyf_bc_args* bc, float* preds_dev, void* stream) {

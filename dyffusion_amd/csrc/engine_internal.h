@@ -160,6 +160,8 @@ struct dyf_engine {
     size_t ens_scores_partials_count = 0;
     double* rank_hist_partials = nullptr;  // dyf_rank_histogram: likewise
     size_t rank_hist_partials_count = 0;
+    double* energy_partials = nullptr;  // dyf_energy_score: likewise (partial sums of squares, then the mean distances)
+    size_t energy_partials_count = 0;
     hipEvent_t traj_uploaded = nullptr, traj_done = nullptr;
     bool traj_pending = false;  // the two events have been recorded
     int prof_layer = -1;

@@ -271,6 +271,28 @@ int rank_histogram_chunks(int n_members, long long n_outer, int n_groups, long l
 hipError_t launch_rank_histogram(const float* const* preds_tab, const float* const* targets_tab, int n_segments, int n_members,
                                  long long member_stride, long long n_outer, int n_groups, long long n_inner, double* partials,
                                  double* out, double* accum, hipStream_t s);
+// the energy score and the member-distance matrix per (segment, group) of the geometry of launch_ensemble_scores (dyf_energy_score;
+// energy_score.hip), without atomics.  A vector is one (outer, group) slab of n_inner points.  Launch 1 leaves float64 sums of squared
+// differences in workspace[n_segments][vectors][chunks][N][N + 1] (entry (i, j), i < j < N: members i and j; entry (i, N): member i and
+// the target), launch 2 takes the square roots of the chunk sums and their mean over outer into workspace + partial_doubles
+// [n_segments][n_groups][N][N + 1], launch 3 writes out[4][n_segments][n_groups] = {es, es_fair, dist_target, dist_pair} (accum += out
+// when given) and, when given, member_out[n_segments][n_groups][N] and pair_out[n_segments][n_groups][N][N].
+constexpr int ENERGY_SCORE_MAX_MEMBERS = 256;                 // DYF_ENERGY_MAX_MEMBERS
+constexpr int ENERGY_SCORE_TILE_POINTS = 64;                  // DYF_ENERGY_TILE_POINTS
+constexpr long long ENERGY_SCORE_MAX_WORKSPACE = 1LL << 27;   // DYF_ENERGY_MAX_WORKSPACE_DOUBLES
+struct EnergyScorePlan {
+    int blocks;                 // ceil(N / 64) slabs of 64 members
+    int block_pairs;            // blocks * (blocks + 1) / 2 pairs (bi <= bj)
+    int chunks;                 // workgroups that share a vector's tiles (1 = the vector is not split)
+    long long vectors;          // n_outer * n_groups per segment
+    long long tiles_per_chunk;  // consecutive tiles of ENERGY_SCORE_TILE_POINTS points per chunk
+    long long partial_doubles, mean_doubles;  // the two regions of the workspace
+};
+// 0 = ok; 1 = bad arguments or n_members beyond the limit; -1 = the workspace would exceed ENERGY_SCORE_MAX_WORKSPACE doubles
+int energy_score_plan(int n_segments, int n_members, long long n_outer, int n_groups, long long n_inner, EnergyScorePlan* plan);
+hipError_t launch_energy_score(const float* const* preds_tab, const float* const* targets_tab, int n_segments, int n_members,
+                               long long member_stride, long long n_outer, int n_groups, long long n_inner, double* workspace,
+                               double* out, double* member_out, double* pair_out, double* accum, hipStream_t s);
 
 // dyf_sample_gather: all-gather receive layout [world][slots][nb][row floats] -> [slots][total_rows][row] in global row order;
 // rank r owns the contiguous block of rows shard(r) (the first total_rows % world ranks one extra), its padding rows are dropped

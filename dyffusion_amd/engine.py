@@ -669,6 +669,32 @@ class HipEngine:
         del keep  # as in trajectory_metrics
         return out
 
+    def energy_score(self, preds, targets, group_shape: Optional[Sequence[int]] = None, accum: Optional[torch.Tensor] = None,
+                     members: bool = False, pairs: bool = False):
+        """The energy score per (segment, group) on the device (dyf_energy_score): the CRPS with |.| replaced by the Euclidean norm
+        over a whole vector of points.  Inputs and `group_shape` as `ensemble_scores`; a vector is one (outer, group) slab of `inner`
+        contiguous points, and a group's values are the means over `outer`: (B, 1, C * H * W) on (B, C, H, W) targets scores whole
+        fields, (B, C, H * W) every channel; None is one vector per segment.  Returns a float64 device tensor (4, T, G), planes es /
+        es_fair / dist_target / dist_pair (`dyffusion_amd.metrics.ENERGY_ROWS`); `accum` (float64, (4, T, G), on the device) += it.
+        With `members` / `pairs` it returns (scores, {"member_dist": (T, G, N) every member's distance to the target, "pair_dist":
+        (T, G, N, N) the symmetric member-distance matrix with a zero diagonal}).  One member gives NaN in es_fair and dist_pair.
+        At most 256 members (NotImplementedError beyond).  No synchronisation."""
+        n, nseg, points, stride, p_ptrs, t_ptrs, keep, dev = self._segments(preds, targets, "energy_score")
+        outer, groups, inner = self._group_shape(group_shape, points)
+        accum_ptr = self._accum_ptr(accum, (4, nseg, groups), dev)
+        out = torch.empty(4, nseg, groups, dtype=torch.float64, device=dev)
+        extra = {}
+        if members:
+            extra["member_dist"] = torch.empty(nseg, groups, n, dtype=torch.float64, device=dev)
+        if pairs:
+            extra["pair_dist"] = torch.empty(nseg, groups, n, n, dtype=torch.float64, device=dev)
+        self._check(self._lib.dyf_energy_score(self._h, nseg, (C.c_void_p * nseg)(*p_ptrs), (C.c_void_p * nseg)(*t_ptrs), n, points,
+                                               stride, outer, groups, inner, out.data_ptr(),
+                                               extra["member_dist"].data_ptr() if members else None,
+                                               extra["pair_dist"].data_ptr() if pairs else None, accum_ptr, self._stream()))
+        del keep  # as in trajectory_metrics
+        return (out, extra) if extra else out
+
     def time_layer_in_rollout(self, layer: int, nb: int):
         """(average ms, launches) of decoder block `layer`'s conv over one eagerly launched rollout of the current plan."""
         ms, cnt = C.c_double(), C.c_int32()

@@ -123,7 +123,7 @@ class MultiHorizonForecastingDYffusion(nn.Module):
                  autoregressive_steps: int = 0, prediction_horizon: Optional[int] = None, datamodule=None,
                  datamodule_config: Optional[Dict[str, Any]] = None, ensemble_size_curves: bool = False,
                  extended_metrics: bool = False, predict_products: Optional[Dict[str, Any]] = None, keep_members: bool = True,
-                 rank_histogram: bool = False):
+                 rank_histogram: bool = False, energy_score: bool = False):
         super().__init__()
         assert autoregressive_steps >= 0, f"Autoregressive steps must be >= 0, but is {autoregressive_steps}"
         if autoregressive_steps > 0:
@@ -148,6 +148,9 @@ class MultiHorizonForecastingDYffusion(nn.Module):
         self.keep_members = keep_members
         # also report the rank histogram of every horizon and its reliability index at the end of validation / test epochs
         self.rank_histogram = rank_histogram
+        # also report the whole-field energy score (es, es_fair) of every horizon and es per channel at the end of validation / pooled
+        # test epochs, and the instance-averaged es curve at the end of a physical-systems test epoch
+        self.energy_score = energy_score
         self._test_metrics_aggregate = None  # TrajectoryMetricsAccumulator of the physical-systems test epoch (first test_step)
         self._predict_step_outputs = []
 
@@ -317,7 +320,8 @@ class MultiHorizonForecastingDYffusion(nn.Module):
         from .metrics import TrajectoryMetricsAccumulator
         if self._test_metrics_aggregate is None:
             self._test_metrics_aggregate = TrajectoryMetricsAccumulator(self.model._engine, by_size=self.ensemble_size_curves,
-                                                                        rank_histogram=self.rank_histogram)
+                                                                        rank_histogram=self.rank_histogram,
+                                                                        energy_score=self.energy_score)
         timesteps = range(1, self.prediction_horizon + 1)
         targets = [results[f"t{t}_targets"] for t in timesteps]
         preds = [results[f"t{t}_preds"] for t in timesteps]
@@ -332,8 +336,9 @@ class MultiHorizonForecastingDYffusion(nn.Module):
         logs: `{split}/{N}ens_mems/t{k}/{crps|ssr|mse}` and `.../avg/...`; with `ensemble_size_curves` also the same keys for the
         first n members, n = 1..N-1 (ensemble_size_metrics_kernel), and with `extended_metrics` `.../t{k}/{nll|corr}` and the five
         scores per channel `.../t{k}/c{j}/{m}` (ensemble_scores_kernel), and with `rank_histogram` `.../t{k}/rank_hist` (an (N + 1,)
-        array of frequencies) and `.../t{k}/reliability_index` (rank_histogram_kernel)."""
-        from .metrics import eval_ensemble_predictions, eval_ensemble_size_curves, eval_rank_histograms
+        array of frequencies) and `.../t{k}/reliability_index` (rank_histogram_kernel), and with `energy_score` `.../t{k}/es`,
+        `.../t{k}/es_fair`, their `avg/` and per channel `.../t{k}/c{j}/es` (energy_score_kernel)."""
+        from .metrics import eval_energy_scores, eval_ensemble_predictions, eval_ensemble_size_curves, eval_rank_histograms
         n = self.hparams.num_predictions
         if n <= 1 or not outputs:  # use_ensemble_predictions(split), :497-498
             return {}
@@ -349,6 +354,8 @@ class MultiHorizonForecastingDYffusion(nn.Module):
             out.update(eval_ensemble_size_curves(results, self.model._engine, split=split))
         if self.rank_histogram:
             out.update(eval_rank_histograms(results, self.model._engine, split=split, infix=self.ensemble_logging_infix(split)))
+        if self.energy_score:
+            out.update(eval_energy_scores(results, self.model._engine, split=split, infix=self.ensemble_logging_infix(split)))
         return out
 
     def on_validation_epoch_end(self) -> Dict[str, float]:

@@ -7,7 +7,8 @@ every member's own MSE) in `ensemble_size_metrics_kernel` through `dyf_ensemble_
 other contiguous run of kept axes (`mean_dims`), together with the Gaussian NLL and the correlation, in `ensemble_scores_kernel`
 through `dyf_ensemble_scores`.  The forecast fields themselves (mean, spread, quantiles, exceedance probabilities per grid point) come
 from `ensemble_products_kernel` through `dyf_ensemble_products`, the rank histogram from `rank_histogram_kernel` through
-`dyf_rank_histogram`.  There is no CPU fallback."""
+`dyf_rank_histogram`.  The multivariate side -- the energy score over whole fields or channels and the member-distance matrix -- comes
+from `energy_score_kernel` through `dyf_energy_score`.  There is no CPU fallback."""
 import math
 from collections import defaultdict
 from typing import Dict, Optional, Sequence, Tuple
@@ -21,6 +22,7 @@ from .engine import HipEngine
 METRIC_ROWS = ("mse", "ssr", "crps")  # row order of the (3, T) tensors of HipEngine.trajectory_metrics
 SIZE_ROWS = METRIC_ROWS + ("mse_per_mem",)  # plane order of the (4, T, N) tensors of HipEngine.ensemble_size_metrics
 SCORE_ROWS = ("mse", "ssr", "crps", "nll", "corr")  # plane order of the (5, T, G) tensors of HipEngine.ensemble_scores
+ENERGY_ROWS = ("es", "es_fair", "dist_target", "dist_pair")  # plane order of the (4, T, G) tensors of HipEngine.energy_score
 
 
 def evaluate_ensemble_prediction(predictions: Tensor, targets: Tensor, engine: HipEngine, mean_over_samples: bool = True,
@@ -260,6 +262,85 @@ def eval_rank_histograms(results: Dict[str, Tensor], engine: HipEngine, split: s
     return out
 
 
+def _energy_inputs(predictions, targets, per_channel: bool):
+    """(prediction list, target list, lists were given, (outer, groups, inner)) for the energy score of (N, B, C, *spatial) forecasts:
+    one vector per sample (the whole field), or per sample and channel."""
+    many = not torch.is_tensor(predictions)
+    plist, tlist = (list(predictions), list(targets)) if many else ([predictions], [targets])
+    if many and (len(plist) != len(tlist) or not plist):
+        raise ValueError(f"{len(plist)} prediction horizons but {len(tlist)} target horizons")
+    for p, t in zip(plist, tlist):
+        if p.shape[1] != t.shape[0]:
+            raise AssertionError(f"predictions.shape[1] ({p.shape[1]}) != targets.shape[0] ({t.shape[0]})")
+        if not p.is_cuda or not t.is_cuda:
+            raise ValueError("dyffusion_amd.metrics works on GPU tensors (the HIP engine computes them)")
+    return plist, tlist, many, _field_group_shape(tuple(tlist[0].shape), per_channel)
+
+
+def _field_group_shape(tshape: Sequence[int], per_channel: bool) -> Tuple[int, int, int]:
+    """(B, 1, C * spatial) or (B, C, spatial) of targets (B, C, *spatial); without a channel axis (at most two axes) the one channel
+    is everything behind the sample axis."""
+    b = tshape[0]
+    c = tshape[1] if per_channel and len(tshape) >= 3 else 1
+    return b, c, math.prod(tshape) // (b * c)
+
+
+def evaluate_ensemble_energy_score(predictions, targets, engine: HipEngine, per_channel: bool = False) -> Dict[str, object]:
+    """The energy score of an ensemble of fields, the multivariate CRPS: {"es", "es_fair", "dist_target", "dist_pair"} (ENERGY_ROWS)
+    in one pass of `energy_score_kernel`.  predictions (n_members, B, C, *spatial), targets (B, C, *spatial), on the engine's GPU.
+    Every sample's whole field is one vector and the scores are means over the samples: host floats; with `per_channel` every
+    (sample, channel) is a vector and each score is a float64 device tensor (C,), nothing synchronised.  es = E||x - y|| - (N - 1) /
+    (2 N) E||x - x'|| (1 / N^2 weights, as the engine's CRPS), es_fair divides the pair sum by N (N - 1) instead.  Lists of equally
+    shaped horizons go through as the segments of one call and give a leading axis (host arrays when not per channel)."""
+    plist, tlist, many, group_shape = _energy_inputs(predictions, targets, per_channel)
+    out = engine.energy_score(plist, tlist, group_shape=group_shape)  # (4, T, G)
+    if per_channel:
+        return {m: (out[i] if many else out[i, 0]) for i, m in enumerate(ENERGY_ROWS)}
+    host = out[:, :, 0].cpu().numpy()
+    return {m: (host[i] if many else float(host[i, 0])) for i, m in enumerate(ENERGY_ROWS)}
+
+
+def evaluate_member_distances(predictions, targets, engine: HipEngine, per_channel: bool = False) -> Dict[str, Tensor]:
+    """The ensemble-diversity diagnostics behind the energy score, as float64 device tensors (nothing synchronised): {"member_dist":
+    (N,) every member's Euclidean distance to the truth (its multivariate skill), "pair_dist": (N, N) the distances between the
+    members (symmetric, zero diagonal: which members collapsed onto each other, which is the outlier)}, means over the samples of
+    the whole-field distances; with `per_channel` (C, N) and (C, N, N).  Inputs as `evaluate_ensemble_energy_score`; lists of
+    horizons give a leading axis."""
+    plist, tlist, many, group_shape = _energy_inputs(predictions, targets, per_channel)
+    _, mats = engine.energy_score(plist, tlist, group_shape=group_shape, members=True, pairs=True)
+    out = {}
+    for k, v in mats.items():  # (T, G, ...)
+        v = v if per_channel else v[:, 0]
+        out[k] = v if many else v[0]
+    return out
+
+
+def eval_energy_scores(results: Dict[str, Tensor], engine: HipEngine, split: str = "val", infix: Optional[str] = None) -> Dict[str, float]:
+    """`{split}/{infix}t{k}/es` and `.../es_fair` (whole-field energy scores, means over the samples) for every `t{k}_preds` /
+    `t{k}_targets` pair of an evaluation step's output, their means over the horizons `{split}/{infix}avg/...`, and per channel j of
+    (B, C, ...) targets `{split}/{infix}t{k}/c{j}/es`; horizons of equal shape are the segments of one `energy_score` call each."""
+    infix = "" if infix is None else infix
+    shapes: Dict[tuple, list] = {}
+    for prefix, key, tkey in _horizon_pairs(results):
+        shapes.setdefault((tuple(results[key].shape), tuple(results[tkey].shape)), []).append((prefix, key, tkey))
+    out: Dict[str, float] = {}
+    acc = defaultdict(list)
+    for (_, tshape), members in shapes.items():
+        plist, tlist = [results[k] for _, k, _ in members], [results[t] for _, _, t in members]
+        field = engine.energy_score(plist, tlist, group_shape=_field_group_shape(tshape, False)).cpu().numpy()  # (4, segments, 1)
+        per_c = engine.energy_score(plist, tlist, group_shape=_field_group_shape(tshape, True)).cpu().numpy()  # (4, segments, C)
+        for s, (prefix, _, _) in enumerate(members):
+            for m in ("es", "es_fair"):
+                v = float(field[ENERGY_ROWS.index(m), s, 0])
+                out[f"{split}/{infix}{prefix}/{m}"] = v
+                acc[f"{split}/{infix}avg/{m}"].append(v)
+            for j in range(per_c.shape[2]):
+                out[f"{split}/{infix}{prefix}/c{j}/es"] = float(per_c[0, s, j])
+    for k, v in acc.items():
+        out[k] = float(sum(v) / len(v))
+    return out
+
+
 def _horizon_pairs(results: Dict[str, Tensor]):
     """(prefix, predictions key, targets key) of every `t{k}_preds` / `t{k}_targets` pair, in the order of `results`."""
     for key in [k for k in results if k.endswith("preds")]:
@@ -330,8 +411,9 @@ class TrajectoryMetricsAccumulator:
     the curves mse / ssr / crps over its T horizon steps, the epoch reports their mean over instances.  The sum of the curves
     stays on the device ((3, T) float64, added to by the kernel itself); `compute()` makes the only device-to-host copy."""
 
-    def __init__(self, engine: HipEngine, by_size: bool = False, rank_histogram: bool = False):
+    def __init__(self, engine: HipEngine, by_size: bool = False, rank_histogram: bool = False, energy_score: bool = False):
         self._engine = engine
+        self._energy_score = energy_score  # also the (4, T, 1) sum of the whole-field energy scores (HipEngine.energy_score)
         self._by_size = by_size  # also the (4, T, N) sum of the ensemble-size curves (HipEngine.ensemble_size_metrics)
         self._rank_histogram = rank_histogram  # also the (T, 1, N + 1) sum of the pooled rank histograms (HipEngine.rank_histogram)
         self.reset()
@@ -340,6 +422,7 @@ class TrajectoryMetricsAccumulator:
         self._sum: Optional[Tensor] = None
         self._size_sum: Optional[Tensor] = None
         self._hist_sum: Optional[Tensor] = None
+        self._energy_sum: Optional[Tensor] = None
         self.count = 0
 
     def update(self, preds_list: Sequence[Tensor], targets_list: Sequence[Tensor]) -> Tensor:
@@ -366,13 +449,19 @@ class TrajectoryMetricsAccumulator:
             elif n + 1 != self._hist_sum.shape[2]:
                 raise ValueError(f"{n} members, but the accumulated rank histograms have {self._hist_sum.shape[2] - 1}")
             self._engine.rank_histogram(preds_list, targets_list, accum=self._hist_sum)
+        if self._energy_score:  # one vector per sample of the instance: its whole field
+            if self._energy_sum is None:
+                self._energy_sum = torch.zeros(4, len(preds_list), 1, dtype=torch.float64, device=preds_list[0].device)
+            self._engine.energy_score(preds_list, targets_list, group_shape=_field_group_shape(tuple(targets_list[0].shape), False),
+                                      accum=self._energy_sum)
         self.count += 1
         return curves
 
     def compute(self) -> Dict[str, np.ndarray]:
         """{metric: (T,) float64 array}: the mean over the instances seen since the last reset ({} before the first update); with
         `by_size` also "by_size": the (4, T, N) mean of the ensemble-size curves (planes SIZE_ROWS); with `rank_histogram` also
-        "rank_hist": the (T, N + 1) frequencies of the rank histograms summed over the instances."""
+        "rank_hist": the (T, N + 1) frequencies of the rank histograms summed over the instances; with `energy_score` also "es": the
+        (T,) mean of the instances' whole-field energy scores."""
         if self._sum is None or self.count == 0:
             return {}
         mean = self._sum.cpu().numpy() / float(self.count)
@@ -381,6 +470,8 @@ class TrajectoryMetricsAccumulator:
             out["by_size"] = self._size_sum.cpu().numpy() / float(self.count)
         if self._hist_sum is not None:
             out["rank_hist"] = rank_histogram_frequencies(self._hist_sum[:, 0].cpu().numpy())[0]
+        if self._energy_sum is not None:
+            out["es"] = self._energy_sum[ENERGY_ROWS.index("es"), :, 0].cpu().numpy() / float(self.count)
         return out
 
 

@@ -383,6 +383,44 @@ dyf_status dyf_ensemble_products(dyf_engine* engine, int32_t n_segments, const f
 dyf_status dyf_rank_histogram(dyf_engine* engine, int32_t n_segments, const float* const* preds_dev, const float* const* targets_dev,
                               int32_t n_members, int64_t n_points, int64_t member_stride, int64_t n_outer, int32_t n_groups,
                               int64_t n_inner, double* out_dev, double* accum_dev, void* stream);
+/* The energy score and the member-distance matrix per (segment, GROUP): the multivariate companion of the CRPS, |.| replaced by the
+ * Euclidean norm over a whole VECTOR of points, so that an ensemble of coherent fields scores better than one with the same
+ * per-point spread and scrambled members.  Segments, member_stride, the two host arrays of device pointers and the group geometry
+ * (n_outer, n_groups, n_inner) exactly as in dyf_ensemble_scores; a vector is one (outer o, group g) slab of n_inner contiguous
+ * points: (B, 1, C * H * W) scores whole fields, (B, C, H * W) every channel, (points, 1, 1) degenerates to the CRPS of
+ * dyf_trajectory_metrics (1 / N and 1 / N^2 weights).  Per vector, members x_0 .. x_{N-1}, target y:
+ *   d_i = ||x_i - y||_2        D_ij = ||x_i - x_j||_2
+ * out_dev (device, [4][n_segments][n_groups] doubles) receives per (segment, group), every mean over o taken first:
+ *   dist_target (plane 2)  mean_o (1 / N) sum_i d_i              dist_pair (plane 3)  mean_o 1 / (N (N - 1)) sum_{i != j} D_ij
+ *   es (plane 0)           dist_target - (N - 1) / (2 N) dist_pair    (N = 1: dist_target; the second term is dropped)
+ *   es_fair (plane 1)      dist_target - dist_pair / 2
+ * member_out_dev (device, [n_segments][n_groups][N], or NULL) receives mean_o d_i, pair_out_dev (device,
+ * [n_segments][n_groups][N][N], or NULL) mean_o D_ij: bitwise symmetric, the diagonal exactly 0; accum_dev (device, the shape of
+ * out_dev, or NULL) += out.
+ *   Stated arithmetic: diff = x_i[p] - x_j[p] (x_i[p] - y[p]) in fp32; the squares accumulate in fp32 (fmaf, in point order) over the
+ * points of one tile, DYF_ENERGY_TILE_POINTS consecutive points of the vector; the tile sums are added in float64, in tile order
+ * (where a vector is split, over each chunk's consecutive tiles, then over the chunks in chunk order); sqrt in float64, once per
+ * vector, after all its tiles; the means over o, then over the members (index order) and the pairs (row i: j = i + 1 .. N - 1 in
+ * order, then the rows in order) in float64.  The differences are taken directly: no Gram-matrix form, nothing cancels for close
+ * members.  IEEE behaviour as numpy: a NaN in member i of a vector makes d_i and D_i. of its (segment, group) NaN and with them the
+ * four planes; other (segment, group) entries are untouched; identical members give exactly 0.0; N = 1 gives es = d_1 and NaN in
+ * dist_pair and es_fair.
+ *   Three launches on `stream`, no atomics, nothing exchanged between workgroups inside a launch: identical calls give identical
+ * bits, and a segment's values depend on its own data, n_members and the geometry alone (not on the other segments or their order).
+ * A vector is split over at most C = min(tiles, max(1, 256 / (vectors x block pairs))) workgroups (chunks of equally many consecutive
+ * tiles), and only where a segment has fewer than 256 work items (vectors = n_outer x n_groups, tiles = ceil(n_inner / DYF_ENERGY_TILE_POINTS), block pairs = B (B + 1) / 2 with B =
+ * ceil(N / 64)).  Engine-owned workspace, grown on demand: at most n_segments x vectors x C x N x (N + 1) doubles of partial sums of squares
+ * (never of square roots) and n_segments x n_groups x N x (N + 1) doubles of mean distances; a call that would need more than
+ * DYF_ENERGY_MAX_WORKSPACE_DOUBLES is DYF_ERR_UNSUPPORTED, before anything is launched.  Does NOT synchronise.  n_members in
+ * [1, DYF_ENERGY_MAX_MEMBERS] (DYF_ERR_UNSUPPORTED beyond), n_segments in [1, 65535]; n_inner >= 1 is arbitrary.  The kernel reads
+ * fp32 only: both builds of the library give the same bits.  (Additive: no ABI change.) */
+#define DYF_ENERGY_TILE_POINTS 64
+#define DYF_ENERGY_MAX_MEMBERS 256
+#define DYF_ENERGY_MAX_WORKSPACE_DOUBLES 134217728 /* 2^27: 1 GiB */
+dyf_status dyf_energy_score(dyf_engine* engine, int32_t n_segments, const float* const* preds_dev, const float* const* targets_dev,
+                            int32_t n_members, int64_t n_points, int64_t member_stride, int64_t n_outer, int32_t n_groups,
+                            int64_t n_inner, double* out_dev, double* member_out_dev, double* pair_out_dev, double* accum_dev,
+                            void* stream);
 /* Copy one (NB,C,H,W) field of the sampler's state after the most recent dyf_sample call: what sample_loop returns
  * beside the intermediates (dyffusion.py:424-426): (x0_hat, ., x_s), or (x_s, ., x_interpolated_s_next) when the sampling
  * schedule stops before T-1. */
