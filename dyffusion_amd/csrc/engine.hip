@@ -461,8 +461,11 @@ dyf_status dyf_engine_create(const dyf_engine_config* cfg, dyf_engine** out_engi
             return bail(DYF_ERR_UNSUPPORTED, "input_dropout > 0: arch simple_conv_net has no such layer");
         if (n.cfg.dropout < 0.0f || n.cfg.dropout >= 1.0f) return bail(DYF_ERR_INVALID_ARGUMENT, "dropout must be in [0, 1)");
         n.cin_total = n.cfg.in_channels + n.cfg.cond_channels;
-        if (n.cin_total < 1 || n.cin_total > DYF_MAX_IN_CH || n.cfg.out_channels < 1 || n.cfg.out_channels > DYF_MAX_OUT_CH)
-            return bail(DYF_ERR_UNSUPPORTED, "channel counts outside the supported range (inputs+cond <= 32, outputs <= 8)");
+        // DYF_MAX_IN_CH is the limit of the U-Nets' stem kernels.  SimpleConvNet has no stem: its input is packed to NHWC and enters
+        // block 0, a conv like the others, at any channel count -- with inputs + cond == dim that block has a residual
+        const bool has_stem = n.cfg.arch != DYF_ARCH_SIMPLE_CONV_NET;
+        if (n.cin_total < 1 || (has_stem && n.cin_total > DYF_MAX_IN_CH) || n.cfg.out_channels < 1 || n.cfg.out_channels > DYF_MAX_OUT_CH)
+            return bail(DYF_ERR_UNSUPPORTED, "channel counts outside the supported range (inputs+cond <= 32 in front of a stem, outputs <= 8)");
         n.dim = n.cfg.dim;
         n.tdim = 2 * n.cfg.dim;
         if (n.cfg.arch == DYF_ARCH_UNET_RESNET) {
