@@ -243,6 +243,7 @@ SYMBOLS = [
     ("dyf_op_linear_attention_fused", C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P]),
     ("dyf_op_attention", C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P]),
     ("dyf_op_attention_dropout", C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_float, _P, _P]),
+    ("dyf_op_attention_mask", C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_float, _P, _P, _P]),
     ("dyf_op_attention_f32", C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_float, _P, C.c_int32, _P, _P]),
     ("dyf_op_train_f32", C.c_int, [_P, C.POINTER(TrainOp), C.POINTER(_P), C.POINTER(_P), _P, _P, C.POINTER(_P), C.POINTER(_P), _P]),
     ("dyf_op_sample16", C.c_int, [_P, C.POINTER(SampleOp), C.POINTER(SampleTensors), C.POINTER(_P), _P]),

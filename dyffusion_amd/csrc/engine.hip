@@ -2668,6 +2668,29 @@ dyf_status dyf_op_attention_dropout(dyf_engine* e, const uint16_t* qkv_dev, int3
     return DYF_OK;
 }
 
+// injected masks (DropSpec mode 2) on the 16-bit core: the AttnArgs of dyf_op_attention_dropout with the caller's keep mask in place of
+// the engine's generator -- nothing is armed, the forward counter does not move, and the attention-dropout mode is not read
+dyf_status dyf_op_attention_mask(dyf_engine* e, const uint16_t* qkv_dev, int32_t n, int32_t hw, float p, const uint8_t* mask_dev,
+                                 uint16_t* out_dev, void* stream) {
+    auto bad = [&](const char* m) { return fail(e, DYF_ERR_INVALID_ARGUMENT, std::string("dyf_op_attention_mask: ") + m); };
+    if (!e || !qkv_dev || !out_dev || n < 1 || hw < 1) return bad("bad arguments");
+    if (!mask_dev) return bad("no mask (dyf_op_attention_dropout draws from the engine's generator, dyf_op_attention runs without dropout)");
+    if (!(p > 0.0f && p < 1.0f)) return bad("p must lie in (0, 1): survivors are scaled by 1 / (1 - p), and p = 0 launches the dropout-free kernels");
+    if ((unsigned long long)n * 4ull * (unsigned long long)hw * (unsigned long long)hw > 0xFFFFFFFFull)  // what a test can allocate, far inside size_t
+        return fail(e, DYF_ERR_UNSUPPORTED, "dyf_op_attention_mask: a keep mask of more than 2^32 - 1 bytes");
+    HIP_TRY(e, hipSetDevice(e->cfg.device));
+    hipStream_t st = (hipStream_t)stream;
+    AttnArgs a{};
+    a.qkv = qkv_dev; a.n = n; a.hw = hw; a.heads = 4; a.out = out_dev; a.drop = DropSpec{};
+    a.drop.mode = 2;
+    a.drop.scale = 1.0f / (1.0f - p);
+    a.drop.mask = mask_dev;
+    hipError_t err = launch_attention(a, st);
+    if (err == hipSuccess) err = hipStreamSynchronize(st);
+    if (err != hipSuccess) return fail(e, DYF_ERR_HIP, std::string("dyf_op_attention_mask: ") + hipGetErrorString(err));
+    return DYF_OK;
+}
+
 dyf_status dyf_op_attention_f32(dyf_engine* e, const float* qkv_dev, int32_t n, int32_t hw, float p, const uint8_t* mask_dev, int32_t form,
                                 float* out_dev, void* stream) {
     if (!e || !qkv_dev || !out_dev || n < 1 || hw < 1 || p < 0.0f || p >= 1.0f || (form != 0 && form != 1) || (mask_dev && p <= 0.0f))

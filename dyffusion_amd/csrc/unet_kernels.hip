@@ -2250,6 +2250,7 @@ hipError_t launch_attention(const AttnArgs& a, hipStream_t s) {
         dyf_form_note("attention_kernel<exact>", a.n);
         hipLaunchKernelGGL(attention_kernel<true>, dim3(a.n * a.heads * qtiles), dim3(64), 0, s, a);
     } else {
+        dyf_form_note("attention_kernel", a.n);
         hipLaunchKernelGGL(attention_kernel<false>, dim3(a.n * a.heads * qtiles), dim3(64), 0, s, a);
     }
     return hipGetLastError();

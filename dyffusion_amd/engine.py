@@ -1090,12 +1090,17 @@ class HipEngine:
     def torch_dtype(self) -> torch.dtype:
         return torch.float16 if L.DTYPES[L.storage_dtype(self.dtype)] else torch.bfloat16
 
-    def op_attention(self, qkv: torch.Tensor, p_drop: float = 0.0) -> torch.Tensor:
+    def op_attention(self, qkv: torch.Tensor, p_drop: float = 0.0, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Test seam: Attention core.  qkv (N,HW,384) in the engine's 16-bit dtype (to_qkv output) -> (N,HW,128); p_drop > 0:
-        dropout on the probabilities from the engine's generator, in the engine's `attention_dropout` mode."""
+        dropout on the probabilities from the engine's generator, in the engine's `attention_dropout` mode -- or, with `mask`
+        (N,4,HW,HW) uint8, on the caller's keep mask (dyf_op_attention_mask: survivors scaled by 1 / (1 - p_drop))."""
         assert qkv.dtype == self.torch_dtype and qkv.is_cuda and qkv.is_contiguous() and qkv.shape[2] == 384
         n, hw, _ = qkv.shape
         y = torch.empty((n, hw, 128), dtype=qkv.dtype, device=qkv.device)
+        if mask is not None:
+            assert mask.dtype == torch.uint8 and mask.is_cuda and mask.is_contiguous() and tuple(mask.shape) == (n, 4, hw, hw)
+            self._check(self._lib.dyf_op_attention_mask(self._h, qkv.data_ptr(), n, hw, float(p_drop), mask.data_ptr(), y.data_ptr(), self._stream()))
+            return y
         self._check(self._lib.dyf_op_attention_dropout(self._h, qkv.data_ptr(), n, hw, float(p_drop), y.data_ptr(), self._stream()))
         return y
 

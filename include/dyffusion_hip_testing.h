@@ -188,6 +188,13 @@ dyf_status dyf_op_attention(dyf_engine* engine, const uint16_t* qkv_dev, int32_t
  * the exact mode more than 32 767 tokens are refused with DYF_ERR_UNSUPPORTED before anything is launched. */
 dyf_status dyf_op_attention_dropout(dyf_engine* engine, const uint16_t* qkv_dev, int32_t n, int32_t hw, float p, uint16_t* out_dev,
                                     void* stream);
+/* ... with the CALLER's keep mask (DropSpec mode 2, what dyf_net_forward's dropout_mode 2 hands the bottleneck): mask_dev
+ * (N,4,HW,HW) uint8, nonzero = keep, indexed ((row * 4 + head) * HW + query) * HW + key; survivors scaled by 1 / (1 - p), 0 < p < 1.
+ * The engine's generator and its attention-dropout mode are not involved.  What the call cannot express is refused with
+ * DYF_ERR_INVALID_ARGUMENT: a missing mask (the generator's masks: dyf_op_attention_dropout) and p outside (0, 1) (p = 0 is the
+ * dropout-free core: dyf_op_attention).  A mask of more than 2^32 - 1 bytes is DYF_ERR_UNSUPPORTED. */
+dyf_status dyf_op_attention_mask(dyf_engine* engine, const uint16_t* qkv_dev, int32_t n, int32_t hw, float p, const uint8_t* mask_dev,
+                                 uint16_t* out_dev, void* stream);
 /* The fp32 Attention core of fp32 sampling and the training step: qkv_dev (N,HW,384) fp32 -> out_dev (N,HW,128) fp32.  form 0: the
  * kernel that keeps its (tokens x tokens) probabilities, in scratch memory here (HW <= 4096, else DYF_ERR_UNSUPPORTED); form 1: the
  * streaming matrix-core kernel a sampling forward takes past 4096 tokens, at any HW <= 32 767.  p > 0 with mask_dev == NULL: dropout

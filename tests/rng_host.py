@@ -71,6 +71,34 @@ def mask_nchw(nb, shape_hwc, p, seed, fwd, layer, row_offset=0):
     return torch.from_numpy(np.stack(rows, 0).astype(np.uint8)).permute(0, 3, 1, 2).contiguous()
 
 
+def keep_threshold8(p):
+    """csrc/common.h:206-210 keep_threshold8: k = floor(fp32((1 - p) * 256)), at most 256, at least 1."""
+    keep = np.float32(np.float32(1.0) - np.float32(p)) * np.float32(256.0)
+    return max(1, 256 if keep >= 256.0 else int(keep))
+
+
+def attn_quad_keep(N, p, seed, fwd, site, grow):
+    """The QUAD form of the 16-bit Attention probability dropout (what a 16-bit engine draws unless the exact mode is on), for global
+    batch row `grow`: (keep bool (4, N, N) indexed [head, query, key], scale of the survivors).
+      * key: the row's site key (k0, k1) as in row_mask_nhwc (csrc/common.h:245-249 drop_row_key), the head folded into k0 --
+        csrc/unet_kernels.hip:1532-1536 attn_drop_key: k0' = fmix32(k0 + (h + 1) * 0x9E3779B9);
+      * element e = i * N + j modulo 2^32 (unet_kernels.hip:1551 attn_drop; :1713 and :1731 the two paths of flash_attention2_kernel;
+        :2045 / :2118 flash_attention4_kernel, which carries the Weyl value of quad e >> 2);
+      * keep iff byte e & 3 of pair_word(e >> 2, k0', k1) is below k = keep_threshold8(p) (csrc/common.h:220-223 rng_keep8);
+      * survivors scaled by 256 / k (DropSpec::scale8, csrc/common.h:236-237)."""
+    k = keep_threshold8(p)
+    r0, r1 = row_key(seed, fwd, grow)
+    s0, s1 = layer_salt(site)
+    k0, k1 = r0 ^ s0, (r1 + s1) & M32
+    e = (np.arange(N, dtype=np.uint64)[:, None] * np.uint64(N) + np.arange(N, dtype=np.uint64)[None, :]) & M32
+    keep = np.empty((4, N, N), dtype=bool)
+    for h in range(4):
+        kh = fmix32((k0 + np.uint64(h + 1) * np.uint64(0x9E3779B9)) & M32)
+        w = pair_word(e >> np.uint64(2), kh, k1)
+        keep[h] = ((w >> (np.uint64(8) * (e & np.uint64(3)))) & np.uint64(0xFF)) < np.uint64(k)
+    return keep, 256.0 / k
+
+
 NOISE_SALT = 0x4E6F6973  # csrc/kernels.hip noisy_condition_kernel: the noise stream's row keys take seed_hi ^ this
 
 

@@ -262,10 +262,11 @@ torch.save(y, {out!r})
 
 
 def test_flash_attention_engine_dropout_draws_the_masks_of_the_plain_kernel(tmp_path, form_switch):
-    """Attention-probability dropout from the engine's generator: the flash kernel hashes one keep word per PAIR of keys
-    (16 x 16 = 256 tokens: both query blocks are whole, the paired form runs), the plain kernel (DYF_FLASH_ATTN=0) evaluates
-    `rng_keep(q * N + j)` per element.  Same seed -> the same masks, so the outputs agree to rounding (different masks at
-    p = 0.3 would differ by tens of percent).  The kernel form is chosen once per process: two subprocesses."""
+    """Attention-probability dropout from the engine's generator, the quad form: the flash kernels hash one keep word per FOUR
+    consecutive keys of a query and compare its bytes with keep_threshold8 (16 x 16 = 256 tokens: every query block and key tile
+    is whole, so the word-per-quad paths run), the plain kernel (DYF_FLASH_ATTN=0) evaluates `rng_keep8(q * N + j)` per element.
+    Same seed -> the same masks, so the outputs agree to rounding (different masks at p = 0.3 would differ by tens of percent).
+    The switch travels to a child process per form (form_switch.env); tests/test_gpu_attention_core.py reads the masks themselves."""
     import subprocess
     import sys as _sys
     root = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
