@@ -137,6 +137,8 @@ MAX_PRODUCT_QUANTILES = MAX_PRODUCT_THRESHOLDS = 16  # DYF_MAX_PRODUCT_QUANTILES
 ENERGY_TILE_POINTS = 64  # DYF_ENERGY_TILE_POINTS: the fp32 accumulation length of dyf_energy_score
 ENERGY_MAX_MEMBERS = 256  # DYF_ENERGY_MAX_MEMBERS
 ENERGY_MAX_WORKSPACE_DOUBLES = 1 << 27  # DYF_ENERGY_MAX_WORKSPACE_DOUBLES
+SPECTRUM_MAX_DIM = 1024  # DYF_SPECTRUM_MAX_DIM: the largest transform length of dyf_power_spectrum
+SPECTRUM_MAX_MEMBERS = 256  # DYF_SPECTRUM_MAX_MEMBERS
 BC_NAVIER_STOKES, BC_SPRING_MESH = 0, 1
 COMM_ID_BYTES = 128  # DYF_COMM_ID_BYTES (ncclUniqueId)
 TRAIN_BATCH_STATS, TRAIN_DROPOUT = 1, 2
@@ -231,6 +233,8 @@ SYMBOLS = [
                                      C.c_int64, _P, _P, _P]),
     ("dyf_energy_score", C.c_int, [_P, C.c_int32, C.POINTER(_P), C.POINTER(_P), C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int32,
                                    C.c_int64, _P, _P, _P, _P, _P]),
+    ("dyf_power_spectrum", C.c_int, [_P, C.c_int32, C.POINTER(_P), C.POINTER(_P), C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                     C.c_int32, C.c_int32, _P, _P, _P]),
     ("dyf_time_layer_in_rollout", C.c_int, [_P, C.c_int32, C.c_int32, _P, C.POINTER(C.c_double), C.POINTER(C.c_int32)]),
     ("dyf_time_kernel_in_rollout", C.c_int, [_P, C.c_int32, C.c_int32, _P, C.POINTER(C.c_double), C.POINTER(C.c_int32),
                                              C.POINTER(C.c_double), C.POINTER(C.c_double)]),

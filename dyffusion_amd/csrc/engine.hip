@@ -1800,7 +1800,15 @@ dyf_status dyf_ensemble_metrics(dyf_engine* e, const float* preds_dev, const flo
         dyf_status s = dev_alloc(e, &e->metric_sums, 4);
         if (s != DYF_OK) return s;
     }
-    HIP_TRY(e, launch_ensemble_metrics(preds_dev, targets_dev, n_members, n_points, e->metric_sums, st));
+    const size_t need = (size_t)ensemble_metrics_partial_doubles(n_members, n_points);
+    if (need > e->metric_partials_count) {  // this entry is synchronous: nothing of an earlier call still reads the old buffer
+        if (e->metric_partials) (void)hipFree(e->metric_partials);
+        e->metric_partials = nullptr;
+        e->metric_partials_count = 0;
+        HIP_TRY(e, hipMalloc((void**)&e->metric_partials, need * sizeof(double)));
+        e->metric_partials_count = need;
+    }
+    HIP_TRY(e, launch_ensemble_metrics(preds_dev, targets_dev, n_members, n_points, e->metric_partials, e->metric_sums, st));
     double h[3];
     HIP_TRY(e, hipMemcpyAsync(h, e->metric_sums, sizeof(h), hipMemcpyDeviceToHost, st));
     HIP_TRY(e, hipStreamSynchronize(st));
@@ -1822,6 +1830,14 @@ static void traj_release(dyf_engine* e) {
     if (e->ens_scores_partials) (void)hipFree(e->ens_scores_partials);
     if (e->rank_hist_partials) (void)hipFree(e->rank_hist_partials);
     if (e->energy_partials) (void)hipFree(e->energy_partials);
+    if (e->spectrum_partials) (void)hipFree(e->spectrum_partials);
+    if (e->metric_partials) (void)hipFree(e->metric_partials);
+    e->metric_partials = nullptr;
+    e->metric_partials_count = 0;
+    for (PowerSpectrumTables& t : e->spectrum_tables) power_spectrum_tables_destroy(&t);
+    e->spectrum_tables.clear();
+    e->spectrum_partials = nullptr;
+    e->spectrum_partials_count = 0;
     if (e->traj_uploaded) (void)hipEventDestroy(e->traj_uploaded);
     if (e->traj_done) (void)hipEventDestroy(e->traj_done);
     e->traj_tab = e->traj_stage = nullptr;
@@ -2046,6 +2062,45 @@ dyf_status dyf_energy_score(dyf_engine* e, int32_t n_segments, const float* cons
     return traj_finish(e, launch_energy_score(e->traj_tab, e->traj_tab + n_segments, n_segments, n_members, member_stride, n_outer,
                                               n_groups, n_inner, e->energy_partials, out_dev, member_out_dev, pair_out_dev, accum_dev,
                                               st), st);
+}
+
+dyf_status dyf_power_spectrum(dyf_engine* e, int32_t n_segments, const float* const* preds_dev, const float* const* targets_dev,
+                              int32_t n_members, int64_t member_stride, int32_t batch, int32_t channels, int32_t height, int32_t width,
+                              int32_t window, double* out_dev, double* accum_dev, void* stream) {
+    if (!e || !preds_dev || !targets_dev || !out_dev) return fail(e, DYF_ERR_INVALID_ARGUMENT, "null argument");
+    if (batch < 1 || channels < 1 || height < 2 || width < 2)
+        return fail(e, DYF_ERR_INVALID_ARGUMENT, "batch and channels must be positive, height and width at least 2");
+    if (window != 0 && window != 1) return fail(e, DYF_ERR_INVALID_ARGUMENT, "window must be 0 (none) or 1 (Hann)");
+    if (height > POWER_SPECTRUM_MAX_DIM || width > POWER_SPECTRUM_MAX_DIM)
+        return fail(e, DYF_ERR_UNSUPPORTED, "height or width beyond DYF_SPECTRUM_MAX_DIM = " + std::to_string(POWER_SPECTRUM_MAX_DIM));
+    // batch * channels <= 2^62 and height * width <= 2^20: the product is formed only where it fits
+    const int64_t fields = (int64_t)batch * channels, hw = (int64_t)height * width;
+    if (fields > POWER_SPECTRUM_MAX_WORKSPACE)
+        return fail(e, DYF_ERR_UNSUPPORTED, "workspace beyond 2^27 = " + std::to_string(POWER_SPECTRUM_MAX_WORKSPACE) + " doubles");
+    dyf_status cs = traj_check_args(e, n_segments, preds_dev, targets_dev, n_members, POWER_SPECTRUM_MAX_MEMBERS, DYF_ERR_UNSUPPORTED,
+                                    fields * hw, member_stride, out_dev);
+    if (cs != DYF_OK) return cs;
+    PowerSpectrumPlan plan;
+    if (power_spectrum_plan(n_segments, n_members, batch, channels, height, width, &plan) != 0)
+        return fail(e, DYF_ERR_UNSUPPORTED, "workspace beyond 2^27 = " + std::to_string(POWER_SPECTRUM_MAX_WORKSPACE) +
+                                                " doubles (n_segments * batch * channels * (height * width / 2 + tiles * (4 * 16 * "
+                                                "ceil16(height) + 4 * (n_bins + 1))))");
+    HIP_TRY(e, hipSetDevice(e->cfg.device));
+    const PowerSpectrumTables* tab = nullptr;
+    for (const PowerSpectrumTables& t : e->spectrum_tables)
+        if (t.H == height && t.W == width) tab = &t;
+    if (!tab) {  // first call at this geometry: build the tables on the host and copy them (the one synchronous step)
+        PowerSpectrumTables t;
+        HIP_TRY(e, power_spectrum_tables_create(height, width, &t));
+        e->spectrum_tables.push_back(t);
+        tab = &e->spectrum_tables.back();
+    }
+    hipStream_t st = (hipStream_t)stream;
+    cs = traj_upload(e, n_segments, preds_dev, targets_dev, &e->spectrum_partials, &e->spectrum_partials_count,
+                     (size_t)(plan.mean_doubles + plan.plane_doubles + plan.partial_doubles), st);
+    if (cs != DYF_OK) return cs;
+    return traj_finish(e, launch_power_spectrum(e->traj_tab, e->traj_tab + n_segments, n_segments, n_members, member_stride, batch,
+                                                channels, height, width, window, *tab, e->spectrum_partials, out_dev, accum_dev, st), st);
 }
 
 dyf_status dyf_apply_boundary_conditions(dyf_engine* e, const dyf_bc_args* bc, float* preds_dev, void* stream) {

@@ -146,6 +146,8 @@ struct dyf_engine {
     hipStream_t cap_stream = nullptr;  // capture never runs on the caller's (possibly legacy default) stream
     // dyf_time_layer_in_rollout: events recorded around the conv of block prof_layer while a rollout runs eagerly
     double* metric_sums = nullptr;  // dyf_ensemble_metrics accumulators (device)
+    double* metric_partials = nullptr;  // dyf_ensemble_metrics: every wave's three sums (device, grown on demand, freed with the traj buffers)
+    size_t metric_partials_count = 0;
     // dyf_trajectory_metrics: device table [2][traj_cap] of segment pointers (predictions, then targets), its pinned host staging, the
     // per-workgroup partial sums (grown on demand), and two events: traj_uploaded behind the table's copy (the host waits for it before
     // it rewrites the staging), traj_done behind the second launch (the next call's stream waits for it before it rewrites the table)
@@ -162,6 +164,9 @@ struct dyf_engine {
     size_t rank_hist_partials_count = 0;
     double* energy_partials = nullptr;  // dyf_energy_score: likewise (partial sums of squares, then the mean distances)
     size_t energy_partials_count = 0;
+    double* spectrum_partials = nullptr;  // dyf_power_spectrum: likewise (xbar, the workgroups' coefficient planes, their shell sums)
+    size_t spectrum_partials_count = 0;
+    std::vector<PowerSpectrumTables> spectrum_tables;  // dyf_power_spectrum: one per (H, W) seen, kept until the engine is destroyed
     hipEvent_t traj_uploaded = nullptr, traj_done = nullptr;
     bool traj_pending = false;  // the two events have been recorded
     int prof_layer = -1;

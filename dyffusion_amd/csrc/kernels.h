@@ -207,9 +207,11 @@ inline int ensemble_tile_points(int n_members) {
     return (size_t)n_members * P * sizeof(float) > 60 * 1024 ? 0 : P;
 }
 // on-device ensemble metrics (evaluation.py:10-118): sums[3] (fp64, device) = {sum (mean-y)^2, sum var, sum crps} over n_points
-// points, member n at preds + n * n_points; up to 15 360 members (ensemble_tile_points)
-hipError_t launch_ensemble_metrics(const float* preds, const float* targets, int n_members, long long n_points, double* sums,
-                                   hipStream_t s);
+// points, member n at preds + n * n_points; up to 15 360 members (ensemble_tile_points).  Without atomics: launch 1 writes every
+// wave's three sums to partials[ensemble_metrics_partial_doubles()], launch 2 (one workgroup) adds them in a fixed order into sums
+long long ensemble_metrics_partial_doubles(int n_members, long long n_points);
+hipError_t launch_ensemble_metrics(const float* preds, const float* targets, int n_members, long long n_points, double* partials,
+                                   double* sums, hipStream_t s);
 // the same per-point quantities per segment (dyf_trajectory_metrics), without atomics: launch 1 writes one {se, var, crps} partial per
 // workgroup to partials[n_segments][trajectory_metrics_blocks()][3], launch 2 (one wave per segment) adds a segment's partials in a
 // fixed order and writes out[3][n_segments] = {mse, ssr, crps} (accum[3][n_segments] += out when given).  preds_tab / targets_tab:
@@ -293,6 +295,35 @@ int energy_score_plan(int n_segments, int n_members, long long n_outer, int n_gr
 hipError_t launch_energy_score(const float* const* preds_tab, const float* const* targets_tab, int n_segments, int n_members,
                                long long member_stride, long long n_outer, int n_groups, long long n_inner, double* workspace,
                                double* out, double* member_out, double* pair_out, double* accum, hipStream_t s);
+// the radially binned power spectra of an ensemble per (segment, channel) (dyf_power_spectrum; power_spectrum.hip), without atomics.
+// Launch 1 leaves xbar (fp32) in workspace[0 .. mean_doubles), launch 2 every workgroup's four float64 coefficient planes in
+// workspace + mean_doubles [workgroups][4][nky * 16][16] and its shell sums behind them [workgroups][4][n_bins + 1] (bin n_bins: the
+// corners), launch 3 writes out[n_segments][C][4][n_bins + 1] (last column: the plane's total; accum += out when given).
+constexpr int POWER_SPECTRUM_MAX_DIM = 1024;                  // DYF_SPECTRUM_MAX_DIM
+constexpr int POWER_SPECTRUM_MAX_MEMBERS = 256;               // DYF_SPECTRUM_MAX_MEMBERS
+constexpr long long POWER_SPECTRUM_MAX_WORKSPACE = 1LL << 27; // DYF_SPECTRUM_MAX_WORKSPACE_DOUBLES
+struct PowerSpectrumPlan {
+    int tiles;   // ceil((W / 2 + 1) / 16) tiles of kx columns
+    int nky;     // ceil(H / 16) tiles of ky rows
+    int n_bins;  // max(H, W) / 2 + 1
+    long long fields, workgroups;  // B * C; n_segments * fields * tiles
+    long long mean_doubles, plane_doubles, partial_doubles;  // the three regions of the workspace
+};
+// 0 = ok; 1 = bad arguments or a limit exceeded; -1 = the workspace would exceed POWER_SPECTRUM_MAX_WORKSPACE doubles
+int power_spectrum_plan(int n_segments, int n_members, int batch, int channels, int H, int W, PowerSpectrumPlan* plan);
+// the shell of coefficient (ky, kx) of an H x W transform by the exact integer rule (may be >= n_bins: a corner)
+int power_spectrum_bin(int H, int W, int ky, int kx);
+struct PowerSpectrumTables {  // per geometry, on the device: twiddles and Hann tables (float64 on the host, rounded to fp32), shell lists
+    int H = 0, W = 0;
+    float* tables = nullptr;             // cosW[W] sinW[W] cosH[H] sinH[H] winH[H] winW[W]
+    unsigned short* csr_idx = nullptr;   // [tiles][H * 16]
+    int* csr_off = nullptr;              // [tiles][n_bins + 2]
+};
+hipError_t power_spectrum_tables_create(int H, int W, PowerSpectrumTables* t);  // allocates and copies synchronously
+void power_spectrum_tables_destroy(PowerSpectrumTables* t);
+hipError_t launch_power_spectrum(const float* const* preds_tab, const float* const* targets_tab, int n_segments, int n_members,
+                                 long long member_stride, int batch, int channels, int H, int W, int window,
+                                 const PowerSpectrumTables& t, double* workspace, double* out, double* accum, hipStream_t s);
 
 // dyf_sample_gather: all-gather receive layout [world][slots][nb][row floats] -> [slots][total_rows][row] in global row order;
 // rank r owns the contiguous block of rows shard(r) (the first total_rows % world ranks one extra), its padding rows are dropped

@@ -1870,9 +1870,11 @@ __device__ __forceinline__ double ensemble_block_total(const double* wsum, int k
     return ((wsum[k] + wsum[K + k]) + wsum[2 * K + k]) + wsum[3 * K + k];
 }
 
-// dyf_ensemble_metrics: one segment, flat points, member stride n_points; {se, var, crps} summed over all points in fp64, wave
-// butterfly and one atomic per wave and quantity (unordered).
-__device__ __forceinline__ void ensemble_atomic_sum(const ensemble_point& pt, double* sums) {
+// dyf_ensemble_metrics: one segment, flat points, member stride n_points; {se, var, crps} summed over all points in fp64: a wave
+// butterfly, the wave's three sums to partials[blockIdx.x * 4 + wave][3], and ensemble_metrics_finish_kernel adds the waves' sums in a
+// fixed order.  No atomics: two evaluations of the same fields give the same bits (the epochs' tests compare them bit for bit; with
+// one unordered atomic per wave that held only while the waves happened to arrive in the same order).
+__device__ __forceinline__ void ensemble_wave_partial(const ensemble_point& pt, double* partials) {
     double d0 = pt.se, d1 = pt.var, d2 = pt.crps;
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
@@ -1881,29 +1883,47 @@ __device__ __forceinline__ void ensemble_atomic_sum(const ensemble_point& pt, do
         d2 += __shfl_xor(d2, off, 64);
     }
     if ((threadIdx.x & 63) == 0) {
-        atomicAdd(sums + 0, d0);
-        atomicAdd(sums + 1, d1);
-        atomicAdd(sums + 2, d2);
+        double* w = partials + ((long long)blockIdx.x * 4 + (threadIdx.x >> 6)) * 3;
+        w[0] = d0, w[1] = d1, w[2] = d2;
+    }
+}
+
+// One workgroup: thread t adds the wave sums t, t + 256, ... in order, then thread k < 3 adds the 256 thread sums of quantity k in
+// thread order.
+__global__ __launch_bounds__(256) void ensemble_metrics_finish_kernel(const double* partials, long long n_waves, double* sums) {
+    __shared__ double part[3][256];
+    double a[3] = {0.0, 0.0, 0.0};
+    for (long long i = threadIdx.x; i < n_waves; i += 256) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) a[k] += partials[i * 3 + k];
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) part[k][threadIdx.x] = a[k];
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        double s = 0.0;
+        for (int t = 0; t < 256; ++t) s += part[threadIdx.x][t];
+        sums[threadIdx.x] = s;
     }
 }
 
 __global__ __launch_bounds__(256) void ensemble_metrics_kernel(const float* preds, const float* targets, int n_members,
-                                                               long long n_points, double* sums) {
+                                                               long long n_points, double* partials) {
     extern __shared__ float xs[];  // [n_members][256]
     const long long p = (long long)blockIdx.x * 256 + threadIdx.x;
     ensemble_point pt = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
     if (p < n_points) pt = ensemble_point_reduce(preds + p, n_points, targets[p], n_members, xs);
-    ensemble_atomic_sum(pt, sums);
+    ensemble_wave_partial(pt, partials);
 }
 
 __global__ __launch_bounds__(256) void ensemble_metrics_tiled_kernel(const float* preds, const float* targets, int n_members,
-                                                                     long long n_points, double* sums, int P) {
+                                                                     long long n_points, double* partials, int P) {
     extern __shared__ float xs[];  // [n_members][P] members, then [2][256] partials
     const long long p0 = (long long)blockIdx.x * P;
     const int n_live = n_points - p0 < P ? (int)(n_points - p0) : P;
     bool holds;
-    ensemble_atomic_sum(ensemble_point_reduce_tiled(preds + p0, n_points, n_live, targets + p0, n_members, P, xs,
-                                                    xs + (size_t)n_members * P, holds), sums);
+    ensemble_wave_partial(ensemble_point_reduce_tiled(preds + p0, n_points, n_live, targets + p0, n_members, P, xs,
+                                                      xs + (size_t)n_members * P, holds), partials);
 }
 
 // Reduction of the training criterion (src/utilities/utils.py:201-212, reduction = "mean"): sum over all elements of
@@ -1977,19 +1997,25 @@ hipError_t launch_criterion_sum_det(const float* p, const float* t, long long co
     return hipGetLastError();
 }
 
-hipError_t launch_ensemble_metrics(const float* preds, const float* targets, int n_members, long long n_points, double* sums,
-                                   hipStream_t s) {
-    hipError_t e = hipMemsetAsync(sums, 0, 3 * sizeof(double), s);
-    if (e != hipSuccess) return e;
+long long ensemble_metrics_partial_doubles(int n_members, long long n_points) {
+    const int P = ensemble_tile_points(n_members);
+    return P == 0 ? 0 : (n_points + P - 1) / P * 12;  // four waves x three sums per workgroup
+}
+
+hipError_t launch_ensemble_metrics(const float* preds, const float* targets, int n_members, long long n_points, double* partials,
+                                   double* sums, hipStream_t s) {
     const int P = ensemble_tile_points(n_members);
     if (P == 0) return hipErrorInvalidValue;  // > 15 360 members
     const dim3 grid((unsigned)((n_points + P - 1) / P));
     if (n_members > 64)
         hipLaunchKernelGGL(ensemble_metrics_tiled_kernel, grid, dim3(256), ((size_t)n_members * P + 2 * 256) * sizeof(float), s, preds,
-                           targets, n_members, n_points, sums, P);
+                           targets, n_members, n_points, partials, P);
     else
         hipLaunchKernelGGL(ensemble_metrics_kernel, grid, dim3(256), (size_t)n_members * 256 * sizeof(float), s, preds, targets,
-                           n_members, n_points, sums);
+                           n_members, n_points, partials);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(ensemble_metrics_finish_kernel, dim3(1), dim3(256), 0, s, partials, (long long)grid.x * 4, sums);
     return hipGetLastError();
 }
 

@@ -695,6 +695,56 @@ class HipEngine:
         del keep  # as in trajectory_metrics
         return (out, extra) if extra else out
 
+    SPECTRUM_WINDOWS = {"none": 0, "hann": 1}
+
+    def power_spectrum(self, preds, targets, window: str = "none", accum: Optional[torch.Tensor] = None) -> dict:
+        """Radially binned power spectra per (segment, channel) on the device (dyf_power_spectrum).  `preds` is one (N, B, C, H, W)
+        tensor with `targets` (B, C, H, W), or lists of such tensors (the segments of one call, all of one shape).  A prediction
+        tensor whose members are each contiguous is read in place through its member stride (a slice of a larger stack is not
+        copied); anything else is made contiguous fp32 first.  `window` "hann" tapers every field with the separable Hann window.
+        Returns {"spread", "mean", "target", "error": float64 device tensors (S, C, n_bins), "total": (S, C, 4) the planes' sums over
+        ALL coefficients, the dropped corners included, "n_bins": max(H, W) // 2 + 1, "planes": the (S, C, 4, n_bins + 1) tensor the
+        others are views of}; `accum` (float64, the shape of "planes", on the device) += it.  The engine builds and keeps the
+        twiddle, taper and shell tables per (H, W) on first use; after that nothing synchronises.  H, W in [2, 1024], at most 256
+        members (NotImplementedError beyond)."""
+        if window not in self.SPECTRUM_WINDOWS:
+            raise ValueError(f"window must be one of {sorted(self.SPECTRUM_WINDOWS)}, not {window!r}")
+        if torch.is_tensor(preds) != torch.is_tensor(targets):
+            raise ValueError("preds and targets must both be lists or both be tensors")
+        plist, tlist = ([preds], [targets]) if torch.is_tensor(preds) else (list(preds), list(targets))
+        if len(plist) != len(tlist) or not plist:
+            raise ValueError(f"{len(plist)} prediction segments but {len(tlist)} target segments")
+        for p, t in zip(plist, tlist):
+            if p.dim() != 5 or p.shape[1:] != t.shape:
+                raise ValueError(f"predictions must be (N, B, C, H, W) with targets (B, C, H, W), not {tuple(p.shape)} and {tuple(t.shape)}")
+            if p.shape != plist[0].shape:
+                raise ValueError(f"segments differ in shape: {tuple(p.shape)} and {tuple(plist[0].shape)}")
+            if not p.is_cuda or not t.is_cuda:
+                raise ValueError("power_spectrum works on GPU tensors (the HIP engine computes them)")
+        n, b, c, h, w = plist[0].shape
+        if min(n, b, c) < 1:
+            raise ValueError("empty predictions")
+        points = b * c * h * w
+
+        def in_place(p):  # fp32, every member contiguous, members a fixed stride apart
+            return p.dtype == torch.float32 and p[0].is_contiguous() and (n == 1 or p.stride(0) >= points)
+        strides = {p.stride(0) if n > 1 else points for p in plist}
+        if not (all(in_place(p) for p in plist) and len(strides) == 1):
+            plist = [p.contiguous().float() for p in plist]
+            strides = {points}
+        tlist = [t.contiguous().float() for t in tlist]
+        nseg, dev = len(plist), plist[0].device
+        n_bins = max(h, w) // 2 + 1
+        accum_ptr = self._accum_ptr(accum, (nseg, c, 4, n_bins + 1), dev)
+        out = torch.empty(nseg, c, 4, n_bins + 1, dtype=torch.float64, device=dev)
+        self._check(self._lib.dyf_power_spectrum(self._h, nseg, (C.c_void_p * nseg)(*[p.data_ptr() for p in plist]),
+                                                 (C.c_void_p * nseg)(*[t.data_ptr() for t in tlist]), n, strides.pop(), b, c, h, w,
+                                                 self.SPECTRUM_WINDOWS[window], out.data_ptr(), accum_ptr, self._stream()))
+        del plist, tlist  # as in trajectory_metrics
+        res = {name: out[:, :, i, :n_bins] for i, name in enumerate(("spread", "mean", "target", "error"))}
+        res.update(total=out[:, :, :, n_bins], n_bins=n_bins, planes=out)
+        return res
+
     def time_layer_in_rollout(self, layer: int, nb: int):
         """(average ms, launches) of decoder block `layer`'s conv over one eagerly launched rollout of the current plan."""
         ms, cnt = C.c_double(), C.c_int32()

@@ -123,7 +123,8 @@ class MultiHorizonForecastingDYffusion(nn.Module):
                  autoregressive_steps: int = 0, prediction_horizon: Optional[int] = None, datamodule=None,
                  datamodule_config: Optional[Dict[str, Any]] = None, ensemble_size_curves: bool = False,
                  extended_metrics: bool = False, predict_products: Optional[Dict[str, Any]] = None, keep_members: bool = True,
-                 rank_histogram: bool = False, energy_score: bool = False):
+                 rank_histogram: bool = False, energy_score: bool = False, power_spectrum: bool = False,
+                 spectrum_window: str = "none"):
         super().__init__()
         assert autoregressive_steps >= 0, f"Autoregressive steps must be >= 0, but is {autoregressive_steps}"
         if autoregressive_steps > 0:
@@ -151,6 +152,10 @@ class MultiHorizonForecastingDYffusion(nn.Module):
         # also report the whole-field energy score (es, es_fair) of every horizon and es per channel at the end of validation / pooled
         # test epochs, and the instance-averaged es curve at the end of a physical-systems test epoch
         self.energy_score = energy_score
+        # also report the log-spectral distances (lsd, lsd_ens_mean, lsd per channel) of every horizon at the end of validation / pooled
+        # test epochs, from radially binned power spectra added over the batches on the device; "hann" tapers the fields first
+        self.power_spectrum = power_spectrum
+        self.spectrum_window = spectrum_window
         self._test_metrics_aggregate = None  # TrajectoryMetricsAccumulator of the physical-systems test epoch (first test_step)
         self._predict_step_outputs = []
 
@@ -337,8 +342,10 @@ class MultiHorizonForecastingDYffusion(nn.Module):
         first n members, n = 1..N-1 (ensemble_size_metrics_kernel), and with `extended_metrics` `.../t{k}/{nll|corr}` and the five
         scores per channel `.../t{k}/c{j}/{m}` (ensemble_scores_kernel), and with `rank_histogram` `.../t{k}/rank_hist` (an (N + 1,)
         array of frequencies) and `.../t{k}/reliability_index` (rank_histogram_kernel), and with `energy_score` `.../t{k}/es`,
-        `.../t{k}/es_fair`, their `avg/` and per channel `.../t{k}/c{j}/es` (energy_score_kernel)."""
-        from .metrics import eval_energy_scores, eval_ensemble_predictions, eval_ensemble_size_curves, eval_rank_histograms
+        `.../t{k}/es_fair`, their `avg/` and per channel `.../t{k}/c{j}/es` (energy_score_kernel), and with `power_spectrum` `.../t{k}/lsd`,
+        `.../t{k}/lsd_ens_mean`, their `avg/` and per channel `.../t{k}/c{j}/lsd` (power_spectrum_kernel)."""
+        from .metrics import (eval_energy_scores, eval_ensemble_predictions, eval_ensemble_size_curves, eval_power_spectra,
+                              eval_rank_histograms)
         n = self.hparams.num_predictions
         if n <= 1 or not outputs:  # use_ensemble_predictions(split), :497-498
             return {}
@@ -356,6 +363,9 @@ class MultiHorizonForecastingDYffusion(nn.Module):
             out.update(eval_rank_histograms(results, self.model._engine, split=split, infix=self.ensemble_logging_infix(split)))
         if self.energy_score:
             out.update(eval_energy_scores(results, self.model._engine, split=split, infix=self.ensemble_logging_infix(split)))
+        if self.power_spectrum:
+            out.update(eval_power_spectra(outputs, self.model._engine, split=split, infix=self.ensemble_logging_infix(split),
+                                          window=self.spectrum_window))
         return out
 
     def on_validation_epoch_end(self) -> Dict[str, float]:

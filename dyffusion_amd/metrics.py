@@ -8,7 +8,9 @@ other contiguous run of kept axes (`mean_dims`), together with the Gaussian NLL 
 through `dyf_ensemble_scores`.  The forecast fields themselves (mean, spread, quantiles, exceedance probabilities per grid point) come
 from `ensemble_products_kernel` through `dyf_ensemble_products`, the rank histogram from `rank_histogram_kernel` through
 `dyf_rank_histogram`.  The multivariate side -- the energy score over whole fields or channels and the member-distance matrix -- comes
-from `energy_score_kernel` through `dyf_energy_score`.  There is no CPU fallback."""
+from `energy_score_kernel` through `dyf_energy_score`; the scores by spatial scale -- radially binned power spectra and the log-spectral
+distances, spectral spread-skill ratio and coherence derived from them -- from `power_spectrum_kernel` through `dyf_power_spectrum`.
+There is no CPU fallback."""
 import math
 from collections import defaultdict
 from typing import Dict, Optional, Sequence, Tuple
@@ -338,6 +340,74 @@ def eval_energy_scores(results: Dict[str, Tensor], engine: HipEngine, split: str
                 out[f"{split}/{infix}{prefix}/c{j}/es"] = float(per_c[0, s, j])
     for k, v in acc.items():
         out[k] = float(sum(v) / len(v))
+    return out
+
+
+SPECTRUM_ROWS = ("spread", "mean", "target", "error")  # plane order of the (S, C, 4, n_bins + 1) tensor of HipEngine.power_spectrum
+
+
+def spectrum_diagnostics(planes: Tensor, n_members: int) -> Dict[str, Tensor]:
+    """What follows from the four spectra `planes` (..., 4, n_bins + 1) of `HipEngine.power_spectrum` (last column: the totals), all
+    float64 on the planes' device, nothing synchronised: the planes themselves (..., n_bins) and "total" (..., 4); "members" = spread +
+    mean, the mean power spectrum of the single members (exact: the anomalies sum to zero; a sum of positives); "spread_fair" = spread
+    N / (N - 1) (NaN for one member); "wavenumber" = arange(n_bins); "spectral_ssr"[k] = sqrt((N + 1) / N spread_fair / error), the
+    spread-skill ratio per scale; "coherence"[k] = (mean + target - error) / (2 sqrt(mean target)), the real coherence of ensemble
+    mean and truth per shell; "lsd" / "lsd_ens_mean" (...): the log-spectral distances in dB, sqrt(mean_k (10 log10(P / target))^2)
+    over the bins 1 .. n_bins - 1 with positive target power, P = members / P = mean."""
+    n_bins = planes.shape[-1] - 1
+    out = {name: planes[..., i, :n_bins] for i, name in enumerate(SPECTRUM_ROWS)}
+    out["total"] = planes[..., n_bins]
+    out["members"] = out["spread"] + out["mean"]
+    out["spread_fair"] = out["spread"] * (n_members / (n_members - 1.0) if n_members > 1 else float("nan"))
+    out["wavenumber"] = torch.arange(n_bins, device=planes.device)
+    out["spectral_ssr"] = torch.sqrt((n_members + 1.0) / n_members * out["spread_fair"] / out["error"])
+    out["coherence"] = (out["mean"] + out["target"] - out["error"]) / (2.0 * torch.sqrt(out["mean"] * out["target"]))
+    target = out["target"][..., 1:]
+    use = target > 0
+    for key, power in (("lsd", out["members"]), ("lsd_ens_mean", out["mean"])):
+        db = 10.0 * torch.log10(power[..., 1:] / torch.where(use, target, torch.ones_like(target)))
+        out[key] = torch.sqrt(torch.where(use, db * db, torch.zeros_like(db)).sum(-1) / use.sum(-1))
+    return out
+
+
+def evaluate_power_spectrum(predictions, targets, engine: HipEngine, window: str = "none") -> Dict[str, object]:
+    """The ensemble's scores by spatial scale, in one pass of `power_spectrum_kernel`: the radially binned power spectra "spread",
+    "mean", "target", "error" per channel and everything `spectrum_diagnostics` derives from them, plus the int "n_bins".
+    predictions (n_members, B, C, H, W), targets (B, C, H, W), on the engine's GPU: spectra (C, n_bins), "total" (C, 4), "lsd" (C,);
+    lists of equally shaped horizons go through as the segments of one call and give a leading axis.  `window` "hann" tapers the
+    (non-periodic) fields.  Everything stays on the device in float64; nothing is synchronised until the caller reads."""
+    many = not torch.is_tensor(predictions)
+    res = engine.power_spectrum(predictions, targets, window=window)
+    n = (predictions[0] if many else predictions).shape[0]
+    out: Dict[str, object] = spectrum_diagnostics(res["planes"] if many else res["planes"][0], n)
+    out["n_bins"] = res["n_bins"]
+    return out
+
+
+def eval_power_spectra(outputs: Sequence[Dict[str, Tensor]], engine: HipEngine, split: str = "val", infix: Optional[str] = None,
+                       window: str = "none") -> Dict[str, float]:
+    """`{split}/{infix}t{k}/lsd`, `.../lsd_ens_mean` (the log-spectral distances of the channel-mean spectra), their means over the
+    horizons `{split}/{infix}avg/...` and per channel j `{split}/{infix}t{k}/c{j}/lsd`, for every `t{k}_preds` / `t{k}_targets` pair of
+    an epoch's evaluation-step outputs.  The spectra of every batch are added on the device, weighted by the batch's samples (the
+    horizons of one batch are the segments of one `power_spectrum` call); the host reads once, at the end."""
+    infix = "" if infix is None else infix
+    pairs = list(_horizon_pairs(outputs[0]))
+    total, samples, n = None, 0, None
+    for o in outputs:
+        plist, tlist = [o[k] for _, k, _ in pairs], [o[t] for _, _, t in pairs]
+        planes = engine.power_spectrum(plist, tlist, window=window)["planes"]  # (horizons, C, 4, n_bins + 1), the mean over the batch
+        b, n = tlist[0].shape[0], plist[0].shape[0]
+        total = planes * float(b) if total is None else total + planes * float(b)
+        samples += b
+    mean = total / float(samples)
+    pooled, per_c = spectrum_diagnostics(mean.mean(dim=1), n), spectrum_diagnostics(mean, n)
+    host = torch.cat([pooled["lsd"][:, None], pooled["lsd_ens_mean"][:, None], per_c["lsd"]], dim=1).cpu().numpy()  # (horizons, 2 + C)
+    out: Dict[str, float] = {}
+    for s, (prefix, _, _) in enumerate(pairs):
+        out[f"{split}/{infix}{prefix}/lsd"], out[f"{split}/{infix}{prefix}/lsd_ens_mean"] = float(host[s, 0]), float(host[s, 1])
+        for j in range(host.shape[1] - 2):
+            out[f"{split}/{infix}{prefix}/c{j}/lsd"] = float(host[s, 2 + j])
+    out[f"{split}/{infix}avg/lsd"], out[f"{split}/{infix}avg/lsd_ens_mean"] = float(host[:, 0].mean()), float(host[:, 1].mean())
     return out
 
 

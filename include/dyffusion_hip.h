@@ -421,6 +421,46 @@ dyf_status dyf_energy_score(dyf_engine* engine, int32_t n_segments, const float*
                             int32_t n_members, int64_t n_points, int64_t member_stride, int64_t n_outer, int32_t n_groups,
                             int64_t n_inner, double* out_dev, double* member_out_dev, double* pair_out_dev, double* accum_dev,
                             void* stream);
+/* Radially binned power spectra of an ensemble forecast per (segment, CHANNEL): at which spatial scales the members are as sharp as
+ * the truth, where the ensemble mean blurs, and where the spread matches the error of the mean.  Segments, member_stride and the two
+ * host arrays of device pointers as in dyf_trajectory_metrics; a segment's members are (batch, channels, height, width) fp32 fields,
+ * member m at preds_dev[s] + m * member_stride (member_stride >= batch * channels * height * width), its target alike at
+ * targets_dev[s].  Per (b, c), members x_0 .. x_{N-1}, target y:
+ *   xbar = (float)((sum_m (double)x_m, member order) / N)      a_m = x_m - xbar      e = xbar - y      (fp32, BEFORE the transform)
+ * and Z = F(z) is the 2-D DFT of each of the N + 3 real fields a_0 .. a_{N-1}, xbar, y, e; with window = 1 every field is first
+ * multiplied by the separable Hann taper (float)w_H[h] * (float)w_W[w] (one fp32 product), w_n[i] = (1 - cos(2 pi i / n)) / 2.
+ * Nothing of the form sum |X_m|^2 - N |Xbar|^2 appears: close members do not cancel.  Four planes, each normalised by 1 / (H W)^2 so
+ * that the sum of a plane over all coefficients is mean(z^2) (Parseval), each the mean over b:
+ *   spread (plane 0)  (1 / N) sum_m |A_m|^2      mean (plane 1)  |Xbar|^2      target (plane 2)  |Y|^2      error (plane 3)  |E|^2
+ * (the host derives members = spread + mean = mean_m |X_m|^2, exact because sum_m a_m = 0, and spread_fair = spread N / (N - 1)).
+ *   Shells: L = max(H, W), n_bins = L / 2 + 1; the coefficient with folded indices kx' = min(kx, W - kx), ky' = min(ky, H - ky) has
+ * kappa = L sqrt((kx' / W)^2 + (ky' / H)^2) and goes to bin round_half_up(kappa), decided on the host in exact integers: bin = k <=>
+ * (2k - 1)^2 H^2 W^2 <= 4 L^2 (kx'^2 H^2 + ky'^2 W^2) < (2k + 1)^2 H^2 W^2.  Bins >= n_bins (the corners) are left out of the shells
+ * and kept in `total`, the sum over ALL coefficients.  out_dev (device, [n_segments][channels][4][n_bins + 1] doubles): bins 0 ..
+ * n_bins - 1, then total; accum_dev (device, the shape of out_dev, or NULL) += out.
+ *   Stated arithmetic: only kx in [0, W / 2] is transformed, a column counted twice unless kx = 0 or 2 kx = W.  Row DFT along w: an
+ * fp32 fmaf chain in w order against twiddles (float)cos / (float)sin(2 pi j / W) (float64 on the host, rounded once).  Column DFT
+ * along h on v_mfma_f32_16x16x4_f32 (exact fp32): per output four fmaf chains in h order (cos Tr, sin Ti, cos Ti, -sin Tr), joined
+ * by one fp32 addition each for the real and the imaginary part.  |Z|^2 = zr^2 + zi^2 and every sum from there on in float64: per
+ * coefficient over the members in member order; per workgroup (b, c, tile of 16 kx columns) and shell in (ky, kx) order; per
+ * (segment, c) over the workgroups in (b, tile) order; then one division by B (H W)^2 (spread: B (H W)^2 N); total = the sum of
+ * the n_bins + 1 joined bins (the corners last) in bin order.
+ *   Three launches on `stream`, no atomics, nothing exchanged between workgroups inside a launch: identical calls give identical
+ * bits, and a segment's values depend on its own data, n_members and the geometry alone.  Engine-owned workspace, grown on demand:
+ * xbar (n_segments B C H W floats), 4 x 16 ceil16(H) x 16 doubles of coefficient planes and 4 (n_bins + 1) doubles of shell sums per
+ * workgroup; a call that would need more than DYF_SPECTRUM_MAX_WORKSPACE_DOUBLES is DYF_ERR_UNSUPPORTED, before anything is launched.
+ * The twiddle, taper and shell tables are built on the host and copied to the device on the FIRST call of an engine at a geometry
+ * (H, W) (a synchronous copy; not inside a stream capture) and kept until dyf_destroy; every later call does NOT synchronise.
+ * 2 <= height, width <= DYF_SPECTRUM_MAX_DIM (DYF_ERR_UNSUPPORTED beyond; the transform's LDS, 128 ceil4(H) + 8 (H + W) + 8192 bytes,
+ * fits the 160 KB of a compute unit up to there), n_members in [1, DYF_SPECTRUM_MAX_MEMBERS] (DYF_ERR_UNSUPPORTED beyond),
+ * n_segments in [1, 65535], window 0 or 1.  The kernels read fp32 only: both builds of the library give the same bits.
+ * (Additive: no ABI change.) */
+#define DYF_SPECTRUM_MAX_DIM 1024
+#define DYF_SPECTRUM_MAX_MEMBERS 256
+#define DYF_SPECTRUM_MAX_WORKSPACE_DOUBLES 134217728 /* 2^27: 1 GiB */
+dyf_status dyf_power_spectrum(dyf_engine* engine, int32_t n_segments, const float* const* preds_dev, const float* const* targets_dev,
+                              int32_t n_members, int64_t member_stride, int32_t batch, int32_t channels, int32_t height, int32_t width,
+                              int32_t window, double* out_dev, double* accum_dev, void* stream);
 /* Copy one (NB,C,H,W) field of the sampler's state after the most recent dyf_sample call: what sample_loop returns
  * beside the intermediates (dyffusion.py:424-426): (x0_hat, ., x_s), or (x_s, ., x_interpolated_s_next) when the sampling
  * schedule stops before T-1. */
